@@ -5,7 +5,7 @@
 // (call order and arena handling of example/main.cpp:274-328; the gravity/damping loop runs on the host between
 // collide() and read_cached_impulses()).  tests/callsite/Makefile links this file
 //   (a) against the reference's own nudge.cpp                    -> oracle/_ref/replay_ref   (the checker)
-//   (b) against nudge_amd/compat/nudge_compat.cpp + libnudge_hip -> nudge_amd/compat/_build/replay_hip
+//   (b) against nudge_amd/compat/nudge_compat.cpp + libnudge_hip -> oracle/_ref/compat/replay_hip
 // and tests/test_gpu_callsite.py requires the two binaries to produce bit-identical worlds.
 //
 // usage: replay <scene.bin> <out.bin> <steps> [mode]

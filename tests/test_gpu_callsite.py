@@ -5,7 +5,7 @@ linked against the GPU backend (nudge_amd/compat/nudge_compat.cpp over the C ABI
     variant, the checker) and against the drop-in; both must leave bit-identical worlds;
   * the reference's OWN test program (tests/main.cpp: 6 known-answer / property tests of collide) runs unmodified
     on the drop-in.
-The binaries are built where the reference's header exists (`make -C nudge_amd/compat`, `make -C oracle`) and travel
+The binaries are built where the reference's header exists (`make -C oracle`, `make -C oracle compat`) and travel
 with the repository; the tests fail, not skip, when a GPU is present and they are missing.
 """
 import os
@@ -49,7 +49,7 @@ def _build(name):
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["pile256", "pile_mixed", "mixed20", "stacks", "pit6", "compound", "example"])
 def test_same_call_site_two_backends_bit_identical(name, tmp_path):
-    assert os.path.exists(CU.REPLAY_HIP), "nudge_amd/compat/_build/replay_hip missing: make -C nudge_amd/compat"
+    assert os.path.exists(CU.REPLAY_HIP), "oracle/_ref/compat/replay_hip missing: make -C oracle compat"
     scene, steps = _build(name)
     nb = CU.write_scene(str(tmp_path / "s.bin"), scene)
     CU.run_replay(CU.REPLAY_HIP, str(tmp_path / "s.bin"), str(tmp_path / "hip.bin"), steps)
@@ -77,7 +77,7 @@ def test_unusual_call_patterns_two_backends_bit_identical(name, mode, tmp_path):
     setup_contact_constraints, nudge.cpp:4563-4632, must still reach momentum -- and stay in the caller's host arrays), reading
     momentum between setup and the first apply_impulses, and user impulses between two apply_impulses calls (the custom-constraint
     hook, example/main.cpp:314-317).  Same source file, reference vs GPU backend, bit-identical worlds and checksums."""
-    assert os.path.exists(CU.REPLAY_HIP), "nudge_amd/compat/_build/replay_hip missing: make -C nudge_amd/compat"
+    assert os.path.exists(CU.REPLAY_HIP), "oracle/_ref/compat/replay_hip missing: make -C oracle compat"
     assert os.path.exists(CU.REPLAY_REF), "oracle/_ref/replay_ref missing: make -C oracle"
     scene, steps = _build(name)
     steps = min(steps, 110)
@@ -99,7 +99,7 @@ def test_custom_contacts_appended_after_collide_two_backends_bit_identical(name,
     a floor at y = 3 under the first dynamic bodies and a sideways push, with tags no collider pair produces -- and bumps contacts.count.  The
     reference sorts them in with everybody else (nudge.cpp:4027-4044); the drop-in uploads them, nh_append_contacts merges them into the
     device's tag order and counts the per-body bookkeeping again.  Same source file, two backends, bit-identical worlds."""
-    assert os.path.exists(CU.REPLAY_HIP), "nudge_amd/compat/_build/replay_hip missing: make -C nudge_amd/compat"
+    assert os.path.exists(CU.REPLAY_HIP), "oracle/_ref/compat/replay_hip missing: make -C oracle compat"
     assert os.path.exists(CU.REPLAY_REF), "oracle/_ref/replay_ref missing: make -C oracle"
     scene, _ = _build(name)
     nb = CU.write_scene(str(tmp_path / "s.bin"), scene)
@@ -129,7 +129,7 @@ def test_two_worlds_on_two_threads_are_independent(tmp_path):
 
 @pytest.mark.gpu
 def test_reference_own_test_program_passes_on_the_gpu_backend():
-    assert os.path.exists(CU.REF_TESTS_HIP), "nudge_amd/compat/_build/ref_tests_hip missing: make -C nudge_amd/compat"
+    assert os.path.exists(CU.REF_TESTS_HIP), "oracle/_ref/compat/ref_tests_hip missing: make -C oracle compat"
     r = subprocess.run([CU.REF_TESTS_HIP], capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert "All tests passed." in r.stdout
