@@ -79,6 +79,8 @@
  *      exported the views: nh_set_option(ctx, "sync_exports_views", 1) restores that contract at its old price; INTEGRATION.md.)  Any entry point outside the sample's
  *      call order between nh_collide and nh_apply_impulses turns a still step into a full one first, so everything it observes is what a full step
  *      produces.  nh_Counts.still_steps / still_replays count them.
+ *      The scene queries (nh_query_build, nh_raycast) are not entry points of the step in this sense: they neither export nor settle nor turn a still step into a
+ *      full one, and they do not count -- see "scene queries" below.
  *
  * Threading: one context = one HIP stream = one world at a time; no global mutable state.
  */
@@ -346,6 +348,34 @@ int nh_step(nh_context* ctx, const nh_StepArgs* args, uint32_t steps);
 typedef struct nh_StreamInfo { uint32_t slot; uint32_t valid; uint64_t step; uint64_t frames, dropped; } nh_StreamInfo;
 int nh_stream_state(nh_context* ctx, const nh_BodyData* bodies, uint32_t count, void* host_ring, uint32_t slots, uint32_t every);
 int nh_stream_latest(nh_context* ctx, nh_StreamInfo* out);
+
+/* ---- scene queries: ray casts against the device-resident world ------------------------------------------------------------------------------------------------
+   nh_query_build snapshots the world transforms and AABBs of ALL box and sphere colliders -- those of sleeping bodies and of body 0 (the static world) included -- and
+   builds a bounding-volume hierarchy over them (a linear BVH: Morton keys, a radix tree, bottom-up boxes) into buffers the library owns: they grow with the collider
+   count (~250 B per collider) and are freed by nh_destroy.  nh_raycast answers `count` rays against the LAST build: the hierarchy does not follow the bodies, so
+   rebuild after they have moved (after nh_step / nh_advance) before casting against the new positions.  All pointers are DEVICE memory; both calls only enqueue work
+   on the context's stream, like every other entry point (read the hits after nh_synchronize or a stream / event wait of your own).
+   Semantics (nudge_amd/csrc/nh_query.h):
+     - closest hit = the smallest t with 0 <= t <= max_t, over the colliders not belonging to `ignore_body` (0xffffffff: none is ignored); ties are broken by
+       (shape, collider index) ascending, so the answer does not depend on the tree -- a brute force over all colliders gives the same bits;
+     - `direction` need not be unit length: t is in units of it;
+     - an origin inside a collider hits it at t = 0 with normal = -d / |d|;
+     - a miss writes shape = NH_SHAPE_NONE, t = max_t, normal = 0 and body = collider = tag = 0xffffffff;
+     - NH_RAY_ANY_HIT may stop at the first hit it finds (shadow / visibility rays): hit or miss agrees with the closest-hit answer and a reported hit is a real one
+       with t <= max_t, but which hit is unspecified;
+     - a ray with a non-finite origin or direction cannot be refused by the return code of an asynchronous call: its record is written as a miss with t = NaN.
+   nh_raycast returns NH_ERR_INVALID before any nh_query_build and for null or not 16-byte aligned `rays` / `hits`; count = 0 is a no-op that returns NH_OK.
+   QUERIES ARE OBSERVERS (note 9): neither call exports a view, settles deferred gravity, turns a still step into a full one or touches nh_Counts.  Made between any two
+   entry points, or between two nh_step calls, they leave every later step bit-identical, with the same still_steps / still_replays / ahead_steps / pair_steps /
+   asleep_steps.  They read bodies->transforms as the stream has them at that point: under NH_FLAG_FUSED_STEP the fused solver advances part of the bodies inside
+   nh_apply_impulses, so a build between nh_apply_impulses and nh_advance sees a world half advanced -- build after nh_advance (or nh_step) for a consistent one.
+   Not built: overlap / sweep queries, queries on a partitioned world (nh_partition_*), an incremental refit across steps. */
+typedef struct nh_Ray { float origin[3]; float max_t; float direction[3]; uint32_t ignore_body; } nh_Ray;                                            /* 32 B */
+typedef struct nh_RayHit { float t; float normal[3]; uint32_t body; uint32_t collider; uint32_t shape; uint32_t tag; } nh_RayHit;                     /* 32 B */
+enum { NH_SHAPE_BOX = 0u, NH_SHAPE_SPHERE = 1u, NH_SHAPE_NONE = 0xffffffffu };    /* nh_RayHit.shape; NONE = miss */
+enum { NH_RAY_ANY_HIT = 1u };
+int nh_query_build(nh_context* ctx, const nh_BodyData* bodies, const nh_ColliderData* colliders);
+int nh_raycast(nh_context* ctx, const nh_Ray* rays, uint32_t count, nh_RayHit* hits, uint32_t flags);
 
 /* ---- multi-GPU: one x-slab of a world per context ------------------------------------------------------------------------------------
    The world is cut into slabs along x, one rank (process, GPU, nh_context) per slab [lo, hi).  A rank's arrays hold

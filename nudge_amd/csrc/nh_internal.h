@@ -489,8 +489,10 @@ struct nh_context {
 	nh_AsleepState asleep;
 	uint32_t first_ghost;          // nh_set_first_ghost_body: bodies >= first_ghost are ghosts of a partitioned world (0 = no ownership rule)
 	nh_StateStream stream_state;
+	struct nh_QueryState* query;   // scene queries (nh_query.hip): the hierarchy of the last nh_query_build; nullptr until the first
 };
 int nh_stream_after_advance(nh_context* ctx);          // nh_advance -> state streaming
+void nh_query_free(nh_context* ctx);                   // nh_destroy -> the scene query's buffers (nh_query.hip)
 
 // Runs work that an earlier call deferred; every entry point that reads or writes momentum / impulses calls it first.
 // `in_sequence`: the caller is the next call of the sample's step (gravity, read, setup, apply): a still step stays speculative across it; every other

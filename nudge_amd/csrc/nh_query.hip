@@ -1,0 +1,353 @@
+// nh_query.hip -- scene queries against the device-resident world: nh_query_build (a linear BVH over every box and sphere collider, built from
+// the current transforms) and nh_raycast (batched closest-hit / any-hit ray casts against the last build).  include/nudge_hip.h, "scene queries".
+//
+// Build (one launch each, plus the library's radix sort):
+//   k_q_xform   one lane per collider (boxes, then spheres): world pose (k_xform's arithmetic, nh_query.h), world AABB, the record the ray test
+//               reads; the bounds of the collider positions by a wave reduction and one atomic per wave
+//   k_q_keys    48-bit Morton key of each position in the frame of those bounds (nh_morton_scale / nh_morton_of), value = collider index
+//   nh_sort_u64_u32  stable: equal keys keep collider order, which the tree's key comparison extends by the sorted index (Karras 2012, 4)
+//   k_q_tree    one lane per internal node: range and split from common prefixes, children and parents; per split, the node that starts right
+//               of it (the escape links below are read from that table)
+//   k_q_refit   one lane per leaf: escape links of its leaf and of the internal node of the same index, the leaf's box, then upwards with an
+//               arrival counter per internal node -- the second child to arrive merges the two boxes and goes on
+// Node ids: internal nodes 0 .. n-2 (root 0), leaf j (j-th collider in key order) n-1+j; with one collider the root is that leaf.
+// Traversal is stackless: a node that is missed or a leaf that is done continues at its ESCAPE link (the next node in pre-order after its subtree),
+// a hit internal node at its left child.  A private stack array would go to scratch memory.
+#include "nh_internal.h"
+#include "nh_query.h"
+
+#define NH_Q_LEAF 0x80000000u
+#define NH_Q_NONE 0xffffffffu
+#define NH_Q_MAX_COLLIDERS (1u << 30)
+
+// The ray test's record of a collider, by collider index: a = (world position, bits(body)), b = world rotation, c = (half extents | radius, -, -,
+// bits(tag))
+struct nh_QRec { float4 a, b, c; };
+// A node: a = (box min, left child | NH_Q_LEAF + collider), b = (box max, escape link)
+struct nh_QNode { float4 a, b; };
+// words the build's kernels share: collider count (the sort reads it), bounds of the positions (flipped floats)
+struct nh_QCtl { uint32_t count, pad0[3]; uint32_t smin[4]; uint32_t smax[4]; };
+
+struct nh_QueryState {
+	uint32_t capacity;           // colliders the buffers have room for
+	bool built;
+	uint32_t n, nbox;            // of the last build
+	nh_QCtl* ctl;
+	nh_QRec* rec;
+	float4* aabb;                // 2 per collider
+	uint64_t* keys_a; uint64_t* keys_b; uint32_t* idx_a; uint32_t* idx_b; uint32_t* hist;
+	nh_QNode* nodes;             // 2 n - 1
+	uint32_t* parent;            // by node id
+	uint32_t* rchild;            // by internal node
+	uint32_t* last;              // by internal node: last leaf of its range
+	uint32_t* right_at;          // by split position: the right child of the node that splits there
+	uint32_t* arrive;            // by internal node: arrival counter of the refit
+};
+
+// ---- build ----------------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_q_xform(const nh_Transform* __restrict__ body_xf, uint32_t nbodies,
+                                                 const nh_Transform* __restrict__ box_xf, const nh_BoxCollider* __restrict__ box_data, const uint32_t* __restrict__ box_tags, uint32_t nbox,
+                                                 const nh_Transform* __restrict__ sph_xf, const nh_SphereCollider* __restrict__ sph_data, const uint32_t* __restrict__ sph_tags, uint32_t nsph,
+                                                 nh_QRec* __restrict__ rec, float4* __restrict__ aabb, nh_QCtl* __restrict__ ctl) {
+	const uint32_t n = nbox + nsph;
+	if (blockIdx.x == 0 && threadIdx.x == 0) ctl->count = n;
+	uint32_t lmin[3] = { 0xffffffffu, 0xffffffffu, 0xffffffffu }, lmax[3] = { 0u, 0u, 0u };
+	for (uint32_t c = blockIdx.x * blockDim.x + threadIdx.x; c < n; c += gridDim.x * blockDim.x) {
+		const bool is_box = c < nbox;
+		const nh_Transform l = is_box ? box_xf[c] : sph_xf[c - nbox];
+		nh_QPose w;
+		nh_f3 h;
+		if (l.body < nbodies) {
+			const nh_Transform b = body_xf[l.body];
+			w = nh_q_pose(b.position, b.rotation, l.position, l.rotation);
+		} else {
+			// (a collider of a body that does not exist: never hit, never in the bounds)
+			const float q = __uint_as_float(0x7fc00000u);
+			w.p = nh_make3(q, q, q); w.q = { q, q, q, q };
+		}
+		if (is_box) {
+			const nh_BoxCollider bc = box_data[c];
+			h = nh_make3(bc.size[0], bc.size[1], bc.size[2]);
+		} else {
+			const float r = sph_data[c - nbox].radius;
+			h = nh_make3(r, r, r);
+		}
+		const nh_f3 e = is_box ? nh_q_box_extent(w.q, h) : h;
+		const uint32_t tag = is_box ? box_tags[c] : sph_tags[c - nbox];
+		nh_QRec r;
+		r.a = make_float4(w.p.x, w.p.y, w.p.z, __uint_as_float(l.body));
+		r.b = make_float4(w.q.x, w.q.y, w.q.z, w.q.s);
+		r.c = make_float4(h.x, h.y, h.z, __uint_as_float(tag));
+		rec[c] = r;
+		aabb[2u * c] = make_float4(w.p.x - e.x, w.p.y - e.y, w.p.z - e.z, 0.0f);
+		aabb[2u * c + 1u] = make_float4(w.p.x + e.x, w.p.y + e.y, w.p.z + e.z, 0.0f);
+		if (w.p.x == w.p.x && w.p.y == w.p.y && w.p.z == w.p.z) {
+			uint32_t f;
+			f = nh_float_flip(w.p.x); lmin[0] = min(lmin[0], f); lmax[0] = max(lmax[0], f);
+			f = nh_float_flip(w.p.y); lmin[1] = min(lmin[1], f); lmax[1] = max(lmax[1], f);
+			f = nh_float_flip(w.p.z); lmin[2] = min(lmin[2], f); lmax[2] = max(lmax[2], f);
+		}
+	}
+	for (int k = 0; k < 3; ++k) {
+		for (int d = 32; d >= 1; d >>= 1) {
+			lmin[k] = min(lmin[k], (uint32_t)__shfl_xor((int)lmin[k], d));
+			lmax[k] = max(lmax[k], (uint32_t)__shfl_xor((int)lmax[k], d));
+		}
+	}
+	if (nh_lane() == 0 && lmin[0] <= lmax[0]) {
+		for (int k = 0; k < 3; ++k) { atomicMin(&ctl->smin[k], lmin[k]); atomicMax(&ctl->smax[k], lmax[k]); }
+	}
+}
+
+__global__ __launch_bounds__(256) void k_q_keys(const nh_QRec* __restrict__ rec, const nh_QCtl* __restrict__ ctl, uint32_t n,
+                                                uint64_t* __restrict__ keys, uint32_t* __restrict__ idx) {
+	const nh_f3 smin = nh_make3(nh_float_unflip(ctl->smin[0]), nh_float_unflip(ctl->smin[1]), nh_float_unflip(ctl->smin[2]));
+	const nh_f3 smax = nh_make3(nh_float_unflip(ctl->smax[0]), nh_float_unflip(ctl->smax[1]), nh_float_unflip(ctl->smax[2]));
+	const float scale = nh_morton_scale(smin, smax);
+	const nh_f3 smin_scaled = smin * scale;
+	for (uint32_t c = blockIdx.x * blockDim.x + threadIdx.x; c < n; c += gridDim.x * blockDim.x) {
+		const float4 a = rec[c].a;
+		keys[c] = nh_morton_of(nh_make3(a.x, a.y, a.z), scale, smin_scaled);
+		idx[c] = c;
+	}
+}
+
+// Karras 2012: length of the common prefix of the keys at sorted positions i and j, extended by the positions themselves on equal keys; -1 outside
+__device__ __forceinline__ int nh_q_delta(const uint64_t* __restrict__ keys, uint32_t n, int64_t i, int64_t j) {
+	if (j < 0 || j >= (int64_t)n) return -1;
+	const uint64_t a = keys[i], b = keys[j];
+	if (a == b) return 64 + __clz((uint32_t)i ^ (uint32_t)j);
+	return __clzll(a ^ b);
+}
+
+__global__ __launch_bounds__(256) void k_q_tree(const uint64_t* __restrict__ keys, uint32_t n, nh_QNode* __restrict__ nodes, uint32_t* __restrict__ parent,
+                                                uint32_t* __restrict__ rchild, uint32_t* __restrict__ last, uint32_t* __restrict__ right_at,
+                                                uint32_t* __restrict__ arrive, nh_QCtl* __restrict__ ctl) {
+	if (blockIdx.x == 0 && threadIdx.x == 0) {
+		parent[0] = NH_Q_NONE;
+		// the bounds the next build accumulates into (k_q_keys of this one has read them)
+		for (int k = 0; k < 3; ++k) { ctl->smin[k] = 0xffffffffu; ctl->smax[k] = 0u; }
+	}
+	for (uint32_t u = blockIdx.x * blockDim.x + threadIdx.x; u + 1u < n; u += gridDim.x * blockDim.x) {
+		const int64_t i = u;
+		const int d = nh_q_delta(keys, n, i, i + 1) > nh_q_delta(keys, n, i, i - 1) ? 1 : -1;
+		const int dmin = nh_q_delta(keys, n, i, i - d);
+		int64_t lmax = 2;
+		while (nh_q_delta(keys, n, i, i + lmax * d) > dmin) lmax *= 2;
+		int64_t l = 0;
+		for (int64_t t = lmax / 2; t >= 1; t /= 2)
+			if (nh_q_delta(keys, n, i, i + (l + t) * d) > dmin) l += t;
+		const int64_t j = i + l * d;
+		const int dnode = nh_q_delta(keys, n, i, j);
+		int64_t s = 0, t = l;
+		do {
+			t = (t + 1) / 2;
+			if (nh_q_delta(keys, n, i, i + (s + t) * d) > dnode) s += t;
+		} while (t > 1);
+		const int64_t gamma = i + s * d + (d < 0 ? -1 : 0);
+		const int64_t first = i < j ? i : j, end = i < j ? j : i;
+		const uint32_t left = first == gamma ? (uint32_t)(n - 1u + gamma) : (uint32_t)gamma;
+		const uint32_t right = end == gamma + 1 ? (uint32_t)(n - 1u + gamma + 1) : (uint32_t)(gamma + 1);
+		nodes[u].a.w = __uint_as_float(left);
+		rchild[u] = right;
+		last[u] = (uint32_t)end;
+		right_at[gamma] = right;
+		parent[left] = u;
+		parent[right] = u;
+		arrive[u] = 0u;
+	}
+}
+
+// conservative box of a leaf: a relative pad of 2^-18 of its largest coordinate, so that no rounding of the ray's slab test can cut off a collider the
+// exact test hits (the ray side adds the same of its origin, k_q_raycast)
+__device__ __forceinline__ float nh_q_pad(float4 mn, float4 mx) {
+	const float m = fmaxf(fmaxf(fmaxf(fabsf(mn.x), fabsf(mn.y)), fmaxf(fabsf(mn.z), fabsf(mx.x))), fmaxf(fabsf(mx.y), fabsf(mx.z)));
+	return m * 3.814697265625e-06f + 1e-30f;
+}
+
+__global__ __launch_bounds__(256) void k_q_refit(const uint32_t* __restrict__ idx, const float4* __restrict__ aabb, uint32_t n, nh_QNode* nodes,
+                                                 const uint32_t* __restrict__ parent, const uint32_t* __restrict__ rchild, const uint32_t* __restrict__ last,
+                                                 const uint32_t* __restrict__ right_at, uint32_t* arrive) {
+	for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += gridDim.x * blockDim.x) {
+		// escape links: the subtree of a node ends at the last leaf of its range; the next node in pre-order is the right child of the split there
+		if (j + 1u < n) {
+			const uint32_t e = last[j];
+			nodes[j].b.w = __uint_as_float(e + 1u == n ? NH_Q_NONE : right_at[e]);
+		}
+		const uint32_t c = idx[j];
+		float4 mn = aabb[2u * c], mx = aabb[2u * c + 1u];
+		const float pad = nh_q_pad(mn, mx);
+		mn = make_float4(mn.x - pad, mn.y - pad, mn.z - pad, __uint_as_float(NH_Q_LEAF | c));
+		mx = make_float4(mx.x + pad, mx.y + pad, mx.z + pad, __uint_as_float(j + 1u == n ? NH_Q_NONE : right_at[j]));
+		uint32_t me = n - 1u + j;
+		nh_QNode leaf; leaf.a = mn; leaf.b = mx;
+		nodes[me] = leaf;
+		// bottom-up: the second child to arrive at a node has both boxes.  Per-XCD L2s are not coherent: the box is released at agent scope before the
+		// arrival, and the second arriver acquires at agent scope before it reads its sibling's (MI355X_MICROARCH, inter-workgroup visibility)
+		uint32_t id = parent[me];
+		while (id != NH_Q_NONE) {
+			__builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+			const uint32_t old = __hip_atomic_fetch_add(&arrive[id], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+			if (old == 0u) break;
+			__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+			const uint32_t l = __float_as_uint(nodes[id].a.w);
+			const uint32_t other = l == me ? rchild[id] : l;
+			const float4 omn = nodes[other].a, omx = nodes[other].b;
+			mn = make_float4(fminf(mn.x, omn.x), fminf(mn.y, omn.y), fminf(mn.z, omn.z), 0.0f);
+			mx = make_float4(fmaxf(mx.x, omx.x), fmaxf(mx.y, omx.y), fmaxf(mx.z, omx.z), 0.0f);
+			float* a = reinterpret_cast<float*>(&nodes[id].a);
+			float* b = reinterpret_cast<float*>(&nodes[id].b);
+			a[0] = mn.x; a[1] = mn.y; a[2] = mn.z;
+			b[0] = mx.x; b[1] = mx.y; b[2] = mx.z;
+			me = id;
+			id = parent[id];
+		}
+	}
+}
+
+// ---- ray cast -------------------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool nh_q_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
+
+__global__ __launch_bounds__(256) void k_q_raycast(const nh_Ray* __restrict__ rays, uint32_t count, nh_RayHit* __restrict__ hits,
+                                                   const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox, uint32_t any_hit) {
+	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
+		const float4* rp = reinterpret_cast<const float4*>(rays + i);
+		const float4 r0 = rp[0], r1 = rp[1];
+		const nh_f3 o = nh_make3(r0.x, r0.y, r0.z), d = nh_make3(r1.x, r1.y, r1.z);
+		const float max_t = r0.w;
+		const uint32_t ignore = __float_as_uint(r1.w);
+		const bool ok = nh_q_finite(o.x) && nh_q_finite(o.y) && nh_q_finite(o.z) && nh_q_finite(d.x) && nh_q_finite(d.y) && nh_q_finite(d.z);
+		float bt = max_t;
+		uint32_t bc = NH_Q_NONE;
+		nh_f3 bn = nh_make3(0.0f, 0.0f, 0.0f);
+		const nh_f3 inv = nh_make3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+		const float s = fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fabsf(o.z)) * 3.814697265625e-06f;
+		uint32_t node = ok && n ? 0u : NH_Q_NONE;
+		while (node != NH_Q_NONE) {
+			const float4 na = nodes[node].a, nb = nodes[node].b;
+			const float ax = ((na.x - s) - o.x) * inv.x, bx = ((nb.x + s) - o.x) * inv.x;
+			const float ay = ((na.y - s) - o.y) * inv.y, by = ((nb.y + s) - o.y) * inv.y;
+			const float az = ((na.z - s) - o.z) * inv.z, bz = ((nb.z + s) - o.z) * inv.z;
+			const float t0 = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fminf(az, bz));
+			const float t1 = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fmaxf(az, bz));
+			const bool enter = t0 <= t1 && t1 >= 0.0f && t0 <= bt;
+			const uint32_t left = __float_as_uint(na.w);
+			const uint32_t rope = __float_as_uint(nb.w);
+			if (!enter) { node = rope; continue; }
+			if (!(left & NH_Q_LEAF)) { node = left; continue; }
+			node = rope;
+			const uint32_t c = left & ~NH_Q_LEAF;
+			const nh_QRec q = rec[c];
+			if (__float_as_uint(q.a.w) == ignore) continue;
+			const nh_f3 p = nh_make3(q.a.x, q.a.y, q.a.z);
+			const nh_QHit h = c < nbox ? nh_q_ray_box(o, d, p, nh_quat{ q.b.x, q.b.y, q.b.z, q.b.w }, nh_make3(q.c.x, q.c.y, q.c.z))
+			                           : nh_q_ray_sphere(o, d, p, q.c.x);
+			if (h.hit && nh_q_better(h.t, c, max_t, bt, bc)) {
+				bt = h.t; bc = c; bn = h.n;
+				if (any_hit) break;
+			}
+		}
+		nh_RayHit out;
+		if (bc == NH_Q_NONE) {
+			out.t = ok ? max_t : __uint_as_float(0x7fc00000u);
+			out.normal[0] = out.normal[1] = out.normal[2] = 0.0f;
+			out.body = out.collider = out.tag = NH_Q_NONE;
+			out.shape = NH_SHAPE_NONE;
+		} else {
+			const nh_QRec q = rec[bc];
+			out.t = bt; out.normal[0] = bn.x; out.normal[1] = bn.y; out.normal[2] = bn.z;
+			out.body = __float_as_uint(q.a.w);
+			out.collider = bc < nbox ? bc : bc - nbox;
+			out.shape = bc < nbox ? NH_SHAPE_BOX : NH_SHAPE_SPHERE;
+			out.tag = __float_as_uint(q.c.w);
+		}
+		float4* hp = reinterpret_cast<float4*>(hits + i);
+		hp[0] = make_float4(out.t, out.normal[0], out.normal[1], out.normal[2]);
+		hp[1] = make_float4(__uint_as_float(out.body), __uint_as_float(out.collider), __uint_as_float(out.shape), __uint_as_float(out.tag));
+	}
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------------------------------
+void nh_query_free(nh_context* ctx) {
+	nh_QueryState* q = ctx->query;
+	if (!q) return;
+	void* bufs[] = { q->ctl, q->rec, q->aabb, q->keys_a, q->keys_b, q->idx_a, q->idx_b, q->hist, q->nodes, q->parent, q->rchild, q->last, q->right_at, q->arrive };
+	for (void* b : bufs) if (b) hipFree(b);
+	delete q;
+	ctx->query = nullptr;
+}
+
+// (buffers by collider count; a growth waits for the stream first: the last build / cast may still read the old ones)
+static int nh_query_reserve(nh_context* ctx, uint32_t C) {
+	if (!ctx->query) ctx->query = new nh_QueryState();
+	nh_QueryState* q = ctx->query;
+	if (!q->ctl) {
+		NH_HIP_CHECK(ctx, hipMalloc((void**)&q->ctl, sizeof(nh_QCtl)));
+		NH_HIP_CHECK(ctx, hipMemsetAsync(q->ctl, 0, sizeof(nh_QCtl), ctx->stream));
+		NH_HIP_CHECK(ctx, hipMemsetAsync(q->ctl->smin, 0xff, sizeof(q->ctl->smin), ctx->stream));
+		NH_HIP_CHECK(ctx, hipMalloc((void**)&q->hist, sizeof(uint32_t) * (256u * NH_SORT_GRID + 512u)));
+	}
+	if (C <= q->capacity) return NH_OK;
+	const uint32_t cap = C + C / 8u + 64u;
+	NH_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+	void* old[] = { q->rec, q->aabb, q->keys_a, q->keys_b, q->idx_a, q->idx_b, q->nodes, q->parent, q->rchild, q->last, q->right_at, q->arrive };
+	for (void* b : old) if (b) hipFree(b);
+	q->rec = nullptr; q->aabb = nullptr; q->keys_a = q->keys_b = nullptr; q->idx_a = q->idx_b = nullptr; q->nodes = nullptr;
+	q->parent = q->rchild = q->last = q->right_at = q->arrive = nullptr;
+	q->capacity = 0; q->built = false;
+	NH_HIP_CHECK(ctx, hipMalloc((void**)&q->rec, sizeof(nh_QRec) * (size_t)cap));
+	NH_HIP_CHECK(ctx, hipMalloc((void**)&q->aabb, 2u * sizeof(float4) * (size_t)cap));
+	NH_HIP_CHECK(ctx, hipMalloc((void**)&q->keys_a, sizeof(uint64_t) * (size_t)cap));
+	NH_HIP_CHECK(ctx, hipMalloc((void**)&q->keys_b, sizeof(uint64_t) * (size_t)cap));
+	NH_HIP_CHECK(ctx, hipMalloc((void**)&q->idx_a, sizeof(uint32_t) * (size_t)cap));
+	NH_HIP_CHECK(ctx, hipMalloc((void**)&q->idx_b, sizeof(uint32_t) * (size_t)cap));
+	NH_HIP_CHECK(ctx, hipMalloc((void**)&q->nodes, 2u * sizeof(nh_QNode) * (size_t)cap));
+	NH_HIP_CHECK(ctx, hipMalloc((void**)&q->parent, 2u * sizeof(uint32_t) * (size_t)cap));
+	NH_HIP_CHECK(ctx, hipMalloc((void**)&q->rchild, sizeof(uint32_t) * (size_t)cap));
+	NH_HIP_CHECK(ctx, hipMalloc((void**)&q->last, sizeof(uint32_t) * (size_t)cap));
+	NH_HIP_CHECK(ctx, hipMalloc((void**)&q->right_at, sizeof(uint32_t) * (size_t)cap));
+	NH_HIP_CHECK(ctx, hipMalloc((void**)&q->arrive, sizeof(uint32_t) * (size_t)cap));
+	q->capacity = cap;
+	return NH_OK;
+}
+
+// Observer: no nh_flush_pending, no view export, no counter -- only launches on the stream and buffers of its own (header, "scene queries").
+extern "C" int nh_query_build(nh_context* ctx, const nh_BodyData* bodies, const nh_ColliderData* colliders) {
+	if (!ctx || !bodies || !colliders) return NH_ERR_INVALID;
+	const uint32_t nbox = colliders->boxes.count, nsph = colliders->spheres.count;
+	const uint64_t C64 = (uint64_t)nbox + nsph;
+	if (C64 >= NH_Q_MAX_COLLIDERS) return NH_ERR_INVALID;
+	const uint32_t C = (uint32_t)C64;
+	if (C && (!bodies->transforms && bodies->count)) return NH_ERR_INVALID;
+	if (nbox && (!colliders->boxes.tags || !colliders->boxes.data || !colliders->boxes.transforms)) return NH_ERR_INVALID;
+	if (nsph && (!colliders->spheres.tags || !colliders->spheres.data || !colliders->spheres.transforms)) return NH_ERR_INVALID;
+	NH_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+	{ const int rc = nh_query_reserve(ctx, C); if (rc) return rc; }
+	nh_QueryState* q = ctx->query;
+	if (C) {
+		NH_LAUNCH(ctx, "q_xform", k_q_xform, nh_grid_for(C, 256, 4096), 256, bodies->transforms, bodies->count,
+		          colliders->boxes.transforms, colliders->boxes.data, colliders->boxes.tags, nbox,
+		          colliders->spheres.transforms, colliders->spheres.data, colliders->spheres.tags, nsph, q->rec, q->aabb, q->ctl);
+		NH_LAUNCH(ctx, "q_keys", k_q_keys, nh_grid_for(C, 256, 4096), 256, q->rec, q->ctl, C, q->keys_a, q->idx_a);
+		// 48-bit keys: six passes, the result back in the *_a buffers
+		const int in_b = nh_sort_u64_u32(ctx, q->keys_a, q->keys_b, q->idx_a, q->idx_b, &q->ctl->count, q->hist, 0, 48);
+		const uint64_t* keys = in_b ? q->keys_b : q->keys_a;
+		const uint32_t* idx = in_b ? q->idx_b : q->idx_a;
+		NH_LAUNCH(ctx, "q_tree", k_q_tree, nh_grid_for(C > 1u ? C - 1u : 1u, 256, 4096), 256, keys, C, q->nodes, q->parent, q->rchild, q->last, q->right_at, q->arrive, q->ctl);
+		NH_LAUNCH(ctx, "q_refit", k_q_refit, nh_grid_for(C, 256, 4096), 256, idx, q->aabb, C, q->nodes, q->parent, q->rchild, q->last, q->right_at, q->arrive);
+	}
+	q->built = true; q->n = C; q->nbox = nbox;
+	return NH_OK;
+}
+
+extern "C" int nh_raycast(nh_context* ctx, const nh_Ray* rays, uint32_t count, nh_RayHit* hits, uint32_t flags) {
+	if (!ctx || !ctx->query || !ctx->query->built) return NH_ERR_INVALID;
+	if (flags & ~(uint32_t)NH_RAY_ANY_HIT) return NH_ERR_INVALID;
+	if (count == 0u) return NH_OK;
+	if (!rays || !hits || (((uintptr_t)rays | (uintptr_t)hits) & 15u)) return NH_ERR_INVALID;      // (records are moved as 16-byte words)
+	NH_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+	nh_QueryState* q = ctx->query;
+	NH_LAUNCH(ctx, "q_raycast", k_q_raycast, nh_grid_for(count, 256, 1u << 20), 256, rays, count, hits, q->nodes, q->rec, q->n, q->nbox,
+	          (flags & NH_RAY_ANY_HIT) ? 1u : 0u);
+	return NH_OK;
+}

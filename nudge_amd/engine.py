@@ -43,6 +43,7 @@ EXPORTS = [
     "nh_partition_top_speed", "nh_partition_set_peer_speeds", "nh_partition_refresh_is_quiet", "nh_partition_mark_ghosts", "nh_partition_pack_deltas", "nh_partition_unpack_deltas",
     "nh_partition_pack_momentum", "nh_partition_unpack_momentum", "nh_partition_exchange_iteration", "nh_partition_unpack_ghosts", "nh_partition_pack_step", "nh_partition_unpack_step", "nh_partition_choose_cut", "nh_partition_set_cut",
     "nh_partition_set_transport", "nh_partition_exchange_step", "nh_partition_step", "nh_partition_transport_check", "nh_partition_transport_result", "nh_set_first_ghost_body",
+    "nh_query_build", "nh_raycast",
 ]
 HALO_RECORD_BYTES = 64
 
@@ -106,6 +107,21 @@ class PartitionConfig(C.Structure):
 class PartitionInfo(C.Structure):
     _fields_ = [("n_owned", C.c_uint32), ("n_bodies", C.c_uint32), ("n_boxes", C.c_uint32), ("n_spheres", C.c_uint32), ("ghost_out", C.c_uint32 * 2), ("ghost_in", C.c_uint32 * 2),
                 ("lo", C.c_double), ("hi", C.c_double), ("migrated_out", C.c_uint64), ("migrated_in", C.c_uint64), ("refreshes", C.c_uint64), ("cut_moves", C.c_uint64), ("quiet_refreshes", C.c_uint64)]
+
+
+class Ray(C.Structure):
+    _fields_ = [("origin", C.c_float * 3), ("max_t", C.c_float), ("direction", C.c_float * 3), ("ignore_body", C.c_uint32)]
+
+
+class RayHit(C.Structure):
+    _fields_ = [("t", C.c_float), ("normal", C.c_float * 3), ("body", C.c_uint32), ("collider", C.c_uint32), ("shape", C.c_uint32), ("tag", C.c_uint32)]
+
+
+# scene queries (include/nudge_hip.h, "scene queries"): nh_RayHit.shape, nh_raycast flags; numpy forms of the two records
+NH_SHAPE_BOX, NH_SHAPE_SPHERE, NH_SHAPE_NONE = 0, 1, 0xFFFFFFFF
+NH_RAY_ANY_HIT = 1
+RAY = np.dtype([("origin", "<f4", 3), ("max_t", "<f4"), ("direction", "<f4", 3), ("ignore_body", "<u4")])
+RAY_HIT = np.dtype([("t", "<f4"), ("normal", "<f4", 3), ("body", "<u4"), ("collider", "<u4"), ("shape", "<u4"), ("tag", "<u4")])
 
 
 class KernelTime(C.Structure):
@@ -191,6 +207,8 @@ def lib():
         L.nh_partition_transport_check.argtypes = [C.c_void_p, C.c_uint32, C.c_int]
         L.nh_partition_transport_result.argtypes = [C.c_void_p]
         L.nh_set_first_ghost_body.argtypes = [C.c_void_p, C.c_uint32]
+        L.nh_query_build.argtypes = [C.c_void_p, C.POINTER(BodyData), C.POINTER(ColliderData)]
+        L.nh_raycast.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
         _LIB = L
     return _LIB
 
@@ -547,6 +565,47 @@ class World:
             return None, stats
         raw = self._stream_ring[info.slot].numpy().tobytes()
         return (int(info.step), np.frombuffer(raw, dtype=S.TRANSFORM, count=self._stream_count).copy()), stats
+
+    # ---- scene queries (include/nudge_hip.h, "scene queries"): observers of the world, they change nothing about stepping ----
+    def query_build(self):
+        """Build the ray-cast hierarchy over every collider from the current transforms (nh_query_build; enqueued, no synchronisation)."""
+        _check(self.L, self.L.nh_query_build(self.ctx, C.byref(self.bodies), C.byref(self.colliders)), "nh_query_build")
+
+    def raycast_records(self, rays, any_hit=False, hits=None):
+        """nh_raycast on records already laid out as nh_Ray: `rays` a contiguous device tensor of count x 32 bytes (any dtype).  Returns the
+        count x 32-byte uint8 device tensor of nh_RayHit records (`hits`, or a new one)."""
+        torch = self.torch
+        n = rays.numel() * rays.element_size() // 32
+        if hits is None:
+            hits = torch.empty((n, 32), dtype=torch.uint8, device=self.dev)
+        _check(self.L, self.L.nh_raycast(self.ctx, C.c_void_p(rays.data_ptr() if n else 0), n, C.c_void_p(hits.data_ptr() if n else 0),
+                                         NH_RAY_ANY_HIT if any_hit else 0), "nh_raycast")
+        return hits
+
+    def raycast(self, origins, directions, max_t=float("inf"), ignore_body=None, any_hit=False, synchronize=False):
+        """Closest-hit (or any-hit) ray casts against the last query_build().  `origins` / `directions`: (n, 3) torch tensors or arrays (uploaded once);
+        `max_t`: a number or n values; `ignore_body`: None, a body index, or n of them.  Returns a dict of device tensors: t (n), normal (n, 3), body,
+        collider, shape, tag (n, int64; 0xffffffff = none) and `raw`, the nh_RayHit records.  Nothing waits for the device unless `synchronize`."""
+        torch = self.torch
+        o = torch.as_tensor(origins, dtype=torch.float32, device=self.dev).reshape(-1, 3)
+        d = torch.as_tensor(directions, dtype=torch.float32, device=self.dev).reshape(-1, 3)
+        n = o.shape[0]
+        if d.shape[0] != n:
+            raise ValueError(f"raycast: {n} origins but {d.shape[0]} directions")
+        rays = torch.empty((n, 8), dtype=torch.float32, device=self.dev)
+        rays[:, 0:3] = o
+        rays[:, 3] = torch.as_tensor(max_t, dtype=torch.float32, device=self.dev)
+        rays[:, 4:7] = d
+        ign = 0xFFFFFFFF if ignore_body is None else ignore_body
+        ign = torch.as_tensor(ign, dtype=torch.int64, device=self.dev)
+        rays.view(torch.int32)[:, 7] = (((ign & 0xFFFFFFFF) ^ 0x80000000) - 0x80000000).to(torch.int32)          # (the uint32 bits, as int32)
+        raw = self.raycast_records(rays, any_hit=any_hit)
+        f = raw.view(torch.float32).reshape(n, 8)
+        u = raw.view(torch.int32).reshape(n, 8).to(torch.int64) & 0xFFFFFFFF
+        out = dict(t=f[:, 0], normal=f[:, 1:4], body=u[:, 4], collider=u[:, 5], shape=u[:, 6], tag=u[:, 7], raw=raw)
+        if synchronize:
+            torch.cuda.current_stream(self.dev).synchronize()
+        return out
 
     # ---- measurement ----
     def enable_timing(self, on=True, only=None):

@@ -1,0 +1,342 @@
+"""Scene queries on the GPU (pytest -m gpu): nh_query_build / nh_raycast (include/nudge_hip.h, "scene queries").
+
+The oracle is a brute force over every collider on the host with the same per-item arithmetic (nudge_amd/csrc/nh_query.h through
+tests/hostquery_util.py): closest hit is defined exactly -- smallest t, ties by (shape, collider index) -- so the tree's answer must equal it bit
+for bit in every field.  Queries are observers: worlds that answer them between every pair of entry points must step exactly like worlds that do not."""
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import hostquery_util as Q                   # noqa: E402
+import parity_util as P                      # noqa: E402
+from nudge_amd import engine as E           # noqa: E402
+from nudge_amd import scenes as S           # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+NONE = 0xFFFFFFFF
+FUSED = E.NH_FLAG_SINGLE_APPLY | E.NH_FLAG_FUSED_STEP
+
+
+def _bounds(rec):
+    p = rec["p"][np.isfinite(rec["p"]).all(axis=1)].astype(np.float64)
+    return p.min(axis=0), p.max(axis=0)
+
+
+def _rays(rng, n, lo, hi, kind, max_t=np.inf):
+    """`kind`: random origins / directions around the scene; axis-aligned (one or two direction components exactly zero); a downward grid."""
+    lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
+    span = np.maximum(hi - lo, 1.0)
+    r = np.zeros(n, dtype=E.RAY)
+    r["max_t"] = max_t
+    r["ignore_body"] = NONE
+    if kind == "random":
+        r["origin"] = rng.uniform(lo - 0.2 * span, hi + 0.2 * span, size=(n, 3))
+        aim = rng.uniform(lo, hi, size=(n, 3))
+        d = aim - r["origin"]
+        r["direction"] = d / np.linalg.norm(d, axis=1, keepdims=True) * rng.uniform(0.25, 4.0, size=(n, 1))
+    elif kind == "axis":
+        r["origin"] = rng.uniform(lo - 0.1 * span, hi + 0.1 * span, size=(n, 3))
+        d = np.zeros((n, 3))
+        ax = rng.integers(0, 3, size=n)
+        d[np.arange(n), ax] = rng.choice([-1.0, 1.0], size=n) * rng.uniform(0.5, 2.0, size=n)
+        two = rng.random(n) < 0.3          # (a third of them with one zero component only)
+        ax2 = (ax + 1) % 3
+        d[two, ax2[two]] = rng.uniform(-1.0, 1.0, size=int(two.sum()))
+        r["direction"] = d
+    else:
+        side = int(np.sqrt(n))
+        gx, gz = np.meshgrid(np.linspace(lo[0], hi[0], side), np.linspace(lo[2], hi[2], n // side + 1))
+        r["origin"][:, 0] = gx.reshape(-1)[:n]
+        r["origin"][:, 1] = hi[1] + 5.0
+        r["origin"][:, 2] = gz.reshape(-1)[:n]
+        r["direction"] = (0.0, -1.0, 0.0)
+    return r
+
+
+def _upload(w, rays):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(rays).view(np.uint8).copy()).to(w.dev)
+
+
+def _cast(w, rays, any_hit=False):
+    raw = w.raycast_records(_upload(w, rays), any_hit=any_hit)
+    return np.frombuffer(raw.cpu().numpy().tobytes(), dtype=E.RAY_HIT).copy()
+
+
+def _same_hits(got, ref, what):
+    assert got.tobytes() == ref.tobytes(), f"{what}: {int((got.view(np.uint8).reshape(-1, 32) != ref.view(np.uint8).reshape(-1, 32)).any(axis=1).sum())} of {len(ref)} hit records differ"
+
+
+def _check_world(w, scene, rng, n, what):
+    w.query_build()
+    rec = Q.records(w.get_bodies()["transforms"], scene, w.nbox, w.nsph)
+    lo, hi = _bounds(rec)
+    hit_share = []
+    for kind in ("random", "axis", "down"):
+        rays = _rays(rng, n, lo, hi, kind)
+        got = _cast(w, rays)
+        ref = Q.raycast(rec, w.nbox, rays)
+        _same_hits(got, ref, f"{what} / {kind}")
+        hit_share.append(float((ref["shape"] != NONE).mean()))
+    return hit_share
+
+
+SMALL = {
+    "pile": lambda: S.pile(256, 64, seed=1),
+    "compound": lambda: S.compound(150, seed=6),
+    "stacks": lambda: S.stacks(64, 3, seed=5),
+    "grid_tiles": lambda: S.grid_tiles(4, side=16, sphere_fraction=0.5, seed=2),
+    "ball_pit": lambda: S.ball_pit(6, 6, 6, seed=4),
+}
+
+
+@pytest.mark.parametrize("name", sorted(SMALL))
+def test_closest_hits_equal_the_brute_force_before_and_after_stepping(name):
+    scene = SMALL[name]()
+    rng = np.random.default_rng(100 + sorted(SMALL).index(name))
+    w = E.World(scene, flags=FUSED)
+    share = _check_world(w, scene, rng, 65536, f"{name} initial")
+    assert max(share) > 0.05, share
+    w.step(50)
+    share = _check_world(w, scene, rng, 65536, f"{name} after 50 steps")
+    assert max(share) > 0.05, share
+    w.close()
+
+
+def test_a_single_collider():
+    scene = S.pile(4, 0, seed=3)
+    w = E.World(scene, flags=FUSED)
+    w.set_counts(len(scene["body_transforms"]), 1, 0)          # the ground slab alone (body 0)
+    rng = np.random.default_rng(1)
+    _check_world(w, scene, rng, 4096, "one collider")
+    rays = _rays(rng, 64, (-1, -12, -1), (1, -10, 1), "down")
+    got = _cast(w, rays)
+    assert (got["shape"] == E.NH_SHAPE_BOX).all() and (got["collider"] == 0).all() and (got["body"] == 0).all()
+    w.close()
+
+
+def test_only_spheres_and_only_boxes():
+    scene = S.pile(300, 300, seed=3)
+    nb = len(scene["body_transforms"])
+    w = E.World(scene, flags=FUSED)
+    rng = np.random.default_rng(2)
+    w.set_counts(nb, 0, 300)
+    _check_world(w, scene, rng, 16384, "spheres only")
+    w.set_counts(nb, 301, 0)
+    _check_world(w, scene, rng, 16384, "boxes only")
+    w.close()
+
+
+def test_four_thousand_boxes_at_one_position():
+    scene = S.pile(4096, 0, seed=3)
+    scene["body_transforms"]["position"][1:] = (0.25, 3.0, -0.5)        # every Morton key equal but the ground's
+    w = E.World(scene, flags=FUSED)
+    rng = np.random.default_rng(3)
+    _check_world(w, scene, rng, 16384, "4096 coincident boxes")
+    rays = _rays(rng, 256, (0.2, 3.0, -0.6), (0.3, 3.1, -0.4), "down")
+    got = _cast(w, rays)
+    assert (got["shape"] == E.NH_SHAPE_BOX).all()
+    w.close()
+
+
+def test_a_scene_spanning_a_thousandth_and_ten_thousand_units():
+    scene = S.pile(2000, 1000, seed=3)
+    rng = np.random.default_rng(4)
+    nb = len(scene["body_transforms"])
+    small = rng.random(nb) < 0.5
+    pos = np.where(small[:, None], rng.uniform(-0.05, 0.05, size=(nb, 3)), rng.uniform(-1e4, 1e4, size=(nb, 3))).astype(np.float32)
+    scene["body_transforms"]["position"][1:] = pos[1:]
+    bsmall = small[scene["box_transforms"]["body"][1:]]
+    scene["box_data"]["size"][1:] = np.where(bsmall[:, None], np.float32(1e-3), np.float32(30.0))
+    scene["sphere_data"]["radius"] = np.where(small[scene["sphere_transforms"]["body"]], np.float32(1e-3), np.float32(25.0))
+    w = E.World(scene, flags=FUSED)
+    _check_world(w, scene, rng, 32768, "1e-3 .. 1e4")
+    # rays at the small cluster from afar and from inside it
+    rec = Q.records(w.get_bodies()["transforms"], scene)
+    for lo, hi in (((-0.05,) * 3, (0.05,) * 3), ((-0.01,) * 3, (0.01,) * 3)):
+        rays = _rays(rng, 16384, lo, hi, "random")
+        _same_hits(_cast(w, rays), Q.raycast(rec, w.nbox, rays), f"small cluster {lo}")
+    w.close()
+
+
+def test_abi_edge_cases():
+    scene = S.pile(64, 16, seed=3)
+    w = E.World(scene, flags=FUSED, capacity=dict(bodies=len(scene["body_transforms"]), boxes=65, spheres=16))
+    L = w.L
+    rays = _rays(np.random.default_rng(5), 1024, (-5, -10, -5), (5, 300, 5), "random")
+    t = _upload(w, rays)
+    import torch
+    hits = torch.zeros((1024, 32), dtype=torch.uint8, device=w.dev)
+    assert L.nh_raycast(w.ctx, C.c_void_p(t.data_ptr()), 1024, C.c_void_p(hits.data_ptr()), 0) == 1          # before any build: NH_ERR_INVALID
+    assert L.nh_raycast(None, C.c_void_p(t.data_ptr()), 1024, C.c_void_p(hits.data_ptr()), 0) == 1
+    w.query_build()
+    assert L.nh_raycast(w.ctx, C.c_void_p(t.data_ptr()), 0, C.c_void_p(hits.data_ptr()), 0) == 0            # count 0: a no-op
+    assert L.nh_raycast(w.ctx, None, 0, None, 0) == 0
+    assert L.nh_raycast(w.ctx, C.c_void_p(t.data_ptr()), 1024, None, 0) == 1                                  # null hits
+    assert L.nh_raycast(w.ctx, None, 1024, C.c_void_p(hits.data_ptr()), 0) == 1
+    assert L.nh_raycast(w.ctx, C.c_void_p(t.data_ptr()), 1024, C.c_void_p(hits.data_ptr()), 2) == 1           # unknown flag
+    assert L.nh_query_build(w.ctx, None, C.byref(w.colliders)) == 1
+    w.torch.cuda.synchronize()
+    assert int(hits.sum()) == 0                                                                               # nothing was written
+    # the world shrinks: the rebuild must not answer with colliders that are gone
+    full = _cast(w, rays)
+    assert (full["collider"][full["shape"] == E.NH_SHAPE_SPHERE] >= 8).any() and (full["collider"][full["shape"] == E.NH_SHAPE_BOX] >= 33).any()
+    w.set_counts(len(scene["body_transforms"]), 33, 8)
+    w.query_build()
+    got = _cast(w, rays)
+    rec = Q.records(w.get_bodies()["transforms"], scene, 33, 8)
+    _same_hits(got, Q.raycast(rec, 33, rays), "after set_counts")
+    assert not ((got["shape"] == E.NH_SHAPE_BOX) & (got["collider"] >= 33)).any()
+    assert not ((got["shape"] == E.NH_SHAPE_SPHERE) & (got["collider"] >= 8)).any()
+    # ... and grows back
+    w.set_counts(len(scene["body_transforms"]), 65, 16)
+    w.query_build()
+    _same_hits(_cast(w, rays), full, "grown back")
+    w.close()
+
+
+@pytest.mark.parametrize("name", ["pile", "grid_tiles"])
+def test_any_hit_agrees_with_closest_hit_about_hit_or_miss(name):
+    scene = SMALL[name]()
+    w = E.World(scene, flags=FUSED)
+    w.step(30)
+    w.query_build()
+    rec = Q.records(w.get_bodies()["transforms"], scene, w.nbox, w.nsph)
+    lo, hi = _bounds(rec)
+    rng = np.random.default_rng(6)
+    for kind in ("random", "axis", "down"):
+        rays = _rays(rng, 32768, lo, hi, kind)
+        rays["max_t"] = rng.choice([np.inf, 5.0, 50.0], size=len(rays))
+        closest, anyh = _cast(w, rays), _cast(w, rays, any_hit=True)
+        assert np.array_equal(closest["shape"] == NONE, anyh["shape"] == NONE), kind
+        miss = anyh["shape"] == NONE
+        assert anyh[miss].tobytes() == closest[miss].tobytes()
+        idx = np.nonzero(~miss)[0]
+        assert len(idx) > 100
+        assert (anyh["t"][idx] <= rays["max_t"][idx]).all()
+        for i in idx[:: max(1, len(idx) // 500)]:
+            c = int(anyh["collider"][i]) + (0 if anyh["shape"][i] == E.NH_SHAPE_BOX else w.nbox)
+            one = Q.raycast(rec, w.nbox, rays[i:i + 1], only=c)[0]
+            assert one.tobytes() == anyh[i].tobytes(), (kind, i)
+    w.close()
+
+
+# ---- observers -----------------------------------------------------------------------------------------------------------------------------
+def _query(w, rays_t, hits_t):
+    w.query_build()
+    w.raycast_records(rays_t, hits=hits_t)
+    w.raycast_records(rays_t, any_hit=True, hits=hits_t)
+
+
+def _same_stepped_world(a, b, what):
+    ba, bb = a.get_bodies(), b.get_bodies()
+    assert P.bits_equal(ba["transforms"], bb["transforms"]) and P.bits_equal(ba["momentum"], bb["momentum"]) and np.array_equal(ba["idle"], bb["idle"]), what
+    a.export_views(E.NH_VIEW_ALL)
+    b.export_views(E.NH_VIEW_ALL)
+    ka, kb = a.get_contacts(), b.get_contacts()
+    assert ka["count"] == kb["count"] and ka["data"].tobytes() == kb["data"].tobytes() and np.array_equal(ka["tags"], kb["tags"]), what
+    assert np.array_equal(ka["features"], kb["features"]) and np.array_equal(ka["bodies"], kb["bodies"]) and np.array_equal(ka["sleeping_pairs"], kb["sleeping_pairs"]), what
+    ca, cb = a.get_cache(), b.get_cache()
+    assert ca["count"] == cb["count"] and ca["data"].tobytes() == cb["data"].tobytes() and np.array_equal(ca["tags"], cb["tags"]), what
+    assert np.array_equal(a.get_active(), b.get_active()), what
+    assert a.counts() == b.counts(), (what, a.counts(), b.counts())
+
+
+OBSERVED = {"pile": lambda: S.pile(256, 0, seed=1), "grid_tiles": lambda: S.grid_tiles(2, side=20, seed=2)}
+
+
+@pytest.mark.parametrize("name", sorted(OBSERVED))
+def test_queries_between_nh_step_calls_change_nothing(name):
+    scene = OBSERVED[name]()
+    a, b = E.World(scene, flags=FUSED), E.World(scene, flags=FUSED)
+    rays = _rays(np.random.default_rng(7), 4096, (-30, -12, -30), (30, 20, 30), "random")
+    rt = _upload(a, rays)
+    ht = a.torch.empty((4096, 32), dtype=a.torch.uint8, device=a.dev)
+    lengths = [1, 2, 3, 5, 7, 4, 8] * 10
+    done = 0
+    for k in lengths:
+        k = min(k, 300 - done)
+        if k <= 0:
+            break
+        _query(a, rt, ht)
+        a.step(k)
+        b.step(k)
+        done += k
+    _query(a, rt, ht)
+    assert done == 300
+    _same_stepped_world(a, b, f"{name} nh_step")
+    c = a.counts()
+    print(f"\n[{name}, nh_step] " + ", ".join(f"{k} {c[k]}" for k in ("still_steps", "still_replays", "ahead_steps", "pair_steps", "asleep_steps")))
+    if name == "grid_tiles":                        # (a pile never takes still steps: tests/test_gpu_still.py)
+        assert c["still_steps"] > 0, c
+    a.close(); b.close()
+
+
+@pytest.mark.parametrize("name", sorted(OBSERVED))
+def test_queries_between_every_call_of_the_fused_step_change_nothing(name):
+    scene = OBSERVED[name]()
+    a, b = E.World(scene, flags=FUSED), E.World(scene, flags=FUSED)
+    rays = _rays(np.random.default_rng(8), 4096, (-30, -12, -30), (30, 20, 30), "random")
+    rt = _upload(a, rays)
+    ht = a.torch.empty((4096, 32), dtype=a.torch.uint8, device=a.dev)
+    calls = ("collide", "gravity", "read_cache", "setup", "apply", "update", "write_cache", "advance")
+    for s in range(300):
+        for name_ in calls:
+            _query(a, rt, ht)
+            getattr(a, name_)()
+            getattr(b, name_)()
+        a.step_done(); b.step_done()
+    _query(a, rt, ht)
+    _same_stepped_world(a, b, f"{name} call by call")
+    c = a.counts()
+    print(f"\n[{name}, call by call] " + ", ".join(f"{k} {c[k]}" for k in ("still_steps", "still_replays", "ahead_steps", "pair_steps", "asleep_steps")))
+    if name == "grid_tiles":
+        assert c["still_steps"] > 0, c
+    a.close(); b.close()
+
+
+# ---- at size -------------------------------------------------------------------------------------------------------------------------------
+def test_a_million_rays_on_the_landed_config_2_world():
+    scene = S.grid_tiles(124, side=90, seed=2, lattice_cols=11)
+    nb = len(scene["body_transforms"])
+    n_tiles = len(scene["tile_of_static"])
+    w = E.World(scene, flags=FUSED, max_contacts=6 * nb)
+    w.step(70)
+    assert w.counts()["error"] == 0
+    w.query_build()
+    rec = Q.records(w.get_bodies()["transforms"], scene)
+    lo, hi = _bounds(rec)
+    rng = np.random.default_rng(9)
+    n = 1 << 20
+    # half the batch: downward rays into the tiles (within each ground slab's footprint), the rest random and axis-aligned over the whole world
+    nd = n // 2
+    tile = rng.integers(0, n_tiles, size=nd)
+    centre = scene["box_transforms"]["position"][tile].astype(np.float64)
+    half = scene["box_data"]["size"][tile, 0].astype(np.float64) - 0.5
+    down = np.zeros(nd, dtype=E.RAY)
+    down["origin"][:, 0] = centre[:, 0] + rng.uniform(-1, 1, size=nd) * half
+    down["origin"][:, 1] = 20.0
+    down["origin"][:, 2] = centre[:, 2] + rng.uniform(-1, 1, size=nd) * half
+    down["direction"] = (0.0, -1.0, 0.0)
+    down["max_t"] = np.inf
+    down["ignore_body"] = NONE
+    rays = np.concatenate([down, _rays(rng, n // 4, lo, hi, "random"), _rays(rng, n - nd - n // 4, lo, hi, "axis")])
+    got = _cast(w, rays)
+    # every downward ray hits its own tile: one of its bodies or its ground slab (box `tile` on body 0)
+    g = got[:nd]
+    assert (g["shape"] != NONE).all()
+    slab = g["body"] == 0
+    assert (g["collider"][slab] == tile[slab]).all()
+    tob = scene["tile_of_body"]
+    assert (tob[g["body"][~slab]] == tile[~slab]).all()
+    assert (~slab).mean() > 0.2
+    # 1024 rays spread over the batch, bit for bit against the brute force over all 1,004,524 colliders
+    pick = np.linspace(0, n - 1, 1024).astype(np.int64)
+    ref = Q.raycast(rec, w.nbox, rays[pick])
+    _same_hits(got[pick], ref, "config 2, 1 M rays")
+    w.close()
