@@ -79,7 +79,7 @@
  *      exported the views: nh_set_option(ctx, "sync_exports_views", 1) restores that contract at its old price; INTEGRATION.md.)  Any entry point outside the sample's
  *      call order between nh_collide and nh_apply_impulses turns a still step into a full one first, so everything it observes is what a full step
  *      produces.  nh_Counts.still_steps / still_replays count them.
- *      The scene queries (nh_query_build, nh_raycast) are not entry points of the step in this sense: they neither export nor settle nor turn a still step into a
+ *      The scene queries (nh_query_build, nh_raycast, nh_overlap) are not entry points of the step in this sense: they neither export nor settle nor turn a still step into a
  *      full one, and they do not count -- see "scene queries" below.
  *
  * Threading: one context = one HIP stream = one world at a time; no global mutable state.
@@ -349,10 +349,10 @@ typedef struct nh_StreamInfo { uint32_t slot; uint32_t valid; uint64_t step; uin
 int nh_stream_state(nh_context* ctx, const nh_BodyData* bodies, uint32_t count, void* host_ring, uint32_t slots, uint32_t every);
 int nh_stream_latest(nh_context* ctx, nh_StreamInfo* out);
 
-/* ---- scene queries: ray casts against the device-resident world ------------------------------------------------------------------------------------------------
+/* ---- scene queries: ray casts and overlaps against the device-resident world -------------------------------------------------------------------------------
    nh_query_build snapshots the world transforms and AABBs of ALL box and sphere colliders -- those of sleeping bodies and of body 0 (the static world) included -- and
    builds a bounding-volume hierarchy over them (a linear BVH: Morton keys, a radix tree, bottom-up boxes) into buffers the library owns: they grow with the collider
-   count (~250 B per collider) and are freed by nh_destroy.  nh_raycast answers `count` rays against the LAST build: the hierarchy does not follow the bodies, so
+   count (~250 B per collider) and are freed by nh_destroy.  nh_raycast answers `count` rays (nh_overlap, below, `count` shapes) against the LAST build: the hierarchy does not follow the bodies, so
    rebuild after they have moved (after nh_step / nh_advance) before casting against the new positions.  All pointers are DEVICE memory; both calls only enqueue work
    on the context's stream, like every other entry point (read the hits after nh_synchronize or a stream / event wait of your own).
    Semantics (nudge_amd/csrc/nh_query.h):
@@ -365,17 +365,47 @@ int nh_stream_latest(nh_context* ctx, nh_StreamInfo* out);
        with t <= max_t, but which hit is unspecified;
      - a ray with a non-finite origin or direction cannot be refused by the return code of an asynchronous call: its record is written as a miss with t = NaN.
    nh_raycast returns NH_ERR_INVALID before any nh_query_build and for null or not 16-byte aligned `rays` / `hits`; count = 0 is a no-op that returns NH_OK.
-   QUERIES ARE OBSERVERS (note 9): neither call exports a view, settles deferred gravity, turns a still step into a full one or touches nh_Counts.  Made between any two
+   QUERIES ARE OBSERVERS (note 9): no query call exports a view, settles deferred gravity, turns a still step into a full one or touches nh_Counts.  Made between any two
    entry points, or between two nh_step calls, they leave every later step bit-identical, with the same still_steps / still_replays / ahead_steps / pair_steps /
    asleep_steps.  They read bodies->transforms as the stream has them at that point: under NH_FLAG_FUSED_STEP the fused solver advances part of the bodies inside
    nh_apply_impulses, so a build between nh_apply_impulses and nh_advance sees a world half advanced -- build after nh_advance (or nh_step) for a consistent one.
-   Not built: overlap / sweep queries, queries on a partitioned world (nh_partition_*), an incremental refit across steps. */
+   Not built: sweep queries (sphere casts), queries on a partitioned world (nh_partition_*), an incremental refit across steps. */
 typedef struct nh_Ray { float origin[3]; float max_t; float direction[3]; uint32_t ignore_body; } nh_Ray;                                            /* 32 B */
 typedef struct nh_RayHit { float t; float normal[3]; uint32_t body; uint32_t collider; uint32_t shape; uint32_t tag; } nh_RayHit;                     /* 32 B */
 enum { NH_SHAPE_BOX = 0u, NH_SHAPE_SPHERE = 1u, NH_SHAPE_NONE = 0xffffffffu };    /* nh_RayHit.shape; NONE = miss */
 enum { NH_RAY_ANY_HIT = 1u };
 int nh_query_build(nh_context* ctx, const nh_BodyData* bodies, const nh_ColliderData* colliders);
 int nh_raycast(nh_context* ctx, const nh_Ray* rays, uint32_t count, nh_RayHit* hits, uint32_t flags);
+
+/* nh_overlap: which colliders of the LAST nh_query_build touch each of `count` query shapes -- explosion radii, trigger volumes, "is this spot free".
+   Query shapes (nh_OverlapQuery):
+     - shape = NH_SHAPE_SPHERE: the ball of radius size[0] around `center`; rotation and size[1..2] are ignored.  Radius 0 is a point query;
+     - shape = NH_SHAPE_BOX: the oriented box of half extents `size` (as in nh_BoxCollider) and rotation `rotation`, a unit quaternion in nh_Transform's
+       (x, y, z, s) order that the library does not normalise.
+   The answer of query i is the set of colliders that overlap its shape as CLOSED sets (touching counts), over every box and sphere collider of the last build
+   (those of sleeping bodies and of body 0 included), less the colliders of `ignore_body` (0xffffffff: none is ignored).  A collider whose body does not exist
+   (NaN pose) overlaps nothing.  Exact predicates: nudge_amd/csrc/nh_query.h.
+   Output, by the exclusive scan of the per-query counts:
+     - offsets[0 .. count] (count + 1 words): offsets[i] = the records before query i, offsets[count] = the total;
+     - the records of query i are hits[offsets[i] .. offsets[i+1]), in ascending COMBINED collider index (boxes 0 .. nbox-1, then the spheres -- the ray
+       tie-break's order), so the output does not depend on the tree: a brute force gives the same bytes.  `collider` is the index within its own array and
+       `shape` says which array, as in nh_RayHit;
+     - COUNT ONLY: hits == NULL and capacity == 0 write offsets alone (count, read offsets[count], allocate, list);
+     - CAPACITY: the records of query i are written if and only if offsets[i+1] <= capacity -- the written part is a prefix of whole segments, every byte of
+       `hits` behind it is left untouched, and `offsets` is always complete;
+     - a true total of 2^32 - 1 or more writes offsets[count] = 0xffffffff and no record at all (the other offsets are then unspecified).  Every per-query
+       count is below 2^30, so the 32-bit scan has wrapped iff some offsets[i+1] < offsets[i]; a total of exactly 2^32 - 1 is the marker itself.
+   An INVALID query overlaps nothing (count 0): an unknown shape, a non-finite centre or size (for a sphere size[0] alone), for a box a non-finite rotation,
+   or a negative size.  As with non-finite rays, an asynchronous call cannot refuse one record.
+   Returns NH_ERR_INVALID before any nh_query_build, for flags != 0, for `queries` null or not 16-byte aligned, `offsets` null or not 4-byte aligned, `hits`
+   null with capacity > 0 or not 16-byte aligned, and for count >= 2^30; count = 0 is a no-op that returns NH_OK.
+   An OBSERVER like nh_raycast (note 9): no view export, no settling of deferred gravity, no still step turned into a full one, no change to nh_Counts.  Everything
+   is enqueued on the context's stream, except that a larger capacity than any before grows the library's sort scratch (~24 B per record of capacity) after a
+   stream synchronise, as a build that grows does. */
+typedef struct nh_OverlapQuery { float center[3]; uint32_t shape; float rotation[4]; float size[3]; uint32_t ignore_body; } nh_OverlapQuery;  /* 48 B */
+typedef struct nh_OverlapHit { uint32_t body; uint32_t collider; uint32_t shape; uint32_t tag; } nh_OverlapHit;                            /* 16 B */
+int nh_overlap(nh_context* ctx, const nh_OverlapQuery* queries, uint32_t count, uint32_t* offsets /* count + 1 */, nh_OverlapHit* hits, uint32_t capacity,
+               uint32_t flags /* 0 */);
 
 /* ---- multi-GPU: one x-slab of a world per context ------------------------------------------------------------------------------------
    The world is cut into slabs along x, one rank (process, GPU, nh_context) per slab [lo, hi).  A rank's arrays hold

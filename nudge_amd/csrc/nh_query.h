@@ -1,5 +1,5 @@
-// nh_query.h -- per-item arithmetic of the scene query (nh_query_build / nh_raycast, nh_query.hip): a collider's world pose, and a ray
-// against one box and against one sphere.
+// nh_query.h -- per-item arithmetic of the scene query (nh_query_build / nh_raycast / nh_overlap, nh_query.hip): a collider's world pose, a ray
+// against one box and against one sphere, and the overlap predicates of a query sphere or box against one collider.
 //
 // Every function is `NH_HD` so that tests/hostquery builds the SAME arithmetic with g++ -ffp-contract=off and gets the device's bits: the
 // brute force over all colliders there is the oracle of the GPU's tree traversal.  Only + - * /, sqrtf (correctly rounded on both sides)
@@ -99,6 +99,73 @@ NH_HD nh_QHit nh_q_ray_sphere(nh_f3 o, nh_f3 d, nh_f3 c, float rad) {
 NH_HD bool nh_q_better(float t, uint32_t c, float max_t, float bt, uint32_t bc) {
 	if (!(t >= 0.0f && t <= max_t)) return false;
 	return bc == 0xffffffffu || t < bt || (t == bt && c < bc);
+}
+
+// ---- overlap (nh_overlap): does a query shape touch a collider?  Closed sets: touching counts ----------------------------------------------
+// Each predicate reads "overlap iff every test holds with <=", so a NaN anywhere fails a test and gives NO overlap (the collider of a body that
+// does not exist has a NaN pose).  These are geometric queries, not contact generation: nothing is shared with the narrowphase's SAT.
+
+// sphere (c, r) against sphere (p, R): m = c - p, overlap iff m.m <= (r + R)^2
+NH_HD bool nh_q_overlap_sphere_sphere(nh_f3 c, float r, nh_f3 p, float R) {
+	const nh_f3 m = c - p;
+	const float s = r + R;
+	return nh_dot(m, m) <= s * s;
+}
+
+// sphere (c, r) against the box of world pose (p, q) and half extents h -- a sphere query against a box collider and a box query against a sphere
+// collider alike.  The centre is brought into the box frame by the inverse rotation (as nh_q_ray_box does) and clamped to [-h, h]; overlap iff the
+// squared distance to the clamped point is <= r^2.  Per axis that distance is |l| - h where positive, 0 inside (l - clamp(l) is +-(|l| - h), the
+// same bits squared); a NaN keeps its NaN through `e <= 0 ? 0 : e`.
+NH_HD bool nh_q_overlap_sphere_box(nh_f3 c, float r, nh_f3 p, nh_quat q, nh_f3 h) {
+	const nh_quat qi = { nh_neg(q.x), nh_neg(q.y), nh_neg(q.z), q.s };
+	const nh_f3 l = nh_rotate(qi, c - p);
+	const float ex = nh_abs(l.x) - h.x, ey = nh_abs(l.y) - h.y, ez = nh_abs(l.z) - h.z;
+	const float dx = ex <= 0.0f ? 0.0f : ex, dy = ey <= 0.0f ? 0.0f : ey, dz = ez <= 0.0f ? 0.0f : ez;
+	return dx * dx + dy * dy + dz * dz <= r * r;
+}
+
+// Box a (ca, qa, ha) -- the QUERY box -- against box b (cb, qb, hb) -- the collider: the 15 separating axes in a's frame (Gottschalk, Lin & Manocha
+// 1996, "OBBTree"; Ericson, Real-Time Collision Detection 4.4.1), R = Ra^T Rb (R_ij = A_i . B_j), t = Ra^T (cb - ca).  The radii use
+// E_ij = |R_ij| + 2^-20: when an edge of a is (nearly) parallel to an edge of b, their cross product is (nearly) zero and both sides of its test are
+// rounding noise, so without the epsilon a pair of boxes that overlaps could be separated by a degenerate axis.  The epsilon is above the rounding of
+// R for unit quaternions (a few ulp of 1) and only ever widens the radii: it can add a touch, never remove one.  What it adds is bounded by three
+// more tests, first: the two world AABBs -- c -+ nh_q_box_extent, the very bounds the build (k_q_xform) and the query walk compute before padding --
+// must touch.  Exact boxes that overlap have touching AABBs (up to rounding), and a pair the epsilon lets through is at least in the tree's reach:
+// the padded node boxes contain these bounds, so the walk can never prune what this predicate accepts.
+#define NH_Q_SAT_EPS 9.5367431640625e-07f
+NH_HD bool nh_q_overlap_box_box(nh_f3 ca, nh_quat qa, nh_f3 ha, nh_f3 cb, nh_quat qb, nh_f3 hb) {
+	const nh_f3 ea = nh_q_box_extent(qa, ha), eb = nh_q_box_extent(qb, hb);
+	if (!((cb.x - eb.x) <= (ca.x + ea.x) && (ca.x - ea.x) <= (cb.x + eb.x) && (cb.y - eb.y) <= (ca.y + ea.y) && (ca.y - ea.y) <= (cb.y + eb.y) &&
+	      (cb.z - eb.z) <= (ca.z + ea.z) && (ca.z - ea.z) <= (cb.z + eb.z))) return false;
+	const nh_m33 A = nh_matrix(qa), B = nh_matrix(qb);
+	const nh_f3 d = cb - ca;
+	const float t0 = nh_dot(A.c0, d), t1 = nh_dot(A.c1, d), t2 = nh_dot(A.c2, d);
+	const float R00 = nh_dot(A.c0, B.c0), R01 = nh_dot(A.c0, B.c1), R02 = nh_dot(A.c0, B.c2);
+	const float R10 = nh_dot(A.c1, B.c0), R11 = nh_dot(A.c1, B.c1), R12 = nh_dot(A.c1, B.c2);
+	const float R20 = nh_dot(A.c2, B.c0), R21 = nh_dot(A.c2, B.c1), R22 = nh_dot(A.c2, B.c2);
+	const float E00 = nh_abs(R00) + NH_Q_SAT_EPS, E01 = nh_abs(R01) + NH_Q_SAT_EPS, E02 = nh_abs(R02) + NH_Q_SAT_EPS;
+	const float E10 = nh_abs(R10) + NH_Q_SAT_EPS, E11 = nh_abs(R11) + NH_Q_SAT_EPS, E12 = nh_abs(R12) + NH_Q_SAT_EPS;
+	const float E20 = nh_abs(R20) + NH_Q_SAT_EPS, E21 = nh_abs(R21) + NH_Q_SAT_EPS, E22 = nh_abs(R22) + NH_Q_SAT_EPS;
+	const float a0 = ha.x, a1 = ha.y, a2 = ha.z, b0 = hb.x, b1 = hb.y, b2 = hb.z;
+	// a's face normals A_0 .. A_2
+	bool ok = nh_abs(t0) <= a0 + (b0 * E00 + b1 * E01 + b2 * E02);
+	ok = ok && nh_abs(t1) <= a1 + (b0 * E10 + b1 * E11 + b2 * E12);
+	ok = ok && nh_abs(t2) <= a2 + (b0 * E20 + b1 * E21 + b2 * E22);
+	// b's face normals B_0 .. B_2
+	ok = ok && nh_abs(t0 * R00 + t1 * R10 + t2 * R20) <= (a0 * E00 + a1 * E10 + a2 * E20) + b0;
+	ok = ok && nh_abs(t0 * R01 + t1 * R11 + t2 * R21) <= (a0 * E01 + a1 * E11 + a2 * E21) + b1;
+	ok = ok && nh_abs(t0 * R02 + t1 * R12 + t2 * R22) <= (a0 * E02 + a1 * E12 + a2 * E22) + b2;
+	// edge x edge: A_i x B_j
+	ok = ok && nh_abs(t2 * R10 - t1 * R20) <= (a1 * E20 + a2 * E10) + (b1 * E02 + b2 * E01);
+	ok = ok && nh_abs(t2 * R11 - t1 * R21) <= (a1 * E21 + a2 * E11) + (b0 * E02 + b2 * E00);
+	ok = ok && nh_abs(t2 * R12 - t1 * R22) <= (a1 * E22 + a2 * E12) + (b0 * E01 + b1 * E00);
+	ok = ok && nh_abs(t0 * R20 - t2 * R00) <= (a0 * E20 + a2 * E00) + (b1 * E12 + b2 * E11);
+	ok = ok && nh_abs(t0 * R21 - t2 * R01) <= (a0 * E21 + a2 * E01) + (b0 * E12 + b2 * E10);
+	ok = ok && nh_abs(t0 * R22 - t2 * R02) <= (a0 * E22 + a2 * E02) + (b0 * E11 + b1 * E10);
+	ok = ok && nh_abs(t1 * R00 - t0 * R10) <= (a0 * E10 + a1 * E00) + (b1 * E22 + b2 * E21);
+	ok = ok && nh_abs(t1 * R01 - t0 * R11) <= (a0 * E11 + a1 * E01) + (b0 * E22 + b2 * E20);
+	ok = ok && nh_abs(t1 * R02 - t0 * R12) <= (a0 * E12 + a1 * E02) + (b0 * E21 + b1 * E20);
+	return ok;
 }
 
 #endif

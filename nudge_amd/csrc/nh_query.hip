@@ -1,5 +1,6 @@
 // nh_query.hip -- scene queries against the device-resident world: nh_query_build (a linear BVH over every box and sphere collider, built from
-// the current transforms) and nh_raycast (batched closest-hit / any-hit ray casts against the last build).  include/nudge_hip.h, "scene queries".
+// the current transforms), nh_raycast (batched closest-hit / any-hit ray casts against the last build) and nh_overlap (the colliders touching each
+// of a batch of spheres or boxes, as variable-length segments).  include/nudge_hip.h, "scene queries".
 //
 // Build (one launch each, plus the library's radix sort):
 //   k_q_xform   one lane per collider (boxes, then spheres): world pose (k_xform's arithmetic, nh_query.h), world AABB, the record the ray test
@@ -25,8 +26,9 @@
 struct nh_QRec { float4 a, b, c; };
 // A node: a = (box min, left child | NH_Q_LEAF + collider), b = (box max, escape link)
 struct nh_QNode { float4 a, b; };
-// words the build's kernels share: collider count (the sort reads it), bounds of the positions (flipped floats)
-struct nh_QCtl { uint32_t count, pad0[3]; uint32_t smin[4]; uint32_t smax[4]; };
+// words the build's kernels share: collider count (the sort reads it), bounds of the positions (flipped floats); nh_overlap's: a word that stays 0
+// (the element count of its scan is all `extra`), the length of the written prefix of records (its sort and gather read it), the wrap flag
+struct nh_QCtl { uint32_t count, zero, ov_written, ov_wrap; uint32_t smin[4]; uint32_t smax[4]; };
 
 struct nh_QueryState {
 	uint32_t capacity;           // colliders the buffers have room for
@@ -42,6 +44,8 @@ struct nh_QueryState {
 	uint32_t* last;              // by internal node: last leaf of its range
 	uint32_t* right_at;          // by split position: the right child of the node that splits there
 	uint32_t* arrive;            // by internal node: arrival counter of the refit
+	uint32_t ov_capacity;        // nh_overlap's sort scratch, by record of the caller's capacity
+	uint64_t* ov_keys_a; uint64_t* ov_keys_b; uint32_t* ov_vals_a; uint32_t* ov_vals_b;
 };
 
 // ---- build ----------------------------------------------------------------------------------------------------------------------------------
@@ -267,11 +271,107 @@ __global__ __launch_bounds__(256) void k_q_raycast(const nh_Ray* __restrict__ ra
 	}
 }
 
+// ---- overlap ---------------------------------------------------------------------------------------------------------------------------------
+// nh_overlap is a chain of launches with kernel boundaries as the only hand-offs; no atomic decides where a record goes:
+//   k_q_overlap<false>  one lane per query: the tree walk of k_q_raycast (stackless, escape links) with the query's padded world AABB, the exact
+//                       predicate at the leaves; offsets[i] = the count (offsets[count] = 0, scanned along)
+//   nh_scan_u32         in place over count + 1 words: offsets and the total
+//   k_q_overlap_fix     the wrap (offsets[i+1] < offsets[i]) and the written prefix: the one i with offsets[i] <= capacity < offsets[i+1], or the total
+//   k_q_overlap_fin     one lane: on a wrap or a total equal to the marker, offsets[count] = 0xffffffff and nothing is written
+//   k_q_overlap<true>   the same walk (the same template: the same set) for the queries whose segment fits: key (i << cbits | c), value c at offsets[i] + k
+//   nh_sort_u64_u32     over the written prefix (its length from the device): keys are unique, so (query, combined index) ascending is the only order
+//   k_q_overlap_gather  nh_OverlapHit {body, collider, shape, tag} from the record of each sorted collider, one 16-byte store each
+template <bool LIST>
+__global__ __launch_bounds__(256) void k_q_overlap(const nh_OverlapQuery* __restrict__ queries, uint32_t count, uint32_t* offsets,
+                                                   const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox,
+                                                   nh_QCtl* ctl, uint64_t* __restrict__ keys, uint32_t* __restrict__ vals, uint32_t cbits) {
+	if (!LIST && blockIdx.x == 0 && threadIdx.x == 0) { offsets[count] = 0u; ctl->ov_wrap = 0u; ctl->ov_written = 0u; }   // (k_q_overlap_fix sets both)
+	const uint32_t written = LIST ? ctl->ov_written : 0u;
+	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
+		uint32_t base = 0u, end = 0u;
+		if (LIST) {
+			base = offsets[i]; end = offsets[i + 1u];
+			if (!(base < end && end <= written)) continue;          // empty, or not in the written prefix
+		}
+		const float4* qp = reinterpret_cast<const float4*>(queries + i);
+		const float4 q0 = qp[0], q1 = qp[1], q2 = qp[2];
+		const nh_f3 c = nh_make3(q0.x, q0.y, q0.z), h = nh_make3(q2.x, q2.y, q2.z);
+		const nh_quat qr = { q1.x, q1.y, q1.z, q1.w };
+		const uint32_t shape = __float_as_uint(q0.w), ignore = __float_as_uint(q2.w);
+		const bool sphere = shape == NH_SHAPE_SPHERE;
+		bool ok = (sphere || shape == NH_SHAPE_BOX) && nh_q_finite(c.x) && nh_q_finite(c.y) && nh_q_finite(c.z) && nh_q_finite(h.x) && !(h.x < 0.0f);
+		if (!sphere) ok = ok && nh_q_finite(h.y) && nh_q_finite(h.z) && !(h.y < 0.0f) && !(h.z < 0.0f) &&
+		                  nh_q_finite(qr.x) && nh_q_finite(qr.y) && nh_q_finite(qr.z) && nh_q_finite(qr.s);
+		// the query's world AABB, padded by 2^-18 of its largest coordinate (only ever more generous than the exact test)
+		const nh_f3 e = sphere ? nh_make3(h.x, h.x, h.x) : nh_q_box_extent(qr, h);
+		nh_f3 lo = c - e, hi = c + e;
+		const float s = fmaxf(fmaxf(fmaxf(fabsf(lo.x), fabsf(lo.y)), fmaxf(fabsf(lo.z), fabsf(hi.x))), fmaxf(fabsf(hi.y), fabsf(hi.z))) * 3.814697265625e-06f;
+		lo = nh_make3(lo.x - s, lo.y - s, lo.z - s); hi = nh_make3(hi.x + s, hi.y + s, hi.z + s);
+		uint32_t k = 0u;
+		uint32_t node = ok && n ? 0u : NH_Q_NONE;
+		while (node != NH_Q_NONE) {
+			const float4 na = nodes[node].a, nb = nodes[node].b;
+			const bool enter = na.x <= hi.x && lo.x <= nb.x && na.y <= hi.y && lo.y <= nb.y && na.z <= hi.z && lo.z <= nb.z;
+			const uint32_t left = __float_as_uint(na.w);
+			const uint32_t rope = __float_as_uint(nb.w);
+			if (!enter) { node = rope; continue; }
+			if (!(left & NH_Q_LEAF)) { node = left; continue; }
+			node = rope;
+			const uint32_t cc = left & ~NH_Q_LEAF;
+			const nh_QRec r = rec[cc];
+			if (__float_as_uint(r.a.w) == ignore) continue;
+			const nh_f3 p = nh_make3(r.a.x, r.a.y, r.a.z), rh = nh_make3(r.c.x, r.c.y, r.c.z);
+			const nh_quat rq = { r.b.x, r.b.y, r.b.z, r.b.w };
+			bool hit;
+			if (cc < nbox) hit = sphere ? nh_q_overlap_sphere_box(c, h.x, p, rq, rh) : nh_q_overlap_box_box(c, qr, h, p, rq, rh);
+			else hit = sphere ? nh_q_overlap_sphere_sphere(c, h.x, p, rh.x) : nh_q_overlap_sphere_box(p, rh.x, c, qr, h);
+			if (!hit) continue;
+			if (LIST) {
+				// (the count pass found exactly end - base: the segment is full once they are written, nothing else can follow)
+				keys[base + k] = ((uint64_t)i << cbits) | cc;
+				vals[base + k] = cc;
+				if (base + k + 1u == end) break;
+			}
+			++k;
+		}
+		if (!LIST) offsets[i] = k;
+	}
+}
+
+__global__ __launch_bounds__(256) void k_q_overlap_fix(const uint32_t* __restrict__ offsets, uint32_t count, uint32_t capacity, nh_QCtl* __restrict__ ctl) {
+	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i <= count; i += gridDim.x * blockDim.x) {
+		const uint32_t lo = offsets[i];
+		if (i == count) {
+			if (lo <= capacity) ctl->ov_written = lo;             // everything fits
+			continue;
+		}
+		const uint32_t hi = offsets[i + 1u];
+		if (hi < lo) ctl->ov_wrap = 1u;                            // (every store writes the same word)
+		else if (lo <= capacity && capacity < hi) ctl->ov_written = lo;   // monotone offsets: exactly one lane, when there is no wrap
+	}
+}
+
+__global__ void k_q_overlap_fin(uint32_t* __restrict__ offsets, uint32_t count, nh_QCtl* __restrict__ ctl) {
+	if (ctl->ov_wrap || offsets[count] == NH_Q_NONE) { offsets[count] = NH_Q_NONE; ctl->ov_written = 0u; }
+}
+
+__global__ __launch_bounds__(256) void k_q_overlap_gather(const uint32_t* __restrict__ vals, const nh_QCtl* __restrict__ ctl, const nh_QRec* __restrict__ rec,
+                                                          uint32_t n, uint32_t nbox, nh_OverlapHit* __restrict__ hits) {
+	const uint32_t m = ctl->ov_written;
+	for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < m; j += gridDim.x * blockDim.x) {
+		const uint32_t c = vals[j];
+		if (c >= n) continue;          // (cannot happen: the list pass fills the whole prefix; a guard against reading outside the records)
+		const nh_QRec r = rec[c];
+		*reinterpret_cast<uint4*>(hits + j) = make_uint4(__float_as_uint(r.a.w), c < nbox ? c : c - nbox, c < nbox ? NH_SHAPE_BOX : NH_SHAPE_SPHERE, __float_as_uint(r.c.w));
+	}
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------------------------------
 void nh_query_free(nh_context* ctx) {
 	nh_QueryState* q = ctx->query;
 	if (!q) return;
-	void* bufs[] = { q->ctl, q->rec, q->aabb, q->keys_a, q->keys_b, q->idx_a, q->idx_b, q->hist, q->nodes, q->parent, q->rchild, q->last, q->right_at, q->arrive };
+	void* bufs[] = { q->ctl, q->rec, q->aabb, q->keys_a, q->keys_b, q->idx_a, q->idx_b, q->hist, q->nodes, q->parent, q->rchild, q->last, q->right_at, q->arrive,
+	                 q->ov_keys_a, q->ov_keys_b, q->ov_vals_a, q->ov_vals_b };
 	for (void* b : bufs) if (b) hipFree(b);
 	delete q;
 	ctx->query = nullptr;
@@ -349,5 +449,55 @@ extern "C" int nh_raycast(nh_context* ctx, const nh_Ray* rays, uint32_t count, n
 	nh_QueryState* q = ctx->query;
 	NH_LAUNCH(ctx, "q_raycast", k_q_raycast, nh_grid_for(count, 256, 1u << 20), 256, rays, count, hits, q->nodes, q->rec, q->n, q->nbox,
 	          (flags & NH_RAY_ANY_HIT) ? 1u : 0u);
+	return NH_OK;
+}
+
+// nh_overlap's sort scratch, by record of the caller's capacity (a growth waits for the stream first, as nh_query_reserve's does)
+static int nh_overlap_reserve(nh_context* ctx, uint32_t capacity) {
+	nh_QueryState* q = ctx->query;
+	if (capacity <= q->ov_capacity) return NH_OK;
+	const uint64_t cap64 = (uint64_t)capacity + capacity / 8u + 64u;
+	const uint32_t cap = cap64 > 0xffffffffull ? 0xffffffffu : (uint32_t)cap64;
+	NH_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+	void* old[] = { q->ov_keys_a, q->ov_keys_b, q->ov_vals_a, q->ov_vals_b };
+	for (void* b : old) if (b) hipFree(b);
+	q->ov_keys_a = q->ov_keys_b = nullptr; q->ov_vals_a = q->ov_vals_b = nullptr;
+	q->ov_capacity = 0;
+	NH_HIP_CHECK(ctx, hipMalloc((void**)&q->ov_keys_a, sizeof(uint64_t) * (size_t)cap));
+	NH_HIP_CHECK(ctx, hipMalloc((void**)&q->ov_keys_b, sizeof(uint64_t) * (size_t)cap));
+	NH_HIP_CHECK(ctx, hipMalloc((void**)&q->ov_vals_a, sizeof(uint32_t) * (size_t)cap));
+	NH_HIP_CHECK(ctx, hipMalloc((void**)&q->ov_vals_b, sizeof(uint32_t) * (size_t)cap));
+	q->ov_capacity = cap;
+	return NH_OK;
+}
+
+static int nh_q_bits(uint32_t x) { return x ? 32 - __builtin_clz(x) : 0; }
+
+extern "C" int nh_overlap(nh_context* ctx, const nh_OverlapQuery* queries, uint32_t count, uint32_t* offsets, nh_OverlapHit* hits, uint32_t capacity,
+                          uint32_t flags) {
+	if (!ctx || !ctx->query || !ctx->query->built) return NH_ERR_INVALID;
+	if (flags != 0u || count >= NH_Q_MAX_COLLIDERS) return NH_ERR_INVALID;
+	if (count == 0u) return NH_OK;
+	if (!queries || ((uintptr_t)queries & 15u)) return NH_ERR_INVALID;        // (records are read as 16-byte words)
+	if (!offsets || ((uintptr_t)offsets & 3u)) return NH_ERR_INVALID;
+	if ((!hits && capacity) || ((uintptr_t)hits & 15u)) return NH_ERR_INVALID;
+	NH_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+	nh_QueryState* q = ctx->query;
+	const bool list = hits != nullptr && capacity != 0u;
+	if (list) { const int rc = nh_overlap_reserve(ctx, capacity); if (rc) return rc; }
+	const uint32_t cbits = (uint32_t)nh_q_bits(q->n);
+	const uint32_t grid = nh_grid_for(count, 256, 1u << 20);
+	NH_LAUNCH(ctx, "q_overlap_count", k_q_overlap<false>, grid, 256, queries, count, offsets, q->nodes, q->rec, q->n, q->nbox, q->ctl,
+	          (uint64_t*)nullptr, (uint32_t*)nullptr, cbits);
+	nh_scan_u32(ctx, offsets, offsets, &q->ctl->zero, count + 1u, q->hist, nullptr);
+	NH_LAUNCH(ctx, "q_overlap_fix", k_q_overlap_fix, nh_grid_for((uint64_t)count + 1u, 256, 4096), 256, offsets, count, capacity, q->ctl);
+	NH_LAUNCH(ctx, "q_overlap_fin", k_q_overlap_fin, 1, 1, offsets, count, q->ctl);
+	if (!list) return NH_OK;
+	NH_LAUNCH(ctx, "q_overlap_list", k_q_overlap<true>, grid, 256, queries, count, offsets, q->nodes, q->rec, q->n, q->nbox, q->ctl,
+	          q->ov_keys_a, q->ov_vals_a, cbits);
+	const int bits = (((int)cbits + nh_q_bits(count)) + 7) / 8 * 8;
+	const int in_b = nh_sort_u64_u32(ctx, q->ov_keys_a, q->ov_keys_b, q->ov_vals_a, q->ov_vals_b, &q->ctl->ov_written, q->hist, 0, bits);
+	NH_LAUNCH(ctx, "q_overlap_gather", k_q_overlap_gather, nh_grid_for(capacity, 256, 4096), 256, in_b ? q->ov_vals_b : q->ov_vals_a, q->ctl, q->rec, q->n, q->nbox,
+	          hits);
 	return NH_OK;
 }

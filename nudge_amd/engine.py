@@ -43,7 +43,7 @@ EXPORTS = [
     "nh_partition_top_speed", "nh_partition_set_peer_speeds", "nh_partition_refresh_is_quiet", "nh_partition_mark_ghosts", "nh_partition_pack_deltas", "nh_partition_unpack_deltas",
     "nh_partition_pack_momentum", "nh_partition_unpack_momentum", "nh_partition_exchange_iteration", "nh_partition_unpack_ghosts", "nh_partition_pack_step", "nh_partition_unpack_step", "nh_partition_choose_cut", "nh_partition_set_cut",
     "nh_partition_set_transport", "nh_partition_exchange_step", "nh_partition_step", "nh_partition_transport_check", "nh_partition_transport_result", "nh_set_first_ghost_body",
-    "nh_query_build", "nh_raycast",
+    "nh_query_build", "nh_raycast", "nh_overlap",
 ]
 HALO_RECORD_BYTES = 64
 
@@ -122,6 +122,17 @@ NH_SHAPE_BOX, NH_SHAPE_SPHERE, NH_SHAPE_NONE = 0, 1, 0xFFFFFFFF
 NH_RAY_ANY_HIT = 1
 RAY = np.dtype([("origin", "<f4", 3), ("max_t", "<f4"), ("direction", "<f4", 3), ("ignore_body", "<u4")])
 RAY_HIT = np.dtype([("t", "<f4"), ("normal", "<f4", 3), ("body", "<u4"), ("collider", "<u4"), ("shape", "<u4"), ("tag", "<u4")])
+OVERLAP_QUERY = np.dtype([("center", "<f4", 3), ("shape", "<u4"), ("rotation", "<f4", 4), ("size", "<f4", 3), ("ignore_body", "<u4")])
+OVERLAP_HIT = np.dtype([("body", "<u4"), ("collider", "<u4"), ("shape", "<u4"), ("tag", "<u4")])
+NH_OVERLAP_OVERFLOW = 0xFFFFFFFF          # offsets[count] when the total is 2^32 - 1 or more
+
+
+class OverlapQuery(C.Structure):
+    _fields_ = [("center", C.c_float * 3), ("shape", C.c_uint32), ("rotation", C.c_float * 4), ("size", C.c_float * 3), ("ignore_body", C.c_uint32)]
+
+
+class OverlapHit(C.Structure):
+    _fields_ = [("body", C.c_uint32), ("collider", C.c_uint32), ("shape", C.c_uint32), ("tag", C.c_uint32)]
 
 
 class KernelTime(C.Structure):
@@ -209,6 +220,7 @@ def lib():
         L.nh_set_first_ghost_body.argtypes = [C.c_void_p, C.c_uint32]
         L.nh_query_build.argtypes = [C.c_void_p, C.POINTER(BodyData), C.POINTER(ColliderData)]
         L.nh_raycast.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
+        L.nh_overlap.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
         _LIB = L
     return _LIB
 
@@ -606,6 +618,73 @@ class World:
         if synchronize:
             torch.cuda.current_stream(self.dev).synchronize()
         return out
+
+    def overlap_records(self, queries, offsets=None, hits=None, capacity=0):
+        """nh_overlap on records already laid out as nh_OverlapQuery: `queries` a contiguous device tensor of count x 48 bytes (any dtype).  Returns
+        (offsets, hits): the count + 1 offsets as an int32 device tensor holding the uint32 bits (`offsets`, or a new one) and `hits` as given.  With
+        hits = None and capacity = 0 only the offsets are written (count only); otherwise `hits` must hold `capacity` x 16 bytes, and the records of
+        query i are written iff offsets[i + 1] <= capacity.  Enqueued; nothing waits (but a capacity larger than any before grows the scratch)."""
+        torch = self.torch
+        n = queries.numel() * queries.element_size() // 48
+        if offsets is None:
+            offsets = torch.empty(n + 1, dtype=torch.int32, device=self.dev)
+        if hits is not None and hits.numel() * hits.element_size() < 16 * capacity:
+            raise ValueError(f"overlap_records: hits holds {hits.numel() * hits.element_size()} bytes, capacity {capacity} needs {16 * capacity}")
+        _check(self.L, self.L.nh_overlap(self.ctx, C.c_void_p(queries.data_ptr() if n else 0), n, C.c_void_p(offsets.data_ptr()),
+                                         C.c_void_p(hits.data_ptr() if hits is not None else 0), capacity, 0), "nh_overlap")
+        return offsets, hits
+
+    def overlap(self, centres, radii=None, half_extents=None, rotations=None, ignore_body=None, capacity=None, synchronize=False):
+        """The colliders touching each of n spheres (`radii`: a number or n values) or n oriented boxes (`half_extents` (n, 3) or (3,), `rotations`
+        (n, 4) or (4,) quaternions (x, y, z, s), default identity), against the last query_build().  Give exactly one of radii / half_extents;
+        mixed batches go through overlap_records.  `ignore_body`: None, a body index, or n of them.
+        capacity=None: a count call, then the total is read -- this WAITS for the device -- and an exactly sized list call.  A capacity: one call, and
+        nothing waits; only the segments that fit are listed (offsets[i + 1] <= capacity).
+        Returns a dict of device tensors: offsets (n + 1, int64; offsets[n] = 0xffffffff when the total is 2^32 - 1 or more), `written` (0-d: the
+        records listed, a prefix of whole segments), and per record slot (capacity of them; the first `written` are meaningful) query, body,
+        collider, shape, tag (int64) and `raw`, the nh_OverlapHit records (capacity x 16 bytes)."""
+        torch = self.torch
+        if (radii is None) == (half_extents is None):
+            raise ValueError("overlap: give exactly one of radii / half_extents")
+        c = torch.as_tensor(centres, dtype=torch.float32, device=self.dev).reshape(-1, 3)
+        n = c.shape[0]
+        q = torch.zeros((n, 12), dtype=torch.float32, device=self.dev)
+        qi = q.view(torch.int32)
+        q[:, 0:3] = c
+        if radii is not None:
+            qi[:, 3] = NH_SHAPE_SPHERE
+            q[:, 8] = torch.as_tensor(radii, dtype=torch.float32, device=self.dev).reshape(-1)
+            q[:, 7] = 1.0
+        else:
+            qi[:, 3] = NH_SHAPE_BOX
+            q[:, 8:11] = torch.as_tensor(half_extents, dtype=torch.float32, device=self.dev).reshape(-1, 3)
+            if rotations is None:
+                q[:, 7] = 1.0
+            else:
+                q[:, 4:8] = torch.as_tensor(rotations, dtype=torch.float32, device=self.dev).reshape(-1, 4)
+        ign = 0xFFFFFFFF if ignore_body is None else ignore_body
+        ign = torch.as_tensor(ign, dtype=torch.int64, device=self.dev)
+        qi[:, 11] = (((ign & 0xFFFFFFFF) ^ 0x80000000) - 0x80000000).to(torch.int32)          # (the uint32 bits, as int32)
+        if capacity is None:
+            offsets, _ = self.overlap_records(q)
+            total = int(offsets[n].item()) & 0xFFFFFFFF if n else 0          # (a synchronisation)
+            capacity = 0 if total == NH_OVERLAP_OVERFLOW else total
+            hits = torch.empty((capacity, 16), dtype=torch.uint8, device=self.dev)
+            if capacity:
+                self.overlap_records(q, offsets=offsets, hits=hits, capacity=capacity)
+        else:
+            hits = torch.empty((capacity, 16), dtype=torch.uint8, device=self.dev)
+            offsets, _ = self.overlap_records(q, hits=hits if capacity else None, capacity=capacity)
+        off = offsets.to(torch.int64) & 0xFFFFFFFF
+        # the written prefix: the largest offset <= capacity (offsets are monotone unless the total overflowed, and then nothing is written)
+        last = torch.searchsorted(off, torch.tensor([capacity], dtype=torch.int64, device=self.dev), right=True) - 1
+        written = torch.where(off[n] == NH_OVERLAP_OVERFLOW, torch.zeros_like(last), off[last.clamp(min=0)])[0]
+        j = torch.arange(capacity, dtype=torch.int64, device=self.dev)
+        query = (torch.searchsorted(off[1:], j, right=True) if n else j).clamp(max=max(n - 1, 0))
+        u = hits.view(torch.int32).reshape(-1, 4).to(torch.int64) & 0xFFFFFFFF
+        if synchronize:
+            torch.cuda.current_stream(self.dev).synchronize()
+        return dict(offsets=off, written=written, query=query, body=u[:, 0], collider=u[:, 1], shape=u[:, 2], tag=u[:, 3], raw=hits)
 
     # ---- measurement ----
     def enable_timing(self, on=True, only=None):
