@@ -221,7 +221,7 @@ typedef struct nh_Counts {
 	uint32_t asleep_steps;      /* steps since nh_create that nh_step found to be steps of a world in which every body is asleep and nothing has changed: done without a launch */
 	uint32_t ahead_steps;       /* still steps (launched, since nh_create) that started at the narrowphase: the solver of the sub-step before them, inside the same nh_step call, had
 	                               already written their colliders' world transforms and boxes (note 9, "xform ahead") */
-	uint32_t fused_steps;       /* ... and that went through as ONE out-of-place launch with a look-back (option "fused_still", off by default: measured slower) */
+	uint32_t fused_steps;       /* always 0: the one-kernel still step was removed (the word keeps the struct's layout) */
 	uint32_t pair_steps;        /* still steps that started at the SOLVER: the solver lanes of the sub-step before them had evaluated every body's own collider pair for them as well
 	                               (note 9, "pair ahead") -- a step of ONE launch behind a one-workgroup prologue */
 	uint32_t pair_diag[4];      /* why such steps were refused, summed since nh_create: which collider plays "a" could not be told without the next scene frame / the record was not the
@@ -258,7 +258,7 @@ int nh_set_pair_capacity(nh_context* ctx, uint32_t pairs);
    environment.  Names (value 0 / 1 unless noted): "no_still", "no_kept_pairs", "no_incremental", "no_sort_reuse", "sort_classic", "sort_radix", "bucket_tile" (n),
    "bucket_target" (n), "colour_jp", "colour_check_seeds", "no_resident", "solver_waves" (1, 2, 4), "fp_sub" (0, 1, 2, 4, 16), "cooperative", "no_blocks", "blk_check",
    "blk_min" (n), "blk_target" (n), "blk_rows_global", "blk_global_colours", "blk_profile", "no_asleep", "no_blk_chain", "no_local_still", "no_xform_ahead",
-   "no_pair_ahead", "no_sleeper_skip", "no_sleeper_ahead", "no_early_counts", "halo_overlap" (1 = on), "fused_still", "fused_fail_in" (n: test hook), "sync_exports_views".  Unknown name: NH_ERR_INVALID.  Call right after nh_create.
+   "no_pair_ahead", "no_sleeper_skip", "no_sleeper_ahead", "no_early_counts", "halo_overlap" (1 = on), "sync_exports_views".  Unknown name: NH_ERR_INVALID.  Call right after nh_create.
    (nudge_amd/engine.py maps environment variables NH_<NAME> onto these calls for its tests: a convenience of that host, not of the library.) */
 int nh_set_option(nh_context* ctx, const char* name, int value);
 const char* nh_error_string(int code);

@@ -2188,7 +2188,6 @@ static int collide_impl(nh_context* ctx, nh_ActiveBodies* active_bodies, nh_Cont
 		NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->still_delta, sizeof(int2) * 2u * NH_DELTA_MAX));
 		ctx->raw_slots = (uint32_t)slots;
 		ctx->lay_capacity = pair_cap; ctx->lay_contact_capacity = cap; lay_fresh = true;
-		ctx->fused.map_valid = false;
 	}
 	if (ctx->lay_body_capacity < B) {
 		void** bufs[] = { (void**)&ctx->lay_class, (void**)&ctx->lay_simple, (void**)&ctx->body_rec, (void**)&ctx->body_pos };
@@ -2247,28 +2246,16 @@ static int collide_impl(nh_context* ctx, nh_ActiveBodies* active_bodies, nh_Cont
 			// (the step in which the host can no longer rule sleepers out is the one before the first of them falls asleep: what stood still until now was a world awake)
 			if (sleepers && !ss.was_sleepers) ss.sleep_stable = 0u;
 			ss.was_sleepers = sleepers;
-			const bool sleep_stable = sleepers && !ss.no_sleeper_ahead && !ss.no_pair && ss.sleep_stable >= 4u && ss.sleep_backoff == 0u && !ctx->step_hook && ss.pipelined && !ctx->fused.enabled && C <= (2u << 20);
+			const bool sleep_stable = sleepers && !ss.no_sleeper_ahead && !ss.no_pair && ss.sleep_stable >= 4u && ss.sleep_backoff == 0u && !ctx->step_hook && ss.pipelined && C <= (2u << 20);
 			const bool plain = !movers && (!sleepers || sleep_stable) && !ss.appended_pairs && (nbox >= 2 || nsph != 0u);
 			// (sleepers: the whole pair step or the three kernels -- a step that starts at the narrowphase would need its sleepers form there)
 			const bool ahead_step = plain && ss.ahead_ready && !ss.no_ahead && (!sleepers || ss.pair_ready);
 			ss.ahead_ready = false; ss.ahead_plain = plain;
-			// THE ONE-KERNEL STILL STEP (nh_fused.hip): a plain step that starts at the narrowphase, inside nh_step with late verdicts, and is not the call's last -- nothing is
-			// launched here; the solver call launches k_still_fused, which evaluates every kept pair in the lane that solves its body
-			const bool fused = ahead_step && !sleepers && ss.pipelined && ss.more_steps && nh_fused_wanted(ctx, B, C, ss.steps_left);
-			ss.fused = fused;
-			if (movers) ctx->fused.map_valid = false;          // (re-stamped and appended pairs: the position table describes another kept list)
-			if (!fused && ctx->fused.cur != 0u) {
-				// the bodies live in the shadow arrays (an odd run of fused steps) and this step works in place: the run's last verdict first -- a failed step's output
-				// must not be copied over the state it has to be replayed from -- then the bodies go home
-				if (ss.verdict.pending && nh_still_verdict_now(ctx)) return NH_INTERNAL_STILL_FAILED;
-				{ int rc = nh_fused_come_home(ctx); if (rc) return rc; }
-			}
 			// PAIR AHEAD (nh_internal.h): the last step's solver lanes evaluated this step's pairs too -- this step starts at the solver, behind one wave of bookkeeping
-			const bool pair_step = ahead_step && ss.pair_ready && !fused && !ss.no_pair;
+			const bool pair_step = ahead_step && ss.pair_ready && !ss.no_pair;
 			ss.pair_ready = false; ss.pair_step = pair_step; ss.early_verdict = false;
 			if (pair_step) ss.pair_steps++;
 			if (pair_step && sleepers && ss.sleep_run < 0xffffu) ss.sleep_run++;
-			if (!ahead_step) ctx->fused.statics_copied = false;          // (k_xform<true> rewrites the current set of collider buffers, the static world's entries included)
 			if (ahead_step) ss.ahead_steps++;
 			else
 			NH_LAUNCH(ctx, "xform_still", (k_xform<true>), nh_grid_for(C > B ? C : B, 1024, 256), 1024, st, bodies->transforms,
@@ -2332,14 +2319,14 @@ static int collide_impl(nh_context* ctx, nh_ActiveBodies* active_bodies, nh_Cont
 				ss.early_verdict = true;
 			}
 			}
-			else if (!fused) {
+			else {
 			if (nbox >= 2) NH_NARROW_STILL(false, "narrowphase_still", 4096);
 			if (nsph) NH_NARROW_STILL(true, "narrowphase_sph_still", 8192);
 			}
 			// every record's first contact in the dense (tag-ordered) list = the scan of the counts in tag order: kept from step to step, shifted by the listed changes
 			// (the solver keeps the total).  More pairs changing their count than the list holds: a world of up to two million colliders fails the step (a handful change
 			// per million and step at rest); a larger one runs the scan instead -- two launches that leave at once otherwise, nothing next to its step
-			if (delta_scan && !fused) nh_scan_u32(ctx, ctx->cnt_sorted, ctx->start_sorted, &st->records, 1, scan_tmp, nullptr, &st->delta_overflow[ctx->step_parity]);
+			if (delta_scan) nh_scan_u32(ctx, ctx->cnt_sorted, ctx->start_sorted, &st->records, 1, scan_tmp, nullptr, &st->delta_overflow[ctx->step_parity]);
 			ss.active = true; ss.resolved = false; ss.launched++;
 			ctx->gravity_may_overlap = false;
 			ctx->after_collide = true;
@@ -2348,9 +2335,7 @@ static int collide_impl(nh_context* ctx, nh_ActiveBodies* active_bodies, nh_Cont
 	}
 	// a full step.  (nh_step: a still step whose verdict has not been looked at yet must have happened before anything is built on it)
 	if (ctx->still.verdict.pending && nh_still_verdict_now(ctx)) return NH_INTERNAL_STILL_FAILED;
-	ctx->still.fused = false; ctx->fused.map_valid = false; ctx->fused.statics_copied = false;
 	ctx->still.pair_ready = false; ctx->still.pair_step = false; ctx->still.early_verdict = false; ctx->still.pair_world_bad = false; ctx->still.pair_world_ok = false; ctx->still.pair_owned_seq = 0u;          // (another layout: whether every kept pair is some body's own is found out again)
-	{ int rc = nh_fused_come_home(ctx); if (rc) return rc; }          // (every fused step before this one is confirmed: the bodies it left in the shadow arrays go home)
 	// The solver reads the caller's cache arrays and this nh_collide lays the dense contact list out -- whatever still steps kept by slot goes home first
 	{ int rc = nh_still_export_cache(ctx); if (rc) return rc; }
 	ctx->still.ahead_ready = false; ctx->still.ahead_plain = false;

@@ -61,7 +61,6 @@ extern "C" int nh_create(nh_context** out, int device, void* stream, uint32_t fl
 	ctx->still_awake = nullptr; ctx->still_awake_capacity = 0; ctx->exp_sleep_a = nullptr; ctx->exp_sleep_b = nullptr; ctx->exp_sleep_hist = nullptr; ctx->exp_flags = nullptr; ctx->exp_sleep_capacity = 0; ctx->exp_flags_capacity = 0;
 	ctx->lay_class = nullptr; ctx->lay_simple = nullptr; ctx->body_rec = nullptr; ctx->body_pos = nullptr; ctx->lay_body_capacity = 0;
 	memset(&ctx->still, 0, sizeof(ctx->still));
-	memset(&ctx->fused, 0, sizeof(ctx->fused));
 	ctx->step_hook = nullptr; ctx->step_hook_user = nullptr; ctx->halo_ghost_first = 0u;
 	ctx->first_ghost = 0;
 	memset(&ctx->asleep, 0, sizeof(ctx->asleep));
@@ -127,7 +126,6 @@ extern "C" void nh_destroy(nh_context* ctx) {
 	if (ctx->sort_counts) hipFree(ctx->sort_counts);
 	if (ctx->sort_starts) hipFree(ctx->sort_starts);
 	for (int k = 0; k < 2; ++k) { if (ctx->still.h_ring[k]) hipHostFree(ctx->still.h_ring[k]); if (ctx->still.ev_ring[k]) hipEventDestroy(ctx->still.ev_ring[k]); }
-	nh_fused_free(ctx);
 	nh_query_free(ctx);
 	{
 		void* bufs[] = { ctx->raw_data, ctx->raw_feature, ctx->rec, ctx->lay_rank, ctx->cnt_sorted, ctx->start_sorted, ctx->dense_slot, ctx->sc_imp, ctx->sc_feat, ctx->sc_count, ctx->sc_undo, ctx->pair_mark, ctx->pair_list, ctx->exp_cnt, ctx->exp_start,
@@ -171,8 +169,6 @@ extern "C" int nh_set_option(nh_context* ctx, const char* name, int value) {
 	ctx->asleep.streak = 0;
 	if (n == "no_asleep") ctx->asleep.disabled = on;                      // nh_step runs every step of a world that is asleep in full (nh_internal.h: nh_AsleepState)
 	else if (n == "sync_exports_views") ctx->sync_exports_views = on;          // legacy observers: nh_synchronize / nh_read_counts end with nh_export_views(NH_VIEW_ALL) like they did before round 5 (note 9)
-	else if (n == "fused_fail_in") ctx->fused.debug_fail_in = (uint32_t)value;   // TEST HOOK: the value-th fused launch from now raises the failure flag at its very end (rollback exercised on purpose)
-	else if (n == "fused_still") ctx->fused.enabled = on;                      // plain still steps inside nh_step as ONE out-of-place kernel with a look-back (nh_fused.hip): bit-exact, measured SLOWER, off by default
 	else if (n == "no_early_counts") ctx->no_early_counts = on;                // a full step's counters by a copy behind its solver, not by the solver's first thread (nh_internal.h: early counters; A/B, tests)
 	else if (n == "no_sleeper_ahead") ctx->still.no_sleeper_ahead = on;        // a still step in sleepers form always launches its three kernels (nh_internal.h: sleepers ahead; A/B, tests)
 	else if (n == "no_sleeper_skip") ctx->still.no_sleeper_skip = on;          // the sleepers form of a still step does all its work for sleeping bodies too (nh_internal.h; A/B, tests)
@@ -250,7 +246,7 @@ void nh_counts_from_mirror(nh_context* ctx, nh_Counts* out) {
 	out->general_contacts = h->general_contacts; out->levels = h->levels; out->error = h->error;
 	out->still_steps = (uint32_t)(ctx->still.launched - ctx->still.failed - ((ctx->still.active && !ctx->still.resolved) ? 1u : 0u)); out->still_replays = (uint32_t)ctx->still.failed;
 	for (int k = 0; k < 4; ++k) out->still_diff[k] = h->still_diff[k];
-	out->asleep_steps = (uint32_t)ctx->asleep.steps; out->ahead_steps = (uint32_t)ctx->still.ahead_steps; out->fused_steps = (uint32_t)ctx->fused.steps; out->pair_steps = (uint32_t)ctx->still.pair_steps;
+	out->asleep_steps = (uint32_t)ctx->asleep.steps; out->ahead_steps = (uint32_t)ctx->still.ahead_steps; out->fused_steps = 0u; out->pair_steps = (uint32_t)ctx->still.pair_steps;
 	for (int k = 0; k < 4; ++k) out->pair_diag[k] = h->pair_diag[k];
 	out->blk_blocks = h->blk.nblk; out->blk_bodies = h->blk.bodies; out->blk_ghosts = h->blk.ghost_cursor;
 	out->has_other_bodies = h->has_other; out->broadphase_rebuilds = h->fat_rebuilds; out->sort_reuses = h->sort_reuses; out->broadphase_inserts = h->fat_inserts; out->unleveled = h->unleveled; out->raw_pairs = h->pairs + h->pairs_sph;

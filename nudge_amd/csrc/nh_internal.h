@@ -208,25 +208,6 @@ struct nh_BlkBuffers {
 // three kernels (k_xform<true>, k_narrowphase<*, true>, the solver reading and writing the cache in place); they CHECK what they rely on (nobody left its
 // inflated box or is asleep; every record has the key, contact count and feature words it had; body 0 inert) and raise st->still_fail otherwise -- after which
 // each of them leaves without having changed anything that matters, and the host, which learns of it with the step's one round trip, replays the step in full.
-// THE ONE-KERNEL STILL STEP (round 6; nh_fused.hip).  A plain still step that starts at the narrowphase (xform ahead) and is not the last sub-step of its nh_step call
-// is ONE launch: the lane that solves a body evaluates the body's one kept pair itself and keeps the contacts on chip.  The kernel reads body state, slot cache and
-// collider transforms from one set of buffers and writes the other (a check that fails in one wave must find the world as it was, although other waves have long
-// advanced their bodies): `cur` says where the BODY state lives -- 0: the caller's arrays, 1: the shadow arrays below -- while the library-owned buffers simply
-// change names with their twins (ctx->sc_* / own_* always name the current ones).  Fused steps come in pairs, so a call ends in the caller's arrays.
-struct nh_FusedState {
-	bool enabled;                   // option "fused_still" (OFF by default: measured slower than the two launches it replaces -- nh_fused.hip)
-	uint32_t debug_fail_in;         // option "fused_fail_in" (tests): the n-th fused launch from now fails itself after its waves have written
-	uint32_t cur;                   // which set holds the body state
-	uint32_t unconfirmed;           // fused launches whose verdict the host has not seen (each changed the sets over: a failure changes them back)
-	uint64_t steps, homecomings;    // statistics: fused steps that happened; copies of the shadow arrays back into the caller's outside the pairing
-	unsigned long long* seg; uint32_t seg_words; bool seg_clean[2];          // segment sums of the look-back, by step parity (nh_fused.hip)
-	uint4* fz; unsigned long long* status; bool map_valid; uint32_t map_records;      // per tag-order position: record, body, colliders (k_fused_map); the look-back words
-	bool statics_copied;            // the static world's collider transforms / boxes are in both sets (since the last k_xform<true>)
-	float4* sc_imp_alt; uint32_t* sc_feat_alt; uint32_t* sc_count_alt; uint32_t pair_capacity;
-	struct nh_xform* own_xf_alt; float4* own_aabb_min_alt; float4* own_aabb_max_alt; uint32_t collider_capacity;
-	nh_Transform* shadow_xf; nh_BodyMomentum* shadow_mom; uint8_t* shadow_idle; uint32_t body_capacity;
-};
-
 struct nh_StillStep {
 	bool disabled;                  // nh option / NH_NO_STILL=1: never launch a step speculatively (A/B, tests)
 	bool ok_next;                   // the last step left a layout, body classes and a cache that a still step may rely on (decided at its round trip / end)
@@ -268,8 +249,6 @@ struct nh_StillStep {
 	bool pair_world_bad;            // a round trip showed more such pairs than the list holds: not offered until the next full step
 	bool pair_world_ok;             // ... a round trip showed the list complete (for the layout it was made from): only then are the lanes asked to evaluate their pairs
 	uint64_t pair_steps;            // statistics: still steps that were ONE solver launch (+ its one-workgroup prologue)
-	bool fused;                     // the still step being launched is a fused one (nh_FusedState): nh_collide launched nothing, the solver call launches k_still_fused
-	bool verdict_fused;             // ... and so was the step whose verdict is pending
 	uint32_t steps_left;            // nh_step: sub-steps of this call behind the one being launched
 	uint32_t confirmed_seq;         // collide_seq of the newest still step whose verdict was "confirmed" (every drop noted in ctx->sc_undo under a later number is undone on failure)
 	bool undo_dirty;                // a narrowphase in sleepers form has run since sc_undo was last swept
@@ -475,7 +454,6 @@ struct nh_context {
 	// per body (k_adj_simple): class, contact-list record of the full path; the record a body's contacts come from (| NH_BODY_REC_IS_A) and its tag-order position
 	uint8_t* lay_class; uint2* lay_simple; uint32_t* body_rec; uint32_t* body_pos; uint32_t lay_body_capacity;
 	nh_StillStep still;
-	nh_FusedState fused;
 	// nh_partition_step (nh_partition.hip): K sub-steps of a slab in one nh_step call -- before every sub-step's nh_collide the library calls the hook, which enqueues the
 	// per-step halo exchange (and, for a step that starts further down the chain, the ghosts' transforms); halo_ghost_first: the first ghost body while such a call runs
 	int (*step_hook)(nh_context* ctx, void* user, uint32_t sub_step); void* step_hook_user; uint32_t halo_ghost_first;
@@ -504,12 +482,6 @@ int nh_still_abandon(nh_context* ctx);
 int nh_still_sync_outputs(nh_context* ctx, uint32_t what = 7u /* NH_VIEW_ALL */);
 int nh_still_export_cache(nh_context* ctx);
 int nh_still_undo_drops(nh_context* ctx);
-// nh_fused.hip
-bool nh_fused_wanted(nh_context* ctx, uint32_t B, uint32_t C, uint32_t steps_left);
-int nh_fused_launch(nh_context* ctx, const nh_BodyData* bodies, uint32_t iterations, uint32_t guard_seq);
-int nh_fused_come_home(nh_context* ctx);
-void nh_fused_void_last(nh_context* ctx, uint32_t launches);
-void nh_fused_free(nh_context* ctx);
 void nh_stream_void_advance(nh_context* ctx);
 int nh_still_verdict_now(nh_context* ctx);            // nh_step: the pending verdict of the last still step, waited for: 0 = it happened, 1 = it did not
 #define NH_INTERNAL_STILL_FAILED (-1000)      // (never leaves the library) first_apply -> nh_step: the still step before this one failed, run both again

@@ -3094,8 +3094,8 @@ static int first_apply(nh_context* ctx, nh_ContactConstraintData* d, const nh_Bo
 			fs.gx_dt = ctx->grav.gx_dt; fs.gy_dt = ctx->grav.gy_dt; fs.gz_dt = ctx->grav.gz_dt; fs.damping = ctx->grav.damping; fs.time_step = ctx->grav.time_step;
 			fs.bits = 3u | (ss.sleepers ? 4u : 0u) | ((ss.sleepers && !ss.no_sleeper_skip) ? 8u : 0u); fs.idle = bodies->idle_counters; fs.seq = ctx->collide_seq;          // (bit 3: waves of sleeping bodies leave at once)
 			fs.ghost_first = ctx->halo_ghost_first;
-			// (late verdicts: the solver's first thread writes the step's counters into the pinned ring slot itself -- not the fused look-back kernel, which keeps the copy)
-			const bool self_report = ss.pipelined && ss.h_ring[0] && !ss.fused;
+			// (late verdicts: the solver's first thread writes the step's counters into the pinned ring slot itself)
+			const bool self_report = ss.pipelined && ss.h_ring[0];
 			fs.host_counters = self_report ? reinterpret_cast<uint32_t*>(ss.h_ring[ctx->collide_seq & 1u]) : nullptr;
 			fs.guard_seq = ss.verdict.pending ? ss.verdict.seq : ctx->collide_seq;          // (a solver behind an unconfirmed still step leaves when THAT one failed)
 #define NH_SOLVE_STILL(NWAVES) NH_LAUNCH(ctx, "solve_still", (k_solve_one_body<4, true, true, NWAVES, true>), (B + 64u * NWAVES - 1u) / (64u * NWAVES), 64 * NWAVES, B, d->body_class, d->body_off, d->adj, d->bodies, bodies->properties, bodies->momentum, \
@@ -3106,12 +3106,8 @@ static int first_apply(nh_context* ctx, nh_ContactConstraintData* d, const nh_Bo
 			const bool ahead = ss.ahead_plain && ss.more_steps && ss.ahead_map_ok && !ss.no_ahead && !ss.ahead_world_bad && ctx->env_solver_waves != 4 && ctx->env_solver_waves != 2 &&
 			                   ctx->own_xf && ctx->body_col && ctx->body_col_capacity >= B;
 			// PAIR AHEAD (nh_internal.h): ... and the next sub-step's narrowphase for the body's own pair -- that sub-step then starts at the solver
-			const bool pair = ahead && !ss.fused && !ss.no_pair && !ss.pair_world_bad && ss.pair_owned_seq != 0u && ctx->pair_list && ctx->fat_pairs && ctx->own_ctag && !(cd_count_over(ss.colliders));
-			if (ss.fused) {
-				// ONE launch for the whole step (nh_fused.hip): pair evaluation, solver, advance and the next sub-step's transforms
-				int rc = nh_fused_launch(ctx, bodies, iterations, fs.guard_seq);
-				if (rc) return rc;
-			} else if (ahead) {
+			const bool pair = ahead && !ss.no_pair && !ss.pair_world_bad && ss.pair_owned_seq != 0u && ctx->pair_list && ctx->fat_pairs && ctx->own_ctag && !(cd_count_over(ss.colliders));
+			if (ahead) {
 				const nh_ColliderData& cd = ss.colliders;
 				const uint32_t C = cd.boxes.count + cd.spheres.count;
 				const uint8_t* gen = (C < (1u << NH_GEN_SHIFT) && !ctx->env_no_incremental) ? ctx->fat_gen : (const uint8_t*)nullptr;
@@ -3140,8 +3136,8 @@ static int first_apply(nh_context* ctx, nh_ContactConstraintData* d, const nh_Bo
 				          (float4*)d->states, iterations, ctx->raw_data, bodies->transforms, d->impulses, cv, ctx->hint, NH_CLS_STATIC4, NH_CLS_STATIC4, 2u, d->simple, fs, sv, av);
 			} else
 			if (ctx->env_solver_waves == 4) NH_SOLVE_STILL(4); else if (ctx->env_solver_waves == 2) NH_SOLVE_STILL(2); else NH_SOLVE_STILL(1);
-			ss.ahead_ready = ahead || ss.fused;
-			ss.pair_ready = pair && !ss.fused;
+			ss.ahead_ready = ahead;
+			ss.pair_ready = pair;
 			if (ss.pipelined && ss.h_ring[0]) {
 				// nh_step: first the verdict of the still step BEFORE this one (its counters landed long ago) ...
 				if (ss.verdict.pending) {
@@ -3149,7 +3145,6 @@ static int first_apply(nh_context* ctx, nh_ContactConstraintData* d, const nh_Bo
 					const nh_DevState* h = ss.h_ring[ss.verdict.slot];
 					if (h->still_failed_seq >= ss.verdict.seq || h->error) return NH_INTERNAL_STILL_FAILED;       // (nh_step cleans up and runs both steps again)
 					ss.confirmed_seq = ss.verdict.seq;
-					if (ss.verdict_fused && ctx->fused.unconfirmed) ctx->fused.unconfirmed--;
 					memcpy(ctx->h_state, h, NH_COUNTER_WORDS * sizeof(uint32_t));
 					if (!ctx->idle_unknown) { ctx->idle_bound = (int)h->max_idle[ss.verdict.parity]; ctx->idle_bound_mark = ss.verdict.collide_mark; }
 					ss.verdict.pending = false;
@@ -3161,7 +3156,6 @@ static int first_apply(nh_context* ctx, nh_ContactConstraintData* d, const nh_Bo
 				NH_HIP_CHECK(ctx, hipEventRecord(ss.ev_ring[slot], ctx->stream));
 				ss.verdict.pending = true; ss.verdict.seq = ctx->collide_seq; ss.verdict.parity = ctx->step_parity; ss.verdict.slot = slot; ss.verdict.collide_mark = ctx->collide_mark;
 				ss.verdict.self_report = self_report && !ctx->halo_split.launched;
-				ss.verdict_fused = ss.fused;
 				confirmed = true;          // (until the next step says otherwise)
 			} else if (ss.early_verdict) {
 				// nh_partition_step, a step that started at the solver: everything such a step can fail on is checked by its PROLOGUE (k_pair_begin: the step-wide words,
@@ -3613,7 +3607,6 @@ int nh_still_verdict_now(nh_context* ctx) {
 	ss.verdict.pending = false;
 	if (h->still_failed_seq >= ss.verdict.seq || h->error) return 1;
 	ss.confirmed_seq = ss.verdict.seq;
-	if (ss.verdict_fused && ctx->fused.unconfirmed) ctx->fused.unconfirmed--;
 	memcpy(ctx->h_state, h, NH_COUNTER_WORDS * sizeof(uint32_t));
 	if (!ctx->idle_unknown) { ctx->idle_bound = (int)h->max_idle[ss.verdict.parity]; ctx->idle_bound_mark = ss.verdict.collide_mark; }
 	still_note_movers(ctx, h, ss.verdict.seq);
@@ -3637,11 +3630,6 @@ static int still_forget_failed(nh_context* ctx, bool advanced, uint32_t voided) 
 	ctx->grav.pending = false; ctx->grav.rest_pending = false; ctx->adv.done = false;
 	ctx->after_collide = false; ctx->gravity_may_overlap = false;
 	if (advanced && ctx->advance_count) ctx->advance_count--;          // (the failed step's nh_advance was counted: the sleep prediction counts real ones)
-	// fused launches among the voided steps (nh_fused.hip) wrote into the OTHER set of buffers: the sets change back, and if the state they were given lives in the
-	// shadow arrays it goes home -- the replay is a full step, in place
-	nh_fused_void_last(ctx, ctx->fused.unconfirmed);
-	ss.fused = false; ss.verdict_fused = false;
-	{ int rc = nh_fused_come_home(ctx); if (rc) return rc; }
 	if (advanced) nh_stream_void_advance(ctx);          // (... and so does the state stream; a frame taken at that nh_advance shows the state BEFORE the step: it is withdrawn)
 	{ int rc = nh_still_undo_drops(ctx); if (rc) return rc; }          // (sleepers form: slot-cache counts the voided steps' narrowphases dropped)
 	return nh_still_export_cache(ctx);                                 // (the slot cache holds the last step that DID happen: the full solver reads the caller's arrays)
@@ -3724,10 +3712,7 @@ extern "C" int nh_step(nh_context* ctx, const nh_StepArgs* a, uint32_t steps) {
 		    (rc = nh_advance(ctx, a->active_bodies, a->bodies, a->time_step))) { result = rc; break; }
 		++i;
 	}
-	ss.pipelined = false; ss.more_steps = false; ss.ahead_ready = false; ss.ahead_map_ok = false; ss.steps_left = 0u; ss.fused = false; ss.substep = 0u;
+	ss.pipelined = false; ss.more_steps = false; ss.ahead_ready = false; ss.ahead_map_ok = false; ss.steps_left = 0u; ss.substep = 0u;
 	if (result && ss.verdict.pending) { hipEventSynchronize(ss.ev_ring[ss.verdict.slot]); ss.verdict.pending = false; }
-	// (fused steps are launched in pairs and every verdict of the call is in: the bodies are in the caller's arrays -- unless the call ends in an error)
-	if (ctx->fused.cur != 0u) { ctx->fused.unconfirmed = 0u; int rc = nh_fused_come_home(ctx); if (rc && !result) result = rc; }
-	ctx->fused.unconfirmed = 0u;
 	return result;
 }

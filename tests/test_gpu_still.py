@@ -860,67 +860,12 @@ def test_pair_ahead_with_kept_pairs_that_are_nobodys():
     a.close(); b.close(); c.close()
 
 
-# ---- the one-kernel still step with a look-back (nudge_amd/csrc/nh_fused.hip; option "fused_still", off by default: bit-exact but measured slower) -------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("sphere_fraction", [0.0, 0.5])
-def test_fused_still_steps_leave_the_bits_of_the_two_kernel_form(sphere_fraction):
-    """Inside an nh_step call a plain still step that starts at the narrowphase and is not the call's last is ONE launch: the lane that solves a body evaluates the body's
-    kept pair itself, the contacts never reach HBM, the dense contact indices travel from wave to wave by a look-back, and body state / slot cache / collider buffers are
-    written out of place (nh_fused.hip).  Against the same library with the option off and against the one that never speculates, checkpoint by checkpoint: calls of
-    every length (one and two sub-steps: never fused; three: never -- pairs; four and more: fused), through rest, a hop and a shove, and falling asleep."""
-    scene = S.grid_tiles(2, side=36, sphere_fraction=sphere_fraction, seed=57, lattice_cols=2)
-    a, b, c = _world(scene, True, env=["NH_FUSED_STILL"]), _world(scene, True), _world(scene, False)
-    done = 0
-    for cp in (90, 91, 93, 96, 100, 105, 111, 118, 126, 160, 161, 163, 200):
-        for w in (a, b, c):
-            w.step(cp - done)
-        done = cp
-        _same_world(a, b, f"step {cp} (fused vs two kernels)"); _same_world(a, c, f"step {cp} (fused vs never speculating)")
-    c0 = a.counts()
-    assert c0["fused_steps"] >= 40 and c0["fused_steps"] % 2 == 0, c0
-    assert b.counts()["fused_steps"] == 0 and b.counts()["ahead_steps"] >= 40
-    for w in (a, b, c):
-        m = w.get_bodies()["momentum"]
-        m["velocity"][7::89, 1] = 3.0
-        m["velocity"][13::101, 2] = 1.0
-        w.set_bodies(momentum=m)
-    for cp in (240, 300, 370, 460, 560):
-        for w in (a, b, c):
-            w.step(cp - done)
-        done = cp
-        _same_world(a, b, f"step {cp} (fused vs two kernels)"); _same_world(a, c, f"step {cp} (fused vs never speculating)")
-    c1 = a.counts()
-    print(f"\n[fused, spheres {sphere_fraction}] {c1['fused_steps']} fused of {c1['ahead_steps']} ahead of {c1['still_steps']} still steps; replays {c1['still_replays']} (two kernels: {b.counts()['still_replays']})")
-    assert c1["error"] == 0 and c1["fused_steps"] > c0["fused_steps"], (c0, c1)
-    a.close(); b.close(); c.close()
-
-
-@pytest.mark.parametrize("fail_in", [1, 2, 5, 6])
-def test_a_fused_step_that_fails_after_its_waves_have_written_is_run_again_from_the_state_it_was_given(fail_in):
-    """The reason the fused kernel writes out of place: a wave may raise the failure flag when others have long advanced their bodies.  The test hook "fused_fail_in"
-    makes the n-th fused launch do exactly that at the very end of one of its middle waves -- with the state it was given in the caller's arrays (odd n) and in the
-    shadow arrays (even n).  The step and the one launched behind it are run again; every bit is the library's that never speculates."""
-    scene = S.grid_tiles(1, side=40, sphere_fraction=0.5, seed=59)
-    a, c = _world(scene, True, env=["NH_FUSED_STILL"]), _world(scene, False)
-    a.step(100); c.step(100)
-    _same_world(a, c, "at rest")
-    c0 = a.counts()
-    a.set_option("fused_fail_in", fail_in)
-    a.step(14); c.step(14)
-    _same_world(a, c, f"fused launch {fail_in} failed on purpose")
-    c1 = a.counts()
-    assert c1["still_replays"] > c0["still_replays"] and c1["fused_steps"] > c0["fused_steps"], (c0, c1)
-    a.step(40); c.step(40)
-    _same_world(a, c, "and on")
-    c2 = a.counts()
-    assert c2["error"] == 0 and c2["fused_steps"] > c1["fused_steps"]
-    a.close(); c.close()
-
-
-def test_two_dynamic_bodies_that_come_to_touch_inside_their_boxes_fail_a_fused_step_cleanly():
+# ---- a still step that meets two dynamic bodies touching (nudge_amd/csrc/nh_internal.h: nh_StillStep) --------------------------------------------------------------
+def test_two_dynamic_bodies_that_come_to_touch_inside_their_boxes_fail_a_still_step_cleanly():
     """A sphere creeping towards its neighbour inside its inflated box: the kept pair of the two dynamic bodies is a record nobody's lane owns, and the step in which it
     first yields a contact must fail -- in whatever form it is launched -- and be run again in full.  Bits of the library that never speculates throughout."""
     scene = S.grid_tiles(1, side=16, sphere_fraction=0.5, seed=61)
-    a, c = _world(scene, True, env=["NH_FUSED_STILL"]), _world(scene, False)
+    a, c = _world(scene, True), _world(scene, False)
     a.step(150); c.step(150)
     sph_body = scene["sphere_transforms"]["body"]
     rad = scene["sphere_data"]["radius"]
@@ -950,5 +895,5 @@ def test_two_dynamic_bodies_that_come_to_touch_inside_their_boxes_fail_a_fused_s
         a.step(cp - done); c.step(cp - done); done = cp
         _same_world(a, c, f"A rolls into B, step {cp}")
     c1 = a.counts()
-    print(f"\n[touching] fused {c1['fused_steps'] - c0['fused_steps']}, still {c1['still_steps'] - c0['still_steps']}, replays {c1['still_replays'] - c0['still_replays']}, general contacts now {c1['general_contacts']}")
+    print(f"\n[touching] pair {c1['pair_steps'] - c0['pair_steps']}, ahead {c1['ahead_steps'] - c0['ahead_steps']}, still {c1['still_steps'] - c0['still_steps']}, replays {c1['still_replays'] - c0['still_replays']}, general contacts now {c1['general_contacts']}")
     a.close(); c.close()
