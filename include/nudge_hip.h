@@ -79,7 +79,7 @@
  *      exported the views: nh_set_option(ctx, "sync_exports_views", 1) restores that contract at its old price; INTEGRATION.md.)  Any entry point outside the sample's
  *      call order between nh_collide and nh_apply_impulses turns a still step into a full one first, so everything it observes is what a full step
  *      produces.  nh_Counts.still_steps / still_replays count them.
- *      The scene queries (nh_query_build, nh_raycast, nh_overlap) are not entry points of the step in this sense: they neither export nor settle nor turn a still step into a
+ *      The scene queries (nh_query_build, nh_raycast, nh_spherecast, nh_overlap) are not entry points of the step in this sense: they neither export nor settle nor turn a still step into a
  *      full one, and they do not count -- see "scene queries" below.
  *
  * Threading: one context = one HIP stream = one world at a time; no global mutable state.
@@ -349,7 +349,7 @@ typedef struct nh_StreamInfo { uint32_t slot; uint32_t valid; uint64_t step; uin
 int nh_stream_state(nh_context* ctx, const nh_BodyData* bodies, uint32_t count, void* host_ring, uint32_t slots, uint32_t every);
 int nh_stream_latest(nh_context* ctx, nh_StreamInfo* out);
 
-/* ---- scene queries: ray casts and overlaps against the device-resident world -------------------------------------------------------------------------------
+/* ---- scene queries: ray casts, sphere casts and overlaps against the device-resident world -----------------------------------------------------------------
    nh_query_build snapshots the world transforms and AABBs of ALL box and sphere colliders -- those of sleeping bodies and of body 0 (the static world) included -- and
    builds a bounding-volume hierarchy over them (a linear BVH: Morton keys, a radix tree, bottom-up boxes) into buffers the library owns: they grow with the collider
    count (~250 B per collider) and are freed by nh_destroy.  nh_raycast answers `count` rays (nh_overlap, below, `count` shapes) against the LAST build: the hierarchy does not follow the bodies, so
@@ -369,13 +369,33 @@ int nh_stream_latest(nh_context* ctx, nh_StreamInfo* out);
    entry points, or between two nh_step calls, they leave every later step bit-identical, with the same still_steps / still_replays / ahead_steps / pair_steps /
    asleep_steps.  They read bodies->transforms as the stream has them at that point: under NH_FLAG_FUSED_STEP the fused solver advances part of the bodies inside
    nh_apply_impulses, so a build between nh_apply_impulses and nh_advance sees a world half advanced -- build after nh_advance (or nh_step) for a consistent one.
-   Not built: sweep queries (sphere casts), queries on a partitioned world (nh_partition_*), an incremental refit across steps. */
+   Not built: queries on a partitioned world (nh_partition_*), an incremental refit across steps. */
 typedef struct nh_Ray { float origin[3]; float max_t; float direction[3]; uint32_t ignore_body; } nh_Ray;                                            /* 32 B */
 typedef struct nh_RayHit { float t; float normal[3]; uint32_t body; uint32_t collider; uint32_t shape; uint32_t tag; } nh_RayHit;                     /* 32 B */
 enum { NH_SHAPE_BOX = 0u, NH_SHAPE_SPHERE = 1u, NH_SHAPE_NONE = 0xffffffffu };    /* nh_RayHit.shape; NONE = miss */
 enum { NH_RAY_ANY_HIT = 1u };
 int nh_query_build(nh_context* ctx, const nh_BodyData* bodies, const nh_ColliderData* colliders);
 int nh_raycast(nh_context* ctx, const nh_Ray* rays, uint32_t count, nh_RayHit* hits, uint32_t flags);
+
+/* nh_spherecast: where a swept ball first touches the world of the LAST nh_query_build -- character controllers, thick projectiles, camera collision.
+   nh_SphereCast's first 32 bytes are nh_Ray's fields at the same offsets; `reserved` is not read.  Exact predicates: nudge_amd/csrc/nh_query.h.
+     - the swept ball is the ball of radius r = `radius` centred at o + t d, for 0 <= t <= max_t; t is in units of d, as for rays;
+     - the hit on one collider is the smallest such t at which the ball touches it (touching counts, as in nh_overlap); the normal is a unit vector from
+       the collider towards the ball's centre at t, so the contact point is o + t d - r * normal;
+     - START OVERLAP: a ball that overlaps a collider at t = 0 under nh_overlap's own predicates (nh_q_overlap_sphere_sphere / nh_q_overlap_sphere_box) hits
+       it at t = 0 with normal = -d / |d|, the ray's inside rule;
+     - over all colliders the answer follows nh_raycast: the closest hit, ties by (shape, collider index), `ignore_body`, NH_RAY_ANY_HIT, and a miss written
+       exactly as a ray miss (shape = NH_SHAPE_NONE, t = max_t, normal = 0, body = collider = tag = 0xffffffff);
+     - r = 0 IS A RAY: it writes the same bytes as nh_raycast with the same first 32 bytes.  A zero direction does what it does for a ray: a ball that
+       touches at t = 0 hits there with a NaN normal (-d / |d| = 0 / 0), any other cast misses;
+     - for r > 0 a hit also needs the ray to enter the collider's box in the hierarchy grown by r, and t is at least that entry (the reach rule, DESIGN 10.2:
+       it is what lets the walk prune exactly; it moves t only where the predicate's rounding put the hit in front of a padded box);
+     - a cast with a non-finite origin, direction or radius, or a negative radius, is written as a miss with t = NaN.
+   Returns NH_ERR_INVALID before any nh_query_build, for flags other than 0 or NH_RAY_ANY_HIT, and for null or not 16-byte aligned `casts` / `hits`;
+   count = 0 is a no-op that returns NH_OK.  An OBSERVER like nh_raycast (note 9): no view export, no settling of deferred gravity, no still step turned
+   into a full one, no change to nh_Counts. */
+typedef struct nh_SphereCast { float origin[3]; float max_t; float direction[3]; uint32_t ignore_body; float radius; uint32_t reserved[3]; } nh_SphereCast;  /* 48 B */
+int nh_spherecast(nh_context* ctx, const nh_SphereCast* casts, uint32_t count, nh_RayHit* hits, uint32_t flags /* 0 or NH_RAY_ANY_HIT */);
 
 /* nh_overlap: which colliders of the LAST nh_query_build touch each of `count` query shapes -- explosion radii, trigger volumes, "is this spot free".
    Query shapes (nh_OverlapQuery):

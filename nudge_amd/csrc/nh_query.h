@@ -1,9 +1,10 @@
-// nh_query.h -- per-item arithmetic of the scene query (nh_query_build / nh_raycast / nh_overlap, nh_query.hip): a collider's world pose, a ray
-// against one box and against one sphere, and the overlap predicates of a query sphere or box against one collider.
+// nh_query.h -- per-item arithmetic of the scene query (nh_query_build / nh_raycast / nh_spherecast / nh_overlap, nh_query.hip): a collider's world
+// pose, a ray against one box and against one sphere, the overlap predicates of a query sphere or box against one collider, and a swept ball against
+// one box and one sphere with the walk's node test it is pruned by.
 //
-// Every function is `NH_HD` so that tests/hostquery builds the SAME arithmetic with g++ -ffp-contract=off and gets the device's bits: the
+// Every function is `NH_HD` so that tests/hostquery (hostoverlap, hostsweep) builds the SAME arithmetic with g++ -ffp-contract=off and gets the device's bits: the
 // brute force over all colliders there is the oracle of the GPU's tree traversal.  Only + - * /, sqrtf (correctly rounded on both sides)
-// and sign / absolute-value bit operations are used.
+// and sign / absolute-value bit operations are used (and fminf / fmaxf in the pads and the walk's node test, which agree on both sides).
 //
 // Exact semantics (include/nudge_hip.h, "scene queries"):
 //   box     (size = half extents, as in the narrowphase): the ray is brought into the box frame by the inverse rotation, then a slab test.
@@ -95,6 +96,13 @@ NH_HD nh_QHit nh_q_ray_sphere(nh_f3 o, nh_f3 d, nh_f3 c, float rad) {
 	return r;
 }
 
+// Conservative box of a leaf (k_q_refit): a relative pad of 2^-18 of its largest coordinate, so that no rounding of the walk's slab tests can cut off a
+// collider the exact test hits (the cast side adds the same of its origin, k_q_raycast / k_q_spherecast)
+NH_HD float nh_q_pad(nh_f3 mn, nh_f3 mx) {
+	const float m = fmaxf(fmaxf(fmaxf(fabsf(mn.x), fabsf(mn.y)), fmaxf(fabsf(mn.z), fabsf(mx.x))), fmaxf(fabsf(mx.y), fabsf(mx.z)));
+	return m * 3.814697265625e-06f + 1e-30f;
+}
+
 // Does (t, c) beat the best hit so far (bt, bc)?  bc = 0xffffffff: none yet.  Counting needs 0 <= t <= max_t.
 NH_HD bool nh_q_better(float t, uint32_t c, float max_t, float bt, uint32_t bc) {
 	if (!(t >= 0.0f && t <= max_t)) return false;
@@ -167,5 +175,128 @@ NH_HD bool nh_q_overlap_box_box(nh_f3 ca, nh_quat qa, nh_f3 ha, nh_f3 cb, nh_qua
 	ok = ok && nh_abs(t1 * R02 - t0 * R12) <= (a0 * E12 + a1 * E02) + (b0 * E21 + b1 * E20);
 	return ok;
 }
+
+// ---- sphere casts (nh_spherecast): the first t at which the ball of radius r centred at o + t d touches a collider --------------------------------
+// The hit is that of the ray against the collider grown by r (its Minkowski sum with the ball): the normal points from the collider to the centre.
+// A ball that touches at t = 0 under nh_overlap's predicates hits at t = 0 with the ray's inside normal -d / |d|.  r = 0 is a ray cast, bit for bit.
+
+// First entry t >= 0 of the ray (o, d) into the ball of centre c, radius r; INFINITY when there is none.  The closest-approach form (Hearn & Baker; Haines
+// et al., "Precision Improvements for Ray / Sphere Intersection", Ray Tracing Gems 7): disc = r^2 - |m + t_m d|^2 with t_m = -m.d / d.d, so that a grazing
+// ray keeps its accuracy when m is much longer than r.  An origin inside the ball (by rounding: callers have ruled out a real start overlap) gives t = 0.
+NH_HD float nh_q_ball_entry(nh_f3 o, nh_f3 d, nh_f3 c, float r) {
+	const nh_f3 m = o - c;
+	const float a = nh_dot(d, d);
+	if (!(a > 0.0f)) return INFINITY;
+	const float tm = nh_neg(nh_dot(m, d)) / a;
+	const nh_f3 l = m + tm * d;
+	const float q = r * r - nh_dot(l, l);
+	if (!(q >= 0.0f)) return INFINITY;
+	const float dt = sqrtf(q / a);
+	if (!(tm + dt >= 0.0f)) return INFINITY;
+	const float t = tm - dt;
+	return t > 0.0f ? t : 0.0f;
+}
+
+// First entry t >= 0 of a ray in a box frame into the capsule of radius r around the box edge parallel to axis k through (ci, cj) on the other two axes
+// i, j, from -hk to +hk on k: the least of its side (the infinite cylinder's entry, if it lies within [-hk, hk]) and its two end balls (a ray that enters
+// the finite cylinder through an end disc is inside that end's ball already).  INFINITY when there is none.
+NH_HD float nh_q_capsule_entry(float oi, float oj, float ok, float di, float dj, float dk, float ci, float cj, float hk, float r) {
+	float t = INFINITY;
+	const float mi = oi - ci, mj = oj - cj;
+	const float a = di * di + dj * dj;
+	if (a > 0.0f) {
+		const float tm = nh_neg(mi * di + mj * dj) / a;
+		const float li = mi + tm * di, lj = mj + tm * dj;
+		const float q = r * r - (li * li + lj * lj);
+		if (q >= 0.0f) {
+			const float dt = sqrtf(q / a);
+			if (tm + dt >= 0.0f) {
+				const float ts = tm - dt > 0.0f ? tm - dt : 0.0f;
+				const float xk = ok + ts * dk;
+				if (nh_abs(xk) <= hk) t = ts;
+			}
+		}
+	}
+	const nh_f3 o3 = nh_make3(oi, oj, ok), d3 = nh_make3(di, dj, dk);
+	const float t0 = nh_q_ball_entry(o3, d3, nh_make3(ci, cj, nh_neg(hk)), r), t1 = nh_q_ball_entry(o3, d3, nh_make3(ci, cj, hk), r);
+	t = t0 < t ? t0 : t;
+	return t1 < t ? t1 : t;
+}
+
+// The ball (o + t d, r) against the box of world pose (p, q) and half extents h (Ericson, Real-Time Collision Detection 5.5.7).  In the box frame
+// (nh_q_ray_box's): the start overlap by nh_q_overlap_sphere_box; otherwise the ray's entry into the box grown by r on every side (nh_q_slab with h + r,
+// from t = 0 on) is classified by the coordinates that lie beyond +-h: none or one -- a face region, and that entry is the hit, the entering slab's axis
+// the normal; two -- an edge region, the hit is on that edge's capsule or nowhere; three -- a vertex region, the least hit on its three capsules.  An edge
+// or vertex hit's normal is the hit centre minus its closest point on the box (its clamp to [-h, h]), normalised.  r = 0: nh_q_ray_box itself.
+NH_HD nh_QHit nh_q_sweep_box(nh_f3 o, nh_f3 d, float r, nh_f3 p, nh_quat q, nh_f3 h) {
+	if (r == 0.0f) return nh_q_ray_box(o, d, p, q, h);
+	if (nh_q_overlap_sphere_box(o, r, p, q, h)) return nh_q_inside(d);
+	nh_QHit res; res.t = 0.0f; res.n = nh_make3(0.0f, 0.0f, 0.0f); res.hit = false;
+	const nh_quat qi = { nh_neg(q.x), nh_neg(q.y), nh_neg(q.z), q.s };
+	const nh_f3 ol = nh_rotate(qi, o - p), dl = nh_rotate(qi, d);
+	float t0 = -INFINITY, t1 = INFINITY;
+	int enter = -1;
+	bool all = true;
+	nh_q_slab(ol.x, dl.x, h.x + r, 0, t0, t1, enter, all);
+	nh_q_slab(ol.y, dl.y, h.y + r, 1, t0, t1, enter, all);
+	nh_q_slab(ol.z, dl.z, h.z + r, 2, t0, t1, enter, all);
+	if (!all || enter < 0 || !(t0 <= t1) || !(t1 >= 0.0f)) return res;
+	const float tc = t0 > 0.0f ? t0 : 0.0f;
+	const nh_f3 e = ol + tc * dl;
+	const float sx = e.x < nh_neg(h.x) ? -1.0f : e.x > h.x ? 1.0f : 0.0f;
+	const float sy = e.y < nh_neg(h.y) ? -1.0f : e.y > h.y ? 1.0f : 0.0f;
+	const float sz = e.z < nh_neg(h.z) ? -1.0f : e.z > h.z ? 1.0f : 0.0f;
+	const int beyond = (sx != 0.0f) + (sy != 0.0f) + (sz != 0.0f);
+	if (beyond <= 1) {
+		// (an origin inside the grown box in a face region is within r of the box: a start overlap that rounding kept from the test above)
+		if (!(t0 > 0.0f)) return nh_q_inside(d);
+		const float dk = enter == 0 ? dl.x : enter == 1 ? dl.y : dl.z;
+		const float s = dk > 0.0f ? -1.0f : 1.0f;
+		res.t = t0; res.n = nh_rotate(q, nh_make3(enter == 0 ? s : 0.0f, enter == 1 ? s : 0.0f, enter == 2 ? s : 0.0f)); res.hit = true;
+		return res;
+	}
+	float t = INFINITY;
+	if (sx != 0.0f && sy != 0.0f) t = nh_q_capsule_entry(ol.x, ol.y, ol.z, dl.x, dl.y, dl.z, sx * h.x, sy * h.y, h.z, r);
+	if (sx != 0.0f && sz != 0.0f) { const float u = nh_q_capsule_entry(ol.z, ol.x, ol.y, dl.z, dl.x, dl.y, sz * h.z, sx * h.x, h.y, r); t = u < t ? u : t; }
+	if (sy != 0.0f && sz != 0.0f) { const float u = nh_q_capsule_entry(ol.y, ol.z, ol.x, dl.y, dl.z, dl.x, sy * h.y, sz * h.z, h.x, r); t = u < t ? u : t; }
+	if (!(t < INFINITY)) return res;
+	const nh_f3 x = ol + t * dl;
+	nh_f3 v = nh_make3(x.x - nh_max(nh_neg(h.x), nh_min(x.x, h.x)), x.y - nh_max(nh_neg(h.y), nh_min(x.y, h.y)), x.z - nh_max(nh_neg(h.z), nh_min(x.z, h.z)));
+	float vv = nh_dot(v, v);
+	if (!(vv > 0.0f)) { v = nh_make3(sx, sy, sz); vv = nh_dot(v, v); }         // (r below the rounding of the coordinates: the region's direction)
+	const float len = sqrtf(vv);
+	res.t = t; res.n = nh_rotate(q, nh_make3(v.x / len, v.y / len, v.z / len)); res.hit = true;
+	return res;
+}
+
+// The ball (o + t d, r) against the sphere collider (c, R): the ray against the sphere of radius R + r -- its start test is nh_q_overlap_sphere_sphere's
+// to the bit, and r = 0 is nh_q_ray_sphere itself.
+NH_HD nh_QHit nh_q_sweep_sphere(nh_f3 o, nh_f3 d, float r, nh_f3 c, float R) { return nh_q_ray_sphere(o, d, c, R + r); }
+
+// The walk's node test of a cast (k_q_spherecast): the slab test of the ray against the node box grown by w = r + s (s: the cast's pad), with the
+// ray cast's operations (k_q_raycast: w = s).  Entered iff t0 <= t1 and t1 >= 0; t0 = the entry.
+NH_HD bool nh_q_cast_node(nh_f3 lo, nh_f3 hi, nh_f3 o, nh_f3 inv, float w, float& t0) {
+	const float ax = ((lo.x - w) - o.x) * inv.x, bx = ((hi.x + w) - o.x) * inv.x;
+	const float ay = ((lo.y - w) - o.y) * inv.y, by = ((hi.y + w) - o.y) * inv.y;
+	const float az = ((lo.z - w) - o.z) * inv.z, bz = ((hi.z + w) - o.z) * inv.z;
+	t0 = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fminf(az, bz));
+	const float t1 = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fmaxf(az, bz));
+	return t0 <= t1 && t1 >= 0.0f;
+}
+
+// The box of a leaf as the build stores it (k_q_xform's world AABB, k_q_refit's pad): what the host rebuilds to apply the sweep's reach rule.
+NH_HD void nh_q_leaf_box(nh_f3 p, nh_quat q, nh_f3 h, bool box, nh_f3& lo, nh_f3& hi) {
+	const nh_f3 e = box ? nh_q_box_extent(q, h) : h;
+	const nh_f3 mn = p - e, mx = p + e;
+	const float pad = nh_q_pad(mn, mx);
+	lo = nh_make3(mn.x - pad, mn.y - pad, mn.z - pad);
+	hi = nh_make3(mx.x + pad, mx.y + pad, mx.z + pad);
+}
+
+// The sweep's pad and the reach rule.  A cast of radius r > 0 hits a collider at t = max(t_pred, t_leaf) where t_pred is the predicate's
+// t and t_leaf the entry into the collider's leaf box under nh_q_cast_node -- and not at all when that box is not entered.  Every ancestor box contains
+// the leaf box and the node test is monotone in the box, so the walk reaches every collider this rule lets hit at or before the best t so far, whatever
+// the rounding of t_pred.  The clamp changes t only where t_pred lies in front of a box padded by 2^-18 of the coordinates around the grown collider.
+NH_HD float nh_q_cast_pad(nh_f3 o, float r) { return fmaxf(fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fabsf(o.z)), r) * 3.814697265625e-06f; }
 
 #endif

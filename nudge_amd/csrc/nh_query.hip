@@ -1,6 +1,6 @@
 // nh_query.hip -- scene queries against the device-resident world: nh_query_build (a linear BVH over every box and sphere collider, built from
-// the current transforms), nh_raycast (batched closest-hit / any-hit ray casts against the last build) and nh_overlap (the colliders touching each
-// of a batch of spheres or boxes, as variable-length segments).  include/nudge_hip.h, "scene queries".
+// the current transforms), nh_raycast (batched closest-hit / any-hit ray casts against the last build), nh_spherecast (the same for swept balls) and
+// nh_overlap (the colliders touching each of a batch of spheres or boxes, as variable-length segments).  include/nudge_hip.h, "scene queries".
 //
 // Build (one launch each, plus the library's radix sort):
 //   k_q_xform   one lane per collider (boxes, then spheres): world pose (k_xform's arithmetic, nh_query.h), world AABB, the record the ray test
@@ -162,13 +162,6 @@ __global__ __launch_bounds__(256) void k_q_tree(const uint64_t* __restrict__ key
 	}
 }
 
-// conservative box of a leaf: a relative pad of 2^-18 of its largest coordinate, so that no rounding of the ray's slab test can cut off a collider the
-// exact test hits (the ray side adds the same of its origin, k_q_raycast)
-__device__ __forceinline__ float nh_q_pad(float4 mn, float4 mx) {
-	const float m = fmaxf(fmaxf(fmaxf(fabsf(mn.x), fabsf(mn.y)), fmaxf(fabsf(mn.z), fabsf(mx.x))), fmaxf(fabsf(mx.y), fabsf(mx.z)));
-	return m * 3.814697265625e-06f + 1e-30f;
-}
-
 __global__ __launch_bounds__(256) void k_q_refit(const uint32_t* __restrict__ idx, const float4* __restrict__ aabb, uint32_t n, nh_QNode* nodes,
                                                  const uint32_t* __restrict__ parent, const uint32_t* __restrict__ rchild, const uint32_t* __restrict__ last,
                                                  const uint32_t* __restrict__ right_at, uint32_t* arrive) {
@@ -180,7 +173,7 @@ __global__ __launch_bounds__(256) void k_q_refit(const uint32_t* __restrict__ id
 		}
 		const uint32_t c = idx[j];
 		float4 mn = aabb[2u * c], mx = aabb[2u * c + 1u];
-		const float pad = nh_q_pad(mn, mx);
+		const float pad = nh_q_pad(nh_make3(mn.x, mn.y, mn.z), nh_make3(mx.x, mx.y, mx.z));      // (nh_query.h: the host's sweep rule rebuilds this box)
 		mn = make_float4(mn.x - pad, mn.y - pad, mn.z - pad, __uint_as_float(NH_Q_LEAF | c));
 		mx = make_float4(mx.x + pad, mx.y + pad, mx.z + pad, __uint_as_float(j + 1u == n ? NH_Q_NONE : right_at[j]));
 		uint32_t me = n - 1u + j;
@@ -246,6 +239,68 @@ __global__ __launch_bounds__(256) void k_q_raycast(const nh_Ray* __restrict__ ra
 			const nh_f3 p = nh_make3(q.a.x, q.a.y, q.a.z);
 			const nh_QHit h = c < nbox ? nh_q_ray_box(o, d, p, nh_quat{ q.b.x, q.b.y, q.b.z, q.b.w }, nh_make3(q.c.x, q.c.y, q.c.z))
 			                           : nh_q_ray_sphere(o, d, p, q.c.x);
+			if (h.hit && nh_q_better(h.t, c, max_t, bt, bc)) {
+				bt = h.t; bc = c; bn = h.n;
+				if (any_hit) break;
+			}
+		}
+		nh_RayHit out;
+		if (bc == NH_Q_NONE) {
+			out.t = ok ? max_t : __uint_as_float(0x7fc00000u);
+			out.normal[0] = out.normal[1] = out.normal[2] = 0.0f;
+			out.body = out.collider = out.tag = NH_Q_NONE;
+			out.shape = NH_SHAPE_NONE;
+		} else {
+			const nh_QRec q = rec[bc];
+			out.t = bt; out.normal[0] = bn.x; out.normal[1] = bn.y; out.normal[2] = bn.z;
+			out.body = __float_as_uint(q.a.w);
+			out.collider = bc < nbox ? bc : bc - nbox;
+			out.shape = bc < nbox ? NH_SHAPE_BOX : NH_SHAPE_SPHERE;
+			out.tag = __float_as_uint(q.c.w);
+		}
+		float4* hp = reinterpret_cast<float4*>(hits + i);
+		hp[0] = make_float4(out.t, out.normal[0], out.normal[1], out.normal[2]);
+		hp[1] = make_float4(__uint_as_float(out.body), __uint_as_float(out.collider), __uint_as_float(out.shape), __uint_as_float(out.tag));
+	}
+}
+
+// ---- sphere cast ------------------------------------------------------------------------------------------------------------------------------
+// k_q_raycast's walk with every node box grown by the radius (nh_q_cast_node, w = r + pad), the sweep predicates of nh_query.h at the leaves, and the
+// reach rule for r > 0: the hit is at max(t_pred, the leaf's entry), which is what makes the pruning exact.  r = 0 walks and answers as
+// k_q_raycast does.
+__global__ __launch_bounds__(256) void k_q_spherecast(const nh_SphereCast* __restrict__ casts, uint32_t count, nh_RayHit* __restrict__ hits,
+                                                      const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox, uint32_t any_hit) {
+	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
+		const float4* cp = reinterpret_cast<const float4*>(casts + i);
+		const float4 c0 = cp[0], c1 = cp[1], c2 = cp[2];
+		const nh_f3 o = nh_make3(c0.x, c0.y, c0.z), d = nh_make3(c1.x, c1.y, c1.z);
+		const float max_t = c0.w, r = c2.x;
+		const uint32_t ignore = __float_as_uint(c1.w);
+		const bool ok = nh_q_finite(o.x) && nh_q_finite(o.y) && nh_q_finite(o.z) && nh_q_finite(d.x) && nh_q_finite(d.y) && nh_q_finite(d.z) &&
+		                nh_q_finite(r) && !(r < 0.0f);
+		float bt = max_t;
+		uint32_t bc = NH_Q_NONE;
+		nh_f3 bn = nh_make3(0.0f, 0.0f, 0.0f);
+		const nh_f3 inv = nh_make3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+		const float w = r + nh_q_cast_pad(o, r);
+		const bool reach = r > 0.0f;
+		uint32_t node = ok && n ? 0u : NH_Q_NONE;
+		while (node != NH_Q_NONE) {
+			const float4 na = nodes[node].a, nb = nodes[node].b;
+			float t0;
+			const bool enter = nh_q_cast_node(nh_make3(na.x, na.y, na.z), nh_make3(nb.x, nb.y, nb.z), o, inv, w, t0) && t0 <= bt;
+			const uint32_t left = __float_as_uint(na.w);
+			const uint32_t rope = __float_as_uint(nb.w);
+			if (!enter) { node = rope; continue; }
+			if (!(left & NH_Q_LEAF)) { node = left; continue; }
+			node = rope;
+			const uint32_t c = left & ~NH_Q_LEAF;
+			const nh_QRec q = rec[c];
+			if (__float_as_uint(q.a.w) == ignore) continue;
+			const nh_f3 p = nh_make3(q.a.x, q.a.y, q.a.z);
+			nh_QHit h = c < nbox ? nh_q_sweep_box(o, d, r, p, nh_quat{ q.b.x, q.b.y, q.b.z, q.b.w }, nh_make3(q.c.x, q.c.y, q.c.z))
+			                     : nh_q_sweep_sphere(o, d, r, p, q.c.x);
+			if (reach && t0 > h.t) h.t = t0;
 			if (h.hit && nh_q_better(h.t, c, max_t, bt, bc)) {
 				bt = h.t; bc = c; bn = h.n;
 				if (any_hit) break;
@@ -448,6 +503,18 @@ extern "C" int nh_raycast(nh_context* ctx, const nh_Ray* rays, uint32_t count, n
 	NH_HIP_CHECK(ctx, hipSetDevice(ctx->device));
 	nh_QueryState* q = ctx->query;
 	NH_LAUNCH(ctx, "q_raycast", k_q_raycast, nh_grid_for(count, 256, 1u << 20), 256, rays, count, hits, q->nodes, q->rec, q->n, q->nbox,
+	          (flags & NH_RAY_ANY_HIT) ? 1u : 0u);
+	return NH_OK;
+}
+
+extern "C" int nh_spherecast(nh_context* ctx, const nh_SphereCast* casts, uint32_t count, nh_RayHit* hits, uint32_t flags) {
+	if (!ctx || !ctx->query || !ctx->query->built) return NH_ERR_INVALID;
+	if (flags & ~(uint32_t)NH_RAY_ANY_HIT) return NH_ERR_INVALID;
+	if (count == 0u) return NH_OK;
+	if (!casts || !hits || (((uintptr_t)casts | (uintptr_t)hits) & 15u)) return NH_ERR_INVALID;    // (records are moved as 16-byte words)
+	NH_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+	nh_QueryState* q = ctx->query;
+	NH_LAUNCH(ctx, "q_spherecast", k_q_spherecast, nh_grid_for(count, 256, 1u << 20), 256, casts, count, hits, q->nodes, q->rec, q->n, q->nbox,
 	          (flags & NH_RAY_ANY_HIT) ? 1u : 0u);
 	return NH_OK;
 }
