@@ -1049,11 +1049,7 @@ __global__ __launch_bounds__(256) void k_narrowphase(nh_DevState* __restrict__ s
 		}
 		// (every lane's FIRST kept pair is asked for before the frame is put together: the wave waits once for both)
 		i_first = blockIdx.x * blockDim.x + threadIdx.x;
-#ifndef NH_NO_PAIR_PREFETCH
 		{ const uint32_t ic = min(i_first, kept_cap - 1u); kp_first = pairs[SPH ? kept_cap - 1u - ic : ic]; }
-#else
-		i_first = 0xFFFFFFFFu;
-#endif
 		still_frame();
 		// (the layout must be the last full step's, and the kept list at least as long as the pair list it was written from: what lies behind are pairs APPENDED by
 		// still steps in movers form since -- below)
@@ -1815,13 +1811,8 @@ __global__ __launch_bounds__(256) void k_gather_contacts(nh_DevState* __restrict
 				// (where a body of the one-pair class finds its record and the record's place in the tag order: k_adj_simple -> body_rec / body_pos)
 				if (body_a) first_contact[body_a + NH_DEG_STRIDE(nbodies)] = lo;
 				if (body_b) first_contact[body_b + NH_DEG_STRIDE(nbodies)] = lo;
-#if defined(NH_GATHER_32)      // A/B only: the two 32-bit atomics per body of rounds 1 and 2, on the halves of the same counter
-				if (body_a) { uint32_t* h = reinterpret_cast<uint32_t*>(&pair_counter[body_a]); atomicAdd(h, cnt); atomicAdd(h + 1, body_b ? 0x10001u : 1u); first_contact[body_a] = start | 0x80000000u; }
-				if (body_b) { uint32_t* h = reinterpret_cast<uint32_t*>(&pair_counter[body_b]); atomicAdd(h, cnt); atomicAdd(h + 1, body_a ? 0x10001u : 1u); first_contact[body_b] = start; }
-#else
 				if (body_a) { atomicAdd(&pair_counter[body_a], (unsigned long long)cnt | ((unsigned long long)(body_b ? 0x10001u : 1u) << 32)); first_contact[body_a] = start | 0x80000000u; }      // top bit: plays "a"
 				if (body_b) { atomicAdd(&pair_counter[body_b], (unsigned long long)cnt | ((unsigned long long)(body_a ? 0x10001u : 1u) << 32)); first_contact[body_b] = start; }
-#endif
 			}
 		}
 		// (first output slot of the wave's records: the smallest start among those that HAVE contacts -- a record without any may carry a start that still steps
@@ -2028,10 +2019,7 @@ static int collide_impl(nh_context* ctx, nh_ActiveBodies* active_bodies, nh_Cont
 	uint32_t* vals_a = nh_arena_array<uint32_t>(A, C, &err);
 	// broadphase pairs (each owns 4 raw contact slots, further contacts overflow): nh_set_pair_capacity, else half the contact capacity
 	const uint32_t pair_cap = ctx->pair_capacity ? ctx->pair_capacity : cap / 2 + 1024;
-	const bool onesweep = !ctx->env_sort_classic;                    // one kernel per radix pass (nh_util.hip); NH_SORT_CLASSIC=1: three
-	size_t hist_words = 256 * NH_SORT_GRID + 512;
-	if (onesweep && nh_sort_scratch_words(C > pair_cap ? C : pair_cap) > hist_words) hist_words = nh_sort_scratch_words(C > pair_cap ? C : pair_cap);
-	uint32_t* hist = nh_arena_array<uint32_t>(A, hist_words, &err);
+	uint32_t* sort_scratch = nh_arena_array<uint32_t>(A, nh_sort_scratch_words(C > pair_cap ? C : pair_cap), &err);      // (the one-kernel radix passes of the tag sort: nh_util.hip)
 	uint32_t* scan_tmp = nh_arena_array<uint32_t>(A, 2 * NH_SORT_GRID + 64, &err);
 	// grid table: a power of two >= 4 cells per collider, 2^16 .. 2^24 entries (flat scenes populate one layer of a grid that is three cells high:
 	// with fewer entries the cell has to double -- four times the candidates per collider; measured at 2 M mixed bodies: pair search 153 -> 80 us)
@@ -2217,7 +2205,7 @@ static int collide_impl(nh_context* ctx, nh_ActiveBodies* active_bodies, nh_Cont
 			NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->still_awake, (size_t)B + 64u));
 			ctx->still_awake_capacity = B;
 		}
-		const bool still = want_still && (no_islands || sleepers_ok) && !bp_direct && !drop_kept && !drop_sort_order && !lay_fresh && !ctx->env_sort_classic && ctx->sort_seeded && !ctx->env_sort_radix &&
+		const bool still = want_still && (no_islands || sleepers_ok) && !bp_direct && !drop_kept && !drop_sort_order && !lay_fresh && ctx->sort_seeded && !ctx->env_sort_radix &&
 		                   !ctx->env_no_sort_reuse && C != 0u;
 		if (still) {
 			const bool sleepers = may_sleep;
@@ -2343,7 +2331,7 @@ static int collide_impl(nh_context* ctx, nh_ActiveBodies* active_bodies, nh_Cont
 	ctx->still.contacts_stale = false; ctx->still.slots_current = false; ctx->still.views_sleepers = false; ctx->still.appended_pairs = false;          // (a full step writes the contact list, the sleeping pairs and the active list itself)
 	NH_LAUNCH(ctx, "collide_begin", k_collide_begin, begin_grid, 256, st, C, B, parent, set_active, ctx->deg, bodies->idle_counters, ctx->step_parity, coarse_parent, coarse_active, no_islands ? 1u : 0u, block_top,
 	          drop_kept ? 1u : 0u, drop_sort_order ? 1u : 0u);
-	const bool seeded_sort = !ctx->env_sort_classic && ctx->sort_seeded && !ctx->env_sort_radix;      // (NH_SORT_RADIX=1: radix passes every step)
+	const bool seeded_sort = ctx->sort_seeded && !ctx->env_sort_radix;      // (NH_SORT_RADIX=1: radix passes every step)
 	uint64_t* rec_key_a = ctx->sort_keys_by_position;
 	if (C) {
 		NH_LAUNCH(ctx, "xform_aabb", (k_xform<false>), nh_grid_for(C, 1024, 256), 1024, st, bodies->transforms,
@@ -2360,25 +2348,20 @@ static int collide_impl(nh_context* ctx, nh_ActiveBodies* active_bodies, nh_Cont
 		float4* sbox = ctx->grid_sbox; uint32_t* large_list = ctx->grid_large; uint32_t* cell_start = ctx->grid_cstart; uint32_t* cstart = ctx->grid_counts;       // (cstart: the cell COUNTS of a rebuild, all zero between rebuilds)
 		uint2* kept = ctx->fat_pairs;
 		const uint32_t kept_cap = ctx->fat_pair_capacity;
-		const bool measure_skip = ctx->env_measure_skip && ctx->collide_seq > 66u;       // NH_MEASURE_SKIP_CHAINS=1: MEASUREMENT ONLY (wrong as soon as anything moves): what the launches that leave at once cost
-		if (!measure_skip) {
 		NH_LAUNCH(ctx, "cell_keys", k_cell_keys, nh_grid_for(C, 256, 2048), 256, st, C, aabb_min, aabb_max, fbox, keys_a, vals_a, large_list, cstart, incremental ? ctx->fat_gen : (uint8_t*)nullptr);
 		NH_LAUNCH(ctx, "cell_scan", k_cscan_sums, max_cells / CS_TILE, 256, st, cstart, cscan_sums);
 		NH_LAUNCH(ctx, "cell_scan", k_cscan_final, max_cells / CS_TILE, 256, st, cstart, cscan_sums, max_cells, cell_start);
 		NH_LAUNCH(ctx, "cell_scatter", k_cell_scatter, nh_grid_for(C, 256, 2048), 256, st, C, keys_a, vals_a, cell_start, fbox, keys_b, sbox);
-		}
 		// (KEPT: the chain fills the kept list, k_kept_filter makes this step's pairs of it; DIRECT: the chain writes this step's pairs itself)
-		const bool many_lanes = ctx->env_fp_sub ? ctx->env_fp_sub > 1 : C <= 16384u;
+		const bool many_lanes = C <= 16384u;
 #define NH_FIND_PAIRS(SUBL, DIR, OUT, OUTCAP) NH_LAUNCH(ctx, "find_pairs", (k_find_pairs<SUBL, DIR>), nh_grid_for((uint64_t)C * SUBL, 256, 4096), 256, st, C, nbox, keys_b, sbox, cell_start, large_list, fbox, OUT, OUTCAP, \
 		          coarse_parent, ctx->step_parity, bodies->idle_counters)
 		if (bp_direct) {
 			if (many_lanes) NH_FIND_PAIRS(16, true, pairs, pair_cap); else NH_FIND_PAIRS(1, true, pairs, pair_cap);
 			NH_LAUNCH(ctx, "large_pairs", (k_large_pairs<true>), LP_GRID, LP_THREADS, st, nbox, sbox, cell_start, large_list, fbox, pairs, pair_cap, coarse_parent, ctx->step_parity, bodies->idle_counters);
 		} else {
-			if (!measure_skip) {
 			if (many_lanes) NH_FIND_PAIRS(16, false, kept, kept_cap); else NH_FIND_PAIRS(1, false, kept, kept_cap);
 			NH_LAUNCH(ctx, "large_pairs", (k_large_pairs<false>), LP_GRID, LP_THREADS, st, nbox, sbox, cell_start, large_list, fbox, kept, kept_cap, coarse_parent, ctx->step_parity, bodies->idle_counters);
-			}
 			// colliders that left their boxes this step (a few: otherwise the chain above has run): new boxes, new pairs appended to the kept list
 			if (incremental)
 				NH_LAUNCH(ctx, "reinsert", k_reinsert, 256, 256, st, nbox, sbox, cell_start, large_list, fbox, ctx->fat_gen, ctx->fat_esc_mark, ctx->fat_esc_list, ctx->fat_moved_list,
@@ -2444,24 +2427,14 @@ static int collide_impl(nh_context* ctx, nh_ActiveBodies* active_bodies, nh_Cont
 	const uint64_t* sorted_keys = rec_key_a;
 	const uint32_t* sorted_idx = rec_idx_a;
 	if (seeded_sort) {
-		if (!(ctx->env_measure_skip && ctx->collide_seq > 66u))
 		nh_bucket_sort_u64_u32(ctx, rec_key_a, rec_key_b, rec_idx_a, rec_idx_b, pair_cap, sort_place, key_bits, ctx->sort_sorted_keys, ctx->sort_sorted_idx);
 		sorted_keys = ctx->sort_sorted_keys; sorted_idx = ctx->sort_sorted_idx;
-	} else if (onesweep) {
-		if (nh_onesweep_u64_u32_two_fields(ctx, rec_key_a, rec_key_b, rec_idx_a, rec_idx_b, &st->records, pair_cap, ctx->h_state->records, hist, key_bits)) {
-			uint64_t* t = rec_key_a; rec_key_a = rec_key_b; rec_key_b = t; uint32_t* u = rec_idx_a; rec_idx_a = rec_idx_b; rec_idx_b = u;
-		}
-	} else {
-		if (nh_sort_u64_u32(ctx, rec_key_a, rec_key_b, rec_idx_a, rec_idx_b, &st->records, hist, 0, ((key_bits + 7) / 8) * 8)) {
-			uint64_t* t = rec_key_a; rec_key_a = rec_key_b; rec_key_b = t; uint32_t* u = rec_idx_a; rec_idx_a = rec_idx_b; rec_idx_b = u;
-		}
-		if (nh_sort_u64_u32(ctx, rec_key_a, rec_key_b, rec_idx_a, rec_idx_b, &st->records, hist, 32, 32 + ((key_bits + 7) / 8) * 8)) {
-			uint64_t* t = rec_key_a; rec_key_a = rec_key_b; rec_key_b = t; uint32_t* u = rec_idx_a; rec_idx_a = rec_idx_b; rec_idx_b = u;
-		}
+	} else if (nh_onesweep_u64_u32_two_fields(ctx, rec_key_a, rec_key_b, rec_idx_a, rec_idx_b, &st->records, pair_cap, ctx->h_state->records, sort_scratch, key_bits)) {
+		uint64_t* t = rec_key_a; rec_key_a = rec_key_b; rec_key_b = t; uint32_t* u = rec_idx_a; rec_idx_a = rec_idx_b; rec_idx_b = u;
 	}
 	// (dropped records carry count 0, so where they land in the order is irrelevant)
 	if (!seeded_sort) { sorted_keys = rec_key_a; sorted_idx = rec_idx_a; }         // (the radix passes leave the result in whichever buffer they ended in)
-	if (onesweep && !seeded_sort) { nh_bucket_sort_seed(ctx, rec_key_a, pair_cap); ctx->sort_seeded = true; }
+	if (!seeded_sort) { nh_bucket_sort_seed(ctx, rec_key_a, pair_cap); ctx->sort_seeded = true; }
 	if (fork) NH_HIP_CHECK(ctx, hipStreamWaitEvent(main_stream, ctx->ev_join, 0));
 	NH_LAUNCH(ctx, "sorted_counts", k_sorted_counts, nh_grid_for(pair_cap, 256, 2048), 256, st, sorted_idx, rec, rec_counts, sleep_flags, seeded_sort ? 1u : 0u, ctx->lay_rank);
 	// contact starts and sleeping-pair slots: two scans over the sorted records in one pair of launches

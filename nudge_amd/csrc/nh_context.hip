@@ -33,12 +33,10 @@ extern "C" int nh_create(nh_context** out, int device, void* stream, uint32_t fl
 	ctx->idle_bound = -1; ctx->idle_unknown = true; ctx->advance_count = 0; ctx->collide_mark = 0; ctx->idle_bound_mark = 0; ctx->islands_skipped = false;
 	// Behaviour switches (A/B runs, tests): defaults here, changed through nh_set_option -- the library itself never reads the environment
 	ctx->sort_tile = 0u; ctx->sort_target = 0u;
-	ctx->env_sort_classic = false; ctx->env_sort_radix = false; ctx->env_colour_jp = false;
-	ctx->env_solver_waves = 1; ctx->env_fp_sub = 0;
+	ctx->env_sort_radix = false;
 	ctx->env_no_sort_reuse = false;
 	ctx->sort_keys_by_position = nullptr; ctx->sort_sorted_keys = nullptr; ctx->sort_sorted_idx = nullptr;
 	ctx->bp_seen_rebuilds = 0; ctx->bp_rebuild_streak = 0; ctx->bp_direct_left = 0;
-	ctx->env_measure_skip = false;
 	ctx->env_no_fat = false;
 	ctx->fat_pairs = nullptr; ctx->fat_pair_capacity = 0; ctx->fat_box = nullptr; ctx->fat_collider_capacity = 0; ctx->fat_nbox = ctx->fat_nsph = 0xffffffffu;
 	ctx->grid_sbox = nullptr; ctx->grid_skeys = nullptr; ctx->grid_cstart = nullptr; ctx->grid_counts = nullptr; ctx->grid_large = nullptr; ctx->grid_cells = 0; ctx->grid_collider_capacity = 0;
@@ -48,7 +46,7 @@ extern "C" int nh_create(nh_context** out, int device, void* stream, uint32_t fl
 	ctx->env_no_incremental = false;
 	ctx->env_colour_check_seeds = false;
 	ctx->env_no_resident = false;
-	ctx->os_resident = 0; ctx->os_plain_launch = true;
+	ctx->os_resident = 0;
 	memset(&ctx->blk, 0, sizeof(ctx->blk));
 	ctx->blk.scale = 1.0f;
 	ctx->blk.disabled = false; ctx->blk.check = false;
@@ -177,19 +175,14 @@ extern "C" int nh_set_option(nh_context* ctx, const char* name, int value) {
 	else if (n == "no_xform_ahead") ctx->still.no_ahead = on;                  // every still step launches k_xform<true> itself (nh_internal.h: xform ahead)
 	else if (n == "no_local_still") ctx->still.no_local = on;                  // a collider that leaves its inflated box fails a still step as a whole (round 4's behaviour; nh_internal.h "LOCAL speculation")
 	else if (n == "no_still") ctx->still.disabled = on;                        // no step is launched speculatively as a still step (note 9)
-	else if (n == "sort_classic") ctx->env_sort_classic = on;             // three-kernel radix passes
 	else if (n == "sort_radix") ctx->env_sort_radix = on;                 // radix passes every step (no seeded bucket sort)
 	else if (n == "no_sort_reuse") ctx->env_no_sort_reuse = on;           // the tag sort of the contact records runs every step even when nothing has changed
 	else if (n == "bucket_tile") ctx->sort_tile = (uint32_t)value;
 	else if (n == "bucket_target") ctx->sort_target = (uint32_t)value;
-	else if (n == "colour_jp") ctx->env_colour_jp = on;                   // Jones-Plassmann colouring rounds
 	else if (n == "colour_check_seeds") ctx->env_colour_check_seeds = on; // colours seeded from the cache go through a settle round instead of being final at once
-	else if (n == "solver_waves") ctx->env_solver_waves = value;          // wavefronts per workgroup of the fused solver (1, 2, 4)
-	else if (n == "fp_sub") ctx->env_fp_sub = value;                      // lanes per collider in the pair search (1, 2, 4, 16; 0 = by world size)
 	else if (n == "no_kept_pairs") ctx->env_no_fat = on;                  // the broadphase regroups and searches every step instead of re-using its kept pair list
 	else if (n == "no_incremental") ctx->env_no_incremental = on;         // a collider that leaves its inflated box forces a rebuild of the kept pair list
 	else if (n == "no_resident") ctx->env_no_resident = on;               // small general sets also take the one-launch-per-level path
-	else if (n == "cooperative") ctx->os_plain_launch = !on;              // the one-kernel radix passes go out as cooperative launches (nh_util.hip)
 	else if (n == "no_blocks") ctx->blk.disabled = on;                    // large general sets take the per-colour global launches instead of the blocked solver
 	else if (n == "blk_check") ctx->blk.check = on;                       // verify the block tables on the device every step
 	else if (n == "blk_min") ctx->blk.min_contacts = (uint32_t)value;     // general contacts from which the blocked form is used
@@ -200,9 +193,6 @@ extern "C" int nh_set_option(nh_context* ctx, const char* name, int value) {
 	else if (n == "blk_profile") {                                         // wall-clock readings of the sweep workgroups, printed now and then
 		if (on && !ctx->blk.prof) NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->blk.prof, sizeof(unsigned long long) * 4u * 8u * NH_BLK_MAX_BLOCKS));
 	}
-#if defined(NH_MEASURE)
-	else if (n == "measure_skip_chains") ctx->env_measure_skip = on;      // MEASUREMENT BUILDS ONLY (-DNH_MEASURE): wrong as soon as anything moves
-#endif
 	else return NH_ERR_INVALID;
 	return NH_OK;
 }

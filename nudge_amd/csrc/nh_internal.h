@@ -384,7 +384,6 @@ struct nh_context {
 	uint32_t last_general_contacts;       // general contacts of the last setup: does this step's adjacency build leave the general bodies to the per-block colouring?
 	uint32_t fat_nbox, fat_nsph;          // collider counts of the last nh_collide (a change invalidates the list)
 	uint32_t bp_seen_rebuilds, bp_rebuild_streak; int bp_direct_left;      // direct search instead of the kept list while every step rebuilds it (nh_collide)
-	bool env_measure_skip;                // NH_MEASURE_SKIP_CHAINS=1: measurement only (nh_collide)
 	bool env_no_fat;                      // NH_NO_KEPT_PAIRS=1: rebuild every step (A/B, tests)
 	uint32_t step_parity;
 	uint32_t order_seq;
@@ -399,9 +398,7 @@ struct nh_context {
 	uint64_t advance_count, collide_mark, idle_bound_mark;     // nh_advance calls so far; their number at the last nh_collide / at the measuring one
 	bool islands_skipped;                 // the last nh_collide launched no island kernels (its prediction is checked on the device: NH_ERR_STALE_HINT)
 	// behaviour switches read ONCE from the environment by nh_create (test / A-B knobs, see nh_context.hip)
-	bool env_sort_classic, env_sort_radix, env_colour_jp, env_no_resident, env_colour_check_seeds;
-	int env_solver_waves, env_fp_sub;
-	bool os_plain_launch;                 // cooperative launches are not available here: the radix passes use plain launches bounded by os_resident
+	bool env_sort_radix, env_no_resident, env_colour_check_seeds;
 	int os_resident;                      // co-resident workgroups of a one-kernel radix pass on THIS device (nh_util.hip), 0 = not yet asked
 	// tag sort seeded by the previous step's order (nh_util.hip): splitters persist across steps; counts / starts are scratch that must
 	// outlive nothing but is zeroed by its own kernels.  `sort_seeded`: the splitters describe the previous nh_collide of this capacity

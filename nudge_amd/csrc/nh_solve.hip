@@ -1547,9 +1547,8 @@ __global__ __launch_bounds__(256) void k_level_relax(nh_DevState* __restrict__ s
 
 
 // Default (throughput) order for contacts off the one-body fast path: a deterministic greedy COLOURING of the contact graph
-// (two contacts conflict iff they share a dynamic body).  Jones-Plassmann rounds with fixed hashed priorities: a contact whose
-// priority beats every still-uncoloured neighbour takes the smallest colour none of its neighbours holds.  Two such contacts
-// are never adjacent, so a round is race free in place.  colour+1 is stored where the exact mode stores the dependency level,
+// (two contacts conflict iff they share a dynamic body), with fixed hashed priorities deciding between neighbours (the speculative
+// rounds below).  colour+1 is stored where the exact mode stores the dependency level,
 // and the same executor runs colour classes in order: a valid Gauss-Seidel sweep (a different one than the reference's; on
 // chaotic scenes that is the statistical-parity regime), with ~max-degree classes instead of one level per
 // link of the longest dependency chain.
@@ -1557,63 +1556,9 @@ __global__ void k_level_reset_progress(nh_DevState* st) { st->unleveled = 0; st-
 
 __device__ __forceinline__ uint32_t colour_priority(uint32_t c) { uint32_t h = c * 2654435761u; h ^= h >> 15; h *= 2246822519u; h ^= h >> 13; return h; }
 
-__global__ __launch_bounds__(256) void k_colour_round(nh_DevState* __restrict__ st, const uint32_t* __restrict__ general_list, const nh_BodyPair* __restrict__ bodies,
-                                                      const uint32_t* __restrict__ off, const uint32_t* __restrict__ adj, uint32_t* __restrict__ level, uint32_t round, uint32_t n_list) {
-	// n_list != 0: `general_list` is the compacted list of the contacts that were still uncoloured after an earlier batch of rounds
-	uint32_t n = n_list ? n_list : st->general_contacts;
-	uint32_t left = 0, lmax = 0;
-	for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < n; k += gridDim.x * blockDim.x) {
-		uint32_t c = general_list[k];
-		if (__hip_atomic_load(&level[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != NH_UNSET) continue;
-		const uint32_t pc = colour_priority(c);
-		nh_BodyPair p = bodies[c];
-		bool is_max = true;
-		unsigned long long used = 0ull;        // colours 1..64 held by neighbours
-		bool overflow = false;
-		for (int side = 0; side < 2 && is_max; ++side) {
-			uint32_t x = side ? p.b : p.a;
-			if (!x) continue;
-			uint32_t b = off[x], e = off[x + 1];
-			for (uint32_t q = b; q < e; ++q) {
-				uint32_t m = adj[q];
-				if (m == c) continue;
-				uint32_t lm = __hip_atomic_load(&level[m], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-				if (lm == NH_UNSET) {
-					uint32_t pm = colour_priority(m);
-					if (pm > pc || (pm == pc && m > c)) { is_max = false; break; }
-				} else if (lm >= 1 && lm <= 64) {
-					used |= 1ull << (lm - 1);
-				} else if (lm > 64) {
-					overflow = true;
-				}
-			}
-		}
-		if (!is_max) { ++left; continue; }
-		uint32_t colour;
-		if (~used) colour = (uint32_t)__ffsll((long long)~used);          // smallest free colour in 1..64
-		else { colour = 65; overflow = true; }
-		if (overflow && colour > 64) {
-			// more than 64 colours around one contact: fall back to "one past the largest neighbour colour"
-			uint32_t mx = 64;
-			for (int side = 0; side < 2; ++side) {
-				uint32_t x = side ? p.b : p.a;
-				if (!x) continue;
-				for (uint32_t q = off[x]; q < off[x + 1]; ++q) {
-					uint32_t lm = __hip_atomic_load(&level[adj[q]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-					if (lm != NH_UNSET && lm > mx) mx = lm;
-				}
-			}
-			colour = mx + 1;
-		}
-		__hip_atomic_store(&level[c], colour, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		lmax = max(lmax, colour);
-	}
-	block_report(st, left, lmax, round);
-}
-
 // counting sort of the general contacts by level / colour.  Levels are few and hot: histogram and cursors are kept per
 // workgroup in LDS, global atomics happen once per (workgroup, level).
-// Colouring, speculative form (the default; NH_COLOUR_JP=1 selects the Jones-Plassmann rounds above).  A round is two kernels:
+// Colouring, speculative form.  A round is two kernels:
 //   try     every uncoloured contact picks the smallest colour that none of its FINISHED neighbours holds -> tent[c]   (reads only `level`,
 //           which nobody writes meanwhile)
 //   settle  two neighbours that picked the same colour in this round are in conflict: the one with the lower hashed priority stays
@@ -2785,9 +2730,6 @@ static void still_note_movers(nh_context* ctx, const nh_DevState* h, uint32_t se
 	if (ss.sleepers && h->active == 0u) ss.ok_next = false;
 	// (sleepers ahead: how long has the sleeping set stood still?  Counted over confirmed still steps -- `seq` != 0 -- by the active count they report)
 	if (seq != 0u) { if (h->active == ss.sleep_last_active) { if (ss.sleep_stable < 0xffffu) ss.sleep_stable++; } else { ss.sleep_stable = 0u; ss.sleep_last_active = h->active; } }
-#ifdef NH_DEBUG_PAIR
-	fprintf(stderr, "[pair] verdict: map_ok %d unowned %u records %u pairs %u+%u world_bad %d ok %d ready %d\n", (int)ss.ahead_map_ok, h->pair_unowned, h->records, h->pairs, h->pairs_sph, (int)ss.pair_world_bad, (int)ss.pair_world_ok, (int)ss.pair_ready);
-#endif
 	// (... counted by k_pair_owned in the nh_collide numbered pair_owned_seq: counters of an earlier step, or of a full step -- which voids the count -- say nothing)
 	if (ss.pair_owned_seq != 0u && seq >= ss.pair_owned_seq) { if (h->pair_unowned > ctx->pair_list_capacity) ss.pair_world_bad = true; else ss.pair_world_ok = true; }         // (pair ahead: some kept pair is nobody's -- k_pair_owned; the step that relied on it has failed itself)
 	if (h->ahead_multi) ss.ahead_world_bad = true;          // (xform ahead: some body carries several colliders -- k_ahead_check; the step that relied on the map has failed itself)
@@ -2916,7 +2858,7 @@ static int finish_setup(nh_context* ctx, nh_ContactConstraintData* d) {
 			d->general_lists = true;
 		}
 		// A few thousand contacts in default order: colouring and level order by ONE workgroup, no host round trip until the solver's (k_colour_small)
-		if (!(ctx->flags & NH_FLAG_EXACT_ORDER) && !ctx->env_colour_jp && !ctx->env_no_resident && !ctx->env_colour_check_seeds && G <= NH_COLOUR_SMALL_MAX &&
+		if (!(ctx->flags & NH_FLAG_EXACT_ORDER) && !ctx->env_no_resident && !ctx->env_colour_check_seeds && G <= NH_COLOUR_SMALL_MAX &&
 		    (G <= NH_RES_MAX_FULL || B <= NH_RESB_MAX_BODIES)) {
 			NH_LAUNCH(ctx, "colour_small", k_colour_small, 1, 1024, st, general_list, imp->data, contacts->bodies, d->body_off, d->adj, level, d->cont.tent, level_hist, d->level_order, B);
 			NH_LAUNCH(ctx, "rows_general", k_rows_general, nh_grid_for(G, 256, 4096), 256, st, d->level_order, contacts->data, contacts->bodies, bodies->transforms, bodies->properties,
@@ -2937,19 +2879,16 @@ static int finish_setup(nh_context* ctx, nh_ContactConstraintData* d) {
 		NH_LAUNCH(ctx, "level_reset", k_level_reset_progress, 1, 1, st);
 		// colouring: most contacts are settled by the first rounds; the later ones walk a compacted list of the rest (pred_a / pred_b, which
 		// only the exact mode uses, serve as its two buffers)
-		const bool colour_jp = ctx->env_colour_jp;
 		const uint32_t* colour_list = general_list;
 		uint32_t colour_n = 0;                         // 0: the whole general list
 		uint32_t* spare[2] = { pred_a, pred_b };
 		int spare_at = 0;
 		for (;;) {
 			// (short batches first while colouring: the list shrinks fastest in the first rounds, and a batch ends with its compaction)
-			const int batch = (ctx->flags & NH_FLAG_EXACT_ORDER) ? 8 : (colour_jp ? (rounds < 4 ? 2 : (rounds < 8 ? 4 : 8)) : 1);
+			const int batch = (ctx->flags & NH_FLAG_EXACT_ORDER) ? 8 : 1;
 			for (int r = 0; r < batch; ++r, ++rounds) {
 				if (ctx->flags & NH_FLAG_EXACT_ORDER)
 					NH_LAUNCH(ctx, "level_relax", k_level_relax, nh_grid_for(G, 256, 1024), 256, st, general_list, pred_a, pred_b, level, rounds);
-				else if (colour_jp)
-					NH_LAUNCH(ctx, "colour_round", k_colour_round, nh_grid_for(colour_n ? colour_n : G, 256, 1024), 256, st, colour_list, contacts->bodies, d->body_off, d->adj, level, rounds, colour_n);
 				else {
 					if (rounds == 0 && !ctx->env_colour_check_seeds) {
 						NH_LAUNCH(ctx, "colour_seed", k_colour_seed_final, nh_grid_for(G, 256, 2048), 256, st, general_list, imp->data, level, d->cont.tent);
@@ -3098,12 +3037,10 @@ static int first_apply(nh_context* ctx, nh_ContactConstraintData* d, const nh_Bo
 			const bool self_report = ss.pipelined && ss.h_ring[0];
 			fs.host_counters = self_report ? reinterpret_cast<uint32_t*>(ss.h_ring[ctx->collide_seq & 1u]) : nullptr;
 			fs.guard_seq = ss.verdict.pending ? ss.verdict.seq : ctx->collide_seq;          // (a solver behind an unconfirmed still step leaves when THAT one failed)
-#define NH_SOLVE_STILL(NWAVES) NH_LAUNCH(ctx, "solve_still", (k_solve_one_body<4, true, true, NWAVES, true>), (B + 64u * NWAVES - 1u) / (64u * NWAVES), 64 * NWAVES, B, d->body_class, d->body_off, d->adj, d->bodies, bodies->properties, bodies->momentum, \
-		          (float4*)d->states, iterations, ctx->raw_data, bodies->transforms, d->impulses, cv, ctx->hint, NH_CLS_STATIC4, NH_CLS_STATIC4, 2u, d->simple, fs, sv, nh_AheadView())
 			// XFORM AHEAD (nh_internal.h): another sub-step of this nh_step call follows, the step is in the plain form and every dynamic body has its one collider on the
 			// map -- the lanes do the next step's k_xform<true> on their way out
 			ctx->halo_split.launched = false;          // (this step's solver has not gone out in two parts yet)
-			const bool ahead = ss.ahead_plain && ss.more_steps && ss.ahead_map_ok && !ss.no_ahead && !ss.ahead_world_bad && ctx->env_solver_waves != 4 && ctx->env_solver_waves != 2 &&
+			const bool ahead = ss.ahead_plain && ss.more_steps && ss.ahead_map_ok && !ss.no_ahead && !ss.ahead_world_bad &&
 			                   ctx->own_xf && ctx->body_col && ctx->body_col_capacity >= B;
 			// PAIR AHEAD (nh_internal.h): ... and the next sub-step's narrowphase for the body's own pair -- that sub-step then starts at the solver
 			const bool pair = ahead && !ss.no_pair && !ss.pair_world_bad && ss.pair_owned_seq != 0u && ctx->pair_list && ctx->fat_pairs && ctx->own_ctag && !(cd_count_over(ss.colliders));
@@ -3135,7 +3072,8 @@ static int first_apply(nh_context* ctx, nh_ContactConstraintData* d, const nh_Bo
 				NH_LAUNCH(ctx, "solve_still", (k_solve_one_body<4, true, true, 1, true, true>), (B + 63u) / 64u, 64, B, d->body_class, d->body_off, d->adj, d->bodies, bodies->properties, bodies->momentum,
 				          (float4*)d->states, iterations, ctx->raw_data, bodies->transforms, d->impulses, cv, ctx->hint, NH_CLS_STATIC4, NH_CLS_STATIC4, 2u, d->simple, fs, sv, av);
 			} else
-			if (ctx->env_solver_waves == 4) NH_SOLVE_STILL(4); else if (ctx->env_solver_waves == 2) NH_SOLVE_STILL(2); else NH_SOLVE_STILL(1);
+				NH_LAUNCH(ctx, "solve_still", (k_solve_one_body<4, true, true, 1, true>), (B + 63u) / 64u, 64, B, d->body_class, d->body_off, d->adj, d->bodies, bodies->properties, bodies->momentum,
+				          (float4*)d->states, iterations, ctx->raw_data, bodies->transforms, d->impulses, cv, ctx->hint, NH_CLS_STATIC4, NH_CLS_STATIC4, 2u, d->simple, fs, sv, nh_AheadView());
 			ss.ahead_ready = ahead;
 			ss.pair_ready = pair;
 			if (ss.pipelined && ss.h_ring[0]) {
@@ -3214,16 +3152,15 @@ static int first_apply(nh_context* ctx, nh_ContactConstraintData* d, const nh_Bo
 			fs.bits = 1u;
 			if (from_apply && bodies->idle_counters) { fs.bits |= 2u; fs.idle = bodies->idle_counters; ctx->adv.done = true; ctx->adv.time_step = fs.time_step; ctx->adv.body_class = d->body_class; }
 		}
-#define NH_SOLVE_CONTIG(NWAVES) NH_LAUNCH(ctx, "solve_one_body", (k_solve_one_body<4, true, true, NWAVES>), (B + 64u * NWAVES - 1u) / (64u * NWAVES), 64 * NWAVES, B, d->body_class, d->body_off, d->adj, d->bodies, bodies->properties, bodies->momentum, \
-		          (float4*)d->states, iterations, d->contact_data, bodies->transforms, d->impulses, cv, ctx->hint, NH_CLS_STATIC4, NH_CLS_STATIC4, \
-		          1u | (drop_states ? 2u : 0u), d->simple, fs, nh_StillView(), nh_AheadView())
 		// (early counters: not with EVERY launch timed -- the events of a step are collected at its round trip, when they must have happened; timing restricted to one kernel, what
 		// bench.py keeps on, collects at nh_kernel_times -- and not under the legacy observer contract, whose round trips do more than read)
 		d->early_seq = 0u;
 		if (ctx->h_early && !ctx->no_early_counts && B != 0u && !(ctx->timing && ctx->timing_filter.empty()) && !ctx->sync_exports_views && !(ctx->flags & NH_FLAG_SYNC_COUNTS)) {
 			fs.host_counters = ctx->h_early; fs.seq = ctx->collide_seq; d->early_seq = ctx->collide_seq;
 		}
-		if (ctx->env_solver_waves == 4) NH_SOLVE_CONTIG(4); else if (ctx->env_solver_waves == 2) NH_SOLVE_CONTIG(2); else NH_SOLVE_CONTIG(1);
+		NH_LAUNCH(ctx, "solve_one_body", (k_solve_one_body<4, true, true, 1>), (B + 63u) / 64u, 64, B, d->body_class, d->body_off, d->adj, d->bodies, bodies->properties, bodies->momentum,
+		          (float4*)d->states, iterations, d->contact_data, bodies->transforms, d->impulses, cv, ctx->hint, NH_CLS_STATIC4, NH_CLS_STATIC4,
+		          1u | (drop_states ? 2u : 0u), d->simple, fs, nh_StillView(), nh_AheadView());
 		ctx->grav.rest_pending = gravity_here;        // everybody else's gravity: finish_setup, once the round trip has told whether there is anybody else
 		int rc = finish_setup(ctx, d);
 		if (rc) return rc;

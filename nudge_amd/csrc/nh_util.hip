@@ -5,7 +5,6 @@
 // own one contiguous chunk of the input, so a pass is  histogram[digit][block] -> one scan -> stable scatter.
 // Element counts live in device memory (no host round trip); kernels are launched with a fixed grid.
 #include "nh_internal.h"
-#include <mutex>
 
 #define RS_G NH_SORT_GRID
 #define RS_TILE 256
@@ -335,8 +334,6 @@ __global__ __launch_bounds__(256) void os_pass(const K* __restrict__ keys, K* __
 	}
 }
 
-static std::mutex& nh_cooperative_launch_lock() { static std::mutex m; return m; }
-
 template<typename K, typename V, bool HAS_V>
 static int onesweep_impl(nh_context* ctx, K* keys_a, K* keys_b, V* vals_a, V* vals_b, const uint32_t* d_count, uint32_t capacity, uint32_t expected, uint32_t* scratch, const os_shifts& sh) {
 	K* kin = keys_a; K* kout = keys_b;
@@ -367,29 +364,12 @@ static int onesweep_impl(nh_context* ctx, K* keys_a, K* keys_b, V* vals_a, V* va
 	NH_LAUNCH(ctx, "radix_hist", (os_hist<K>), (uint32_t)(cap_tiles < 512 ? cap_tiles : 512), 256, (const K*)kin, d_count, scratch, sh);
 	// (history) The workgroups of a pass used to wait for each other in both directions (earlier counts, group sums of ALL groups): all of them had to be resident.  The launch is
 	// bounded by 3/4 of what the occupancy query says is resident at once, and nothing this library runs beside it (side stream) ever waits for it, so
-	// workgroups that find the compute units busy with somebody else's kernels are merely late.  NH_COOPERATIVE=1 turns the bound into the runtime's
-	// promise (hipLaunchCooperativeKernel; a grid it finds too large is halved -- any grid sorts correctly).  It is not the default because of what it
-	// costs: with two processes sharing one MI355X (the N = 2 rehearsal, whose refresh re-seeds the sort every 16 steps) every cooperative launch took
-	// ~10 ms against ~0.05 ms for the plain one (profiles/r03_cooperative_launch_ab.txt).
-	uint32_t g = grid;
+	// workgroups that find the compute units busy with somebody else's kernels are merely late.
 	for (int p = 0; p < sh.n; ++p) {
 		uint32_t* c = scratch + (size_t)p * OS_PASS_WORDS;
 		uint32_t* c2 = c + (size_t)OS_MAX_GRID * 256;
-		int shift = sh.s[p];
-		void* args[] = { (void*)&kin, (void*)&kout, (void*)&vin, (void*)&vout, (void*)&d_count, (void*)&c, (void*)&c2, (void*)&shift };
 		if (ctx->timing) nh_timer_begin(ctx, "radix_pass");
-		hipError_t le = hipErrorUnknown;
-		while (!ctx->os_plain_launch) {
-			// (one cooperative launch at a time process-wide: the runtime sets up its cooperative queue on first use and two host threads racing
-			// there -- two worlds stepped by two threads -- crashed its teardown; the lock costs nothing on the one-thread path)
-			std::lock_guard<std::mutex> guard(nh_cooperative_launch_lock());
-			le = hipLaunchCooperativeKernel((const void*)os_pass<K, V, HAS_V>, dim3(g), dim3(256), args, 0, ctx->stream);
-			if (le == hipSuccess) break;
-			(void)hipGetLastError();
-			if (le == hipErrorCooperativeLaunchTooLarge && g > 16u) { g /= 2u; resident = (int)g; continue; }
-			ctx->os_plain_launch = true;           // no cooperative launches on this device / runtime: the occupancy-bounded plain launch, as before
-		}
-		if (ctx->os_plain_launch) hipLaunchKernelGGL((os_pass<K, V, HAS_V>), dim3(g), dim3(256), 0, ctx->stream, kin, kout, vin, vout, d_count, c, c2, shift);
+		hipLaunchKernelGGL((os_pass<K, V, HAS_V>), dim3(grid), dim3(256), 0, ctx->stream, kin, kout, vin, vout, d_count, c, c2, sh.s[p]);
 		if (ctx->timing) nh_timer_end(ctx);
 		K* tk = kin; kin = kout; kout = tk;
 		V* tv = vin; vin = vout; vout = tv;

@@ -29,9 +29,9 @@ NH_FLAG_SINGLE_APPLY = 4
 NH_FLAG_FUSED_STEP = 8
 NH_VIEW_CONTACTS, NH_VIEW_CACHE, NH_VIEW_ACTIVE, NH_VIEW_ALL = 1, 2, 4, 7
 # environment variables NH_<NAME> that World() forwards to nh_set_option (tests and dev scripts; include/nudge_hip.h lists what each does)
-OPTION_NAMES = ("no_still", "no_kept_pairs", "no_incremental", "no_sort_reuse", "sort_classic", "sort_radix", "bucket_tile", "bucket_target", "colour_jp",
-                "colour_check_seeds", "no_resident", "solver_waves", "fp_sub", "cooperative", "no_blocks", "blk_check", "blk_min", "blk_target", "blk_rows_global",
-                "blk_global_colours", "blk_profile", "no_asleep", "no_blk_chain", "no_local_still", "no_xform_ahead", "measure_skip_chains", "sync_exports_views", "no_pair_ahead", "no_sleeper_skip", "halo_overlap", "no_early_counts", "no_sleeper_ahead")
+OPTION_NAMES = ("no_still", "no_kept_pairs", "no_incremental", "no_sort_reuse", "sort_radix", "bucket_tile", "bucket_target",
+                "colour_check_seeds", "no_resident", "no_blocks", "blk_check", "blk_min", "blk_target", "blk_rows_global",
+                "blk_global_colours", "blk_profile", "no_asleep", "no_blk_chain", "no_local_still", "no_xform_ahead", "sync_exports_views", "no_pair_ahead", "no_sleeper_skip", "halo_overlap", "no_early_counts", "no_sleeper_ahead")
 
 EXPORTS = [
     "nh_create", "nh_destroy", "nh_set_flags", "nh_synchronize", "nh_read_counts", "nh_export_views", "nh_set_cache_count",
@@ -321,15 +321,14 @@ class World:
                 continue
             name = key[3:].lower()
             if name not in OPTION_NAMES:           # (a stale or unrelated NH_* variable must not keep a world from being created)
-                if name not in ("gather_32",):
-                    warnings.warn(f"nudge_amd: environment variable {key} names no library option; ignored")
+                warnings.warn(f"nudge_amd: environment variable {key} names no library option; ignored")
                 continue
             try:
                 num = int(val)
             except ValueError:
                 num = 1
             rc = self.L.nh_set_option(self.ctx, name.encode(), num)
-            if rc:                                 # (e.g. measure_skip_chains on a build without -DNH_MEASURE)
+            if rc:
                 warnings.warn(f"nudge_amd: nh_set_option({name}, {num}) refused: {self.L.nh_error_string(rc).decode()}")
         if tag_bits is None:
             mt = 1

@@ -788,13 +788,13 @@ def test_seeded_sort_oversized_buckets_and_abrupt_change(tile, target, monkeypat
 
 
 @pytest.mark.parametrize("mult,offset", [(1, 0), (257, 3), (70001, 12345), (1048573, 4000000000 - 1048573 * 500)])
-@pytest.mark.parametrize("sort", ["seeded", "radix", "classic"])
+@pytest.mark.parametrize("sort", ["seeded", "radix"])
 def test_wide_sparse_collider_tags_do_not_change_the_world(mult, offset, sort, monkeypatch):
     """Collider tags are 32-bit in this ABI and only their ORDER matters (contacts come out in tag order, the solver order follows):
     an order-preserving re-tagging up to the top of the 32-bit range (9..32 significant bits: 2 to 8 digit passes of the packed key,
-    seeded sort, one-kernel and three-kernel radix passes alike) must leave bodies bit-identical and map the contact tags one to one."""
-    if sort != "seeded":
-        monkeypatch.setenv("NH_SORT_RADIX" if sort == "radix" else "NH_SORT_CLASSIC", "1")
+    seeded sort and radix passes alike) must leave bodies bit-identical and map the contact tags one to one."""
+    if sort == "radix":
+        monkeypatch.setenv("NH_SORT_RADIX", "1")
     scene = S.pile(n_boxes=300, n_spheres=150, seed=21, iterations=4)
     scene["body_transforms"]["position"][1:, 1] *= 0.1
     wide = dict(scene)
