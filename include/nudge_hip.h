@@ -79,7 +79,7 @@
  *      exported the views: nh_set_option(ctx, "sync_exports_views", 1) restores that contract at its old price; INTEGRATION.md.)  Any entry point outside the sample's
  *      call order between nh_collide and nh_apply_impulses turns a still step into a full one first, so everything it observes is what a full step
  *      produces.  nh_Counts.still_steps / still_replays count them.
- *      The scene queries (nh_query_build, nh_raycast, nh_spherecast, nh_overlap) are not entry points of the step in this sense: they neither export nor settle nor turn a still step into a
+ *      The scene queries (nh_query_build, nh_raycast, nh_spherecast, nh_boxcast, nh_overlap) are not entry points of the step in this sense: they neither export nor settle nor turn a still step into a
  *      full one, and they do not count -- see "scene queries" below.
  *
  * Threading: one context = one HIP stream = one world at a time; no global mutable state.
@@ -349,7 +349,7 @@ typedef struct nh_StreamInfo { uint32_t slot; uint32_t valid; uint64_t step; uin
 int nh_stream_state(nh_context* ctx, const nh_BodyData* bodies, uint32_t count, void* host_ring, uint32_t slots, uint32_t every);
 int nh_stream_latest(nh_context* ctx, nh_StreamInfo* out);
 
-/* ---- scene queries: ray casts, sphere casts and overlaps against the device-resident world -----------------------------------------------------------------
+/* ---- scene queries: ray casts, sphere and box casts, and overlaps against the device-resident world -----------------------------------------------------------------
    nh_query_build snapshots the world transforms and AABBs of ALL box and sphere colliders -- those of sleeping bodies and of body 0 (the static world) included -- and
    builds a bounding-volume hierarchy over them (a linear BVH: Morton keys, a radix tree, bottom-up boxes) into buffers the library owns: they grow with the collider
    count (~250 B per collider) and are freed by nh_destroy.  nh_raycast answers `count` rays (nh_overlap, below, `count` shapes) against the LAST build: the hierarchy does not follow the bodies, so
@@ -396,6 +396,34 @@ int nh_raycast(nh_context* ctx, const nh_Ray* rays, uint32_t count, nh_RayHit* h
    into a full one, no change to nh_Counts. */
 typedef struct nh_SphereCast { float origin[3]; float max_t; float direction[3]; uint32_t ignore_body; float radius; uint32_t reserved[3]; } nh_SphereCast;  /* 48 B */
 int nh_spherecast(nh_context* ctx, const nh_SphereCast* casts, uint32_t count, nh_RayHit* hits, uint32_t flags /* 0 or NH_RAY_ANY_HIT */);
+
+/* nh_boxcast: where a swept oriented box first touches the world of the LAST nh_query_build -- "can this crate be pushed 3 m along x", where a door, lift or
+   character hull stops.  nh_BoxCast's first 32 bytes are nh_Ray's fields at the same offsets; `size` holds half extents (as in nh_BoxCollider); `rotation`
+   is a unit quaternion in (x, y, z, s) order (as in nh_OverlapQuery) that the library does not normalise; `reserved` is not read.  Exact predicates:
+   nudge_amd/csrc/nh_query.h.
+     - the swept box is the closed box of pose (o + t d, rotation) and half extents `size`, for 0 <= t <= max_t; it translates only, nothing rotates during
+       the sweep; t is in units of d, as for rays;
+     - the hit on one collider is the smallest such t at which the box touches it (touching counts, as in nh_overlap); the normal is a unit vector from the
+       collider towards the cast box along the separating axis that is the last to close -- a face normal of either box or the normalised cross product of
+       an edge pair -- signed against the direction (n.d < 0).  An edge pair within ~1e-3 rad of parallel still bounds t but never gives the normal (its
+       cross product is rounding noise): when it closes last, the normal is the axis that closed last before it.  No contact point is reported;
+     - START OVERLAP: a box that overlaps a collider at t = 0 under nh_overlap's own predicates (nh_q_overlap_box_box with the cast box as the query,
+       nh_q_overlap_sphere_box for a sphere collider) hits it at t = 0 with normal = -d / |d|, the ray's inside rule; a start contact that only the sweep's
+       rounding finds does the same;
+     - over all colliders the answer follows nh_raycast: the closest hit, ties by (shape, collider index), `ignore_body`, NH_RAY_ANY_HIT, and a miss written
+       exactly as a ray miss (shape = NH_SHAPE_NONE, t = max_t, normal = 0, body = collider = tag = 0xffffffff); a collider of a body that does not exist
+       (NaN pose) is never hit;
+     - SIZE (0, 0, 0) IS A RAY: it writes the same bytes as nh_raycast with the same first 32 bytes, and `rotation` is not read.  A zero direction does what it
+       does for a ray: a box that touches at t = 0 hits there with a NaN normal (-d / |d| = 0 / 0), any other cast misses;
+     - for a nonzero size a hit also needs the ray to enter the collider's box in the hierarchy grown per axis by the cast box's world AABB half extent,
+       and t is at least that entry (the reach rule, DESIGN 10.3, as for sphere casts);
+     - a cast with a non-finite origin, direction or size, a negative size, or a nonzero size with a non-finite rotation is written as a miss with t = NaN.
+   Returns NH_ERR_INVALID before any nh_query_build, for flags other than 0 or NH_RAY_ANY_HIT, and for null or not 16-byte aligned `casts` / `hits`;
+   count = 0 is a no-op that returns NH_OK.  An OBSERVER like nh_raycast (note 9): no view export, no settling of deferred gravity, no still step turned
+   into a full one, no change to nh_Counts. */
+typedef struct nh_BoxCast { float origin[3]; float max_t; float direction[3]; uint32_t ignore_body;
+                            float rotation[4]; float size[3]; uint32_t reserved; } nh_BoxCast;                                                    /* 64 B */
+int nh_boxcast(nh_context* ctx, const nh_BoxCast* casts, uint32_t count, nh_RayHit* hits, uint32_t flags /* 0 or NH_RAY_ANY_HIT */);
 
 /* nh_overlap: which colliders of the LAST nh_query_build touch each of `count` query shapes -- explosion radii, trigger volumes, "is this spot free".
    Query shapes (nh_OverlapQuery):

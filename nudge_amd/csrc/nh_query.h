@@ -1,8 +1,8 @@
-// nh_query.h -- per-item arithmetic of the scene query (nh_query_build / nh_raycast / nh_spherecast / nh_overlap, nh_query.hip): a collider's world
-// pose, a ray against one box and against one sphere, the overlap predicates of a query sphere or box against one collider, and a swept ball against
-// one box and one sphere with the walk's node test it is pruned by.
+// nh_query.h -- per-item arithmetic of the scene query (nh_query_build / nh_raycast / nh_spherecast / nh_boxcast / nh_overlap, nh_query.hip): a
+// collider's world pose, a ray against one box and against one sphere, the overlap predicates of a query sphere or box against one collider, a swept
+// ball and a swept box against one box and one sphere, with the walk's node tests they are pruned by.
 //
-// Every function is `NH_HD` so that tests/hostquery (hostoverlap, hostsweep) builds the SAME arithmetic with g++ -ffp-contract=off and gets the device's bits: the
+// Every function is `NH_HD` so that tests/hostquery (hostoverlap, hostsweep, hostboxcast) builds the SAME arithmetic with g++ -ffp-contract=off and gets the device's bits: the
 // brute force over all colliders there is the oracle of the GPU's tree traversal.  Only + - * /, sqrtf (correctly rounded on both sides)
 // and sign / absolute-value bit operations are used (and fminf / fmaxf in the pads and the walk's node test, which agree on both sides).
 //
@@ -298,5 +298,115 @@ NH_HD void nh_q_leaf_box(nh_f3 p, nh_quat q, nh_f3 h, bool box, nh_f3& lo, nh_f3
 // the leaf box and the node test is monotone in the box, so the walk reaches every collider this rule lets hit at or before the best t so far, whatever
 // the rounding of t_pred.  The clamp changes t only where t_pred lies in front of a box padded by 2^-18 of the coordinates around the grown collider.
 NH_HD float nh_q_cast_pad(nh_f3 o, float r) { return fmaxf(fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fabsf(o.z)), r) * 3.814697265625e-06f; }
+
+// ---- box casts (nh_boxcast): the first t at which the box of pose (o + t d, qa) and half extents ha touches a collider ------------------------------
+// The box translates only.  A box that touches at t = 0 under nh_overlap's own predicates (nh_q_overlap_box_box with the cast box as the query,
+// nh_q_overlap_sphere_box) hits at t = 0 with the ray's inside normal -d / |d|.  ha = (0, 0, 0) is a ray cast, bit for bit, and qa is not read.
+
+// One separating axis of the translational SAT: the projected centre distance is s - tau u, and the axis holds while |s - tau u| <= rho.  [te, tx] is
+// narrowed to that interval at t = base + tau.  A `lead` axis may give the normal: its lower end enters at `axis` when it is the largest lower end of the
+// lead axes so far (tn; the first axis on equality), and ue is then its u.  u == 0: all or nothing, |s| <= rho (no 0 * inf).  A NaN fails the axis.
+NH_HD void nh_q_sat_axis(float s, float u, float rho, float base, int axis, bool lead, float& te, float& tn, float& tx, int& enter, float& ue, bool& all) {
+	if (u == 0.0f) {
+		if (!(nh_abs(s) <= rho)) all = false;
+		return;
+	}
+	const float a = base + (s - rho) / u, b = base + (s + rho) / u;
+	const float lo = b < a ? b : a, hi = b < a ? a : b;
+	if (!(lo <= hi)) all = false;
+	if (lo > te) te = lo;
+	if (lead && lo > tn) { tn = lo; enter = axis; ue = u; }
+	if (hi < tx) tx = hi;
+}
+
+// The cast box (o + t d, qa, ha) against the box collider (p, qb, hb): the translational form of nh_q_overlap_box_box's 15 axes -- the same frame (the
+// cast box's), the same R = Ra^T Rb and radii with E = |R| + 2^-20 -- where each axis is a t interval, the entry t is the largest lower end, and a hit
+// needs every interval to hold with t_enter <= t_exit, t_exit >= 0.  ha = 0: nh_q_ray_box.  A start contact that only this rounding finds
+// (t_enter <= 0) also returns the inside rule.
+// Near-parallel edges: the six face axes are solved first from the centres, and the edge axes from the centres at the face entry
+// tb = max(t_face, 0), where the boxes are within their sizes of each other -- so the rounding of a (nearly) zero cross axis is a few ulp of the
+// sizes, which the 2^-20 of its radius covers, and it cannot separate boxes that touch however far the cast started.  Every axis bounds t; but an
+// edge pair whose squared cross product |A_i x B_j|^2 (read off R) is below 2^-20 (edges within ~1e-3 rad of parallel) never gives the normal, whose
+// direction would be rounding noise.  The normal is the LEAD axis that closes last (faces of the cast box, faces of the collider, then the other
+// edge pairs; the first on equality), from the collider to the cast box, normalised, signed against the direction.
+NH_HD nh_QHit nh_q_sweep_box_box(nh_f3 o, nh_f3 d, nh_quat qa, nh_f3 ha, nh_f3 p, nh_quat qb, nh_f3 hb) {
+	if (ha.x == 0.0f && ha.y == 0.0f && ha.z == 0.0f) return nh_q_ray_box(o, d, p, qb, hb);
+	if (nh_q_overlap_box_box(o, qa, ha, p, qb, hb)) return nh_q_inside(d);
+	nh_QHit res; res.t = 0.0f; res.n = nh_make3(0.0f, 0.0f, 0.0f); res.hit = false;
+	const nh_m33 A = nh_matrix(qa), B = nh_matrix(qb);
+	const nh_f3 m = p - o;
+	const float t0 = nh_dot(A.c0, m), t1 = nh_dot(A.c1, m), t2 = nh_dot(A.c2, m);
+	const float u0 = nh_dot(A.c0, d), u1 = nh_dot(A.c1, d), u2 = nh_dot(A.c2, d);
+	const float R00 = nh_dot(A.c0, B.c0), R01 = nh_dot(A.c0, B.c1), R02 = nh_dot(A.c0, B.c2);
+	const float R10 = nh_dot(A.c1, B.c0), R11 = nh_dot(A.c1, B.c1), R12 = nh_dot(A.c1, B.c2);
+	const float R20 = nh_dot(A.c2, B.c0), R21 = nh_dot(A.c2, B.c1), R22 = nh_dot(A.c2, B.c2);
+	const float E00 = nh_abs(R00) + NH_Q_SAT_EPS, E01 = nh_abs(R01) + NH_Q_SAT_EPS, E02 = nh_abs(R02) + NH_Q_SAT_EPS;
+	const float E10 = nh_abs(R10) + NH_Q_SAT_EPS, E11 = nh_abs(R11) + NH_Q_SAT_EPS, E12 = nh_abs(R12) + NH_Q_SAT_EPS;
+	const float E20 = nh_abs(R20) + NH_Q_SAT_EPS, E21 = nh_abs(R21) + NH_Q_SAT_EPS, E22 = nh_abs(R22) + NH_Q_SAT_EPS;
+	const float a0 = ha.x, a1 = ha.y, a2 = ha.z, b0 = hb.x, b1 = hb.y, b2 = hb.z;
+	float te = -INFINITY, tn = -INFINITY, tx = INFINITY, ue = 0.0f;
+	int enter = -1;
+	bool all = true;
+	// a's face normals A_0 .. A_2, then b's B_0 .. B_2, from the centres at t = 0
+	nh_q_sat_axis(t0, u0, a0 + (b0 * E00 + b1 * E01 + b2 * E02), 0.0f, 0, true, te, tn, tx, enter, ue, all);
+	nh_q_sat_axis(t1, u1, a1 + (b0 * E10 + b1 * E11 + b2 * E12), 0.0f, 1, true, te, tn, tx, enter, ue, all);
+	nh_q_sat_axis(t2, u2, a2 + (b0 * E20 + b1 * E21 + b2 * E22), 0.0f, 2, true, te, tn, tx, enter, ue, all);
+	nh_q_sat_axis(t0 * R00 + t1 * R10 + t2 * R20, u0 * R00 + u1 * R10 + u2 * R20, (a0 * E00 + a1 * E10 + a2 * E20) + b0, 0.0f, 3, true, te, tn, tx, enter, ue, all);
+	nh_q_sat_axis(t0 * R01 + t1 * R11 + t2 * R21, u0 * R01 + u1 * R11 + u2 * R21, (a0 * E01 + a1 * E11 + a2 * E21) + b1, 0.0f, 4, true, te, tn, tx, enter, ue, all);
+	nh_q_sat_axis(t0 * R02 + t1 * R12 + t2 * R22, u0 * R02 + u1 * R12 + u2 * R22, (a0 * E02 + a1 * E12 + a2 * E22) + b2, 0.0f, 5, true, te, tn, tx, enter, ue, all);
+	if (!all || !(te <= tx) || !(tx >= 0.0f)) return res;
+	// edge x edge: A_i x B_j, from the centres at the face entry; a near-parallel pair bounds t but does not lead
+	const float tb = te > 0.0f ? te : 0.0f;
+	const nh_f3 mb = p - (o + tb * d);
+	const float v0 = nh_dot(A.c0, mb), v1 = nh_dot(A.c1, mb), v2 = nh_dot(A.c2, mb);
+	nh_q_sat_axis(v2 * R10 - v1 * R20, u2 * R10 - u1 * R20, (a1 * E20 + a2 * E10) + (b1 * E02 + b2 * E01), tb, 6, R10 * R10 + R20 * R20 >= NH_Q_SAT_EPS, te, tn, tx, enter, ue, all);
+	nh_q_sat_axis(v2 * R11 - v1 * R21, u2 * R11 - u1 * R21, (a1 * E21 + a2 * E11) + (b0 * E02 + b2 * E00), tb, 7, R11 * R11 + R21 * R21 >= NH_Q_SAT_EPS, te, tn, tx, enter, ue, all);
+	nh_q_sat_axis(v2 * R12 - v1 * R22, u2 * R12 - u1 * R22, (a1 * E22 + a2 * E12) + (b0 * E01 + b1 * E00), tb, 8, R12 * R12 + R22 * R22 >= NH_Q_SAT_EPS, te, tn, tx, enter, ue, all);
+	nh_q_sat_axis(v0 * R20 - v2 * R00, u0 * R20 - u2 * R00, (a0 * E20 + a2 * E00) + (b1 * E12 + b2 * E11), tb, 9, R00 * R00 + R20 * R20 >= NH_Q_SAT_EPS, te, tn, tx, enter, ue, all);
+	nh_q_sat_axis(v0 * R21 - v2 * R01, u0 * R21 - u2 * R01, (a0 * E21 + a2 * E01) + (b0 * E12 + b2 * E10), tb, 10, R01 * R01 + R21 * R21 >= NH_Q_SAT_EPS, te, tn, tx, enter, ue, all);
+	nh_q_sat_axis(v0 * R22 - v2 * R02, u0 * R22 - u2 * R02, (a0 * E22 + a2 * E02) + (b0 * E11 + b1 * E10), tb, 11, R02 * R02 + R22 * R22 >= NH_Q_SAT_EPS, te, tn, tx, enter, ue, all);
+	nh_q_sat_axis(v1 * R00 - v0 * R10, u1 * R00 - u0 * R10, (a0 * E10 + a1 * E00) + (b1 * E22 + b2 * E21), tb, 12, R00 * R00 + R10 * R10 >= NH_Q_SAT_EPS, te, tn, tx, enter, ue, all);
+	nh_q_sat_axis(v1 * R01 - v0 * R11, u1 * R01 - u0 * R11, (a0 * E11 + a1 * E01) + (b0 * E22 + b2 * E20), tb, 13, R01 * R01 + R11 * R11 >= NH_Q_SAT_EPS, te, tn, tx, enter, ue, all);
+	nh_q_sat_axis(v1 * R02 - v0 * R12, u1 * R02 - u0 * R12, (a0 * E12 + a1 * E02) + (b0 * E21 + b1 * E20), tb, 14, R02 * R02 + R12 * R12 >= NH_Q_SAT_EPS, te, tn, tx, enter, ue, all);
+	if (!all || enter < 0 || !(te <= tx) || !(tx >= 0.0f)) return res;
+	if (!(te > 0.0f)) return nh_q_inside(d);
+	// the entering axis in world space: A_k, B_k or A_i x B_j
+	nh_f3 L;
+	if (enter < 3) L = enter == 0 ? A.c0 : enter == 1 ? A.c1 : A.c2;
+	else if (enter < 6) L = enter == 3 ? B.c0 : enter == 4 ? B.c1 : B.c2;
+	else {
+		const int i = (enter - 6) / 3, j = (enter - 6) % 3;
+		L = nh_cross(i == 0 ? A.c0 : i == 1 ? A.c1 : A.c2, j == 0 ? B.c0 : j == 1 ? B.c1 : B.c2);
+	}
+	// entering at the lower end: u > 0 puts the collider on the +L side of the cast box, so the normal is -L (which closes with u, whatever closed last)
+	const float len = sqrtf(nh_dot(L, L));
+	const nh_f3 n = nh_make3(L.x / len, L.y / len, L.z / len);
+	res.t = te; res.n = ue > 0.0f ? nh_make3(nh_neg(n.x), nh_neg(n.y), nh_neg(n.z)) : n; res.hit = true;
+	return res;
+}
+
+// The cast box (o + t d, qa, ha) against the sphere collider (c, R): the ball swept by -d against the box at rest, nh_q_sweep_box(c, -d, R, o, qa, ha),
+// with its normal negated (from the sphere to the box).  The start test is nh_q_overlap_sphere_box(c, R, o, qa, ha), nh_overlap's predicate of a box
+// query against a sphere collider, answered with nh_q_inside(d) itself; ha = 0: nh_q_ray_sphere.
+NH_HD nh_QHit nh_q_sweep_box_sphere(nh_f3 o, nh_f3 d, nh_quat qa, nh_f3 ha, nh_f3 c, float R) {
+	if (ha.x == 0.0f && ha.y == 0.0f && ha.z == 0.0f) return nh_q_ray_sphere(o, d, c, R);
+	// (nh_q_sweep_box repeats this test first; it is made here so that a start hit is nh_q_inside(d) itself.  The negated nh_q_inside(-d) has the same
+	// bits except for a zero direction, whose 0 / 0 NaN would carry the sign of the platform's default NaN flipped -- host and device would differ)
+	if (nh_q_overlap_sphere_box(c, R, o, qa, ha)) return nh_q_inside(d);
+	nh_QHit h = nh_q_sweep_box(c, nh_make3(nh_neg(d.x), nh_neg(d.y), nh_neg(d.z)), R, o, qa, ha);
+	h.n = nh_make3(nh_neg(h.n.x), nh_neg(h.n.y), nh_neg(h.n.z));
+	return h;
+}
+
+// The walk's node test of a box cast (k_q_boxcast): nh_q_cast_node with the node box grown by w_k on axis k -- w = e + s, e the cast box's world AABB
+// half extents (nh_q_box_extent; 0 for a ray), s = nh_q_cast_pad(o, max_k e_k).  At e = 0 it is the ray's test to the bit.
+NH_HD bool nh_q_cast_node3(nh_f3 lo, nh_f3 hi, nh_f3 o, nh_f3 inv, nh_f3 w, float& t0) {
+	const float ax = ((lo.x - w.x) - o.x) * inv.x, bx = ((hi.x + w.x) - o.x) * inv.x;
+	const float ay = ((lo.y - w.y) - o.y) * inv.y, by = ((hi.y + w.y) - o.y) * inv.y;
+	const float az = ((lo.z - w.z) - o.z) * inv.z, bz = ((hi.z + w.z) - o.z) * inv.z;
+	t0 = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fminf(az, bz));
+	const float t1 = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fmaxf(az, bz));
+	return t0 <= t1 && t1 >= 0.0f;
+}
 
 #endif

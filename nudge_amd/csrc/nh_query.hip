@@ -1,6 +1,6 @@
 // nh_query.hip -- scene queries against the device-resident world: nh_query_build (a linear BVH over every box and sphere collider, built from
-// the current transforms), nh_raycast (batched closest-hit / any-hit ray casts against the last build), nh_spherecast (the same for swept balls) and
-// nh_overlap (the colliders touching each of a batch of spheres or boxes, as variable-length segments).  include/nudge_hip.h, "scene queries".
+// the current transforms), nh_raycast (batched closest-hit / any-hit ray casts against the last build), nh_spherecast and nh_boxcast (the same for
+// swept balls and swept oriented boxes) and nh_overlap (the colliders touching each of a batch of spheres or boxes, as variable-length segments).  include/nudge_hip.h, "scene queries".
 //
 // Build (one launch each, plus the library's radix sort):
 //   k_q_xform   one lane per collider (boxes, then spheres): world pose (k_xform's arithmetic, nh_query.h), world AABB, the record the ray test
@@ -326,6 +326,72 @@ __global__ __launch_bounds__(256) void k_q_spherecast(const nh_SphereCast* __res
 	}
 }
 
+// ---- box cast ---------------------------------------------------------------------------------------------------------------------------------
+// k_q_spherecast's walk with the node box grown per axis by the cast box's world AABB half extent plus the pad (nh_q_cast_node3), the box-cast
+// predicates of nh_query.h at the leaves, and the reach rule for a nonzero size.  Size 0 walks and answers as k_q_raycast does, and
+// does not read the rotation.  (Without the waves-per-EU hint the box-box test lands at 129 VGPRs and 3 waves; with it, 128 and 4, no scratch.)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k_q_boxcast(const nh_BoxCast* __restrict__ casts, uint32_t count, nh_RayHit* __restrict__ hits,
+                                                   const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox, uint32_t any_hit) {
+	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
+		const float4* cp = reinterpret_cast<const float4*>(casts + i);
+		const float4 c0 = cp[0], c1 = cp[1], c2 = cp[2], c3 = cp[3];
+		const nh_f3 o = nh_make3(c0.x, c0.y, c0.z), d = nh_make3(c1.x, c1.y, c1.z), h = nh_make3(c3.x, c3.y, c3.z);
+		const nh_quat qa = { c2.x, c2.y, c2.z, c2.w };
+		const float max_t = c0.w;
+		const uint32_t ignore = __float_as_uint(c1.w);
+		const bool ray = h.x == 0.0f && h.y == 0.0f && h.z == 0.0f;
+		const bool ok = nh_q_finite(o.x) && nh_q_finite(o.y) && nh_q_finite(o.z) && nh_q_finite(d.x) && nh_q_finite(d.y) && nh_q_finite(d.z) &&
+		                nh_q_finite(h.x) && nh_q_finite(h.y) && nh_q_finite(h.z) && !(h.x < 0.0f) && !(h.y < 0.0f) && !(h.z < 0.0f) &&
+		                (ray || (nh_q_finite(qa.x) && nh_q_finite(qa.y) && nh_q_finite(qa.z) && nh_q_finite(qa.s)));
+		float bt = max_t;
+		uint32_t bc = NH_Q_NONE;
+		nh_f3 bn = nh_make3(0.0f, 0.0f, 0.0f);
+		const nh_f3 inv = nh_make3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+		const nh_f3 e = ray ? nh_make3(0.0f, 0.0f, 0.0f) : nh_q_box_extent(qa, h);
+		const float s = nh_q_cast_pad(o, fmaxf(fmaxf(e.x, e.y), e.z));
+		const nh_f3 w = nh_make3(e.x + s, e.y + s, e.z + s);
+		uint32_t node = ok && n ? 0u : NH_Q_NONE;
+		while (node != NH_Q_NONE) {
+			const float4 na = nodes[node].a, nb = nodes[node].b;
+			float t0;
+			const bool enter = nh_q_cast_node3(nh_make3(na.x, na.y, na.z), nh_make3(nb.x, nb.y, nb.z), o, inv, w, t0) && t0 <= bt;
+			const uint32_t left = __float_as_uint(na.w);
+			const uint32_t rope = __float_as_uint(nb.w);
+			if (!enter) { node = rope; continue; }
+			if (!(left & NH_Q_LEAF)) { node = left; continue; }
+			node = rope;
+			const uint32_t c = left & ~NH_Q_LEAF;
+			const nh_QRec q = rec[c];
+			if (__float_as_uint(q.a.w) == ignore) continue;
+			const nh_f3 p = nh_make3(q.a.x, q.a.y, q.a.z);
+			nh_QHit hh = c < nbox ? nh_q_sweep_box_box(o, d, qa, h, p, nh_quat{ q.b.x, q.b.y, q.b.z, q.b.w }, nh_make3(q.c.x, q.c.y, q.c.z))
+			                      : nh_q_sweep_box_sphere(o, d, qa, h, p, q.c.x);
+			if (!ray && t0 > hh.t) hh.t = t0;
+			if (hh.hit && nh_q_better(hh.t, c, max_t, bt, bc)) {
+				bt = hh.t; bc = c; bn = hh.n;
+				if (any_hit) break;
+			}
+		}
+		nh_RayHit out;
+		if (bc == NH_Q_NONE) {
+			out.t = ok ? max_t : __uint_as_float(0x7fc00000u);
+			out.normal[0] = out.normal[1] = out.normal[2] = 0.0f;
+			out.body = out.collider = out.tag = NH_Q_NONE;
+			out.shape = NH_SHAPE_NONE;
+		} else {
+			const nh_QRec q = rec[bc];
+			out.t = bt; out.normal[0] = bn.x; out.normal[1] = bn.y; out.normal[2] = bn.z;
+			out.body = __float_as_uint(q.a.w);
+			out.collider = bc < nbox ? bc : bc - nbox;
+			out.shape = bc < nbox ? NH_SHAPE_BOX : NH_SHAPE_SPHERE;
+			out.tag = __float_as_uint(q.c.w);
+		}
+		float4* hp = reinterpret_cast<float4*>(hits + i);
+		hp[0] = make_float4(out.t, out.normal[0], out.normal[1], out.normal[2]);
+		hp[1] = make_float4(__uint_as_float(out.body), __uint_as_float(out.collider), __uint_as_float(out.shape), __uint_as_float(out.tag));
+	}
+}
+
 // ---- overlap ---------------------------------------------------------------------------------------------------------------------------------
 // nh_overlap is a chain of launches with kernel boundaries as the only hand-offs; no atomic decides where a record goes:
 //   k_q_overlap<false>  one lane per query: the tree walk of k_q_raycast (stackless, escape links) with the query's padded world AABB, the exact
@@ -515,6 +581,18 @@ extern "C" int nh_spherecast(nh_context* ctx, const nh_SphereCast* casts, uint32
 	NH_HIP_CHECK(ctx, hipSetDevice(ctx->device));
 	nh_QueryState* q = ctx->query;
 	NH_LAUNCH(ctx, "q_spherecast", k_q_spherecast, nh_grid_for(count, 256, 1u << 20), 256, casts, count, hits, q->nodes, q->rec, q->n, q->nbox,
+	          (flags & NH_RAY_ANY_HIT) ? 1u : 0u);
+	return NH_OK;
+}
+
+extern "C" int nh_boxcast(nh_context* ctx, const nh_BoxCast* casts, uint32_t count, nh_RayHit* hits, uint32_t flags) {
+	if (!ctx || !ctx->query || !ctx->query->built) return NH_ERR_INVALID;
+	if (flags & ~(uint32_t)NH_RAY_ANY_HIT) return NH_ERR_INVALID;
+	if (count == 0u) return NH_OK;
+	if (!casts || !hits || (((uintptr_t)casts | (uintptr_t)hits) & 15u)) return NH_ERR_INVALID;    // (records are moved as 16-byte words)
+	NH_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+	nh_QueryState* q = ctx->query;
+	NH_LAUNCH(ctx, "q_boxcast", k_q_boxcast, nh_grid_for(count, 256, 1u << 20), 256, casts, count, hits, q->nodes, q->rec, q->n, q->nbox,
 	          (flags & NH_RAY_ANY_HIT) ? 1u : 0u);
 	return NH_OK;
 }

@@ -43,7 +43,7 @@ EXPORTS = [
     "nh_partition_top_speed", "nh_partition_set_peer_speeds", "nh_partition_refresh_is_quiet", "nh_partition_mark_ghosts", "nh_partition_pack_deltas", "nh_partition_unpack_deltas",
     "nh_partition_pack_momentum", "nh_partition_unpack_momentum", "nh_partition_exchange_iteration", "nh_partition_unpack_ghosts", "nh_partition_pack_step", "nh_partition_unpack_step", "nh_partition_choose_cut", "nh_partition_set_cut",
     "nh_partition_set_transport", "nh_partition_exchange_step", "nh_partition_step", "nh_partition_transport_check", "nh_partition_transport_result", "nh_set_first_ghost_body",
-    "nh_query_build", "nh_raycast", "nh_overlap", "nh_spherecast",
+    "nh_query_build", "nh_raycast", "nh_overlap", "nh_spherecast", "nh_boxcast",
 ]
 HALO_RECORD_BYTES = 64
 
@@ -122,12 +122,19 @@ class SphereCast(C.Structure):
                 ("reserved", C.c_uint32 * 3)]
 
 
+class BoxCast(C.Structure):
+    _fields_ = [("origin", C.c_float * 3), ("max_t", C.c_float), ("direction", C.c_float * 3), ("ignore_body", C.c_uint32), ("rotation", C.c_float * 4),
+                ("size", C.c_float * 3), ("reserved", C.c_uint32)]
+
+
 # scene queries (include/nudge_hip.h, "scene queries"): nh_RayHit.shape, nh_raycast flags; numpy forms of the two records
 NH_SHAPE_BOX, NH_SHAPE_SPHERE, NH_SHAPE_NONE = 0, 1, 0xFFFFFFFF
 NH_RAY_ANY_HIT = 1
 RAY = np.dtype([("origin", "<f4", 3), ("max_t", "<f4"), ("direction", "<f4", 3), ("ignore_body", "<u4")])
 RAY_HIT = np.dtype([("t", "<f4"), ("normal", "<f4", 3), ("body", "<u4"), ("collider", "<u4"), ("shape", "<u4"), ("tag", "<u4")])
 SPHERE_CAST = np.dtype([("origin", "<f4", 3), ("max_t", "<f4"), ("direction", "<f4", 3), ("ignore_body", "<u4"), ("radius", "<f4"), ("reserved", "<u4", 3)])
+BOX_CAST = np.dtype([("origin", "<f4", 3), ("max_t", "<f4"), ("direction", "<f4", 3), ("ignore_body", "<u4"), ("rotation", "<f4", 4), ("size", "<f4", 3),
+                     ("reserved", "<u4")])
 OVERLAP_QUERY = np.dtype([("center", "<f4", 3), ("shape", "<u4"), ("rotation", "<f4", 4), ("size", "<f4", 3), ("ignore_body", "<u4")])
 OVERLAP_HIT = np.dtype([("body", "<u4"), ("collider", "<u4"), ("shape", "<u4"), ("tag", "<u4")])
 NH_OVERLAP_OVERFLOW = 0xFFFFFFFF          # offsets[count] when the total is 2^32 - 1 or more
@@ -227,6 +234,7 @@ def lib():
         L.nh_query_build.argtypes = [C.c_void_p, C.POINTER(BodyData), C.POINTER(ColliderData)]
         L.nh_raycast.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
         L.nh_spherecast.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
+        L.nh_boxcast.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
         L.nh_overlap.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
         _LIB = L
     return _LIB
@@ -655,6 +663,48 @@ class World:
         casts.view(torch.int32)[:, 7] = (((ign & 0xFFFFFFFF) ^ 0x80000000) - 0x80000000).to(torch.int32)          # (the uint32 bits, as int32)
         casts[:, 8] = torch.as_tensor(radii, dtype=torch.float32, device=self.dev).reshape(-1)
         raw = self.spherecast_records(casts, any_hit=any_hit)
+        f = raw.view(torch.float32).reshape(n, 8)
+        u = raw.view(torch.int32).reshape(n, 8).to(torch.int64) & 0xFFFFFFFF
+        out = dict(t=f[:, 0], normal=f[:, 1:4], body=u[:, 4], collider=u[:, 5], shape=u[:, 6], tag=u[:, 7], raw=raw)
+        if synchronize:
+            torch.cuda.current_stream(self.dev).synchronize()
+        return out
+
+    def boxcast_records(self, casts, any_hit=False, hits=None):
+        """nh_boxcast on records already laid out as nh_BoxCast: `casts` a contiguous device tensor of count x 64 bytes (any dtype).  Returns the
+        count x 32-byte uint8 device tensor of nh_RayHit records (`hits`, or a new one)."""
+        torch = self.torch
+        n = casts.numel() * casts.element_size() // 64
+        if hits is None:
+            hits = torch.empty((n, 32), dtype=torch.uint8, device=self.dev)
+        _check(self.L, self.L.nh_boxcast(self.ctx, C.c_void_p(casts.data_ptr() if n else 0), n, C.c_void_p(hits.data_ptr() if n else 0),
+                                         NH_RAY_ANY_HIT if any_hit else 0), "nh_boxcast")
+        return hits
+
+    def boxcast(self, origins, directions, half_extents, rotations=None, max_t=float("inf"), ignore_body=None, any_hit=False, synchronize=False):
+        """Closest-hit (or any-hit) box casts against the last query_build(): the oriented box of `half_extents` ((n, 3) or (3,)) and `rotations`
+        ((n, 4) or (4,) quaternions (x, y, z, s); None = identity) swept, without turning, from `origins` along `directions` ((n, 3) each).  `max_t`,
+        `ignore_body` and the result are raycast()'s: t, normal (from the collider to the cast box), body, collider, shape, tag and `raw`.  Nothing
+        waits unless `synchronize`."""
+        torch = self.torch
+        o = torch.as_tensor(origins, dtype=torch.float32, device=self.dev).reshape(-1, 3)
+        d = torch.as_tensor(directions, dtype=torch.float32, device=self.dev).reshape(-1, 3)
+        n = o.shape[0]
+        if d.shape[0] != n:
+            raise ValueError(f"boxcast: {n} origins but {d.shape[0]} directions")
+        casts = torch.zeros((n, 16), dtype=torch.float32, device=self.dev)
+        casts[:, 0:3] = o
+        casts[:, 3] = torch.as_tensor(max_t, dtype=torch.float32, device=self.dev)
+        casts[:, 4:7] = d
+        ign = 0xFFFFFFFF if ignore_body is None else ignore_body
+        ign = torch.as_tensor(ign, dtype=torch.int64, device=self.dev)
+        casts.view(torch.int32)[:, 7] = (((ign & 0xFFFFFFFF) ^ 0x80000000) - 0x80000000).to(torch.int32)          # (the uint32 bits, as int32)
+        if rotations is None:
+            casts[:, 11] = 1.0
+        else:
+            casts[:, 8:12] = torch.as_tensor(rotations, dtype=torch.float32, device=self.dev).reshape(-1, 4)
+        casts[:, 12:15] = torch.as_tensor(half_extents, dtype=torch.float32, device=self.dev).reshape(-1, 3)
+        raw = self.boxcast_records(casts, any_hit=any_hit)
         f = raw.view(torch.float32).reshape(n, 8)
         u = raw.view(torch.int32).reshape(n, 8).to(torch.int64) & 0xFFFFFFFF
         out = dict(t=f[:, 0], normal=f[:, 1:4], body=u[:, 4], collider=u[:, 5], shape=u[:, 6], tag=u[:, 7], raw=raw)

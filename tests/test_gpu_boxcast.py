@@ -1,0 +1,366 @@
+"""Box casts on the GPU (pytest -m gpu): nh_boxcast (include/nudge_hip.h, "scene queries").
+
+The oracle is a brute force over every collider on the host with the same arithmetic (nudge_amd/csrc/nh_query.h through tests/hostboxcast_util.py)
+and the header's exact rules, so the tree's answer must equal it bit for bit in every field.  Size 0 must give nh_raycast's bytes, a start box that
+nh_overlap finds touching something must hit at t = 0, and casts are observers like the other queries."""
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import hostboxcast_util as B                 # noqa: E402
+import hostquery_util as Q                   # noqa: E402
+from test_gpu_query import OBSERVED, SMALL, _bounds, _rays, _same_stepped_world, _upload      # noqa: E402
+from nudge_amd import engine as E           # noqa: E402
+from nudge_amd import scenes as S           # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+NONE = 0xFFFFFFFF
+FUSED = E.NH_FLAG_SINGLE_APPLY | E.NH_FLAG_FUSED_STEP
+SIZES = (0.05, 0.5, 2.0)
+
+
+def _unit_quats(rng, n):
+    q = rng.normal(size=(n, 4))
+    return (q / np.linalg.norm(q, axis=1, keepdims=True)).astype(np.float32)
+
+
+def _casts(rays, size, rotation=None):
+    """nh_BoxCast records from rays: half extents `size` (a number, n values or (n, 3)), `rotation` (n, 4) or identity."""
+    c = np.zeros(len(rays), dtype=E.BOX_CAST)
+    for k in ("origin", "max_t", "direction", "ignore_body"):
+        c[k] = rays[k]
+    size = np.asarray(size, dtype=np.float32)
+    c["size"] = size.reshape(-1, 1) if size.ndim == 1 else size
+    if rotation is None:
+        c["rotation"][:, 3] = 1.0
+    else:
+        c["rotation"] = rotation
+    return c
+
+
+def _sweep(w, casts, any_hit=False):
+    raw = w.boxcast_records(_upload(w, casts), any_hit=any_hit)
+    return np.frombuffer(raw.cpu().numpy().tobytes(), dtype=E.RAY_HIT).copy()
+
+
+def _same_hits(got, ref, what):
+    bad = (got.view(np.uint8).reshape(-1, 32) != ref.view(np.uint8).reshape(-1, 32)).any(axis=1)
+    assert not bad.any(), f"{what}: {int(bad.sum())} of {len(ref)} hit records differ, first at {int(np.argmax(bad))}"
+
+
+def _check_world(w, scene, rng, n, what, sizes=SIZES):
+    w.query_build()
+    rec = Q.records(w.get_bodies()["transforms"], scene, w.nbox, w.nsph)
+    lo, hi = _bounds(rec)
+    share = []
+    for kind in ("random", "axis", "down"):
+        for h in sizes:
+            for rot in (None, _unit_quats(rng, n)):
+                casts = _casts(_rays(rng, n, lo, hi, kind), h, rot)
+                ref = B.boxcast(rec, w.nbox, casts)
+                _same_hits(_sweep(w, casts), ref, f"{what} / {kind} / size {h} / {'identity' if rot is None else 'rotated'}")
+                share.append(float((ref["shape"] != NONE).mean()))
+    return share
+
+
+@pytest.mark.parametrize("name", sorted(SMALL))
+def test_box_casts_equal_the_brute_force_before_and_after_stepping(name):
+    scene = SMALL[name]()
+    rng = np.random.default_rng(300 + sorted(SMALL).index(name))
+    w = E.World(scene, flags=FUSED)
+    assert max(_check_world(w, scene, rng, 8192, f"{name} initial")) > 0.05
+    w.step(50)
+    assert max(_check_world(w, scene, rng, 8192, f"{name} after 50 steps")) > 0.05
+    w.close()
+
+
+def test_degenerate_worlds():
+    scene = S.pile(4, 0, seed=3)
+    w = E.World(scene, flags=FUSED)
+    w.set_counts(len(scene["body_transforms"]), 1, 0)          # the ground slab alone (body 0)
+    rng = np.random.default_rng(31)
+    _check_world(w, scene, rng, 4096, "one collider")
+    w.close()
+
+    scene = S.pile(300, 300, seed=3)
+    nb = len(scene["body_transforms"])
+    w = E.World(scene, flags=FUSED)
+    w.set_counts(nb, 0, 300)
+    _check_world(w, scene, rng, 4096, "spheres only")
+    w.set_counts(nb, 301, 0)
+    _check_world(w, scene, rng, 4096, "boxes only")
+    w.close()
+
+    scene = S.pile(4096, 0, seed=3)
+    scene["body_transforms"]["position"][1:] = (0.25, 3.0, -0.5)        # every Morton key equal but the ground's
+    w = E.World(scene, flags=FUSED)
+    _check_world(w, scene, rng, 2048, "4096 coincident boxes")
+    w.close()
+
+
+def test_grazing_casts_beside_resting_boxes():
+    """Boxes that slide past a face of a resting box at the touching distance + offset, offsets 0 and +-1e-8 .. 1e-2, in the resting box's own
+    orientation (every edge pair parallel) and turned at random: the walk's pruning is tested where the node test and the predicate are closest."""
+    scene = S.stacks(64, 3, seed=5)
+    w = E.World(scene, flags=FUSED)
+    w.step(60)
+    w.query_build()
+    rec = Q.records(w.get_bodies()["transforms"], scene, w.nbox, w.nsph)
+    boxes = np.nonzero(rec["body"][: w.nbox] != 0)[0][:64]
+    offs = [0.0] + [s * 10.0 ** e for e in range(-8, -1) for s in (-1.0, 1.0)]
+    rng = np.random.default_rng(32)
+
+    def mat(q):
+        x, y, z, s = (float(v) for v in q)
+        return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - s * z), 2 * (x * z + s * y)], [2 * (x * y + s * z), 1 - 2 * (x * x + z * z), 2 * (y * z - s * x)],
+                         [2 * (x * z - s * y), 2 * (y * z + s * x), 1 - 2 * (x * x + y * y)]])
+
+    casts = []
+    for k, c in enumerate(boxes):
+        p, q, h = rec["p"][c].astype(np.float64), rec["q"][c], rec["h"][c].astype(np.float64)
+        R = mat(q)
+        for hc in (np.array([0.05, 0.05, 0.05]), np.array([0.3, 0.2, 0.4])):
+            for turned in (False, True):
+                qc = _unit_quats(rng, 1)[0] if turned else q
+                Rl = R.T @ mat(qc)                                  # the cast box's axes in the resting box's frame
+                ext = np.abs(Rl) @ hc                               # its support along each of those axes
+                for off in offs:
+                    a, b = k % 3, (k + 1) % 3                      # slide along axis a past the face of axis b
+                    for sb in (-1.0, 1.0):
+                        ol, dl = np.zeros(3), np.zeros(3)
+                        ol[a], ol[b], dl[a] = -(h[a] + ext[a] + 2.0), sb * (h[b] + ext[b] + off), 1.0
+                        casts.append((p + R @ ol, R @ dl, qc, hc))
+    c = np.zeros(len(casts), dtype=E.BOX_CAST)
+    c["origin"] = [o for o, _, _, _ in casts]
+    c["direction"] = [d for _, d, _, _ in casts]
+    c["rotation"] = [q for _, _, q, _ in casts]
+    c["size"] = [h for _, _, _, h in casts]
+    c["max_t"] = np.inf
+    c["ignore_body"] = NONE
+    ref = B.boxcast(rec, w.nbox, c)
+    _same_hits(_sweep(w, c), ref, "grazing")
+    assert (ref["shape"] != NONE).mean() > 0.1
+    w.close()
+
+
+@pytest.mark.parametrize("name", ["pile", "grid_tiles", "ball_pit"])
+def test_size_zero_equals_the_ray_cast(name):
+    scene = SMALL[name]()
+    w = E.World(scene, flags=FUSED)
+    w.step(20)
+    w.query_build()
+    rec = Q.records(w.get_bodies()["transforms"], scene, w.nbox, w.nsph)
+    lo, hi = _bounds(rec)
+    rng = np.random.default_rng(33)
+    for kind in ("random", "axis", "down"):
+        rays = _rays(rng, 32768, lo, hi, kind)
+        rays["max_t"][::3] = 7.0
+        rays["ignore_body"][::5] = rng.integers(0, 64, size=len(rays[::5]))
+        raw = w.raycast_records(_upload(w, rays))
+        ray_hits = np.frombuffer(raw.cpu().numpy().tobytes(), dtype=E.RAY_HIT)
+        rot = _unit_quats(rng, len(rays))
+        rot[::2] = np.nan                                       # (size 0 does not read the rotation)
+        _same_hits(_sweep(w, _casts(rays, 0.0, rot)), ray_hits, f"{name} / {kind}: size 0 against nh_raycast")
+    w.close()
+
+
+@pytest.mark.parametrize("name", ["pile", "grid_tiles"])
+def test_a_start_box_that_overlaps_hits_at_zero(name):
+    scene = SMALL[name]()
+    w = E.World(scene, flags=FUSED)
+    w.step(30)
+    w.query_build()
+    rec = Q.records(w.get_bodies()["transforms"], scene, w.nbox, w.nsph)
+    lo, hi = _bounds(rec)
+    rng = np.random.default_rng(34)
+    n = 16384
+    rays = _rays(rng, n, lo, hi, "random")
+    rays["origin"] = rng.uniform(lo, hi, size=(n, 3))
+    rays["ignore_body"][::4] = rng.integers(0, 64, size=len(rays[::4]))
+    size = rng.uniform(0.05, 1.5, size=(n, 3)).astype(np.float32)
+    rot = _unit_quats(rng, n)
+    casts = _casts(rays, size, rot)
+    got = _sweep(w, casts)
+    ov = w.overlap(rays["origin"], half_extents=size, rotations=rot, ignore_body=rays["ignore_body"].astype(np.int64), synchronize=True)
+    off = ov["offsets"].cpu().numpy()
+    touching = np.diff(off) > 0
+    assert touching.mean() > 0.05, touching.mean()
+    assert (got["t"][touching] == 0.0).all() and (got["shape"][touching] != NONE).all()
+    first = off[:-1][touching]
+    lowest = ov["collider"].cpu().numpy()[first] + np.where(ov["shape"].cpu().numpy()[first] == E.NH_SHAPE_SPHERE, w.nbox, 0)
+    mine = got["collider"][touching].astype(np.int64) + np.where(got["shape"][touching] == E.NH_SHAPE_SPHERE, w.nbox, 0)
+    assert (mine <= lowest).all()
+    _same_hits(got, B.boxcast(rec, w.nbox, casts), f"{name} start boxes")
+    w.close()
+
+
+@pytest.mark.parametrize("name", ["pile", "grid_tiles"])
+def test_any_hit_agrees_with_closest_hit_about_hit_or_miss(name):
+    scene = SMALL[name]()
+    w = E.World(scene, flags=FUSED)
+    w.step(30)
+    w.query_build()
+    rec = Q.records(w.get_bodies()["transforms"], scene, w.nbox, w.nsph)
+    lo, hi = _bounds(rec)
+    rng = np.random.default_rng(35)
+    for kind in ("random", "axis", "down"):
+        rays = _rays(rng, 16384, lo, hi, kind)
+        rays["max_t"] = rng.choice([np.inf, 5.0, 50.0], size=len(rays))
+        casts = _casts(rays, rng.uniform(0.1, 1.5, size=(len(rays), 3)), _unit_quats(rng, len(rays)))
+        closest, anyh = _sweep(w, casts), _sweep(w, casts, any_hit=True)
+        assert np.array_equal(closest["shape"] == NONE, anyh["shape"] == NONE), kind
+        miss = anyh["shape"] == NONE
+        assert anyh[miss].tobytes() == closest[miss].tobytes()
+        idx = np.nonzero(~miss)[0]
+        assert len(idx) > 100
+        assert (anyh["t"][idx] <= casts["max_t"][idx]).all()
+        for i in idx[:: max(1, len(idx) // 500)]:
+            c = int(anyh["collider"][i]) + (0 if anyh["shape"][i] == E.NH_SHAPE_BOX else w.nbox)
+            one = B.boxcast(rec, w.nbox, casts[i:i + 1], only=c)[0]
+            assert one.tobytes() == anyh[i].tobytes(), (kind, i)
+    w.close()
+
+
+def test_abi_edge_cases():
+    scene = S.pile(64, 16, seed=3)
+    w = E.World(scene, flags=FUSED)
+    L = w.L
+    casts = _casts(_rays(np.random.default_rng(36), 1024, (-5, -10, -5), (5, 300, 5), "random"), 0.5)
+    t = _upload(w, casts)
+    import torch
+    hits = torch.zeros((1025, 32), dtype=torch.uint8, device=w.dev)
+    hp = hits.data_ptr()
+    assert L.nh_boxcast(w.ctx, C.c_void_p(t.data_ptr()), 1024, C.c_void_p(hp), 0) == 1          # before any build: NH_ERR_INVALID
+    assert L.nh_boxcast(None, C.c_void_p(t.data_ptr()), 1024, C.c_void_p(hp), 0) == 1
+    w.query_build()
+    assert L.nh_boxcast(w.ctx, C.c_void_p(t.data_ptr()), 0, C.c_void_p(hp), 0) == 0            # count 0: a no-op
+    assert L.nh_boxcast(w.ctx, None, 0, None, 0) == 0
+    assert L.nh_boxcast(w.ctx, C.c_void_p(t.data_ptr()), 1024, None, 0) == 1                    # null hits / casts
+    assert L.nh_boxcast(w.ctx, None, 1024, C.c_void_p(hp), 0) == 1
+    assert L.nh_boxcast(w.ctx, C.c_void_p(t.data_ptr()), 1024, C.c_void_p(hp), 2) == 1           # unknown flags
+    assert L.nh_boxcast(w.ctx, C.c_void_p(t.data_ptr()), 1024, C.c_void_p(hp), 3) == 1
+    assert L.nh_boxcast(w.ctx, C.c_void_p(t.data_ptr() + 4), 1023, C.c_void_p(hp), 0) == 1       # misaligned casts / hits
+    assert L.nh_boxcast(w.ctx, C.c_void_p(t.data_ptr()), 1024, C.c_void_p(hp + 8), 0) == 1
+    w.torch.cuda.synchronize()
+    assert int(hits.sum()) == 0                                                                 # nothing was written
+    assert L.nh_boxcast(w.ctx, C.c_void_p(t.data_ptr()), 1024, C.c_void_p(hp), 1) == 0
+    w.torch.cuda.synchronize()
+    assert int(hits[1024].sum()) == 0                                                           # nothing behind the last record
+    w.close()
+
+
+def test_the_python_wrapper_writes_the_records_it_describes():
+    scene = S.pile(64, 16, seed=3)
+    w = E.World(scene, flags=FUSED)
+    w.step(10)
+    w.query_build()
+    rec = Q.records(w.get_bodies()["transforms"], scene, w.nbox, w.nsph)
+    rng = np.random.default_rng(37)
+    rays = _rays(rng, 2048, *_bounds(rec), "random")
+    size = rng.uniform(0.1, 1.0, size=(len(rays), 3)).astype(np.float32)
+    rot = _unit_quats(rng, len(rays))
+    rays["ignore_body"][::3] = 2
+    out = w.boxcast(rays["origin"], rays["direction"], size, rot, max_t=40.0, ignore_body=rays["ignore_body"].astype(np.int64), synchronize=True)
+    rays["max_t"] = 40.0
+    ref = B.boxcast(rec, w.nbox, _casts(rays, size, rot))
+    _same_hits(np.frombuffer(out["raw"].cpu().numpy().tobytes(), dtype=E.RAY_HIT), ref, "World.boxcast")
+    assert np.array_equal(out["collider"].cpu().numpy(), ref["collider"].astype(np.int64))
+    out = w.boxcast(rays["origin"], rays["direction"], (0.5, 0.5, 0.5), synchronize=True)        # rotations=None: identity
+    rays["max_t"] = np.inf
+    rays["ignore_body"] = NONE
+    _same_hits(np.frombuffer(out["raw"].cpu().numpy().tobytes(), dtype=E.RAY_HIT), B.boxcast(rec, w.nbox, _casts(rays, 0.5)), "World.boxcast, identity")
+    w.close()
+
+
+# ---- observers -----------------------------------------------------------------------------------------------------------------------------
+def _query(w, casts_t, hits_t):
+    w.query_build()
+    w.boxcast_records(casts_t, hits=hits_t)
+    w.boxcast_records(casts_t, any_hit=True, hits=hits_t)
+
+
+@pytest.mark.parametrize("name", sorted(OBSERVED))
+def test_box_casts_between_calls_change_nothing(name):
+    scene = OBSERVED[name]()
+    rng = np.random.default_rng(38)
+    casts = _casts(_rays(rng, 4096, (-30, -12, -30), (30, 20, 30), "random"), 0.5, _unit_quats(rng, 4096))
+    # between nh_step calls
+    a, b = E.World(scene, flags=FUSED), E.World(scene, flags=FUSED)
+    ct = _upload(a, casts)
+    ht = a.torch.empty((4096, 32), dtype=a.torch.uint8, device=a.dev)
+    done = 0
+    for k in [1, 2, 3, 5, 7, 4, 8] * 10:
+        k = min(k, 300 - done)
+        if k <= 0:
+            break
+        _query(a, ct, ht)
+        a.step(k)
+        b.step(k)
+        done += k
+    _query(a, ct, ht)
+    _same_stepped_world(a, b, f"{name} nh_step")
+    if name == "grid_tiles":
+        assert a.counts()["still_steps"] > 0, a.counts()
+    a.close(); b.close()
+    # between every call of the fused step
+    a, b = E.World(scene, flags=FUSED), E.World(scene, flags=FUSED)
+    ct = _upload(a, casts)
+    ht = a.torch.empty((4096, 32), dtype=a.torch.uint8, device=a.dev)
+    for s in range(300):
+        for call in ("collide", "gravity", "read_cache", "setup", "apply", "update", "write_cache", "advance"):
+            _query(a, ct, ht)
+            getattr(a, call)()
+            getattr(b, call)()
+        a.step_done(); b.step_done()
+    _query(a, ct, ht)
+    _same_stepped_world(a, b, f"{name} call by call")
+    if name == "grid_tiles":
+        assert a.counts()["still_steps"] > 0, a.counts()
+    a.close(); b.close()
+
+
+# ---- at size -------------------------------------------------------------------------------------------------------------------------------
+def test_a_million_box_casts_on_the_landed_config_2_world():
+    scene = S.grid_tiles(124, side=90, seed=2, lattice_cols=11)
+    nb = len(scene["body_transforms"])
+    n_tiles = len(scene["tile_of_static"])
+    w = E.World(scene, flags=FUSED, max_contacts=6 * nb)
+    w.step(70)
+    assert w.counts()["error"] == 0
+    w.query_build()
+    rec = Q.records(w.get_bodies()["transforms"], scene)
+    lo, hi = _bounds(rec)
+    rng = np.random.default_rng(39)
+    n = 1 << 20
+    nd = n // 2
+    tile = rng.integers(0, n_tiles, size=nd)
+    centre = scene["box_transforms"]["position"][tile].astype(np.float64)
+    half = scene["box_data"]["size"][tile, 0].astype(np.float64) - 2.5          # (a box of half extent <= 1 stays inside its tile's footprint)
+    down = np.zeros(nd, dtype=E.RAY)
+    down["origin"][:, 0] = centre[:, 0] + rng.uniform(-1, 1, size=nd) * half
+    down["origin"][:, 1] = 20.0
+    down["origin"][:, 2] = centre[:, 2] + rng.uniform(-1, 1, size=nd) * half
+    down["direction"] = (0.0, -1.0, 0.0)
+    down["max_t"] = np.inf
+    down["ignore_body"] = NONE
+    rays = np.concatenate([down, _rays(rng, n // 4, lo, hi, "random"), _rays(rng, n - nd - n // 4, lo, hi, "axis")])
+    rot = _unit_quats(rng, n)
+    rot[: n // 4] = (0.0, 0.0, 0.0, 1.0)
+    casts = _casts(rays, rng.choice(np.float32([0.25, 0.5, 0.75]), size=(n, 3)), rot)
+    got = _sweep(w, casts)
+    g = got[:nd]
+    assert (g["shape"] != NONE).all()
+    slab = g["body"] == 0
+    assert (g["collider"][slab] == tile[slab]).all()
+    tob = scene["tile_of_body"]
+    assert (tob[g["body"][~slab]] == tile[~slab]).all()
+    assert (~slab).mean() > 0.2
+    # 1024 casts spread over the batch, bit for bit against the brute force over all 1,004,524 colliders
+    pick = np.linspace(0, n - 1, 1024).astype(np.int64)
+    _same_hits(got[pick], B.boxcast(rec, w.nbox, casts[pick]), "config 2, 1 M box casts")
+    w.close()
