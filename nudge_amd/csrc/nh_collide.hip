@@ -1278,7 +1278,7 @@ __global__ __launch_bounds__(256) void k_narrowphase(nh_DevState* __restrict__ s
 				for (int index = 0; index < 16; ++index) {
 					if (((bb.mask >> index) & 1u) && k < count) {
 						nh_contact_out o;
-						nh_bb_contact(bb, index, bb.lx[index], bb.ly[index], bb.lz[index], bb.penetration[index], bb.tags[index], o);
+						nh_bb_contact(bb, index, bb.fx[index], bb.fy[index], bb.fz[index], bb.penetration[index], bb.tags[index], o);
 						put(k, o);
 						++k;
 					}
@@ -1519,7 +1519,7 @@ __global__ __launch_bounds__(256) void k_pair_begin(nh_DevState* __restrict__ st
 				for (int index = 0; index < 16; ++index) {
 					if (((bb.mask >> index) & 1u) && k < count) {
 						nh_contact_out o;
-						nh_bb_contact(bb, index, bb.lx[index], bb.ly[index], bb.lz[index], bb.penetration[index], bb.tags[index], o);
+						nh_bb_contact(bb, index, bb.fx[index], bb.fy[index], bb.fz[index], bb.penetration[index], bb.tags[index], o);
 						float4* dp = reinterpret_cast<float4*>(raw_data + base + k);
 						dp[0] = make_float4(o.px, o.py, o.pz, o.penetration); dp[1] = make_float4(o.nx, o.ny, o.nz, o.friction);
 						raw_feature[base + k] = o.feature;

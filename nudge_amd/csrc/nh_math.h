@@ -108,10 +108,26 @@ __device__ __forceinline__ float nh_rsqrt_guarded_z(float x) {
 	if (__builtin_expect(bad != 0, 0)) r = nh_rsqrt(x);
 	return r;
 }
+// N independent reciprocals behind ONE ballot and one branch (the face clip of the narrowphase takes five at once).  Each short result
+// whose predicate holds is already the exact one, so recomputing ALL N exactly when any lane's any value fails gives the same bits as N
+// separate nh_recip_guarded -- the proof obligation above, tests/fastmath/exhaustive.hip.
+template <int N> __device__ __forceinline__ void nh_recip_guarded_n(float (&x)[N]) {
+	float r[N];
+	bool bad = false;
+#pragma unroll
+	for (int k = 0; k < N; ++k) { r[k] = nh_recip_fast_z(x[k]); bad |= nh_recip_fast_z_bad(r[k]); }
+	if (__builtin_expect(__builtin_amdgcn_ballot_w64(bad) != 0, 0)) {
+#pragma unroll
+		for (int k = 0; k < N; ++k) r[k] = nh_recip(x[k]);
+	}
+#pragma unroll
+	for (int k = 0; k < N; ++k) x[k] = r[k];
+}
 #else
 NH_HD float nh_rsqrt_guarded(float x) { return nh_rsqrt(x); }
 NH_HD float nh_recip_guarded(float x) { return nh_recip(x); }
 NH_HD float nh_rsqrt_guarded_z(float x) { return nh_rsqrt(x); }
+template <int N> NH_HD void nh_recip_guarded_n(float (&x)[N]) { for (int k = 0; k < N; ++k) x[k] = nh_recip(x[k]); }
 #endif
 
 // x86 cvttps2dq semantics (nudge.cpp:336-338): truncate; out of range or NaN -> 0x80000000.

@@ -52,8 +52,9 @@ struct nh_bb_result {
 	int swapped;
 	unsigned mask;
 	unsigned tag_swap;
+	unsigned a_face;
 	nh_contact_out edge;
-	float lx[16], ly[16], lz[16], penetration[16];   // candidate points in a's local frame
+	float fx[16], fy[16], fz[16], penetration[16];   // candidate points in a's local frame, axes rotated to (X', Y', Z') = (a_face+1, a_face+2, a_face) % 3
 	uint32_t tags[16];
 	float w0[3], w1[3], w2[3], wn[3], apos[3];
 };
@@ -64,9 +65,16 @@ NH_HD int nh_bb_count(const nh_bb_result& r) {
 	return 0;
 }
 
-// materialise candidate `index` (0..15) of a face result (nudge.cpp:2095-2108)
-NH_HD void nh_bb_contact(const nh_bb_result& r, int index, float lx, float ly, float lz, float pen, uint32_t tag, nh_contact_out& o) {
+// selects v[k] for a per-lane k in 0..2 without indexing a private array (which would put it in scratch memory)
+NH_HD float nh_pick3(unsigned k, float v0, float v1, float v2) { return k == 0 ? v0 : (k == 1 ? v1 : v2); }
+
+// materialise candidate `index` (0..15) of a face result (nudge.cpp:2095-2108).  (fx, fy, fz) is the candidate in the a_face frame:
+// only the contacts that are emitted are permuted back to a's local axes (nudge.cpp:2021-2026).
+NH_HD void nh_bb_contact(const nh_bb_result& r, int index, float fx, float fy, float fz, float pen, uint32_t tag, nh_contact_out& o) {
 	(void)index;
+	const float lx = nh_pick3(r.a_face, fz, fy, fx);
+	const float ly = nh_pick3(r.a_face, fx, fz, fy);
+	const float lz = nh_pick3(r.a_face, fy, fx, fz);
 	o.px = r.w0[0] * lx + r.w1[0] * ly + r.w2[0] * lz + r.apos[0];
 	o.py = r.w0[1] * lx + r.w1[1] * ly + r.w2[1] * lz + r.apos[1];
 	o.pz = r.w0[2] * lx + r.w1[2] * ly + r.w2[2] * lz + r.apos[2];
@@ -143,8 +151,8 @@ NH_HD void nh_box_box_edge(const nh_xform& A, const nh_xform& B, const float* sa
 	unsigned ea = edge & 0xffffu, eb = edge >> 16;
 	unsigned ra = (ea & 2u) ? 2u : ((ea & 1u) ? 1u : 0u);
 	unsigned rb = (eb & 2u) ? 2u : ((eb & 1u) ? 1u : 0u);
-	float ux = ab[ra * 3 + 0], uy = ab[ra * 3 + 1], uz = ab[ra * 3 + 2];
-	float vx = bb[rb * 3 + 0], vy = bb[rb * 3 + 1], vz = bb[rb * 3 + 2];
+	float ux = nh_pick3(ra, ab[0], ab[3], ab[6]), uy = nh_pick3(ra, ab[1], ab[4], ab[7]), uz = nh_pick3(ra, ab[2], ab[5], ab[8]);
+	float vx = nh_pick3(rb, bb[0], bb[3], bb[6]), vy = nh_pick3(rb, bb[1], bb[4], bb[7]), vz = nh_pick3(rb, bb[2], bb[5], bb[8]);
 
 	float nx = uy * vz - uz * vy;
 	float ny = uz * vx - ux * vz;
@@ -272,40 +280,53 @@ NH_HD void nh_box_box_eval(nh_xform A, nh_xform B, const float* size_a, const fl
 	unsigned a_edge = 0, b_edge = 0;
 	{
 		float epa[9], epb[9];
-		for (unsigned i = 0; i < 3; ++i) {
-			float acx = a_to_b[0 * 3 + i], acy = a_to_b[1 * 3 + i], acz = a_to_b[2 * 3 + i];
-			float bcx = a_to_b[i * 3 + 0], bcy = a_to_b[i * 3 + 1], bcz = a_to_b[i * 3 + 2];
-			float ac2x = acx * acx, ac2y = acy * acy, ac2z = acz * acz;
-			float bc2x = bcx * bcx, bc2y = bcy * bcy, bc2z = bcz * bcz;
-			float aacx = nh_abs(acx), aacy = nh_abs(acy), aacz = nh_abs(acz);
-			float abcx = nh_abs(bcx), abcy = nh_abs(bcy), abcz = nh_abs(bcz);
-			float r_a0 = ac2y + ac2z, r_a1 = ac2z + ac2x, r_a2 = ac2x + ac2y;
-			float r_b0 = bc2y + bc2z, r_b1 = bc2z + bc2x, r_b2 = bc2x + bc2y;
-			const float nan_threshold = 1e-3f;
-			// rsqrt OR all-ones when r <= threshold -> NaN (nudge.cpp:1613-1619)
-			const float qnan = nh_asfloat(0xffffffffu);
-			r_a0 = (r_a0 <= nan_threshold) ? qnan : nh_rsqrt_guarded((r_a0 <= nan_threshold) ? 1.0f : r_a0);
-			r_a1 = (r_a1 <= nan_threshold) ? qnan : nh_rsqrt_guarded((r_a1 <= nan_threshold) ? 1.0f : r_a1);
-			r_a2 = (r_a2 <= nan_threshold) ? qnan : nh_rsqrt_guarded((r_a2 <= nan_threshold) ? 1.0f : r_a2);
-			r_b0 = (r_b0 <= nan_threshold) ? qnan : nh_rsqrt_guarded((r_b0 <= nan_threshold) ? 1.0f : r_b0);
-			r_b1 = (r_b1 <= nan_threshold) ? qnan : nh_rsqrt_guarded((r_b1 <= nan_threshold) ? 1.0f : r_b1);
-			r_b2 = (r_b2 <= nan_threshold) ? qnan : nh_rsqrt_guarded((r_b2 <= nan_threshold) ? 1.0f : r_b2);
-			float pa0 = aacy * sa[2] + aacz * sa[1];
-			float pa1 = aacz * sa[0] + aacx * sa[2];
-			float pa2 = aacx * sa[1] + aacy * sa[0];
-			float pb0 = abcy * sb[2] + abcz * sb[1];
-			float pb1 = abcz * sb[0] + abcx * sb[2];
-			float pb2 = abcx * sb[1] + abcy * sb[0];
-			float o0 = nh_abs(acy * b_offset.z - acz * b_offset.y);
-			float o1 = nh_abs(acz * b_offset.x - acx * b_offset.z);
-			float o2 = nh_abs(acx * b_offset.y - acy * b_offset.x);
-			epa[i * 3 + 0] = (pa0 - o0) * r_a0;
-			epa[i * 3 + 1] = (pa1 - o1) * r_a1;
-			epa[i * 3 + 2] = (pa2 - o2) * r_a2;
-			epb[i * 3 + 0] = pb0 * r_b0;
-			epb[i * 3 + 1] = pb1 * r_b1;
-			epb[i * 3 + 2] = pb2 * r_b2;
-		}
+		const float nan_threshold = 1e-3f;
+		const float qnan = nh_asfloat(0xffffffffu);
+		auto edge_axes = [&](auto root) {
+#pragma unroll
+			for (unsigned i = 0; i < 3; ++i) {
+				float acx = a_to_b[0 * 3 + i], acy = a_to_b[1 * 3 + i], acz = a_to_b[2 * 3 + i];
+				float bcx = a_to_b[i * 3 + 0], bcy = a_to_b[i * 3 + 1], bcz = a_to_b[i * 3 + 2];
+				float ac2x = acx * acx, ac2y = acy * acy, ac2z = acz * acz;
+				float bc2x = bcx * bcx, bc2y = bcy * bcy, bc2z = bcz * bcz;
+				float aacx = nh_abs(acx), aacy = nh_abs(acy), aacz = nh_abs(acz);
+				float abcx = nh_abs(bcx), abcy = nh_abs(bcy), abcz = nh_abs(bcz);
+				float r_a0 = ac2y + ac2z, r_a1 = ac2z + ac2x, r_a2 = ac2x + ac2y;
+				float r_b0 = bc2y + bc2z, r_b1 = bc2z + bc2x, r_b2 = bc2x + bc2y;
+				// rsqrt OR all-ones when r <= threshold -> NaN (nudge.cpp:1613-1619)
+				r_a0 = (r_a0 <= nan_threshold) ? qnan : root((r_a0 <= nan_threshold) ? 1.0f : r_a0);
+				r_a1 = (r_a1 <= nan_threshold) ? qnan : root((r_a1 <= nan_threshold) ? 1.0f : r_a1);
+				r_a2 = (r_a2 <= nan_threshold) ? qnan : root((r_a2 <= nan_threshold) ? 1.0f : r_a2);
+				r_b0 = (r_b0 <= nan_threshold) ? qnan : root((r_b0 <= nan_threshold) ? 1.0f : r_b0);
+				r_b1 = (r_b1 <= nan_threshold) ? qnan : root((r_b1 <= nan_threshold) ? 1.0f : r_b1);
+				r_b2 = (r_b2 <= nan_threshold) ? qnan : root((r_b2 <= nan_threshold) ? 1.0f : r_b2);
+				float pa0 = aacy * sa[2] + aacz * sa[1];
+				float pa1 = aacz * sa[0] + aacx * sa[2];
+				float pa2 = aacx * sa[1] + aacy * sa[0];
+				float pb0 = abcy * sb[2] + abcz * sb[1];
+				float pb1 = abcz * sb[0] + abcx * sb[2];
+				float pb2 = abcx * sb[1] + abcy * sb[0];
+				float o0 = nh_abs(acy * b_offset.z - acz * b_offset.y);
+				float o1 = nh_abs(acz * b_offset.x - acx * b_offset.z);
+				float o2 = nh_abs(acx * b_offset.y - acy * b_offset.x);
+				epa[i * 3 + 0] = (pa0 - o0) * r_a0;
+				epa[i * 3 + 1] = (pa1 - o1) * r_a1;
+				epa[i * 3 + 2] = (pa2 - o2) * r_a2;
+				epb[i * 3 + 0] = pb0 * r_b0;
+				epb[i * 3 + 1] = pb1 * r_b1;
+				epb[i * 3 + 2] = pb2 * r_b2;
+			}
+		};
+#if defined(__HIP_DEVICE_COMPILE__)
+		// One guard for all 18 roots instead of one ballot and branch each: wherever the nh_rsqrt_fast_ok predicate holds, the short
+		// root IS the correctly rounded one (all 2^32 inputs, tests/fastmath/exhaustive.hip), so when any lane's any root fails it
+		// all 18 are recomputed with the exact form -- the same bits as 18 separate nh_rsqrt_guarded, one branch
+		bool bad = false;
+		edge_axes([&](float x) { const float r = nh_rsqrt_fast(x); bad |= !nh_rsqrt_fast_ok(r); return r; });
+		if (__builtin_expect(__builtin_amdgcn_ballot_w64(bad) != 0, 0)) edge_axes([](float x) { return nh_rsqrt(x); });
+#else
+		edge_axes([](float x) { return nh_rsqrt(x); });
+#endif
 		for (unsigned i = 0; i < 3; ++i) {
 			for (unsigned j = 0; j < 3; ++j) {
 				float p = epa[i * 3 + j] + epb[j * 3 + i];
@@ -337,7 +358,9 @@ NH_HD void nh_box_box_eval(nh_xform A, nh_xform B, const float* size_a, const fl
 	}
 
 	// ---- face-face clipping (nudge.cpp:1678-2112) ----
-	float dirs[3] = { nh_abs(a_to_b[a_face * 3 + 0]), nh_abs(a_to_b[a_face * 3 + 1]), nh_abs(a_to_b[a_face * 3 + 2]) };
+	// a_face is a per-lane value: everything it (or b_face) selects is picked with compile-time indices, so no array goes to scratch memory
+	float dirs[3] = { nh_abs(nh_pick3(a_face, a_to_b[0], a_to_b[3], a_to_b[6])), nh_abs(nh_pick3(a_face, a_to_b[1], a_to_b[4], a_to_b[7])),
+	                  nh_abs(nh_pick3(a_face, a_to_b[2], a_to_b[5], a_to_b[8])) };
 	float c0[3] = { a_to_b[0], a_to_b[3], a_to_b[6] };
 	float c1[3] = { a_to_b[1], a_to_b[4], a_to_b[7] };
 	float c2[3] = { a_to_b[2], a_to_b[5], a_to_b[8] };
@@ -359,17 +382,22 @@ NH_HD void nh_box_box_eval(nh_xform A, nh_xform B, const float* size_a, const fl
 	const float* dxv = c1;
 	const float* dyv = c2;
 
-	unsigned b_positive_face_bit = ((nh_asuint(bo[a_face]) ^ nh_asuint(c[a_face])) >> 31);
-	unsigned b_offset_neg = nh_signbit(bo[a_face]);
+	const float bo_face = nh_pick3(a_face, bo[0], bo[1], bo[2]);
+	unsigned b_positive_face_bit = ((nh_asuint(bo_face) ^ nh_asuint(nh_pick3(a_face, c[0], c[1], c[2]))) >> 31);
+	unsigned b_offset_neg = nh_signbit(bo_face);
 	if (!b_positive_face_bit) { c[0] = nh_neg(c[0]); c[1] = nh_neg(c[1]); c[2] = nh_neg(c[2]); }
 	c[0] += bo[0]; c[1] += bo[1]; c[2] += bo[2];
 
 	// quads[axis] = { a.size, c, dx, dy } ; transformed axes (nudge.cpp:1764-1778)
 	unsigned AX = (a_face + 1) % 3, AY = (a_face + 2) % 3, AZ = a_face;
-	float sx = sa[AX], sy = sa[AY], sz_ = sa[AZ];
-	float cx = c[AX], cy = c[AY], cz = c[AZ];
-	float dxx = dxv[AX], dxy_ = dxv[AY], dxz = dxv[AZ];
-	float dyx = dyv[AX], dyy = dyv[AY], dyz = dyv[AZ];
+	float sx = nh_pick3(AX, sa[0], sa[1], sa[2]), sy = nh_pick3(AY, sa[0], sa[1], sa[2]), sz_ = nh_pick3(AZ, sa[0], sa[1], sa[2]);
+	float cx = nh_pick3(AX, c[0], c[1], c[2]), cy = nh_pick3(AY, c[0], c[1], c[2]), cz = nh_pick3(AZ, c[0], c[1], c[2]);
+	float dxx = nh_pick3(AX, dxv[0], dxv[1], dxv[2]), dxy_ = nh_pick3(AY, dxv[0], dxv[1], dxv[2]), dxz = nh_pick3(AZ, dxv[0], dxv[1], dxv[2]);
+	float dyx = nh_pick3(AX, dyv[0], dyv[1], dyv[2]), dyy = nh_pick3(AY, dyv[0], dyv[1], dyv[2]), dyz = nh_pick3(AZ, dyv[0], dyv[1], dyv[2]);
+	// the five reciprocals of the clip (edge slopes of quad b, z-plane) behind one guard (nh_recip_guarded_n; 1 / +-0 = +-inf like 1.0f / x):
+	// rdxy[k] = 1 / dxyv[k] (nudge.cpp:1844-1898) and 1 / zn2, where zn2 = dxx * dyy - dxy_ * dyx (nudge.cpp:1973-2019)
+	float rcp5[5] = { dxx, dxy_, dyx, dyy, dxx * dyy - dxy_ * dyx };
+	nh_recip_guarded_n(rcp5);
 
 	float support_x[16], support_y[16], support_z[16];
 	float* penetrations = res.penetration;
@@ -407,7 +435,7 @@ NH_HD void nh_box_box_eval(nh_xform A, nh_xform B, const float* size_a, const fl
 
 		// edges of quad b against the bounds of quad a (nudge.cpp:1844-1898)
 		const float dxyv[4] = { dxx, dxy_, dyx, dyy };
-		float rdxy[4] = { 1.0f / dxyv[0], 1.0f / dxyv[1], 1.0f / dxyv[2], 1.0f / dxyv[3] };
+		const float rdxy[4] = { rcp5[0], rcp5[1], rcp5[2], rcp5[3] };
 		const int i0022[4] = { 0, 0, 2, 2 }, i1133[4] = { 1, 1, 3, 3 }, i2200[4] = { 2, 2, 0, 0 }, i3311[4] = { 3, 3, 1, 1 };
 		unsigned edge_axis_near = 0, edge_axis_far = 0;
 		bool mask_a[4], mask_b[4];
@@ -483,7 +511,7 @@ NH_HD void nh_box_box_eval(nh_xform A, nh_xform B, const float* size_a, const fl
 		float zn1 = dxz * dyx - dxx * dyz;
 		float zn2 = dxx * dyy - dxy_ * dyx;
 		float dotc = cx * zn0 + cy * zn1 + cz * zn2;
-		float inv = 1.0f / zn2;
+		float inv = rcp5[4];          // 1 / zn2
 		float plane0 = nh_neg(zn0) * inv, plane1 = nh_neg(zn1) * inv, plane2 = dotc * inv;
 		uint32_t z_sign = b_offset_neg ? 0x80000000u : 0u;
 		float half_signed = nh_xorf(0.5f, z_sign);
@@ -516,8 +544,7 @@ NH_HD void nh_box_box_eval(nh_xform A, nh_xform B, const float* size_a, const fl
 		w2[1] = (ky * qz + ks * qx) - 0.0f;
 		w2[2] = nh_neg((kx * qx + ky * qy) - 1.0f);
 	}
-	const float* wn_src = a_face == 0 ? w0 : (a_face == 1 ? w1 : w2);
-	float wn[3] = { wn_src[0], wn_src[1], wn_src[2] };
+	float wn[3] = { nh_pick3(a_face, w0[0], w1[0], w2[0]), nh_pick3(a_face, w0[1], w1[1], w2[1]), nh_pick3(a_face, w0[2], w1[2], w2[2]) };
 	if (b_offset_neg) { wn[0] = nh_neg(wn[0]); wn[1] = nh_neg(wn[1]); wn[2] = nh_neg(wn[2]); }
 
 	unsigned tag_swap = 0;
@@ -527,15 +554,10 @@ NH_HD void nh_box_box_eval(nh_xform A, nh_xform B, const float* size_a, const fl
 		wn[0] = nh_neg(wn[0]); wn[1] = nh_neg(wn[1]); wn[2] = nh_neg(wn[2]);
 	}
 
-	// local axes of the support blocks: X' = (a_face+1)%3, Y' = (a_face+2)%3, Z' = a_face (nudge.cpp:2021-2026);
-	// selected with compile-time indices so the candidate arrays stay in registers
+	// the candidates stay in the a_face frame (X' = (a_face+1)%3, Y' = (a_face+2)%3, Z' = a_face); nh_bb_contact permutes the emitted ones
 #pragma unroll
-	for (int i = 0; i < 16; ++i) {
-		float bx = support_x[i], by = support_y[i], bz = support_z[i];
-		res.lx[i] = a_face == 0 ? bz : (a_face == 1 ? by : bx);
-		res.ly[i] = a_face == 0 ? bx : (a_face == 1 ? bz : by);
-		res.lz[i] = a_face == 0 ? by : (a_face == 1 ? bx : bz);
-	}
+	for (int i = 0; i < 16; ++i) { res.fx[i] = support_x[i]; res.fy[i] = support_y[i]; res.fz[i] = support_z[i]; }
+	res.a_face = a_face;
 	for (int k = 0; k < 3; ++k) { res.w0[k] = w0[k]; res.w1[k] = w1[k]; res.w2[k] = w2[k]; res.wn[k] = wn[k]; }
 	res.apos[0] = A.px; res.apos[1] = A.py; res.apos[2] = A.pz;
 	res.kind = 2;
@@ -554,7 +576,7 @@ NH_HD nh_pair_result nh_box_box(nh_xform A, nh_xform B, const float* size_a, con
 	else if (r.kind == 2) {
 		for (int index = 0; index < 16; ++index) {
 			if (!((r.mask >> index) & 1u)) continue;
-			nh_bb_contact(r, index, r.lx[index], r.ly[index], r.lz[index], r.penetration[index], r.tags[index], out[res.count++]);
+			nh_bb_contact(r, index, r.fx[index], r.fy[index], r.fz[index], r.penetration[index], r.tags[index], out[res.count++]);
 		}
 	}
 	return res;
@@ -569,7 +591,7 @@ NH_HD int nh_sphere_sphere(float ra, float rb, const nh_xform& A, const nh_xform
 	if (l2 > r * r) return 0;
 	nh_f3 n;
 	float l = sqrtf(l2);
-	if (l2 > 1e-4f) n = dp * (1.0f / l);
+	if (l2 > 1e-4f) n = dp * nh_recip_guarded(l);
 	else n = nh_make3(1.0f, 0.0f, 0.0f);
 	nh_f3 p = nh_make3(A.px, A.py, A.pz) + n * (l - rb);
 	out->px = p.x; out->py = p.y; out->pz = p.z;
@@ -601,7 +623,7 @@ NH_HD int nh_box_sphere(const float* size, float radius, const nh_xform& A, cons
 		float l2 = nh_dot(dp, dp);
 		if (l2 > r * r) return 0;
 		float l = sqrtf(l2);
-		float m = 1.0f / l;
+		float m = nh_recip_guarded(l);
 		n = dp * m;
 		penetration = r - l;
 	} else if (w - dx < h - dy && w - dx < d - dz) {

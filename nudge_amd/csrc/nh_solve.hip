@@ -1442,7 +1442,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MAXC ==
 								for (int index = 0; index < 16; ++index) {
 									if (((bb.mask >> index) & 1u) && k < pp_count && k < M) {
 										nh_contact_out o;
-										nh_bb_contact(bb, index, bb.lx[index], bb.ly[index], bb.lz[index], bb.penetration[index], bb.tags[index], o);
+										nh_bb_contact(bb, index, bb.fx[index], bb.fy[index], bb.fz[index], bb.penetration[index], bb.tags[index], o);
 										stage[k].c0 = make_float4(o.px, o.py, o.pz, o.penetration); stage[k].c1 = make_float4(o.nx, o.ny, o.nz, o.friction); stage[k].w.x = __uint_as_float(o.feature);
 										scid[lane * M + k] = still_base + (uint32_t)k;
 										++k;
