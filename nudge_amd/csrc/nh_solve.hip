@@ -1207,10 +1207,16 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MAXC ==
 		nh_row1 r[M];
 		nh_state s[M];
 		bool is_a[M];
+		// the sweeps divide with nh_div_deferred and take ONE verdict at their end (nh_solver.h); a wave that must solve again exactly starts from the
+		// velocity and the warm start's inputs (the states, unfused) kept here -- LDS cannot keep them: AHEAD lands the collider there during the sweeps
+		nh_div_deferred dd;
+		const nh_vel v0 = v;
+		nh_state w0[M];
 		// phase B: rows, and (fused) the warm start in slot order
 #pragma unroll
 		for (int q = 0; q < M; ++q) {
 			is_a[q] = false;
+			w0[q].normal = 0.0f; w0[q].friction_x = 0.0f; w0[q].friction_y = 0.0f;
 			if ((uint32_t)q < cnt) {
 				const nh_ob_slot o = slot[lane * M + (STILL ? sl[q] : (uint32_t)q)];
 				const uint32_t flags = STILL ? 0u : __float_as_uint(o.w.w);
@@ -1228,9 +1234,11 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MAXC ==
 						const float4 found = cache_search(cv.ctags, cv.cfeatures, cv.cdata, m, h != NH_HINT_NONE ? h + (cid[q] - first) : cid[q], cv.tags[cid[q]], cv.features[cid[q]]);
 						wx = found.x; wy = found.y; wz = found.z;
 					}
-					nh_warm_start1(r[q], wx, wy, wz, v, is_a[q], s[q]);
+					w0[q].normal = wx; w0[q].friction_x = wy; w0[q].friction_y = wz;
+					nh_warm_start1(r[q], wx, wy, wz, v, is_a[q], s[q], dd);
 				} else {
-					s[q].normal = o.w.x; s[q].friction_x = o.w.y; s[q].friction_y = o.w.z;
+					w0[q].normal = o.w.x; w0[q].friction_x = o.w.y; w0[q].friction_y = o.w.z;
+					s[q] = w0[q];
 				}
 			}
 		}
@@ -1269,18 +1277,34 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MAXC ==
 			nh_glds16(av.fat_box + 2u * (size_t)cc, &s_ah[128u + lane]); nh_glds16(av.fat_box + 2u * (size_t)cc + 1u, &s_ah[192u + lane]);
 			nh_glds16(sp4, &s_ah[256u + lane]);
 		}
-		if (CONTIG && __builtin_amdgcn_ballot_w64(mine && (STILL ? (still_has && (br & NH_BODY_REC_IS_A) != 0) : ((sp.y >> 28) & 1u) != 0)) == 0) {
-			for (uint32_t it = 0; it < iterations; ++it) {
+		const bool none_a = CONTIG && __builtin_amdgcn_ballot_w64(mine && (STILL ? (still_has && (br & NH_BODY_REC_IS_A) != 0) : ((sp.y >> 28) & 1u) != 0)) == 0;
+		auto sweeps = [&](auto& div) {
+			if (none_a) {
+				for (uint32_t it = 0; it < iterations; ++it) {
 #pragma unroll
-				for (int q = 0; q < M; ++q)
-					if ((uint32_t)q < cnt) nh_apply_one1(r[q], s[q], v, false);
-			}
-		} else {
-			for (uint32_t it = 0; it < iterations; ++it) {
+					for (int q = 0; q < M; ++q)
+						if ((uint32_t)q < cnt) nh_apply_one1(r[q], s[q], v, false, div);
+				}
+			} else {
+				for (uint32_t it = 0; it < iterations; ++it) {
 #pragma unroll
-				for (int q = 0; q < M; ++q)
-					if ((uint32_t)q < cnt) nh_apply_one1(r[q], s[q], v, is_a[q]);
+					for (int q = 0; q < M; ++q)
+						if ((uint32_t)q < cnt) nh_apply_one1(r[q], s[q], v, is_a[q], div);
+				}
 			}
+		};
+		sweeps(dd);
+		if (__builtin_expect(dd.bad != 0ull, 0)) {
+			nh_div_exact ex;
+			v = v0;
+#pragma unroll
+			for (int q = 0; q < M; ++q) {
+				if ((uint32_t)q < cnt) {
+					if (FUSED) nh_warm_start1(r[q], w0[q].normal, w0[q].friction_x, w0[q].friction_y, v, is_a[q], s[q], ex);
+					else s[q] = w0[q];
+				}
+			}
+			sweeps(ex);
 		}
 		// NH_FLAG_FUSED_STEP: the advance (k_advance) on the way out, from the transform held since phase A (7 registers; a reload would be a third exposed round trip)
 		float4 a0 = make_float4(0, 0, 0, 0), a1 = a0;

@@ -35,6 +35,33 @@ NH_HD float nh_recip_s(float x) { return nh_recip_guarded(x); }
 NH_HD float nh_rsqrt_s(float x) { return nh_rsqrt_guarded_z(x); }
 #endif
 
+// How the sweeps (nh_warm_start1 / nh_apply_one1) divide, a policy argument so that every form runs the same arithmetic around it:
+//   nh_div_exact    -- nh_recip / nh_rsqrt
+//   nh_div_deferred -- the short sequences of nh_math.h with NO verdict per call: the guards' own predicates (those of nh_recip_guarded /
+//                      nh_rsqrt_guarded_z) are ORed into `bad`, one bit per lane, and the caller takes one verdict for the whole body solve -- if any lane
+//                      of the wave flagged, it solves again from the start with nh_div_exact.  A lane that never flagged has the exact bits: whenever the
+//                      predicate does not hold the short result IS the exact one (tests/fastmath/exhaustive.hip), call after call.  `bad` is a wave mask:
+//                      the calls sit under per-contact branches, across which the mask too is kept in VGPRs (about 5 VALU per contact update more than
+//                      per-call guards), yet the branches it saves make the still solver faster; a per-lane bool flag -- alone, or with the slots every
+//                      lane has moved behind wave-uniform branches so that it stays in SGPRs -- measured slower (profiles/r08_deferred_verdict_ab.log).
+struct nh_div_exact {
+	NH_HD float recip(float x) { return nh_recip(x); }
+	NH_HD float rsqrt(float x) { return nh_rsqrt(x); }
+};
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(NH_SOLVER_EXACT_DIV)
+struct nh_div_deferred {
+	uint64_t bad = 0;
+	__device__ __forceinline__ float recip(float x) { float r = nh_recip_fast_z(x); bad |= __builtin_amdgcn_ballot_w64(nh_recip_fast_z_bad(r)); return r; }
+	__device__ __forceinline__ float rsqrt(float x) {
+		float r = nh_rsqrt_fast_z(x);
+		bad |= __builtin_amdgcn_ballot_w64(nh_rsqrt_fast_z_bad(r)) | (__builtin_amdgcn_ballot_w64(nh_rsqrt_fast_z_small(x)) & ~__builtin_amdgcn_ballot_w64(x == 0.0f));
+		return r;
+	}
+};
+#else
+struct nh_div_deferred : nh_div_exact { uint64_t bad = 0; };
+#endif
+
 // World-space inverse inertia R diag R^T, 6 unique terms (nudge.cpp:4182-4197).
 struct nh_inertia { float xx, yy, zz, xy, xz, yz; };
 
@@ -438,13 +465,14 @@ NH_HD void nh_build_row1(const nh_contact_in& c, nh_f3 dpos, const nh_inertia& D
 }
 
 // nh_warm_start, D's half
-NH_HD void nh_warm_start1(const nh_row1& r, float cix, float ciy, float ciz, nh_vel& d, bool d_is_a, nh_state& st) {
+template <class DIV = nh_div_exact>
+NH_HD void nh_warm_start1(const nh_row1& r, float cix, float ciy, float ciz, nh_vel& d, bool d_is_a, nh_state& st, DIV&& div = DIV()) {
 	float normal_impulse = nh_max(r.n_x * cix + r.n_y * ciy + r.n_z * ciz, 0.0f);
 	float max_friction_impulse = normal_impulse * r.friction;
 	float fx = r.u_x * cix + r.u_y * ciy + r.u_z * ciz;
 	float fy = r.v_x * cix + r.v_y * ciy + r.v_z * ciz;
 	float scale = fx * fx + fy * fy;
-	scale = nh_rsqrt_s(scale);
+	scale = div.rsqrt(scale);
 	scale = scale * max_friction_impulse;
 	scale = nh_min(1.0f, scale);
 	fx = fx * scale;
@@ -466,7 +494,8 @@ NH_HD void nh_warm_start1(const nh_row1& r, float cix, float ciy, float ciz, nh_
 }
 
 // nh_apply_one, D's half
-NH_HD void nh_apply_one1(const nh_row1& r, nh_state& st, nh_vel& d, bool d_is_a) {
+template <class DIV = nh_div_exact>
+NH_HD void nh_apply_one1(const nh_row1& r, nh_state& st, nh_vel& d, bool d_is_a, DIV&& div = DIV()) {
 	// velocity of the contact point on D, split the way the general form splits it between its two accumulators
 	float l_x = nh_madd(d.wy, r.p_z, d.vx);
 	float l_y = nh_madd(d.wz, r.p_x, d.vy);
@@ -519,7 +548,7 @@ NH_HD void nh_apply_one1(const nh_row1& r, nh_state& st, nh_vel& d, bool d_is_a)
 	friction_factor = nh_madd(t_xy, r.friction_coefficient_z, friction_factor);
 	float linear_impulse_z = r.n_z * normal_impulse;
 
-	friction_factor = nh_recip_s(friction_factor);
+	friction_factor = div.recip(friction_factor);
 
 	d.wx = nh_madd(r.nd_x, normal_impulse, d.wx);
 	d.wy = nh_madd(r.nd_y, normal_impulse, d.wy);
@@ -536,7 +565,7 @@ NH_HD void nh_apply_one1(const nh_row1& r, nh_state& st, nh_vel& d, bool d_is_a)
 	friction_impulse_y = old_friction_impulse_y - friction_impulse_y;
 
 	float friction_clamp_scale = friction_impulse_x * friction_impulse_x + friction_impulse_y * friction_impulse_y;
-	friction_clamp_scale = nh_rsqrt_s(friction_clamp_scale);
+	friction_clamp_scale = div.rsqrt(friction_clamp_scale);
 
 	friction_clamp_scale = friction_clamp_scale * max_friction_impulse;
 	friction_clamp_scale = nh_min(1.0f, friction_clamp_scale);
