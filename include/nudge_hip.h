@@ -79,7 +79,7 @@
  *      exported the views: nh_set_option(ctx, "sync_exports_views", 1) restores that contract at its old price; INTEGRATION.md.)  Any entry point outside the sample's
  *      call order between nh_collide and nh_apply_impulses turns a still step into a full one first, so everything it observes is what a full step
  *      produces.  nh_Counts.still_steps / still_replays count them.
- *      The scene queries (nh_query_build, nh_raycast, nh_spherecast, nh_boxcast, nh_overlap) are not entry points of the step in this sense: they neither export nor settle nor turn a still step into a
+ *      The scene queries (nh_query_build, nh_raycast, nh_spherecast, nh_boxcast, nh_capsulecast, nh_overlap) are not entry points of the step in this sense: they neither export nor settle nor turn a still step into a
  *      full one, and they do not count -- see "scene queries" below.
  *
  * Threading: one context = one HIP stream = one world at a time; no global mutable state.
@@ -349,7 +349,7 @@ typedef struct nh_StreamInfo { uint32_t slot; uint32_t valid; uint64_t step; uin
 int nh_stream_state(nh_context* ctx, const nh_BodyData* bodies, uint32_t count, void* host_ring, uint32_t slots, uint32_t every);
 int nh_stream_latest(nh_context* ctx, nh_StreamInfo* out);
 
-/* ---- scene queries: ray casts, sphere and box casts, and overlaps against the device-resident world -----------------------------------------------------------------
+/* ---- scene queries: ray casts, sphere, box and capsule casts, and overlaps against the device-resident world ------------------------------------------------------------
    nh_query_build snapshots the world transforms and AABBs of ALL box and sphere colliders -- those of sleeping bodies and of body 0 (the static world) included -- and
    builds a bounding-volume hierarchy over them (a linear BVH: Morton keys, a radix tree, bottom-up boxes) into buffers the library owns: they grow with the collider
    count (~250 B per collider) and are freed by nh_destroy.  nh_raycast answers `count` rays (nh_overlap, below, `count` shapes) against the LAST build: the hierarchy does not follow the bodies, so
@@ -372,7 +372,9 @@ int nh_stream_latest(nh_context* ctx, nh_StreamInfo* out);
    Not built: queries on a partitioned world (nh_partition_*), an incremental refit across steps. */
 typedef struct nh_Ray { float origin[3]; float max_t; float direction[3]; uint32_t ignore_body; } nh_Ray;                                            /* 32 B */
 typedef struct nh_RayHit { float t; float normal[3]; uint32_t body; uint32_t collider; uint32_t shape; uint32_t tag; } nh_RayHit;                     /* 32 B */
-enum { NH_SHAPE_BOX = 0u, NH_SHAPE_SPHERE = 1u, NH_SHAPE_NONE = 0xffffffffu };    /* nh_RayHit.shape; NONE = miss */
+enum { NH_SHAPE_BOX = 0u, NH_SHAPE_SPHERE = 1u, NH_SHAPE_CAPSULE = 2u, NH_SHAPE_NONE = 0xffffffffu };    /* nh_RayHit.shape; NONE = miss.  CAPSULE is a QUERY
+                                                                                                       shape only (nh_OverlapQuery.shape): never in
+                                                                                                       nh_RayHit.shape or nh_OverlapHit.shape */
 enum { NH_RAY_ANY_HIT = 1u };
 int nh_query_build(nh_context* ctx, const nh_BodyData* bodies, const nh_ColliderData* colliders);
 int nh_raycast(nh_context* ctx, const nh_Ray* rays, uint32_t count, nh_RayHit* hits, uint32_t flags);
@@ -425,11 +427,46 @@ typedef struct nh_BoxCast { float origin[3]; float max_t; float direction[3]; ui
                             float rotation[4]; float size[3]; uint32_t reserved; } nh_BoxCast;                                                    /* 64 B */
 int nh_boxcast(nh_context* ctx, const nh_BoxCast* casts, uint32_t count, nh_RayHit* hits, uint32_t flags /* 0 or NH_RAY_ANY_HIT */);
 
+/* nh_capsulecast: where a swept capsule first touches the world of the LAST nh_query_build -- character controllers, ragdoll limbs, thick swept projectiles,
+   "is there head room to stand up".  A CAPSULE of centre c, rotation `rotation` (a unit quaternion in (x, y, z, s) order, as in nh_OverlapQuery, that the
+   library does not normalise), radius r = `radius` >= 0 and half height hh = `half_height` >= 0 is the set of points within r of the segment c -+ a,
+   a = rotate(rotation, (0, hh, 0)): its axis is the local y axis (the identity gives an upright capsule), and hh is half the segment's length, caps not
+   included.  nh_CapsuleCast's first 32 bytes are nh_Ray's fields at the same offsets; `reserved` is not read.  Exact predicates: nudge_amd/csrc/nh_query.h.
+     - the swept capsule is centred at o + t d, for 0 <= t <= max_t; it translates only, nothing rotates during the sweep; t is in units of d, as for rays;
+     - the hit on one collider is the smallest such t at which the capsule touches it (touching counts, as in nh_overlap); the normal is a unit vector from
+       the collider towards the capsule: against a sphere collider from its centre towards the segment's closest point; against a box, from an end ball
+       (nh_spherecast's normal of that ball), from a box vertex towards the capsule's axis, or along the common normal of a box edge and the segment,
+       signed against the direction (n.d < 0).  Box candidates are taken in the order end balls (the -a end first), vertices, edges, the first on equal
+       t; an edge within ~1e-3 rad of parallel to the segment is left to the end balls and vertices.  No contact point is reported;
+     - START OVERLAP: a capsule that overlaps a collider at t = 0 under nh_overlap's capsule predicates hits it at t = 0 with normal = -d / |d|, the ray's
+       inside rule; a start contact that only the sweep's rounding finds does the same;
+     - over all colliders the answer follows nh_raycast: the closest hit, ties by (shape, collider index), `ignore_body`, NH_RAY_ANY_HIT (hit or miss agrees
+       with the closest-hit answer, a reported hit is real), and a miss written exactly as a ray miss (shape = NH_SHAPE_NONE, t = max_t, normal = 0,
+       body = collider = tag = 0xffffffff); a collider of a body that does not exist (NaN pose) is never hit;
+     - HALF HEIGHT 0 IS A BALL: it writes the same bytes as nh_spherecast with the same first 32 bytes and radius, and `rotation` is not read -- so r = 0 with
+       hh = 0 writes nh_raycast's bytes.  r = 0 with hh > 0 is a swept segment;
+     - unless r = hh = 0, a hit also needs the ray to enter the collider's box in the hierarchy grown per axis by the capsule's world AABB half extent
+       |a_k| + r, and t is at least that entry (the reach rule, DESIGN 10.4, as for sphere and box casts);
+     - a cast with a non-finite origin, direction, radius or half height, a negative radius or half height, or hh > 0 with a non-finite rotation is written
+       as a miss with t = NaN.
+   Returns NH_ERR_INVALID before any nh_query_build, for flags other than 0 or NH_RAY_ANY_HIT, and for null or not 16-byte aligned `casts` / `hits`;
+   count = 0 is a no-op that returns NH_OK.  An OBSERVER like nh_raycast (note 9): no view export, no settling of deferred gravity, no still step turned
+   into a full one, no change to nh_Counts. */
+typedef struct nh_CapsuleCast { float origin[3]; float max_t; float direction[3]; uint32_t ignore_body;
+                                float rotation[4]; float radius; float half_height; uint32_t reserved[2]; } nh_CapsuleCast;                           /* 64 B */
+int nh_capsulecast(nh_context* ctx, const nh_CapsuleCast* casts, uint32_t count, nh_RayHit* hits, uint32_t flags /* 0 or NH_RAY_ANY_HIT */);
+
 /* nh_overlap: which colliders of the LAST nh_query_build touch each of `count` query shapes -- explosion radii, trigger volumes, "is this spot free".
    Query shapes (nh_OverlapQuery):
      - shape = NH_SHAPE_SPHERE: the ball of radius size[0] around `center`; rotation and size[1..2] are ignored.  Radius 0 is a point query;
      - shape = NH_SHAPE_BOX: the oriented box of half extents `size` (as in nh_BoxCollider) and rotation `rotation`, a unit quaternion in nh_Transform's
        (x, y, z, s) order that the library does not normalise.
+     - shape = NH_SHAPE_CAPSULE: the capsule (nh_capsulecast) of radius size[0], half height size[1] and rotation `rotation` around `center`; size[2] is
+       not read.  Against a sphere collider (p, R) it overlaps iff the squared distance from p to its segment is at most (r + R)^2; against a box collider
+       iff its segment comes within r of the box: the ball of radius r swept from c - a to c + a reaches the box (nh_q_sweep_box, t <= 1) or the ball at
+       c + a touches it -- so whatever the sphere query accepts at either end point is accepted.  Both predicates also require the capsule's world AABB,
+       c -+ (|a_k| + r), to touch the collider's, so that the walk never prunes a collider they accept.  Half height 0 IS A SPHERE query of radius size[0]:
+       the same records, and `rotation` is not read.
    The answer of query i is the set of colliders that overlap its shape as CLOSED sets (touching counts), over every box and sphere collider of the last build
    (those of sleeping bodies and of body 0 included), less the colliders of `ignore_body` (0xffffffff: none is ignored).  A collider whose body does not exist
    (NaN pose) overlaps nothing.  Exact predicates: nudge_amd/csrc/nh_query.h.
@@ -443,8 +480,8 @@ int nh_boxcast(nh_context* ctx, const nh_BoxCast* casts, uint32_t count, nh_RayH
        `hits` behind it is left untouched, and `offsets` is always complete;
      - a true total of 2^32 - 1 or more writes offsets[count] = 0xffffffff and no record at all (the other offsets are then unspecified).  Every per-query
        count is below 2^30, so the 32-bit scan has wrapped iff some offsets[i+1] < offsets[i]; a total of exactly 2^32 - 1 is the marker itself.
-   An INVALID query overlaps nothing (count 0): an unknown shape, a non-finite centre or size (for a sphere size[0] alone), for a box a non-finite rotation,
-   or a negative size.  As with non-finite rays, an asynchronous call cannot refuse one record.
+   An INVALID query overlaps nothing (count 0): an unknown shape, a non-finite centre or size (for a sphere size[0] alone, for a capsule size[0] and
+   size[1]), for a box or a capsule of nonzero half height a non-finite rotation, or a negative size (of those read).  As with non-finite rays, an asynchronous call cannot refuse one record.
    Returns NH_ERR_INVALID before any nh_query_build, for flags != 0, for `queries` null or not 16-byte aligned, `offsets` null or not 4-byte aligned, `hits`
    null with capacity > 0 or not 16-byte aligned, and for count >= 2^30; count = 0 is a no-op that returns NH_OK.
    An OBSERVER like nh_raycast (note 9): no view export, no settling of deferred gravity, no still step turned into a full one, no change to nh_Counts.  Everything

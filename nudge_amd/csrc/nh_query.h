@@ -1,8 +1,8 @@
-// nh_query.h -- per-item arithmetic of the scene query (nh_query_build / nh_raycast / nh_spherecast / nh_boxcast / nh_overlap, nh_query.hip): a
-// collider's world pose, a ray against one box and against one sphere, the overlap predicates of a query sphere or box against one collider, a swept
-// ball and a swept box against one box and one sphere, with the walk's node tests they are pruned by.
+// nh_query.h -- per-item arithmetic of the scene query (nh_query_build / nh_raycast / nh_spherecast / nh_boxcast / nh_capsulecast / nh_overlap,
+// nh_query.hip): a collider's world pose, a ray against one box and against one sphere, the overlap predicates of a query sphere, box or capsule against
+// one collider, a swept ball, box and capsule against one box and one sphere, with the walk's node tests they are pruned by.
 //
-// Every function is `NH_HD` so that tests/hostquery (hostoverlap, hostsweep, hostboxcast) builds the SAME arithmetic with g++ -ffp-contract=off and gets the device's bits: the
+// Every function is `NH_HD` so that tests/hostquery (hostoverlap, hostsweep, hostboxcast, hostcapsule) builds the SAME arithmetic with g++ -ffp-contract=off and gets the device's bits: the
 // brute force over all colliders there is the oracle of the GPU's tree traversal.  Only + - * /, sqrtf (correctly rounded on both sides)
 // and sign / absolute-value bit operations are used (and fminf / fmaxf in the pads and the walk's node test, which agree on both sides).
 //
@@ -407,6 +407,188 @@ NH_HD bool nh_q_cast_node3(nh_f3 lo, nh_f3 hi, nh_f3 o, nh_f3 inv, nh_f3 w, floa
 	t0 = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fminf(az, bz));
 	const float t1 = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fmaxf(az, bz));
 	return t0 <= t1 && t1 >= 0.0f;
+}
+
+// ---- capsules (nh_overlap's NH_SHAPE_CAPSULE, nh_capsulecast) -------------------------------------------------------------------------------
+// A capsule of centre c, rotation q, radius r and half height hh is the set of points within r of the segment c -+ a, a = rotate(q, (0, hh, 0)):
+// its axis is the local y axis.  hh = 0 is a ball: every capsule function below then IS the sphere function of the same name, to the bit, and does
+// not read q.  The capsule's world AABB is c -+ (|a_k| + r) per axis -- what nh_overlap's walk and the guards below compute.
+
+// The half axis a (0 for hh = 0, where q is not read).
+NH_HD nh_f3 nh_q_capsule_axis(nh_quat q, float hh) { return hh == 0.0f ? nh_make3(0.0f, 0.0f, 0.0f) : nh_rotate(q, nh_make3(0.0f, hh, 0.0f)); }
+
+// The capsule's world AABB half extents |a_k| + r.
+NH_HD nh_f3 nh_q_capsule_extent(nh_f3 a, float r) { return nh_make3(nh_abs(a.x) + r, nh_abs(a.y) + r, nh_abs(a.z) + r); }
+
+// Do the world AABBs c -+ ea and p -+ eb touch?  (nh_q_overlap_box_box's guard)
+NH_HD bool nh_q_aabbs_touch(nh_f3 ca, nh_f3 ea, nh_f3 cb, nh_f3 eb) {
+	return (cb.x - eb.x) <= (ca.x + ea.x) && (ca.x - ea.x) <= (cb.x + eb.x) && (cb.y - eb.y) <= (ca.y + ea.y) && (ca.y - ea.y) <= (cb.y + eb.y) &&
+	       (cb.z - eb.z) <= (ca.z + ea.z) && (ca.z - ea.z) <= (cb.z + eb.z);
+}
+
+// Capsule (c, a, r) against the sphere collider (p, R), a != 0: the two world AABBs touch, and the squared distance from p to the segment is at most
+// (r + R)^2 -- the segment's closest point is c + u a with u = (p - c).a / a.a clamped to [-1, 1].  The guard only removes what rounding could put
+// outside the AABBs, so that the walk, which prunes by those AABBs padded, never prunes a collider this accepts.
+NH_HD bool nh_q_overlap_capsule_sphere_a(nh_f3 c, nh_f3 a, float r, nh_f3 p, float R) {
+	if (!nh_q_aabbs_touch(c, nh_q_capsule_extent(a, r), p, nh_make3(R, R, R))) return false;
+	const float aa = nh_dot(a, a);
+	float u = aa > 0.0f ? nh_dot(p - c, a) / aa : 0.0f;
+	u = u < -1.0f ? -1.0f : u > 1.0f ? 1.0f : u;
+	const nh_f3 m = (c + u * a) - p;
+	const float s = r + R;
+	return nh_dot(m, m) <= s * s;
+}
+
+// Capsule (c, a, r) against the box collider (p, q, h), a != 0: the two world AABBs touch (as in nh_q_overlap_box_box), and the segment comes within
+// r of the box -- the ball of radius r swept from c - a along 2a reaches the box by t = 1 (nh_q_sweep_box, whose start test is the ball at c - a),
+// or the ball at c + a touches it (nh_q_overlap_sphere_box).  So both end balls that nh_q_overlap_sphere_box accepts are accepted.
+NH_HD bool nh_q_overlap_capsule_box_a(nh_f3 c, nh_f3 a, float r, nh_f3 p, nh_quat q, nh_f3 h) {
+	if (!nh_q_aabbs_touch(c, nh_q_capsule_extent(a, r), p, nh_q_box_extent(q, h))) return false;
+	if (nh_q_overlap_sphere_box(c + a, r, p, q, h)) return true;
+	const nh_QHit s = nh_q_sweep_box(c - a, a + a, r, p, q, h);
+	return s.hit && s.t <= 1.0f;
+}
+
+// nh_overlap's capsule predicates: hh = 0 is the sphere query's predicate itself (and q is not read).
+NH_HD bool nh_q_overlap_capsule_sphere(nh_f3 c, nh_quat q, float r, float hh, nh_f3 p, float R) {
+	if (hh == 0.0f) return nh_q_overlap_sphere_sphere(c, r, p, R);
+	return nh_q_overlap_capsule_sphere_a(c, nh_q_capsule_axis(q, hh), r, p, R);
+}
+NH_HD bool nh_q_overlap_capsule_box(nh_f3 c, nh_quat q, float r, float hh, nh_f3 p, nh_quat qb, nh_f3 h) {
+	if (hh == 0.0f) return nh_q_overlap_sphere_box(c, r, p, qb, h);
+	return nh_q_overlap_capsule_box_a(c, nh_q_capsule_axis(q, hh), r, p, qb, h);
+}
+
+// ---- capsule casts (nh_capsulecast): the first t at which the capsule (o + t d, q, r, hh) touches a collider ----------------------------------------
+// The capsule translates only.  One that touches at t = 0 under nh_overlap's capsule predicates hits at t = 0 with the ray's inside normal -d / |d|,
+// and so does a start contact that only the sweep's rounding finds (a candidate at t = 0).  hh = 0 is nh_spherecast's predicate, bit for bit, and q is
+// not read.  The normal is a unit vector from the collider towards the capsule.
+
+// The capsule cast against the sphere collider (p, R): in the capsule's frame (the inverse of q), the ray from p along -d into the capsule of radius
+// r + R around the segment from -hh to hh on y -- nh_q_capsule_entry with k = y.  The normal points from p to the segment's closest point at the hit
+// (-d / |d| where that distance is 0: r = R = 0).
+NH_HD nh_QHit nh_q_sweep_capsule_sphere(nh_f3 o, nh_f3 d, nh_quat q, float r, float hh, nh_f3 p, float R) {
+	if (hh == 0.0f) return nh_q_sweep_sphere(o, d, r, p, R);
+	if (nh_q_overlap_capsule_sphere_a(o, nh_q_capsule_axis(q, hh), r, p, R)) return nh_q_inside(d);
+	nh_QHit res; res.t = 0.0f; res.n = nh_make3(0.0f, 0.0f, 0.0f); res.hit = false;
+	const nh_quat qi = { nh_neg(q.x), nh_neg(q.y), nh_neg(q.z), q.s };
+	const nh_f3 pl = nh_rotate(qi, p - o), dl = nh_rotate(qi, d);
+	const nh_f3 ml = nh_make3(nh_neg(dl.x), nh_neg(dl.y), nh_neg(dl.z));
+	const float t = nh_q_capsule_entry(pl.x, pl.z, pl.y, ml.x, ml.z, ml.y, 0.0f, 0.0f, hh, r + R);
+	if (!(t < INFINITY)) return res;
+	if (!(t > 0.0f)) return nh_q_inside(d);
+	const nh_f3 y = pl + t * ml;
+	const nh_f3 v = nh_make3(nh_neg(y.x), nh_max(nh_neg(hh), nh_min(y.y, hh)) - y.y, nh_neg(y.z));
+	const float vv = nh_dot(v, v);
+	if (!(vv > 0.0f)) { const nh_QHit in = nh_q_inside(d); res.n = in.n; }
+	else { const float len = sqrtf(vv); res.n = nh_rotate(q, nh_make3(v.x / len, v.y / len, v.z / len)); }
+	res.t = t; res.hit = true;
+	return res;
+}
+
+// The capsule cast against the box collider (p, qb, hb), in the box frame (the inverse of qb): o, d and the half axis a (world, nh_q_capsule_axis)
+// become ol, dl, al.  First the ray (ol, dl) against the box grown by the capsule's box-frame AABB half extents |al_k| + r: a capsule that never
+// enters it never touches the box, and the candidates below are solved from tb = max(its entry, 0), where the capsule is within its size of the box --
+// so a cast from far away loses no accuracy in them.  t is the least of:
+//   1. the END BALLS c -+ a, swept by nh_q_sweep_box (the -a end first);
+//   2. the VERTICES: each of the 8 box vertices as a ray along -d into the infinite cylinder of radius r about the capsule's axis (closest-approach form,
+//      as nh_q_ball_entry), counted where the entry's axial coordinate lies within the segment;
+//   3. the EDGES: each of the 12 box edges against the segment.  Their distance along the common normal n = al x e (e the edge's unit axis) is linear
+//      in t; the entering root at distance r counts when the closest points of the two lines lie within both segments there.  An edge whose
+//      |al x e|^2 is below 2^-20 |al|^2 (within ~1e-3 rad of parallel) is skipped: its direction would be rounding noise.
+// FACES need no case of their own: the distance from a face's plane to a point of the segment is linear along it, so a segment not parallel to the
+// face reaches it first with an end point (its end ball, kind 1), and a parallel one reaches it with every point at once, end points included.  For
+// the same reason a near-parallel edge contact is found by an end ball or a vertex of the edge (kinds 1 and 2).  Ties go to the first candidate in
+// the order above (end balls, vertices in (x, y, z) sign order from -, edges by axis x, y, z).
+// Normals: an end ball's is nh_q_sweep_box's; a vertex's points from the vertex towards the axis (the direction it approached from when r = 0); an
+// edge's is -+n / |n|, signed against d.
+NH_HD nh_QHit nh_q_sweep_capsule_box(nh_f3 o, nh_f3 d, nh_quat q, float r, float hh, nh_f3 p, nh_quat qb, nh_f3 hb) {
+	if (hh == 0.0f) return nh_q_sweep_box(o, d, r, p, qb, hb);
+	const nh_f3 a = nh_q_capsule_axis(q, hh);
+	if (nh_q_overlap_capsule_box_a(o, a, r, p, qb, hb)) return nh_q_inside(d);
+	nh_QHit res; res.t = 0.0f; res.n = nh_make3(0.0f, 0.0f, 0.0f); res.hit = false;
+	const nh_quat qi = { nh_neg(qb.x), nh_neg(qb.y), nh_neg(qb.z), qb.s };
+	const nh_f3 ol = nh_rotate(qi, o - p), dl = nh_rotate(qi, d), al = nh_rotate(qi, a);
+	float te = -INFINITY, tx = INFINITY;
+	int enter = -1;
+	bool all = true;
+	nh_q_slab(ol.x, dl.x, hb.x + (nh_abs(al.x) + r), 0, te, tx, enter, all);
+	nh_q_slab(ol.y, dl.y, hb.y + (nh_abs(al.y) + r), 1, te, tx, enter, all);
+	nh_q_slab(ol.z, dl.z, hb.z + (nh_abs(al.z) + r), 2, te, tx, enter, all);
+	if (!all || !(te <= tx) || !(tx >= 0.0f)) return res;
+	const float tb = te > 0.0f ? te : 0.0f;
+	const nh_f3 ob = ol + tb * dl;
+	// 1. end balls (world frame)
+	float t = INFINITY;
+	int kind = 0;                        // 1: an end ball (world normal in n), 2: a vertex, 3: an edge (box-frame normal in n)
+	nh_f3 n = nh_make3(0.0f, 0.0f, 0.0f);
+	{
+		const nh_QHit b0 = nh_q_sweep_box(o - a, d, r, p, qb, hb);
+		if (b0.hit) { t = b0.t; n = b0.n; kind = 1; }
+		const nh_QHit b1 = nh_q_sweep_box(o + a, d, r, p, qb, hb);
+		if (b1.hit && b1.t < t) { t = b1.t; n = b1.n; kind = 1; }
+	}
+	const float A = nh_dot(al, al);
+	const float invA = 1.0f / A;
+	// 2. vertices: v - tau dl against the cylinder |perp(v - ob - tau dl)| = r, perp = the part orthogonal to al
+	const nh_f3 dp = dl - (nh_dot(dl, al) * invA) * al;
+	const float aa = nh_dot(dp, dp);
+	if (aa > 0.0f) {
+		const float inva = 1.0f / aa, rr = r * r;
+		for (int v = 0; v < 8; ++v) {
+			const nh_f3 m = nh_make3((v & 1) ? hb.x : nh_neg(hb.x), (v & 2) ? hb.y : nh_neg(hb.y), (v & 4) ? hb.z : nh_neg(hb.z)) - ob;
+			const nh_f3 mp = m - (nh_dot(m, al) * invA) * al;
+			const float tm = nh_dot(mp, dp) * inva;
+			const nh_f3 l = mp - tm * dp;
+			const float qq = rr - nh_dot(l, l);
+			if (!(qq >= 0.0f)) continue;
+			const float dt = sqrtf(qq * inva);
+			if (!(tm + dt >= 0.0f)) continue;
+			const float ts = tm - dt > 0.0f ? tm - dt : 0.0f;
+			const float u = nh_dot(m - ts * dl, al) * invA;
+			const float tv = tb + ts;
+			if (nh_abs(u) <= 1.0f && tv < t) {
+				t = tv; kind = 2;
+				n = ts * dp - mp;                                          // (from the vertex to the axis)
+				if (!(nh_dot(n, n) > 0.0f)) n = nh_make3(nh_neg(dp.x), nh_neg(dp.y), nh_neg(dp.z));
+			}
+		}
+	}
+	// 3. edges along axis k, at (-+h_i, -+h_j) on the other two axes i, j
+	for (int k = 0; k < 3; ++k) {
+		const float ai = k == 0 ? al.y : k == 1 ? al.z : al.x, aj = k == 0 ? al.z : k == 1 ? al.x : al.y, ak = k == 0 ? al.x : k == 1 ? al.y : al.z;
+		const float di = k == 0 ? dl.y : k == 1 ? dl.z : dl.x, dj = k == 0 ? dl.z : k == 1 ? dl.x : dl.y, dk = k == 0 ? dl.x : k == 1 ? dl.y : dl.z;
+		const float bi = k == 0 ? ob.y : k == 1 ? ob.z : ob.x, bj = k == 0 ? ob.z : k == 1 ? ob.x : ob.y, bk = k == 0 ? ob.x : k == 1 ? ob.y : ob.z;
+		const float hi = k == 0 ? hb.y : k == 1 ? hb.z : hb.x, hj = k == 0 ? hb.z : k == 1 ? hb.x : hb.y, hk = k == 0 ? hb.x : k == 1 ? hb.y : hb.z;
+		const float D = ai * ai + aj * aj;                                // |al x e_k|^2; the normal is (-aj, ai) on (i, j)
+		if (!(D >= NH_Q_SAT_EPS * A)) continue;
+		const float f1 = ai * dj - aj * di;
+		if (f1 == 0.0f) continue;
+		const float L = sqrtf(D), invD = 1.0f / D, inv1 = 1.0f / nh_abs(f1), rL = r * L;
+		const float fb = ai * bj - aj * bi;
+		for (int e = 0; e < 4; ++e) {
+			const float ci = (e & 1) ? hi : nh_neg(hi), cj = (e & 2) ? hj : nh_neg(hj);
+			const float f0 = fb - (ai * cj - aj * ci);
+			const float sf = f1 < 0.0f ? f0 : nh_neg(f0);                  // the signed distance on the side the segment comes from
+			if (!((sf + rL) * inv1 >= 0.0f)) continue;
+			const float te0 = (sf - rL) * inv1;
+			const float ts = te0 > 0.0f ? te0 : 0.0f;
+			const float wi = (bi + ts * di) - ci, wj = (bj + ts * dj) - cj, wk = bk + ts * dk;
+			const float u = nh_neg(ai * wi + aj * wj) * invD;
+			const float s = wk + u * ak;
+			const float tv = tb + ts;
+			if (nh_abs(u) <= 1.0f && nh_abs(s) <= hk && tv < t) {
+				t = tv; kind = 3;
+				const float ni = (f1 > 0.0f ? aj : nh_neg(aj)) / L, nj = (f1 > 0.0f ? nh_neg(ai) : ai) / L;
+				n = nh_make3(k == 0 ? 0.0f : k == 1 ? nj : ni, k == 0 ? ni : k == 1 ? 0.0f : nj, k == 0 ? nj : k == 1 ? ni : 0.0f);
+			}
+		}
+	}
+	if (kind == 0) return res;
+	if (!(t > 0.0f)) return nh_q_inside(d);
+	if (kind == 2) { const float len = sqrtf(nh_dot(n, n)); n = nh_make3(n.x / len, n.y / len, n.z / len); }
+	res.t = t; res.n = kind == 1 ? n : nh_rotate(qb, n); res.hit = true;
+	return res;
 }
 
 #endif

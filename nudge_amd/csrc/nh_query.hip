@@ -1,6 +1,7 @@
 // nh_query.hip -- scene queries against the device-resident world: nh_query_build (a linear BVH over every box and sphere collider, built from
-// the current transforms), nh_raycast (batched closest-hit / any-hit ray casts against the last build), nh_spherecast and nh_boxcast (the same for
-// swept balls and swept oriented boxes) and nh_overlap (the colliders touching each of a batch of spheres or boxes, as variable-length segments).  include/nudge_hip.h, "scene queries".
+// the current transforms), nh_raycast (batched closest-hit / any-hit ray casts against the last build), nh_spherecast, nh_boxcast and nh_capsulecast (the
+// same for swept balls, oriented boxes and capsules) and nh_overlap (the colliders touching each of a batch of spheres, boxes or capsules, as
+// variable-length segments).  include/nudge_hip.h, "scene queries".
 //
 // Build (one launch each, plus the library's radix sort):
 //   k_q_xform   one lane per collider (boxes, then spheres): world pose (k_xform's arithmetic, nh_query.h), world AABB, the record the ray test
@@ -392,21 +393,89 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
 	}
 }
 
+// ---- capsule cast -----------------------------------------------------------------------------------------------------------------------------
+// k_q_boxcast's walk with the node box grown per axis by the capsule's world AABB half extent |a_k| + r plus the pad (nh_q_cast_node3), the capsule-cast
+// predicates of nh_query.h at the leaves, and the reach rule unless r = hh = 0.  hh = 0 walks and answers as k_q_spherecast does (e = r
+// on every axis, the same pad, the same node test's bits) and does not read the rotation.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k_q_capsulecast(const nh_CapsuleCast* __restrict__ casts, uint32_t count, nh_RayHit* __restrict__ hits,
+                                                   const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox, uint32_t any_hit) {
+	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
+		const float4* cp = reinterpret_cast<const float4*>(casts + i);
+		const float4 c0 = cp[0], c1 = cp[1], c2 = cp[2], c3 = cp[3];
+		const nh_f3 o = nh_make3(c0.x, c0.y, c0.z), d = nh_make3(c1.x, c1.y, c1.z);
+		const nh_quat qa = { c2.x, c2.y, c2.z, c2.w };
+		const float max_t = c0.w, r = c3.x, hh = c3.y;
+		const uint32_t ignore = __float_as_uint(c1.w);
+		const bool ok = nh_q_finite(o.x) && nh_q_finite(o.y) && nh_q_finite(o.z) && nh_q_finite(d.x) && nh_q_finite(d.y) && nh_q_finite(d.z) &&
+		                nh_q_finite(r) && nh_q_finite(hh) && !(r < 0.0f) && !(hh < 0.0f) &&
+		                (hh == 0.0f || (nh_q_finite(qa.x) && nh_q_finite(qa.y) && nh_q_finite(qa.z) && nh_q_finite(qa.s)));
+		float bt = max_t;
+		uint32_t bc = NH_Q_NONE;
+		nh_f3 bn = nh_make3(0.0f, 0.0f, 0.0f);
+		const nh_f3 inv = nh_make3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+		const nh_f3 e = nh_q_capsule_extent(nh_q_capsule_axis(qa, hh), r);
+		const float s = nh_q_cast_pad(o, fmaxf(fmaxf(e.x, e.y), e.z));
+		const nh_f3 w = nh_make3(e.x + s, e.y + s, e.z + s);
+		const bool reach = r > 0.0f || hh > 0.0f;
+		uint32_t node = ok && n ? 0u : NH_Q_NONE;
+		while (node != NH_Q_NONE) {
+			const float4 na = nodes[node].a, nb = nodes[node].b;
+			float t0;
+			const bool enter = nh_q_cast_node3(nh_make3(na.x, na.y, na.z), nh_make3(nb.x, nb.y, nb.z), o, inv, w, t0) && t0 <= bt;
+			const uint32_t left = __float_as_uint(na.w);
+			const uint32_t rope = __float_as_uint(nb.w);
+			if (!enter) { node = rope; continue; }
+			if (!(left & NH_Q_LEAF)) { node = left; continue; }
+			node = rope;
+			const uint32_t c = left & ~NH_Q_LEAF;
+			const nh_QRec q = rec[c];
+			if (__float_as_uint(q.a.w) == ignore) continue;
+			const nh_f3 p = nh_make3(q.a.x, q.a.y, q.a.z);
+			nh_QHit h = c < nbox ? nh_q_sweep_capsule_box(o, d, qa, r, hh, p, nh_quat{ q.b.x, q.b.y, q.b.z, q.b.w }, nh_make3(q.c.x, q.c.y, q.c.z))
+			                     : nh_q_sweep_capsule_sphere(o, d, qa, r, hh, p, q.c.x);
+			if (reach && t0 > h.t) h.t = t0;
+			if (h.hit && nh_q_better(h.t, c, max_t, bt, bc)) {
+				bt = h.t; bc = c; bn = h.n;
+				if (any_hit) break;
+			}
+		}
+		nh_RayHit out;
+		if (bc == NH_Q_NONE) {
+			out.t = ok ? max_t : __uint_as_float(0x7fc00000u);
+			out.normal[0] = out.normal[1] = out.normal[2] = 0.0f;
+			out.body = out.collider = out.tag = NH_Q_NONE;
+			out.shape = NH_SHAPE_NONE;
+		} else {
+			const nh_QRec q = rec[bc];
+			out.t = bt; out.normal[0] = bn.x; out.normal[1] = bn.y; out.normal[2] = bn.z;
+			out.body = __float_as_uint(q.a.w);
+			out.collider = bc < nbox ? bc : bc - nbox;
+			out.shape = bc < nbox ? NH_SHAPE_BOX : NH_SHAPE_SPHERE;
+			out.tag = __float_as_uint(q.c.w);
+		}
+		float4* hp = reinterpret_cast<float4*>(hits + i);
+		hp[0] = make_float4(out.t, out.normal[0], out.normal[1], out.normal[2]);
+		hp[1] = make_float4(__uint_as_float(out.body), __uint_as_float(out.collider), __uint_as_float(out.shape), __uint_as_float(out.tag));
+	}
+}
+
 // ---- overlap ---------------------------------------------------------------------------------------------------------------------------------
 // nh_overlap is a chain of launches with kernel boundaries as the only hand-offs; no atomic decides where a record goes:
-//   k_q_overlap<false>  one lane per query: the tree walk of k_q_raycast (stackless, escape links) with the query's padded world AABB, the exact
+//   k_q_overlap<false, false>  one lane per query: the tree walk of k_q_raycast (stackless, escape links) with the query's padded world AABB, the exact
 //                       predicate at the leaves; offsets[i] = the count (offsets[count] = 0, scanned along)
+//   k_q_overlap<false, true>   the same for the capsule queries of nonzero half height, which the first skips: their predicates need more registers
+//                       than the sphere and box walk's occupancy allows, so they run in an instantiation of their own
 //   nh_scan_u32         in place over count + 1 words: offsets and the total
 //   k_q_overlap_fix     the wrap (offsets[i+1] < offsets[i]) and the written prefix: the one i with offsets[i] <= capacity < offsets[i+1], or the total
 //   k_q_overlap_fin     one lane: on a wrap or a total equal to the marker, offsets[count] = 0xffffffff and nothing is written
-//   k_q_overlap<true>   the same walk (the same template: the same set) for the queries whose segment fits: key (i << cbits | c), value c at offsets[i] + k
+//   k_q_overlap<true, *> the same walks (the same template: the same set) for the queries whose segment fits: key (i << cbits | c), value c at offsets[i] + k
 //   nh_sort_u64_u32     over the written prefix (its length from the device): keys are unique, so (query, combined index) ascending is the only order
 //   k_q_overlap_gather  nh_OverlapHit {body, collider, shape, tag} from the record of each sorted collider, one 16-byte store each
-template <bool LIST>
+template <bool LIST, bool CAPSULE>
 __global__ __launch_bounds__(256) void k_q_overlap(const nh_OverlapQuery* __restrict__ queries, uint32_t count, uint32_t* offsets,
                                                    const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox,
                                                    nh_QCtl* ctl, uint64_t* __restrict__ keys, uint32_t* __restrict__ vals, uint32_t cbits) {
-	if (!LIST && blockIdx.x == 0 && threadIdx.x == 0) { offsets[count] = 0u; ctl->ov_wrap = 0u; ctl->ov_written = 0u; }   // (k_q_overlap_fix sets both)
+	if (!LIST && !CAPSULE && blockIdx.x == 0 && threadIdx.x == 0) { offsets[count] = 0u; ctl->ov_wrap = 0u; ctl->ov_written = 0u; }   // (k_q_overlap_fix sets both)
 	const uint32_t written = LIST ? ctl->ov_written : 0u;
 	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
 		uint32_t base = 0u, end = 0u;
@@ -419,12 +488,17 @@ __global__ __launch_bounds__(256) void k_q_overlap(const nh_OverlapQuery* __rest
 		const nh_f3 c = nh_make3(q0.x, q0.y, q0.z), h = nh_make3(q2.x, q2.y, q2.z);
 		const nh_quat qr = { q1.x, q1.y, q1.z, q1.w };
 		const uint32_t shape = __float_as_uint(q0.w), ignore = __float_as_uint(q2.w);
-		const bool sphere = shape == NH_SHAPE_SPHERE;
-		bool ok = (sphere || shape == NH_SHAPE_BOX) && nh_q_finite(c.x) && nh_q_finite(c.y) && nh_q_finite(c.z) && nh_q_finite(h.x) && !(h.x < 0.0f);
-		if (!sphere) ok = ok && nh_q_finite(h.y) && nh_q_finite(h.z) && !(h.y < 0.0f) && !(h.z < 0.0f) &&
-		                  nh_q_finite(qr.x) && nh_q_finite(qr.y) && nh_q_finite(qr.z) && nh_q_finite(qr.s);
+		// (a capsule of half height 0 is a sphere query: the same walk, the same predicates, its rotation not read.  Every other capsule -- an invalid
+		// half height included -- is the CAPSULE instantiation's, and only its)
+		if ((shape == NH_SHAPE_CAPSULE && h.y != 0.0f) != CAPSULE) continue;
+		const bool capsule = CAPSULE;
+		const bool sphere = !CAPSULE && (shape == NH_SHAPE_SPHERE || shape == NH_SHAPE_CAPSULE);
+		bool ok = (sphere || capsule || shape == NH_SHAPE_BOX) && nh_q_finite(c.x) && nh_q_finite(c.y) && nh_q_finite(c.z) && nh_q_finite(h.x) && !(h.x < 0.0f);
+		if (!sphere) ok = ok && nh_q_finite(h.y) && !(h.y < 0.0f) && nh_q_finite(qr.x) && nh_q_finite(qr.y) && nh_q_finite(qr.z) && nh_q_finite(qr.s);
+		if (!sphere && !capsule) ok = ok && nh_q_finite(h.z) && !(h.z < 0.0f);
 		// the query's world AABB, padded by 2^-18 of its largest coordinate (only ever more generous than the exact test)
-		const nh_f3 e = sphere ? nh_make3(h.x, h.x, h.x) : nh_q_box_extent(qr, h);
+		const nh_f3 a = capsule ? nh_q_capsule_axis(qr, h.y) : nh_make3(0.0f, 0.0f, 0.0f);
+		const nh_f3 e = sphere ? nh_make3(h.x, h.x, h.x) : capsule ? nh_q_capsule_extent(a, h.x) : nh_q_box_extent(qr, h);
 		nh_f3 lo = c - e, hi = c + e;
 		const float s = fmaxf(fmaxf(fmaxf(fabsf(lo.x), fabsf(lo.y)), fmaxf(fabsf(lo.z), fabsf(hi.x))), fmaxf(fabsf(hi.y), fabsf(hi.z))) * 3.814697265625e-06f;
 		lo = nh_make3(lo.x - s, lo.y - s, lo.z - s); hi = nh_make3(hi.x + s, hi.y + s, hi.z + s);
@@ -444,7 +518,8 @@ __global__ __launch_bounds__(256) void k_q_overlap(const nh_OverlapQuery* __rest
 			const nh_f3 p = nh_make3(r.a.x, r.a.y, r.a.z), rh = nh_make3(r.c.x, r.c.y, r.c.z);
 			const nh_quat rq = { r.b.x, r.b.y, r.b.z, r.b.w };
 			bool hit;
-			if (cc < nbox) hit = sphere ? nh_q_overlap_sphere_box(c, h.x, p, rq, rh) : nh_q_overlap_box_box(c, qr, h, p, rq, rh);
+			if (capsule) hit = cc < nbox ? nh_q_overlap_capsule_box_a(c, a, h.x, p, rq, rh) : nh_q_overlap_capsule_sphere_a(c, a, h.x, p, rh.x);
+			else if (cc < nbox) hit = sphere ? nh_q_overlap_sphere_box(c, h.x, p, rq, rh) : nh_q_overlap_box_box(c, qr, h, p, rq, rh);
 			else hit = sphere ? nh_q_overlap_sphere_sphere(c, h.x, p, rh.x) : nh_q_overlap_sphere_box(p, rh.x, c, qr, h);
 			if (!hit) continue;
 			if (LIST) {
@@ -585,6 +660,18 @@ extern "C" int nh_spherecast(nh_context* ctx, const nh_SphereCast* casts, uint32
 	return NH_OK;
 }
 
+extern "C" int nh_capsulecast(nh_context* ctx, const nh_CapsuleCast* casts, uint32_t count, nh_RayHit* hits, uint32_t flags) {
+	if (!ctx || !ctx->query || !ctx->query->built) return NH_ERR_INVALID;
+	if (flags & ~(uint32_t)NH_RAY_ANY_HIT) return NH_ERR_INVALID;
+	if (count == 0u) return NH_OK;
+	if (!casts || !hits || (((uintptr_t)casts | (uintptr_t)hits) & 15u)) return NH_ERR_INVALID;    // (records are moved as 16-byte words)
+	NH_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+	nh_QueryState* q = ctx->query;
+	NH_LAUNCH(ctx, "q_capsulecast", k_q_capsulecast, nh_grid_for(count, 256, 1u << 20), 256, casts, count, hits, q->nodes, q->rec, q->n, q->nbox,
+	          (flags & NH_RAY_ANY_HIT) ? 1u : 0u);
+	return NH_OK;
+}
+
 extern "C" int nh_boxcast(nh_context* ctx, const nh_BoxCast* casts, uint32_t count, nh_RayHit* hits, uint32_t flags) {
 	if (!ctx || !ctx->query || !ctx->query->built) return NH_ERR_INVALID;
 	if (flags & ~(uint32_t)NH_RAY_ANY_HIT) return NH_ERR_INVALID;
@@ -632,13 +719,17 @@ extern "C" int nh_overlap(nh_context* ctx, const nh_OverlapQuery* queries, uint3
 	if (list) { const int rc = nh_overlap_reserve(ctx, capacity); if (rc) return rc; }
 	const uint32_t cbits = (uint32_t)nh_q_bits(q->n);
 	const uint32_t grid = nh_grid_for(count, 256, 1u << 20);
-	NH_LAUNCH(ctx, "q_overlap_count", k_q_overlap<false>, grid, 256, queries, count, offsets, q->nodes, q->rec, q->n, q->nbox, q->ctl,
+	NH_LAUNCH(ctx, "q_overlap_count", (k_q_overlap<false, false>), grid, 256, queries, count, offsets, q->nodes, q->rec, q->n, q->nbox, q->ctl,
+	          (uint64_t*)nullptr, (uint32_t*)nullptr, cbits);
+	NH_LAUNCH(ctx, "q_overlap_count_capsule", (k_q_overlap<false, true>), grid, 256, queries, count, offsets, q->nodes, q->rec, q->n, q->nbox, q->ctl,
 	          (uint64_t*)nullptr, (uint32_t*)nullptr, cbits);
 	nh_scan_u32(ctx, offsets, offsets, &q->ctl->zero, count + 1u, q->hist, nullptr);
 	NH_LAUNCH(ctx, "q_overlap_fix", k_q_overlap_fix, nh_grid_for((uint64_t)count + 1u, 256, 4096), 256, offsets, count, capacity, q->ctl);
 	NH_LAUNCH(ctx, "q_overlap_fin", k_q_overlap_fin, 1, 1, offsets, count, q->ctl);
 	if (!list) return NH_OK;
-	NH_LAUNCH(ctx, "q_overlap_list", k_q_overlap<true>, grid, 256, queries, count, offsets, q->nodes, q->rec, q->n, q->nbox, q->ctl,
+	NH_LAUNCH(ctx, "q_overlap_list", (k_q_overlap<true, false>), grid, 256, queries, count, offsets, q->nodes, q->rec, q->n, q->nbox, q->ctl,
+	          q->ov_keys_a, q->ov_vals_a, cbits);
+	NH_LAUNCH(ctx, "q_overlap_list_capsule", (k_q_overlap<true, true>), grid, 256, queries, count, offsets, q->nodes, q->rec, q->n, q->nbox, q->ctl,
 	          q->ov_keys_a, q->ov_vals_a, cbits);
 	const int bits = (((int)cbits + nh_q_bits(count)) + 7) / 8 * 8;
 	const int in_b = nh_sort_u64_u32(ctx, q->ov_keys_a, q->ov_keys_b, q->ov_vals_a, q->ov_vals_b, &q->ctl->ov_written, q->hist, 0, bits);

@@ -43,7 +43,7 @@ EXPORTS = [
     "nh_partition_top_speed", "nh_partition_set_peer_speeds", "nh_partition_refresh_is_quiet", "nh_partition_mark_ghosts", "nh_partition_pack_deltas", "nh_partition_unpack_deltas",
     "nh_partition_pack_momentum", "nh_partition_unpack_momentum", "nh_partition_exchange_iteration", "nh_partition_unpack_ghosts", "nh_partition_pack_step", "nh_partition_unpack_step", "nh_partition_choose_cut", "nh_partition_set_cut",
     "nh_partition_set_transport", "nh_partition_exchange_step", "nh_partition_step", "nh_partition_transport_check", "nh_partition_transport_result", "nh_set_first_ghost_body",
-    "nh_query_build", "nh_raycast", "nh_overlap", "nh_spherecast", "nh_boxcast",
+    "nh_query_build", "nh_raycast", "nh_overlap", "nh_spherecast", "nh_boxcast", "nh_capsulecast",
 ]
 HALO_RECORD_BYTES = 64
 
@@ -127,14 +127,21 @@ class BoxCast(C.Structure):
                 ("size", C.c_float * 3), ("reserved", C.c_uint32)]
 
 
-# scene queries (include/nudge_hip.h, "scene queries"): nh_RayHit.shape, nh_raycast flags; numpy forms of the two records
-NH_SHAPE_BOX, NH_SHAPE_SPHERE, NH_SHAPE_NONE = 0, 1, 0xFFFFFFFF
+class CapsuleCast(C.Structure):
+    _fields_ = [("origin", C.c_float * 3), ("max_t", C.c_float), ("direction", C.c_float * 3), ("ignore_body", C.c_uint32), ("rotation", C.c_float * 4),
+                ("radius", C.c_float), ("half_height", C.c_float), ("reserved", C.c_uint32 * 2)]
+
+
+# scene queries (include/nudge_hip.h, "scene queries"): nh_RayHit.shape (CAPSULE: a query shape only), nh_raycast flags; numpy forms of the records
+NH_SHAPE_BOX, NH_SHAPE_SPHERE, NH_SHAPE_CAPSULE, NH_SHAPE_NONE = 0, 1, 2, 0xFFFFFFFF
 NH_RAY_ANY_HIT = 1
 RAY = np.dtype([("origin", "<f4", 3), ("max_t", "<f4"), ("direction", "<f4", 3), ("ignore_body", "<u4")])
 RAY_HIT = np.dtype([("t", "<f4"), ("normal", "<f4", 3), ("body", "<u4"), ("collider", "<u4"), ("shape", "<u4"), ("tag", "<u4")])
 SPHERE_CAST = np.dtype([("origin", "<f4", 3), ("max_t", "<f4"), ("direction", "<f4", 3), ("ignore_body", "<u4"), ("radius", "<f4"), ("reserved", "<u4", 3)])
 BOX_CAST = np.dtype([("origin", "<f4", 3), ("max_t", "<f4"), ("direction", "<f4", 3), ("ignore_body", "<u4"), ("rotation", "<f4", 4), ("size", "<f4", 3),
                      ("reserved", "<u4")])
+CAPSULE_CAST = np.dtype([("origin", "<f4", 3), ("max_t", "<f4"), ("direction", "<f4", 3), ("ignore_body", "<u4"), ("rotation", "<f4", 4), ("radius", "<f4"),
+                         ("half_height", "<f4"), ("reserved", "<u4", 2)])
 OVERLAP_QUERY = np.dtype([("center", "<f4", 3), ("shape", "<u4"), ("rotation", "<f4", 4), ("size", "<f4", 3), ("ignore_body", "<u4")])
 OVERLAP_HIT = np.dtype([("body", "<u4"), ("collider", "<u4"), ("shape", "<u4"), ("tag", "<u4")])
 NH_OVERLAP_OVERFLOW = 0xFFFFFFFF          # offsets[count] when the total is 2^32 - 1 or more
@@ -235,6 +242,7 @@ def lib():
         L.nh_raycast.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
         L.nh_spherecast.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
         L.nh_boxcast.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
+        L.nh_capsulecast.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
         L.nh_overlap.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
         _LIB = L
     return _LIB
@@ -712,6 +720,50 @@ class World:
             torch.cuda.current_stream(self.dev).synchronize()
         return out
 
+    def capsulecast_records(self, casts, any_hit=False, hits=None):
+        """nh_capsulecast on records already laid out as nh_CapsuleCast: `casts` a contiguous device tensor of count x 64 bytes (any dtype).  Returns
+        the count x 32-byte uint8 device tensor of nh_RayHit records (`hits`, or a new one)."""
+        torch = self.torch
+        n = casts.numel() * casts.element_size() // 64
+        if hits is None:
+            hits = torch.empty((n, 32), dtype=torch.uint8, device=self.dev)
+        _check(self.L, self.L.nh_capsulecast(self.ctx, C.c_void_p(casts.data_ptr() if n else 0), n, C.c_void_p(hits.data_ptr() if n else 0),
+                                             NH_RAY_ANY_HIT if any_hit else 0), "nh_capsulecast")
+        return hits
+
+    def capsulecast(self, origins, directions, radii, half_heights, rotations=None, max_t=float("inf"), ignore_body=None, any_hit=False,
+                    synchronize=False):
+        """Closest-hit (or any-hit) capsule casts against the last query_build(): the capsule of `radii` and `half_heights` (numbers or n values) about
+        its local y axis, turned by `rotations` ((n, 4) or (4,) quaternions (x, y, z, s); None = identity, upright), swept without turning from
+        `origins` along `directions` ((n, 3) each).  `max_t`, `ignore_body` and the result are raycast()'s: t, normal (from the collider to the
+        capsule), body, collider, shape, tag and `raw`.  Nothing waits unless `synchronize`."""
+        torch = self.torch
+        o = torch.as_tensor(origins, dtype=torch.float32, device=self.dev).reshape(-1, 3)
+        d = torch.as_tensor(directions, dtype=torch.float32, device=self.dev).reshape(-1, 3)
+        n = o.shape[0]
+        if d.shape[0] != n:
+            raise ValueError(f"capsulecast: {n} origins but {d.shape[0]} directions")
+        casts = torch.zeros((n, 16), dtype=torch.float32, device=self.dev)
+        casts[:, 0:3] = o
+        casts[:, 3] = torch.as_tensor(max_t, dtype=torch.float32, device=self.dev)
+        casts[:, 4:7] = d
+        ign = 0xFFFFFFFF if ignore_body is None else ignore_body
+        ign = torch.as_tensor(ign, dtype=torch.int64, device=self.dev)
+        casts.view(torch.int32)[:, 7] = (((ign & 0xFFFFFFFF) ^ 0x80000000) - 0x80000000).to(torch.int32)          # (the uint32 bits, as int32)
+        if rotations is None:
+            casts[:, 11] = 1.0
+        else:
+            casts[:, 8:12] = torch.as_tensor(rotations, dtype=torch.float32, device=self.dev).reshape(-1, 4)
+        casts[:, 12] = torch.as_tensor(radii, dtype=torch.float32, device=self.dev).reshape(-1)
+        casts[:, 13] = torch.as_tensor(half_heights, dtype=torch.float32, device=self.dev).reshape(-1)
+        raw = self.capsulecast_records(casts, any_hit=any_hit)
+        f = raw.view(torch.float32).reshape(n, 8)
+        u = raw.view(torch.int32).reshape(n, 8).to(torch.int64) & 0xFFFFFFFF
+        out = dict(t=f[:, 0], normal=f[:, 1:4], body=u[:, 4], collider=u[:, 5], shape=u[:, 6], tag=u[:, 7], raw=raw)
+        if synchronize:
+            torch.cuda.current_stream(self.dev).synchronize()
+        return out
+
     def overlap_records(self, queries, offsets=None, hits=None, capacity=0):
         """nh_overlap on records already laid out as nh_OverlapQuery: `queries` a contiguous device tensor of count x 48 bytes (any dtype).  Returns
         (offsets, hits): the count + 1 offsets as an int32 device tensor holding the uint32 bits (`offsets`, or a new one) and `hits` as given.  With
@@ -727,10 +779,11 @@ class World:
                                          C.c_void_p(hits.data_ptr() if hits is not None else 0), capacity, 0), "nh_overlap")
         return offsets, hits
 
-    def overlap(self, centres, radii=None, half_extents=None, rotations=None, ignore_body=None, capacity=None, synchronize=False):
-        """The colliders touching each of n spheres (`radii`: a number or n values) or n oriented boxes (`half_extents` (n, 3) or (3,), `rotations`
-        (n, 4) or (4,) quaternions (x, y, z, s), default identity), against the last query_build().  Give exactly one of radii / half_extents;
-        mixed batches go through overlap_records.  `ignore_body`: None, a body index, or n of them.
+    def overlap(self, centres, radii=None, half_extents=None, rotations=None, ignore_body=None, capacity=None, synchronize=False, half_heights=None):
+        """The colliders touching each of n spheres (`radii`: a number or n values), n oriented boxes (`half_extents` (n, 3) or (3,), `rotations`
+        (n, 4) or (4,) quaternions (x, y, z, s), default identity) or n capsules (`radii` with `half_heights`, numbers or n values, and `rotations`;
+        the axis is the local y axis), against the last query_build().  Give exactly one of radii / half_extents; mixed batches go through
+        overlap_records.  `ignore_body`: None, a body index, or n of them.
         capacity=None: a count call, then the total is read -- this WAITS for the device -- and an exactly sized list call.  A capacity: one call, and
         nothing waits; only the segments that fit are listed (offsets[i + 1] <= capacity).
         Returns a dict of device tensors: offsets (n + 1, int64; offsets[n] = 0xffffffff when the total is 2^32 - 1 or more), `written` (0-d: the
@@ -739,12 +792,22 @@ class World:
         torch = self.torch
         if (radii is None) == (half_extents is None):
             raise ValueError("overlap: give exactly one of radii / half_extents")
+        if half_heights is not None and radii is None:
+            raise ValueError("overlap: half_heights go with radii (a capsule)")
         c = torch.as_tensor(centres, dtype=torch.float32, device=self.dev).reshape(-1, 3)
         n = c.shape[0]
         q = torch.zeros((n, 12), dtype=torch.float32, device=self.dev)
         qi = q.view(torch.int32)
         q[:, 0:3] = c
-        if radii is not None:
+        if half_heights is not None:
+            qi[:, 3] = NH_SHAPE_CAPSULE
+            q[:, 8] = torch.as_tensor(radii, dtype=torch.float32, device=self.dev).reshape(-1)
+            q[:, 9] = torch.as_tensor(half_heights, dtype=torch.float32, device=self.dev).reshape(-1)
+            if rotations is None:
+                q[:, 7] = 1.0
+            else:
+                q[:, 4:8] = torch.as_tensor(rotations, dtype=torch.float32, device=self.dev).reshape(-1, 4)
+        elif radii is not None:
             qi[:, 3] = NH_SHAPE_SPHERE
             q[:, 8] = torch.as_tensor(radii, dtype=torch.float32, device=self.dev).reshape(-1)
             q[:, 7] = 1.0
