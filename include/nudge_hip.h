@@ -79,7 +79,7 @@
  *      exported the views: nh_set_option(ctx, "sync_exports_views", 1) restores that contract at its old price; INTEGRATION.md.)  Any entry point outside the sample's
  *      call order between nh_collide and nh_apply_impulses turns a still step into a full one first, so everything it observes is what a full step
  *      produces.  nh_Counts.still_steps / still_replays count them.
- *      The scene queries (nh_query_build, nh_raycast, nh_spherecast, nh_boxcast, nh_capsulecast, nh_overlap) are not entry points of the step in this sense: they neither export nor settle nor turn a still step into a
+ *      The scene queries (nh_query_build, nh_raycast, nh_spherecast, nh_boxcast, nh_capsulecast, nh_overlap, nh_closest) are not entry points of the step in this sense: they neither export nor settle nor turn a still step into a
  *      full one, and they do not count -- see "scene queries" below.
  *
  * Threading: one context = one HIP stream = one world at a time; no global mutable state.
@@ -349,7 +349,7 @@ typedef struct nh_StreamInfo { uint32_t slot; uint32_t valid; uint64_t step; uin
 int nh_stream_state(nh_context* ctx, const nh_BodyData* bodies, uint32_t count, void* host_ring, uint32_t slots, uint32_t every);
 int nh_stream_latest(nh_context* ctx, nh_StreamInfo* out);
 
-/* ---- scene queries: ray casts, sphere, box and capsule casts, and overlaps against the device-resident world ------------------------------------------------------------
+/* ---- scene queries: ray casts, sphere, box and capsule casts, overlaps and closest points against the device-resident world ---------------------------------------------
    nh_query_build snapshots the world transforms and AABBs of ALL box and sphere colliders -- those of sleeping bodies and of body 0 (the static world) included -- and
    builds a bounding-volume hierarchy over them (a linear BVH: Morton keys, a radix tree, bottom-up boxes) into buffers the library owns: they grow with the collider
    count (~250 B per collider) and are freed by nh_destroy.  nh_raycast answers `count` rays (nh_overlap, below, `count` shapes) against the LAST build: the hierarchy does not follow the bodies, so
@@ -455,6 +455,34 @@ int nh_boxcast(nh_context* ctx, const nh_BoxCast* casts, uint32_t count, nh_RayH
 typedef struct nh_CapsuleCast { float origin[3]; float max_t; float direction[3]; uint32_t ignore_body;
                                 float rotation[4]; float radius; float half_height; uint32_t reserved[2]; } nh_CapsuleCast;                           /* 64 B */
 int nh_capsulecast(nh_context* ctx, const nh_CapsuleCast* casts, uint32_t count, nh_RayHit* hits, uint32_t flags /* 0 or NH_RAY_ANY_HIT */);
+
+/* nh_closest: how far each of `count` points lies from the world of the LAST nh_query_build, and where the nearest surface is -- depenetration, "snap to
+   the nearest surface", proximity and cover tests, keeping a distance from everything.  `reserved` is not read.  Exact predicates: nudge_amd/csrc/nh_query.h.
+     - the SIGNED DISTANCE of p from one collider is negative inside it.  A sphere (c, R): m = p - c, L = sqrtf(m.m), distance = L - R, normal = m / L,
+       point = c + R normal; at L = 0 (the centre) the normal is +y.  A box (pose, half extents h), p in the box frame l (nh_q_overlap_sphere_box's
+       inverse rotation): OUTSIDE (some |l_k| > h_k) the clamp ql = clamp(l, -h, h), e = l - ql, distance = sqrtf(e.e), normal = e / distance turned
+       to world, point = the world position of ql; INSIDE or on the surface the face k of least depth h_k - |l_k| (the lowest axis on equality),
+       distance = 0 - depth (+0 on the surface, never -0), normal = +-e_k by the sign of l_k (a zero l_k counts as +) turned to world, point = l with
+       l_k replaced by +-h_k, in world;
+     - `normal` is a unit vector out of the collider (towards p when p is outside); `point` is on the collider's surface, so p = point + distance normal
+       up to rounding;
+     - the answer is the smallest distance with distance <= max_distance over the colliders not belonging to `ignore_body` (0xffffffff: none is
+       ignored) -- inside several, the deepest -- with ties by (shape, collider index) ascending, so a brute force over all colliders gives the same
+       bytes.  max_distance = +inf finds the nearest collider anywhere; max_distance = 0 only colliders that contain or touch p.  A collider of a body
+       that does not exist (NaN pose) is never reported;
+     - THE REACH RULE: where p lies outside the collider's box in the hierarchy (k_q_refit's padded box) at squared distance d2 > 0
+       (per axis fmaxf(fmaxf(lo - p, p - hi), 0), then the sum of the squares), the distance is max(distance, sqrtf(d2)).  It is what lets the walk
+       prune exactly; it moves a distance only where rounding put the predicate in front of a box padded by 2^-18 of its coordinates;
+     - a miss writes shape = NH_SHAPE_NONE, distance = max_distance, normal = point = 0 and body = collider = tag = 0xffffffff;
+     - a query with a non-finite point, or a NaN or negative max_distance, is written as a miss with distance = NaN;
+     - `reserved` of every hit is written 0.
+   Returns NH_ERR_INVALID before any nh_query_build, for flags != 0, and for null or not 16-byte aligned `queries` / `hits`; count = 0 is a no-op that
+   returns NH_OK.  An OBSERVER like nh_raycast (note 9): no view export, no settling of deferred gravity, no still step turned into a full one, no change
+   to nh_Counts.  Not built: the distance of a shape from the world (GJK), the k nearest colliders. */
+typedef struct nh_PointQuery { float point[3]; float max_distance; uint32_t ignore_body; uint32_t reserved[3]; } nh_PointQuery;                     /* 32 B */
+typedef struct nh_PointHit { float distance; float normal[3]; float point[3]; uint32_t body;
+                             uint32_t collider; uint32_t shape; uint32_t tag; uint32_t reserved; } nh_PointHit;                                  /* 48 B */
+int nh_closest(nh_context* ctx, const nh_PointQuery* queries, uint32_t count, nh_PointHit* hits, uint32_t flags /* 0 */);
 
 /* nh_overlap: which colliders of the LAST nh_query_build touch each of `count` query shapes -- explosion radii, trigger volumes, "is this spot free".
    Query shapes (nh_OverlapQuery):

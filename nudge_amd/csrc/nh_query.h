@@ -1,8 +1,9 @@
-// nh_query.h -- per-item arithmetic of the scene query (nh_query_build / nh_raycast / nh_spherecast / nh_boxcast / nh_capsulecast / nh_overlap,
-// nh_query.hip): a collider's world pose, a ray against one box and against one sphere, the overlap predicates of a query sphere, box or capsule against
-// one collider, a swept ball, box and capsule against one box and one sphere, with the walk's node tests they are pruned by.
+// nh_query.h -- per-item arithmetic of the scene query (nh_query_build / nh_raycast / nh_spherecast / nh_boxcast / nh_capsulecast / nh_overlap /
+// nh_closest, nh_query.hip): a collider's world pose, a ray against one box and against one sphere, the overlap predicates of a query sphere, box or
+// capsule against one collider, a swept ball, box and capsule against one box and one sphere, the signed distance of a point from one box and one
+// sphere, with the walk's node tests they are pruned by.
 //
-// Every function is `NH_HD` so that tests/hostquery (hostoverlap, hostsweep, hostboxcast, hostcapsule) builds the SAME arithmetic with g++ -ffp-contract=off and gets the device's bits: the
+// Every function is `NH_HD` so that tests/hostquery (hostoverlap, hostsweep, hostboxcast, hostcapsule, hostpoint) builds the SAME arithmetic with g++ -ffp-contract=off and gets the device's bits: the
 // brute force over all colliders there is the oracle of the GPU's tree traversal.  Only + - * /, sqrtf (correctly rounded on both sides)
 // and sign / absolute-value bit operations are used (and fminf / fmaxf in the pads and the walk's node test, which agree on both sides).
 //
@@ -589,6 +590,86 @@ NH_HD nh_QHit nh_q_sweep_capsule_box(nh_f3 o, nh_f3 d, nh_quat q, float r, float
 	if (kind == 2) { const float len = sqrtf(nh_dot(n, n)); n = nh_make3(n.x / len, n.y / len, n.z / len); }
 	res.t = t; res.n = kind == 1 ? n : nh_rotate(qb, n); res.hit = true;
 	return res;
+}
+
+// ---- closest points (nh_closest): the signed distance of a point from one collider, and the nearest point of its surface ---------------------------
+// Negative inside.  Every function returns the distance d, the unit normal n (outwards from the collider, towards p when p is outside) and the surface
+// point x; a collider of a NaN pose gives a NaN distance, which no comparison accepts.
+struct nh_QPoint { float d; nh_f3 n; nh_f3 x; };
+
+// The sphere (c, R): m = p - c, L = sqrtf(m.m), d = L - R, n = m / L, x = c + n R.  L = 0 (m.m zero, or below the float range when squared): n = +y.
+NH_HD nh_QPoint nh_q_point_sphere(nh_f3 p, nh_f3 c, float R) {
+	const nh_f3 m = p - c;
+	const float L = sqrtf(nh_dot(m, m));
+	nh_QPoint r;
+	r.d = L - R;
+	r.n = L > 0.0f ? nh_make3(m.x / L, m.y / L, m.z / L) : nh_make3(0.0f, 1.0f, 0.0f);
+	r.x = c + r.n * R;
+	return r;
+}
+
+// The box of world pose (c, q) and half extents h.  l = p in the box frame, by nh_q_overlap_sphere_box's inverse rotation.
+//   OUTSIDE (some |l_k| > h_k): ql = clamp(l, -h, h), e = l - ql, d = sqrtf(e.e), n = rotate(q, e / d), x = c + rotate(q, ql).  Where e.e is below the
+//           float range (d = 0), n is the region's direction (the signs of e) normalised, as nh_q_sweep_box does for its edge normals.
+//   INSIDE or on the surface (every |l_k| <= h_k): the face k of least depth h_k - |l_k| (the lowest axis on equality), d = 0 - depth (+0 on the
+//           surface, never -0), n = rotate(q, s e_k), x = c + rotate(q, l with l_k = s h_k), s = -1 where l_k < 0 and +1 otherwise (a zero l_k is +).
+NH_HD nh_QPoint nh_q_point_box(nh_f3 p, nh_f3 c, nh_quat q, nh_f3 h) {
+	const nh_quat qi = { nh_neg(q.x), nh_neg(q.y), nh_neg(q.z), q.s };
+	const nh_f3 l = nh_rotate(qi, p - c);
+	nh_QPoint r;
+	if (nh_abs(l.x) <= h.x && nh_abs(l.y) <= h.y && nh_abs(l.z) <= h.z) {
+		const float dx = h.x - nh_abs(l.x), dy = h.y - nh_abs(l.y), dz = h.z - nh_abs(l.z);
+		int k = 0;
+		float dep = dx;
+		if (dy < dep) { k = 1; dep = dy; }
+		if (dz < dep) { k = 2; dep = dz; }
+		const float lk = k == 0 ? l.x : k == 1 ? l.y : l.z, hk = k == 0 ? h.x : k == 1 ? h.y : h.z;
+		const float s = lk < 0.0f ? -1.0f : 1.0f;
+		r.d = 0.0f - dep;
+		r.n = nh_rotate(q, nh_make3(k == 0 ? s : 0.0f, k == 1 ? s : 0.0f, k == 2 ? s : 0.0f));
+		r.x = c + nh_rotate(q, nh_make3(k == 0 ? s * hk : l.x, k == 1 ? s * hk : l.y, k == 2 ? s * hk : l.z));
+		return r;
+	}
+	const nh_f3 ql = nh_make3(nh_max(nh_neg(h.x), nh_min(l.x, h.x)), nh_max(nh_neg(h.y), nh_min(l.y, h.y)), nh_max(nh_neg(h.z), nh_min(l.z, h.z)));
+	nh_f3 e = l - ql;
+	const float ee = nh_dot(e, e);
+	r.d = sqrtf(ee);
+	if (ee == 0.0f) {
+		// (a point beyond a face by less than the square root of the smallest float: the signs of e give the region)
+		e = nh_make3(e.x > 0.0f ? 1.0f : e.x < 0.0f ? -1.0f : 0.0f, e.y > 0.0f ? 1.0f : e.y < 0.0f ? -1.0f : 0.0f, e.z > 0.0f ? 1.0f : e.z < 0.0f ? -1.0f : 0.0f);
+		const float len = sqrtf(nh_dot(e, e));
+		r.n = nh_rotate(q, nh_make3(e.x / len, e.y / len, e.z / len));
+	} else {
+		r.n = nh_rotate(q, nh_make3(e.x / r.d, e.y / r.d, e.z / r.d));
+	}
+	r.x = c + nh_rotate(q, ql);
+	return r;
+}
+
+// The squared distance from p to the box [lo, hi] as the walk computes it for a node and the reach rule for a leaf: per axis
+// fmaxf(fmaxf(lo - p, p - hi), 0), then the sum of the squares in x, y, z order.  0 when p lies in the box (or the box is NaN: a collider of a body
+// that does not exist, whose predicate distance is NaN anyway).
+NH_HD float nh_q_point_node(nh_f3 lo, nh_f3 hi, nh_f3 p) {
+	const float ax = fmaxf(fmaxf(lo.x - p.x, p.x - hi.x), 0.0f);
+	const float ay = fmaxf(fmaxf(lo.y - p.y, p.y - hi.y), 0.0f);
+	const float az = fmaxf(fmaxf(lo.z - p.z, p.z - hi.z), 0.0f);
+	return ax * ax + ay * ay + az * az;
+}
+
+// The reach rule of nh_closest: a collider's key is its predicate distance d where its leaf box contains p (d2 = 0), and
+// max(d, sqrtf(d2)) otherwise (a NaN d stays NaN).  Every ancestor box contains the leaf box and every operation of nh_q_point_node is monotone in the
+// box, so an ancestor's d2 is never larger than the leaf's: a node with d2 > 0 and sqrtf(d2) > the best key so far holds no collider that could win,
+// and a node with d2 = 0 is always entered.
+NH_HD float nh_q_point_key(float d, float d2) {
+	if (!(d2 > 0.0f)) return d;
+	const float s = sqrtf(d2);
+	return s > d ? s : d;
+}
+
+// Does (d, c) beat the best so far (bd, bc)?  bc = 0xffffffff: none yet.  Counting needs d <= max_d; ties go to the lower combined index c.
+NH_HD bool nh_q_closer(float d, uint32_t c, float max_d, float bd, uint32_t bc) {
+	if (!(d <= max_d)) return false;
+	return bc == 0xffffffffu || d < bd || (d == bd && c < bc);
 }
 
 #endif

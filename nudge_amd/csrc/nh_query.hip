@@ -28,8 +28,9 @@ struct nh_QRec { float4 a, b, c; };
 // A node: a = (box min, left child | NH_Q_LEAF + collider), b = (box max, escape link)
 struct nh_QNode { float4 a, b; };
 // words the build's kernels share: collider count (the sort reads it), bounds of the positions (flipped floats); nh_overlap's: a word that stays 0
-// (the element count of its scan is all `extra`), the length of the written prefix of records (its sort and gather read it), the wrap flag
-struct nh_QCtl { uint32_t count, zero, ov_written, ov_wrap; uint32_t smin[4]; uint32_t smax[4]; };
+// (the element count of its scan is all `extra`), the length of the written prefix of records (its sort and gather read it), the wrap flag; the bounds
+// of the LAST build (k_q_tree keeps them there before it resets smin / smax: nh_closest's seed finds a point's place among the keys in their frame)
+struct nh_QCtl { uint32_t count, zero, ov_written, ov_wrap; uint32_t smin[4]; uint32_t smax[4]; uint32_t kmin[4]; uint32_t kmax[4]; };
 
 struct nh_QueryState {
 	uint32_t capacity;           // colliders the buffers have room for
@@ -39,6 +40,7 @@ struct nh_QueryState {
 	nh_QRec* rec;
 	float4* aabb;                // 2 per collider
 	uint64_t* keys_a; uint64_t* keys_b; uint32_t* idx_a; uint32_t* idx_b; uint32_t* hist;
+	const uint64_t* keys;        // the sorted keys of the last build (keys_a or keys_b, as the sort left them): leaf j's is keys[j]
 	nh_QNode* nodes;             // 2 n - 1
 	uint32_t* parent;            // by node id
 	uint32_t* rchild;            // by internal node
@@ -130,8 +132,8 @@ __global__ __launch_bounds__(256) void k_q_tree(const uint64_t* __restrict__ key
                                                 uint32_t* __restrict__ arrive, nh_QCtl* __restrict__ ctl) {
 	if (blockIdx.x == 0 && threadIdx.x == 0) {
 		parent[0] = NH_Q_NONE;
-		// the bounds the next build accumulates into (k_q_keys of this one has read them)
-		for (int k = 0; k < 3; ++k) { ctl->smin[k] = 0xffffffffu; ctl->smax[k] = 0u; }
+		// the bounds the next build accumulates into (k_q_keys of this one has read them); this build's are kept for nh_closest
+		for (int k = 0; k < 3; ++k) { ctl->kmin[k] = ctl->smin[k]; ctl->kmax[k] = ctl->smax[k]; ctl->smin[k] = 0xffffffffu; ctl->smax[k] = 0u; }
 	}
 	for (uint32_t u = blockIdx.x * blockDim.x + threadIdx.x; u + 1u < n; u += gridDim.x * blockDim.x) {
 		const int64_t i = u;
@@ -459,6 +461,88 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
 	}
 }
 
+// ---- closest point ----------------------------------------------------------------------------------------------------------------------------
+// One lane per query.  The bound bd starts at max_distance and only ever falls to the key of a real candidate (nh_q_point_key, nh_q_closer: the reach
+// rule of DESIGN 10.5), so a node of squared distance d2 > 0 from p with sqrtf(d2) > bd can be skipped, and one with d2 = 0 is always entered.
+//   seed  p's Morton key in the frame of the last build (clamped to its bounds), its place among the sorted keys by binary search, and the exact keys of
+//         the NH_Q_SEED leaves on either side of that place: a bound near p before the walk, which otherwise goes left first from the root -- towards
+//         the lowest Morton region, usually far from p.  Compiled out by -DNH_Q_CLOSEST_NO_SEED (tools/closest_rates.py measures both).
+//   walk  k_q_raycast's stackless walk with the node test above; the leaves evaluate nh_q_point_box / nh_q_point_sphere and the key.  A seeded winner
+//         met again does not replace itself (equal key and index), so the seed changes the work, never the answer.
+#define NH_Q_SEED 4
+__global__ __launch_bounds__(256) void k_q_closest(const nh_PointQuery* __restrict__ queries, uint32_t count, nh_PointHit* __restrict__ hits,
+                                                   const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec, const uint64_t* __restrict__ keys,
+                                                   const nh_QCtl* __restrict__ ctl, uint32_t n, uint32_t nbox) {
+	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
+		const float4* qp = reinterpret_cast<const float4*>(queries + i);
+		const float4 q0 = qp[0], q1 = qp[1];
+		const nh_f3 p = nh_make3(q0.x, q0.y, q0.z);
+		const float max_d = q0.w;
+		const uint32_t ignore = __float_as_uint(q1.x);
+		const bool ok = nh_q_finite(p.x) && nh_q_finite(p.y) && nh_q_finite(p.z) && max_d >= 0.0f;       // (+inf is a valid max_distance; NaN is not)
+		float bd = max_d;
+		uint32_t bc = NH_Q_NONE;
+		nh_f3 bn = nh_make3(0.0f, 0.0f, 0.0f), bx = nh_make3(0.0f, 0.0f, 0.0f);
+		const bool walk = ok && n;
+#ifndef NH_Q_CLOSEST_NO_SEED
+		if (walk) {
+			const nh_f3 smin = nh_make3(nh_float_unflip(ctl->kmin[0]), nh_float_unflip(ctl->kmin[1]), nh_float_unflip(ctl->kmin[2]));
+			const nh_f3 smax = nh_make3(nh_float_unflip(ctl->kmax[0]), nh_float_unflip(ctl->kmax[1]), nh_float_unflip(ctl->kmax[2]));
+			const float scale = nh_morton_scale(smin, smax);
+			const nh_f3 pc = nh_make3(fminf(fmaxf(p.x, smin.x), smax.x), fminf(fmaxf(p.y, smin.y), smax.y), fminf(fmaxf(p.z, smin.z), smax.z));
+			const uint64_t key = nh_morton_of(pc, scale, smin * scale);
+			uint32_t lo = 0u, hi = n;
+			while (lo < hi) {
+				const uint32_t mid = (lo + hi) >> 1;
+				if (keys[mid] < key) lo = mid + 1u; else hi = mid;
+			}
+			const uint32_t j0 = lo > NH_Q_SEED ? lo - NH_Q_SEED : 0u, j1 = n - lo > NH_Q_SEED ? lo + NH_Q_SEED : n;
+			for (uint32_t j = j0; j < j1; ++j) {
+				const float4 na = nodes[n - 1u + j].a, nb = nodes[n - 1u + j].b;
+				const uint32_t c = __float_as_uint(na.w) & ~NH_Q_LEAF;
+				const nh_QRec q = rec[c];
+				if (__float_as_uint(q.a.w) == ignore) continue;
+				const nh_f3 cp = nh_make3(q.a.x, q.a.y, q.a.z);
+				const nh_QPoint h = c < nbox ? nh_q_point_box(p, cp, nh_quat{ q.b.x, q.b.y, q.b.z, q.b.w }, nh_make3(q.c.x, q.c.y, q.c.z))
+				                             : nh_q_point_sphere(p, cp, q.c.x);
+				const float k = nh_q_point_key(h.d, nh_q_point_node(nh_make3(na.x, na.y, na.z), nh_make3(nb.x, nb.y, nb.z), p));
+				if (nh_q_closer(k, c, max_d, bd, bc)) { bd = k; bc = c; bn = h.n; bx = h.x; }
+			}
+		}
+#endif
+		uint32_t node = walk ? 0u : NH_Q_NONE;
+		while (node != NH_Q_NONE) {
+			const float4 na = nodes[node].a, nb = nodes[node].b;
+			const float d2 = nh_q_point_node(nh_make3(na.x, na.y, na.z), nh_make3(nb.x, nb.y, nb.z), p);
+			const uint32_t left = __float_as_uint(na.w);
+			const uint32_t rope = __float_as_uint(nb.w);
+			if (d2 > 0.0f && sqrtf(d2) > bd) { node = rope; continue; }
+			if (!(left & NH_Q_LEAF)) { node = left; continue; }
+			node = rope;
+			const uint32_t c = left & ~NH_Q_LEAF;
+			const nh_QRec q = rec[c];
+			if (__float_as_uint(q.a.w) == ignore) continue;
+			const nh_f3 cp = nh_make3(q.a.x, q.a.y, q.a.z);
+			const nh_QPoint h = c < nbox ? nh_q_point_box(p, cp, nh_quat{ q.b.x, q.b.y, q.b.z, q.b.w }, nh_make3(q.c.x, q.c.y, q.c.z))
+			                             : nh_q_point_sphere(p, cp, q.c.x);
+			const float k = nh_q_point_key(h.d, d2);
+			if (nh_q_closer(k, c, max_d, bd, bc)) { bd = k; bc = c; bn = h.n; bx = h.x; }
+		}
+		float4* hp = reinterpret_cast<float4*>(hits + i);
+		if (bc == NH_Q_NONE) {
+			const float md = ok ? max_d : __uint_as_float(0x7fc00000u);
+			hp[0] = make_float4(md, 0.0f, 0.0f, 0.0f);
+			hp[1] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(NH_Q_NONE));
+			hp[2] = make_float4(__uint_as_float(NH_Q_NONE), __uint_as_float(NH_SHAPE_NONE), __uint_as_float(NH_Q_NONE), 0.0f);
+		} else {
+			const nh_QRec q = rec[bc];
+			hp[0] = make_float4(bd, bn.x, bn.y, bn.z);
+			hp[1] = make_float4(bx.x, bx.y, bx.z, q.a.w);
+			hp[2] = make_float4(__uint_as_float(bc < nbox ? bc : bc - nbox), __uint_as_float(bc < nbox ? NH_SHAPE_BOX : NH_SHAPE_SPHERE), q.c.w, 0.0f);
+		}
+	}
+}
+
 // ---- overlap ---------------------------------------------------------------------------------------------------------------------------------
 // nh_overlap is a chain of launches with kernel boundaries as the only hand-offs; no atomic decides where a record goes:
 //   k_q_overlap<false, false>  one lane per query: the tree walk of k_q_raycast (stackless, escape links) with the query's padded world AABB, the exact
@@ -590,7 +674,7 @@ static int nh_query_reserve(nh_context* ctx, uint32_t C) {
 	for (void* b : old) if (b) hipFree(b);
 	q->rec = nullptr; q->aabb = nullptr; q->keys_a = q->keys_b = nullptr; q->idx_a = q->idx_b = nullptr; q->nodes = nullptr;
 	q->parent = q->rchild = q->last = q->right_at = q->arrive = nullptr;
-	q->capacity = 0; q->built = false;
+	q->capacity = 0; q->built = false; q->keys = nullptr;
 	NH_HIP_CHECK(ctx, hipMalloc((void**)&q->rec, sizeof(nh_QRec) * (size_t)cap));
 	NH_HIP_CHECK(ctx, hipMalloc((void**)&q->aabb, 2u * sizeof(float4) * (size_t)cap));
 	NH_HIP_CHECK(ctx, hipMalloc((void**)&q->keys_a, sizeof(uint64_t) * (size_t)cap));
@@ -628,6 +712,7 @@ extern "C" int nh_query_build(nh_context* ctx, const nh_BodyData* bodies, const 
 		// 48-bit keys: six passes, the result back in the *_a buffers
 		const int in_b = nh_sort_u64_u32(ctx, q->keys_a, q->keys_b, q->idx_a, q->idx_b, &q->ctl->count, q->hist, 0, 48);
 		const uint64_t* keys = in_b ? q->keys_b : q->keys_a;
+		q->keys = keys;
 		const uint32_t* idx = in_b ? q->idx_b : q->idx_a;
 		NH_LAUNCH(ctx, "q_tree", k_q_tree, nh_grid_for(C > 1u ? C - 1u : 1u, 256, 4096), 256, keys, C, q->nodes, q->parent, q->rchild, q->last, q->right_at, q->arrive, q->ctl);
 		NH_LAUNCH(ctx, "q_refit", k_q_refit, nh_grid_for(C, 256, 4096), 256, idx, q->aabb, C, q->nodes, q->parent, q->rchild, q->last, q->right_at, q->arrive);
@@ -681,6 +766,17 @@ extern "C" int nh_boxcast(nh_context* ctx, const nh_BoxCast* casts, uint32_t cou
 	nh_QueryState* q = ctx->query;
 	NH_LAUNCH(ctx, "q_boxcast", k_q_boxcast, nh_grid_for(count, 256, 1u << 20), 256, casts, count, hits, q->nodes, q->rec, q->n, q->nbox,
 	          (flags & NH_RAY_ANY_HIT) ? 1u : 0u);
+	return NH_OK;
+}
+
+extern "C" int nh_closest(nh_context* ctx, const nh_PointQuery* queries, uint32_t count, nh_PointHit* hits, uint32_t flags) {
+	if (!ctx || !ctx->query || !ctx->query->built) return NH_ERR_INVALID;
+	if (flags != 0u) return NH_ERR_INVALID;
+	if (count == 0u) return NH_OK;
+	if (!queries || !hits || (((uintptr_t)queries | (uintptr_t)hits) & 15u)) return NH_ERR_INVALID;    // (records are moved as 16-byte words)
+	NH_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+	nh_QueryState* q = ctx->query;
+	NH_LAUNCH(ctx, "q_closest", k_q_closest, nh_grid_for(count, 256, 1u << 20), 256, queries, count, hits, q->nodes, q->rec, q->keys, q->ctl, q->n, q->nbox);
 	return NH_OK;
 }
 

@@ -43,7 +43,7 @@ EXPORTS = [
     "nh_partition_top_speed", "nh_partition_set_peer_speeds", "nh_partition_refresh_is_quiet", "nh_partition_mark_ghosts", "nh_partition_pack_deltas", "nh_partition_unpack_deltas",
     "nh_partition_pack_momentum", "nh_partition_unpack_momentum", "nh_partition_exchange_iteration", "nh_partition_unpack_ghosts", "nh_partition_pack_step", "nh_partition_unpack_step", "nh_partition_choose_cut", "nh_partition_set_cut",
     "nh_partition_set_transport", "nh_partition_exchange_step", "nh_partition_step", "nh_partition_transport_check", "nh_partition_transport_result", "nh_set_first_ghost_body",
-    "nh_query_build", "nh_raycast", "nh_overlap", "nh_spherecast", "nh_boxcast", "nh_capsulecast",
+    "nh_query_build", "nh_raycast", "nh_overlap", "nh_spherecast", "nh_boxcast", "nh_capsulecast", "nh_closest",
 ]
 HALO_RECORD_BYTES = 64
 
@@ -132,6 +132,15 @@ class CapsuleCast(C.Structure):
                 ("radius", C.c_float), ("half_height", C.c_float), ("reserved", C.c_uint32 * 2)]
 
 
+class PointQuery(C.Structure):
+    _fields_ = [("point", C.c_float * 3), ("max_distance", C.c_float), ("ignore_body", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class PointHit(C.Structure):
+    _fields_ = [("distance", C.c_float), ("normal", C.c_float * 3), ("point", C.c_float * 3), ("body", C.c_uint32), ("collider", C.c_uint32),
+                ("shape", C.c_uint32), ("tag", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 # scene queries (include/nudge_hip.h, "scene queries"): nh_RayHit.shape (CAPSULE: a query shape only), nh_raycast flags; numpy forms of the records
 NH_SHAPE_BOX, NH_SHAPE_SPHERE, NH_SHAPE_CAPSULE, NH_SHAPE_NONE = 0, 1, 2, 0xFFFFFFFF
 NH_RAY_ANY_HIT = 1
@@ -144,6 +153,9 @@ CAPSULE_CAST = np.dtype([("origin", "<f4", 3), ("max_t", "<f4"), ("direction", "
                          ("half_height", "<f4"), ("reserved", "<u4", 2)])
 OVERLAP_QUERY = np.dtype([("center", "<f4", 3), ("shape", "<u4"), ("rotation", "<f4", 4), ("size", "<f4", 3), ("ignore_body", "<u4")])
 OVERLAP_HIT = np.dtype([("body", "<u4"), ("collider", "<u4"), ("shape", "<u4"), ("tag", "<u4")])
+POINT_QUERY = np.dtype([("point", "<f4", 3), ("max_distance", "<f4"), ("ignore_body", "<u4"), ("reserved", "<u4", 3)])
+POINT_HIT = np.dtype([("distance", "<f4"), ("normal", "<f4", 3), ("point", "<f4", 3), ("body", "<u4"), ("collider", "<u4"), ("shape", "<u4"), ("tag", "<u4"),
+                      ("reserved", "<u4")])
 NH_OVERLAP_OVERFLOW = 0xFFFFFFFF          # offsets[count] when the total is 2^32 - 1 or more
 
 
@@ -243,6 +255,7 @@ def lib():
         L.nh_spherecast.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
         L.nh_boxcast.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
         L.nh_capsulecast.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
+        L.nh_closest.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
         L.nh_overlap.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
         _LIB = L
     return _LIB
@@ -760,6 +773,39 @@ class World:
         f = raw.view(torch.float32).reshape(n, 8)
         u = raw.view(torch.int32).reshape(n, 8).to(torch.int64) & 0xFFFFFFFF
         out = dict(t=f[:, 0], normal=f[:, 1:4], body=u[:, 4], collider=u[:, 5], shape=u[:, 6], tag=u[:, 7], raw=raw)
+        if synchronize:
+            torch.cuda.current_stream(self.dev).synchronize()
+        return out
+
+    def closest_records(self, queries, hits=None):
+        """nh_closest on records already laid out as nh_PointQuery: `queries` a contiguous device tensor of count x 32 bytes (any dtype).  Returns
+        the count x 48-byte uint8 device tensor of nh_PointHit records (`hits`, or a new one)."""
+        torch = self.torch
+        n = queries.numel() * queries.element_size() // 32
+        if hits is None:
+            hits = torch.empty((n, 48), dtype=torch.uint8, device=self.dev)
+        _check(self.L, self.L.nh_closest(self.ctx, C.c_void_p(queries.data_ptr() if n else 0), n, C.c_void_p(hits.data_ptr() if n else 0), 0),
+               "nh_closest")
+        return hits
+
+    def closest(self, points, max_distance=float("inf"), ignore_body=None, synchronize=False):
+        """The nearest collider to each of `points` ((n, 3)) in the last query_build(), within `max_distance` (a number or n values; inf: anywhere),
+        skipping the colliders of `ignore_body` (None, a body index, or n of them).  Returns a dict of device tensors: distance (n; negative inside),
+        normal (n, 3; out of the collider), point (n, 3; on its surface), body, collider, shape, tag (n, int64; 0xffffffff = none) and `raw`, the
+        nh_PointHit records.  Nothing waits for the device unless `synchronize`."""
+        torch = self.torch
+        p = torch.as_tensor(points, dtype=torch.float32, device=self.dev).reshape(-1, 3)
+        n = p.shape[0]
+        queries = torch.zeros((n, 8), dtype=torch.float32, device=self.dev)
+        queries[:, 0:3] = p
+        queries[:, 3] = torch.as_tensor(max_distance, dtype=torch.float32, device=self.dev)
+        ign = 0xFFFFFFFF if ignore_body is None else ignore_body
+        ign = torch.as_tensor(ign, dtype=torch.int64, device=self.dev)
+        queries.view(torch.int32)[:, 4] = (((ign & 0xFFFFFFFF) ^ 0x80000000) - 0x80000000).to(torch.int32)          # (the uint32 bits, as int32)
+        raw = self.closest_records(queries)
+        f = raw.view(torch.float32).reshape(n, 12)
+        u = raw.view(torch.int32).reshape(n, 12).to(torch.int64) & 0xFFFFFFFF
+        out = dict(distance=f[:, 0], normal=f[:, 1:4], point=f[:, 4:7], body=u[:, 7], collider=u[:, 8], shape=u[:, 9], tag=u[:, 10], raw=raw)
         if synchronize:
             torch.cuda.current_stream(self.dev).synchronize()
         return out
