@@ -79,7 +79,7 @@
  *      exported the views: nh_set_option(ctx, "sync_exports_views", 1) restores that contract at its old price; INTEGRATION.md.)  Any entry point outside the sample's
  *      call order between nh_collide and nh_apply_impulses turns a still step into a full one first, so everything it observes is what a full step
  *      produces.  nh_Counts.still_steps / still_replays count them.
- *      The scene queries (nh_query_build, nh_raycast, nh_spherecast, nh_boxcast, nh_capsulecast, nh_overlap, nh_closest) are not entry points of the step in this sense: they neither export nor settle nor turn a still step into a
+ *      The scene queries (nh_query_build, nh_query_refit, nh_raycast, nh_spherecast, nh_boxcast, nh_capsulecast, nh_overlap, nh_closest) are not entry points of the step in this sense: they neither export nor settle nor turn a still step into a
  *      full one, and they do not count -- see "scene queries" below.
  *
  * Threading: one context = one HIP stream = one world at a time; no global mutable state.
@@ -352,8 +352,9 @@ int nh_stream_latest(nh_context* ctx, nh_StreamInfo* out);
 /* ---- scene queries: ray casts, sphere, box and capsule casts, overlaps and closest points against the device-resident world ---------------------------------------------
    nh_query_build snapshots the world transforms and AABBs of ALL box and sphere colliders -- those of sleeping bodies and of body 0 (the static world) included -- and
    builds a bounding-volume hierarchy over them (a linear BVH: Morton keys, a radix tree, bottom-up boxes) into buffers the library owns: they grow with the collider
-   count (~250 B per collider) and are freed by nh_destroy.  nh_raycast answers `count` rays (nh_overlap, below, `count` shapes) against the LAST build: the hierarchy does not follow the bodies, so
-   rebuild after they have moved (after nh_step / nh_advance) before casting against the new positions.  All pointers are DEVICE memory; both calls only enqueue work
+   count (~190 B per collider) and are freed by nh_destroy.  nh_raycast answers `count` rays (nh_overlap, below, `count` shapes) against the LAST build: the hierarchy does not follow the bodies by itself, so
+   after they have moved (after nh_step / nh_advance) call nh_query_refit (below: the same tree, today's boxes) or rebuild before casting against the new positions;
+   wherever this header says "the LAST nh_query_build", a later nh_query_refit counts.  All pointers are DEVICE memory; both calls only enqueue work
    on the context's stream, like every other entry point (read the hits after nh_synchronize or a stream / event wait of your own).
    Semantics (nudge_amd/csrc/nh_query.h):
      - closest hit = the smallest t with 0 <= t <= max_t, over the colliders not belonging to `ignore_body` (0xffffffff: none is ignored); ties are broken by
@@ -369,7 +370,7 @@ int nh_stream_latest(nh_context* ctx, nh_StreamInfo* out);
    entry points, or between two nh_step calls, they leave every later step bit-identical, with the same still_steps / still_replays / ahead_steps / pair_steps /
    asleep_steps.  They read bodies->transforms as the stream has them at that point: under NH_FLAG_FUSED_STEP the fused solver advances part of the bodies inside
    nh_apply_impulses, so a build between nh_apply_impulses and nh_advance sees a world half advanced -- build after nh_advance (or nh_step) for a consistent one.
-   Not built: queries on a partitioned world (nh_partition_*), an incremental refit across steps. */
+   Not built: queries on a partitioned world (nh_partition_*). */
 typedef struct nh_Ray { float origin[3]; float max_t; float direction[3]; uint32_t ignore_body; } nh_Ray;                                            /* 32 B */
 typedef struct nh_RayHit { float t; float normal[3]; uint32_t body; uint32_t collider; uint32_t shape; uint32_t tag; } nh_RayHit;                     /* 32 B */
 enum { NH_SHAPE_BOX = 0u, NH_SHAPE_SPHERE = 1u, NH_SHAPE_CAPSULE = 2u, NH_SHAPE_NONE = 0xffffffffu };    /* nh_RayHit.shape; NONE = miss.  CAPSULE is a QUERY
@@ -378,6 +379,27 @@ enum { NH_SHAPE_BOX = 0u, NH_SHAPE_SPHERE = 1u, NH_SHAPE_CAPSULE = 2u, NH_SHAPE_
 enum { NH_RAY_ANY_HIT = 1u };
 int nh_query_build(nh_context* ctx, const nh_BodyData* bodies, const nh_ColliderData* colliders);
 int nh_raycast(nh_context* ctx, const nh_Ray* rays, uint32_t count, nh_RayHit* hits, uint32_t flags);
+
+/* nh_query_refit: the hierarchy of the last nh_query_build, made current -- the per-step call of a character controller, a camera or a sensor that casts every step.
+   It keeps the leaf order, the tree's links, the sorted keys and the key frame of that build, and re-reads EVERYTHING else from the arrays it is given: body and
+   collider transforms, shapes, tags, the collider -> body mapping.  Every collider record, every leaf box (the build's arithmetic and pad) and every internal box is
+   rewritten.
+   CONTRACT: after nh_query_refit(ctx, b, c) every query call writes exactly the bytes it writes after nh_query_build(ctx, b, c) on the same arrays -- for
+   NH_RAY_ANY_HIT the same hit-or-miss, which is all that flag promises.  Only the TIME the queries take may differ: the tree keeps the topology of the last BUILD, so
+   its boxes loosen as bodies move away from where they were sorted (nh_closest's Morton seed then looks among the keys of that build; it only proposes real colliders
+   that are evaluated exactly).  Measured at 1,004,524 colliders on one MI355X
+   (profiles/refit_rates.log): a refit takes 0.23 ms where a build takes 0.60 ms (0.42 and 1.1 full steps of that world); after 70 steps of free fall and landing
+   the refitted tree answered 1 M incoherent rays at 1.00x and 1 M unbounded nh_closest queries at 1.00x the rate of a fresh one -- a lattice that falls straight
+   down keeps its order; bodies that travel across the scene will loosen the tree faster, and the caller rebuilds when its own query times say so.
+   Returns NH_ERR_INVALID for null arguments, before any nh_query_build, when boxes.count or spheres.count differs from the last build's (the leaf order is by
+   combined collider index: another count is another world -- rebuild), and for the null arrays nh_query_build refuses.  Zero colliders: NH_OK, nothing launched.
+   Never allocates, never waits.  An OBSERVER like the build (note 9): only launches on the context's stream; it leaves the bounds the next build accumulates alone,
+   so a build after any number of refits is the build it would have been without them.
+   nh_query_stats (diagnostic; WAITS for the stream): of the last build's tree, the collider count, the length and number of the leaf runs the box pass cuts it into,
+   the number of nodes that cross a run boundary (the pass's second, single-workgroup phase) and the height of the tree those nodes form. */
+typedef struct nh_QueryStats { uint32_t colliders, run_length, runs, top_nodes, top_depth; } nh_QueryStats;
+int nh_query_refit(nh_context* ctx, const nh_BodyData* bodies, const nh_ColliderData* colliders);
+int nh_query_stats(nh_context* ctx, nh_QueryStats* out);
 
 /* nh_spherecast: where a swept ball first touches the world of the LAST nh_query_build -- character controllers, thick projectiles, camera collision.
    nh_SphereCast's first 32 bytes are nh_Ray's fields at the same offsets; `reserved` is not read.  Exact predicates: nudge_amd/csrc/nh_query.h.
@@ -470,7 +492,7 @@ int nh_capsulecast(nh_context* ctx, const nh_CapsuleCast* casts, uint32_t count,
        ignored) -- inside several, the deepest -- with ties by (shape, collider index) ascending, so a brute force over all colliders gives the same
        bytes.  max_distance = +inf finds the nearest collider anywhere; max_distance = 0 only colliders that contain or touch p.  A collider of a body
        that does not exist (NaN pose) is never reported;
-     - THE REACH RULE: where p lies outside the collider's box in the hierarchy (k_q_refit's padded box) at squared distance d2 > 0
+     - THE REACH RULE: where p lies outside the collider's box in the hierarchy (k_q_boxes_runs' padded box) at squared distance d2 > 0
        (per axis fmaxf(fmaxf(lo - p, p - hi), 0), then the sum of the squares), the distance is max(distance, sqrtf(d2)).  It is what lets the walk
        prune exactly; it moves a distance only where rounding put the predicate in front of a box padded by 2^-18 of its coordinates;
      - a miss writes shape = NH_SHAPE_NONE, distance = max_distance, normal = point = 0 and body = collider = tag = 0xffffffff;

@@ -97,7 +97,21 @@ NH_HD nh_QHit nh_q_ray_sphere(nh_f3 o, nh_f3 d, nh_f3 c, float rad) {
 	return r;
 }
 
-// Conservative box of a leaf (k_q_refit): a relative pad of 2^-18 of its largest coordinate, so that no rounding of the walk's slab tests can cut off a
+// The cut of the box pass (nh_query.hip, k_q_boxes_runs / k_q_boxes_top): the leaves, in key order, are cut into runs of NH_Q_RUN.  A Karras node
+// covers the contiguous leaf range [first, last] and its own index is one end of it, so a node whose range lies in ONE run has its index, both
+// children and their whole subtrees in that run (its workgroup merges it in LDS, slot = index - run start); every other node CROSSES a run boundary
+// and belongs to the top phase.  k_q_tree writes the verdict on a node's PARENT next to the parent's index (parents are internal nodes: < 2^30), with
+// the side the node hangs on: the left child of a split at g has index g, the right child g + 1, leaf or not.
+#define NH_Q_RUN 1024u
+#define NH_Q_PARENT_TOP 0x80000000u      // the parent crosses a run boundary (the root's parent word, 0xffffffff, reads as "top" as well)
+#define NH_Q_PARENT_RIGHT 0x40000000u    // this node is its parent's right child
+#define NH_Q_PARENT_ID 0x3fffffffu
+NH_HD bool nh_q_run_crossing(uint32_t first, uint32_t last) { return first / NH_Q_RUN != last / NH_Q_RUN; }
+NH_HD uint32_t nh_q_parent_word(uint32_t parent, bool right, bool top) {
+	return parent | (right ? NH_Q_PARENT_RIGHT : 0u) | (top ? NH_Q_PARENT_TOP : 0u);
+}
+
+// Conservative box of a leaf (k_q_boxes_runs): a relative pad of 2^-18 of its largest coordinate, so that no rounding of the walk's slab tests can cut off a
 // collider the exact test hits (the cast side adds the same of its origin, k_q_raycast / k_q_spherecast)
 NH_HD float nh_q_pad(nh_f3 mn, nh_f3 mx) {
 	const float m = fmaxf(fmaxf(fmaxf(fabsf(mn.x), fabsf(mn.y)), fmaxf(fabsf(mn.z), fabsf(mx.x))), fmaxf(fabsf(mx.y), fabsf(mx.z)));
@@ -138,7 +152,7 @@ NH_HD bool nh_q_overlap_sphere_box(nh_f3 c, float r, nh_f3 p, nh_quat q, nh_f3 h
 // E_ij = |R_ij| + 2^-20: when an edge of a is (nearly) parallel to an edge of b, their cross product is (nearly) zero and both sides of its test are
 // rounding noise, so without the epsilon a pair of boxes that overlaps could be separated by a degenerate axis.  The epsilon is above the rounding of
 // R for unit quaternions (a few ulp of 1) and only ever widens the radii: it can add a touch, never remove one.  What it adds is bounded by three
-// more tests, first: the two world AABBs -- c -+ nh_q_box_extent, the very bounds the build (k_q_xform) and the query walk compute before padding --
+// more tests, first: the two world AABBs -- c -+ nh_q_box_extent, the very bounds the build (k_q_boxes_runs) and the query walk compute before padding --
 // must touch.  Exact boxes that overlap have touching AABBs (up to rounding), and a pair the epsilon lets through is at least in the tree's reach:
 // the padded node boxes contain these bounds, so the walk can never prune what this predicate accepts.
 #define NH_Q_SAT_EPS 9.5367431640625e-07f
@@ -285,7 +299,7 @@ NH_HD bool nh_q_cast_node(nh_f3 lo, nh_f3 hi, nh_f3 o, nh_f3 inv, float w, float
 	return t0 <= t1 && t1 >= 0.0f;
 }
 
-// The box of a leaf as the build stores it (k_q_xform's world AABB, k_q_refit's pad): what the host rebuilds to apply the sweep's reach rule.
+// The box of a leaf as the build stores it (the world AABB and the pad of k_q_boxes_runs): what the host rebuilds to apply the sweep's reach rule.
 NH_HD void nh_q_leaf_box(nh_f3 p, nh_quat q, nh_f3 h, bool box, nh_f3& lo, nh_f3& hi) {
 	const nh_f3 e = box ? nh_q_box_extent(q, h) : h;
 	const nh_f3 mn = p - e, mx = p + e;

@@ -1,17 +1,22 @@
 // nh_query.hip -- scene queries against the device-resident world: nh_query_build (a linear BVH over every box and sphere collider, built from
-// the current transforms), nh_raycast (batched closest-hit / any-hit ray casts against the last build), nh_spherecast, nh_boxcast and nh_capsulecast (the
-// same for swept balls, oriented boxes and capsules) and nh_overlap (the colliders touching each of a batch of spheres, boxes or capsules, as
-// variable-length segments).  include/nudge_hip.h, "scene queries".
+// the current transforms), nh_query_refit (the same tree with the boxes of the current transforms), nh_raycast (batched closest-hit / any-hit ray
+// casts against the last build or refit), nh_spherecast, nh_boxcast and nh_capsulecast (the same for swept balls, oriented boxes and capsules) and
+// nh_overlap (the colliders touching each of a batch of spheres, boxes or capsules, as variable-length segments).  include/nudge_hip.h, "scene queries".
 //
 // Build (one launch each, plus the library's radix sort):
-//   k_q_xform   one lane per collider (boxes, then spheres): world pose (k_xform's arithmetic, nh_query.h), world AABB, the record the ray test
-//               reads; the bounds of the collider positions by a wave reduction and one atomic per wave
+//   k_q_xform   one lane per collider (boxes, then spheres): world pose (k_xform's arithmetic, nh_query.h) and the record the ray test reads; the
+//               bounds of the collider positions by a wave reduction, a reduction over the workgroup's waves in LDS and one atomic per workgroup
 //   k_q_keys    48-bit Morton key of each position in the frame of those bounds (nh_morton_scale / nh_morton_of), value = collider index
 //   nh_sort_u64_u32  stable: equal keys keep collider order, which the tree's key comparison extends by the sorted index (Karras 2012, 4)
-//   k_q_tree    one lane per internal node: range and split from common prefixes, children and parents; per split, the node that starts right
-//               of it (the escape links below are read from that table)
-//   k_q_refit   one lane per leaf: escape links of its leaf and of the internal node of the same index, the leaf's box, then upwards with an
-//               arrival counter per internal node -- the second child to arrive merges the two boxes and goes on
+//   k_q_tree    one lane per internal node: range and split from common prefixes, children and parents (the parent word says whether the parent
+//               crosses a run boundary, nh_query.h); per split, the node that starts right of it; the list of the top phase's entry nodes
+//   k_q_links   one lane per internal node: its escape link, read from that table
+//   the box pass, below
+// Box pass (the tail of the build, and all of nh_query_refit: it reads the sorted index, the parent words, rchild and right_at of the last build):
+//   k_q_boxes_runs  one workgroup per run of NH_Q_RUN consecutive leaves, a lane per leaf: world pose, record and padded leaf box straight from the
+//               caller's arrays, then the internal nodes whose range lies inside the run, bottom-up with arrival counters in LDS
+//   k_q_boxes_top   behind the kernel boundary, ONE workgroup: the nodes whose range crosses a run boundary, from the entry list, with arrival
+//               counters in global memory at workgroup scope
 // Node ids: internal nodes 0 .. n-2 (root 0), leaf j (j-th collider in key order) n-1+j; with one collider the root is that leaf.
 // Traversal is stackless: a node that is missed or a leaf that is done continues at its ESCAPE link (the next node in pre-order after its subtree),
 // a hit internal node at its left child.  A private stack array would go to scratch memory.
@@ -29,8 +34,11 @@ struct nh_QRec { float4 a, b, c; };
 struct nh_QNode { float4 a, b; };
 // words the build's kernels share: collider count (the sort reads it), bounds of the positions (flipped floats); nh_overlap's: a word that stays 0
 // (the element count of its scan is all `extra`), the length of the written prefix of records (its sort and gather read it), the wrap flag; the bounds
-// of the LAST build (k_q_tree keeps them there before it resets smin / smax: nh_closest's seed finds a point's place among the keys in their frame)
-struct nh_QCtl { uint32_t count, zero, ov_written, ov_wrap; uint32_t smin[4]; uint32_t smax[4]; uint32_t kmin[4]; uint32_t kmax[4]; };
+// of the LAST build (k_q_tree keeps them there before it resets smin / smax: nh_closest's seed finds a point's place among the keys in their frame);
+// the box pass's: the number of entry nodes of the top phase (k_q_tree counts them) and the height of the tree of top nodes (k_q_boxes_top, for
+// nh_query_stats).  A refit touches top_depth alone.
+struct nh_QCtl { uint32_t count, zero, ov_written, ov_wrap; uint32_t smin[4]; uint32_t smax[4]; uint32_t kmin[4]; uint32_t kmax[4];
+                 uint32_t top_n, top_depth, pad0, pad1; };
 
 struct nh_QueryState {
 	uint32_t capacity;           // colliders the buffers have room for
@@ -38,61 +46,70 @@ struct nh_QueryState {
 	uint32_t n, nbox;            // of the last build
 	nh_QCtl* ctl;
 	nh_QRec* rec;
-	float4* aabb;                // 2 per collider
 	uint64_t* keys_a; uint64_t* keys_b; uint32_t* idx_a; uint32_t* idx_b; uint32_t* hist;
 	const uint64_t* keys;        // the sorted keys of the last build (keys_a or keys_b, as the sort left them): leaf j's is keys[j]
+	const uint32_t* idx;         // the leaf order of the last build (idx_a or idx_b): leaf j is collider idx[j]
 	nh_QNode* nodes;             // 2 n - 1
-	uint32_t* parent;            // by node id
+	uint32_t* parent;            // by node id: nh_q_parent_word (nh_query.h)
 	uint32_t* rchild;            // by internal node
 	uint32_t* last;              // by internal node: last leaf of its range
 	uint32_t* right_at;          // by split position: the right child of the node that splits there
-	uint32_t* arrive;            // by internal node: arrival counter of the refit
+	uint32_t* arrive;            // by internal node: arrival counter of the top phase (0 between launches)
+	uint32_t* top;               // the entry nodes of the top phase: nodes inside one run whose parent crosses a run boundary (ctl->top_n of them)
 	uint32_t ov_capacity;        // nh_overlap's sort scratch, by record of the caller's capacity
 	uint64_t* ov_keys_a; uint64_t* ov_keys_b; uint32_t* ov_vals_a; uint32_t* ov_vals_b;
 };
 
+// the caller's arrays as the kernels read them
+struct nh_QWorld {
+	const nh_Transform* body_xf; uint32_t nbodies;
+	const nh_Transform* box_xf; const nh_BoxCollider* box_data; const uint32_t* box_tags; uint32_t nbox;
+	const nh_Transform* sph_xf; const nh_SphereCollider* sph_data; const uint32_t* sph_tags; uint32_t nsph;
+};
+
+// Collider c (combined index): its record, and the half extents of its world AABB
+__device__ __forceinline__ nh_f3 nh_q_collider(const nh_QWorld& W, uint32_t c, nh_QRec& r) {
+	const bool is_box = c < W.nbox;
+	const nh_Transform l = is_box ? W.box_xf[c] : W.sph_xf[c - W.nbox];
+	nh_QPose w;
+	nh_f3 h;
+	if (l.body < W.nbodies) {
+		const nh_Transform b = W.body_xf[l.body];
+		w = nh_q_pose(b.position, b.rotation, l.position, l.rotation);
+	} else {
+		// (a collider of a body that does not exist: never hit, never in the bounds)
+		const float q = __uint_as_float(0x7fc00000u);
+		w.p = nh_make3(q, q, q); w.q = { q, q, q, q };
+	}
+	if (is_box) {
+		const nh_BoxCollider bc = W.box_data[c];
+		h = nh_make3(bc.size[0], bc.size[1], bc.size[2]);
+	} else {
+		const float rad = W.sph_data[c - W.nbox].radius;
+		h = nh_make3(rad, rad, rad);
+	}
+	const uint32_t tag = is_box ? W.box_tags[c] : W.sph_tags[c - W.nbox];
+	r.a = make_float4(w.p.x, w.p.y, w.p.z, __uint_as_float(l.body));
+	r.b = make_float4(w.q.x, w.q.y, w.q.z, w.q.s);
+	r.c = make_float4(h.x, h.y, h.z, __uint_as_float(tag));
+	return is_box ? nh_q_box_extent(w.q, h) : h;
+}
+
 // ---- build ----------------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_q_xform(const nh_Transform* __restrict__ body_xf, uint32_t nbodies,
-                                                 const nh_Transform* __restrict__ box_xf, const nh_BoxCollider* __restrict__ box_data, const uint32_t* __restrict__ box_tags, uint32_t nbox,
-                                                 const nh_Transform* __restrict__ sph_xf, const nh_SphereCollider* __restrict__ sph_data, const uint32_t* __restrict__ sph_tags, uint32_t nsph,
-                                                 nh_QRec* __restrict__ rec, float4* __restrict__ aabb, nh_QCtl* __restrict__ ctl) {
-	const uint32_t n = nbox + nsph;
-	if (blockIdx.x == 0 && threadIdx.x == 0) ctl->count = n;
+__global__ __launch_bounds__(256) void k_q_xform(nh_QWorld W, nh_QRec* __restrict__ rec, nh_QCtl* __restrict__ ctl) {
+	__shared__ uint32_t wave_min[4][3], wave_max[4][3];
+	const uint32_t n = W.nbox + W.nsph;
+	if (blockIdx.x == 0 && threadIdx.x == 0) { ctl->count = n; ctl->top_n = 0u; ctl->top_depth = 0u; }
 	uint32_t lmin[3] = { 0xffffffffu, 0xffffffffu, 0xffffffffu }, lmax[3] = { 0u, 0u, 0u };
 	for (uint32_t c = blockIdx.x * blockDim.x + threadIdx.x; c < n; c += gridDim.x * blockDim.x) {
-		const bool is_box = c < nbox;
-		const nh_Transform l = is_box ? box_xf[c] : sph_xf[c - nbox];
-		nh_QPose w;
-		nh_f3 h;
-		if (l.body < nbodies) {
-			const nh_Transform b = body_xf[l.body];
-			w = nh_q_pose(b.position, b.rotation, l.position, l.rotation);
-		} else {
-			// (a collider of a body that does not exist: never hit, never in the bounds)
-			const float q = __uint_as_float(0x7fc00000u);
-			w.p = nh_make3(q, q, q); w.q = { q, q, q, q };
-		}
-		if (is_box) {
-			const nh_BoxCollider bc = box_data[c];
-			h = nh_make3(bc.size[0], bc.size[1], bc.size[2]);
-		} else {
-			const float r = sph_data[c - nbox].radius;
-			h = nh_make3(r, r, r);
-		}
-		const nh_f3 e = is_box ? nh_q_box_extent(w.q, h) : h;
-		const uint32_t tag = is_box ? box_tags[c] : sph_tags[c - nbox];
 		nh_QRec r;
-		r.a = make_float4(w.p.x, w.p.y, w.p.z, __uint_as_float(l.body));
-		r.b = make_float4(w.q.x, w.q.y, w.q.z, w.q.s);
-		r.c = make_float4(h.x, h.y, h.z, __uint_as_float(tag));
+		nh_q_collider(W, c, r);
 		rec[c] = r;
-		aabb[2u * c] = make_float4(w.p.x - e.x, w.p.y - e.y, w.p.z - e.z, 0.0f);
-		aabb[2u * c + 1u] = make_float4(w.p.x + e.x, w.p.y + e.y, w.p.z + e.z, 0.0f);
-		if (w.p.x == w.p.x && w.p.y == w.p.y && w.p.z == w.p.z) {
+		if (r.a.x == r.a.x && r.a.y == r.a.y && r.a.z == r.a.z) {
 			uint32_t f;
-			f = nh_float_flip(w.p.x); lmin[0] = min(lmin[0], f); lmax[0] = max(lmax[0], f);
-			f = nh_float_flip(w.p.y); lmin[1] = min(lmin[1], f); lmax[1] = max(lmax[1], f);
-			f = nh_float_flip(w.p.z); lmin[2] = min(lmin[2], f); lmax[2] = max(lmax[2], f);
+			f = nh_float_flip(r.a.x); lmin[0] = min(lmin[0], f); lmax[0] = max(lmax[0], f);
+			f = nh_float_flip(r.a.y); lmin[1] = min(lmin[1], f); lmax[1] = max(lmax[1], f);
+			f = nh_float_flip(r.a.z); lmin[2] = min(lmin[2], f); lmax[2] = max(lmax[2], f);
 		}
 	}
 	for (int k = 0; k < 3; ++k) {
@@ -101,8 +118,16 @@ __global__ __launch_bounds__(256) void k_q_xform(const nh_Transform* __restrict_
 			lmax[k] = max(lmax[k], (uint32_t)__shfl_xor((int)lmax[k], d));
 		}
 	}
-	if (nh_lane() == 0 && lmin[0] <= lmax[0]) {
-		for (int k = 0; k < 3; ++k) { atomicMin(&ctl->smin[k], lmin[k]); atomicMax(&ctl->smax[k], lmax[k]); }
+	if (nh_lane() == 0) {
+		for (int k = 0; k < 3; ++k) { wave_min[threadIdx.x >> 6][k] = lmin[k]; wave_max[threadIdx.x >> 6][k] = lmax[k]; }
+	}
+	__syncthreads();
+	if (threadIdx.x < 3u) {
+		const uint32_t k = threadIdx.x;
+		const uint32_t mn = min(min(wave_min[0][k], wave_min[1][k]), min(wave_min[2][k], wave_min[3][k]));
+		const uint32_t mx = max(max(wave_max[0][k], wave_max[1][k]), max(wave_max[2][k], wave_max[3][k]));
+		// (no finite position in this workgroup: mn stays all ones and mx 0, which change nothing)
+		if (mn <= mx) { atomicMin(&ctl->smin[k], mn); atomicMax(&ctl->smax[k], mx); }
 	}
 }
 
@@ -129,69 +154,140 @@ __device__ __forceinline__ int nh_q_delta(const uint64_t* __restrict__ keys, uin
 
 __global__ __launch_bounds__(256) void k_q_tree(const uint64_t* __restrict__ keys, uint32_t n, nh_QNode* __restrict__ nodes, uint32_t* __restrict__ parent,
                                                 uint32_t* __restrict__ rchild, uint32_t* __restrict__ last, uint32_t* __restrict__ right_at,
-                                                uint32_t* __restrict__ arrive, nh_QCtl* __restrict__ ctl) {
+                                                uint32_t* __restrict__ arrive, uint32_t* __restrict__ top, nh_QCtl* __restrict__ ctl) {
 	if (blockIdx.x == 0 && threadIdx.x == 0) {
 		parent[0] = NH_Q_NONE;
 		// the bounds the next build accumulates into (k_q_keys of this one has read them); this build's are kept for nh_closest
 		for (int k = 0; k < 3; ++k) { ctl->kmin[k] = ctl->smin[k]; ctl->kmax[k] = ctl->smax[k]; ctl->smin[k] = 0xffffffffu; ctl->smax[k] = 0u; }
 	}
-	for (uint32_t u = blockIdx.x * blockDim.x + threadIdx.x; u + 1u < n; u += gridDim.x * blockDim.x) {
-		const int64_t i = u;
-		const int d = nh_q_delta(keys, n, i, i + 1) > nh_q_delta(keys, n, i, i - 1) ? 1 : -1;
-		const int dmin = nh_q_delta(keys, n, i, i - d);
-		int64_t lmax = 2;
-		while (nh_q_delta(keys, n, i, i + lmax * d) > dmin) lmax *= 2;
-		int64_t l = 0;
-		for (int64_t t = lmax / 2; t >= 1; t /= 2)
-			if (nh_q_delta(keys, n, i, i + (l + t) * d) > dmin) l += t;
-		const int64_t j = i + l * d;
-		const int dnode = nh_q_delta(keys, n, i, j);
-		int64_t s = 0, t = l;
-		do {
-			t = (t + 1) / 2;
-			if (nh_q_delta(keys, n, i, i + (s + t) * d) > dnode) s += t;
-		} while (t > 1);
-		const int64_t gamma = i + s * d + (d < 0 ? -1 : 0);
-		const int64_t first = i < j ? i : j, end = i < j ? j : i;
-		const uint32_t left = first == gamma ? (uint32_t)(n - 1u + gamma) : (uint32_t)gamma;
-		const uint32_t right = end == gamma + 1 ? (uint32_t)(n - 1u + gamma + 1) : (uint32_t)(gamma + 1);
-		nodes[u].a.w = __uint_as_float(left);
-		rchild[u] = right;
-		last[u] = (uint32_t)end;
-		right_at[gamma] = right;
-		parent[left] = u;
-		parent[right] = u;
-		arrive[u] = 0u;
+	// (whole waves go round together: the entry list is reserved per wave)
+	for (uint32_t u0 = blockIdx.x * blockDim.x; u0 + 1u < n; u0 += gridDim.x * blockDim.x) {
+		const uint32_t u = u0 + threadIdx.x;
+		bool enter_left = false, enter_right = false;
+		uint32_t left = 0u, right = 0u;
+		if (u + 1u < n) {
+			const int64_t i = u;
+			const int d = nh_q_delta(keys, n, i, i + 1) > nh_q_delta(keys, n, i, i - 1) ? 1 : -1;
+			const int dmin = nh_q_delta(keys, n, i, i - d);
+			int64_t lmax = 2;
+			while (nh_q_delta(keys, n, i, i + lmax * d) > dmin) lmax *= 2;
+			int64_t l = 0;
+			for (int64_t t = lmax / 2; t >= 1; t /= 2)
+				if (nh_q_delta(keys, n, i, i + (l + t) * d) > dmin) l += t;
+			const int64_t j = i + l * d;
+			const int dnode = nh_q_delta(keys, n, i, j);
+			int64_t s = 0, t = l;
+			do {
+				t = (t + 1) / 2;
+				if (nh_q_delta(keys, n, i, i + (s + t) * d) > dnode) s += t;
+			} while (t > 1);
+			const int64_t gamma = i + s * d + (d < 0 ? -1 : 0);
+			const int64_t first = i < j ? i : j, end = i < j ? j : i;
+			left = first == gamma ? (uint32_t)(n - 1u + gamma) : (uint32_t)gamma;
+			right = end == gamma + 1 ? (uint32_t)(n - 1u + gamma + 1) : (uint32_t)(gamma + 1);
+			nodes[u].a.w = __uint_as_float(left);
+			rchild[u] = right;
+			last[u] = (uint32_t)end;
+			right_at[gamma] = right;
+			const bool crossing = nh_q_run_crossing((uint32_t)first, (uint32_t)end);
+			parent[left] = nh_q_parent_word(u, false, crossing);
+			parent[right] = nh_q_parent_word(u, true, crossing);
+			arrive[u] = 0u;
+			// the top phase starts at the children that lie inside one run
+			enter_left = crossing && !nh_q_run_crossing((uint32_t)first, (uint32_t)gamma);
+			enter_right = crossing && !nh_q_run_crossing((uint32_t)gamma + 1u, (uint32_t)end);
+		}
+		const uint32_t at_left = nh_wave_reserve1(&ctl->top_n, enter_left);
+		if (enter_left) top[at_left] = left;
+		const uint32_t at_right = nh_wave_reserve1(&ctl->top_n, enter_right);
+		if (enter_right) top[at_right] = right;
 	}
 }
 
-__global__ __launch_bounds__(256) void k_q_refit(const uint32_t* __restrict__ idx, const float4* __restrict__ aabb, uint32_t n, nh_QNode* nodes,
-                                                 const uint32_t* __restrict__ parent, const uint32_t* __restrict__ rchild, const uint32_t* __restrict__ last,
-                                                 const uint32_t* __restrict__ right_at, uint32_t* arrive) {
-	for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += gridDim.x * blockDim.x) {
-		// escape links: the subtree of a node ends at the last leaf of its range; the next node in pre-order is the right child of the split there
-		if (j + 1u < n) {
-			const uint32_t e = last[j];
-			nodes[j].b.w = __uint_as_float(e + 1u == n ? NH_Q_NONE : right_at[e]);
-		}
+// escape links of the internal nodes: the subtree of a node ends at the last leaf of its range; the next node in pre-order is the right child of the
+// split there (a leaf's is right_at[its position]: k_q_boxes_runs writes it with the leaf)
+__global__ __launch_bounds__(256) void k_q_links(uint32_t n, nh_QNode* __restrict__ nodes, const uint32_t* __restrict__ last, const uint32_t* __restrict__ right_at) {
+	for (uint32_t u = blockIdx.x * blockDim.x + threadIdx.x; u + 1u < n; u += gridDim.x * blockDim.x) {
+		const uint32_t e = last[u];
+		nodes[u].b.w = __uint_as_float(e + 1u == n ? NH_Q_NONE : right_at[e]);
+	}
+}
+
+// ---- box pass -------------------------------------------------------------------------------------------------------------------------------
+// Bottom phase.  Workgroup b owns leaves [b * NH_Q_RUN, (b + 1) * NH_Q_RUN) and the internal nodes whose range lies inside them (nh_query.h): LDS slot
+// = node index - run start.  A slot holds the boxes of the node's two children, by side, and its arrival counter: a lane puts its box on its side,
+// then counts itself in; the second to arrive reads the other side, merges and goes on with the parent, until the parent word says "top".  Every
+// hand-off is inside the workgroup: LDS stores released and acquired at workgroup scope by the counter's atomic, no agent-scope fence, no global
+// atomic.  fminf / fmaxf: the boxes do not depend on who arrives first, and a NaN leaf (a body that does not exist) drops out of its ancestors.
+// The finished nodes leave through the slots after a barrier (the .w words of an internal node, child and escape links, stay as the build wrote them).
+__global__ __launch_bounds__(NH_Q_RUN) void k_q_boxes_runs(nh_QWorld W, const uint32_t* __restrict__ idx, const uint32_t* __restrict__ parent,
+                                                           const uint32_t* __restrict__ right_at, uint32_t n, nh_QRec* __restrict__ rec, nh_QNode* __restrict__ nodes) {
+	__shared__ float child_box[NH_Q_RUN][2][6];
+	__shared__ uint32_t arrived[NH_Q_RUN];
+	__shared__ uint32_t up[NH_Q_RUN];            // parent words of the run's internal nodes
+	const uint32_t base = blockIdx.x * NH_Q_RUN, s = threadIdx.x, j = base + s;
+	arrived[s] = 0u;
+	up[s] = j + 1u < n ? parent[j] : NH_Q_NONE;
+	uint32_t pw = NH_Q_NONE;
+	float lo[3] = { 0.0f, 0.0f, 0.0f }, hi[3] = { 0.0f, 0.0f, 0.0f };
+	if (j < n) {
 		const uint32_t c = idx[j];
-		float4 mn = aabb[2u * c], mx = aabb[2u * c + 1u];
-		const float pad = nh_q_pad(nh_make3(mn.x, mn.y, mn.z), nh_make3(mx.x, mx.y, mx.z));      // (nh_query.h: the host's sweep rule rebuilds this box)
-		mn = make_float4(mn.x - pad, mn.y - pad, mn.z - pad, __uint_as_float(NH_Q_LEAF | c));
-		mx = make_float4(mx.x + pad, mx.y + pad, mx.z + pad, __uint_as_float(j + 1u == n ? NH_Q_NONE : right_at[j]));
-		uint32_t me = n - 1u + j;
-		nh_QNode leaf; leaf.a = mn; leaf.b = mx;
-		nodes[me] = leaf;
-		// bottom-up: the second child to arrive at a node has both boxes.  Per-XCD L2s are not coherent: the box is released at agent scope before the
-		// arrival, and the second arriver acquires at agent scope before it reads its sibling's (MI355X_MICROARCH, inter-workgroup visibility)
-		uint32_t id = parent[me];
-		while (id != NH_Q_NONE) {
-			__builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-			const uint32_t old = __hip_atomic_fetch_add(&arrive[id], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-			if (old == 0u) break;
-			__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-			const uint32_t l = __float_as_uint(nodes[id].a.w);
-			const uint32_t other = l == me ? rchild[id] : l;
+		nh_QRec r;
+		const nh_f3 e = nh_q_collider(W, c, r);
+		rec[c] = r;
+		const nh_f3 mn = nh_make3(r.a.x - e.x, r.a.y - e.y, r.a.z - e.z), mx = nh_make3(r.a.x + e.x, r.a.y + e.y, r.a.z + e.z);
+		const float pad = nh_q_pad(mn, mx);      // (nh_query.h: the host's sweep rule rebuilds this box)
+		lo[0] = mn.x - pad; lo[1] = mn.y - pad; lo[2] = mn.z - pad;
+		hi[0] = mx.x + pad; hi[1] = mx.y + pad; hi[2] = mx.z + pad;
+		nh_QNode leaf;
+		leaf.a = make_float4(lo[0], lo[1], lo[2], __uint_as_float(NH_Q_LEAF | c));
+		leaf.b = make_float4(hi[0], hi[1], hi[2], __uint_as_float(j + 1u == n ? NH_Q_NONE : right_at[j]));
+		nodes[n - 1u + j] = leaf;
+		pw = parent[n - 1u + j];
+	}
+	__syncthreads();
+	while (!(pw & NH_Q_PARENT_TOP)) {
+		const uint32_t slot = (pw & NH_Q_PARENT_ID) - base, side = (pw & NH_Q_PARENT_RIGHT) ? 1u : 0u;
+		float* mine = child_box[slot][side];
+		for (int k = 0; k < 3; ++k) { mine[k] = lo[k]; mine[3 + k] = hi[k]; }
+		const uint32_t before = __hip_atomic_fetch_add(&arrived[slot], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
+		if (before == 0u) break;
+		const float* other = child_box[slot][side ^ 1u];
+		for (int k = 0; k < 3; ++k) { lo[k] = fminf(lo[k], other[k]); hi[k] = fmaxf(hi[k], other[3 + k]); }
+		pw = up[slot];
+	}
+	__syncthreads();
+	if (arrived[s] == 2u) {
+		const float* l = child_box[s][0];
+		const float* r = child_box[s][1];
+		float* a = reinterpret_cast<float*>(&nodes[j].a);
+		float* b = reinterpret_cast<float*>(&nodes[j].b);
+		for (int k = 0; k < 3; ++k) { a[k] = fminf(l[k], r[k]); b[k] = fmaxf(l[3 + k], r[3 + k]); }
+	}
+}
+
+// Top phase: the nodes that cross a run boundary -- with B runs at most B - 2 have two crossing children, the rest are chains with one child finished
+// below; few (nh_query_stats counts them) but deep.  The launch boundary has made k_q_boxes_runs' boxes visible.  ONE workgroup climbs from the entry
+// list: a lane whose box is in nodes[] counts itself in at the parent; the second to arrive merges its sibling's box, writes the parent and goes on.
+// All hand-offs are between waves of this one workgroup -- one CU, one L1, one L2 -- so the counter's atomic releases and acquires at WORKGROUP
+// scope and nothing in the pass needs an agent-scope fence.  The second arriver leaves the counter at 0 for the next pass.  The counter's upper 24
+// bits carry the first arriver's height, so that the root's lane knows the height of the top tree (the longest chain, for nh_query_stats).
+#define NH_Q_TOP_BLOCK 1024
+__global__ __launch_bounds__(NH_Q_TOP_BLOCK) void k_q_boxes_top(const uint32_t* __restrict__ top, nh_QCtl* ctl, nh_QNode* nodes,
+                                                                const uint32_t* __restrict__ parent, const uint32_t* __restrict__ rchild, uint32_t* arrive) {
+	const uint32_t m = ctl->top_n;
+	for (uint32_t e = threadIdx.x; e < m; e += NH_Q_TOP_BLOCK) {
+		const uint32_t me = top[e];
+		float4 mn = nodes[me].a, mx = nodes[me].b;
+		uint32_t height = 0u;
+		uint32_t pw = parent[me];
+		while (pw != NH_Q_NONE) {
+			const uint32_t id = pw & NH_Q_PARENT_ID;
+			const uint32_t before = __hip_atomic_fetch_add(&arrive[id], 1u | (height << 8), __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
+			if ((before & 0xffu) == 0u) break;
+			__hip_atomic_store(&arrive[id], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+			height = min(max(height, before >> 8) + 1u, 0xffffffu);
+			const uint32_t other = (pw & NH_Q_PARENT_RIGHT) ? __float_as_uint(nodes[id].a.w) : rchild[id];
 			const float4 omn = nodes[other].a, omx = nodes[other].b;
 			mn = make_float4(fminf(mn.x, omn.x), fminf(mn.y, omn.y), fminf(mn.z, omn.z), 0.0f);
 			mx = make_float4(fmaxf(mx.x, omx.x), fmaxf(mx.y, omx.y), fmaxf(mx.z, omx.z), 0.0f);
@@ -199,9 +295,9 @@ __global__ __launch_bounds__(256) void k_q_refit(const uint32_t* __restrict__ id
 			float* b = reinterpret_cast<float*>(&nodes[id].b);
 			a[0] = mn.x; a[1] = mn.y; a[2] = mn.z;
 			b[0] = mx.x; b[1] = mx.y; b[2] = mx.z;
-			me = id;
-			id = parent[id];
+			pw = parent[id];
 		}
+		if (pw == NH_Q_NONE) ctl->top_depth = height;
 	}
 }
 
@@ -650,7 +746,7 @@ __global__ __launch_bounds__(256) void k_q_overlap_gather(const uint32_t* __rest
 void nh_query_free(nh_context* ctx) {
 	nh_QueryState* q = ctx->query;
 	if (!q) return;
-	void* bufs[] = { q->ctl, q->rec, q->aabb, q->keys_a, q->keys_b, q->idx_a, q->idx_b, q->hist, q->nodes, q->parent, q->rchild, q->last, q->right_at, q->arrive,
+	void* bufs[] = { q->ctl, q->rec, q->keys_a, q->keys_b, q->idx_a, q->idx_b, q->hist, q->nodes, q->parent, q->rchild, q->last, q->right_at, q->arrive, q->top,
 	                 q->ov_keys_a, q->ov_keys_b, q->ov_vals_a, q->ov_vals_b };
 	for (void* b : bufs) if (b) hipFree(b);
 	delete q;
@@ -670,13 +766,12 @@ static int nh_query_reserve(nh_context* ctx, uint32_t C) {
 	if (C <= q->capacity) return NH_OK;
 	const uint32_t cap = C + C / 8u + 64u;
 	NH_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-	void* old[] = { q->rec, q->aabb, q->keys_a, q->keys_b, q->idx_a, q->idx_b, q->nodes, q->parent, q->rchild, q->last, q->right_at, q->arrive };
+	void* old[] = { q->rec, q->keys_a, q->keys_b, q->idx_a, q->idx_b, q->nodes, q->parent, q->rchild, q->last, q->right_at, q->arrive, q->top };
 	for (void* b : old) if (b) hipFree(b);
-	q->rec = nullptr; q->aabb = nullptr; q->keys_a = q->keys_b = nullptr; q->idx_a = q->idx_b = nullptr; q->nodes = nullptr;
-	q->parent = q->rchild = q->last = q->right_at = q->arrive = nullptr;
-	q->capacity = 0; q->built = false; q->keys = nullptr;
+	q->rec = nullptr; q->keys_a = q->keys_b = nullptr; q->idx_a = q->idx_b = nullptr; q->nodes = nullptr;
+	q->parent = q->rchild = q->last = q->right_at = q->arrive = q->top = nullptr;
+	q->capacity = 0; q->built = false; q->keys = nullptr; q->idx = nullptr;
 	NH_HIP_CHECK(ctx, hipMalloc((void**)&q->rec, sizeof(nh_QRec) * (size_t)cap));
-	NH_HIP_CHECK(ctx, hipMalloc((void**)&q->aabb, 2u * sizeof(float4) * (size_t)cap));
 	NH_HIP_CHECK(ctx, hipMalloc((void**)&q->keys_a, sizeof(uint64_t) * (size_t)cap));
 	NH_HIP_CHECK(ctx, hipMalloc((void**)&q->keys_b, sizeof(uint64_t) * (size_t)cap));
 	NH_HIP_CHECK(ctx, hipMalloc((void**)&q->idx_a, sizeof(uint32_t) * (size_t)cap));
@@ -687,37 +782,92 @@ static int nh_query_reserve(nh_context* ctx, uint32_t C) {
 	NH_HIP_CHECK(ctx, hipMalloc((void**)&q->last, sizeof(uint32_t) * (size_t)cap));
 	NH_HIP_CHECK(ctx, hipMalloc((void**)&q->right_at, sizeof(uint32_t) * (size_t)cap));
 	NH_HIP_CHECK(ctx, hipMalloc((void**)&q->arrive, sizeof(uint32_t) * (size_t)cap));
+	// (a node has at most one entry child per side, and a tree of n leaves at most n entries: every entry is the root of a disjoint subtree)
+	NH_HIP_CHECK(ctx, hipMalloc((void**)&q->top, sizeof(uint32_t) * (size_t)cap));
 	q->capacity = cap;
 	return NH_OK;
+}
+
+static int nh_query_args(const nh_BodyData* bodies, const nh_ColliderData* colliders, uint32_t* count) {
+	const uint32_t nbox = colliders->boxes.count, nsph = colliders->spheres.count;
+	const uint64_t C64 = (uint64_t)nbox + nsph;
+	if (C64 >= NH_Q_MAX_COLLIDERS) return NH_ERR_INVALID;
+	if (C64 && (!bodies->transforms && bodies->count)) return NH_ERR_INVALID;
+	if (nbox && (!colliders->boxes.tags || !colliders->boxes.data || !colliders->boxes.transforms)) return NH_ERR_INVALID;
+	if (nsph && (!colliders->spheres.tags || !colliders->spheres.data || !colliders->spheres.transforms)) return NH_ERR_INVALID;
+	*count = (uint32_t)C64;
+	return NH_OK;
+}
+
+static nh_QWorld nh_query_world(const nh_BodyData* bodies, const nh_ColliderData* colliders) {
+	nh_QWorld W;
+	W.body_xf = bodies->transforms; W.nbodies = bodies->count;
+	W.box_xf = colliders->boxes.transforms; W.box_data = colliders->boxes.data; W.box_tags = colliders->boxes.tags; W.nbox = colliders->boxes.count;
+	W.sph_xf = colliders->spheres.transforms; W.sph_data = colliders->spheres.data; W.sph_tags = colliders->spheres.tags; W.nsph = colliders->spheres.count;
+	return W;
+}
+
+// The box pass over the tree of the last build: two launches, the second only where the tree has more than one run.
+static void nh_query_boxes(nh_context* ctx, const nh_QWorld& W, uint32_t C) {
+	nh_QueryState* q = ctx->query;
+	NH_LAUNCH(ctx, "q_boxes_runs", k_q_boxes_runs, (C + NH_Q_RUN - 1u) / NH_Q_RUN, NH_Q_RUN, W, q->idx, q->parent, q->right_at, C, q->rec, q->nodes);
+	if (C > NH_Q_RUN) NH_LAUNCH(ctx, "q_boxes_top", k_q_boxes_top, 1, NH_Q_TOP_BLOCK, q->top, q->ctl, q->nodes, q->parent, q->rchild, q->arrive);
 }
 
 // Observer: no nh_flush_pending, no view export, no counter -- only launches on the stream and buffers of its own (header, "scene queries").
 extern "C" int nh_query_build(nh_context* ctx, const nh_BodyData* bodies, const nh_ColliderData* colliders) {
 	if (!ctx || !bodies || !colliders) return NH_ERR_INVALID;
-	const uint32_t nbox = colliders->boxes.count, nsph = colliders->spheres.count;
-	const uint64_t C64 = (uint64_t)nbox + nsph;
-	if (C64 >= NH_Q_MAX_COLLIDERS) return NH_ERR_INVALID;
-	const uint32_t C = (uint32_t)C64;
-	if (C && (!bodies->transforms && bodies->count)) return NH_ERR_INVALID;
-	if (nbox && (!colliders->boxes.tags || !colliders->boxes.data || !colliders->boxes.transforms)) return NH_ERR_INVALID;
-	if (nsph && (!colliders->spheres.tags || !colliders->spheres.data || !colliders->spheres.transforms)) return NH_ERR_INVALID;
+	uint32_t C = 0;
+	{ const int rc = nh_query_args(bodies, colliders, &C); if (rc) return rc; }
 	NH_HIP_CHECK(ctx, hipSetDevice(ctx->device));
 	{ const int rc = nh_query_reserve(ctx, C); if (rc) return rc; }
 	nh_QueryState* q = ctx->query;
 	if (C) {
-		NH_LAUNCH(ctx, "q_xform", k_q_xform, nh_grid_for(C, 256, 4096), 256, bodies->transforms, bodies->count,
-		          colliders->boxes.transforms, colliders->boxes.data, colliders->boxes.tags, nbox,
-		          colliders->spheres.transforms, colliders->spheres.data, colliders->spheres.tags, nsph, q->rec, q->aabb, q->ctl);
+		const nh_QWorld W = nh_query_world(bodies, colliders);
+		NH_LAUNCH(ctx, "q_xform", k_q_xform, nh_grid_for(C, 256, 4096), 256, W, q->rec, q->ctl);
 		NH_LAUNCH(ctx, "q_keys", k_q_keys, nh_grid_for(C, 256, 4096), 256, q->rec, q->ctl, C, q->keys_a, q->idx_a);
 		// 48-bit keys: six passes, the result back in the *_a buffers
 		const int in_b = nh_sort_u64_u32(ctx, q->keys_a, q->keys_b, q->idx_a, q->idx_b, &q->ctl->count, q->hist, 0, 48);
-		const uint64_t* keys = in_b ? q->keys_b : q->keys_a;
-		q->keys = keys;
-		const uint32_t* idx = in_b ? q->idx_b : q->idx_a;
-		NH_LAUNCH(ctx, "q_tree", k_q_tree, nh_grid_for(C > 1u ? C - 1u : 1u, 256, 4096), 256, keys, C, q->nodes, q->parent, q->rchild, q->last, q->right_at, q->arrive, q->ctl);
-		NH_LAUNCH(ctx, "q_refit", k_q_refit, nh_grid_for(C, 256, 4096), 256, idx, q->aabb, C, q->nodes, q->parent, q->rchild, q->last, q->right_at, q->arrive);
+		q->keys = in_b ? q->keys_b : q->keys_a;
+		q->idx = in_b ? q->idx_b : q->idx_a;
+		NH_LAUNCH(ctx, "q_tree", k_q_tree, nh_grid_for(C > 1u ? C - 1u : 1u, 256, 4096), 256, q->keys, C, q->nodes, q->parent, q->rchild, q->last, q->right_at, q->arrive,
+		          q->top, q->ctl);
+		if (C > 1u) NH_LAUNCH(ctx, "q_links", k_q_links, nh_grid_for(C - 1u, 256, 4096), 256, C, q->nodes, q->last, q->right_at);
+		nh_query_boxes(ctx, W, C);
 	}
-	q->built = true; q->n = C; q->nbox = nbox;
+	q->built = true; q->n = C; q->nbox = colliders->boxes.count;
+	return NH_OK;
+}
+
+// The tree of the last build with the boxes of the arrays given now (header: the contract).  Observer like the build; no allocation, no wait.
+extern "C" int nh_query_refit(nh_context* ctx, const nh_BodyData* bodies, const nh_ColliderData* colliders) {
+	if (!ctx || !bodies || !colliders) return NH_ERR_INVALID;
+	nh_QueryState* q = ctx->query;
+	if (!q || !q->built) return NH_ERR_INVALID;
+	uint32_t C = 0;
+	{ const int rc = nh_query_args(bodies, colliders, &C); if (rc) return rc; }
+	// (the leaf order is by combined collider index: other counts are another world)
+	if (colliders->boxes.count != q->nbox || C != q->n) return NH_ERR_INVALID;
+	if (!C) return NH_OK;
+	NH_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+	nh_query_boxes(ctx, nh_query_world(bodies, colliders), C);
+	return NH_OK;
+}
+
+// Diagnostics of the last build's tree (tools/refit_rates.py).  Waits for the stream.
+extern "C" int nh_query_stats(nh_context* ctx, nh_QueryStats* out) {
+	if (!ctx || !out) return NH_ERR_INVALID;
+	nh_QueryState* q = ctx->query;
+	if (!q || !q->built) return NH_ERR_INVALID;
+	NH_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+	nh_QCtl ctl;
+	NH_HIP_CHECK(ctx, hipMemcpyAsync(&ctl, q->ctl, sizeof(ctl), hipMemcpyDeviceToHost, ctx->stream));
+	NH_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+	out->colliders = q->n;
+	out->run_length = NH_Q_RUN;
+	out->runs = (q->n + NH_Q_RUN - 1u) / NH_Q_RUN;
+	out->top_nodes = q->n > NH_Q_RUN && ctl.top_n ? ctl.top_n - 1u : 0u;
+	out->top_depth = q->n > NH_Q_RUN ? ctl.top_depth : 0u;
 	return NH_OK;
 }
 

@@ -43,7 +43,7 @@ EXPORTS = [
     "nh_partition_top_speed", "nh_partition_set_peer_speeds", "nh_partition_refresh_is_quiet", "nh_partition_mark_ghosts", "nh_partition_pack_deltas", "nh_partition_unpack_deltas",
     "nh_partition_pack_momentum", "nh_partition_unpack_momentum", "nh_partition_exchange_iteration", "nh_partition_unpack_ghosts", "nh_partition_pack_step", "nh_partition_unpack_step", "nh_partition_choose_cut", "nh_partition_set_cut",
     "nh_partition_set_transport", "nh_partition_exchange_step", "nh_partition_step", "nh_partition_transport_check", "nh_partition_transport_result", "nh_set_first_ghost_body",
-    "nh_query_build", "nh_raycast", "nh_overlap", "nh_spherecast", "nh_boxcast", "nh_capsulecast", "nh_closest",
+    "nh_query_build", "nh_query_refit", "nh_query_stats", "nh_raycast", "nh_overlap", "nh_spherecast", "nh_boxcast", "nh_capsulecast", "nh_closest",
 ]
 HALO_RECORD_BYTES = 64
 
@@ -107,6 +107,10 @@ class PartitionConfig(C.Structure):
 class PartitionInfo(C.Structure):
     _fields_ = [("n_owned", C.c_uint32), ("n_bodies", C.c_uint32), ("n_boxes", C.c_uint32), ("n_spheres", C.c_uint32), ("ghost_out", C.c_uint32 * 2), ("ghost_in", C.c_uint32 * 2),
                 ("lo", C.c_double), ("hi", C.c_double), ("migrated_out", C.c_uint64), ("migrated_in", C.c_uint64), ("refreshes", C.c_uint64), ("cut_moves", C.c_uint64), ("quiet_refreshes", C.c_uint64)]
+
+
+class QueryStats(C.Structure):
+    _fields_ = [("colliders", C.c_uint32), ("run_length", C.c_uint32), ("runs", C.c_uint32), ("top_nodes", C.c_uint32), ("top_depth", C.c_uint32)]
 
 
 class Ray(C.Structure):
@@ -251,6 +255,10 @@ def lib():
         L.nh_partition_transport_result.argtypes = [C.c_void_p]
         L.nh_set_first_ghost_body.argtypes = [C.c_void_p, C.c_uint32]
         L.nh_query_build.argtypes = [C.c_void_p, C.POINTER(BodyData), C.POINTER(ColliderData)]
+        # (an older build of the library, loaded through NUDGE_HIP_LIBRARY for an A/B, has no refit: World.query_refit then raises AttributeError)
+        if hasattr(L, "nh_query_refit"):
+            L.nh_query_refit.argtypes = [C.c_void_p, C.POINTER(BodyData), C.POINTER(ColliderData)]
+            L.nh_query_stats.argtypes = [C.c_void_p, C.POINTER(QueryStats)]
         L.nh_raycast.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
         L.nh_spherecast.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
         L.nh_boxcast.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
@@ -617,6 +625,17 @@ class World:
     def query_build(self):
         """Build the ray-cast hierarchy over every collider from the current transforms (nh_query_build; enqueued, no synchronisation)."""
         _check(self.L, self.L.nh_query_build(self.ctx, C.byref(self.bodies), C.byref(self.colliders)), "nh_query_build")
+
+    def query_refit(self):
+        """Make the hierarchy of the last query_build() current: the same tree, every record and box from the current transforms (nh_query_refit;
+        enqueued, no synchronisation).  Every query then answers exactly as after a query_build() now; only its speed may differ."""
+        _check(self.L, self.L.nh_query_refit(self.ctx, C.byref(self.bodies), C.byref(self.colliders)), "nh_query_refit")
+
+    def query_stats(self):
+        """Diagnostics of the last query_build()'s tree (nh_query_stats; waits for the stream): colliders, run_length, runs, top_nodes, top_depth."""
+        st = QueryStats()
+        _check(self.L, self.L.nh_query_stats(self.ctx, C.byref(st)), "nh_query_stats")
+        return {k: int(getattr(st, k)) for k, _ in QueryStats._fields_}
 
     def raycast_records(self, rays, any_hit=False, hits=None):
         """nh_raycast on records already laid out as nh_Ray: `rays` a contiguous device tensor of count x 32 bytes (any dtype).  Returns the

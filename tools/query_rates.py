@@ -19,19 +19,22 @@ from nudge_amd import scenes as S           # noqa: E402
 HBM = 8.0e12
 
 # bytes each kernel moves at C colliders (n rays), read + write, counting every record once (caches not modelled)
-#   q_xform: collider transform 32 + body transform 32 + shape 16 + tag 4 in; record 48 + AABB 32 out
+#   q_xform: collider transform 32 + body transform 32 + shape 16 + tag 4 in; record 48 out
 #   q_keys: record position 16 in; key 8 + index 4 out
 #   radix_*: 6 passes of (key 8 + value 4) read twice (histogram, scatter) and written once
 #   q_tree: ~2 log2(C) key reads of 8 B per internal node (binary searches hit cache lines shared by neighbours: counted as 4 keys) + 5 words out
-#   q_refit: index 4 + AABB 32 + leaf node 32 per leaf; per internal node two child boxes read 32 + its box 32 + parent / child words 12 + the counter 4
+#   q_links: last 4 + table 4 in, the link 4 out per internal node
+#   q_boxes_runs: per leaf index 4 + what q_xform reads 84 + parent word 4 + escape 4 in, record 48 + leaf node 32 out; per internal node parent word 4 in, box 24 out
+#   (q_boxes_top: a few thousand nodes, latency bound: no share printed; tools/refit_rates.py)
 #   q_raycast: ray 32 + hit 32 per ray (node and record reads come from the caches: the share printed is of the compulsory traffic only)
 def byte_model(C, n_rays):
     return {
-        "q_xform": C * (32 + 32 + 16 + 4 + 48 + 32),
+        "q_xform": C * (32 + 32 + 16 + 4 + 48),
         "q_keys": C * (16 + 8 + 4),
         "radix_hist": 6 * C * 8, "radix_scan": 6 * 256 * 512 * 4 * 2, "radix_scatter": 6 * C * (8 + 4) * 2,
-        "q_tree": (C - 1) * (4 * 8 + 20),
-        "q_refit": C * (4 + 32 + 32) + (C - 1) * (32 + 32 + 12 + 4) + C * 8,
+        "q_tree": (C - 1) * (4 * 8 + 28),
+        "q_links": (C - 1) * 12,
+        "q_boxes_runs": C * (4 + 84 + 4 + 4 + 48 + 32) + (C - 1) * (4 + 24),
         "q_raycast": n_rays * 64,
     }
 
