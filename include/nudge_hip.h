@@ -407,7 +407,7 @@ int nh_query_stats(nh_context* ctx, nh_QueryStats* out);
      - the hit on one collider is the smallest such t at which the ball touches it (touching counts, as in nh_overlap); the normal is a unit vector from
        the collider towards the ball's centre at t, so the contact point is o + t d - r * normal;
      - START OVERLAP: a ball that overlaps a collider at t = 0 under nh_overlap's own predicates (nh_q_overlap_sphere_sphere / nh_q_overlap_sphere_box) hits
-       it at t = 0 with normal = -d / |d|, the ray's inside rule;
+       it at t = 0 with normal = -d / |d|, the ray's inside rule (how deep and which way out: nh_penetration, below);
      - over all colliders the answer follows nh_raycast: the closest hit, ties by (shape, collider index), `ignore_body`, NH_RAY_ANY_HIT, and a miss written
        exactly as a ray miss (shape = NH_SHAPE_NONE, t = max_t, normal = 0, body = collider = tag = 0xffffffff);
      - r = 0 IS A RAY: it writes the same bytes as nh_raycast with the same first 32 bytes.  A zero direction does what it does for a ray: a ball that
@@ -433,7 +433,7 @@ int nh_spherecast(nh_context* ctx, const nh_SphereCast* casts, uint32_t count, n
        cross product is rounding noise): when it closes last, the normal is the axis that closed last before it.  No contact point is reported;
      - START OVERLAP: a box that overlaps a collider at t = 0 under nh_overlap's own predicates (nh_q_overlap_box_box with the cast box as the query,
        nh_q_overlap_sphere_box for a sphere collider) hits it at t = 0 with normal = -d / |d|, the ray's inside rule; a start contact that only the sweep's
-       rounding finds does the same;
+       rounding finds does the same (how deep and which way out: nh_penetration, below);
      - over all colliders the answer follows nh_raycast: the closest hit, ties by (shape, collider index), `ignore_body`, NH_RAY_ANY_HIT, and a miss written
        exactly as a ray miss (shape = NH_SHAPE_NONE, t = max_t, normal = 0, body = collider = tag = 0xffffffff); a collider of a body that does not exist
        (NaN pose) is never hit;
@@ -461,7 +461,7 @@ int nh_boxcast(nh_context* ctx, const nh_BoxCast* casts, uint32_t count, nh_RayH
        signed against the direction (n.d < 0).  Box candidates are taken in the order end balls (the -a end first), vertices, edges, the first on equal
        t; an edge within ~1e-3 rad of parallel to the segment is left to the end balls and vertices.  No contact point is reported;
      - START OVERLAP: a capsule that overlaps a collider at t = 0 under nh_overlap's capsule predicates hits it at t = 0 with normal = -d / |d|, the ray's
-       inside rule; a start contact that only the sweep's rounding finds does the same;
+       inside rule; a start contact that only the sweep's rounding finds does the same (how deep and which way out: nh_penetration, below);
      - over all colliders the answer follows nh_raycast: the closest hit, ties by (shape, collider index), `ignore_body`, NH_RAY_ANY_HIT (hit or miss agrees
        with the closest-hit answer, a reported hit is real), and a miss written exactly as a ray miss (shape = NH_SHAPE_NONE, t = max_t, normal = 0,
        body = collider = tag = 0xffffffff); a collider of a body that does not exist (NaN pose) is never hit;
@@ -541,6 +541,44 @@ typedef struct nh_OverlapQuery { float center[3]; uint32_t shape; float rotation
 typedef struct nh_OverlapHit { uint32_t body; uint32_t collider; uint32_t shape; uint32_t tag; } nh_OverlapHit;                            /* 16 B */
 int nh_overlap(nh_context* ctx, const nh_OverlapQuery* queries, uint32_t count, uint32_t* offsets /* count + 1 */, nh_OverlapHit* hits, uint32_t capacity,
                uint32_t flags /* 0 */);
+
+/* nh_penetration: the push that frees a query shape -- for every collider of the LAST nh_query_build that each of `count` query shapes overlaps, the
+   least translation of the query shape after which the two only touch (the penetration depth, "compute penetration", MTD): what a character
+   controller needs when a cast starts in contact (START OVERLAP above), a crate pushed against a wall, a spawn test that nudges a shape into free space.
+   THE CALL IS nh_overlap WITH A RICHER RECORD, and that is a contract:
+     - for the same queries on the same build or refit, `offsets` holds exactly the bytes nh_overlap writes, and record j carries in its last 16 bytes
+       (body, collider, shape, tag) exactly the nh_OverlapHit nh_overlap writes at j.  The set is decided by nh_overlap's own predicates (the same
+       kernels run them), and the order is nh_overlap's: by query, then by combined collider index;
+     - everything else carries over unchanged, with 32-byte records: query shapes (a capsule of half height 0 IS A SPHERE query: the same bytes as the
+       sphere query of that radius, `rotation` not read), COUNT ONLY, the CAPACITY prefix rule (the records of query i are written iff
+       offsets[i+1] <= capacity, every byte behind the written prefix is left untouched), the 0xffffffff overflow marker, invalid queries counting 0,
+       `ignore_body`, colliders of a NaN pose, the return codes (`hits` 16-byte aligned), the growth of the sort scratch by capacity, and the OBSERVER
+       property (note 9);
+     - `normal` is a unit vector from the collider towards the query shape, the casts' convention;
+     - `depth` >= +0: the query shape moved by depth * normal touches the collider, and no shorter translation in any direction separates the two, up
+       to rounding and to the 2^-20 the box / box radii carry (measured: within 3.7e-6 of the pair's sizes plus centre distance).  A pair
+       that nh_overlap accepts by rounding alone gets depth = +0, never a negative value or -0.
+   Per pair (exact arithmetic: nudge_amd/csrc/nh_query.h, "penetration"; d and the normals of a point are nh_closest's):
+     - sphere query / sphere: depth = r - (|c - p| - R), normal = (c - p) / |c - p|, +y at coincident centres;
+     - sphere query / box: depth = r - d with d the signed distance of the centre from the box (inside: r + the depth of its nearest face), its normal;
+     - box query / sphere: depth = R - d with d the signed distance of the sphere's centre from the query box, that normal negated;
+     - capsule / sphere: from the sphere's centre to the segment's closest point m: depth = (r + R) - |m|, normal = m / |m|; where the segment passes
+       through the centre, a x e_k normalised for the axis k of the smallest |a_k|;
+     - box query / box: the least overlap over the 15 separating axes of nh_overlap's test, an edge pair's divided by the length of its cross product;
+       ties to the first of: faces of the query box, faces of the collider, edge pairs; an edge pair within ~1e-3 rad of parallel gives neither depth
+       nor normal.  normal = that axis, from the collider to the query box (the + side where the centres project to the same point);
+     - capsule / box: where the segment misses the box, depth = r - their distance (the end points against the box, the -a end first, then the twelve
+       box edges against the segment) and normal = along their closest points; where it meets the box, depth = r + the least overlap over the box's
+       face normals and the three a x e_k, normal = that axis on the centre's side.
+   No contact point and no resolved push-out of a query against all its colliders is reported: callers combine the records.  Not built: the distance
+   of a shape from colliders it does not touch (GJK).
+   Cost: the chain is nh_overlap's in list mode (1.49 ms to list 1 M sphere queries of one box's size on the landed config-2 world) with a
+   gather that reads 108 and writes 32 bytes per record where nh_overlap's reads 52 and writes 16.  NOT MEASURED YET: tools/penetration_rates.py times
+   nh_penetration beside nh_overlap in list mode for 1 M sphere, box and capsule queries and writes profiles/penetration_rates.log; no GPU run of it
+   exists. */
+typedef struct nh_PenetrationHit { float normal[3]; float depth; uint32_t body; uint32_t collider; uint32_t shape; uint32_t tag; } nh_PenetrationHit;  /* 32 B */
+int nh_penetration(nh_context* ctx, const nh_OverlapQuery* queries, uint32_t count, uint32_t* offsets /* count + 1 */, nh_PenetrationHit* hits,
+                   uint32_t capacity, uint32_t flags /* 0 */);
 
 /* ---- multi-GPU: one x-slab of a world per context ------------------------------------------------------------------------------------
    The world is cut into slabs along x, one rank (process, GPU, nh_context) per slab [lo, hi).  A rank's arrays hold

@@ -686,4 +686,254 @@ NH_HD bool nh_q_closer(float d, uint32_t c, float max_d, float bd, uint32_t bc) 
 	return bc == 0xffffffffu || d < bd || (d == bd && c < bc);
 }
 
+// ---- penetration (nh_penetration): the least translation that frees a query shape from one collider it overlaps ----------------------------------------
+// Every function returns the unit normal n, from the collider towards the query shape, and depth >= +0: the query moved by depth * n touches the
+// collider, and no shorter translation in any direction does (a ball adds its radius to the depth of what it inflates; the depth of two
+// polytopes lies on a face normal of either or on the cross product of an edge pair).  They are called for pairs nh_overlap's predicates accepted; a
+// pair that those accept by rounding alone has a distance at or above the radii here, and its depth is clamped to +0 (never negative, never -0).
+struct nh_QPen { nh_f3 n; float depth; };
+
+NH_HD float nh_q_pen_clamp(float depth) { return depth > 0.0f ? depth : 0.0f; }
+
+// Sphere query (c, r) / sphere collider (p, R): nh_q_point_sphere(c, p, R) gives d = |c - p| - R and n = (c - p) / |c - p|; depth = r - d.
+// Coincident centres: n = +y (nh_q_point_sphere's).
+NH_HD nh_QPen nh_q_pen_sphere_sphere(nh_f3 c, float r, nh_f3 p, float R) {
+	const nh_QPoint s = nh_q_point_sphere(c, p, R);
+	nh_QPen o; o.n = s.n; o.depth = nh_q_pen_clamp(r - s.d);
+	return o;
+}
+
+// Sphere query (c, r) / box collider (p, q, h): nh_q_point_box(c, p, q, h) gives the signed distance d of the centre and its normal; depth = r - d, so
+// a centre inside the box gives r + the depth of its nearest face (the lowest axis on equality, a zero coordinate on the + side) and n = that face's.
+NH_HD nh_QPen nh_q_pen_sphere_box(nh_f3 c, float r, nh_f3 p, nh_quat q, nh_f3 h) {
+	const nh_QPoint s = nh_q_point_box(c, p, q, h);
+	nh_QPen o; o.n = s.n; o.depth = nh_q_pen_clamp(r - s.d);
+	return o;
+}
+
+// Box query (ca, qa, ha) / sphere collider (p, R): nh_q_point_box(p, ca, qa, ha), the collider's centre against the QUERY box; depth = R - d and n is
+// that normal negated (it points from the query box to the sphere).
+NH_HD nh_QPen nh_q_pen_box_sphere(nh_f3 ca, nh_quat qa, nh_f3 ha, nh_f3 p, float R) {
+	const nh_QPoint s = nh_q_point_box(p, ca, qa, ha);
+	nh_QPen o; o.n = nh_make3(nh_neg(s.n.x), nh_neg(s.n.y), nh_neg(s.n.z)); o.depth = nh_q_pen_clamp(R - s.d);
+	return o;
+}
+
+// A unit vector perpendicular to a: a x e_k / |a x e_k| for the axis k of a's smallest |a_k| (the lowest on equality); +y where that has no length (a = 0).
+NH_HD nh_f3 nh_q_perpendicular(nh_f3 a) {
+	const float ax = nh_abs(a.x), ay = nh_abs(a.y), az = nh_abs(a.z);
+	nh_f3 v;
+	if (ax <= ay && ax <= az) v = nh_make3(0.0f, a.z, nh_neg(a.y));
+	else if (ay <= az) v = nh_make3(nh_neg(a.z), 0.0f, a.x);
+	else v = nh_make3(a.y, nh_neg(a.x), 0.0f);
+	const float vv = nh_dot(v, v);
+	if (!(vv > 0.0f)) return nh_make3(0.0f, 1.0f, 0.0f);
+	const float len = sqrtf(vv);
+	return nh_make3(v.x / len, v.y / len, v.z / len);
+}
+
+// Capsule (c, a, r), a != 0 / sphere collider (p, R): the segment's closest point c + u a with nh_q_overlap_capsule_sphere_a's own u, m = (c - p) + u a,
+// depth = (r + R) - |m|, n = m / |m|.  |m| = 0 (the segment passes through p): n = nh_q_perpendicular(a), and the depth r + R is that of every
+// direction perpendicular to the axis.
+NH_HD nh_QPen nh_q_pen_capsule_sphere_a(nh_f3 c, nh_f3 a, float r, nh_f3 p, float R) {
+	const float aa = nh_dot(a, a);
+	float u = aa > 0.0f ? nh_dot(p - c, a) / aa : 0.0f;
+	u = u < -1.0f ? -1.0f : u > 1.0f ? 1.0f : u;
+	const nh_f3 m = (c - p) + u * a;          // ((c + u a) - p without the rounding of c + u a to the grid of the world coordinates)
+	const float L = sqrtf(nh_dot(m, m));
+	nh_QPen o;
+	o.n = L > 0.0f ? nh_make3(m.x / L, m.y / L, m.z / L) : nh_q_perpendicular(a);
+	o.depth = nh_q_pen_clamp((r + R) - L);
+	return o;
+}
+
+// One axis of nh_q_pen_box_box: its overlap rho - |s| (>= 0 for a pair nh_q_overlap_box_box accepted: the same expressions) over the axis' length,
+// kept when it is below the least so far -- so the first axis wins on equality.
+NH_HD void nh_q_pen_axis(float s, float rho, float len, int axis, float& best, float& sb, int& at) {
+	const float o = (rho - nh_abs(s)) / len;
+	if (o < best) { best = o; sb = s; at = axis; }
+}
+
+// Box query a (ca, qa, ha) / box collider b (cb, qb, hb): the 15 axes of nh_q_overlap_box_box with its very expressions -- a's frame, R = Ra^T Rb,
+// t = Ra^T (cb - ca), radii with E = |R| + 2^-20 -- so that every overlap rho_k - |s_k| of an accepted pair is >= 0.  A face axis has unit length; the
+// overlap of the edge axis A_i x B_j is divided by its length sqrtf(|A_i x B_j|^2), the squared length read off R (the sum of the squares of column j
+// without row i).  An edge pair whose squared length is below NH_Q_SAT_EPS gives neither depth nor normal, as in nh_q_sweep_box_box: both its overlap
+// and its direction are rounding noise, and (nearly) parallel edges meet along a face axis anyway.  depth = the least normalised overlap, the first
+// axis on equality in the order A_0 .. A_2, B_0 .. B_2, A_0 x B_0, A_0 x B_1 .. A_2 x B_2.  n = that axis in world space, normalised, pointing from
+// b to a: against the sign of the projected centre distance s_k, and the + side of the axis where s_k is exactly 0.  The 2^-20 of E only ever adds
+// to an overlap: at most 6 * 2^-20 of the sizes on a face axis, the same over the length on an edge axis.
+NH_HD nh_QPen nh_q_pen_box_box(nh_f3 ca, nh_quat qa, nh_f3 ha, nh_f3 cb, nh_quat qb, nh_f3 hb) {
+	const nh_m33 A = nh_matrix(qa), B = nh_matrix(qb);
+	const nh_f3 d = cb - ca;
+	const float t0 = nh_dot(A.c0, d), t1 = nh_dot(A.c1, d), t2 = nh_dot(A.c2, d);
+	const float R00 = nh_dot(A.c0, B.c0), R01 = nh_dot(A.c0, B.c1), R02 = nh_dot(A.c0, B.c2);
+	const float R10 = nh_dot(A.c1, B.c0), R11 = nh_dot(A.c1, B.c1), R12 = nh_dot(A.c1, B.c2);
+	const float R20 = nh_dot(A.c2, B.c0), R21 = nh_dot(A.c2, B.c1), R22 = nh_dot(A.c2, B.c2);
+	const float E00 = nh_abs(R00) + NH_Q_SAT_EPS, E01 = nh_abs(R01) + NH_Q_SAT_EPS, E02 = nh_abs(R02) + NH_Q_SAT_EPS;
+	const float E10 = nh_abs(R10) + NH_Q_SAT_EPS, E11 = nh_abs(R11) + NH_Q_SAT_EPS, E12 = nh_abs(R12) + NH_Q_SAT_EPS;
+	const float E20 = nh_abs(R20) + NH_Q_SAT_EPS, E21 = nh_abs(R21) + NH_Q_SAT_EPS, E22 = nh_abs(R22) + NH_Q_SAT_EPS;
+	const float a0 = ha.x, a1 = ha.y, a2 = ha.z, b0 = hb.x, b1 = hb.y, b2 = hb.z;
+	float best = INFINITY, sb = 0.0f;
+	int at = 0;
+	// a's face normals A_0 .. A_2, then b's B_0 .. B_2
+	nh_q_pen_axis(t0, a0 + (b0 * E00 + b1 * E01 + b2 * E02), 1.0f, 0, best, sb, at);
+	nh_q_pen_axis(t1, a1 + (b0 * E10 + b1 * E11 + b2 * E12), 1.0f, 1, best, sb, at);
+	nh_q_pen_axis(t2, a2 + (b0 * E20 + b1 * E21 + b2 * E22), 1.0f, 2, best, sb, at);
+	nh_q_pen_axis(t0 * R00 + t1 * R10 + t2 * R20, (a0 * E00 + a1 * E10 + a2 * E20) + b0, 1.0f, 3, best, sb, at);
+	nh_q_pen_axis(t0 * R01 + t1 * R11 + t2 * R21, (a0 * E01 + a1 * E11 + a2 * E21) + b1, 1.0f, 4, best, sb, at);
+	nh_q_pen_axis(t0 * R02 + t1 * R12 + t2 * R22, (a0 * E02 + a1 * E12 + a2 * E22) + b2, 1.0f, 5, best, sb, at);
+	// edge x edge: A_i x B_j
+	float D;
+	D = R10 * R10 + R20 * R20; if (D >= NH_Q_SAT_EPS) nh_q_pen_axis(t2 * R10 - t1 * R20, (a1 * E20 + a2 * E10) + (b1 * E02 + b2 * E01), sqrtf(D), 6, best, sb, at);
+	D = R11 * R11 + R21 * R21; if (D >= NH_Q_SAT_EPS) nh_q_pen_axis(t2 * R11 - t1 * R21, (a1 * E21 + a2 * E11) + (b0 * E02 + b2 * E00), sqrtf(D), 7, best, sb, at);
+	D = R12 * R12 + R22 * R22; if (D >= NH_Q_SAT_EPS) nh_q_pen_axis(t2 * R12 - t1 * R22, (a1 * E22 + a2 * E12) + (b0 * E01 + b1 * E00), sqrtf(D), 8, best, sb, at);
+	D = R00 * R00 + R20 * R20; if (D >= NH_Q_SAT_EPS) nh_q_pen_axis(t0 * R20 - t2 * R00, (a0 * E20 + a2 * E00) + (b1 * E12 + b2 * E11), sqrtf(D), 9, best, sb, at);
+	D = R01 * R01 + R21 * R21; if (D >= NH_Q_SAT_EPS) nh_q_pen_axis(t0 * R21 - t2 * R01, (a0 * E21 + a2 * E01) + (b0 * E12 + b2 * E10), sqrtf(D), 10, best, sb, at);
+	D = R02 * R02 + R22 * R22; if (D >= NH_Q_SAT_EPS) nh_q_pen_axis(t0 * R22 - t2 * R02, (a0 * E22 + a2 * E02) + (b0 * E11 + b1 * E10), sqrtf(D), 11, best, sb, at);
+	D = R00 * R00 + R10 * R10; if (D >= NH_Q_SAT_EPS) nh_q_pen_axis(t1 * R00 - t0 * R10, (a0 * E10 + a1 * E00) + (b1 * E22 + b2 * E21), sqrtf(D), 12, best, sb, at);
+	D = R01 * R01 + R11 * R11; if (D >= NH_Q_SAT_EPS) nh_q_pen_axis(t1 * R01 - t0 * R11, (a0 * E11 + a1 * E01) + (b0 * E22 + b2 * E20), sqrtf(D), 13, best, sb, at);
+	D = R02 * R02 + R12 * R12; if (D >= NH_Q_SAT_EPS) nh_q_pen_axis(t1 * R02 - t0 * R12, (a0 * E12 + a1 * E02) + (b0 * E21 + b1 * E20), sqrtf(D), 14, best, sb, at);
+	// the axis in world space: A_k, B_k or A_i x B_j (nh_q_sweep_box_box's); s > 0 puts b on its + side, so the normal from b to a is the - side
+	nh_f3 L;
+	if (at < 3) L = at == 0 ? A.c0 : at == 1 ? A.c1 : A.c2;
+	else if (at < 6) L = at == 3 ? B.c0 : at == 4 ? B.c1 : B.c2;
+	else {
+		const int i = (at - 6) / 3, j = (at - 6) % 3;
+		L = nh_cross(i == 0 ? A.c0 : i == 1 ? A.c1 : A.c2, j == 0 ? B.c0 : j == 1 ? B.c1 : B.c2);
+	}
+	const float len = sqrtf(nh_dot(L, L));
+	const nh_f3 n = nh_make3(L.x / len, L.y / len, L.z / len);
+	nh_QPen o;
+	o.n = sb > 0.0f ? nh_make3(nh_neg(n.x), nh_neg(n.y), nh_neg(n.z)) : n;
+	o.depth = nh_q_pen_clamp(best);
+	return o;
+}
+
+// The closest points of the segment o + u a, u in [-1, 1], and the box edge (ci, cj, v), v in [-hk, hk], all on the axes (i, j, k): the closest points of
+// two segments (Ericson, Real-Time Collision Detection 5.1.9) with d1 = a, d2 = e_k, m = o - (ci, cj, 0): u = -(a_i m_i + a_j m_j) / (a_i^2 + a_j^2)
+// clamped (0 where the two are exactly parallel), v = m_k + u a_k clamped, then u = (a_k v - a.m) / a.a clamped again where v was clamped.  Returns
+// the squared distance; w = the segment's point minus the edge's -- where neither parameter was clamped, the component of m along the lines' common
+// normal, which that difference is.
+NH_HD float nh_q_segment_edge(float oi, float oj, float ok, float ai, float aj, float ak, float A, float ci, float cj, float hk, float& wi, float& wj, float& wk) {
+	const float mi = oi - ci, mj = oj - cj;
+	const float D = ai * ai + aj * aj;
+	const float cm = ai * mi + aj * mj;
+	float u = D > 0.0f ? nh_neg(cm) / D : 0.0f;
+	u = u < -1.0f ? -1.0f : u > 1.0f ? 1.0f : u;
+	float v = ok + u * ak;
+	if (nh_abs(v) > hk) {
+		v = v < 0.0f ? nh_neg(hk) : hk;
+		u = (ak * v - (cm + ak * ok)) / A;
+		u = u < -1.0f ? -1.0f : u > 1.0f ? 1.0f : u;
+	} else if (D > 0.0f && nh_abs(u) < 1.0f) {
+		// both points inside their segments: w lies along the common normal (aj, -ai, 0) of the two lines, at the distance f / sqrtf(D) along it, read
+		// off m without the cancellation of m + u a when the two nearly touch
+		const float f = (mi * aj - mj * ai) / D;
+		wi = f * aj; wj = nh_neg(f * ai); wk = 0.0f;
+		return wi * wi + wj * wj;
+	}
+	wi = mi + u * ai; wj = mj + u * aj; wk = (ok + u * ak) - v;
+	return wi * wi + wj * wj + wk * wk;
+}
+
+// Capsule (c, a, r), a != 0 / box collider (p, qb, hb), in the box frame (the inverse of qb, as in nh_q_sweep_capsule_box): the centre and the half
+// axis become ol and al, and the segment is ol + u al, u in [-1, 1].
+//   SHALLOW  the segment misses the box (its parameter range, clipped against the three slabs by nh_q_slab from [-1, 1], is empty): the distance d > 0
+//            between segment and box with its pair of closest points is the least of
+//              1. the two END POINTS against the box -- nh_q_point_box's outside branch: the point minus its clamp to [-h, h] -- the -a end first;
+//              2. the twelve box EDGES against the segment (nh_q_segment_edge), in nh_q_sweep_capsule_box's order: by axis x, y, z, and on each the
+//                 corners (-, -), (+, -), (-, +), (+, +) on the other two axes.
+//            The first candidate wins on equality.  depth = r - d clamped at +0, n = (segment point - box point) / d turned to world.
+//            FACES need no case of their own, as in nh_q_sweep_capsule_box: the distance from a face's plane to a point of the segment is linear along
+//            it, so a segment not parallel to the face is nearest to it with an end point (kind 1); a parallel one is equally near with every point,
+//            and then either an end point lies over the face (kind 1) or the segment passes above one of the face's edges (kind 2).
+//   DEEP     the segment meets the box (or the candidates above found no distance: d = 0 by rounding).  The Minkowski difference of a box and a segment
+//            is a zonotope whose face normals are e_k and al x e_k, so the depth of the segment is the least overlap over those six axes:
+//              e_k       (h_k + |al_k|) - |ol_k|;
+//              al x e_k  the box's radius on it minus the centre's projection, over its length sqrtf(al_i^2 + al_j^2); skipped where its squared
+//                        length is below 2^-20 |al|^2, as the cast skips that edge direction -- the face axes bound the depth there.
+//            The first axis wins on equality (e_x, e_y, e_z, al x e_x, al x e_y, al x e_z).  depth = r + the least overlap, clamped at +0, and n = that
+//            axis on the side of ol (the + side where ol's projection is exactly 0), turned to world.
+NH_HD nh_QPen nh_q_pen_capsule_box_a(nh_f3 c, nh_f3 a, float r, nh_f3 p, nh_quat qb, nh_f3 hb) {
+	const nh_quat qi = { nh_neg(qb.x), nh_neg(qb.y), nh_neg(qb.z), qb.s };
+	const nh_f3 ol = nh_rotate(qi, c - p), al = nh_rotate(qi, a);
+	const float A = nh_dot(al, al);
+	nh_QPen o;
+	float u0 = -1.0f, u1 = 1.0f;
+	int enter = -1;
+	bool all = true;
+	nh_q_slab(ol.x, al.x, hb.x, 0, u0, u1, enter, all);
+	nh_q_slab(ol.y, al.y, hb.y, 1, u0, u1, enter, all);
+	nh_q_slab(ol.z, al.z, hb.z, 2, u0, u1, enter, all);
+	if (!(all && u0 <= u1)) {
+		// SHALLOW 1. the end points
+		nh_f3 w = nh_make3(0.0f, 0.0f, 0.0f);
+		float dd = INFINITY;
+		for (int e = 0; e < 2; ++e) {
+			const nh_f3 x = e == 0 ? ol - al : ol + al;
+			const nh_f3 ql = nh_make3(nh_max(nh_neg(hb.x), nh_min(x.x, hb.x)), nh_max(nh_neg(hb.y), nh_min(x.y, hb.y)), nh_max(nh_neg(hb.z), nh_min(x.z, hb.z)));
+			const nh_f3 v = x - ql;
+			const float vv = nh_dot(v, v);
+			if (vv < dd) { dd = vv; w = v; }
+		}
+		// 2. the edges along axis k, at (-+h_i, -+h_j) on the other two axes i, j
+		for (int k = 0; k < 3; ++k) {
+			const float ai = k == 0 ? al.y : k == 1 ? al.z : al.x, aj = k == 0 ? al.z : k == 1 ? al.x : al.y, ak = k == 0 ? al.x : k == 1 ? al.y : al.z;
+			const float bi = k == 0 ? ol.y : k == 1 ? ol.z : ol.x, bj = k == 0 ? ol.z : k == 1 ? ol.x : ol.y, bk = k == 0 ? ol.x : k == 1 ? ol.y : ol.z;
+			const float hi = k == 0 ? hb.y : k == 1 ? hb.z : hb.x, hj = k == 0 ? hb.z : k == 1 ? hb.x : hb.y, hk = k == 0 ? hb.x : k == 1 ? hb.y : hb.z;
+			for (int e = 0; e < 4; ++e) {
+				const float ci = (e & 1) ? hi : nh_neg(hi), cj = (e & 2) ? hj : nh_neg(hj);
+				float wi, wj, wk;
+				const float vv = nh_q_segment_edge(bi, bj, bk, ai, aj, ak, A, ci, cj, hk, wi, wj, wk);
+				if (vv < dd) { dd = vv; w = nh_make3(k == 0 ? wk : k == 1 ? wj : wi, k == 0 ? wi : k == 1 ? wk : wj, k == 0 ? wj : k == 1 ? wi : wk); }
+			}
+		}
+		if (dd > 0.0f && dd < INFINITY) {
+			const float d = sqrtf(dd);
+			o.n = nh_rotate(qb, nh_make3(w.x / d, w.y / d, w.z / d));
+			o.depth = nh_q_pen_clamp(r - d);
+			return o;
+		}
+	}
+	// DEEP: the box's face normals, then al x e_k
+	float best = (hb.x + nh_abs(al.x)) - nh_abs(ol.x), sb = ol.x;
+	int at = 0;
+	{ const float v = (hb.y + nh_abs(al.y)) - nh_abs(ol.y); if (v < best) { best = v; sb = ol.y; at = 1; } }
+	{ const float v = (hb.z + nh_abs(al.z)) - nh_abs(ol.z); if (v < best) { best = v; sb = ol.z; at = 2; } }
+	float lb = 1.0f;
+	for (int k = 0; k < 3; ++k) {
+		const float ai = k == 0 ? al.y : k == 1 ? al.z : al.x, aj = k == 0 ? al.z : k == 1 ? al.x : al.y;
+		const float bi = k == 0 ? ol.y : k == 1 ? ol.z : ol.x, bj = k == 0 ? ol.z : k == 1 ? ol.x : ol.y;
+		const float hi = k == 0 ? hb.y : k == 1 ? hb.z : hb.x, hj = k == 0 ? hb.z : k == 1 ? hb.x : hb.y;
+		const float D = ai * ai + aj * aj;                                // |al x e_k|^2; al x e_k = (aj, -ai) on (i, j)
+		if (!(D >= NH_Q_SAT_EPS * A)) continue;
+		const float L = sqrtf(D);
+		const float s = bi * aj - bj * ai;
+		const float v = ((hi * nh_abs(aj) + hj * nh_abs(ai)) - nh_abs(s)) / L;
+		if (v < best) { best = v; sb = s; at = 3 + k; lb = L; }
+	}
+	const float sg = sb < 0.0f ? -1.0f : 1.0f;
+	nh_f3 nl;
+	if (at < 3) nl = nh_make3(at == 0 ? sg : 0.0f, at == 1 ? sg : 0.0f, at == 2 ? sg : 0.0f);
+	else {
+		const int k = at - 3;
+		const float ai = k == 0 ? al.y : k == 1 ? al.z : al.x, aj = k == 0 ? al.z : k == 1 ? al.x : al.y;
+		const float ni = sg * aj / lb, nj = nh_neg(sg * ai) / lb;
+		nl = nh_make3(k == 0 ? 0.0f : k == 1 ? nj : ni, k == 0 ? ni : k == 1 ? 0.0f : nj, k == 0 ? nj : k == 1 ? ni : 0.0f);
+	}
+	o.n = nh_rotate(qb, nl);
+	o.depth = nh_q_pen_clamp(r + best);
+	return o;
+}
+
+// nh_penetration's capsule functions: hh = 0 is the sphere query's function itself (and q is not read).
+NH_HD nh_QPen nh_q_pen_capsule_sphere(nh_f3 c, nh_quat q, float r, float hh, nh_f3 p, float R) {
+	if (hh == 0.0f) return nh_q_pen_sphere_sphere(c, r, p, R);
+	return nh_q_pen_capsule_sphere_a(c, nh_q_capsule_axis(q, hh), r, p, R);
+}
+NH_HD nh_QPen nh_q_pen_capsule_box(nh_f3 c, nh_quat q, float r, float hh, nh_f3 p, nh_quat qb, nh_f3 hb) {
+	if (hh == 0.0f) return nh_q_pen_sphere_box(c, r, p, qb, hb);
+	return nh_q_pen_capsule_box_a(c, nh_q_capsule_axis(q, hh), r, p, qb, hb);
+}
+
 #endif

@@ -742,6 +742,43 @@ __global__ __launch_bounds__(256) void k_q_overlap_gather(const uint32_t* __rest
 	}
 }
 
+// nh_penetration's gather: one lane per written record.  The sort carries keys and values, so the query index is the sorted key's upper part
+// (key >> cbits) and the collider the sorted value: the lane re-reads the 48-byte query and the 48-byte collider record, evaluates the pair function
+// (nh_query.h, "penetration") under the query decode of k_q_overlap, and writes {normal, depth} and nh_OverlapHit's four words as two 16-byte stores.
+// Records are sorted by query and, within a query, boxes come before spheres: a wave diverges only by the shape mix of neighbouring queries.  One
+// instantiation serves every shape (the capsule / box function sets the register count at 7 of 8 waves per SIMD, and a lane does one
+// record -- 140 bytes moved, no loop for occupancy to pay for).
+__global__ __launch_bounds__(256) void k_q_penetration_gather(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, const nh_QCtl* __restrict__ ctl,
+                                                              const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox,
+                                                              const nh_OverlapQuery* __restrict__ queries, uint32_t count, uint32_t cbits,
+                                                              nh_PenetrationHit* __restrict__ hits) {
+	const uint32_t m = ctl->ov_written;
+	for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < m; j += gridDim.x * blockDim.x) {
+		const uint32_t cc = vals[j];
+		const uint64_t i = keys[j] >> cbits;
+		if (cc >= n || i >= count) continue;          // (cannot happen: the list pass fills the whole prefix; a guard against reading outside the records)
+		const float4* qp = reinterpret_cast<const float4*>(queries + i);
+		const float4 q0 = qp[0], q1 = qp[1], q2 = qp[2];
+		const nh_f3 c = nh_make3(q0.x, q0.y, q0.z), h = nh_make3(q2.x, q2.y, q2.z);
+		const nh_quat qr = { q1.x, q1.y, q1.z, q1.w };
+		const uint32_t shape = __float_as_uint(q0.w);
+		const bool capsule = shape == NH_SHAPE_CAPSULE && h.y != 0.0f;
+		const bool sphere = !capsule && (shape == NH_SHAPE_SPHERE || shape == NH_SHAPE_CAPSULE);
+		const nh_QRec r = rec[cc];
+		const nh_f3 p = nh_make3(r.a.x, r.a.y, r.a.z), rh = nh_make3(r.c.x, r.c.y, r.c.z);
+		const nh_quat rq = { r.b.x, r.b.y, r.b.z, r.b.w };
+		nh_QPen o;
+		if (capsule) {
+			const nh_f3 a = nh_q_capsule_axis(qr, h.y);
+			o = cc < nbox ? nh_q_pen_capsule_box_a(c, a, h.x, p, rq, rh) : nh_q_pen_capsule_sphere_a(c, a, h.x, p, rh.x);
+		} else if (cc < nbox) o = sphere ? nh_q_pen_sphere_box(c, h.x, p, rq, rh) : nh_q_pen_box_box(c, qr, h, p, rq, rh);
+		else o = sphere ? nh_q_pen_sphere_sphere(c, h.x, p, rh.x) : nh_q_pen_box_sphere(c, qr, h, p, rh.x);
+		uint4* out = reinterpret_cast<uint4*>(hits + j);
+		out[0] = make_uint4(__float_as_uint(o.n.x), __float_as_uint(o.n.y), __float_as_uint(o.n.z), __float_as_uint(o.depth));
+		out[1] = make_uint4(__float_as_uint(r.a.w), cc < nbox ? cc : cc - nbox, cc < nbox ? NH_SHAPE_BOX : NH_SHAPE_SPHERE, __float_as_uint(r.c.w));
+	}
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------------------------------
 void nh_query_free(nh_context* ctx) {
 	nh_QueryState* q = ctx->query;
@@ -951,8 +988,12 @@ static int nh_overlap_reserve(nh_context* ctx, uint32_t capacity) {
 
 static int nh_q_bits(uint32_t x) { return x ? 32 - __builtin_clz(x) : 0; }
 
-extern "C" int nh_overlap(nh_context* ctx, const nh_OverlapQuery* queries, uint32_t count, uint32_t* offsets, nh_OverlapHit* hits, uint32_t capacity,
-                          uint32_t flags) {
+// The chain nh_overlap and nh_penetration share, from the argument checks to the sort: offsets are complete behind it, and for a list call (*list) the
+// written prefix (ctl->ov_written records) lies sorted by (query, combined collider index) in the ov_*_b buffers (*in_b) or the ov_*_a ones.  Each
+// entry point ends in its own gather.  `hits` is only checked here: records of either size are moved as 16-byte words.
+static int nh_overlap_chain(nh_context* ctx, const nh_OverlapQuery* queries, uint32_t count, uint32_t* offsets, const void* hits, uint32_t capacity,
+                            uint32_t flags, bool* list_out, int* in_b, uint32_t* cbits_out) {
+	*list_out = false;
 	if (!ctx || !ctx->query || !ctx->query->built) return NH_ERR_INVALID;
 	if (flags != 0u || count >= NH_Q_MAX_COLLIDERS) return NH_ERR_INVALID;
 	if (count == 0u) return NH_OK;
@@ -964,6 +1005,7 @@ extern "C" int nh_overlap(nh_context* ctx, const nh_OverlapQuery* queries, uint3
 	const bool list = hits != nullptr && capacity != 0u;
 	if (list) { const int rc = nh_overlap_reserve(ctx, capacity); if (rc) return rc; }
 	const uint32_t cbits = (uint32_t)nh_q_bits(q->n);
+	*cbits_out = cbits;
 	const uint32_t grid = nh_grid_for(count, 256, 1u << 20);
 	NH_LAUNCH(ctx, "q_overlap_count", (k_q_overlap<false, false>), grid, 256, queries, count, offsets, q->nodes, q->rec, q->n, q->nbox, q->ctl,
 	          (uint64_t*)nullptr, (uint32_t*)nullptr, cbits);
@@ -978,8 +1020,32 @@ extern "C" int nh_overlap(nh_context* ctx, const nh_OverlapQuery* queries, uint3
 	NH_LAUNCH(ctx, "q_overlap_list_capsule", (k_q_overlap<true, true>), grid, 256, queries, count, offsets, q->nodes, q->rec, q->n, q->nbox, q->ctl,
 	          q->ov_keys_a, q->ov_vals_a, cbits);
 	const int bits = (((int)cbits + nh_q_bits(count)) + 7) / 8 * 8;
-	const int in_b = nh_sort_u64_u32(ctx, q->ov_keys_a, q->ov_keys_b, q->ov_vals_a, q->ov_vals_b, &q->ctl->ov_written, q->hist, 0, bits);
+	*in_b = nh_sort_u64_u32(ctx, q->ov_keys_a, q->ov_keys_b, q->ov_vals_a, q->ov_vals_b, &q->ctl->ov_written, q->hist, 0, bits);
+	*list_out = true;
+	return NH_OK;
+}
+
+extern "C" int nh_overlap(nh_context* ctx, const nh_OverlapQuery* queries, uint32_t count, uint32_t* offsets, nh_OverlapHit* hits, uint32_t capacity,
+                          uint32_t flags) {
+	bool list = false;
+	int in_b = 0;
+	uint32_t cbits = 0u;
+	{ const int rc = nh_overlap_chain(ctx, queries, count, offsets, hits, capacity, flags, &list, &in_b, &cbits); if (rc || !list) return rc; }
+	nh_QueryState* q = ctx->query;
 	NH_LAUNCH(ctx, "q_overlap_gather", k_q_overlap_gather, nh_grid_for(capacity, 256, 4096), 256, in_b ? q->ov_vals_b : q->ov_vals_a, q->ctl, q->rec, q->n, q->nbox,
 	          hits);
+	return NH_OK;
+}
+
+// nh_overlap's chain with a gather that evaluates the pair function of each record (header: the same set, the same order, the same offsets).
+extern "C" int nh_penetration(nh_context* ctx, const nh_OverlapQuery* queries, uint32_t count, uint32_t* offsets, nh_PenetrationHit* hits, uint32_t capacity,
+                              uint32_t flags) {
+	bool list = false;
+	int in_b = 0;
+	uint32_t cbits = 0u;
+	{ const int rc = nh_overlap_chain(ctx, queries, count, offsets, hits, capacity, flags, &list, &in_b, &cbits); if (rc || !list) return rc; }
+	nh_QueryState* q = ctx->query;
+	NH_LAUNCH(ctx, "q_penetration_gather", k_q_penetration_gather, nh_grid_for(capacity, 256, 1u << 20), 256, in_b ? q->ov_keys_b : q->ov_keys_a,
+	          in_b ? q->ov_vals_b : q->ov_vals_a, q->ctl, q->rec, q->n, q->nbox, queries, count, cbits, hits);
 	return NH_OK;
 }

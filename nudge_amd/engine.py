@@ -43,7 +43,7 @@ EXPORTS = [
     "nh_partition_top_speed", "nh_partition_set_peer_speeds", "nh_partition_refresh_is_quiet", "nh_partition_mark_ghosts", "nh_partition_pack_deltas", "nh_partition_unpack_deltas",
     "nh_partition_pack_momentum", "nh_partition_unpack_momentum", "nh_partition_exchange_iteration", "nh_partition_unpack_ghosts", "nh_partition_pack_step", "nh_partition_unpack_step", "nh_partition_choose_cut", "nh_partition_set_cut",
     "nh_partition_set_transport", "nh_partition_exchange_step", "nh_partition_step", "nh_partition_transport_check", "nh_partition_transport_result", "nh_set_first_ghost_body",
-    "nh_query_build", "nh_query_refit", "nh_query_stats", "nh_raycast", "nh_overlap", "nh_spherecast", "nh_boxcast", "nh_capsulecast", "nh_closest",
+    "nh_query_build", "nh_query_refit", "nh_query_stats", "nh_raycast", "nh_overlap", "nh_penetration", "nh_spherecast", "nh_boxcast", "nh_capsulecast", "nh_closest",
 ]
 HALO_RECORD_BYTES = 64
 
@@ -157,6 +157,7 @@ CAPSULE_CAST = np.dtype([("origin", "<f4", 3), ("max_t", "<f4"), ("direction", "
                          ("half_height", "<f4"), ("reserved", "<u4", 2)])
 OVERLAP_QUERY = np.dtype([("center", "<f4", 3), ("shape", "<u4"), ("rotation", "<f4", 4), ("size", "<f4", 3), ("ignore_body", "<u4")])
 OVERLAP_HIT = np.dtype([("body", "<u4"), ("collider", "<u4"), ("shape", "<u4"), ("tag", "<u4")])
+PENETRATION_HIT = np.dtype([("normal", "<f4", 3), ("depth", "<f4"), ("body", "<u4"), ("collider", "<u4"), ("shape", "<u4"), ("tag", "<u4")])
 POINT_QUERY = np.dtype([("point", "<f4", 3), ("max_distance", "<f4"), ("ignore_body", "<u4"), ("reserved", "<u4", 3)])
 POINT_HIT = np.dtype([("distance", "<f4"), ("normal", "<f4", 3), ("point", "<f4", 3), ("body", "<u4"), ("collider", "<u4"), ("shape", "<u4"), ("tag", "<u4"),
                       ("reserved", "<u4")])
@@ -169,6 +170,10 @@ class OverlapQuery(C.Structure):
 
 class OverlapHit(C.Structure):
     _fields_ = [("body", C.c_uint32), ("collider", C.c_uint32), ("shape", C.c_uint32), ("tag", C.c_uint32)]
+
+
+class PenetrationHit(C.Structure):
+    _fields_ = [("normal", C.c_float * 3), ("depth", C.c_float), ("body", C.c_uint32), ("collider", C.c_uint32), ("shape", C.c_uint32), ("tag", C.c_uint32)]
 
 
 class KernelTime(C.Structure):
@@ -265,6 +270,7 @@ def lib():
         L.nh_capsulecast.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
         L.nh_closest.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
         L.nh_overlap.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+        L.nh_penetration.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
         _LIB = L
     return _LIB
 
@@ -844,21 +850,13 @@ class World:
                                          C.c_void_p(hits.data_ptr() if hits is not None else 0), capacity, 0), "nh_overlap")
         return offsets, hits
 
-    def overlap(self, centres, radii=None, half_extents=None, rotations=None, ignore_body=None, capacity=None, synchronize=False, half_heights=None):
-        """The colliders touching each of n spheres (`radii`: a number or n values), n oriented boxes (`half_extents` (n, 3) or (3,), `rotations`
-        (n, 4) or (4,) quaternions (x, y, z, s), default identity) or n capsules (`radii` with `half_heights`, numbers or n values, and `rotations`;
-        the axis is the local y axis), against the last query_build().  Give exactly one of radii / half_extents; mixed batches go through
-        overlap_records.  `ignore_body`: None, a body index, or n of them.
-        capacity=None: a count call, then the total is read -- this WAITS for the device -- and an exactly sized list call.  A capacity: one call, and
-        nothing waits; only the segments that fit are listed (offsets[i + 1] <= capacity).
-        Returns a dict of device tensors: offsets (n + 1, int64; offsets[n] = 0xffffffff when the total is 2^32 - 1 or more), `written` (0-d: the
-        records listed, a prefix of whole segments), and per record slot (capacity of them; the first `written` are meaningful) query, body,
-        collider, shape, tag (int64) and `raw`, the nh_OverlapHit records (capacity x 16 bytes)."""
+    def _overlap_queries(self, what, centres, radii, half_extents, rotations, ignore_body, half_heights):
+        """The nh_OverlapQuery records (n x 12 float32 words on the device) of overlap() / penetration()'s arguments."""
         torch = self.torch
         if (radii is None) == (half_extents is None):
-            raise ValueError("overlap: give exactly one of radii / half_extents")
+            raise ValueError(f"{what}: give exactly one of radii / half_extents")
         if half_heights is not None and radii is None:
-            raise ValueError("overlap: half_heights go with radii (a capsule)")
+            raise ValueError(f"{what}: half_heights go with radii (a capsule)")
         c = torch.as_tensor(centres, dtype=torch.float32, device=self.dev).reshape(-1, 3)
         n = c.shape[0]
         q = torch.zeros((n, 12), dtype=torch.float32, device=self.dev)
@@ -886,26 +884,77 @@ class World:
         ign = 0xFFFFFFFF if ignore_body is None else ignore_body
         ign = torch.as_tensor(ign, dtype=torch.int64, device=self.dev)
         qi[:, 11] = (((ign & 0xFFFFFFFF) ^ 0x80000000) - 0x80000000).to(torch.int32)          # (the uint32 bits, as int32)
+        return q, n
+
+    def _overlap_lists(self, records, q, n, capacity, size):
+        """The count-then-list path (capacity=None) or the one call with a capacity, through `records` (overlap_records / penetration_records) with
+        records of `size` bytes: (hits, offsets as int64, written, the query of every record slot)."""
+        torch = self.torch
         if capacity is None:
-            offsets, _ = self.overlap_records(q)
+            offsets, _ = records(q)
             total = int(offsets[n].item()) & 0xFFFFFFFF if n else 0          # (a synchronisation)
             capacity = 0 if total == NH_OVERLAP_OVERFLOW else total
-            hits = torch.empty((capacity, 16), dtype=torch.uint8, device=self.dev)
+            hits = torch.empty((capacity, size), dtype=torch.uint8, device=self.dev)
             if capacity:
-                self.overlap_records(q, offsets=offsets, hits=hits, capacity=capacity)
+                records(q, offsets=offsets, hits=hits, capacity=capacity)
         else:
-            hits = torch.empty((capacity, 16), dtype=torch.uint8, device=self.dev)
-            offsets, _ = self.overlap_records(q, hits=hits if capacity else None, capacity=capacity)
+            hits = torch.empty((capacity, size), dtype=torch.uint8, device=self.dev)
+            offsets, _ = records(q, hits=hits if capacity else None, capacity=capacity)
         off = offsets.to(torch.int64) & 0xFFFFFFFF
         # the written prefix: the largest offset <= capacity (offsets are monotone unless the total overflowed, and then nothing is written)
         last = torch.searchsorted(off, torch.tensor([capacity], dtype=torch.int64, device=self.dev), right=True) - 1
         written = torch.where(off[n] == NH_OVERLAP_OVERFLOW, torch.zeros_like(last), off[last.clamp(min=0)])[0]
         j = torch.arange(capacity, dtype=torch.int64, device=self.dev)
         query = (torch.searchsorted(off[1:], j, right=True) if n else j).clamp(max=max(n - 1, 0))
+        return hits, off, written, query
+
+    def overlap(self, centres, radii=None, half_extents=None, rotations=None, ignore_body=None, capacity=None, synchronize=False, half_heights=None):
+        """The colliders touching each of n spheres (`radii`: a number or n values), n oriented boxes (`half_extents` (n, 3) or (3,), `rotations`
+        (n, 4) or (4,) quaternions (x, y, z, s), default identity) or n capsules (`radii` with `half_heights`, numbers or n values, and `rotations`;
+        the axis is the local y axis), against the last query_build().  Give exactly one of radii / half_extents; mixed batches go through
+        overlap_records.  `ignore_body`: None, a body index, or n of them.
+        capacity=None: a count call, then the total is read -- this WAITS for the device -- and an exactly sized list call.  A capacity: one call, and
+        nothing waits; only the segments that fit are listed (offsets[i + 1] <= capacity).
+        Returns a dict of device tensors: offsets (n + 1, int64; offsets[n] = 0xffffffff when the total is 2^32 - 1 or more), `written` (0-d: the
+        records listed, a prefix of whole segments), and per record slot (capacity of them; the first `written` are meaningful) query, body,
+        collider, shape, tag (int64) and `raw`, the nh_OverlapHit records (capacity x 16 bytes)."""
+        torch = self.torch
+        q, n = self._overlap_queries("overlap", centres, radii, half_extents, rotations, ignore_body, half_heights)
+        hits, off, written, query = self._overlap_lists(self.overlap_records, q, n, capacity, 16)
         u = hits.view(torch.int32).reshape(-1, 4).to(torch.int64) & 0xFFFFFFFF
         if synchronize:
             torch.cuda.current_stream(self.dev).synchronize()
         return dict(offsets=off, written=written, query=query, body=u[:, 0], collider=u[:, 1], shape=u[:, 2], tag=u[:, 3], raw=hits)
+
+    def penetration_records(self, queries, offsets=None, hits=None, capacity=0):
+        """nh_penetration on records already laid out as nh_OverlapQuery: overlap_records with 32-byte nh_PenetrationHit records -- `hits` must hold
+        `capacity` x 32 bytes.  The offsets, the set, the order and the capacity rule are nh_overlap's.  Enqueued; nothing waits (but a capacity
+        larger than any before grows the scratch)."""
+        torch = self.torch
+        n = queries.numel() * queries.element_size() // 48
+        if offsets is None:
+            offsets = torch.empty(n + 1, dtype=torch.int32, device=self.dev)
+        if hits is not None and hits.numel() * hits.element_size() < 32 * capacity:
+            raise ValueError(f"penetration_records: hits holds {hits.numel() * hits.element_size()} bytes, capacity {capacity} needs {32 * capacity}")
+        _check(self.L, self.L.nh_penetration(self.ctx, C.c_void_p(queries.data_ptr() if n else 0), n, C.c_void_p(offsets.data_ptr()),
+                                             C.c_void_p(hits.data_ptr() if hits is not None else 0), capacity, 0), "nh_penetration")
+        return offsets, hits
+
+    def penetration(self, centres, radii=None, half_extents=None, rotations=None, ignore_body=None, capacity=None, synchronize=False, half_heights=None):
+        """The push that frees a shape: for every collider that each of n spheres, oriented boxes or capsules touches (overlap()'s arguments, set,
+        order and count-then-list path), the least translation of the shape after which the two only touch.
+        Returns overlap()'s dict with, per record slot, `normal` ((capacity, 3) float32: a unit vector from the collider towards the shape) and
+        `depth` (float32, >= 0: the shape moved by depth * normal touches the collider); `raw` holds the nh_PenetrationHit records
+        (capacity x 32 bytes)."""
+        torch = self.torch
+        q, n = self._overlap_queries("penetration", centres, radii, half_extents, rotations, ignore_body, half_heights)
+        hits, off, written, query = self._overlap_lists(self.penetration_records, q, n, capacity, 32)
+        f = hits.view(torch.float32).reshape(-1, 8)
+        u = hits.view(torch.int32).reshape(-1, 8).to(torch.int64) & 0xFFFFFFFF
+        if synchronize:
+            torch.cuda.current_stream(self.dev).synchronize()
+        return dict(offsets=off, written=written, query=query, normal=f[:, 0:3], depth=f[:, 3], body=u[:, 4], collider=u[:, 5], shape=u[:, 6], tag=u[:, 7],
+                    raw=hits)
 
     # ---- measurement ----
     def enable_timing(self, on=True, only=None):
