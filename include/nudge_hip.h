@@ -79,7 +79,7 @@
  *      exported the views: nh_set_option(ctx, "sync_exports_views", 1) restores that contract at its old price; INTEGRATION.md.)  Any entry point outside the sample's
  *      call order between nh_collide and nh_apply_impulses turns a still step into a full one first, so everything it observes is what a full step
  *      produces.  nh_Counts.still_steps / still_replays count them.
- *      The scene queries (nh_query_build, nh_query_refit, nh_raycast, nh_spherecast, nh_boxcast, nh_capsulecast, nh_overlap, nh_closest) are not entry points of the step in this sense: they neither export nor settle nor turn a still step into a
+ *      The scene queries (nh_query_build, nh_query_refit, nh_raycast, nh_spherecast, nh_raycast_all, nh_spherecast_all, nh_boxcast, nh_capsulecast, nh_overlap, nh_penetration, nh_closest) are not entry points of the step in this sense: they neither export nor settle nor turn a still step into a
  *      full one, and they do not count -- see "scene queries" below.
  *
  * Threading: one context = one HIP stream = one world at a time; no global mutable state.
@@ -349,7 +349,7 @@ typedef struct nh_StreamInfo { uint32_t slot; uint32_t valid; uint64_t step; uin
 int nh_stream_state(nh_context* ctx, const nh_BodyData* bodies, uint32_t count, void* host_ring, uint32_t slots, uint32_t every);
 int nh_stream_latest(nh_context* ctx, nh_StreamInfo* out);
 
-/* ---- scene queries: ray casts, sphere, box and capsule casts, overlaps and closest points against the device-resident world ---------------------------------------------
+/* ---- scene queries: ray casts, sphere, box and capsule casts, all-hits casts, overlaps and closest points against the device-resident world ---------------------------------------------
    nh_query_build snapshots the world transforms and AABBs of ALL box and sphere colliders -- those of sleeping bodies and of body 0 (the static world) included -- and
    builds a bounding-volume hierarchy over them (a linear BVH: Morton keys, a radix tree, bottom-up boxes) into buffers the library owns: they grow with the collider
    count (~190 B per collider) and are freed by nh_destroy.  nh_raycast answers `count` rays (nh_overlap, below, `count` shapes) against the LAST build: the hierarchy does not follow the bodies by itself, so
@@ -420,6 +420,48 @@ int nh_query_stats(nh_context* ctx, nh_QueryStats* out);
    into a full one, no change to nh_Counts. */
 typedef struct nh_SphereCast { float origin[3]; float max_t; float direction[3]; uint32_t ignore_body; float radius; uint32_t reserved[3]; } nh_SphereCast;  /* 48 B */
 int nh_spherecast(nh_context* ctx, const nh_SphereCast* casts, uint32_t count, nh_RayHit* hits, uint32_t flags /* 0 or NH_RAY_ANY_HIT */);
+
+/* nh_raycast_all / nh_spherecast_all: EVERY collider of the LAST nh_query_build that a ray (a swept ball) passes through, ordered along the cast -- a bullet or
+   a laser that penetrates, line of sight through things the caller skips by tag, picking front to back, sensors that report all returns, a thick projectile.
+   Input records are nh_raycast's / nh_spherecast's, output records nh_RayHit, in variable-length segments under nh_overlap's offsets and capacity contract.
+     - THE SET of query i: every box and sphere collider of the last build (those of sleeping bodies and of body 0 included), less the colliders of
+       `ignore_body`, on which the closest-hit call has a hit with 0 <= t <= max_t: for rays nh_q_ray_box / nh_q_ray_sphere; for sphere casts nh_q_sweep_box /
+       nh_q_sweep_sphere, for r > 0 under nh_spherecast's reach rule applied to the collider's OWN box in the hierarchy (nh_q_leaf_box, nh_q_cast_node with
+       w = r + nh_q_cast_pad): that box must be entered, and t = max(t of the predicate, the entry).  It is the test the closest-hit walk makes at a leaf
+       with no best hit so far (nh_q_all_hit, nudge_amd/csrc/nh_query.h), so a brute force over all colliders gives the same set.  ONE record per collider:
+       its entry.  An origin inside a collider, or a ball that starts in overlap, hits it at t = 0 with normal = -d / |d|, as in the closest-hit calls.
+       Exits are not reported.  A collider of a NaN pose is never hit;
+     - THE RECORD of a hit is byte for byte what the closest-hit call would write if that collider were the only one: t, normal, body, collider (the
+       index within its own array), shape, tag;
+     - THE ORDER within query i: ascending t compared as floats (-0 equals +0), ties by COMBINED collider index ascending (boxes 0 .. nbox-1, then the
+       spheres -- the ray tie-break's order), so the output does not depend on the tree;
+     - FIRST RECORD = CLOSEST HIT, a contract: where offsets[i+1] > offsets[i], hits[offsets[i]] holds exactly the 32 bytes nh_raycast (nh_spherecast)
+       with flags = 0 writes for the same record on the same build or refit; where the segment is empty, that call writes a miss;
+     - r = 0 IS A RAY: nh_spherecast_all with radius 0 writes the bytes nh_raycast_all writes for the same first 32 bytes;
+     - offsets[0 .. count] (count + 1 words) by the exclusive scan of the per-query counts: offsets[i] = the records before query i, offsets[count] = the
+       total; the records of query i are hits[offsets[i] .. offsets[i+1]);
+     - COUNT ONLY: hits == NULL and capacity == 0 write offsets alone (count, read offsets[count], allocate, list);
+     - CAPACITY: the records of query i are written if and only if offsets[i+1] <= capacity -- the written part is a prefix of whole segments, every byte of
+       `hits` behind it is left untouched, and `offsets` is always complete;
+     - a true total of 2^32 - 1 or more writes offsets[count] = 0xffffffff and no record at all (the other offsets are then unspecified), as in nh_overlap;
+     - an INVALID record counts 0: a non-finite origin or direction, for sphere casts a non-finite or negative radius.  A NaN max_t lists nothing
+       (t <= NaN is false); max_t = +inf lists everything ahead on the line.  A zero direction does what it does for the closest hit: the colliders that
+       contain the origin (overlap the ball) at t = 0, with the NaN normal, and nothing else.
+   Returns NH_ERR_INVALID before any nh_query_build, for flags != 0 (NH_RAY_ANY_HIT included: it has no meaning here), for `rays` / `casts` null or not
+   16-byte aligned, `offsets` null or not 4-byte aligned, `hits` null with capacity > 0 or not 16-byte aligned, and for count >= 2^30; count = 0 is a no-op
+   that returns NH_OK.
+   An OBSERVER like nh_raycast (note 9): no view export, no settling of deferred gravity, no still step turned into a full one, no change to nh_Counts.
+   Everything is enqueued on the context's stream, except that a larger capacity than any before grows the library's sort scratch after a stream
+   synchronise, as in nh_overlap: the scratch is nh_overlap's own, and the ordering by t needs no further array -- it still takes ~24 B per record of capacity.
+   Cost: the walk cannot prune by a best hit, only by max_t, it runs twice (count, list), and for rays it grows every node box by 2^-9 of its distance from
+   the origin, so that no collider the ray predicates accept by rounding is pruned; the records are then ordered by one radix sort where
+   bits(count) + 32 + bits(colliders) <= 64 and by two otherwise.  NOT MEASURED YET: tools/castall_rates.py times both calls (count only, count + list) on the landed config-2 world beside nh_raycast / nh_spherecast on the same records
+   and nh_overlap in list mode, and writes profiles/castall_rates.log; no GPU run of it has been made, so neither ratio (count walk / closest-hit cast, list chain / nh_overlap's per record) is known.
+   Not built: all-hits box and capsule casts, exits, a per-query hit limit ("the first k"). */
+int nh_raycast_all(nh_context* ctx, const nh_Ray* rays, uint32_t count, uint32_t* offsets /* count + 1 */, nh_RayHit* hits, uint32_t capacity,
+                   uint32_t flags /* 0 */);
+int nh_spherecast_all(nh_context* ctx, const nh_SphereCast* casts, uint32_t count, uint32_t* offsets /* count + 1 */, nh_RayHit* hits, uint32_t capacity,
+                      uint32_t flags /* 0 */);
 
 /* nh_boxcast: where a swept oriented box first touches the world of the LAST nh_query_build -- "can this crate be pushed 3 m along x", where a door, lift or
    character hull stops.  nh_BoxCast's first 32 bytes are nh_Ray's fields at the same offsets; `size` holds half extents (as in nh_BoxCollider); `rotation`

@@ -936,4 +936,46 @@ NH_HD nh_QPen nh_q_pen_capsule_box(nh_f3 c, nh_quat q, float r, float hh, nh_f3 
 	return nh_q_pen_capsule_box_a(c, nh_q_capsule_axis(q, hh), r, p, qb, hb);
 }
 
+// ---- all-hits casts (nh_raycast_all / nh_spherecast_all): the hit of ONE collider, as the closest-hit walk decides it at a leaf with no best so far --
+// The ray's own predicates (SWEEP = false) or the swept ball's with the reach rule for r > 0 (SWEEP = true; t0 = the entry into the collider's leaf box
+// under nh_q_cast_node, w = r + nh_q_cast_pad), then 0 <= t <= max_t (nh_q_better against nothing).  The count walk, the list walk and the gather call
+// this one function on the same inputs, so all three get the same bits; the host's brute force calls it too.
+template <bool SWEEP>
+NH_HD nh_QHit nh_q_all_hit(nh_f3 o, nh_f3 d, float r, float max_t, float t0, nh_f3 p, nh_quat q, nh_f3 h, bool box) {
+	nh_QHit s;
+	if (SWEEP) {
+		s = box ? nh_q_sweep_box(o, d, r, p, q, h) : nh_q_sweep_sphere(o, d, r, p, h.x);
+		if (r > 0.0f && t0 > s.t) s.t = t0;
+	} else {
+		s = box ? nh_q_ray_box(o, d, p, q, h) : nh_q_ray_sphere(o, d, p, h.x);
+	}
+	s.hit = s.hit && nh_q_better(s.t, 0u, max_t, max_t, 0xffffffffu);
+	return s;
+}
+
+// The entry of a cast into a collider's own leaf box (nh_q_leaf_box: the box the build stores), for the caller that has no walk to take it from: the
+// gather and the host.  false: the leaf is not entered, and under the reach rule (r > 0) the collider is not hit.
+NH_HD bool nh_q_leaf_entry(nh_f3 o, nh_f3 inv, float w, nh_f3 p, nh_quat q, nh_f3 h, bool box, float& t0) {
+	nh_f3 lo, hi;
+	nh_q_leaf_box(p, q, h, box, lo, hi);
+	return nh_q_cast_node(lo, hi, o, inv, w, t0);
+}
+
+// The all-hits walk's node pad for a RAY (r = 0).  The closest-hit ray walk prunes with boxes padded by 2^-18 of the coordinates, which does not bound the
+// rounding of the ray predicates: nh_q_ray_sphere accepts where the computed b*b - a*(m.m - R*R) >= 0, and with |m| = |o - c| the roundings of that
+// expression sum to under 32 * 2^-24 * |m|^2 |d|^2 (three rounded products and sums per dot product, the squares, the product with a and the
+// differences), so an accepted ray may pass the centre at up to sqrt(R^2 + 2^-19 |m|^2) <= R + 2^-9.5 |m|, and the reported point o + t d lies within that
+// distance of the centre as well (its offset along the ray from the closest approach is sqrt(disc) / |d|).  nh_q_ray_box rounds linearly in |m| (a few
+// 2^-24 of |m| + |h| in the box frame), far below that.  A closest-hit call loses such a far grazing hit only where it is the closest; the all-hits set
+// is every collider the predicate accepts, so its walk grows each node box by 2^-9 of L, an upper bound (the 1-norm) of the distance from the origin to
+// the farthest point of the box: L >= |m| for every collider whose leaf box lies inside, L and the grown box are monotone in the box, so no ancestor
+// prunes what a leaf would accept.  (Sphere casts of r > 0 need none of this: the reach rule makes their set a function of the leaf test.)
+NH_HD float nh_q_all_pad(nh_f3 lo, nh_f3 hi, nh_f3 o) {
+	const float fx = fmaxf(fabsf(lo.x - o.x), fabsf(hi.x - o.x)), fy = fmaxf(fabsf(lo.y - o.y), fabsf(hi.y - o.y)), fz = fmaxf(fabsf(lo.z - o.z), fabsf(hi.z - o.z));
+	return ((fx + fy) + fz) * 0.001953125f;
+}
+
+// The sort key of a hit's t: the bits of t + 0.0f.  t >= 0, so -0 becomes +0 and the bits order as the floats do.
+NH_HD uint32_t nh_q_tbits(float t) { return nh_asuint(t + 0.0f); }
+
 #endif

@@ -20,6 +20,7 @@
 // Node ids: internal nodes 0 .. n-2 (root 0), leaf j (j-th collider in key order) n-1+j; with one collider the root is that leaf.
 // Traversal is stackless: a node that is missed or a leaf that is done continues at its ESCAPE link (the next node in pre-order after its subtree),
 // a hit internal node at its left child.  A private stack array would go to scratch memory.
+#include <utility>
 #include "nh_internal.h"
 #include "nh_query.h"
 
@@ -779,6 +780,121 @@ __global__ __launch_bounds__(256) void k_q_penetration_gather(const uint64_t* __
 	}
 }
 
+// ---- all-hits casts ---------------------------------------------------------------------------------------------------------------------------
+// nh_raycast_all / nh_spherecast_all: every collider a cast passes through, ordered along the cast.  nh_overlap's chain (kernel boundaries are the
+// only hand-offs, no atomic decides where a record goes) with the casts' walk in place of the volume walk and an ordering by t behind it:
+//   k_q_castall<S, false>  one lane per cast: k_q_raycast's (S = false) / k_q_spherecast's (S = true) stackless walk with the pruning bound FIXED at
+//                       max_t -- there is no best hit to tighten it -- and nh_q_all_hit at every entered leaf; offsets[i] = the number of hits.
+//                       For a ray (and r = 0) every node box is grown by nh_q_all_pad as well: the set is every collider the PREDICATE accepts, and the
+//                       closest-hit walk's pad does not cover the predicates' rounding at a distance (nh_query.h)
+//   nh_scan_u32, k_q_overlap_fix, k_q_overlap_fin   nh_overlap's own (nh_overlap_offsets)
+//   k_q_castall<S, true>   the same walk (the same template: the same set) for the casts whose segment fits; hit k of cast i goes to offsets[i] + k
+//   the ordering by (cast, t, combined collider index), one of
+//     ONE SORT   where bits(count) + 32 + cbits <= 64: key (i << (32 + cbits)) | (tbits << cbits) | c, value c, one nh_sort_u64_u32
+//     TWO SORTS  otherwise (a million rays on a million colliders need 72 bits): key (i << cbits) | c, value tbits; nh_sort_u64_u32 over the cbits of c
+//                (LSD: the least significant part first); k_q_castall_rekey to key (i << 32) | tbits, value c; a second, stable nh_sort_u64_u32 over
+//                32 + bits(count) bits, whose stability carries the index order into the ties of t
+//   k_q_castall_gather<S>  one lane per written record: the cast index from the key, the collider from the value; it re-reads the cast and the 48-byte
+//                       collider record and evaluates nh_q_all_hit again -- the same function on the same inputs, the leaf entry of the reach rule
+//                       rebuilt by nh_q_leaf_entry as the build stores it -- and writes nh_RayHit as two 16-byte stores.  No normal goes through a sort.
+struct nh_QCast { nh_f3 o, d, inv; float max_t, r, w; uint32_t ignore; bool ok; };
+
+template <bool SWEEP>
+__device__ __forceinline__ nh_QCast nh_q_cast_read(const float4* __restrict__ casts, uint32_t i) {
+	const float4* cp = casts + (size_t)i * (SWEEP ? 3u : 2u);
+	const float4 c0 = cp[0], c1 = cp[1];
+	nh_QCast k;
+	k.o = nh_make3(c0.x, c0.y, c0.z); k.d = nh_make3(c1.x, c1.y, c1.z);
+	k.max_t = c0.w; k.ignore = __float_as_uint(c1.w);
+	k.r = SWEEP ? cp[2].x : 0.0f;
+	k.ok = nh_q_finite(k.o.x) && nh_q_finite(k.o.y) && nh_q_finite(k.o.z) && nh_q_finite(k.d.x) && nh_q_finite(k.d.y) && nh_q_finite(k.d.z);
+	if (SWEEP) k.ok = k.ok && nh_q_finite(k.r) && !(k.r < 0.0f);
+	k.inv = nh_make3(1.0f / k.d.x, 1.0f / k.d.y, 1.0f / k.d.z);
+	// (k_q_raycast's pad and k_q_spherecast's: the same number for r = 0)
+	k.w = SWEEP ? k.r + nh_q_cast_pad(k.o, k.r) : fmaxf(fmaxf(fabsf(k.o.x), fabsf(k.o.y)), fabsf(k.o.z)) * 3.814697265625e-06f;
+	return k;
+}
+
+template <bool SWEEP, bool LIST>
+__global__ __launch_bounds__(256) void k_q_castall(const float4* __restrict__ casts, uint32_t count, uint32_t* offsets,
+                                                   const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox,
+                                                   nh_QCtl* ctl, uint64_t* __restrict__ keys, uint32_t* __restrict__ vals, uint32_t cbits, uint32_t one_sort) {
+	if (!LIST && blockIdx.x == 0 && threadIdx.x == 0) { offsets[count] = 0u; ctl->ov_wrap = 0u; ctl->ov_written = 0u; }   // (k_q_overlap_fix sets both)
+	const uint32_t written = LIST ? ctl->ov_written : 0u;
+	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
+		uint32_t base = 0u, end = 0u;
+		if (LIST) {
+			base = offsets[i]; end = offsets[i + 1u];
+			if (!(base < end && end <= written)) continue;          // empty, or not in the written prefix
+		}
+		const nh_QCast k = nh_q_cast_read<SWEEP>(casts, i);
+		const bool ray = !SWEEP || !(k.r > 0.0f);
+		uint32_t hits = 0u;
+		uint32_t node = k.ok && n ? 0u : NH_Q_NONE;
+		while (node != NH_Q_NONE) {
+			const float4 na = nodes[node].a, nb = nodes[node].b;
+			float t0;
+			const nh_f3 lo = nh_make3(na.x, na.y, na.z), hi = nh_make3(nb.x, nb.y, nb.z);
+			// (a ray's node box also takes the predicates' own rounding, nh_q_all_pad; a ball's reach rule reads the entry of the box as the build stores it)
+			const float w = ray ? k.w + nh_q_all_pad(lo, hi, k.o) : k.w;
+			const bool enter = nh_q_cast_node(lo, hi, k.o, k.inv, w, t0) && t0 <= k.max_t;
+			const uint32_t left = __float_as_uint(na.w);
+			const uint32_t rope = __float_as_uint(nb.w);
+			if (!enter) { node = rope; continue; }
+			if (!(left & NH_Q_LEAF)) { node = left; continue; }
+			node = rope;
+			const uint32_t c = left & ~NH_Q_LEAF;
+			const nh_QRec q = rec[c];
+			if (__float_as_uint(q.a.w) == k.ignore) continue;
+			const nh_QHit h = nh_q_all_hit<SWEEP>(k.o, k.d, k.r, k.max_t, t0, nh_make3(q.a.x, q.a.y, q.a.z), nh_quat{ q.b.x, q.b.y, q.b.z, q.b.w },
+			                                      nh_make3(q.c.x, q.c.y, q.c.z), c < nbox);
+			if (!h.hit) continue;
+			if (LIST) {
+				// (the count pass found exactly end - base: the segment is full once they are written, nothing else can follow)
+				const uint32_t tb = nh_q_tbits(h.t);
+				keys[base + hits] = one_sort ? ((uint64_t)i << (32u + cbits)) | ((uint64_t)tb << cbits) | c : ((uint64_t)i << cbits) | c;
+				vals[base + hits] = one_sort ? c : tb;
+				if (base + hits + 1u == end) break;
+			}
+			++hits;
+		}
+		if (!LIST) offsets[i] = hits;
+	}
+}
+
+// between the two sorts: (i << cbits | c, tbits) becomes (i << 32 | tbits, c), in place
+__global__ __launch_bounds__(256) void k_q_castall_rekey(uint64_t* __restrict__ keys, uint32_t* __restrict__ vals, const nh_QCtl* __restrict__ ctl, uint32_t cbits) {
+	const uint32_t m = ctl->ov_written;
+	for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < m; j += gridDim.x * blockDim.x) {
+		const uint64_t key = keys[j];
+		const uint32_t tb = vals[j];
+		keys[j] = ((key >> cbits) << 32) | tb;
+		vals[j] = (uint32_t)(key & ((1ull << cbits) - 1ull));
+	}
+}
+
+template <bool SWEEP>
+__global__ __launch_bounds__(256) void k_q_castall_gather(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, const nh_QCtl* __restrict__ ctl,
+                                                          const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox,
+                                                          const float4* __restrict__ casts, uint32_t count, uint32_t ishift, nh_RayHit* __restrict__ hits) {
+	const uint32_t m = ctl->ov_written;
+	for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < m; j += gridDim.x * blockDim.x) {
+		const uint32_t c = vals[j];
+		const uint64_t i = keys[j] >> ishift;
+		if (c >= n || i >= count) continue;          // (cannot happen: the list pass fills the whole prefix; a guard against reading outside the records)
+		const nh_QCast k = nh_q_cast_read<SWEEP>(casts, (uint32_t)i);
+		const nh_QRec q = rec[c];
+		const nh_f3 p = nh_make3(q.a.x, q.a.y, q.a.z), qh = nh_make3(q.c.x, q.c.y, q.c.z);
+		const nh_quat qq = { q.b.x, q.b.y, q.b.z, q.b.w };
+		float t0 = 0.0f;
+		if (SWEEP && k.r > 0.0f) nh_q_leaf_entry(k.o, k.inv, k.w, p, qq, qh, c < nbox, t0);      // (entered: the walk listed it)
+		const nh_QHit h = nh_q_all_hit<SWEEP>(k.o, k.d, k.r, k.max_t, t0, p, qq, qh, c < nbox);
+		float4* hp = reinterpret_cast<float4*>(hits + j);
+		hp[0] = make_float4(h.t, h.n.x, h.n.y, h.n.z);
+		hp[1] = make_float4(q.a.w, __uint_as_float(c < nbox ? c : c - nbox), __uint_as_float(c < nbox ? NH_SHAPE_BOX : NH_SHAPE_SPHERE), q.c.w);
+	}
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------------------------------
 void nh_query_free(nh_context* ctx) {
 	nh_QueryState* q = ctx->query;
@@ -988,6 +1104,15 @@ static int nh_overlap_reserve(nh_context* ctx, uint32_t capacity) {
 
 static int nh_q_bits(uint32_t x) { return x ? 32 - __builtin_clz(x) : 0; }
 
+// From the per-query counts in offsets[0 .. count) (offsets[count] = 0) to the complete offsets, the written prefix and the overflow marker: the three
+// launches nh_overlap's chain and the all-hits casts share.
+static void nh_overlap_offsets(nh_context* ctx, uint32_t* offsets, uint32_t count, uint32_t capacity) {
+	nh_QueryState* q = ctx->query;
+	nh_scan_u32(ctx, offsets, offsets, &q->ctl->zero, count + 1u, q->hist, nullptr);
+	NH_LAUNCH(ctx, "q_overlap_fix", k_q_overlap_fix, nh_grid_for((uint64_t)count + 1u, 256, 4096), 256, offsets, count, capacity, q->ctl);
+	NH_LAUNCH(ctx, "q_overlap_fin", k_q_overlap_fin, 1, 1, offsets, count, q->ctl);
+}
+
 // The chain nh_overlap and nh_penetration share, from the argument checks to the sort: offsets are complete behind it, and for a list call (*list) the
 // written prefix (ctl->ov_written records) lies sorted by (query, combined collider index) in the ov_*_b buffers (*in_b) or the ov_*_a ones.  Each
 // entry point ends in its own gather.  `hits` is only checked here: records of either size are moved as 16-byte words.
@@ -1011,9 +1136,7 @@ static int nh_overlap_chain(nh_context* ctx, const nh_OverlapQuery* queries, uin
 	          (uint64_t*)nullptr, (uint32_t*)nullptr, cbits);
 	NH_LAUNCH(ctx, "q_overlap_count_capsule", (k_q_overlap<false, true>), grid, 256, queries, count, offsets, q->nodes, q->rec, q->n, q->nbox, q->ctl,
 	          (uint64_t*)nullptr, (uint32_t*)nullptr, cbits);
-	nh_scan_u32(ctx, offsets, offsets, &q->ctl->zero, count + 1u, q->hist, nullptr);
-	NH_LAUNCH(ctx, "q_overlap_fix", k_q_overlap_fix, nh_grid_for((uint64_t)count + 1u, 256, 4096), 256, offsets, count, capacity, q->ctl);
-	NH_LAUNCH(ctx, "q_overlap_fin", k_q_overlap_fin, 1, 1, offsets, count, q->ctl);
+	nh_overlap_offsets(ctx, offsets, count, capacity);
 	if (!list) return NH_OK;
 	NH_LAUNCH(ctx, "q_overlap_list", (k_q_overlap<true, false>), grid, 256, queries, count, offsets, q->nodes, q->rec, q->n, q->nbox, q->ctl,
 	          q->ov_keys_a, q->ov_vals_a, cbits);
@@ -1048,4 +1171,54 @@ extern "C" int nh_penetration(nh_context* ctx, const nh_OverlapQuery* queries, u
 	NH_LAUNCH(ctx, "q_penetration_gather", k_q_penetration_gather, nh_grid_for(capacity, 256, 1u << 20), 256, in_b ? q->ov_keys_b : q->ov_keys_a,
 	          in_b ? q->ov_vals_b : q->ov_vals_a, q->ctl, q->rec, q->n, q->nbox, queries, count, cbits, hits);
 	return NH_OK;
+}
+
+// The all-hits chain (the comment above k_q_castall): nh_overlap's argument rules, offsets and capacity contract, the casts' walk, the ordering by t.
+template <bool SWEEP>
+static int nh_castall(nh_context* ctx, const void* casts, uint32_t count, uint32_t* offsets, nh_RayHit* hits, uint32_t capacity, uint32_t flags) {
+	if (!ctx || !ctx->query || !ctx->query->built) return NH_ERR_INVALID;
+	if (flags != 0u || count >= NH_Q_MAX_COLLIDERS) return NH_ERR_INVALID;
+	if (count == 0u) return NH_OK;
+	if (!casts || ((uintptr_t)casts & 15u)) return NH_ERR_INVALID;            // (records are read as 16-byte words)
+	if (!offsets || ((uintptr_t)offsets & 3u)) return NH_ERR_INVALID;
+	if ((!hits && capacity) || ((uintptr_t)hits & 15u)) return NH_ERR_INVALID;
+	NH_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+	nh_QueryState* q = ctx->query;
+	const bool list = hits != nullptr && capacity != 0u;
+	if (list) { const int rc = nh_overlap_reserve(ctx, capacity); if (rc) return rc; }
+	const float4* recs = static_cast<const float4*>(casts);
+	const uint32_t cbits = (uint32_t)nh_q_bits(q->n);
+	const int ibits = nh_q_bits(count);
+	const bool one_sort = ibits + 32 + (int)cbits <= 64;
+	const uint32_t grid = nh_grid_for(count, 256, 1u << 20);
+	NH_LAUNCH(ctx, SWEEP ? "q_spherecast_all_count" : "q_raycast_all_count", (k_q_castall<SWEEP, false>), grid, 256, recs, count, offsets, q->nodes, q->rec, q->n,
+	          q->nbox, q->ctl, (uint64_t*)nullptr, (uint32_t*)nullptr, cbits, one_sort ? 1u : 0u);
+	nh_overlap_offsets(ctx, offsets, count, capacity);
+	if (!list) return NH_OK;
+	NH_LAUNCH(ctx, SWEEP ? "q_spherecast_all_list" : "q_raycast_all_list", (k_q_castall<SWEEP, true>), grid, 256, recs, count, offsets, q->nodes, q->rec, q->n,
+	          q->nbox, q->ctl, q->ov_keys_a, q->ov_vals_a, cbits, one_sort ? 1u : 0u);
+	uint64_t* keys = q->ov_keys_a; uint64_t* keys_other = q->ov_keys_b;
+	uint32_t* vals = q->ov_vals_a; uint32_t* vals_other = q->ov_vals_b;
+	const uint32_t* m = &q->ctl->ov_written;
+	if (nh_sort_u64_u32(ctx, keys, keys_other, vals, vals_other, m, q->hist, 0, one_sort ? (ibits + 32 + (int)cbits + 7) / 8 * 8 : ((int)cbits + 7) / 8 * 8)) {
+		std::swap(keys, keys_other); std::swap(vals, vals_other);
+	}
+	if (!one_sort) {
+		NH_LAUNCH(ctx, "q_castall_rekey", k_q_castall_rekey, nh_grid_for(capacity, 256, 4096), 256, keys, vals, q->ctl, cbits);
+		if (nh_sort_u64_u32(ctx, keys, keys_other, vals, vals_other, m, q->hist, 0, (ibits + 32 + 7) / 8 * 8)) {
+			std::swap(keys, keys_other); std::swap(vals, vals_other);
+		}
+	}
+	NH_LAUNCH(ctx, SWEEP ? "q_spherecast_all_gather" : "q_raycast_all_gather", (k_q_castall_gather<SWEEP>), nh_grid_for(capacity, 256, 1u << 20), 256, keys, vals,
+	          q->ctl, q->rec, q->n, q->nbox, recs, count, one_sort ? 32u + cbits : 32u, hits);
+	return NH_OK;
+}
+
+extern "C" int nh_raycast_all(nh_context* ctx, const nh_Ray* rays, uint32_t count, uint32_t* offsets, nh_RayHit* hits, uint32_t capacity, uint32_t flags) {
+	return nh_castall<false>(ctx, rays, count, offsets, hits, capacity, flags);
+}
+
+extern "C" int nh_spherecast_all(nh_context* ctx, const nh_SphereCast* casts, uint32_t count, uint32_t* offsets, nh_RayHit* hits, uint32_t capacity,
+                                 uint32_t flags) {
+	return nh_castall<true>(ctx, casts, count, offsets, hits, capacity, flags);
 }

@@ -43,7 +43,7 @@ EXPORTS = [
     "nh_partition_top_speed", "nh_partition_set_peer_speeds", "nh_partition_refresh_is_quiet", "nh_partition_mark_ghosts", "nh_partition_pack_deltas", "nh_partition_unpack_deltas",
     "nh_partition_pack_momentum", "nh_partition_unpack_momentum", "nh_partition_exchange_iteration", "nh_partition_unpack_ghosts", "nh_partition_pack_step", "nh_partition_unpack_step", "nh_partition_choose_cut", "nh_partition_set_cut",
     "nh_partition_set_transport", "nh_partition_exchange_step", "nh_partition_step", "nh_partition_transport_check", "nh_partition_transport_result", "nh_set_first_ghost_body",
-    "nh_query_build", "nh_query_refit", "nh_query_stats", "nh_raycast", "nh_overlap", "nh_penetration", "nh_spherecast", "nh_boxcast", "nh_capsulecast", "nh_closest",
+    "nh_query_build", "nh_query_refit", "nh_query_stats", "nh_raycast", "nh_overlap", "nh_penetration", "nh_spherecast", "nh_raycast_all", "nh_spherecast_all", "nh_boxcast", "nh_capsulecast", "nh_closest",
 ]
 HALO_RECORD_BYTES = 64
 
@@ -271,6 +271,10 @@ def lib():
         L.nh_closest.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
         L.nh_overlap.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
         L.nh_penetration.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+        # (an older build of the library, loaded through NUDGE_HIP_LIBRARY for an A/B, has no all-hits casts: World.raycast_all then raises AttributeError)
+        if hasattr(L, "nh_raycast_all"):
+            L.nh_raycast_all.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+            L.nh_spherecast_all.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
         _LIB = L
     return _LIB
 
@@ -715,6 +719,79 @@ class World:
         if synchronize:
             torch.cuda.current_stream(self.dev).synchronize()
         return out
+
+    def _castall_records(self, name, size, casts, offsets, hits, capacity):
+        torch = self.torch
+        n = casts.numel() * casts.element_size() // size
+        if offsets is None:
+            offsets = torch.empty(n + 1, dtype=torch.int32, device=self.dev)
+        if hits is not None and hits.numel() * hits.element_size() < 32 * capacity:
+            raise ValueError(f"{name}: hits holds {hits.numel() * hits.element_size()} bytes, capacity {capacity} needs {32 * capacity}")
+        _check(self.L, getattr(self.L, name)(self.ctx, C.c_void_p(casts.data_ptr() if n else 0), n, C.c_void_p(offsets.data_ptr()),
+                                             C.c_void_p(hits.data_ptr() if hits is not None else 0), capacity, 0), name)
+        return offsets, hits
+
+    def raycast_all_records(self, rays, offsets=None, hits=None, capacity=0):
+        """nh_raycast_all on records already laid out as nh_Ray: `rays` a contiguous device tensor of count x 32 bytes (any dtype).  Returns
+        (offsets, hits) as overlap_records does: the count + 1 offsets as an int32 device tensor holding the uint32 bits and `hits` as given.  With
+        hits = None and capacity = 0 only the offsets are written (count only); otherwise `hits` must hold `capacity` x 32 bytes (nh_RayHit), and the
+        records of ray i are written iff offsets[i + 1] <= capacity.  Enqueued; nothing waits (but a capacity larger than any before grows the scratch)."""
+        return self._castall_records("nh_raycast_all", 32, rays, offsets, hits, capacity)
+
+    def spherecast_all_records(self, casts, offsets=None, hits=None, capacity=0):
+        """nh_spherecast_all on records already laid out as nh_SphereCast (count x 48 bytes): raycast_all_records for swept balls."""
+        return self._castall_records("nh_spherecast_all", 48, casts, offsets, hits, capacity)
+
+    def _castall(self, records, casts, n, capacity, synchronize):
+        torch = self.torch
+        hits, off, written, query = self._overlap_lists(records, casts, n, capacity, 32)
+        f = hits.view(torch.float32).reshape(-1, 8)
+        u = hits.view(torch.int32).reshape(-1, 8).to(torch.int64) & 0xFFFFFFFF
+        if synchronize:
+            torch.cuda.current_stream(self.dev).synchronize()
+        return dict(offsets=off, written=written, query=query, t=f[:, 0], normal=f[:, 1:4], body=u[:, 4], collider=u[:, 5], shape=u[:, 6], tag=u[:, 7], raw=hits)
+
+    def raycast_all(self, origins, directions, max_t=float("inf"), ignore_body=None, capacity=None, synchronize=False):
+        """Every collider each of n rays passes through, ordered along the ray (nh_raycast_all), against the last query_build().  The arguments are
+        raycast()'s.  capacity=None: a count call, then the total is read -- this WAITS for the device -- and an exactly sized list call.  A capacity:
+        one call, and nothing waits; only the segments that fit are listed (offsets[i + 1] <= capacity).
+        Returns a dict of device tensors: offsets (n + 1, int64; offsets[n] = 0xffffffff when the total is 2^32 - 1 or more), `written` (0-d: the
+        records listed, a prefix of whole segments), and per record slot (capacity of them; the first `written` are meaningful) query, t, normal
+        ((capacity, 3)), body, collider, shape, tag (int64) and `raw`, the nh_RayHit records (capacity x 32 bytes).  Within a ray the records come
+        in ascending t, ties by combined collider index; the first is raycast()'s closest hit."""
+        torch = self.torch
+        o = torch.as_tensor(origins, dtype=torch.float32, device=self.dev).reshape(-1, 3)
+        d = torch.as_tensor(directions, dtype=torch.float32, device=self.dev).reshape(-1, 3)
+        n = o.shape[0]
+        if d.shape[0] != n:
+            raise ValueError(f"raycast_all: {n} origins but {d.shape[0]} directions")
+        rays = torch.empty((n, 8), dtype=torch.float32, device=self.dev)
+        rays[:, 0:3] = o
+        rays[:, 3] = torch.as_tensor(max_t, dtype=torch.float32, device=self.dev)
+        rays[:, 4:7] = d
+        ign = 0xFFFFFFFF if ignore_body is None else ignore_body
+        ign = torch.as_tensor(ign, dtype=torch.int64, device=self.dev)
+        rays.view(torch.int32)[:, 7] = (((ign & 0xFFFFFFFF) ^ 0x80000000) - 0x80000000).to(torch.int32)          # (the uint32 bits, as int32)
+        return self._castall(self.raycast_all_records, rays, n, capacity, synchronize)
+
+    def spherecast_all(self, origins, directions, radii, max_t=float("inf"), ignore_body=None, capacity=None, synchronize=False):
+        """Every collider each of n swept balls touches, ordered along the cast (nh_spherecast_all): spherecast()'s arguments, raycast_all()'s
+        capacity rule and result (normal: from the collider to the ball's centre); the first record of a cast is spherecast()'s closest hit."""
+        torch = self.torch
+        o = torch.as_tensor(origins, dtype=torch.float32, device=self.dev).reshape(-1, 3)
+        d = torch.as_tensor(directions, dtype=torch.float32, device=self.dev).reshape(-1, 3)
+        n = o.shape[0]
+        if d.shape[0] != n:
+            raise ValueError(f"spherecast_all: {n} origins but {d.shape[0]} directions")
+        casts = torch.zeros((n, 12), dtype=torch.float32, device=self.dev)
+        casts[:, 0:3] = o
+        casts[:, 3] = torch.as_tensor(max_t, dtype=torch.float32, device=self.dev)
+        casts[:, 4:7] = d
+        ign = 0xFFFFFFFF if ignore_body is None else ignore_body
+        ign = torch.as_tensor(ign, dtype=torch.int64, device=self.dev)
+        casts.view(torch.int32)[:, 7] = (((ign & 0xFFFFFFFF) ^ 0x80000000) - 0x80000000).to(torch.int32)          # (the uint32 bits, as int32)
+        casts[:, 8] = torch.as_tensor(radii, dtype=torch.float32, device=self.dev).reshape(-1)
+        return self._castall(self.spherecast_all_records, casts, n, capacity, synchronize)
 
     def boxcast_records(self, casts, any_hit=False, hits=None):
         """nh_boxcast on records already laid out as nh_BoxCast: `casts` a contiguous device tensor of count x 64 bytes (any dtype).  Returns the
