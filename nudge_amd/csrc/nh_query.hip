@@ -20,6 +20,7 @@
 // Node ids: internal nodes 0 .. n-2 (root 0), leaf j (j-th collider in key order) n-1+j; with one collider the root is that leaf.
 // Traversal is stackless: a node that is missed or a leaf that is done continues at its ESCAPE link (the next node in pre-order after its subtree),
 // a hit internal node at its left child.  A private stack array would go to scratch memory.
+#include <type_traits>
 #include <utility>
 #include "nh_internal.h"
 #include "nh_query.h"
@@ -302,260 +303,204 @@ __global__ __launch_bounds__(NH_Q_TOP_BLOCK) void k_q_boxes_top(const uint32_t* 
 	}
 }
 
-// ---- ray cast -------------------------------------------------------------------------------------------------------------------------------
+// ---- what the walks share -------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ bool nh_q_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
+__device__ __forceinline__ bool nh_q_finite(nh_f3 v) { return nh_q_finite(v.x) && nh_q_finite(v.y) && nh_q_finite(v.z); }
+__device__ __forceinline__ bool nh_q_finite(nh_quat q) { return nh_q_finite(q.x) && nh_q_finite(q.y) && nh_q_finite(q.z) && nh_q_finite(q.s); }
+
+// A collider's record as the predicates of nh_query.h take it: position, rotation, half extents (h.x: the radius of a sphere)
+struct nh_QShape { nh_f3 p; nh_quat q; nh_f3 h; };
+__device__ __forceinline__ nh_QShape nh_q_unpack(const nh_QRec& r) {
+	return { nh_make3(r.a.x, r.a.y, r.a.z), nh_quat{ r.b.x, r.b.y, r.b.z, r.b.w }, nh_make3(r.c.x, r.c.y, r.c.z) };
+}
+
+// Who collider c (combined index) is: (body, index among its shape, shape, tag) -- nh_OverlapHit's four words, and the second 16 bytes of nh_RayHit
+// and nh_PenetrationHit
+__device__ __forceinline__ uint4 nh_q_identity(uint32_t c, uint32_t nbox, const nh_QRec& r) {
+	return make_uint4(__float_as_uint(r.a.w), c < nbox ? c : c - nbox, c < nbox ? NH_SHAPE_BOX : NH_SHAPE_SPHERE, __float_as_uint(r.c.w));
+}
+
+// The stackless walk (the head of this file) from `node`: enter(lo, hi, x) says whether a node's box is entered and may leave a number x for the leaf
+// (the casts' entry t0, the point query's squared distance); leaf(c, record, x) sees every entered leaf whose body is not `ignore` and returns true
+// to end the walk (any-hit; a list segment that is full).
+template <class Enter, class Leaf>
+__device__ __forceinline__ void nh_q_walk(const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec, uint32_t node, uint32_t ignore, Enter enter, Leaf leaf) {
+	float x = 0.0f;
+	while (node != NH_Q_NONE) {
+		const float4 na = nodes[node].a, nb = nodes[node].b;
+		const bool in = enter(nh_make3(na.x, na.y, na.z), nh_make3(nb.x, nb.y, nb.z), x);
+		const uint32_t left = __float_as_uint(na.w);
+		const uint32_t rope = __float_as_uint(nb.w);
+		if (!in) { node = rope; continue; }
+		if (!(left & NH_Q_LEAF)) { node = left; continue; }
+		node = rope;
+		const uint32_t c = left & ~NH_Q_LEAF;
+		const nh_QRec q = rec[c];
+		if (__float_as_uint(q.a.w) == ignore) continue;
+		if (leaf(c, q, x)) break;
+	}
+}
+
+// ---- closest-hit casts ------------------------------------------------------------------------------------------------------------------------
+// Every cast record starts as nh_Ray does: (origin, max_t), (direction, bits(ignore_body)).  A cast shape adds its own words and gives the walk three
+// things: read() -- the decode, `ok` (every field it reads is finite and no size is negative) and the grow w of the node boxes; node() -- the node
+// test, nh_q_cast_node / nh_q_cast_node3 (nh_query.h) under that grow; leaf() -- the two predicates of nh_query.h and, for a shape with a size, the
+// reach rule: the hit is at max(t_pred, the leaf's entry t0), which is what makes the pruning exact.  The all-hits kernels below read
+// their rays and balls through the same structs.
+struct nh_QCastHead {
+	nh_f3 o, d, inv;
+	float max_t;
+	uint32_t ignore;
+	bool ok;
+	__device__ __forceinline__ void head(float4 c0, float4 c1) {
+		o = nh_make3(c0.x, c0.y, c0.z); d = nh_make3(c1.x, c1.y, c1.z);
+		max_t = c0.w; ignore = __float_as_uint(c1.w);
+		ok = nh_q_finite(o) && nh_q_finite(d);
+		inv = nh_make3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+	}
+};
+
+// nh_Ray.  The pad is 2^-18 of the largest coordinate of the origin: nh_q_cast_pad(o, 0), the number a ball of radius 0 gets.
+struct nh_QRay : nh_QCastHead {
+	static constexpr uint32_t WORDS = 2u;
+	float r, w;
+	__device__ __forceinline__ void read(const float4* __restrict__ cp) {
+		head(cp[0], cp[1]);
+		r = 0.0f;
+		w = fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fabsf(o.z)) * 3.814697265625e-06f;
+	}
+	__device__ __forceinline__ bool node(nh_f3 lo, nh_f3 hi, float& t0) const { return nh_q_cast_node(lo, hi, o, inv, w, t0); }
+	__device__ __forceinline__ nh_QHit leaf(const nh_QShape& c, bool box, float) const {
+		return box ? nh_q_ray_box(o, d, c.p, c.q, c.h) : nh_q_ray_sphere(o, d, c.p, c.h.x);
+	}
+};
+
+// nh_SphereCast: every node box grown by w = r + pad.  r = 0 walks and answers as the ray does.
+struct nh_QBall : nh_QCastHead {
+	static constexpr uint32_t WORDS = 3u;
+	float r, w;
+	__device__ __forceinline__ void read(const float4* __restrict__ cp) {
+		head(cp[0], cp[1]);
+		r = cp[2].x;
+		ok = ok && nh_q_finite(r) && !(r < 0.0f);
+		w = r + nh_q_cast_pad(o, r);
+	}
+	__device__ __forceinline__ bool node(nh_f3 lo, nh_f3 hi, float& t0) const { return nh_q_cast_node(lo, hi, o, inv, w, t0); }
+	__device__ __forceinline__ nh_QHit leaf(const nh_QShape& c, bool box, float t0) const {
+		nh_QHit hit = box ? nh_q_sweep_box(o, d, r, c.p, c.q, c.h) : nh_q_sweep_sphere(o, d, r, c.p, c.h.x);
+		if (r > 0.0f && t0 > hit.t) hit.t = t0;
+		return hit;
+	}
+};
+
+// nh_BoxCast: the node box grown per axis by the cast box's world AABB half extent plus the pad.  Size 0 (`ray`) walks and answers as the
+// ray does and does not read the rotation.
+struct nh_QBox : nh_QCastHead {
+	static constexpr uint32_t WORDS = 4u;
+	nh_quat qa;
+	nh_f3 h, w;
+	bool ray;
+	__device__ __forceinline__ void read(const float4* __restrict__ cp) {
+		head(cp[0], cp[1]);
+		const float4 c2 = cp[2], c3 = cp[3];
+		qa = { c2.x, c2.y, c2.z, c2.w }; h = nh_make3(c3.x, c3.y, c3.z);
+		ray = h.x == 0.0f && h.y == 0.0f && h.z == 0.0f;
+		ok = ok && nh_q_finite(h) && !(h.x < 0.0f) && !(h.y < 0.0f) && !(h.z < 0.0f) && (ray || nh_q_finite(qa));
+		const nh_f3 e = ray ? nh_make3(0.0f, 0.0f, 0.0f) : nh_q_box_extent(qa, h);
+		const float s = nh_q_cast_pad(o, fmaxf(fmaxf(e.x, e.y), e.z));
+		w = nh_make3(e.x + s, e.y + s, e.z + s);
+	}
+	__device__ __forceinline__ bool node(nh_f3 lo, nh_f3 hi, float& t0) const { return nh_q_cast_node3(lo, hi, o, inv, w, t0); }
+	__device__ __forceinline__ nh_QHit leaf(const nh_QShape& c, bool box, float t0) const {
+		nh_QHit hit = box ? nh_q_sweep_box_box(o, d, qa, h, c.p, c.q, c.h) : nh_q_sweep_box_sphere(o, d, qa, h, c.p, c.h.x);
+		if (!ray && t0 > hit.t) hit.t = t0;
+		return hit;
+	}
+};
+
+// nh_CapsuleCast: the box cast's node test with the capsule's world AABB half extent |a_k| + r, the reach rule unless r = hh = 0.  hh = 0
+// walks and answers as the ball does (e = r on every axis, the same pad, the same node test's bits) and does not read the rotation.
+struct nh_QCapsule : nh_QCastHead {
+	static constexpr uint32_t WORDS = 4u;
+	nh_quat qa;
+	float r, hh;
+	nh_f3 w;
+	__device__ __forceinline__ void read(const float4* __restrict__ cp) {
+		head(cp[0], cp[1]);
+		const float4 c2 = cp[2], c3 = cp[3];
+		qa = { c2.x, c2.y, c2.z, c2.w }; r = c3.x; hh = c3.y;
+		ok = ok && nh_q_finite(r) && nh_q_finite(hh) && !(r < 0.0f) && !(hh < 0.0f) && (hh == 0.0f || nh_q_finite(qa));
+		const nh_f3 e = nh_q_capsule_extent(nh_q_capsule_axis(qa, hh), r);
+		const float s = nh_q_cast_pad(o, fmaxf(fmaxf(e.x, e.y), e.z));
+		w = nh_make3(e.x + s, e.y + s, e.z + s);
+	}
+	__device__ __forceinline__ bool node(nh_f3 lo, nh_f3 hi, float& t0) const { return nh_q_cast_node3(lo, hi, o, inv, w, t0); }
+	__device__ __forceinline__ nh_QHit leaf(const nh_QShape& c, bool box, float t0) const {
+		nh_QHit hit = box ? nh_q_sweep_capsule_box(o, d, qa, r, hh, c.p, c.q, c.h) : nh_q_sweep_capsule_sphere(o, d, qa, r, hh, c.p, c.h.x);
+		if ((r > 0.0f || hh > 0.0f) && t0 > hit.t) hit.t = t0;
+		return hit;
+	}
+};
+
+// One nh_RayHit, as two 16-byte stores: collider c hit at t with normal n, or, for c = NH_Q_NONE, the miss record, whose t is the cast's max_t (the
+// caller's t) -- a quiet NaN where the cast itself is not `valid`.
+__device__ __forceinline__ void nh_q_write_hit(nh_RayHit* __restrict__ hit, const nh_QRec* __restrict__ rec, uint32_t nbox, bool valid, uint32_t c, float t, nh_f3 n) {
+	nh_RayHit out;
+	out.t = valid ? t : __uint_as_float(0x7fc00000u);
+	out.normal[0] = n.x; out.normal[1] = n.y; out.normal[2] = n.z;
+	if (c == NH_Q_NONE) {
+		out.body = out.collider = out.tag = NH_Q_NONE;
+		out.shape = NH_SHAPE_NONE;
+	} else {
+		const uint4 id = nh_q_identity(c, nbox, rec[c]);
+		out.body = id.x; out.collider = id.y; out.shape = id.z; out.tag = id.w;
+	}
+	float4* hp = reinterpret_cast<float4*>(hit);
+	hp[0] = make_float4(out.t, out.normal[0], out.normal[1], out.normal[2]);
+	hp[1] = make_float4(__uint_as_float(out.body), __uint_as_float(out.collider), __uint_as_float(out.shape), __uint_as_float(out.tag));
+}
+
+// One lane per cast: the walk prunes at the best t so far, nh_q_better (nh_query.h) keeps the closest hit and the tie rule, any_hit stops at the first.
+template <class Shape>
+__device__ __forceinline__ void nh_q_cast(const float4* __restrict__ casts, uint32_t count, nh_RayHit* __restrict__ hits, const nh_QNode* __restrict__ nodes,
+                                          const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox, uint32_t any_hit) {
+	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
+		Shape k;
+		k.read(casts + (size_t)i * Shape::WORDS);
+		float bt = k.max_t;
+		uint32_t bc = NH_Q_NONE;
+		nh_f3 bn = nh_make3(0.0f, 0.0f, 0.0f);
+		nh_q_walk(nodes, rec, k.ok && n ? 0u : NH_Q_NONE, k.ignore,
+			[&](nh_f3 lo, nh_f3 hi, float& t0) { return k.node(lo, hi, t0) && t0 <= bt; },
+			[&](uint32_t c, const nh_QRec& q, float t0) {
+				const nh_QHit h = k.leaf(nh_q_unpack(q), c < nbox, t0);
+				if (!(h.hit && nh_q_better(h.t, c, k.max_t, bt, bc))) return false;
+				bt = h.t; bc = c; bn = h.n;
+				return any_hit != 0u;
+			});
+		nh_q_write_hit(hits + i, rec, nbox, k.ok, bc, bt, bn);
+	}
+}
 
 __global__ __launch_bounds__(256) void k_q_raycast(const nh_Ray* __restrict__ rays, uint32_t count, nh_RayHit* __restrict__ hits,
                                                    const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox, uint32_t any_hit) {
-	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
-		const float4* rp = reinterpret_cast<const float4*>(rays + i);
-		const float4 r0 = rp[0], r1 = rp[1];
-		const nh_f3 o = nh_make3(r0.x, r0.y, r0.z), d = nh_make3(r1.x, r1.y, r1.z);
-		const float max_t = r0.w;
-		const uint32_t ignore = __float_as_uint(r1.w);
-		const bool ok = nh_q_finite(o.x) && nh_q_finite(o.y) && nh_q_finite(o.z) && nh_q_finite(d.x) && nh_q_finite(d.y) && nh_q_finite(d.z);
-		float bt = max_t;
-		uint32_t bc = NH_Q_NONE;
-		nh_f3 bn = nh_make3(0.0f, 0.0f, 0.0f);
-		const nh_f3 inv = nh_make3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
-		const float s = fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fabsf(o.z)) * 3.814697265625e-06f;
-		uint32_t node = ok && n ? 0u : NH_Q_NONE;
-		while (node != NH_Q_NONE) {
-			const float4 na = nodes[node].a, nb = nodes[node].b;
-			const float ax = ((na.x - s) - o.x) * inv.x, bx = ((nb.x + s) - o.x) * inv.x;
-			const float ay = ((na.y - s) - o.y) * inv.y, by = ((nb.y + s) - o.y) * inv.y;
-			const float az = ((na.z - s) - o.z) * inv.z, bz = ((nb.z + s) - o.z) * inv.z;
-			const float t0 = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fminf(az, bz));
-			const float t1 = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fmaxf(az, bz));
-			const bool enter = t0 <= t1 && t1 >= 0.0f && t0 <= bt;
-			const uint32_t left = __float_as_uint(na.w);
-			const uint32_t rope = __float_as_uint(nb.w);
-			if (!enter) { node = rope; continue; }
-			if (!(left & NH_Q_LEAF)) { node = left; continue; }
-			node = rope;
-			const uint32_t c = left & ~NH_Q_LEAF;
-			const nh_QRec q = rec[c];
-			if (__float_as_uint(q.a.w) == ignore) continue;
-			const nh_f3 p = nh_make3(q.a.x, q.a.y, q.a.z);
-			const nh_QHit h = c < nbox ? nh_q_ray_box(o, d, p, nh_quat{ q.b.x, q.b.y, q.b.z, q.b.w }, nh_make3(q.c.x, q.c.y, q.c.z))
-			                           : nh_q_ray_sphere(o, d, p, q.c.x);
-			if (h.hit && nh_q_better(h.t, c, max_t, bt, bc)) {
-				bt = h.t; bc = c; bn = h.n;
-				if (any_hit) break;
-			}
-		}
-		nh_RayHit out;
-		if (bc == NH_Q_NONE) {
-			out.t = ok ? max_t : __uint_as_float(0x7fc00000u);
-			out.normal[0] = out.normal[1] = out.normal[2] = 0.0f;
-			out.body = out.collider = out.tag = NH_Q_NONE;
-			out.shape = NH_SHAPE_NONE;
-		} else {
-			const nh_QRec q = rec[bc];
-			out.t = bt; out.normal[0] = bn.x; out.normal[1] = bn.y; out.normal[2] = bn.z;
-			out.body = __float_as_uint(q.a.w);
-			out.collider = bc < nbox ? bc : bc - nbox;
-			out.shape = bc < nbox ? NH_SHAPE_BOX : NH_SHAPE_SPHERE;
-			out.tag = __float_as_uint(q.c.w);
-		}
-		float4* hp = reinterpret_cast<float4*>(hits + i);
-		hp[0] = make_float4(out.t, out.normal[0], out.normal[1], out.normal[2]);
-		hp[1] = make_float4(__uint_as_float(out.body), __uint_as_float(out.collider), __uint_as_float(out.shape), __uint_as_float(out.tag));
-	}
+	nh_q_cast<nh_QRay>(reinterpret_cast<const float4*>(rays), count, hits, nodes, rec, n, nbox, any_hit);
 }
 
-// ---- sphere cast ------------------------------------------------------------------------------------------------------------------------------
-// k_q_raycast's walk with every node box grown by the radius (nh_q_cast_node, w = r + pad), the sweep predicates of nh_query.h at the leaves, and the
-// reach rule for r > 0: the hit is at max(t_pred, the leaf's entry), which is what makes the pruning exact.  r = 0 walks and answers as
-// k_q_raycast does.
 __global__ __launch_bounds__(256) void k_q_spherecast(const nh_SphereCast* __restrict__ casts, uint32_t count, nh_RayHit* __restrict__ hits,
                                                       const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox, uint32_t any_hit) {
-	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
-		const float4* cp = reinterpret_cast<const float4*>(casts + i);
-		const float4 c0 = cp[0], c1 = cp[1], c2 = cp[2];
-		const nh_f3 o = nh_make3(c0.x, c0.y, c0.z), d = nh_make3(c1.x, c1.y, c1.z);
-		const float max_t = c0.w, r = c2.x;
-		const uint32_t ignore = __float_as_uint(c1.w);
-		const bool ok = nh_q_finite(o.x) && nh_q_finite(o.y) && nh_q_finite(o.z) && nh_q_finite(d.x) && nh_q_finite(d.y) && nh_q_finite(d.z) &&
-		                nh_q_finite(r) && !(r < 0.0f);
-		float bt = max_t;
-		uint32_t bc = NH_Q_NONE;
-		nh_f3 bn = nh_make3(0.0f, 0.0f, 0.0f);
-		const nh_f3 inv = nh_make3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
-		const float w = r + nh_q_cast_pad(o, r);
-		const bool reach = r > 0.0f;
-		uint32_t node = ok && n ? 0u : NH_Q_NONE;
-		while (node != NH_Q_NONE) {
-			const float4 na = nodes[node].a, nb = nodes[node].b;
-			float t0;
-			const bool enter = nh_q_cast_node(nh_make3(na.x, na.y, na.z), nh_make3(nb.x, nb.y, nb.z), o, inv, w, t0) && t0 <= bt;
-			const uint32_t left = __float_as_uint(na.w);
-			const uint32_t rope = __float_as_uint(nb.w);
-			if (!enter) { node = rope; continue; }
-			if (!(left & NH_Q_LEAF)) { node = left; continue; }
-			node = rope;
-			const uint32_t c = left & ~NH_Q_LEAF;
-			const nh_QRec q = rec[c];
-			if (__float_as_uint(q.a.w) == ignore) continue;
-			const nh_f3 p = nh_make3(q.a.x, q.a.y, q.a.z);
-			nh_QHit h = c < nbox ? nh_q_sweep_box(o, d, r, p, nh_quat{ q.b.x, q.b.y, q.b.z, q.b.w }, nh_make3(q.c.x, q.c.y, q.c.z))
-			                     : nh_q_sweep_sphere(o, d, r, p, q.c.x);
-			if (reach && t0 > h.t) h.t = t0;
-			if (h.hit && nh_q_better(h.t, c, max_t, bt, bc)) {
-				bt = h.t; bc = c; bn = h.n;
-				if (any_hit) break;
-			}
-		}
-		nh_RayHit out;
-		if (bc == NH_Q_NONE) {
-			out.t = ok ? max_t : __uint_as_float(0x7fc00000u);
-			out.normal[0] = out.normal[1] = out.normal[2] = 0.0f;
-			out.body = out.collider = out.tag = NH_Q_NONE;
-			out.shape = NH_SHAPE_NONE;
-		} else {
-			const nh_QRec q = rec[bc];
-			out.t = bt; out.normal[0] = bn.x; out.normal[1] = bn.y; out.normal[2] = bn.z;
-			out.body = __float_as_uint(q.a.w);
-			out.collider = bc < nbox ? bc : bc - nbox;
-			out.shape = bc < nbox ? NH_SHAPE_BOX : NH_SHAPE_SPHERE;
-			out.tag = __float_as_uint(q.c.w);
-		}
-		float4* hp = reinterpret_cast<float4*>(hits + i);
-		hp[0] = make_float4(out.t, out.normal[0], out.normal[1], out.normal[2]);
-		hp[1] = make_float4(__uint_as_float(out.body), __uint_as_float(out.collider), __uint_as_float(out.shape), __uint_as_float(out.tag));
-	}
+	nh_q_cast<nh_QBall>(reinterpret_cast<const float4*>(casts), count, hits, nodes, rec, n, nbox, any_hit);
 }
 
-// ---- box cast ---------------------------------------------------------------------------------------------------------------------------------
-// k_q_spherecast's walk with the node box grown per axis by the cast box's world AABB half extent plus the pad (nh_q_cast_node3), the box-cast
-// predicates of nh_query.h at the leaves, and the reach rule for a nonzero size.  Size 0 walks and answers as k_q_raycast does, and
-// does not read the rotation.  (Without the waves-per-EU hint the box-box test lands at 129 VGPRs and 3 waves; with it, 128 and 4, no scratch.)
+// (Without the waves-per-EU hint the box-box test lands at 129 VGPRs and 3 waves; with it, 128 and 4, no scratch.)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k_q_boxcast(const nh_BoxCast* __restrict__ casts, uint32_t count, nh_RayHit* __restrict__ hits,
                                                    const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox, uint32_t any_hit) {
-	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
-		const float4* cp = reinterpret_cast<const float4*>(casts + i);
-		const float4 c0 = cp[0], c1 = cp[1], c2 = cp[2], c3 = cp[3];
-		const nh_f3 o = nh_make3(c0.x, c0.y, c0.z), d = nh_make3(c1.x, c1.y, c1.z), h = nh_make3(c3.x, c3.y, c3.z);
-		const nh_quat qa = { c2.x, c2.y, c2.z, c2.w };
-		const float max_t = c0.w;
-		const uint32_t ignore = __float_as_uint(c1.w);
-		const bool ray = h.x == 0.0f && h.y == 0.0f && h.z == 0.0f;
-		const bool ok = nh_q_finite(o.x) && nh_q_finite(o.y) && nh_q_finite(o.z) && nh_q_finite(d.x) && nh_q_finite(d.y) && nh_q_finite(d.z) &&
-		                nh_q_finite(h.x) && nh_q_finite(h.y) && nh_q_finite(h.z) && !(h.x < 0.0f) && !(h.y < 0.0f) && !(h.z < 0.0f) &&
-		                (ray || (nh_q_finite(qa.x) && nh_q_finite(qa.y) && nh_q_finite(qa.z) && nh_q_finite(qa.s)));
-		float bt = max_t;
-		uint32_t bc = NH_Q_NONE;
-		nh_f3 bn = nh_make3(0.0f, 0.0f, 0.0f);
-		const nh_f3 inv = nh_make3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
-		const nh_f3 e = ray ? nh_make3(0.0f, 0.0f, 0.0f) : nh_q_box_extent(qa, h);
-		const float s = nh_q_cast_pad(o, fmaxf(fmaxf(e.x, e.y), e.z));
-		const nh_f3 w = nh_make3(e.x + s, e.y + s, e.z + s);
-		uint32_t node = ok && n ? 0u : NH_Q_NONE;
-		while (node != NH_Q_NONE) {
-			const float4 na = nodes[node].a, nb = nodes[node].b;
-			float t0;
-			const bool enter = nh_q_cast_node3(nh_make3(na.x, na.y, na.z), nh_make3(nb.x, nb.y, nb.z), o, inv, w, t0) && t0 <= bt;
-			const uint32_t left = __float_as_uint(na.w);
-			const uint32_t rope = __float_as_uint(nb.w);
-			if (!enter) { node = rope; continue; }
-			if (!(left & NH_Q_LEAF)) { node = left; continue; }
-			node = rope;
-			const uint32_t c = left & ~NH_Q_LEAF;
-			const nh_QRec q = rec[c];
-			if (__float_as_uint(q.a.w) == ignore) continue;
-			const nh_f3 p = nh_make3(q.a.x, q.a.y, q.a.z);
-			nh_QHit hh = c < nbox ? nh_q_sweep_box_box(o, d, qa, h, p, nh_quat{ q.b.x, q.b.y, q.b.z, q.b.w }, nh_make3(q.c.x, q.c.y, q.c.z))
-			                      : nh_q_sweep_box_sphere(o, d, qa, h, p, q.c.x);
-			if (!ray && t0 > hh.t) hh.t = t0;
-			if (hh.hit && nh_q_better(hh.t, c, max_t, bt, bc)) {
-				bt = hh.t; bc = c; bn = hh.n;
-				if (any_hit) break;
-			}
-		}
-		nh_RayHit out;
-		if (bc == NH_Q_NONE) {
-			out.t = ok ? max_t : __uint_as_float(0x7fc00000u);
-			out.normal[0] = out.normal[1] = out.normal[2] = 0.0f;
-			out.body = out.collider = out.tag = NH_Q_NONE;
-			out.shape = NH_SHAPE_NONE;
-		} else {
-			const nh_QRec q = rec[bc];
-			out.t = bt; out.normal[0] = bn.x; out.normal[1] = bn.y; out.normal[2] = bn.z;
-			out.body = __float_as_uint(q.a.w);
-			out.collider = bc < nbox ? bc : bc - nbox;
-			out.shape = bc < nbox ? NH_SHAPE_BOX : NH_SHAPE_SPHERE;
-			out.tag = __float_as_uint(q.c.w);
-		}
-		float4* hp = reinterpret_cast<float4*>(hits + i);
-		hp[0] = make_float4(out.t, out.normal[0], out.normal[1], out.normal[2]);
-		hp[1] = make_float4(__uint_as_float(out.body), __uint_as_float(out.collider), __uint_as_float(out.shape), __uint_as_float(out.tag));
-	}
+	nh_q_cast<nh_QBox>(reinterpret_cast<const float4*>(casts), count, hits, nodes, rec, n, nbox, any_hit);
 }
 
-// ---- capsule cast -----------------------------------------------------------------------------------------------------------------------------
-// k_q_boxcast's walk with the node box grown per axis by the capsule's world AABB half extent |a_k| + r plus the pad (nh_q_cast_node3), the capsule-cast
-// predicates of nh_query.h at the leaves, and the reach rule unless r = hh = 0.  hh = 0 walks and answers as k_q_spherecast does (e = r
-// on every axis, the same pad, the same node test's bits) and does not read the rotation.
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k_q_capsulecast(const nh_CapsuleCast* __restrict__ casts, uint32_t count, nh_RayHit* __restrict__ hits,
                                                    const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox, uint32_t any_hit) {
-	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
-		const float4* cp = reinterpret_cast<const float4*>(casts + i);
-		const float4 c0 = cp[0], c1 = cp[1], c2 = cp[2], c3 = cp[3];
-		const nh_f3 o = nh_make3(c0.x, c0.y, c0.z), d = nh_make3(c1.x, c1.y, c1.z);
-		const nh_quat qa = { c2.x, c2.y, c2.z, c2.w };
-		const float max_t = c0.w, r = c3.x, hh = c3.y;
-		const uint32_t ignore = __float_as_uint(c1.w);
-		const bool ok = nh_q_finite(o.x) && nh_q_finite(o.y) && nh_q_finite(o.z) && nh_q_finite(d.x) && nh_q_finite(d.y) && nh_q_finite(d.z) &&
-		                nh_q_finite(r) && nh_q_finite(hh) && !(r < 0.0f) && !(hh < 0.0f) &&
-		                (hh == 0.0f || (nh_q_finite(qa.x) && nh_q_finite(qa.y) && nh_q_finite(qa.z) && nh_q_finite(qa.s)));
-		float bt = max_t;
-		uint32_t bc = NH_Q_NONE;
-		nh_f3 bn = nh_make3(0.0f, 0.0f, 0.0f);
-		const nh_f3 inv = nh_make3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
-		const nh_f3 e = nh_q_capsule_extent(nh_q_capsule_axis(qa, hh), r);
-		const float s = nh_q_cast_pad(o, fmaxf(fmaxf(e.x, e.y), e.z));
-		const nh_f3 w = nh_make3(e.x + s, e.y + s, e.z + s);
-		const bool reach = r > 0.0f || hh > 0.0f;
-		uint32_t node = ok && n ? 0u : NH_Q_NONE;
-		while (node != NH_Q_NONE) {
-			const float4 na = nodes[node].a, nb = nodes[node].b;
-			float t0;
-			const bool enter = nh_q_cast_node3(nh_make3(na.x, na.y, na.z), nh_make3(nb.x, nb.y, nb.z), o, inv, w, t0) && t0 <= bt;
-			const uint32_t left = __float_as_uint(na.w);
-			const uint32_t rope = __float_as_uint(nb.w);
-			if (!enter) { node = rope; continue; }
-			if (!(left & NH_Q_LEAF)) { node = left; continue; }
-			node = rope;
-			const uint32_t c = left & ~NH_Q_LEAF;
-			const nh_QRec q = rec[c];
-			if (__float_as_uint(q.a.w) == ignore) continue;
-			const nh_f3 p = nh_make3(q.a.x, q.a.y, q.a.z);
-			nh_QHit h = c < nbox ? nh_q_sweep_capsule_box(o, d, qa, r, hh, p, nh_quat{ q.b.x, q.b.y, q.b.z, q.b.w }, nh_make3(q.c.x, q.c.y, q.c.z))
-			                     : nh_q_sweep_capsule_sphere(o, d, qa, r, hh, p, q.c.x);
-			if (reach && t0 > h.t) h.t = t0;
-			if (h.hit && nh_q_better(h.t, c, max_t, bt, bc)) {
-				bt = h.t; bc = c; bn = h.n;
-				if (any_hit) break;
-			}
-		}
-		nh_RayHit out;
-		if (bc == NH_Q_NONE) {
-			out.t = ok ? max_t : __uint_as_float(0x7fc00000u);
-			out.normal[0] = out.normal[1] = out.normal[2] = 0.0f;
-			out.body = out.collider = out.tag = NH_Q_NONE;
-			out.shape = NH_SHAPE_NONE;
-		} else {
-			const nh_QRec q = rec[bc];
-			out.t = bt; out.normal[0] = bn.x; out.normal[1] = bn.y; out.normal[2] = bn.z;
-			out.body = __float_as_uint(q.a.w);
-			out.collider = bc < nbox ? bc : bc - nbox;
-			out.shape = bc < nbox ? NH_SHAPE_BOX : NH_SHAPE_SPHERE;
-			out.tag = __float_as_uint(q.c.w);
-		}
-		float4* hp = reinterpret_cast<float4*>(hits + i);
-		hp[0] = make_float4(out.t, out.normal[0], out.normal[1], out.normal[2]);
-		hp[1] = make_float4(__uint_as_float(out.body), __uint_as_float(out.collider), __uint_as_float(out.shape), __uint_as_float(out.tag));
-	}
+	nh_q_cast<nh_QCapsule>(reinterpret_cast<const float4*>(casts), count, hits, nodes, rec, n, nbox, any_hit);
 }
 
 // ---- closest point ----------------------------------------------------------------------------------------------------------------------------
@@ -564,7 +509,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
 //   seed  p's Morton key in the frame of the last build (clamped to its bounds), its place among the sorted keys by binary search, and the exact keys of
 //         the NH_Q_SEED leaves on either side of that place: a bound near p before the walk, which otherwise goes left first from the root -- towards
 //         the lowest Morton region, usually far from p.  Compiled out by -DNH_Q_CLOSEST_NO_SEED (tools/closest_rates.py measures both).
-//   walk  k_q_raycast's stackless walk with the node test above; the leaves evaluate nh_q_point_box / nh_q_point_sphere and the key.  A seeded winner
+//   walk  nh_q_walk with the node test above; the leaves evaluate nh_q_point_box / nh_q_point_sphere and the key.  A seeded winner
 //         met again does not replace itself (equal key and index), so the seed changes the work, never the answer.
 #define NH_Q_SEED 4
 __global__ __launch_bounds__(256) void k_q_closest(const nh_PointQuery* __restrict__ queries, uint32_t count, nh_PointHit* __restrict__ hits,
@@ -576,11 +521,19 @@ __global__ __launch_bounds__(256) void k_q_closest(const nh_PointQuery* __restri
 		const nh_f3 p = nh_make3(q0.x, q0.y, q0.z);
 		const float max_d = q0.w;
 		const uint32_t ignore = __float_as_uint(q1.x);
-		const bool ok = nh_q_finite(p.x) && nh_q_finite(p.y) && nh_q_finite(p.z) && max_d >= 0.0f;       // (+inf is a valid max_distance; NaN is not)
+		const bool ok = nh_q_finite(p) && max_d >= 0.0f;       // (+inf is a valid max_distance; NaN is not)
 		float bd = max_d;
 		uint32_t bc = NH_Q_NONE;
 		nh_f3 bn = nh_make3(0.0f, 0.0f, 0.0f), bx = nh_make3(0.0f, 0.0f, 0.0f);
 		const bool walk = ok && n;
+		// a leaf of squared box distance d2, for the seed and the walk alike
+		const auto leaf = [&](uint32_t c, const nh_QRec& q, float d2) {
+			const nh_QShape s = nh_q_unpack(q);
+			const nh_QPoint h = c < nbox ? nh_q_point_box(p, s.p, s.q, s.h) : nh_q_point_sphere(p, s.p, s.h.x);
+			const float k = nh_q_point_key(h.d, d2);
+			if (nh_q_closer(k, c, max_d, bd, bc)) { bd = k; bc = c; bn = h.n; bx = h.x; }
+			return false;
+		};
 #ifndef NH_Q_CLOSEST_NO_SEED
 		if (walk) {
 			const nh_f3 smin = nh_make3(nh_float_unflip(ctl->kmin[0]), nh_float_unflip(ctl->kmin[1]), nh_float_unflip(ctl->kmin[2]));
@@ -599,32 +552,12 @@ __global__ __launch_bounds__(256) void k_q_closest(const nh_PointQuery* __restri
 				const uint32_t c = __float_as_uint(na.w) & ~NH_Q_LEAF;
 				const nh_QRec q = rec[c];
 				if (__float_as_uint(q.a.w) == ignore) continue;
-				const nh_f3 cp = nh_make3(q.a.x, q.a.y, q.a.z);
-				const nh_QPoint h = c < nbox ? nh_q_point_box(p, cp, nh_quat{ q.b.x, q.b.y, q.b.z, q.b.w }, nh_make3(q.c.x, q.c.y, q.c.z))
-				                             : nh_q_point_sphere(p, cp, q.c.x);
-				const float k = nh_q_point_key(h.d, nh_q_point_node(nh_make3(na.x, na.y, na.z), nh_make3(nb.x, nb.y, nb.z), p));
-				if (nh_q_closer(k, c, max_d, bd, bc)) { bd = k; bc = c; bn = h.n; bx = h.x; }
+				leaf(c, q, nh_q_point_node(nh_make3(na.x, na.y, na.z), nh_make3(nb.x, nb.y, nb.z), p));
 			}
 		}
 #endif
-		uint32_t node = walk ? 0u : NH_Q_NONE;
-		while (node != NH_Q_NONE) {
-			const float4 na = nodes[node].a, nb = nodes[node].b;
-			const float d2 = nh_q_point_node(nh_make3(na.x, na.y, na.z), nh_make3(nb.x, nb.y, nb.z), p);
-			const uint32_t left = __float_as_uint(na.w);
-			const uint32_t rope = __float_as_uint(nb.w);
-			if (d2 > 0.0f && sqrtf(d2) > bd) { node = rope; continue; }
-			if (!(left & NH_Q_LEAF)) { node = left; continue; }
-			node = rope;
-			const uint32_t c = left & ~NH_Q_LEAF;
-			const nh_QRec q = rec[c];
-			if (__float_as_uint(q.a.w) == ignore) continue;
-			const nh_f3 cp = nh_make3(q.a.x, q.a.y, q.a.z);
-			const nh_QPoint h = c < nbox ? nh_q_point_box(p, cp, nh_quat{ q.b.x, q.b.y, q.b.z, q.b.w }, nh_make3(q.c.x, q.c.y, q.c.z))
-			                             : nh_q_point_sphere(p, cp, q.c.x);
-			const float k = nh_q_point_key(h.d, d2);
-			if (nh_q_closer(k, c, max_d, bd, bc)) { bd = k; bc = c; bn = h.n; bx = h.x; }
-		}
+		nh_q_walk(nodes, rec, walk ? 0u : NH_Q_NONE, ignore,
+			[&](nh_f3 lo, nh_f3 hi, float& d2) { d2 = nh_q_point_node(lo, hi, p); return !(d2 > 0.0f && sqrtf(d2) > bd); }, leaf);
 		float4* hp = reinterpret_cast<float4*>(hits + i);
 		if (bc == NH_Q_NONE) {
 			const float md = ok ? max_d : __uint_as_float(0x7fc00000u);
@@ -632,17 +565,17 @@ __global__ __launch_bounds__(256) void k_q_closest(const nh_PointQuery* __restri
 			hp[1] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(NH_Q_NONE));
 			hp[2] = make_float4(__uint_as_float(NH_Q_NONE), __uint_as_float(NH_SHAPE_NONE), __uint_as_float(NH_Q_NONE), 0.0f);
 		} else {
-			const nh_QRec q = rec[bc];
+			const uint4 id = nh_q_identity(bc, nbox, rec[bc]);
 			hp[0] = make_float4(bd, bn.x, bn.y, bn.z);
-			hp[1] = make_float4(bx.x, bx.y, bx.z, q.a.w);
-			hp[2] = make_float4(__uint_as_float(bc < nbox ? bc : bc - nbox), __uint_as_float(bc < nbox ? NH_SHAPE_BOX : NH_SHAPE_SPHERE), q.c.w, 0.0f);
+			hp[1] = make_float4(bx.x, bx.y, bx.z, __uint_as_float(id.x));
+			hp[2] = make_float4(__uint_as_float(id.y), __uint_as_float(id.z), __uint_as_float(id.w), 0.0f);
 		}
 	}
 }
 
 // ---- overlap ---------------------------------------------------------------------------------------------------------------------------------
 // nh_overlap is a chain of launches with kernel boundaries as the only hand-offs; no atomic decides where a record goes:
-//   k_q_overlap<false, false>  one lane per query: the tree walk of k_q_raycast (stackless, escape links) with the query's padded world AABB, the exact
+//   k_q_overlap<false, false>  one lane per query: nh_q_walk (stackless, escape links) with the query's padded world AABB as the node test, the exact
 //                       predicate at the leaves; offsets[i] = the count (offsets[count] = 0, scanned along)
 //   k_q_overlap<false, true>   the same for the capsule queries of nonzero half height, which the first skips: their predicates need more registers
 //                       than the sphere and box walk's occupancy allows, so they run in an instantiation of their own
@@ -684,33 +617,24 @@ __global__ __launch_bounds__(256) void k_q_overlap(const nh_OverlapQuery* __rest
 		const float s = fmaxf(fmaxf(fmaxf(fabsf(lo.x), fabsf(lo.y)), fmaxf(fabsf(lo.z), fabsf(hi.x))), fmaxf(fabsf(hi.y), fabsf(hi.z))) * 3.814697265625e-06f;
 		lo = nh_make3(lo.x - s, lo.y - s, lo.z - s); hi = nh_make3(hi.x + s, hi.y + s, hi.z + s);
 		uint32_t k = 0u;
-		uint32_t node = ok && n ? 0u : NH_Q_NONE;
-		while (node != NH_Q_NONE) {
-			const float4 na = nodes[node].a, nb = nodes[node].b;
-			const bool enter = na.x <= hi.x && lo.x <= nb.x && na.y <= hi.y && lo.y <= nb.y && na.z <= hi.z && lo.z <= nb.z;
-			const uint32_t left = __float_as_uint(na.w);
-			const uint32_t rope = __float_as_uint(nb.w);
-			if (!enter) { node = rope; continue; }
-			if (!(left & NH_Q_LEAF)) { node = left; continue; }
-			node = rope;
-			const uint32_t cc = left & ~NH_Q_LEAF;
-			const nh_QRec r = rec[cc];
-			if (__float_as_uint(r.a.w) == ignore) continue;
-			const nh_f3 p = nh_make3(r.a.x, r.a.y, r.a.z), rh = nh_make3(r.c.x, r.c.y, r.c.z);
-			const nh_quat rq = { r.b.x, r.b.y, r.b.z, r.b.w };
-			bool hit;
-			if (capsule) hit = cc < nbox ? nh_q_overlap_capsule_box_a(c, a, h.x, p, rq, rh) : nh_q_overlap_capsule_sphere_a(c, a, h.x, p, rh.x);
-			else if (cc < nbox) hit = sphere ? nh_q_overlap_sphere_box(c, h.x, p, rq, rh) : nh_q_overlap_box_box(c, qr, h, p, rq, rh);
-			else hit = sphere ? nh_q_overlap_sphere_sphere(c, h.x, p, rh.x) : nh_q_overlap_sphere_box(p, rh.x, c, qr, h);
-			if (!hit) continue;
-			if (LIST) {
-				// (the count pass found exactly end - base: the segment is full once they are written, nothing else can follow)
-				keys[base + k] = ((uint64_t)i << cbits) | cc;
-				vals[base + k] = cc;
-				if (base + k + 1u == end) break;
-			}
-			++k;
-		}
+		nh_q_walk(nodes, rec, ok && n ? 0u : NH_Q_NONE, ignore,
+			[&](nh_f3 nlo, nh_f3 nhi, float&) { return nlo.x <= hi.x && lo.x <= nhi.x && nlo.y <= hi.y && lo.y <= nhi.y && nlo.z <= hi.z && lo.z <= nhi.z; },
+			[&](uint32_t cc, const nh_QRec& r, float) {
+				const nh_QShape col = nh_q_unpack(r);
+				bool hit;
+				if (capsule) hit = cc < nbox ? nh_q_overlap_capsule_box_a(c, a, h.x, col.p, col.q, col.h) : nh_q_overlap_capsule_sphere_a(c, a, h.x, col.p, col.h.x);
+				else if (cc < nbox) hit = sphere ? nh_q_overlap_sphere_box(c, h.x, col.p, col.q, col.h) : nh_q_overlap_box_box(c, qr, h, col.p, col.q, col.h);
+				else hit = sphere ? nh_q_overlap_sphere_sphere(c, h.x, col.p, col.h.x) : nh_q_overlap_sphere_box(col.p, col.h.x, c, qr, h);
+				if (!hit) return false;
+				if (LIST) {
+					// (the count pass found exactly end - base: the segment is full once they are written, nothing else can follow)
+					keys[base + k] = ((uint64_t)i << cbits) | cc;
+					vals[base + k] = cc;
+					if (base + k + 1u == end) return true;
+				}
+				++k;
+				return false;
+			});
 		if (!LIST) offsets[i] = k;
 	}
 }
@@ -738,8 +662,7 @@ __global__ __launch_bounds__(256) void k_q_overlap_gather(const uint32_t* __rest
 	for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < m; j += gridDim.x * blockDim.x) {
 		const uint32_t c = vals[j];
 		if (c >= n) continue;          // (cannot happen: the list pass fills the whole prefix; a guard against reading outside the records)
-		const nh_QRec r = rec[c];
-		*reinterpret_cast<uint4*>(hits + j) = make_uint4(__float_as_uint(r.a.w), c < nbox ? c : c - nbox, c < nbox ? NH_SHAPE_BOX : NH_SHAPE_SPHERE, __float_as_uint(r.c.w));
+		*reinterpret_cast<uint4*>(hits + j) = nh_q_identity(c, nbox, rec[c]);
 	}
 }
 
@@ -766,24 +689,23 @@ __global__ __launch_bounds__(256) void k_q_penetration_gather(const uint64_t* __
 		const bool capsule = shape == NH_SHAPE_CAPSULE && h.y != 0.0f;
 		const bool sphere = !capsule && (shape == NH_SHAPE_SPHERE || shape == NH_SHAPE_CAPSULE);
 		const nh_QRec r = rec[cc];
-		const nh_f3 p = nh_make3(r.a.x, r.a.y, r.a.z), rh = nh_make3(r.c.x, r.c.y, r.c.z);
-		const nh_quat rq = { r.b.x, r.b.y, r.b.z, r.b.w };
+		const nh_QShape s = nh_q_unpack(r);
 		nh_QPen o;
 		if (capsule) {
 			const nh_f3 a = nh_q_capsule_axis(qr, h.y);
-			o = cc < nbox ? nh_q_pen_capsule_box_a(c, a, h.x, p, rq, rh) : nh_q_pen_capsule_sphere_a(c, a, h.x, p, rh.x);
-		} else if (cc < nbox) o = sphere ? nh_q_pen_sphere_box(c, h.x, p, rq, rh) : nh_q_pen_box_box(c, qr, h, p, rq, rh);
-		else o = sphere ? nh_q_pen_sphere_sphere(c, h.x, p, rh.x) : nh_q_pen_box_sphere(c, qr, h, p, rh.x);
+			o = cc < nbox ? nh_q_pen_capsule_box_a(c, a, h.x, s.p, s.q, s.h) : nh_q_pen_capsule_sphere_a(c, a, h.x, s.p, s.h.x);
+		} else if (cc < nbox) o = sphere ? nh_q_pen_sphere_box(c, h.x, s.p, s.q, s.h) : nh_q_pen_box_box(c, qr, h, s.p, s.q, s.h);
+		else o = sphere ? nh_q_pen_sphere_sphere(c, h.x, s.p, s.h.x) : nh_q_pen_box_sphere(c, qr, h, s.p, s.h.x);
 		uint4* out = reinterpret_cast<uint4*>(hits + j);
 		out[0] = make_uint4(__float_as_uint(o.n.x), __float_as_uint(o.n.y), __float_as_uint(o.n.z), __float_as_uint(o.depth));
-		out[1] = make_uint4(__float_as_uint(r.a.w), cc < nbox ? cc : cc - nbox, cc < nbox ? NH_SHAPE_BOX : NH_SHAPE_SPHERE, __float_as_uint(r.c.w));
+		out[1] = nh_q_identity(cc, nbox, r);
 	}
 }
 
 // ---- all-hits casts ---------------------------------------------------------------------------------------------------------------------------
 // nh_raycast_all / nh_spherecast_all: every collider a cast passes through, ordered along the cast.  nh_overlap's chain (kernel boundaries are the
 // only hand-offs, no atomic decides where a record goes) with the casts' walk in place of the volume walk and an ordering by t behind it:
-//   k_q_castall<S, false>  one lane per cast: k_q_raycast's (S = false) / k_q_spherecast's (S = true) stackless walk with the pruning bound FIXED at
+//   k_q_castall<S, false>  one lane per cast: the ray's (S = false) / the ball's (S = true) decode and node test in nh_q_walk, with the pruning bound FIXED at
 //                       max_t -- there is no best hit to tighten it -- and nh_q_all_hit at every entered leaf; offsets[i] = the number of hits.
 //                       For a ray (and r = 0) every node box is grown by nh_q_all_pad as well: the set is every collider the PREDICATE accepts, and the
 //                       closest-hit walk's pad does not cover the predicates' rounding at a distance (nh_query.h)
@@ -797,23 +719,9 @@ __global__ __launch_bounds__(256) void k_q_penetration_gather(const uint64_t* __
 //   k_q_castall_gather<S>  one lane per written record: the cast index from the key, the collider from the value; it re-reads the cast and the 48-byte
 //                       collider record and evaluates nh_q_all_hit again -- the same function on the same inputs, the leaf entry of the reach rule
 //                       rebuilt by nh_q_leaf_entry as the build stores it -- and writes nh_RayHit as two 16-byte stores.  No normal goes through a sort.
-struct nh_QCast { nh_f3 o, d, inv; float max_t, r, w; uint32_t ignore; bool ok; };
-
-template <bool SWEEP>
-__device__ __forceinline__ nh_QCast nh_q_cast_read(const float4* __restrict__ casts, uint32_t i) {
-	const float4* cp = casts + (size_t)i * (SWEEP ? 3u : 2u);
-	const float4 c0 = cp[0], c1 = cp[1];
-	nh_QCast k;
-	k.o = nh_make3(c0.x, c0.y, c0.z); k.d = nh_make3(c1.x, c1.y, c1.z);
-	k.max_t = c0.w; k.ignore = __float_as_uint(c1.w);
-	k.r = SWEEP ? cp[2].x : 0.0f;
-	k.ok = nh_q_finite(k.o.x) && nh_q_finite(k.o.y) && nh_q_finite(k.o.z) && nh_q_finite(k.d.x) && nh_q_finite(k.d.y) && nh_q_finite(k.d.z);
-	if (SWEEP) k.ok = k.ok && nh_q_finite(k.r) && !(k.r < 0.0f);
-	k.inv = nh_make3(1.0f / k.d.x, 1.0f / k.d.y, 1.0f / k.d.z);
-	// (k_q_raycast's pad and k_q_spherecast's: the same number for r = 0)
-	k.w = SWEEP ? k.r + nh_q_cast_pad(k.o, k.r) : fmaxf(fmaxf(fabsf(k.o.x), fabsf(k.o.y)), fabsf(k.o.z)) * 3.814697265625e-06f;
-	return k;
-}
+// the ray's and the ball's decode, validity and grow are the closest-hit casts' own: radius 0 gives the ray's bytes, and the first record of a cast is
+// the closest-hit record
+template <bool SWEEP> using nh_QCastAll = std::conditional_t<SWEEP, nh_QBall, nh_QRay>;
 
 template <bool SWEEP, bool LIST>
 __global__ __launch_bounds__(256) void k_q_castall(const float4* __restrict__ casts, uint32_t count, uint32_t* offsets,
@@ -827,37 +735,30 @@ __global__ __launch_bounds__(256) void k_q_castall(const float4* __restrict__ ca
 			base = offsets[i]; end = offsets[i + 1u];
 			if (!(base < end && end <= written)) continue;          // empty, or not in the written prefix
 		}
-		const nh_QCast k = nh_q_cast_read<SWEEP>(casts, i);
+		nh_QCastAll<SWEEP> k;
+		k.read(casts + (size_t)i * k.WORDS);
 		const bool ray = !SWEEP || !(k.r > 0.0f);
 		uint32_t hits = 0u;
-		uint32_t node = k.ok && n ? 0u : NH_Q_NONE;
-		while (node != NH_Q_NONE) {
-			const float4 na = nodes[node].a, nb = nodes[node].b;
-			float t0;
-			const nh_f3 lo = nh_make3(na.x, na.y, na.z), hi = nh_make3(nb.x, nb.y, nb.z);
-			// (a ray's node box also takes the predicates' own rounding, nh_q_all_pad; a ball's reach rule reads the entry of the box as the build stores it)
-			const float w = ray ? k.w + nh_q_all_pad(lo, hi, k.o) : k.w;
-			const bool enter = nh_q_cast_node(lo, hi, k.o, k.inv, w, t0) && t0 <= k.max_t;
-			const uint32_t left = __float_as_uint(na.w);
-			const uint32_t rope = __float_as_uint(nb.w);
-			if (!enter) { node = rope; continue; }
-			if (!(left & NH_Q_LEAF)) { node = left; continue; }
-			node = rope;
-			const uint32_t c = left & ~NH_Q_LEAF;
-			const nh_QRec q = rec[c];
-			if (__float_as_uint(q.a.w) == k.ignore) continue;
-			const nh_QHit h = nh_q_all_hit<SWEEP>(k.o, k.d, k.r, k.max_t, t0, nh_make3(q.a.x, q.a.y, q.a.z), nh_quat{ q.b.x, q.b.y, q.b.z, q.b.w },
-			                                      nh_make3(q.c.x, q.c.y, q.c.z), c < nbox);
-			if (!h.hit) continue;
-			if (LIST) {
-				// (the count pass found exactly end - base: the segment is full once they are written, nothing else can follow)
-				const uint32_t tb = nh_q_tbits(h.t);
-				keys[base + hits] = one_sort ? ((uint64_t)i << (32u + cbits)) | ((uint64_t)tb << cbits) | c : ((uint64_t)i << cbits) | c;
-				vals[base + hits] = one_sort ? c : tb;
-				if (base + hits + 1u == end) break;
-			}
-			++hits;
-		}
+		nh_q_walk(nodes, rec, k.ok && n ? 0u : NH_Q_NONE, k.ignore,
+			[&](nh_f3 lo, nh_f3 hi, float& t0) {
+				// (a ray's node box also takes the predicates' own rounding, nh_q_all_pad; a ball's reach rule reads the entry of the box as the build stores it)
+				const float w = ray ? k.w + nh_q_all_pad(lo, hi, k.o) : k.w;
+				return nh_q_cast_node(lo, hi, k.o, k.inv, w, t0) && t0 <= k.max_t;
+			},
+			[&](uint32_t c, const nh_QRec& q, float t0) {
+				const nh_QShape s = nh_q_unpack(q);
+				const nh_QHit h = nh_q_all_hit<SWEEP>(k.o, k.d, k.r, k.max_t, t0, s.p, s.q, s.h, c < nbox);
+				if (!h.hit) return false;
+				if (LIST) {
+					// (the count pass found exactly end - base: the segment is full once they are written, nothing else can follow)
+					const uint32_t tb = nh_q_tbits(h.t);
+					keys[base + hits] = one_sort ? ((uint64_t)i << (32u + cbits)) | ((uint64_t)tb << cbits) | c : ((uint64_t)i << cbits) | c;
+					vals[base + hits] = one_sort ? c : tb;
+					if (base + hits + 1u == end) return true;
+				}
+				++hits;
+				return false;
+			});
 		if (!LIST) offsets[i] = hits;
 	}
 }
@@ -882,16 +783,13 @@ __global__ __launch_bounds__(256) void k_q_castall_gather(const uint64_t* __rest
 		const uint32_t c = vals[j];
 		const uint64_t i = keys[j] >> ishift;
 		if (c >= n || i >= count) continue;          // (cannot happen: the list pass fills the whole prefix; a guard against reading outside the records)
-		const nh_QCast k = nh_q_cast_read<SWEEP>(casts, (uint32_t)i);
-		const nh_QRec q = rec[c];
-		const nh_f3 p = nh_make3(q.a.x, q.a.y, q.a.z), qh = nh_make3(q.c.x, q.c.y, q.c.z);
-		const nh_quat qq = { q.b.x, q.b.y, q.b.z, q.b.w };
+		nh_QCastAll<SWEEP> k;
+		k.read(casts + (size_t)i * k.WORDS);
+		const nh_QShape s = nh_q_unpack(rec[c]);
 		float t0 = 0.0f;
-		if (SWEEP && k.r > 0.0f) nh_q_leaf_entry(k.o, k.inv, k.w, p, qq, qh, c < nbox, t0);      // (entered: the walk listed it)
-		const nh_QHit h = nh_q_all_hit<SWEEP>(k.o, k.d, k.r, k.max_t, t0, p, qq, qh, c < nbox);
-		float4* hp = reinterpret_cast<float4*>(hits + j);
-		hp[0] = make_float4(h.t, h.n.x, h.n.y, h.n.z);
-		hp[1] = make_float4(q.a.w, __uint_as_float(c < nbox ? c : c - nbox), __uint_as_float(c < nbox ? NH_SHAPE_BOX : NH_SHAPE_SPHERE), q.c.w);
+		if (SWEEP && k.r > 0.0f) nh_q_leaf_entry(k.o, k.inv, k.w, s.p, s.q, s.h, c < nbox, t0);      // (entered: the walk listed it)
+		const nh_QHit h = nh_q_all_hit<SWEEP>(k.o, k.d, k.r, k.max_t, t0, s.p, s.q, s.h, c < nbox);
+		nh_q_write_hit(hits + j, rec, nbox, true, c, h.t, h.n);
 	}
 }
 
@@ -1024,52 +922,34 @@ extern "C" int nh_query_stats(nh_context* ctx, nh_QueryStats* out) {
 	return NH_OK;
 }
 
-extern "C" int nh_raycast(nh_context* ctx, const nh_Ray* rays, uint32_t count, nh_RayHit* hits, uint32_t flags) {
+// The four closest-hit casts: one record type and one kernel each, the same checks in the same order.
+template <class Cast>
+static int nh_cast(nh_context* ctx, const char* label, void (*kernel)(const Cast*, uint32_t, nh_RayHit*, const nh_QNode*, const nh_QRec*, uint32_t, uint32_t, uint32_t),
+                   const Cast* casts, uint32_t count, nh_RayHit* hits, uint32_t flags) {
 	if (!ctx || !ctx->query || !ctx->query->built) return NH_ERR_INVALID;
 	if (flags & ~(uint32_t)NH_RAY_ANY_HIT) return NH_ERR_INVALID;
 	if (count == 0u) return NH_OK;
-	if (!rays || !hits || (((uintptr_t)rays | (uintptr_t)hits) & 15u)) return NH_ERR_INVALID;      // (records are moved as 16-byte words)
+	if (!casts || !hits || (((uintptr_t)casts | (uintptr_t)hits) & 15u)) return NH_ERR_INVALID;    // (records are moved as 16-byte words)
 	NH_HIP_CHECK(ctx, hipSetDevice(ctx->device));
 	nh_QueryState* q = ctx->query;
-	NH_LAUNCH(ctx, "q_raycast", k_q_raycast, nh_grid_for(count, 256, 1u << 20), 256, rays, count, hits, q->nodes, q->rec, q->n, q->nbox,
-	          (flags & NH_RAY_ANY_HIT) ? 1u : 0u);
+	NH_LAUNCH(ctx, label, kernel, nh_grid_for(count, 256, 1u << 20), 256, casts, count, hits, q->nodes, q->rec, q->n, q->nbox, (flags & NH_RAY_ANY_HIT) ? 1u : 0u);
 	return NH_OK;
+}
+
+extern "C" int nh_raycast(nh_context* ctx, const nh_Ray* rays, uint32_t count, nh_RayHit* hits, uint32_t flags) {
+	return nh_cast(ctx, "q_raycast", k_q_raycast, rays, count, hits, flags);
 }
 
 extern "C" int nh_spherecast(nh_context* ctx, const nh_SphereCast* casts, uint32_t count, nh_RayHit* hits, uint32_t flags) {
-	if (!ctx || !ctx->query || !ctx->query->built) return NH_ERR_INVALID;
-	if (flags & ~(uint32_t)NH_RAY_ANY_HIT) return NH_ERR_INVALID;
-	if (count == 0u) return NH_OK;
-	if (!casts || !hits || (((uintptr_t)casts | (uintptr_t)hits) & 15u)) return NH_ERR_INVALID;    // (records are moved as 16-byte words)
-	NH_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-	nh_QueryState* q = ctx->query;
-	NH_LAUNCH(ctx, "q_spherecast", k_q_spherecast, nh_grid_for(count, 256, 1u << 20), 256, casts, count, hits, q->nodes, q->rec, q->n, q->nbox,
-	          (flags & NH_RAY_ANY_HIT) ? 1u : 0u);
-	return NH_OK;
+	return nh_cast(ctx, "q_spherecast", k_q_spherecast, casts, count, hits, flags);
 }
 
 extern "C" int nh_capsulecast(nh_context* ctx, const nh_CapsuleCast* casts, uint32_t count, nh_RayHit* hits, uint32_t flags) {
-	if (!ctx || !ctx->query || !ctx->query->built) return NH_ERR_INVALID;
-	if (flags & ~(uint32_t)NH_RAY_ANY_HIT) return NH_ERR_INVALID;
-	if (count == 0u) return NH_OK;
-	if (!casts || !hits || (((uintptr_t)casts | (uintptr_t)hits) & 15u)) return NH_ERR_INVALID;    // (records are moved as 16-byte words)
-	NH_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-	nh_QueryState* q = ctx->query;
-	NH_LAUNCH(ctx, "q_capsulecast", k_q_capsulecast, nh_grid_for(count, 256, 1u << 20), 256, casts, count, hits, q->nodes, q->rec, q->n, q->nbox,
-	          (flags & NH_RAY_ANY_HIT) ? 1u : 0u);
-	return NH_OK;
+	return nh_cast(ctx, "q_capsulecast", k_q_capsulecast, casts, count, hits, flags);
 }
 
 extern "C" int nh_boxcast(nh_context* ctx, const nh_BoxCast* casts, uint32_t count, nh_RayHit* hits, uint32_t flags) {
-	if (!ctx || !ctx->query || !ctx->query->built) return NH_ERR_INVALID;
-	if (flags & ~(uint32_t)NH_RAY_ANY_HIT) return NH_ERR_INVALID;
-	if (count == 0u) return NH_OK;
-	if (!casts || !hits || (((uintptr_t)casts | (uintptr_t)hits) & 15u)) return NH_ERR_INVALID;    // (records are moved as 16-byte words)
-	NH_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-	nh_QueryState* q = ctx->query;
-	NH_LAUNCH(ctx, "q_boxcast", k_q_boxcast, nh_grid_for(count, 256, 1u << 20), 256, casts, count, hits, q->nodes, q->rec, q->n, q->nbox,
-	          (flags & NH_RAY_ANY_HIT) ? 1u : 0u);
-	return NH_OK;
+	return nh_cast(ctx, "q_boxcast", k_q_boxcast, casts, count, hits, flags);
 }
 
 extern "C" int nh_closest(nh_context* ctx, const nh_PointQuery* queries, uint32_t count, nh_PointHit* hits, uint32_t flags) {
@@ -1104,6 +984,21 @@ static int nh_overlap_reserve(nh_context* ctx, uint32_t capacity) {
 
 static int nh_q_bits(uint32_t x) { return x ? 32 - __builtin_clz(x) : 0; }
 
+// The argument rules nh_overlap, nh_penetration and the all-hits casts share, in the order that decides the error code; then, for a list call (*list:
+// hits and a capacity given), the sort scratch.  The caller returns what this returns where that is an error or count == 0.
+static int nh_overlap_args(nh_context* ctx, const void* queries, uint32_t count, const uint32_t* offsets, const void* hits, uint32_t capacity, uint32_t flags,
+                           bool* list) {
+	if (!ctx || !ctx->query || !ctx->query->built) return NH_ERR_INVALID;
+	if (flags != 0u || count >= NH_Q_MAX_COLLIDERS) return NH_ERR_INVALID;
+	if (count == 0u) return NH_OK;
+	if (!queries || ((uintptr_t)queries & 15u)) return NH_ERR_INVALID;        // (records are read as 16-byte words)
+	if (!offsets || ((uintptr_t)offsets & 3u)) return NH_ERR_INVALID;
+	if ((!hits && capacity) || ((uintptr_t)hits & 15u)) return NH_ERR_INVALID;
+	NH_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+	*list = hits != nullptr && capacity != 0u;
+	return *list ? nh_overlap_reserve(ctx, capacity) : NH_OK;
+}
+
 // From the per-query counts in offsets[0 .. count) (offsets[count] = 0) to the complete offsets, the written prefix and the overflow marker: the three
 // launches nh_overlap's chain and the all-hits casts share.
 static void nh_overlap_offsets(nh_context* ctx, uint32_t* offsets, uint32_t count, uint32_t capacity) {
@@ -1119,16 +1014,9 @@ static void nh_overlap_offsets(nh_context* ctx, uint32_t* offsets, uint32_t coun
 static int nh_overlap_chain(nh_context* ctx, const nh_OverlapQuery* queries, uint32_t count, uint32_t* offsets, const void* hits, uint32_t capacity,
                             uint32_t flags, bool* list_out, int* in_b, uint32_t* cbits_out) {
 	*list_out = false;
-	if (!ctx || !ctx->query || !ctx->query->built) return NH_ERR_INVALID;
-	if (flags != 0u || count >= NH_Q_MAX_COLLIDERS) return NH_ERR_INVALID;
-	if (count == 0u) return NH_OK;
-	if (!queries || ((uintptr_t)queries & 15u)) return NH_ERR_INVALID;        // (records are read as 16-byte words)
-	if (!offsets || ((uintptr_t)offsets & 3u)) return NH_ERR_INVALID;
-	if ((!hits && capacity) || ((uintptr_t)hits & 15u)) return NH_ERR_INVALID;
-	NH_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+	bool list = false;
+	{ const int rc = nh_overlap_args(ctx, queries, count, offsets, hits, capacity, flags, &list); if (rc || count == 0u) return rc; }
 	nh_QueryState* q = ctx->query;
-	const bool list = hits != nullptr && capacity != 0u;
-	if (list) { const int rc = nh_overlap_reserve(ctx, capacity); if (rc) return rc; }
 	const uint32_t cbits = (uint32_t)nh_q_bits(q->n);
 	*cbits_out = cbits;
 	const uint32_t grid = nh_grid_for(count, 256, 1u << 20);
@@ -1176,16 +1064,9 @@ extern "C" int nh_penetration(nh_context* ctx, const nh_OverlapQuery* queries, u
 // The all-hits chain (the comment above k_q_castall): nh_overlap's argument rules, offsets and capacity contract, the casts' walk, the ordering by t.
 template <bool SWEEP>
 static int nh_castall(nh_context* ctx, const void* casts, uint32_t count, uint32_t* offsets, nh_RayHit* hits, uint32_t capacity, uint32_t flags) {
-	if (!ctx || !ctx->query || !ctx->query->built) return NH_ERR_INVALID;
-	if (flags != 0u || count >= NH_Q_MAX_COLLIDERS) return NH_ERR_INVALID;
-	if (count == 0u) return NH_OK;
-	if (!casts || ((uintptr_t)casts & 15u)) return NH_ERR_INVALID;            // (records are read as 16-byte words)
-	if (!offsets || ((uintptr_t)offsets & 3u)) return NH_ERR_INVALID;
-	if ((!hits && capacity) || ((uintptr_t)hits & 15u)) return NH_ERR_INVALID;
-	NH_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+	bool list = false;
+	{ const int rc = nh_overlap_args(ctx, casts, count, offsets, hits, capacity, flags, &list); if (rc || count == 0u) return rc; }
 	nh_QueryState* q = ctx->query;
-	const bool list = hits != nullptr && capacity != 0u;
-	if (list) { const int rc = nh_overlap_reserve(ctx, capacity); if (rc) return rc; }
 	const float4* recs = static_cast<const float4*>(casts);
 	const uint32_t cbits = (uint32_t)nh_q_bits(q->n);
 	const int ibits = nh_q_bits(count);

@@ -647,78 +647,72 @@ class World:
         _check(self.L, self.L.nh_query_stats(self.ctx, C.byref(st)), "nh_query_stats")
         return {k: int(getattr(st, k)) for k, _ in QueryStats._fields_}
 
-    def raycast_records(self, rays, any_hit=False, hits=None):
-        """nh_raycast on records already laid out as nh_Ray: `rays` a contiguous device tensor of count x 32 bytes (any dtype).  Returns the
-        count x 32-byte uint8 device tensor of nh_RayHit records (`hits`, or a new one)."""
+    def _ignore_bits(self, ignore_body):
+        """`ignore_body` (None, a body index, or n of them) as the uint32 bits in an int32 tensor."""
         torch = self.torch
-        n = rays.numel() * rays.element_size() // 32
-        if hits is None:
-            hits = torch.empty((n, 32), dtype=torch.uint8, device=self.dev)
-        _check(self.L, self.L.nh_raycast(self.ctx, C.c_void_p(rays.data_ptr() if n else 0), n, C.c_void_p(hits.data_ptr() if n else 0),
-                                         NH_RAY_ANY_HIT if any_hit else 0), "nh_raycast")
-        return hits
+        ign = 0xFFFFFFFF if ignore_body is None else ignore_body
+        ign = torch.as_tensor(ign, dtype=torch.int64, device=self.dev)
+        return (((ign & 0xFFFFFFFF) ^ 0x80000000) - 0x80000000).to(torch.int32)
 
-    def raycast(self, origins, directions, max_t=float("inf"), ignore_body=None, any_hit=False, synchronize=False):
-        """Closest-hit (or any-hit) ray casts against the last query_build().  `origins` / `directions`: (n, 3) torch tensors or arrays (uploaded once);
-        `max_t`: a number or n values; `ignore_body`: None, a body index, or n of them.  Returns a dict of device tensors: t (n), normal (n, 3), body,
-        collider, shape, tag (n, int64; 0xffffffff = none) and `raw`, the nh_RayHit records.  Nothing waits for the device unless `synchronize`."""
+    def _cast_head(self, name, origins, directions, max_t, ignore_body, width):
+        """New cast records of `width` floats with the words every cast starts with (nh_Ray) filled in: (records, n).  Wider records start as
+        zeros: the kernel reads their padding as part of 16-byte words."""
         torch = self.torch
         o = torch.as_tensor(origins, dtype=torch.float32, device=self.dev).reshape(-1, 3)
         d = torch.as_tensor(directions, dtype=torch.float32, device=self.dev).reshape(-1, 3)
         n = o.shape[0]
         if d.shape[0] != n:
-            raise ValueError(f"raycast: {n} origins but {d.shape[0]} directions")
-        rays = torch.empty((n, 8), dtype=torch.float32, device=self.dev)
-        rays[:, 0:3] = o
-        rays[:, 3] = torch.as_tensor(max_t, dtype=torch.float32, device=self.dev)
-        rays[:, 4:7] = d
-        ign = 0xFFFFFFFF if ignore_body is None else ignore_body
-        ign = torch.as_tensor(ign, dtype=torch.int64, device=self.dev)
-        rays.view(torch.int32)[:, 7] = (((ign & 0xFFFFFFFF) ^ 0x80000000) - 0x80000000).to(torch.int32)          # (the uint32 bits, as int32)
-        raw = self.raycast_records(rays, any_hit=any_hit)
-        f = raw.view(torch.float32).reshape(n, 8)
-        u = raw.view(torch.int32).reshape(n, 8).to(torch.int64) & 0xFFFFFFFF
-        out = dict(t=f[:, 0], normal=f[:, 1:4], body=u[:, 4], collider=u[:, 5], shape=u[:, 6], tag=u[:, 7], raw=raw)
+            raise ValueError(f"{name}: {n} origins but {d.shape[0]} directions")
+        casts = (torch.zeros if width > 8 else torch.empty)((n, width), dtype=torch.float32, device=self.dev)
+        casts[:, 0:3] = o
+        casts[:, 3] = torch.as_tensor(max_t, dtype=torch.float32, device=self.dev)
+        casts[:, 4:7] = d
+        casts.view(torch.int32)[:, 7] = self._ignore_bits(ignore_body)
+        return casts, n
+
+    def _cast_records(self, name, size, casts, any_hit, hits):
+        torch = self.torch
+        n = casts.numel() * casts.element_size() // size
+        if hits is None:
+            hits = torch.empty((n, 32), dtype=torch.uint8, device=self.dev)
+        _check(self.L, getattr(self.L, name)(self.ctx, C.c_void_p(casts.data_ptr() if n else 0), n, C.c_void_p(hits.data_ptr() if n else 0),
+                                             NH_RAY_ANY_HIT if any_hit else 0), name)
+        return hits
+
+    def _ray_hits(self, raw, synchronize, **first):
+        """The dict the casts return: `first`, then the fields of the nh_RayHit records `raw` and `raw` itself."""
+        torch = self.torch
+        f = raw.view(torch.float32).reshape(-1, 8)
+        u = raw.view(torch.int32).reshape(-1, 8).to(torch.int64) & 0xFFFFFFFF
         if synchronize:
             torch.cuda.current_stream(self.dev).synchronize()
-        return out
+        return dict(first, t=f[:, 0], normal=f[:, 1:4], body=u[:, 4], collider=u[:, 5], shape=u[:, 6], tag=u[:, 7], raw=raw)
+
+    def raycast_records(self, rays, any_hit=False, hits=None):
+        """nh_raycast on records already laid out as nh_Ray: `rays` a contiguous device tensor of count x 32 bytes (any dtype).  Returns the
+        count x 32-byte uint8 device tensor of nh_RayHit records (`hits`, or a new one)."""
+        return self._cast_records("nh_raycast", 32, rays, any_hit, hits)
+
+    def raycast(self, origins, directions, max_t=float("inf"), ignore_body=None, any_hit=False, synchronize=False):
+        """Closest-hit (or any-hit) ray casts against the last query_build().  `origins` / `directions`: (n, 3) torch tensors or arrays (uploaded once);
+        `max_t`: a number or n values; `ignore_body`: None, a body index, or n of them.  Returns a dict of device tensors: t (n), normal (n, 3), body,
+        collider, shape, tag (n, int64; 0xffffffff = none) and `raw`, the nh_RayHit records.  Nothing waits for the device unless `synchronize`."""
+        rays, _ = self._cast_head("raycast", origins, directions, max_t, ignore_body, 8)
+        return self._ray_hits(self.raycast_records(rays, any_hit=any_hit), synchronize)
 
     def spherecast_records(self, casts, any_hit=False, hits=None):
         """nh_spherecast on records already laid out as nh_SphereCast: `casts` a contiguous device tensor of count x 48 bytes (any dtype).  Returns the
         count x 32-byte uint8 device tensor of nh_RayHit records (`hits`, or a new one)."""
-        torch = self.torch
-        n = casts.numel() * casts.element_size() // 48
-        if hits is None:
-            hits = torch.empty((n, 32), dtype=torch.uint8, device=self.dev)
-        _check(self.L, self.L.nh_spherecast(self.ctx, C.c_void_p(casts.data_ptr() if n else 0), n, C.c_void_p(hits.data_ptr() if n else 0),
-                                            NH_RAY_ANY_HIT if any_hit else 0), "nh_spherecast")
-        return hits
+        return self._cast_records("nh_spherecast", 48, casts, any_hit, hits)
 
     def spherecast(self, origins, directions, radii, max_t=float("inf"), ignore_body=None, any_hit=False, synchronize=False):
         """Closest-hit (or any-hit) sphere casts against the last query_build(): the ball of radius `radii` (a number or n values) swept from `origins`
         along `directions` ((n, 3) each).  `max_t`, `ignore_body` and the result are raycast()'s: t, normal (from the collider to the ball's centre; the
         contact point is origin + t * direction - radius * normal), body, collider, shape, tag and `raw`.  Nothing waits unless `synchronize`."""
         torch = self.torch
-        o = torch.as_tensor(origins, dtype=torch.float32, device=self.dev).reshape(-1, 3)
-        d = torch.as_tensor(directions, dtype=torch.float32, device=self.dev).reshape(-1, 3)
-        n = o.shape[0]
-        if d.shape[0] != n:
-            raise ValueError(f"spherecast: {n} origins but {d.shape[0]} directions")
-        casts = torch.zeros((n, 12), dtype=torch.float32, device=self.dev)
-        casts[:, 0:3] = o
-        casts[:, 3] = torch.as_tensor(max_t, dtype=torch.float32, device=self.dev)
-        casts[:, 4:7] = d
-        ign = 0xFFFFFFFF if ignore_body is None else ignore_body
-        ign = torch.as_tensor(ign, dtype=torch.int64, device=self.dev)
-        casts.view(torch.int32)[:, 7] = (((ign & 0xFFFFFFFF) ^ 0x80000000) - 0x80000000).to(torch.int32)          # (the uint32 bits, as int32)
+        casts, _ = self._cast_head("spherecast", origins, directions, max_t, ignore_body, 12)
         casts[:, 8] = torch.as_tensor(radii, dtype=torch.float32, device=self.dev).reshape(-1)
-        raw = self.spherecast_records(casts, any_hit=any_hit)
-        f = raw.view(torch.float32).reshape(n, 8)
-        u = raw.view(torch.int32).reshape(n, 8).to(torch.int64) & 0xFFFFFFFF
-        out = dict(t=f[:, 0], normal=f[:, 1:4], body=u[:, 4], collider=u[:, 5], shape=u[:, 6], tag=u[:, 7], raw=raw)
-        if synchronize:
-            torch.cuda.current_stream(self.dev).synchronize()
-        return out
+        return self._ray_hits(self.spherecast_records(casts, any_hit=any_hit), synchronize)
 
     def _castall_records(self, name, size, casts, offsets, hits, capacity):
         torch = self.torch
@@ -743,13 +737,8 @@ class World:
         return self._castall_records("nh_spherecast_all", 48, casts, offsets, hits, capacity)
 
     def _castall(self, records, casts, n, capacity, synchronize):
-        torch = self.torch
         hits, off, written, query = self._overlap_lists(records, casts, n, capacity, 32)
-        f = hits.view(torch.float32).reshape(-1, 8)
-        u = hits.view(torch.int32).reshape(-1, 8).to(torch.int64) & 0xFFFFFFFF
-        if synchronize:
-            torch.cuda.current_stream(self.dev).synchronize()
-        return dict(offsets=off, written=written, query=query, t=f[:, 0], normal=f[:, 1:4], body=u[:, 4], collider=u[:, 5], shape=u[:, 6], tag=u[:, 7], raw=hits)
+        return self._ray_hits(hits, synchronize, offsets=off, written=written, query=query)
 
     def raycast_all(self, origins, directions, max_t=float("inf"), ignore_body=None, capacity=None, synchronize=False):
         """Every collider each of n rays passes through, ordered along the ray (nh_raycast_all), against the last query_build().  The arguments are
@@ -759,50 +748,21 @@ class World:
         records listed, a prefix of whole segments), and per record slot (capacity of them; the first `written` are meaningful) query, t, normal
         ((capacity, 3)), body, collider, shape, tag (int64) and `raw`, the nh_RayHit records (capacity x 32 bytes).  Within a ray the records come
         in ascending t, ties by combined collider index; the first is raycast()'s closest hit."""
-        torch = self.torch
-        o = torch.as_tensor(origins, dtype=torch.float32, device=self.dev).reshape(-1, 3)
-        d = torch.as_tensor(directions, dtype=torch.float32, device=self.dev).reshape(-1, 3)
-        n = o.shape[0]
-        if d.shape[0] != n:
-            raise ValueError(f"raycast_all: {n} origins but {d.shape[0]} directions")
-        rays = torch.empty((n, 8), dtype=torch.float32, device=self.dev)
-        rays[:, 0:3] = o
-        rays[:, 3] = torch.as_tensor(max_t, dtype=torch.float32, device=self.dev)
-        rays[:, 4:7] = d
-        ign = 0xFFFFFFFF if ignore_body is None else ignore_body
-        ign = torch.as_tensor(ign, dtype=torch.int64, device=self.dev)
-        rays.view(torch.int32)[:, 7] = (((ign & 0xFFFFFFFF) ^ 0x80000000) - 0x80000000).to(torch.int32)          # (the uint32 bits, as int32)
+        rays, n = self._cast_head("raycast_all", origins, directions, max_t, ignore_body, 8)
         return self._castall(self.raycast_all_records, rays, n, capacity, synchronize)
 
     def spherecast_all(self, origins, directions, radii, max_t=float("inf"), ignore_body=None, capacity=None, synchronize=False):
         """Every collider each of n swept balls touches, ordered along the cast (nh_spherecast_all): spherecast()'s arguments, raycast_all()'s
         capacity rule and result (normal: from the collider to the ball's centre); the first record of a cast is spherecast()'s closest hit."""
         torch = self.torch
-        o = torch.as_tensor(origins, dtype=torch.float32, device=self.dev).reshape(-1, 3)
-        d = torch.as_tensor(directions, dtype=torch.float32, device=self.dev).reshape(-1, 3)
-        n = o.shape[0]
-        if d.shape[0] != n:
-            raise ValueError(f"spherecast_all: {n} origins but {d.shape[0]} directions")
-        casts = torch.zeros((n, 12), dtype=torch.float32, device=self.dev)
-        casts[:, 0:3] = o
-        casts[:, 3] = torch.as_tensor(max_t, dtype=torch.float32, device=self.dev)
-        casts[:, 4:7] = d
-        ign = 0xFFFFFFFF if ignore_body is None else ignore_body
-        ign = torch.as_tensor(ign, dtype=torch.int64, device=self.dev)
-        casts.view(torch.int32)[:, 7] = (((ign & 0xFFFFFFFF) ^ 0x80000000) - 0x80000000).to(torch.int32)          # (the uint32 bits, as int32)
+        casts, n = self._cast_head("spherecast_all", origins, directions, max_t, ignore_body, 12)
         casts[:, 8] = torch.as_tensor(radii, dtype=torch.float32, device=self.dev).reshape(-1)
         return self._castall(self.spherecast_all_records, casts, n, capacity, synchronize)
 
     def boxcast_records(self, casts, any_hit=False, hits=None):
         """nh_boxcast on records already laid out as nh_BoxCast: `casts` a contiguous device tensor of count x 64 bytes (any dtype).  Returns the
         count x 32-byte uint8 device tensor of nh_RayHit records (`hits`, or a new one)."""
-        torch = self.torch
-        n = casts.numel() * casts.element_size() // 64
-        if hits is None:
-            hits = torch.empty((n, 32), dtype=torch.uint8, device=self.dev)
-        _check(self.L, self.L.nh_boxcast(self.ctx, C.c_void_p(casts.data_ptr() if n else 0), n, C.c_void_p(hits.data_ptr() if n else 0),
-                                         NH_RAY_ANY_HIT if any_hit else 0), "nh_boxcast")
-        return hits
+        return self._cast_records("nh_boxcast", 64, casts, any_hit, hits)
 
     def boxcast(self, origins, directions, half_extents, rotations=None, max_t=float("inf"), ignore_body=None, any_hit=False, synchronize=False):
         """Closest-hit (or any-hit) box casts against the last query_build(): the oriented box of `half_extents` ((n, 3) or (3,)) and `rotations`
@@ -810,41 +770,18 @@ class World:
         `ignore_body` and the result are raycast()'s: t, normal (from the collider to the cast box), body, collider, shape, tag and `raw`.  Nothing
         waits unless `synchronize`."""
         torch = self.torch
-        o = torch.as_tensor(origins, dtype=torch.float32, device=self.dev).reshape(-1, 3)
-        d = torch.as_tensor(directions, dtype=torch.float32, device=self.dev).reshape(-1, 3)
-        n = o.shape[0]
-        if d.shape[0] != n:
-            raise ValueError(f"boxcast: {n} origins but {d.shape[0]} directions")
-        casts = torch.zeros((n, 16), dtype=torch.float32, device=self.dev)
-        casts[:, 0:3] = o
-        casts[:, 3] = torch.as_tensor(max_t, dtype=torch.float32, device=self.dev)
-        casts[:, 4:7] = d
-        ign = 0xFFFFFFFF if ignore_body is None else ignore_body
-        ign = torch.as_tensor(ign, dtype=torch.int64, device=self.dev)
-        casts.view(torch.int32)[:, 7] = (((ign & 0xFFFFFFFF) ^ 0x80000000) - 0x80000000).to(torch.int32)          # (the uint32 bits, as int32)
+        casts, _ = self._cast_head("boxcast", origins, directions, max_t, ignore_body, 16)
         if rotations is None:
             casts[:, 11] = 1.0
         else:
             casts[:, 8:12] = torch.as_tensor(rotations, dtype=torch.float32, device=self.dev).reshape(-1, 4)
         casts[:, 12:15] = torch.as_tensor(half_extents, dtype=torch.float32, device=self.dev).reshape(-1, 3)
-        raw = self.boxcast_records(casts, any_hit=any_hit)
-        f = raw.view(torch.float32).reshape(n, 8)
-        u = raw.view(torch.int32).reshape(n, 8).to(torch.int64) & 0xFFFFFFFF
-        out = dict(t=f[:, 0], normal=f[:, 1:4], body=u[:, 4], collider=u[:, 5], shape=u[:, 6], tag=u[:, 7], raw=raw)
-        if synchronize:
-            torch.cuda.current_stream(self.dev).synchronize()
-        return out
+        return self._ray_hits(self.boxcast_records(casts, any_hit=any_hit), synchronize)
 
     def capsulecast_records(self, casts, any_hit=False, hits=None):
         """nh_capsulecast on records already laid out as nh_CapsuleCast: `casts` a contiguous device tensor of count x 64 bytes (any dtype).  Returns
         the count x 32-byte uint8 device tensor of nh_RayHit records (`hits`, or a new one)."""
-        torch = self.torch
-        n = casts.numel() * casts.element_size() // 64
-        if hits is None:
-            hits = torch.empty((n, 32), dtype=torch.uint8, device=self.dev)
-        _check(self.L, self.L.nh_capsulecast(self.ctx, C.c_void_p(casts.data_ptr() if n else 0), n, C.c_void_p(hits.data_ptr() if n else 0),
-                                             NH_RAY_ANY_HIT if any_hit else 0), "nh_capsulecast")
-        return hits
+        return self._cast_records("nh_capsulecast", 64, casts, any_hit, hits)
 
     def capsulecast(self, origins, directions, radii, half_heights, rotations=None, max_t=float("inf"), ignore_body=None, any_hit=False,
                     synchronize=False):
@@ -853,31 +790,14 @@ class World:
         `origins` along `directions` ((n, 3) each).  `max_t`, `ignore_body` and the result are raycast()'s: t, normal (from the collider to the
         capsule), body, collider, shape, tag and `raw`.  Nothing waits unless `synchronize`."""
         torch = self.torch
-        o = torch.as_tensor(origins, dtype=torch.float32, device=self.dev).reshape(-1, 3)
-        d = torch.as_tensor(directions, dtype=torch.float32, device=self.dev).reshape(-1, 3)
-        n = o.shape[0]
-        if d.shape[0] != n:
-            raise ValueError(f"capsulecast: {n} origins but {d.shape[0]} directions")
-        casts = torch.zeros((n, 16), dtype=torch.float32, device=self.dev)
-        casts[:, 0:3] = o
-        casts[:, 3] = torch.as_tensor(max_t, dtype=torch.float32, device=self.dev)
-        casts[:, 4:7] = d
-        ign = 0xFFFFFFFF if ignore_body is None else ignore_body
-        ign = torch.as_tensor(ign, dtype=torch.int64, device=self.dev)
-        casts.view(torch.int32)[:, 7] = (((ign & 0xFFFFFFFF) ^ 0x80000000) - 0x80000000).to(torch.int32)          # (the uint32 bits, as int32)
+        casts, _ = self._cast_head("capsulecast", origins, directions, max_t, ignore_body, 16)
         if rotations is None:
             casts[:, 11] = 1.0
         else:
             casts[:, 8:12] = torch.as_tensor(rotations, dtype=torch.float32, device=self.dev).reshape(-1, 4)
         casts[:, 12] = torch.as_tensor(radii, dtype=torch.float32, device=self.dev).reshape(-1)
         casts[:, 13] = torch.as_tensor(half_heights, dtype=torch.float32, device=self.dev).reshape(-1)
-        raw = self.capsulecast_records(casts, any_hit=any_hit)
-        f = raw.view(torch.float32).reshape(n, 8)
-        u = raw.view(torch.int32).reshape(n, 8).to(torch.int64) & 0xFFFFFFFF
-        out = dict(t=f[:, 0], normal=f[:, 1:4], body=u[:, 4], collider=u[:, 5], shape=u[:, 6], tag=u[:, 7], raw=raw)
-        if synchronize:
-            torch.cuda.current_stream(self.dev).synchronize()
-        return out
+        return self._ray_hits(self.capsulecast_records(casts, any_hit=any_hit), synchronize)
 
     def closest_records(self, queries, hits=None):
         """nh_closest on records already laid out as nh_PointQuery: `queries` a contiguous device tensor of count x 32 bytes (any dtype).  Returns
@@ -901,9 +821,7 @@ class World:
         queries = torch.zeros((n, 8), dtype=torch.float32, device=self.dev)
         queries[:, 0:3] = p
         queries[:, 3] = torch.as_tensor(max_distance, dtype=torch.float32, device=self.dev)
-        ign = 0xFFFFFFFF if ignore_body is None else ignore_body
-        ign = torch.as_tensor(ign, dtype=torch.int64, device=self.dev)
-        queries.view(torch.int32)[:, 4] = (((ign & 0xFFFFFFFF) ^ 0x80000000) - 0x80000000).to(torch.int32)          # (the uint32 bits, as int32)
+        queries.view(torch.int32)[:, 4] = self._ignore_bits(ignore_body)
         raw = self.closest_records(queries)
         f = raw.view(torch.float32).reshape(n, 12)
         u = raw.view(torch.int32).reshape(n, 12).to(torch.int64) & 0xFFFFFFFF
@@ -958,9 +876,7 @@ class World:
                 q[:, 7] = 1.0
             else:
                 q[:, 4:8] = torch.as_tensor(rotations, dtype=torch.float32, device=self.dev).reshape(-1, 4)
-        ign = 0xFFFFFFFF if ignore_body is None else ignore_body
-        ign = torch.as_tensor(ign, dtype=torch.int64, device=self.dev)
-        qi[:, 11] = (((ign & 0xFFFFFFFF) ^ 0x80000000) - 0x80000000).to(torch.int32)          # (the uint32 bits, as int32)
+        qi[:, 11] = self._ignore_bits(ignore_body)
         return q, n
 
     def _overlap_lists(self, records, q, n, capacity, size):
