@@ -2224,7 +2224,7 @@ static int collide_impl(nh_context* ctx, nh_ActiveBodies* active_bodies, nh_Cont
 				NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->own_aabb_min, sizeof(float4) * (size_t)C + 64u));
 				NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->own_aabb_max, sizeof(float4) * (size_t)C + 64u));
 				NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->own_ctag, sizeof(uint32_t) * (size_t)C + 64u));
-				ctx->own_capacity = C; ss.ahead_ready = false;
+				ctx->own_capacity = C; ss.ahead_ready = false; ss.own_current = false;
 			}
 			xf = ctx->own_xf; aabb_min = ctx->own_aabb_min; aabb_max = ctx->own_aabb_max; ctag = ctx->own_ctag;
 			// XFORM AHEAD: the solver of the step before this one -- same nh_step call, plain form -- has written all of that for the dynamic bodies' colliders; this step
@@ -2251,7 +2251,7 @@ static int collide_impl(nh_context* ctx, nh_ActiveBodies* active_bodies, nh_Cont
 			          colliders->spheres.transforms, colliders->spheres.data, colliders->spheres.tags, nsph,
 			          xf, aabb_min, aabb_max, ctag, (uint4*)nullptr, 0u, ctx->fat_box, 0u,
 			          movers ? ctx->fat_gen : (uint8_t*)nullptr, ctx->fat_esc_mark, ctx->fat_esc_list, ctx->fat_moved_list, ctx->collide_seq, bodies->idle_counters, B, ctx->step_parity,
-			          sleepers ? ctx->still_awake : (uint8_t*)nullptr, (sleepers && ss.substep > 0u && !ctx->step_hook && !ss.no_sleeper_skip) ? 1u : 0u);          // (the narrowphase's `sleeper_skip` below)
+			          sleepers ? ctx->still_awake : (uint8_t*)nullptr, (sleepers && ss.substep > 0u && ss.own_current && !ctx->step_hook && !ss.no_sleeper_skip) ? 1u : 0u);          // (the narrowphase's `sleeper_skip` below)
 			// (sleepers ahead: the static world's share of the scene bounds holds the sleepers' -- a step with a k_xform<true> and a narrowphase of its own may be the one in
 			// which somebody falls asleep without failing anything, so every such step of a world with sleepers takes the map again before lanes work ahead on it)
 			if (sleepers && !ahead_step) ss.ahead_map_ok = false;
@@ -2288,8 +2288,10 @@ static int collide_impl(nh_context* ctx, nh_ActiveBodies* active_bodies, nh_Cont
 			// form, or somebody may be asleep)
 			if (movers) ss.appended_pairs = true;
 			const bool local = sleepers || ss.appended_pairs;
-			// (sleepers form inside an nh_step call, not its first sub-step: what was asleep when the sub-step before this one looked and is asleep now has not moved)
-			const uint32_t sleeper_skip = (sleepers && ss.substep > 0u && !ctx->step_hook && !ss.no_sleeper_skip) ? 1u : 0u;
+			// (sleepers form inside an nh_step call, not its first sub-step, and the sub-step before this one wrote own_* in the same form (nh_internal.h: own_current):
+			// what was asleep when that one looked and is asleep now has not moved)
+			const uint32_t sleeper_skip = (sleepers && ss.substep > 0u && ss.own_current && !ctx->step_hook && !ss.no_sleeper_skip) ? 1u : 0u;
+			ss.own_current = sleepers;          // (this step's k_xform<true> has written the arrays and the marks -- or the last solver's lanes did, on top of a sleepers-form step's: ahead_ready)
 #define NH_NARROW_STILL(SPHERES, NAME, GRIDMAX) do { if (local) NH_LAUNCH(ctx, NAME, (k_narrowphase<SPHERES, true, true>), nh_grid_for(pair_cap, 256, GRIDMAX), 256, st, ctx->fat_pairs, xf, ctag, \
 				          colliders->boxes.data, colliders->spheres.data, nbox, raw_data, raw_feature, pair_cap, 0u, ctx->sort_keys_by_position, rec, (uint32_t*)nullptr, \
 				          (const uint32_t*)nullptr, (const uint32_t*)nullptr, ctx->step_parity, 0u, ctx->fat_pair_capacity, aabb_min, aabb_max, gen, ctx->lay_rank, ctx->cnt_sorted, ctx->body_rec, ctx->collide_seq, ctx->still_delta, delta_scan ? 1u : 0u, sc_count, 0u, ctx->sc_undo, sleeper_skip); \
@@ -2326,7 +2328,7 @@ static int collide_impl(nh_context* ctx, nh_ActiveBodies* active_bodies, nh_Cont
 	ctx->still.pair_ready = false; ctx->still.pair_step = false; ctx->still.early_verdict = false; ctx->still.pair_world_bad = false; ctx->still.pair_world_ok = false; ctx->still.pair_owned_seq = 0u;          // (another layout: whether every kept pair is some body's own is found out again)
 	// The solver reads the caller's cache arrays and this nh_collide lays the dense contact list out -- whatever still steps kept by slot goes home first
 	{ int rc = nh_still_export_cache(ctx); if (rc) return rc; }
-	ctx->still.ahead_ready = false; ctx->still.ahead_plain = false;
+	ctx->still.ahead_ready = false; ctx->still.ahead_plain = false; ctx->still.own_current = false;          // (a full step writes the arena's arrays, not own_*)
 	if (!no_islands) ctx->still.ahead_map_ok = false;          // (sleepers ahead: the static world's share of the scene bounds holds the sleepers' -- and who sleeps may change in a full step)
 	ctx->still.contacts_stale = false; ctx->still.slots_current = false; ctx->still.views_sleepers = false; ctx->still.appended_pairs = false;          // (a full step writes the contact list, the sleeping pairs and the active list itself)
 	NH_LAUNCH(ctx, "collide_begin", k_collide_begin, begin_grid, 256, st, C, B, parent, set_active, ctx->deg, bodies->idle_counters, ctx->step_parity, coarse_parent, coarse_active, no_islands ? 1u : 0u, block_top,

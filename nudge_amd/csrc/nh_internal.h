@@ -297,6 +297,12 @@ struct nh_StillStep {
 	uint32_t sleep_backoff_len, sleep_run;          // how long the form is left alone after a failure (8 steps, doubled up to 64 by failures in quick succession), pair steps in sleepers form since the last one
 	uint32_t sleep_last_active, sleep_stable, sleep_backoff;      // the active count of the latest confirmed sleepers-form step, how many in a row reported it, steps until the form may be tried again
 	bool no_sleeper_skip;           // option "no_sleeper_skip": the sleepers form does everything for every collider / pair / wave, asleep or not (A/B, tests)
+	// WHO WROTE own_* LAST.  Skipping a sleeper's collider / pair keeps what is on file for it in own_xf / own_aabb_* / own_ctag (and the marks in own_aabb_max.w): that is
+	// only the sleeper's pose NOW if the sub-step immediately before this one, in the same nh_step call, was itself a still step in sleepers form (its k_xform<true>, or the
+	// lanes that worked ahead for it, wrote the arrays; what they left alone was already that form's).  Set where such a step is launched; cleared by a full step
+	// (collide_impl), a failed one (still_forget_failed), nh_bodies_changed, the end of nh_step and a re-allocation of the buffers -- a body moved from outside, an interlude
+	// of full steps or fresh memory never meets the skip.
+	bool own_current;
 	bool views_sleepers;            // sleepers-form still steps have run since the caller's active list / sleeping pairs were last written by a full step
 	bool sleep_pairs_current, active_current;       // ... and those two views have been exported since the last such step
 	void note_failure() { hold = (1u << fail_level) - 1u; if (fail_level < 6u) ++fail_level; good_run = 0; }
@@ -343,6 +349,7 @@ struct nh_context {
 	// while the solver runs: what it launches next queues up behind the solver instead of behind a copy and a wake-up on an idle GPU (26 us of a 550 us step).
 	uint32_t* h_early;             // pinned, NH_COUNTER_WORDS + 16 words; nullptr: could not be had, the host copies
 	bool no_early_counts;          // option "no_early_counts" (A/B, tests): the copy behind the solver, as before
+	bool no_listed_lookup;         // option "no_listed_lookup" (A/B, tests): the warm-start lookup always walks every contact (k_cache_lookup), never the list of general ones
 	uint64_t early_reads, early_fallbacks;      // round trips answered by the solver's first thread / by the copy after all (the stream ran dry without the word)
 	int last_hip_error;
 	// timing

@@ -39,6 +39,9 @@ struct nh_partition {
 	// scratch: two flag / scan arrays of body_capacity + 1 words, scan temporaries, sort buffers, a staging copy of the body records for the compaction
 	uint32_t* flag[2]; uint32_t* scan_tmp; uint32_t* sort_a; uint32_t* sort_b; uint32_t* sort_va; uint32_t* sort_vb; uint32_t* sort_hist;
 	nh_FullRecord* stage;
+	// where each body slot's boxes / spheres start among the dynamic colliders (exclusive scans of nbx / nsp, body_capacity + 1 words): written by
+	// nh_partition_unpack_ghosts and read by k_xform_ghosts on every step until the next refresh -- NOT scratch, so the checks that use flag[] between refreshes leave it alone
+	uint32_t* col_start[2];
 	nh_PartDev* d; nh_PartDev* h;
 	bool leavers_flagged;
 	// optional transport for the PER-STEP halo (nh_partition_set_transport): an RCCL communicator and the five RCCL entry points, handed in by the host as plain
@@ -283,6 +286,7 @@ extern "C" int nh_partition_create(nh_partition** out, nh_context* ctx, const nh
 	          hipMalloc((void**)&p->reach, sizeof(float) * cap) == hipSuccess &&
 	          hipMalloc((void**)&p->list[0], sizeof(uint32_t) * cap) == hipSuccess && hipMalloc((void**)&p->list[1], sizeof(uint32_t) * cap) == hipSuccess &&
 	          hipMalloc((void**)&p->flag[0], sizeof(uint32_t) * (cap + 2u)) == hipSuccess && hipMalloc((void**)&p->flag[1], sizeof(uint32_t) * (cap + 2u)) == hipSuccess &&
+	          hipMalloc((void**)&p->col_start[0], sizeof(uint32_t) * (cap + 2u)) == hipSuccess && hipMalloc((void**)&p->col_start[1], sizeof(uint32_t) * (cap + 2u)) == hipSuccess &&
 	          hipMalloc((void**)&p->scan_tmp, sizeof(uint32_t) * (2u * NH_SORT_GRID + 64u)) == hipSuccess &&
 	          hipMalloc((void**)&p->sort_a, sizeof(uint32_t) * cap) == hipSuccess && hipMalloc((void**)&p->sort_b, sizeof(uint32_t) * cap) == hipSuccess &&
 	          hipMalloc((void**)&p->sort_va, sizeof(uint32_t) * cap) == hipSuccess && hipMalloc((void**)&p->sort_vb, sizeof(uint32_t) * cap) == hipSuccess &&
@@ -317,7 +321,7 @@ extern "C" void nh_partition_destroy(nh_partition* p) {
 	hipSetDevice(p->ctx->device);
 	hipStreamSynchronize(p->ctx->stream);
 	for (int side = 0; side < 2; ++side) { if (p->step_out[side]) hipFree(p->step_out[side]); if (p->step_in[side]) hipFree(p->step_in[side]); }
-	void* bufs[] = { p->shape, p->cxf, p->tag, p->nbx, p->nsp, p->reach, p->list[0], p->list[1], p->flag[0], p->flag[1], p->scan_tmp, p->sort_a, p->sort_b, p->sort_va, p->sort_vb, p->sort_hist, p->stage, p->d, p->ghost_ref,
+	void* bufs[] = { p->shape, p->cxf, p->tag, p->nbx, p->nsp, p->reach, p->list[0], p->list[1], p->flag[0], p->flag[1], p->col_start[0], p->col_start[1], p->scan_tmp, p->sort_a, p->sort_b, p->sort_va, p->sort_vb, p->sort_hist, p->stage, p->d, p->ghost_ref,
 	                 p->loop_out, p->loop_in, p->loop_idx, p->split_list, p->split_count, p->split_mask };
 	for (void* b : bufs) if (b) hipFree(b);
 	if (p->split_stream) { hipStreamSynchronize(p->split_stream); hipStreamDestroy(p->split_stream); }
@@ -495,8 +499,8 @@ extern "C" int nh_partition_unpack_ghosts(nh_partition* p, nh_BodyData* bodies, 
 	// colliders: the static ones stay, then one per dynamic body slot (owned, then ghosts) -- boxes and spheres each compacted in slot order
 	NH_LAUNCH(ctx, "part_reset", k_part_reset, 1, 1, p->d);
 	NP_LAUNCH("part_flag_kinds", k_part_flag_kinds, at, at, p->nbx, p->nsp, p->flag[0], p->flag[1]);
-	nh_scan2_u32(ctx, p->flag[0], p->flag[0], &p->d->kinds[0], p->flag[1], p->flag[1], &p->d->kinds[1], &p->d->zero, at + 1u, p->scan_tmp);
-	NP_LAUNCH("part_write_colliders", k_part_write_colliders, at, at, p->flag[0], p->flag[1], part_cols(p),
+	nh_scan2_u32(ctx, p->flag[0], p->col_start[0], &p->d->kinds[0], p->flag[1], p->col_start[1], &p->d->kinds[1], &p->d->zero, at + 1u, p->scan_tmp);
+	NP_LAUNCH("part_write_colliders", k_part_write_colliders, at, at, p->col_start[0], p->col_start[1], part_cols(p),
 	          p->cfg.n_static_box, p->cfg.box_capacity, colliders->boxes.tags, colliders->boxes.data, colliders->boxes.transforms,
 	          p->cfg.n_static_sph, p->cfg.sphere_capacity, colliders->spheres.tags, colliders->spheres.data, colliders->spheres.transforms, p->d);
 	int rc = part_read_back(p);
@@ -909,7 +913,7 @@ static void part_xform_ghosts(nh_partition* p, hipStream_t stream) {
 	const nh_ColliderData* cd = p->step_args->colliders;
 	const uint32_t n_ghost = p->ghost_in[0] + p->ghost_in[1], first = p->n_owned + 1u;
 	hipLaunchKernelGGL(k_xform_ghosts, dim3(nh_grid_for(n_ghost, 256, 256)), dim3(256), 0, stream, ctx->d_state, first, bodies->count, bodies->transforms, bodies->idle_counters,
-	                   p->nbx, p->nsp, p->flag[0], p->flag[1], p->cfg.n_static_box, p->cfg.n_static_sph, cd->boxes.count,
+	                   p->nbx, p->nsp, p->col_start[0], p->col_start[1], p->cfg.n_static_box, p->cfg.n_static_sph, cd->boxes.count,
 	                   cd->boxes.transforms, cd->boxes.data, cd->spheres.transforms, cd->spheres.data,
 	                   reinterpret_cast<float4*>(ctx->own_xf), ctx->own_aabb_min, ctx->own_aabb_max, ctx->fat_box, ctx->step_parity ^ 1u, ctx->collide_seq + 1u);
 }

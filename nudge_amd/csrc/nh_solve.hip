@@ -2344,8 +2344,8 @@ extern "C" int nh_read_cached_impulses(nh_context* ctx, const nh_ContactCache* c
 static void materialize_lookup(nh_context* ctx, nh_ContactImpulseData* d, const nh_BodyPair* bodies = nullptr, const uint8_t* body_class = nullptr, const uint32_t* general_list = nullptr, uint32_t general = 0u) {
 	if (!d->lookup_pending) return;
 	d->lookup_pending = false;
-	if (general_list && general != 0u && (uint64_t)general * 16u < d->capacity) {
-		NH_LAUNCH(ctx, "cache_lookup", k_cache_lookup_listed, nh_grid_for(general, 256, 4096), 256, ctx->d_state, general_list, d->tags, d->features, d->ctags, d->cfeatures, d->cdata, d->data);
+	if (general_list && general != 0u && (uint64_t)general * 16u < d->capacity && !ctx->no_listed_lookup) {
+		NH_LAUNCH(ctx, "cache_lookup_listed", k_cache_lookup_listed, nh_grid_for(general, 256, 4096), 256, ctx->d_state, general_list, d->tags, d->features, d->ctags, d->cfeatures, d->cdata, d->data);
 		return;
 	}
 	NH_LAUNCH(ctx, "cache_lookup", k_cache_lookup, nh_grid_for(d->capacity, 256, 16384), 256, ctx->d_state, d->tags, d->features, d->ctags, d->cfeatures, d->cdata, d->data, bodies, body_class);
@@ -3578,7 +3578,7 @@ int nh_still_verdict_now(nh_context* ctx) {
 static int still_forget_failed(nh_context* ctx, bool advanced, uint32_t voided) {
 	nh_StillStep& ss = ctx->still;
 	ss.verdict.pending = false;
-	ss.active = false; ss.resolved = false; ss.setup_d = nullptr; ss.ok_next = false; ss.ahead_ready = false;
+	ss.active = false; ss.resolved = false; ss.setup_d = nullptr; ss.ok_next = false; ss.ahead_ready = false; ss.own_current = false;
 	ss.note_failure();
 	if (ss.sleepers) {
 		// (sleepers ahead: somebody fell asleep, most likely.  One sleeper now and then costs the form eight steps; failures in quick succession -- a world dozing off in a
@@ -3673,7 +3673,7 @@ extern "C" int nh_step(nh_context* ctx, const nh_StepArgs* a, uint32_t steps) {
 		    (rc = nh_advance(ctx, a->active_bodies, a->bodies, a->time_step))) { result = rc; break; }
 		++i;
 	}
-	ss.pipelined = false; ss.more_steps = false; ss.ahead_ready = false; ss.ahead_map_ok = false; ss.steps_left = 0u; ss.substep = 0u;
+	ss.pipelined = false; ss.more_steps = false; ss.ahead_ready = false; ss.ahead_map_ok = false; ss.steps_left = 0u; ss.substep = 0u; ss.own_current = false;
 	if (result && ss.verdict.pending) { hipEventSynchronize(ss.ev_ring[ss.verdict.slot]); ss.verdict.pending = false; }
 	return result;
 }

@@ -952,3 +952,53 @@ def test_append_contacts_through_the_resident_abi(shared_tag):
     with pytest.raises(E.NudgeError, match="capacity"):
         wa.append_contacts(np.zeros(n, dtype=S.CONTACT), np.zeros((n, 2), np.uint32), np.zeros(n, np.uint64), np.zeros(n, np.uint32))
     wa.close(); wb.close()
+
+
+@pytest.mark.parametrize("flags", [EXACT, FAST])
+def test_the_listed_cache_lookup_is_the_lookup_over_every_contact(flags):
+    """nh_read_cached_impulses defers the warm-start lookup; where the general contacts are few (16 x their number below the contact capacity, no body of the many-contact
+    class) k_cache_lookup_listed walks the list of them instead of k_cache_lookup walking every contact.  Option "no_listed_lookup" takes the second where the library
+    would have taken the first.  A small drop tile at rest with two boxes set down on their neighbours -- hundreds of simple contacts, a dozen or two general ones -- through
+    the landing and 60 steps of rest: bodies, contact impulses and cache of the two bit for bit, the listed form did run in the one and not in the other, and (exact
+    order) both are the compiled reference."""
+    scene = S.grid_tiles(1, side=12, seed=29)
+    pos = scene["body_transforms"]["position"]
+    riders = (5, 77)
+    for j in riders:
+        pos[j] = pos[j + 1] + np.float32([0.3, 2.3, 0.2])
+    a, b = E.World(scene, flags=flags), E.World(scene, flags=flags)
+    b.set_option("no_listed_lookup", 1)
+    if flags == EXACT:          # (only the exact order is compared with the compiled reference: a box without it must fail that case, not shrink it, and still run the other)
+        assert refworld.available("exact"), "oracle/_ref/libnudge_ref_exact.so did not travel to this box: the parity tests need the compiled reference"
+    ref = refworld.RefWorld(scene) if flags == EXACT else None
+    warm, steps = 120, 60
+    for w in (a, b) + ((ref,) if ref else ()):
+        w.step(warm)
+    a.enable_timing(True); b.enable_timing(True)
+    a.kernel_times(reset=True); b.kernel_times(reset=True)
+    general = []
+    for s in range(steps):
+        a.step(1); b.step(1)
+        ia, ib = a.get_contact_impulses(), b.get_contact_impulses()
+        assert len(ia) == len(ib) and P.bits_equal(ia["impulse"], ib["impulse"]), f"step {s}: contact impulses differ"
+        ga, gb = a.get_bodies(), b.get_bodies()
+        assert P.bits_equal(ga["transforms"], gb["transforms"]) and P.bits_equal(ga["momentum"], gb["momentum"]) and np.array_equal(ga["idle"], gb["idle"]), f"step {s}: bodies differ"
+        ca, cb = a.get_cache(), b.get_cache()
+        assert ca["count"] == cb["count"] and np.array_equal(ca["tags"], cb["tags"]) and np.array_equal(ca["features"], cb["features"]), f"step {s}: cache identities differ"
+        assert P.bits_equal(ca["data"]["impulse"], cb["data"]["impulse"]), f"step {s}: cached impulses differ"
+        general.append(a.counts()["general_contacts"])
+        if ref:
+            ref.step(1)
+            rb = ref.bodies()
+            assert P.bits_equal(rb["transforms"], ga["transforms"]) and P.bits_equal(rb["momentum"]["velocity"], ga["momentum"]["velocity"]), f"step {s}: differs from the reference"
+    ta, tb = a.kernel_times(), b.kernel_times()
+    c = a.counts()
+    print(f"\n[listed lookup] contacts {c['contacts']}, general {min(general)}..{max(general)}; listed launches {ta.get('cache_lookup_listed', (0.0, 0))[1]} / {tb.get('cache_lookup_listed', (0.0, 0))[1]}, "
+          f"full launches {ta.get('cache_lookup', (0.0, 0))[1]} / {tb.get('cache_lookup', (0.0, 0))[1]}")
+    assert c["error"] == 0 and b.counts()["error"] == 0
+    assert min(general) > 0 and 16 * max(general) < c["contacts"], (general, c)          # (many simple contacts, few general ones: the case the listed form is selected for)
+    assert ta.get("cache_lookup_listed", (0.0, 0))[1] >= steps and "cache_lookup_listed" not in tb and tb.get("cache_lookup", (0.0, 0))[1] >= steps, (sorted(ta), sorted(tb))
+    if ref:
+        rc, gc = ref.cache(), a.get_cache()
+        assert rc["count"] == gc["count"] and P.bits_equal(rc["data"]["impulse"], gc["data"]["impulse"])
+    a.close(); b.close()

@@ -441,3 +441,100 @@ def test_sub_steps_in_one_library_call_with_ghosts_arriving_through_the_transpor
     L.nh_partition_set_transport(q.hip, None, None, None, None, None, -1, -1)
     for p in p1 + p2:
         p.e.close()
+
+
+@pytest.mark.parametrize("overlap", [False, True])
+def test_a_quiet_refresh_between_two_library_calls_costs_the_chain_nothing(overlap):
+    """nh_partition_refresh_is_quiet between two nh_partition_step calls.  The check used to run its flag kernels in the two arrays that nh_partition_unpack_ghosts had left
+    the colliders' start offsets in, and k_xform_ghosts reads those offsets for every ghost on every sub-step that works ahead: the sentinel the flag kernels write at
+    [n_owned + 1] is the FIRST ghost's entry, so after a quiet boundary that ghost's pose went into the first owned body's collider slot, the inflated-box test compared
+    the wrong slot, and the step was replayed in full.  The replay hides the damage -- the BIT comparison below passed on that code -- so what catches it is the
+    COUNTER comparison: over the call behind the quiet boundary, replays / ahead steps / pair steps equal those of a control that plays the same recording through the
+    same two calls and never asks.  (The offsets now live in arrays of their own: nh_partition::col_start.)
+    The neighbour is a recording, as in the test above: cluster 1 is stepped one sub-step at a time through the epoch boundary at step 128, which must be QUIET on
+    every partition; partition 0 of cluster 2 plays 28 + 24 sub-steps in two library calls with the boundary's peer speed and refresh_is_quiet in between; partition 0
+    of cluster 3 is the control."""
+    import ctypes as C
+    BENCH = E.NH_FLAG_SINGLE_APPLY | E.NH_FLAG_FUSED_STEP
+    scene = S.grid_tiles(2, side=24, seed=91, lattice_cols=2)
+    clusters = [_cluster(scene, 2, epoch=64, flags=BENCH) for _ in range(3)]
+    every = [p for _, ps in clusters for p in ps]
+    for p in every:
+        p.quiet_refresh = False          # (as above: the refresh at step 64 ends the back-off of the landing)
+    for c, _ in clusters:
+        c.step(100)                      # landed and at rest; refreshes at steps 0 and 64
+    for p in every:
+        p.quiet_refresh = True
+    (c1, p1), (_, p2), (_, p3) = clusters
+    recorded, speeds = [], []
+    orig_pack, orig_speed = p1[1].step_pack, p1[1].speed_pack
+
+    def recording_pack():
+        out = orig_pack()
+        recorded.append(out[-1].clone())
+        return out
+
+    def recording_speed():
+        out = orig_speed()
+        speeds.append(out[-1].clone())
+        return out
+    p1[1].step_pack, p1[1].speed_pack = recording_pack, recording_speed
+    K0, K = 28, 24
+    before = [(int(p._hip_info().quiet_refreshes), dict(p.stats)) for p in p1]
+    c1.step(K0 + K)
+    for p, (q0, s0) in zip(p1, before):
+        assert int(p._hip_info().quiet_refreshes) == q0 + 1, "the boundary at step 128 was meant to be quiet on every partition"
+        assert all(p.stats[k] == s0[k] for k in ("refreshes", "migrated_out", "migrated_in", "cut_moves")), (s0, p.stats)
+    assert len(recorded) == K0 + K and len(speeds) == 1 and p1[0].ghost_in[+1] > 0 and recorded[0].shape[0] == p1[0].ghost_in[+1]
+
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+    GROUP = C.CFUNCTYPE(C.c_int)
+    XFER = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p)
+
+    def play(q, ask):
+        """partition 0 alone through the library's loop, the recording as its neighbour; `ask`: refresh_is_quiet at the boundary.  Counters of the second call."""
+        played = [0]
+        group = GROUP(lambda: 0)
+        send = XFER(lambda buf, count, dtype, peer, comm, stream: 0)
+
+        def recv_fn(buf, count, dtype, peer, comm, stream):
+            played[0] += 1
+            msg = recorded[played[0] - 1]
+            assert count == msg.numel()
+            return hip.hipMemcpyAsync(buf, msg.data_ptr(), count, 3, stream)          # hipMemcpyDeviceToDevice, on the library's stream
+        recv = XFER(recv_fn)
+        if overlap:
+            q.e.set_option("halo_overlap", 1)
+        L = q.e.L
+        L.nh_partition_set_transport.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_int]
+        E._check(L, L.nh_partition_set_transport(q.hip, C.c_void_p(1), C.cast(group, C.c_void_p), C.cast(group, C.c_void_p), C.cast(send, C.c_void_p), C.cast(recv, C.c_void_p), -1, 1), "set_transport")
+        q.library_steps(K0, exchange_first=True)
+        assert q.needs_refresh()
+        q.speed_pack()                                       # (the boundary as LocalCluster.step goes through it: speeds across the cut, then the question)
+        q.speed_unpack({+1: speeds[0]})
+        if ask:
+            assert q.refresh_is_quiet() is True
+        c0 = q.e.counts()
+        q.library_steps(K, exchange_first=True)
+        cb = q.e.counts()
+        assert played[0] == K0 + K
+        L.nh_partition_set_transport(q.hip, None, None, None, None, None, -1, -1)
+        assert cb["error"] == 0, cb
+        return {k: cb[k] - c0[k] for k in ("still_steps", "still_replays", "ahead_steps", "pair_steps")}
+
+    got = play(p2[0], True)
+    control = play(p3[0], False)
+    print(f"\n[quiet boundary, then {K} sub-steps in one call with {p2[0].ghost_in[+1]} ghosts] asked {got}  control {control}")
+    a = p1[0].owned_state()
+    for q in (p2[0], p3[0]):
+        b = q.owned_state()
+        assert np.array_equal(a[0], b[0])
+        assert P.bits_equal(a[1], b[1]), "transforms of the owned bodies differ"
+        assert P.bits_equal(a[2], b[2]), "momentum of the owned bodies differs"
+        assert np.array_equal(a[3], b[3])
+    for k in ("still_replays", "ahead_steps", "pair_steps"):
+        assert got[k] == control[k], (k, got, control)
+    assert got["ahead_steps"] >= K - 4 and got["pair_steps"] >= K - 6, got
+    for p in every:
+        p.e.close()

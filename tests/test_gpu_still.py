@@ -522,6 +522,289 @@ def test_sleepers_ahead_against_full_steps_through_random_wake_ups(seed):
     a.close(); c.close()
 
 
+def _half_awake(scene, worlds):
+    """A two-tile drop scene asleep, tile 0 woken by its idle counters: from here on half the world rests awake, half sleeps.  Returns the woken bodies."""
+    for w in worlds:
+        w.step(420)
+    x = scene["body_transforms"]["position"][:, 0]
+    tile0 = np.flatnonzero(x < np.median(x[1:]))
+    tile0 = tile0[tile0 > 0]
+    for w in worlds:
+        assert w.counts()["active_bodies"] == 0, "the scene was meant to be asleep"
+        idle = w.get_bodies()["idle"].copy()
+        idle[tile0] = 0
+        w.set_bodies(idle=idle)
+    return tile0
+
+
+@pytest.mark.parametrize("variant", ["into an awake body", "a few centimetres", "onto another sleeper", "into an awake body during an interlude of full steps",
+                                     "hanging over an awake body", "hanging over an awake body during an interlude of full steps"])
+def test_a_sleeper_the_caller_moves_stays_where_the_caller_put_it(variant):
+    """Inside an nh_step call a still step in sleepers form keeps what is on file for a sleeping body's collider -- world transform, box, tag, its share of the scene bounds --
+    and skips its pairs.  That is the body's pose only if the sub-step before it wrote the file in the same form.  The caller may move a body that is asleep and stays
+    asleep between two calls (transforms rewritten, idle counters as they were, nh_bodies_changed): sub-step 0 of the next call is a full step, which writes other arrays,
+    and the first still step behind it used to skip the sleeper on the strength of the pose from before the move (nh_collide.hip: `skip_asleep` / `sleeper_skip` on
+    `substep > 0` alone).  Now nh_StillStep::own_current says who wrote the file last.  Half a world awake and taking sleepers-form still steps; sleepers picked from the
+    data are (i) lifted out and set down inside the awake tile INTO an awake body at rest, box in box, (ii) moved a few centimetres aside, inside their inflated boxes,
+    (iii) set down on another sleeper, (iv) as (i) but while option no_still is on for three calls of full steps, so that the file is several steps old when still steps
+    resume; and, as (i) and (iv), left hanging above the awake bodies clear of every box, where a moved sleeper stays a set of its own.  Then calls of 2, 3, 8 and 64
+    sub-steps: the speculating library and the one with option no_sleeper_skip against the library that runs every step in full -- bodies, idle counters, contacts,
+    sleeping pairs, active list, cache, counters bit for bit -- and the speculating one did take still steps past the move.
+    What keeps (i) and (iv) right on a library WITHOUT own_current are two guards, not the flag: a sleeper in contact with an awake body makes general contacts, and
+    nh_solve.hip:2813-2814 (`ok_next` needs `general_contacts == 0`) offers no still step while they last (measured: 0 of 77, no replay); one whose box merely overlaps
+    an awake body's fails every still step in k_narrowphase's sleepers form, nh_collide.hip:1160-1165 (two dynamic bodies with a sleeping end: "not this step's
+    business").  So in (i), (iv) and (iii) the movers are taken off again after the four calls and the calls repeated: the still steps must come back.  What the flag
+    itself changes is pinned in (iii): while two sleepers overlap NO still step may be confirmed -- a library that skips the new pair on the strength of stale marks
+    confirms 71 of 77 there."""
+    scene = S.grid_tiles(2, side=16, sphere_fraction=0.5, seed=77, lattice_cols=2)
+    nb = len(scene["body_transforms"])
+    a, b, c = _world(scene, True), _world(scene, True, env=["NH_NO_SLEEPER_SKIP"]), _plain_world(scene)
+    worlds = (a, b, c)
+    _half_awake(scene, worlds)
+    c0 = a.counts()
+    for n in (40, 40):
+        for w in worlds:
+            w.step(n)
+        _same_sleepy_world(a, c, f"half awake, call of {n}"); _same_sleepy_world(b, c, f"half awake, call of {n} (skip off)")
+    cm = a.counts()
+    print(f"\n[moved sleeper: {variant}] before the move: still {cm['still_steps'] - c0['still_steps']} of 80, active {cm['active_bodies']} of {nb - 1}")
+    assert cm["still_steps"] - c0["still_steps"] > 0 and 0 < cm["active_bodies"] < nb - 1, (c0, cm)
+    bd = c.get_bodies()
+    pos, idle = bd["transforms"]["position"], bd["idle"]
+    asleep = np.flatnonzero(idle == 0xff); asleep = asleep[asleep > 0]
+    awake = np.flatnonzero(idle != 0xff); awake = awake[awake > 0]
+    assert len(asleep) >= 8 and len(awake) >= 8
+
+    def nearest_to_centre(ids, k):
+        centre = pos[ids].mean(axis=0)
+        return ids[np.argsort(((pos[ids][:, [0, 2]] - centre[[0, 2]]) ** 2).sum(axis=1), kind="stable")[:k]]
+    sph_body, rad = scene["sphere_transforms"]["body"], scene["sphere_data"]["radius"]
+    radius = np.zeros(nb, np.float32); radius[sph_body] = rad
+    if variant == "a few centimetres":
+        movers = asleep[:: max(1, len(asleep) // 5)][:5]
+        where = pos[movers] + np.float32([0.03, 0.0, 0.02])
+    elif variant == "onto another sleeper":
+        targets = nearest_to_centre(asleep, 2)          # (interior bodies of the sleeping tile)
+        movers = np.setdiff1d(asleep, targets)[[3, len(asleep) // 2]]
+        where = pos[targets] + np.float32([0.25, 0.9, 0.2])          # (half extents and radii are >= 0.5: set down INTO the target's box)
+    elif variant.startswith("into an awake body"):
+        targets = nearest_to_centre(awake, 2)          # (interior bodies of the awake tile)
+        movers = asleep[[3, len(asleep) // 2]]
+        where = pos[targets] + np.float32([0.8, 0.05, 0.5])          # (half extents and radii are >= 0.5: set down INTO the target's box, overlapping its rest position)
+    else:
+        # lifted out of the sleeping tile and left hanging over two awake bodies in the middle of the awake tile, clear of every box (half extents and radii are below 1.5)
+        targets = nearest_to_centre(awake, 2)
+        movers = asleep[[3, len(asleep) // 2]]
+        where = pos[targets] + np.float32([0.0, 4.0, 0.0])
+    home = pos[movers].copy()
+    assert len(movers) > 0 and np.all(idle[movers] == 0xff)
+    interlude = "interlude" in variant
+    if interlude:
+        a.set_option("no_still", 1); b.set_option("no_still", 1)
+    for w in worlds:
+        d = w.get_bodies()
+        t = d["transforms"].copy()
+        t["position"][movers] = where
+        w.set_bodies(transforms=t, idle=d["idle"])          # (idle counters as they are: the movers stay asleep; nh_bodies_changed is called)
+    if interlude:
+        for n in (2, 3, 2):
+            for w in worlds:
+                w.step(n)
+            _same_sleepy_world(a, c, f"{variant}: full steps, call of {n}")
+        a.set_option("no_still", 0); b.set_option("no_still", 0)
+    c1 = a.counts()
+    moved_at = a.steps_done
+    for n in (2, 3, 8, 64):
+        for w in worlds:
+            w.step(n)
+        _same_sleepy_world(a, c, f"{variant}: call of {n}"); _same_sleepy_world(b, c, f"{variant}: call of {n} (skip off)")
+    if variant == "onto another sleeper" or variant.startswith("into an awake body"):
+        cr = a.counts()
+        print(f"[moved sleeper: {variant}] while together: still {cr['still_steps'] - c1['still_steps']} of 77, replays {cr['still_replays'] - c1['still_replays']}, active {cr['active_bodies']}")
+        if variant == "onto another sleeper":
+            # (two sleepers with overlapping boxes are a set of two: every still step offered meanwhile must fail and be replayed -- 13 replayed of 77.  A library that
+            # trusts the marks on file from before the move skips the new pair and confirms 71 still steps here)
+            assert cr["still_replays"] - c1["still_replays"] > 0 and cr["still_steps"] - c1["still_steps"] == 0, (c1, cr)
+        # the movers are taken off again -- sleepers left hanging over their old places, clear of every box; the ones that woke in contact put back ON their old places, or
+        # they would fall for fifty steps -- and the calls are repeated: the still steps must come back
+        lift = np.float32([0.0, 4.0 if variant == "onto another sleeper" else 0.0, 0.0])
+        for w in worlds:
+            d = w.get_bodies()
+            t = d["transforms"].copy()
+            t["position"][movers] = home + lift
+            w.set_bodies(transforms=t, idle=d["idle"])
+        for n in (2, 3, 8, 64):
+            for w in worlds:
+                w.step(n)
+            _same_sleepy_world(a, c, f"{variant}, taken off again: call of {n}"); _same_sleepy_world(b, c, f"{variant}, taken off again: call of {n} (skip off)")
+    c2 = a.counts()
+    print(f"[moved sleeper: {variant}] after the move: still {c2['still_steps'] - c1['still_steps']} of {a.steps_done - moved_at}, replays {c2['still_replays'] - c1['still_replays']}, active {c2['active_bodies']}")
+    assert c2["error"] == 0 and c2["still_steps"] - c1["still_steps"] > 0, (c1, c2)
+    for w in worlds:
+        w.close()
+
+
+WALK_KINDS = ("idle", "shove", "teleport", "move a sleeper", "collider edit", "snapshot / restore", "append contacts", "option toggle")
+WALK_OPTIONS = ("no_pair_ahead", "no_xform_ahead", "no_sleeper_ahead", "no_sleeper_skip", "no_local_still", "no_still")
+WALK_SEEDS = 16
+_walk_done = {}          # seed -> counter deltas of a walk that passed (so that the test of the sums below does not walk again what this process has walked)
+
+
+def _walk(seed):
+    """One seeded walk (the test below says what it is); returns the speculating world's counter deltas."""
+    if seed in _walk_done:
+        return _walk_done[seed]
+    rng = np.random.default_rng(1000 + seed)
+    scene = S.grid_tiles(2, side=12, sphere_fraction=0.4, seed=200 + seed, lattice_cols=2)
+    nb = len(scene["body_transforms"])
+    nbox_static = 2
+    a, c = _world(scene, True, tag_bits=32), _plain_world(scene, tag_bits=32)          # (the appended contacts carry tags no collider has)
+    worlds = (a, c)
+    for w in worlds:
+        w.step(420)
+    _same_sleepy_world(a, c, "asleep")
+    order = np.argsort(scene["body_transforms"]["position"][1:, 0], kind="stable") + 1
+    for w in worlds:
+        idle = w.get_bodies()["idle"].copy()
+        idle[order[: (nb - 1) // 3]] = 0
+        w.set_bodies(idle=idle)
+    c0 = a.counts()
+    options = {k: 0 for k in WALK_OPTIONS}
+    kinds = list(rng.permutation(len(WALK_KINDS))) + list(rng.integers(0, len(WALK_KINDS), size=4))
+    steps = 0
+
+    def call(n, what):
+        nonlocal steps
+        for w in worlds:
+            w.step(int(n))
+        steps += int(n)
+        _same_sleepy_world(a, c, f"seed {seed}, {what}, step {steps}")
+
+    call(40, "a third awake")
+    for rnd, k in enumerate(kinds):
+        kind = WALK_KINDS[int(k)]
+        if options["no_still"]:          # (the one option that ends all speculation lasts one round)
+            options["no_still"] = 0
+            a.set_option("no_still", 0)
+        bd = c.get_bodies()
+        idle0 = bd["idle"]
+        asleep = np.flatnonzero(idle0 == 0xff); asleep = asleep[asleep > 0]
+        awake = np.flatnonzero(idle0 != 0xff); awake = awake[awake > 0]
+        if len(awake) == 0 and kind in ("shove", "teleport", "append contacts"):          # (nobody awake: these kinds wake their body first, like the shove of the walk above)
+            awake = asleep[:1]
+        what = f"round {rnd} ({kind})"
+        if kind == "idle":
+            n = int(rng.integers(1, nb // 3))
+            who = rng.choice(np.arange(1, nb), size=n, replace=False)
+            idles = rng.integers(0, 255, size=n).astype(np.uint8)
+            for w in worlds:
+                idle = w.get_bodies()["idle"].copy(); idle[who] = idles
+                w.set_bodies(idle=idle)
+        elif kind == "shove":
+            j = int(rng.choice(awake))
+            v = np.float32([rng.uniform(-1, 1), rng.uniform(0.5, 2.0), rng.uniform(-1, 1)])
+            for w in worlds:
+                d = w.get_bodies()
+                m, idle = d["momentum"].copy(), d["idle"].copy()
+                m["velocity"][j] = v; idle[j] = 0
+                w.set_bodies(momentum=m, idle=idle)
+        elif kind == "teleport":
+            j = int(rng.choice(awake))
+            off = np.float32([rng.uniform(-1.5, 1.5), rng.uniform(0.2, 1.5), rng.uniform(-1.5, 1.5)])
+            for w in worlds:
+                d = w.get_bodies()
+                t, idle = d["transforms"].copy(), d["idle"].copy()
+                t["position"][j] += off; idle[j] = min(int(idle[j]), 0xfe)
+                w.set_bodies(transforms=t, idle=idle)
+        elif kind == "move a sleeper":
+            assert len(asleep) > 0
+            j = int(rng.choice(asleep))
+            far = bool(rng.integers(0, 2))
+            tgt = int(rng.choice(np.arange(1, nb)))
+            for w in worlds:
+                d = w.get_bodies()
+                t = d["transforms"].copy()
+                if far and tgt != j:
+                    t["position"][j] = t["position"][tgt] + np.float32([0.0, 4.0, 0.0])          # (left hanging above another body, clear of its box: a set of its own, as in the test above)
+                else:
+                    t["position"][j] += np.float32([0.03, 0.0, 0.02])
+                w.set_bodies(transforms=t, idle=d["idle"])
+        elif kind == "collider edit":
+            # (the dynamic colliders follow the static slabs in the caller's arrays, one per body: half extents of a box / radius of a sphere scaled by 0.9 .. 1.1)
+            scale = np.float32(rng.uniform(0.9, 1.1))
+            nbx = len(scene["box_transforms"])
+            nsp = len(scene["sphere_transforms"])
+            sphere = nsp > 0 and bool(rng.integers(0, 2))
+            k_col = int(rng.integers(0, nsp)) if sphere else int(rng.integers(nbox_static, nbx))
+            for w in worlds:
+                w.synchronize()
+                rec = w.records("sd", 4) if sphere else w.records("xd", 16)
+                raw = np.frombuffer(rec[k_col:k_col + 1].cpu().numpy().tobytes(), dtype=np.float32).copy()
+                raw[: 1 if sphere else 3] *= scale
+                rec[k_col:k_col + 1] = w.torch.from_numpy(raw.view(np.uint8).reshape(1, -1).copy()).to(rec.device)
+                w.L.nh_bodies_changed(w.ctx)
+        elif kind == "snapshot / restore":
+            snaps = [w.snapshot() for w in worlds]
+            call(rng.integers(1, 70), what + ", between snapshot and restore")
+            for w, sn in zip(worlds, snaps):
+                w.restore(sn)
+        elif kind == "append contacts":
+            j = int(rng.choice(awake))
+            for w in worlds:
+                d = w.get_bodies()
+                if d["idle"][j] == 0xff:
+                    idle = d["idle"].copy(); idle[j] = 0
+                    w.set_bodies(idle=idle)
+                w.collide()
+                data = np.zeros(1, dtype=S.CONTACT)
+                data["position"] = d["transforms"]["position"][j] - np.float32([0.0, 0.25, 0.0])
+                data["penetration"] = 0.05
+                data["normal"] = (0.0, 1.0, 0.0)
+                data["friction"] = 0.25
+                w.append_contacts(data, np.array([[0, j]], np.uint32), np.array([0x70000 | ((0x71000 + j) << 32)], np.uint64), np.ones(1, np.uint32))
+                w.gravity(); w.read_cache(); w.setup(); w.apply(); w.update(); w.write_cache(); w.advance(); w.step_done()
+            steps += 1
+            _same_sleepy_world(a, c, f"seed {seed}, {what}, the step with the custom contact")
+        elif kind == "option toggle":
+            name = WALK_OPTIONS[int(rng.integers(0, len(WALK_OPTIONS)))]
+            options[name] ^= 1
+            a.set_option(name, options[name])
+            what += f" {name}={options[name]}"
+        for n in rng.integers(1, 71, size=3):
+            call(n, what)
+    c1 = a.counts()
+    delta = {k: c1[k] - c0[k] for k in ("still_steps", "ahead_steps", "pair_steps", "asleep_steps", "still_replays")}
+    print(f"\n[walk {seed}] {steps} steps: {delta}")
+    assert c1["error"] == 0 and c.counts()["error"] == 0
+    assert delta["still_steps"] > 0, delta
+    assert c.counts()["still_steps"] == 0
+    for w in worlds:
+        w.close()
+    _walk_done[seed] = delta
+    return delta
+
+
+@pytest.mark.parametrize("seed", range(WALK_SEEDS))
+def test_a_seeded_walk_over_what_a_host_can_do_between_two_calls(seed):
+    """Everything a host can do to a world between two nh_step calls, drawn at random, against the library that runs every step in full.  A small two-tile drop scene
+    asleep, a third of it woken; then rounds of ONE perturbation -- idle counters rewritten; a shove; an awake body teleported; a body that stays asleep moved (the test
+    above); a collider edited (half extents or radius in the caller's collider arrays, nh_bodies_changed); snapshot, a call, restore; custom contacts appended for one
+    step driven through the eight calls; one of the live options toggled (no_pair_ahead, no_xform_ahead, no_sleeper_ahead, no_sleeper_skip, no_local_still, no_still:
+    in the speculating world only) -- followed by calls of 1-70 sub-steps, each compared bit for bit: bodies, idle counters, contacts, sleeping pairs, active list, cache,
+    counters.  Every kind is drawn once per seed before any is drawn twice.  So that the walk cannot pass by never speculating: every seed takes still steps, and over the
+    sixteen seeds still, ahead, pair and asleep steps and replays all occur (the test below)."""
+    _walk(seed)
+
+
+def test_the_seeded_walks_speculate_in_every_form():
+    """Summed over the sixteen seeds of the walk above, still steps, steps that started at the narrowphase, steps that started at the solver, asleep steps and replays
+    all occur.  Seeds this process has not walked yet (a selection by name, another worker) are walked here."""
+    deltas = [_walk(seed) for seed in range(WALK_SEEDS)]
+    sums = {k: sum(d[k] for d in deltas) for k in deltas[0]}
+    print(f"\n[walk, all {WALK_SEEDS} seeds] {sums}")
+    assert all(v > 0 for v in sums.values()), sums
+
+
 def test_a_sleeper_next_to_an_awake_body_is_not_the_still_steps_business():
     """A sleeping body whose AABB overlaps an awake dynamic body's belongs to a set of more than one body (nudge.cpp:3575-3650): whether it sleeps is not local.  Such a
     step must fail as a still step and be run in full -- the world ends in the bits of the library that never speculates."""
