@@ -635,8 +635,6 @@ int nh_sort_u64(nh_context* ctx, uint64_t* keys_a, uint64_t* keys_b,
 // One-kernel-per-pass variant (see nh_util.hip).  `capacity` is a host-side upper bound of *d_count (sizes the launch);
 // `expected` a guess of it (0 = none; sizes the grid, any value is correct); `scratch` needs nh_sort_scratch_words(capacity) words.
 size_t nh_sort_scratch_words(uint32_t capacity);
-int nh_onesweep_u32_u32(nh_context* ctx, uint32_t* keys_a, uint32_t* keys_b, uint32_t* vals_a, uint32_t* vals_b,
-                         const uint32_t* d_count, uint32_t capacity, uint32_t expected, uint32_t* scratch, int begin_bit, int end_bit);
 int nh_onesweep_u64_u32_two_fields(nh_context* ctx, uint64_t* keys_a, uint64_t* keys_b, uint32_t* vals_a, uint32_t* vals_b,
                                     const uint32_t* d_count, uint32_t capacity, uint32_t expected, uint32_t* scratch, int field_bits);
 // Tag sort of st->records (key, value) pairs seeded by the previous step's result (see nh_util.hip).  Sorted data ends in keys_a / vals_a.

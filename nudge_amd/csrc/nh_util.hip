@@ -377,16 +377,6 @@ static int onesweep_impl(nh_context* ctx, K* keys_a, K* keys_b, V* vals_a, V* va
 	return sh.n & 1;      // 1: the sorted data sits in the *_b buffers
 }
 
-static os_shifts shifts_for(int begin_bit, int end_bit, os_shifts sh = os_shifts{ {}, 0 }) {
-	for (int s = begin_bit; s < end_bit && sh.n < OS_MAX_PASSES; s += 8) sh.s[sh.n++] = OS_DESC(s, 8, 0);
-	return sh;
-}
-
-int nh_onesweep_u32_u32(nh_context* ctx, uint32_t* keys_a, uint32_t* keys_b, uint32_t* vals_a, uint32_t* vals_b,
-                         const uint32_t* d_count, uint32_t capacity, uint32_t expected, uint32_t* scratch, int begin_bit, int end_bit) {
-	return onesweep_impl<uint32_t, uint32_t, true>(ctx, keys_a, keys_b, vals_a, vals_b, d_count, capacity, expected, scratch, shifts_for(begin_bit, end_bit));
-}
-
 // sorts 64-bit keys made of two `bits`-wide fields, one at bit 0 and one at bit 32, by (high field, low field): the 2 x bits
 // significant bits are consumed eight at a time as if the fields were adjacent, so 20-bit fields take 5 passes, not 6
 static os_shifts two_field_shifts(int bits) {
@@ -758,7 +748,7 @@ __global__ __launch_bounds__(256) void sc_sums(const uint32_t* __restrict__ in_a
 	}
 }
 
-__global__ __launch_bounds__(256) void sc_final(const uint32_t* __restrict__ in_a, uint32_t* __restrict__ out_a, const uint32_t* __restrict__ in_b, uint32_t* __restrict__ out_b,
+__global__ __launch_bounds__(256) void sc_final(const uint32_t* in_a, uint32_t* out_a, const uint32_t* in_b, uint32_t* out_b,      // (no __restrict__: out may be in -- nh_overlap_offsets scans in place)
                                                 const uint32_t* __restrict__ d_n, uint32_t extra, const uint32_t* __restrict__ tmp,
                                                 uint32_t* __restrict__ d_total_a, uint32_t* __restrict__ d_total_b, const uint32_t* __restrict__ d_enable) {
 	__shared__ uint32_t wsum[4];
@@ -784,12 +774,14 @@ __global__ __launch_bounds__(256) void sc_final(const uint32_t* __restrict__ in_
 	}
 	// eight consecutive items per thread: local sums, ONE workgroup scan per 2048 items and array, eight outputs
 	constexpr uint32_t SC_IPT = 8;
+	// 16-byte accesses only where every array is 16-byte aligned: nh_overlap's `offsets` need 4-byte alignment only and then go word by word
+	const bool vec = ((((uintptr_t)in_a | (uintptr_t)out_a | (uintptr_t)in_b | (uintptr_t)out_b) & 15u) == 0u);
 	for (uint32_t tile = begin; tile < end; tile += RS_TILE * SC_IPT) {
 		const uint32_t i0 = tile + threadIdx.x * SC_IPT;
 		uint32_t va[SC_IPT], vb[SC_IPT], sa = 0, sb = 0;
 #pragma unroll
 		for (uint32_t k = 0; k < SC_IPT; ++k) va[k] = vb[k] = 0u;
-		const bool full = i0 + SC_IPT <= end;           // (chunks start at multiples of 256 items and the arrays are 16-byte aligned)
+		const bool full = vec && i0 + SC_IPT <= end;    // (chunks start at multiples of 256 items)
 		if (full) {
 			const uint4 x0 = *reinterpret_cast<const uint4*>(in_a + i0), x1 = *reinterpret_cast<const uint4*>(in_a + i0 + 4);
 			va[0] = x0.x; va[1] = x0.y; va[2] = x0.z; va[3] = x0.w; va[4] = x1.x; va[5] = x1.y; va[6] = x1.z; va[7] = x1.w;
