@@ -79,7 +79,7 @@
  *      exported the views: nh_set_option(ctx, "sync_exports_views", 1) restores that contract at its old price; INTEGRATION.md.)  Any entry point outside the sample's
  *      call order between nh_collide and nh_apply_impulses turns a still step into a full one first, so everything it observes is what a full step
  *      produces.  nh_Counts.still_steps / still_replays count them.
- *      The scene queries (nh_query_build, nh_query_refit, nh_raycast, nh_spherecast, nh_raycast_all, nh_spherecast_all, nh_boxcast, nh_capsulecast, nh_overlap, nh_penetration, nh_closest) are not entry points of the step in this sense: they neither export nor settle nor turn a still step into a
+ *      The scene queries (nh_query_build, nh_query_refit, nh_raycast, nh_spherecast, nh_raycast_all, nh_spherecast_all, nh_boxcast, nh_capsulecast, nh_overlap, nh_penetration, nh_closest, nh_closest_k) are not entry points of the step in this sense: they neither export nor settle nor turn a still step into a
  *      full one, and they do not count -- see "scene queries" below.
  *
  * Threading: one context = one HIP stream = one world at a time; no global mutable state.
@@ -542,11 +542,39 @@ int nh_capsulecast(nh_context* ctx, const nh_CapsuleCast* casts, uint32_t count,
      - `reserved` of every hit is written 0.
    Returns NH_ERR_INVALID before any nh_query_build, for flags != 0, and for null or not 16-byte aligned `queries` / `hits`; count = 0 is a no-op that
    returns NH_OK.  An OBSERVER like nh_raycast (note 9): no view export, no settling of deferred gravity, no still step turned into a full one, no change
-   to nh_Counts.  Not built: the distance of a shape from the world (GJK), the k nearest colliders. */
+   to nh_Counts.  Not built: the distance of a shape from the world (GJK).  The k nearest colliders: nh_closest_k, below. */
 typedef struct nh_PointQuery { float point[3]; float max_distance; uint32_t ignore_body; uint32_t reserved[3]; } nh_PointQuery;                     /* 32 B */
 typedef struct nh_PointHit { float distance; float normal[3]; float point[3]; uint32_t body;
                              uint32_t collider; uint32_t shape; uint32_t tag; uint32_t reserved; } nh_PointHit;                                  /* 48 B */
 int nh_closest(nh_context* ctx, const nh_PointQuery* queries, uint32_t count, nh_PointHit* hits, uint32_t flags /* 0 */);
+
+/* nh_closest_k: the `k` nearest colliders to each of `count` points, nearest first -- proximity sensors, crowd and flocking neighbourhoods, "which crates
+   are within reach", candidate sets for grabbing and audio occlusion, a depenetration that needs more than the deepest collider.  The records are
+   nh_closest's (nh_PointQuery in, nh_PointHit out); `k` is one value per call, 1 .. NH_CLOSEST_K_MAX.
+     - THE CANDIDATES of query i: every box and sphere collider of the last build or refit -- those of sleeping bodies and of body 0 included -- less the
+       colliders of `ignore_body`.  A candidate's key is nh_closest's distance for that collider alone: the predicate distance d under the reach rule
+       (nh_q_point_key(d, d2), d2 the squared distance of the point from the collider's own leaf box), and it must satisfy
+       key <= max_distance.  A collider of a NaN pose is never a candidate;
+     - THE ORDER: ascending key, compared as floats; ties go to the lower combined collider index (boxes 0 .. nbox-1, then the spheres).  This is the
+       strict order nh_closest chooses by, so the answer does not depend on the tree, and a brute force that sorts all candidates gives the same bytes;
+     - THE OUTPUT: with m_i = min(k, number of candidates), hits[i*k + j] for j < m_i is the j-th candidate in that order, byte for byte the record
+       nh_closest writes for that collider alone (distance = its key, normal, point, body, collider, shape, tag, reserved = 0); hits[i*k + j] for
+       j >= m_i is nh_closest's miss record (distance = max_distance, or NaN for an invalid query).  Every byte of all count*k records is written and
+       nothing behind them; counts[i] = m_i where `counts` is not NULL;
+     - k = 1 IS nh_closest: `hits` holds exactly the bytes nh_closest writes for the same queries on the same build or refit.  PREFIX: for k < k' the
+       first k records of every query under k' are the records under k;
+     - an invalid query (non-finite point, NaN or negative max_distance) finds nothing: counts[i] = 0 and k miss records of distance NaN.
+       max_distance = +inf finds the k nearest anywhere; max_distance = 0 only colliders that contain or touch the point, the deepest first.
+   Returns NH_ERR_INVALID before any nh_query_build, for flags != 0, for k = 0 or k > NH_CLOSEST_K_MAX, for `queries` or `hits` null or not 16-byte
+   aligned, for `counts` not 4-byte aligned, and for count >= 2^30; count = 0 is a no-op that returns NH_OK.  An OBSERVER like nh_closest (note 9): no
+   view export, no settling of deferred gravity, no still step turned into a full one, no change to nh_Counts; it never allocates and never waits, it
+   only launches on the context's stream.
+   One lane per query keeps its list of k (key, index) pairs in LDS and prunes the walk at the k-th key so far (why that is exact).
+   NOT MEASURED YET, and not run on a GPU yet: no GPU could be had while this was built.  tools/nearest_rates.py is the measurement (the landed config-2 world of
+   1,004,524 colliders, 1 M queries, k = 1 .. 32 beside nh_closest and beside the nh_overlap detour in one run -> profiles/nearest_rates.log). */
+#define NH_CLOSEST_K_MAX 32u
+int nh_closest_k(nh_context* ctx, const nh_PointQuery* queries, uint32_t count, uint32_t k,
+                 uint32_t* counts /* count words, or NULL */, nh_PointHit* hits /* count * k records */, uint32_t flags /* 0 */);
 
 /* nh_overlap: which colliders of the LAST nh_query_build touch each of `count` query shapes -- explosion radii, trigger volumes, "is this spot free".
    Query shapes (nh_OverlapQuery):

@@ -686,6 +686,36 @@ NH_HD bool nh_q_closer(float d, uint32_t c, float max_d, float bd, uint32_t bc) 
 	return bc == 0xffffffffu || d < bd || (d == bd && c < bc);
 }
 
+// ---- the k nearest (nh_closest_k): a bounded list of (key, combined index) in nh_q_closer's strict order ---------------------------------------------
+// The list lives in storage of the caller's with a stride: slot j at base[j * stride] (the kernel's lists lie slot-major in LDS, stride = the workgroup's
+// size; a host array has stride 1).  `held` <= k entries are in use, the nearest first.
+struct alignas(8) nh_QNear { float key; uint32_t c; };
+
+// Offer the candidate (key, c).  Refused: a key that is not <= max_d (NaN included); with the list full, a candidate that does not beat the last entry;
+// a candidate that is already held -- equal key and equal index: the order is strict, so such an entry sits directly in front of the place the candidate
+// would take, and a walk may meet a collider again that a seed has proposed.  Otherwise the entries behind its place move back one slot (the last one
+// out, where the list is full) and it goes in.  True when the list changed.
+NH_HD bool nh_q_nearest_insert(nh_QNear* base, uint32_t stride, uint32_t k, uint32_t* held, float key, uint32_t c, float max_d) {
+	if (!(key <= max_d)) return false;
+	const uint32_t m = *held;
+	uint32_t at = m;                          // the candidate's place: behind every entry it does not beat
+	while (at > 0u) {
+		const nh_QNear e = base[(at - 1u) * stride];
+		if (!nh_q_closer(key, c, max_d, e.key, e.c)) break;
+		--at;
+	}
+	if (at == k) return false;
+	if (at > 0u) {
+		const nh_QNear e = base[(at - 1u) * stride];
+		if (e.key == key && e.c == c) return false;
+	}
+	for (uint32_t j = m < k ? m : k - 1u; j > at; --j) base[j * stride] = base[(j - 1u) * stride];
+	nh_QNear in; in.key = key; in.c = c;
+	base[at * stride] = in;
+	if (m < k) *held = m + 1u;
+	return true;
+}
+
 // ---- penetration (nh_penetration): the least translation that frees a query shape from one collider it overlaps ----------------------------------------
 // Every function returns the unit normal n, from the collider towards the query shape, and depth >= +0: the query moved by depth * n touches the
 // collider, and no shorter translation in any direction does (a ball adds its radius to the depth of what it inflates; the depth of two

@@ -573,6 +573,99 @@ __global__ __launch_bounds__(256) void k_q_closest(const nh_PointQuery* __restri
 	}
 }
 
+// ---- the k nearest ------------------------------------------------------------------------------------------------------------------------------
+// One lane per query on nh_q_walk, as k_q_closest; what a lane keeps is not one best candidate but the bounded ordered list of nh_query.h
+// (nh_q_nearest_insert: (key, combined index), nh_q_closer's order, a candidate met twice goes in once).
+//   list   in LDS, slot-major: entry j of lane l at lds[j * blockDim.x + l], 8 bytes -- a wave's access to one slot is contiguous, and no register
+//          array is indexed dynamically (it would go to scratch).  Dynamic shared memory of blockDim.x * k * 8 bytes, the block size by k:
+//              k  1 ..  8   256 lanes   at most 16 KiB
+//              k  9 .. 16   128 lanes   at most 16 KiB
+//              k 17 .. 32    64 lanes   at most 16 KiB
+//          so a workgroup never takes more than a quarter of the 64 KiB it may have, and a CU's 160 KiB hold ten of the largest.
+//   bound  bd, in a register: max_distance while fewer than k are held, the k-th key once the list is full.  A leaf whose key is not <= bd is
+//          dropped by that one compare without touching LDS (equality goes on: a tie can still win by index).  The node test is k_q_closest's:
+//          skip iff d2 > 0 && sqrtf(d2) > bd.
+//   exact  bd is always the k-th key of a SUBSET of the candidates (or max_distance), hence at least the final k-th key K.  A collider of the
+//          answer has key <= K, and its key is at least sqrtf(d2) of its own leaf box (nh_q_point_key); every ancestor's d2 is at most the
+//          leaf's (nh_query.h).  So sqrtf(d2) <= K <= bd at every ancestor of a winner: none is ever skipped, whatever the order of the walk.
+//   seed   k_q_closest's, the window widened to NH_Q_SEED + k / 2 leaves on either side (k = 1: the same leaves): the bound is usually the k-th
+//          key of a neighbourhood of p before the walk starts.  The walk meets those leaves again and nh_q_nearest_insert drops them, so the
+//          seed changes the work, never the bytes.  Compiled out by -DNH_Q_CLOSEST_K_NO_SEED (tools/nearest_rates.py measures both).
+//   out    the list holds (key, index) only: nh_q_point_box / nh_q_point_sphere run again for the m held colliders -- the same bits -- and each
+//          record leaves as three 16-byte stores, then the k - m miss records, then counts[i] = m.
+static inline uint32_t nh_q_nearest_block(uint32_t k) { return k <= 8u ? 256u : k <= 16u ? 128u : 64u; }
+
+__global__ __launch_bounds__(256) void k_q_closest_k(const nh_PointQuery* __restrict__ queries, uint32_t count, uint32_t k, uint32_t* __restrict__ counts,
+                                                     nh_PointHit* __restrict__ hits, const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec,
+                                                     const uint64_t* __restrict__ keys, const nh_QCtl* __restrict__ ctl, uint32_t n, uint32_t nbox) {
+	extern __shared__ nh_QNear q_near[];
+	const uint32_t stride = blockDim.x;
+	nh_QNear* const list = q_near + threadIdx.x;
+	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
+		const float4* qp = reinterpret_cast<const float4*>(queries + i);
+		const float4 q0 = qp[0], q1 = qp[1];
+		const nh_f3 p = nh_make3(q0.x, q0.y, q0.z);
+		const float max_d = q0.w;
+		const uint32_t ignore = __float_as_uint(q1.x);
+		const bool ok = nh_q_finite(p) && max_d >= 0.0f;       // (+inf is a valid max_distance; NaN is not)
+		float bd = max_d;
+		uint32_t held = 0u;
+		const bool walk = ok && n;
+		// a leaf of squared box distance d2, for the seed and the walk alike
+		const auto leaf = [&](uint32_t c, const nh_QRec& q, float d2) {
+			const nh_QShape s = nh_q_unpack(q);
+			const nh_QPoint h = c < nbox ? nh_q_point_box(p, s.p, s.q, s.h) : nh_q_point_sphere(p, s.p, s.h.x);
+			const float key = nh_q_point_key(h.d, d2);
+			if (!(key <= bd)) return false;
+			if (nh_q_nearest_insert(list, stride, k, &held, key, c, max_d) && held == k) bd = list[(k - 1u) * stride].key;
+			return false;
+		};
+#ifndef NH_Q_CLOSEST_K_NO_SEED
+		if (walk) {
+			const nh_f3 smin = nh_make3(nh_float_unflip(ctl->kmin[0]), nh_float_unflip(ctl->kmin[1]), nh_float_unflip(ctl->kmin[2]));
+			const nh_f3 smax = nh_make3(nh_float_unflip(ctl->kmax[0]), nh_float_unflip(ctl->kmax[1]), nh_float_unflip(ctl->kmax[2]));
+			const float scale = nh_morton_scale(smin, smax);
+			const nh_f3 pc = nh_make3(fminf(fmaxf(p.x, smin.x), smax.x), fminf(fmaxf(p.y, smin.y), smax.y), fminf(fmaxf(p.z, smin.z), smax.z));
+			const uint64_t key = nh_morton_of(pc, scale, smin * scale);
+			uint32_t lo = 0u, hi = n;
+			while (lo < hi) {
+				const uint32_t mid = (lo + hi) >> 1;
+				if (keys[mid] < key) lo = mid + 1u; else hi = mid;
+			}
+			const uint32_t win = NH_Q_SEED + k / 2u;
+			const uint32_t j0 = lo > win ? lo - win : 0u, j1 = n - lo > win ? lo + win : n;
+			for (uint32_t j = j0; j < j1; ++j) {
+				const float4 na = nodes[n - 1u + j].a, nb = nodes[n - 1u + j].b;
+				const uint32_t c = __float_as_uint(na.w) & ~NH_Q_LEAF;
+				const nh_QRec q = rec[c];
+				if (__float_as_uint(q.a.w) == ignore) continue;
+				leaf(c, q, nh_q_point_node(nh_make3(na.x, na.y, na.z), nh_make3(nb.x, nb.y, nb.z), p));
+			}
+		}
+#endif
+		nh_q_walk(nodes, rec, walk ? 0u : NH_Q_NONE, ignore,
+			[&](nh_f3 lo, nh_f3 hi, float& d2) { d2 = nh_q_point_node(lo, hi, p); return !(d2 > 0.0f && sqrtf(d2) > bd); }, leaf);
+		float4* hp = reinterpret_cast<float4*>(hits + (size_t)i * k);
+		for (uint32_t j = 0u; j < held; ++j, hp += 3) {
+			const nh_QNear e = list[j * stride];
+			const nh_QRec q = rec[e.c];
+			const nh_QShape s = nh_q_unpack(q);
+			const nh_QPoint h = e.c < nbox ? nh_q_point_box(p, s.p, s.q, s.h) : nh_q_point_sphere(p, s.p, s.h.x);
+			const uint4 id = nh_q_identity(e.c, nbox, q);
+			hp[0] = make_float4(e.key, h.n.x, h.n.y, h.n.z);
+			hp[1] = make_float4(h.x.x, h.x.y, h.x.z, __uint_as_float(id.x));
+			hp[2] = make_float4(__uint_as_float(id.y), __uint_as_float(id.z), __uint_as_float(id.w), 0.0f);
+		}
+		const float md = ok ? max_d : __uint_as_float(0x7fc00000u);
+		for (uint32_t j = held; j < k; ++j, hp += 3) {
+			hp[0] = make_float4(md, 0.0f, 0.0f, 0.0f);
+			hp[1] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(NH_Q_NONE));
+			hp[2] = make_float4(__uint_as_float(NH_Q_NONE), __uint_as_float(NH_SHAPE_NONE), __uint_as_float(NH_Q_NONE), 0.0f);
+		}
+		if (counts) counts[i] = held;
+	}
+}
+
 // ---- overlap ---------------------------------------------------------------------------------------------------------------------------------
 // nh_overlap is a chain of launches with kernel boundaries as the only hand-offs; no atomic decides where a record goes:
 //   k_q_overlap<false, false>  one lane per query: nh_q_walk (stackless, escape links) with the query's padded world AABB as the node test, the exact
@@ -960,6 +1053,22 @@ extern "C" int nh_closest(nh_context* ctx, const nh_PointQuery* queries, uint32_
 	NH_HIP_CHECK(ctx, hipSetDevice(ctx->device));
 	nh_QueryState* q = ctx->query;
 	NH_LAUNCH(ctx, "q_closest", k_q_closest, nh_grid_for(count, 256, 1u << 20), 256, queries, count, hits, q->nodes, q->rec, q->keys, q->ctl, q->n, q->nbox);
+	return NH_OK;
+}
+
+// One launch with the lists' LDS sized by k (the table at k_q_closest_k); no allocation, no wait.
+extern "C" int nh_closest_k(nh_context* ctx, const nh_PointQuery* queries, uint32_t count, uint32_t k, uint32_t* counts, nh_PointHit* hits, uint32_t flags) {
+	if (!ctx || !ctx->query || !ctx->query->built) return NH_ERR_INVALID;
+	if (flags != 0u || k == 0u || k > NH_CLOSEST_K_MAX || count >= (1u << 30)) return NH_ERR_INVALID;
+	if (count == 0u) return NH_OK;
+	if (!queries || !hits || (((uintptr_t)queries | (uintptr_t)hits) & 15u) || ((uintptr_t)counts & 3u)) return NH_ERR_INVALID;    // (records are moved as 16-byte words)
+	NH_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+	nh_QueryState* q = ctx->query;
+	const uint32_t block = nh_q_nearest_block(k);
+	if (ctx->timing) nh_timer_begin(ctx, "q_closest_k");
+	hipLaunchKernelGGL(k_q_closest_k, dim3(nh_grid_for(count, block, 1u << 20)), dim3(block), block * k * sizeof(nh_QNear), ctx->stream,
+	                   queries, count, k, counts, hits, q->nodes, q->rec, q->keys, q->ctl, q->n, q->nbox);
+	if (ctx->timing) nh_timer_end(ctx);
 	return NH_OK;
 }
 

@@ -43,7 +43,7 @@ EXPORTS = [
     "nh_partition_top_speed", "nh_partition_set_peer_speeds", "nh_partition_refresh_is_quiet", "nh_partition_mark_ghosts", "nh_partition_pack_deltas", "nh_partition_unpack_deltas",
     "nh_partition_pack_momentum", "nh_partition_unpack_momentum", "nh_partition_exchange_iteration", "nh_partition_unpack_ghosts", "nh_partition_pack_step", "nh_partition_unpack_step", "nh_partition_choose_cut", "nh_partition_set_cut",
     "nh_partition_set_transport", "nh_partition_exchange_step", "nh_partition_step", "nh_partition_transport_check", "nh_partition_transport_result", "nh_set_first_ghost_body",
-    "nh_query_build", "nh_query_refit", "nh_query_stats", "nh_raycast", "nh_overlap", "nh_penetration", "nh_spherecast", "nh_raycast_all", "nh_spherecast_all", "nh_boxcast", "nh_capsulecast", "nh_closest",
+    "nh_query_build", "nh_query_refit", "nh_query_stats", "nh_raycast", "nh_overlap", "nh_penetration", "nh_spherecast", "nh_raycast_all", "nh_spherecast_all", "nh_boxcast", "nh_capsulecast", "nh_closest", "nh_closest_k",
 ]
 HALO_RECORD_BYTES = 64
 
@@ -269,6 +269,7 @@ def lib():
         L.nh_boxcast.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
         L.nh_capsulecast.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
         L.nh_closest.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
+        L.nh_closest_k.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]
         L.nh_overlap.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
         L.nh_penetration.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
         # (an older build of the library, loaded through NUDGE_HIP_LIBRARY for an A/B, has no all-hits casts: World.raycast_all then raises AttributeError)
@@ -810,11 +811,8 @@ class World:
                "nh_closest")
         return hits
 
-    def closest(self, points, max_distance=float("inf"), ignore_body=None, synchronize=False):
-        """The nearest collider to each of `points` ((n, 3)) in the last query_build(), within `max_distance` (a number or n values; inf: anywhere),
-        skipping the colliders of `ignore_body` (None, a body index, or n of them).  Returns a dict of device tensors: distance (n; negative inside),
-        normal (n, 3; out of the collider), point (n, 3; on its surface), body, collider, shape, tag (n, int64; 0xffffffff = none) and `raw`, the
-        nh_PointHit records.  Nothing waits for the device unless `synchronize`."""
+    def _point_queries(self, points, max_distance, ignore_body):
+        """The nh_PointQuery records (n x 8 float32 words on the device) of closest() / closest_k()'s arguments: (records, n)."""
         torch = self.torch
         p = torch.as_tensor(points, dtype=torch.float32, device=self.dev).reshape(-1, 3)
         n = p.shape[0]
@@ -822,10 +820,49 @@ class World:
         queries[:, 0:3] = p
         queries[:, 3] = torch.as_tensor(max_distance, dtype=torch.float32, device=self.dev)
         queries.view(torch.int32)[:, 4] = self._ignore_bits(ignore_body)
+        return queries, n
+
+    def closest(self, points, max_distance=float("inf"), ignore_body=None, synchronize=False):
+        """The nearest collider to each of `points` ((n, 3)) in the last query_build(), within `max_distance` (a number or n values; inf: anywhere),
+        skipping the colliders of `ignore_body` (None, a body index, or n of them).  Returns a dict of device tensors: distance (n; negative inside),
+        normal (n, 3; out of the collider), point (n, 3; on its surface), body, collider, shape, tag (n, int64; 0xffffffff = none) and `raw`, the
+        nh_PointHit records.  Nothing waits for the device unless `synchronize`."""
+        torch = self.torch
+        queries, n = self._point_queries(points, max_distance, ignore_body)
         raw = self.closest_records(queries)
         f = raw.view(torch.float32).reshape(n, 12)
         u = raw.view(torch.int32).reshape(n, 12).to(torch.int64) & 0xFFFFFFFF
         out = dict(distance=f[:, 0], normal=f[:, 1:4], point=f[:, 4:7], body=u[:, 7], collider=u[:, 8], shape=u[:, 9], tag=u[:, 10], raw=raw)
+        if synchronize:
+            torch.cuda.current_stream(self.dev).synchronize()
+        return out
+
+    def closest_k_records(self, queries, k, counts=None, hits=None):
+        """nh_closest_k on records already laid out as nh_PointQuery: `queries` a contiguous device tensor of count x 32 bytes (any dtype).  Returns
+        (counts, hits): the count words as an int32 device tensor (`counts`, or a new one) and the count x k x 48-byte uint8 device tensor of
+        nh_PointHit records (`hits`, or a new one), the k of a query nearest first."""
+        torch = self.torch
+        n = queries.numel() * queries.element_size() // 32
+        if counts is None:
+            counts = torch.empty(n, dtype=torch.int32, device=self.dev)
+        if hits is None:
+            hits = torch.empty((n, max(int(k), 0), 48), dtype=torch.uint8, device=self.dev)
+        _check(self.L, self.L.nh_closest_k(self.ctx, C.c_void_p(queries.data_ptr() if n else 0), n, k, C.c_void_p(counts.data_ptr() if n else 0),
+                                           C.c_void_p(hits.data_ptr() if n else 0), 0), "nh_closest_k")
+        return counts, hits
+
+    def closest_k(self, points, k, max_distance=float("inf"), ignore_body=None, synchronize=False):
+        """The `k` (1 .. 32) nearest colliders to each of `points` ((n, 3)) in the last query_build(), nearest first; `max_distance` and `ignore_body`
+        are closest()'s.  Returns a dict of device tensors: count (n, int64: how many of the k slots of a point hold a collider), distance (n, k),
+        normal (n, k, 3), point (n, k, 3), body, collider, shape, tag ((n, k), int64; 0xffffffff in the slots behind `count`) and `raw`, the
+        nh_PointHit records (n x k x 48 bytes).  Nothing waits for the device unless `synchronize`."""
+        torch = self.torch
+        queries, n = self._point_queries(points, max_distance, ignore_body)
+        counts, raw = self.closest_k_records(queries, k)
+        f = raw.view(torch.float32).reshape(n, k, 12)
+        u = raw.view(torch.int32).reshape(n, k, 12).to(torch.int64) & 0xFFFFFFFF
+        out = dict(count=counts.to(torch.int64), distance=f[..., 0], normal=f[..., 1:4], point=f[..., 4:7], body=u[..., 7], collider=u[..., 8],
+                   shape=u[..., 9], tag=u[..., 10], raw=raw)
         if synchronize:
             torch.cuda.current_stream(self.dev).synchronize()
         return out
