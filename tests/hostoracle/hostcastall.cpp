@@ -1,27 +1,18 @@
-// hostcastall.cpp -- CPU build of the all-hits casts (nh_raycast_all / nh_spherecast_all of include/nudge_hip.h), the oracle of the GPU's chain.
-// Built with g++ -ffp-contract=off (tests/hostcastall_util.py), so that every function returns the device's bits; loaded with ctypes.
+// hostcastall.cpp -- CPU build of the all-hits casts (nh_raycast_all / nh_spherecast_all of include/nudge_hip.h), the oracle of the GPU's chain
+// (tests/hostcastall_util.py).
 //   hc_castall  per cast, a brute force over all colliders in index order with the header's exact rules -- invalid casts, ignore_body, the reach rule
 //               for r > 0 on the leaf box rebuilt as the build stores it, 0 <= t <= max_t -- then std::stable_sort by t over the index-ordered hits,
 //               the offsets by an exclusive scan, the capacity prefix of whole segments and the overflow marker; on several threads
-#include <stdint.h>
-#include <math.h>
 #include <algorithm>
-#include <thread>
-#include <vector>
-#include "../../include/nudge_hip.h"
-#include "../../nudge_amd/csrc/nh_query.h"
+#include "oracle.h"
 
-// 12 words per collider (tests/hostquery_util.py REC, nh_query.hip's nh_QRec): position, bits(body), rotation, half extents | radius (x3), bits(tag)
-struct Rec { float p[3]; uint32_t body; float q[4]; float h[3]; uint32_t tag; };
 struct Hit { float t; nh_f3 n; uint32_t c; };
-
-static bool finite(float x) { return (nh_asuint(x) & 0x7f800000u) != 0x7f800000u; }
 
 // the hits of one cast, ordered; `out` == nullptr: the count alone
 template <bool SWEEP>
 static uint32_t cast_one(const Rec* rec, uint32_t n, uint32_t nbox, const void* cast, std::vector<Hit>* out) {
 	const nh_Ray& ray = *static_cast<const nh_Ray*>(cast);          // (nh_SphereCast's first 32 bytes are nh_Ray's)
-	const nh_f3 o = nh_make3(ray.origin[0], ray.origin[1], ray.origin[2]), d = nh_make3(ray.direction[0], ray.direction[1], ray.direction[2]);
+	const nh_f3 o = v3(ray.origin), d = v3(ray.direction);
 	const float r = SWEEP ? static_cast<const nh_SphereCast*>(cast)->radius : 0.0f;
 	bool ok = finite(o.x) && finite(o.y) && finite(o.z) && finite(d.x) && finite(d.y) && finite(d.z);
 	if (SWEEP) ok = ok && finite(r) && !(r < 0.0f);
@@ -33,8 +24,8 @@ static uint32_t cast_one(const Rec* rec, uint32_t n, uint32_t nbox, const void* 
 		const Rec& e = rec[c];
 		if (e.body == ray.ignore_body) continue;
 		const bool box = c < nbox;
-		const nh_f3 p = nh_make3(e.p[0], e.p[1], e.p[2]), h = nh_make3(e.h[0], e.h[1], e.h[2]);
-		const nh_quat q = { e.q[0], e.q[1], e.q[2], e.q[3] };
+		const nh_f3 p = rec_pos(e), h = rec_half(e);
+		const nh_quat q = rec_rot(e);
 		float t0 = 0.0f;
 		// the reach rule: the collider's own leaf box must be entered, and the hit is no earlier than that entry
 		if (SWEEP && r > 0.0f && !nh_q_leaf_entry(o, inv, w, p, q, h, box, t0)) continue;
@@ -52,37 +43,19 @@ template <bool SWEEP>
 static uint64_t castall(const Rec* rec, uint32_t n, uint32_t nbox, const uint8_t* casts, uint32_t count, uint32_t* offsets, nh_RayHit* hits,
                         uint32_t capacity, uint32_t threads) {
 	const size_t stride = SWEEP ? sizeof(nh_SphereCast) : sizeof(nh_Ray);
-	if (threads < 1) threads = 1;
 	std::vector<uint32_t> counts(count);
-	{
-		std::vector<std::thread> pool;
-		for (uint32_t k = 0; k < threads; ++k)
-			pool.emplace_back([&, k]() { for (uint32_t i = k; i < count; i += threads) counts[i] = cast_one<SWEEP>(rec, n, nbox, casts + stride * i, nullptr); });
-		for (auto& t : pool) t.join();
-	}
+	parallel(count, threads, [&](uint32_t i) { counts[i] = cast_one<SWEEP>(rec, n, nbox, casts + stride * i, nullptr); });
 	uint64_t total = 0;
 	for (uint32_t i = 0; i < count; ++i) { offsets[i] = (uint32_t)total; total += counts[i]; }
 	offsets[count] = (uint32_t)total;
 	if (total >= 0xffffffffull) { offsets[count] = 0xffffffffu; return total; }      // the marker: no record at all
 	if (!hits || !capacity) return total;
-	std::vector<std::thread> pool;
-	for (uint32_t k = 0; k < threads; ++k)
-		pool.emplace_back([&, k]() {
-			std::vector<Hit> found;
-			for (uint32_t i = k; i < count; i += threads) {
-				if (!(offsets[i + 1] <= capacity) || !counts[i]) continue;      // whole segments that fit
-				found.clear();
-				cast_one<SWEEP>(rec, n, nbox, casts + stride * i, &found);
-				for (uint32_t j = 0; j < found.size(); ++j) {
-					const Hit& f = found[j];
-					nh_RayHit& out = hits[offsets[i] + j];
-					out.t = f.t; out.normal[0] = f.n.x; out.normal[1] = f.n.y; out.normal[2] = f.n.z;
-					out.body = rec[f.c].body; out.collider = f.c < nbox ? f.c : f.c - nbox; out.shape = f.c < nbox ? NH_SHAPE_BOX : NH_SHAPE_SPHERE;
-					out.tag = rec[f.c].tag;
-				}
-			}
-		});
-	for (auto& t : pool) t.join();
+	parallel(count, threads, [&](uint32_t i) {
+		if (!(offsets[i + 1] <= capacity) || !counts[i]) return;      // whole segments that fit
+		std::vector<Hit> found;
+		cast_one<SWEEP>(rec, n, nbox, casts + stride * i, &found);
+		for (uint32_t j = 0; j < found.size(); ++j) write_ray_hit(hits[offsets[i] + j], rec, nbox, found[j].c, found[j].t, found[j].n);
+	});
 	return total;
 }
 

@@ -1,0 +1,36 @@
+// hostoverlap.cpp -- CPU build of the overlap predicates of nudge_amd/csrc/nh_query.h, the oracle of the GPU's nh_overlap (tests/hostoverlap_util.py).
+//   ho_overlap   offsets and records of a batch of sphere and box queries by brute force over all colliders, with the header's exact semantics
+//                (ignore_body, invalid queries, capacity prefix, the 2^32 - 1 marker), on several threads: oracle.h's overlap_all
+//   hc_overlap   the same with capsule queries valid, as nh_overlap has them now; to ho_overlap a capsule query is invalid
+//   ho_*         the three predicates alone (the capsule's: hostcapsule.cpp)
+#include "oracle.h"
+
+static uint64_t overlap(const Rec* rec, uint32_t n, uint32_t nbox, const nh_OverlapQuery* queries, uint32_t count, uint32_t* offsets, nh_OverlapHit* hits,
+                        uint32_t capacity, uint32_t threads, bool capsules) {
+	return overlap_all(rec, n, nbox, queries, count, offsets, hits, capacity, threads, capsules,
+	                   [=](nh_OverlapHit& o, const nh_OverlapQuery&, uint32_t c) { write_who(o, rec, nbox, c); });
+}
+
+extern "C" {
+
+uint64_t ho_overlap(const Rec* rec, uint32_t n, uint32_t nbox, const nh_OverlapQuery* queries, uint32_t count, uint32_t* offsets, nh_OverlapHit* hits,
+                    uint32_t capacity, uint32_t threads) {
+	return overlap(rec, n, nbox, queries, count, offsets, hits, capacity, threads, false);
+}
+
+uint64_t hc_overlap(const Rec* rec, uint32_t n, uint32_t nbox, const nh_OverlapQuery* queries, uint32_t count, uint32_t* offsets, nh_OverlapHit* hits,
+                    uint32_t capacity, uint32_t threads) {
+	return overlap(rec, n, nbox, queries, count, offsets, hits, capacity, threads, true);
+}
+
+int ho_sphere_sphere(const float c[3], float r, const float p[3], float R) { return nh_q_overlap_sphere_sphere(v3(c), r, v3(p), R) ? 1 : 0; }
+
+int ho_sphere_box(const float c[3], float r, const float p[3], const float q[4], const float h[3]) {
+	return nh_q_overlap_sphere_box(v3(c), r, v3(p), q4(q), v3(h)) ? 1 : 0;
+}
+
+int ho_box_box(const float ca[3], const float qa[4], const float ha[3], const float cb[3], const float qb[4], const float hb[3]) {
+	return nh_q_overlap_box_box(v3(ca), q4(qa), v3(ha), v3(cb), q4(qb), v3(hb)) ? 1 : 0;
+}
+
+}

@@ -1,32 +1,18 @@
 """ctypes access to tests/hostsim/libhostsim.so (CPU build of the kernels' per-item device functions)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
+import hostlib as H
+from hostlib import p as _p
 from nudge_amd import scenes as S
 
-_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostsim")
-_LIB = None
+_SRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostsim", "hostsim.cpp")
 
 
 def lib():
-    global _LIB
-    if _LIB is None:
-        so = os.path.join(_DIR, "libhostsim.so")
-        src = os.path.join(_DIR, "hostsim.cpp")
-        hdrs = [os.path.join(_DIR, "..", "..", "nudge_amd", "csrc", h) for h in ("nh_math.h", "nh_narrowphase.h", "nh_solver.h")]
-        newest = max(os.path.getmtime(p) for p in [src] + hdrs)
-        if not os.path.exists(so) or os.path.getmtime(so) < newest:
-            subprocess.check_call(["g++", "-O2", "-mavx2", "-mfma", "-ffp-contract=off", "-fPIC", "-shared",
-                                   "-std=c++14", src, "-o", so])
-        _LIB = C.CDLL(so)
-    return _LIB
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
+    return H.build("hostsim", [_SRC], extra_flags=("-mavx2", "-mfma"))
 
 
 def collide(body_transforms, scene, cap=1 << 20):

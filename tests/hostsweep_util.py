@@ -1,63 +1,36 @@
-"""ctypes access to tests/hostsweep/libhostsweep.so: the sphere-cast arithmetic of nudge_amd/csrc/nh_query.h built for the host with
-g++ -ffp-contract=off -- the same bits as the device -- and a brute-force nh_spherecast over all colliders with the header's exact rules, the oracle
-of the GPU's tree traversal.  The per-collider records come from tests/hostquery_util.records()."""
+"""ctypes access to the sphere-cast oracle of tests/hostoracle/hostsweep.cpp (built by tests/hostlib.py): the sphere-cast arithmetic of
+nudge_amd/csrc/nh_query.h with the device's bits, and a brute-force nh_spherecast over all colliders with the header's exact rules, the oracle of the
+GPU's tree traversal."""
 import ctypes as C
-import os
-import subprocess
-
 import numpy as np
 
-import hostquery_util as Q
+import hostlib as H
+from hostlib import records      # noqa: F401
+from hostquery_util import _hit5
 from nudge_amd import engine as E
 
-_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostsweep")
-_LIB = None
-records = Q.records
-
-
-def lib():
-    global _LIB
-    if _LIB is None:
-        so = os.path.join(_DIR, "libhostsweep.so")
-        src = os.path.join(_DIR, "hostsweep.cpp")
-        hdrs = [os.path.join(_DIR, "..", "..", "nudge_amd", "csrc", h) for h in ("nh_math.h", "nh_query.h")] + [os.path.join(_DIR, "..", "..", "include", "nudge_hip.h")]
-        newest = max(os.path.getmtime(p) for p in [src] + hdrs)
-        if not os.path.exists(so) or os.path.getmtime(so) < newest:
-            subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++14", "-pthread", src, "-o", so])
-        L = C.CDLL(so)
-        L.hs_spherecast.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_uint32]
-        L.hs_sweep_box.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.hs_sweep_sphere.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_float, C.c_void_p]
-        _LIB = L
-    return _LIB
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
-
-
-def _f(a, n):
-    return np.ascontiguousarray(a, dtype=np.float32).reshape(n)
+_SIG = {
+    "hs_spherecast": ([C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_uint32], None),
+    "hs_sweep_box": ([C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], None),
+    "hs_sweep_sphere": ([C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_float, C.c_void_p], None),
+}
+lib = H.oracle(_SIG)
 
 
 def spherecast(rec, nbox, casts, only=-1, threads=None):
     """nh_RayHit records (E.RAY_HIT) of `casts` (E.SPHERE_CAST) by brute force over `rec`; `only` >= 0: that one collider (combined index) alone."""
     casts = np.ascontiguousarray(casts, dtype=E.SPHERE_CAST)
     hits = np.zeros(len(casts), dtype=E.RAY_HIT)
-    rec = np.ascontiguousarray(rec, dtype=Q.REC)
-    lib().hs_spherecast(_p(rec), len(rec), nbox, _p(casts), len(casts), _p(hits), int(only), threads or min(os.cpu_count() or 1, 16))
+    rec = np.ascontiguousarray(rec, dtype=H.REC)
+    lib().hs_spherecast(H.p(rec), len(rec), nbox, H.p(casts), len(casts), H.p(hits), int(only), H.threads(threads))
     return hits
 
 
 def sweep_box(o, d, r, p, q, h):
     """(t, normal, hit) of nh_q_sweep_box."""
-    out = np.zeros(5, dtype=np.float32)
-    lib().hs_sweep_box(_p(_f(o, 3)), _p(_f(d, 3)), C.c_float(r), _p(_f(p, 3)), _p(_f(q, 4)), _p(_f(h, 3)), _p(out))
-    return float(out[0]), out[1:4].copy(), bool(out[4])
+    return _hit5(lib().hs_sweep_box, H.p(H.f(o, 3)), H.p(H.f(d, 3)), C.c_float(r), H.p(H.f(p, 3)), H.p(H.f(q, 4)), H.p(H.f(h, 3)))
 
 
 def sweep_sphere(o, d, r, c, R):
     """(t, normal, hit) of nh_q_sweep_sphere."""
-    out = np.zeros(5, dtype=np.float32)
-    lib().hs_sweep_sphere(_p(_f(o, 3)), _p(_f(d, 3)), C.c_float(r), _p(_f(c, 3)), C.c_float(R), _p(out))
-    return float(out[0]), out[1:4].copy(), bool(out[4])
+    return _hit5(lib().hs_sweep_sphere, H.p(H.f(o, 3)), H.p(H.f(d, 3)), C.c_float(r), H.p(H.f(c, 3)), C.c_float(R))

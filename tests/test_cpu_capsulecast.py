@@ -16,6 +16,7 @@ import hostcapsule_util as H                 # noqa: E402
 import hostoverlap_util as O                 # noqa: E402
 import hostquery_util as Q                   # noqa: E402
 import hostsweep_util as W                   # noqa: E402
+from query_util import unit_quats as _unit_quats      # noqa: E402
 from nudge_amd import engine as E           # noqa: E402
 from nudge_amd import scenes as S           # noqa: E402
 
@@ -52,11 +53,6 @@ def _mat(q):
     return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - s * z), 2 * (x * z + s * y)],
                      [2 * (x * y + s * z), 1 - 2 * (x * x + z * z), 2 * (y * z - s * x)],
                      [2 * (x * z - s * y), 2 * (y * z + s * x), 1 - 2 * (x * x + y * y)]])
-
-
-def _unit_quats(rng, n):
-    q = rng.normal(size=(n, 4))
-    return (q / np.linalg.norm(q, axis=1, keepdims=True)).astype(np.float32)
 
 
 def _ternary(f, lo, hi, iters):

@@ -16,21 +16,12 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import hostcastall_util as A                 # noqa: E402
 import hostquery_util as Q                   # noqa: E402
 import hostsweep_util as W                   # noqa: E402
+from query_util import SMALL, bounds as _bounds      # noqa: E402
 from nudge_amd import engine as E           # noqa: E402
 from nudge_amd import scenes as S           # noqa: E402
 
 NONE = 0xFFFFFFFF
 SENTINEL = 0xA5
-
-# the small scenes of the existing query tests (tests/test_gpu_query.py SMALL)
-SMALL = {
-    "pile": lambda: S.pile(256, 64, seed=1),
-    "compound": lambda: S.compound(150, seed=6),
-    "stacks": lambda: S.stacks(64, 3, seed=5),
-    "grid_tiles": lambda: S.grid_tiles(4, side=16, sphere_fraction=0.5, seed=2),
-    "ball_pit": lambda: S.ball_pit(6, 6, 6, seed=4),
-}
-
 
 def test_both_entry_points_are_exported_with_their_prototypes():
     assert {"nh_raycast_all", "nh_spherecast_all"} <= set(E.EXPORTS)
@@ -48,11 +39,6 @@ def test_both_entry_points_are_exported_with_their_prototypes():
     src = open(os.path.join(ROOT, "nudge_amd", "engine.py")).read()
     proto = "argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]"
     assert f"L.nh_raycast_all.{proto}" in src and f"L.nh_spherecast_all.{proto}" in src
-
-
-def _bounds(rec):
-    p = rec["p"][np.isfinite(rec["p"]).all(axis=1)].astype(np.float64)
-    return p.min(axis=0), p.max(axis=0)
 
 
 def _rays(rng, n, rec):

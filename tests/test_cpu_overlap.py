@@ -12,6 +12,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import hostoverlap_util as O                 # noqa: E402
+from query_util import unit_quats as _quats  # noqa: E402
 from nudge_amd import engine as E           # noqa: E402
 from nudge_amd import scenes as S           # noqa: E402
 
@@ -83,11 +84,6 @@ def _clear(f):
     """The float64 answer where it does not change when every size grows or shrinks by DELTA (relative), else None."""
     lo, hi = f(1.0 - DELTA), f(1.0 + DELTA)
     return lo if lo == hi else None
-
-
-def _quats(rng, n):
-    q = rng.normal(size=(n, 4))
-    return (q / np.linalg.norm(q, axis=1, keepdims=True)).astype(np.float32)
 
 
 def test_predicates_agree_with_float64_closed_forms_on_random_poses():

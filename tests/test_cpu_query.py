@@ -12,6 +12,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import hostquery_util as Q                   # noqa: E402
+from query_util import unit_quats as _unit_quats      # noqa: E402
 from nudge_amd import engine as E           # noqa: E402
 from nudge_amd import scenes as S           # noqa: E402
 
@@ -83,11 +84,6 @@ def _sphere64(o, d, c, r):
     if t < 0:
         return False, 0.0, None
     return True, t, (o + t * d - c) / r
-
-
-def _unit_quats(rng, n):
-    q = rng.normal(size=(n, 4))
-    return (q / np.linalg.norm(q, axis=1, keepdims=True)).astype(np.float32)
 
 
 def _rays_at(rng, n, centres):

@@ -13,6 +13,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import hostoverlap_util as O                 # noqa: E402
 import hostquery_util as Q                   # noqa: E402
 import hostsweep_util as W                   # noqa: E402
+from query_util import unit_quats as _unit_quats      # noqa: E402
 from nudge_amd import engine as E           # noqa: E402
 from nudge_amd import scenes as S           # noqa: E402
 
@@ -92,11 +93,6 @@ def _sweep_box64(o, d, r, p, R, h):
     x = ol + best * dl
     v = x - np.clip(x, -h, h)
     return True, best, R @ (v / np.linalg.norm(v)), feat
-
-
-def _unit_quats(rng, n):
-    q = rng.normal(size=(n, 4))
-    return (q / np.linalg.norm(q, axis=1, keepdims=True)).astype(np.float32)
 
 
 def _casts_at(rng, n, centres):

@@ -23,6 +23,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
 
 from nudge_amd import scenes as S                  # noqa: E402
 from nudge_amd import engine as E                  # noqa: E402
+import hostlib                                     # noqa: E402
 import parity_util as P                            # noqa: E402
 from oracle import refworld                        # noqa: E402
 
@@ -50,7 +51,7 @@ def _tiled_reference(scene, n_tiles, steps):
         sub, body_map = S.extract_tile(scene, t)
         worlds.append(refworld.RefWorld(sub, max_contacts=6 * len(sub["body_transforms"])))
         maps.append(body_map)
-    refworld.step_tiles(worlds, steps, threads=os.cpu_count() or 1, ftz=False)
+    refworld.step_tiles(worlds, steps, threads=hostlib.threads(), ftz=False)
     return worlds, maps
 
 

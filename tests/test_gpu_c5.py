@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import hostlib                                     # noqa: E402
 import parity_util as P                            # noqa: E402
 from nudge_amd import engine as E                  # noqa: E402
 from nudge_amd import partition as PT              # noqa: E402
@@ -123,7 +124,7 @@ def test_c5_sixteen_million_boxes_in_eight_partitions_vs_single_world_and_refere
         sub, body_map = S.extract_tile(g, t)
         worlds.append(refworld.RefWorld(sub, max_contacts=6 * len(sub["body_transforms"])))
         maps.append(body_map)
-    refworld.step_tiles(worlds, steps, threads=os.cpu_count() or 1, ftz=False)
+    refworld.step_tiles(worlds, steps, threads=hostlib.threads(), ftz=False)
     errs, worst_p, worst_v = [], 0.0, 0.0
     worst_p1 = 0.0
     for t, wr, body_map in zip(sample, worlds, maps):

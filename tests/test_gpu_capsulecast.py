@@ -16,6 +16,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import hostcapsule_util as H                 # noqa: E402
 import hostoverlap_util as O                 # noqa: E402
 import hostquery_util as Q                   # noqa: E402
+from query_util import unit_quats as _unit_quats      # noqa: E402
 from test_gpu_overlap import SENTINEL, _gpu, _queries                                       # noqa: E402
 from test_gpu_query import OBSERVED, SMALL, _bounds, _rays, _same_stepped_world, _upload      # noqa: E402
 from nudge_amd import engine as E           # noqa: E402
@@ -26,11 +27,6 @@ pytestmark = pytest.mark.gpu
 NONE = 0xFFFFFFFF
 FUSED = E.NH_FLAG_SINGLE_APPLY | E.NH_FLAG_FUSED_STEP
 SHAPES = ((0.05, 0.5), (0.5, 0.5), (1.0, 2.0), (0.0, 1.0))         # (radius, half height)
-
-
-def _unit_quats(rng, n):
-    q = rng.normal(size=(n, 4))
-    return (q / np.linalg.norm(q, axis=1, keepdims=True)).astype(np.float32)
 
 
 def _casts(rays, radius, half_height, rotation=None):

@@ -15,6 +15,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import hostoverlap_util as O                 # noqa: E402
 import parity_util as P                      # noqa: E402
+from query_util import SMALL, bounds as _bounds, unit_quats as _unit_quats      # noqa: E402
 from nudge_amd import engine as E           # noqa: E402
 from nudge_amd import scenes as S           # noqa: E402
 
@@ -23,16 +24,6 @@ pytestmark = pytest.mark.gpu
 NONE = 0xFFFFFFFF
 FUSED = E.NH_FLAG_SINGLE_APPLY | E.NH_FLAG_FUSED_STEP
 SENTINEL = 0xA5
-
-
-def _bounds(rec):
-    p = rec["p"][np.isfinite(rec["p"]).all(axis=1)].astype(np.float64)
-    return p.min(axis=0), p.max(axis=0)
-
-
-def _unit_quats(rng, n):
-    q = rng.normal(size=(n, 4))
-    return (q / np.linalg.norm(q, axis=1, keepdims=True)).astype(np.float32)
 
 
 def _queries(rng, n, rec, kind, scale=1.0):
@@ -125,15 +116,6 @@ def _check_world(w, scene, rng, n, what):
         _, total = _same(w, rec, _queries(rng, n, rec, kind), f"{what} / {kind}")
         totals.append(total)
     return totals
-
-
-SMALL = {
-    "pile": lambda: S.pile(256, 64, seed=1),
-    "compound": lambda: S.compound(150, seed=6),
-    "stacks": lambda: S.stacks(64, 3, seed=5),
-    "grid_tiles": lambda: S.grid_tiles(4, side=16, sphere_fraction=0.5, seed=2),
-    "ball_pit": lambda: S.ball_pit(6, 6, 6, seed=4),
-}
 
 
 @pytest.mark.parametrize("name", sorted(SMALL))

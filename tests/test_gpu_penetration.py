@@ -14,6 +14,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import hostpen_util as H                     # noqa: E402
 import hostquery_util as Q                   # noqa: E402
+from query_util import unit_quats as _unit_quats      # noqa: E402
 from test_gpu_query import OBSERVED, SMALL, _bounds, _same_stepped_world, _upload      # noqa: E402
 from nudge_amd import engine as E           # noqa: E402
 from nudge_amd import scenes as S           # noqa: E402
@@ -24,11 +25,6 @@ NONE = 0xFFFFFFFF
 FUSED = E.NH_FLAG_SINGLE_APPLY | E.NH_FLAG_FUSED_STEP
 SENTINEL = 0xA5
 KINDS = ("sphere", "box", "capsule", "mixed")
-
-
-def _unit_quats(rng, n):
-    q = rng.normal(size=(n, 4))
-    return (q / np.linalg.norm(q, axis=1, keepdims=True)).astype(np.float32)
 
 
 def _queries(rng, n, rec, kind, scale=1.0):
