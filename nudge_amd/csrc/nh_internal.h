@@ -473,21 +473,32 @@ struct nh_context {
 	nh_StateStream stream_state;
 	struct nh_QueryState* query;   // scene queries (nh_query.hip): the hierarchy of the last nh_query_build; nullptr until the first
 };
-int nh_stream_after_advance(nh_context* ctx);          // nh_advance -> state streaming
+int nh_stream_after_advance(nh_context* ctx);          // nh_advance -> state streaming (nh_context.hip)
 void nh_query_free(nh_context* ctx);                   // nh_destroy -> the scene query's buffers (nh_query.hip)
 
+// ---- functions used across the .hip files: each is declared here, once, and defined in the file named behind it --------------------------------------
+// (NH_LOCAL: a helper of the library's own that is not part of what libnudge_hip.so exports)
+#define NH_LOCAL __attribute__((visibility("hidden")))
 // Runs work that an earlier call deferred; every entry point that reads or writes momentum / impulses calls it first.
 // `in_sequence`: the caller is the next call of the sample's step (gravity, read, setup, apply): a still step stays speculative across it; every other
 // entry point first turns a still step that has not been confirmed yet into a full one (nh_still_abandon)
-int nh_flush_pending(nh_context* ctx, bool keep_gravity = false, bool in_sequence = false);
-int nh_still_abandon(nh_context* ctx);
+int nh_flush_pending(nh_context* ctx, bool keep_gravity = false, bool in_sequence = false);          // nh_solve.hip
+int nh_still_abandon(nh_context* ctx);                // nh_schedule.hip
 // The caller's view of what still steps keep by slot -- the dense contact list and the contact cache in tag order -- brought up to date (every entry point outside
 // the sample's call order that hands the arrays to the caller: nh_export_views, nh_append_contacts, nh_contact_impulses_device -- NOT nh_read_counts / nh_synchronize)
-int nh_still_sync_outputs(nh_context* ctx, uint32_t what = 7u /* NH_VIEW_ALL */);
-int nh_still_export_cache(nh_context* ctx);
-int nh_still_undo_drops(nh_context* ctx);
-void nh_stream_void_advance(nh_context* ctx);
-int nh_still_verdict_now(nh_context* ctx);            // nh_step: the pending verdict of the last still step, waited for: 0 = it happened, 1 = it did not
+int nh_still_sync_outputs(nh_context* ctx, uint32_t what = 7u /* NH_VIEW_ALL */);          // nh_step.hip
+int nh_still_export_cache(nh_context* ctx);           // nh_cache.hip
+int nh_still_undo_drops(nh_context* ctx);             // nh_cache.hip
+void nh_stream_void_advance(nh_context* ctx);         // nh_context.hip
+int nh_still_verdict_now(nh_context* ctx);            // nh_step.hip -- nh_step: the pending verdict of the last still step, waited for: 0 = it happened, 1 = it did not
+NH_LOCAL void nh_still_note_movers(nh_context* ctx, const nh_DevState* h, uint32_t seq = 0u);          // nh_step.hip
+int nh_asleep_remember(nh_context* ctx);              // nh_collide.hip (asleep steps: nh_AsleepState)
+int nh_asleep_verify(nh_context* ctx, const nh_BodyData* bodies, const nh_ColliderData* colliders);      // nh_collide.hip
+int nh_still_collide_again(nh_context* ctx);          // nh_collide.hip
+int nh_still_view_contacts(nh_context* ctx);          // nh_collide.hip: the dense contact list laid out again from the slots (k_gather_contacts, view only)
+struct nh_ContactImpulseData;
+NH_LOCAL void nh_run_cull(nh_context* ctx, nh_ContactImpulseData* d, uint32_t sleeping_on_host);          // nh_cache.hip
+NH_LOCAL void nh_materialize_lookup(nh_context* ctx, nh_ContactImpulseData* d, const nh_BodyPair* bodies = nullptr, const uint8_t* body_class = nullptr, const uint32_t* general_list = nullptr, uint32_t general = 0u);          // nh_cache.hip
 #define NH_INTERNAL_STILL_FAILED (-1000)      // (never leaves the library) first_apply -> nh_step: the still step before this one failed, run both again
 #define NH_DELTA_MAX 256u
 #define NH_GEN_SHIFT 24u             // kept pairs carry the generation stamps of their two colliders above the 24-bit collider index (nh_collide.hip, "7. re-insertion")
@@ -496,7 +507,7 @@ int nh_still_verdict_now(nh_context* ctx);            // nh_step: the pending ve
 #define NH_BODY_REC_IS_A 0x80000000u
 struct nh_Record { uint32_t body_a, body_b, overflow, count; };          // one per collider pair that reached the narrowphase (nh_collide.hip)
 #define NH_REC_SLEEPING 0x80000000u
-void nh_counts_from_mirror(nh_context* ctx, nh_Counts* out);
+void nh_counts_from_mirror(nh_context* ctx, nh_Counts* out);          // nh_context.hip
 #define NH_COUNTER_WORDS 41u          // leading words of nh_DevState that the host mirrors (nh_read_counts)
 
 struct nh_ContactImpulseData {
@@ -645,8 +656,8 @@ void nh_bucket_sort_seed(nh_context* ctx, const uint64_t* sorted_keys, uint32_t 
 // Exclusive scan of `in[0..n)` into `out` (may alias); n read from *d_count (+ `extra` elements);
 // the grand total is also stored to *d_total if non-null.  `tmp` needs 2 * NH_SORT_GRID words.
 // If `d_enable` is given and *d_enable == 0 the scan is skipped on the device (the total is reported as 0).
-void nh_halo_pack_on(hipStream_t stream, const nh_BodyData* bodies, const uint32_t* indices, uint32_t count, void* out);          // nh_solve.hip
-void nh_halo_update_on(hipStream_t stream, const nh_BodyData* bodies, uint32_t first_slot, uint32_t count, const void* in);
+void nh_halo_pack_on(hipStream_t stream, const nh_BodyData* bodies, const uint32_t* indices, uint32_t count, void* out);          // nh_partition.hip
+void nh_halo_update_on(hipStream_t stream, const nh_BodyData* bodies, uint32_t first_slot, uint32_t count, const void* in);          // nh_partition.hip
 void nh_scan_u32(nh_context* ctx, const uint32_t* in, uint32_t* out, const uint32_t* d_count, uint32_t extra,
                  uint32_t* tmp, uint32_t* d_total, const uint32_t* d_enable = nullptr);
 // the same for two arrays of equal length in one pair of launches
@@ -655,6 +666,19 @@ void nh_scan2_u32(nh_context* ctx, const uint32_t* in_a, uint32_t* out_a, uint32
 
 // dst[0 .. *d_count * words_per_item) = src[...]
 void nh_copy_back_u32(nh_context* ctx, const uint32_t* src, uint32_t* dst, const uint32_t* d_count, uint32_t words_per_item);
+
+#define NH_NONE 0xFFFFFFFFu
+// body classes: the one-body fast path by contact count (<= 4, <= 8, more) or the level-scheduled path
+#define NH_CLS_NONE 0u
+#define NH_CLS_STATIC4 1u
+#define NH_CLS_STATIC8 2u
+#define NH_CLS_STATICN 3u
+#define NH_CLS_GENERAL 4u
+#define NH_CLS_PENDING 0xFFu         // k_adj_simple could not settle it: k_adj_fill / k_adj_sort do
+// one-body bodies classified by k_adj_sort (after the counts round trip): the kernel speculatively launched before it has not seen them
+#define NH_CLS_STATIC4_LATE 5u
+#define NH_CLS_STATIC8_LATE 6u
+#define NH_UNSET 0xFFFFFFFFu
 
 // ---- device helpers ------------------------------------------------------------------------------------
 #if defined(__HIPCC__)
@@ -701,6 +725,14 @@ __device__ __forceinline__ uint32_t nh_wave_reserve1(uint32_t* counter, bool fla
 	if (nh_lane() == leader) base = atomicAdd(counter, (uint32_t)__popcll(bal));
 	base = __shfl(base, (int)leader);
 	return base + (uint32_t)__popcll(bal & ((1ull << nh_lane()) - 1ull));
+}
+
+__device__ __forceinline__ bool tag_less(uint64_t ta, uint32_t fa, uint64_t tb, uint32_t fb) { return ta < tb || (ta == tb && fa < fb); }
+
+__device__ __forceinline__ uint32_t slot_key_of(uint32_t i, const uint32_t* __restrict__ slot_key) {
+	// closed form of the reference's round-robin scheduler when it meets no lane conflict:
+	// contact i -> bucket i%16, lane (i/16)%8; batches fill (and are emitted) bucket by bucket every 128 contacts.
+	return slot_key ? slot_key[i] : ((i >> 7) * 16u + (i & 15u));
 }
 #endif
 

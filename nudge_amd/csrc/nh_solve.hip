@@ -1,5 +1,6 @@
-// nh_solve.hip -- contact cache (read/write), constraint setup, the sequential-impulse solver, cached-impulse
-// export, gravity/damping and the integrator.  Replaces reference nudge.cpp:4011-4926 and the caller-side
+// nh_solve.hip -- the sequential-impulse solver with the part of the constraint setup that chooses between its forms
+// (finish_setup and the kernels it launches), cached-impulse export, gravity/damping and the integrator.  With
+// nh_cache.hip, nh_schedule.hip and nh_step.hip it replaces reference nudge.cpp:4011-4926 and the caller-side
 // loop example/main.cpp:290-305.
 //
 // Solver order.  The reference runs projected Gauss-Seidel over 8-wide batches produced by a sequential
@@ -16,27 +17,11 @@
 //     levels run one after the other, contacts inside a level are independent.  Executing levels in order
 //     is exactly the sequential Gauss-Seidel sweep in slot order.
 #include "nh_internal.h"
-int nh_asleep_remember(nh_context* ctx);            // nh_collide.hip (asleep steps: nh_internal.h)
 #include <type_traits>
 #include <atomic>
 #include <string.h>
 #include "nh_solver.h"
 #include "nh_narrowphase.h"          // (PAIR AHEAD: the still solver's lanes evaluate their bodies' own collider pairs for the next sub-step)
-
-#define NH_NONE 0xFFFFFFFFu
-// body classes: the one-body fast path by contact count (<= 4, <= 8, more) or the level-scheduled path
-#define NH_CLS_NONE 0u
-#define NH_CLS_STATIC4 1u
-#define NH_CLS_STATIC8 2u
-#define NH_CLS_STATICN 3u
-#define NH_CLS_GENERAL 4u
-#define NH_CLS_PENDING 0xFFu         // k_adj_simple could not settle it: k_adj_fill / k_adj_sort do
-// one-body bodies classified by k_adj_sort (after the counts round trip): the kernel speculatively launched before it has not seen them
-#define NH_CLS_STATIC4_LATE 5u
-#define NH_CLS_STATIC8_LATE 6u
-#define NH_UNSET 0xFFFFFFFFu
-
-__device__ __forceinline__ bool tag_less(uint64_t ta, uint32_t fa, uint64_t tb, uint32_t fb) { return ta < tb || (ta == tb && fa < fb); }
 
 // ---- gravity + damping over the active list (example/main.cpp:290-305) -------------------------------------
 __global__ __launch_bounds__(256) void k_gravity(const nh_DevState* __restrict__ st, const uint32_t* __restrict__ active, nh_BodyMomentum* __restrict__ momentum,
@@ -92,103 +77,6 @@ __global__ __launch_bounds__(256) void k_advance_rest(const nh_DevState* __restr
 	}
 }
 
-// ---- read_cached_impulses (nudge.cpp:4021-4108) ------------------------------------------------------------------
-// contacts are already in tag order, so the reference's merge-join becomes one binary search per contact.
-__global__ __launch_bounds__(256) void k_cache_lookup(const nh_DevState* __restrict__ st, const uint64_t* __restrict__ tags, const uint32_t* __restrict__ features,
-                                                      const uint64_t* __restrict__ ctags, const uint32_t* __restrict__ cfeatures, const nh_CachedContactImpulse* __restrict__ cdata,
-                                                      nh_CachedContactImpulse* __restrict__ out, const nh_BodyPair* __restrict__ bodies, const uint8_t* __restrict__ body_class) {
-	uint32_t n = st->contacts, m = st->cache;
-	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-		if (body_class) {
-			// only contacts of the >8-contact one-body class and of the level-scheduled path read their warm start from `out`; the
-			// fused one-body solver looks its own up and may already have put its SOLVED impulses there
-			const nh_BodyPair p = bodies[i];
-			const uint32_t ca = p.a ? body_class[p.a] : 0u, cb = p.b ? body_class[p.b] : 0u;
-			if (ca != NH_CLS_GENERAL && cb != NH_CLS_GENERAL && ca != NH_CLS_STATICN && cb != NH_CLS_STATICN) continue;
-		}
-		uint64_t t = tags[i]; uint32_t f = features[i];
-		uint32_t lo = 0, hi = m;
-		// steady state: the cache is last step's contact list, so the entry usually sits at the same index
-		if (i < m && ctags[i] == t && cfeatures[i] == f) { lo = i; hi = i; }
-		while (lo < hi) { uint32_t mid = (lo + hi) >> 1; if (tag_less(ctags[mid], cfeatures[mid], t, f)) lo = mid + 1; else hi = mid; }
-		nh_CachedContactImpulse r = { { 0.0f, 0.0f, 0.0f }, 0.0f };
-		if (lo < m && ctags[lo] == t && cfeatures[lo] == f) r = cdata[lo];
-		out[i] = r;
-	}
-}
-
-// ... over a LIST of contacts: the general ones of a world in which they are few (k_contact_class: `general_list`, st->general_contacts of them) -- two bodies touching among a
-// million that rest on the ground cost the lookup 43 us of reading every contact's bodies and classes to find them
-__global__ __launch_bounds__(256) void k_cache_lookup_listed(const nh_DevState* __restrict__ st, const uint32_t* __restrict__ list, const uint64_t* __restrict__ tags, const uint32_t* __restrict__ features,
-                                                             const uint64_t* __restrict__ ctags, const uint32_t* __restrict__ cfeatures, const nh_CachedContactImpulse* __restrict__ cdata,
-                                                             nh_CachedContactImpulse* __restrict__ out) {
-	const uint32_t n = st->contacts, m = st->cache, g = st->general_contacts;
-	for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < g; j += gridDim.x * blockDim.x) {
-		const uint32_t i = list[j];
-		if (i >= n) continue;
-		const uint64_t t = tags[i]; const uint32_t f = features[i];
-		uint32_t lo = 0, hi = m;
-		if (i < m && ctags[i] == t && cfeatures[i] == f) { lo = i; hi = i; }
-		while (lo < hi) { uint32_t mid = (lo + hi) >> 1; if (tag_less(ctags[mid], cfeatures[mid], t, f)) lo = mid + 1; else hi = mid; }
-		nh_CachedContactImpulse r = { { 0.0f, 0.0f, 0.0f }, 0.0f };
-		if (lo < m && ctags[lo] == t && cfeatures[lo] == f) r = cdata[lo];
-		out[i] = r;
-	}
-}
-
-// cached impulses of sleeping pairs are kept aside (nudge.cpp:4064-4101)
-__global__ __launch_bounds__(256) void k_cull_flags(const nh_DevState* __restrict__ st, const uint64_t* __restrict__ ctags, const uint64_t* __restrict__ sleeping, uint32_t* __restrict__ flags) {
-	uint32_t m = st->cache, ns = st->sleeping;
-	if (blockIdx.x == 0 && threadIdx.x == 0) flags[m] = 0;       // sentinel so that scan[m] = number of culled entries
-	if (ns == 0) return;                                         // nothing sleeps: the scan and the write below are skipped on the device
-	for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < m; j += gridDim.x * blockDim.x) {
-		uint64_t t = ctags[j];
-		uint32_t lo = 0, hi = ns;
-		while (lo < hi) { uint32_t mid = (lo + hi) >> 1; if (sleeping[mid] < t) lo = mid + 1; else hi = mid; }
-		flags[j] = (lo < ns && sleeping[lo] == t) ? 1u : 0u;
-	}
-}
-
-__global__ __launch_bounds__(256) void k_cull_write(const nh_DevState* __restrict__ st, const uint32_t* __restrict__ flags_in, const uint32_t* __restrict__ scan,
-                                                    const uint64_t* __restrict__ ctags, const uint32_t* __restrict__ cfeatures, const nh_CachedContactImpulse* __restrict__ cdata,
-                                                    uint64_t* __restrict__ otags, uint32_t* __restrict__ ofeatures, nh_CachedContactImpulse* __restrict__ odata) {
-	uint32_t m = st->cache;
-	if (st->sleeping == 0) return;
-	for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < m; j += gridDim.x * blockDim.x) {
-		// flags were scanned in place into `scan`; an entry is culled iff scan[j+1] != scan[j]
-		uint32_t p = scan[j], q = scan[j + 1];
-		if (q != p) { otags[p] = ctags[j]; ofeatures[p] = cfeatures[j]; odata[p] = cdata[j]; }
-		(void)flags_in;
-	}
-}
-
-// ---- write_cached_impulses (nudge.cpp:4110-4158): merge of two sorted runs by rank -------------------------------
-__global__ __launch_bounds__(256) void k_write_cache(nh_DevState* __restrict__ st, const uint64_t* __restrict__ tags, const uint32_t* __restrict__ features, const nh_CachedContactImpulse* __restrict__ imp,
-                                                     const uint64_t* __restrict__ ktags, const uint32_t* __restrict__ kfeatures, const nh_CachedContactImpulse* __restrict__ kdata,
-                                                     uint64_t* __restrict__ otags, uint32_t* __restrict__ ofeatures, nh_CachedContactImpulse* __restrict__ odata, uint32_t capacity) {
-	uint32_t n = st->contacts, m = st->culled;
-	uint32_t total = n + m;
-	if (total > capacity) { if (blockIdx.x == 0 && threadIdx.x == 0) { st->error = NH_ERR_CACHE_CAPACITY; st->cache = 0; } return; }
-	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-		if (i < n) {
-			// contact i goes after every culled entry with key <= its key ("if (a < b) contact else culled")
-			uint64_t t = tags[i]; uint32_t f = features[i];
-			uint32_t lo = 0, hi = m;
-			while (lo < hi) { uint32_t mid = (lo + hi) >> 1; if (!tag_less(t, f, ktags[mid], kfeatures[mid])) lo = mid + 1; else hi = mid; }
-			uint32_t pos = i + lo;
-			otags[pos] = t; ofeatures[pos] = f; odata[pos] = imp[i];
-		} else {
-			uint32_t j = i - n;
-			uint64_t t = ktags[j]; uint32_t f = kfeatures[j];
-			uint32_t lo = 0, hi = n;
-			while (lo < hi) { uint32_t mid = (lo + hi) >> 1; if (tag_less(tags[mid], features[mid], t, f)) lo = mid + 1; else hi = mid; }
-			uint32_t pos = j + lo;
-			otags[pos] = t; ofeatures[pos] = f; odata[pos] = kdata[j];
-		}
-	}
-	if (blockIdx.x == 0 && threadIdx.x == 0) st->cache = total;
-}
-
 // ---- setup: per-body adjacency in solver order -------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_zero_u32(uint32_t* __restrict__ p, uint32_t n) {
 	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) p[i] = 0;
@@ -221,98 +109,6 @@ __global__ __launch_bounds__(256) void k_adj_fill(const nh_DevState* __restrict_
 		if ((ca == NH_CLS_PENDING && (which & 1u)) || (ca == NH_CLS_GENERAL && (which & 2u))) { uint32_t base = off[p.a] + atomicAdd(&cursor[p.a], len); for (uint32_t k = 0; k < len; ++k) adj[base + k] = i + k; }
 		if ((cb == NH_CLS_PENDING && (which & 1u)) || (cb == NH_CLS_GENERAL && (which & 2u))) { uint32_t base = off[p.b] + atomicAdd(&cursor[p.b], len); for (uint32_t k = 0; k < len; ++k) adj[base + k] = i + k; }
 	}
-}
-
-__device__ __forceinline__ uint32_t slot_key_of(uint32_t i, const uint32_t* __restrict__ slot_key) {
-	// closed form of the reference's round-robin scheduler when it meets no lane conflict:
-	// contact i -> bucket i%16, lane (i/16)%8; batches fill (and are emitted) bucket by bucket every 128 contacts.
-	return slot_key ? slot_key[i] : ((i >> 7) * 16u + (i & 15u));
-}
-
-// One lane per body.  A body that sits in exactly ONE collider pair, with the static world, and has <= 8 contacts -- the box on the
-// ground -- needs no CSR build: its contacts are first .. first+d-1 (a pair's contacts are adjacent in tag order), recorded here in slot
-// order as ONE word pair the solver reads next to the body state: simple[x] = (first contact, count | 3-bit offsets in slot order << 4 |
-// body-is-"a" << 28).  Degrees come straight from nh_collide's counters: no scan, no adjacency array on this path (k_adj_from_simple
-// writes the CSR form on demand).  Everything else is left PENDING for the general k_adj_fill / k_adj_sort, which do not even start
-// when nothing is pending.
-#define NH_FIRST_IS_A 0x80000000u        // in first_contact[]: the body plays "a" in its last pair (k_gather_contacts)
-__global__ __launch_bounds__(256) void k_adj_simple(nh_DevState* __restrict__ st, uint32_t nbodies, uint32_t* __restrict__ deg, const unsigned long long* __restrict__ pair_counter,
-                                                    const uint32_t* __restrict__ first_contact, const uint32_t* __restrict__ slot_key,
-                                                    uint8_t* __restrict__ body_class, const nh_BodyProperties* __restrict__ props, nh_BodyMomentum* __restrict__ momentum,
-                                                    uint2* __restrict__ simple, uint32_t* __restrict__ body_rec, uint32_t* __restrict__ body_pos, const uint32_t* __restrict__ sorted_idx) {
-	// body_rec / body_pos (nh_internal.h, contact storage by slot): for a body of the one-pair class the record its contacts come from (| role) and that record's
-	// place in the tag order -- what a still step's solver lane starts from; NH_BODY_REC_NONE for a body without contacts
-	bool other = false, unstable = false;
-	for (uint32_t x = blockIdx.x * blockDim.x + threadIdx.x; x < nbodies; x += gridDim.x * blockDim.x) {
-		if (x == 0) {
-			body_class[0] = 0;
-			momentum[0].unused0 = props[0].mass_inverse;             // the reference stashes mass_inverse in unused0 of EVERY body (nudge.cpp:4198)
-			const nh_BodyMomentum m0 = momentum[0];
-			const nh_BodyProperties p0 = props[0];
-			st->static_inert = nh_is_inert(m0.velocity, m0.angular_velocity, p0.inertia_inverse, p0.mass_inverse) ? 1u : 0u;
-			deg[0] = 0u;
-			continue;
-		}
-		const unsigned long long pc = pair_counter[x];
-		const uint32_t d = (uint32_t)pc;
-		deg[x] = d;                                 // (the degrees as an array of their own: what the CSR scan reads, ensure_csr)
-		uint32_t cls = NH_CLS_NONE;
-		if (d) {
-			const uint32_t inf = (uint32_t)(pc >> 32);
-			if ((inf & 0xFFFFu) == 1u && (inf >> 16) == 0u && d <= 8u) {
-				const uint32_t fc = first_contact[x];
-				const uint32_t f = fc & ~NH_FIRST_IS_A;
-				// contacts f .. f+d-1 in slot order (insertion sort in registers: a 4-entry network for the usual box on the ground, 8 otherwise)
-				auto emit = [&](auto tag) {
-					constexpr int W = decltype(tag)::value;
-					uint32_t c[W], k[W];
-#pragma unroll
-					for (int q = 0; q < W; ++q) { c[q] = (uint32_t)q < d ? f + q : 0xFFFFFFFFu; k[q] = (uint32_t)q < d ? slot_key_of(c[q], slot_key) : 0xFFFFFFFFu; }
-#pragma unroll
-					for (int q = 1; q < W; ++q) {
-#pragma unroll
-						for (int j = q; j > 0; --j) {
-							bool sw = (k[j] < k[j - 1]) || (k[j] == k[j - 1] && c[j] < c[j - 1]);
-							uint32_t tc = sw ? c[j - 1] : c[j], tk = sw ? k[j - 1] : k[j];
-							c[j - 1] = sw ? c[j] : c[j - 1]; k[j - 1] = sw ? k[j] : k[j - 1];
-							c[j] = tc; k[j] = tk;
-						}
-					}
-					uint32_t perm = 0;
-#pragma unroll
-					for (int q = 0; q < W; ++q) if ((uint32_t)q < d) perm |= (c[q] - f) << (3 * q);
-					simple[x] = make_uint2(f, d | (perm << 4) | ((fc & NH_FIRST_IS_A) ? (1u << 28) : 0u));
-					if (body_rec) {
-						const uint32_t pos = first_contact[x + NH_DEG_STRIDE(nbodies)];
-						body_pos[x] = pos;
-						body_rec[x] = (sorted_idx ? sorted_idx[pos] : NH_BODY_REC_NONE) | ((fc & NH_FIRST_IS_A) ? NH_BODY_REC_IS_A : 0u);
-					}
-				};
-				if (d <= 4u) emit(std::integral_constant<int, 4>()); else emit(std::integral_constant<int, 8>());
-				cls = d <= 4u ? NH_CLS_STATIC4 : NH_CLS_STATIC8;
-				if (cls == NH_CLS_STATIC8) st->has_static8 = 1;
-			} else if (!slot_key && (inf >> 16) != 0u) {
-				// default (colour) order and a dynamic partner: a general body, settled here -- its adjacency list is filled like a pending body's
-				// (k_adj_fill) but needs neither the per-body sort by slot key nor the predecessor links of the exact order (k_adj_sort walks and
-				// sorts every list it classifies: 0.5 ms in a pit of 4 M spheres that are ALL of this kind)
-				cls = NH_CLS_GENERAL;
-				st->has_pending = 1;
-				momentum[x].unused0 = props[x].mass_inverse;         // (nudge.cpp:4198: the level-scheduled sweeps read it from there)
-			} else {
-				cls = NH_CLS_PENDING;
-				st->has_pending = 1;
-			}
-		} else {
-			momentum[x].unused0 = props[x].mass_inverse;
-			if (body_rec) { body_rec[x] = NH_BODY_REC_NONE; body_pos[x] = 0u; }
-		}
-		body_class[x] = (uint8_t)cls;
-		other |= cls != NH_CLS_STATIC4;
-		unstable |= cls != NH_CLS_STATIC4 && cls != NH_CLS_NONE;
-	}
-	if (__builtin_amdgcn_ballot_w64(unstable) != 0 && nh_lane() == 0) st->has_unstable = 1u;
-	// (one plain store per wave that has such a body: no counting)
-	if (__builtin_amdgcn_ballot_w64(other) != 0 && nh_lane() == 0) st->has_other = 1u;
 }
 
 // CSR form of the lists k_adj_simple recorded (only when a kernel that walks off[] / adj[] is about to run: several apply calls per
@@ -442,145 +238,6 @@ __global__ __launch_bounds__(256) void k_contact_class(nh_DevState* __restrict__
 		for (uint32_t w = 0; w < 4; ++w) { if (w < wave) before += s_wave[w]; total += s_wave[w]; }
 		if (general) general_list[cursor + before + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull))] = i;
 		cursor += total;
-	}
-}
-
-// ---- exact replay of the reference's greedy batch scheduler (nudge.cpp:4206-4339), one wave -------------------
-#define GR_BUCKETS 16
-#define GR_OPEN 64          // open (vacant) batches kept per bucket in LDS
-// Exact-order mode, common case first.  When the scheduler below never meets a lane conflict, contact i ends up in batch
-// (i / 128) * 16 + i % 16 (its bucket's batch completes with every eighth contact of the bucket, batches are emitted in that order,
-// leftovers bucket by bucket).  The first conflict the scheduler can meet is two contacts of ONE such batch sharing a dynamic body, so if no
-// batch of the closed form holds one, the closed form IS the schedule: checked here with one lane per batch; only otherwise the
-// sequential replay runs (it is a single wave walking all contacts: milliseconds for tens of thousands).
-__global__ __launch_bounds__(256) void k_order_check(nh_DevState* __restrict__ st, const nh_BodyPair* __restrict__ bodies, uint32_t* __restrict__ slot_key, uint32_t seq) {
-	const uint32_t n = st->contacts;
-	const uint32_t nbatch = ((n + 127u) / 128u) * 16u;
-	for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < nbatch; t += gridDim.x * blockDim.x) {
-		const uint32_t first = (t >> 4) * 128u + (t & 15u);
-		uint32_t ca[8], cb[8];
-		bool conflict = false;
-#pragma unroll
-		for (int k = 0; k < 8; ++k) {
-			const uint32_t i = first + 16u * k;
-			ca[k] = NH_NONE; cb[k] = NH_NONE;
-			if (i < n) {
-				const nh_BodyPair bp = bodies[i];
-				ca[k] = bp.a ? bp.a : bp.b; cb[k] = bp.b ? bp.b : bp.a;      // dependencies on body 0 do not count (nudge.cpp:4238-4240)
-				slot_key[i] = t;
-#pragma unroll
-				for (int j = 0; j < k; ++j) conflict |= ca[j] == ca[k] || cb[j] == ca[k] || ca[j] == cb[k] || cb[j] == cb[k];
-			}
-		}
-		if (conflict) st->order_conflict = seq;
-	}
-}
-
-// Open batches beyond the GR_OPEN kept in LDS spill to global memory (`spill_ab` / `spill_idx`: GR_BUCKETS x spill_cap x 8 entries from the
-// arena): a dynamic hub body with thousands of contacts (a tray of boxes) makes every contact of a bucket conflict, so no batch completes
-// and the open list grows with the contact count -- the reference sizes these arrays by contacts.count (nudge.cpp:4222-4223).
-struct gr_store {
-	uint2 (*lds_ab)[GR_OPEN + 1][8];
-	uint32_t (*lds_idx)[GR_OPEN + 1][8];
-	uint2* spill_ab; uint32_t* spill_idx; uint32_t spill_cap;
-	__device__ __forceinline__ size_t at(uint32_t b, uint32_t j, uint32_t l) const { return ((size_t)b * spill_cap + (j - (GR_OPEN + 1u))) * 8u + l; }
-	__device__ __forceinline__ uint2 ab(uint32_t b, uint32_t j, uint32_t l) const {
-		if (j <= GR_OPEN) return lds_ab[b][j][l];
-		const unsigned long long v = __hip_atomic_load(reinterpret_cast<const unsigned long long*>(spill_ab + at(b, j, l)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		return make_uint2((uint32_t)v, (uint32_t)(v >> 32));
-	}
-	__device__ __forceinline__ void set_ab(uint32_t b, uint32_t j, uint32_t l, uint2 v) const {
-		if (j <= GR_OPEN) lds_ab[b][j][l] = v;
-		else __hip_atomic_store(reinterpret_cast<unsigned long long*>(spill_ab + at(b, j, l)), (unsigned long long)v.x | ((unsigned long long)v.y << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-	}
-	__device__ __forceinline__ uint32_t idx(uint32_t b, uint32_t j, uint32_t l) const {
-		return j <= GR_OPEN ? lds_idx[b][j][l] : __hip_atomic_load(spill_idx + at(b, j, l), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-	}
-	__device__ __forceinline__ void set_idx(uint32_t b, uint32_t j, uint32_t l, uint32_t v) const {
-		if (j <= GR_OPEN) lds_idx[b][j][l] = v; else __hip_atomic_store(spill_idx + at(b, j, l), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-	}
-};
-
-__global__ __launch_bounds__(64) void k_greedy_replay(nh_DevState* __restrict__ st, const nh_BodyPair* __restrict__ bodies, uint32_t* __restrict__ slot_key, uint32_t seq,
-                                                      uint2* __restrict__ spill_ab, uint32_t* __restrict__ spill_idx, uint32_t spill_cap) {
-	if (st->order_conflict != seq) return;          // k_order_check: the closed form it wrote is the schedule
-	__shared__ uint2 pair_ab[GR_BUCKETS][GR_OPEN + 1][8];
-	__shared__ uint32_t slot_idx[GR_BUCKETS][GR_OPEN + 1][8];
-	__shared__ uint32_t vacancy[GR_BUCKETS];
-	__shared__ uint32_t emitted;
-	const gr_store S = { pair_ab, slot_idx, spill_ab, spill_idx, spill_cap };
-	const uint32_t max_open = GR_OPEN + spill_cap;      // largest legal index of the all-invalid padding entry
-	const uint32_t lane = threadIdx.x, sub = lane >> 3, ln = lane & 7;
-	const uint32_t n = st->contacts;
-	if (lane < GR_BUCKETS) { vacancy[lane] = 0; }
-	if (lane == 0) emitted = 0;
-	for (uint32_t k = lane; k < GR_BUCKETS * 8; k += 64) pair_ab[k >> 3][0][k & 7] = make_uint2(NH_NONE, NH_NONE);
-	__syncthreads();
-	for (uint32_t i = 0; i < n; ++i) {
-		nh_BodyPair bp = bodies[i];
-		uint32_t bucket = i % GR_BUCKETS;
-		uint32_t ca = bp.a ? bp.a : bp.b, cb = bp.b ? bp.b : bp.a;     // ignore dependencies on body 0
-		uint32_t vac = vacancy[bucket];
-		// first open batch (or the all-invalid padding entry at index vac) without a conflicting lane
-		uint32_t j = NH_NONE;
-		for (uint32_t base = 0; j == NH_NONE; base += 8) {
-			uint32_t jb = base + sub;
-			bool in_range = jb <= vac;
-			uint2 ab = in_range ? S.ab(bucket, jb, ln) : make_uint2(NH_NONE, NH_NONE);
-			bool conflict = in_range && (ab.x == ca || ab.y == ca || ab.x == cb || ab.y == cb);
-			unsigned long long bal = __ballot(conflict);
-			unsigned long long rng = __ballot(in_range);
-			for (uint32_t s = 0; s < 8; ++s) {
-				bool ok = ((rng >> (s * 8)) & 1ull) && (((bal >> (s * 8)) & 0xffull) == 0ull);
-				if (ok) { j = base + s; break; }
-			}
-		}
-		// first free lane of that batch
-		uint2 mine = S.ab(bucket, j, ln);
-		unsigned long long freeb = __ballot(sub == 0 && mine.x == NH_NONE && mine.y == NH_NONE);
-		uint32_t free_lane = (uint32_t)__ffsll((long long)(freeb & 0xffull)) - 1u;
-		__syncthreads();
-		if (lane == 0) {
-			S.set_idx(bucket, j, free_lane, i);
-			S.set_ab(bucket, j, free_lane, make_uint2(ca, cb));
-		}
-		__syncthreads();
-		bool changed = false;
-		if (j == vac) {
-			vac = vac + 1;
-			changed = true;
-			if (vac > max_open) { if (lane == 0) st->error = NH_ERR_SCHEDULER_CAPACITY; return; }
-		} else if (free_lane == 7) {
-			// batch complete: emit it, move the last open batch into its place
-			uint32_t e = emitted;
-			if (lane < 8) slot_key[S.idx(bucket, j, lane)] = e;
-			vac = vac - 1;
-			__syncthreads();
-			if (lane < 8) {
-				S.set_ab(bucket, j, lane, S.ab(bucket, vac, lane));
-				S.set_idx(bucket, j, lane, S.idx(bucket, vac, lane));
-			}
-			if (lane == 0) emitted = e + 1;
-			changed = true;
-		}
-		__syncthreads();
-		if (changed) {
-			if (lane == 0) vacancy[bucket] = vac;
-			if (lane < 8) S.set_ab(bucket, vac, lane, make_uint2(NH_NONE, NH_NONE));
-		}
-		__syncthreads();
-	}
-	// leftovers, bucket by bucket (nudge.cpp:4316-4337)
-	uint32_t e = emitted;
-	for (uint32_t b = 0; b < GR_BUCKETS; ++b) {
-		uint32_t vac = vacancy[b];
-		for (uint32_t j = 0; j < vac; ++j) {
-			if (lane < 8) {
-				uint2 ab = S.ab(b, j, lane);
-				if (!(ab.x == NH_NONE && ab.y == NH_NONE)) slot_key[S.idx(b, j, lane)] = e;
-			}
-			++e;
-		}
 	}
 }
 
@@ -2222,20 +1879,6 @@ __global__ __launch_bounds__(256) void k_update_impulses(const nh_DevState* __re
 #include "nh_blocks.h"
 
 // =====================================================================================================================================
-static nh_ContactImpulseData* new_impulse_data(nh_context* ctx) {
-	if (ctx->impulse_ring.empty()) { ctx->impulse_ring.resize(64, nullptr); ctx->constraint_ring.resize(64, nullptr); }
-	uint32_t k = ctx->ring_pos % 64;
-	if (!ctx->impulse_ring[k]) ctx->impulse_ring[k] = new nh_ContactImpulseData();
-	return ctx->impulse_ring[k];
-}
-
-static nh_ContactConstraintData* new_constraint_data(nh_context* ctx) {
-	if (ctx->constraint_ring.empty()) { ctx->impulse_ring.resize(64, nullptr); ctx->constraint_ring.resize(64, nullptr); }
-	uint32_t k = ctx->ring_pos % 64;
-	if (!ctx->constraint_ring[k]) ctx->constraint_ring[k] = new nh_ContactConstraintData();
-	return ctx->constraint_ring[k];
-}
-
 extern "C" int nh_apply_gravity_damping(nh_context* ctx, const nh_ActiveBodies* active_bodies, const nh_BodyData* bodies,
                                         float time_step, const float gravity[3], float damping_rate) {
 	if (!ctx || !active_bodies || !bodies || !gravity) return NH_ERR_INVALID;
@@ -2284,226 +1927,6 @@ extern "C" int nh_advance(nh_context* ctx, const nh_ActiveBodies* active_bodies,
 	NH_LAUNCH(ctx, "advance", k_advance, nh_grid_for(bodies->count, 256, 2048), 256, ctx->d_state, active_bodies->indices, bodies->transforms,
 	          bodies->momentum, bodies->idle_counters, time_step);
 	return ctx->stream_state.every ? nh_stream_after_advance(ctx) : NH_OK;
-}
-
-// cached impulses of sleeping pairs are kept aside (nudge.cpp:4064-4101); skipped entirely when nothing sleeps (culled = 0 since nh_collide)
-static void run_cull(nh_context* ctx, nh_ContactImpulseData* d, uint32_t sleeping_on_host) {
-	if (!d->cull_pending) return;
-	d->cull_pending = false;
-	if (sleeping_on_host == 0) return;
-	nh_DevState* st = ctx->d_state;
-	const uint32_t ccap = d->cache_capacity;
-	NH_LAUNCH(ctx, "cull_flags", k_cull_flags, nh_grid_for(ccap, 256, 4096), 256, st, d->ctags, d->sleeping_pairs, d->cull_flags);
-	nh_scan_u32(ctx, d->cull_flags, d->cull_flags, &st->cache, 1, d->cull_tmp, &st->culled, &st->sleeping);   // +1: the sentinel, so scan[j+1] exists for every j
-	NH_LAUNCH(ctx, "cull_write", k_cull_write, nh_grid_for(ccap, 256, 4096), 256, st, d->cull_flags, d->cull_flags, d->ctags, d->cfeatures, d->cdata,
-	          d->culled_tags, d->culled_features, d->culled_data);
-}
-
-extern "C" int nh_read_cached_impulses(nh_context* ctx, const nh_ContactCache* cache, const nh_ContactData* contacts, nh_Arena* memory, nh_ContactImpulseData** out) {
-	if (!ctx || !cache || !contacts || !memory || !out) return NH_ERR_INVALID;
-	{
-		// still step: only on the cache and the contact list it was launched for
-		const nh_StillStep& ss = ctx->still;
-		const bool in_sequence = ss.active && !ss.resolved && !ctx->pending && cache->tags == ss.cache_tags && cache->features == ss.cache_features && cache->data == ss.cache_data &&
-		                         cache->capacity == ss.cache_capacity && contacts->data == ss.lay_contacts.data && contacts->tags == ss.lay_contacts.tags;
-		int rc = nh_flush_pending(ctx, true, in_sequence); if (rc) return rc;
-	}
-	const uint32_t kcap = contacts->capacity, ccap = cache->capacity;
-	int err = NH_OK;
-	ctx->ring_pos++;
-	nh_ContactImpulseData* d = new_impulse_data(ctx);
-	d->data = nh_arena_array<nh_CachedContactImpulse>(memory, kcap, &err);
-	d->culled_tags = nh_arena_array<uint64_t>(memory, ccap, &err);
-	d->culled_features = nh_arena_array<uint32_t>(memory, ccap, &err);
-	d->culled_data = nh_arena_array<nh_CachedContactImpulse>(memory, ccap, &err);
-	d->capacity = kcap; d->culled_capacity = ccap;
-	// culling of cached impulses of sleeping pairs (nudge.cpp:4064-4101) only has work when something sleeps; the scratch for it is
-	// reserved here, the kernels run once the host knows the sleeping-pair count (run_cull)
-	d->cull_flags = nh_arena_array<uint32_t>(memory, ccap + 1, &err);
-	d->cull_tmp = nh_arena_array<uint32_t>(memory, 2 * NH_SORT_GRID + 64, &err);
-	if (err) return err;
-	// the per-contact lookup is deferred: bodies on the one-body path fetch their impulses inside the fused solver kernel, and
-	// materialize_lookup() fills d->data for everything else (only if such contacts exist, which setup learns)
-	d->lookup_pending = true; d->ctx = ctx; d->consumed = false;
-	d->tags = contacts->tags; d->features = contacts->features;
-	d->ctags = cache->tags; d->cfeatures = cache->features; d->cdata = cache->data;
-	d->cull_pending = contacts->sleeping_pairs != nullptr;
-	d->sleeping_pairs = contacts->sleeping_pairs;
-	d->cache_capacity = ccap;
-	if (d->cull_pending && (ctx->flags & NH_FLAG_SYNC_COUNTS)) {
-		// reference semantics: nh_collide has just synchronised, the count is on the host
-		run_cull(ctx, d, ctx->h_state->sleeping);
-	}
-	*out = d;
-	return NH_OK;
-}
-
-// `bodies` / `body_class` given: restrict to the contacts that read their warm start from d->data (see k_cache_lookup)
-// (`general_list`, `general`: the contacts that read their warm start from d->data are the listed general ones and nothing else -- no body of the rare many-contact class -- and
-// they are few: the lookup walks the list)
-static void materialize_lookup(nh_context* ctx, nh_ContactImpulseData* d, const nh_BodyPair* bodies = nullptr, const uint8_t* body_class = nullptr, const uint32_t* general_list = nullptr, uint32_t general = 0u) {
-	if (!d->lookup_pending) return;
-	d->lookup_pending = false;
-	if (general_list && general != 0u && (uint64_t)general * 16u < d->capacity && !ctx->no_listed_lookup) {
-		NH_LAUNCH(ctx, "cache_lookup_listed", k_cache_lookup_listed, nh_grid_for(general, 256, 4096), 256, ctx->d_state, general_list, d->tags, d->features, d->ctags, d->cfeatures, d->cdata, d->data);
-		return;
-	}
-	NH_LAUNCH(ctx, "cache_lookup", k_cache_lookup, nh_grid_for(d->capacity, 256, 16384), 256, ctx->d_state, d->tags, d->features, d->ctags, d->cfeatures, d->cdata, d->data, bodies, body_class);
-}
-
-extern "C" const nh_CachedContactImpulse* nh_contact_impulses_device(const nh_ContactImpulseData* d) {
-	if (!d) return nullptr;
-	nh_ContactImpulseData* m = const_cast<nh_ContactImpulseData*>(d);
-	if (m->ctx) {
-		// before the solver has run this holds the warm-start impulses, afterwards the solved ones: make either visible
-		if (m->ctx->pending) nh_flush_pending(m->ctx);
-		else if (!m->consumed) materialize_lookup(m->ctx, m);
-		nh_StillStep& ss = m->ctx->still;
-		if (ss.active && ss.resolved && m->consumed && m->cdata == ss.cache_data) {
-			// a still step: the solved impulses live in the slot cache; in tag order they are what the exported cache holds (nothing is culled in a still step)
-			if (nh_still_sync_outputs(m->ctx, NH_VIEW_CACHE) == NH_OK)
-				hipMemcpyAsync(m->data, ss.cache.data, sizeof(nh_CachedContactImpulse) * (size_t)(m->capacity < ss.cache.capacity ? m->capacity : ss.cache.capacity), hipMemcpyDeviceToDevice, m->ctx->stream);
-		}
-	}
-	return d->data;
-}
-
-__global__ void k_cache_to_slots(const nh_DevState* __restrict__ st, const uint32_t* __restrict__ dense_slot, const nh_CachedContactImpulse* __restrict__ imp,
-                                 const uint32_t* __restrict__ features, const nh_Record* __restrict__ rec, float4* __restrict__ sc_imp, uint32_t* __restrict__ sc_feat, uint32_t* __restrict__ sc_count);
-
-__global__ void k_culled_to_slots(const nh_DevState* __restrict__ st, const uint64_t* __restrict__ ctags, const uint32_t* __restrict__ cfeatures,
-                                  const nh_CachedContactImpulse* __restrict__ cdata, const uint64_t* __restrict__ sorted_keys, const uint32_t* __restrict__ sorted_idx,
-                                  const nh_Record* __restrict__ rec, uint32_t pair_cap, float4* __restrict__ sc_imp, uint32_t* __restrict__ sc_feat, uint32_t* __restrict__ sc_count);
-
-extern "C" int nh_write_cached_impulses(nh_context* ctx, nh_ContactCache* cache, const nh_ContactData* contacts, nh_ContactImpulseData* imp) {
-	if (!ctx || !cache || !contacts || !imp) return NH_ERR_INVALID;
-	{ int rc = nh_flush_pending(ctx); if (rc) return rc; }
-	{
-		nh_StillStep& ss = ctx->still;
-		// a still step that went through: the solver has written every contact's impulse into its cache entry, tags and features are last step's -- nothing to do
-		if (ss.active && ss.resolved && cache->data == ss.cache_data && imp->ctx == ctx && imp->consumed) return NH_OK;
-		// a full step: afterwards the cache IS this step's contact list when nothing was culled (the round trip has told) -- what the next still step relies on
-		// (sleepers form: entries kept aside for sleeping pairs are part of such a cache -- they go to the slots of their records below)
-		ss.cache_ok = imp->consumed && !imp->cull_pending && !(ctx->flags & NH_FLAG_SYNC_COUNTS) && ((ctx->h_state->sleeping == 0u && ctx->h_state->culled == 0u) || !ss.no_local) &&
-		              contacts->data == ss.lay_contacts.data && contacts->tags == ss.lay_contacts.tags;
-		ss.cache_tags = cache->tags; ss.cache_features = cache->features; ss.cache_data = cache->data; ss.cache_capacity = cache->capacity;
-		ss.cache = *cache;
-		ss.slots_current = false;
-	}
-	if (!imp->consumed) materialize_lookup(ctx, imp);      // no setup ran on this handle: the cache is rewritten from the looked-up impulses
-	if (imp->cull_pending) {
-		nh_Counts c;
-		int rc = nh_read_counts(ctx, &c);
-		if (rc) return rc;
-		run_cull(ctx, imp, c.sleeping_pairs);
-	}
-	nh_DevState* st = ctx->d_state;
-	NH_LAUNCH(ctx, "write_cache", k_write_cache, nh_grid_for((uint64_t)contacts->capacity + cache->capacity, 256, 4096), 256, st,
-	          contacts->tags, contacts->features, imp->data, imp->culled_tags, imp->culled_features, imp->culled_data,
-	          cache->tags, cache->features, cache->data, cache->capacity);
-	if (ctx->still.ok_next && ctx->still.cache_ok && !ctx->still.disabled && (ctx->flags & NH_FLAG_FUSED_STEP) && ctx->sort_seeded) {
-		// the next step may be a still one: the cache goes to the slots as well (solved impulse + feature word to the raw slot each contact came from)
-		NH_LAUNCH(ctx, "cache_to_slots", k_cache_to_slots, nh_grid_for(contacts->capacity, 256, 4096), 256, st, ctx->dense_slot, imp->data, contacts->features, ctx->rec,
-		          ctx->sc_imp, ctx->sc_feat, ctx->sc_count);
-		// (the entries kept aside for sleeping pairs, nudge.cpp:4064-4101: to the slots of the pairs' records -- a step in sleepers form keeps them there)
-		// (the host's mirror knows the step's sleeping pairs from the round trip; how many entries were kept aside is counted on the device after it: the kernel reads that)
-		if (ctx->h_state->sleeping)
-			NH_LAUNCH(ctx, "culled_to_slots", k_culled_to_slots, nh_grid_for(imp->culled_capacity, 256, 2048), 256, st, imp->culled_tags, imp->culled_features, imp->culled_data, ctx->sort_sorted_keys,
-			          ctx->sort_sorted_idx, ctx->rec, ctx->lay_capacity, ctx->sc_imp, ctx->sc_feat, ctx->sc_count);
-		ctx->still.slots_current = true;
-	}
-	if (ctx->flags & NH_FLAG_SYNC_COUNTS) {
-		nh_Counts c;
-		int rc = nh_read_counts(ctx, &c);
-		if (rc) return rc;
-		cache->count = c.cache;
-		if (c.error) return (int)c.error;
-	}
-	return NH_OK;
-}
-
-extern "C" int nh_setup_contact_constraints(nh_context* ctx, const nh_ActiveBodies* active_bodies, const nh_ContactData* contacts,
-                                            const nh_BodyData* bodies, nh_ContactImpulseData* imp, nh_Arena* memory, nh_ContactConstraintData** out) {
-	if (!ctx || !contacts || !bodies || !imp || !memory || !out) return NH_ERR_INVALID;
-	{
-		const nh_StillStep& ss = ctx->still;
-		const bool in_sequence = ss.active && !ss.resolved && !ctx->pending && contacts->data == ss.lay_contacts.data && contacts->bodies == ss.lay_contacts.bodies &&
-		                         bodies->momentum == ss.bodies.momentum && bodies->transforms == ss.bodies.transforms && bodies->count == ss.bodies.count && imp->ctx == ctx && !imp->consumed;
-		int rc = nh_flush_pending(ctx, true, in_sequence); if (rc) return rc;
-	}
-	(void)active_bodies;
-	nh_DevState* st = ctx->d_state;
-	const uint32_t kcap = contacts->capacity;
-	const uint32_t B = bodies->count;
-	int err = NH_OK;
-	nh_ContactConstraintData* d = new_constraint_data(ctx);
-	d->rows = nh_arena_array<float>(memory, (size_t)kcap * 40, &err);
-	d->states = nh_arena_array<float>(memory, (size_t)kcap * 4, &err);
-	if (!ctx->deg || ctx->deg_capacity < NH_DEG_WORDS(B)) return NH_ERR_INVALID;      // nh_collide of this step sized and filled it
-	// one setup per collide: the fill cursors and the contact layout below belong to the last nh_collide (header note 8)
-	if (ctx->setup_seq == ctx->collide_seq) return NH_ERR_STALE_SETUP;
-	if ((ctx->flags & NH_FLAG_SYNC_COUNTS) && contacts->count != ctx->h_state->contacts) return NH_ERR_STALE_SETUP;
-	ctx->setup_seq = ctx->collide_seq;
-	d->body_off = nh_arena_array<uint32_t>(memory, (size_t)B + 2u, &err);           // CSR offsets (scan of the degrees nh_collide counted)
-	d->adj = nh_arena_array<uint32_t>(memory, (size_t)kcap * 2, &err);
-	if (!ctx->lay_class || ctx->lay_body_capacity < B) return NH_ERR_INVALID;        // (sized by this step's nh_collide)
-	d->body_class = ctx->lay_class;          // library-owned: a still step reads what the last full step's k_adj_simple left here
-	d->simple = ctx->lay_simple;
-	d->level_order = nh_arena_array<uint32_t>(memory, kcap, &err);
-	d->gpair = nh_arena_array<uint2>(memory, kcap, &err);
-	d->gstates = nh_arena_array<float4>(memory, kcap, &err);
-	uint32_t* cursor = ctx->deg + NH_DEG_STRIDE(B);                                   // fill cursors (zeroed by nh_collide)
-	uint32_t* pred_a = nh_arena_array<uint32_t>(memory, kcap, &err);
-	uint32_t* pred_b = nh_arena_array<uint32_t>(memory, kcap, &err);
-	uint32_t* level = nh_arena_array<uint32_t>(memory, kcap, &err);
-	uint32_t* general_list = nh_arena_array<uint32_t>(memory, kcap, &err);
-	uint32_t* slot_key = (ctx->flags & NH_FLAG_EXACT_ORDER) ? nh_arena_array<uint32_t>(memory, kcap, &err) : nullptr;
-	uint32_t* tent = (ctx->flags & NH_FLAG_EXACT_ORDER) ? nullptr : nh_arena_array<uint32_t>(memory, kcap, &err);      // colouring: this round's picks
-	// exact order: spill space of the scheduler replay's open batches (k_greedy_replay), at most 8192 per bucket = 12.6 MB
-	const uint32_t spill_cap = slot_key ? (kcap / GR_BUCKETS + 1u < 8192u ? kcap / GR_BUCKETS + 1u : 8192u) : 0u;
-	uint2* spill_ab = slot_key ? nh_arena_array<uint2>(memory, (size_t)GR_BUCKETS * spill_cap * 8u, &err) : nullptr;
-	uint32_t* spill_idx = slot_key ? nh_arena_array<uint32_t>(memory, (size_t)GR_BUCKETS * spill_cap * 8u, &err) : nullptr;
-	uint32_t* level_hist = nh_arena_array<uint32_t>(memory, 2 * (NH_MAX_LEVELS + 2), &err);       // [0, L+2): histogram -> offsets; [L+2, 2L+4): class has a full row
-	uint32_t* level_cursor = nh_arena_array<uint32_t>(memory, NH_MAX_LEVELS + 2, &err);
-	uint32_t* tmp = nh_arena_array<uint32_t>(memory, 2 * NH_SORT_GRID + 64, &err);
-	if (err) return err;
-	d->contact_capacity = kcap; d->body_count = B; d->bodies = contacts->bodies;
-	d->contact_data = contacts->data; d->impulses = imp->data; d->general_list = general_list;
-	d->levels = 0; d->general_contacts = 0;
-	d->blk.active = false; d->blk.warm_pending = false; d->blk.local = false;
-
-	// (degrees were counted by nh_collide while it laid the contacts out; their scan into CSR offsets waits until somebody needs it: ensure_csr)
-	d->csr_ready = false;
-	if (slot_key) {
-		const uint32_t seq = ++ctx->order_seq ? ctx->order_seq : ++ctx->order_seq;       // never 0: tells this call's verdict from an older one
-		NH_LAUNCH(ctx, "order_check", k_order_check, nh_grid_for(kcap / 8u + 16u, 256, 1024), 256, st, contacts->bodies, slot_key, seq);
-		NH_LAUNCH(ctx, "greedy_replay", k_greedy_replay, 1, 64, st, contacts->bodies, slot_key, seq, spill_ab, spill_idx, spill_cap);
-	}
-	if (ctx->still.active && !ctx->still.resolved) ctx->still.setup_d = d;      // still step: classes and records are last step's (nh_still_abandon launches the kernel if it comes to that)
-	else
-	NH_LAUNCH(ctx, "adjacency_simple", k_adj_simple, nh_grid_for(B, 256, 4096), 256, st, B, ctx->deg, reinterpret_cast<const unsigned long long*>(ctx->deg + 2u * NH_DEG_STRIDE(B)), ctx->deg + 4u * NH_DEG_STRIDE(B), slot_key,
-	          d->body_class, bodies->properties, bodies->momentum, d->simple, ctx->body_rec, ctx->body_pos, ctx->sort_seeded ? ctx->sort_sorted_idx : (const uint32_t*)nullptr);
-	if (ctx->hint_capacity < B) {
-		// library-owned, persistent across steps: per body, where its contacts started in the previous step's list (warm-start hint)
-		if (ctx->hint) NH_HIP_CHECK(ctx, hipFree(ctx->hint));
-		ctx->hint = nullptr; ctx->hint_capacity = 0;
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->hint, sizeof(uint32_t) * (size_t)B));
-		NH_HIP_CHECK(ctx, hipMemsetAsync(ctx->hint, 0xFF, sizeof(uint32_t) * (size_t)B, ctx->stream));
-		ctx->hint_capacity = B;
-	}
-	// No host round trip here.  The one-body path (lookup + rows + warm start) runs fused with the first sweeps, and everything that
-	// needs the device counters is finished behind it (finish_setup), by nh_apply_impulses or by the next call that observes
-	// momentum / impulses / counters (nh_flush_pending).
-	d->cont.contacts = *contacts;
-	d->cont.cursor = cursor; d->cont.pred_a = pred_a; d->cont.pred_b = pred_b; d->cont.level = level; d->cont.slot_key = slot_key;
-	d->cont.level_hist = level_hist; d->cont.level_cursor = level_cursor; d->cont.tmp = tmp; d->cont.tent = tent;
-	d->has_static8 = d->has_staticN = d->has_late = false; d->static_inert = false; d->general_lists = true;
-	d->finish_pending = true;
-	d->setup_pending = true; d->imp = imp; d->bodies_at_setup = *bodies;
-	imp->consumed = true;
-	ctx->pending = d;
-	*out = d;
-	return NH_OK;
 }
 
 // The part of setup_contact_constraints that needs the device counters on the host: general adjacency for bodies k_adj_simple left
@@ -2746,22 +2169,6 @@ static void blk_run(nh_context* ctx, nh_ContactConstraintData* d, const nh_BodyD
 	NH_LAUNCH(ctx, "blk_scatter_back", k_blk_scatter_back, nh_grid_for(B, 256, 4096), 256, B, k.brank, k.own_base, (const float4*)k.bm, (float4*)bodies->momentum);
 }
 
-// LOCAL speculation (nh_internal.h): every round trip -- a full step's, a still step's verdict -- tells whether somebody left its inflated box in that step; the
-// movers form of the still step stays on for 16 steps after the last one who did
-static void still_note_movers(nh_context* ctx, const nh_DevState* h, uint32_t seq = 0u) {          // `seq`: the nh_collide the counters belong to (0: a full step's round trip)
-	nh_StillStep& ss = ctx->still;
-	// (a still step in sleepers form that found NOBODY awake: the next step is a full one -- two of those in a row start the asleep steps, which cost nothing)
-	if (ss.sleepers && h->active == 0u) ss.ok_next = false;
-	// (sleepers ahead: how long has the sleeping set stood still?  Counted over confirmed still steps -- `seq` != 0 -- by the active count they report)
-	if (seq != 0u) { if (h->active == ss.sleep_last_active) { if (ss.sleep_stable < 0xffffu) ss.sleep_stable++; } else { ss.sleep_stable = 0u; ss.sleep_last_active = h->active; } }
-	// (... counted by k_pair_owned in the nh_collide numbered pair_owned_seq: counters of an earlier step, or of a full step -- which voids the count -- say nothing)
-	if (ss.pair_owned_seq != 0u && seq >= ss.pair_owned_seq) { if (h->pair_unowned > ctx->pair_list_capacity) ss.pair_world_bad = true; else ss.pair_world_ok = true; }         // (pair ahead: some kept pair is nobody's -- k_pair_owned; the step that relied on it has failed itself)
-	if (h->ahead_multi) ss.ahead_world_bad = true;          // (xform ahead: some body carries several colliders -- k_ahead_check; the step that relied on the map has failed itself)
-	if (h->fat_inserts != ss.seen_inserts) ss.movers_left = 16u;
-	else if (ss.movers_left) ss.movers_left--;
-	ss.seen_inserts = h->fat_inserts; ss.seen_rebuilds = h->fat_rebuilds;
-}
-
 // EARLY COUNTERS (nh_internal.h): the counters the launch numbered `seq` left in the pinned block as it started.  The host polls the word behind them; should the stream run dry
 // without it (a launch that never happened) the ordinary copy answers instead -- nothing can hang here that could not hang in hipStreamSynchronize
 static int read_counts_early(nh_context* ctx, nh_Counts* out, uint32_t seq) {
@@ -2818,7 +2225,7 @@ static int finish_setup(nh_context* ctx, nh_ContactConstraintData* d) {
 		// layout, rules the next step out; a re-insertion switches the movers form on for the steps that follow)
 		const bool local = !ctx->still.no_local && !ctx->env_no_incremental && !ctx->env_no_fat;
 		if ((h->fat_inserts != ctx->still.seen_inserts && !local) || h->fat_rebuilds != ctx->still.seen_rebuilds) ctx->still.ok_next = false;
-		still_note_movers(ctx, h);
+		nh_still_note_movers(ctx, h);
 		// asleep steps (nh_internal.h: nh_AsleepState): was this step the fixed point of a world in which every body is asleep -- nobody active, no contact, every cache
 		// entry kept aside -- and the second one in a row with the same counts?  Then nh_step may take the steps that follow as done (after its own check)
 		nh_AsleepState& as = ctx->asleep;
@@ -2854,7 +2261,7 @@ static int finish_setup(nh_context* ctx, nh_ContactConstraintData* d) {
 		if (rc) return rc;
 		if (c.error) return (int)c.error;
 	}
-	run_cull(ctx, imp, c.sleeping_pairs);
+	nh_run_cull(ctx, imp, c.sleeping_pairs);
 	d->general_contacts = c.general_contacts;
 	ctx->last_general_contacts = c.general_contacts;
 	d->has_static8 = ctx->h_state->has_static8 != 0;
@@ -2862,13 +2269,13 @@ static int finish_setup(nh_context* ctx, nh_ContactConstraintData* d) {
 	d->static_inert = ctx->h_state->static_inert != 0;
 	if (d->has_staticN) {
 		// bodies with more than 8 static contacts are rare: the warm start reads the materialised lookup
-		materialize_lookup(ctx, imp, contacts->bodies, d->body_class);
+		nh_materialize_lookup(ctx, imp, contacts->bodies, d->body_class);
 		NH_LAUNCH(ctx, "setup_staticN", (k_setup_static<true>), nh_grid_for(B, 256, 8192), 256, B, d->body_class, d->body_off, d->adj,
 		          contacts->data, contacts->bodies, imp->data, bodies->transforms, bodies->properties, bodies->momentum, d->rows, (float4*)d->states, (const uint32_t*)nullptr);
 	}
 	if (c.general_contacts) {
 		const uint32_t G = c.general_contacts;
-		materialize_lookup(ctx, imp, contacts->bodies, d->body_class, d->has_staticN ? (const uint32_t*)nullptr : general_list, G);
+		nh_materialize_lookup(ctx, imp, contacts->bodies, d->body_class, d->has_staticN ? (const uint32_t*)nullptr : general_list, G);
 		// a large set in default order with no contact that no block can own: the blocks colour their own contacts (nh_blocks.h, k_blk_prepare_local) --
 		// no world-wide colouring, no adjacency lists of the general bodies
 		if (!(ctx->flags & NH_FLAG_EXACT_ORDER) && !ctx->env_blk_global_colours) {
@@ -3110,7 +2517,7 @@ static int first_apply(nh_context* ctx, nh_ContactConstraintData* d, const nh_Bo
 					memcpy(ctx->h_state, h, NH_COUNTER_WORDS * sizeof(uint32_t));
 					if (!ctx->idle_unknown) { ctx->idle_bound = (int)h->max_idle[ss.verdict.parity]; ctx->idle_bound_mark = ss.verdict.collide_mark; }
 					ss.verdict.pending = false;
-					still_note_movers(ctx, h, ss.verdict.seq);
+					nh_still_note_movers(ctx, h, ss.verdict.seq);
 				}
 				// ... then this step's counters on their way, to be looked at by the next step
 				const int slot = (int)(ctx->collide_seq & 1u);
@@ -3131,7 +2538,7 @@ static int first_apply(nh_context* ctx, nh_ContactConstraintData* d, const nh_Bo
 					ss.confirmed_seq = ctx->collide_seq;
 					memcpy(ctx->h_state, h, NH_COUNTER_WORDS * sizeof(uint32_t));
 					if (!ctx->idle_unknown) { ctx->idle_bound = (int)h->max_idle[ctx->step_parity]; ctx->idle_bound_mark = ctx->collide_mark; }
-					still_note_movers(ctx, h, ctx->collide_seq);
+					nh_still_note_movers(ctx, h, ctx->collide_seq);
 					// (halo split: the step happened -- what the neighbours get of it may leave now, behind the boundary launch on its stream)
 					if (ctx->halo_split.launched && ctx->halo_split.after_verdict) { int rc = ctx->halo_split.after_verdict(ctx, ctx->halo_split.user); if (rc) return rc; }
 				} else {
@@ -3145,7 +2552,7 @@ static int first_apply(nh_context* ctx, nh_ContactConstraintData* d, const nh_Bo
 				if (ctx->timing) nh_timer_collect(ctx);
 				confirmed = ctx->h_state->still_failed_seq < ctx->collide_seq && ctx->h_state->error == 0u;
 				if (confirmed) ss.confirmed_seq = ctx->collide_seq;
-				if (confirmed) { nh_Counts c; nh_counts_from_mirror(ctx, &c); still_note_movers(ctx, ctx->h_state, ctx->collide_seq); }              // (the sleep prediction: largest idle counter this step saw)
+				if (confirmed) { nh_Counts c; nh_counts_from_mirror(ctx, &c); nh_still_note_movers(ctx, ctx->h_state, ctx->collide_seq); }              // (the sleep prediction: largest idle counter this step saw)
 			}
 		}
 		if (confirmed) {
@@ -3191,224 +2598,6 @@ static int first_apply(nh_context* ctx, nh_ContactConstraintData* d, const nh_Bo
 		early4_done = d->static_inert;          // (if body 0 is not inert the speculative launch left at once and the general kernels take everything)
 	}
 	launch_apply_static(ctx, d, bodies, iterations, true, early4_done, drop_states);
-	return NH_OK;
-}
-
-int nh_still_collide_again(nh_context* ctx);       // nh_collide.hip
-int nh_asleep_verify(nh_context* ctx, const nh_BodyData* bodies, const nh_ColliderData* colliders);      // nh_collide.hip
-int nh_still_view_contacts(nh_context* ctx);       // nh_collide.hip: the dense contact list laid out again from the slots (k_gather_contacts, view only)
-
-// ---- the contact cache between its two homes: the caller's arrays (tag order) and the slots (nh_internal.h, contact storage by slot) ------------------------
-// full step -> slots: the solved impulse and feature word of dense contact c go to the raw slot c came from (k_gather_contacts recorded it), every record's count
-__global__ __launch_bounds__(256) void k_cache_to_slots(const nh_DevState* __restrict__ st, const uint32_t* __restrict__ dense_slot, const nh_CachedContactImpulse* __restrict__ imp,
-                                                        const uint32_t* __restrict__ features, const nh_Record* __restrict__ rec, float4* __restrict__ sc_imp, uint32_t* __restrict__ sc_feat,
-                                                        uint32_t* __restrict__ sc_count) {
-	const uint32_t n = st->contacts, nrec = st->records;
-	for (uint32_t c = blockIdx.x * blockDim.x + threadIdx.x; c < n; c += gridDim.x * blockDim.x) {
-		const uint32_t slot = dense_slot[c];
-		sc_imp[slot] = *reinterpret_cast<const float4*>(imp + c);
-		sc_feat[slot] = features[c];
-	}
-	for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < nrec; r += gridDim.x * blockDim.x) { const uint32_t k = rec[r].count; sc_count[r] = (k & NH_REC_SLEEPING) ? 0u : k; }
-}
-
-// entries kept aside for sleeping pairs (the culled arrays of this step's nh_ContactImpulseData: tag order, st->culled of them) -> the slots of the pairs' records.  A
-// record is found by its key -- a sleeping record's key is the pair's word, which is what the cache tag equals for every entry that was kept (k_cull_flags) -- in the
-// tag order of the layout; an entry's place among its record's slots is its place in the run of equal tags (the entries are ranked by feature word, like the slots' export)
-__global__ __launch_bounds__(256) void k_culled_to_slots(const nh_DevState* __restrict__ st, const uint64_t* __restrict__ ctags, const uint32_t* __restrict__ cfeatures,
-                                                         const nh_CachedContactImpulse* __restrict__ cdata, const uint64_t* __restrict__ sorted_keys, const uint32_t* __restrict__ sorted_idx,
-                                                         const nh_Record* __restrict__ rec, uint32_t pair_cap, float4* __restrict__ sc_imp, uint32_t* __restrict__ sc_feat, uint32_t* __restrict__ sc_count) {
-	const uint32_t n = st->culled, nrec = st->records, n_bb = min(st->pairs, pair_cap);
-	for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += gridDim.x * blockDim.x) {
-		const uint64_t t = ctags[j];
-		uint32_t k = 0;                                   // place in the run of equal tags
-		while (k < 4u && j > k && ctags[j - 1u - k] == t) ++k;
-		uint32_t lo = 0, hi = nrec;
-		while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (sorted_keys[mid] < t) lo = mid + 1u; else hi = mid; }
-		if (lo >= nrec || sorted_keys[lo] != t) continue;
-		const uint32_t ri = sorted_idx[lo];
-		if (!(rec[ri].count & NH_REC_SLEEPING)) continue;
-		const bool sph = ri >= n_bb;
-		if (k >= (sph ? 1u : 4u)) continue;
-		const uint32_t base = sph ? 4u * n_bb + (ri - n_bb) : 4u * ri;
-		sc_imp[base + k] = *reinterpret_cast<const float4*>(cdata + j);
-		sc_feat[base + k] = cfeatures[j];
-		if (j + 1u >= n || ctags[j + 1u] != t) sc_count[ri] = k + 1u;          // (the last entry of the run knows how many there are)
-	}
-}
-
-// slots -> the caller's cache arrays, in tag order: counts in tag order (scanned by the host's launch in between), then the entries ranked by feature word
-__global__ __launch_bounds__(256) void k_slot_counts_sorted(const nh_DevState* __restrict__ st, const uint32_t* __restrict__ sorted_idx, const uint32_t* __restrict__ sc_count, uint32_t* __restrict__ out) {
-	const uint32_t nrec = st->records;
-	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i <= nrec; i += gridDim.x * blockDim.x) out[i] = i < nrec ? min(sc_count[sorted_idx[i]], 4u) : 0u;
-}
-
-__global__ __launch_bounds__(256) void k_slots_to_cache(nh_DevState* __restrict__ st, const uint32_t* __restrict__ sorted_idx, const uint64_t* __restrict__ sorted_keys, const uint32_t* __restrict__ cnt,
-                                                        const uint32_t* __restrict__ start, const float4* __restrict__ sc_imp, const uint32_t* __restrict__ sc_feat, uint32_t pair_cap,
-                                                        uint64_t* __restrict__ otags, uint32_t* __restrict__ ofeatures, nh_CachedContactImpulse* __restrict__ odata, uint32_t capacity) {
-	const uint32_t nrec = st->records, n_bb = min(st->pairs, pair_cap);
-	if (blockIdx.x == 0 && threadIdx.x == 0) { const uint32_t total = start[nrec]; if (total > capacity) { st->error = NH_ERR_CACHE_CAPACITY; st->cache = 0u; } else st->cache = total; }
-	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < nrec; i += gridDim.x * blockDim.x) {
-		// two dependent round trips: the record's place and count, then its four slots' feature words and impulses at once (a record of a pair with a sphere owns one
-		// slot: the other three loads fall into the neighbours' slots and are not used)
-		const uint32_t k = min(cnt[i], 4u), ri = sorted_idx[i], first = start[i];
-		const uint64_t key = sorted_keys[i];
-		const uint32_t base = ri < n_bb ? 4u * ri : 4u * n_bb + (ri - n_bb);
-		uint32_t f[4]; float4 w[4];
-#pragma unroll
-		for (int j = 0; j < 4; ++j) { f[j] = sc_feat[base + j]; w[j] = sc_imp[base + j]; }
-		if (!k || first + k > capacity) continue;
-#pragma unroll
-		for (int j = 0; j < 4; ++j) {
-			if ((uint32_t)j < k) {
-				uint32_t r = 0;
-#pragma unroll
-				for (int q = 0; q < 4; ++q) r += ((uint32_t)q < k && (f[q] < f[j] || (f[q] == f[j] && q < j))) ? 1u : 0u;
-				otags[first + r] = key; ofeatures[first + r] = f[j];
-				*reinterpret_cast<float4*>(odata + first + r) = w[j];
-			}
-		}
-	}
-}
-
-// Sleepers form: the slot-cache counts a still narrowphase dropped in a step that did not happen (nh_internal.h: sc_undo) come back.  Called wherever a still step is
-// given up -- failed on the device (still_forget_failed), or left by the caller between its nh_collide and its solver (nh_still_abandon) -- BEFORE the slot cache goes
-// home to the caller's arrays, which is what the full replay warm-starts from.  Notes of confirmed steps (numbers <= confirmed_seq) are simply cleared.
-__global__ __launch_bounds__(256) void k_sleep_undo(uint64_t* __restrict__ sc_undo, uint32_t* __restrict__ sc_count, uint32_t n, uint32_t confirmed_seq) {
-	for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < n; r += gridDim.x * blockDim.x) {
-		const uint64_t u = sc_undo[r];
-		if (u == 0ull) continue;
-		if ((uint32_t)(u >> 32) > confirmed_seq) sc_count[r] = (uint32_t)u;
-		sc_undo[r] = 0ull;
-	}
-}
-
-int nh_still_undo_drops(nh_context* ctx) {
-	nh_StillStep& ss = ctx->still;
-	if (!ss.undo_dirty || !ctx->sc_undo || !ctx->lay_capacity) return NH_OK;
-	ss.undo_dirty = false;
-	NH_LAUNCH(ctx, "sleep_undo", k_sleep_undo, nh_grid_for(ctx->lay_capacity, 256, 2048), 256, ctx->sc_undo, ctx->sc_count, ctx->lay_capacity, ss.confirmed_seq);
-	return NH_OK;
-}
-
-int nh_still_export_cache(nh_context* ctx) {
-	nh_StillStep& ss = ctx->still;
-	if (!ss.cache_stale) return NH_OK;
-	ss.cache_stale = false;
-	nh_DevState* st = ctx->d_state;
-	const uint32_t P = ctx->lay_capacity;
-	// (scratch: the tag-order starts of the dense VIEW are this step's -- a failed still step may already have overwritten them -- so the cache gets its own scan;
-	// dense_slot is free between two full steps)
-	uint32_t* tmp_cnt = ctx->exp_cnt; uint32_t* tmp_start = ctx->exp_start;
-	NH_LAUNCH(ctx, "slot_counts", k_slot_counts_sorted, nh_grid_for(P, 256, 2048), 256, st, ctx->sort_sorted_idx, ctx->sc_count, tmp_cnt);
-	nh_scan_u32(ctx, tmp_cnt, tmp_start, &st->records, 1, ctx->exp_scan_tmp, nullptr);
-	NH_LAUNCH(ctx, "slots_to_cache", k_slots_to_cache, nh_grid_for(P, 256, 4096), 256, st, ctx->sort_sorted_idx, ctx->sort_sorted_keys, tmp_cnt, tmp_start, ctx->sc_imp, ctx->sc_feat, P,
-	          ss.cache.tags, ss.cache.features, ss.cache.data, ss.cache.capacity);
-	return NH_OK;
-}
-
-// ---- views of a world with sleepers (nh_internal.h, "SLEEPERS form"): the list of sleeping pairs and the active list, as a full step would have written them -------
-__global__ __launch_bounds__(256) void k_view_sleep_keys(const nh_DevState* __restrict__ st, const nh_Record* __restrict__ rec, const uint64_t* __restrict__ rec_key, uint64_t* __restrict__ out) {
-	const uint32_t n = st->records;
-	for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < n; r += gridDim.x * blockDim.x) out[r] = (rec[r].count & NH_REC_SLEEPING) ? rec_key[r] : ~0ull;      // (a sleeping record carries the pair's word)
-}
-__global__ __launch_bounds__(256) void k_view_sleep_copy(nh_DevState* __restrict__ st, const uint64_t* __restrict__ sorted, uint64_t* __restrict__ out, uint32_t capacity) {
-	const uint32_t n = st->sleeping;
-	if (n > capacity) { if (blockIdx.x == 0 && threadIdx.x == 0) st->error = NH_ERR_CONTACT_CAPACITY; return; }
-	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) out[i] = sorted[i];
-}
-__global__ __launch_bounds__(256) void k_view_awake_flags(const uint8_t* __restrict__ awake, uint32_t nbodies, uint32_t* __restrict__ flags) {
-	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i <= nbodies; i += gridDim.x * blockDim.x) flags[i] = (i >= 1u && i < nbodies && awake[i]) ? 1u : 0u;
-}
-__global__ __launch_bounds__(256) void k_view_active_write(nh_DevState* __restrict__ st, const uint8_t* __restrict__ awake, const uint32_t* __restrict__ scan, uint32_t nbodies,
-                                                           uint32_t* __restrict__ indices, uint32_t capacity) {
-	for (uint32_t i = 1u + blockIdx.x * blockDim.x + threadIdx.x; i < nbodies; i += gridDim.x * blockDim.x) {
-		if (!awake[i]) continue;
-		const uint32_t at = scan[i];
-		if (at < capacity) indices[at] = i; else st->error = NH_ERR_ACTIVE_CAPACITY;
-	}
-}
-
-static int still_view_sleepers(nh_context* ctx, uint32_t what) {
-	nh_StillStep& ss = ctx->still;
-	nh_DevState* st = ctx->d_state;
-	if (what & NH_VIEW_CONTACTS) {
-		// sleeping pairs in ascending order (nudge.cpp:4008): the words of the sleeping records, sorted -- every other record sorts behind them
-		const uint32_t P = ctx->lay_capacity;
-		if (ss.lay_contacts.sleeping_pairs) {
-			if (ctx->exp_sleep_capacity < P) {
-				void** bufs[] = { (void**)&ctx->exp_sleep_a, (void**)&ctx->exp_sleep_b, (void**)&ctx->exp_sleep_hist };
-				for (void** b : bufs) { if (*b) NH_HIP_CHECK(ctx, hipFree(*b)); *b = nullptr; }
-				ctx->exp_sleep_capacity = 0;
-				NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->exp_sleep_a, sizeof(uint64_t) * (size_t)P + 64u));
-				NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->exp_sleep_b, sizeof(uint64_t) * (size_t)P + 64u));
-				NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->exp_sleep_hist, sizeof(uint32_t) * (256u * NH_SORT_GRID + 512u)));
-				ctx->exp_sleep_capacity = P;
-			}
-			NH_LAUNCH(ctx, "view_sleep_keys", k_view_sleep_keys, nh_grid_for(P, 256, 2048), 256, st, ctx->rec, ctx->sort_keys_by_position, ctx->exp_sleep_a);
-			uint64_t* a = ctx->exp_sleep_a; uint64_t* b = ctx->exp_sleep_b;
-			int bits = (int)ctx->tag_bits; if (bits < 1) bits = 1; if (bits > 32) bits = 32;
-			const int top = ((bits + 7) / 8) * 8;
-			if (nh_sort_u64(ctx, a, b, &st->records, ctx->exp_sleep_hist, 0, top)) { uint64_t* t = a; a = b; b = t; }
-			if (nh_sort_u64(ctx, a, b, &st->records, ctx->exp_sleep_hist, 32, 32 + top)) { uint64_t* t = a; a = b; b = t; }
-			NH_LAUNCH(ctx, "view_sleep_copy", k_view_sleep_copy, nh_grid_for(P, 256, 1024), 256, st, a, ss.lay_contacts.sleeping_pairs, ss.lay_contacts.capacity);
-		}
-	}
-	if ((what & NH_VIEW_ACTIVE) && ss.lay_active && ctx->still_awake) {
-		const uint32_t B = ss.lay_bodies.count;
-		if (ctx->exp_flags_capacity < B + 2u) {
-			if (ctx->exp_flags) NH_HIP_CHECK(ctx, hipFree(ctx->exp_flags));
-			ctx->exp_flags = nullptr; ctx->exp_flags_capacity = 0;
-			NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->exp_flags, sizeof(uint32_t) * ((size_t)B + 66u)));
-			ctx->exp_flags_capacity = B + 2u;
-		}
-		NH_LAUNCH(ctx, "view_awake_flags", k_view_awake_flags, nh_grid_for(B, 256, 2048), 256, ctx->still_awake, B, ctx->exp_flags);
-		nh_scan_u32(ctx, ctx->exp_flags, ctx->exp_flags, &st->pad0 /* always 0 */, B, ctx->exp_scan_tmp, nullptr);
-		NH_LAUNCH(ctx, "view_active_write", k_view_active_write, nh_grid_for(B, 256, 2048), 256, st, ctx->still_awake, ctx->exp_flags, B, const_cast<uint32_t*>(ss.lay_active), ss.lay_active_capacity);
-	}
-	return NH_OK;
-}
-
-int nh_still_sync_outputs(nh_context* ctx, uint32_t what) {
-	nh_StillStep& ss = ctx->still;
-	if (ss.active && !ss.resolved) return NH_OK;          // (an unconfirmed still step is abandoned by the caller first: nh_flush_pending)
-	int rc = NH_OK;
-	if (what & NH_VIEW_CACHE) rc = nh_still_export_cache(ctx);
-	if (rc) return rc;
-	if ((what & NH_VIEW_CONTACTS) && ss.contacts_stale) { ss.contacts_stale = false; rc = nh_still_view_contacts(ctx); if (!rc && ss.views_sleepers) rc = still_view_sleepers(ctx, NH_VIEW_CONTACTS); ss.sleep_pairs_current = true; }
-	else if ((what & NH_VIEW_CONTACTS) && ss.views_sleepers && !ss.sleep_pairs_current) { rc = still_view_sleepers(ctx, NH_VIEW_CONTACTS); ss.sleep_pairs_current = true; }
-	if (rc) return rc;
-	if ((what & NH_VIEW_ACTIVE) && ss.views_sleepers && !ss.active_current) { rc = still_view_sleepers(ctx, NH_VIEW_ACTIVE); ss.active_current = true; }
-	return rc;
-}
-
-extern "C" int nh_export_views(nh_context* ctx, uint32_t what) {
-	if (!ctx || (what & ~(uint32_t)NH_VIEW_ALL)) return NH_ERR_INVALID;          // (NH_VIEW_ALL = contacts | cache | active)
-	NH_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-	{ int rc = nh_flush_pending(ctx, true); if (rc) return rc; }
-	return nh_still_sync_outputs(ctx, what);
-}
-
-// A still step that has not been confirmed, met by anything but the next call of the sample's order (or failed on the device): the step is launched again in full.
-int nh_still_abandon(nh_context* ctx) {
-	nh_StillStep& ss = ctx->still;
-	if (!ss.active || ss.resolved || ss.replaying) return NH_OK;
-	nh_ContactConstraintData* d = ss.setup_d;
-	ss.setup_d = nullptr;
-	int rc = nh_still_undo_drops(ctx);                    // (what this step's narrowphase dropped from the slot cache in sleepers form comes back first)
-	if (rc) return rc;
-	rc = nh_still_export_cache(ctx);                      // (the slot cache holds the last confirmed step's impulses: the full solver reads the caller's arrays)
-	if (rc) return rc;
-	ss.contacts_stale = false;                         // (the replay lays the dense list out itself)
-	rc = nh_still_collide_again(ctx);
-	if (rc) return rc;
-	if (d) {
-		// the adjacency kernel the still setup left out (default order only: still steps are not launched in exact-order mode)
-		const uint32_t B = d->body_count;
-		NH_LAUNCH(ctx, "adjacency_simple", k_adj_simple, nh_grid_for(B, 256, 4096), 256, ctx->d_state, B, ctx->deg, reinterpret_cast<const unsigned long long*>(ctx->deg + 2u * NH_DEG_STRIDE(B)),
-		          ctx->deg + 4u * NH_DEG_STRIDE(B), (const uint32_t*)nullptr, d->body_class, d->bodies_at_setup.properties, d->bodies_at_setup.momentum, d->simple,
-		          ctx->body_rec, ctx->body_pos, ctx->sort_seeded ? ctx->sort_sorted_idx : (const uint32_t*)nullptr);
-	}
 	return NH_OK;
 }
 
@@ -3480,200 +2669,3 @@ extern "C" int nh_update_cached_impulses(nh_context* ctx, nh_ContactConstraintDa
 	return NH_OK;
 }
 
-// ---- halo records (multi-GPU partitions, include/nudge_hip.h) ---------------------------------------------------------------------
-struct nh_HaloRecord { float position[3]; float rotation[4]; float momentum[8]; uint32_t idle; };     // 64 B
-static_assert(sizeof(nh_HaloRecord) == NH_HALO_RECORD_BYTES, "halo record layout");
-
-__global__ __launch_bounds__(256) void k_halo_pack(const nh_Transform* __restrict__ xf, const nh_BodyMomentum* __restrict__ momentum, const uint8_t* __restrict__ idle,
-                                                   const uint32_t* __restrict__ indices, uint32_t count, nh_HaloRecord* __restrict__ out) {
-	for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x) {
-		const uint32_t i = indices[k];
-		const float4 t0 = reinterpret_cast<const float4*>(xf + i)[0], t1 = reinterpret_cast<const float4*>(xf + i)[1];
-		const float4 m0 = reinterpret_cast<const float4*>(momentum + i)[0], m1 = reinterpret_cast<const float4*>(momentum + i)[1];
-		float4* o = reinterpret_cast<float4*>(out + k);
-		o[0] = make_float4(t0.x, t0.y, t0.z, t1.x);
-		o[1] = make_float4(t1.y, t1.z, t1.w, m0.x);
-		o[2] = make_float4(m0.y, m0.z, m0.w, m1.x);
-		o[3] = make_float4(m1.y, m1.z, m1.w, __uint_as_float((uint32_t)idle[i]));
-	}
-}
-
-__global__ __launch_bounds__(256) void k_halo_unpack(nh_Transform* __restrict__ xf, nh_BodyMomentum* __restrict__ momentum, uint8_t* __restrict__ idle,
-                                                     uint32_t first_slot, uint32_t count, const nh_HaloRecord* __restrict__ in) {
-	for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x) {
-		const uint32_t i = first_slot + k;
-		const float4* r = reinterpret_cast<const float4*>(in + k);
-		const float4 a = r[0], b = r[1], c = r[2], d = r[3];
-		nh_Transform* t = xf + i;
-		t->position[0] = a.x; t->position[1] = a.y; t->position[2] = a.z;             // t->body keeps what the owner of the slot put there
-		reinterpret_cast<float4*>(t)[1] = make_float4(a.w, b.x, b.y, b.z);
-		reinterpret_cast<float4*>(momentum + i)[0] = make_float4(b.w, c.x, c.y, c.z);
-		reinterpret_cast<float4*>(momentum + i)[1] = make_float4(c.w, d.x, d.y, d.z);
-		idle[i] = (uint8_t)__float_as_uint(d.w);
-	}
-}
-
-extern "C" int nh_halo_pack(nh_context* ctx, const nh_BodyData* bodies, const uint32_t* indices, uint32_t count, void* out) {
-	if (!ctx || !bodies || (count && (!indices || !out))) return NH_ERR_INVALID;
-	{ int rc = nh_flush_pending(ctx); if (rc) return rc; }
-	if (count) NH_LAUNCH(ctx, "halo_pack", k_halo_pack, nh_grid_for(count, 256, 1024), 256, bodies->transforms, bodies->momentum, bodies->idle_counters, indices, count, (nh_HaloRecord*)out);
-	return NH_OK;
-}
-
-// nh_halo_update: the same for records of the SAME bodies that already occupy those slots, one step further on their owner (the per-step halo of a
-// partitioned world).  Their idle counters rise by at most one per step there as here, so what the last measuring nh_collide saw of them still bounds
-// them: the host's sleep prediction survives (a sleeper the prediction had ruled out is still caught on the device: NH_ERR_STALE_HINT).
-static int halo_unpack(nh_context* ctx, const nh_BodyData* bodies, uint32_t first_slot, uint32_t count, const void* in, bool same_bodies);
-extern "C" int nh_halo_update(nh_context* ctx, const nh_BodyData* bodies, uint32_t first_slot, uint32_t count, const void* in) { return halo_unpack(ctx, bodies, first_slot, count, in, true); }
-extern "C" int nh_halo_unpack(nh_context* ctx, const nh_BodyData* bodies, uint32_t first_slot, uint32_t count, const void* in) { return halo_unpack(ctx, bodies, first_slot, count, in, false); }
-
-static int halo_unpack(nh_context* ctx, const nh_BodyData* bodies, uint32_t first_slot, uint32_t count, const void* in, bool same_bodies) {
-	if (!ctx || !bodies || (count && !in) || (uint64_t)first_slot + count > bodies->count) return NH_ERR_INVALID;
-	{ int rc = nh_flush_pending(ctx); if (rc) return rc; }
-	if (count && !same_bodies) { ctx->idle_bound = -1; ctx->idle_unknown = true; }             // idle counters arrive from another world: nothing is known about them until the next nh_collide has looked
-	if (count) NH_LAUNCH(ctx, "halo_unpack", k_halo_unpack, nh_grid_for(count, 256, 1024), 256, bodies->transforms, bodies->momentum, bodies->idle_counters, first_slot, count, (const nh_HaloRecord*)in);
-	return NH_OK;
-}
-
-// (the two kernels on a stream of the caller's choice, nothing completed, nothing noted: nh_partition_step's exchange beside the interior's solver -- halo split)
-void nh_halo_pack_on(hipStream_t stream, const nh_BodyData* bodies, const uint32_t* indices, uint32_t count, void* out) {
-	if (count) hipLaunchKernelGGL(k_halo_pack, dim3(nh_grid_for(count, 256, 1024)), dim3(256), 0, stream, bodies->transforms, bodies->momentum, bodies->idle_counters, indices, count, (nh_HaloRecord*)out);
-}
-void nh_halo_update_on(hipStream_t stream, const nh_BodyData* bodies, uint32_t first_slot, uint32_t count, const void* in) {
-	if (count) hipLaunchKernelGGL(k_halo_unpack, dim3(nh_grid_for(count, 256, 1024)), dim3(256), 0, stream, bodies->transforms, bodies->momentum, bodies->idle_counters, first_slot, count, (const nh_HaloRecord*)in);
-}
-
-// ---- nh_step: the sample's sub-step loop (example/main.cpp:274-328) as one entry point ----------------------------------------------------------------------
-// The eight calls, `steps` times.  Besides sparing the caller eight crossings of the ABI per step, the library -- driving the call order itself -- may look at a still
-// step's verdict one step late (nh_internal.h: nh_StillStep::pipelined), so that neither the host nor the GPU ever waits for the other inside the loop; a failed
-// still step and the one launched behind it (both did nothing) are simply run again.  On return every step is confirmed.
-int nh_still_verdict_now(nh_context* ctx) {
-	// the pending verdict, waited for: 0 confirmed, 1 failed
-	nh_StillStep& ss = ctx->still;
-	if (!ss.verdict.pending) return 0;
-	const nh_DevState* h = ss.h_ring[ss.verdict.slot];
-	bool seen = false;
-	if (ss.verdict.self_report && !ctx->no_early_counts && !(ctx->timing && ctx->timing_filter.empty())) {
-		// early counters (nh_internal.h): the step's solver left counters and number in the ring slot as it STARTED -- everything a still step can fail on was decided by
-		// then -- so the call's last verdict does not wait for the launch to end (the event is the fallback: a launch that never ran writes no number)
-		volatile const uint32_t* const flag = reinterpret_cast<volatile const uint32_t*>(h) + NH_COUNTER_WORDS;
-		for (uint32_t spins = 0; ; ++spins) {
-			if (*flag == ss.verdict.seq) { seen = true; break; }
-			if ((spins & 255u) == 255u && hipEventQuery(ss.ev_ring[ss.verdict.slot]) != hipErrorNotReady) break;
-			__builtin_ia32_pause();
-		}
-		if (seen) { std::atomic_thread_fence(std::memory_order_acquire); ctx->early_reads++; }
-	}
-	if (!seen && hipEventSynchronize(ss.ev_ring[ss.verdict.slot]) != hipSuccess) return 1;
-	ss.verdict.pending = false;
-	if (h->still_failed_seq >= ss.verdict.seq || h->error) return 1;
-	ss.confirmed_seq = ss.verdict.seq;
-	memcpy(ctx->h_state, h, NH_COUNTER_WORDS * sizeof(uint32_t));
-	if (!ctx->idle_unknown) { ctx->idle_bound = (int)h->max_idle[ss.verdict.parity]; ctx->idle_bound_mark = ss.verdict.collide_mark; }
-	still_note_movers(ctx, h, ss.verdict.seq);
-	return 0;
-}
-
-// after a failed still step: nothing of it (or of the step launched behind it) has happened; the next nh_collide is a full one
-static int still_forget_failed(nh_context* ctx, bool advanced, uint32_t voided) {
-	nh_StillStep& ss = ctx->still;
-	ss.verdict.pending = false;
-	ss.active = false; ss.resolved = false; ss.setup_d = nullptr; ss.ok_next = false; ss.ahead_ready = false; ss.own_current = false;
-	ss.note_failure();
-	if (ss.sleepers) {
-		// (sleepers ahead: somebody fell asleep, most likely.  One sleeper now and then costs the form eight steps; failures in quick succession -- a world dozing off in a
-		// trickle -- double that up to 64)
-		if (ss.sleep_backoff_len < 8u || ss.sleep_run >= 32u) ss.sleep_backoff_len = 8u; else if (ss.sleep_backoff_len < 64u) ss.sleep_backoff_len *= 2u;
-		ss.sleep_backoff = ss.sleep_backoff_len; ss.sleep_stable = 0u; ss.sleep_run = 0u;
-	}
-	ss.failed += voided;                               // (still steps launched that did not happen: the failed one, and the one launched behind it if it got that far)
-	ctx->pending = nullptr;
-	ctx->grav.pending = false; ctx->grav.rest_pending = false; ctx->adv.done = false;
-	ctx->after_collide = false; ctx->gravity_may_overlap = false;
-	if (advanced && ctx->advance_count) ctx->advance_count--;          // (the failed step's nh_advance was counted: the sleep prediction counts real ones)
-	if (advanced) nh_stream_void_advance(ctx);          // (... and so does the state stream; a frame taken at that nh_advance shows the state BEFORE the step: it is withdrawn)
-	{ int rc = nh_still_undo_drops(ctx); if (rc) return rc; }          // (sleepers form: slot-cache counts the voided steps' narrowphases dropped)
-	return nh_still_export_cache(ctx);                                 // (the slot cache holds the last step that DID happen: the full solver reads the caller's arrays)
-}
-
-static bool same_bodies_arrays(const nh_BodyData& a, const nh_BodyData& b) {
-	return a.transforms == b.transforms && a.properties == b.properties && a.momentum == b.momentum && a.idle_counters == b.idle_counters && a.count == b.count;
-}
-static bool same_collider_arrays(const nh_ColliderData& a, const nh_ColliderData& b) {
-	return a.boxes.tags == b.boxes.tags && a.boxes.data == b.boxes.data && a.boxes.transforms == b.boxes.transforms && a.boxes.count == b.boxes.count &&
-	       a.spheres.tags == b.spheres.tags && a.spheres.data == b.spheres.data && a.spheres.transforms == b.spheres.transforms && a.spheres.count == b.spheres.count;
-}
-
-extern "C" int nh_step(nh_context* ctx, const nh_StepArgs* a, uint32_t steps) {
-	if (!ctx || !a || !a->active_bodies || !a->contacts || !a->bodies || !a->colliders || !a->contact_cache) return NH_ERR_INVALID;
-	NH_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-	nh_StillStep& ss = ctx->still;
-	if (!ss.h_ring[0] && !ss.ring_failed) {
-		for (int k = 0; k < 2; ++k) {
-			if (hipHostMalloc((void**)&ss.h_ring[k], sizeof(nh_DevState), 0) != hipSuccess || hipEventCreateWithFlags(&ss.ev_ring[k], hipEventDisableTiming) != hipSuccess) { ss.ring_failed = true; break; }
-			memset(ss.h_ring[k], 0, sizeof(nh_DevState));
-		}
-		if (ss.ring_failed) {
-			// whatever was created goes back, both slots end empty, and the loop runs with the verdict inside every step from now on (no retry per call)
-			for (int k = 0; k < 2; ++k) {
-				if (ss.h_ring[k]) { (void)hipHostFree(ss.h_ring[k]); ss.h_ring[k] = nullptr; }
-				if (ss.ev_ring[k]) { (void)hipEventDestroy(ss.ev_ring[k]); ss.ev_ring[k] = nullptr; }
-			}
-		}
-	}
-	// (per-kernel timing of EVERY launch collects its events at the step's round trip; timing restricted to one kernel -- nh_set_timing_filter: two events per step, what
-	// bench.py keeps on during its timed region -- leaves the loop as it is: the events are collected when the call's last verdict has been waited for)
-	ss.pipelined = ss.h_ring[0] != nullptr && (ctx->flags & NH_FLAG_FUSED_STEP) && !(ctx->flags & (NH_FLAG_SYNC_COUNTS | NH_FLAG_EXACT_ORDER)) && !ss.disabled &&
-	               !(ctx->timing && ctx->timing_filter.empty()) &&
-	               !ctx->step_hook;          // (nh_partition_step: what a step sends to the neighbours must be a step that HAPPENED -- its verdict is looked at inside the step)
-	ss.verdict.pending = false;
-	ss.ahead_map_ok = false; ss.ahead_ready = false;          // (xform ahead, nh_internal.h: nothing carries over from another call -- the caller may have changed anything in between)
-	int result = NH_OK;
-	uint32_t i = 0;
-	while (i < steps || ss.verdict.pending) {
-		if (i >= steps) {
-			// the last step's verdict, waited for; a failure sends the loop back one step
-			if (nh_still_verdict_now(ctx) == 0) break;
-			{ int rc = still_forget_failed(ctx, true, 1u); if (rc) { result = rc; break; } }
-			i -= 1;
-			continue;
-		}
-		// A world asleep (nh_internal.h: nh_AsleepState): two full steps in a row were its fixed point.  ONE check per call that nothing the caller owns has changed since
-		// -- and the remaining steps of this call are done: nothing inside the library wakes a world in which nobody is awake.
-		// (never inside nh_partition_step: the neighbours expect this rank's halo before every sub-step, whether anything moves here or not)
-		if (ctx->asleep.streak >= 2u && !ctx->asleep.disabled && !ctx->step_hook && !ss.verdict.pending && !ctx->pending && (ctx->flags & NH_FLAG_FUSED_STEP) && !(ctx->flags & NH_FLAG_SYNC_COUNTS) && !ctx->timing &&
-		    same_bodies_arrays(*a->bodies, ss.lay_bodies) && same_collider_arrays(*a->colliders, ss.lay_colliders) && a->contacts->data == ss.lay_contacts.data && a->contacts->tags == ss.lay_contacts.tags &&
-		    a->contacts->sleeping_pairs == ss.lay_contacts.sleeping_pairs && a->active_bodies->indices == ss.lay_active && a->contact_cache->data == ss.cache_data && a->contact_cache->tags == ss.cache_tags && a->contact_cache->features == ss.cache_features) {
-			const int v = nh_asleep_verify(ctx, a->bodies, a->colliders);
-			if (v < 0) { result = -v; break; }
-			if (v == 0) { ss.sleep_backoff = ss.sleep_backoff > steps - i ? ss.sleep_backoff - (steps - i) : 0u; ctx->asleep.steps += steps - i; if (ctx->stream_state.every) ctx->stream_state.advances += steps - i; i = steps; continue; }          // (no frames: nothing moves)
-			ctx->asleep.streak = 0;
-		}
-		int rc;
-		if (ctx->step_hook && (rc = ctx->step_hook(ctx, ctx->step_hook_user, i))) { result = rc; break; }
-		ss.more_steps = i + 1u < steps; ss.steps_left = steps - 1u - i; ss.substep = i;
-		nh_Arena temporary = a->arena;
-		nh_ContactImpulseData* imp = nullptr;
-		nh_ContactConstraintData* con = nullptr;
-		if ((rc = nh_collide(ctx, a->active_bodies, a->contacts, a->bodies, a->colliders, a->body_connections, temporary)) ||
-		    (rc = nh_apply_gravity_damping(ctx, a->active_bodies, a->bodies, a->time_step, a->gravity, a->damping_rate)) ||
-		    (rc = nh_read_cached_impulses(ctx, a->contact_cache, a->contacts, &temporary, &imp)) ||
-		    (rc = nh_setup_contact_constraints(ctx, a->active_bodies, a->contacts, a->bodies, imp, &temporary, &con)) ||
-		    (rc = nh_apply_impulses(ctx, con, a->bodies, a->iterations))) {
-			if (rc == NH_INTERNAL_STILL_FAILED && i > 0) {
-				// the still step before this one failed: neither it nor this one has happened
-				{ int rc2 = still_forget_failed(ctx, true, ctx->still.active ? 2u : 1u); if (rc2) { result = rc2; break; } }
-				i -= 1;
-				continue;
-			}
-			result = rc == NH_INTERNAL_STILL_FAILED ? NH_ERR_INVALID : rc;
-			break;
-		}
-		if ((rc = nh_update_cached_impulses(ctx, con, imp)) || (rc = nh_write_cached_impulses(ctx, a->contact_cache, a->contacts, imp)) ||
-		    (rc = nh_advance(ctx, a->active_bodies, a->bodies, a->time_step))) { result = rc; break; }
-		++i;
-	}
-	ss.pipelined = false; ss.more_steps = false; ss.ahead_ready = false; ss.ahead_map_ok = false; ss.steps_left = 0u; ss.substep = 0u; ss.own_current = false;
-	if (result && ss.verdict.pending) { hipEventSynchronize(ss.ev_ring[ss.verdict.slot]); ss.verdict.pending = false; }
-	return result;
-}
