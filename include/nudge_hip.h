@@ -79,7 +79,7 @@
  *      exported the views: nh_set_option(ctx, "sync_exports_views", 1) restores that contract at its old price; INTEGRATION.md.)  Any entry point outside the sample's
  *      call order between nh_collide and nh_apply_impulses turns a still step into a full one first, so everything it observes is what a full step
  *      produces.  nh_Counts.still_steps / still_replays count them.
- *      The scene queries (nh_query_build, nh_query_refit, nh_raycast, nh_spherecast, nh_raycast_all, nh_spherecast_all, nh_boxcast, nh_capsulecast, nh_overlap, nh_penetration, nh_closest, nh_closest_k) are not entry points of the step in this sense: they neither export nor settle nor turn a still step into a
+ *      The scene queries (nh_query_build, nh_query_refit, nh_raycast, nh_spherecast, nh_raycast_all, nh_spherecast_all, nh_boxcast_all, nh_capsulecast_all, nh_boxcast, nh_capsulecast, nh_overlap, nh_penetration, nh_closest, nh_closest_k) are not entry points of the step in this sense: they neither export nor settle nor turn a still step into a
  *      full one, and they do not count -- see "scene queries" below.
  *
  * Threading: one context = one HIP stream = one world at a time; no global mutable state.
@@ -457,7 +457,8 @@ int nh_spherecast(nh_context* ctx, const nh_SphereCast* casts, uint32_t count, n
    the origin, so that no collider the ray predicates accept by rounding is pruned; the records are then ordered by one radix sort where
    bits(count) + 32 + bits(colliders) <= 64 and by two otherwise.  NOT MEASURED YET: tools/castall_rates.py times both calls (count only, count + list) on the landed config-2 world beside nh_raycast / nh_spherecast on the same records
    and nh_overlap in list mode, and writes profiles/castall_rates.log; no GPU run of it has been made, so neither ratio (count walk / closest-hit cast, list chain / nh_overlap's per record) is known.
-   Not built: all-hits box and capsule casts, exits, a per-query hit limit ("the first k"). */
+   The all-hits casts of the other two shapes: nh_boxcast_all / nh_capsulecast_all, declared behind nh_capsulecast, whose records they read.
+   Not built: exits, a per-query hit limit ("the first k"). */
 int nh_raycast_all(nh_context* ctx, const nh_Ray* rays, uint32_t count, uint32_t* offsets /* count + 1 */, nh_RayHit* hits, uint32_t capacity,
                    uint32_t flags /* 0 */);
 int nh_spherecast_all(nh_context* ctx, const nh_SphereCast* casts, uint32_t count, uint32_t* offsets /* count + 1 */, nh_RayHit* hits, uint32_t capacity,
@@ -519,6 +520,48 @@ int nh_boxcast(nh_context* ctx, const nh_BoxCast* casts, uint32_t count, nh_RayH
 typedef struct nh_CapsuleCast { float origin[3]; float max_t; float direction[3]; uint32_t ignore_body;
                                 float rotation[4]; float radius; float half_height; uint32_t reserved[2]; } nh_CapsuleCast;                           /* 64 B */
 int nh_capsulecast(nh_context* ctx, const nh_CapsuleCast* casts, uint32_t count, nh_RayHit* hits, uint32_t flags /* 0 or NH_RAY_ANY_HIT */);
+
+/* nh_boxcast_all / nh_capsulecast_all: EVERY collider of the LAST nh_query_build that a swept oriented box (a swept capsule) touches, ordered along the
+   cast -- a controller that slides past what it filters by tag, a push that wants every crate it will shove, a stand-up test that lists what is overhead.
+   Input records are nh_boxcast's / nh_capsulecast's (64 B), output records nh_RayHit; everything else is nh_raycast_all's contract:
+     - THE SET of cast i: every box and sphere collider of the last build or refit (those of sleeping bodies and of body 0 included), less the colliders of
+       `ignore_body`, on which the closest-hit call has a hit with 0 <= t <= max_t.  It is the test nh_boxcast / nh_capsulecast make at a leaf with no best
+       hit so far (nh_q_all_hit_box / nh_q_all_hit_capsule, nudge_amd/csrc/nh_query.h): the predicates nh_q_sweep_box_box / nh_q_sweep_box_sphere and
+       nh_q_sweep_capsule_box / nh_q_sweep_capsule_sphere, and for a shape with a size -- a box of nonzero size, a capsule unless r = hh = 0 -- the reach
+       rule applied to the collider's OWN box in the hierarchy (nh_q_leaf_box) grown per axis by the cast's world AABB half extent and pad under
+       nh_q_cast_node3 (nh_q_leaf_entry3): that box must be entered, and t = max(t of the predicate, the entry).  So a brute force over all colliders gives
+       the same set.  ONE record per collider: its entry.  A shape that starts in overlap with a collider hits it at t = 0 with normal = -d / |d|, as in the
+       closest-hit calls.  Exits are not reported.  A collider of a NaN pose is never hit;
+     - THE RECORD of a hit is byte for byte what nh_boxcast / nh_capsulecast with flags = 0 would write if that collider were the only one;
+     - THE ORDER within cast i: ascending t compared as floats (-0 equals +0), ties by COMBINED collider index ascending (boxes 0 .. nbox-1, then the spheres);
+     - FIRST RECORD = CLOSEST HIT, a contract: where offsets[i+1] > offsets[i], hits[offsets[i]] holds exactly the 32 bytes nh_boxcast (nh_capsulecast)
+       with flags = 0 writes for the same record on the same build or refit; where the segment is empty, that call writes a miss;
+     - DEGENERATE SHAPES write the bytes of the simpler all-hits call, offsets and records: a box of size (0, 0, 0) those of nh_raycast_all for the same first
+       32 bytes, its rotation not read; a capsule of half_height 0 those of nh_spherecast_all for the same first 32 bytes and radius, its rotation not
+       read; a capsule of radius = half_height = 0 those of nh_raycast_all.  In exactly these ray-like cases -- no size at all -- the walk grows every node
+       box by 2^-9 of its distance from the origin, as nh_raycast_all's does; with a size, the reach rule makes the set a function of the leaf test alone;
+     - offsets[0 .. count] (count + 1 words) by the exclusive scan of the per-cast counts: offsets[i] = the records before cast i, offsets[count] = the
+       total; the records of cast i are hits[offsets[i] .. offsets[i+1]);
+     - COUNT ONLY: hits == NULL and capacity == 0 write offsets alone (count, read offsets[count], allocate, list);
+     - CAPACITY: the records of cast i are written if and only if offsets[i+1] <= capacity -- the written part is a prefix of whole segments, every byte of
+       `hits` behind it is left untouched, and `offsets` is always complete;
+     - a true total of 2^32 - 1 or more writes offsets[count] = 0xffffffff and no record at all (the other offsets are then unspecified), as in nh_overlap;
+     - an INVALID record counts 0 -- exactly the records the closest-hit call writes with t = NaN: a non-finite origin, direction or size (radius, half
+       height), a negative size, a non-finite rotation where the rotation is read.  A NaN max_t lists nothing (t <= NaN is false).  A zero direction lists
+       the colliders the shape overlaps at t = 0, with the NaN normal, and nothing else.
+   Returns NH_ERR_INVALID before any nh_query_build, for flags != 0 (NH_RAY_ANY_HIT included: it has no meaning here), for `casts` null or not 16-byte
+   aligned, `offsets` null or not 4-byte aligned, `hits` null with capacity > 0 or not 16-byte aligned, and for count >= 2^30 -- nh_overlap's checks in
+   nh_overlap's order; count = 0 is a no-op that returns NH_OK.
+   An OBSERVER like nh_raycast (note 9): no view export, no settling of deferred gravity, no still step turned into a full one, no change to nh_Counts.
+   Everything is enqueued on the context's stream, except that a larger capacity than any before grows the library's sort scratch after a stream
+   synchronise: the scratch is nh_overlap's own, and nothing else is allocated.
+   Cost: nh_raycast_all's chain with the box's / the capsule's predicates at the leaves -- the walk prunes by max_t only and runs twice (count, list), then
+   one or two radix sorts and a gather that evaluates the predicate a third time for the written records (figures, or NOT MEASURED YET).
+   Not built: exits, a per-query hit limit ("the first k"), rotating sweeps. */
+int nh_boxcast_all(nh_context* ctx, const nh_BoxCast* casts, uint32_t count, uint32_t* offsets /* count + 1 */, nh_RayHit* hits, uint32_t capacity,
+                   uint32_t flags /* 0 */);
+int nh_capsulecast_all(nh_context* ctx, const nh_CapsuleCast* casts, uint32_t count, uint32_t* offsets /* count + 1 */, nh_RayHit* hits, uint32_t capacity,
+                       uint32_t flags /* 0 */);
 
 /* nh_closest: how far each of `count` points lies from the world of the LAST nh_query_build, and where the nearest surface is -- depenetration, "snap to
    the nearest surface", proximity and cover tests, keeping a distance from everything.  `reserved` is not read.  Exact predicates: nudge_amd/csrc/nh_query.h.

@@ -966,7 +966,7 @@ NH_HD nh_QPen nh_q_pen_capsule_box(nh_f3 c, nh_quat q, float r, float hh, nh_f3 
 	return nh_q_pen_capsule_box_a(c, nh_q_capsule_axis(q, hh), r, p, qb, hb);
 }
 
-// ---- all-hits casts (nh_raycast_all / nh_spherecast_all): the hit of ONE collider, as the closest-hit walk decides it at a leaf with no best so far --
+// ---- all-hits casts (nh_raycast_all / nh_spherecast_all / nh_boxcast_all / nh_capsulecast_all): the hit of ONE collider, as the closest-hit walk decides it at a leaf with no best so far --
 // The ray's own predicates (SWEEP = false) or the swept ball's with the reach rule for r > 0 (SWEEP = true; t0 = the entry into the collider's leaf box
 // under nh_q_cast_node, w = r + nh_q_cast_pad), then 0 <= t <= max_t (nh_q_better against nothing).  The count walk, the list walk and the gather call
 // this one function on the same inputs, so all three get the same bits; the host's brute force calls it too.
@@ -991,6 +991,33 @@ NH_HD bool nh_q_leaf_entry(nh_f3 o, nh_f3 inv, float w, nh_f3 p, nh_quat q, nh_f
 	return nh_q_cast_node(lo, hi, o, inv, w, t0);
 }
 
+// nh_boxcast_all / nh_capsulecast_all: the same decision for the cast box (qa, ha) and the capsule (qa, r, hh) -- nh_QBox::leaf / nh_QCapsule::leaf
+// (nh_query.hip) at a leaf with no best hit so far, then 0 <= t <= max_t.  t0 = the entry into the collider's leaf box under nh_q_cast_node3 with the cast's
+// per-axis grow (nh_q_leaf_entry3 rebuilds it); it is read exactly where the closest-hit leaf reads it: for a box of nonzero size, and for a capsule
+// unless r = hh = 0.  A size-0 box is nh_q_all_hit<false> and a capsule of hh = 0 nh_q_all_hit<true>, bit for bit, through the predicates' own first
+// lines.  The count walk, the list walk, the gather and the host's brute force call these on the same inputs.
+NH_HD nh_QHit nh_q_all_hit_box(nh_f3 o, nh_f3 d, nh_quat qa, nh_f3 ha, float max_t, float t0, nh_f3 p, nh_quat q, nh_f3 h, bool box) {
+	nh_QHit s = box ? nh_q_sweep_box_box(o, d, qa, ha, p, q, h) : nh_q_sweep_box_sphere(o, d, qa, ha, p, h.x);
+	const bool ray = ha.x == 0.0f && ha.y == 0.0f && ha.z == 0.0f;
+	if (!ray && t0 > s.t) s.t = t0;
+	s.hit = s.hit && nh_q_better(s.t, 0u, max_t, max_t, 0xffffffffu);
+	return s;
+}
+
+NH_HD nh_QHit nh_q_all_hit_capsule(nh_f3 o, nh_f3 d, nh_quat qa, float r, float hh, float max_t, float t0, nh_f3 p, nh_quat q, nh_f3 h, bool box) {
+	nh_QHit s = box ? nh_q_sweep_capsule_box(o, d, qa, r, hh, p, q, h) : nh_q_sweep_capsule_sphere(o, d, qa, r, hh, p, h.x);
+	if ((r > 0.0f || hh > 0.0f) && t0 > s.t) s.t = t0;
+	s.hit = s.hit && nh_q_better(s.t, 0u, max_t, max_t, 0xffffffffu);
+	return s;
+}
+
+// nh_q_leaf_entry under the per-axis grow w of a box or capsule cast (nh_q_cast_node3).  With the same w on every axis it is nh_q_leaf_entry to the bit.
+NH_HD bool nh_q_leaf_entry3(nh_f3 o, nh_f3 inv, nh_f3 w, nh_f3 p, nh_quat q, nh_f3 h, bool box, float& t0) {
+	nh_f3 lo, hi;
+	nh_q_leaf_box(p, q, h, box, lo, hi);
+	return nh_q_cast_node3(lo, hi, o, inv, w, t0);
+}
+
 // The all-hits walk's node pad for a RAY (r = 0).  The closest-hit ray walk prunes with boxes padded by 2^-18 of the coordinates, which does not bound the
 // rounding of the ray predicates: nh_q_ray_sphere accepts where the computed b*b - a*(m.m - R*R) >= 0, and with |m| = |o - c| the roundings of that
 // expression sum to under 32 * 2^-24 * |m|^2 |d|^2 (three rounded products and sums per dot product, the squares, the product with a and the
@@ -999,7 +1026,8 @@ NH_HD bool nh_q_leaf_entry(nh_f3 o, nh_f3 inv, float w, nh_f3 p, nh_quat q, nh_f
 // 2^-24 of |m| + |h| in the box frame), far below that.  A closest-hit call loses such a far grazing hit only where it is the closest; the all-hits set
 // is every collider the predicate accepts, so its walk grows each node box by 2^-9 of L, an upper bound (the 1-norm) of the distance from the origin to
 // the farthest point of the box: L >= |m| for every collider whose leaf box lies inside, L and the grown box are monotone in the box, so no ancestor
-// prunes what a leaf would accept.  (Sphere casts of r > 0 need none of this: the reach rule makes their set a function of the leaf test.)
+// prunes what a leaf would accept.  (Casts of a shape with a size -- r > 0, a box of nonzero size, a capsule unless r = hh = 0 -- need none of this: the reach rule makes their set a
+// function of the leaf test.  A box of size 0 and a capsule of r = hh = 0 are rays and take the pad.)
 NH_HD float nh_q_all_pad(nh_f3 lo, nh_f3 hi, nh_f3 o) {
 	const float fx = fmaxf(fabsf(lo.x - o.x), fabsf(hi.x - o.x)), fy = fmaxf(fabsf(lo.y - o.y), fabsf(hi.y - o.y)), fz = fmaxf(fabsf(lo.z - o.z), fabsf(hi.z - o.z));
 	return ((fx + fy) + fz) * 0.001953125f;

@@ -346,7 +346,9 @@ __device__ __forceinline__ void nh_q_walk(const nh_QNode* __restrict__ nodes, co
 // things: read() -- the decode, `ok` (every field it reads is finite and no size is negative) and the grow w of the node boxes; node() -- the node
 // test, nh_q_cast_node / nh_q_cast_node3 (nh_query.h) under that grow; leaf() -- the two predicates of nh_query.h and, for a shape with a size, the
 // reach rule: the hit is at max(t_pred, the leaf's entry t0), which is what makes the pruning exact.  The all-hits kernels below read
-// their rays and balls through the same structs.
+// their casts through the same structs, and each shape gives them three more: raylike() -- the shape has no size, so the set is the predicates' and the
+// walk adds nh_q_all_pad to grow(), the one number its grow then is; all() -- the per-collider decision of nh_query.h (leaf() and then 0 <= t <= max_t); entry() -- the leaf entry t0 rebuilt where
+// all() reads it, for the gather, which has no walk to take it from.  ALL_WAVES is the waves-per-EU hint of the all-hits kernels (0: none).
 struct nh_QCastHead {
 	nh_f3 o, d, inv;
 	float max_t;
@@ -373,6 +375,11 @@ struct nh_QRay : nh_QCastHead {
 	__device__ __forceinline__ nh_QHit leaf(const nh_QShape& c, bool box, float) const {
 		return box ? nh_q_ray_box(o, d, c.p, c.q, c.h) : nh_q_ray_sphere(o, d, c.p, c.h.x);
 	}
+	static constexpr int ALL_WAVES = 0;
+	__device__ __forceinline__ bool raylike() const { return true; }
+	__device__ __forceinline__ float grow() const { return w; }
+	__device__ __forceinline__ void entry(const nh_QShape&, bool, float&) const {}
+	__device__ __forceinline__ nh_QHit all(const nh_QShape& c, bool box, float t0) const { return nh_q_all_hit<false>(o, d, r, max_t, t0, c.p, c.q, c.h, box); }
 };
 
 // nh_SphereCast: every node box grown by w = r + pad.  r = 0 walks and answers as the ray does.
@@ -391,6 +398,11 @@ struct nh_QBall : nh_QCastHead {
 		if (r > 0.0f && t0 > hit.t) hit.t = t0;
 		return hit;
 	}
+	static constexpr int ALL_WAVES = 0;
+	__device__ __forceinline__ bool raylike() const { return !(r > 0.0f); }
+	__device__ __forceinline__ float grow() const { return w; }
+	__device__ __forceinline__ void entry(const nh_QShape& c, bool box, float& t0) const { if (r > 0.0f) nh_q_leaf_entry(o, inv, w, c.p, c.q, c.h, box, t0); }
+	__device__ __forceinline__ nh_QHit all(const nh_QShape& c, bool box, float t0) const { return nh_q_all_hit<true>(o, d, r, max_t, t0, c.p, c.q, c.h, box); }
 };
 
 // nh_BoxCast: the node box grown per axis by the cast box's world AABB half extent plus the pad.  Size 0 (`ray`) walks and answers as the
@@ -416,6 +428,11 @@ struct nh_QBox : nh_QCastHead {
 		if (!ray && t0 > hit.t) hit.t = t0;
 		return hit;
 	}
+	static constexpr int ALL_WAVES = 4;
+	__device__ __forceinline__ bool raylike() const { return ray; }
+	__device__ __forceinline__ float grow() const { return w.x; }          // (ray-like: the three are one number, the ray's)
+	__device__ __forceinline__ void entry(const nh_QShape& c, bool box, float& t0) const { if (!ray) nh_q_leaf_entry3(o, inv, w, c.p, c.q, c.h, box, t0); }
+	__device__ __forceinline__ nh_QHit all(const nh_QShape& c, bool box, float t0) const { return nh_q_all_hit_box(o, d, qa, h, max_t, t0, c.p, c.q, c.h, box); }
 };
 
 // nh_CapsuleCast: the box cast's node test with the capsule's world AABB half extent |a_k| + r, the reach rule unless r = hh = 0.  hh = 0
@@ -440,6 +457,11 @@ struct nh_QCapsule : nh_QCastHead {
 		if ((r > 0.0f || hh > 0.0f) && t0 > hit.t) hit.t = t0;
 		return hit;
 	}
+	static constexpr int ALL_WAVES = 4;
+	__device__ __forceinline__ bool raylike() const { return r == 0.0f && hh == 0.0f; }
+	__device__ __forceinline__ float grow() const { return w.x; }
+	__device__ __forceinline__ void entry(const nh_QShape& c, bool box, float& t0) const { if (r > 0.0f || hh > 0.0f) nh_q_leaf_entry3(o, inv, w, c.p, c.q, c.h, box, t0); }
+	__device__ __forceinline__ nh_QHit all(const nh_QShape& c, bool box, float t0) const { return nh_q_all_hit_capsule(o, d, qa, r, hh, max_t, t0, c.p, c.q, c.h, box); }
 };
 
 // One nh_RayHit, as two 16-byte stores: collider c hit at t with normal n, or, for c = NH_Q_NONE, the miss record, whose t is the cast's max_t (the
@@ -796,12 +818,13 @@ __global__ __launch_bounds__(256) void k_q_penetration_gather(const uint64_t* __
 }
 
 // ---- all-hits casts ---------------------------------------------------------------------------------------------------------------------------
-// nh_raycast_all / nh_spherecast_all: every collider a cast passes through, ordered along the cast.  nh_overlap's chain (kernel boundaries are the
+// nh_raycast_all / nh_spherecast_all / nh_boxcast_all / nh_capsulecast_all: every collider a cast passes through, ordered along the cast.  nh_overlap's chain (kernel boundaries are the
 // only hand-offs, no atomic decides where a record goes) with the casts' walk in place of the volume walk and an ordering by t behind it:
-//   k_q_castall<S, false>  one lane per cast: the ray's (S = false) / the ball's (S = true) decode and node test in nh_q_walk, with the pruning bound FIXED at
-//                       max_t -- there is no best hit to tighten it -- and nh_q_all_hit at every entered leaf; offsets[i] = the number of hits.
-//                       For a ray (and r = 0) every node box is grown by nh_q_all_pad as well: the set is every collider the PREDICATE accepts, and the
-//                       closest-hit walk's pad does not cover the predicates' rounding at a distance (nh_query.h)
+//   k_q_castall<S, false>  one lane per cast: the decode and node test of the shape S (nh_QRay, nh_QBall, nh_QBox, nh_QCapsule) in nh_q_walk, with the pruning
+//                       bound FIXED at max_t -- there is no best hit to tighten it -- and S::all at every entered leaf; offsets[i] = the number of hits.
+//                       For a ray-like shape (a ray, r = 0, a box of size 0, a capsule of r = hh = 0) every node box is grown by nh_q_all_pad as well: the
+//                       set is every collider the PREDICATE accepts, and the closest-hit walk's pad does not cover the predicates' rounding at a distance
+//                       (nh_query.h).  A shape with a size needs none: its reach rule makes the set a function of the leaf test
 //   nh_scan_u32, k_q_overlap_fix, k_q_overlap_fin   nh_overlap's own (nh_overlap_offsets)
 //   k_q_castall<S, true>   the same walk (the same template: the same set) for the casts whose segment fits; hit k of cast i goes to offsets[i] + k
 //   the ordering by (cast, t, combined collider index), one of
@@ -810,14 +833,13 @@ __global__ __launch_bounds__(256) void k_q_penetration_gather(const uint64_t* __
 //                (LSD: the least significant part first); k_q_castall_rekey to key (i << 32) | tbits, value c; a second, stable nh_sort_u64_u32 over
 //                32 + bits(count) bits, whose stability carries the index order into the ties of t
 //   k_q_castall_gather<S>  one lane per written record: the cast index from the key, the collider from the value; it re-reads the cast and the 48-byte
-//                       collider record and evaluates nh_q_all_hit again -- the same function on the same inputs, the leaf entry of the reach rule
-//                       rebuilt by nh_q_leaf_entry as the build stores it -- and writes nh_RayHit as two 16-byte stores.  No normal goes through a sort.
-// the ray's and the ball's decode, validity and grow are the closest-hit casts' own: radius 0 gives the ray's bytes, and the first record of a cast is
-// the closest-hit record
-template <bool SWEEP> using nh_QCastAll = std::conditional_t<SWEEP, nh_QBall, nh_QRay>;
-
-template <bool SWEEP, bool LIST>
-__global__ __launch_bounds__(256) void k_q_castall(const float4* __restrict__ casts, uint32_t count, uint32_t* offsets,
+//                       collider record and evaluates S::all again -- the same function on the same inputs, the leaf entry of the reach rule
+//                       rebuilt by S::entry (nh_q_leaf_entry / nh_q_leaf_entry3) as the build stores it -- and writes nh_RayHit as two 16-byte stores.  No
+//                       normal goes through a sort.
+// every shape's decode, validity and grow are the closest-hit casts' own: a shape without a size gives the ray's bytes, a capsule of hh = 0 the ball's, and
+// the first record of a cast is the closest-hit record.  The box and capsule instantiations take their closest-hit siblings' waves-per-EU hint (ALL_WAVES)
+template <class Shape, bool LIST>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(Shape::ALL_WAVES))) void k_q_castall(const float4* __restrict__ casts, uint32_t count, uint32_t* offsets,
                                                    const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox,
                                                    nh_QCtl* ctl, uint64_t* __restrict__ keys, uint32_t* __restrict__ vals, uint32_t cbits, uint32_t one_sort) {
 	if (!LIST && blockIdx.x == 0 && threadIdx.x == 0) { offsets[count] = 0u; ctl->ov_wrap = 0u; ctl->ov_written = 0u; }   // (k_q_overlap_fix sets both)
@@ -828,19 +850,18 @@ __global__ __launch_bounds__(256) void k_q_castall(const float4* __restrict__ ca
 			base = offsets[i]; end = offsets[i + 1u];
 			if (!(base < end && end <= written)) continue;          // empty, or not in the written prefix
 		}
-		nh_QCastAll<SWEEP> k;
-		k.read(casts + (size_t)i * k.WORDS);
-		const bool ray = !SWEEP || !(k.r > 0.0f);
+		Shape k;
+		k.read(casts + (size_t)i * Shape::WORDS);
+		const bool ray = k.raylike();
 		uint32_t hits = 0u;
 		nh_q_walk(nodes, rec, k.ok && n ? 0u : NH_Q_NONE, k.ignore,
 			[&](nh_f3 lo, nh_f3 hi, float& t0) {
-				// (a ray's node box also takes the predicates' own rounding, nh_q_all_pad; a ball's reach rule reads the entry of the box as the build stores it)
-				const float w = ray ? k.w + nh_q_all_pad(lo, hi, k.o) : k.w;
-				return nh_q_cast_node(lo, hi, k.o, k.inv, w, t0) && t0 <= k.max_t;
+				// (a ray's node box also takes the predicates' own rounding, nh_q_all_pad; a sized shape's reach rule reads the entry of the box as the build stores it)
+				if (ray) return nh_q_cast_node(lo, hi, k.o, k.inv, k.grow() + nh_q_all_pad(lo, hi, k.o), t0) && t0 <= k.max_t;
+				return k.node(lo, hi, t0) && t0 <= k.max_t;
 			},
 			[&](uint32_t c, const nh_QRec& q, float t0) {
-				const nh_QShape s = nh_q_unpack(q);
-				const nh_QHit h = nh_q_all_hit<SWEEP>(k.o, k.d, k.r, k.max_t, t0, s.p, s.q, s.h, c < nbox);
+				const nh_QHit h = k.all(nh_q_unpack(q), c < nbox, t0);
 				if (!h.hit) return false;
 				if (LIST) {
 					// (the count pass found exactly end - base: the segment is full once they are written, nothing else can follow)
@@ -867,8 +888,8 @@ __global__ __launch_bounds__(256) void k_q_castall_rekey(uint64_t* __restrict__ 
 	}
 }
 
-template <bool SWEEP>
-__global__ __launch_bounds__(256) void k_q_castall_gather(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, const nh_QCtl* __restrict__ ctl,
+template <class Shape>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(Shape::ALL_WAVES))) void k_q_castall_gather(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, const nh_QCtl* __restrict__ ctl,
                                                           const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox,
                                                           const float4* __restrict__ casts, uint32_t count, uint32_t ishift, nh_RayHit* __restrict__ hits) {
 	const uint32_t m = ctl->ov_written;
@@ -876,12 +897,12 @@ __global__ __launch_bounds__(256) void k_q_castall_gather(const uint64_t* __rest
 		const uint32_t c = vals[j];
 		const uint64_t i = keys[j] >> ishift;
 		if (c >= n || i >= count) continue;          // (cannot happen: the list pass fills the whole prefix; a guard against reading outside the records)
-		nh_QCastAll<SWEEP> k;
-		k.read(casts + (size_t)i * k.WORDS);
+		Shape k;
+		k.read(casts + (size_t)i * Shape::WORDS);
 		const nh_QShape s = nh_q_unpack(rec[c]);
 		float t0 = 0.0f;
-		if (SWEEP && k.r > 0.0f) nh_q_leaf_entry(k.o, k.inv, k.w, s.p, s.q, s.h, c < nbox, t0);      // (entered: the walk listed it)
-		const nh_QHit h = nh_q_all_hit<SWEEP>(k.o, k.d, k.r, k.max_t, t0, s.p, s.q, s.h, c < nbox);
+		k.entry(s, c < nbox, t0);                          // (entered: the walk listed it)
+		const nh_QHit h = k.all(s, c < nbox, t0);
 		nh_q_write_hit(hits + j, rec, nbox, true, c, h.t, h.n);
 	}
 }
@@ -1171,8 +1192,10 @@ extern "C" int nh_penetration(nh_context* ctx, const nh_OverlapQuery* queries, u
 }
 
 // The all-hits chain (the comment above k_q_castall): nh_overlap's argument rules, offsets and capacity contract, the casts' walk, the ordering by t.
-template <bool SWEEP>
-static int nh_castall(nh_context* ctx, const void* casts, uint32_t count, uint32_t* offsets, nh_RayHit* hits, uint32_t capacity, uint32_t flags) {
+// `label`: the timing labels' stem, q_<entry point without nh_>.
+template <class Shape>
+static int nh_castall(nh_context* ctx, const char* const label[3], const void* casts, uint32_t count, uint32_t* offsets, nh_RayHit* hits, uint32_t capacity,
+                      uint32_t flags) {
 	bool list = false;
 	{ const int rc = nh_overlap_args(ctx, casts, count, offsets, hits, capacity, flags, &list); if (rc || count == 0u) return rc; }
 	nh_QueryState* q = ctx->query;
@@ -1181,12 +1204,12 @@ static int nh_castall(nh_context* ctx, const void* casts, uint32_t count, uint32
 	const int ibits = nh_q_bits(count);
 	const bool one_sort = ibits + 32 + (int)cbits <= 64;
 	const uint32_t grid = nh_grid_for(count, 256, 1u << 20);
-	NH_LAUNCH(ctx, SWEEP ? "q_spherecast_all_count" : "q_raycast_all_count", (k_q_castall<SWEEP, false>), grid, 256, recs, count, offsets, q->nodes, q->rec, q->n,
-	          q->nbox, q->ctl, (uint64_t*)nullptr, (uint32_t*)nullptr, cbits, one_sort ? 1u : 0u);
+	NH_LAUNCH(ctx, label[0], (k_q_castall<Shape, false>), grid, 256, recs, count, offsets, q->nodes, q->rec, q->n, q->nbox, q->ctl, (uint64_t*)nullptr,
+	          (uint32_t*)nullptr, cbits, one_sort ? 1u : 0u);
 	nh_overlap_offsets(ctx, offsets, count, capacity);
 	if (!list) return NH_OK;
-	NH_LAUNCH(ctx, SWEEP ? "q_spherecast_all_list" : "q_raycast_all_list", (k_q_castall<SWEEP, true>), grid, 256, recs, count, offsets, q->nodes, q->rec, q->n,
-	          q->nbox, q->ctl, q->ov_keys_a, q->ov_vals_a, cbits, one_sort ? 1u : 0u);
+	NH_LAUNCH(ctx, label[1], (k_q_castall<Shape, true>), grid, 256, recs, count, offsets, q->nodes, q->rec, q->n, q->nbox, q->ctl, q->ov_keys_a, q->ov_vals_a,
+	          cbits, one_sort ? 1u : 0u);
 	uint64_t* keys = q->ov_keys_a; uint64_t* keys_other = q->ov_keys_b;
 	uint32_t* vals = q->ov_vals_a; uint32_t* vals_other = q->ov_vals_b;
 	const uint32_t* m = &q->ctl->ov_written;
@@ -1199,16 +1222,31 @@ static int nh_castall(nh_context* ctx, const void* casts, uint32_t count, uint32
 			std::swap(keys, keys_other); std::swap(vals, vals_other);
 		}
 	}
-	NH_LAUNCH(ctx, SWEEP ? "q_spherecast_all_gather" : "q_raycast_all_gather", (k_q_castall_gather<SWEEP>), nh_grid_for(capacity, 256, 1u << 20), 256, keys, vals,
-	          q->ctl, q->rec, q->n, q->nbox, recs, count, one_sort ? 32u + cbits : 32u, hits);
+	NH_LAUNCH(ctx, label[2], (k_q_castall_gather<Shape>), nh_grid_for(capacity, 256, 1u << 20), 256, keys, vals, q->ctl, q->rec, q->n, q->nbox, recs, count,
+	          one_sort ? 32u + cbits : 32u, hits);
 	return NH_OK;
 }
 
+#define NH_CASTALL_LABELS(stem) static const char* const label[3] = { stem "_count", stem "_list", stem "_gather" }
+
 extern "C" int nh_raycast_all(nh_context* ctx, const nh_Ray* rays, uint32_t count, uint32_t* offsets, nh_RayHit* hits, uint32_t capacity, uint32_t flags) {
-	return nh_castall<false>(ctx, rays, count, offsets, hits, capacity, flags);
+	NH_CASTALL_LABELS("q_raycast_all");
+	return nh_castall<nh_QRay>(ctx, label, rays, count, offsets, hits, capacity, flags);
 }
 
 extern "C" int nh_spherecast_all(nh_context* ctx, const nh_SphereCast* casts, uint32_t count, uint32_t* offsets, nh_RayHit* hits, uint32_t capacity,
                                  uint32_t flags) {
-	return nh_castall<true>(ctx, casts, count, offsets, hits, capacity, flags);
+	NH_CASTALL_LABELS("q_spherecast_all");
+	return nh_castall<nh_QBall>(ctx, label, casts, count, offsets, hits, capacity, flags);
+}
+
+extern "C" int nh_boxcast_all(nh_context* ctx, const nh_BoxCast* casts, uint32_t count, uint32_t* offsets, nh_RayHit* hits, uint32_t capacity, uint32_t flags) {
+	NH_CASTALL_LABELS("q_boxcast_all");
+	return nh_castall<nh_QBox>(ctx, label, casts, count, offsets, hits, capacity, flags);
+}
+
+extern "C" int nh_capsulecast_all(nh_context* ctx, const nh_CapsuleCast* casts, uint32_t count, uint32_t* offsets, nh_RayHit* hits, uint32_t capacity,
+                                  uint32_t flags) {
+	NH_CASTALL_LABELS("q_capsulecast_all");
+	return nh_castall<nh_QCapsule>(ctx, label, casts, count, offsets, hits, capacity, flags);
 }

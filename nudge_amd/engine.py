@@ -43,7 +43,7 @@ EXPORTS = [
     "nh_partition_top_speed", "nh_partition_set_peer_speeds", "nh_partition_refresh_is_quiet", "nh_partition_mark_ghosts", "nh_partition_pack_deltas", "nh_partition_unpack_deltas",
     "nh_partition_pack_momentum", "nh_partition_unpack_momentum", "nh_partition_exchange_iteration", "nh_partition_unpack_ghosts", "nh_partition_pack_step", "nh_partition_unpack_step", "nh_partition_choose_cut", "nh_partition_set_cut",
     "nh_partition_set_transport", "nh_partition_exchange_step", "nh_partition_step", "nh_partition_transport_check", "nh_partition_transport_result", "nh_set_first_ghost_body",
-    "nh_query_build", "nh_query_refit", "nh_query_stats", "nh_raycast", "nh_overlap", "nh_penetration", "nh_spherecast", "nh_raycast_all", "nh_spherecast_all", "nh_boxcast", "nh_capsulecast", "nh_closest", "nh_closest_k",
+    "nh_query_build", "nh_query_refit", "nh_query_stats", "nh_raycast", "nh_overlap", "nh_penetration", "nh_spherecast", "nh_raycast_all", "nh_spherecast_all", "nh_boxcast_all", "nh_capsulecast_all", "nh_boxcast", "nh_capsulecast", "nh_closest", "nh_closest_k",
 ]
 HALO_RECORD_BYTES = 64
 
@@ -276,6 +276,10 @@ def lib():
         if hasattr(L, "nh_raycast_all"):
             L.nh_raycast_all.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
             L.nh_spherecast_all.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+        # (likewise the all-hits box and capsule casts: World.boxcast_all / capsulecast_all then raise AttributeError)
+        if hasattr(L, "nh_boxcast_all"):
+            L.nh_boxcast_all.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+            L.nh_capsulecast_all.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
         _LIB = L
     return _LIB
 
@@ -760,6 +764,29 @@ class World:
         casts[:, 8] = torch.as_tensor(radii, dtype=torch.float32, device=self.dev).reshape(-1)
         return self._castall(self.spherecast_all_records, casts, n, capacity, synchronize)
 
+    def _box_casts(self, name, origins, directions, half_extents, rotations, max_t, ignore_body):
+        """(records, n): nh_BoxCast records from boxcast()'s arguments."""
+        torch = self.torch
+        casts, n = self._cast_head(name, origins, directions, max_t, ignore_body, 16)
+        if rotations is None:
+            casts[:, 11] = 1.0
+        else:
+            casts[:, 8:12] = torch.as_tensor(rotations, dtype=torch.float32, device=self.dev).reshape(-1, 4)
+        casts[:, 12:15] = torch.as_tensor(half_extents, dtype=torch.float32, device=self.dev).reshape(-1, 3)
+        return casts, n
+
+    def _capsule_casts(self, name, origins, directions, radii, half_heights, rotations, max_t, ignore_body):
+        """(records, n): nh_CapsuleCast records from capsulecast()'s arguments."""
+        torch = self.torch
+        casts, n = self._cast_head(name, origins, directions, max_t, ignore_body, 16)
+        if rotations is None:
+            casts[:, 11] = 1.0
+        else:
+            casts[:, 8:12] = torch.as_tensor(rotations, dtype=torch.float32, device=self.dev).reshape(-1, 4)
+        casts[:, 12] = torch.as_tensor(radii, dtype=torch.float32, device=self.dev).reshape(-1)
+        casts[:, 13] = torch.as_tensor(half_heights, dtype=torch.float32, device=self.dev).reshape(-1)
+        return casts, n
+
     def boxcast_records(self, casts, any_hit=False, hits=None):
         """nh_boxcast on records already laid out as nh_BoxCast: `casts` a contiguous device tensor of count x 64 bytes (any dtype).  Returns the
         count x 32-byte uint8 device tensor of nh_RayHit records (`hits`, or a new one)."""
@@ -770,13 +797,7 @@ class World:
         ((n, 4) or (4,) quaternions (x, y, z, s); None = identity) swept, without turning, from `origins` along `directions` ((n, 3) each).  `max_t`,
         `ignore_body` and the result are raycast()'s: t, normal (from the collider to the cast box), body, collider, shape, tag and `raw`.  Nothing
         waits unless `synchronize`."""
-        torch = self.torch
-        casts, _ = self._cast_head("boxcast", origins, directions, max_t, ignore_body, 16)
-        if rotations is None:
-            casts[:, 11] = 1.0
-        else:
-            casts[:, 8:12] = torch.as_tensor(rotations, dtype=torch.float32, device=self.dev).reshape(-1, 4)
-        casts[:, 12:15] = torch.as_tensor(half_extents, dtype=torch.float32, device=self.dev).reshape(-1, 3)
+        casts, _ = self._box_casts("boxcast", origins, directions, half_extents, rotations, max_t, ignore_body)
         return self._ray_hits(self.boxcast_records(casts, any_hit=any_hit), synchronize)
 
     def capsulecast_records(self, casts, any_hit=False, hits=None):
@@ -790,15 +811,29 @@ class World:
         its local y axis, turned by `rotations` ((n, 4) or (4,) quaternions (x, y, z, s); None = identity, upright), swept without turning from
         `origins` along `directions` ((n, 3) each).  `max_t`, `ignore_body` and the result are raycast()'s: t, normal (from the collider to the
         capsule), body, collider, shape, tag and `raw`.  Nothing waits unless `synchronize`."""
-        torch = self.torch
-        casts, _ = self._cast_head("capsulecast", origins, directions, max_t, ignore_body, 16)
-        if rotations is None:
-            casts[:, 11] = 1.0
-        else:
-            casts[:, 8:12] = torch.as_tensor(rotations, dtype=torch.float32, device=self.dev).reshape(-1, 4)
-        casts[:, 12] = torch.as_tensor(radii, dtype=torch.float32, device=self.dev).reshape(-1)
-        casts[:, 13] = torch.as_tensor(half_heights, dtype=torch.float32, device=self.dev).reshape(-1)
+        casts, _ = self._capsule_casts("capsulecast", origins, directions, radii, half_heights, rotations, max_t, ignore_body)
         return self._ray_hits(self.capsulecast_records(casts, any_hit=any_hit), synchronize)
+
+    def boxcast_all_records(self, casts, offsets=None, hits=None, capacity=0):
+        """nh_boxcast_all on records already laid out as nh_BoxCast (count x 64 bytes): raycast_all_records for swept oriented boxes."""
+        return self._castall_records("nh_boxcast_all", 64, casts, offsets, hits, capacity)
+
+    def capsulecast_all_records(self, casts, offsets=None, hits=None, capacity=0):
+        """nh_capsulecast_all on records already laid out as nh_CapsuleCast (count x 64 bytes): raycast_all_records for swept capsules."""
+        return self._castall_records("nh_capsulecast_all", 64, casts, offsets, hits, capacity)
+
+    def boxcast_all(self, origins, directions, half_extents, rotations=None, max_t=float("inf"), ignore_body=None, capacity=None, synchronize=False):
+        """Every collider each of n swept oriented boxes touches, ordered along the cast (nh_boxcast_all): boxcast()'s arguments, raycast_all()'s
+        capacity rule and result (normal: from the collider to the cast box); the first record of a cast is boxcast()'s closest hit."""
+        casts, n = self._box_casts("boxcast_all", origins, directions, half_extents, rotations, max_t, ignore_body)
+        return self._castall(self.boxcast_all_records, casts, n, capacity, synchronize)
+
+    def capsulecast_all(self, origins, directions, radii, half_heights, rotations=None, max_t=float("inf"), ignore_body=None, capacity=None,
+                        synchronize=False):
+        """Every collider each of n swept capsules touches, ordered along the cast (nh_capsulecast_all): capsulecast()'s arguments, raycast_all()'s
+        capacity rule and result (normal: from the collider to the capsule); the first record of a cast is capsulecast()'s closest hit."""
+        casts, n = self._capsule_casts("capsulecast_all", origins, directions, radii, half_heights, rotations, max_t, ignore_body)
+        return self._castall(self.capsulecast_all_records, casts, n, capacity, synchronize)
 
     def closest_records(self, queries, hits=None):
         """nh_closest on records already laid out as nh_PointQuery: `queries` a contiguous device tensor of count x 32 bytes (any dtype).  Returns

@@ -1,9 +1,11 @@
-"""All-hits cast rates on the landed config-2 world (1,004,400 boxes + 124 ground slabs; include/nudge_hip.h, nh_raycast_all / nh_spherecast_all):
+"""All-hits cast rates on the landed config-2 world (1,004,400 boxes + 124 ground slabs; include/nudge_hip.h, nh_raycast_all / nh_spherecast_all /
+nh_boxcast_all / nh_capsulecast_all):
 each workload timed with device events -- the count-only call, the count + list pair, and BESIDE them in the same process the closest-hit call
-(nh_raycast / nh_spherecast) on the same records and nh_overlap in list mode with the 1 M sphere queries of tools/overlap_rates.py (interleaved
+(nh_raycast / nh_spherecast / nh_boxcast / nh_capsulecast) on the same records and nh_overlap in list mode with the 1 M sphere queries of tools/overlap_rates.py (interleaved
 repeats; the median and the spread of --repeats blocks of --reps calls) -- and broken down per kernel with the library's own event timing
 (nh_kernel_times).  Workloads: tools/query_rates.py's 1,048,576 incoherent rays and its coherent downward grid, and the same as sphere casts of
-radius 0.75.  The ratios the documents quote: the all-hits count walk over the closest-hit cast (what the missing best-hit pruning costs), and
+radius 0.75, as box casts of half extent 0.75 (identity and random rotations) and as capsule casts of radius 0.5 and half height 0.5 (upright and
+random rotations) -- the workloads of tools/boxcast_rates.py and tools/capsulecast_rates.py.  The ratios the documents quote: the all-hits count walk over the closest-hit cast (what the missing best-hit pruning costs), and
 the list call over nh_overlap's list call per record written.
 
     python tools/castall_rates.py [--steps 70] [--reps 10] [--repeats 5] [--out profiles/castall_rates.log]
@@ -30,6 +32,7 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--rays", type=int, default=1 << 20)
+    ap.add_argument("--only", default="", help="time only the workloads whose name contains this")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "castall_rates.log"))
     a = ap.parse_args()
     import torch
@@ -96,8 +99,30 @@ def main():
         c["radius"] = radius
         return c
 
+    def shaped(rays, dtype, turned):
+        c = np.zeros(len(rays), dtype=dtype)
+        for k in ("origin", "max_t", "direction", "ignore_body"):
+            c[k] = rays[k]
+        c["rotation"] = (0.0, 0.0, 0.0, 1.0)
+        if turned:
+            qr = np.random.default_rng(2).normal(size=(len(rays), 4))
+            c["rotation"] = qr / np.linalg.norm(qr, axis=1, keepdims=True)
+        if dtype == E.BOX_CAST:
+            c["size"] = 0.75
+        else:
+            c["radius"], c["half_height"] = 0.5, 0.5
+        return c
+
     sets = {"rays, incoherent": incoherent, "rays, coherent grid": coherent,
             "balls r=.75, incoherent": casts(incoherent, 0.75), "balls r=.75, coherent grid": casts(coherent, 0.75)}
+    for label, dtype in (("boxes h=.75", E.BOX_CAST), ("capsules r=.5 hh=.5", E.CAPSULE_CAST)):
+        for turn, turned in (("identity", False), ("random rot", True)):
+            sets[f"{label} {turn}, incoherent"] = shaped(incoherent, dtype, turned)
+            sets[f"{label} {turn}, coherent grid"] = shaped(coherent, dtype, turned)
+    if a.only:
+        sets = {k: v for k, v in sets.items() if a.only in k}
+    calls = {E.RAY: (w.raycast_all_records, w.raycast_records), E.SPHERE_CAST: (w.spherecast_all_records, w.spherecast_records),
+             E.BOX_CAST: (w.boxcast_all_records, w.boxcast_records), E.CAPSULE_CAST: (w.capsulecast_all_records, w.capsulecast_records)}
 
     # nh_overlap's usual 1 M sphere queries (tools/overlap_rates.py's first set), list mode
     pos = w.get_bodies()["transforms"]["position"][1:].astype(np.float64)
@@ -115,9 +140,7 @@ def main():
 
     rows = {}
     for name, recs in sets.items():
-        sweep = recs.dtype == E.SPHERE_CAST
-        all_records = w.spherecast_all_records if sweep else w.raycast_all_records
-        closest_records = w.spherecast_records if sweep else w.raycast_records
+        all_records, closest_records = calls[recs.dtype]
         ct = torch.from_numpy(recs.view(np.uint8).copy()).to(w.dev)
         ot = torch.empty(n + 1, dtype=torch.int32, device=w.dev)
         bt = torch.empty((n, 32), dtype=torch.uint8, device=w.dev)
@@ -144,7 +167,7 @@ def main():
         kl = kernels(lst, a.reps)
         kb = kernels(best, a.reps)
         walk = [v for k, v in kl.items() if k.endswith("_all_count")][0]
-        closest_kernel = [v for k, v in kb.items() if k in ("q_raycast", "q_spherecast")][0]
+        closest_kernel = [v for k, v in kb.items() if k in ("q_raycast", "q_spherecast", "q_boxcast", "q_capsulecast")][0]
         c, ls, b, o = med(tc), med(tl), med(tb), med(to)
         rows[name] = dict(casts=n, records=total, per_cast=total / n, longest=longest, closest=b, count_only=c, list_call=ls, count_plus_list_ms=c["ms"] + ls["ms"],
                           overlap_list=o, overlap_records=qtotal,
@@ -155,15 +178,15 @@ def main():
     say(f"landed config-2 world: {C:,} colliders, {nb:,} bodies, after {a.steps} steps; GPU {torch.cuda.get_device_name(w.dev)}")
     say(f"median of {a.repeats} blocks of {a.reps} calls, interleaved (min .. max of the blocks); one box, one run")
     say(f"nh_overlap, list mode, {n:,} sphere queries r=1: {qtotal:,} records")
-    say(f"{'workload':<28}{'records':>11}{'/cast':>7}{'longest':>8}{'closest hit ms':>24}{'all: count only ms':>24}{'all: list call ms':>24}{'nh_overlap list ms':>24}")
+    say(f"{'workload':<48}{'records':>11}{'/cast':>7}{'longest':>8}{'closest hit ms':>24}{'all: count only ms':>24}{'all: list call ms':>24}{'nh_overlap list ms':>24}")
     fmt = lambda v: f"{v['ms']:.3f} ({v['min']:.3f} .. {v['max']:.3f})"                       # noqa: E731
     for k, v in rows.items():
-        say(f"{k:<28}{v['records']:11d}{v['per_cast']:7.2f}{v['longest']:8d}{fmt(v['closest']):>24}{fmt(v['count_only']):>24}{fmt(v['list_call']):>24}{fmt(v['overlap_list']):>24}")
+        say(f"{k:<48}{v['records']:11d}{v['per_cast']:7.2f}{v['longest']:8d}{fmt(v['closest']):>24}{fmt(v['count_only']):>24}{fmt(v['list_call']):>24}{fmt(v['overlap_list']):>24}")
     say()
     say("(the list call runs the count walk, the scan, the list walk, the ordering and the gather: count, read the total, list = the two columns added)")
-    say(f"{'workload':<28}{'count + list ms':>16}{'count walk / closest kernel':>29}{'count only / closest call':>27}{'list / overlap list, per record':>33}")
+    say(f"{'workload':<48}{'count + list ms':>16}{'count walk / closest kernel':>29}{'count only / closest call':>27}{'list / overlap list, per record':>33}")
     for k, v in rows.items():
-        say(f"{k:<28}{v['count_plus_list_ms']:16.3f}{v['count_walk_over_closest_kernel']:29.2f}{v['count_only_over_closest_call']:27.2f}{v['list_per_record_over_overlap_per_record']:33.2f}")
+        say(f"{k:<48}{v['count_plus_list_ms']:16.3f}{v['count_walk_over_closest_kernel']:29.2f}{v['count_only_over_closest_call']:27.2f}{v['list_per_record_over_overlap_per_record']:33.2f}")
     for k, v in rows.items():
         say(f"\n{k}: the list call per kernel, ms per call (nh_kernel_times); closest hit: " + ", ".join(f"{kn} {t:.4f}" for kn, t in v["kernels_closest"].items()))
         for kn, t in sorted(v["kernels_list_call"].items(), key=lambda kv: -kv[1]):
