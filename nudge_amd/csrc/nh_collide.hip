@@ -528,6 +528,7 @@ __device__ __forceinline__ void emit_kept(nh_DevState* st, uint2* __restrict__ k
 // 1e-5 of the radii "surely apart" never drops a pair the narrowphase would give a contact (nudge.cpp:2495: l2 > r * r means none).  Only in the
 // DIRECT search (the kept list has to stay a superset across steps), and only between two bodies that are AWAKE: an edge with a sleeping end takes part in
 // the coarse islands and may have to be reported as a sleeping pair although its boxes merely overlap (nudge.cpp:3575-3703).
+// (pinned by tests/test_gpu_sphere_cases.py, case ss_grazing, DIRECT search: pairs one ulp either side of l2 == r * r, out to 5e4 from the origin, radii 1e-3 with 10 and 30 with 0.01)
 __device__ __forceinline__ bool spheres_surely_apart(const float4& amin, const float4& amax, const float4& bmin, const float4& bmax) {
 	const float ax = 0.5f * (amin.x + amax.x), ay = 0.5f * (amin.y + amax.y), az = 0.5f * (amin.z + amax.z);
 	const float bx = 0.5f * (bmin.x + bmax.x), by = 0.5f * (bmin.y + bmax.y), bz = 0.5f * (bmin.z + bmax.z);
