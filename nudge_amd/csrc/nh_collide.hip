@@ -1394,40 +1394,53 @@ __global__ __launch_bounds__(256) void k_pair_list(nh_DevState* __restrict__ st,
 // parity's words cleared for what this step's lanes gather (first workgroup) -- one check of its own: the lanes decided which collider of a pair plays "a" with the LAST
 // frame's cells as their yardstick (k_solve_one_body<.., PAIR>), so this step's cells must not be much larger -- and the kept pairs that are NO body's own (k_pair_list),
 // evaluated like k_narrowphase<*, true, false> evaluates them: a record nobody's lane solves must stay without contacts and keep its key, or this is not a still step.
-__global__ __launch_bounds__(256) void k_pair_begin(nh_DevState* __restrict__ st, uint32_t parity, uint32_t seq, const uint32_t* __restrict__ list, uint32_t list_cap,
-                                                    const uint2* __restrict__ kept, uint32_t kept_cap, uint32_t pair_cap, const uint8_t* __restrict__ gen,
-                                                    const nh_xform* __restrict__ xf, const float4* __restrict__ aabb_min, const float4* __restrict__ aabb_max, const uint32_t* __restrict__ ctag,
-                                                    const nh_BoxCollider* __restrict__ box_data, const nh_SphereCollider* __restrict__ sph_data, uint32_t nbox,
-                                                    const uint64_t* __restrict__ rec_key, nh_Record* __restrict__ rec,
-                                                    const uint32_t* __restrict__ lay_rank, uint32_t* __restrict__ cnt_sorted, const uint32_t* __restrict__ body_rec, int2* __restrict__ delta,
-                                                    nh_Contact* __restrict__ raw_data, uint32_t* __restrict__ raw_feature,
-                                                    const nh_BodyMomentum* __restrict__ momentum, const nh_BodyProperties* __restrict__ props, uint32_t delta_scan,
-                                                    // sleepers ahead (nh_internal.h): the number of bodies of a world with sleepers in it -- the step's sleeper counts are the last step's
-                                                    uint32_t sleepers_bodies = 0u) {
-	const uint32_t lane = nh_lane();
-	uint32_t fr_min[3], fr_max[3], fr_top;
-	{
-		const uint32_t* part = &st->ahead_part[parity][lane & (NH_AHEAD_PARTS - 1u)][0];
-		fr_top = part[6];
-		for (int k = 0; k < 3; ++k) { fr_min[k] = min(part[k], st->still_static_min[k]); fr_max[k] = max(part[3 + k], st->still_static_max[k]); }
-	}
+// Launched with ONE wave per workgroup.  Workgroup 0 does what concerns the step as a whole; every other wave takes the listed pairs, one lane per pair.  The launch is
+// latency, not traffic (0.4 MB in c2), so each wave asks for everything whose address it knows at the same time: a pair lane makes three dependent round trips -- the
+// step's words and its list entry (at a clamped index); behind the entry the pair, the key on file, the place in the tag order; behind the pair both boxes, transforms,
+// tags, shapes and stamps and the count on file -- whether the boxes overlap or not, like k_narrowphase<.., true>.
+// The empty asm statements below are what keeps a group of loads together: each names values the compiler would otherwise fetch where they are first used (inside a
+// branch, behind the reduction), and so makes it wait for the whole group at that point.  Nothing checks this at build time.  After an edit, read it off the ISA
+// (hipcc -S --cuda-device-only with the Makefile's flags): in a pair lane's path there must be ONE s_waitcnt vmcnt between the list entry's load and kept / rec_key /
+// lay_rank, ONE between those and the group of 14 to 18 loads that ends with cnt_sorted[pos], and no global_load behind the overlap test other than body_rec's and
+// delta_overflow's (profiles/r09_steady_step_ab.log lists the trips).
+__device__ __forceinline__ void nh_pair_frame(const nh_DevState* __restrict__ st, uint32_t parity, uint32_t lane, uint32_t (&fr_min)[3], uint32_t (&fr_max)[3], uint32_t& fr_top) {
+	const uint32_t* part = &st->ahead_part[parity][lane & (NH_AHEAD_PARTS - 1u)][0];
+	fr_top = part[6];
+	for (int k = 0; k < 3; ++k) { fr_min[k] = min(part[k], st->still_static_min[k]); fr_max[k] = max(part[3 + k], st->still_static_max[k]); }
 	for (int k = 0; k < 3; ++k)
 		for (int d = 32; d >= 1; d >>= 1) { fr_min[k] = min(fr_min[k], (uint32_t)__shfl_xor((int)fr_min[k], d)); fr_max[k] = max(fr_max[k], (uint32_t)__shfl_xor((int)fr_max[k], d)); }
 	for (int d = 32; d >= 1; d >>= 1) fr_top = max(fr_top, (uint32_t)__shfl_xor((int)fr_top, d));
-	const nh_f3 smin = nh_make3(nh_float_unflip(fr_min[0]), nh_float_unflip(fr_min[1]), nh_float_unflip(fr_min[2]));
-	const nh_f3 smax = nh_make3(nh_float_unflip(fr_max[0]), nh_float_unflip(fr_max[1]), nh_float_unflip(fr_max[2]));
-	const float mscale = nh_morton_scale(smin, smax);
-	const nh_f3 mmin = nh_make3(smin.x * mscale, smin.y * mscale, smin.z * mscale);
-	const uint32_t n_list = st->pair_unowned;
-	if (blockIdx.x == 0 && threadIdx.x < 64u) {
+}
+__global__ __launch_bounds__(64) void k_pair_begin(nh_DevState* __restrict__ st, uint32_t parity, uint32_t seq, const uint32_t* __restrict__ list, uint32_t list_cap,
+                                                   const uint2* __restrict__ kept, uint32_t kept_cap, uint32_t pair_cap, const uint8_t* __restrict__ gen,
+                                                   const nh_xform* __restrict__ xf, const float4* __restrict__ aabb_min, const float4* __restrict__ aabb_max, const uint32_t* __restrict__ ctag,
+                                                   const nh_BoxCollider* __restrict__ box_data, const nh_SphereCollider* __restrict__ sph_data, uint32_t nbox,
+                                                   const uint64_t* __restrict__ rec_key, nh_Record* __restrict__ rec,
+                                                   const uint32_t* __restrict__ lay_rank, uint32_t* __restrict__ cnt_sorted, const uint32_t* __restrict__ body_rec, int2* __restrict__ delta,
+                                                   nh_Contact* __restrict__ raw_data, uint32_t* __restrict__ raw_feature,
+                                                   const nh_BodyMomentum* __restrict__ momentum, const nh_BodyProperties* __restrict__ props, uint32_t delta_scan,
+                                                   // sleepers ahead (nh_internal.h): the number of bodies of a world with sleepers in it -- the step's sleeper counts are the last step's
+                                                   uint32_t sleepers_bodies = 0u) {
+	const uint32_t lane = threadIdx.x;
+	if (blockIdx.x == 0) {
+		// ---- the step as a whole: every word it needs is asked for here, in one round trip ----
 		const uint32_t op = parity ^ 1u;
-		const float scale_was = nh_morton_scale(nh_make3(nh_float_unflip(st->still_smin[op][0]), nh_float_unflip(st->still_smin[op][1]), nh_float_unflip(st->still_smin[op][2])),
-		                                        nh_make3(nh_float_unflip(st->still_smax[op][0]), nh_float_unflip(st->still_smax[op][1]), nh_float_unflip(st->still_smax[op][2])));
+		uint32_t was_min[3], was_max[3];
+		for (int k = 0; k < 3; ++k) { was_min[k] = st->still_smin[op][k]; was_max[k] = st->still_smax[op][k]; }
 		// (body 0 inert: the solver checks it too -- here so that the step's verdict is complete when this launch ends, nh_StillStep::early_verdict)
 		const nh_BodyMomentum m0 = momentum[0];
 		const nh_BodyProperties p0 = props[0];
+		const uint32_t n_list = st->pair_unowned, ahead_failed_seq = st->ahead_failed_seq, ahead_multi = st->ahead_multi, lay_valid = st->lay_valid;
+		const uint32_t fat_count = st->fat_count, fat_count_sph = st->fat_count_sph, n_pairs = st->pairs, n_pairs_sph = st->pairs_sph;
+		const uint32_t active = st->active, sleeping = st->sleeping, culled = st->culled;
+		uint32_t fr_min[3], fr_max[3], fr_top;
+		nh_pair_frame(st, parity, lane, fr_min, fr_max, fr_top);
+		const float mscale = nh_morton_scale(nh_make3(nh_float_unflip(fr_min[0]), nh_float_unflip(fr_min[1]), nh_float_unflip(fr_min[2])),
+		                                     nh_make3(nh_float_unflip(fr_max[0]), nh_float_unflip(fr_max[1]), nh_float_unflip(fr_max[2])));
+		const float scale_was = nh_morton_scale(nh_make3(nh_float_unflip(was_min[0]), nh_float_unflip(was_min[1]), nh_float_unflip(was_min[2])),
+		                                        nh_make3(nh_float_unflip(was_max[0]), nh_float_unflip(was_max[1]), nh_float_unflip(was_max[2])));
 		const bool inert = nh_is_inert(m0.velocity, m0.angular_velocity, p0.inertia_inverse, p0.mass_inverse);
-		const bool bad = st->ahead_failed_seq >= seq || st->ahead_multi != 0u || !st->lay_valid || st->fat_count != st->pairs || st->fat_count_sph != st->pairs_sph ||
+		const bool bad = ahead_failed_seq >= seq || ahead_multi != 0u || !lay_valid || fat_count != n_pairs || fat_count_sph != n_pairs_sph ||
 		                 n_list > list_cap || !(mscale >= 0.75f * scale_was) || !inert;
 		__builtin_amdgcn_wave_barrier();
 		if (lane == 0) {
@@ -1439,8 +1452,8 @@ __global__ __launch_bounds__(256) void k_pair_begin(nh_DevState* __restrict__ st
 			if (sleepers_bodies) {
 				// (nobody fell asleep or woke since the last step -- that step's lanes would have failed this one: k_solve_one_body<.., AHEAD> -- so what a k_xform<true> and a
 				// narrowphase in sleepers form would count now is what they counted then; the solver's first thread turns the parity words into the step's counters)
-				const uint32_t asleep = (sleepers_bodies - 1u) - min(st->active, sleepers_bodies - 1u);
-				st->still_asleep[parity] = asleep; st->still_sleeping[parity] = st->sleeping; st->still_culled[parity] = st->culled;
+				const uint32_t asleep = (sleepers_bodies - 1u) - min(active, sleepers_bodies - 1u);
+				st->still_asleep[parity] = asleep; st->still_sleeping[parity] = sleeping; st->still_culled[parity] = culled;
 				if (asleep) top = 0xffu;
 			}
 			st->max_idle[parity] = top;
@@ -1448,102 +1461,137 @@ __global__ __launch_bounds__(256) void k_pair_begin(nh_DevState* __restrict__ st
 			st->max_idle[op] = 0u; st->delta_count[op] = 0u; st->delta_overflow[op] = 0u; st->still_esc[op] = 0u;
 			st->still_asleep[op] = 0u; st->still_sleeping[op] = 0u; st->still_culled[op] = 0u;
 			for (int k = 0; k < 3; ++k) { st->still_smin[op][k] = 0xffffffffu; st->still_smax[op][k] = 0u; }
-			st->still_fat0 = st->fat_count + st->fat_count_sph;
+			st->still_fat0 = fat_count + fat_count_sph;
 		}
 		for (uint32_t k = lane; k < NH_AHEAD_PARTS * 8u; k += 64u) (&st->ahead_part[op][0][0])[k] = (k & 7u) < 3u ? 0xffffffffu : 0u;
 		if (sleepers_bodies) for (uint32_t k = lane; k < NH_SLEEP_PARTS * 2u; k += 64u) (&st->sleep_part[parity][0][0])[k] = 0u;          // (no narrowphase adds to them in such a step)
+		return;
 	}
 	// ---- the kept pairs that are nobody's: exact boxes, stamps, roles by Morton order, contact arithmetic -- and the verdict: no contact, the key on file ----
-	const uint32_t n_bb = min(st->pairs, pair_cap);
+	// round trip 1: the step's words, the frame's parts and this lane's first list entry (the list holds list_cap words: the index is clamped, the entry used only if it is one)
+	const uint32_t stride = (gridDim.x - 1u) * 64u;
+	uint32_t j = (blockIdx.x - 1u) * 64u + lane;
+	uint32_t r = list[min(j, list_cap - 1u)];
+	const uint32_t n_list = st->pair_unowned, n_pairs = st->pairs, moved = st->moved_count;
+	uint32_t fr_min[3], fr_max[3], fr_top;
+	nh_pair_frame(st, parity, lane, fr_min, fr_max, fr_top);
+	asm volatile("" :: "s"(n_list), "s"(n_pairs), "s"(moved), "v"(r));          // (asked for with the parts, not behind their reduction)
+	const nh_f3 smin = nh_make3(nh_float_unflip(fr_min[0]), nh_float_unflip(fr_min[1]), nh_float_unflip(fr_min[2]));
+	const nh_f3 smax = nh_make3(nh_float_unflip(fr_max[0]), nh_float_unflip(fr_max[1]), nh_float_unflip(fr_max[2]));
+	const float mscale = nh_morton_scale(smin, smax);
+	const nh_f3 mmin = nh_make3(smin.x * mscale, smin.y * mscale, smin.z * mscale);
+	const uint32_t n = min(n_list, list_cap);
+	const uint32_t n_bb = min(n_pairs, pair_cap);
 	const uint32_t index_mask = gen ? NH_GEN_INDEX : 0xFFFFFFFFu;
-	const bool stamps = gen && st->moved_count != 0u;
+	const bool stamps = gen && moved != 0u;
 	bool changed = false;
-	for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < min(n_list, list_cap); j += gridDim.x * blockDim.x) {
-		const uint32_t r = list[j];
-		if (sleepers_bodies && rec[r].count == NH_REC_SLEEPING) continue;          // (a listed pair whose body has fallen asleep since: a settled sleeping pair, nobody's business)
+	while (j < n) {
+		// round trip 2, behind the list entry: the pair, the key on file, the record's place in the tag order (and whether it has become a sleeping pair)
 		const uint2 kp = r < n_bb ? kept[r] : kept[kept_cap - 1u - (r - n_bb)];
-		const uint32_t ca = kp.x & index_mask, cb = kp.y & index_mask;
-		const float4 amin = aabb_min[ca], amax = aabb_max[ca], bmin = aabb_min[cb], bmax = aabb_max[cb];
-		bool hit = aabb_overlap(amin, amax, bmin, bmax) && (__float_as_uint(bmin.w) != __float_as_uint(amin.w));
-		if (stamps && hit) hit = (uint32_t)(gen[ca] & 0x7Fu) == (kp.x >> NH_GEN_SHIFT) && (uint32_t)(gen[cb] & 0x7Fu) == (kp.y >> NH_GEN_SHIFT);
-		// (sleepers ahead: the boxes of a pair with a SLEEPING end overlap -- an awake body has come within reach of a sleeper, which wakes it (its set holds more than itself,
-		// nudge.cpp:3575-3650), or a sleeper's pair that was no sleeping pair has become one: either way the three kernels' business, k_narrowphase<*, true, true> -- not this step's)
-		if (sleepers_bodies && hit && (__float_as_uint(amax.w) | __float_as_uint(bmax.w)) != 0u) { changed = true; atomicAdd(&st->still_diff[3], 1u); hit = false; }
-		int count = 0;
-		uint64_t key = ~0ull;
-		uint32_t body_a = 0, body_b = 0;
-		nh_bb_result bb;
-		bb.kind = 0; bb.mask = 0;
-		nh_contact_out single;
-		single.px = single.py = single.pz = single.penetration = single.nx = single.ny = single.nz = 0.0f; single.friction = 0.5f; single.feature = 0u;
-		if (hit) {
-			const uint64_t ka = nh_morton_of(nh_make3(amin.x, amin.y, amin.z), mscale, mmin), kb = nh_morton_of(nh_make3(bmin.x, bmin.y, bmin.z), mscale, mmin);
-			const bool a_first = (ka < kb) || (ka == kb && ca < cb);
-			const uint32_t a = a_first ? cb : ca, b = a_first ? ca : cb;          // narrowphase "a" = later in Morton order (emit_pair)
-			const nh_xform A = xf[a], B = xf[b];
-			const uint32_t ta = ctag[a], tb = ctag[b];
-			const bool a_sph = a >= nbox, b_sph = b >= nbox;
-			if (!a_sph && !b_sph) {
-				const nh_BoxCollider sa = box_data[a], sb = box_data[b];
-				nh_box_box_eval(A, B, sa.size, sb.size, ta, tb, bb);
-				count = nh_bb_count(bb);
-				key = (uint64_t)(bb.swapped ? tb : ta) | ((uint64_t)(bb.swapped ? ta : tb) << 32);
-				body_a = bb.swapped ? B.body : A.body; body_b = bb.swapped ? A.body : B.body;
-			} else if (a_sph && b_sph) {
-				count = nh_sphere_sphere(sph_data[b - nbox].radius, sph_data[a - nbox].radius, B, A, &single);
-				key = (uint64_t)tb | ((uint64_t)ta << 32);
-				body_a = B.body; body_b = A.body;
-			} else {
-				const uint32_t bx = a_sph ? b : a, sp = a_sph ? a : b;
-				const nh_BoxCollider sz = box_data[bx];
-				const nh_xform BX = a_sph ? B : A, SP = a_sph ? A : B;
-				count = nh_box_sphere(sz.size, sph_data[sp - nbox].radius, BX, SP, &single);
-				key = (uint64_t)(a_sph ? tb : ta) | ((uint64_t)(a_sph ? ta : tb) << 32);
-				body_a = BX.body; body_b = SP.body;
-			}
-		}
-		// still_record (k_narrowphase): the key on file -- or the pair gone --, at most four contacts, and a pair WITH contacts joins a dynamic body to the static world and
-		// is that body's own record (a ghost's, in a partitioned world: its lane solves it, this launch evaluates it)
 		const uint64_t was_key = rec_key[r];
 		const uint32_t pos = lay_rank[r];
-		bool ok = (was_key == key || !hit) && count <= 4;
-		if (ok && count) {
-			const uint32_t dyn = body_a ? body_a : body_b;
-			ok = (body_a == 0u) != (body_b == 0u) && (body_rec[dyn] & ~NH_BODY_REC_IS_A) == r;
-		}
-		if (!ok) { changed = true; atomicAdd(&st->still_diff[(was_key != key && hit) ? 0 : (count > 4 ? 1 : 2)], 1u); count = 0; }
-		else if (count) {
-			const size_t base = r < n_bb ? (size_t)4 * r : (size_t)4 * n_bb + (r - n_bb);
-			if (bb.kind == 2) {
-				int k = 0;
-#pragma unroll
-				for (int index = 0; index < 16; ++index) {
-					if (((bb.mask >> index) & 1u) && k < count) {
-						nh_contact_out o;
-						nh_bb_contact(bb, index, bb.fx[index], bb.fy[index], bb.fz[index], bb.penetration[index], bb.tags[index], o);
-						float4* dp = reinterpret_cast<float4*>(raw_data + base + k);
-						dp[0] = make_float4(o.px, o.py, o.pz, o.penetration); dp[1] = make_float4(o.nx, o.ny, o.nz, o.friction);
-						raw_feature[base + k] = o.feature;
-						++k;
-					}
+		const uint32_t was_count = sleepers_bodies ? rec[r].count : 0u;
+		// (a listed pair whose body has fallen asleep since: a settled sleeping pair, nobody's business)
+		if (!(sleepers_bodies && was_count == NH_REC_SLEEPING)) {
+			// round trip 3, behind the pair: everything an evaluation reads, asked for whether the boxes overlap or not (both colliders exist: the indices need no clamp)
+			const uint32_t ca = kp.x & index_mask, cb = kp.y & index_mask;
+			const float4 amin = aabb_min[ca], amax = aabb_max[ca], bmin = aabb_min[cb], bmax = aabb_max[cb];
+			const nh_xform XA = xf[ca], XB = xf[cb];
+			const uint32_t tca = ctag[ca], tcb = ctag[cb];
+			const bool ca_sph = ca >= nbox, cb_sph = cb >= nbox;
+			// (shapes at clamped indices behind wave-uniform branches: a wave that holds a box knows that box 0 exists, one that holds a sphere that sphere 0 does)
+			nh_BoxCollider sza, szb;
+			sza.size[0] = sza.size[1] = sza.size[2] = sza.unused = 0.0f; szb = sza;
+			float rada = 0.0f, radb = 0.0f;
+			if (__ballot(!ca_sph || !cb_sph) != 0ull) { sza = box_data[ca_sph ? 0u : ca]; szb = box_data[cb_sph ? 0u : cb]; }
+			if (__ballot(ca_sph || cb_sph) != 0ull) { rada = sph_data[ca_sph ? ca - nbox : 0u].radius; radb = sph_data[cb_sph ? cb - nbox : 0u].radius; }
+			uint32_t gena = 0u, genb = 0u;
+			if (gen) { gena = gen[ca]; genb = gen[cb]; }
+			const uint32_t old = cnt_sorted[pos];
+			// (all of it has arrived before the first branch on any of it: nothing of the round trip is left for the inside of a branch)
+			asm volatile("" :: "v"(XA.px), "v"(XA.py), "v"(XA.pz), "v"(XA.body), "v"(XA.qx), "v"(XA.qy), "v"(XA.qz), "v"(XA.qs));
+			asm volatile("" :: "v"(XB.px), "v"(XB.py), "v"(XB.pz), "v"(XB.body), "v"(XB.qx), "v"(XB.qy), "v"(XB.qz), "v"(XB.qs));
+			asm volatile("" :: "v"(tca), "v"(tcb), "v"(sza.size[0]), "v"(sza.size[1]), "v"(sza.size[2]), "v"(szb.size[0]), "v"(szb.size[1]), "v"(szb.size[2]), "v"(rada), "v"(radb), "v"(gena), "v"(genb), "v"(old));
+			bool hit = aabb_overlap(amin, amax, bmin, bmax) && (__float_as_uint(bmin.w) != __float_as_uint(amin.w));
+			if (stamps && hit) hit = (uint32_t)(gena & 0x7Fu) == (kp.x >> NH_GEN_SHIFT) && (uint32_t)(genb & 0x7Fu) == (kp.y >> NH_GEN_SHIFT);
+			// (sleepers ahead: the boxes of a pair with a SLEEPING end overlap -- an awake body has come within reach of a sleeper, which wakes it (its set holds more than itself,
+			// nudge.cpp:3575-3650), or a sleeper's pair that was no sleeping pair has become one: either way the three kernels' business, k_narrowphase<*, true, true> -- not this step's)
+			if (sleepers_bodies && hit && (__float_as_uint(amax.w) | __float_as_uint(bmax.w)) != 0u) { changed = true; atomicAdd(&st->still_diff[3], 1u); hit = false; }
+			int count = 0;
+			uint64_t key = ~0ull;
+			uint32_t body_a = 0, body_b = 0;
+			nh_bb_result bb;
+			bb.kind = 0; bb.mask = 0;
+			nh_contact_out single;
+			single.px = single.py = single.pz = single.penetration = single.nx = single.ny = single.nz = 0.0f; single.friction = 0.5f; single.feature = 0u;
+			if (hit) {
+				const uint64_t ka = nh_morton_of(nh_make3(amin.x, amin.y, amin.z), mscale, mmin), kb = nh_morton_of(nh_make3(bmin.x, bmin.y, bmin.z), mscale, mmin);
+				const bool a_first = (ka < kb) || (ka == kb && ca < cb);
+				// narrowphase "a" = later in Morton order (emit_pair)
+				const nh_xform A = a_first ? XB : XA, B = a_first ? XA : XB;
+				const uint32_t ta = a_first ? tcb : tca, tb = a_first ? tca : tcb;
+				const bool a_sph = a_first ? cb_sph : ca_sph, b_sph = a_first ? ca_sph : cb_sph;
+				const nh_BoxCollider sa = a_first ? szb : sza, sb = a_first ? sza : szb;
+				const float ra = a_first ? radb : rada, rb = a_first ? rada : radb;
+				if (!a_sph && !b_sph) {
+					nh_box_box_eval(A, B, sa.size, sb.size, ta, tb, bb);
+					count = nh_bb_count(bb);
+					key = (uint64_t)(bb.swapped ? tb : ta) | ((uint64_t)(bb.swapped ? ta : tb) << 32);
+					body_a = bb.swapped ? B.body : A.body; body_b = bb.swapped ? A.body : B.body;
+				} else if (a_sph && b_sph) {
+					count = nh_sphere_sphere(rb, ra, B, A, &single);
+					key = (uint64_t)tb | ((uint64_t)ta << 32);
+					body_a = B.body; body_b = A.body;
+				} else {
+					const nh_BoxCollider sz = a_sph ? sb : sa;
+					const nh_xform BX = a_sph ? B : A, SP = a_sph ? A : B;
+					count = nh_box_sphere(sz.size, a_sph ? ra : rb, BX, SP, &single);
+					key = (uint64_t)(a_sph ? tb : ta) | ((uint64_t)(a_sph ? ta : tb) << 32);
+					body_a = BX.body; body_b = SP.body;
 				}
-			} else {
-				const nh_contact_out o = bb.kind == 1 ? bb.edge : single;
-				float4* dp = reinterpret_cast<float4*>(raw_data + base);
-				dp[0] = make_float4(o.px, o.py, o.pz, o.penetration); dp[1] = make_float4(o.nx, o.ny, o.nz, o.friction);
-				raw_feature[base] = o.feature;
+			}
+			// still_record (k_narrowphase): the key on file -- or the pair gone --, at most four contacts, and a pair WITH contacts joins a dynamic body to the static world and
+			// is that body's own record (a ghost's, in a partitioned world: its lane solves it, this launch evaluates it)
+			bool ok = (was_key == key || !hit) && count <= 4;
+			if (ok && count) {
+				const uint32_t dyn = body_a ? body_a : body_b;
+				ok = (body_a == 0u) != (body_b == 0u) && (body_rec[dyn] & ~NH_BODY_REC_IS_A) == r;
+			}
+			if (!ok) { changed = true; atomicAdd(&st->still_diff[(was_key != key && hit) ? 0 : (count > 4 ? 1 : 2)], 1u); count = 0; }
+			else if (count) {
+				const size_t base = r < n_bb ? (size_t)4 * r : (size_t)4 * n_bb + (r - n_bb);
+				if (bb.kind == 2) {
+					int k = 0;
+#pragma unroll
+					for (int index = 0; index < 16; ++index) {
+						if (((bb.mask >> index) & 1u) && k < count) {
+							nh_contact_out o;
+							nh_bb_contact(bb, index, bb.fx[index], bb.fy[index], bb.fz[index], bb.penetration[index], bb.tags[index], o);
+							float4* dp = reinterpret_cast<float4*>(raw_data + base + k);
+							dp[0] = make_float4(o.px, o.py, o.pz, o.penetration); dp[1] = make_float4(o.nx, o.ny, o.nz, o.friction);
+							raw_feature[base + k] = o.feature;
+							++k;
+						}
+					}
+				} else {
+					const nh_contact_out o = bb.kind == 1 ? bb.edge : single;
+					float4* dp = reinterpret_cast<float4*>(raw_data + base);
+					dp[0] = make_float4(o.px, o.py, o.pz, o.penetration); dp[1] = make_float4(o.nx, o.ny, o.nz, o.friction);
+					raw_feature[base] = o.feature;
+				}
+			}
+			rec[r].count = (uint32_t)count;
+			if (old != (uint32_t)count) {
+				cnt_sorted[pos] = (uint32_t)count;
+				if (!st->delta_overflow[parity]) {
+					const uint32_t k = atomicAdd(&st->delta_count[parity], 1u);
+					if (k < NH_DELTA_MAX) delta[parity * NH_DELTA_MAX + k] = make_int2((int)pos, count - (int)old);
+					else { st->delta_overflow[parity] = 1u; if (!delta_scan) changed = true; }
+				}
 			}
 		}
-		rec[r].count = (uint32_t)count;
-		const uint32_t old = cnt_sorted[pos];
-		if (old != (uint32_t)count) {
-			cnt_sorted[pos] = (uint32_t)count;
-			if (!st->delta_overflow[parity]) {
-				const uint32_t k = atomicAdd(&st->delta_count[parity], 1u);
-				if (k < NH_DELTA_MAX) delta[parity * NH_DELTA_MAX + k] = make_int2((int)pos, count - (int)old);
-				else { st->delta_overflow[parity] = 1u; if (!delta_scan) changed = true; }
-			}
-		}
+		j += stride;
+		if (j < n) r = list[j];
 	}
 	if (__ballot(changed) != 0ull && lane == 0) atomicMax(&st->still_failed_seq, seq);
 }
@@ -2300,7 +2348,10 @@ static int collide_impl(nh_context* ctx, nh_ActiveBodies* active_bodies, nh_Cont
 				          colliders->boxes.data, colliders->spheres.data, nbox, raw_data, raw_feature, pair_cap, 0u, ctx->sort_keys_by_position, rec, (uint32_t*)nullptr, \
 				          (const uint32_t*)nullptr, (const uint32_t*)nullptr, ctx->step_parity, 0u, ctx->fat_pair_capacity, aabb_min, aabb_max, gen, ctx->lay_rank, ctx->cnt_sorted, ctx->body_rec, ctx->collide_seq, ctx->still_delta, delta_scan ? 1u : 0u, (uint32_t*)nullptr, ahead_step ? 1u : 0u); } while (0)
 			if (pair_step) {
-			NH_LAUNCH(ctx, "pair_begin", k_pair_begin, 32, 256, st, ctx->step_parity, ctx->collide_seq, ctx->pair_list, ctx->pair_list_capacity, ctx->fat_pairs, ctx->fat_pair_capacity, pair_cap, gen,
+			// (one wave for the step-wide checks and one lane per listed pair -- 651 in c2: 12 waves; until a round trip has told how many the list holds, and beyond 127
+			// waves, the lanes stride over it)
+			const uint32_t pair_waves = ss.pair_world_ok ? std::min(std::max((ss.pair_listed + 63u) / 64u, 1u), 127u) : 127u;
+			NH_LAUNCH(ctx, "pair_begin", k_pair_begin, 1u + pair_waves, 64, st, ctx->step_parity, ctx->collide_seq, ctx->pair_list, ctx->pair_list_capacity, ctx->fat_pairs, ctx->fat_pair_capacity, pair_cap, gen,
 			                         xf, aabb_min, aabb_max, ctag, colliders->boxes.data, colliders->spheres.data, nbox, ctx->sort_keys_by_position, rec,
 			                         ctx->lay_rank, ctx->cnt_sorted, ctx->body_rec, ctx->still_delta, raw_data, raw_feature, bodies->momentum, bodies->properties, delta_scan ? 1u : 0u, sleepers ? B : 0u);
 			ss.early_verdict = false;
@@ -2326,7 +2377,7 @@ static int collide_impl(nh_context* ctx, nh_ActiveBodies* active_bodies, nh_Cont
 	}
 	// a full step.  (nh_step: a still step whose verdict has not been looked at yet must have happened before anything is built on it)
 	if (ctx->still.verdict.pending && nh_still_verdict_now(ctx)) return NH_INTERNAL_STILL_FAILED;
-	ctx->still.pair_ready = false; ctx->still.pair_step = false; ctx->still.early_verdict = false; ctx->still.pair_world_bad = false; ctx->still.pair_world_ok = false; ctx->still.pair_owned_seq = 0u;          // (another layout: whether every kept pair is some body's own is found out again)
+	ctx->still.pair_ready = false; ctx->still.pair_step = false; ctx->still.early_verdict = false; ctx->still.pair_world_bad = false; ctx->still.pair_world_ok = false; ctx->still.pair_listed = 0u; ctx->still.pair_owned_seq = 0u;          // (another layout: whether every kept pair is some body's own is found out again)
 	// The solver reads the caller's cache arrays and this nh_collide lays the dense contact list out -- whatever still steps kept by slot goes home first
 	{ int rc = nh_still_export_cache(ctx); if (rc) return rc; }
 	ctx->still.ahead_ready = false; ctx->still.ahead_plain = false; ctx->still.own_current = false;          // (a full step writes the arena's arrays, not own_*)

@@ -248,6 +248,7 @@ struct nh_StillStep {
 	uint32_t pair_owned_seq;        // the nh_collide (collide_seq) in which the kept pairs that are nobody's were last listed; 0: the list is void (a full step has laid the records out again)
 	bool pair_world_bad;            // a round trip showed more such pairs than the list holds: not offered until the next full step
 	bool pair_world_ok;             // ... a round trip showed the list complete (for the layout it was made from): only then are the lanes asked to evaluate their pairs
+	uint32_t pair_listed;           // ... and how many pairs that list holds (valid with pair_world_ok): k_pair_begin is launched with one lane for each
 	uint64_t pair_steps;            // statistics: still steps that were ONE solver launch (+ its one-workgroup prologue)
 	uint32_t steps_left;            // nh_step: sub-steps of this call behind the one being launched
 	uint32_t confirmed_seq;         // collide_seq of the newest still step whose verdict was "confirmed" (every drop noted in ctx->sc_undo under a later number is undone on failure)

@@ -13,7 +13,7 @@ void nh_still_note_movers(nh_context* ctx, const nh_DevState* h, uint32_t seq) {
 	// (sleepers ahead: how long has the sleeping set stood still?  Counted over confirmed still steps -- `seq` != 0 -- by the active count they report)
 	if (seq != 0u) { if (h->active == ss.sleep_last_active) { if (ss.sleep_stable < 0xffffu) ss.sleep_stable++; } else { ss.sleep_stable = 0u; ss.sleep_last_active = h->active; } }
 	// (... counted by k_pair_owned in the nh_collide numbered pair_owned_seq: counters of an earlier step, or of a full step -- which voids the count -- say nothing)
-	if (ss.pair_owned_seq != 0u && seq >= ss.pair_owned_seq) { if (h->pair_unowned > ctx->pair_list_capacity) ss.pair_world_bad = true; else ss.pair_world_ok = true; }         // (pair ahead: some kept pair is nobody's -- k_pair_owned; the step that relied on it has failed itself)
+	if (ss.pair_owned_seq != 0u && seq >= ss.pair_owned_seq) { if (h->pair_unowned > ctx->pair_list_capacity) ss.pair_world_bad = true; else { ss.pair_world_ok = true; ss.pair_listed = h->pair_unowned; } }         // (pair ahead: some kept pair is nobody's -- k_pair_owned; the step that relied on it has failed itself)
 	if (h->ahead_multi) ss.ahead_world_bad = true;          // (xform ahead: some body carries several colliders -- k_ahead_check; the step that relied on the map has failed itself)
 	if (h->fat_inserts != ss.seen_inserts) ss.movers_left = 16u;
 	else if (ss.movers_left) ss.movers_left--;
