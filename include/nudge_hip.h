@@ -79,7 +79,7 @@
  *      exported the views: nh_set_option(ctx, "sync_exports_views", 1) restores that contract at its old price; INTEGRATION.md.)  Any entry point outside the sample's
  *      call order between nh_collide and nh_apply_impulses turns a still step into a full one first, so everything it observes is what a full step
  *      produces.  nh_Counts.still_steps / still_replays count them.
- *      The scene queries (nh_query_build, nh_query_refit, nh_raycast, nh_spherecast, nh_raycast_all, nh_spherecast_all, nh_boxcast_all, nh_capsulecast_all, nh_boxcast, nh_capsulecast, nh_overlap, nh_penetration, nh_closest, nh_closest_k) are not entry points of the step in this sense: they neither export nor settle nor turn a still step into a
+ *      The scene queries (nh_query_build, nh_query_refit, nh_raycast, nh_spherecast, nh_raycast_all, nh_spherecast_all, nh_boxcast_all, nh_capsulecast_all, nh_boxcast, nh_capsulecast, nh_overlap, nh_penetration, nh_closest, nh_closest_k, nh_distance) are not entry points of the step in this sense: they neither export nor settle nor turn a still step into a
  *      full one, and they do not count -- see "scene queries" below.
  *
  * Threading: one context = one HIP stream = one world at a time; no global mutable state.
@@ -585,7 +585,7 @@ int nh_capsulecast_all(nh_context* ctx, const nh_CapsuleCast* casts, uint32_t co
      - `reserved` of every hit is written 0.
    Returns NH_ERR_INVALID before any nh_query_build, for flags != 0, and for null or not 16-byte aligned `queries` / `hits`; count = 0 is a no-op that
    returns NH_OK.  An OBSERVER like nh_raycast (note 9): no view export, no settling of deferred gravity, no still step turned into a full one, no change
-   to nh_Counts.  Not built: the distance of a shape from the world (GJK).  The k nearest colliders: nh_closest_k, below. */
+   to nh_Counts.  The distance of a shape from the world: nh_distance, below.  The k nearest colliders: nh_closest_k, below. */
 typedef struct nh_PointQuery { float point[3]; float max_distance; uint32_t ignore_body; uint32_t reserved[3]; } nh_PointQuery;                     /* 32 B */
 typedef struct nh_PointHit { float distance; float normal[3]; float point[3]; uint32_t body;
                              uint32_t collider; uint32_t shape; uint32_t tag; uint32_t reserved; } nh_PointHit;                                  /* 48 B */
@@ -683,8 +683,8 @@ int nh_overlap(nh_context* ctx, const nh_OverlapQuery* queries, uint32_t count, 
      - capsule / box: where the segment misses the box, depth = r - their distance (the end points against the box, the -a end first, then the twelve
        box edges against the segment) and normal = along their closest points; where it meets the box, depth = r + the least overlap over the box's
        face normals and the three a x e_k, normal = that axis on the centre's side.
-   No contact point and no resolved push-out of a query against all its colliders is reported: callers combine the records.  Not built: the distance
-   of a shape from colliders it does not touch (GJK).
+   No contact point and no resolved push-out of a query against all its colliders is reported: callers combine the records.  The distance
+   of a shape from colliders it does not touch: nh_distance, below.
    Cost: the chain is nh_overlap's in list mode (1.49 ms to list 1 M sphere queries of one box's size on the landed config-2 world) with a
    gather that reads 108 and writes 32 bytes per record where nh_overlap's reads 52 and writes 16.  NOT MEASURED YET: tools/penetration_rates.py times
    nh_penetration beside nh_overlap in list mode for 1 M sphere, box and capsule queries and writes profiles/penetration_rates.log; no GPU run of it
@@ -692,6 +692,57 @@ int nh_overlap(nh_context* ctx, const nh_OverlapQuery* queries, uint32_t count, 
 typedef struct nh_PenetrationHit { float normal[3]; float depth; uint32_t body; uint32_t collider; uint32_t shape; uint32_t tag; } nh_PenetrationHit;  /* 32 B */
 int nh_penetration(nh_context* ctx, const nh_OverlapQuery* queries, uint32_t count, uint32_t* offsets /* count + 1 */, nh_PenetrationHit* hits,
                    uint32_t capacity, uint32_t flags /* 0 */);
+
+/* nh_distance: how far each of `count` query shapes is from the world of the LAST nh_query_build or nh_query_refit, and towards what -- the clearance
+   of a crate, a hull or a limb.  nh_penetration describes a pair that overlaps; this describes the pairs that do not.
+   Query shapes: nh_overlap's (NH_SHAPE_SPHERE, NH_SHAPE_BOX, NH_SHAPE_CAPSULE), the same fields read and the same validity rules; the first 48 bytes
+   of nh_DistanceQuery are an nh_OverlapQuery.  `reserved` is not read.
+   Output: one nh_PointHit per query, nh_closest's record --
+     - `distance`: the key of the collider, below;
+     - `normal`: a unit vector from the collider towards the query shape;
+     - `point`: the witness on the collider's surface; the witness on the query shape is point + distance * normal;
+     - body, collider, shape, tag as in nh_closest; `reserved` = 0.
+   THE ANSWER is the smallest key with key <= max_distance over every collider of the last build or refit (those of sleeping bodies and of body 0
+   included), less those of `ignore_body` (0xffffffff: none is ignored); ties go to the lower combined collider index (boxes 0 .. nbox-1, then the
+   spheres).  A collider of a NaN pose is never reported.  A miss is nh_closest's miss record (shape = NH_SHAPE_NONE, normal = point = 0,
+   body = collider = tag = 0xffffffff) with distance = max_distance; an INVALID query -- one that nh_overlap counts 0, or whose max_distance is NaN or
+   negative -- writes the miss record with distance = NaN.  max_distance = +inf finds the nearest collider anywhere; max_distance = 0 only overlaps.
+   Per pair (exact arithmetic: nudge_amd/csrc/nh_query.h, "distance": fixed enumerations, no iterative GJK, so a brute force gives the same bytes):
+     - sphere query (c, r) / sphere or box: nh_closest's signed distance d of c, separation = d - r, its normal and its point;
+     - box query / sphere (p, R): d of p from the QUERY box, separation = d - R, that normal negated, point = p + R normal;
+     - capsule / sphere (p, R): m from p to the segment's closest point, separation = (|m| - R) - r, normal = m / |m|, point = p + R normal;
+     - capsule / box: the least of nh_penetration's SHALLOW candidates (the end points against the box, the -a end first, then the twelve box edges against
+       the segment; the first on equality) at distance d, separation = d - r, normal along the closest points, point = the box's;
+     - box query / box: the least distance over, in this order and the first on equality, the 8 vertices of the query box against the collider (vertex v
+       has the sign + on axis k where bit k of v is set), the 8 vertices of the collider against the query box, and the 144 edge pairs (the query box's
+       edges by axis x, y, z and corner (-, -), (+, -), (-, +), (+, +), each against the collider's twelve in the same order).  A box with a zero half
+       extent is valid.
+   THE OVERLAP RECORD: distance 0, normal = point = 0, the identity fields filled.  It is written where nh_overlap's predicate of the pair accepts, where
+   the computed separation is <= 0, and where there is no direction (the closest points coincide) -- the casts' START OVERLAP stance: how deep and which
+   way out is nh_penetration's answer.  INVARIANT: the normal is a unit vector iff the record is a separated one.
+   THE KEY, under the reach rule of DESIGN 10.5: key = max(separation clamped at +0, sqrtf(g2)), g2 the squared per-axis gap between the query's world
+   AABB (centre -+ r; the box's |R| size; the capsule's |a_k| + r; not padded) and the collider's own box in the hierarchy (k_q_boxes_runs' padded box).
+   The written `distance` is the key.  It moves a distance only where rounding put the pair function in front of a box padded by 2^-18 of its
+   coordinates.  THE CORNER: the key holds for an overlap record too -- should rounding ever put apart (g2 > 0) the boxes of a pair that is accepted as
+   overlapping, the record carries the distance sqrtf(g2) > 0 with its zero normal, and it competes (and is cut by max_distance) with that key, exactly
+   as the walk sees it.  Test the normal, not the distance, to tell the two kinds of record apart.  For box / box and both capsule pairs the corner
+   cannot occur: their overlap predicates require the unpadded AABBs to touch.
+   IDENTITIES (contracts):
+     - a capsule of half height 0 writes the sphere query's bytes, and its rotation is not read;
+     - a sphere of radius 0 writes nh_closest's bytes for the same point, max_distance and ignore_body, wherever nh_closest reports distance > 0;
+     - after nh_query_refit the bytes are those after an nh_query_build of the same transforms.
+   Accuracy (measured): against float64 evaluations the distance lies within 2.3e-7, and both witnesses within 3.7e-7, of the pair's sizes
+   plus centre distance.
+   Returns NH_ERR_INVALID before any nh_query_build, for flags != 0, for null or not 16-byte aligned `queries` / `hits`, and for count >= 2^30;
+   count = 0 is a no-op that returns NH_OK and launches nothing.  An OBSERVER like nh_closest (note 9): no view export, no settling of deferred gravity,
+   no still step turned into a full one, no change to nh_Counts; it never allocates and never waits, it only launches on the context's stream.
+   Cost: one lane per query on the walk of nh_closest; the box / box pair function is ~150 segment tests where nh_closest's is one clamp.
+   Measured (MI355X, the landed config-2 world of 1,004,524 colliders, 1 M queries of up to half a body's size, tools/distance_rates.py ->
+   profiles/distance_rates.log): unbounded, 1.6-1.8 ms as spheres, 4.2-4.4 ms as capsules, 33-36 ms as boxes beside nh_closest's 1.1-1.3 ms on
+   the centres; with max_distance 2 near the bodies 0.77 / 1.02 / 4.92 ms beside 0.81 ms. */
+typedef struct nh_DistanceQuery { float center[3]; uint32_t shape; float rotation[4]; float size[3]; uint32_t ignore_body;   /* = nh_OverlapQuery, 48 B */
+                                  float max_distance; uint32_t reserved[3]; } nh_DistanceQuery;                              /* 64 B */
+int nh_distance(nh_context* ctx, const nh_DistanceQuery* queries, uint32_t count, nh_PointHit* hits, uint32_t flags /* 0 */);
 
 /* ---- multi-GPU: one x-slab of a world per context ------------------------------------------------------------------------------------
    The world is cut into slabs along x, one rank (process, GPU, nh_context) per slab [lo, hi).  A rank's arrays hold

@@ -1,5 +1,5 @@
 // nh_query.h -- per-item arithmetic of the scene query (nh_query_build / nh_raycast / nh_spherecast / nh_boxcast / nh_capsulecast / nh_overlap /
-// nh_closest, nh_query.hip): a collider's world pose, a ray against one box and against one sphere, the overlap predicates of a query sphere, box or
+// nh_closest / nh_distance, nh_query.hip): a collider's world pose, a ray against one box and against one sphere, the overlap predicates of a query sphere, box or
 // capsule against one collider, a swept ball, box and capsule against one box and one sphere, the signed distance of a point from one box and one
 // sphere, with the walk's node tests they are pruned by.
 //
@@ -762,14 +762,20 @@ NH_HD nh_f3 nh_q_perpendicular(nh_f3 a) {
 	return nh_make3(v.x / len, v.y / len, v.z / len);
 }
 
-// Capsule (c, a, r), a != 0 / sphere collider (p, R): the segment's closest point c + u a with nh_q_overlap_capsule_sphere_a's own u, m = (c - p) + u a,
-// depth = (r + R) - |m|, n = m / |m|.  |m| = 0 (the segment passes through p): n = nh_q_perpendicular(a), and the depth r + R is that of every
-// direction perpendicular to the axis.
-NH_HD nh_QPen nh_q_pen_capsule_sphere_a(nh_f3 c, nh_f3 a, float r, nh_f3 p, float R) {
+// The segment-to-point step of a capsule (c, a) against the centre p of a sphere collider: m, from p to the segment's closest point c + u a, with
+// nh_q_overlap_capsule_sphere_a's own u.  nh_q_pen_capsule_sphere_a and nh_q_dist_capsule_sphere_a ("distance", below) both start from it.
+NH_HD nh_f3 nh_q_segment_point(nh_f3 c, nh_f3 a, nh_f3 p) {
 	const float aa = nh_dot(a, a);
 	float u = aa > 0.0f ? nh_dot(p - c, a) / aa : 0.0f;
 	u = u < -1.0f ? -1.0f : u > 1.0f ? 1.0f : u;
-	const nh_f3 m = (c - p) + u * a;          // ((c + u a) - p without the rounding of c + u a to the grid of the world coordinates)
+	return (c - p) + u * a;                   // ((c + u a) - p without the rounding of c + u a to the grid of the world coordinates)
+}
+
+// Capsule (c, a, r), a != 0 / sphere collider (p, R): the segment's closest point c + u a with nh_q_overlap_capsule_sphere_a's own u, m = (c - p) + u a
+// (nh_q_segment_point), depth = (r + R) - |m|, n = m / |m|.  |m| = 0 (the segment passes through p): n = nh_q_perpendicular(a), and the depth r + R is
+// that of every direction perpendicular to the axis.
+NH_HD nh_QPen nh_q_pen_capsule_sphere_a(nh_f3 c, nh_f3 a, float r, nh_f3 p, float R) {
+	const nh_f3 m = nh_q_segment_point(c, a, p);
 	const float L = sqrtf(nh_dot(m, m));
 	nh_QPen o;
 	o.n = L > 0.0f ? nh_make3(m.x / L, m.y / L, m.z / L) : nh_q_perpendicular(a);
@@ -843,8 +849,8 @@ NH_HD nh_QPen nh_q_pen_box_box(nh_f3 ca, nh_quat qa, nh_f3 ha, nh_f3 cb, nh_quat
 // two segments (Ericson, Real-Time Collision Detection 5.1.9) with d1 = a, d2 = e_k, m = o - (ci, cj, 0): u = -(a_i m_i + a_j m_j) / (a_i^2 + a_j^2)
 // clamped (0 where the two are exactly parallel), v = m_k + u a_k clamped, then u = (a_k v - a.m) / a.a clamped again where v was clamped.  Returns
 // the squared distance; w = the segment's point minus the edge's -- where neither parameter was clamped, the component of m along the lines' common
-// normal, which that difference is.
-NH_HD float nh_q_segment_edge(float oi, float oj, float ok, float ai, float aj, float ak, float A, float ci, float cj, float hk, float& wi, float& wj, float& wk) {
+// normal, which that difference is; ve = v, the edge's point on axis k (the box side's closest point is (ci, cj, ve)).
+NH_HD float nh_q_segment_edge(float oi, float oj, float ok, float ai, float aj, float ak, float A, float ci, float cj, float hk, float& wi, float& wj, float& wk, float& ve) {
 	const float mi = oi - ci, mj = oj - cj;
 	const float D = ai * ai + aj * aj;
 	const float cm = ai * mi + aj * mj;
@@ -859,11 +865,56 @@ NH_HD float nh_q_segment_edge(float oi, float oj, float ok, float ai, float aj, 
 		// both points inside their segments: w lies along the common normal (aj, -ai, 0) of the two lines, at the distance f / sqrtf(D) along it, read
 		// off m without the cancellation of m + u a when the two nearly touch
 		const float f = (mi * aj - mj * ai) / D;
-		wi = f * aj; wj = nh_neg(f * ai); wk = 0.0f;
+		wi = f * aj; wj = nh_neg(f * ai); wk = 0.0f; ve = v;
 		return wi * wi + wj * wj;
 	}
-	wi = mi + u * ai; wj = mj + u * aj; wk = (ok + u * ak) - v;
+	wi = mi + u * ai; wj = mj + u * aj; wk = (ok + u * ak) - v; ve = v;
 	return wi * wi + wj * wj + wk * wk;
+}
+
+// The SHALLOW candidates of a segment ol + u al, u in [-1, 1] (A = al.al), against the box [-hb, hb], all in the box frame -- shared by
+// nh_q_pen_capsule_box_a and the distance functions below, which enumerate the same candidates in the same order:
+//   1. the two END POINTS against the box (the point minus its clamp to [-h, h]), the -a end first;
+//   2. the twelve box EDGES against the segment (nh_q_segment_edge): by axis x, y, z, and on each the corners (-, -), (+, -), (-, +), (+, +) on the other
+//      two axes.
+// Returns the least squared distance, the first candidate on equality (INFINITY where every candidate is NaN); w = the segment's point minus the box's,
+// xb = the box's point.  FACES need no case of their own (nh_q_pen_capsule_box_a says why).  Its two halves stand alone for the box / box distance:
+// nh_q_vertex_box offers one point (true where it became the least so far), nh_q_segment_edges the twelve edges.
+NH_HD bool nh_q_vertex_box(nh_f3 x, nh_f3 hb, float& dd, nh_f3& w, nh_f3& xb) {
+	const nh_f3 ql = nh_make3(nh_max(nh_neg(hb.x), nh_min(x.x, hb.x)), nh_max(nh_neg(hb.y), nh_min(x.y, hb.y)), nh_max(nh_neg(hb.z), nh_min(x.z, hb.z)));
+	const nh_f3 v = x - ql;
+	const float vv = nh_dot(v, v);
+	if (!(vv < dd)) return false;
+	dd = vv; w = v; xb = ql;
+	return true;
+}
+
+NH_HD void nh_q_segment_edges(nh_f3 ol, nh_f3 al, float A, nh_f3 hb, float& dd, nh_f3& w, nh_f3& xb) {
+	// the edges along axis k, at (-+h_i, -+h_j) on the other two axes i, j
+	for (int k = 0; k < 3; ++k) {
+		const float ai = k == 0 ? al.y : k == 1 ? al.z : al.x, aj = k == 0 ? al.z : k == 1 ? al.x : al.y, ak = k == 0 ? al.x : k == 1 ? al.y : al.z;
+		const float bi = k == 0 ? ol.y : k == 1 ? ol.z : ol.x, bj = k == 0 ? ol.z : k == 1 ? ol.x : ol.y, bk = k == 0 ? ol.x : k == 1 ? ol.y : ol.z;
+		const float hi = k == 0 ? hb.y : k == 1 ? hb.z : hb.x, hj = k == 0 ? hb.z : k == 1 ? hb.x : hb.y, hk = k == 0 ? hb.x : k == 1 ? hb.y : hb.z;
+		for (int e = 0; e < 4; ++e) {
+			const float ci = (e & 1) ? hi : nh_neg(hi), cj = (e & 2) ? hj : nh_neg(hj);
+			float wi, wj, wk, ve;
+			const float vv = nh_q_segment_edge(bi, bj, bk, ai, aj, ak, A, ci, cj, hk, wi, wj, wk, ve);
+			if (vv < dd) {
+				dd = vv;
+				w = nh_make3(k == 0 ? wk : k == 1 ? wj : wi, k == 0 ? wi : k == 1 ? wk : wj, k == 0 ? wj : k == 1 ? wi : wk);
+				xb = nh_make3(k == 0 ? ve : k == 1 ? cj : ci, k == 0 ? ci : k == 1 ? ve : cj, k == 0 ? cj : k == 1 ? ci : ve);
+			}
+		}
+	}
+}
+
+NH_HD float nh_q_segment_box(nh_f3 ol, nh_f3 al, float A, nh_f3 hb, nh_f3& w, nh_f3& xb) {
+	w = nh_make3(0.0f, 0.0f, 0.0f); xb = nh_make3(0.0f, 0.0f, 0.0f);
+	float dd = INFINITY;
+	nh_q_vertex_box(ol - al, hb, dd, w, xb);
+	nh_q_vertex_box(ol + al, hb, dd, w, xb);
+	nh_q_segment_edges(ol, al, A, hb, dd, w, xb);
+	return dd;
 }
 
 // Capsule (c, a, r), a != 0 / box collider (p, qb, hb), in the box frame (the inverse of qb, as in nh_q_sweep_capsule_box): the centre and the half
@@ -896,28 +947,9 @@ NH_HD nh_QPen nh_q_pen_capsule_box_a(nh_f3 c, nh_f3 a, float r, nh_f3 p, nh_quat
 	nh_q_slab(ol.y, al.y, hb.y, 1, u0, u1, enter, all);
 	nh_q_slab(ol.z, al.z, hb.z, 2, u0, u1, enter, all);
 	if (!(all && u0 <= u1)) {
-		// SHALLOW 1. the end points
-		nh_f3 w = nh_make3(0.0f, 0.0f, 0.0f);
-		float dd = INFINITY;
-		for (int e = 0; e < 2; ++e) {
-			const nh_f3 x = e == 0 ? ol - al : ol + al;
-			const nh_f3 ql = nh_make3(nh_max(nh_neg(hb.x), nh_min(x.x, hb.x)), nh_max(nh_neg(hb.y), nh_min(x.y, hb.y)), nh_max(nh_neg(hb.z), nh_min(x.z, hb.z)));
-			const nh_f3 v = x - ql;
-			const float vv = nh_dot(v, v);
-			if (vv < dd) { dd = vv; w = v; }
-		}
-		// 2. the edges along axis k, at (-+h_i, -+h_j) on the other two axes i, j
-		for (int k = 0; k < 3; ++k) {
-			const float ai = k == 0 ? al.y : k == 1 ? al.z : al.x, aj = k == 0 ? al.z : k == 1 ? al.x : al.y, ak = k == 0 ? al.x : k == 1 ? al.y : al.z;
-			const float bi = k == 0 ? ol.y : k == 1 ? ol.z : ol.x, bj = k == 0 ? ol.z : k == 1 ? ol.x : ol.y, bk = k == 0 ? ol.x : k == 1 ? ol.y : ol.z;
-			const float hi = k == 0 ? hb.y : k == 1 ? hb.z : hb.x, hj = k == 0 ? hb.z : k == 1 ? hb.x : hb.y, hk = k == 0 ? hb.x : k == 1 ? hb.y : hb.z;
-			for (int e = 0; e < 4; ++e) {
-				const float ci = (e & 1) ? hi : nh_neg(hi), cj = (e & 2) ? hj : nh_neg(hj);
-				float wi, wj, wk;
-				const float vv = nh_q_segment_edge(bi, bj, bk, ai, aj, ak, A, ci, cj, hk, wi, wj, wk);
-				if (vv < dd) { dd = vv; w = nh_make3(k == 0 ? wk : k == 1 ? wj : wi, k == 0 ? wi : k == 1 ? wk : wj, k == 0 ? wj : k == 1 ? wi : wk); }
-			}
-		}
+		// SHALLOW: the end points, then the edges (nh_q_segment_box)
+		nh_f3 w, xb;
+		const float dd = nh_q_segment_box(ol, al, A, hb, w, xb);
 		if (dd > 0.0f && dd < INFINITY) {
 			const float d = sqrtf(dd);
 			o.n = nh_rotate(qb, nh_make3(w.x / d, w.y / d, w.z / d));
@@ -965,6 +997,152 @@ NH_HD nh_QPen nh_q_pen_capsule_box(nh_f3 c, nh_quat q, float r, float hh, nh_f3 
 	if (hh == 0.0f) return nh_q_pen_sphere_box(c, r, p, qb, hb);
 	return nh_q_pen_capsule_box_a(c, nh_q_capsule_axis(q, hh), r, p, qb, hb);
 }
+
+// ---- distance (nh_distance): how far a query shape is from one collider it does not touch, and towards what ---------------------------------------------
+// One function per pair, each a fixed, loop-free-in-the-data enumeration (no iteration to a tolerance: the host's brute force runs the same operations and
+// gets the same bits).  Each returns an nh_QPoint: d = the separation, n = the unit normal from the collider towards the query shape, x = the witness on the
+// collider's surface (the witness on the query shape is x + d n).  THE OVERLAP RECORD is d = +0, n = x = 0: it is returned when nh_overlap's predicate of
+// the pair accepts, when the computed separation is <= 0, and when there is no direction (the closest points coincide).  How deep and which way out is
+// nh_penetration's answer.  So n is a unit vector iff d > 0.  A collider of a NaN pose gives d = NaN, which no comparison accepts.
+NH_HD nh_QPoint nh_q_dist_overlap() {
+	nh_QPoint r; r.d = 0.0f; r.n = nh_make3(0.0f, 0.0f, 0.0f); r.x = nh_make3(0.0f, 0.0f, 0.0f);
+	return r;
+}
+NH_HD nh_QPoint nh_q_dist_apart(float sep, nh_f3 n, nh_f3 x) {
+	if (sep <= 0.0f) return nh_q_dist_overlap();          // (a NaN goes on as a NaN)
+	nh_QPoint r; r.d = sep; r.n = n; r.x = x;
+	return r;
+}
+
+// Sphere query (c, r) / sphere collider (p, R) and box collider (p, q, h): nh_q_point_sphere / nh_q_point_box of the centre; separation = d - r, its normal
+// and its point.  r = 0 is nh_closest's answer wherever that is positive.
+NH_HD nh_QPoint nh_q_dist_sphere_sphere(nh_f3 c, float r, nh_f3 p, float R) {
+	if (nh_q_overlap_sphere_sphere(c, r, p, R)) return nh_q_dist_overlap();
+	const nh_QPoint s = nh_q_point_sphere(c, p, R);
+	return nh_q_dist_apart(s.d - r, s.n, s.x);
+}
+NH_HD nh_QPoint nh_q_dist_sphere_box(nh_f3 c, float r, nh_f3 p, nh_quat q, nh_f3 h) {
+	if (nh_q_overlap_sphere_box(c, r, p, q, h)) return nh_q_dist_overlap();
+	const nh_QPoint s = nh_q_point_box(c, p, q, h);
+	return nh_q_dist_apart(s.d - r, s.n, s.x);
+}
+
+// Box query (ca, qa, ha) / sphere collider (p, R): nh_q_point_box of p against the QUERY box; separation = d - R, the normal is that normal negated (it
+// points from the query box to the sphere), the point p + R n.
+NH_HD nh_QPoint nh_q_dist_box_sphere(nh_f3 ca, nh_quat qa, nh_f3 ha, nh_f3 p, float R) {
+	if (nh_q_overlap_sphere_box(p, R, ca, qa, ha)) return nh_q_dist_overlap();
+	const nh_QPoint s = nh_q_point_box(p, ca, qa, ha);
+	const nh_f3 n = nh_make3(nh_neg(s.n.x), nh_neg(s.n.y), nh_neg(s.n.z));
+	return nh_q_dist_apart(s.d - R, n, p + n * R);
+}
+
+// Capsule (c, a, r), a != 0 / sphere collider (p, R): m from p to the segment's closest point (nh_q_segment_point, nh_q_pen_capsule_sphere_a's);
+// separation = (|m| - R) - r, n = m / |m|, point = p + R n.  |m| = 0 has a separation <= 0: the overlap record.
+NH_HD nh_QPoint nh_q_dist_capsule_sphere_a(nh_f3 c, nh_f3 a, float r, nh_f3 p, float R) {
+	if (nh_q_overlap_capsule_sphere_a(c, a, r, p, R)) return nh_q_dist_overlap();
+	const nh_f3 m = nh_q_segment_point(c, a, p);
+	const float L = sqrtf(nh_dot(m, m));
+	const nh_f3 n = nh_make3(m.x / L, m.y / L, m.z / L);
+	return nh_q_dist_apart((L - R) - r, n, p + n * R);
+}
+
+// Capsule (c, a, r), a != 0 / box collider (p, qb, hb): the least of nh_q_pen_capsule_box_a's SHALLOW candidates (nh_q_segment_box: the end points, the -a
+// end first, then the twelve edges; the first on equality) in the box frame; separation = d - r, n = w / d turned to world, point = the box side's closest
+// point in world.  (A segment that passes through the box has candidates of its own, all wrong; nh_overlap's predicate, asked first, accepts it.)
+NH_HD nh_QPoint nh_q_dist_capsule_box_a(nh_f3 c, nh_f3 a, float r, nh_f3 p, nh_quat qb, nh_f3 hb) {
+	if (nh_q_overlap_capsule_box_a(c, a, r, p, qb, hb)) return nh_q_dist_overlap();
+	const nh_quat qi = { nh_neg(qb.x), nh_neg(qb.y), nh_neg(qb.z), qb.s };
+	const nh_f3 ol = nh_rotate(qi, c - p), al = nh_rotate(qi, a);
+	nh_f3 w, xb;
+	const float dd = nh_q_segment_box(ol, al, nh_dot(al, al), hb, w, xb);
+	if (!(dd < INFINITY)) return nh_q_dist_apart(nh_asfloat(0x7fc00000u), w, xb);          // (every candidate NaN: a NaN pose)
+	if (!(dd > 0.0f)) return nh_q_dist_overlap();
+	const float d = sqrtf(dd);
+	return nh_q_dist_apart(d - r, nh_rotate(qb, nh_make3(w.x / d, w.y / d, w.z / d)), p + nh_rotate(qb, xb));
+}
+
+// Box query a (ca, qa, ha) / box collider b (cb, qb, hb): the least squared distance over a fixed list of candidates, the first on equality:
+//   1. the 8 vertices of a, in b's frame, against b -- the vertex minus its clamp to [-hb, hb] (nh_q_vertex_box).  In b's frame a's centre is
+//      o = Rb^T (ca - cb) and its scaled axes a_k = Rb^T (A_k ha_k); vertex v (0 .. 7) is ((o + s0 a_0) + s1 a_1) + s2 a_2 with s_k = +1 where bit k of v
+//      is set and -1 otherwise;
+//   2. the 8 vertices of b, in a's frame, against a, numbered the same way;
+//   3. the 144 edge pairs: each of a's 12 edges as a segment in b's frame -- by axis i = x, y, z, and on each the corners (-, -), (+, -), (-, +), (+, +)
+//      on the axes (i + 1) % 3, (i + 2) % 3: centre (o + s1 a_j) + s2 a_k, half axis a_i -- against b's 12 edges in nh_q_segment_edges' order.  An edge of
+//      a box with ha_i = 0 is its vertex (group 1) and is skipped.
+// This is exact: the closest features of two disjoint convex polytopes always contain a vertex / face or an edge / edge pair at the same distance (a face
+// against a face or an edge is nearest at a vertex or at a crossing of edges, as "FACES need no case of their own" argues for the capsule), a vertex
+// against the whole box covers vertex / anything, and a segment against an edge covers edge / edge with the clamps at the ends.
+// separation = sqrtf of that least, n = (a's point - b's point) / separation and point = b's point, turned to world from the frame the candidate was
+// found in.  A box with a zero half extent is valid on either side.
+NH_HD nh_QPoint nh_q_dist_box_box(nh_f3 ca, nh_quat qa, nh_f3 ha, nh_f3 cb, nh_quat qb, nh_f3 hb) {
+	if (nh_q_overlap_box_box(ca, qa, ha, cb, qb, hb)) return nh_q_dist_overlap();
+	const nh_quat qai = { nh_neg(qa.x), nh_neg(qa.y), nh_neg(qa.z), qa.s }, qbi = { nh_neg(qb.x), nh_neg(qb.y), nh_neg(qb.z), qb.s };
+	const nh_m33 A = nh_matrix(qa), B = nh_matrix(qb);
+	float dd = INFINITY;
+	nh_f3 w = nh_make3(0.0f, 0.0f, 0.0f), xb = nh_make3(0.0f, 0.0f, 0.0f);          // a's point minus b's, and b's point, in the frame `in_a` says
+	bool in_a = false;
+	const nh_f3 o = nh_rotate(qbi, ca - cb);
+	const nh_f3 a0 = nh_rotate(qbi, A.c0 * ha.x), a1 = nh_rotate(qbi, A.c1 * ha.y), a2 = nh_rotate(qbi, A.c2 * ha.z);
+	// 1. a's vertices against b
+	for (int v = 0; v < 8; ++v) {
+		const float s0 = (v & 1) ? 1.0f : -1.0f, s1 = (v & 2) ? 1.0f : -1.0f, s2 = (v & 4) ? 1.0f : -1.0f;
+		nh_q_vertex_box(((o + s0 * a0) + s1 * a1) + s2 * a2, hb, dd, w, xb);
+	}
+	// 2. b's vertices against a: the candidate's vector points from a's point to the vertex, so w is its negative and b's point is the vertex itself
+	{
+		const nh_f3 m = nh_rotate(qai, cb - ca);
+		const nh_f3 b0 = nh_rotate(qai, B.c0 * hb.x), b1 = nh_rotate(qai, B.c1 * hb.y), b2 = nh_rotate(qai, B.c2 * hb.z);
+		for (int v = 0; v < 8; ++v) {
+			const float s0 = (v & 1) ? 1.0f : -1.0f, s1 = (v & 2) ? 1.0f : -1.0f, s2 = (v & 4) ? 1.0f : -1.0f;
+			const nh_f3 x = ((m + s0 * b0) + s1 * b1) + s2 * b2;
+			nh_f3 e, ql;
+			if (nh_q_vertex_box(x, ha, dd, e, ql)) { w = nh_make3(nh_neg(e.x), nh_neg(e.y), nh_neg(e.z)); xb = x; in_a = true; }
+		}
+	}
+	// 3. a's edges against b's edges
+	for (int i = 0; i < 3; ++i) {
+		const nh_f3 al = i == 0 ? a0 : i == 1 ? a1 : a2, aj = i == 0 ? a1 : i == 1 ? a2 : a0, ak = i == 0 ? a2 : i == 1 ? a0 : a1;
+		const float AA = nh_dot(al, al);
+		if (!(AA > 0.0f)) continue;
+		for (int e = 0; e < 4; ++e) {
+			const float s1 = (e & 1) ? 1.0f : -1.0f, s2 = (e & 2) ? 1.0f : -1.0f;
+			const float before = dd;
+			nh_q_segment_edges((o + s1 * aj) + s2 * ak, al, AA, hb, dd, w, xb);
+			if (dd < before) in_a = false;
+		}
+	}
+	if (!(dd < INFINITY)) return nh_q_dist_apart(nh_asfloat(0x7fc00000u), w, xb);          // (every candidate NaN: a NaN pose)
+	if (!(dd > 0.0f)) return nh_q_dist_overlap();
+	const float d = sqrtf(dd);
+	const nh_quat qf = in_a ? qa : qb;
+	const nh_f3 cf = in_a ? ca : cb;
+	return nh_q_dist_apart(d, nh_rotate(qf, nh_make3(w.x / d, w.y / d, w.z / d)), cf + nh_rotate(qf, xb));
+}
+
+// nh_distance's capsule functions: hh = 0 is the sphere query's function itself (and q is not read).
+NH_HD nh_QPoint nh_q_dist_capsule_sphere(nh_f3 c, nh_quat q, float r, float hh, nh_f3 p, float R) {
+	if (hh == 0.0f) return nh_q_dist_sphere_sphere(c, r, p, R);
+	return nh_q_dist_capsule_sphere_a(c, nh_q_capsule_axis(q, hh), r, p, R);
+}
+NH_HD nh_QPoint nh_q_dist_capsule_box(nh_f3 c, nh_quat q, float r, float hh, nh_f3 p, nh_quat qb, nh_f3 hb) {
+	if (hh == 0.0f) return nh_q_dist_sphere_box(c, r, p, qb, hb);
+	return nh_q_dist_capsule_box_a(c, nh_q_capsule_axis(q, hh), r, p, qb, hb);
+}
+
+// The squared gap between the query's world AABB [qlo, qhi] (centre -+ r, nh_q_box_extent or nh_q_capsule_extent; not padded) and the box [lo, hi] of a
+// node or a leaf: nh_q_point_node's operations with an interval in place of the point -- per axis fmaxf(fmaxf(lo - qhi, qlo - hi), 0), then the sum of the
+// squares in x, y, z order.  Monotone in the box: a box inside another never has the smaller gap.  With qlo = qhi = p it IS nh_q_point_node(lo, hi, p).
+NH_HD float nh_q_dist_node(nh_f3 lo, nh_f3 hi, nh_f3 qlo, nh_f3 qhi) {
+	const float ax = fmaxf(fmaxf(lo.x - qhi.x, qlo.x - hi.x), 0.0f);
+	const float ay = fmaxf(fmaxf(lo.y - qhi.y, qlo.y - hi.y), 0.0f);
+	const float az = fmaxf(fmaxf(lo.z - qhi.z, qlo.z - hi.z), 0.0f);
+	return ax * ax + ay * ay + az * az;
+}
+// The key of a pair under the reach rule: nh_q_point_key(d, g2) with d the pair function's separation (>= +0, or NaN) and g2 =
+// nh_q_dist_node of the collider's OWN leaf box (nh_q_leaf_box) -- max(d, sqrtf(g2)).  A function of the pair alone, so the answer does not depend on the
+// walk.  It is the `distance` that is written, for an overlap record as well: where nh_overlap's predicate accepts a pair whose boxes rounding has put
+// apart (g2 > 0; it cannot happen for box / box and the capsule pairs, whose predicates ask that the unpadded boxes touch, and float subtraction is
+// monotone), the overlap record carries that tiny positive distance with its zero normal -- the normal, not the distance, says which kind a record is.
 
 // ---- all-hits casts (nh_raycast_all / nh_spherecast_all / nh_boxcast_all / nh_capsulecast_all): the hit of ONE collider, as the closest-hit walk decides it at a leaf with no best so far --
 // The ray's own predicates (SWEEP = false) or the swept ball's with the reach rule for r > 0 (SWEEP = true; t0 = the entry into the collider's leaf box

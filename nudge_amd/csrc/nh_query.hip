@@ -528,12 +528,38 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
 // ---- closest point ----------------------------------------------------------------------------------------------------------------------------
 // One lane per query.  The bound bd starts at max_distance and only ever falls to the key of a real candidate (nh_q_point_key, nh_q_closer: the reach
 // rule of DESIGN 10.5), so a node of squared distance d2 > 0 from p with sqrtf(d2) > bd can be skipped, and one with d2 = 0 is always entered.
-//   seed  p's Morton key in the frame of the last build (clamped to its bounds), its place among the sorted keys by binary search, and the exact keys of
+//   seed  nh_q_seed: p's Morton key in the frame of the last build (clamped to its bounds), its place among the sorted keys by binary search, and the exact keys of
 //         the NH_Q_SEED leaves on either side of that place: a bound near p before the walk, which otherwise goes left first from the root -- towards
 //         the lowest Morton region, usually far from p.  Compiled out by -DNH_Q_CLOSEST_NO_SEED (tools/closest_rates.py measures both).
 //   walk  nh_q_walk with the node test above; the leaves evaluate nh_q_point_box / nh_q_point_sphere and the key.  A seeded winner
 //         met again does not replace itself (equal key and index), so the seed changes the work, never the answer.
 #define NH_Q_SEED 4
+// The Morton seed of the nearest-collider walks (k_q_closest, k_q_closest_k, k_q_distance): p's Morton key in the frame of the last build (clamped to its
+// bounds), its place among the sorted keys by binary search, and the `win` leaves on either side of that place -- visit(c, record, lo, hi) for each whose
+// body is not `ignore`, with its leaf box.  It only proposes real colliders to the caller's own leaf function, so it changes the work, never the answer.
+template <class Visit>
+__device__ __forceinline__ void nh_q_seed(nh_f3 p, uint32_t win, uint32_t ignore, const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec,
+                                          const uint64_t* __restrict__ keys, const nh_QCtl* __restrict__ ctl, uint32_t n, Visit visit) {
+	const nh_f3 smin = nh_make3(nh_float_unflip(ctl->kmin[0]), nh_float_unflip(ctl->kmin[1]), nh_float_unflip(ctl->kmin[2]));
+	const nh_f3 smax = nh_make3(nh_float_unflip(ctl->kmax[0]), nh_float_unflip(ctl->kmax[1]), nh_float_unflip(ctl->kmax[2]));
+	const float scale = nh_morton_scale(smin, smax);
+	const nh_f3 pc = nh_make3(fminf(fmaxf(p.x, smin.x), smax.x), fminf(fmaxf(p.y, smin.y), smax.y), fminf(fmaxf(p.z, smin.z), smax.z));
+	const uint64_t key = nh_morton_of(pc, scale, smin * scale);
+	uint32_t lo = 0u, hi = n;
+	while (lo < hi) {
+		const uint32_t mid = (lo + hi) >> 1;
+		if (keys[mid] < key) lo = mid + 1u; else hi = mid;
+	}
+	const uint32_t j0 = lo > win ? lo - win : 0u, j1 = n - lo > win ? lo + win : n;
+	for (uint32_t j = j0; j < j1; ++j) {
+		const float4 na = nodes[n - 1u + j].a, nb = nodes[n - 1u + j].b;
+		const uint32_t c = __float_as_uint(na.w) & ~NH_Q_LEAF;
+		const nh_QRec q = rec[c];
+		if (__float_as_uint(q.a.w) == ignore) continue;
+		visit(c, q, nh_make3(na.x, na.y, na.z), nh_make3(nb.x, nb.y, nb.z));
+	}
+}
+
 __global__ __launch_bounds__(256) void k_q_closest(const nh_PointQuery* __restrict__ queries, uint32_t count, nh_PointHit* __restrict__ hits,
                                                    const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec, const uint64_t* __restrict__ keys,
                                                    const nh_QCtl* __restrict__ ctl, uint32_t n, uint32_t nbox) {
@@ -557,26 +583,7 @@ __global__ __launch_bounds__(256) void k_q_closest(const nh_PointQuery* __restri
 			return false;
 		};
 #ifndef NH_Q_CLOSEST_NO_SEED
-		if (walk) {
-			const nh_f3 smin = nh_make3(nh_float_unflip(ctl->kmin[0]), nh_float_unflip(ctl->kmin[1]), nh_float_unflip(ctl->kmin[2]));
-			const nh_f3 smax = nh_make3(nh_float_unflip(ctl->kmax[0]), nh_float_unflip(ctl->kmax[1]), nh_float_unflip(ctl->kmax[2]));
-			const float scale = nh_morton_scale(smin, smax);
-			const nh_f3 pc = nh_make3(fminf(fmaxf(p.x, smin.x), smax.x), fminf(fmaxf(p.y, smin.y), smax.y), fminf(fmaxf(p.z, smin.z), smax.z));
-			const uint64_t key = nh_morton_of(pc, scale, smin * scale);
-			uint32_t lo = 0u, hi = n;
-			while (lo < hi) {
-				const uint32_t mid = (lo + hi) >> 1;
-				if (keys[mid] < key) lo = mid + 1u; else hi = mid;
-			}
-			const uint32_t j0 = lo > NH_Q_SEED ? lo - NH_Q_SEED : 0u, j1 = n - lo > NH_Q_SEED ? lo + NH_Q_SEED : n;
-			for (uint32_t j = j0; j < j1; ++j) {
-				const float4 na = nodes[n - 1u + j].a, nb = nodes[n - 1u + j].b;
-				const uint32_t c = __float_as_uint(na.w) & ~NH_Q_LEAF;
-				const nh_QRec q = rec[c];
-				if (__float_as_uint(q.a.w) == ignore) continue;
-				leaf(c, q, nh_q_point_node(nh_make3(na.x, na.y, na.z), nh_make3(nb.x, nb.y, nb.z), p));
-			}
-		}
+		if (walk) nh_q_seed(p, NH_Q_SEED, ignore, nodes, rec, keys, ctl, n, [&](uint32_t c, const nh_QRec& q, nh_f3 lo, nh_f3 hi) { leaf(c, q, nh_q_point_node(lo, hi, p)); });
 #endif
 		nh_q_walk(nodes, rec, walk ? 0u : NH_Q_NONE, ignore,
 			[&](nh_f3 lo, nh_f3 hi, float& d2) { d2 = nh_q_point_node(lo, hi, p); return !(d2 > 0.0f && sqrtf(d2) > bd); }, leaf);
@@ -643,27 +650,7 @@ __global__ __launch_bounds__(256) void k_q_closest_k(const nh_PointQuery* __rest
 			return false;
 		};
 #ifndef NH_Q_CLOSEST_K_NO_SEED
-		if (walk) {
-			const nh_f3 smin = nh_make3(nh_float_unflip(ctl->kmin[0]), nh_float_unflip(ctl->kmin[1]), nh_float_unflip(ctl->kmin[2]));
-			const nh_f3 smax = nh_make3(nh_float_unflip(ctl->kmax[0]), nh_float_unflip(ctl->kmax[1]), nh_float_unflip(ctl->kmax[2]));
-			const float scale = nh_morton_scale(smin, smax);
-			const nh_f3 pc = nh_make3(fminf(fmaxf(p.x, smin.x), smax.x), fminf(fmaxf(p.y, smin.y), smax.y), fminf(fmaxf(p.z, smin.z), smax.z));
-			const uint64_t key = nh_morton_of(pc, scale, smin * scale);
-			uint32_t lo = 0u, hi = n;
-			while (lo < hi) {
-				const uint32_t mid = (lo + hi) >> 1;
-				if (keys[mid] < key) lo = mid + 1u; else hi = mid;
-			}
-			const uint32_t win = NH_Q_SEED + k / 2u;
-			const uint32_t j0 = lo > win ? lo - win : 0u, j1 = n - lo > win ? lo + win : n;
-			for (uint32_t j = j0; j < j1; ++j) {
-				const float4 na = nodes[n - 1u + j].a, nb = nodes[n - 1u + j].b;
-				const uint32_t c = __float_as_uint(na.w) & ~NH_Q_LEAF;
-				const nh_QRec q = rec[c];
-				if (__float_as_uint(q.a.w) == ignore) continue;
-				leaf(c, q, nh_q_point_node(nh_make3(na.x, na.y, na.z), nh_make3(nb.x, nb.y, nb.z), p));
-			}
-		}
+		if (walk) nh_q_seed(p, NH_Q_SEED + k / 2u, ignore, nodes, rec, keys, ctl, n, [&](uint32_t c, const nh_QRec& q, nh_f3 lo, nh_f3 hi) { leaf(c, q, nh_q_point_node(lo, hi, p)); });
 #endif
 		nh_q_walk(nodes, rec, walk ? 0u : NH_Q_NONE, ignore,
 			[&](nh_f3 lo, nh_f3 hi, float& d2) { d2 = nh_q_point_node(lo, hi, p); return !(d2 > 0.0f && sqrtf(d2) > bd); }, leaf);
@@ -685,6 +672,67 @@ __global__ __launch_bounds__(256) void k_q_closest_k(const nh_PointQuery* __rest
 			hp[2] = make_float4(__uint_as_float(NH_Q_NONE), __uint_as_float(NH_SHAPE_NONE), __uint_as_float(NH_Q_NONE), 0.0f);
 		}
 		if (counts) counts[i] = held;
+	}
+}
+
+// ---- distance ---------------------------------------------------------------------------------------------------------------------------------
+// nh_distance: one lane per query shape on nh_q_walk, k_q_closest with a volume in place of the point.
+//   decode  k_q_overlap's: the shape, its validity (nh_overlap's, and max_distance >= 0), the half axis of a capsule, the world AABB [qlo, qhi] (not padded)
+//   bound   bd starts at max_distance and only ever falls to the key of a real candidate (nh_q_point_key of the pair function's separation and the gap to
+//           the collider's own leaf box, nh_q_closer), so a node at squared gap g2 > 0 from the query's AABB with sqrtf(g2) > bd can be skipped: the gap is
+//           monotone from a leaf box to every box that contains it (nh_q_dist_node), and a collider's key is at least sqrtf of its leaf's gap
+//   seed    nh_q_seed at the query's centre, k_q_closest's window
+//   leaf    the pair function of nh_query.h, "distance"; one instantiation serves every shape, the lanes of a wave diverge by the shapes of neighbouring
+//           queries and colliders (the box / box enumeration sets the registers)
+__global__ __launch_bounds__(256) void k_q_distance(const nh_DistanceQuery* __restrict__ queries, uint32_t count, nh_PointHit* __restrict__ hits,
+                                                    const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec, const uint64_t* __restrict__ keys,
+                                                    const nh_QCtl* __restrict__ ctl, uint32_t n, uint32_t nbox) {
+	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
+		const float4* qp = reinterpret_cast<const float4*>(queries + i);
+		const float4 q0 = qp[0], q1 = qp[1], q2 = qp[2];
+		const float max_d = qp[3].x;          // (the record moves as four 16-byte words; of the fourth only .x is used: `reserved` takes part in nothing)
+		const nh_f3 c = nh_make3(q0.x, q0.y, q0.z), h = nh_make3(q2.x, q2.y, q2.z);
+		const nh_quat qr = { q1.x, q1.y, q1.z, q1.w };
+		const uint32_t shape = __float_as_uint(q0.w), ignore = __float_as_uint(q2.w);
+		// (a capsule of half height 0 is a sphere query: the same functions, its rotation not read)
+		const bool capsule = shape == NH_SHAPE_CAPSULE && h.y != 0.0f;
+		const bool sphere = !capsule && (shape == NH_SHAPE_SPHERE || shape == NH_SHAPE_CAPSULE);
+		bool ok = (sphere || capsule || shape == NH_SHAPE_BOX) && nh_q_finite(c) && nh_q_finite(h.x) && !(h.x < 0.0f) && max_d >= 0.0f;
+		if (!sphere) ok = ok && nh_q_finite(h.y) && !(h.y < 0.0f) && nh_q_finite(qr);
+		if (!sphere && !capsule) ok = ok && nh_q_finite(h.z) && !(h.z < 0.0f);
+		const nh_f3 a = capsule ? nh_q_capsule_axis(qr, h.y) : nh_make3(0.0f, 0.0f, 0.0f);
+		const nh_f3 e = sphere ? nh_make3(h.x, h.x, h.x) : capsule ? nh_q_capsule_extent(a, h.x) : nh_q_box_extent(qr, h);
+		const nh_f3 qlo = c - e, qhi = c + e;
+		float bd = max_d;
+		uint32_t bc = NH_Q_NONE;
+		nh_f3 bn = nh_make3(0.0f, 0.0f, 0.0f), bx = nh_make3(0.0f, 0.0f, 0.0f);
+		const bool walk = ok && n;
+		// a leaf at squared box gap g2, for the seed and the walk alike
+		const auto leaf = [&](uint32_t cc, const nh_QRec& r, float g2) {
+			const nh_QShape s = nh_q_unpack(r);
+			nh_QPoint d;
+			if (capsule) d = cc < nbox ? nh_q_dist_capsule_box_a(c, a, h.x, s.p, s.q, s.h) : nh_q_dist_capsule_sphere_a(c, a, h.x, s.p, s.h.x);
+			else if (cc < nbox) d = sphere ? nh_q_dist_sphere_box(c, h.x, s.p, s.q, s.h) : nh_q_dist_box_box(c, qr, h, s.p, s.q, s.h);
+			else d = sphere ? nh_q_dist_sphere_sphere(c, h.x, s.p, s.h.x) : nh_q_dist_box_sphere(c, qr, h, s.p, s.h.x);
+			const float k = nh_q_point_key(d.d, g2);
+			if (nh_q_closer(k, cc, max_d, bd, bc)) { bd = k; bc = cc; bn = d.n; bx = d.x; }
+			return false;
+		};
+		if (walk) nh_q_seed(c, NH_Q_SEED, ignore, nodes, rec, keys, ctl, n, [&](uint32_t cc, const nh_QRec& r, nh_f3 lo, nh_f3 hi) { leaf(cc, r, nh_q_dist_node(lo, hi, qlo, qhi)); });
+		nh_q_walk(nodes, rec, walk ? 0u : NH_Q_NONE, ignore,
+			[&](nh_f3 lo, nh_f3 hi, float& g2) { g2 = nh_q_dist_node(lo, hi, qlo, qhi); return !(g2 > 0.0f && sqrtf(g2) > bd); }, leaf);
+		float4* hp = reinterpret_cast<float4*>(hits + i);
+		if (bc == NH_Q_NONE) {
+			const float md = ok ? max_d : __uint_as_float(0x7fc00000u);
+			hp[0] = make_float4(md, 0.0f, 0.0f, 0.0f);
+			hp[1] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(NH_Q_NONE));
+			hp[2] = make_float4(__uint_as_float(NH_Q_NONE), __uint_as_float(NH_SHAPE_NONE), __uint_as_float(NH_Q_NONE), 0.0f);
+		} else {
+			const uint4 id = nh_q_identity(bc, nbox, rec[bc]);
+			hp[0] = make_float4(bd, bn.x, bn.y, bn.z);
+			hp[1] = make_float4(bx.x, bx.y, bx.z, __uint_as_float(id.x));
+			hp[2] = make_float4(__uint_as_float(id.y), __uint_as_float(id.z), __uint_as_float(id.w), 0.0f);
+		}
 	}
 }
 
@@ -1090,6 +1138,18 @@ extern "C" int nh_closest_k(nh_context* ctx, const nh_PointQuery* queries, uint3
 	hipLaunchKernelGGL(k_q_closest_k, dim3(nh_grid_for(count, block, 1u << 20)), dim3(block), block * k * sizeof(nh_QNear), ctx->stream,
 	                   queries, count, k, counts, hits, q->nodes, q->rec, q->keys, q->ctl, q->n, q->nbox);
 	if (ctx->timing) nh_timer_end(ctx);
+	return NH_OK;
+}
+
+// One launch, as nh_closest; no allocation, no wait.
+extern "C" int nh_distance(nh_context* ctx, const nh_DistanceQuery* queries, uint32_t count, nh_PointHit* hits, uint32_t flags) {
+	if (!ctx || !ctx->query || !ctx->query->built) return NH_ERR_INVALID;
+	if (flags != 0u || count >= (1u << 30)) return NH_ERR_INVALID;
+	if (count == 0u) return NH_OK;
+	if (!queries || !hits || (((uintptr_t)queries | (uintptr_t)hits) & 15u)) return NH_ERR_INVALID;    // (records are moved as 16-byte words)
+	NH_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+	nh_QueryState* q = ctx->query;
+	NH_LAUNCH(ctx, "q_distance", k_q_distance, nh_grid_for(count, 256, 1u << 20), 256, queries, count, hits, q->nodes, q->rec, q->keys, q->ctl, q->n, q->nbox);
 	return NH_OK;
 }
 

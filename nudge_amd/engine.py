@@ -43,7 +43,7 @@ EXPORTS = [
     "nh_partition_top_speed", "nh_partition_set_peer_speeds", "nh_partition_refresh_is_quiet", "nh_partition_mark_ghosts", "nh_partition_pack_deltas", "nh_partition_unpack_deltas",
     "nh_partition_pack_momentum", "nh_partition_unpack_momentum", "nh_partition_exchange_iteration", "nh_partition_unpack_ghosts", "nh_partition_pack_step", "nh_partition_unpack_step", "nh_partition_choose_cut", "nh_partition_set_cut",
     "nh_partition_set_transport", "nh_partition_exchange_step", "nh_partition_step", "nh_partition_transport_check", "nh_partition_transport_result", "nh_set_first_ghost_body",
-    "nh_query_build", "nh_query_refit", "nh_query_stats", "nh_raycast", "nh_overlap", "nh_penetration", "nh_spherecast", "nh_raycast_all", "nh_spherecast_all", "nh_boxcast_all", "nh_capsulecast_all", "nh_boxcast", "nh_capsulecast", "nh_closest", "nh_closest_k",
+    "nh_query_build", "nh_query_refit", "nh_query_stats", "nh_raycast", "nh_overlap", "nh_penetration", "nh_spherecast", "nh_raycast_all", "nh_spherecast_all", "nh_boxcast_all", "nh_capsulecast_all", "nh_boxcast", "nh_capsulecast", "nh_closest", "nh_closest_k", "nh_distance",
 ]
 HALO_RECORD_BYTES = 64
 
@@ -161,6 +161,8 @@ PENETRATION_HIT = np.dtype([("normal", "<f4", 3), ("depth", "<f4"), ("body", "<u
 POINT_QUERY = np.dtype([("point", "<f4", 3), ("max_distance", "<f4"), ("ignore_body", "<u4"), ("reserved", "<u4", 3)])
 POINT_HIT = np.dtype([("distance", "<f4"), ("normal", "<f4", 3), ("point", "<f4", 3), ("body", "<u4"), ("collider", "<u4"), ("shape", "<u4"), ("tag", "<u4"),
                       ("reserved", "<u4")])
+DISTANCE_QUERY = np.dtype([("center", "<f4", 3), ("shape", "<u4"), ("rotation", "<f4", 4), ("size", "<f4", 3), ("ignore_body", "<u4"), ("max_distance", "<f4"),
+                           ("reserved", "<u4", 3)])
 NH_OVERLAP_OVERFLOW = 0xFFFFFFFF          # offsets[count] when the total is 2^32 - 1 or more
 
 
@@ -270,6 +272,9 @@ def lib():
         L.nh_capsulecast.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
         L.nh_closest.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
         L.nh_closest_k.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]
+        # (an older build of the library, loaded through NUDGE_HIP_LIBRARY for an A/B, has no nh_distance: World.distance then raises AttributeError)
+        if hasattr(L, "nh_distance"):
+            L.nh_distance.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
         L.nh_overlap.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
         L.nh_penetration.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
         # (an older build of the library, loaded through NUDGE_HIP_LIBRARY for an A/B, has no all-hits casts: World.raycast_all then raises AttributeError)
@@ -898,6 +903,37 @@ class World:
         u = raw.view(torch.int32).reshape(n, k, 12).to(torch.int64) & 0xFFFFFFFF
         out = dict(count=counts.to(torch.int64), distance=f[..., 0], normal=f[..., 1:4], point=f[..., 4:7], body=u[..., 7], collider=u[..., 8],
                    shape=u[..., 9], tag=u[..., 10], raw=raw)
+        if synchronize:
+            torch.cuda.current_stream(self.dev).synchronize()
+        return out
+
+    def distance_records(self, queries, hits=None):
+        """nh_distance on records already laid out as nh_DistanceQuery: `queries` a contiguous device tensor of count x 64 bytes (any dtype).  Returns
+        the count x 48-byte uint8 device tensor of nh_PointHit records (`hits`, or a new one)."""
+        torch = self.torch
+        n = queries.numel() * queries.element_size() // 64
+        if hits is None:
+            hits = torch.empty((n, 48), dtype=torch.uint8, device=self.dev)
+        _check(self.L, self.L.nh_distance(self.ctx, C.c_void_p(queries.data_ptr() if n else 0), n, C.c_void_p(hits.data_ptr() if n else 0), 0),
+               "nh_distance")
+        return hits
+
+    def distance(self, centres, radii=None, half_extents=None, rotations=None, half_heights=None, max_distance=float("inf"), ignore_body=None,
+                 synchronize=False):
+        """How far each of n spheres, oriented boxes or capsules (overlap()'s shape arguments) is from the nearest collider of the last query_build(),
+        within `max_distance` (a number or n values; inf: anywhere), skipping the colliders of `ignore_body`.  Returns closest()'s dict: distance
+        (n; 0 where the shape touches a collider), normal (n, 3; a unit vector from the collider towards the shape, 0 where they touch), point
+        (n, 3; on the collider's surface -- the shape's own nearest point is point + distance * normal), body, collider, shape, tag (n, int64;
+        0xffffffff = none) and `raw`, the nh_PointHit records.  Nothing waits for the device unless `synchronize`."""
+        torch = self.torch
+        q, n = self._overlap_queries("distance", centres, radii, half_extents, rotations, ignore_body, half_heights)
+        queries = torch.zeros((n, 16), dtype=torch.float32, device=self.dev)
+        queries[:, 0:12] = q
+        queries[:, 12] = torch.as_tensor(max_distance, dtype=torch.float32, device=self.dev)
+        raw = self.distance_records(queries)
+        f = raw.view(torch.float32).reshape(n, 12)
+        u = raw.view(torch.int32).reshape(n, 12).to(torch.int64) & 0xFFFFFFFF
+        out = dict(distance=f[:, 0], normal=f[:, 1:4], point=f[:, 4:7], body=u[:, 7], collider=u[:, 8], shape=u[:, 9], tag=u[:, 10], raw=raw)
         if synchronize:
             torch.cuda.current_stream(self.dev).synchronize()
         return out
