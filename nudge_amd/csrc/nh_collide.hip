@@ -2376,7 +2376,7 @@ static int collide_impl(nh_context* ctx, nh_ActiveBodies* active_bodies, nh_Cont
 		}
 	}
 	// a full step.  (nh_step: a still step whose verdict has not been looked at yet must have happened before anything is built on it)
-	if (ctx->still.verdict.pending && nh_still_verdict_now(ctx)) return NH_INTERNAL_STILL_FAILED;
+	if (ctx->still.verdict.pending) { const int v = nh_still_verdict_now(ctx); if (v) return v == 2 ? NH_ERR_HIP : NH_INTERNAL_STILL_FAILED; }
 	ctx->still.pair_ready = false; ctx->still.pair_step = false; ctx->still.early_verdict = false; ctx->still.pair_world_bad = false; ctx->still.pair_world_ok = false; ctx->still.pair_listed = 0u; ctx->still.pair_owned_seq = 0u;          // (another layout: whether every kept pair is some body's own is found out again)
 	// The solver reads the caller's cache arrays and this nh_collide lays the dense contact list out -- whatever still steps kept by slot goes home first
 	{ int rc = nh_still_export_cache(ctx); if (rc) return rc; }

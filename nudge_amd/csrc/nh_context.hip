@@ -167,7 +167,7 @@ extern "C" int nh_set_option(nh_context* ctx, const char* name, int value) {
 	ctx->asleep.streak = 0;
 	if (n == "no_asleep") ctx->asleep.disabled = on;                      // nh_step runs every step of a world that is asleep in full (nh_internal.h: nh_AsleepState)
 	else if (n == "sync_exports_views") ctx->sync_exports_views = on;          // legacy observers: nh_synchronize / nh_read_counts end with nh_export_views(NH_VIEW_ALL) like they did before round 5 (note 9)
-	else if (n == "no_early_counts") ctx->no_early_counts = on;                // a full step's counters by a copy behind its solver, not by the solver's first thread (nh_internal.h: early counters; A/B, tests)
+	else if (n == "no_early_counts") ctx->no_early_counts = on;                // a full step's counters by a copy behind its solver, not by the solver's first thread; nh_step: record and wait for the ring event behind every still solver (nh_internal.h: early counters; A/B, tests)
 	else if (n == "no_listed_lookup") ctx->no_listed_lookup = on;              // the warm-start lookup of a full step is k_cache_lookup even where the general contacts are few and listed (nh_solve.hip: materialize_lookup; A/B, tests)
 	else if (n == "no_sleeper_ahead") ctx->still.no_sleeper_ahead = on;        // a still step in sleepers form always launches its three kernels (nh_internal.h: sleepers ahead; A/B, tests)
 	else if (n == "no_sleeper_skip") ctx->still.no_sleeper_skip = on;          // the sleepers form of a still step does all its work for sleeping bodies too (nh_internal.h; A/B, tests)

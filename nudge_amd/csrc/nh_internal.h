@@ -223,7 +223,7 @@ struct nh_StillStep {
 	// counters it looks at has long landed), and the GPU never waits for the host.  A still step that failed did nothing, nor did the one launched behind it (their
 	// solvers compare st->still_failed_seq with `guard`): nh_step runs both again, the first in full.
 	bool pipelined;                 // inside nh_step
-	struct { bool pending; uint32_t seq, parity; int slot; uint64_t collide_mark; bool self_report; } verdict;      // the still step whose counters the host has not looked at yet (self_report: the solver's first thread left them in the ring slot, its number behind them -- the host may poll for that word instead of waiting for the launch to END: early counters)
+	struct { bool pending; uint32_t seq, parity; int slot; uint64_t collide_mark; bool event; } verdict;      // the still step whose counters the host has not looked at yet (event: ev_ring[slot] was recorded behind its solver and says when they have landed; false -- the step reports itself: the solver's first thread leaves them in the ring slot, its number behind them, and the host spins on that word, nh_still_await_number)
 	nh_DevState* h_ring[2]; hipEvent_t ev_ring[2];      // pinned landing places of the counter copies, and when they have landed
 	bool ring_failed;                                    // ... could not be created: nh_step looks at every verdict inside its step
 	nh_ContactConstraintData* setup_d;      // its nh_setup_contact_constraints has run (without the adjacency kernel the replay then owes)
@@ -349,7 +349,7 @@ struct nh_context {
 	// them in this pinned block -- NH_COUNTER_WORDS words, then the nh_collide number as the word that says "complete" -- and the host, polling that word, has them
 	// while the solver runs: what it launches next queues up behind the solver instead of behind a copy and a wake-up on an idle GPU (26 us of a 550 us step).
 	uint32_t* h_early;             // pinned, NH_COUNTER_WORDS + 16 words; nullptr: could not be had, the host copies
-	bool no_early_counts;          // option "no_early_counts" (A/B, tests): the copy behind the solver, as before
+	bool no_early_counts;          // option "no_early_counts" (A/B, tests): the copy behind the solver, as before; nh_step's still steps: the ring event recorded and waited for
 	bool no_listed_lookup;         // option "no_listed_lookup" (A/B, tests): the warm-start lookup always walks every contact (k_cache_lookup), never the list of general ones
 	uint64_t early_reads, early_fallbacks;      // round trips answered by the solver's first thread / by the copy after all (the stream ran dry without the word)
 	int last_hip_error;
@@ -491,7 +491,8 @@ int nh_still_sync_outputs(nh_context* ctx, uint32_t what = 7u /* NH_VIEW_ALL */)
 int nh_still_export_cache(nh_context* ctx);           // nh_cache.hip
 int nh_still_undo_drops(nh_context* ctx);             // nh_cache.hip
 void nh_stream_void_advance(nh_context* ctx);         // nh_context.hip
-int nh_still_verdict_now(nh_context* ctx);            // nh_step.hip -- nh_step: the pending verdict of the last still step, waited for: 0 = it happened, 1 = it did not
+int nh_still_verdict_now(nh_context* ctx);            // nh_step.hip -- nh_step: the pending verdict of the last still step, waited for: 0 = it happened, 1 = it did not, 2 = HIP error
+int nh_still_await_number(nh_context* ctx);           // nh_step.hip -- the pending step's number in its ring slot, spun on (no event behind a solver that reports itself): 0 there, 1 never came, 2 HIP error
 NH_LOCAL void nh_still_note_movers(nh_context* ctx, const nh_DevState* h, uint32_t seq = 0u);          // nh_step.hip
 int nh_asleep_remember(nh_context* ctx);              // nh_collide.hip (asleep steps: nh_AsleepState)
 int nh_asleep_verify(nh_context* ctx, const nh_BodyData* bodies, const nh_ColliderData* colliders);      // nh_collide.hip

@@ -630,13 +630,14 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MAXC ==
 			stw->active = (nbodies - 1u) - min(stw->still_asleep[sv.parity], nbodies - 1u); stw->sleeping = n_sleeping; stw->culled = n_culled;
 			// nh_step with late verdicts: everything a still step can fail on has been decided before this launch (k_xform<true>, the narrowphase or k_pair_begin) or at its
 			// top (body 0) -- what the lanes find wanting fails the NEXT step -- so the step's counters are final here, and this thread leaves them where the host will look
-			// (pinned memory, visible when the launch has ended: the host waits for the event behind it).  The copy the runtime made instead cost 6 us of stream time per step.
+			// (pinned memory).  The copy the runtime made instead cost 6 us of stream time per step.
 			if (fs.host_counters) {
 				const volatile uint32_t* src = reinterpret_cast<const volatile uint32_t*>(cv.st);
 #pragma unroll
 				for (uint32_t k = 0; k < NH_COUNTER_WORDS; ++k) fs.host_counters[k] = src[k];
-				// (early counters: ... and this step's number behind them, released at system scope -- the host that waits for the LAST verdict of an nh_step call polls for
-				// it and returns while this launch runs: the caller's next call queues up behind it instead of behind a wake-up)
+				// (early counters: ... and this step's number behind them, released at system scope -- the host spins on that number, inside an nh_step call for the verdict
+				// of the step before the one it has just enqueued, at its end for the last one, and never waits for this launch to END.  One lane per word instead of this
+				// thread's 41 stores was built and measured: not faster)
 				__threadfence_system();
 				__hip_atomic_store(fs.host_counters + NH_COUNTER_WORDS, fs.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 			}
@@ -2510,7 +2511,8 @@ static int first_apply(nh_context* ctx, nh_ContactConstraintData* d, const nh_Bo
 			if (ss.pipelined && ss.h_ring[0]) {
 				// nh_step: first the verdict of the still step BEFORE this one (its counters landed long ago) ...
 				if (ss.verdict.pending) {
-					NH_HIP_CHECK(ctx, hipEventSynchronize(ss.ev_ring[ss.verdict.slot]));
+					if (ss.verdict.event) NH_HIP_CHECK(ctx, hipEventSynchronize(ss.ev_ring[ss.verdict.slot]));
+					else { const int w = nh_still_await_number(ctx); if (w) return w == 2 ? NH_ERR_HIP : NH_INTERNAL_STILL_FAILED; }          // (that step reported itself: its number, spun on)
 					const nh_DevState* h = ss.h_ring[ss.verdict.slot];
 					if (h->still_failed_seq >= ss.verdict.seq || h->error) return NH_INTERNAL_STILL_FAILED;       // (nh_step cleans up and runs both steps again)
 					ss.confirmed_seq = ss.verdict.seq;
@@ -2522,9 +2524,11 @@ static int first_apply(nh_context* ctx, nh_ContactConstraintData* d, const nh_Bo
 				// ... then this step's counters on their way, to be looked at by the next step
 				const int slot = (int)(ctx->collide_seq & 1u);
 				if (!self_report) NH_HIP_CHECK(ctx, hipMemcpyAsync(ss.h_ring[slot], ctx->d_state, NH_COUNTER_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-				NH_HIP_CHECK(ctx, hipEventRecord(ss.ev_ring[slot], ctx->stream));
+				// (a step that reports itself -- not in two launches, not under option "no_early_counts" -- needs no event: the host takes its verdict from the number in the slot)
+				const bool ring_event = !self_report || ctx->halo_split.launched || ctx->no_early_counts;
+				if (ring_event) NH_HIP_CHECK(ctx, hipEventRecord(ss.ev_ring[slot], ctx->stream));
+				ss.verdict.event = ring_event;
 				ss.verdict.pending = true; ss.verdict.seq = ctx->collide_seq; ss.verdict.parity = ctx->step_parity; ss.verdict.slot = slot; ss.verdict.collide_mark = ctx->collide_mark;
-				ss.verdict.self_report = self_report && !ctx->halo_split.launched;
 				confirmed = true;          // (until the next step says otherwise)
 			} else if (ss.early_verdict) {
 				// nh_partition_step, a step that started at the solver: everything such a step can fail on is checked by its PROLOGUE (k_pair_begin: the step-wide words,

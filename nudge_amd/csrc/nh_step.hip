@@ -2,6 +2,7 @@
 // (nh_export_views: dense contact list, cache, active list, sleeping pairs).
 #include "nh_internal.h"
 #include <atomic>
+#include <chrono>
 #include <string.h>
 
 // LOCAL speculation (nh_internal.h): every round trip -- a full step's, a still step's verdict -- tells whether somebody left its inflated box in that step; the
@@ -106,24 +107,46 @@ extern "C" int nh_export_views(nh_context* ctx, uint32_t what) {
 // The eight calls, `steps` times.  Besides sparing the caller eight crossings of the ABI per step, the library -- driving the call order itself -- may look at a still
 // step's verdict one step late (nh_internal.h: nh_StillStep::pipelined), so that neither the host nor the GPU ever waits for the other inside the loop; a failed
 // still step and the one launched behind it (both did nothing) are simply run again.  On return every step is confirmed.
+// A still step that reports itself (nh_solve.hip: nh_FusedStep::host_counters) leaves its counters and, behind them, its number in the pinned ring slot as its solver STARTS --
+// everything a still step can fail on was decided by then -- and NO event is recorded behind that solver (nh_StillStep::verdict.event): the host spins on the number,
+// acquires, and reads the counters from the slot.  A launch that never ran writes no number: every 256 spins the host looks at the clock, and once the wait has lasted
+// longer than any healthy step of a small world (2 ms) at the stream as well -- not before: a query puts a packet of its own behind the launch the host has just
+// enqueued (measured: with a query every 256 spins the 5.9 us gap behind the solver is back, profiles/r10_steady_step_ab.log); a step longer than 2 ms pays at most that one.  0 = the number is there; 1 = the stream has drained and one more look did not find it; 2 = the runtime reports an error (ctx->last_hip_error).
+int nh_still_await_number(nh_context* ctx) {
+	nh_StillStep& ss = ctx->still;
+	volatile const uint32_t* const flag = reinterpret_cast<volatile const uint32_t*>(ss.h_ring[ss.verdict.slot]) + NH_COUNTER_WORDS;
+	std::chrono::steady_clock::time_point t0;
+	for (uint32_t spins = 0; ; ++spins) {
+		if (*flag == ss.verdict.seq) break;
+		if ((spins & 255u) == 255u) {
+			const auto now = std::chrono::steady_clock::now();
+			if (spins == 255u) t0 = now;
+			else if (now - t0 > std::chrono::milliseconds(2)) {
+				const hipError_t q = hipStreamQuery(ctx->stream);
+				if (q == hipSuccess) { if (*flag == ss.verdict.seq) break; return 1; }
+				if (q != hipErrorNotReady) { ctx->last_hip_error = (int)q; return 2; }
+			}
+		}
+		__builtin_ia32_pause();
+	}
+	std::atomic_thread_fence(std::memory_order_acquire);
+	ctx->early_reads++;
+	return 0;
+}
+
 int nh_still_verdict_now(nh_context* ctx) {
-	// the pending verdict, waited for: 0 confirmed, 1 failed
+	// the pending verdict, waited for: 0 confirmed, 1 failed, 2 the runtime reports an error (ctx->last_hip_error)
 	nh_StillStep& ss = ctx->still;
 	if (!ss.verdict.pending) return 0;
 	const nh_DevState* h = ss.h_ring[ss.verdict.slot];
-	bool seen = false;
-	if (ss.verdict.self_report && !ctx->no_early_counts && !(ctx->timing && ctx->timing_filter.empty())) {
-		// early counters (nh_internal.h): the step's solver left counters and number in the ring slot as it STARTED -- everything a still step can fail on was decided by
-		// then -- so the call's last verdict does not wait for the launch to end (the event is the fallback: a launch that never ran writes no number)
-		volatile const uint32_t* const flag = reinterpret_cast<volatile const uint32_t*>(h) + NH_COUNTER_WORDS;
-		for (uint32_t spins = 0; ; ++spins) {
-			if (*flag == ss.verdict.seq) { seen = true; break; }
-			if ((spins & 255u) == 255u && hipEventQuery(ss.ev_ring[ss.verdict.slot]) != hipErrorNotReady) break;
-			__builtin_ia32_pause();
-		}
-		if (seen) { std::atomic_thread_fence(std::memory_order_acquire); ctx->early_reads++; }
+	if (ss.verdict.event) {
+		// (a counter copy by the runtime, the halo split or option "no_early_counts": the event behind the solver says the slot is complete)
+		const hipError_t e = hipEventSynchronize(ss.ev_ring[ss.verdict.slot]);
+		if (e != hipSuccess) { ss.verdict.pending = false; ctx->last_hip_error = (int)e; return 2; }
+	} else {
+		const int w = nh_still_await_number(ctx);
+		if (w) { ss.verdict.pending = false; return w; }
 	}
-	if (!seen && hipEventSynchronize(ss.ev_ring[ss.verdict.slot]) != hipSuccess) return 1;
 	ss.verdict.pending = false;
 	if (h->still_failed_seq >= ss.verdict.seq || h->error) return 1;
 	ss.confirmed_seq = ss.verdict.seq;
@@ -192,7 +215,9 @@ extern "C" int nh_step(nh_context* ctx, const nh_StepArgs* a, uint32_t steps) {
 	while (i < steps || ss.verdict.pending) {
 		if (i >= steps) {
 			// the last step's verdict, waited for; a failure sends the loop back one step
-			if (nh_still_verdict_now(ctx) == 0) break;
+			const int v = nh_still_verdict_now(ctx);
+			if (v == 0) break;
+			if (v == 2) { result = NH_ERR_HIP; break; }
 			{ int rc = still_forget_failed(ctx, true, 1u); if (rc) { result = rc; break; } }
 			i -= 1;
 			continue;
@@ -233,6 +258,6 @@ extern "C" int nh_step(nh_context* ctx, const nh_StepArgs* a, uint32_t steps) {
 		++i;
 	}
 	ss.pipelined = false; ss.more_steps = false; ss.ahead_ready = false; ss.ahead_map_ok = false; ss.steps_left = 0u; ss.substep = 0u; ss.own_current = false;
-	if (result && ss.verdict.pending) { hipEventSynchronize(ss.ev_ring[ss.verdict.slot]); ss.verdict.pending = false; }
+	if (result && ss.verdict.pending) { if (ss.verdict.event) hipEventSynchronize(ss.ev_ring[ss.verdict.slot]); else hipStreamSynchronize(ctx->stream); ss.verdict.pending = false; }          // (no event behind a solver that reports itself: the stream)
 	return result;
 }
