@@ -554,6 +554,15 @@ struct nh_StillView { const uint32_t* body_rec; const uint32_t* body_pos; const 
 // transform, AABB, the test against the inflated box, scene bounds, largest idle counter -- with k_xform's own arithmetic (nh_collide.hip: k_xform, k_asleep_check).
 // PAIR (AHEAD only; nh_internal.h: pair ahead): ... and the next step's NARROWPHASE for the body's one kept pair, from what the lane holds in registers and the static
 // partner's transform, box and shape: contacts into the record's raw slots, count into its place in the tag order, a change of the count onto the next step's list.
+// The STILL head's load schedule: two dependent trips to memory in front of the sweeps (marked TRIP 1 and TRIP 2 below), where lazy fetches had made nine.  The empty asm
+// statements are what holds a group together -- the first names the values the verdict and trip 2's addresses need, so the wave waits for them once, and is a compiler
+// barrier for memory, so nothing of the group is left to be fetched at its first use; the second closes trip 2.  No asm statement may stand in FRONT of the loads of the
+// device state: behind one the compiler no longer proves them unclobbered and fetches them with vector loads.  Nothing checks the grouping at build time.  After an edit
+// read it off the ISA (hipcc -S --cuda-device-only with the Makefile's flags; k_solve_one_body<4,true,true,1,true,true,true,false>), along the path of a wave that is not
+// workgroup 0: ONE s_waitcnt lgkmcnt(0) behind the s_loads of the state's words and body 0, with the lane's global_loads (record, position, collider, the list entry)
+// issued in front of it and the body state's five behind it; ONE s_waitcnt vmcnt(5) in front of the first asm; then no vmcnt wait at all until the 13 record-addressed
+// loads and the 12 wave-cooperative ones have been issued (only lgkmcnt waits for the s_first exchange and for kernel arguments); no global_load of the device state
+// anywhere behind the verdict outside workgroup 0's first thread.  profiles/r11_solver_head_ab.log lists the waits of this build and of its parent.
 template<int MAXC, bool FUSED, bool CONTIG = false, int NW = 4, bool STILL = false, bool AHEAD = false, bool PAIR = false, bool PART = false>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MAXC == 4 ? NH_SOLVER_WPE : 1, MAXC == 4 ? NH_SOLVER_WPE : 1))) void k_solve_one_body(uint32_t nbodies, const uint8_t* __restrict__ body_class, const uint32_t* __restrict__ off, const uint32_t* __restrict__ adj,
                                                         const nh_BodyPair* __restrict__ bodies, const nh_BodyProperties* __restrict__ props, nh_BodyMomentum* __restrict__ momentum,
@@ -579,13 +588,46 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MAXC ==
 	}
 	// (the two words of device state -- is body 0 inert, how long is the cache -- are fetched beside the first round of loads, not before it)
 	uint32_t inert_word = (require_inert & 1u) ? cv.st->static_inert : 1u;
+	uint32_t x = blockIdx.x * blockDim.x + threadIdx.x;
+	// STILL, TRIP 1 -- everything the launch alone addresses, asked for at once and before any verdict: the words of the device state the kernel ever reads, body 0, this
+	// thread's entry of the change list (at a fixed index, listed or not), the lane's words (record, tag-order position, collider, idle counter) and the body's state.
+	// Every index is clamped to a capacity, not to a count of this step: a launch that leaves at its top has read nothing it must not.  (The listed bodies of a halo
+	// split's boundary launch know their body only from the list: their lane words follow behind it.)
+	const bool lane_early = STILL && !(PART && fs.part == 1u);
+	uint32_t h_failed = 0u, h_pairs = 0u, h_records = 0u, h_dcount = 0u, h_dover = 0u, h_moved = 0u, h_unowned = 0u;
+	uint32_t h_smin[3] = { 0u, 0u, 0u }, h_smax[3] = { 0u, 0u, 0u };
+	int2 h_delta = make_int2(0, 0);
+	uint32_t l_br = NH_BODY_REC_NONE, l_bpos = 0u, l_idle = 0u, l_col = 0xFFFFFFFFu;
+	float4 l_m0 = make_float4(0, 0, 0, 0), l_m1 = l_m0, l_pr = l_m0, l_t0 = l_m0, l_t1 = l_m0;
+	auto lane_words = [&](uint32_t xi) {          // (xi < nbodies)
+		l_br = sv.body_rec[xi]; l_bpos = sv.body_pos[xi];
+		if (CONTIG && (fs.bits & 6u)) l_idle = fs.idle[xi];          // (bit 2 of fs.bits: sleepers form -- somebody may be asleep; bit 1: the body is advanced here)
+		if (AHEAD) l_col = av.body_col[xi];
+		l_m0 = reinterpret_cast<const float4*>(momentum + xi)[0]; l_m1 = reinterpret_cast<const float4*>(momentum + xi)[1];
+		l_pr = *reinterpret_cast<const float4*>(props + xi);
+		l_t0 = reinterpret_cast<const float4*>(xf + xi)[0]; l_t1 = reinterpret_cast<const float4*>(xf + xi)[1];
+	};
+	float pair_scale0 = 0.0f;
 	if (STILL) {
 		// (every workgroup reads the same words and comes to the same verdict)
+		const nh_DevState* const st0 = cv.st;
 		const nh_BodyMomentum m0 = momentum[0];
 		const nh_BodyProperties p0 = props[0];
+		h_failed = st0->still_failed_seq; h_pairs = st0->pairs; h_records = st0->records;
+		h_dcount = st0->delta_count[sv.parity]; h_dover = st0->delta_overflow[sv.parity];
+		if (PAIR) {
+			h_moved = st0->moved_count; h_unowned = st0->pair_unowned;
+			for (int k = 0; k < 3; ++k) { h_smin[k] = st0->still_smin[sv.parity][k]; h_smax[k] = st0->still_smax[sv.parity][k]; }
+		}
+		h_delta = sv.delta[sv.parity * NH_DELTA_MAX + (threadIdx.x & (NH_DELTA_MAX - 1u))];
+		if (lane_early) lane_words(min(x, nbodies - 1u));
+		// (the group is held together here: the words the verdict and the next trip's addresses need are named -- the wave waits for them once -- and nothing of the group is
+		// left to be fetched where it is first used; the body's state is asked for LAST, so that this wait does not cover it)
+		asm volatile("" :: "s"(h_failed), "s"(h_pairs), "s"(h_records), "s"(h_dcount), "s"(h_dover), "v"(h_delta.x), "v"(h_delta.y), "v"(l_br), "v"(l_bpos), "v"(l_idle), "v"(l_col) : "memory");
+		if (PAIR) asm volatile("" :: "s"(h_moved), "s"(h_unowned), "s"(h_smin[0]), "s"(h_smin[1]), "s"(h_smin[2]), "s"(h_smax[0]), "s"(h_smax[1]), "s"(h_smax[2]));
 		const bool inert = nh_is_inert(m0.velocity, m0.angular_velocity, p0.inertia_inverse, p0.mass_inverse);
 		if (!inert && blockIdx.x == 0 && threadIdx.x == 0) atomicMax(&const_cast<nh_DevState*>(cv.st)->still_failed_seq, fs.seq);
-		if (!inert || cv.st->still_failed_seq >= fs.guard_seq) {
+		if (!inert || h_failed >= fs.guard_seq) {
 			// (the verdict the host is waiting for: see below)
 			if (fs.host_counters && blockIdx.x == 0 && threadIdx.x == 0 && !(PART && fs.part == 1u)) {
 				const volatile uint32_t* src = reinterpret_cast<const volatile uint32_t*>(cv.st);
@@ -597,6 +639,9 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MAXC ==
 			return;
 		}
 		inert_word = 1u;
+		// (PAIR: the Morton scale of THIS step's scene frame, nudge.cpp:3096-3099 -- the yardstick of the role rule far below -- from the frame's words while they are at hand)
+		if (PAIR) pair_scale0 = nh_morton_scale(nh_make3(nh_float_unflip(h_smin[0]), nh_float_unflip(h_smin[1]), nh_float_unflip(h_smin[2])),
+		                                        nh_make3(nh_float_unflip(h_smax[0]), nh_float_unflip(h_smax[1]), nh_float_unflip(h_smax[2])));
 	}
 	__shared__ nh_ob_slot s_slot[NW][64 * M];
 	__shared__ uint32_t s_cid[NW][64 * M];
@@ -611,11 +656,13 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MAXC ==
 	if (STILL) {
 		// The first contact of every record in the dense list is kept from step to step (start_sorted); the records whose count changed this step are listed, and a lane
 		// shifts its record's start by the changes BEFORE it in the tag order.  (More changes than the list holds: the scan has run instead, nothing to shift.)
-		n_delta = cv.st->delta_overflow[sv.parity] ? 0u : min(cv.st->delta_count[sv.parity], NH_DELTA_MAX);
-		for (uint32_t k = threadIdx.x; k < n_delta; k += blockDim.x) s_delta[k] = sv.delta[sv.parity * NH_DELTA_MAX + k];
+		// (the first entry per thread came with trip 1; a list longer than the workgroup -- nothing a steady world sees -- takes a trip of its own for the rest)
+		n_delta = h_dover ? 0u : min(h_dcount, NH_DELTA_MAX);
+		if (threadIdx.x < n_delta) s_delta[threadIdx.x] = h_delta;
+		for (uint32_t k = threadIdx.x + blockDim.x; k < n_delta; k += blockDim.x) s_delta[k] = sv.delta[sv.parity * NH_DELTA_MAX + k];
 		if (blockIdx.x == 0 && threadIdx.x == 0 && !(PART && fs.part == 1u)) {          // (halo split: the interior launch does what a step does once)
 			// the contact count of the step = the total behind the last record: kept like the starts
-			const uint32_t nrec = cv.st->records;
+			const uint32_t nrec = h_records;
 			int shift = 0;
 			for (uint32_t k = 0; k < n_delta; ++k) shift += sv.delta[sv.parity * NH_DELTA_MAX + k].y;
 			const uint32_t total = sv.start_sorted[nrec] + (uint32_t)shift;
@@ -660,7 +707,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MAXC ==
 	nh_CachedContactImpulse* const out_impulses = STILL ? const_cast<nh_CachedContactImpulse*>(cv.cdata) : impulses;
 	const uint32_t rounded = (nbodies + (64u * NW - 1u)) / (64u * NW) * (64u * NW);
 	// block-uniform trip count; the CONTIG launch covers every body with one pass (no loop: nothing is carried in registers across iterations)
-	uint32_t x = blockIdx.x * blockDim.x + threadIdx.x;
 	if (PART && fs.part == 1u) {
 		// (the listed bodies, in whatever order the list was made: a lane is a body wherever it sits; lanes behind the list's end stand on the static world, nobody's)
 		const uint32_t cnt_listed = *fs.xcount;
@@ -680,9 +726,9 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MAXC ==
 		if (CONTIG && !STILL) sp = simple[xc];
 		if (FUSED && !STILL) h = hint[xc];
 		uint32_t br = NH_BODY_REC_NONE, bpos = 0u, idle0 = 0u;
-		if (STILL) { br = sv.body_rec[xc]; bpos = sv.body_pos[xc]; if (CONTIG && (fs.bits & 4u)) idle0 = fs.idle[xc]; }          // (bit 2 of fs.bits: sleepers form -- somebody may be asleep)
+		if (STILL) { if (!lane_early) lane_words(xc); br = l_br; bpos = l_bpos; if (CONTIG && (fs.bits & 4u)) idle0 = l_idle; }
 		uint32_t col = 0xFFFFFFFFu;
-		if (AHEAD) col = av.body_col[xc];
+		if (AHEAD) col = STILL ? l_col : av.body_col[xc];
 		if (!inert_word) return;
 		// (STILL: a body asleep -- only a step in sleepers form gets this far with one -- is nobody's: no gravity, no contacts, no advance, nothing stored; nudge.cpp:3669-3703, 4896-4898)
 		bool mine = STILL ? (x >= 1u && x < nbodies && idle0 != 0xffu) : (x < nbodies && (my_class == cls_a || my_class == cls_b));
@@ -700,11 +746,15 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MAXC ==
 		uint32_t first = 0xFFFFFFFFu;
 		uint32_t still_base = 0, still_rec = 0;
 		bool still_has = false;
-		// STILL: two memory round trips, like the full form -- (1) the body's record and tag-order position (above); (2) EVERYTHING else at once: the record's count,
-		// start and cached count, the feature words of its four slots (this step's and the cached ones), the four contacts and the four cached impulses IN SLOT ORDER
-		// (the wave-cooperative loads below), the body state.  Which slot is solved when, and which cached impulse it starts from, is worked out afterwards in
-		// registers -- the version that first read counts, then features, then sorted, then fetched the contacts in solve order waited for four dependent round trips
+		// STILL, TRIP 2 -- everything the body's record addresses, behind trip 1 (the record, its tag-order position and `pairs` came with it; the body's state is on its way
+		// since): the record's count, start and cached count, the kept pair and the key on file (PAIR), the feature words of its four slots (this step's and the cached
+		// ones), and in the same group the four contacts and the four cached impulses IN SLOT ORDER (the wave-cooperative loads below: where a body's slots are takes the
+		// record and `pairs` only, so the exchange through s_first waits for none of the loads here).  Which slot is solved when, and which cached impulse it starts from,
+		// is worked out afterwards in registers -- the version that first read counts, then features, then sorted, then fetched the contacts in solve order waited for
+		// four dependent round trips.  How to re-read the grouping off the ISA: the note above the kernel.
 		uint32_t st_start = 0, st_cnt = 0, st_oc = 0;
+		uint2 st_kp = make_uint2(0u, 0u);
+		uint64_t st_pk = 0ull;
 		uint32_t nf[M], of[M];
 		uint32_t sl[M], jm[M];          // solve order -> slot of the contact, slot of the cached impulse it starts from (0xFFFFFFFF: none)
 #pragma unroll
@@ -712,18 +762,17 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MAXC ==
 		if (STILL) {
 			still_has = br != NH_BODY_REC_NONE;
 			still_rec = still_has ? (br & ~NH_BODY_REC_IS_A) : 0u;
-			const uint32_t n_bb = min(cv.st->pairs, sv.pair_cap);
+			const uint32_t n_bb = min(h_pairs, sv.pair_cap);
 			still_base = still_rec < n_bb ? 4u * still_rec : 4u * n_bb + (still_rec - n_bb);       // (a record of a pair with a sphere owns ONE slot, behind the box-box records' four each)
 			const uint32_t bp = still_has ? bpos : 0u;
 			st_cnt = sv.cnt_sorted[bp]; st_start = sv.start_sorted[bp]; st_oc = sv.sc_count[still_rec];
+			s_first[wave][lane] = still_has ? still_base : 0xFFFFFFFFu;          // (where the wave-cooperative loads find this body's four slots)
 			if (PAIR) {
-				const uint2 kp = still_rec < n_bb ? av.kept[still_rec] : av.kept[av.kept_cap - 1u - (still_rec - n_bb)];
-				const uint64_t pk = av.rec_key[still_rec];
-				s_pk[wave][0][lane] = kp.x; s_pk[wave][1][lane] = kp.y; s_pk[wave][2][lane] = (uint32_t)pk; s_pk[wave][3][lane] = (uint32_t)(pk >> 32);
+				st_kp = still_rec < n_bb ? av.kept[still_rec] : av.kept[av.kept_cap - 1u - (still_rec - n_bb)];
+				st_pk = av.rec_key[still_rec];          // (into s_pk behind the issue of the wave's loads below: an LDS store of a loaded value is a wait for it)
 			}
 #pragma unroll
 			for (int k = 0; k < M; ++k) { nf[k] = sv.raw_feature[still_base + k]; of[k] = sv.sc_feat[still_base + k]; }
-			s_first[wave][lane] = still_has ? still_base : 0xFFFFFFFFu;          // (where the wave-cooperative loads find this body's four slots)
 		} else {
 		if (CONTIG) cnt = sp.y & 15u;
 		else if (mine) { b = off[x]; cnt = off[x + 1] - b; }
@@ -774,11 +823,20 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MAXC ==
 		// body state: 16-byte loads (the records are 16 / 32 bytes and aligned, include/nudge_hip.h)
 		float4 m0 = make_float4(0, 0, 0, 0), m1 = m0, pr = m0, t0 = m0, t1 = make_float4(0, 0, 0, 1);
 		uint32_t idle_early = 0;
+		if (STILL) {
+			// (the group ends here: nothing of it is fetched behind this point; then the kept pair and the key on file to where the lane finds them before the sweeps)
+			asm volatile("" ::: "memory");
+			if (PAIR) { s_pk[wave][0][lane] = st_kp.x; s_pk[wave][1][lane] = st_kp.y; s_pk[wave][2][lane] = (uint32_t)st_pk; s_pk[wave][3][lane] = (uint32_t)(st_pk >> 32); }
+		}
 		if (mine) {
+			if (STILL) {          // (asked for with trip 1, at the clamped index -- a lane that is somebody's stands on its own body)
+				m0 = l_m0; m1 = l_m1; pr = l_pr; t0 = l_t0; t1 = l_t1;
+			} else {
 			m0 = reinterpret_cast<const float4*>(momentum + x)[0]; m1 = reinterpret_cast<const float4*>(momentum + x)[1];
 			pr = *reinterpret_cast<const float4*>(props + x);
 			t0 = reinterpret_cast<const float4*>(xf + x)[0]; t1 = reinterpret_cast<const float4*>(xf + x)[1];
-			if (CONTIG && (fs.bits & 2u)) idle_early = (STILL && (fs.bits & 4u)) ? idle0 : fs.idle[x];
+			}
+			if (CONTIG && (fs.bits & 2u)) idle_early = STILL ? l_idle : fs.idle[x];
 			if (CONTIG && (fs.bits & 1u)) {          // NH_FLAG_FUSED_STEP: gravity / damping (k_gravity) on the way in
 				float vel[3] = { m0.x, m0.y, m0.z }, ang[3] = { m1.x, m1.y, m1.z };
 				nh_gravity_damping(vel, ang, fs.gx_dt, fs.gy_dt, fs.gz_dt, fs.damping);
@@ -913,7 +971,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MAXC ==
 			const uint32_t ca = kx & index_mask, cb = ky & index_mask;
 			pp_partner = ca == ah_col ? cb : ca;
 			pp_bits = 1u | ((ca != ah_col && cb != ah_col) ? 4u : 0u);
-			if (av.gen && cv.st->moved_count != 0u && !((uint32_t)(av.gen[ca] & 0x7Fu) == (kx >> NH_GEN_SHIFT) && (uint32_t)(av.gen[cb] & 0x7Fu) == (ky >> NH_GEN_SHIFT))) pp_bits |= 2u;
+			if (av.gen && h_moved != 0u && !((uint32_t)(av.gen[ca] & 0x7Fu) == (kx >> NH_GEN_SHIFT) && (uint32_t)(av.gen[cb] & 0x7Fu) == (ky >> NH_GEN_SHIFT))) pp_bits |= 2u;
 			pp_x = av.xf[pp_partner]; pp_min = av.aabb_min[pp_partner]; pp_max = av.aabb_max[pp_partner];
 			if (pp_partner < av.nbox) pp_shape = *reinterpret_cast<const float4*>(av.box_data + pp_partner);
 			else pp_shape.x = av.sph_data[pp_partner - av.nbox].radius;
@@ -1013,13 +1071,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MAXC ==
 			__builtin_amdgcn_wave_barrier();          // (every lane of the wave has read where the results went)
 #pragma unroll
 			for (int k = 0; k < M; ++k) scid[lane * M + k] = 0xFFFFFFFFu;          // (where the next step's contacts go: nowhere, unless the lane says so below)
-			// the Morton scale of THIS step's scene frame (nudge.cpp:3096-3099): the yardstick of the role rule below
-			const nh_DevState* const sp = cv.st;
-			const nh_f3 smin = nh_make3(nh_float_unflip(sp->still_smin[sv.parity][0]), nh_float_unflip(sp->still_smin[sv.parity][1]), nh_float_unflip(sp->still_smin[sv.parity][2]));
-			const nh_f3 smax = nh_make3(nh_float_unflip(sp->still_smax[sv.parity][0]), nh_float_unflip(sp->still_smax[sv.parity][1]), nh_float_unflip(sp->still_smax[sv.parity][2]));
-			pair_scale = nh_morton_scale(smin, smax);
+			// the Morton scale of THIS step's scene frame: the yardstick of the role rule below (worked out at the kernel's head, from words that came with trip 1)
+			pair_scale = pair_scale0;
 			// more kept pairs that are nobody's than their list holds (k_pair_list): somebody would go unevaluated -- the next step is not this form's
-			if (sp->pair_unowned > av.unowned_cap) nfail = true;
+			if (h_unowned > av.unowned_cap) nfail = true;
 		}
 		if (advance_here) {
 			float pos[3] = { a0.x, a0.y, a0.z }, rot[4] = { a1.x, a1.y, a1.z, a1.w };
