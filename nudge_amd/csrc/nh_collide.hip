@@ -9,6 +9,7 @@
 // How it is computed is GPU-first: the reference's O(C^2/1024) grouped all-pairs sweep is replaced by a
 // uniform grid over "small" colliders (cell = power of two >= their largest extent) plus a brute-force pass for
 // the few large ones (ground slabs); union-find runs lock-free with atomicCAS hooking.
+// Sections 1-10 are the kernels in the order a full step launches them, 11 the entry points, 12 the host side of one call.  (nh_append_contacts: nh_append.hip)
 #include "nh_internal.h"
 #include "nh_narrowphase.h"
 #include <type_traits>
@@ -31,7 +32,7 @@
 // (NH_GEN_SHIFT / NH_GEN_INDEX -- kept pairs carry the generation stamps of their two colliders above the 24-bit collider index: nh_internal.h)
 __device__ __forceinline__ float nh_kept_margin(float cell_inv) { return cell_inv > 0.0f ? 0.03125f / cell_inv : 0.05f; }
 
-// STILL (nh_collide, "9. still steps"): the step was launched as one in which nothing changes structurally.  The kernel then only CHECKS -- a collider
+// STILL (nh_collide, "11. still steps"): the step was launched as one in which nothing changes structurally.  The kernel then only CHECKS -- a collider
 // outside its inflated box, a body asleep: the step fails (st->still_fail) and is replayed in full -- and gathers nothing a rebuild would need; it also does
 // what k_collide_begin does for a full step as far as a still step needs it (largest idle counter; next step's flags and bounds cleared).
 template<bool STILL>
@@ -735,7 +736,7 @@ __global__ __launch_bounds__(LP_THREADS) void k_large_pairs(nh_DevState* __restr
 	flush_pairs_block(st, kept, kept_cap, ps, DIRECT ? &st->pairs : &st->fat_count, DIRECT ? &st->pairs_sph : &st->fat_count_sph);
 }
 
-// ---- 7. re-insertion: the kept list survives a few colliders leaving their boxes ------------------------------------------------------------
+// ---- 6. re-insertion: the kept list survives a few colliders leaving their boxes ------------------------------------------------------------
 // A collider that has left its inflated box used to cost everybody the rebuild (regroup 1 M colliders, search, 117 us) -- one rolling ball in a world at
 // rest, every step.  Now k_xform gives a SMALL leaver a new box and the next GENERATION stamp on the spot, and this kernel finds the pairs of the new box:
 //   * a kept pair carries the stamps of its two colliders (7 bits each, above the 24-bit indices); k_kept_filter skips pairs whose stamps are not the
@@ -873,7 +874,7 @@ __global__ __launch_bounds__(256) void k_reinsert(nh_DevState* __restrict__ st, 
 	flush_pairs_block(st, kept, kept_cap, ps, &st->fat_count, &st->fat_count_sph);
 }
 
-// ---- 6. kept pairs -> this step's pairs ------------------------------------------------------------------------------------------------
+// ---- 7. kept pairs -> this step's pairs ------------------------------------------------------------------------------------------------
 // Temporal coherence.  The grid search above runs on AABBs inflated by 1/32 of a cell and its result is KEPT.  As long as every collider's
 // AABB lies inside the inflated box it had then (checked by k_xform every step; a moved, resized or re-parented collider simply leaves its
 // box), two AABBs that overlap now had overlapping inflated boxes then: the kept list is a superset of this step's pairs, and this one pass
@@ -948,14 +949,14 @@ __global__ __launch_bounds__(256) void k_kept_filter(nh_DevState* __restrict__ s
 	if (threadIdx.x == 0 && s_hits) atomicAdd(&st->fat_hits, s_hits);
 }
 
-// ---- 6. narrowphase -----------------------------------------------------------------------------------------
+// ---- 8. narrowphase -----------------------------------------------------------------------------------------
 // raw contacts are appended in arbitrary order; one record per pair that produced contacts.
 // record i belongs to pair i: its first 4 contacts sit at raw[4*i .. 4*i+3], further ones in the overflow area
 // (struct nh_Record, NH_REC_SLEEPING: nh_internal.h -- the records are library-owned and outlive the step)
 
 // SPH = false: the box-box pairs (front of `pairs`, records 0 .. n_bb-1); SPH = true: the pairs with a sphere (back of `pairs`, records
 // n_bb .. n_bb+n_sph-1).  Record r owns the raw contact slots 4r .. 4r+3 either way (a sphere pair uses the first one).
-// STILL (nh_collide, "9. still steps"): the pairs are taken straight from the KEPT list (what k_kept_filter does in place: exact AABB test, bodies,
+// STILL (nh_collide, "11. still steps"): the pairs are taken straight from the KEPT list (what k_kept_filter does in place: exact AABB test, bodies,
 // stamps, roles by Morton order -- a kept pair's position is its record's) and the contacts go to the record's own raw slots like in a full step: a pair that
 // gains or loses a contact moves nobody else's data.  What a still step RELIES on is checked -- the record's key is what it was (tag order unchanged), at most
 // four contacts, a pair with contacts joins a dynamic body to the static world and is the one pair that body's solver lane knows (body_rec) -- and raises
@@ -1669,12 +1670,8 @@ static int asleep_snapshot(nh_context* ctx) {
 	as.snap_C = 0;
 	if (!C || !as.last_aabb_min) return 1;
 	if (as.capacity < C) {
-		void** bufs[] = { (void**)&as.aabb_min, (void**)&as.aabb_max, (void**)&as.tags };
-		for (void** b : bufs) { if (*b) NH_HIP_CHECK(ctx, hipFree(*b)); *b = nullptr; }
 		as.capacity = 0;
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&as.aabb_min, sizeof(float4) * (size_t)C));
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&as.aabb_max, sizeof(float4) * (size_t)C));
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&as.tags, sizeof(uint32_t) * (size_t)C));
+		{ int rc = nh_device_buffers(ctx, { { &as.aabb_min, sizeof(float4) * (size_t)C }, { &as.aabb_max, sizeof(float4) * (size_t)C }, { &as.tags, sizeof(uint32_t) * (size_t)C } }); if (rc) return rc; }
 		as.capacity = C;
 	}
 	NH_HIP_CHECK(ctx, hipMemcpyAsync(as.aabb_min, as.last_aabb_min, sizeof(float4) * (size_t)C, hipMemcpyDeviceToDevice, ctx->stream));
@@ -1684,7 +1681,7 @@ static int asleep_snapshot(nh_context* ctx) {
 	return 0;
 }
 
-// ---- 7. islands (lock-free union-find), active bodies, sleeping -------------------------------------------
+// ---- 9. islands (lock-free union-find), active bodies, sleeping -------------------------------------------
 // find with path halving: every visited node is re-pointed at its grandparent (an ancestor stays an ancestor whatever other
 // lanes do, and parent[x] <= x is preserved), so the long chains of one big island (ball pit) collapse as they are walked
 __device__ __forceinline__ uint32_t uf_find(uint32_t* parent, uint32_t x) {
@@ -1789,7 +1786,7 @@ __global__ __launch_bounds__(256) void k_filter_records(nh_DevState* __restrict_
 	}
 }
 
-// ---- 8. tag-ordered output ------------------------------------------------------------------------------------
+// ---- 10. tag-ordered output -----------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_sorted_counts(nh_DevState* __restrict__ st, const uint32_t* __restrict__ rec_idx, const nh_Record* __restrict__ rec,
                                                        uint32_t* __restrict__ counts, uint32_t* __restrict__ sleep_flags, uint32_t order_kept, uint32_t* __restrict__ lay_rank) {
 	uint32_t n = st->records;
@@ -1975,7 +1972,7 @@ __global__ __launch_bounds__(256) void k_collide_begin(nh_DevState* st, uint32_t
 }
 
 // =================================================================================================================
-// ---- 9. still steps (nh_internal.h: nh_StillStep) --------------------------------------------------------------------------------------------------------
+// ---- 11. still steps (nh_internal.h: nh_StillStep) -------------------------------------------------------------------------------------------------------
 static bool same_bodies(const nh_BodyData& a, const nh_BodyData& b) {
 	return a.transforms == b.transforms && a.properties == b.properties && a.momentum == b.momentum && a.idle_counters == b.idle_counters && a.count == b.count;
 }
@@ -2039,413 +2036,357 @@ int nh_still_view_contacts(nh_context* ctx) {
 	return NH_OK;
 }
 
-static int collide_impl(nh_context* ctx, nh_ActiveBodies* active_bodies, nh_ContactData* contacts, const nh_BodyData* bodies, const nh_ColliderData* colliders,
-                        const nh_BodyConnections* body_connections, nh_Arena temporary, bool want_still) {
-	ctx->adv.done = false;
-	ctx->step_parity ^= 1u;
-	ctx->collide_seq++;
-	ctx->collide_mark = ctx->advance_count;
-	// can anybody be asleep?  (counters rise by at most one per nh_advance since the nh_collide that measured them)
-	const bool no_islands = ctx->idle_bound >= 0 && (uint64_t)ctx->idle_bound + (ctx->advance_count - ctx->idle_bound_mark) < 0xffu;
-	ctx->islands_skipped = no_islands;
-	ctx->idle_unknown = false;                   // this call looks at the counters as they are now (k_collide_begin): its maximum may be adopted again
-	nh_DevState* st = ctx->d_state;
-	const uint32_t nbox = colliders->boxes.count, nsph = colliders->spheres.count;
-	const uint32_t C = nbox + nsph;
-	const uint32_t B = bodies->count;
-	const uint32_t cap = contacts->capacity;
-	ctx->body_count = B;
+// ---- 12. nh_collide on the host: one call as a sequence of stages (collide_impl, at the end, is the list of them) ------------------------------------------
+// what a call is given, and what follows from it before anything is decided
+struct CollideCall {
+	nh_ActiveBodies* active_bodies; nh_ContactData* contacts; const nh_BodyData* bodies; const nh_ColliderData* colliders; const nh_BodyConnections* body_connections;
+	uint32_t nbox, nsph, C, B, cap;          // boxes, spheres, colliders, bodies; the caller's contact capacity
+	bool no_islands;                         // nobody can be asleep (the host's sleep prediction): no island kernel is launched
+};
 
+// the caller's arena carved into this call's arrays, and the sizes they follow from
+struct CollideScratch {
+	nh_xform* xf; float4* aabb_min; float4* aabb_max; uint32_t* ctag;
+	uint32_t* keys_a; uint32_t* keys_b; uint32_t* vals_a; uint32_t* sort_scratch; uint32_t* scan_tmp; uint32_t* cscan_sums;
+	uint2* pairs; uint64_t* rec_key_b; uint32_t* rec_idx_a; uint32_t* rec_idx_b; uint2* sort_place; uint32_t* sleep_flags;
+	uint32_t* parent; uint32_t* set_active; uint32_t* root_of; uint32_t* flags; uint32_t* coarse_parent; uint32_t* coarse_active; uint32_t* coarse_root; uint32_t* block_top;
+	uint32_t pair_cap, max_cells, begin_grid;
+};
+
+// what the reserve stages and the broadphase mode leave for the step: a `drop_*` tells the device that what it kept describes other buffers or another world
+struct CollideMode { bool bp_direct, incremental, drop_kept, drop_sort_order; };
+
+static int carve_scratch(nh_context* ctx, const CollideCall& c, nh_Arena temporary, CollideScratch* out) {
+	CollideScratch& s = *out;
+	const uint32_t C = c.C, B = c.B;
 	int err = NH_OK;
 	nh_Arena* A = &temporary;
-	nh_xform* xf = nh_arena_array<nh_xform>(A, C, &err);
-	float4* aabb_min = nh_arena_array<float4>(A, C, &err);
-	float4* aabb_max = nh_arena_array<float4>(A, C, &err);
-	uint32_t* ctag = nh_arena_array<uint32_t>(A, C, &err);
-	ctx->asleep.last_aabb_min = aabb_min; ctx->asleep.last_aabb_max = aabb_max; ctx->asleep.last_ctag = ctag; ctx->asleep.last_C = C;          // (nh_asleep_remember)
-	uint32_t* keys_a = nh_arena_array<uint32_t>(A, C, &err);
-	uint32_t* keys_b = nh_arena_array<uint32_t>(A, C, &err);
-	uint32_t* vals_a = nh_arena_array<uint32_t>(A, C, &err);
+	s.xf = nh_arena_array<nh_xform>(A, C, &err);
+	s.aabb_min = nh_arena_array<float4>(A, C, &err); s.aabb_max = nh_arena_array<float4>(A, C, &err);
+	s.ctag = nh_arena_array<uint32_t>(A, C, &err);
+	ctx->asleep.last_aabb_min = s.aabb_min; ctx->asleep.last_aabb_max = s.aabb_max; ctx->asleep.last_ctag = s.ctag; ctx->asleep.last_C = C;          // (nh_asleep_remember)
+	s.keys_a = nh_arena_array<uint32_t>(A, C, &err); s.keys_b = nh_arena_array<uint32_t>(A, C, &err); s.vals_a = nh_arena_array<uint32_t>(A, C, &err);
 	// broadphase pairs (each owns 4 raw contact slots, further contacts overflow): nh_set_pair_capacity, else half the contact capacity
-	const uint32_t pair_cap = ctx->pair_capacity ? ctx->pair_capacity : cap / 2 + 1024;
-	uint32_t* sort_scratch = nh_arena_array<uint32_t>(A, nh_sort_scratch_words(C > pair_cap ? C : pair_cap), &err);      // (the one-kernel radix passes of the tag sort: nh_util.hip)
-	uint32_t* scan_tmp = nh_arena_array<uint32_t>(A, 2 * NH_SORT_GRID + 64, &err);
+	s.pair_cap = ctx->pair_capacity ? ctx->pair_capacity : c.cap / 2 + 1024;
+	s.sort_scratch = nh_arena_array<uint32_t>(A, nh_sort_scratch_words(C > s.pair_cap ? C : s.pair_cap), &err);      // (the one-kernel radix passes of the tag sort: nh_util.hip)
+	s.scan_tmp = nh_arena_array<uint32_t>(A, 2 * NH_SORT_GRID + 64, &err);
 	// grid table: a power of two >= 4 cells per collider, 2^16 .. 2^24 entries (flat scenes populate one layer of a grid that is three cells high:
 	// with fewer entries the cell has to double -- four times the candidates per collider; measured at 2 M mixed bodies: pair search 153 -> 80 us)
 	uint64_t want = 1; while (want < 4ull * C) want <<= 1;
 	if (want < (1u << 16)) want = 1u << 16;
 	if (want > (1u << 24)) want = 1u << 24;
-	const uint32_t max_cells = (uint32_t)want;
-	int cell_bits = 0; while ((1ull << cell_bits) < want) ++cell_bits;
-	uint32_t* cscan_sums = nh_arena_array<uint32_t>(A, max_cells / CS_TILE + 8, &err);
-	const uint32_t overflow_cap = cap;
-	uint2* pairs = nh_arena_array<uint2>(A, pair_cap, &err);
-	uint64_t* rec_key_b = nh_arena_array<uint64_t>(A, pair_cap, &err);
-	uint32_t* rec_idx_a = nh_arena_array<uint32_t>(A, pair_cap, &err);
-	uint32_t* rec_idx_b = nh_arena_array<uint32_t>(A, pair_cap, &err);
-	uint2* sort_place = nh_arena_array<uint2>(A, pair_cap, &err);
-	uint32_t* sleep_flags = nh_arena_array<uint32_t>(A, pair_cap + 1, &err);
-	uint32_t* parent = nh_arena_array<uint32_t>(A, B, &err);
-	uint32_t* set_active = nh_arena_array<uint32_t>(A, B, &err);
-	uint32_t* root_of = nh_arena_array<uint32_t>(A, B, &err);
-	uint32_t* flags = nh_arena_array<uint32_t>(A, B + 1, &err);
-	uint32_t* coarse_parent = nh_arena_array<uint32_t>(A, B, &err);
-	uint32_t* coarse_active = nh_arena_array<uint32_t>(A, B, &err);
-	uint32_t* coarse_root = nh_arena_array<uint32_t>(A, B, &err);
-	const uint32_t begin_grid = nh_grid_for(B, 256, 2048);
-	uint32_t* block_top = nh_arena_array<uint32_t>(A, begin_grid, &err);
-	if (err) return err;
+	s.max_cells = (uint32_t)want;
+	s.cscan_sums = nh_arena_array<uint32_t>(A, s.max_cells / CS_TILE + 8, &err);
+	s.pairs = nh_arena_array<uint2>(A, s.pair_cap, &err);
+	s.rec_key_b = nh_arena_array<uint64_t>(A, s.pair_cap, &err);
+	s.rec_idx_a = nh_arena_array<uint32_t>(A, s.pair_cap, &err); s.rec_idx_b = nh_arena_array<uint32_t>(A, s.pair_cap, &err);
+	s.sort_place = nh_arena_array<uint2>(A, s.pair_cap, &err);
+	s.sleep_flags = nh_arena_array<uint32_t>(A, s.pair_cap + 1, &err);
+	s.parent = nh_arena_array<uint32_t>(A, B, &err); s.set_active = nh_arena_array<uint32_t>(A, B, &err); s.root_of = nh_arena_array<uint32_t>(A, B, &err);
+	s.flags = nh_arena_array<uint32_t>(A, B + 1, &err);
+	s.coarse_parent = nh_arena_array<uint32_t>(A, B, &err); s.coarse_active = nh_arena_array<uint32_t>(A, B, &err); s.coarse_root = nh_arena_array<uint32_t>(A, B, &err);
+	s.begin_grid = nh_grid_for(B, 256, 2048);
+	s.block_top = nh_arena_array<uint32_t>(A, s.begin_grid, &err);
+	return err;
+}
 
-	hipStream_t s = ctx->stream;
-	bool drop_sort_order = ctx->env_no_sort_reuse;
-	if (ctx->deg_capacity < NH_DEG_WORDS(B)) {
-		// library-owned (layout: NH_DEG_STRIDE in nh_internal.h): per body the contact degree, the pair info (collider pairs it is in | pairs with a
-		// dynamic partner << 16) and the first contact of its last pair -- written while the contacts are laid out, consumed by setup
-		if (ctx->deg) NH_HIP_CHECK(ctx, hipFree(ctx->deg));
-		ctx->deg = nullptr; ctx->deg_capacity = 0;
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->deg, sizeof(uint32_t) * NH_DEG_WORDS(B)));
-		ctx->deg_capacity = (uint32_t)NH_DEG_WORDS(B);
-	}
+// ---- the library's own buffers: one reserve stage per family.  Each tests its capacity, zeroes it, replaces the buffers (nh_device_buffers: a failed call is
+// made again, whole, by the next step), sets the new capacity -- and sets *fresh when what the old buffers held is gone.
+// (a single buffer that only grows: ctx->deg, and what still steps keep per body)
+template<class T>
+static int reserve_one(nh_context* ctx, T** buffer, uint32_t* capacity, uint32_t want, size_t bytes) {
+	if (*capacity >= want) return NH_OK;
+	*capacity = 0;
+	{ int rc = nh_device_buffers(ctx, { { buffer, bytes } }); if (rc) return rc; }
+	*capacity = want;
+	return NH_OK;
+}
 
-	if (ctx->sort_capacity != pair_cap) {
-		// library-owned: splitters of the seeded tag sort (they persist from one nh_collide to the next) + its bucket counters
-		if (ctx->sort_splitters) NH_HIP_CHECK(ctx, hipFree(ctx->sort_splitters));
-		if (ctx->sort_counts) NH_HIP_CHECK(ctx, hipFree(ctx->sort_counts));
-		if (ctx->sort_starts) NH_HIP_CHECK(ctx, hipFree(ctx->sort_starts));
-		if (ctx->sort_keys_by_position) NH_HIP_CHECK(ctx, hipFree(ctx->sort_keys_by_position));
-		if (ctx->sort_sorted_keys) NH_HIP_CHECK(ctx, hipFree(ctx->sort_sorted_keys));
-		if (ctx->sort_sorted_idx) NH_HIP_CHECK(ctx, hipFree(ctx->sort_sorted_idx));
-		ctx->sort_keys_by_position = nullptr; ctx->sort_sorted_keys = nullptr; ctx->sort_sorted_idx = nullptr;
-		ctx->sort_splitters = nullptr; ctx->sort_counts = nullptr; ctx->sort_starts = nullptr; ctx->sort_capacity = 0; ctx->sort_seeded = false;
-		const size_t nbk = (size_t)nh_bucket_sort_max_buckets(ctx, pair_cap) + 1u;
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->sort_splitters, sizeof(uint64_t) * nbk));
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->sort_counts, sizeof(uint32_t) * nbk));
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->sort_starts, sizeof(uint32_t) * nbk));
-		NH_HIP_CHECK(ctx, hipMemsetAsync(ctx->sort_counts, 0, sizeof(uint32_t) * nbk, s));
-		// sort re-use: the record keys by record position (k_narrowphase compares and rewrites them every step) and the tag order of the last sort
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->sort_keys_by_position, sizeof(uint64_t) * (size_t)pair_cap));
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->sort_sorted_keys, sizeof(uint64_t) * (size_t)pair_cap));
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->sort_sorted_idx, sizeof(uint32_t) * (size_t)pair_cap));
-		NH_HIP_CHECK(ctx, hipMemsetAsync(ctx->sort_keys_by_position, 0, sizeof(uint64_t) * (size_t)pair_cap, s));
-		drop_sort_order = true;
-		ctx->sort_capacity = pair_cap;
+// splitters of the seeded tag sort (they persist from one nh_collide to the next) + its bucket counters; and for sort re-use the record keys by record
+// position (k_narrowphase compares and rewrites them every step) and the tag order of the last sort
+static int reserve_sort(nh_context* ctx, uint32_t pair_cap, bool* fresh) {
+	if (ctx->sort_capacity == pair_cap) return NH_OK;
+	ctx->sort_capacity = 0; ctx->sort_seeded = false;
+	const size_t nbk = (size_t)nh_bucket_sort_max_buckets(ctx, pair_cap) + 1u;
+	{ int rc = nh_device_buffers(ctx, { { &ctx->sort_splitters, sizeof(uint64_t) * nbk }, { &ctx->sort_counts, sizeof(uint32_t) * nbk, true }, { &ctx->sort_starts, sizeof(uint32_t) * nbk },
+	                                    { &ctx->sort_keys_by_position, sizeof(uint64_t) * (size_t)pair_cap, true }, { &ctx->sort_sorted_keys, sizeof(uint64_t) * (size_t)pair_cap },
+	                                    { &ctx->sort_sorted_idx, sizeof(uint32_t) * (size_t)pair_cap } }); if (rc) return rc; }
+	ctx->sort_capacity = pair_cap; *fresh = true;
+	return NH_OK;
+}
+
+// Kept pair list or direct search?  Keeping pairs pays while the list outlives a few steps.  In a world where somebody leaves its box every step
+// (millions of bodies of which a few always roll) every step rebuilds and the filter pass only adds to it: after eight rebuilds in a row (the count
+// rides back with every step's round trip) the next 64 steps search the grid with the exact boxes and write the pairs directly, then the list gets
+// another chance.
+static bool broadphase_direct(nh_context* ctx) {
+	const uint32_t seen = ctx->h_state->fat_rebuilds;
+	if (ctx->bp_direct_left > 0) { if (--ctx->bp_direct_left == 0) ctx->bp_rebuild_streak = 0; }
+	else {
+		ctx->bp_rebuild_streak = seen != ctx->bp_seen_rebuilds ? ctx->bp_rebuild_streak + 1u : 0u;
+		if (ctx->bp_rebuild_streak >= 8u) ctx->bp_direct_left = 64;
 	}
-	// Kept pair list or direct search?  Keeping pairs pays while the list outlives a few steps.  In a world where somebody leaves its box every step
-	// (millions of bodies of which a few always roll) every step rebuilds and the filter pass only adds to it: after eight rebuilds in a row (the count
-	// rides back with every step's round trip) the next 64 steps search the grid with the exact boxes and write the pairs directly, then the list gets
-	// another chance.
-	{
-		const uint32_t seen = ctx->h_state->fat_rebuilds;
-		if (ctx->bp_direct_left > 0) { if (--ctx->bp_direct_left == 0) ctx->bp_rebuild_streak = 0; }
-		else {
-			ctx->bp_rebuild_streak = seen != ctx->bp_seen_rebuilds ? ctx->bp_rebuild_streak + 1u : 0u;
-			if (ctx->bp_rebuild_streak >= 8u) ctx->bp_direct_left = 64;
-		}
-		ctx->bp_seen_rebuilds = seen;
-	}
-	const bool bp_direct = ctx->env_no_fat || ctx->bp_direct_left > 0;
-	// library-owned: the kept pair list of the broadphase and the two buffers of inflated boxes (they persist from one nh_collide to the next)
-	bool drop_kept = ctx->fat_nbox != nbox || ctx->fat_nsph != nsph;
+	ctx->bp_seen_rebuilds = seen;
+	return ctx->env_no_fat || ctx->bp_direct_left > 0;
+}
+
+// the kept pair list of the broadphase and the two buffers of inflated boxes (they persist from one nh_collide to the next); the grid of the last rebuild
+static int reserve_kept(nh_context* ctx, const CollideCall& c, const CollideScratch& s, bool* fresh) {
+	const uint32_t C = c.C, pair_cap = s.pair_cap;
+	if (ctx->fat_nbox != c.nbox || ctx->fat_nsph != c.nsph) *fresh = true;
 	// (the kept list holds pairs of INFLATED boxes: more than overlap exactly -- twice the pair capacity, at least 4096)
 	const uint32_t want_kept = pair_cap > 0x7fffffffu / 2u ? 0xfffffffeu : (2u * pair_cap > 4096u ? 2u * pair_cap : 4096u);
 	if (ctx->fat_pair_capacity != want_kept) {
-		if (ctx->fat_pairs) NH_HIP_CHECK(ctx, hipFree(ctx->fat_pairs));
-		ctx->fat_pairs = nullptr; ctx->fat_pair_capacity = 0;
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->fat_pairs, sizeof(uint2) * (size_t)want_kept));
-		ctx->fat_pair_capacity = want_kept;
-		drop_kept = true;
+		ctx->fat_pair_capacity = 0;
+		{ int rc = nh_device_buffers(ctx, { { &ctx->fat_pairs, sizeof(uint2) * (size_t)want_kept } }); if (rc) return rc; }
+		ctx->fat_pair_capacity = want_kept; *fresh = true;
 	}
 	if (ctx->fat_collider_capacity < C) {
-		if (ctx->fat_box) NH_HIP_CHECK(ctx, hipFree(ctx->fat_box));
-		ctx->fat_box = nullptr; ctx->fat_collider_capacity = 0;
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->fat_box, sizeof(float4) * 2u * (size_t)C));
-		ctx->fat_collider_capacity = C;
-		drop_kept = true;
+		ctx->fat_collider_capacity = 0;
+		{ int rc = nh_device_buffers(ctx, { { &ctx->fat_box, sizeof(float4) * 2u * (size_t)C } }); if (rc) return rc; }
+		ctx->fat_collider_capacity = C; *fresh = true;
 	}
-	ctx->fat_nbox = nbox; ctx->fat_nsph = nsph;
+	ctx->fat_nbox = c.nbox; ctx->fat_nsph = c.nsph;
 	// library-owned as well: the grid of the last rebuild (cell-sorted boxes, cell starts, large list) and the book-keeping of re-insertions -- a
 	// collider that leaves its box is looked up in THAT grid steps later, so none of it may live in the caller's temporary arena
-	if (ctx->grid_cells < max_cells || ctx->grid_collider_capacity < ctx->fat_collider_capacity) {
-		if (ctx->grid_sbox) NH_HIP_CHECK(ctx, hipFree(ctx->grid_sbox));
-		if (ctx->grid_cstart) NH_HIP_CHECK(ctx, hipFree(ctx->grid_cstart));
-		if (ctx->grid_counts) NH_HIP_CHECK(ctx, hipFree(ctx->grid_counts));
-		if (ctx->grid_large) NH_HIP_CHECK(ctx, hipFree(ctx->grid_large));
-		if (ctx->fat_gen) NH_HIP_CHECK(ctx, hipFree(ctx->fat_gen));
-		if (ctx->fat_esc_mark) NH_HIP_CHECK(ctx, hipFree(ctx->fat_esc_mark));
-		if (ctx->fat_esc_list) NH_HIP_CHECK(ctx, hipFree(ctx->fat_esc_list));
-		if (ctx->fat_moved_list) NH_HIP_CHECK(ctx, hipFree(ctx->fat_moved_list));
-		ctx->grid_sbox = nullptr; ctx->grid_cstart = nullptr; ctx->grid_counts = nullptr; ctx->grid_large = nullptr; ctx->fat_gen = nullptr; ctx->fat_esc_mark = nullptr;
-		ctx->fat_esc_list = nullptr; ctx->fat_moved_list = nullptr; ctx->grid_cells = 0; ctx->grid_collider_capacity = 0;
+	if (ctx->grid_cells < s.max_cells || ctx->grid_collider_capacity < ctx->fat_collider_capacity) {
+		ctx->grid_cells = 0; ctx->grid_collider_capacity = 0;
 		const size_t cc = ctx->fat_collider_capacity;              // (>= C: set with the boxes above)
-		const uint32_t cells = max_cells > ctx->grid_cells ? max_cells : ctx->grid_cells;
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->grid_sbox, sizeof(float4) * 2u * cc + 64u));
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->grid_cstart, sizeof(uint32_t) * ((size_t)cells + 8u)));
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->grid_counts, sizeof(uint32_t) * ((size_t)cells + 8u)));
-		NH_HIP_CHECK(ctx, hipMemsetAsync(ctx->grid_counts, 0, sizeof(uint32_t) * ((size_t)cells + 8u), s));
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->grid_large, sizeof(uint32_t) * cc + 64u));
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->fat_gen, cc + 64u));
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->fat_esc_mark, sizeof(uint32_t) * cc + 64u));
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->fat_esc_list, sizeof(uint32_t) * NH_ESC_MAX));
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->fat_moved_list, sizeof(uint32_t) * NH_MOVED_MAX));
-		NH_HIP_CHECK(ctx, hipMemsetAsync(ctx->fat_esc_mark, 0, sizeof(uint32_t) * cc + 64u, s));
-		NH_HIP_CHECK(ctx, hipMemsetAsync(ctx->fat_gen, 0, cc + 64u, s));
-		ctx->grid_cells = cells; ctx->grid_collider_capacity = (uint32_t)cc;
-		drop_kept = true;
+		const size_t cells = s.max_cells;
+		{ int rc = nh_device_buffers(ctx, { { &ctx->grid_sbox, sizeof(float4) * 2u * cc + 64u }, { &ctx->grid_cstart, sizeof(uint32_t) * (cells + 8u) }, { &ctx->grid_counts, sizeof(uint32_t) * (cells + 8u), true },
+		                                    { &ctx->grid_large, sizeof(uint32_t) * cc + 64u }, { &ctx->fat_gen, cc + 64u, true }, { &ctx->fat_esc_mark, sizeof(uint32_t) * cc + 64u, true },
+		                                    { &ctx->fat_esc_list, sizeof(uint32_t) * NH_ESC_MAX }, { &ctx->fat_moved_list, sizeof(uint32_t) * NH_MOVED_MAX } }); if (rc) return rc; }
+		ctx->grid_cells = s.max_cells; ctx->grid_collider_capacity = (uint32_t)cc; *fresh = true;
 	}
-	// re-insertion of colliders that leave their boxes (k_reinsert): kept-list steps only, indices that leave room for the stamps
-	const bool incremental = !bp_direct && !ctx->env_no_incremental && C < (1u << NH_GEN_SHIFT);
-	// library-owned: contact storage by slot, the records, their place in the tag order, the slot cache; per body class / contact-list record / record (nh_internal.h)
-	bool lay_fresh = false;
-	if (ctx->lay_capacity != pair_cap || ctx->lay_contact_capacity != cap) {
-		void** bufs[] = { (void**)&ctx->raw_data, (void**)&ctx->raw_feature, (void**)&ctx->rec, (void**)&ctx->lay_rank, (void**)&ctx->cnt_sorted, (void**)&ctx->start_sorted, (void**)&ctx->dense_slot,
-		                  (void**)&ctx->sc_imp, (void**)&ctx->sc_feat, (void**)&ctx->sc_count, (void**)&ctx->sc_undo, (void**)&ctx->pair_mark, (void**)&ctx->pair_list, (void**)&ctx->exp_cnt, (void**)&ctx->exp_start, (void**)&ctx->exp_scan_tmp, (void**)&ctx->still_delta };
-		for (void** b : bufs) { if (*b) NH_HIP_CHECK(ctx, hipFree(*b)); *b = nullptr; }
-		ctx->lay_capacity = 0; ctx->lay_contact_capacity = 0;
-		const size_t slots = (size_t)4 * pair_cap + cap, cache_slots = (size_t)5 * pair_cap + 64u;
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->raw_data, sizeof(nh_Contact) * slots));
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->raw_feature, sizeof(uint32_t) * slots + 64u));
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->rec, sizeof(nh_Record) * (size_t)pair_cap + 64u));
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->lay_rank, sizeof(uint32_t) * (size_t)pair_cap + 64u));
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->cnt_sorted, sizeof(uint32_t) * ((size_t)pair_cap + 2u)));
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->start_sorted, sizeof(uint32_t) * ((size_t)pair_cap + 2u)));
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->dense_slot, sizeof(uint32_t) * (size_t)cap + 64u));
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->sc_imp, sizeof(float4) * cache_slots));
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->sc_feat, sizeof(uint32_t) * cache_slots));
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->sc_count, sizeof(uint32_t) * (size_t)pair_cap + 64u));
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->sc_undo, sizeof(uint64_t) * (size_t)pair_cap + 64u));
-		NH_HIP_CHECK(ctx, hipMemsetAsync(ctx->sc_undo, 0, sizeof(uint64_t) * (size_t)pair_cap + 64u, s));
-		ctx->still.undo_dirty = false;
-		ctx->pair_list_capacity = pair_cap / 8u + 1024u;
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->pair_mark, sizeof(uint32_t) * (size_t)pair_cap + 64u));
-		NH_HIP_CHECK(ctx, hipMemsetAsync(ctx->pair_mark, 0, sizeof(uint32_t) * (size_t)pair_cap + 64u, s));
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->pair_list, sizeof(uint32_t) * (size_t)ctx->pair_list_capacity));
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->exp_cnt, sizeof(uint32_t) * ((size_t)pair_cap + 2u)));
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->exp_start, sizeof(uint32_t) * ((size_t)pair_cap + 2u)));
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->exp_scan_tmp, sizeof(uint32_t) * (2u * NH_SORT_GRID + 64u)));
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->still_delta, sizeof(int2) * 2u * NH_DELTA_MAX));
-		ctx->raw_slots = (uint32_t)slots;
-		ctx->lay_capacity = pair_cap; ctx->lay_contact_capacity = cap; lay_fresh = true;
-	}
-	if (ctx->lay_body_capacity < B) {
-		void** bufs[] = { (void**)&ctx->lay_class, (void**)&ctx->lay_simple, (void**)&ctx->body_rec, (void**)&ctx->body_pos };
-		for (void** b : bufs) { if (*b) NH_HIP_CHECK(ctx, hipFree(*b)); *b = nullptr; }
-		ctx->lay_body_capacity = 0;
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->lay_class, (size_t)B + 64u));
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->lay_simple, sizeof(uint2) * (size_t)B + 64u));
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->body_rec, sizeof(uint32_t) * (size_t)B + 64u));
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->body_pos, sizeof(uint32_t) * (size_t)B + 64u));
-		ctx->lay_body_capacity = B; lay_fresh = true;
-	}
-	nh_Contact* raw_data = ctx->raw_data; uint32_t* raw_feature = ctx->raw_feature; nh_Record* rec = ctx->rec; uint32_t* rec_counts = ctx->cnt_sorted;
-	if (lay_fresh) { ctx->still.slots_current = false; ctx->still.ok_next = false; }
-	{
-		nh_StillStep& ss = ctx->still;
-		if (!same_colliders(*colliders, ss.lay_colliders)) ss.ahead_world_bad = false;          // (other colliders: whether bodies carry several of them is found out again)
-		ss.lay_bodies = *bodies; ss.lay_colliders = *colliders; ss.lay_contacts = *contacts; ss.lay_active = active_bodies->indices; ss.lay_active_capacity = active_bodies->capacity;
-		ss.appended = false;
-		// ---- the still step: three launches instead of the thirty below ----
-		// SLEEPERS form (nh_internal.h): somebody may be asleep (the host cannot rule it out) -- bodies asleep in sets of their own are the step's business, without
-		// user connections (they join sets: nudge.cpp:3511-3575) and with the per-body notes the views are made of
-		const bool may_sleep = !no_islands;
-		const bool sleepers_ok = !ss.no_local && !(body_connections && body_connections->count);
-		if (may_sleep && sleepers_ok && ctx->still_awake_capacity < B) {
-			if (ctx->still_awake) NH_HIP_CHECK(ctx, hipFree(ctx->still_awake));
-			ctx->still_awake = nullptr; ctx->still_awake_capacity = 0;
-			NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->still_awake, (size_t)B + 64u));
-			ctx->still_awake_capacity = B;
-		}
-		const bool still = want_still && (no_islands || sleepers_ok) && !bp_direct && !drop_kept && !drop_sort_order && !lay_fresh && ctx->sort_seeded && !ctx->env_sort_radix &&
-		                   !ctx->env_no_sort_reuse && C != 0u;
-		if (still) {
-			const bool sleepers = may_sleep;
-			ss.sleepers = sleepers;
-			nh_DevState* st = ctx->d_state;
-			// MOVERS form (nh_internal.h, "LOCAL speculation"): while somebody has been leaving its inflated box lately, the step re-boxes its leavers and re-inserts them
-			// into the kept list itself (one more launch, which leaves at once in a step nobody moves in); otherwise a leaver fails the step, and the full step that
-			// re-inserts it switches this on
-			const bool movers = incremental && !ss.no_local && ss.movers_left != 0u;
-			// (the colliders' world transforms, boxes and tags of a still step live in buffers of the library's own: nh_internal.h, xform ahead)
-			if (ctx->own_capacity < C) {
-				void** bufs[] = { (void**)&ctx->own_xf, (void**)&ctx->own_aabb_min, (void**)&ctx->own_aabb_max, (void**)&ctx->own_ctag };
-				for (void** b : bufs) { if (*b) NH_HIP_CHECK(ctx, hipFree(*b)); *b = nullptr; }
-				ctx->own_capacity = 0;
-				NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->own_xf, sizeof(nh_xform) * (size_t)C + 64u));
-				NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->own_aabb_min, sizeof(float4) * (size_t)C + 64u));
-				NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->own_aabb_max, sizeof(float4) * (size_t)C + 64u));
-				NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->own_ctag, sizeof(uint32_t) * (size_t)C + 64u));
-				ctx->own_capacity = C; ss.ahead_ready = false; ss.own_current = false;
-			}
-			xf = ctx->own_xf; aabb_min = ctx->own_aabb_min; aabb_max = ctx->own_aabb_max; ctag = ctx->own_ctag;
-			// XFORM AHEAD: the solver of the step before this one -- same nh_step call, plain form -- has written all of that for the dynamic bodies' colliders; this step
-			// starts at the narrowphase
-			// SLEEPERS AHEAD (nh_internal.h): the sleeping set has stood still for a few confirmed steps -- the awake bodies' lanes work ahead as in the plain form
-			if (ss.sleep_backoff) ss.sleep_backoff--;
-			// (the step in which the host can no longer rule sleepers out is the one before the first of them falls asleep: what stood still until now was a world awake)
-			if (sleepers && !ss.was_sleepers) ss.sleep_stable = 0u;
-			ss.was_sleepers = sleepers;
-			const bool sleep_stable = sleepers && !ss.no_sleeper_ahead && !ss.no_pair && ss.sleep_stable >= 4u && ss.sleep_backoff == 0u && !ctx->step_hook && ss.pipelined && C <= (2u << 20);
-			const bool plain = !movers && (!sleepers || sleep_stable) && !ss.appended_pairs && (nbox >= 2 || nsph != 0u);
-			// (sleepers: the whole pair step or the three kernels -- a step that starts at the narrowphase would need its sleepers form there)
-			const bool ahead_step = plain && ss.ahead_ready && !ss.no_ahead && (!sleepers || ss.pair_ready);
-			ss.ahead_ready = false; ss.ahead_plain = plain;
-			// PAIR AHEAD (nh_internal.h): the last step's solver lanes evaluated this step's pairs too -- this step starts at the solver, behind one wave of bookkeeping
-			const bool pair_step = ahead_step && ss.pair_ready && !ss.no_pair;
-			ss.pair_ready = false; ss.pair_step = pair_step; ss.early_verdict = false;
-			if (pair_step) ss.pair_steps++;
-			if (pair_step && sleepers && ss.sleep_run < 0xffffu) ss.sleep_run++;
-			if (ahead_step) ss.ahead_steps++;
-			else
-			NH_LAUNCH(ctx, "xform_still", (k_xform<true>), nh_grid_for(C > B ? C : B, 1024, 256), 1024, st, bodies->transforms,
-			          colliders->boxes.transforms, colliders->boxes.data, colliders->boxes.tags, nbox,
-			          colliders->spheres.transforms, colliders->spheres.data, colliders->spheres.tags, nsph,
-			          xf, aabb_min, aabb_max, ctag, (uint4*)nullptr, 0u, ctx->fat_box, 0u,
-			          movers ? ctx->fat_gen : (uint8_t*)nullptr, ctx->fat_esc_mark, ctx->fat_esc_list, ctx->fat_moved_list, ctx->collide_seq, bodies->idle_counters, B, ctx->step_parity,
-			          sleepers ? ctx->still_awake : (uint8_t*)nullptr, (sleepers && ss.substep > 0u && ss.own_current && !ctx->step_hook && !ss.no_sleeper_skip) ? 1u : 0u);          // (the narrowphase's `sleeper_skip` below)
-			// (sleepers ahead: the static world's share of the scene bounds holds the sleepers' -- a step with a k_xform<true> and a narrowphase of its own may be the one in
-			// which somebody falls asleep without failing anything, so every such step of a world with sleepers takes the map again before lanes work ahead on it)
-			if (sleepers && !ahead_step) ss.ahead_map_ok = false;
-			if (!ahead_step && plain && ss.more_steps && !ss.no_ahead && !ss.ahead_world_bad && !ss.ahead_map_ok && bodies->idle_counters) {
-				// (once per nh_step call: which collider each body's lane stands in for, and the static world's share of the scene bounds)
-				if (ctx->body_col_capacity < B) {
-					if (ctx->body_col) NH_HIP_CHECK(ctx, hipFree(ctx->body_col));
-					ctx->body_col = nullptr; ctx->body_col_capacity = 0;
-					NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->body_col, sizeof(uint32_t) * (size_t)B + 64u));
-					ctx->body_col_capacity = B;
-				}
-				NH_HIP_CHECK(ctx, hipMemsetAsync(ctx->body_col, 0xff, sizeof(uint32_t) * (size_t)B, ctx->stream));
-				NH_LAUNCH(ctx, "ahead_map", k_ahead_map, nh_grid_for(C, 256, 2048), 256, st, aabb_min, C, ctx->body_col);
-				NH_LAUNCH(ctx, "ahead_check", k_ahead_check, nh_grid_for(C, 256, 1024), 256, st, aabb_min, C, ctx->body_col, sleepers ? bodies->idle_counters : (const uint8_t*)nullptr);
-				if (ss.pair_owned_seq == 0u && !ss.no_pair && ctx->pair_mark) {
-					// (pair ahead: the kept pairs that are no body's own, listed once per layout)
-					NH_HIP_CHECK(ctx, hipMemsetAsync(&st->pair_unowned, 0, sizeof(uint32_t), ctx->stream));
-					NH_LAUNCH(ctx, "pair_mark", k_pair_mark, nh_grid_for(B, 256, 2048), 256, ctx->body_rec, (ctx->halo_ghost_first && ctx->halo_ghost_first < B) ? ctx->halo_ghost_first : B, ctx->pair_mark, ctx->collide_seq);
-					NH_LAUNCH(ctx, "pair_list", k_pair_list, nh_grid_for(pair_cap, 256, 2048), 256, st, ctx->pair_mark, ctx->collide_seq, ctx->pair_list, ctx->pair_list_capacity, sleepers ? ctx->rec : (const nh_Record*)nullptr);
-					ss.pair_owned_seq = ctx->collide_seq;
-				}
-				ss.ahead_map_ok = true;
-			}
-			if (movers)
-				NH_LAUNCH(ctx, "reinsert_still", k_reinsert, 256, 256, st, nbox, ctx->grid_sbox, ctx->grid_cstart, ctx->grid_large, ctx->fat_box, ctx->fat_gen, ctx->fat_esc_mark, ctx->fat_esc_list,
-				          ctx->fat_moved_list, ctx->collide_seq, ctx->fat_pairs, ctx->fat_pair_capacity, 1u, ctx->step_parity, C, ctx->body_rec, pair_cap);
-			const uint8_t* gen = incremental ? ctx->fat_gen : (const uint8_t*)nullptr;
-			// (a world dozing off changes thousands of contact counts per step: the scan, not the list -- but not in a pair step of a world whose sleeping set stands still,
-			// sleepers ahead: its lanes listed their changes like a plain world's, and the two launches that leave at once are 4 us of an 80 us step)
-			const bool delta_scan = C > (2u << 20) || (sleepers && !pair_step);
-			uint32_t* const sc_count = sleepers ? ctx->sc_count : (uint32_t*)nullptr;
-			if (sleepers) ss.undo_dirty = true;
-			// (the LOCAL form of the narrowphase -- appended pairs, sleeping bodies -- only where it can matter: this step or an earlier one since the layout ran in movers
-			// form, or somebody may be asleep)
-			if (movers) ss.appended_pairs = true;
-			const bool local = sleepers || ss.appended_pairs;
-			// (sleepers form inside an nh_step call, not its first sub-step, and the sub-step before this one wrote own_* in the same form (nh_internal.h: own_current):
-			// what was asleep when that one looked and is asleep now has not moved)
-			const uint32_t sleeper_skip = (sleepers && ss.substep > 0u && ss.own_current && !ctx->step_hook && !ss.no_sleeper_skip) ? 1u : 0u;
-			ss.own_current = sleepers;          // (this step's k_xform<true> has written the arrays and the marks -- or the last solver's lanes did, on top of a sleepers-form step's: ahead_ready)
-#define NH_NARROW_STILL(SPHERES, NAME, GRIDMAX) do { if (local) NH_LAUNCH(ctx, NAME, (k_narrowphase<SPHERES, true, true>), nh_grid_for(pair_cap, 256, GRIDMAX), 256, st, ctx->fat_pairs, xf, ctag, \
-				          colliders->boxes.data, colliders->spheres.data, nbox, raw_data, raw_feature, pair_cap, 0u, ctx->sort_keys_by_position, rec, (uint32_t*)nullptr, \
-				          (const uint32_t*)nullptr, (const uint32_t*)nullptr, ctx->step_parity, 0u, ctx->fat_pair_capacity, aabb_min, aabb_max, gen, ctx->lay_rank, ctx->cnt_sorted, ctx->body_rec, ctx->collide_seq, ctx->still_delta, delta_scan ? 1u : 0u, sc_count, 0u, ctx->sc_undo, sleeper_skip); \
-				else NH_LAUNCH(ctx, NAME, (k_narrowphase<SPHERES, true, false>), nh_grid_for(pair_cap, 256, GRIDMAX), 256, st, ctx->fat_pairs, xf, ctag, \
-				          colliders->boxes.data, colliders->spheres.data, nbox, raw_data, raw_feature, pair_cap, 0u, ctx->sort_keys_by_position, rec, (uint32_t*)nullptr, \
-				          (const uint32_t*)nullptr, (const uint32_t*)nullptr, ctx->step_parity, 0u, ctx->fat_pair_capacity, aabb_min, aabb_max, gen, ctx->lay_rank, ctx->cnt_sorted, ctx->body_rec, ctx->collide_seq, ctx->still_delta, delta_scan ? 1u : 0u, (uint32_t*)nullptr, ahead_step ? 1u : 0u); } while (0)
-			if (pair_step) {
-			// (one wave for the step-wide checks and one lane per listed pair -- 651 in c2: 12 waves; until a round trip has told how many the list holds, and beyond 127
-			// waves, the lanes stride over it)
-			const uint32_t pair_waves = ss.pair_world_ok ? std::min(std::max((ss.pair_listed + 63u) / 64u, 1u), 127u) : 127u;
-			NH_LAUNCH(ctx, "pair_begin", k_pair_begin, 1u + pair_waves, 64, st, ctx->step_parity, ctx->collide_seq, ctx->pair_list, ctx->pair_list_capacity, ctx->fat_pairs, ctx->fat_pair_capacity, pair_cap, gen,
-			                         xf, aabb_min, aabb_max, ctag, colliders->boxes.data, colliders->spheres.data, nbox, ctx->sort_keys_by_position, rec,
-			                         ctx->lay_rank, ctx->cnt_sorted, ctx->body_rec, ctx->still_delta, raw_data, raw_feature, bodies->momentum, bodies->properties, delta_scan ? 1u : 0u, sleepers ? B : 0u);
-			ss.early_verdict = false;
-			if (ctx->step_hook && !ss.pipelined && ss.h_ring[0] && !ctx->timing) {
-				NH_HIP_CHECK(ctx, hipMemcpyAsync(ss.h_ring[0], st, NH_COUNTER_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-				NH_HIP_CHECK(ctx, hipEventRecord(ss.ev_ring[0], ctx->stream));
-				ss.early_verdict = true;
-			}
-			}
-			else {
-			if (nbox >= 2) NH_NARROW_STILL(false, "narrowphase_still", 4096);
-			if (nsph) NH_NARROW_STILL(true, "narrowphase_sph_still", 8192);
-			}
-			// every record's first contact in the dense (tag-ordered) list = the scan of the counts in tag order: kept from step to step, shifted by the listed changes
-			// (the solver keeps the total).  More pairs changing their count than the list holds: a world of up to two million colliders fails the step (a handful change
-			// per million and step at rest); a larger one runs the scan instead -- two launches that leave at once otherwise, nothing next to its step
-			if (delta_scan) nh_scan_u32(ctx, ctx->cnt_sorted, ctx->start_sorted, &st->records, 1, scan_tmp, nullptr, &st->delta_overflow[ctx->step_parity]);
-			ss.active = true; ss.resolved = false; ss.launched++;
-			ctx->gravity_may_overlap = false;
-			ctx->after_collide = true;
-			return NH_OK;
-		}
-	}
-	// a full step.  (nh_step: a still step whose verdict has not been looked at yet must have happened before anything is built on it)
-	if (ctx->still.verdict.pending) { const int v = nh_still_verdict_now(ctx); if (v) return v == 2 ? NH_ERR_HIP : NH_INTERNAL_STILL_FAILED; }
-	ctx->still.pair_ready = false; ctx->still.pair_step = false; ctx->still.early_verdict = false; ctx->still.pair_world_bad = false; ctx->still.pair_world_ok = false; ctx->still.pair_listed = 0u; ctx->still.pair_owned_seq = 0u;          // (another layout: whether every kept pair is some body's own is found out again)
-	// The solver reads the caller's cache arrays and this nh_collide lays the dense contact list out -- whatever still steps kept by slot goes home first
-	{ int rc = nh_still_export_cache(ctx); if (rc) return rc; }
-	ctx->still.ahead_ready = false; ctx->still.ahead_plain = false; ctx->still.own_current = false;          // (a full step writes the arena's arrays, not own_*)
-	if (!no_islands) ctx->still.ahead_map_ok = false;          // (sleepers ahead: the static world's share of the scene bounds holds the sleepers' -- and who sleeps may change in a full step)
-	ctx->still.contacts_stale = false; ctx->still.slots_current = false; ctx->still.views_sleepers = false; ctx->still.appended_pairs = false;          // (a full step writes the contact list, the sleeping pairs and the active list itself)
-	NH_LAUNCH(ctx, "collide_begin", k_collide_begin, begin_grid, 256, st, C, B, parent, set_active, ctx->deg, bodies->idle_counters, ctx->step_parity, coarse_parent, coarse_active, no_islands ? 1u : 0u, block_top,
-	          drop_kept ? 1u : 0u, drop_sort_order ? 1u : 0u);
-	const bool seeded_sort = ctx->sort_seeded && !ctx->env_sort_radix;      // (NH_SORT_RADIX=1: radix passes every step)
-	uint64_t* rec_key_a = ctx->sort_keys_by_position;
-	if (C) {
-		NH_LAUNCH(ctx, "xform_aabb", (k_xform<false>), nh_grid_for(C, 1024, 256), 1024, st, bodies->transforms,
+	return NH_OK;
+}
+
+// contact storage by slot, the records, their place in the tag order, the slot cache; per contact-list record / record (nh_internal.h)
+static int reserve_pair_layout(nh_context* ctx, uint32_t pair_cap, uint32_t cap, bool* fresh) {
+	if (ctx->lay_capacity == pair_cap && ctx->lay_contact_capacity == cap) return NH_OK;
+	ctx->lay_capacity = 0; ctx->lay_contact_capacity = 0;
+	const size_t slots = (size_t)4 * pair_cap + cap, cache_slots = (size_t)5 * pair_cap + 64u, pairs = pair_cap;
+	ctx->pair_list_capacity = pair_cap / 8u + 1024u;
+	{ int rc = nh_device_buffers(ctx, { { &ctx->raw_data, sizeof(nh_Contact) * slots }, { &ctx->raw_feature, sizeof(uint32_t) * slots + 64u }, { &ctx->rec, sizeof(nh_Record) * pairs + 64u },
+	                                    { &ctx->lay_rank, sizeof(uint32_t) * pairs + 64u }, { &ctx->cnt_sorted, sizeof(uint32_t) * (pairs + 2u) }, { &ctx->start_sorted, sizeof(uint32_t) * (pairs + 2u) },
+	                                    { &ctx->dense_slot, sizeof(uint32_t) * (size_t)cap + 64u }, { &ctx->sc_imp, sizeof(float4) * cache_slots }, { &ctx->sc_feat, sizeof(uint32_t) * cache_slots },
+	                                    { &ctx->sc_count, sizeof(uint32_t) * pairs + 64u }, { &ctx->sc_undo, sizeof(uint64_t) * pairs + 64u, true }, { &ctx->pair_mark, sizeof(uint32_t) * pairs + 64u, true },
+	                                    { &ctx->pair_list, sizeof(uint32_t) * (size_t)ctx->pair_list_capacity }, { &ctx->exp_cnt, sizeof(uint32_t) * (pairs + 2u) }, { &ctx->exp_start, sizeof(uint32_t) * (pairs + 2u) },
+	                                    { &ctx->exp_scan_tmp, sizeof(uint32_t) * (2u * NH_SORT_GRID + 64u) }, { &ctx->still_delta, sizeof(int2) * 2u * NH_DELTA_MAX } }); if (rc) return rc; }
+	ctx->still.undo_dirty = false;
+	ctx->raw_slots = (uint32_t)slots;
+	ctx->lay_capacity = pair_cap; ctx->lay_contact_capacity = cap; *fresh = true;
+	return NH_OK;
+}
+
+// per body: class, one-body record, the record and tag-order position of its pair (nh_internal.h)
+static int reserve_body_layout(nh_context* ctx, uint32_t B, bool* fresh) {
+	if (ctx->lay_body_capacity >= B) return NH_OK;
+	ctx->lay_body_capacity = 0;
+	{ int rc = nh_device_buffers(ctx, { { &ctx->lay_class, (size_t)B + 64u }, { &ctx->lay_simple, sizeof(uint2) * (size_t)B + 64u }, { &ctx->body_rec, sizeof(uint32_t) * (size_t)B + 64u },
+	                                    { &ctx->body_pos, sizeof(uint32_t) * (size_t)B + 64u } }); if (rc) return rc; }
+	ctx->lay_body_capacity = B; *fresh = true;
+	return NH_OK;
+}
+
+// still steps: the colliders' world transforms, boxes and tags live in buffers of the library's own (nh_internal.h, xform ahead)
+static int reserve_own(nh_context* ctx, uint32_t C) {
+	if (ctx->own_capacity >= C) return NH_OK;
+	ctx->own_capacity = 0;
+	{ int rc = nh_device_buffers(ctx, { { &ctx->own_xf, sizeof(nh_xform) * (size_t)C + 64u }, { &ctx->own_aabb_min, sizeof(float4) * (size_t)C + 64u }, { &ctx->own_aabb_max, sizeof(float4) * (size_t)C + 64u },
+	                                    { &ctx->own_ctag, sizeof(uint32_t) * (size_t)C + 64u } }); if (rc) return rc; }
+	ctx->own_capacity = C; ctx->still.ahead_ready = false; ctx->still.own_current = false;
+	return NH_OK;
+}
+
+// ---- the still step: three launches instead of the thirty of a full step ----
+// The form one still step takes (the forms themselves: nh_internal.h, nh_StillStep).  still_decide settles it and does the bookkeeping; still_launch only launches.
+struct StillForm {
+	bool sleepers;            // SLEEPERS: somebody may be asleep (the host cannot rule it out) -- bodies asleep in sets of their own are the step's business
+	bool movers;              // MOVERS ("LOCAL speculation"): while somebody has been leaving its inflated box lately, the step re-boxes its leavers and re-inserts them into the kept list
+	                          // itself (one more launch, which leaves at once in a step nobody moves in); otherwise a leaver fails the step, and the full step that re-inserts it switches this on
+	bool ahead_step;          // XFORM AHEAD: the last step's solver has written own_* for the dynamic bodies' colliders -- this step starts at the narrowphase
+	bool pair_step;           // PAIR AHEAD: its lanes evaluated this step's pairs too -- this step starts at the solver, behind one wave of bookkeeping
+	bool take_map;            // once per nh_step call: which collider each body's lane stands in for, and the static world's share of the scene bounds
+	bool list_unowned;        // ... and, once per layout, the kept pairs that are no body's own (pair ahead)
+	bool early_verdict;       // a pair step under a step hook reports through ring slot 0 right behind k_pair_begin
+	bool delta_scan;          // contact starts by scan, not by the list of changed counts
+	bool local;               // the LOCAL form of the narrowphase (appended pairs, sleeping bodies)
+	uint32_t sleeper_skip;    // sleepers form inside an nh_step call, not its first sub-step, and the sub-step before this one wrote own_* in the same form (nh_internal.h: own_current):
+	                          // what was asleep when that one looked and is asleep now has not moved
+};
+
+static StillForm still_decide(nh_context* ctx, const CollideCall& c, const CollideMode& m) {
+	nh_StillStep& ss = ctx->still;
+	const uint32_t C = c.C, nbox = c.nbox, nsph = c.nsph;
+	StillForm f;
+	const bool sleepers = f.sleepers = !c.no_islands;
+	ss.sleepers = sleepers;
+	const bool movers = f.movers = m.incremental && !ss.no_local && ss.movers_left != 0u;
+	// SLEEPERS AHEAD (nh_internal.h): the sleeping set has stood still for a few confirmed steps -- the awake bodies' lanes work ahead as in the plain form
+	if (ss.sleep_backoff) ss.sleep_backoff--;
+	// (the step in which the host can no longer rule sleepers out is the one before the first of them falls asleep: what stood still until now was a world awake)
+	if (sleepers && !ss.was_sleepers) ss.sleep_stable = 0u;
+	ss.was_sleepers = sleepers;
+	const bool sleep_stable = sleepers && !ss.no_sleeper_ahead && !ss.no_pair && ss.sleep_stable >= 4u && ss.sleep_backoff == 0u && !ctx->step_hook && ss.pipelined && C <= (2u << 20);
+	const bool plain = !movers && (!sleepers || sleep_stable) && !ss.appended_pairs && (nbox >= 2 || nsph != 0u);
+	// (sleepers: the whole pair step or the three kernels -- a step that starts at the narrowphase would need its sleepers form there)
+	const bool ahead_step = f.ahead_step = plain && ss.ahead_ready && !ss.no_ahead && (!sleepers || ss.pair_ready);
+	ss.ahead_ready = false; ss.ahead_plain = plain;
+	const bool pair_step = f.pair_step = ahead_step && ss.pair_ready && !ss.no_pair;
+	ss.pair_ready = false; ss.pair_step = pair_step; ss.early_verdict = false;
+	if (pair_step) ss.pair_steps++;
+	if (pair_step && sleepers && ss.sleep_run < 0xffffu) ss.sleep_run++;
+	if (ahead_step) ss.ahead_steps++;
+	f.sleeper_skip = (sleepers && ss.substep > 0u && ss.own_current && !ctx->step_hook && !ss.no_sleeper_skip) ? 1u : 0u;
+	// (sleepers ahead: the static world's share of the scene bounds holds the sleepers' -- a step with a k_xform<true> and a narrowphase of its own may be the one in
+	// which somebody falls asleep without failing anything, so every such step of a world with sleepers takes the map again before lanes work ahead on it)
+	if (sleepers && !ahead_step) ss.ahead_map_ok = false;
+	f.take_map = !ahead_step && plain && ss.more_steps && !ss.no_ahead && !ss.ahead_world_bad && !ss.ahead_map_ok && c.bodies->idle_counters;
+	f.list_unowned = f.take_map && ss.pair_owned_seq == 0u && !ss.no_pair && ctx->pair_mark;
+	// (a world dozing off changes thousands of contact counts per step: the scan, not the list -- but not in a pair step of a world whose sleeping set stands still,
+	// sleepers ahead: its lanes listed their changes like a plain world's, and the two launches that leave at once are 4 us of an 80 us step)
+	f.delta_scan = C > (2u << 20) || (sleepers && !pair_step);
+	if (sleepers) ss.undo_dirty = true;
+	// (the LOCAL form of the narrowphase -- appended pairs, sleeping bodies -- only where it can matter: this step or an earlier one since the layout ran in movers
+	// form, or somebody may be asleep)
+	if (movers) ss.appended_pairs = true;
+	f.local = sleepers || ss.appended_pairs;
+	ss.own_current = sleepers;          // (this step's k_xform<true> writes the arrays and the marks -- or the last solver's lanes did, on top of a sleepers-form step's: ahead_ready)
+	f.early_verdict = pair_step && ctx->step_hook && !ss.pipelined && ss.h_ring[0] && !ctx->timing;
+	return f;
+}
+
+// (LOCAL = false: the kernel's defaults for what only the LOCAL form reads, written out -- both forms share the argument list)
+template<bool SPH, bool LOCAL>
+static void launch_narrow_still(nh_context* ctx, const CollideCall& c, uint32_t pair_cap, const StillForm& f, const uint8_t* gen) {
+	NH_LAUNCH(ctx, SPH ? "narrowphase_sph_still" : "narrowphase_still", (k_narrowphase<SPH, true, LOCAL>), nh_grid_for(pair_cap, 256, SPH ? 8192 : 4096), 256, ctx->d_state, ctx->fat_pairs, ctx->own_xf, ctx->own_ctag,
+	          c.colliders->boxes.data, c.colliders->spheres.data, c.nbox, ctx->raw_data, ctx->raw_feature, pair_cap, 0u, ctx->sort_keys_by_position, ctx->rec, (uint32_t*)nullptr,
+	          (const uint32_t*)nullptr, (const uint32_t*)nullptr, ctx->step_parity, 0u, ctx->fat_pair_capacity, ctx->own_aabb_min, ctx->own_aabb_max, gen, ctx->lay_rank, ctx->cnt_sorted, ctx->body_rec, ctx->collide_seq, ctx->still_delta, f.delta_scan ? 1u : 0u,
+	          /* sc_count */ (LOCAL && f.sleepers) ? ctx->sc_count : (uint32_t*)nullptr, /* ahead */ (!LOCAL && f.ahead_step) ? 1u : 0u, /* sc_undo */ LOCAL ? ctx->sc_undo : (uint64_t*)nullptr,
+	          /* quick_sleepers */ LOCAL ? f.sleeper_skip : 0u);
+}
+
+static int still_launch(nh_context* ctx, const CollideCall& c, const CollideScratch& s, const CollideMode& m, const StillForm& f) {
+	nh_StillStep& ss = ctx->still;
+	nh_DevState* st = ctx->d_state;
+	const nh_BodyData* bodies = c.bodies; const nh_ColliderData* colliders = c.colliders;
+	const uint32_t C = c.C, B = c.B, nbox = c.nbox, nsph = c.nsph, pair_cap = s.pair_cap;
+	nh_xform* xf = ctx->own_xf; float4* aabb_min = ctx->own_aabb_min; float4* aabb_max = ctx->own_aabb_max; uint32_t* ctag = ctx->own_ctag;
+	if (!f.ahead_step)
+		NH_LAUNCH(ctx, "xform_still", (k_xform<true>), nh_grid_for(C > B ? C : B, 1024, 256), 1024, st, bodies->transforms,
 		          colliders->boxes.transforms, colliders->boxes.data, colliders->boxes.tags, nbox,
 		          colliders->spheres.transforms, colliders->spheres.data, colliders->spheres.tags, nsph,
-		          xf, aabb_min, aabb_max, ctag, (uint4*)nullptr, 0u, ctx->fat_box, bp_direct ? 1u : 0u,
-		          incremental ? ctx->fat_gen : (uint8_t*)nullptr, ctx->fat_esc_mark, ctx->fat_esc_list, ctx->fat_moved_list, ctx->collide_seq);
-		// (asleep steps, nh_internal.h: this step may turn out to be the second fixed point in a row -- its boxes and tags are kept while they are still where k_xform put them)
-		if (ctx->asleep.streak >= 1u && !ctx->asleep.disabled) (void)asleep_snapshot(ctx);
-		// Morton frame; and the decision whether the grid chain below runs this step or the kept pair list is re-used (its kernels are launched
-		// either way: the decision is made on the device, and a kernel that leaves at once costs two microseconds)
-		NH_LAUNCH(ctx, "grid_setup", k_grid_setup, 1, 64, st, C, max_cells, bp_direct ? 1u : 0u, ctx->fat_pair_capacity);
-		float4* fbox = ctx->fat_box;
-		float4* sbox = ctx->grid_sbox; uint32_t* large_list = ctx->grid_large; uint32_t* cell_start = ctx->grid_cstart; uint32_t* cstart = ctx->grid_counts;       // (cstart: the cell COUNTS of a rebuild, all zero between rebuilds)
-		uint2* kept = ctx->fat_pairs;
-		const uint32_t kept_cap = ctx->fat_pair_capacity;
-		NH_LAUNCH(ctx, "cell_keys", k_cell_keys, nh_grid_for(C, 256, 2048), 256, st, C, aabb_min, aabb_max, fbox, keys_a, vals_a, large_list, cstart, incremental ? ctx->fat_gen : (uint8_t*)nullptr);
-		NH_LAUNCH(ctx, "cell_scan", k_cscan_sums, max_cells / CS_TILE, 256, st, cstart, cscan_sums);
-		NH_LAUNCH(ctx, "cell_scan", k_cscan_final, max_cells / CS_TILE, 256, st, cstart, cscan_sums, max_cells, cell_start);
-		NH_LAUNCH(ctx, "cell_scatter", k_cell_scatter, nh_grid_for(C, 256, 2048), 256, st, C, keys_a, vals_a, cell_start, fbox, keys_b, sbox);
-		// (KEPT: the chain fills the kept list, k_kept_filter makes this step's pairs of it; DIRECT: the chain writes this step's pairs itself)
-		const bool many_lanes = C <= 16384u;
-#define NH_FIND_PAIRS(SUBL, DIR, OUT, OUTCAP) NH_LAUNCH(ctx, "find_pairs", (k_find_pairs<SUBL, DIR>), nh_grid_for((uint64_t)C * SUBL, 256, 4096), 256, st, C, nbox, keys_b, sbox, cell_start, large_list, fbox, OUT, OUTCAP, \
-		          coarse_parent, ctx->step_parity, bodies->idle_counters)
-		if (bp_direct) {
-			if (many_lanes) NH_FIND_PAIRS(16, true, pairs, pair_cap); else NH_FIND_PAIRS(1, true, pairs, pair_cap);
-			NH_LAUNCH(ctx, "large_pairs", (k_large_pairs<true>), LP_GRID, LP_THREADS, st, nbox, sbox, cell_start, large_list, fbox, pairs, pair_cap, coarse_parent, ctx->step_parity, bodies->idle_counters);
-		} else {
-			if (many_lanes) NH_FIND_PAIRS(16, false, kept, kept_cap); else NH_FIND_PAIRS(1, false, kept, kept_cap);
-			NH_LAUNCH(ctx, "large_pairs", (k_large_pairs<false>), LP_GRID, LP_THREADS, st, nbox, sbox, cell_start, large_list, fbox, kept, kept_cap, coarse_parent, ctx->step_parity, bodies->idle_counters);
-			// colliders that left their boxes this step (a few: otherwise the chain above has run): new boxes, new pairs appended to the kept list
-			if (incremental)
-				NH_LAUNCH(ctx, "reinsert", k_reinsert, 256, 256, st, nbox, sbox, cell_start, large_list, fbox, ctx->fat_gen, ctx->fat_esc_mark, ctx->fat_esc_list, ctx->fat_moved_list,
-				          ctx->collide_seq, kept, kept_cap);
-			// this step's pairs: the kept ones whose exact AABBs overlap now (every step)
-			NH_LAUNCH(ctx, "kept_filter", k_kept_filter, nh_grid_for(kept_cap, 256, 1024), 256, st, kept, kept_cap, nbox, aabb_min, aabb_max, pairs, pair_cap, coarse_parent, ctx->step_parity, bodies->idle_counters,
-			          (seeded_sort && !ctx->env_no_sort_reuse) ? 1u : 0u, incremental ? ctx->fat_gen : (const uint8_t*)nullptr);
+		          xf, aabb_min, aabb_max, ctag, (uint4*)nullptr, 0u, ctx->fat_box, 0u,
+		          f.movers ? ctx->fat_gen : (uint8_t*)nullptr, ctx->fat_esc_mark, ctx->fat_esc_list, ctx->fat_moved_list, ctx->collide_seq, bodies->idle_counters, B, ctx->step_parity,
+		          f.sleepers ? ctx->still_awake : (uint8_t*)nullptr, f.sleeper_skip);
+	if (f.take_map) {
+		{ int rc = reserve_one(ctx, &ctx->body_col, &ctx->body_col_capacity, B, sizeof(uint32_t) * (size_t)B + 64u); if (rc) return rc; }
+		NH_HIP_CHECK(ctx, hipMemsetAsync(ctx->body_col, 0xff, sizeof(uint32_t) * (size_t)B, ctx->stream));
+		NH_LAUNCH(ctx, "ahead_map", k_ahead_map, nh_grid_for(C, 256, 2048), 256, st, aabb_min, C, ctx->body_col);
+		NH_LAUNCH(ctx, "ahead_check", k_ahead_check, nh_grid_for(C, 256, 1024), 256, st, aabb_min, C, ctx->body_col, f.sleepers ? bodies->idle_counters : (const uint8_t*)nullptr);
+		if (f.list_unowned) {
+			NH_HIP_CHECK(ctx, hipMemsetAsync(&st->pair_unowned, 0, sizeof(uint32_t), ctx->stream));
+			NH_LAUNCH(ctx, "pair_mark", k_pair_mark, nh_grid_for(B, 256, 2048), 256, ctx->body_rec, (ctx->halo_ghost_first && ctx->halo_ghost_first < B) ? ctx->halo_ghost_first : B, ctx->pair_mark, ctx->collide_seq);
+			NH_LAUNCH(ctx, "pair_list", k_pair_list, nh_grid_for(pair_cap, 256, 2048), 256, st, ctx->pair_mark, ctx->collide_seq, ctx->pair_list, ctx->pair_list_capacity, f.sleepers ? ctx->rec : (const nh_Record*)nullptr);
+			ss.pair_owned_seq = ctx->collide_seq;
 		}
-		// coarse islands over the broadphase pairs (united where the pairs were emitted) + connections: only when some body is asleep (a device
-		// flag: the kernels leave at once otherwise)
-		if (!no_islands && body_connections && body_connections->count)
-			NH_LAUNCH(ctx, "uf_union_connections", k_uf_union_connections, nh_grid_for(body_connections->count, 256, 512), 256, st, body_connections->data, body_connections->count, coarse_parent, ctx->step_parity, bodies->idle_counters);
-		if (!no_islands) NH_LAUNCH(ctx, "coarse_flatten", k_uf_flatten, nh_grid_for(B, 256, 512), 256, st, ctx->step_parity, B, coarse_parent, bodies->idle_counters, coarse_active, coarse_root);
-		// box-box pairs and pairs with a sphere are separate lists (emit_pair): one launch each, each running one kind of arithmetic.
-		// (the host does not know the counts: a launch over a list that turns out empty costs a few microseconds, so the launch for a
-		// shape the world does not contain is skipped outright)
-		if (nbox >= 2)
-			NH_LAUNCH(ctx, "narrowphase", (k_narrowphase<false, false>), nh_grid_for(pair_cap, 256, 4096), 256, st, pairs, xf, ctag,
-			          colliders->boxes.data, colliders->spheres.data, nbox, raw_data, raw_feature, pair_cap, overflow_cap, rec_key_a, rec, rec_idx_a,
-			          coarse_root, coarse_active, ctx->step_parity, ctx->first_ghost);
-		if (nsph)
-			NH_LAUNCH(ctx, "narrowphase_sph", (k_narrowphase<true, false>), nh_grid_for(pair_cap, 256, 8192), 256, st, pairs, xf, ctag,
-			          colliders->boxes.data, colliders->spheres.data, nbox, raw_data, raw_feature, pair_cap, overflow_cap, rec_key_a, rec, rec_idx_a,
-			          coarse_root, coarse_active, ctx->step_parity, ctx->first_ghost);
+		ss.ahead_map_ok = true;
 	}
-	// islands over contact records (+ user connections): a chain of small kernels that the tag sort of the records does not depend
-	// on -- it runs on the side stream while the caller's stream sorts (fork here, join before k_sorted_counts)
-	// (only while the side chain is small: the radix passes spin-wait on each other and must not share the machine with a long
-	// kernel -- with millions of records in one island the union-find alone takes a millisecond)
-	const bool fork = !no_islands && ctx->side != nullptr && (seeded_sort || ctx->h_state->records <= 1500000u);
+	if (f.movers)
+		NH_LAUNCH(ctx, "reinsert_still", k_reinsert, 256, 256, st, nbox, ctx->grid_sbox, ctx->grid_cstart, ctx->grid_large, ctx->fat_box, ctx->fat_gen, ctx->fat_esc_mark, ctx->fat_esc_list,
+		          ctx->fat_moved_list, ctx->collide_seq, ctx->fat_pairs, ctx->fat_pair_capacity, 1u, ctx->step_parity, C, ctx->body_rec, pair_cap);
+	const uint8_t* gen = m.incremental ? ctx->fat_gen : (const uint8_t*)nullptr;
+	if (f.pair_step) {
+		// (one wave for the step-wide checks and one lane per listed pair -- 651 in c2: 12 waves; until a round trip has told how many the list holds, and beyond 127
+		// waves, the lanes stride over it)
+		const uint32_t pair_waves = ss.pair_world_ok ? std::min(std::max((ss.pair_listed + 63u) / 64u, 1u), 127u) : 127u;
+		NH_LAUNCH(ctx, "pair_begin", k_pair_begin, 1u + pair_waves, 64, st, ctx->step_parity, ctx->collide_seq, ctx->pair_list, ctx->pair_list_capacity, ctx->fat_pairs, ctx->fat_pair_capacity, pair_cap, gen,
+		          xf, aabb_min, aabb_max, ctag, colliders->boxes.data, colliders->spheres.data, nbox, ctx->sort_keys_by_position, ctx->rec,
+		          ctx->lay_rank, ctx->cnt_sorted, ctx->body_rec, ctx->still_delta, ctx->raw_data, ctx->raw_feature, bodies->momentum, bodies->properties, f.delta_scan ? 1u : 0u, f.sleepers ? B : 0u);
+		if (f.early_verdict) {
+			NH_HIP_CHECK(ctx, hipMemcpyAsync(ss.h_ring[0], st, NH_COUNTER_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+			NH_HIP_CHECK(ctx, hipEventRecord(ss.ev_ring[0], ctx->stream));
+			ss.early_verdict = true;
+		}
+	} else {
+		if (nbox >= 2) { if (f.local) launch_narrow_still<false, true>(ctx, c, pair_cap, f, gen); else launch_narrow_still<false, false>(ctx, c, pair_cap, f, gen); }
+		if (nsph) { if (f.local) launch_narrow_still<true, true>(ctx, c, pair_cap, f, gen); else launch_narrow_still<true, false>(ctx, c, pair_cap, f, gen); }
+	}
+	// every record's first contact in the dense (tag-ordered) list = the scan of the counts in tag order: kept from step to step, shifted by the listed changes
+	// (the solver keeps the total).  More pairs changing their count than the list holds: a world of up to two million colliders fails the step (a handful change
+	// per million and step at rest); a larger one runs the scan instead -- two launches that leave at once otherwise, nothing next to its step
+	if (f.delta_scan) nh_scan_u32(ctx, ctx->cnt_sorted, ctx->start_sorted, &st->records, 1, s.scan_tmp, nullptr, &st->delta_overflow[ctx->step_parity]);
+	return NH_OK;
+}
+
+// ---- the full step, in three runs of launches ----
+// broadphase (grid chain into the kept list or, DIRECT, into this step's pairs; re-insertion; filter), coarse islands, narrowphase
+static void full_find_contacts(nh_context* ctx, const CollideCall& c, const CollideScratch& s, const CollideMode& m, bool seeded_sort) {
+	nh_DevState* st = ctx->d_state;
+	const nh_BodyData* bodies = c.bodies; const nh_ColliderData* colliders = c.colliders; const nh_BodyConnections* body_connections = c.body_connections;
+	const uint32_t C = c.C, B = c.B, nbox = c.nbox, nsph = c.nsph, pair_cap = s.pair_cap, max_cells = s.max_cells;
+	const bool bp_direct = m.bp_direct, incremental = m.incremental, no_islands = c.no_islands;
+	NH_LAUNCH(ctx, "xform_aabb", (k_xform<false>), nh_grid_for(C, 1024, 256), 1024, st, bodies->transforms,
+	          colliders->boxes.transforms, colliders->boxes.data, colliders->boxes.tags, nbox,
+	          colliders->spheres.transforms, colliders->spheres.data, colliders->spheres.tags, nsph,
+	          s.xf, s.aabb_min, s.aabb_max, s.ctag, (uint4*)nullptr, 0u, ctx->fat_box, bp_direct ? 1u : 0u,
+	          incremental ? ctx->fat_gen : (uint8_t*)nullptr, ctx->fat_esc_mark, ctx->fat_esc_list, ctx->fat_moved_list, ctx->collide_seq);
+	// (asleep steps, nh_internal.h: this step may turn out to be the second fixed point in a row -- its boxes and tags are kept while they are still where k_xform put them)
+	if (ctx->asleep.streak >= 1u && !ctx->asleep.disabled) (void)asleep_snapshot(ctx);
+	// Morton frame; and the decision whether the grid chain below runs this step or the kept pair list is re-used (its kernels are launched
+	// either way: the decision is made on the device, and a kernel that leaves at once costs two microseconds)
+	NH_LAUNCH(ctx, "grid_setup", k_grid_setup, 1, 64, st, C, max_cells, bp_direct ? 1u : 0u, ctx->fat_pair_capacity);
+	float4* fbox = ctx->fat_box;
+	float4* sbox = ctx->grid_sbox; uint32_t* large_list = ctx->grid_large; uint32_t* cell_start = ctx->grid_cstart; uint32_t* cstart = ctx->grid_counts;       // (cstart: the cell COUNTS of a rebuild, all zero between rebuilds)
+	uint2* kept = ctx->fat_pairs;
+	const uint32_t kept_cap = ctx->fat_pair_capacity;
+	NH_LAUNCH(ctx, "cell_keys", k_cell_keys, nh_grid_for(C, 256, 2048), 256, st, C, s.aabb_min, s.aabb_max, fbox, s.keys_a, s.vals_a, large_list, cstart, incremental ? ctx->fat_gen : (uint8_t*)nullptr);
+	NH_LAUNCH(ctx, "cell_scan", k_cscan_sums, max_cells / CS_TILE, 256, st, cstart, s.cscan_sums);
+	NH_LAUNCH(ctx, "cell_scan", k_cscan_final, max_cells / CS_TILE, 256, st, cstart, s.cscan_sums, max_cells, cell_start);
+	NH_LAUNCH(ctx, "cell_scatter", k_cell_scatter, nh_grid_for(C, 256, 2048), 256, st, C, s.keys_a, s.vals_a, cell_start, fbox, s.keys_b, sbox);
+	// (KEPT: the chain fills the kept list, k_kept_filter makes this step's pairs of it; DIRECT: the chain writes this step's pairs itself)
+	const bool many_lanes = C <= 16384u;
+#define NH_FIND_PAIRS(SUBL, DIR, OUT, OUTCAP) NH_LAUNCH(ctx, "find_pairs", (k_find_pairs<SUBL, DIR>), nh_grid_for((uint64_t)C * SUBL, 256, 4096), 256, st, C, nbox, s.keys_b, sbox, cell_start, large_list, fbox, OUT, OUTCAP, \
+	          s.coarse_parent, ctx->step_parity, bodies->idle_counters)
+	if (bp_direct) {
+		if (many_lanes) NH_FIND_PAIRS(16, true, s.pairs, pair_cap); else NH_FIND_PAIRS(1, true, s.pairs, pair_cap);
+		NH_LAUNCH(ctx, "large_pairs", (k_large_pairs<true>), LP_GRID, LP_THREADS, st, nbox, sbox, cell_start, large_list, fbox, s.pairs, pair_cap, s.coarse_parent, ctx->step_parity, bodies->idle_counters);
+	} else {
+		if (many_lanes) NH_FIND_PAIRS(16, false, kept, kept_cap); else NH_FIND_PAIRS(1, false, kept, kept_cap);
+		NH_LAUNCH(ctx, "large_pairs", (k_large_pairs<false>), LP_GRID, LP_THREADS, st, nbox, sbox, cell_start, large_list, fbox, kept, kept_cap, s.coarse_parent, ctx->step_parity, bodies->idle_counters);
+		// colliders that left their boxes this step (a few: otherwise the chain above has run): new boxes, new pairs appended to the kept list
+		if (incremental)
+			NH_LAUNCH(ctx, "reinsert", k_reinsert, 256, 256, st, nbox, sbox, cell_start, large_list, fbox, ctx->fat_gen, ctx->fat_esc_mark, ctx->fat_esc_list, ctx->fat_moved_list,
+			          ctx->collide_seq, kept, kept_cap);
+		// this step's pairs: the kept ones whose exact AABBs overlap now (every step)
+		NH_LAUNCH(ctx, "kept_filter", k_kept_filter, nh_grid_for(kept_cap, 256, 1024), 256, st, kept, kept_cap, nbox, s.aabb_min, s.aabb_max, s.pairs, pair_cap, s.coarse_parent, ctx->step_parity, bodies->idle_counters,
+		          (seeded_sort && !ctx->env_no_sort_reuse) ? 1u : 0u, incremental ? ctx->fat_gen : (const uint8_t*)nullptr);
+	}
+	// coarse islands over the broadphase pairs (united where the pairs were emitted) + connections: only when some body is asleep (a device
+	// flag: the kernels leave at once otherwise)
+	if (!no_islands && body_connections && body_connections->count)
+		NH_LAUNCH(ctx, "uf_union_connections", k_uf_union_connections, nh_grid_for(body_connections->count, 256, 512), 256, st, body_connections->data, body_connections->count, s.coarse_parent, ctx->step_parity, bodies->idle_counters);
+	if (!no_islands) NH_LAUNCH(ctx, "coarse_flatten", k_uf_flatten, nh_grid_for(B, 256, 512), 256, st, ctx->step_parity, B, s.coarse_parent, bodies->idle_counters, s.coarse_active, s.coarse_root);
+	// box-box pairs and pairs with a sphere are separate lists (emit_pair): one launch each, each running one kind of arithmetic.
+	// (the host does not know the counts: a launch over a list that turns out empty costs a few microseconds, so the launch for a
+	// shape the world does not contain is skipped outright)
+	if (nbox >= 2)
+		NH_LAUNCH(ctx, "narrowphase", (k_narrowphase<false, false>), nh_grid_for(pair_cap, 256, 4096), 256, st, s.pairs, s.xf, s.ctag,
+		          colliders->boxes.data, colliders->spheres.data, nbox, ctx->raw_data, ctx->raw_feature, pair_cap, c.cap, ctx->sort_keys_by_position, ctx->rec, s.rec_idx_a,
+		          s.coarse_root, s.coarse_active, ctx->step_parity, ctx->first_ghost);
+	if (nsph)
+		NH_LAUNCH(ctx, "narrowphase_sph", (k_narrowphase<true, false>), nh_grid_for(pair_cap, 256, 8192), 256, st, s.pairs, s.xf, s.ctag,
+		          colliders->boxes.data, colliders->spheres.data, nbox, ctx->raw_data, ctx->raw_feature, pair_cap, c.cap, ctx->sort_keys_by_position, ctx->rec, s.rec_idx_a,
+		          s.coarse_root, s.coarse_active, ctx->step_parity, ctx->first_ghost);
+}
+
+// islands over contact records (+ user connections), the active list, the records of sleeping sets filtered out: a chain of small kernels that the tag sort
+// of the records does not depend on -- it runs on the side stream while the caller's stream sorts (`fork`: forked here, joined by full_order_contacts)
+static int full_islands(nh_context* ctx, const CollideCall& c, const CollideScratch& s, bool fork) {
+	nh_DevState* st = ctx->d_state;
+	const nh_BodyData* bodies = c.bodies; const nh_BodyConnections* body_connections = c.body_connections; nh_ActiveBodies* active_bodies = c.active_bodies;
+	const uint32_t B = c.B, pair_cap = s.pair_cap; const bool no_islands = c.no_islands;
 	hipStream_t main_stream = ctx->stream;
 	if (fork) {
 		NH_HIP_CHECK(ctx, hipEventRecord(ctx->ev_fork, main_stream));
@@ -2454,26 +2395,31 @@ static int collide_impl(nh_context* ctx, nh_ActiveBodies* active_bodies, nh_Cont
 	}
 	if (!no_islands) {
 		if (body_connections && body_connections->count)
-			NH_LAUNCH(ctx, "uf_union_connections", k_uf_union_connections, nh_grid_for(body_connections->count, 256, 2048), 256, st, body_connections->data, body_connections->count, parent, ctx->step_parity, bodies->idle_counters);
-		NH_LAUNCH(ctx, "uf_union_records", k_uf_union_records, nh_grid_for(pair_cap, 256, 2048), 256, st, rec, parent, ctx->step_parity, bodies->idle_counters);
-		NH_LAUNCH(ctx, "uf_flatten", k_uf_flatten, nh_grid_for(B, 256, 2048), 256, st, ctx->step_parity, B, parent, bodies->idle_counters, set_active, root_of);
-		NH_LAUNCH(ctx, "active_flags", k_active_flags, nh_grid_for(B, 256, 2048), 256, st, ctx->step_parity, B, root_of, set_active, flags);
+			NH_LAUNCH(ctx, "uf_union_connections", k_uf_union_connections, nh_grid_for(body_connections->count, 256, 2048), 256, st, body_connections->data, body_connections->count, s.parent, ctx->step_parity, bodies->idle_counters);
+		NH_LAUNCH(ctx, "uf_union_records", k_uf_union_records, nh_grid_for(pair_cap, 256, 2048), 256, st, ctx->rec, s.parent, ctx->step_parity, bodies->idle_counters);
+		NH_LAUNCH(ctx, "uf_flatten", k_uf_flatten, nh_grid_for(B, 256, 2048), 256, st, ctx->step_parity, B, s.parent, bodies->idle_counters, s.set_active, s.root_of);
+		NH_LAUNCH(ctx, "active_flags", k_active_flags, nh_grid_for(B, 256, 2048), 256, st, ctx->step_parity, B, s.root_of, s.set_active, s.flags);
 		// number of bodies is known on the host: reuse the device-count scan with a constant count of 0 + extra
-		nh_scan_u32(ctx, flags, flags, &st->pad0 /* always 0 */, B, scan_tmp, &st->active, &st->any_idle[ctx->step_parity]);    // (skipped on the device when nobody sleeps)
+		nh_scan_u32(ctx, s.flags, s.flags, &st->pad0 /* always 0 */, B, s.scan_tmp, &st->active, &st->any_idle[ctx->step_parity]);    // (skipped on the device when nobody sleeps)
 	}
 	// (nobody asleep -- known on the device, or already on the host: the active list is 1 .. B-1, written without looking at any set)
-	NH_LAUNCH(ctx, "active_write", k_active_write, nh_grid_for(B, 256, 2048), 256, st, B, root_of, set_active, flags, active_bodies->indices, active_bodies->capacity, ctx->step_parity, no_islands ? 1u : 0u, block_top, begin_grid);
+	NH_LAUNCH(ctx, "active_write", k_active_write, nh_grid_for(B, 256, 2048), 256, st, B, s.root_of, s.set_active, s.flags, active_bodies->indices, active_bodies->capacity, ctx->step_parity, no_islands ? 1u : 0u, s.block_top, s.begin_grid);
 	// (what a gravity call on the side stream waits for; NH_FLAG_FUSED_STEP never takes that road, and an event on the stream is a bubble of a few microseconds)
 	if (ctx->side && !(ctx->flags & NH_FLAG_FUSED_STEP)) NH_HIP_CHECK(ctx, hipEventRecord(ctx->ev_active, ctx->stream));         // (ctx->stream is the side stream inside a fork)
-	if (!no_islands) NH_LAUNCH(ctx, "filter_records", k_filter_records, nh_grid_for(pair_cap, 256, 2048), 256, st, rec, root_of, set_active, ctx->step_parity);
+	if (!no_islands) NH_LAUNCH(ctx, "filter_records", k_filter_records, nh_grid_for(pair_cap, 256, 2048), 256, st, ctx->rec, s.root_of, s.set_active, ctx->step_parity);
 	if (fork) {
 		ctx->stream = main_stream;
 		NH_HIP_CHECK(ctx, hipEventRecord(ctx->ev_join, ctx->side));
 	}
-	// tag order: sort records by (b_tag, a_tag), then lay contacts out pair by pair
-	int key_bits = (int)ctx->tag_bits;
-	if (key_bits < 1) key_bits = 1;
-	if (key_bits > 32) key_bits = 32;
+	return NH_OK;
+}
+
+// tag order: sort records by (b_tag, a_tag), then lay contacts out pair by pair
+static int full_order_contacts(nh_context* ctx, const CollideCall& c, const CollideScratch& s, bool seeded_sort, bool fork) {
+	nh_DevState* st = ctx->d_state;
+	const uint32_t pair_cap = s.pair_cap;
+	uint64_t* rec_key_a = ctx->sort_keys_by_position; uint64_t* rec_key_b = s.rec_key_b; uint32_t* rec_idx_a = s.rec_idx_a; uint32_t* rec_idx_b = s.rec_idx_b;
+	int key_bits = (int)ctx->tag_bits; if (key_bits < 1) key_bits = 1; if (key_bits > 32) key_bits = 32;
 	// keys are a | b<<32: sort the low field, then the high field (stable) -- dropped records carry ~0 and end up last
 	// Sort re-use.  The record keys live in a context buffer indexed by record position; k_narrowphase has compared every key with what that position
 	// held last step.  When nothing differs (and the record count is the same) the order the last sort left in the context's buffers still holds: the four
@@ -2481,161 +2427,100 @@ static int collide_impl(nh_context* ctx, nh_ActiveBodies* active_bodies, nh_Cont
 	const uint64_t* sorted_keys = rec_key_a;
 	const uint32_t* sorted_idx = rec_idx_a;
 	if (seeded_sort) {
-		nh_bucket_sort_u64_u32(ctx, rec_key_a, rec_key_b, rec_idx_a, rec_idx_b, pair_cap, sort_place, key_bits, ctx->sort_sorted_keys, ctx->sort_sorted_idx);
+		nh_bucket_sort_u64_u32(ctx, rec_key_a, rec_key_b, rec_idx_a, rec_idx_b, pair_cap, s.sort_place, key_bits, ctx->sort_sorted_keys, ctx->sort_sorted_idx);
 		sorted_keys = ctx->sort_sorted_keys; sorted_idx = ctx->sort_sorted_idx;
-	} else if (nh_onesweep_u64_u32_two_fields(ctx, rec_key_a, rec_key_b, rec_idx_a, rec_idx_b, &st->records, pair_cap, ctx->h_state->records, sort_scratch, key_bits)) {
+	} else if (nh_onesweep_u64_u32_two_fields(ctx, rec_key_a, rec_key_b, rec_idx_a, rec_idx_b, &st->records, pair_cap, ctx->h_state->records, s.sort_scratch, key_bits)) {
 		uint64_t* t = rec_key_a; rec_key_a = rec_key_b; rec_key_b = t; uint32_t* u = rec_idx_a; rec_idx_a = rec_idx_b; rec_idx_b = u;
 	}
 	// (dropped records carry count 0, so where they land in the order is irrelevant)
 	if (!seeded_sort) { sorted_keys = rec_key_a; sorted_idx = rec_idx_a; }         // (the radix passes leave the result in whichever buffer they ended in)
 	if (!seeded_sort) { nh_bucket_sort_seed(ctx, rec_key_a, pair_cap); ctx->sort_seeded = true; }
-	if (fork) NH_HIP_CHECK(ctx, hipStreamWaitEvent(main_stream, ctx->ev_join, 0));
-	NH_LAUNCH(ctx, "sorted_counts", k_sorted_counts, nh_grid_for(pair_cap, 256, 2048), 256, st, sorted_idx, rec, rec_counts, sleep_flags, seeded_sort ? 1u : 0u, ctx->lay_rank);
+	if (fork) NH_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
+	NH_LAUNCH(ctx, "sorted_counts", k_sorted_counts, nh_grid_for(pair_cap, 256, 2048), 256, st, sorted_idx, ctx->rec, ctx->cnt_sorted, s.sleep_flags, seeded_sort ? 1u : 0u, ctx->lay_rank);
 	// contact starts and sleeping-pair slots: two scans over the sorted records in one pair of launches
-	nh_scan2_u32(ctx, rec_counts, ctx->start_sorted, &st->contacts, sleep_flags, sleep_flags, &st->sleeping, &st->records, 1, scan_tmp);
-	NH_LAUNCH(ctx, "gather_contacts", k_gather_contacts, nh_grid_for(pair_cap, 256, 8192), 256, st, sorted_idx, rec, sorted_keys, ctx->start_sorted, raw_data, raw_feature,
-	          contacts->data, contacts->bodies, contacts->tags, contacts->features, cap, pair_cap, sleep_flags, contacts->sleeping_pairs, ctx->deg, B,
+	nh_scan2_u32(ctx, ctx->cnt_sorted, ctx->start_sorted, &st->contacts, s.sleep_flags, s.sleep_flags, &st->sleeping, &st->records, 1, s.scan_tmp);
+	NH_LAUNCH(ctx, "gather_contacts", k_gather_contacts, nh_grid_for(pair_cap, 256, 8192), 256, st, sorted_idx, ctx->rec, sorted_keys, ctx->start_sorted, ctx->raw_data, ctx->raw_feature,
+	          c.contacts->data, c.contacts->bodies, c.contacts->tags, c.contacts->features, c.cap, pair_cap, s.sleep_flags, c.contacts->sleeping_pairs, ctx->deg, c.B,
 	          ctx->dense_slot, seeded_sort ? 1u : 0u, 0u);
+	return NH_OK;
+}
 
+static int full_step(nh_context* ctx, const CollideCall& c, const CollideScratch& s, const CollideMode& m) {
+	nh_DevState* st = ctx->d_state;
+	// (nh_step: a still step whose verdict has not been looked at yet must have happened before anything is built on it)
+	if (ctx->still.verdict.pending) { const int v = nh_still_verdict_now(ctx); if (v) return v == 2 ? NH_ERR_HIP : NH_INTERNAL_STILL_FAILED; }
+	ctx->still.pair_ready = false; ctx->still.pair_step = false; ctx->still.early_verdict = false; ctx->still.pair_world_bad = false; ctx->still.pair_world_ok = false; ctx->still.pair_listed = 0u; ctx->still.pair_owned_seq = 0u;          // (another layout: whether every kept pair is some body's own is found out again)
+	// The solver reads the caller's cache arrays and this nh_collide lays the dense contact list out -- whatever still steps kept by slot goes home first
+	{ int rc = nh_still_export_cache(ctx); if (rc) return rc; }
+	ctx->still.ahead_ready = false; ctx->still.ahead_plain = false; ctx->still.own_current = false;          // (a full step writes the arena's arrays, not own_*)
+	if (!c.no_islands) ctx->still.ahead_map_ok = false;          // (sleepers ahead: the static world's share of the scene bounds holds the sleepers' -- and who sleeps may change in a full step)
+	ctx->still.contacts_stale = false; ctx->still.slots_current = false; ctx->still.views_sleepers = false; ctx->still.appended_pairs = false;          // (a full step writes the contact list, the sleeping pairs and the active list itself)
+	NH_LAUNCH(ctx, "collide_begin", k_collide_begin, s.begin_grid, 256, st, c.C, c.B, s.parent, s.set_active, ctx->deg, c.bodies->idle_counters, ctx->step_parity, s.coarse_parent, s.coarse_active, c.no_islands ? 1u : 0u, s.block_top,
+	          m.drop_kept ? 1u : 0u, m.drop_sort_order ? 1u : 0u);
+	const bool seeded_sort = ctx->sort_seeded && !ctx->env_sort_radix;      // (NH_SORT_RADIX=1: radix passes every step)
+	if (c.C) full_find_contacts(ctx, c, s, m, seeded_sort);
+	// (the side stream only while its chain is small: the radix passes spin-wait on each other and must not share the machine with a long
+	// kernel -- with millions of records in one island the union-find alone takes a millisecond)
+	const bool fork = !c.no_islands && ctx->side != nullptr && (seeded_sort || ctx->h_state->records <= 1500000u);
+	{ int rc = full_islands(ctx, c, s, fork); if (rc) return rc; }
+	{ int rc = full_order_contacts(ctx, c, s, seeded_sort, fork); if (rc) return rc; }
 	if (ctx->flags & NH_FLAG_SYNC_COUNTS) {
-		nh_Counts c;
-		int rc = nh_read_counts(ctx, &c);
-		if (rc) return rc;
-		contacts->count = c.contacts;
-		contacts->sleeping_count = c.sleeping_pairs;
-		active_bodies->count = c.active_bodies;
-		if (c.error) return (int)c.error;
+		nh_Counts n;
+		{ int rc = nh_read_counts(ctx, &n); if (rc) return rc; }
+		c.contacts->count = n.contacts; c.contacts->sleeping_count = n.sleeping_pairs; c.active_bodies->count = n.active_bodies;
+		if (n.error) return (int)n.error;
 	}
 	ctx->gravity_may_overlap = ctx->side != nullptr;       // until any other entry point enqueues work
 	ctx->after_collide = true;
 	return NH_OK;
 }
 
-// ---- contacts appended by the caller after nh_collide -----------------------------------------------------------------------------------------------
-// The reference lets its caller append contacts between collide() and read_cached_impulses() ("Custom contacts can be added here",
-// example/main.cpp:287): they simply take part in the tag sort of read_cached_impulses (nudge.cpp:4027-4044) and everything downstream walks the
-// sorted order.  Here the list nh_collide returns is already IN tag order and carries per-body bookkeeping counted while it was laid out (degrees,
-// pair counts, first contact), so appended contacts are merged into that order and the bookkeeping is counted again -- a slow path, paid only by
-// the steps that use it: one pass over all contacts.
-__device__ __forceinline__ bool app_less(uint64_t ta, uint32_t fa, uint64_t tb, uint32_t fb) { return ta < tb || (ta == tb && fa < fb); }
-
-// rank of every appended contact among the appended ones (ties: position), and the sorted keys
-// (every k_app_* kernel leaves at once when the merged list would not fit the caller's arrays: k_app_count reports NH_ERR_CONTACT_CAPACITY and nothing is written out of bounds)
-__global__ __launch_bounds__(256) void k_app_rank(const nh_DevState* __restrict__ st, uint32_t extra, const uint64_t* __restrict__ tags, const uint32_t* __restrict__ features,
-                                                  uint32_t* __restrict__ rank, uint64_t* __restrict__ skey, uint32_t* __restrict__ sfeat, uint32_t capacity) {
-	const uint32_t K = st->contacts;
-	if ((uint64_t)K + extra > capacity) return;
-	for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < extra; j += gridDim.x * blockDim.x) {
-		const uint64_t t = tags[K + j]; const uint32_t f = features[K + j];
-		uint32_t r = 0;
-		for (uint32_t i = 0; i < extra; ++i) {
-			const uint64_t ti = tags[K + i]; const uint32_t fi = features[K + i];
-			r += (app_less(ti, fi, t, f) || (ti == t && fi == f && i < j)) ? 1u : 0u;
-		}
-		rank[j] = r; skey[r] = t; sfeat[r] = f;
-	}
-}
-
-// new position of every contact: an old one moves up by the appended ones that sort before it, an appended one lands behind the old ones with a key <= its own
-__global__ __launch_bounds__(256) void k_app_positions(const nh_DevState* __restrict__ st, uint32_t extra, const uint64_t* __restrict__ tags, const uint32_t* __restrict__ features,
-                                                       const uint32_t* __restrict__ rank, const uint64_t* __restrict__ skey, const uint32_t* __restrict__ sfeat, uint32_t* __restrict__ pos, uint32_t capacity) {
-	const uint32_t K = st->contacts;
-	if ((uint64_t)K + extra > capacity) return;
-	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < K + extra; i += gridDim.x * blockDim.x) {
-		const uint64_t t = tags[i]; const uint32_t f = features[i];
-		if (i < K) {
-			uint32_t lo = 0, hi = extra;                         // appended contacts with a key < (t, f)
-			while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (app_less(skey[mid], sfeat[mid], t, f)) lo = mid + 1u; else hi = mid; }
-			pos[i] = i + lo;
-		} else {
-			uint32_t lo = 0, hi = K;                             // old contacts with a key <= (t, f)
-			while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (!app_less(t, f, tags[mid], features[mid])) lo = mid + 1u; else hi = mid; }
-			pos[i] = rank[i - K] + lo;
-		}
-	}
-}
-
-__global__ __launch_bounds__(256) void k_app_copy(const nh_DevState* __restrict__ st, uint32_t extra, const nh_Contact* __restrict__ data, const nh_BodyPair* __restrict__ bodies,
-                                                  const uint64_t* __restrict__ tags, const uint32_t* __restrict__ features, float4* __restrict__ t_data, nh_BodyPair* __restrict__ t_bodies,
-                                                  uint64_t* __restrict__ t_tags, uint32_t* __restrict__ t_features, uint32_t capacity) {
-	if ((uint64_t)st->contacts + extra > capacity) return;
-	const uint32_t n = st->contacts + extra;
-	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-		t_data[2 * (size_t)i] = reinterpret_cast<const float4*>(data + i)[0]; t_data[2 * (size_t)i + 1] = reinterpret_cast<const float4*>(data + i)[1];
-		t_bodies[i] = bodies[i]; t_tags[i] = tags[i]; t_features[i] = features[i];
-	}
-}
-
-__global__ __launch_bounds__(256) void k_app_scatter(const nh_DevState* __restrict__ st, uint32_t extra, const uint32_t* __restrict__ pos, const float4* __restrict__ t_data,
-                                                     const nh_BodyPair* __restrict__ t_bodies, const uint64_t* __restrict__ t_tags, const uint32_t* __restrict__ t_features,
-                                                     nh_Contact* __restrict__ data, nh_BodyPair* __restrict__ bodies, uint64_t* __restrict__ tags, uint32_t* __restrict__ features, uint32_t capacity) {
-	if ((uint64_t)st->contacts + extra > capacity) return;
-	const uint32_t n = st->contacts + extra;
-	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-		const uint32_t p = pos[i];
-		reinterpret_cast<float4*>(data + p)[0] = t_data[2 * (size_t)i]; reinterpret_cast<float4*>(data + p)[1] = t_data[2 * (size_t)i + 1];
-		bodies[p] = t_bodies[i]; tags[p] = t_tags[i]; features[p] = t_features[i];
-	}
-}
-
-// the per-body bookkeeping of k_gather_contacts, from the merged list: a run of equal tags AND equal bodies is one collider pair (appended contacts may share a tag --
-// the reference only sorts by it -- while naming different bodies: each such stretch is a pair of its own for its two bodies)
-__global__ __launch_bounds__(256) void k_app_recount(nh_DevState* __restrict__ st, uint32_t extra, const nh_BodyPair* __restrict__ bodies, const uint64_t* __restrict__ tags,
-                                                     uint32_t* __restrict__ deg, uint32_t nbodies, uint32_t capacity) {
-	if ((uint64_t)st->contacts + extra > capacity) return;
-	unsigned long long* __restrict__ pair_counter = reinterpret_cast<unsigned long long*>(deg + 2u * NH_DEG_STRIDE(nbodies));
-	uint32_t* __restrict__ first_contact = deg + 4u * NH_DEG_STRIDE(nbodies);
-	const uint32_t n = st->contacts + extra;
-	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-		const nh_BodyPair p = bodies[i];
-		if (i > 0 && tags[i - 1] == tags[i] && bodies[i - 1].a == p.a && bodies[i - 1].b == p.b) continue;          // not the head of its run
-		const uint64_t t = tags[i];
-		uint32_t len = 1;
-		while (i + len < n && tags[i + len] == t && bodies[i + len].a == p.a && bodies[i + len].b == p.b) ++len;
-		if (p.a) { atomicAdd(&pair_counter[p.a], (unsigned long long)len | ((unsigned long long)(p.b ? 0x10001u : 1u) << 32)); first_contact[p.a] = i | 0x80000000u; }
-		if (p.b) { atomicAdd(&pair_counter[p.b], (unsigned long long)len | ((unsigned long long)(p.a ? 0x10001u : 1u) << 32)); first_contact[p.b] = i; }
-	}
-}
-
-__global__ void k_app_count(nh_DevState* st, uint32_t extra, uint32_t capacity) {
-	if (st->contacts + extra > capacity) st->error = NH_ERR_CONTACT_CAPACITY; else st->contacts += extra;
-}
-
-extern "C" int nh_append_contacts(nh_context* ctx, nh_ContactData* contacts, const nh_BodyData* bodies, uint32_t extra, uint32_t* positions, nh_Arena temporary) {
-	if (!ctx || !contacts || !bodies) return NH_ERR_INVALID;
-	if (!extra) return NH_OK;
-	if (extra > 65536u || extra > contacts->capacity) return NH_ERR_INVALID;      // (the appended contacts are ranked against each other by comparison: a slow path for a handful)
-	if (ctx->setup_seq == ctx->collide_seq || !ctx->deg) return NH_ERR_STALE_SETUP;      // after nh_collide, before nh_read_cached_impulses / nh_setup_contact_constraints
-	{ int rc = nh_flush_pending(ctx); if (rc) return rc; }
-	{ int rc = nh_still_sync_outputs(ctx); if (rc) return rc; }
-	ctx->still.appended = true; ctx->still.ok_next = false;
-	nh_DevState* st = ctx->d_state;
-	const uint32_t cap = contacts->capacity, B = bodies->count;
-	int err = NH_OK;
-	uint32_t* rank = nh_arena_array<uint32_t>(&temporary, extra, &err);
-	uint64_t* skey = nh_arena_array<uint64_t>(&temporary, extra, &err);
-	uint32_t* sfeat = nh_arena_array<uint32_t>(&temporary, extra, &err);
-	uint32_t* pos = positions ? positions : nh_arena_array<uint32_t>(&temporary, cap, &err);
-	float4* t_data = nh_arena_array<float4>(&temporary, 2 * (size_t)cap, &err);
-	nh_BodyPair* t_bodies = nh_arena_array<nh_BodyPair>(&temporary, cap, &err);
-	uint64_t* t_tags = nh_arena_array<uint64_t>(&temporary, cap, &err);
-	uint32_t* t_features = nh_arena_array<uint32_t>(&temporary, cap, &err);
-	if (err) return err;
-	if ((ctx->flags & NH_FLAG_SYNC_COUNTS) && (uint64_t)contacts->count + extra > cap) return NH_ERR_CONTACT_CAPACITY;
-	NH_LAUNCH(ctx, "append_rank", k_app_rank, nh_grid_for(extra, 256, 1024), 256, st, extra, contacts->tags, contacts->features, rank, skey, sfeat, cap);
-	NH_LAUNCH(ctx, "append_positions", k_app_positions, nh_grid_for(cap, 256, 2048), 256, st, extra, contacts->tags, contacts->features, rank, skey, sfeat, pos, cap);
-	NH_LAUNCH(ctx, "append_copy", k_app_copy, nh_grid_for(cap, 256, 2048), 256, st, extra, contacts->data, contacts->bodies, contacts->tags, contacts->features, t_data, t_bodies, t_tags, t_features, cap);
-	NH_LAUNCH(ctx, "append_scatter", k_app_scatter, nh_grid_for(cap, 256, 2048), 256, st, extra, pos, t_data, t_bodies, t_tags, t_features, contacts->data, contacts->bodies, contacts->tags, contacts->features, cap);
-	// degrees, pair info, first contact: counted again
-	NH_HIP_CHECK(ctx, hipMemsetAsync(ctx->deg, 0, sizeof(uint32_t) * NH_DEG_WORDS(B), ctx->stream));
-	NH_LAUNCH(ctx, "append_recount", k_app_recount, nh_grid_for(cap, 256, 2048), 256, st, extra, contacts->bodies, contacts->tags, ctx->deg, B, cap);
-	NH_LAUNCH(ctx, "append_count", k_app_count, 1, 1, st, extra, cap);
-	if (ctx->flags & NH_FLAG_SYNC_COUNTS) {
-		nh_Counts c;
-		int rc = nh_read_counts(ctx, &c);
-		if (rc) return rc;
-		if (c.error) return (int)c.error;
-		contacts->count = c.contacts;
-	}
+static int collide_impl(nh_context* ctx, nh_ActiveBodies* active_bodies, nh_ContactData* contacts, const nh_BodyData* bodies, const nh_ColliderData* colliders,
+                        const nh_BodyConnections* body_connections, nh_Arena temporary, bool want_still) {
+	ctx->adv.done = false;
+	ctx->step_parity ^= 1u;
+	ctx->collide_seq++;
+	ctx->collide_mark = ctx->advance_count;
+	CollideCall c = { active_bodies, contacts, bodies, colliders, body_connections };
+	// can anybody be asleep?  (counters rise by at most one per nh_advance since the nh_collide that measured them)
+	c.no_islands = ctx->idle_bound >= 0 && (uint64_t)ctx->idle_bound + (ctx->advance_count - ctx->idle_bound_mark) < 0xffu;
+	ctx->islands_skipped = c.no_islands;
+	ctx->idle_unknown = false;                   // this call looks at the counters as they are now (k_collide_begin): its maximum may be adopted again
+	c.nbox = colliders->boxes.count; c.nsph = colliders->spheres.count; c.C = c.nbox + c.nsph; c.B = bodies->count; c.cap = contacts->capacity;
+	ctx->body_count = c.B;
+	CollideScratch s;
+	{ int rc = carve_scratch(ctx, c, temporary, &s); if (rc) return rc; }
+	CollideMode m = {};
+	m.drop_sort_order = ctx->env_no_sort_reuse;
+	// per body the contact degree, the pair info (collider pairs it is in | pairs with a dynamic partner << 16) and the first contact of its last pair -- written
+	// while the contacts are laid out, consumed by setup (layout: NH_DEG_STRIDE in nh_internal.h)
+	{ int rc = reserve_one(ctx, &ctx->deg, &ctx->deg_capacity, (uint32_t)NH_DEG_WORDS(c.B), sizeof(uint32_t) * NH_DEG_WORDS(c.B)); if (rc) return rc; }
+	{ int rc = reserve_sort(ctx, s.pair_cap, &m.drop_sort_order); if (rc) return rc; }
+	m.bp_direct = broadphase_direct(ctx);
+	{ int rc = reserve_kept(ctx, c, s, &m.drop_kept); if (rc) return rc; }
+	// re-insertion of colliders that leave their boxes (k_reinsert): kept-list steps only, indices that leave room for the stamps
+	m.incremental = !m.bp_direct && !ctx->env_no_incremental && c.C < (1u << NH_GEN_SHIFT);
+	bool lay_fresh = false;
+	{ int rc = reserve_pair_layout(ctx, s.pair_cap, c.cap, &lay_fresh); if (rc) return rc; }
+	{ int rc = reserve_body_layout(ctx, c.B, &lay_fresh); if (rc) return rc; }
+	nh_StillStep& ss = ctx->still;
+	if (lay_fresh) { ss.slots_current = false; ss.ok_next = false; }
+	if (!same_colliders(*colliders, ss.lay_colliders)) ss.ahead_world_bad = false;          // (other colliders: whether bodies carry several of them is found out again)
+	ss.lay_bodies = *bodies; ss.lay_colliders = *colliders; ss.lay_contacts = *contacts; ss.lay_active = active_bodies->indices; ss.lay_active_capacity = active_bodies->capacity;
+	ss.appended = false;
+	// A still step?  SLEEPERS form (nh_internal.h): somebody may be asleep (the host cannot rule it out) -- bodies asleep in sets of their own are the step's business,
+	// without user connections (they join sets: nudge.cpp:3511-3575) and with the per-body notes the views are made of
+	const bool may_sleep = !c.no_islands;
+	const bool sleepers_ok = !ss.no_local && !(body_connections && body_connections->count);
+	if (may_sleep && sleepers_ok) { int rc = reserve_one(ctx, &ctx->still_awake, &ctx->still_awake_capacity, c.B, (size_t)c.B + 64u); if (rc) return rc; }          // (who is awake, per body: k_xform<true>)
+	const bool still = want_still && (c.no_islands || sleepers_ok) && !m.bp_direct && !m.drop_kept && !m.drop_sort_order && !lay_fresh && ctx->sort_seeded && !ctx->env_sort_radix &&
+	                   !ctx->env_no_sort_reuse && c.C != 0u;
+	if (!still) return full_step(ctx, c, s, m);
+	{ int rc = reserve_own(ctx, c.C); if (rc) return rc; }
+	const StillForm f = still_decide(ctx, c, m);
+	{ int rc = still_launch(ctx, c, s, m, f); if (rc) return rc; }
+	ss.active = true; ss.resolved = false; ss.launched++;
+	ctx->gravity_may_overlap = false;
+	ctx->after_collide = true;
 	return NH_OK;
 }

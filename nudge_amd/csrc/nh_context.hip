@@ -101,32 +101,12 @@ extern "C" void nh_destroy(nh_context* ctx) {
 		if (ss.staged) hipEventDestroy(ss.staged);
 		for (int k = 0; k < NH_STREAM_MAX_SLOTS; ++k) if (ss.landed[k]) hipEventDestroy(ss.landed[k]);
 	}
-	if (ctx->asleep.aabb_min) hipFree(ctx->asleep.aabb_min);
-	if (ctx->asleep.aabb_max) hipFree(ctx->asleep.aabb_max);
-	if (ctx->asleep.tags) hipFree(ctx->asleep.tags);
-	if (ctx->hint) hipFree(ctx->hint);
-	if (ctx->deg) hipFree(ctx->deg);
-	if (ctx->fat_pairs) hipFree(ctx->fat_pairs);
-	if (ctx->fat_box) hipFree(ctx->fat_box);
-	if (ctx->grid_sbox) hipFree(ctx->grid_sbox);
-	if (ctx->grid_skeys) hipFree(ctx->grid_skeys);
-	if (ctx->grid_cstart) hipFree(ctx->grid_cstart);
-	if (ctx->grid_counts) hipFree(ctx->grid_counts);
-	if (ctx->grid_large) hipFree(ctx->grid_large);
-	if (ctx->fat_gen) hipFree(ctx->fat_gen);
-	if (ctx->fat_esc_mark) hipFree(ctx->fat_esc_mark);
-	if (ctx->fat_esc_list) hipFree(ctx->fat_esc_list);
-	if (ctx->fat_moved_list) hipFree(ctx->fat_moved_list);
-	if (ctx->sort_keys_by_position) hipFree(ctx->sort_keys_by_position);
-	if (ctx->sort_sorted_keys) hipFree(ctx->sort_sorted_keys);
-	if (ctx->sort_sorted_idx) hipFree(ctx->sort_sorted_idx);
-	if (ctx->sort_splitters) hipFree(ctx->sort_splitters);
-	if (ctx->sort_counts) hipFree(ctx->sort_counts);
-	if (ctx->sort_starts) hipFree(ctx->sort_starts);
 	for (int k = 0; k < 2; ++k) { if (ctx->still.h_ring[k]) hipHostFree(ctx->still.h_ring[k]); if (ctx->still.ev_ring[k]) hipEventDestroy(ctx->still.ev_ring[k]); }
 	nh_query_free(ctx);
 	{
-		void* bufs[] = { ctx->raw_data, ctx->raw_feature, ctx->rec, ctx->lay_rank, ctx->cnt_sorted, ctx->start_sorted, ctx->dense_slot, ctx->sc_imp, ctx->sc_feat, ctx->sc_count, ctx->sc_undo, ctx->pair_mark, ctx->pair_list, ctx->exp_cnt, ctx->exp_start,
+		void* bufs[] = { ctx->asleep.aabb_min, ctx->asleep.aabb_max, ctx->asleep.tags, ctx->hint, ctx->deg, ctx->fat_pairs, ctx->fat_box, ctx->grid_sbox, ctx->grid_skeys, ctx->grid_cstart, ctx->grid_counts, ctx->grid_large, ctx->fat_gen,
+		                 ctx->fat_esc_mark, ctx->fat_esc_list, ctx->fat_moved_list, ctx->sort_keys_by_position, ctx->sort_sorted_keys, ctx->sort_sorted_idx, ctx->sort_splitters, ctx->sort_counts, ctx->sort_starts,
+		                 ctx->raw_data, ctx->raw_feature, ctx->rec, ctx->lay_rank, ctx->cnt_sorted, ctx->start_sorted, ctx->dense_slot, ctx->sc_imp, ctx->sc_feat, ctx->sc_count, ctx->sc_undo, ctx->pair_mark, ctx->pair_list, ctx->exp_cnt, ctx->exp_start,
 		                 ctx->exp_scan_tmp, ctx->still_delta, ctx->lay_class, ctx->lay_simple, ctx->body_rec, ctx->body_pos, ctx->still_awake, ctx->exp_sleep_a, ctx->exp_sleep_b, ctx->exp_sleep_hist, ctx->exp_flags,
 		                 ctx->own_xf, ctx->own_aabb_min, ctx->own_aabb_max, ctx->own_ctag, ctx->body_col };
 		for (void* b : bufs) if (b) hipFree(b);
@@ -278,9 +258,8 @@ extern "C" int nh_stream_state(nh_context* ctx, const nh_BodyData* bodies, uint3
 	if (every == 0u) return NH_OK;
 	if (!bodies || !bodies->transforms || !host_ring || count == 0u || count > bodies->count || slots == 0u || slots > NH_STREAM_MAX_SLOTS || !ctx->side) return NH_ERR_INVALID;
 	if (ss.stage_capacity < count) {
-		if (ss.stage) NH_HIP_CHECK(ctx, hipFree(ss.stage));
-		ss.stage = nullptr; ss.stage_capacity = 0;
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&ss.stage, sizeof(nh_Transform) * (size_t)count));
+		ss.stage_capacity = 0;
+		{ int rc = nh_device_buffers(ctx, { { &ss.stage, sizeof(nh_Transform) * (size_t)count } }); if (rc) return rc; }
 		ss.stage_capacity = count;
 	}
 	if (!ss.staged) NH_HIP_CHECK(ctx, hipEventCreateWithFlags(&ss.staged, hipEventDisableTiming));

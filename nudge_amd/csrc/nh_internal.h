@@ -70,7 +70,7 @@ struct nh_DevState {
 	uint32_t fat_rebuilds;                // broadphase rebuilds since nh_create (the steps in between re-used the kept pair list: below)
 	uint32_t sort_reuses;                 // steps since nh_create whose record sort was skipped because last step's tag order still held
 	uint32_t fat_inserts;                 // colliders re-inserted into the kept pair list since nh_create (they left their inflated box; no rebuild)
-	// "still" steps (nh_collide.hip, "9. still steps"): a step the host launched speculatively as a world whose contact layout is last step's
+	// "still" steps (nh_collide.hip, "11. still steps"): a step the host launched speculatively as a world whose contact layout is last step's
 	uint32_t still_failed_seq;            // the latest still step (its nh_collide's sequence number) that met something that is NOT as it was -- a collider left its box, a body is
 	                                      // asleep, a collider pair changed its key or has more than four contacts or a partner the solver lane does not know, body 0 not inert:
 	                                      // the solver of that step, and of every still step launched behind it before the host has looked, leaves without touching anything;
@@ -95,7 +95,7 @@ struct nh_DevState {
 	float fat_margin;                     // inflation of the boxes a rebuild writes this step (k_grid_setup -> k_cell_keys)
 	uint32_t fat_count_sph;               // kept pairs with a sphere (they fill the kept buffer from the back; fat_count counts the box-box ones)
 	uint32_t fat_hits, fat_hits_prev;     // kept pairs that overlapped in this / the last k_kept_filter pass
-	// incremental insertion (nh_collide.hip, "7. re-insertion"): a few colliders left their boxes -- they get new boxes, their old pairs die (generation
+	// incremental insertion (nh_collide.hip, "6. re-insertion"): a few colliders left their boxes -- they get new boxes, their old pairs die (generation
 	// stamps) and their new pairs are appended; the grid of the last rebuild keeps serving everybody who has not moved since
 	uint32_t esc_count;                   // this step: colliders that left their box and were given a new one (k_xform)
 	uint32_t moved_count;                 // colliders re-inserted at least once since the last rebuild (their grid entry is stale: the `moved` list)
@@ -131,11 +131,11 @@ struct nh_DevState {
 	uint32_t still_smin[2][3], still_smax[2][3];   // by step parity: scene bounds of a still step (k_xform<true>; cleared for the next step by the step before)
 	uint32_t asleep_failed;                // k_asleep_check (nh_step, asleep steps): something is not what it was when the world went to sleep
 	uint32_t still_top[2];        // by step parity: largest idle counter a still step saw
-	// still steps with movers (nh_collide.hip, "9. still steps", LOCAL speculation): colliders that left their inflated boxes in a still step are given new boxes and
+	// still steps with movers (nh_collide.hip, "11. still steps", LOCAL speculation): colliders that left their inflated boxes in a still step are given new boxes and
 	// re-inserted into the kept pair list by the step itself (k_xform<true> with stamps, k_reinsert in still mode) instead of failing it
 	uint32_t still_esc[2];        // by step parity: colliders a still step re-boxed (the esc_count of a full step; cleared for the next step by the step before)
 	uint32_t still_fat0;          // kept pairs (both kinds) when this still step began: what k_reinsert's "crowded" verdict is taken from (the list grows while it runs)
-	// still steps with SLEEPERS (nh_collide.hip, "9. still steps", LOCAL speculation): by step parity, what a still step in sleepers form counted -- bodies asleep, their
+	// still steps with SLEEPERS (nh_collide.hip, "11. still steps", LOCAL speculation): by step parity, what a still step in sleepers form counted -- bodies asleep, their
 	// collider pairs (the step's sleeping pairs), the cache entries kept aside for them; the solver turns them into the step's counters (active / sleeping / culled)
 	uint32_t still_asleep[2], still_sleeping[2], still_culled[2];
 	// (the narrowphase's share -- sleeping pairs, entries kept aside -- arrives in NH_SLEEP_PARTS places per parity: four thousand workgroups on ONE address queued for
@@ -201,7 +201,7 @@ struct nh_BlkBuffers {
 	unsigned long long* prof; uint32_t prof_calls;       // NH_BLK_PROFILE=1: wall-clock readings of the sweep workgroups (8 launches x NH_BLK_MAX_BLOCKS x 4), printed now and then
 };
 
-// ---- still steps (nh_collide.hip, "9. still steps") --------------------------------------------------------------------------------------------------
+// ---- still steps (nh_collide.hip, "11. still steps") --------------------------------------------------------------------------------------------------
 // A world at rest on static geometry repeats itself: the same pairs at the same places of the kept pair list, the same contacts in the same order, every body
 // with its one contact-list record, the contact cache = last step's contact list.  Everything a step does to FIND that out again -- grid chain, pair filter,
 // tag sort, scans, contact gather, adjacency, cache merge: two dozen launches, most of them leaving at once -- is then skipped by the HOST, which launches
@@ -503,7 +503,7 @@ NH_LOCAL void nh_run_cull(nh_context* ctx, nh_ContactImpulseData* d, uint32_t sl
 NH_LOCAL void nh_materialize_lookup(nh_context* ctx, nh_ContactImpulseData* d, const nh_BodyPair* bodies = nullptr, const uint8_t* body_class = nullptr, const uint32_t* general_list = nullptr, uint32_t general = 0u);          // nh_cache.hip
 #define NH_INTERNAL_STILL_FAILED (-1000)      // (never leaves the library) first_apply -> nh_step: the still step before this one failed, run both again
 #define NH_DELTA_MAX 256u
-#define NH_GEN_SHIFT 24u             // kept pairs carry the generation stamps of their two colliders above the 24-bit collider index (nh_collide.hip, "7. re-insertion")
+#define NH_GEN_SHIFT 24u             // kept pairs carry the generation stamps of their two colliders above the 24-bit collider index (nh_collide.hip, "6. re-insertion")
 #define NH_GEN_INDEX 0xFFFFFFu
 #define NH_BODY_REC_NONE 0xFFFFFFFFu
 #define NH_BODY_REC_IS_A 0x80000000u
@@ -622,6 +622,17 @@ void nh_timer_collect(nh_context* ctx);
 		hipError_t e_ = (expr);                                                                  \
 		if (e_ != hipSuccess) { (ctx)->last_hip_error = (int)e_; return NH_ERR_HIP; }            \
 	} while (0)
+
+// ---- library-owned device buffers that grow with the world (nh_util.hip) ------------------------------
+// The buffers of one growth branch, replaced together: every non-null *ptr is freed and nulled, then every entry with bytes != 0 is allocated, then those that
+// ask for it are zero-filled on ctx->stream.  NH_OK, or NH_ERR_HIP (last_hip_error set) with every pointer null or valid.  The caller tests its capacity, zeroes
+// it, calls this and then sets the new capacity and its flags: a call that failed is made again, whole, by the next step.  Growth branches only -- hipFree waits
+// for the device.
+struct nh_DeviceBuffer {
+	void** ptr; size_t bytes; bool zero;
+	template<class T> nh_DeviceBuffer(T** p, size_t n, bool z = false) : ptr((void**)p), bytes(n), zero(z) {}
+};
+NH_LOCAL int nh_device_buffers(nh_context* ctx, std::initializer_list<nh_DeviceBuffer> buffers);
 
 // layout of ctx->deg (32-bit words, S = NH_DEG_STRIDE(bodies)): [0, S) contact degree per body (k_adj_simple writes it out of the counters below: the CSR
 // scan reads it); [S, 2S) fill cursors of the CSR build (zero until then); [2S, 4S) one 64-bit counter per body, bumped ONCE per collider pair while the

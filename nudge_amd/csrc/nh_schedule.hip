@@ -300,9 +300,8 @@ extern "C" int nh_setup_contact_constraints(nh_context* ctx, const nh_ActiveBodi
 	          d->body_class, bodies->properties, bodies->momentum, d->simple, ctx->body_rec, ctx->body_pos, ctx->sort_seeded ? ctx->sort_sorted_idx : (const uint32_t*)nullptr);
 	if (ctx->hint_capacity < B) {
 		// library-owned, persistent across steps: per body, where its contacts started in the previous step's list (warm-start hint)
-		if (ctx->hint) NH_HIP_CHECK(ctx, hipFree(ctx->hint));
-		ctx->hint = nullptr; ctx->hint_capacity = 0;
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->hint, sizeof(uint32_t) * (size_t)B));
+		ctx->hint_capacity = 0;
+		{ int rc = nh_device_buffers(ctx, { { &ctx->hint, sizeof(uint32_t) * (size_t)B } }); if (rc) return rc; }
 		NH_HIP_CHECK(ctx, hipMemsetAsync(ctx->hint, 0xFF, sizeof(uint32_t) * (size_t)B, ctx->stream));
 		ctx->hint_capacity = B;
 	}

@@ -2018,23 +2018,14 @@ static int blk_reserve(nh_context* ctx, uint32_t B, uint32_t kcap) {
 		k.tables = true;
 	}
 	if (k.body_capacity < B + 1u) {
-		if (k.brank) hipFree(k.brank);
-		if (k.bm) hipFree(k.bm);
-		if (k.pos_body) hipFree(k.pos_body);
-		if (k.touch) hipFree(k.touch);
-		k.brank = nullptr; k.bm = nullptr; k.pos_body = nullptr; k.touch = nullptr; k.body_capacity = 0;
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&k.brank, sizeof(uint2) * (size_t)(B + 1u)));
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&k.bm, sizeof(float4) * 2u * (size_t)(B + 1u)));
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&k.pos_body, sizeof(uint32_t) * (size_t)(B + 1u)));
-		if (k.check) NH_HIP_CHECK(ctx, hipMalloc((void**)&k.touch, sizeof(uint32_t) * 2u * (size_t)(B + 1u)));
+		k.body_capacity = 0;
+		{ int rc = nh_device_buffers(ctx, { { &k.brank, sizeof(uint2) * (size_t)(B + 1u) }, { &k.bm, sizeof(float4) * 2u * (size_t)(B + 1u) }, { &k.pos_body, sizeof(uint32_t) * (size_t)(B + 1u) },
+		                                    { &k.touch, k.check ? sizeof(uint32_t) * 2u * (size_t)(B + 1u) : 0u } }); if (rc) return rc; }          // (touch: only under the ownership check)
 		k.body_capacity = B + 1u;
 	}
 	if (k.contact_capacity < kcap) {
-		if (k.lpair) hipFree(k.lpair);
-		if (k.ghost_list) hipFree(k.ghost_list);
-		k.lpair = nullptr; k.ghost_list = nullptr; k.contact_capacity = 0;
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&k.lpair, sizeof(uint32_t) * (size_t)kcap));
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&k.ghost_list, sizeof(uint32_t) * (size_t)kcap));
+		k.contact_capacity = 0;
+		{ int rc = nh_device_buffers(ctx, { { &k.lpair, sizeof(uint32_t) * (size_t)kcap }, { &k.ghost_list, sizeof(uint32_t) * (size_t)kcap } }); if (rc) return rc; }
 		k.contact_capacity = kcap;
 	}
 	return NH_OK;

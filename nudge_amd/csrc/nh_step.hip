@@ -51,12 +51,9 @@ static int still_view_sleepers(nh_context* ctx, uint32_t what) {
 		const uint32_t P = ctx->lay_capacity;
 		if (ss.lay_contacts.sleeping_pairs) {
 			if (ctx->exp_sleep_capacity < P) {
-				void** bufs[] = { (void**)&ctx->exp_sleep_a, (void**)&ctx->exp_sleep_b, (void**)&ctx->exp_sleep_hist };
-				for (void** b : bufs) { if (*b) NH_HIP_CHECK(ctx, hipFree(*b)); *b = nullptr; }
 				ctx->exp_sleep_capacity = 0;
-				NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->exp_sleep_a, sizeof(uint64_t) * (size_t)P + 64u));
-				NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->exp_sleep_b, sizeof(uint64_t) * (size_t)P + 64u));
-				NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->exp_sleep_hist, sizeof(uint32_t) * (256u * NH_SORT_GRID + 512u)));
+				{ int rc = nh_device_buffers(ctx, { { &ctx->exp_sleep_a, sizeof(uint64_t) * (size_t)P + 64u }, { &ctx->exp_sleep_b, sizeof(uint64_t) * (size_t)P + 64u },
+				                                    { &ctx->exp_sleep_hist, sizeof(uint32_t) * (256u * NH_SORT_GRID + 512u) } }); if (rc) return rc; }
 				ctx->exp_sleep_capacity = P;
 			}
 			NH_LAUNCH(ctx, "view_sleep_keys", k_view_sleep_keys, nh_grid_for(P, 256, 2048), 256, st, ctx->rec, ctx->sort_keys_by_position, ctx->exp_sleep_a);
@@ -71,9 +68,8 @@ static int still_view_sleepers(nh_context* ctx, uint32_t what) {
 	if ((what & NH_VIEW_ACTIVE) && ss.lay_active && ctx->still_awake) {
 		const uint32_t B = ss.lay_bodies.count;
 		if (ctx->exp_flags_capacity < B + 2u) {
-			if (ctx->exp_flags) NH_HIP_CHECK(ctx, hipFree(ctx->exp_flags));
-			ctx->exp_flags = nullptr; ctx->exp_flags_capacity = 0;
-			NH_HIP_CHECK(ctx, hipMalloc((void**)&ctx->exp_flags, sizeof(uint32_t) * ((size_t)B + 66u)));
+			ctx->exp_flags_capacity = 0;
+			{ int rc = nh_device_buffers(ctx, { { &ctx->exp_flags, sizeof(uint32_t) * ((size_t)B + 66u) } }); if (rc) return rc; }
 			ctx->exp_flags_capacity = B + 2u;
 		}
 		NH_LAUNCH(ctx, "view_awake_flags", k_view_awake_flags, nh_grid_for(B, 256, 2048), 256, ctx->still_awake, B, ctx->exp_flags);

@@ -836,3 +836,11 @@ void nh_scan2_u32(nh_context* ctx, const uint32_t* in_a, uint32_t* out_a, uint32
 	NH_LAUNCH(ctx, "scan_sums", sc_sums, RS_G, 256, in_a, in_b, d_count, extra, tmp, (const uint32_t*)nullptr);
 	NH_LAUNCH(ctx, "scan_final", sc_final, RS_G, 256, in_a, out_a, in_b, out_b, d_count, extra, tmp, d_total_a, d_total_b, (const uint32_t*)nullptr);
 }
+
+// ---- library-owned device buffers (nh_internal.h) ---------------------------------------------------------
+int nh_device_buffers(nh_context* ctx, std::initializer_list<nh_DeviceBuffer> buffers) {
+	for (const nh_DeviceBuffer& b : buffers) if (*b.ptr) { void* old = *b.ptr; *b.ptr = nullptr; NH_HIP_CHECK(ctx, hipFree(old)); }          // (nulled first: a free that fails is never tried again)
+	for (const nh_DeviceBuffer& b : buffers) if (b.bytes) NH_HIP_CHECK(ctx, hipMalloc(b.ptr, b.bytes));
+	for (const nh_DeviceBuffer& b : buffers) if (b.zero && b.bytes) NH_HIP_CHECK(ctx, hipMemsetAsync(*b.ptr, 0, b.bytes, ctx->stream));
+	return NH_OK;
+}

@@ -1,4 +1,4 @@
-"""What a few moving bodies cost a large world at rest, with and without re-insertion into the kept pair list (nh_collide.hip, "7. re-insertion").
+"""What a few moving bodies cost a large world at rest, with and without re-insertion into the kept pair list (nh_collide.hip, "6. re-insertion").
 The 1,004,400-box drop scene of bench.py, landed.  "hop": every 12 steps K boxes are kicked (untimed) and hop across their neighbours -- they leave their
 inflated boxes for a few steps, then rest again.  "fly": K boxes are thrown up once and are in the air for the whole window -- each of them leaves its box on
 EVERY step.  Timed: 96 steps (between the kicks).  Three broadphase modes: default (leavers re-inserted), NH_NO_INCREMENTAL=1 (a leaver

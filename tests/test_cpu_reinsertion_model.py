@@ -1,4 +1,4 @@
-"""The ALGORITHM of the kept pair list with re-insertion (nudge_amd/csrc/nh_collide.hip, "6. kept pairs", "7. re-insertion"), restated in numpy and checked
+"""The ALGORITHM of the kept pair list with re-insertion (nudge_amd/csrc/nh_collide.hip, "6. re-insertion", "7. kept pairs"), restated in numpy and checked
 against a brute-force overlap test on random motion -- no GPU.  The kernels are tested on the device (tests/test_gpu_parity.py, test_gpu_atsize.py); this file
 pins the reasoning they rest on:
   * boxes are inflated by a margin and sorted into a uniform grid by the cell of their min corner; a box is "small" iff it spans at most two cells per axis,

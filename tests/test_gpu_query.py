@@ -220,7 +220,14 @@ def _query(w, rays_t, hits_t):
     w.raycast_records(rays_t, any_hit=True, hits=hits_t)
 
 
-def _same_stepped_world(a, b, what):
+# what nh_read_counts reports of a context's history, not of its last step: tallies over its whole life, and the large colliders of the broadphase's last grid --
+# built whenever this context last had to (a context that rebuilt eight steps in a row searches directly for a while: same pairs, another grid)
+BY_HISTORY = ("large_colliders", "broadphase_rebuilds", "sort_reuses", "broadphase_inserts", "still_steps", "still_replays", "still_diff_key", "still_diff_count", "still_diff_feature",
+           "still_diff_escape", "asleep_steps", "ahead_steps", "fused_steps", "pair_steps", "pair_diag_roles", "pair_diag_record", "pair_diag_scale", "pair_diag_owned")
+
+
+def _same_stepped_world(a, b, what, history=True):
+    """history=False: for two contexts of different age, which can only agree about the last step."""
     ba, bb = a.get_bodies(), b.get_bodies()
     assert P.bits_equal(ba["transforms"], bb["transforms"]) and P.bits_equal(ba["momentum"], bb["momentum"]) and np.array_equal(ba["idle"], bb["idle"]), what
     a.export_views(E.NH_VIEW_ALL)
@@ -231,7 +238,10 @@ def _same_stepped_world(a, b, what):
     ca, cb = a.get_cache(), b.get_cache()
     assert ca["count"] == cb["count"] and ca["data"].tobytes() == cb["data"].tobytes() and np.array_equal(ca["tags"], cb["tags"]), what
     assert np.array_equal(a.get_active(), b.get_active()), what
-    assert a.counts() == b.counts(), (what, a.counts(), b.counts())
+    na, nb = a.counts(), b.counts()
+    if not history:
+        na, nb = ({k: v for k, v in n.items() if k not in BY_HISTORY} for n in (na, nb))
+    assert na == nb, (what, na, nb)
 
 
 OBSERVED = {"pile": lambda: S.pile(256, 0, seed=1), "grid_tiles": lambda: S.grid_tiles(2, side=20, seed=2)}
