@@ -23,7 +23,7 @@
 #include "nh_solver.h"
 #include "nh_narrowphase.h"          // (PAIR AHEAD: the still solver's lanes evaluate their bodies' own collider pairs for the next sub-step)
 
-// ---- gravity + damping over the active list (example/main.cpp:290-305) -------------------------------------
+// ---- 1. gravity + damping over the active list (example/main.cpp:290-305) -------------------------------------
 __global__ __launch_bounds__(256) void k_gravity(const nh_DevState* __restrict__ st, const uint32_t* __restrict__ active, nh_BodyMomentum* __restrict__ momentum,
                                                  float gx_dt, float gy_dt, float gz_dt, float damping) {
 	uint32_t n = st->active;
@@ -35,7 +35,7 @@ __global__ __launch_bounds__(256) void k_gravity(const nh_DevState* __restrict__
 	}
 }
 
-// ---- advance (nudge.cpp:4886-4926) ----------------------------------------------------------------------------
+// ---- 2. advance (nudge.cpp:4886-4926) ----------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_advance(const nh_DevState* __restrict__ st, const uint32_t* __restrict__ active, nh_Transform* __restrict__ xf,
                                                  const nh_BodyMomentum* __restrict__ momentum, uint8_t* __restrict__ idle, float time_step) {
 	uint32_t n = st->active;
@@ -77,7 +77,7 @@ __global__ __launch_bounds__(256) void k_advance_rest(const nh_DevState* __restr
 	}
 }
 
-// ---- setup: per-body adjacency in solver order -------------------------------------------------------------------
+// ---- 3. setup: per-body adjacency in solver order -------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_zero_u32(uint32_t* __restrict__ p, uint32_t n) {
 	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) p[i] = 0;
 }
@@ -241,7 +241,7 @@ __global__ __launch_bounds__(256) void k_contact_class(nh_DevState* __restrict__
 	}
 }
 
-// ---- body state access -------------------------------------------------------------------------------------------------
+// ---- 4. body state access -------------------------------------------------------------------------------------------------
 __device__ __forceinline__ nh_vel load_vel(const nh_BodyMomentum* __restrict__ momentum, const nh_BodyProperties* __restrict__ props, uint32_t i) {
 	nh_BodyMomentum m = momentum[i];
 	nh_vel v;
@@ -280,7 +280,7 @@ __device__ __forceinline__ void load_row(const float* __restrict__ rows, uint32_
 	for (int k = 0; k < 10; ++k) dst[k] = src[k];
 }
 
-// ---- one-body fast path: setup (rows + warm start) ----------------------------------------------------------------------
+// ---- 5. one-body fast path: setup (rows + warm start) ----------------------------------------------------------------------
 template<bool STORE>
 __global__ __launch_bounds__(256) void k_setup_static(uint32_t nbodies, const uint8_t* __restrict__ body_class, const uint32_t* __restrict__ off, const uint32_t* __restrict__ adj,
                                                       const nh_Contact* __restrict__ contacts, const nh_BodyPair* __restrict__ bodies, nh_CachedContactImpulse* __restrict__ cached,
@@ -345,7 +345,7 @@ __global__ __launch_bounds__(256) void k_setup_static(uint32_t nbodies, const ui
 	}
 }
 
-// ---- one-body fast path: `iterations` PGS sweeps ---------------------------------------------------------------------------
+// ---- 6. one-body fast path: `iterations` PGS sweeps ---------------------------------------------------------------------------
 // MAXC > 0: the body's <= MAXC constraint rows stay in registers across all iterations (160 B each): every row is
 // read from HBM once per call, not once per iteration.  MAXC == 0: any contact count, rows re-read per iteration.
 // FUSED: the call also does what nh_setup_contact_constraints deferred for these bodies -- fetch the cached impulse of every
@@ -484,7 +484,7 @@ __global__ __launch_bounds__(256) void k_apply_static(uint32_t nbodies, const ui
 	}
 }
 
-// ---- one-body fast path, inert static world (the usual case): one-body forms of nh_solver.h ---------------------------------
+// ---- 7. one-body fast path, inert static world (the usual case): one-body forms of nh_solver.h ---------------------------------
 // Same contract as k_apply_static<MAXC, FUSED>, for MAXC in {4, 8}; rows are the 27-float nh_row1.
 //
 // Warm-start lookup (FUSED).  The cache is last step's contact list (plus culled entries), sorted like this step's, so a
@@ -1246,7 +1246,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MAXC ==
 	} while (x < rounded);
 }
 
-// ---- level-scheduled path ------------------------------------------------------------------------------------------------------
+// ---- 8. level-scheduled path ------------------------------------------------------------------------------------------------------
 // one atomicAdd / atomicMax per workgroup (same-address atomics cost ~12 ns each on this chip)
 __device__ __forceinline__ void block_report(nh_DevState* st, uint32_t left, uint32_t lmax, uint32_t round) {
 	// progress counters alternate between rounds; each round clears the counter of the next one (nobody touches it meanwhile)
@@ -1438,7 +1438,7 @@ __global__ __launch_bounds__(256) void k_colour_settle(nh_DevState* __restrict__
 	block_report(st, left, lmax, round);
 }
 
-// ---- small general sets: the whole colouring and the level order in ONE workgroup -------------------------------------------------------------
+// ---- 9. small general sets: the whole colouring and the level order in ONE workgroup -------------------------------------------------------------
 // Seeds, try / settle rounds, level histogram, offsets and the scatter into level order are seven kinds of launches and, between the rounds, one host
 // round trip each (the host asks whether anybody is still uncoloured).  For a few thousand contacts the round trips ARE the cost (the sample
 // application's pile: 0.37 of its 1.0 ms step).  One 1024-thread workgroup does all of it with __syncthreads() between the phases; same rules as the
@@ -1619,7 +1619,7 @@ __global__ __launch_bounds__(256) void k_level_scatter(const nh_DevState* __rest
 	}
 }
 
-// ---- general contacts: everything per contact lives in LEVEL ORDER (position k in level_order) ------------------------------------
+// ---- 10. general contacts: everything per contact lives in LEVEL ORDER (position k in level_order) ------------------------------------
 // rows as structure-of-float4 (chunk q of contact k at rows4[q * stride + k]: a wave's ten row loads are ten contiguous
 // kilobytes), the body pair, the solver state.  The sweeps then stream rows / pairs / states and only gather the two momentum
 // records (32 B each; mass_inverse rides in momentum.unused0 like in the reference, nudge.cpp:4198 -- k_adj_sort put it there).
@@ -1739,7 +1739,7 @@ __global__ __launch_bounds__(256) void k_level_exec(const uint32_t* __restrict__
 	}
 }
 
-// ---- small general sets: ONE workgroup, constraint rows resident in LDS across the warm start and all sweeps ------------------------------------
+// ---- 11. small general sets: ONE workgroup, constraint rows resident in LDS across the warm start and all sweeps ------------------------------------
 // The level / colour schedule needs a synchronisation between consecutive levels.  Across workgroups that is a kernel boundary (a device-wide
 // barrier costs more than one on this part); inside ONE workgroup it is __syncthreads().  So when the whole general set fits one compute unit's
 // LDS -- 704 rows of 160 B (or 1792 radial rows of 48 B), their states and body pairs: 155 KB of the 160 KB -- one workgroup loads the rows ONCE and walks
@@ -1809,9 +1809,7 @@ __global__ __launch_bounds__(NH_RES_THREADS) void k_solve_resident(const nh_DevS
 	for (uint32_t k = threadIdx.x; k < G; k += NH_RES_THREADS) gstates[k] = s_state[k];
 }
 
-// ---- update_cached_impulses (nudge.cpp:4857-4884) --------------------------------------------------------------------------------
-// (contacts on the one-body fast path export their impulse at the end of every nh_apply_impulses call)
-// ---- mid-size general sets in small worlds: ONE workgroup, every body's momentum resident in LDS ------------------------------------------------
+// ---- 12. mid-size general sets in small worlds: ONE workgroup, every body's momentum resident in LDS ------------------------------------------------
 // When the rows do not fit one compute unit's LDS (k_solve_resident) but the WORLD is small -- at most NH_RESB_MAX_BODIES bodies: the sample
 // application's 1536-body pile -- the other half of the per-sweep traffic does: one workgroup keeps the momentum of every body in LDS (32 B each) for
 // the warm start and all sweeps, streams rows, pairs and states from L2, and separates levels with __syncthreads() instead of kernel boundaries.
@@ -1905,6 +1903,8 @@ __global__ __launch_bounds__(NH_RESB_THREADS) void k_solve_resident_bodies(const
 	}
 }
 
+// ---- 13. update_cached_impulses (nudge.cpp:4857-4884) --------------------------------------------------------------------------------
+// (contacts on the one-body fast path export their impulse at the end of every nh_apply_impulses call)
 __global__ __launch_bounds__(256) void k_update_impulses(const nh_DevState* __restrict__ st, const uint32_t* __restrict__ order, const float4* __restrict__ rows4, size_t stride,
                                                          const float4* __restrict__ gstates, nh_CachedContactImpulse* __restrict__ out, const uint32_t* __restrict__ colour,
                                                          const uint2* __restrict__ gpair, uint32_t packed_end = 0u) {
@@ -1934,7 +1934,7 @@ __global__ __launch_bounds__(256) void k_update_impulses(const nh_DevState* __re
 
 #include "nh_blocks.h"
 
-// =====================================================================================================================================
+// ---- 14. host side: gravity / damping and the integrator ------------------------------------------------------------------------------------------------
 extern "C" int nh_apply_gravity_damping(nh_context* ctx, const nh_ActiveBodies* active_bodies, const nh_BodyData* bodies,
                                         float time_step, const float gravity[3], float damping_rate) {
 	if (!ctx || !active_bodies || !bodies || !gravity) return NH_ERR_INVALID;
@@ -1985,9 +1985,6 @@ extern "C" int nh_advance(nh_context* ctx, const nh_ActiveBodies* active_bodies,
 	return ctx->stream_state.every ? nh_stream_after_advance(ctx) : NH_OK;
 }
 
-// The part of setup_contact_constraints that needs the device counters on the host: general adjacency for bodies k_adj_simple left
-// pending, culling when something sleeps, the >8-contact one-body class, and the level-scheduled path (colouring / levels, rows,
-// warm start).  Runs once per setup, with ctx->pending already cleared.
 // CSR adjacency (body_off[] offsets, adj[] lists) -- needed by every kernel but the speculative one-body launch
 static void ensure_csr(nh_context* ctx, nh_ContactConstraintData* d) {
 	if (d->csr_ready) return;
@@ -1997,7 +1994,7 @@ static void ensure_csr(nh_context* ctx, nh_ContactConstraintData* d) {
 	NH_LAUNCH(ctx, "adjacency_from_simple", k_adj_from_simple, nh_grid_for(B, 256, 4096), 256, B, d->body_class, d->body_off, d->simple, d->adj);
 }
 
-// ---- spatially blocked solver (nh_blocks.h): host side ---------------------------------------------------------------------------------------------
+// ---- 15. spatially blocked solver (nh_blocks.h): host side ---------------------------------------------------------------------------------------------
 static int blk_reserve(nh_context* ctx, uint32_t B, uint32_t kcap) {
 	nh_BlkBuffers& k = ctx->blk;
 	if (!k.tables) {
@@ -2216,6 +2213,56 @@ static void blk_run(nh_context* ctx, nh_ContactConstraintData* d, const nh_BodyD
 	NH_LAUNCH(ctx, "blk_scatter_back", k_blk_scatter_back, nh_grid_for(B, 256, 4096), 256, B, k.brank, k.own_base, (const float4*)k.bm, (float4*)bodies->momentum);
 }
 
+// ---- 16. solver launches: one argument list per kernel ------------------------------------------------------------------------------------------------------
+// k_solve_one_body: what differs from one launch to the next (the rest of its argument list is the setup's).  `side`: untimed, on that stream -- the halo
+// split's boundary launch; otherwise on ctx->stream, as NH_LAUNCH does it
+struct nh_OneBodyLaunch { const nh_Contact* contacts; uint32_t cls_a, cls_b, flags; const uint2* simple; const nh_FusedStep& fs; const nh_StillView& sv; const nh_AheadView& av; };
+template<int MAXC, bool FUSED, bool CONTIG = false, int NW = 4, bool STILL = false, bool AHEAD = false, bool PAIR = false, bool PART = false>
+static void launch_one_body(nh_context* ctx, const char* name, uint32_t grid, nh_ContactConstraintData* d, const nh_BodyData* bodies, uint32_t iterations, const nh_CacheView& cv,
+                            const nh_OneBodyLaunch& v, hipStream_t side = nullptr) {
+	const bool timed = !side && ctx->timing;
+	if (timed) nh_timer_begin(ctx, name);
+	hipLaunchKernelGGL((k_solve_one_body<MAXC, FUSED, CONTIG, NW, STILL, AHEAD, PAIR, PART>), dim3(grid), dim3(64 * NW), 0, side ? side : ctx->stream, d->body_count, d->body_class, d->body_off, d->adj, d->bodies,
+	                   bodies->properties, bodies->momentum, (float4*)d->states, iterations, v.contacts, bodies->transforms, d->impulses, cv, ctx->hint, v.cls_a, v.cls_b, v.flags, v.simple, v.fs, v.sv, v.av);
+	if (timed) nh_timer_end(ctx);
+}
+// k_apply_static: the one-body classes when body 0 is not inert (MAXC 4 / 8), and the class with more than 8 static contacts (MAXC 0)
+template<int MAXC, bool FUSED>
+static void launch_static(nh_context* ctx, const char* name, nh_ContactConstraintData* d, const nh_BodyData* bodies, uint32_t iterations, const nh_CacheView& cv, uint32_t cls_a, uint32_t cls_b) {
+	NH_LAUNCH(ctx, name, (k_apply_static<MAXC, FUSED>), nh_grid_for(d->body_count, 256, 8192), 256, d->body_count, d->body_class, d->body_off, d->adj, d->bodies, bodies->properties, bodies->momentum,
+	          d->rows, (float4*)d->states, iterations, d->contact_data, bodies->transforms, d->impulses, cv, cls_a, cls_b);
+}
+// A small general set solved by ONE workgroup: its rows resident in LDS (k_solve_resident, d->resident) or every body's momentum (k_solve_resident_bodies).
+// `levels` 0: on the device (st->levels, behind k_colour_small); `warm_impulses`: the warm start's, with `warm` = 1 and no sweeps
+static void launch_resident(nh_context* ctx, nh_ContactConstraintData* d, const nh_BodyData* bodies, uint32_t levels, const nh_CachedContactImpulse* warm_impulses, uint32_t iterations, uint32_t warm) {
+	if (d->resident)
+		NH_LAUNCH(ctx, "solve_resident", k_solve_resident, 1, NH_RES_THREADS, ctx->d_state, d->cont.level_hist, levels, d->level_order, d->gpair, warm_impulses,
+		          bodies->momentum, (const float4*)d->rows, (size_t)d->contact_capacity, d->gstates, iterations, warm, d->resident_cap);
+	else
+		NH_LAUNCH(ctx, "solve_resident_bodies", k_solve_resident_bodies, 1, NH_RESB_THREADS, ctx->d_state, d->cont.level_hist, d->cont.level_hist + (NH_MAX_LEVELS + 2), levels, d->level_order, d->gpair,
+		          warm_impulses, bodies->momentum, d->body_count, (const float4*)d->rows, (size_t)d->contact_capacity, d->gstates, iterations, warm);
+}
+// one pass over the levels in order (they are numbered from 1): the warm start, or one sweep
+template<bool WARM>
+static void launch_levels(nh_context* ctx, nh_ContactConstraintData* d, const nh_BodyData* bodies, const nh_CachedContactImpulse* impulses) {
+	for (uint32_t l = 1; l <= d->levels; ++l) {
+		uint32_t b = d->level_off[l], e = d->level_off[l + 1];
+		if (e > b && !d->level_full[l])
+			NH_LAUNCH(ctx, WARM ? "warm_level" : "apply_level", (k_level_exec<WARM, true>), nh_grid_for(e - b, 256, 8192), 256, d->level_order, b, e, d->gpair, impulses, bodies->momentum, (const float4*)d->rows, (size_t)d->contact_capacity, d->gstates);
+		else if (e > b)
+			NH_LAUNCH(ctx, WARM ? "warm_level" : "apply_level", (k_level_exec<WARM>), nh_grid_for(e - b, 256, 4096), 256, d->level_order, b, e, d->gpair, impulses, bodies->momentum, (const float4*)d->rows, (size_t)d->contact_capacity, d->gstates);
+	}
+}
+static void launch_rows_general(nh_context* ctx, nh_ContactConstraintData* d, uint32_t G, uint32_t coloured) {          // (`coloured`: d->cont.level holds colours, not the exact order's levels)
+	NH_LAUNCH(ctx, "rows_general", k_rows_general, nh_grid_for(G, 256, 4096), 256, ctx->d_state, d->level_order, d->cont.contacts.data, d->cont.contacts.bodies, d->bodies_at_setup.transforms, d->bodies_at_setup.properties, (float4*)d->rows, (size_t)d->contact_capacity,
+	          d->gpair, coloured, d->static_inert ? 1u : 0u, d->cont.level, d->cont.level_hist + (NH_MAX_LEVELS + 2), (const nh_CachedContactImpulse*)nullptr, (float4*)nullptr, (uint32_t*)nullptr, 0u);
+}
+static nh_FusedStep fused_gravity(const nh_context* ctx) {          // NH_FLAG_FUSED_STEP: the pending gravity / damping, as the fused solver applies it when it loads a body
+	nh_FusedStep fs = nh_FusedStep();
+	fs.gx_dt = ctx->grav.gx_dt; fs.gy_dt = ctx->grav.gy_dt; fs.gz_dt = ctx->grav.gz_dt; fs.damping = ctx->grav.damping; fs.time_step = ctx->grav.time_step;
+	return fs;
+}
+
 // EARLY COUNTERS (nh_internal.h): the counters the launch numbered `seq` left in the pinned block as it started.  The host polls the word behind them; should the stream run dry
 // without it (a launch that never happened) the ordinary copy answers instead -- nothing can hang here that could not hang in hipStreamSynchronize
 static int read_counts_early(nh_context* ctx, nh_Counts* out, uint32_t seq) {
@@ -2239,258 +2286,363 @@ static int read_counts_early(nh_context* ctx, nh_Counts* out, uint32_t seq) {
 	return NH_OK;
 }
 
-static int finish_setup(nh_context* ctx, nh_ContactConstraintData* d) {
-	nh_DevState* st = ctx->d_state;
-	const nh_ContactData* contacts = &d->cont.contacts;
-	const nh_BodyData* bodies = &d->bodies_at_setup;
-	nh_ContactImpulseData* imp = d->imp;
-	const uint32_t kcap = d->contact_capacity, B = d->body_count;
-	uint32_t* pred_a = d->cont.pred_a; uint32_t* pred_b = d->cont.pred_b; uint32_t* level = d->cont.level;
-	uint32_t* slot_key = d->cont.slot_key; uint32_t* level_hist = d->cont.level_hist; uint32_t* level_cursor = d->cont.level_cursor;
-	uint32_t* general_list = d->general_list;
-	// one round trip: body classes, whether anything sleeps, whether the general adjacency build has work
-	// (early counters, nh_internal.h: the speculative one-body launch before this call has them on their way to the host as it STARTS -- the solver runs on while the host reads)
-	nh_Counts c;
-	int rc = d->early_seq ? read_counts_early(ctx, &c, d->early_seq) : nh_read_counts(ctx, &c);
+// ---- 17. finish_setup: the part of setup_contact_constraints that needs the device counters on the host -------------------------------------------------------
+static inline int counts_result(int rc, const nh_Counts& c) { return rc ? rc : (int)c.error; }
+// one round trip: body classes, whether anything sleeps, whether the general adjacency build has work
+// (early counters, nh_internal.h: the speculative one-body launch before this call has them on their way to the host as it STARTS -- the solver runs on while the host reads)
+static int setup_counts(nh_context* ctx, nh_ContactConstraintData* d, nh_Counts* c) {
+	const int rc = counts_result(d->early_seq ? read_counts_early(ctx, c, d->early_seq) : nh_read_counts(ctx, c), *c);
 	d->early_seq = 0u;
-	if (rc) return rc;
-	if (c.error) return (int)c.error;
-	d->has_late = ctx->h_state->has_pending != 0;
-	{
-		// may the NEXT step be launched as a still step?  (nh_internal.h: nh_StillStep)  This step laid its contacts out in a layout a still step can write through, every
-		// dynamic body sits in one pair with an inert static world (the fused solver owns them all), nothing sleeps, nothing was culled
-		const nh_DevState* h = ctx->h_state;
-		// (SLEEPERS form, nh_internal.h: sleeping pairs and kept-aside cache entries no longer rule the next step out -- as long as somebody is awake; a world in which
-		// nobody is belongs to the asleep steps below, which need full steps to get going)
-		const bool sleepers_ok = !ctx->still.no_local;
-		const bool nobody_sleeps = !h->any_sleeping && h->sleeping == 0u && h->culled == 0u;
-		ctx->still.ok_next = h->lay_valid && !h->has_unstable && h->static_inert && !h->has_pending && !h->has_static8 && !h->has_staticN && (nobody_sleeps || (sleepers_ok && h->active != 0u)) &&
-		                     h->general_contacts == 0u && !h->error;
-		// ... and nobody moved: a collider that left its inflated box in THIS step (re-inserted, or the kept list rebuilt) will most likely leave it again in the next
-		// one -- a body in the air does on every step -- and a still step that fails costs two steps' worth of launches
-		// (LOCAL speculation, nh_internal.h: a still step in movers form re-inserts its own leavers -- then only a REBUILD of the kept list, which also voids the
-		// layout, rules the next step out; a re-insertion switches the movers form on for the steps that follow)
-		const bool local = !ctx->still.no_local && !ctx->env_no_incremental && !ctx->env_no_fat;
-		if ((h->fat_inserts != ctx->still.seen_inserts && !local) || h->fat_rebuilds != ctx->still.seen_rebuilds) ctx->still.ok_next = false;
-		nh_still_note_movers(ctx, h);
-		// asleep steps (nh_internal.h: nh_AsleepState): was this step the fixed point of a world in which every body is asleep -- nobody active, no contact, every cache
-		// entry kept aside -- and the second one in a row with the same counts?  Then nh_step may take the steps that follow as done (after its own check)
-		nh_AsleepState& as = ctx->asleep;
-		const uint32_t pairs_now = h->pairs + h->pairs_sph;
-		// (the cache: entries of sleeping pairs are kept aside and written back, nudge.cpp:4064-4101, by kernels that run after this round trip -- what shows here is that
-		//  the count the LAST step left is the count it found, i.e. nothing but kept-aside entries was in it)
-		const bool fixed_point = h->active == 0u && h->contacts == 0u && h->general_contacts == 0u && !h->error && h->sleeping != 0u && !ctx->first_ghost;
-		if (fixed_point && as.streak && as.prev_pairs == pairs_now && as.prev_sleeping == h->sleeping && as.prev_cache == h->cache) as.streak++;
-		else as.streak = fixed_point ? 1u : 0u;
-		as.prev_pairs = pairs_now; as.prev_sleeping = h->sleeping; as.prev_cache = h->cache;
-		if (as.streak == 2u && !as.disabled) { as.B = d->body_count; if (nh_asleep_remember(ctx)) as.streak = 0; }
-	}
-	// NH_FLAG_FUSED_STEP: gravity / damping of the bodies the fused solver does not own, before anything else reads their momentum -- not launched
-	// at all when every body is the fused solver's (a landed drop scene)
+	if (!rc) d->has_late = ctx->h_state->has_pending != 0;
+	return rc;
+}
+static void outlook_for_next_step(nh_context* ctx, nh_ContactConstraintData* d) {
+	// may the NEXT step be launched as a still step?  (nh_internal.h: nh_StillStep)  This step laid its contacts out in a layout a still step can write through, every
+	// dynamic body sits in one pair with an inert static world (the fused solver owns them all), nothing sleeps, nothing was culled
+	const nh_DevState* h = ctx->h_state;
+	// (SLEEPERS form, nh_internal.h: sleeping pairs and kept-aside cache entries no longer rule the next step out -- as long as somebody is awake; a world in which
+	// nobody is belongs to the asleep steps below, which need full steps to get going)
+	const bool sleepers_ok = !ctx->still.no_local;
+	const bool nobody_sleeps = !h->any_sleeping && h->sleeping == 0u && h->culled == 0u;
+	ctx->still.ok_next = h->lay_valid && !h->has_unstable && h->static_inert && !h->has_pending && !h->has_static8 && !h->has_staticN && (nobody_sleeps || (sleepers_ok && h->active != 0u)) &&
+	                     h->general_contacts == 0u && !h->error;
+	// ... and nobody moved: a collider that left its inflated box in THIS step (re-inserted, or the kept list rebuilt) will most likely leave it again in the next
+	// one -- a body in the air does on every step -- and a still step that fails costs two steps' worth of launches
+	// (LOCAL speculation, nh_internal.h: a still step in movers form re-inserts its own leavers -- then only a REBUILD of the kept list, which also voids the
+	// layout, rules the next step out; a re-insertion switches the movers form on for the steps that follow)
+	const bool local = !ctx->still.no_local && !ctx->env_no_incremental && !ctx->env_no_fat;
+	if ((h->fat_inserts != ctx->still.seen_inserts && !local) || h->fat_rebuilds != ctx->still.seen_rebuilds) ctx->still.ok_next = false;
+	nh_still_note_movers(ctx, h);
+	// asleep steps (nh_internal.h: nh_AsleepState): was this step the fixed point of a world in which every body is asleep -- nobody active, no contact, every cache
+	// entry kept aside -- and the second one in a row with the same counts?  Then nh_step may take the steps that follow as done (after its own check)
+	nh_AsleepState& as = ctx->asleep;
+	const uint32_t pairs_now = h->pairs + h->pairs_sph;
+	// (the cache: entries of sleeping pairs are kept aside and written back, nudge.cpp:4064-4101, by kernels that run after this round trip -- what shows here is that
+	//  the count the LAST step left is the count it found, i.e. nothing but kept-aside entries was in it)
+	const bool fixed_point = h->active == 0u && h->contacts == 0u && h->general_contacts == 0u && !h->error && h->sleeping != 0u && !ctx->first_ghost;
+	if (fixed_point && as.streak && as.prev_pairs == pairs_now && as.prev_sleeping == h->sleeping && as.prev_cache == h->cache) as.streak++;
+	else as.streak = fixed_point ? 1u : 0u;
+	as.prev_pairs = pairs_now; as.prev_sleeping = h->sleeping; as.prev_cache = h->cache;
+	if (as.streak == 2u && !as.disabled) { as.B = d->body_count; if (nh_asleep_remember(ctx)) as.streak = 0; }
+}
+// NH_FLAG_FUSED_STEP: gravity / damping of the bodies the fused solver does not own, before anything else reads their momentum -- not launched
+// at all when every body is the fused solver's (a landed drop scene)
+static void rest_gravity(nh_context* ctx, nh_ContactConstraintData* d) {
 	ctx->adv.rest = ctx->h_state->has_other != 0 || !ctx->h_state->static_inert;
 	if (ctx->grav.rest_pending) {
 		ctx->grav.rest_pending = false;
 		if (ctx->adv.rest)
-			NH_LAUNCH(ctx, "gravity_rest", k_gravity_rest, nh_grid_for(ctx->grav.body_count, 256, 2048), 256, st, ctx->grav.active, d->body_class, ctx->grav.momentum,
-			          ctx->grav.gx_dt, ctx->grav.gy_dt, ctx->grav.gz_dt, ctx->grav.damping);
+			NH_LAUNCH(ctx, "gravity_rest", k_gravity_rest, nh_grid_for(ctx->grav.body_count, 256, 2048), 256, ctx->d_state, ctx->grav.active, d->body_class, ctx->grav.momentum, ctx->grav.gx_dt, ctx->grav.gy_dt, ctx->grav.gz_dt, ctx->grav.damping);
 	}
+}
+// bodies in several pairs or with dynamic partners (piles, pits): general CSR fill + sort + classification, then the counts again
+static int general_adjacency(nh_context* ctx, nh_ContactConstraintData* d, nh_Counts* c) {
 	if (d->has_late || ctx->h_state->has_static8 || !ctx->h_state->static_inert) ensure_csr(ctx, d);
-	if (d->has_late) {
-		// bodies in several pairs or with dynamic partners (piles, pits): general CSR fill + sort + classification, then the counts again
-		// (a world that had enough general contacts for the blocked solver last step will most likely colour them block by block again: the general bodies'
-		// lists -- which only the world-wide colouring reads -- are then left out, and filled in a second pass if it comes to that)
-		const bool local_candidate = !(ctx->flags & NH_FLAG_EXACT_ORDER) && !ctx->blk.disabled && !ctx->env_blk_global_colours && ctx->last_general_contacts >= ctx->blk.min_contacts;
-		d->general_lists = !local_candidate;
-		NH_LAUNCH(ctx, "adjacency_fill", k_adj_fill, nh_grid_for(kcap, 256, 4096), 256, st, contacts->bodies, contacts->tags, d->body_off, d->cont.cursor, d->adj, d->body_class, local_candidate ? 1u : 3u);
-		NH_LAUNCH(ctx, "adjacency_sort", k_adj_sort, nh_grid_for(B, 256, 4096), 256, st, B, contacts->bodies, d->body_off, d->adj, slot_key, d->body_class, pred_a, pred_b, bodies->properties, bodies->momentum);
-		NH_LAUNCH(ctx, "contact_class", k_contact_class, nh_grid_for(kcap, 256, 2048), 256, st, contacts->bodies, d->body_class, level, general_list, pred_a, pred_b);
-		rc = nh_read_counts(ctx, &c);
-		if (rc) return rc;
-		if (c.error) return (int)c.error;
-	}
-	nh_run_cull(ctx, imp, c.sleeping_pairs);
-	d->general_contacts = c.general_contacts;
-	ctx->last_general_contacts = c.general_contacts;
-	d->has_static8 = ctx->h_state->has_static8 != 0;
-	d->has_staticN = ctx->h_state->has_staticN != 0;
-	d->static_inert = ctx->h_state->static_inert != 0;
-	if (d->has_staticN) {
-		// bodies with more than 8 static contacts are rare: the warm start reads the materialised lookup
-		nh_materialize_lookup(ctx, imp, contacts->bodies, d->body_class);
-		NH_LAUNCH(ctx, "setup_staticN", (k_setup_static<true>), nh_grid_for(B, 256, 8192), 256, B, d->body_class, d->body_off, d->adj,
-		          contacts->data, contacts->bodies, imp->data, bodies->transforms, bodies->properties, bodies->momentum, d->rows, (float4*)d->states, (const uint32_t*)nullptr);
-	}
-	if (c.general_contacts) {
-		const uint32_t G = c.general_contacts;
-		nh_materialize_lookup(ctx, imp, contacts->bodies, d->body_class, d->has_staticN ? (const uint32_t*)nullptr : general_list, G);
-		// a large set in default order with no contact that no block can own: the blocks colour their own contacts (nh_blocks.h, k_blk_prepare_local) --
-		// no world-wide colouring, no adjacency lists of the general bodies
-		if (!(ctx->flags & NH_FLAG_EXACT_ORDER) && !ctx->env_blk_global_colours) {
-			rc = blk_setup(ctx, d, G, true);
-			if (rc) return rc;
-			if (d->blk.active) return NH_OK;
-		}
-		if (!d->general_lists && d->has_late) {
-			// (the per-block colouring did not apply after all: the lists of the general bodies the adjacency build left out)
-			NH_LAUNCH(ctx, "adjacency_fill", k_adj_fill, nh_grid_for(kcap, 256, 4096), 256, st, contacts->bodies, contacts->tags, d->body_off, d->cont.cursor, d->adj, d->body_class, 2u);
-			d->general_lists = true;
-		}
-		// A few thousand contacts in default order: colouring and level order by ONE workgroup, no host round trip until the solver's (k_colour_small)
-		if (!(ctx->flags & NH_FLAG_EXACT_ORDER) && !ctx->env_no_resident && !ctx->env_colour_check_seeds && G <= NH_COLOUR_SMALL_MAX &&
-		    (G <= NH_RES_MAX_FULL || B <= NH_RESB_MAX_BODIES)) {
-			NH_LAUNCH(ctx, "colour_small", k_colour_small, 1, 1024, st, general_list, imp->data, contacts->bodies, d->body_off, d->adj, level, d->cont.tent, level_hist, d->level_order, B);
-			NH_LAUNCH(ctx, "rows_general", k_rows_general, nh_grid_for(G, 256, 4096), 256, st, d->level_order, contacts->data, contacts->bodies, bodies->transforms, bodies->properties,
-			          (float4*)d->rows, (size_t)kcap, d->gpair, 1u, d->static_inert ? 1u : 0u, level, level_hist + (NH_MAX_LEVELS + 2),
-			          (const nh_CachedContactImpulse*)nullptr, (float4*)nullptr, (uint32_t*)nullptr, 0u);
-			d->levels = 0;                                  // on the device (st->levels)
-			d->resident = G <= NH_RES_MAX_FULL; d->resident_cap = NH_RES_MAX_FULL; d->resident_bodies = !d->resident;
-			if (d->resident)
-				NH_LAUNCH(ctx, "solve_resident", k_solve_resident, 1, NH_RES_THREADS, st, level_hist, 0u, d->level_order, d->gpair, imp->data,
-				          bodies->momentum, (const float4*)d->rows, (size_t)kcap, d->gstates, 0u, 1u, d->resident_cap);
-			else
-				NH_LAUNCH(ctx, "solve_resident_bodies", k_solve_resident_bodies, 1, NH_RESB_THREADS, st, level_hist, level_hist + (NH_MAX_LEVELS + 2), 0u, d->level_order, d->gpair,
-				          imp->data, bodies->momentum, B, (const float4*)d->rows, (size_t)kcap, d->gstates, 0u, 1u);
-			return NH_OK;
-		}
-		// relaxation: every round finalises at least the next level
-		uint32_t rounds = 0;
-		NH_LAUNCH(ctx, "level_reset", k_level_reset_progress, 1, 1, st);
-		// colouring: most contacts are settled by the first rounds; the later ones walk a compacted list of the rest (pred_a / pred_b, which
-		// only the exact mode uses, serve as its two buffers)
-		const uint32_t* colour_list = general_list;
-		uint32_t colour_n = 0;                         // 0: the whole general list
-		uint32_t* spare[2] = { pred_a, pred_b };
-		int spare_at = 0;
-		for (;;) {
-			// (short batches first while colouring: the list shrinks fastest in the first rounds, and a batch ends with its compaction)
-			const int batch = (ctx->flags & NH_FLAG_EXACT_ORDER) ? 8 : 1;
-			for (int r = 0; r < batch; ++r, ++rounds) {
-				if (ctx->flags & NH_FLAG_EXACT_ORDER)
-					NH_LAUNCH(ctx, "level_relax", k_level_relax, nh_grid_for(G, 256, 1024), 256, st, general_list, pred_a, pred_b, level, rounds);
-				else {
-					if (rounds == 0 && !ctx->env_colour_check_seeds) {
-						NH_LAUNCH(ctx, "colour_seed", k_colour_seed_final, nh_grid_for(G, 256, 2048), 256, st, general_list, imp->data, level, d->cont.tent);
-						NH_LAUNCH(ctx, "colour_validate", k_colour_validate, nh_grid_for(B, 256, 4096), 256, st, B, d->body_class, d->body_off, d->adj, level, d->cont.tent);
-						continue;
-					}
-					if (rounds == 0)
-						NH_LAUNCH(ctx, "colour_seed", k_colour_seed, nh_grid_for(G, 256, 2048), 256, st, general_list, imp->data, d->cont.tent);
-					else
-					NH_LAUNCH(ctx, "colour_try", k_colour_try, nh_grid_for(colour_n ? colour_n : G, 256, 2048), 256, st, colour_list, colour_n, contacts->bodies, d->body_off, d->adj, level, d->cont.tent);
-					NH_LAUNCH(ctx, "colour_settle", k_colour_settle, nh_grid_for(colour_n ? colour_n : G, 256, 2048), 256, st, colour_list, colour_n, contacts->bodies, d->body_off, d->adj, level, d->cont.tent, rounds);
+	if (!d->has_late) return NH_OK;
+	nh_DevState* st = ctx->d_state; const nh_ContactData* contacts = &d->cont.contacts; const nh_BodyData* bodies = &d->bodies_at_setup;
+	const uint32_t kcap = d->contact_capacity, B = d->body_count;
+	// (a world that had enough general contacts for the blocked solver last step will most likely colour them block by block again: the general bodies'
+	// lists -- which only the world-wide colouring reads -- are then left out, and filled in a second pass if it comes to that)
+	const bool local_candidate = !(ctx->flags & NH_FLAG_EXACT_ORDER) && !ctx->blk.disabled && !ctx->env_blk_global_colours && ctx->last_general_contacts >= ctx->blk.min_contacts;
+	d->general_lists = !local_candidate;
+	NH_LAUNCH(ctx, "adjacency_fill", k_adj_fill, nh_grid_for(kcap, 256, 4096), 256, st, contacts->bodies, contacts->tags, d->body_off, d->cont.cursor, d->adj, d->body_class, local_candidate ? 1u : 3u);
+	NH_LAUNCH(ctx, "adjacency_sort", k_adj_sort, nh_grid_for(B, 256, 4096), 256, st, B, contacts->bodies, d->body_off, d->adj, d->cont.slot_key, d->body_class, d->cont.pred_a, d->cont.pred_b, bodies->properties, bodies->momentum);
+	NH_LAUNCH(ctx, "contact_class", k_contact_class, nh_grid_for(kcap, 256, 2048), 256, st, contacts->bodies, d->body_class, d->cont.level, d->general_list, d->cont.pred_a, d->cont.pred_b);
+	return counts_result(nh_read_counts(ctx, c), *c);
+}
+// A few thousand contacts in default order: colouring and level order by ONE workgroup, no host round trip until the solver's (k_colour_small)
+static void colour_small_path(nh_context* ctx, nh_ContactConstraintData* d, uint32_t G) {
+	NH_LAUNCH(ctx, "colour_small", k_colour_small, 1, 1024, ctx->d_state, d->general_list, d->imp->data, d->cont.contacts.bodies, d->body_off, d->adj, d->cont.level, d->cont.tent, d->cont.level_hist, d->level_order, d->body_count);
+	launch_rows_general(ctx, d, G, 1u);
+	d->levels = 0; d->resident = G <= NH_RES_MAX_FULL; d->resident_cap = NH_RES_MAX_FULL; d->resident_bodies = !d->resident;          // (levels: on the device, st->levels)
+	launch_resident(ctx, d, &d->bodies_at_setup, 0u, d->imp->data, 0u, 1u);
+}
+// The world-wide colouring (exact order: the relaxation that replays the reference's levels): rounds until no contact is left without a level; `levels`: how many there are
+static int colour_rounds(nh_context* ctx, nh_ContactConstraintData* d, uint32_t G, uint32_t* levels) {
+	nh_DevState* st = ctx->d_state;
+	const nh_ContactData* contacts = &d->cont.contacts;
+	uint32_t* pred_a = d->cont.pred_a; uint32_t* pred_b = d->cont.pred_b; uint32_t* level = d->cont.level; const uint32_t* general_list = d->general_list;
+	const uint32_t B = d->body_count; nh_Counts c;
+	// relaxation: every round finalises at least the next level
+	uint32_t rounds = 0;
+	NH_LAUNCH(ctx, "level_reset", k_level_reset_progress, 1, 1, st);
+	// colouring: most contacts are settled by the first rounds; the later ones walk a compacted list of the rest (pred_a / pred_b, which
+	// only the exact mode uses, serve as its two buffers)
+	const uint32_t* colour_list = general_list; uint32_t colour_n = 0;                         // 0: the whole general list
+	uint32_t* spare[2] = { pred_a, pred_b }; int spare_at = 0;
+	for (;;) {
+		// (short batches first while colouring: the list shrinks fastest in the first rounds, and a batch ends with its compaction)
+		const int batch = (ctx->flags & NH_FLAG_EXACT_ORDER) ? 8 : 1;
+		for (int r = 0; r < batch; ++r, ++rounds) {
+			if (ctx->flags & NH_FLAG_EXACT_ORDER)
+				NH_LAUNCH(ctx, "level_relax", k_level_relax, nh_grid_for(G, 256, 1024), 256, st, general_list, pred_a, pred_b, level, rounds);
+			else {
+				if (rounds == 0 && !ctx->env_colour_check_seeds) {
+					NH_LAUNCH(ctx, "colour_seed", k_colour_seed_final, nh_grid_for(G, 256, 2048), 256, st, general_list, d->imp->data, level, d->cont.tent);
+					NH_LAUNCH(ctx, "colour_validate", k_colour_validate, nh_grid_for(B, 256, 4096), 256, st, B, d->body_class, d->body_off, d->adj, level, d->cont.tent);
+					continue;
 				}
-			}
-			rc = nh_read_counts(ctx, &c);
-			if (rc) return rc;
-			uint32_t left = ((rounds - 1) & 1u) ? ctx->h_state->unleveled_odd : ctx->h_state->unleveled;
-			if (left == 0) break;
-			if (rounds > NH_MAX_LEVELS + 8) return NH_ERR_INVALID;
-			if (!(ctx->flags & NH_FLAG_EXACT_ORDER) && left <= (colour_n ? colour_n : G) / 2u) {
-				NH_HIP_CHECK(ctx, hipMemsetAsync(&st->colour_cursor, 0, sizeof(uint32_t), ctx->stream));
-				NH_LAUNCH(ctx, "colour_compact", k_colour_compact, nh_grid_for(colour_n ? colour_n : G, 256, 1024), 256, st, colour_list, colour_n, level, spare[spare_at]);
-				colour_list = spare[spare_at]; spare_at ^= 1; colour_n = left;
+				if (rounds == 0)
+					NH_LAUNCH(ctx, "colour_seed", k_colour_seed, nh_grid_for(G, 256, 2048), 256, st, general_list, d->imp->data, d->cont.tent);
+				else
+					NH_LAUNCH(ctx, "colour_try", k_colour_try, nh_grid_for(colour_n ? colour_n : G, 256, 2048), 256, st, colour_list, colour_n, contacts->bodies, d->body_off, d->adj, level, d->cont.tent);
+				NH_LAUNCH(ctx, "colour_settle", k_colour_settle, nh_grid_for(colour_n ? colour_n : G, 256, 2048), 256, st, colour_list, colour_n, contacts->bodies, d->body_off, d->adj, level, d->cont.tent, rounds);
 			}
 		}
-		if (c.levels > NH_MAX_LEVELS) return NH_ERR_INVALID;
-		d->levels = c.levels;
-		// a large set in default order: contacts owned by spatial blocks, swept in LDS block by block (nh_blocks.h)
-		rc = blk_setup(ctx, d, G, false);
-		if (rc) return rc;
-		if (d->blk.active) return NH_OK;
-		NH_LAUNCH(ctx, "zero_u32", k_zero_u32, 8, 256, level_hist, 2 * (NH_MAX_LEVELS + 2));       // histogram + the per-class "has a full row" flags behind it
-		NH_LAUNCH(ctx, "level_hist", k_level_hist, nh_grid_for(G, 256, 512), 256, st, general_list, level, level_hist);
-		NH_LAUNCH(ctx, "level_offsets", k_level_offsets, 1, 1024, level_hist, level_cursor);
-		NH_LAUNCH(ctx, "level_scatter", k_level_scatter, nh_grid_for(G, 256, 512), 256, st, general_list, level, level_cursor, d->level_order);
-		NH_LAUNCH(ctx, "rows_general", k_rows_general, nh_grid_for(G, 256, 4096), 256, st, d->level_order, contacts->data, contacts->bodies, bodies->transforms, bodies->properties,
-		          (float4*)d->rows, (size_t)kcap, d->gpair, (ctx->flags & NH_FLAG_EXACT_ORDER) ? 0u : 1u, d->static_inert ? 1u : 0u,
-		          level, level_hist + (NH_MAX_LEVELS + 2), (const nh_CachedContactImpulse*)nullptr, (float4*)nullptr, (uint32_t*)nullptr, 0u);
-		NH_HIP_CHECK(ctx, hipMemcpyAsync(d->level_off, level_hist, sizeof(uint32_t) * (d->levels + 2), hipMemcpyDeviceToHost, ctx->stream));
-		NH_HIP_CHECK(ctx, hipMemcpyAsync(d->level_full, level_hist + (NH_MAX_LEVELS + 2), sizeof(uint32_t) * (d->levels + 2), hipMemcpyDeviceToHost, ctx->stream));
-		NH_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-		// A small general set (a pile of a few hundred boxes, a pit of a thousand balls) is solved by ONE workgroup with its rows resident in LDS for
-		// the warm start and all sweeps (k_solve_resident): one launch per nh_apply_impulses call instead of one per level and sweep
-		bool all_radial = true;
-		for (uint32_t l = 1; l <= d->levels; ++l) all_radial &= d->level_full[l] == 0u;
-		d->resident_cap = all_radial ? NH_RES_MAX_RADIAL : NH_RES_MAX_FULL;
-		d->resident = G <= d->resident_cap && !ctx->env_no_resident;
-		d->resident_bodies = false;
-		if (d->resident) {
-			NH_LAUNCH(ctx, "solve_resident", k_solve_resident, 1, NH_RES_THREADS, st, level_hist, d->levels, d->level_order, d->gpair, imp->data,
-			          bodies->momentum, (const float4*)d->rows, (size_t)kcap, d->gstates, 0u, 1u, d->resident_cap);
-			return NH_OK;
-		}
-		// more rows than one compute unit's LDS holds, but a small world: every body's momentum resident instead (k_solve_resident_bodies)
-		d->resident_bodies = B <= NH_RESB_MAX_BODIES && d->levels <= NH_RESB_MAX_LEVELS && !ctx->env_no_resident;
-		if (d->resident_bodies) {
-			NH_LAUNCH(ctx, "solve_resident_bodies", k_solve_resident_bodies, 1, NH_RESB_THREADS, st, level_hist, level_hist + (NH_MAX_LEVELS + 2), d->levels, d->level_order, d->gpair,
-			          imp->data, bodies->momentum, B, (const float4*)d->rows, (size_t)kcap, d->gstates, 0u, 1u);
-			return NH_OK;
-		}
-		// warm start in level order (levels are numbered from 1)
-		for (uint32_t l = 1; l <= d->levels; ++l) {
-			uint32_t b = d->level_off[l], e = d->level_off[l + 1];
-			if (e > b && !d->level_full[l])
-				NH_LAUNCH(ctx, "warm_level", (k_level_exec<true, true>), nh_grid_for(e - b, 256, 8192), 256, d->level_order, b, e, d->gpair, imp->data,
-				          bodies->momentum, (const float4*)d->rows, (size_t)kcap, d->gstates);
-			else if (e > b)
-				NH_LAUNCH(ctx, "warm_level", (k_level_exec<true>), nh_grid_for(e - b, 256, 4096), 256, d->level_order, b, e, d->gpair, imp->data,
-				          bodies->momentum, (const float4*)d->rows, (size_t)kcap, d->gstates);
+		{ int rc = nh_read_counts(ctx, &c); if (rc) return rc; }
+		uint32_t left = ((rounds - 1) & 1u) ? ctx->h_state->unleveled_odd : ctx->h_state->unleveled;
+		if (left == 0) break;
+		if (rounds > NH_MAX_LEVELS + 8) return NH_ERR_INVALID;
+		if (!(ctx->flags & NH_FLAG_EXACT_ORDER) && left <= (colour_n ? colour_n : G) / 2u) {
+			NH_HIP_CHECK(ctx, hipMemsetAsync(&st->colour_cursor, 0, sizeof(uint32_t), ctx->stream));
+			NH_LAUNCH(ctx, "colour_compact", k_colour_compact, nh_grid_for(colour_n ? colour_n : G, 256, 1024), 256, st, colour_list, colour_n, level, spare[spare_at]);
+			colour_list = spare[spare_at]; spare_at ^= 1; colour_n = left;
 		}
 	}
+	*levels = c.levels;
 	return NH_OK;
 }
-
-// Solver launches for the one-body classes.  `early4_done`: the STATIC4 bodies classified by k_adj_simple have already been taken by
-// the speculative launch (only possible when body 0 is inert: that launch checks it on the device and leaves otherwise).
-static void launch_apply_static(nh_context* ctx, nh_ContactConstraintData* d, const nh_BodyData* bodies, uint32_t iterations, bool fused, bool early4_done, bool drop_states = false) {
-	const uint32_t B = d->body_count;
-	if (!(fused && early4_done && !d->has_late && !d->has_static8 && !d->has_staticN)) ensure_csr(ctx, d);      // (the common step launches nothing below)
-	nh_CacheView cv = { nullptr, nullptr, nullptr, nullptr, nullptr, ctx->d_state };
-	if (fused) { cv.tags = d->imp->tags; cv.features = d->imp->features; cv.ctags = d->imp->ctags; cv.cfeatures = d->imp->cfeatures; cv.cdata = d->imp->cdata; }
-	auto go = [&](const char* name, auto kernel, uint32_t cls_a, uint32_t cls_b) {
-		NH_LAUNCH(ctx, name, kernel, nh_grid_for(B, 256, 8192), 256, B, d->body_class, d->body_off, d->adj, d->bodies, bodies->properties, bodies->momentum,
-		          d->rows, (float4*)d->states, iterations, d->contact_data, bodies->transforms, d->impulses, cv, cls_a, cls_b);
-	};
-	auto go1 = [&](const char* name, auto kernel, uint32_t cls_a, uint32_t cls_b) {
-		NH_LAUNCH(ctx, name, kernel, nh_grid_for(B, 256, 8192), 256, B, d->body_class, d->body_off, d->adj, d->bodies, bodies->properties, bodies->momentum,
-		          (float4*)d->states, iterations, d->contact_data, bodies->transforms, d->impulses, cv, ctx->hint, cls_a, cls_b,
-		          (fused && drop_states) ? 2u : 0u, (const uint2*)nullptr, nh_FusedStep(), nh_StillView(), nh_AheadView());
-	};
-	const bool late = d->has_late;
-	if (d->static_inert) {
-		// body 0 is inert (all-zero velocity, inverse mass, inverse inertia): one-body forms, 27-float rows
-		const bool need4 = !early4_done || late;
-		const uint32_t a4 = early4_done ? NH_CLS_STATIC4_LATE : NH_CLS_STATIC4;
-		if (fused) {
-			if (need4) go1("solve_one_body", k_solve_one_body<4, true>, a4, NH_CLS_STATIC4_LATE);
-			if (d->has_static8) go1("solve_one_body8", k_solve_one_body<8, true>, NH_CLS_STATIC8, NH_CLS_STATIC8_LATE);
-		} else {
-			if (need4) go1("solve_one_body", k_solve_one_body<4, false>, a4, NH_CLS_STATIC4_LATE);
-			if (d->has_static8) go1("solve_one_body8", k_solve_one_body<8, false>, NH_CLS_STATIC8, NH_CLS_STATIC8_LATE);
-		}
-	} else if (fused) {
-		go("apply_static", k_apply_static<4, true>, NH_CLS_STATIC4, NH_CLS_STATIC4_LATE);
-		if (d->has_static8) go("apply_static8", k_apply_static<8, true>, NH_CLS_STATIC8, NH_CLS_STATIC8_LATE);
-	} else {
-		go("apply_static", k_apply_static<4, false>, NH_CLS_STATIC4, NH_CLS_STATIC4_LATE);
-		if (d->has_static8) go("apply_static8", k_apply_static<8, false>, NH_CLS_STATIC8, NH_CLS_STATIC8_LATE);
+// the contacts in level order, their rows, and where each level starts and which levels hold a full row -- on the host
+static int level_order_and_rows(nh_context* ctx, nh_ContactConstraintData* d, uint32_t G) {
+	uint32_t* level_hist = d->cont.level_hist;
+	NH_LAUNCH(ctx, "zero_u32", k_zero_u32, 8, 256, level_hist, 2 * (NH_MAX_LEVELS + 2));       // histogram + the per-class "has a full row" flags behind it
+	NH_LAUNCH(ctx, "level_hist", k_level_hist, nh_grid_for(G, 256, 512), 256, ctx->d_state, d->general_list, d->cont.level, level_hist);
+	NH_LAUNCH(ctx, "level_offsets", k_level_offsets, 1, 1024, level_hist, d->cont.level_cursor);
+	NH_LAUNCH(ctx, "level_scatter", k_level_scatter, nh_grid_for(G, 256, 512), 256, ctx->d_state, d->general_list, d->cont.level, d->cont.level_cursor, d->level_order);
+	launch_rows_general(ctx, d, G, (ctx->flags & NH_FLAG_EXACT_ORDER) ? 0u : 1u);
+	NH_HIP_CHECK(ctx, hipMemcpyAsync(d->level_off, level_hist, sizeof(uint32_t) * (d->levels + 2), hipMemcpyDeviceToHost, ctx->stream));
+	NH_HIP_CHECK(ctx, hipMemcpyAsync(d->level_full, level_hist + (NH_MAX_LEVELS + 2), sizeof(uint32_t) * (d->levels + 2), hipMemcpyDeviceToHost, ctx->stream));
+	NH_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+	return NH_OK;
+}
+// A small general set (a pile of a few hundred boxes, a pit of a thousand balls) is solved by ONE workgroup with its rows resident in LDS for
+// the warm start and all sweeps (k_solve_resident): one launch per nh_apply_impulses call instead of one per level and sweep.  More rows than one
+// compute unit's LDS holds, but a small world: every body's momentum resident instead (k_solve_resident_bodies)
+static bool choose_resident(const nh_context* ctx, nh_ContactConstraintData* d, uint32_t G) {
+	bool all_radial = true;
+	for (uint32_t l = 1; l <= d->levels; ++l) all_radial &= d->level_full[l] == 0u;
+	d->resident_cap = all_radial ? NH_RES_MAX_RADIAL : NH_RES_MAX_FULL; d->resident = G <= d->resident_cap && !ctx->env_no_resident;
+	d->resident_bodies = !d->resident && d->body_count <= NH_RESB_MAX_BODIES && d->levels <= NH_RESB_MAX_LEVELS && !ctx->env_no_resident;
+	return d->resident || d->resident_bodies;
+}
+// The general contacts (bodies in several pairs, or with dynamic partners): which form solves them, its set-up and its warm start
+static int general_setup(nh_context* ctx, nh_ContactConstraintData* d, uint32_t G) {
+	const nh_ContactData* contacts = &d->cont.contacts; const nh_BodyData* bodies = &d->bodies_at_setup;
+	nh_materialize_lookup(ctx, d->imp, contacts->bodies, d->body_class, d->has_staticN ? (const uint32_t*)nullptr : d->general_list, G);
+	// a large set in default order with no contact that no block can own: the blocks colour their own contacts (nh_blocks.h, k_blk_prepare_local) --
+	// no world-wide colouring, no adjacency lists of the general bodies
+	if (!(ctx->flags & NH_FLAG_EXACT_ORDER) && !ctx->env_blk_global_colours) {
+		{ int rc = blk_setup(ctx, d, G, true); if (rc) return rc; }
+		if (d->blk.active) return NH_OK;
 	}
-	if (d->has_staticN && iterations) go("apply_staticN", k_apply_static<0, false>, NH_CLS_STATICN, NH_CLS_STATICN);
+	// (the per-block colouring did not apply after all: the lists of the general bodies the adjacency build left out)
+	if (!d->general_lists && d->has_late) {
+		NH_LAUNCH(ctx, "adjacency_fill", k_adj_fill, nh_grid_for(d->contact_capacity, 256, 4096), 256, ctx->d_state, contacts->bodies, contacts->tags, d->body_off, d->cont.cursor, d->adj, d->body_class, 2u);
+		d->general_lists = true;
+	}
+	if (!(ctx->flags & NH_FLAG_EXACT_ORDER) && !ctx->env_no_resident && !ctx->env_colour_check_seeds && G <= NH_COLOUR_SMALL_MAX && (G <= NH_RES_MAX_FULL || d->body_count <= NH_RESB_MAX_BODIES)) { colour_small_path(ctx, d, G); return NH_OK; }
+	uint32_t levels = 0;
+	{ int rc = colour_rounds(ctx, d, G, &levels); if (rc) return rc; }
+	if (levels > NH_MAX_LEVELS) return NH_ERR_INVALID;
+	d->levels = levels;
+	// a large set in default order: contacts owned by spatial blocks, swept in LDS block by block (nh_blocks.h)
+	{ int rc = blk_setup(ctx, d, G, false); if (rc) return rc; }
+	if (d->blk.active) return NH_OK;
+	{ int rc = level_order_and_rows(ctx, d, G); if (rc) return rc; }
+	if (choose_resident(ctx, d, G)) { launch_resident(ctx, d, bodies, d->levels, d->imp->data, 0u, 1u); return NH_OK; }
+	launch_levels<true>(ctx, d, bodies, d->imp->data);          // warm start in level order
+	return NH_OK;
+}
+// What a setup does once the host knows the counts: general adjacency for bodies k_adj_simple left pending, culling when something sleeps, the >8-contact
+// one-body class, and the general contacts' solver (blocks, one workgroup, or colours / levels, rows, warm start).  Runs once per setup, with ctx->pending already cleared.
+static int finish_setup(nh_context* ctx, nh_ContactConstraintData* d) {
+	nh_Counts c;
+	{ int rc = setup_counts(ctx, d, &c); if (rc) return rc; }
+	outlook_for_next_step(ctx, d);
+	rest_gravity(ctx, d);
+	{ int rc = general_adjacency(ctx, d, &c); if (rc) return rc; }
+	nh_run_cull(ctx, d->imp, c.sleeping_pairs);
+	d->general_contacts = c.general_contacts; ctx->last_general_contacts = c.general_contacts;
+	d->has_static8 = ctx->h_state->has_static8 != 0; d->has_staticN = ctx->h_state->has_staticN != 0; d->static_inert = ctx->h_state->static_inert != 0;
+	if (d->has_staticN) {
+		// bodies with more than 8 static contacts are rare: the warm start reads the materialised lookup
+		const nh_ContactData* contacts = &d->cont.contacts; const nh_BodyData* bodies = &d->bodies_at_setup;
+		nh_materialize_lookup(ctx, d->imp, contacts->bodies, d->body_class);
+		NH_LAUNCH(ctx, "setup_staticN", (k_setup_static<true>), nh_grid_for(d->body_count, 256, 8192), 256, d->body_count, d->body_class, d->body_off, d->adj,
+		          contacts->data, contacts->bodies, d->imp->data, bodies->transforms, bodies->properties, bodies->momentum, d->rows, (float4*)d->states, (const uint32_t*)nullptr);
+	}
+	return c.general_contacts ? general_setup(ctx, d, c.general_contacts) : NH_OK;
 }
 
-// First solver call after a setup (or its flush with zero sweeps): the common one-body kernel goes out BEFORE the counters round trip --
-// the round trip then overlaps with it instead of idling the GPU -- and the rest follows once the host knows what else there is.
+// ---- 18. the solver calls: the one-body classes, the pending gravity ------------------------------------------------------------------------------------------------------------------------------------
+// Solver launches for the one-body classes, with (FUSED: the first call after a setup) or without the cache lookup behind them.  `early4_done`: the STATIC4 bodies
+// classified by k_adj_simple have already been taken by the speculative launch (only possible when body 0 is inert: that launch checks it on the device and leaves otherwise).
+template<bool FUSED>
+static void launch_apply_static(nh_context* ctx, nh_ContactConstraintData* d, const nh_BodyData* bodies, uint32_t iterations, bool early4_done, bool drop_states = false) {
+	if (!(FUSED && early4_done && !d->has_late && !d->has_static8 && !d->has_staticN)) ensure_csr(ctx, d);      // (the common step launches nothing below)
+	nh_CacheView cv = { nullptr, nullptr, nullptr, nullptr, nullptr, ctx->d_state };
+	if (FUSED) { cv.tags = d->imp->tags; cv.features = d->imp->features; cv.ctags = d->imp->ctags; cv.cfeatures = d->imp->cfeatures; cv.cdata = d->imp->cdata; }
+	if (d->static_inert) {
+		// body 0 is inert (all-zero velocity, inverse mass, inverse inertia): one-body forms, 27-float rows
+		const uint32_t grid = nh_grid_for(d->body_count, 256, 8192), flags = (FUSED && drop_states) ? 2u : 0u;
+		if (!early4_done || d->has_late)
+			launch_one_body<4, FUSED>(ctx, "solve_one_body", grid, d, bodies, iterations, cv, { d->contact_data, early4_done ? NH_CLS_STATIC4_LATE : NH_CLS_STATIC4, NH_CLS_STATIC4_LATE, flags, nullptr, nh_FusedStep(), nh_StillView(), nh_AheadView() });
+		if (d->has_static8)
+			launch_one_body<8, FUSED>(ctx, "solve_one_body8", grid, d, bodies, iterations, cv, { d->contact_data, NH_CLS_STATIC8, NH_CLS_STATIC8_LATE, flags, nullptr, nh_FusedStep(), nh_StillView(), nh_AheadView() });
+	} else {
+		launch_static<4, FUSED>(ctx, "apply_static", d, bodies, iterations, cv, NH_CLS_STATIC4, NH_CLS_STATIC4_LATE);
+		if (d->has_static8) launch_static<8, FUSED>(ctx, "apply_static8", d, bodies, iterations, cv, NH_CLS_STATIC8, NH_CLS_STATIC8_LATE);
+	}
+	if (d->has_staticN && iterations) launch_static<0, false>(ctx, "apply_staticN", d, bodies, iterations, cv, NH_CLS_STATICN, NH_CLS_STATICN);
+}
 static int settle_gravity(nh_context* ctx) {
 	if (!ctx->grav.pending) return NH_OK;
 	ctx->grav.pending = false;
-	NH_LAUNCH(ctx, "gravity_damping", k_gravity, nh_grid_for(ctx->grav.body_count, 256, 2048), 256, ctx->d_state, ctx->grav.active, ctx->grav.momentum,
-	          ctx->grav.gx_dt, ctx->grav.gy_dt, ctx->grav.gz_dt, ctx->grav.damping);
+	NH_LAUNCH(ctx, "gravity_damping", k_gravity, nh_grid_for(ctx->grav.body_count, 256, 2048), 256, ctx->d_state, ctx->grav.active, ctx->grav.momentum, ctx->grav.gx_dt, ctx->grav.gy_dt, ctx->grav.gz_dt, ctx->grav.damping);
 	return NH_OK;
 }
 
+// ---- 19. the solver calls: a still step -- ONE launch, then the round trip that confirms it -----------------------------------------------------------------------
+// is the solver call the one the still step's nh_collide prepared for?  (otherwise the caller has left the sample's order: the step again, in full)
+static bool still_usable(const nh_context* ctx, const nh_ContactConstraintData* d, const nh_BodyData* bodies, uint32_t iterations, bool applied, bool from_apply, bool drop_states) {
+	return applied && from_apply && drop_states && iterations != 0u && d->finish_pending && ctx->still.setup_d == d && ctx->grav.pending && ctx->grav.momentum == bodies->momentum && bodies->idle_counters &&
+	       bodies->momentum == ctx->still.bodies.momentum && bodies->transforms == ctx->still.bodies.transforms && d->imp->cdata == ctx->still.cache_data && ctx->still.slots_current;
+}
+static inline bool still_reports_itself(const nh_StillStep& ss) { return ss.pipelined && ss.h_ring[0]; }          // (late verdicts: the solver's first thread writes the step's counters into the pinned ring slot itself)
+// what the lanes need to do the next sub-step's k_xform<true> (and its narrowphase for the body's own pair) on their way out
+static nh_AheadView still_ahead_view(const nh_context* ctx) {
+	const nh_ColliderData& cd = ctx->still.colliders;
+	const uint32_t C = cd.boxes.count + cd.spheres.count;
+	const uint8_t* gen = (C < (1u << NH_GEN_SHIFT) && !ctx->env_no_incremental) ? ctx->fat_gen : (const uint8_t*)nullptr;
+	return { ctx->body_col, cd.boxes.transforms, cd.boxes.data, cd.spheres.transforms, cd.spheres.data, cd.boxes.count, ctx->own_xf, ctx->own_aabb_min, ctx->own_aabb_max, ctx->fat_box, ctx->fat_pairs, ctx->fat_pair_capacity,
+	         ctx->lay_capacity, ctx->sort_keys_by_position, ctx->own_ctag, gen, ctx->rec, ctx->raw_data, ctx->raw_feature, ctx->cnt_sorted, ctx->still_delta, ctx->pair_list_capacity, C > (2u << 20) ? 1u : 0u };
+}
+static int still_solve(nh_context* ctx, nh_ContactConstraintData* d, const nh_BodyData* bodies, uint32_t iterations) {
+	nh_StillStep& ss = ctx->still;
+	const uint32_t B = d->body_count, grid = (B + 63u) / 64u;
+	const nh_CacheView cv = { nullptr, nullptr, nullptr, nullptr, reinterpret_cast<const nh_CachedContactImpulse*>(ctx->sc_imp), ctx->d_state };
+	const nh_StillView sv = { ctx->body_rec, ctx->body_pos, ctx->cnt_sorted, ctx->start_sorted, ctx->raw_feature, ctx->sc_feat, ctx->sc_count, ctx->lay_capacity, ctx->still_delta, ctx->step_parity };
+	nh_FusedStep fs = fused_gravity(ctx);
+	fs.bits = 3u | (ss.sleepers ? 4u : 0u) | ((ss.sleepers && !ss.no_sleeper_skip) ? 8u : 0u); fs.idle = bodies->idle_counters; fs.seq = ctx->collide_seq;          // (bit 3: waves of sleeping bodies leave at once)
+	fs.ghost_first = ctx->halo_ghost_first; fs.host_counters = still_reports_itself(ss) ? reinterpret_cast<uint32_t*>(ss.h_ring[ctx->collide_seq & 1u]) : nullptr;
+	fs.guard_seq = ss.verdict.pending ? ss.verdict.seq : ctx->collide_seq;          // (a solver behind an unconfirmed still step leaves when THAT one failed)
+	// XFORM AHEAD (nh_internal.h): another sub-step of this nh_step call follows, the step is in the plain form and every dynamic body has its one collider on the
+	// map -- the lanes do the next step's k_xform<true> on their way out
+	ctx->halo_split.launched = false;          // (this step's solver has not gone out in two parts yet)
+	const bool ahead = ss.ahead_plain && ss.more_steps && ss.ahead_map_ok && !ss.no_ahead && !ss.ahead_world_bad && ctx->own_xf && ctx->body_col && ctx->body_col_capacity >= B;
+	// PAIR AHEAD (nh_internal.h): ... and the next sub-step's narrowphase for the body's own pair -- that sub-step then starts at the solver
+	const bool pair = ahead && !ss.no_pair && !ss.pair_world_bad && ss.pair_owned_seq != 0u && ctx->pair_list && ctx->fat_pairs && ctx->own_ctag &&
+	                  (uint64_t)ss.colliders.boxes.count + ss.colliders.spheres.count < (1ull << 31);
+	const nh_AheadView av = ahead ? still_ahead_view(ctx) : nh_AheadView();
+	// HALO SPLIT (nh_partition_step): the bodies the neighbours wait for on a second stream, behind the step's prologue like the interior -- the exchange of the NEXT
+	// sub-step is enqueued behind them once the verdict is in (still_verdict) and travels while the interior is being solved
+	const bool split = pair && ctx->halo_split.armed && ss.early_verdict && ss.steps_left > 0u && !ctx->timing && ctx->halo_split.bound != 0u;
+	auto with = [&](const nh_FusedStep& f) { return nh_OneBodyLaunch{ ctx->raw_data, NH_CLS_STATIC4, NH_CLS_STATIC4, 2u, d->simple, f, sv, av }; };
+	if (split) {
+		nh_FusedStep fi = fs, fb = fs;
+		fi.part = 2u; fi.xskip = ctx->halo_split.mask;
+		fb.part = 1u; fb.xlist = ctx->halo_split.list; fb.xcount = ctx->halo_split.count; fb.host_counters = nullptr;
+		launch_one_body<4, true, true, 1, true, true, true, true>(ctx, "solve_still", grid, d, bodies, iterations, cv, with(fi));
+		NH_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->halo_split.stream, ss.ev_ring[0], 0));          // (the counters' copy behind k_pair_begin: the prologue has run)
+		launch_one_body<4, true, true, 1, true, true, true, true>(ctx, nullptr, (ctx->halo_split.bound + 63u) / 64u, d, bodies, iterations, cv, with(fb), ctx->halo_split.stream);
+		ctx->halo_split.launched = true;
+	} else if (pair) launch_one_body<4, true, true, 1, true, true, true>(ctx, "solve_still", grid, d, bodies, iterations, cv, with(fs));
+	else if (ahead) launch_one_body<4, true, true, 1, true, true>(ctx, "solve_still", grid, d, bodies, iterations, cv, with(fs));
+	else launch_one_body<4, true, true, 1, true>(ctx, "solve_still", grid, d, bodies, iterations, cv, with(fs));
+	ss.ahead_ready = ahead; ss.pair_ready = pair;
+	return NH_OK;
+}
+static inline bool still_held(const nh_DevState* h, uint32_t seq) { return h->still_failed_seq < seq && h->error == 0u; }          // did every check of the still step numbered `seq` hold?  `h`: the counters it left
+// the counters of a confirmed still step become the host's: the mirror, the sleep prediction (largest idle counter the step saw), the movers
+static void adopt_counters(nh_context* ctx, const nh_DevState* h, uint32_t seq, uint32_t parity, uint64_t collide_mark) {
+	ctx->still.confirmed_seq = seq;
+	if (h != ctx->h_state) memcpy(ctx->h_state, h, NH_COUNTER_WORDS * sizeof(uint32_t));
+	if (!ctx->idle_unknown) { ctx->idle_bound = (int)h->max_idle[parity]; ctx->idle_bound_mark = collide_mark; }
+	nh_still_note_movers(ctx, h, seq);
+}
+// NH_OK with *confirmed (false: a check failed on the device -- the step again, in full), NH_INTERNAL_STILL_FAILED (the step BEFORE this one failed), or an error
+static int still_verdict(nh_context* ctx, bool* confirmed) {
+	nh_StillStep& ss = ctx->still;
+	if (still_reports_itself(ss)) {
+		// nh_step: first the verdict of the still step BEFORE this one (its counters landed long ago) ...
+		if (ss.verdict.pending) {
+			if (ss.verdict.event) NH_HIP_CHECK(ctx, hipEventSynchronize(ss.ev_ring[ss.verdict.slot]));
+			else { const int w = nh_still_await_number(ctx); if (w) return w == 2 ? NH_ERR_HIP : NH_INTERNAL_STILL_FAILED; }          // (that step reported itself: its number, spun on)
+			const nh_DevState* h = ss.h_ring[ss.verdict.slot];
+			if (!still_held(h, ss.verdict.seq)) return NH_INTERNAL_STILL_FAILED;       // (nh_step cleans up and runs both steps again)
+			adopt_counters(ctx, h, ss.verdict.seq, ss.verdict.parity, ss.verdict.collide_mark);
+			ss.verdict.pending = false;
+		}
+		// ... then this step's counters on their way, to be looked at by the next step
+		const int slot = (int)(ctx->collide_seq & 1u);
+		// (a step that reports itself -- not in two launches, not under option "no_early_counts" -- needs no event: the host takes its verdict from the number in the slot)
+		const bool ring_event = ctx->halo_split.launched || ctx->no_early_counts;
+		if (ring_event) NH_HIP_CHECK(ctx, hipEventRecord(ss.ev_ring[slot], ctx->stream));
+		ss.verdict.event = ring_event;
+		ss.verdict.pending = true; ss.verdict.seq = ctx->collide_seq; ss.verdict.parity = ctx->step_parity; ss.verdict.slot = slot; ss.verdict.collide_mark = ctx->collide_mark;
+		*confirmed = true;          // (until the next step says otherwise)
+	} else if (ss.early_verdict) {
+		// nh_partition_step, a step that started at the solver: everything such a step can fail on is checked by its PROLOGUE (k_pair_begin: the step-wide words,
+		// body 0, the pairs that are nobody's or a ghost's -- the lanes' checks belong to the NEXT step), whose counters nh_collide sent on their way before this
+		// solver was launched.  The host waits for THAT copy -- the solver runs on -- so the next sub-step's halo and launches queue up behind it: no bubble
+		ss.early_verdict = false;
+		NH_HIP_CHECK(ctx, hipEventSynchronize(ss.ev_ring[0]));
+		const nh_DevState* h = ss.h_ring[0];
+		*confirmed = still_held(h, ctx->collide_seq);
+		if (*confirmed) {
+			adopt_counters(ctx, h, ctx->collide_seq, ctx->step_parity, ctx->collide_mark);
+			// (halo split: the step happened -- what the neighbours get of it may leave now, behind the boundary launch on its stream)
+			if (ctx->halo_split.launched && ctx->halo_split.after_verdict) { int rc = ctx->halo_split.after_verdict(ctx, ctx->halo_split.user); if (rc) return rc; }
+		} else {
+			NH_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));          // (the solver has left at once; the replay starts from a quiet stream like every other)
+			if (ctx->halo_split.launched) { NH_HIP_CHECK(ctx, hipStreamSynchronize(ctx->halo_split.stream)); ctx->halo_split.launched = false; }
+		}
+	} else {
+		// the step's one round trip: did every check hold?
+		NH_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_state, ctx->d_state, NH_COUNTER_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+		NH_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+		if (ctx->timing) nh_timer_collect(ctx);
+		*confirmed = still_held(ctx->h_state, ctx->collide_seq);
+		if (*confirmed) adopt_counters(ctx, ctx->h_state, ctx->collide_seq, ctx->step_parity, ctx->collide_mark);
+	}
+	return NH_OK;
+}
+// the still step happened: nothing of the full step is left to do, and the caller's views are an earlier step's
+static void still_confirmed(nh_context* ctx, nh_ContactConstraintData* d) {
+	nh_StillStep& ss = ctx->still;
+	ss.resolved = true; ss.setup_d = nullptr; ss.note_confirmed();
+	ss.cache_stale = true; ss.contacts_stale = true;        // (the caller's cache and dense contact arrays are last written by an earlier step: nh_still_sync_outputs)
+	if (ss.sleepers) { ss.views_sleepers = true; ss.sleep_pairs_current = false; ss.active_current = false; }            // (... and so are its active list and sleeping pairs)
+	d->finish_pending = false; d->has_late = false; d->has_static8 = d->has_staticN = false; d->static_inert = true; d->general_contacts = 0; d->levels = 0;
+	d->imp->cull_pending = false; d->imp->lookup_pending = false; ctx->last_general_contacts = 0;
+	ctx->grav.pending = false; ctx->grav.rest_pending = false;
+	ctx->adv.done = true; ctx->adv.time_step = ctx->grav.time_step; ctx->adv.body_class = d->body_class; ctx->adv.rest = false;
+}
+// ---- 20. the solver calls: the first one after a setup, and the entry points ----------------------------------------------------------------------------------
+// The common one-body kernel, launched BEFORE the host knows the step's counters (they are on their way as it starts); then the rest of the setup
+static int speculative_launch(nh_context* ctx, nh_ContactConstraintData* d, const nh_BodyData* bodies, uint32_t iterations, bool from_apply, bool drop_states) {
+	d->finish_pending = false;
+	const nh_CacheView cv = { d->imp->tags, d->imp->features, d->imp->ctags, d->imp->cfeatures, d->imp->cdata, ctx->d_state };
+	nh_FusedStep fs = nh_FusedStep();
+	const bool gravity_here = ctx->grav.pending && ctx->grav.momentum == bodies->momentum;
+	if (ctx->grav.pending && !gravity_here) { int rc = settle_gravity(ctx); if (rc) return rc; }
+	if (gravity_here) {
+		ctx->grav.pending = false;
+		fs = fused_gravity(ctx); fs.bits = 1u;
+		if (from_apply && bodies->idle_counters) { fs.bits |= 2u; fs.idle = bodies->idle_counters; ctx->adv.done = true; ctx->adv.time_step = fs.time_step; ctx->adv.body_class = d->body_class; }
+	}
+	// (early counters: not with EVERY launch timed -- the events of a step are collected at its round trip, when they must have happened; timing restricted to one kernel, what
+	// bench.py keeps on, collects at nh_kernel_times -- and not under the legacy observer contract, whose round trips do more than read)
+	d->early_seq = 0u;
+	if (ctx->h_early && !ctx->no_early_counts && d->body_count != 0u && !(ctx->timing && ctx->timing_filter.empty()) && !ctx->sync_exports_views && !(ctx->flags & NH_FLAG_SYNC_COUNTS)) { fs.host_counters = ctx->h_early; fs.seq = ctx->collide_seq; d->early_seq = ctx->collide_seq; }
+	launch_one_body<4, true, true, 1>(ctx, "solve_one_body", (d->body_count + 63u) / 64u, d, bodies, iterations, cv, { d->contact_data, NH_CLS_STATIC4, NH_CLS_STATIC4, 1u | (drop_states ? 2u : 0u), d->simple, fs, nh_StillView(), nh_AheadView() });
+	ctx->grav.rest_pending = gravity_here;        // everybody else's gravity: finish_setup, once the round trip has told whether there is anybody else
+	return finish_setup(ctx, d);
+}
+// First solver call after a setup (or its flush with zero sweeps): the common one-body kernel goes out BEFORE the counters round trip --
+// the round trip then overlaps with it instead of idling the GPU -- and the rest follows once the host knows what else there is.
 // `applied`: called by nh_apply_impulses itself (not by the flush of a setup nobody applied): with NH_FLAG_FUSED_STEP the caller has promised
 // that this is the step's only solver call, so the bodies of the fused kernel are advanced there too
-static inline bool cd_count_over(const nh_ColliderData& cd) { return (uint64_t)cd.boxes.count + cd.spheres.count >= (1ull << 31); }
 static int first_apply(nh_context* ctx, nh_ContactConstraintData* d, const nh_BodyData* bodies, uint32_t iterations, bool applied = false) {
 	// the flush of a setup nobody applied yet keeps the solver states whatever the flags say: an nh_apply_impulses may still follow (nh_read_counts
 	// or nh_synchronize between setup and apply must not break the step)
@@ -2498,156 +2650,23 @@ static int first_apply(nh_context* ctx, nh_ContactConstraintData* d, const nh_Bo
 	d->states_kept = !drop_states;
 	bool early4_done = false;
 	if (ctx->still.active && !ctx->still.resolved) {
-		// ---- still step: ONE launch, then the round trip that confirms it ----
-		nh_StillStep& ss = ctx->still;
-		const bool usable = applied && from_apply && drop_states && iterations != 0u && d->finish_pending && ss.setup_d == d && ctx->grav.pending && ctx->grav.momentum == bodies->momentum &&
-		                    bodies->idle_counters && bodies->momentum == ss.bodies.momentum && bodies->transforms == ss.bodies.transforms && d->imp->cdata == ss.cache_data && ss.slots_current;
 		bool confirmed = false;
-		if (usable) {
-			const uint32_t B = d->body_count;
-			nh_CacheView cv = { nullptr, nullptr, nullptr, nullptr, reinterpret_cast<const nh_CachedContactImpulse*>(ctx->sc_imp), ctx->d_state };
-			nh_StillView sv = { ctx->body_rec, ctx->body_pos, ctx->cnt_sorted, ctx->start_sorted, ctx->raw_feature, ctx->sc_feat, ctx->sc_count, ctx->lay_capacity, ctx->still_delta, ctx->step_parity };
-			nh_FusedStep fs = nh_FusedStep();
-			fs.gx_dt = ctx->grav.gx_dt; fs.gy_dt = ctx->grav.gy_dt; fs.gz_dt = ctx->grav.gz_dt; fs.damping = ctx->grav.damping; fs.time_step = ctx->grav.time_step;
-			fs.bits = 3u | (ss.sleepers ? 4u : 0u) | ((ss.sleepers && !ss.no_sleeper_skip) ? 8u : 0u); fs.idle = bodies->idle_counters; fs.seq = ctx->collide_seq;          // (bit 3: waves of sleeping bodies leave at once)
-			fs.ghost_first = ctx->halo_ghost_first;
-			// (late verdicts: the solver's first thread writes the step's counters into the pinned ring slot itself)
-			const bool self_report = ss.pipelined && ss.h_ring[0];
-			fs.host_counters = self_report ? reinterpret_cast<uint32_t*>(ss.h_ring[ctx->collide_seq & 1u]) : nullptr;
-			fs.guard_seq = ss.verdict.pending ? ss.verdict.seq : ctx->collide_seq;          // (a solver behind an unconfirmed still step leaves when THAT one failed)
-			// XFORM AHEAD (nh_internal.h): another sub-step of this nh_step call follows, the step is in the plain form and every dynamic body has its one collider on the
-			// map -- the lanes do the next step's k_xform<true> on their way out
-			ctx->halo_split.launched = false;          // (this step's solver has not gone out in two parts yet)
-			const bool ahead = ss.ahead_plain && ss.more_steps && ss.ahead_map_ok && !ss.no_ahead && !ss.ahead_world_bad &&
-			                   ctx->own_xf && ctx->body_col && ctx->body_col_capacity >= B;
-			// PAIR AHEAD (nh_internal.h): ... and the next sub-step's narrowphase for the body's own pair -- that sub-step then starts at the solver
-			const bool pair = ahead && !ss.no_pair && !ss.pair_world_bad && ss.pair_owned_seq != 0u && ctx->pair_list && ctx->fat_pairs && ctx->own_ctag && !(cd_count_over(ss.colliders));
-			if (ahead) {
-				const nh_ColliderData& cd = ss.colliders;
-				const uint32_t C = cd.boxes.count + cd.spheres.count;
-				const uint8_t* gen = (C < (1u << NH_GEN_SHIFT) && !ctx->env_no_incremental) ? ctx->fat_gen : (const uint8_t*)nullptr;
-				nh_AheadView av = { ctx->body_col, cd.boxes.transforms, cd.boxes.data, cd.spheres.transforms, cd.spheres.data, cd.boxes.count, ctx->own_xf, ctx->own_aabb_min, ctx->own_aabb_max, ctx->fat_box,
-				                    ctx->fat_pairs, ctx->fat_pair_capacity, ctx->lay_capacity, ctx->sort_keys_by_position, ctx->own_ctag, gen,
-				                    ctx->rec, ctx->raw_data, ctx->raw_feature, ctx->cnt_sorted, ctx->still_delta, ctx->pair_list_capacity, C > (2u << 20) ? 1u : 0u };
-				// HALO SPLIT (nh_partition_step): the bodies the neighbours wait for on a second stream, behind the step's prologue like the interior -- the exchange of the NEXT
-				// sub-step is enqueued behind them once the verdict is in (below) and travels while the interior is being solved
-				const bool split = pair && ctx->halo_split.armed && ss.early_verdict && ss.steps_left > 0u && !ctx->timing && ctx->halo_split.bound != 0u;
-				if (split) {
-					nh_FusedStep fi = fs, fb = fs;
-					fi.part = 2u; fi.xskip = ctx->halo_split.mask;
-					fb.part = 1u; fb.xlist = ctx->halo_split.list; fb.xcount = ctx->halo_split.count; fb.host_counters = nullptr;
-					NH_LAUNCH(ctx, "solve_still", (k_solve_one_body<4, true, true, 1, true, true, true, true>), (B + 63u) / 64u, 64, B, d->body_class, d->body_off, d->adj, d->bodies, bodies->properties, bodies->momentum,
-					          (float4*)d->states, iterations, ctx->raw_data, bodies->transforms, d->impulses, cv, ctx->hint, NH_CLS_STATIC4, NH_CLS_STATIC4, 2u, d->simple, fi, sv, av);
-					NH_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->halo_split.stream, ss.ev_ring[0], 0));          // (the counters' copy behind k_pair_begin: the prologue has run)
-					hipLaunchKernelGGL((k_solve_one_body<4, true, true, 1, true, true, true, true>), dim3((ctx->halo_split.bound + 63u) / 64u), dim3(64), 0, ctx->halo_split.stream,
-					                   B, d->body_class, d->body_off, d->adj, d->bodies, bodies->properties, bodies->momentum,
-					                   (float4*)d->states, iterations, ctx->raw_data, bodies->transforms, d->impulses, cv, ctx->hint, NH_CLS_STATIC4, NH_CLS_STATIC4, 2u, d->simple, fb, sv, av);
-					ctx->halo_split.launched = true;
-				} else if (pair)
-				NH_LAUNCH(ctx, "solve_still", (k_solve_one_body<4, true, true, 1, true, true, true>), (B + 63u) / 64u, 64, B, d->body_class, d->body_off, d->adj, d->bodies, bodies->properties, bodies->momentum,
-				          (float4*)d->states, iterations, ctx->raw_data, bodies->transforms, d->impulses, cv, ctx->hint, NH_CLS_STATIC4, NH_CLS_STATIC4, 2u, d->simple, fs, sv, av);
-				else
-				NH_LAUNCH(ctx, "solve_still", (k_solve_one_body<4, true, true, 1, true, true>), (B + 63u) / 64u, 64, B, d->body_class, d->body_off, d->adj, d->bodies, bodies->properties, bodies->momentum,
-				          (float4*)d->states, iterations, ctx->raw_data, bodies->transforms, d->impulses, cv, ctx->hint, NH_CLS_STATIC4, NH_CLS_STATIC4, 2u, d->simple, fs, sv, av);
-			} else
-				NH_LAUNCH(ctx, "solve_still", (k_solve_one_body<4, true, true, 1, true>), (B + 63u) / 64u, 64, B, d->body_class, d->body_off, d->adj, d->bodies, bodies->properties, bodies->momentum,
-				          (float4*)d->states, iterations, ctx->raw_data, bodies->transforms, d->impulses, cv, ctx->hint, NH_CLS_STATIC4, NH_CLS_STATIC4, 2u, d->simple, fs, sv, nh_AheadView());
-			ss.ahead_ready = ahead;
-			ss.pair_ready = pair;
-			if (ss.pipelined && ss.h_ring[0]) {
-				// nh_step: first the verdict of the still step BEFORE this one (its counters landed long ago) ...
-				if (ss.verdict.pending) {
-					if (ss.verdict.event) NH_HIP_CHECK(ctx, hipEventSynchronize(ss.ev_ring[ss.verdict.slot]));
-					else { const int w = nh_still_await_number(ctx); if (w) return w == 2 ? NH_ERR_HIP : NH_INTERNAL_STILL_FAILED; }          // (that step reported itself: its number, spun on)
-					const nh_DevState* h = ss.h_ring[ss.verdict.slot];
-					if (h->still_failed_seq >= ss.verdict.seq || h->error) return NH_INTERNAL_STILL_FAILED;       // (nh_step cleans up and runs both steps again)
-					ss.confirmed_seq = ss.verdict.seq;
-					memcpy(ctx->h_state, h, NH_COUNTER_WORDS * sizeof(uint32_t));
-					if (!ctx->idle_unknown) { ctx->idle_bound = (int)h->max_idle[ss.verdict.parity]; ctx->idle_bound_mark = ss.verdict.collide_mark; }
-					ss.verdict.pending = false;
-					nh_still_note_movers(ctx, h, ss.verdict.seq);
-				}
-				// ... then this step's counters on their way, to be looked at by the next step
-				const int slot = (int)(ctx->collide_seq & 1u);
-				if (!self_report) NH_HIP_CHECK(ctx, hipMemcpyAsync(ss.h_ring[slot], ctx->d_state, NH_COUNTER_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-				// (a step that reports itself -- not in two launches, not under option "no_early_counts" -- needs no event: the host takes its verdict from the number in the slot)
-				const bool ring_event = !self_report || ctx->halo_split.launched || ctx->no_early_counts;
-				if (ring_event) NH_HIP_CHECK(ctx, hipEventRecord(ss.ev_ring[slot], ctx->stream));
-				ss.verdict.event = ring_event;
-				ss.verdict.pending = true; ss.verdict.seq = ctx->collide_seq; ss.verdict.parity = ctx->step_parity; ss.verdict.slot = slot; ss.verdict.collide_mark = ctx->collide_mark;
-				confirmed = true;          // (until the next step says otherwise)
-			} else if (ss.early_verdict) {
-				// nh_partition_step, a step that started at the solver: everything such a step can fail on is checked by its PROLOGUE (k_pair_begin: the step-wide words,
-				// body 0, the pairs that are nobody's or a ghost's -- the lanes' checks belong to the NEXT step), whose counters nh_collide sent on their way before this
-				// solver was launched.  The host waits for THAT copy -- the solver runs on -- so the next sub-step's halo and launches queue up behind it: no bubble
-				ss.early_verdict = false;
-				NH_HIP_CHECK(ctx, hipEventSynchronize(ss.ev_ring[0]));
-				const nh_DevState* h = ss.h_ring[0];
-				confirmed = h->still_failed_seq < ctx->collide_seq && h->error == 0u;
-				if (confirmed) {
-					ss.confirmed_seq = ctx->collide_seq;
-					memcpy(ctx->h_state, h, NH_COUNTER_WORDS * sizeof(uint32_t));
-					if (!ctx->idle_unknown) { ctx->idle_bound = (int)h->max_idle[ctx->step_parity]; ctx->idle_bound_mark = ctx->collide_mark; }
-					nh_still_note_movers(ctx, h, ctx->collide_seq);
-					// (halo split: the step happened -- what the neighbours get of it may leave now, behind the boundary launch on its stream)
-					if (ctx->halo_split.launched && ctx->halo_split.after_verdict) { int rc = ctx->halo_split.after_verdict(ctx, ctx->halo_split.user); if (rc) return rc; }
-				} else {
-					NH_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));          // (the solver has left at once; the replay starts from a quiet stream like every other)
-					if (ctx->halo_split.launched) { NH_HIP_CHECK(ctx, hipStreamSynchronize(ctx->halo_split.stream)); ctx->halo_split.launched = false; }
-				}
-			} else {
-				// the step's one round trip: did every check hold?
-				NH_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_state, ctx->d_state, NH_COUNTER_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-				NH_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-				if (ctx->timing) nh_timer_collect(ctx);
-				confirmed = ctx->h_state->still_failed_seq < ctx->collide_seq && ctx->h_state->error == 0u;
-				if (confirmed) ss.confirmed_seq = ctx->collide_seq;
-				if (confirmed) { nh_Counts c; nh_counts_from_mirror(ctx, &c); nh_still_note_movers(ctx, ctx->h_state, ctx->collide_seq); }              // (the sleep prediction: largest idle counter this step saw)
-			}
+		if (still_usable(ctx, d, bodies, iterations, applied, from_apply, drop_states)) {
+			int rc = still_solve(ctx, d, bodies, iterations);
+			if (!rc) rc = still_verdict(ctx, &confirmed);
+			if (rc) return rc;
 		}
-		if (confirmed) {
-			ss.resolved = true; ss.setup_d = nullptr; ss.note_confirmed();
-			ss.cache_stale = true; ss.contacts_stale = true;        // (the caller's cache and dense contact arrays are last written by an earlier step: nh_still_sync_outputs)
-			if (ss.sleepers) { ss.views_sleepers = true; ss.sleep_pairs_current = false; ss.active_current = false; }            // (... and so are its active list and sleeping pairs)
-			d->finish_pending = false; d->has_late = false; d->has_static8 = d->has_staticN = false; d->static_inert = true; d->general_contacts = 0; d->levels = 0;
-			d->imp->cull_pending = false; d->imp->lookup_pending = false;
-			ctx->last_general_contacts = 0;
-			ctx->grav.pending = false; ctx->grav.rest_pending = false;
-			ctx->adv.done = true; ctx->adv.time_step = ctx->grav.time_step; ctx->adv.body_class = d->body_class; ctx->adv.rest = false;
-			return NH_OK;
-		}
+		if (confirmed) { still_confirmed(ctx, d); return NH_OK; }
 		// not a still step after all (a check failed on the device, or the caller left the sample's order): the step again, in full
 		{ int rc = nh_still_abandon(ctx); if (rc) return rc; }
 	}
 	if (!d->finish_pending) { int rc = settle_gravity(ctx); if (rc) return rc; }
 	if (d->finish_pending) {
-		d->finish_pending = false;
-		const uint32_t B = d->body_count;
-		nh_CacheView cv = { d->imp->tags, d->imp->features, d->imp->ctags, d->imp->cfeatures, d->imp->cdata, ctx->d_state };
-		nh_FusedStep fs = nh_FusedStep();
-		const bool gravity_here = ctx->grav.pending && ctx->grav.momentum == bodies->momentum;
-		if (ctx->grav.pending && !gravity_here) { int rc = settle_gravity(ctx); if (rc) return rc; }
-		if (gravity_here) {
-			ctx->grav.pending = false;
-			fs.gx_dt = ctx->grav.gx_dt; fs.gy_dt = ctx->grav.gy_dt; fs.gz_dt = ctx->grav.gz_dt; fs.damping = ctx->grav.damping; fs.time_step = ctx->grav.time_step;
-			fs.bits = 1u;
-			if (from_apply && bodies->idle_counters) { fs.bits |= 2u; fs.idle = bodies->idle_counters; ctx->adv.done = true; ctx->adv.time_step = fs.time_step; ctx->adv.body_class = d->body_class; }
-		}
-		// (early counters: not with EVERY launch timed -- the events of a step are collected at its round trip, when they must have happened; timing restricted to one kernel, what
-		// bench.py keeps on, collects at nh_kernel_times -- and not under the legacy observer contract, whose round trips do more than read)
-		d->early_seq = 0u;
-		if (ctx->h_early && !ctx->no_early_counts && B != 0u && !(ctx->timing && ctx->timing_filter.empty()) && !ctx->sync_exports_views && !(ctx->flags & NH_FLAG_SYNC_COUNTS)) {
-			fs.host_counters = ctx->h_early; fs.seq = ctx->collide_seq; d->early_seq = ctx->collide_seq;
-		}
-		NH_LAUNCH(ctx, "solve_one_body", (k_solve_one_body<4, true, true, 1>), (B + 63u) / 64u, 64, B, d->body_class, d->body_off, d->adj, d->bodies, bodies->properties, bodies->momentum,
-		          (float4*)d->states, iterations, d->contact_data, bodies->transforms, d->impulses, cv, ctx->hint, NH_CLS_STATIC4, NH_CLS_STATIC4,
-		          1u | (drop_states ? 2u : 0u), d->simple, fs, nh_StillView(), nh_AheadView());
-		ctx->grav.rest_pending = gravity_here;        // everybody else's gravity: finish_setup, once the round trip has told whether there is anybody else
-		int rc = finish_setup(ctx, d);
+		int rc = speculative_launch(ctx, d, bodies, iterations, from_apply, drop_states);
 		if (rc) return rc;
 		early4_done = d->static_inert;          // (if body 0 is not inert the speculative launch left at once and the general kernels take everything)
 	}
-	launch_apply_static(ctx, d, bodies, iterations, true, early4_done, drop_states);
+	launch_apply_static<true>(ctx, d, bodies, iterations, early4_done, drop_states);
 	return NH_OK;
 }
 
@@ -2679,33 +2698,14 @@ extern "C" int nh_apply_impulses(nh_context* ctx, nh_ContactConstraintData* d, c
 	d->setup_pending = false;
 	ctx->pending = nullptr;
 	if (first) { int rc = first_apply(ctx, d, bodies, iterations, true); if (rc) return rc; }
-	else { int rc = settle_gravity(ctx); if (rc) return rc; launch_apply_static(ctx, d, bodies, iterations, false, false); }
+	else { int rc = settle_gravity(ctx); if (rc) return rc; launch_apply_static<false>(ctx, d, bodies, iterations, false); }
 	if (d->general_contacts && d->blk.active) {
 		const bool warm = d->blk.warm_pending;
 		d->blk.warm_pending = false;
 		blk_run(ctx, d, bodies, warm, iterations);
-	} else if (d->general_contacts && d->resident) {
-		// small general set: one workgroup, rows in LDS for all sweeps (k_solve_resident)
-		if (iterations)
-			NH_LAUNCH(ctx, "solve_resident", k_solve_resident, 1, NH_RES_THREADS, ctx->d_state, d->cont.level_hist, d->levels, d->level_order, d->gpair, (const nh_CachedContactImpulse*)nullptr,
-			          bodies->momentum, (const float4*)d->rows, (size_t)d->contact_capacity, d->gstates, iterations, 0u, d->resident_cap);
-	} else if (d->general_contacts && d->resident_bodies) {
-		if (iterations)
-			NH_LAUNCH(ctx, "solve_resident_bodies", k_solve_resident_bodies, 1, NH_RESB_THREADS, ctx->d_state, d->cont.level_hist, d->cont.level_hist + (NH_MAX_LEVELS + 2), d->levels,
-			          d->level_order, d->gpair, (const nh_CachedContactImpulse*)nullptr, bodies->momentum, d->body_count, (const float4*)d->rows, (size_t)d->contact_capacity, d->gstates,
-			          iterations, 0u);
-	} else if (d->general_contacts) {
-		for (uint32_t it = 0; it < iterations; ++it)
-			for (uint32_t l = 1; l <= d->levels; ++l) {
-				uint32_t b = d->level_off[l], e = d->level_off[l + 1];
-				if (e > b && !d->level_full[l])
-					NH_LAUNCH(ctx, "apply_level", (k_level_exec<false, true>), nh_grid_for(e - b, 256, 8192), 256, d->level_order, b, e, d->gpair, (const nh_CachedContactImpulse*)nullptr,
-					          bodies->momentum, (const float4*)d->rows, (size_t)d->contact_capacity, d->gstates);
-				else if (e > b)
-					NH_LAUNCH(ctx, "apply_level", (k_level_exec<false>), nh_grid_for(e - b, 256, 4096), 256, d->level_order, b, e, d->gpair, (const nh_CachedContactImpulse*)nullptr,
-					          bodies->momentum, (const float4*)d->rows, (size_t)d->contact_capacity, d->gstates);
-			}
-	}
+	} else if (d->general_contacts && (d->resident || d->resident_bodies)) {
+		if (iterations) launch_resident(ctx, d, bodies, d->levels, nullptr, iterations, 0u);          // small general set: one workgroup for all sweeps
+	} else if (d->general_contacts) for (uint32_t it = 0; it < iterations; ++it) launch_levels<false>(ctx, d, bodies, nullptr);
 	return NH_OK;
 }
 

@@ -551,7 +551,7 @@ def test_a_sleeper_the_caller_moves_stays_where_the_caller_put_it(variant):
     sub-steps: the speculating library and the one with option no_sleeper_skip against the library that runs every step in full -- bodies, idle counters, contacts,
     sleeping pairs, active list, cache, counters bit for bit -- and the speculating one did take still steps past the move.
     What keeps (i) and (iv) right on a library WITHOUT own_current are two guards, not the flag: a sleeper in contact with an awake body makes general contacts, and
-    nh_solve.hip:2220-2221 (`ok_next` needs `general_contacts == 0`) offers no still step while they last (measured: 0 of 77, no replay); one whose box merely overlaps
+    nh_solve.hip, `outlook_for_next_step` (`ok_next` needs `general_contacts == 0`) offers no still step while they last (measured: 0 of 77, no replay); one whose box merely overlaps
     an awake body's fails every still step in k_narrowphase's sleepers form, nh_collide.hip:1160-1165 (two dynamic bodies with a sleeping end: "not this step's
     business").  So in (i), (iv) and (iii) the movers are taken off again after the four calls and the calls repeated: the still steps must come back.  What the flag
     itself changes is pinned in (iii): while two sleepers overlap NO still step may be confirmed -- a library that skips the new pair on the strength of stale marks
