@@ -79,7 +79,7 @@
  *      exported the views: nh_set_option(ctx, "sync_exports_views", 1) restores that contract at its old price; INTEGRATION.md.)  Any entry point outside the sample's
  *      call order between nh_collide and nh_apply_impulses turns a still step into a full one first, so everything it observes is what a full step
  *      produces.  nh_Counts.still_steps / still_replays count them.
- *      The scene queries (nh_query_build, nh_query_refit, nh_raycast, nh_spherecast, nh_raycast_all, nh_spherecast_all, nh_boxcast_all, nh_capsulecast_all, nh_boxcast, nh_capsulecast, nh_overlap, nh_penetration, nh_closest, nh_closest_k, nh_distance) are not entry points of the step in this sense: they neither export nor settle nor turn a still step into a
+ *      The scene queries (nh_query_build, nh_query_refit, nh_raycast, nh_spherecast, nh_raycast_all, nh_spherecast_all, nh_boxcast_all, nh_capsulecast_all, nh_raycast_k, nh_spherecast_k, nh_boxcast_k, nh_capsulecast_k, nh_boxcast, nh_capsulecast, nh_overlap, nh_penetration, nh_closest, nh_closest_k, nh_distance) are not entry points of the step in this sense: they neither export nor settle nor turn a still step into a
  *      full one, and they do not count -- see "scene queries" below.
  *
  * Threading: one context = one HIP stream = one world at a time; no global mutable state.
@@ -460,7 +460,8 @@ int nh_spherecast(nh_context* ctx, const nh_SphereCast* casts, uint32_t count, n
    bits(count) + 32 + bits(colliders) <= 64 and by two otherwise.  NOT MEASURED YET: tools/castall_rates.py times both calls (count only, count + list) on the landed config-2 world beside nh_raycast / nh_spherecast on the same records
    and nh_overlap in list mode, and writes profiles/castall_rates.log; no GPU run of it has been made, so neither ratio (count walk / closest-hit cast, list chain / nh_overlap's per record) is known.
    The all-hits casts of the other two shapes: nh_boxcast_all / nh_capsulecast_all, declared behind nh_capsulecast, whose records they read.
-   Not built: exits, a per-query hit limit ("the first k"). */
+   The first k of each cast in one launch: nh_raycast_k / nh_spherecast_k, behind nh_capsulecast_all.
+   Not built: exits. */
 int nh_raycast_all(nh_context* ctx, const nh_Ray* rays, uint32_t count, uint32_t* offsets /* count + 1 */, nh_RayHit* hits, uint32_t capacity,
                    uint32_t flags /* 0 */);
 int nh_spherecast_all(nh_context* ctx, const nh_SphereCast* casts, uint32_t count, uint32_t* offsets /* count + 1 */, nh_RayHit* hits, uint32_t capacity,
@@ -559,11 +560,58 @@ int nh_capsulecast(nh_context* ctx, const nh_CapsuleCast* casts, uint32_t count,
    synchronise: the scratch is nh_overlap's own, and nothing else is allocated.
    Cost: nh_raycast_all's chain with the box's / the capsule's predicates at the leaves -- the walk prunes by max_t only and runs twice (count, list), then
    one or two radix sorts and a gather that evaluates the predicate a third time for the written records (figures, or NOT MEASURED YET).
-   Not built: exits, a per-query hit limit ("the first k"), rotating sweeps. */
+   The first k of each cast in one launch: nh_boxcast_k / nh_capsulecast_k, below.
+   Not built: exits, rotating sweeps. */
 int nh_boxcast_all(nh_context* ctx, const nh_BoxCast* casts, uint32_t count, uint32_t* offsets /* count + 1 */, nh_RayHit* hits, uint32_t capacity,
                    uint32_t flags /* 0 */);
 int nh_capsulecast_all(nh_context* ctx, const nh_CapsuleCast* casts, uint32_t count, uint32_t* offsets /* count + 1 */, nh_RayHit* hits, uint32_t capacity,
                        uint32_t flags /* 0 */);
+
+/* nh_raycast_k / nh_spherecast_k / nh_boxcast_k / nh_capsulecast_k: the FIRST `k` colliders along each of `count` casts, in order -- a bullet that goes
+   through at most three crates, line of sight that skips the first thing it meets when the caller filters it by tag, a controller that wants the first
+   few things ahead of its hull, a sensor with a fixed number of returns.  Input records are the closest-hit calls' (nh_Ray, nh_SphereCast, nh_BoxCast,
+   nh_CapsuleCast), output records nh_RayHit at a fixed stride of k per cast, as in nh_closest_k; `k` is one value per call, 1 .. NH_CAST_K_MAX.
+     - THE CONTRACT: for cast i let S_i be the segment nh_<shape>cast_all lists for the same record on the same build or refit -- the same set, the same
+       records, ascending t compared as floats (-0 equals +0), ties by combined collider index ascending -- and m_i = min(k, |S_i|).  Then
+       hits[i*k + j] for j < m_i holds, byte for byte, record j of S_i; hits[i*k + j] for j >= m_i holds the miss record the closest-hit call writes
+       for that cast (shape = NH_SHAPE_NONE, normal = 0, body = collider = tag = 0xffffffff, t = max_t -- t = NaN for a record the closest-hit call
+       writes as t = NaN); counts[i] = m_i where `counts` is not NULL.  Every byte of all count * k records is written and nothing behind them.
+   What follows are identities of that contract and the contracts above:
+     - PREFIX: for k < k' the records under k are the first k records of each cast under k';
+     - k = 1 IS THE CLOSEST-HIT CALL with flags = 0: `hits` holds exactly the bytes nh_raycast (nh_spherecast, nh_boxcast, nh_capsulecast) writes for
+       the same records -- the all-hits calls' FIRST RECORD contract where the segment is not empty, the miss otherwise;
+     - DEGENERATE SHAPES write the simpler call's bytes, counts and records: a box of size (0, 0, 0) those of nh_raycast_k for the same first 32 bytes;
+       a capsule of half_height 0 those of nh_spherecast_k for the same first 32 bytes and radius; a ball of radius 0 those of nh_raycast_k; a capsule
+       of radius = half_height = 0 those of nh_raycast_k.  Rotations are not read where the closest-hit call does not read them;
+     - REFIT: the bytes after nh_query_refit are the bytes after an nh_query_build of the same arrays;
+     - an INVALID record (one the closest-hit call writes with t = NaN) counts 0 and writes k misses of t = NaN;
+     - a NaN max_t lists nothing (t <= NaN is false); its k misses carry t = max_t, the NaN itself.  max_t = +inf finds the first k anywhere ahead;
+     - a ZERO DIRECTION lists the colliders the shape overlaps at t = 0, with the NaN normal, the lowest combined index first, and nothing else;
+     - `ignore_body` and colliders of a NaN pose behave as in the all-hits calls: never listed.
+   Returns NH_ERR_INVALID, in nh_closest_k's order of checks: before any nh_query_build; for flags != 0 (NH_RAY_ANY_HIT included: it has no meaning
+   here); for k = 0 or k > NH_CAST_K_MAX; for count >= 2^30; then, for count > 0, for `casts` or `hits` null or not 16-byte aligned and for `counts` not
+   4-byte aligned.  count = 0 is a no-op that returns NH_OK and launches nothing.  A refused call writes nothing.
+   An OBSERVER like nh_raycast (note 9): no view export, no settling of deferred gravity, no still step turned into a full one, no change to nh_Counts.
+   It never allocates and never waits: ONE launch on the context's stream (timing labels q_raycast_k, q_spherecast_k, q_boxcast_k, q_capsulecast_k),
+   where the all-hits chain walks twice, sorts once or twice, gathers, and has the caller read a total back to size `hits`.
+   One lane per cast keeps its list of k (t, combined index) pairs in LDS and prunes the walk at the k-th t so far (why that is exact);
+   the records are rebuilt from the listed colliders as the all-hits gather rebuilds them.
+   MEASURED (tools/castk_rates.py -> profiles/castk_rates.log; one MI355X, 1,048,576 incoherent casts on the landed config-2 world of 1,004,524
+   colliders, beside the closest-hit call and the all-hits count + list calls on the same records): at k = 1 a shape with a size costs 0.91 - 1.03 of
+   its closest-hit call and a ray 5.7 x nh_raycast (its walk takes the all-hits node pad); the k call takes 0.18 - 0.29 of count + list at k = 1,
+   0.33 - 0.38 at k = 4 and 0.48 - 0.81 at k = 32.  DESIGN 10.13 has the table.
+   Where nh_raycast itself loses a far grazing hit that the ray predicates accept by rounding, the k = 1 identity holds with the
+   all-hits first record, not with nh_raycast's bytes.
+   Not built: a per-cast k, exits, filters by tag. */
+#define NH_CAST_K_MAX 32u
+int nh_raycast_k(nh_context* ctx, const nh_Ray* rays, uint32_t count, uint32_t k,
+                 uint32_t* counts /* count words, or NULL */, nh_RayHit* hits /* count * k */, uint32_t flags /* 0 */);
+int nh_spherecast_k(nh_context* ctx, const nh_SphereCast* casts, uint32_t count, uint32_t k,
+                    uint32_t* counts /* count words, or NULL */, nh_RayHit* hits /* count * k */, uint32_t flags /* 0 */);
+int nh_boxcast_k(nh_context* ctx, const nh_BoxCast* casts, uint32_t count, uint32_t k,
+                 uint32_t* counts /* count words, or NULL */, nh_RayHit* hits /* count * k */, uint32_t flags /* 0 */);
+int nh_capsulecast_k(nh_context* ctx, const nh_CapsuleCast* casts, uint32_t count, uint32_t k,
+                     uint32_t* counts /* count words, or NULL */, nh_RayHit* hits /* count * k */, uint32_t flags /* 0 */);
 
 /* nh_closest: how far each of `count` points lies from the world of the LAST nh_query_build, and where the nearest surface is -- depenetration, "snap to
    the nearest surface", proximity and cover tests, keeping a distance from everything.  `reserved` is not read.  Exact predicates: nudge_amd/csrc/nh_query.h.

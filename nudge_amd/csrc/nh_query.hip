@@ -375,7 +375,7 @@ struct nh_QRay : nh_QCastHead {
 	__device__ __forceinline__ nh_QHit leaf(const nh_QShape& c, bool box, float) const {
 		return box ? nh_q_ray_box(o, d, c.p, c.q, c.h) : nh_q_ray_sphere(o, d, c.p, c.h.x);
 	}
-	static constexpr int ALL_WAVES = 0;
+	static constexpr int ALL_WAVES = 0, K_WAVES = 0;
 	__device__ __forceinline__ bool raylike() const { return true; }
 	__device__ __forceinline__ float grow() const { return w; }
 	__device__ __forceinline__ void entry(const nh_QShape&, bool, float&) const {}
@@ -398,7 +398,7 @@ struct nh_QBall : nh_QCastHead {
 		if (r > 0.0f && t0 > hit.t) hit.t = t0;
 		return hit;
 	}
-	static constexpr int ALL_WAVES = 0;
+	static constexpr int ALL_WAVES = 0, K_WAVES = 0;
 	__device__ __forceinline__ bool raylike() const { return !(r > 0.0f); }
 	__device__ __forceinline__ float grow() const { return w; }
 	__device__ __forceinline__ void entry(const nh_QShape& c, bool box, float& t0) const { if (r > 0.0f) nh_q_leaf_entry(o, inv, w, c.p, c.q, c.h, box, t0); }
@@ -428,7 +428,7 @@ struct nh_QBox : nh_QCastHead {
 		if (!ray && t0 > hit.t) hit.t = t0;
 		return hit;
 	}
-	static constexpr int ALL_WAVES = 4;
+	static constexpr int ALL_WAVES = 4, K_WAVES = 3;
 	__device__ __forceinline__ bool raylike() const { return ray; }
 	__device__ __forceinline__ float grow() const { return w.x; }          // (ray-like: the three are one number, the ray's)
 	__device__ __forceinline__ void entry(const nh_QShape& c, bool box, float& t0) const { if (!ray) nh_q_leaf_entry3(o, inv, w, c.p, c.q, c.h, box, t0); }
@@ -457,7 +457,7 @@ struct nh_QCapsule : nh_QCastHead {
 		if ((r > 0.0f || hh > 0.0f) && t0 > hit.t) hit.t = t0;
 		return hit;
 	}
-	static constexpr int ALL_WAVES = 4;
+	static constexpr int ALL_WAVES = 4, K_WAVES = 4;
 	__device__ __forceinline__ bool raylike() const { return r == 0.0f && hh == 0.0f; }
 	__device__ __forceinline__ float grow() const { return w.x; }
 	__device__ __forceinline__ void entry(const nh_QShape& c, bool box, float& t0) const { if (r > 0.0f || hh > 0.0f) nh_q_leaf_entry3(o, inv, w, c.p, c.q, c.h, box, t0); }
@@ -955,6 +955,59 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(Shape::ALL_
 	}
 }
 
+// ---- first-k casts ------------------------------------------------------------------------------------------------------------------------------
+// nh_raycast_k / nh_spherecast_k / nh_boxcast_k / nh_capsulecast_k: the first k records of the all-hits segment of each cast, in ONE launch.  One lane
+// per cast on nh_q_walk, the decode, node test and per-collider decision (S::all) of k_q_castall, and k_q_closest_k's list in place of the count:
+//   list   nh_QNear / nh_q_nearest_insert (nh_query.h) unchanged, key = t, max_d = max_t.  Its order, nh_q_closer, is ascending key as floats (-0 equals
+//          +0), ties to the lower combined index: the all-hits order.  In LDS, slot-major: entry j of lane l at lds[j * blockDim.x + l], dynamic shared
+//          memory of blockDim.x * k * 8 bytes, the block size from nh_q_nearest_block(k) (the table at k_q_closest_k); no register array is indexed
+//          dynamically.  A lane that takes another cast (the grid is capped) starts again from held = 0: nothing of the last list is read.
+//   bound  bd, in a register: max_t while fewer than k are held, the k-th t once the list is full, reloaded from the last slot after an insert that
+//          changed a full list.  The node test is k_q_castall's with bd in place of max_t; a leaf whose t is not <= bd is dropped by that one compare
+//          without touching LDS (equality goes on: a tie can still win by index).
+//   exact  DESIGN 10.13: bd is never below the final k-th t, and the entry t0 of every ancestor of a listed collider is at most the collider's t.
+//   out    the list holds (t, index) only: each held entry is rebuilt as k_q_castall_gather rebuilds a record (the record re-read, S::entry, S::all --
+//          the same function on the same inputs, the same bits) and leaves through nh_q_write_hit; the k - held miss records follow (t = max_t, or a
+//          quiet NaN for an invalid cast: the closest-hit call's miss), then counts[i] = held.  No normal is kept in LDS.
+// The box and capsule instantiations take their siblings' waves-per-EU hint (ALL_WAVES).
+template <class Shape>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(Shape::K_WAVES))) void k_q_cast_k(const float4* __restrict__ casts, uint32_t count, uint32_t kk,
+                                                   uint32_t* __restrict__ counts, nh_RayHit* __restrict__ hits, const nh_QNode* __restrict__ nodes,
+                                                   const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox) {
+	extern __shared__ nh_QNear q_first[];
+	const uint32_t stride = blockDim.x;
+	nh_QNear* const list = q_first + threadIdx.x;
+	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
+		Shape k;
+		k.read(casts + (size_t)i * Shape::WORDS);
+		const bool ray = k.raylike();
+		float bd = k.max_t;
+		uint32_t held = 0u;
+		nh_q_walk(nodes, rec, k.ok && n ? 0u : NH_Q_NONE, k.ignore,
+			[&](nh_f3 lo, nh_f3 hi, float& t0) {
+				if (ray) return nh_q_cast_node(lo, hi, k.o, k.inv, k.grow() + nh_q_all_pad(lo, hi, k.o), t0) && t0 <= bd;
+				return k.node(lo, hi, t0) && t0 <= bd;
+			},
+			[&](uint32_t c, const nh_QRec& q, float t0) {
+				const nh_QHit h = k.all(nh_q_unpack(q), c < nbox, t0);
+				if (!h.hit || !(h.t <= bd)) return false;
+				if (nh_q_nearest_insert(list, stride, kk, &held, h.t, c, k.max_t) && held == kk) bd = list[(kk - 1u) * stride].key;
+				return false;
+			});
+		nh_RayHit* out = hits + (size_t)i * kk;
+		for (uint32_t j = 0u; j < held; ++j) {
+			const uint32_t c = list[j * stride].c;
+			const nh_QShape s = nh_q_unpack(rec[c]);
+			float t0 = 0.0f;
+			k.entry(s, c < nbox, t0);                          // (entered: the walk listed it)
+			const nh_QHit h = k.all(s, c < nbox, t0);
+			nh_q_write_hit(out + j, rec, nbox, true, c, h.t, h.n);
+		}
+		for (uint32_t j = held; j < kk; ++j) nh_q_write_hit(out + j, rec, nbox, k.ok, NH_Q_NONE, k.max_t, nh_make3(0.0f, 0.0f, 0.0f));
+		if (counts) counts[i] = held;
+	}
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------------------------------
 void nh_query_free(nh_context* ctx) {
 	nh_QueryState* q = ctx->query;
@@ -1309,4 +1362,40 @@ extern "C" int nh_capsulecast_all(nh_context* ctx, const nh_CapsuleCast* casts, 
                                   uint32_t flags) {
 	NH_CASTALL_LABELS("q_capsulecast_all");
 	return nh_castall<nh_QCapsule>(ctx, label, casts, count, offsets, hits, capacity, flags);
+}
+
+// The four first-k casts: nh_closest_k's checks in nh_closest_k's order, one launch with the lists' LDS sized by k (the table at k_q_closest_k); no
+// allocation, no wait.  The grid is capped at NH_Q_CAST_K_GRID workgroups -- what 256 CUs hold of the 256-lane ones at 8 waves per SIMD -- so a batch of
+// half a million casts or more goes round the kernel's loop, each lane starting its list again from empty.
+#define NH_Q_CAST_K_GRID 2048u
+template <class Shape>
+static int nh_cast_k(nh_context* ctx, const char* label, const void* casts, uint32_t count, uint32_t k, uint32_t* counts, nh_RayHit* hits, uint32_t flags) {
+	if (!ctx || !ctx->query || !ctx->query->built) return NH_ERR_INVALID;
+	if (flags != 0u || k == 0u || k > NH_CAST_K_MAX || count >= (1u << 30)) return NH_ERR_INVALID;
+	if (count == 0u) return NH_OK;
+	if (!casts || !hits || (((uintptr_t)casts | (uintptr_t)hits) & 15u) || ((uintptr_t)counts & 3u)) return NH_ERR_INVALID;    // (records are moved as 16-byte words)
+	NH_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+	nh_QueryState* q = ctx->query;
+	const uint32_t block = nh_q_nearest_block(k);
+	if (ctx->timing) nh_timer_begin(ctx, label);
+	hipLaunchKernelGGL(k_q_cast_k<Shape>, dim3(nh_grid_for(count, block, NH_Q_CAST_K_GRID)), dim3(block), block * k * sizeof(nh_QNear), ctx->stream,
+	                   static_cast<const float4*>(casts), count, k, counts, hits, q->nodes, q->rec, q->n, q->nbox);
+	if (ctx->timing) nh_timer_end(ctx);
+	return NH_OK;
+}
+
+extern "C" int nh_raycast_k(nh_context* ctx, const nh_Ray* rays, uint32_t count, uint32_t k, uint32_t* counts, nh_RayHit* hits, uint32_t flags) {
+	return nh_cast_k<nh_QRay>(ctx, "q_raycast_k", rays, count, k, counts, hits, flags);
+}
+
+extern "C" int nh_spherecast_k(nh_context* ctx, const nh_SphereCast* casts, uint32_t count, uint32_t k, uint32_t* counts, nh_RayHit* hits, uint32_t flags) {
+	return nh_cast_k<nh_QBall>(ctx, "q_spherecast_k", casts, count, k, counts, hits, flags);
+}
+
+extern "C" int nh_boxcast_k(nh_context* ctx, const nh_BoxCast* casts, uint32_t count, uint32_t k, uint32_t* counts, nh_RayHit* hits, uint32_t flags) {
+	return nh_cast_k<nh_QBox>(ctx, "q_boxcast_k", casts, count, k, counts, hits, flags);
+}
+
+extern "C" int nh_capsulecast_k(nh_context* ctx, const nh_CapsuleCast* casts, uint32_t count, uint32_t k, uint32_t* counts, nh_RayHit* hits, uint32_t flags) {
+	return nh_cast_k<nh_QCapsule>(ctx, "q_capsulecast_k", casts, count, k, counts, hits, flags);
 }

@@ -44,6 +44,7 @@ EXPORTS = [
     "nh_partition_pack_momentum", "nh_partition_unpack_momentum", "nh_partition_exchange_iteration", "nh_partition_unpack_ghosts", "nh_partition_pack_step", "nh_partition_unpack_step", "nh_partition_choose_cut", "nh_partition_set_cut",
     "nh_partition_set_transport", "nh_partition_exchange_step", "nh_partition_step", "nh_partition_transport_check", "nh_partition_transport_result", "nh_set_first_ghost_body",
     "nh_query_build", "nh_query_refit", "nh_query_stats", "nh_raycast", "nh_overlap", "nh_penetration", "nh_spherecast", "nh_raycast_all", "nh_spherecast_all", "nh_boxcast_all", "nh_capsulecast_all", "nh_boxcast", "nh_capsulecast", "nh_closest", "nh_closest_k", "nh_distance",
+    "nh_raycast_k", "nh_spherecast_k", "nh_boxcast_k", "nh_capsulecast_k",
 ]
 HALO_RECORD_BYTES = 64
 
@@ -272,6 +273,10 @@ def lib():
         L.nh_capsulecast.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
         L.nh_closest.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
         L.nh_closest_k.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]
+        # (likewise the first-k casts: World.raycast_k and its siblings then raise AttributeError)
+        if hasattr(L, "nh_raycast_k"):
+            for fn in (L.nh_raycast_k, L.nh_spherecast_k, L.nh_boxcast_k, L.nh_capsulecast_k):
+                fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]
         # (an older build of the library, loaded through NUDGE_HIP_LIBRARY for an A/B, has no nh_distance: World.distance then raises AttributeError)
         if hasattr(L, "nh_distance"):
             L.nh_distance.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
@@ -839,6 +844,66 @@ class World:
         capacity rule and result (normal: from the collider to the capsule); the first record of a cast is capsulecast()'s closest hit."""
         casts, n = self._capsule_casts("capsulecast_all", origins, directions, radii, half_heights, rotations, max_t, ignore_body)
         return self._castall(self.capsulecast_all_records, casts, n, capacity, synchronize)
+
+    def _castk_records(self, name, size, casts, k, counts, hits):
+        torch = self.torch
+        n = casts.numel() * casts.element_size() // size
+        if counts is None:
+            counts = torch.empty(n, dtype=torch.int32, device=self.dev)
+        if hits is None:
+            hits = torch.empty((n, max(int(k), 0), 32), dtype=torch.uint8, device=self.dev)
+        _check(self.L, getattr(self.L, name)(self.ctx, C.c_void_p(casts.data_ptr() if n else 0), n, k, C.c_void_p(counts.data_ptr() if n else 0),
+                                             C.c_void_p(hits.data_ptr() if n else 0), 0), name)
+        return counts, hits
+
+    def raycast_k_records(self, rays, k, counts=None, hits=None):
+        """nh_raycast_k on records already laid out as nh_Ray: `rays` a contiguous device tensor of count x 32 bytes (any dtype).  Returns
+        (counts, hits): the count words as an int32 device tensor (`counts`, or a new one) and the count x k x 32-byte uint8 device tensor of
+        nh_RayHit records (`hits`, or a new one), the k of a cast in ascending t, misses behind them.  Enqueued; nothing waits or allocates."""
+        return self._castk_records("nh_raycast_k", 32, rays, k, counts, hits)
+
+    def spherecast_k_records(self, casts, k, counts=None, hits=None):
+        """nh_spherecast_k on records already laid out as nh_SphereCast (count x 48 bytes): raycast_k_records for swept balls."""
+        return self._castk_records("nh_spherecast_k", 48, casts, k, counts, hits)
+
+    def boxcast_k_records(self, casts, k, counts=None, hits=None):
+        """nh_boxcast_k on records already laid out as nh_BoxCast (count x 64 bytes): raycast_k_records for swept oriented boxes."""
+        return self._castk_records("nh_boxcast_k", 64, casts, k, counts, hits)
+
+    def capsulecast_k_records(self, casts, k, counts=None, hits=None):
+        """nh_capsulecast_k on records already laid out as nh_CapsuleCast (count x 64 bytes): raycast_k_records for swept capsules."""
+        return self._castk_records("nh_capsulecast_k", 64, casts, k, counts, hits)
+
+    def _castk(self, records, casts, n, k, synchronize):
+        counts, raw = records(casts, k)
+        hits = self._ray_hits(raw, synchronize)
+        return counts.to(self.torch.int64), {name: v if name == "raw" else v.reshape((n, k) + tuple(v.shape[1:])) for name, v in hits.items()}
+
+    def raycast_k(self, origins, directions, k, max_t=float("inf"), ignore_body=None, synchronize=False):
+        """The first `k` (1 .. 32) colliders along each of n rays (nh_raycast_k), against the last query_build(); the other arguments are raycast()'s.
+        Returns (counts, hits): counts (n, int64: how many of the k slots of a ray hold a hit) and raycast()'s dict shaped (n, k) -- t, normal
+        ((n, k, 3)), body, collider, shape, tag (0xffffffff in the slots behind the count, whose t is max_t) and `raw`, the nh_RayHit records
+        (n x k x 32 bytes) -- in ascending t, ties by combined collider index; the first is raycast()'s closest hit.  One launch, whatever the
+        casts pierce; nothing waits for the device unless `synchronize`."""
+        rays, n = self._cast_head("raycast_k", origins, directions, max_t, ignore_body, 8)
+        return self._castk(self.raycast_k_records, rays, n, k, synchronize)
+
+    def spherecast_k(self, origins, directions, radii, k, max_t=float("inf"), ignore_body=None, synchronize=False):
+        """The first `k` colliders each of n swept balls touches (nh_spherecast_k): spherecast()'s arguments, raycast_k()'s result."""
+        torch = self.torch
+        casts, n = self._cast_head("spherecast_k", origins, directions, max_t, ignore_body, 12)
+        casts[:, 8] = torch.as_tensor(radii, dtype=torch.float32, device=self.dev).reshape(-1)
+        return self._castk(self.spherecast_k_records, casts, n, k, synchronize)
+
+    def boxcast_k(self, origins, directions, half_extents, k, rotations=None, max_t=float("inf"), ignore_body=None, synchronize=False):
+        """The first `k` colliders each of n swept oriented boxes touches (nh_boxcast_k): boxcast()'s arguments, raycast_k()'s result."""
+        casts, n = self._box_casts("boxcast_k", origins, directions, half_extents, rotations, max_t, ignore_body)
+        return self._castk(self.boxcast_k_records, casts, n, k, synchronize)
+
+    def capsulecast_k(self, origins, directions, radii, half_heights, k, rotations=None, max_t=float("inf"), ignore_body=None, synchronize=False):
+        """The first `k` colliders each of n swept capsules touches (nh_capsulecast_k): capsulecast()'s arguments, raycast_k()'s result."""
+        casts, n = self._capsule_casts("capsulecast_k", origins, directions, radii, half_heights, rotations, max_t, ignore_body)
+        return self._castk(self.capsulecast_k_records, casts, n, k, synchronize)
 
     def closest_records(self, queries, hits=None):
         """nh_closest on records already laid out as nh_PointQuery: `queries` a contiguous device tensor of count x 32 bytes (any dtype).  Returns
