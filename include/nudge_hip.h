@@ -79,7 +79,7 @@
  *      exported the views: nh_set_option(ctx, "sync_exports_views", 1) restores that contract at its old price; INTEGRATION.md.)  Any entry point outside the sample's
  *      call order between nh_collide and nh_apply_impulses turns a still step into a full one first, so everything it observes is what a full step
  *      produces.  nh_Counts.still_steps / still_replays count them.
- *      The scene queries (nh_query_build, nh_query_refit, nh_raycast, nh_spherecast, nh_raycast_all, nh_spherecast_all, nh_boxcast_all, nh_capsulecast_all, nh_raycast_k, nh_spherecast_k, nh_boxcast_k, nh_capsulecast_k, nh_boxcast, nh_capsulecast, nh_overlap, nh_penetration, nh_closest, nh_closest_k, nh_distance) are not entry points of the step in this sense: they neither export nor settle nor turn a still step into a
+ *      The scene queries (nh_query_build, nh_query_refit, nh_raycast, nh_spherecast, nh_raycast_all, nh_spherecast_all, nh_boxcast_all, nh_capsulecast_all, nh_raycast_k, nh_spherecast_k, nh_boxcast_k, nh_capsulecast_k, nh_boxcast, nh_capsulecast, nh_overlap, nh_penetration, nh_closest, nh_closest_k, nh_distance, nh_query_set_layers, nh_query_filter, nh_query_layer_info) are not entry points of the step in this sense: they neither export nor settle nor turn a still step into a
  *      full one, and they do not count -- see "scene queries" below.
  *
  * Threading: one context = one HIP stream = one world at a time; no global mutable state.
@@ -403,6 +403,65 @@ typedef struct nh_QueryStats { uint32_t colliders, run_length, runs, top_nodes, 
 int nh_query_refit(nh_context* ctx, const nh_BodyData* bodies, const nh_ColliderData* colliders);
 int nh_query_stats(nh_context* ctx, nh_QueryStats* out);
 
+/* ---- layer masks: per-collider layers, per-query masks -- what a query may see ------------------------------------------------------------------------------
+   A camera ray that must not stop at trigger volumes, a character hull that sweeps against the static world but not against debris, a lidar that does not
+   see its own vehicle, an explosion overlap that wants dynamic bodies only: every collider carries one 32-bit word of LAYER bits, every query a MASK, and
+   collider c is seen by a query with mask m if and only if (layers[c] & m) != 0.  The filter sits inside the walk of the hierarchy: each node carries the
+   OR of the words of the leaves below it, so a subtree that holds nothing a query may see is skipped whole -- a ray that only cares about the ground does
+   not walk through a million boxes.
+   LAYERS.  Until nh_query_set_layers is called every collider's word is 0xffffffff.  nh_query_set_layers copies boxes.count / spheres.count words (the
+   counts of the LAST nh_query_build) from DEVICE memory into storage the library owns, by combined collider index (boxes, then spheres), and computes the
+   node words (2 n - 1 words; nothing is added to the hierarchy's nodes or records); the caller's arrays are free once the call returns -- the copy is
+   enqueued on the context's stream like everything else, so "free" means free to be overwritten by later work on that stream.  One NULL array: all ones
+   for that shape.  Both NULL: the layers are forgotten (every word is 0xffffffff again).  A later nh_query_build with the SAME two counts keeps the
+   collider words and recomputes the node words over the new tree (the layers follow the collider index, not the leaf); a build with other counts forgets
+   them -- another count is another world, nh_query_refit's rule.  nh_query_refit keeps the topology and with it the node words: it launches nothing new
+   and costs what it costs without layers.  With no layers set, build and refit launch exactly what they launch without this section.
+   Returns NH_ERR_INVALID before any nh_query_build and for an array that is not 4-byte aligned.  Its first call (and a later one after the collider
+   count has grown) ALLOCATES about 12 B per collider after a stream synchronise, as nh_overlap's scratch does; nh_destroy frees it.  Otherwise it only
+   enqueues: two copies and the layer pass (timing labels q_layers_runs, q_layers_top).
+   FILTER.  Context state, NH_FILTER_OFF after nh_create, read by EVERY later query call until changed:
+     NH_FILTER_OFF        the library without this section; `mask` and `masks` are not read;
+     NH_FILTER_UNIFORM    every query of a call uses `mask`; `masks` is not read;
+     NH_FILTER_PER_QUERY  query i of a call uses masks[i]: DEVICE memory that must hold `count` words for each later call, retained BY POINTER until the
+                          next nh_query_filter (the words are read when the query runs, not when the filter is set).  NULL or not 4-byte aligned:
+                          NH_ERR_INVALID.
+   An unknown mode, or a call before any nh_query_build, returns NH_ERR_INVALID; a refused call changes nothing -- the next query still uses the previous
+   filter.  nh_query_filter is host state only: nothing is launched, nothing waits.  (The calls' own `flags` argument has no bit to spare for this.)
+   THE CONTRACT, for all nineteen query calls (nh_raycast, nh_spherecast, nh_boxcast, nh_capsulecast, their _all and _k forms, nh_overlap, nh_penetration,
+   nh_closest, nh_closest_k, nh_distance):
+     - MASKED WORLD: with the filter on, a query with mask m writes byte for byte what the same call with the filter OFF writes on a world that is the same
+       except for one thing: every collider with (layers & m) == 0 has a NaN pose -- "a collider of a body that does not exist", which every call above
+       documents as never hit, never listed, never reported.  Collider indices, bodies and tags in the records are those of the real world.  For
+       NH_RAY_ANY_HIT the guarantee is the same hit-or-miss, which is all that flag promises.
+     - Everything else composes with the filter exactly as without it: `ignore_body`, NaN poses, invalid records, NH_RAY_ANY_HIT, capacities, counts and
+       offsets, the tie rules, the reach rule.  The answers above are defined without the tree, so pruning by node words changes the work, never the bytes.
+   Identities that follow:
+     - mask 0 sees nothing: misses with t = max_t (max_distance), empty segments, counts 0;
+     - all-ones layers (or none set) with any non-zero mask write the filter-off bytes;
+     - NH_FILTER_OFF after any mode writes the filter-off bytes;
+     - after nh_query_refit the bytes are those after an nh_query_build of the same arrays.
+   A filter by TAG VALUE is a layer the caller derives from its tags ("layers").
+   All three calls are OBSERVERS (note 9): no view export, no settling of deferred gravity, no still step turned into a full one, no change to nh_Counts.
+   nh_query_layer_info (diagnostic; WAITS for the stream, like nh_query_stats): `set` says whether layers are in force, `colliders` is the last build's
+   count, `any_layers` the root's node word -- the OR over all colliders (0xffffffff while none are set and the world has colliders, 0 for an empty world).
+   The filtered calls launch a second instantiation of each walking kernel under the call's own timing label; the unfiltered kernels are unchanged.
+   MEASURED (tools/filter_rates.py -> profiles/filter_rates.log; one MI355X, 1,048,576 incoherent queries on the landed config-2 world of 1,004,524
+   colliders, the dynamic boxes in layer 2 and body 0's slabs in layer 1; ms per call: filter off / uniform mask 3, sees all / uniform mask 1, static only /
+   per-query masks alternating 1 and 2):
+     nh_raycast              1.952 / 2.238 / 0.303 / 2.105        nh_overlap (count, r = 1)   0.360 / 0.318 / 0.190 / 0.281
+     nh_spherecast r = .75   3.591 / 3.835 / 0.325 / 3.608        nh_closest (unbounded)      1.220 / 1.765 / 2.602 / 2.828
+   A cast that sees only the static world takes 0.09 - 0.16 of the unfiltered call; a mask that sees everything costs 7 - 15 % on the casts and 45 % on
+   nh_closest (a third load per node).  nh_closest under a SPARSE mask is slower than unfiltered (2.1 x): its Morton seed meets only rejected leaves and
+   the walk starts without a bound -- exact, but not fast; a seed that steps out to seen leaves is not built.  nh_query_set_layers 0.19 ms; a build with
+   layers 0.79 ms against 0.59 without; a refit 0.24 either way.  The filter-off calls run at 0.994 - 1.005 of the parent commit's library beside it in the
+   same process (which shows 0.999 - 1.015 against itself).  DESIGN 10.14 has the tables. */
+enum { NH_FILTER_OFF = 0u, NH_FILTER_UNIFORM = 1u, NH_FILTER_PER_QUERY = 2u };
+typedef struct nh_QueryLayerInfo { uint32_t set; uint32_t colliders; uint32_t any_layers; uint32_t reserved; } nh_QueryLayerInfo;
+int nh_query_set_layers(nh_context* ctx, const uint32_t* box_layers /* boxes.count words, or NULL */, const uint32_t* sphere_layers /* spheres.count words, or NULL */);
+int nh_query_filter(nh_context* ctx, uint32_t mode, uint32_t mask, const uint32_t* masks);
+int nh_query_layer_info(nh_context* ctx, nh_QueryLayerInfo* out);
+
 /* nh_spherecast: where a swept ball first touches the world of the LAST nh_query_build -- character controllers, thick projectiles, camera collision.
    nh_SphereCast's first 32 bytes are nh_Ray's fields at the same offsets; `reserved` is not read.  Exact predicates: nudge_amd/csrc/nh_query.h.
      - the swept ball is the ball of radius r = `radius` centred at o + t d, for 0 <= t <= max_t; t is in units of d, as for rays;
@@ -568,7 +627,7 @@ int nh_capsulecast_all(nh_context* ctx, const nh_CapsuleCast* casts, uint32_t co
                        uint32_t flags /* 0 */);
 
 /* nh_raycast_k / nh_spherecast_k / nh_boxcast_k / nh_capsulecast_k: the FIRST `k` colliders along each of `count` casts, in order -- a bullet that goes
-   through at most three crates, line of sight that skips the first thing it meets when the caller filters it by tag, a controller that wants the first
+   through at most three crates, line of sight that skips the first thing it meets, a controller that wants the first
    few things ahead of its hull, a sensor with a fixed number of returns.  Input records are the closest-hit calls' (nh_Ray, nh_SphereCast, nh_BoxCast,
    nh_CapsuleCast), output records nh_RayHit at a fixed stride of k per cast, as in nh_closest_k; `k` is one value per call, 1 .. NH_CAST_K_MAX.
      - THE CONTRACT: for cast i let S_i be the segment nh_<shape>cast_all lists for the same record on the same build or refit -- the same set, the same
@@ -602,7 +661,7 @@ int nh_capsulecast_all(nh_context* ctx, const nh_CapsuleCast* casts, uint32_t co
    0.33 - 0.38 at k = 4 and 0.48 - 0.81 at k = 32.  DESIGN 10.13 has the table.
    Where nh_raycast itself loses a far grazing hit that the ray predicates accept by rounding, the k = 1 identity holds with the
    all-hits first record, not with nh_raycast's bytes.
-   Not built: a per-cast k, exits, filters by tag. */
+   Not built: a per-cast k, exits.  (A filter by tag VALUE is a layer the caller derives from its tags: "layer masks", below.) */
 #define NH_CAST_K_MAX 32u
 int nh_raycast_k(nh_context* ctx, const nh_Ray* rays, uint32_t count, uint32_t k,
                  uint32_t* counts /* count words, or NULL */, nh_RayHit* hits /* count * k */, uint32_t flags /* 0 */);

@@ -2,6 +2,8 @@
 // the current transforms), nh_query_refit (the same tree with the boxes of the current transforms), nh_raycast (batched closest-hit / any-hit ray
 // casts against the last build or refit), nh_spherecast, nh_boxcast and nh_capsulecast (the same for swept balls, oriented boxes and capsules) and
 // nh_overlap (the colliders touching each of a batch of spheres, boxes or capsules, as variable-length segments).  include/nudge_hip.h, "scene queries".
+// Layer masks (include/nudge_hip.h, "layer masks"): nh_query_set_layers gives every collider a word of layer bits and every node the OR of the words below it
+// (the layer pass, below the box pass); nh_query_filter sets the mask(s) every later query call walks under, in the FILTER = true instantiation of its kernel.
 //
 // Build (one launch each, plus the library's radix sort):
 //   k_q_xform   one lane per collider (boxes, then spheres): world pose (k_xform's arithmetic, nh_query.h) and the record the ray test reads; the
@@ -60,6 +62,15 @@ struct nh_QueryState {
 	uint32_t* top;               // the entry nodes of the top phase: nodes inside one run whose parent crosses a run boundary (ctl->top_n of them)
 	uint32_t ov_capacity;        // nh_overlap's sort scratch, by record of the caller's capacity
 	uint64_t* ov_keys_a; uint64_t* ov_keys_b; uint32_t* ov_vals_a; uint32_t* ov_vals_b;
+	// layer masks (header, "layer masks"): the layer word of every collider of the last build, by combined index, and per node the OR of the words of
+	// the leaves below it (2 n - 1 words by node id, the layer pass writes them); both are only meaningful while layers_set
+	uint32_t layer_capacity;     // colliders the two arrays have room for
+	bool layers_set;
+	uint32_t* layers;
+	uint32_t* node_layers;
+	uint32_t filter_mode;        // NH_FILTER_*: context state, read by every query call
+	uint32_t filter_mask;
+	const uint32_t* filter_masks;   // the caller's, kept by pointer (NH_FILTER_PER_QUERY)
 };
 
 // the caller's arrays as the kernels read them
@@ -303,6 +314,62 @@ __global__ __launch_bounds__(NH_Q_TOP_BLOCK) void k_q_boxes_top(const uint32_t* 
 	}
 }
 
+// ---- layer pass ------------------------------------------------------------------------------------------------------------------------------
+// Per node, the OR of the layer words of the leaves below it: the box pass's split with a word in place of a box.  It reads the sorted index, the parent
+// words, rchild and the entry list of the last build and counts arrivals as the box pass does; it runs behind nh_query_set_layers and at the tail of a
+// build while layers are set, never in a refit (the topology stands).
+// Bottom phase: workgroup b gathers the words of its run's colliders into leaf order and climbs inside the run, every hand-off in LDS, released and
+// acquired at workgroup scope by the counter's atomic.  OR does not depend on who arrives first.
+__global__ __launch_bounds__(NH_Q_RUN) void k_q_layers_runs(const uint32_t* __restrict__ layers, const uint32_t* __restrict__ idx, const uint32_t* __restrict__ parent,
+                                                            uint32_t n, uint32_t* __restrict__ node_layers) {
+	__shared__ uint32_t child_word[NH_Q_RUN][2];
+	__shared__ uint32_t arrived[NH_Q_RUN];
+	__shared__ uint32_t up[NH_Q_RUN];            // parent words of the run's internal nodes
+	const uint32_t base = blockIdx.x * NH_Q_RUN, s = threadIdx.x, j = base + s;
+	arrived[s] = 0u;
+	up[s] = j + 1u < n ? parent[j] : NH_Q_NONE;
+	uint32_t pw = NH_Q_NONE, word = 0u;
+	if (j < n) {
+		word = layers[idx[j]];
+		node_layers[n - 1u + j] = word;
+		pw = parent[n - 1u + j];
+	}
+	__syncthreads();
+	while (!(pw & NH_Q_PARENT_TOP)) {
+		const uint32_t slot = (pw & NH_Q_PARENT_ID) - base, side = (pw & NH_Q_PARENT_RIGHT) ? 1u : 0u;
+		child_word[slot][side] = word;
+		const uint32_t before = __hip_atomic_fetch_add(&arrived[slot], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
+		if (before == 0u) break;
+		word |= child_word[slot][side ^ 1u];
+		pw = up[slot];
+	}
+	__syncthreads();
+	if (arrived[s] == 2u) node_layers[j] = child_word[s][0] | child_word[s][1];
+}
+
+// Top phase, behind the kernel boundary: k_q_boxes_top's climb from the entry list in ONE workgroup, the same counters (0 between launches, left at 0),
+// hand-offs at workgroup scope.
+__global__ __launch_bounds__(NH_Q_TOP_BLOCK) void k_q_layers_top(const uint32_t* __restrict__ top, const nh_QCtl* __restrict__ ctl, const nh_QNode* __restrict__ nodes,
+                                                                 const uint32_t* __restrict__ parent, const uint32_t* __restrict__ rchild, uint32_t* arrive,
+                                                                 uint32_t* node_layers) {
+	const uint32_t m = ctl->top_n;
+	for (uint32_t e = threadIdx.x; e < m; e += NH_Q_TOP_BLOCK) {
+		const uint32_t me = top[e];
+		uint32_t word = node_layers[me];
+		uint32_t pw = parent[me];
+		while (pw != NH_Q_NONE) {
+			const uint32_t id = pw & NH_Q_PARENT_ID;
+			const uint32_t before = __hip_atomic_fetch_add(&arrive[id], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
+			if (before == 0u) break;
+			__hip_atomic_store(&arrive[id], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+			const uint32_t other = (pw & NH_Q_PARENT_RIGHT) ? __float_as_uint(nodes[id].a.w) : rchild[id];
+			word |= node_layers[other];
+			node_layers[id] = word;
+			pw = parent[id];
+		}
+	}
+}
+
 // ---- what the walks share -------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ bool nh_q_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
 __device__ __forceinline__ bool nh_q_finite(nh_f3 v) { return nh_q_finite(v.x) && nh_q_finite(v.y) && nh_q_finite(v.z); }
@@ -323,11 +390,25 @@ __device__ __forceinline__ uint4 nh_q_identity(uint32_t c, uint32_t nbox, const 
 // The stackless walk (the head of this file) from `node`: enter(lo, hi, x) says whether a node's box is entered and may leave a number x for the leaf
 // (the casts' entry t0, the point query's squared distance); leaf(c, record, x) sees every entered leaf whose body is not `ignore` and returns true
 // to end the walk (any-hit; a list segment that is full).
-template <class Enter, class Leaf>
-__device__ __forceinline__ void nh_q_walk(const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec, uint32_t node, uint32_t ignore, Enter enter, Leaf leaf) {
+//
+// FILTER (header, "layer masks"): a node whose word of layer bits shares none with the query's mask m holds nothing the query may see -- the word is the
+// OR over its leaves -- and is left by its escape link before the box test; a leaf's word is its collider's.  words = NULL: no layers are set, every word
+// is all ones.  The FILTER = false walk reads neither.
+struct nh_QFilter {
+	const uint32_t* words;       // by node id (nh_QueryState::node_layers), or NULL
+	const uint32_t* masks;       // per query, or NULL: every query uses `mask`
+	uint32_t mask;
+	__device__ __forceinline__ uint32_t of(uint32_t i) const { return masks ? masks[i] : mask; }
+	__device__ __forceinline__ bool sees(uint32_t node, uint32_t m) const { return ((words ? words[node] : 0xffffffffu) & m) != 0u; }
+};
+
+template <bool FILTER, class Enter, class Leaf>
+__device__ __forceinline__ void nh_q_walk(const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec, uint32_t node, uint32_t ignore,
+                                          const nh_QFilter& F, uint32_t m, Enter enter, Leaf leaf) {
 	float x = 0.0f;
 	while (node != NH_Q_NONE) {
 		const float4 na = nodes[node].a, nb = nodes[node].b;
+		if (FILTER && !F.sees(node, m)) { node = __float_as_uint(nb.w); continue; }
 		const bool in = enter(nh_make3(na.x, na.y, na.z), nh_make3(nb.x, nb.y, nb.z), x);
 		const uint32_t left = __float_as_uint(na.w);
 		const uint32_t rope = __float_as_uint(nb.w);
@@ -483,16 +564,16 @@ __device__ __forceinline__ void nh_q_write_hit(nh_RayHit* __restrict__ hit, cons
 }
 
 // One lane per cast: the walk prunes at the best t so far, nh_q_better (nh_query.h) keeps the closest hit and the tie rule, any_hit stops at the first.
-template <class Shape>
+template <class Shape, bool FILTER>
 __device__ __forceinline__ void nh_q_cast(const float4* __restrict__ casts, uint32_t count, nh_RayHit* __restrict__ hits, const nh_QNode* __restrict__ nodes,
-                                          const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox, uint32_t any_hit) {
+                                          const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox, uint32_t any_hit, const nh_QFilter& F) {
 	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
 		Shape k;
 		k.read(casts + (size_t)i * Shape::WORDS);
 		float bt = k.max_t;
 		uint32_t bc = NH_Q_NONE;
 		nh_f3 bn = nh_make3(0.0f, 0.0f, 0.0f);
-		nh_q_walk(nodes, rec, k.ok && n ? 0u : NH_Q_NONE, k.ignore,
+		nh_q_walk<FILTER>(nodes, rec, k.ok && n ? 0u : NH_Q_NONE, k.ignore, F, FILTER ? F.of(i) : 0u,
 			[&](nh_f3 lo, nh_f3 hi, float& t0) { return k.node(lo, hi, t0) && t0 <= bt; },
 			[&](uint32_t c, const nh_QRec& q, float t0) {
 				const nh_QHit h = k.leaf(nh_q_unpack(q), c < nbox, t0);
@@ -504,25 +585,30 @@ __device__ __forceinline__ void nh_q_cast(const float4* __restrict__ casts, uint
 	}
 }
 
+template <bool FILTER>
 __global__ __launch_bounds__(256) void k_q_raycast(const nh_Ray* __restrict__ rays, uint32_t count, nh_RayHit* __restrict__ hits,
-                                                   const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox, uint32_t any_hit) {
-	nh_q_cast<nh_QRay>(reinterpret_cast<const float4*>(rays), count, hits, nodes, rec, n, nbox, any_hit);
+                                                   const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox, uint32_t any_hit, nh_QFilter F) {
+	nh_q_cast<nh_QRay, FILTER>(reinterpret_cast<const float4*>(rays), count, hits, nodes, rec, n, nbox, any_hit, F);
 }
 
+template <bool FILTER>
 __global__ __launch_bounds__(256) void k_q_spherecast(const nh_SphereCast* __restrict__ casts, uint32_t count, nh_RayHit* __restrict__ hits,
-                                                      const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox, uint32_t any_hit) {
-	nh_q_cast<nh_QBall>(reinterpret_cast<const float4*>(casts), count, hits, nodes, rec, n, nbox, any_hit);
+                                                      const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox, uint32_t any_hit, nh_QFilter F) {
+	nh_q_cast<nh_QBall, FILTER>(reinterpret_cast<const float4*>(casts), count, hits, nodes, rec, n, nbox, any_hit, F);
 }
 
-// (Without the waves-per-EU hint the box-box test lands at 129 VGPRs and 3 waves; with it, 128 and 4, no scratch.)
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k_q_boxcast(const nh_BoxCast* __restrict__ casts, uint32_t count, nh_RayHit* __restrict__ hits,
-                                                   const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox, uint32_t any_hit) {
-	nh_q_cast<nh_QBox>(reinterpret_cast<const float4*>(casts), count, hits, nodes, rec, n, nbox, any_hit);
+// (Without the waves-per-EU hint the box-box test lands at 129 VGPRs and 3 waves; with it, 128 and 4, no scratch.  The filtered walk holds two more
+// values across the box-box test and under that hint spills them (8 bytes of scratch per lane): it is asked for 3 waves and keeps everything in registers.)
+template <bool FILTER>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FILTER ? 3 : 4))) void k_q_boxcast(const nh_BoxCast* __restrict__ casts, uint32_t count, nh_RayHit* __restrict__ hits,
+                                                   const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox, uint32_t any_hit, nh_QFilter F) {
+	nh_q_cast<nh_QBox, FILTER>(reinterpret_cast<const float4*>(casts), count, hits, nodes, rec, n, nbox, any_hit, F);
 }
 
+template <bool FILTER>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k_q_capsulecast(const nh_CapsuleCast* __restrict__ casts, uint32_t count, nh_RayHit* __restrict__ hits,
-                                                   const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox, uint32_t any_hit) {
-	nh_q_cast<nh_QCapsule>(reinterpret_cast<const float4*>(casts), count, hits, nodes, rec, n, nbox, any_hit);
+                                                   const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox, uint32_t any_hit, nh_QFilter F) {
+	nh_q_cast<nh_QCapsule, FILTER>(reinterpret_cast<const float4*>(casts), count, hits, nodes, rec, n, nbox, any_hit, F);
 }
 
 // ---- closest point ----------------------------------------------------------------------------------------------------------------------------
@@ -537,9 +623,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
 // The Morton seed of the nearest-collider walks (k_q_closest, k_q_closest_k, k_q_distance): p's Morton key in the frame of the last build (clamped to its
 // bounds), its place among the sorted keys by binary search, and the `win` leaves on either side of that place -- visit(c, record, lo, hi) for each whose
 // body is not `ignore`, with its leaf box.  It only proposes real colliders to the caller's own leaf function, so it changes the work, never the answer.
-template <class Visit>
+// FILTER: a leaf the query's mask does not see is skipped, as the walk skips it.
+template <bool FILTER, class Visit>
 __device__ __forceinline__ void nh_q_seed(nh_f3 p, uint32_t win, uint32_t ignore, const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec,
-                                          const uint64_t* __restrict__ keys, const nh_QCtl* __restrict__ ctl, uint32_t n, Visit visit) {
+                                          const uint64_t* __restrict__ keys, const nh_QCtl* __restrict__ ctl, uint32_t n, const nh_QFilter& F, uint32_t m, Visit visit) {
 	const nh_f3 smin = nh_make3(nh_float_unflip(ctl->kmin[0]), nh_float_unflip(ctl->kmin[1]), nh_float_unflip(ctl->kmin[2]));
 	const nh_f3 smax = nh_make3(nh_float_unflip(ctl->kmax[0]), nh_float_unflip(ctl->kmax[1]), nh_float_unflip(ctl->kmax[2]));
 	const float scale = nh_morton_scale(smin, smax);
@@ -552,6 +639,7 @@ __device__ __forceinline__ void nh_q_seed(nh_f3 p, uint32_t win, uint32_t ignore
 	}
 	const uint32_t j0 = lo > win ? lo - win : 0u, j1 = n - lo > win ? lo + win : n;
 	for (uint32_t j = j0; j < j1; ++j) {
+		if (FILTER && !F.sees(n - 1u + j, m)) continue;
 		const float4 na = nodes[n - 1u + j].a, nb = nodes[n - 1u + j].b;
 		const uint32_t c = __float_as_uint(na.w) & ~NH_Q_LEAF;
 		const nh_QRec q = rec[c];
@@ -560,9 +648,10 @@ __device__ __forceinline__ void nh_q_seed(nh_f3 p, uint32_t win, uint32_t ignore
 	}
 }
 
+template <bool FILTER>
 __global__ __launch_bounds__(256) void k_q_closest(const nh_PointQuery* __restrict__ queries, uint32_t count, nh_PointHit* __restrict__ hits,
                                                    const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec, const uint64_t* __restrict__ keys,
-                                                   const nh_QCtl* __restrict__ ctl, uint32_t n, uint32_t nbox) {
+                                                   const nh_QCtl* __restrict__ ctl, uint32_t n, uint32_t nbox, nh_QFilter F) {
 	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
 		const float4* qp = reinterpret_cast<const float4*>(queries + i);
 		const float4 q0 = qp[0], q1 = qp[1];
@@ -574,6 +663,7 @@ __global__ __launch_bounds__(256) void k_q_closest(const nh_PointQuery* __restri
 		uint32_t bc = NH_Q_NONE;
 		nh_f3 bn = nh_make3(0.0f, 0.0f, 0.0f), bx = nh_make3(0.0f, 0.0f, 0.0f);
 		const bool walk = ok && n;
+		const uint32_t fm = FILTER ? F.of(i) : 0u;
 		// a leaf of squared box distance d2, for the seed and the walk alike
 		const auto leaf = [&](uint32_t c, const nh_QRec& q, float d2) {
 			const nh_QShape s = nh_q_unpack(q);
@@ -583,9 +673,9 @@ __global__ __launch_bounds__(256) void k_q_closest(const nh_PointQuery* __restri
 			return false;
 		};
 #ifndef NH_Q_CLOSEST_NO_SEED
-		if (walk) nh_q_seed(p, NH_Q_SEED, ignore, nodes, rec, keys, ctl, n, [&](uint32_t c, const nh_QRec& q, nh_f3 lo, nh_f3 hi) { leaf(c, q, nh_q_point_node(lo, hi, p)); });
+		if (walk) nh_q_seed<FILTER>(p, NH_Q_SEED, ignore, nodes, rec, keys, ctl, n, F, fm, [&](uint32_t c, const nh_QRec& q, nh_f3 lo, nh_f3 hi) { leaf(c, q, nh_q_point_node(lo, hi, p)); });
 #endif
-		nh_q_walk(nodes, rec, walk ? 0u : NH_Q_NONE, ignore,
+		nh_q_walk<FILTER>(nodes, rec, walk ? 0u : NH_Q_NONE, ignore, F, fm,
 			[&](nh_f3 lo, nh_f3 hi, float& d2) { d2 = nh_q_point_node(lo, hi, p); return !(d2 > 0.0f && sqrtf(d2) > bd); }, leaf);
 		float4* hp = reinterpret_cast<float4*>(hits + i);
 		if (bc == NH_Q_NONE) {
@@ -624,9 +714,10 @@ __global__ __launch_bounds__(256) void k_q_closest(const nh_PointQuery* __restri
 //          record leaves as three 16-byte stores, then the k - m miss records, then counts[i] = m.
 static inline uint32_t nh_q_nearest_block(uint32_t k) { return k <= 8u ? 256u : k <= 16u ? 128u : 64u; }
 
+template <bool FILTER>
 __global__ __launch_bounds__(256) void k_q_closest_k(const nh_PointQuery* __restrict__ queries, uint32_t count, uint32_t k, uint32_t* __restrict__ counts,
                                                      nh_PointHit* __restrict__ hits, const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec,
-                                                     const uint64_t* __restrict__ keys, const nh_QCtl* __restrict__ ctl, uint32_t n, uint32_t nbox) {
+                                                     const uint64_t* __restrict__ keys, const nh_QCtl* __restrict__ ctl, uint32_t n, uint32_t nbox, nh_QFilter F) {
 	extern __shared__ nh_QNear q_near[];
 	const uint32_t stride = blockDim.x;
 	nh_QNear* const list = q_near + threadIdx.x;
@@ -640,6 +731,7 @@ __global__ __launch_bounds__(256) void k_q_closest_k(const nh_PointQuery* __rest
 		float bd = max_d;
 		uint32_t held = 0u;
 		const bool walk = ok && n;
+		const uint32_t fm = FILTER ? F.of(i) : 0u;
 		// a leaf of squared box distance d2, for the seed and the walk alike
 		const auto leaf = [&](uint32_t c, const nh_QRec& q, float d2) {
 			const nh_QShape s = nh_q_unpack(q);
@@ -650,9 +742,9 @@ __global__ __launch_bounds__(256) void k_q_closest_k(const nh_PointQuery* __rest
 			return false;
 		};
 #ifndef NH_Q_CLOSEST_K_NO_SEED
-		if (walk) nh_q_seed(p, NH_Q_SEED + k / 2u, ignore, nodes, rec, keys, ctl, n, [&](uint32_t c, const nh_QRec& q, nh_f3 lo, nh_f3 hi) { leaf(c, q, nh_q_point_node(lo, hi, p)); });
+		if (walk) nh_q_seed<FILTER>(p, NH_Q_SEED + k / 2u, ignore, nodes, rec, keys, ctl, n, F, fm, [&](uint32_t c, const nh_QRec& q, nh_f3 lo, nh_f3 hi) { leaf(c, q, nh_q_point_node(lo, hi, p)); });
 #endif
-		nh_q_walk(nodes, rec, walk ? 0u : NH_Q_NONE, ignore,
+		nh_q_walk<FILTER>(nodes, rec, walk ? 0u : NH_Q_NONE, ignore, F, fm,
 			[&](nh_f3 lo, nh_f3 hi, float& d2) { d2 = nh_q_point_node(lo, hi, p); return !(d2 > 0.0f && sqrtf(d2) > bd); }, leaf);
 		float4* hp = reinterpret_cast<float4*>(hits + (size_t)i * k);
 		for (uint32_t j = 0u; j < held; ++j, hp += 3) {
@@ -684,9 +776,10 @@ __global__ __launch_bounds__(256) void k_q_closest_k(const nh_PointQuery* __rest
 //   seed    nh_q_seed at the query's centre, k_q_closest's window
 //   leaf    the pair function of nh_query.h, "distance"; one instantiation serves every shape, the lanes of a wave diverge by the shapes of neighbouring
 //           queries and colliders (the box / box enumeration sets the registers)
+template <bool FILTER>
 __global__ __launch_bounds__(256) void k_q_distance(const nh_DistanceQuery* __restrict__ queries, uint32_t count, nh_PointHit* __restrict__ hits,
                                                     const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec, const uint64_t* __restrict__ keys,
-                                                    const nh_QCtl* __restrict__ ctl, uint32_t n, uint32_t nbox) {
+                                                    const nh_QCtl* __restrict__ ctl, uint32_t n, uint32_t nbox, nh_QFilter F) {
 	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
 		const float4* qp = reinterpret_cast<const float4*>(queries + i);
 		const float4 q0 = qp[0], q1 = qp[1], q2 = qp[2];
@@ -707,6 +800,7 @@ __global__ __launch_bounds__(256) void k_q_distance(const nh_DistanceQuery* __re
 		uint32_t bc = NH_Q_NONE;
 		nh_f3 bn = nh_make3(0.0f, 0.0f, 0.0f), bx = nh_make3(0.0f, 0.0f, 0.0f);
 		const bool walk = ok && n;
+		const uint32_t fm = FILTER ? F.of(i) : 0u;
 		// a leaf at squared box gap g2, for the seed and the walk alike
 		const auto leaf = [&](uint32_t cc, const nh_QRec& r, float g2) {
 			const nh_QShape s = nh_q_unpack(r);
@@ -718,8 +812,8 @@ __global__ __launch_bounds__(256) void k_q_distance(const nh_DistanceQuery* __re
 			if (nh_q_closer(k, cc, max_d, bd, bc)) { bd = k; bc = cc; bn = d.n; bx = d.x; }
 			return false;
 		};
-		if (walk) nh_q_seed(c, NH_Q_SEED, ignore, nodes, rec, keys, ctl, n, [&](uint32_t cc, const nh_QRec& r, nh_f3 lo, nh_f3 hi) { leaf(cc, r, nh_q_dist_node(lo, hi, qlo, qhi)); });
-		nh_q_walk(nodes, rec, walk ? 0u : NH_Q_NONE, ignore,
+		if (walk) nh_q_seed<FILTER>(c, NH_Q_SEED, ignore, nodes, rec, keys, ctl, n, F, fm, [&](uint32_t cc, const nh_QRec& r, nh_f3 lo, nh_f3 hi) { leaf(cc, r, nh_q_dist_node(lo, hi, qlo, qhi)); });
+		nh_q_walk<FILTER>(nodes, rec, walk ? 0u : NH_Q_NONE, ignore, F, fm,
 			[&](nh_f3 lo, nh_f3 hi, float& g2) { g2 = nh_q_dist_node(lo, hi, qlo, qhi); return !(g2 > 0.0f && sqrtf(g2) > bd); }, leaf);
 		float4* hp = reinterpret_cast<float4*>(hits + i);
 		if (bc == NH_Q_NONE) {
@@ -748,10 +842,10 @@ __global__ __launch_bounds__(256) void k_q_distance(const nh_DistanceQuery* __re
 //   k_q_overlap<true, *> the same walks (the same template: the same set) for the queries whose segment fits: key (i << cbits | c), value c at offsets[i] + k
 //   nh_sort_u64_u32     over the written prefix (its length from the device): keys are unique, so (query, combined index) ascending is the only order
 //   k_q_overlap_gather  nh_OverlapHit {body, collider, shape, tag} from the record of each sorted collider, one 16-byte store each
-template <bool LIST, bool CAPSULE>
+template <bool LIST, bool CAPSULE, bool FILTER>
 __global__ __launch_bounds__(256) void k_q_overlap(const nh_OverlapQuery* __restrict__ queries, uint32_t count, uint32_t* offsets,
                                                    const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox,
-                                                   nh_QCtl* ctl, uint64_t* __restrict__ keys, uint32_t* __restrict__ vals, uint32_t cbits) {
+                                                   nh_QCtl* ctl, uint64_t* __restrict__ keys, uint32_t* __restrict__ vals, uint32_t cbits, nh_QFilter F) {
 	if (!LIST && !CAPSULE && blockIdx.x == 0 && threadIdx.x == 0) { offsets[count] = 0u; ctl->ov_wrap = 0u; ctl->ov_written = 0u; }   // (k_q_overlap_fix sets both)
 	const uint32_t written = LIST ? ctl->ov_written : 0u;
 	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
@@ -780,7 +874,7 @@ __global__ __launch_bounds__(256) void k_q_overlap(const nh_OverlapQuery* __rest
 		const float s = fmaxf(fmaxf(fmaxf(fabsf(lo.x), fabsf(lo.y)), fmaxf(fabsf(lo.z), fabsf(hi.x))), fmaxf(fabsf(hi.y), fabsf(hi.z))) * 3.814697265625e-06f;
 		lo = nh_make3(lo.x - s, lo.y - s, lo.z - s); hi = nh_make3(hi.x + s, hi.y + s, hi.z + s);
 		uint32_t k = 0u;
-		nh_q_walk(nodes, rec, ok && n ? 0u : NH_Q_NONE, ignore,
+		nh_q_walk<FILTER>(nodes, rec, ok && n ? 0u : NH_Q_NONE, ignore, F, FILTER ? F.of(i) : 0u,
 			[&](nh_f3 nlo, nh_f3 nhi, float&) { return nlo.x <= hi.x && lo.x <= nhi.x && nlo.y <= hi.y && lo.y <= nhi.y && nlo.z <= hi.z && lo.z <= nhi.z; },
 			[&](uint32_t cc, const nh_QRec& r, float) {
 				const nh_QShape col = nh_q_unpack(r);
@@ -886,10 +980,10 @@ __global__ __launch_bounds__(256) void k_q_penetration_gather(const uint64_t* __
 //                       normal goes through a sort.
 // every shape's decode, validity and grow are the closest-hit casts' own: a shape without a size gives the ray's bytes, a capsule of hh = 0 the ball's, and
 // the first record of a cast is the closest-hit record.  The box and capsule instantiations take their closest-hit siblings' waves-per-EU hint (ALL_WAVES)
-template <class Shape, bool LIST>
+template <class Shape, bool LIST, bool FILTER>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(Shape::ALL_WAVES))) void k_q_castall(const float4* __restrict__ casts, uint32_t count, uint32_t* offsets,
                                                    const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox,
-                                                   nh_QCtl* ctl, uint64_t* __restrict__ keys, uint32_t* __restrict__ vals, uint32_t cbits, uint32_t one_sort) {
+                                                   nh_QCtl* ctl, uint64_t* __restrict__ keys, uint32_t* __restrict__ vals, uint32_t cbits, uint32_t one_sort, nh_QFilter F) {
 	if (!LIST && blockIdx.x == 0 && threadIdx.x == 0) { offsets[count] = 0u; ctl->ov_wrap = 0u; ctl->ov_written = 0u; }   // (k_q_overlap_fix sets both)
 	const uint32_t written = LIST ? ctl->ov_written : 0u;
 	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
@@ -902,7 +996,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(Shape::ALL_
 		k.read(casts + (size_t)i * Shape::WORDS);
 		const bool ray = k.raylike();
 		uint32_t hits = 0u;
-		nh_q_walk(nodes, rec, k.ok && n ? 0u : NH_Q_NONE, k.ignore,
+		nh_q_walk<FILTER>(nodes, rec, k.ok && n ? 0u : NH_Q_NONE, k.ignore, F, FILTER ? F.of(i) : 0u,
 			[&](nh_f3 lo, nh_f3 hi, float& t0) {
 				// (a ray's node box also takes the predicates' own rounding, nh_q_all_pad; a sized shape's reach rule reads the entry of the box as the build stores it)
 				if (ray) return nh_q_cast_node(lo, hi, k.o, k.inv, k.grow() + nh_q_all_pad(lo, hi, k.o), t0) && t0 <= k.max_t;
@@ -970,10 +1064,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(Shape::ALL_
 //          the same function on the same inputs, the same bits) and leaves through nh_q_write_hit; the k - held miss records follow (t = max_t, or a
 //          quiet NaN for an invalid cast: the closest-hit call's miss), then counts[i] = held.  No normal is kept in LDS.
 // The box and capsule instantiations take their siblings' waves-per-EU hint (ALL_WAVES).
-template <class Shape>
+template <class Shape, bool FILTER>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(Shape::K_WAVES))) void k_q_cast_k(const float4* __restrict__ casts, uint32_t count, uint32_t kk,
                                                    uint32_t* __restrict__ counts, nh_RayHit* __restrict__ hits, const nh_QNode* __restrict__ nodes,
-                                                   const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox) {
+                                                   const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox, nh_QFilter F) {
 	extern __shared__ nh_QNear q_first[];
 	const uint32_t stride = blockDim.x;
 	nh_QNear* const list = q_first + threadIdx.x;
@@ -983,7 +1077,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(Shape::K_WA
 		const bool ray = k.raylike();
 		float bd = k.max_t;
 		uint32_t held = 0u;
-		nh_q_walk(nodes, rec, k.ok && n ? 0u : NH_Q_NONE, k.ignore,
+		nh_q_walk<FILTER>(nodes, rec, k.ok && n ? 0u : NH_Q_NONE, k.ignore, F, FILTER ? F.of(i) : 0u,
 			[&](nh_f3 lo, nh_f3 hi, float& t0) {
 				if (ray) return nh_q_cast_node(lo, hi, k.o, k.inv, k.grow() + nh_q_all_pad(lo, hi, k.o), t0) && t0 <= bd;
 				return k.node(lo, hi, t0) && t0 <= bd;
@@ -1013,7 +1107,7 @@ void nh_query_free(nh_context* ctx) {
 	nh_QueryState* q = ctx->query;
 	if (!q) return;
 	void* bufs[] = { q->ctl, q->rec, q->keys_a, q->keys_b, q->idx_a, q->idx_b, q->hist, q->nodes, q->parent, q->rchild, q->last, q->right_at, q->arrive, q->top,
-	                 q->ov_keys_a, q->ov_keys_b, q->ov_vals_a, q->ov_vals_b };
+	                 q->ov_keys_a, q->ov_keys_b, q->ov_vals_a, q->ov_vals_b, q->layers, q->node_layers };
 	for (void* b : bufs) if (b) hipFree(b);
 	delete q;
 	ctx->query = nullptr;
@@ -1080,6 +1174,25 @@ static void nh_query_boxes(nh_context* ctx, const nh_QWorld& W, uint32_t C) {
 	if (C > NH_Q_RUN) NH_LAUNCH(ctx, "q_boxes_top", k_q_boxes_top, 1, NH_Q_TOP_BLOCK, q->top, q->ctl, q->nodes, q->parent, q->rchild, q->arrive);
 }
 
+// The layer pass over the tree of the last build (the comment above k_q_layers_runs): two launches, the second only where the tree has more than one run.
+static void nh_query_layer_pass(nh_context* ctx) {
+	nh_QueryState* q = ctx->query;
+	const uint32_t C = q->n;
+	if (!C) return;
+	NH_LAUNCH(ctx, "q_layers_runs", k_q_layers_runs, (C + NH_Q_RUN - 1u) / NH_Q_RUN, NH_Q_RUN, q->layers, q->idx, q->parent, C, q->node_layers);
+	if (C > NH_Q_RUN) NH_LAUNCH(ctx, "q_layers_top", k_q_layers_top, 1, NH_Q_TOP_BLOCK, q->top, q->ctl, q->nodes, q->parent, q->rchild, q->arrive, q->node_layers);
+}
+
+// What the walking kernels get of the context's filter; `on`: the call launches the FILTER = true instantiation.
+static nh_QFilter nh_query_filter_of(const nh_QueryState* q, bool* on) {
+	*on = q->filter_mode != NH_FILTER_OFF;
+	nh_QFilter F;
+	F.words = q->layers_set ? q->node_layers : nullptr;
+	F.masks = q->filter_mode == NH_FILTER_PER_QUERY ? q->filter_masks : nullptr;
+	F.mask = q->filter_mask;
+	return F;
+}
+
 // Observer: no nh_flush_pending, no view export, no counter -- only launches on the stream and buffers of its own (header, "scene queries").
 extern "C" int nh_query_build(nh_context* ctx, const nh_BodyData* bodies, const nh_ColliderData* colliders) {
 	if (!ctx || !bodies || !colliders) return NH_ERR_INVALID;
@@ -1101,7 +1214,73 @@ extern "C" int nh_query_build(nh_context* ctx, const nh_BodyData* bodies, const 
 		if (C > 1u) NH_LAUNCH(ctx, "q_links", k_q_links, nh_grid_for(C - 1u, 256, 4096), 256, C, q->nodes, q->last, q->right_at);
 		nh_query_boxes(ctx, W, C);
 	}
+	// (layers are by combined collider index: they outlive a build with the same two counts, whose tree needs the node words again)
+	const bool same_world = q->built && q->n == C && q->nbox == colliders->boxes.count;
 	q->built = true; q->n = C; q->nbox = colliders->boxes.count;
+	if (q->layers_set && !same_world) q->layers_set = false;
+	if (q->layers_set) nh_query_layer_pass(ctx);
+	return NH_OK;
+}
+
+// Layer words of the colliders of the last build (header, "layer masks").  Observer like the build.
+extern "C" int nh_query_set_layers(nh_context* ctx, const uint32_t* box_layers, const uint32_t* sphere_layers) {
+	if (!ctx) return NH_ERR_INVALID;
+	nh_QueryState* q = ctx->query;
+	if (!q || !q->built) return NH_ERR_INVALID;
+	if (((uintptr_t)box_layers | (uintptr_t)sphere_layers) & 3u) return NH_ERR_INVALID;
+	if (!box_layers && !sphere_layers) { q->layers_set = false; return NH_OK; }
+	NH_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+	if (q->capacity > q->layer_capacity) {
+		// (a growth waits for the stream first, as nh_query_reserve's does: a filtered call may still read the old words)
+		NH_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+		if (q->layers) hipFree(q->layers);
+		if (q->node_layers) hipFree(q->node_layers);
+		q->layers = q->node_layers = nullptr;
+		q->layer_capacity = 0; q->layers_set = false;
+		NH_HIP_CHECK(ctx, hipMalloc((void**)&q->layers, sizeof(uint32_t) * (size_t)q->capacity));
+		NH_HIP_CHECK(ctx, hipMalloc((void**)&q->node_layers, 2u * sizeof(uint32_t) * (size_t)q->capacity));
+		q->layer_capacity = q->capacity;
+	}
+	const uint32_t nbox = q->nbox, nsph = q->n - q->nbox;
+	if (nbox) {
+		if (box_layers) NH_HIP_CHECK(ctx, hipMemcpyAsync(q->layers, box_layers, sizeof(uint32_t) * (size_t)nbox, hipMemcpyDeviceToDevice, ctx->stream));
+		else NH_HIP_CHECK(ctx, hipMemsetAsync(q->layers, 0xff, sizeof(uint32_t) * (size_t)nbox, ctx->stream));
+	}
+	if (nsph) {
+		if (sphere_layers) NH_HIP_CHECK(ctx, hipMemcpyAsync(q->layers + nbox, sphere_layers, sizeof(uint32_t) * (size_t)nsph, hipMemcpyDeviceToDevice, ctx->stream));
+		else NH_HIP_CHECK(ctx, hipMemsetAsync(q->layers + nbox, 0xff, sizeof(uint32_t) * (size_t)nsph, ctx->stream));
+	}
+	q->layers_set = true;
+	nh_query_layer_pass(ctx);
+	return NH_OK;
+}
+
+// The filter every later query call reads (header, "layer masks").  Host state only: nothing is launched.
+extern "C" int nh_query_filter(nh_context* ctx, uint32_t mode, uint32_t mask, const uint32_t* masks) {
+	if (!ctx) return NH_ERR_INVALID;
+	nh_QueryState* q = ctx->query;
+	if (!q || !q->built) return NH_ERR_INVALID;
+	if (mode != NH_FILTER_OFF && mode != NH_FILTER_UNIFORM && mode != NH_FILTER_PER_QUERY) return NH_ERR_INVALID;
+	if (mode == NH_FILTER_PER_QUERY && (!masks || ((uintptr_t)masks & 3u))) return NH_ERR_INVALID;
+	q->filter_mode = mode;
+	q->filter_mask = mode == NH_FILTER_UNIFORM ? mask : 0u;
+	q->filter_masks = mode == NH_FILTER_PER_QUERY ? masks : nullptr;
+	return NH_OK;
+}
+
+// Diagnostic: whether layers are in force and the root's node word.  Waits for the stream.
+extern "C" int nh_query_layer_info(nh_context* ctx, nh_QueryLayerInfo* out) {
+	if (!ctx || !out) return NH_ERR_INVALID;
+	nh_QueryState* q = ctx->query;
+	if (!q || !q->built) return NH_ERR_INVALID;
+	NH_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+	uint32_t any = q->n ? 0xffffffffu : 0u;
+	if (q->layers_set && q->n) NH_HIP_CHECK(ctx, hipMemcpyAsync(&any, q->node_layers, sizeof(any), hipMemcpyDeviceToHost, ctx->stream));
+	NH_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+	out->set = q->layers_set ? 1u : 0u;
+	out->colliders = q->n;
+	out->any_layers = any;
+	out->reserved = 0u;
 	return NH_OK;
 }
 
@@ -1139,32 +1318,37 @@ extern "C" int nh_query_stats(nh_context* ctx, nh_QueryStats* out) {
 
 // The four closest-hit casts: one record type and one kernel each, the same checks in the same order.
 template <class Cast>
-static int nh_cast(nh_context* ctx, const char* label, void (*kernel)(const Cast*, uint32_t, nh_RayHit*, const nh_QNode*, const nh_QRec*, uint32_t, uint32_t, uint32_t),
-                   const Cast* casts, uint32_t count, nh_RayHit* hits, uint32_t flags) {
+using nh_CastKernel = void (*)(const Cast*, uint32_t, nh_RayHit*, const nh_QNode*, const nh_QRec*, uint32_t, uint32_t, uint32_t, nh_QFilter);
+template <class Cast>
+static int nh_cast(nh_context* ctx, const char* label, nh_CastKernel<Cast> plain, nh_CastKernel<Cast> filtered, const Cast* casts, uint32_t count, nh_RayHit* hits,
+                   uint32_t flags) {
 	if (!ctx || !ctx->query || !ctx->query->built) return NH_ERR_INVALID;
 	if (flags & ~(uint32_t)NH_RAY_ANY_HIT) return NH_ERR_INVALID;
 	if (count == 0u) return NH_OK;
 	if (!casts || !hits || (((uintptr_t)casts | (uintptr_t)hits) & 15u)) return NH_ERR_INVALID;    // (records are moved as 16-byte words)
 	NH_HIP_CHECK(ctx, hipSetDevice(ctx->device));
 	nh_QueryState* q = ctx->query;
-	NH_LAUNCH(ctx, label, kernel, nh_grid_for(count, 256, 1u << 20), 256, casts, count, hits, q->nodes, q->rec, q->n, q->nbox, (flags & NH_RAY_ANY_HIT) ? 1u : 0u);
+	bool on;
+	const nh_QFilter F = nh_query_filter_of(q, &on);
+	NH_LAUNCH(ctx, label, on ? filtered : plain, nh_grid_for(count, 256, 1u << 20), 256, casts, count, hits, q->nodes, q->rec, q->n, q->nbox,
+	          (flags & NH_RAY_ANY_HIT) ? 1u : 0u, F);
 	return NH_OK;
 }
 
 extern "C" int nh_raycast(nh_context* ctx, const nh_Ray* rays, uint32_t count, nh_RayHit* hits, uint32_t flags) {
-	return nh_cast(ctx, "q_raycast", k_q_raycast, rays, count, hits, flags);
+	return nh_cast(ctx, "q_raycast", k_q_raycast<false>, k_q_raycast<true>, rays, count, hits, flags);
 }
 
 extern "C" int nh_spherecast(nh_context* ctx, const nh_SphereCast* casts, uint32_t count, nh_RayHit* hits, uint32_t flags) {
-	return nh_cast(ctx, "q_spherecast", k_q_spherecast, casts, count, hits, flags);
+	return nh_cast(ctx, "q_spherecast", k_q_spherecast<false>, k_q_spherecast<true>, casts, count, hits, flags);
 }
 
 extern "C" int nh_capsulecast(nh_context* ctx, const nh_CapsuleCast* casts, uint32_t count, nh_RayHit* hits, uint32_t flags) {
-	return nh_cast(ctx, "q_capsulecast", k_q_capsulecast, casts, count, hits, flags);
+	return nh_cast(ctx, "q_capsulecast", k_q_capsulecast<false>, k_q_capsulecast<true>, casts, count, hits, flags);
 }
 
 extern "C" int nh_boxcast(nh_context* ctx, const nh_BoxCast* casts, uint32_t count, nh_RayHit* hits, uint32_t flags) {
-	return nh_cast(ctx, "q_boxcast", k_q_boxcast, casts, count, hits, flags);
+	return nh_cast(ctx, "q_boxcast", k_q_boxcast<false>, k_q_boxcast<true>, casts, count, hits, flags);
 }
 
 extern "C" int nh_closest(nh_context* ctx, const nh_PointQuery* queries, uint32_t count, nh_PointHit* hits, uint32_t flags) {
@@ -1174,7 +1358,10 @@ extern "C" int nh_closest(nh_context* ctx, const nh_PointQuery* queries, uint32_
 	if (!queries || !hits || (((uintptr_t)queries | (uintptr_t)hits) & 15u)) return NH_ERR_INVALID;    // (records are moved as 16-byte words)
 	NH_HIP_CHECK(ctx, hipSetDevice(ctx->device));
 	nh_QueryState* q = ctx->query;
-	NH_LAUNCH(ctx, "q_closest", k_q_closest, nh_grid_for(count, 256, 1u << 20), 256, queries, count, hits, q->nodes, q->rec, q->keys, q->ctl, q->n, q->nbox);
+	bool on;
+	const nh_QFilter F = nh_query_filter_of(q, &on);
+	NH_LAUNCH(ctx, "q_closest", on ? k_q_closest<true> : k_q_closest<false>, nh_grid_for(count, 256, 1u << 20), 256, queries, count, hits, q->nodes, q->rec, q->keys,
+	          q->ctl, q->n, q->nbox, F);
 	return NH_OK;
 }
 
@@ -1188,8 +1375,10 @@ extern "C" int nh_closest_k(nh_context* ctx, const nh_PointQuery* queries, uint3
 	nh_QueryState* q = ctx->query;
 	const uint32_t block = nh_q_nearest_block(k);
 	if (ctx->timing) nh_timer_begin(ctx, "q_closest_k");
-	hipLaunchKernelGGL(k_q_closest_k, dim3(nh_grid_for(count, block, 1u << 20)), dim3(block), block * k * sizeof(nh_QNear), ctx->stream,
-	                   queries, count, k, counts, hits, q->nodes, q->rec, q->keys, q->ctl, q->n, q->nbox);
+	bool on;
+	const nh_QFilter F = nh_query_filter_of(q, &on);
+	hipLaunchKernelGGL(on ? k_q_closest_k<true> : k_q_closest_k<false>, dim3(nh_grid_for(count, block, 1u << 20)), dim3(block), block * k * sizeof(nh_QNear), ctx->stream,
+	                   queries, count, k, counts, hits, q->nodes, q->rec, q->keys, q->ctl, q->n, q->nbox, F);
 	if (ctx->timing) nh_timer_end(ctx);
 	return NH_OK;
 }
@@ -1202,7 +1391,10 @@ extern "C" int nh_distance(nh_context* ctx, const nh_DistanceQuery* queries, uin
 	if (!queries || !hits || (((uintptr_t)queries | (uintptr_t)hits) & 15u)) return NH_ERR_INVALID;    // (records are moved as 16-byte words)
 	NH_HIP_CHECK(ctx, hipSetDevice(ctx->device));
 	nh_QueryState* q = ctx->query;
-	NH_LAUNCH(ctx, "q_distance", k_q_distance, nh_grid_for(count, 256, 1u << 20), 256, queries, count, hits, q->nodes, q->rec, q->keys, q->ctl, q->n, q->nbox);
+	bool on;
+	const nh_QFilter F = nh_query_filter_of(q, &on);
+	NH_LAUNCH(ctx, "q_distance", on ? k_q_distance<true> : k_q_distance<false>, nh_grid_for(count, 256, 1u << 20), 256, queries, count, hits, q->nodes, q->rec, q->keys,
+	          q->ctl, q->n, q->nbox, F);
 	return NH_OK;
 }
 
@@ -1263,16 +1455,18 @@ static int nh_overlap_chain(nh_context* ctx, const nh_OverlapQuery* queries, uin
 	const uint32_t cbits = (uint32_t)nh_q_bits(q->n);
 	*cbits_out = cbits;
 	const uint32_t grid = nh_grid_for(count, 256, 1u << 20);
-	NH_LAUNCH(ctx, "q_overlap_count", (k_q_overlap<false, false>), grid, 256, queries, count, offsets, q->nodes, q->rec, q->n, q->nbox, q->ctl,
-	          (uint64_t*)nullptr, (uint32_t*)nullptr, cbits);
-	NH_LAUNCH(ctx, "q_overlap_count_capsule", (k_q_overlap<false, true>), grid, 256, queries, count, offsets, q->nodes, q->rec, q->n, q->nbox, q->ctl,
-	          (uint64_t*)nullptr, (uint32_t*)nullptr, cbits);
+	bool on;
+	const nh_QFilter F = nh_query_filter_of(q, &on);
+	NH_LAUNCH(ctx, "q_overlap_count", (on ? k_q_overlap<false, false, true> : k_q_overlap<false, false, false>), grid, 256, queries, count, offsets, q->nodes, q->rec,
+	          q->n, q->nbox, q->ctl, (uint64_t*)nullptr, (uint32_t*)nullptr, cbits, F);
+	NH_LAUNCH(ctx, "q_overlap_count_capsule", (on ? k_q_overlap<false, true, true> : k_q_overlap<false, true, false>), grid, 256, queries, count, offsets, q->nodes, q->rec,
+	          q->n, q->nbox, q->ctl, (uint64_t*)nullptr, (uint32_t*)nullptr, cbits, F);
 	nh_overlap_offsets(ctx, offsets, count, capacity);
 	if (!list) return NH_OK;
-	NH_LAUNCH(ctx, "q_overlap_list", (k_q_overlap<true, false>), grid, 256, queries, count, offsets, q->nodes, q->rec, q->n, q->nbox, q->ctl,
-	          q->ov_keys_a, q->ov_vals_a, cbits);
-	NH_LAUNCH(ctx, "q_overlap_list_capsule", (k_q_overlap<true, true>), grid, 256, queries, count, offsets, q->nodes, q->rec, q->n, q->nbox, q->ctl,
-	          q->ov_keys_a, q->ov_vals_a, cbits);
+	NH_LAUNCH(ctx, "q_overlap_list", (on ? k_q_overlap<true, false, true> : k_q_overlap<true, false, false>), grid, 256, queries, count, offsets, q->nodes, q->rec,
+	          q->n, q->nbox, q->ctl, q->ov_keys_a, q->ov_vals_a, cbits, F);
+	NH_LAUNCH(ctx, "q_overlap_list_capsule", (on ? k_q_overlap<true, true, true> : k_q_overlap<true, true, false>), grid, 256, queries, count, offsets, q->nodes, q->rec,
+	          q->n, q->nbox, q->ctl, q->ov_keys_a, q->ov_vals_a, cbits, F);
 	const int bits = (((int)cbits + nh_q_bits(count)) + 7) / 8 * 8;
 	*in_b = nh_sort_u64_u32(ctx, q->ov_keys_a, q->ov_keys_b, q->ov_vals_a, q->ov_vals_b, &q->ctl->ov_written, q->hist, 0, bits);
 	*list_out = true;
@@ -1317,12 +1511,14 @@ static int nh_castall(nh_context* ctx, const char* const label[3], const void* c
 	const int ibits = nh_q_bits(count);
 	const bool one_sort = ibits + 32 + (int)cbits <= 64;
 	const uint32_t grid = nh_grid_for(count, 256, 1u << 20);
-	NH_LAUNCH(ctx, label[0], (k_q_castall<Shape, false>), grid, 256, recs, count, offsets, q->nodes, q->rec, q->n, q->nbox, q->ctl, (uint64_t*)nullptr,
-	          (uint32_t*)nullptr, cbits, one_sort ? 1u : 0u);
+	bool on;
+	const nh_QFilter F = nh_query_filter_of(q, &on);
+	NH_LAUNCH(ctx, label[0], (on ? k_q_castall<Shape, false, true> : k_q_castall<Shape, false, false>), grid, 256, recs, count, offsets, q->nodes, q->rec, q->n, q->nbox,
+	          q->ctl, (uint64_t*)nullptr, (uint32_t*)nullptr, cbits, one_sort ? 1u : 0u, F);
 	nh_overlap_offsets(ctx, offsets, count, capacity);
 	if (!list) return NH_OK;
-	NH_LAUNCH(ctx, label[1], (k_q_castall<Shape, true>), grid, 256, recs, count, offsets, q->nodes, q->rec, q->n, q->nbox, q->ctl, q->ov_keys_a, q->ov_vals_a,
-	          cbits, one_sort ? 1u : 0u);
+	NH_LAUNCH(ctx, label[1], (on ? k_q_castall<Shape, true, true> : k_q_castall<Shape, true, false>), grid, 256, recs, count, offsets, q->nodes, q->rec, q->n, q->nbox,
+	          q->ctl, q->ov_keys_a, q->ov_vals_a, cbits, one_sort ? 1u : 0u, F);
 	uint64_t* keys = q->ov_keys_a; uint64_t* keys_other = q->ov_keys_b;
 	uint32_t* vals = q->ov_vals_a; uint32_t* vals_other = q->ov_vals_b;
 	const uint32_t* m = &q->ctl->ov_written;
@@ -1378,8 +1574,10 @@ static int nh_cast_k(nh_context* ctx, const char* label, const void* casts, uint
 	nh_QueryState* q = ctx->query;
 	const uint32_t block = nh_q_nearest_block(k);
 	if (ctx->timing) nh_timer_begin(ctx, label);
-	hipLaunchKernelGGL(k_q_cast_k<Shape>, dim3(nh_grid_for(count, block, NH_Q_CAST_K_GRID)), dim3(block), block * k * sizeof(nh_QNear), ctx->stream,
-	                   static_cast<const float4*>(casts), count, k, counts, hits, q->nodes, q->rec, q->n, q->nbox);
+	bool on;
+	const nh_QFilter F = nh_query_filter_of(q, &on);
+	hipLaunchKernelGGL((on ? k_q_cast_k<Shape, true> : k_q_cast_k<Shape, false>), dim3(nh_grid_for(count, block, NH_Q_CAST_K_GRID)), dim3(block), block * k * sizeof(nh_QNear),
+	                   ctx->stream, static_cast<const float4*>(casts), count, k, counts, hits, q->nodes, q->rec, q->n, q->nbox, F);
 	if (ctx->timing) nh_timer_end(ctx);
 	return NH_OK;
 }

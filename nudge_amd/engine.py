@@ -45,6 +45,7 @@ EXPORTS = [
     "nh_partition_set_transport", "nh_partition_exchange_step", "nh_partition_step", "nh_partition_transport_check", "nh_partition_transport_result", "nh_set_first_ghost_body",
     "nh_query_build", "nh_query_refit", "nh_query_stats", "nh_raycast", "nh_overlap", "nh_penetration", "nh_spherecast", "nh_raycast_all", "nh_spherecast_all", "nh_boxcast_all", "nh_capsulecast_all", "nh_boxcast", "nh_capsulecast", "nh_closest", "nh_closest_k", "nh_distance",
     "nh_raycast_k", "nh_spherecast_k", "nh_boxcast_k", "nh_capsulecast_k",
+    "nh_query_set_layers", "nh_query_filter", "nh_query_layer_info",
 ]
 HALO_RECORD_BYTES = 64
 
@@ -114,6 +115,10 @@ class QueryStats(C.Structure):
     _fields_ = [("colliders", C.c_uint32), ("run_length", C.c_uint32), ("runs", C.c_uint32), ("top_nodes", C.c_uint32), ("top_depth", C.c_uint32)]
 
 
+class QueryLayerInfo(C.Structure):
+    _fields_ = [("set", C.c_uint32), ("colliders", C.c_uint32), ("any_layers", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class Ray(C.Structure):
     _fields_ = [("origin", C.c_float * 3), ("max_t", C.c_float), ("direction", C.c_float * 3), ("ignore_body", C.c_uint32)]
 
@@ -146,6 +151,7 @@ class PointHit(C.Structure):
                 ("shape", C.c_uint32), ("tag", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+NH_FILTER_OFF, NH_FILTER_UNIFORM, NH_FILTER_PER_QUERY = 0, 1, 2      # nh_query_filter modes (include/nudge_hip.h, "layer masks")
 # scene queries (include/nudge_hip.h, "scene queries"): nh_RayHit.shape (CAPSULE: a query shape only), nh_raycast flags; numpy forms of the records
 NH_SHAPE_BOX, NH_SHAPE_SPHERE, NH_SHAPE_CAPSULE, NH_SHAPE_NONE = 0, 1, 2, 0xFFFFFFFF
 NH_RAY_ANY_HIT = 1
@@ -267,6 +273,11 @@ def lib():
         if hasattr(L, "nh_query_refit"):
             L.nh_query_refit.argtypes = [C.c_void_p, C.POINTER(BodyData), C.POINTER(ColliderData)]
             L.nh_query_stats.argtypes = [C.c_void_p, C.POINTER(QueryStats)]
+        # (likewise the layer masks: World.query_set_layers / query_filter / query_layer_info then raise AttributeError)
+        if hasattr(L, "nh_query_set_layers"):
+            L.nh_query_set_layers.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+            L.nh_query_filter.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+            L.nh_query_layer_info.argtypes = [C.c_void_p, C.POINTER(QueryLayerInfo)]
         L.nh_raycast.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
         L.nh_spherecast.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
         L.nh_boxcast.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
@@ -661,6 +672,61 @@ class World:
         st = QueryStats()
         _check(self.L, self.L.nh_query_stats(self.ctx, C.byref(st)), "nh_query_stats")
         return {k: int(getattr(st, k)) for k, _ in QueryStats._fields_}
+
+    def _layer_words(self, name, words, count):
+        """`words` (None, numpy or torch, `count` values below 2^32) as an int32 device tensor of their bits, or None."""
+        torch = self.torch
+        if words is None:
+            return None
+        if not torch.is_tensor(words):
+            words = torch.from_numpy(np.ascontiguousarray(words).astype(np.int64))
+        t = words.to(device=self.dev).reshape(-1)
+        if t.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)):
+            t = (((t.to(torch.int64) & 0xFFFFFFFF) ^ 0x80000000) - 0x80000000).to(torch.int32)
+        t = t.contiguous()
+        if t.numel() != count:
+            raise ValueError(f"{name}: {t.numel()} words for {count}")
+        return t
+
+    def query_set_layers(self, box_layers=None, sphere_layers=None):
+        """Give every collider of the last query_build() its word of layer bits (nh_query_set_layers; enqueued): `box_layers` / `sphere_layers` are
+        numpy arrays or torch tensors of nbox / nsph values below 2^32, None for all ones; both None forgets the layers.  A query with mask m (see
+        query_filter) sees collider c iff layers[c] & m != 0.  The words are copied: the arguments are not kept."""
+        b = self._layer_words("query_set_layers: box_layers", box_layers, self.colliders.boxes.count)
+        s = self._layer_words("query_set_layers: sphere_layers", sphere_layers, self.colliders.spheres.count)
+        # (a shape without colliders has no words to give: its NULL must not read as "forget" while the other shape has some)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None      # noqa: E731
+        pb, ps = ptr(b), ptr(s)
+        if (b is not None or s is not None) and pb is None and ps is None:
+            return
+        _check(self.L, self.L.nh_query_set_layers(self.ctx, pb, ps), "nh_query_set_layers")
+        # (the copy is enqueued on the library's stream; torch frees on its own: keep the sources until the next call)
+        self._layer_sources = (b, s)
+
+    def query_filter(self, mask=None):
+        """The filter every later query call reads (nh_query_filter): None -- off; an int -- every query uses that mask; a uint32 / int32 device
+        tensor -- query i of each later call uses mask[i] (it must hold as many words as the call has queries; the World keeps a reference, the
+        library the pointer, and the words are read when a query runs)."""
+        torch = self.torch
+        if mask is None:
+            rc = self.L.nh_query_filter(self.ctx, NH_FILTER_OFF, 0, None)
+            keep = None
+        elif torch.is_tensor(mask):
+            if mask.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or not mask.is_contiguous() or mask.device != torch.device(self.dev):
+                raise ValueError("query_filter: per-query masks must be a contiguous uint32 / int32 tensor on the world's device")
+            rc = self.L.nh_query_filter(self.ctx, NH_FILTER_PER_QUERY, 0, C.c_void_p(mask.data_ptr()))
+            keep = mask
+        else:
+            rc = self.L.nh_query_filter(self.ctx, NH_FILTER_UNIFORM, int(mask) & 0xFFFFFFFF, None)
+            keep = None
+        _check(self.L, rc, "nh_query_filter")
+        self._filter_masks = keep
+
+    def query_layer_info(self):
+        """Whether layers are in force and the OR of every collider's word (nh_query_layer_info; waits for the stream): set, colliders, any_layers."""
+        st = QueryLayerInfo()
+        _check(self.L, self.L.nh_query_layer_info(self.ctx, C.byref(st)), "nh_query_layer_info")
+        return {k: int(getattr(st, k)) for k, _ in QueryLayerInfo._fields_ if k != "reserved"}
 
     def _ignore_bits(self, ignore_body):
         """`ignore_body` (None, a body index, or n of them) as the uint32 bits in an int32 tensor."""
