@@ -472,10 +472,10 @@ struct nh_context {
 	nh_AsleepState asleep;
 	uint32_t first_ghost;          // nh_set_first_ghost_body: bodies >= first_ghost are ghosts of a partitioned world (0 = no ownership rule)
 	nh_StateStream stream_state;
-	struct nh_QueryState* query;   // scene queries (nh_query.hip): the hierarchy of the last nh_query_build; nullptr until the first
+	struct nh_QueryState* query;   // scene queries (nh_query_tree.h): the hierarchy of the last nh_query_build; nullptr until the first
 };
 int nh_stream_after_advance(nh_context* ctx);          // nh_advance -> state streaming (nh_context.hip)
-void nh_query_free(nh_context* ctx);                   // nh_destroy -> the scene query's buffers (nh_query.hip)
+void nh_query_free(nh_context* ctx);                   // nh_destroy -> the scene query's buffers (nh_query_build.hip)
 
 // ---- functions used across the .hip files: each is declared here, once, and defined in the file named behind it --------------------------------------
 // (NH_LOCAL: a helper of the library's own that is not part of what libnudge_hip.so exports)
@@ -607,12 +607,14 @@ void nh_timer_begin(nh_context* ctx, const char* name);
 void nh_timer_end(nh_context* ctx);
 void nh_timer_collect(nh_context* ctx);
 
-#define NH_LAUNCH(ctx, name, kernel, grid, block, ...)                                           \
-	do {                                                                                         \
-		if ((ctx)->timing) nh_timer_begin((ctx), name);                                          \
-		hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, (ctx)->stream, __VA_ARGS__);      \
-		if ((ctx)->timing) nh_timer_end((ctx));                                                  \
+// (lds_bytes: dynamic shared memory of the launch)
+#define NH_LAUNCH_LDS(ctx, name, kernel, grid, block, lds_bytes, ...)                                    \
+	do {                                                                                                 \
+		if ((ctx)->timing) nh_timer_begin((ctx), name);                                                  \
+		hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), (lds_bytes), (ctx)->stream, __VA_ARGS__);    \
+		if ((ctx)->timing) nh_timer_end((ctx));                                                          \
 	} while (0)
+#define NH_LAUNCH(ctx, name, kernel, grid, block, ...) NH_LAUNCH_LDS(ctx, name, kernel, grid, block, 0, __VA_ARGS__)
 
 // launch on the side stream (untimed; only between a fork and its join inside one entry point)
 #define NH_LAUNCH_SIDE(ctx, kernel, grid, block, ...) hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, (ctx)->side, __VA_ARGS__)

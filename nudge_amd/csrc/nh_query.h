@@ -97,7 +97,7 @@ NH_HD nh_QHit nh_q_ray_sphere(nh_f3 o, nh_f3 d, nh_f3 c, float rad) {
 	return r;
 }
 
-// The cut of the box pass (nh_query.hip, k_q_boxes_runs / k_q_boxes_top): the leaves, in key order, are cut into runs of NH_Q_RUN.  A Karras node
+// The cut of the box pass (nh_query_build.hip, k_q_boxes_runs / k_q_boxes_top): the leaves, in key order, are cut into runs of NH_Q_RUN.  A Karras node
 // covers the contiguous leaf range [first, last] and its own index is one end of it, so a node whose range lies in ONE run has its index, both
 // children and their whole subtrees in that run (its workgroup merges it in LDS, slot = index - run start); every other node CROSSES a run boundary
 // and belongs to the top phase.  k_q_tree writes the verdict on a node's PARENT next to the parent's index (parents are internal nodes: < 2^30), with

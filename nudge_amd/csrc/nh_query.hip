@@ -1,374 +1,14 @@
-// nh_query.hip -- scene queries against the device-resident world: nh_query_build (a linear BVH over every box and sphere collider, built from
-// the current transforms), nh_query_refit (the same tree with the boxes of the current transforms), nh_raycast (batched closest-hit / any-hit ray
-// casts against the last build or refit), nh_spherecast, nh_boxcast and nh_capsulecast (the same for swept balls, oriented boxes and capsules) and
-// nh_overlap (the colliders touching each of a batch of spheres, boxes or capsules, as variable-length segments).  include/nudge_hip.h, "scene queries".
-// Layer masks (include/nudge_hip.h, "layer masks"): nh_query_set_layers gives every collider a word of layer bits and every node the OR of the words below it
-// (the layer pass, below the box pass); nh_query_filter sets the mask(s) every later query call walks under, in the FILTER = true instantiation of its kernel.
-//
-// Build (one launch each, plus the library's radix sort):
-//   k_q_xform   one lane per collider (boxes, then spheres): world pose (k_xform's arithmetic, nh_query.h) and the record the ray test reads; the
-//               bounds of the collider positions by a wave reduction, a reduction over the workgroup's waves in LDS and one atomic per workgroup
-//   k_q_keys    48-bit Morton key of each position in the frame of those bounds (nh_morton_scale / nh_morton_of), value = collider index
-//   nh_sort_u64_u32  stable: equal keys keep collider order, which the tree's key comparison extends by the sorted index (Karras 2012, 4)
-//   k_q_tree    one lane per internal node: range and split from common prefixes, children and parents (the parent word says whether the parent
-//               crosses a run boundary, nh_query.h); per split, the node that starts right of it; the list of the top phase's entry nodes
-//   k_q_links   one lane per internal node: its escape link, read from that table
-//   the box pass, below
-// Box pass (the tail of the build, and all of nh_query_refit: it reads the sorted index, the parent words, rchild and right_at of the last build):
-//   k_q_boxes_runs  one workgroup per run of NH_Q_RUN consecutive leaves, a lane per leaf: world pose, record and padded leaf box straight from the
-//               caller's arrays, then the internal nodes whose range lies inside the run, bottom-up with arrival counters in LDS
-//   k_q_boxes_top   behind the kernel boundary, ONE workgroup: the nodes whose range crosses a run boundary, from the entry list, with arrival
-//               counters in global memory at workgroup scope
-// Node ids: internal nodes 0 .. n-2 (root 0), leaf j (j-th collider in key order) n-1+j; with one collider the root is that leaf.
+
+// nh_query.hip -- scene queries against the tree of the last nh_query_build or nh_query_refit (nh_query_build.hip, nh_query_tree.h): nh_raycast (batched
+// closest-hit / any-hit ray casts), nh_spherecast, nh_boxcast and nh_capsulecast (the same for swept balls, oriented boxes and capsules), their all-hits
+// (_all) and first-k (_k) forms, nh_closest / nh_closest_k / nh_distance (the nearest colliders to a point or a shape) and nh_overlap / nh_penetration (the
+// colliders touching each of a batch of spheres, boxes or capsules, as variable-length segments).  include/nudge_hip.h, "scene queries".
+// Layer masks (include/nudge_hip.h, "layer masks"): every query call walks under the mask(s) nh_query_filter set, in the FILTER = true instantiation of its kernel.
 // Traversal is stackless: a node that is missed or a leaf that is done continues at its ESCAPE link (the next node in pre-order after its subtree),
 // a hit internal node at its left child.  A private stack array would go to scratch memory.
 #include <type_traits>
 #include <utility>
-#include "nh_internal.h"
-#include "nh_query.h"
-
-#define NH_Q_LEAF 0x80000000u
-#define NH_Q_NONE 0xffffffffu
-#define NH_Q_MAX_COLLIDERS (1u << 30)
-
-// The ray test's record of a collider, by collider index: a = (world position, bits(body)), b = world rotation, c = (half extents | radius, -, -,
-// bits(tag))
-struct nh_QRec { float4 a, b, c; };
-// A node: a = (box min, left child | NH_Q_LEAF + collider), b = (box max, escape link)
-struct nh_QNode { float4 a, b; };
-// words the build's kernels share: collider count (the sort reads it), bounds of the positions (flipped floats); nh_overlap's: a word that stays 0
-// (the element count of its scan is all `extra`), the length of the written prefix of records (its sort and gather read it), the wrap flag; the bounds
-// of the LAST build (k_q_tree keeps them there before it resets smin / smax: nh_closest's seed finds a point's place among the keys in their frame);
-// the box pass's: the number of entry nodes of the top phase (k_q_tree counts them) and the height of the tree of top nodes (k_q_boxes_top, for
-// nh_query_stats).  A refit touches top_depth alone.
-struct nh_QCtl { uint32_t count, zero, ov_written, ov_wrap; uint32_t smin[4]; uint32_t smax[4]; uint32_t kmin[4]; uint32_t kmax[4];
-                 uint32_t top_n, top_depth, pad0, pad1; };
-
-struct nh_QueryState {
-	uint32_t capacity;           // colliders the buffers have room for
-	bool built;
-	uint32_t n, nbox;            // of the last build
-	nh_QCtl* ctl;
-	nh_QRec* rec;
-	uint64_t* keys_a; uint64_t* keys_b; uint32_t* idx_a; uint32_t* idx_b; uint32_t* hist;
-	const uint64_t* keys;        // the sorted keys of the last build (keys_a or keys_b, as the sort left them): leaf j's is keys[j]
-	const uint32_t* idx;         // the leaf order of the last build (idx_a or idx_b): leaf j is collider idx[j]
-	nh_QNode* nodes;             // 2 n - 1
-	uint32_t* parent;            // by node id: nh_q_parent_word (nh_query.h)
-	uint32_t* rchild;            // by internal node
-	uint32_t* last;              // by internal node: last leaf of its range
-	uint32_t* right_at;          // by split position: the right child of the node that splits there
-	uint32_t* arrive;            // by internal node: arrival counter of the top phase (0 between launches)
-	uint32_t* top;               // the entry nodes of the top phase: nodes inside one run whose parent crosses a run boundary (ctl->top_n of them)
-	uint32_t ov_capacity;        // nh_overlap's sort scratch, by record of the caller's capacity
-	uint64_t* ov_keys_a; uint64_t* ov_keys_b; uint32_t* ov_vals_a; uint32_t* ov_vals_b;
-	// layer masks (header, "layer masks"): the layer word of every collider of the last build, by combined index, and per node the OR of the words of
-	// the leaves below it (2 n - 1 words by node id, the layer pass writes them); both are only meaningful while layers_set
-	uint32_t layer_capacity;     // colliders the two arrays have room for
-	bool layers_set;
-	uint32_t* layers;
-	uint32_t* node_layers;
-	uint32_t filter_mode;        // NH_FILTER_*: context state, read by every query call
-	uint32_t filter_mask;
-	const uint32_t* filter_masks;   // the caller's, kept by pointer (NH_FILTER_PER_QUERY)
-};
-
-// the caller's arrays as the kernels read them
-struct nh_QWorld {
-	const nh_Transform* body_xf; uint32_t nbodies;
-	const nh_Transform* box_xf; const nh_BoxCollider* box_data; const uint32_t* box_tags; uint32_t nbox;
-	const nh_Transform* sph_xf; const nh_SphereCollider* sph_data; const uint32_t* sph_tags; uint32_t nsph;
-};
-
-// Collider c (combined index): its record, and the half extents of its world AABB
-__device__ __forceinline__ nh_f3 nh_q_collider(const nh_QWorld& W, uint32_t c, nh_QRec& r) {
-	const bool is_box = c < W.nbox;
-	const nh_Transform l = is_box ? W.box_xf[c] : W.sph_xf[c - W.nbox];
-	nh_QPose w;
-	nh_f3 h;
-	if (l.body < W.nbodies) {
-		const nh_Transform b = W.body_xf[l.body];
-		w = nh_q_pose(b.position, b.rotation, l.position, l.rotation);
-	} else {
-		// (a collider of a body that does not exist: never hit, never in the bounds)
-		const float q = __uint_as_float(0x7fc00000u);
-		w.p = nh_make3(q, q, q); w.q = { q, q, q, q };
-	}
-	if (is_box) {
-		const nh_BoxCollider bc = W.box_data[c];
-		h = nh_make3(bc.size[0], bc.size[1], bc.size[2]);
-	} else {
-		const float rad = W.sph_data[c - W.nbox].radius;
-		h = nh_make3(rad, rad, rad);
-	}
-	const uint32_t tag = is_box ? W.box_tags[c] : W.sph_tags[c - W.nbox];
-	r.a = make_float4(w.p.x, w.p.y, w.p.z, __uint_as_float(l.body));
-	r.b = make_float4(w.q.x, w.q.y, w.q.z, w.q.s);
-	r.c = make_float4(h.x, h.y, h.z, __uint_as_float(tag));
-	return is_box ? nh_q_box_extent(w.q, h) : h;
-}
-
-// ---- build ----------------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_q_xform(nh_QWorld W, nh_QRec* __restrict__ rec, nh_QCtl* __restrict__ ctl) {
-	__shared__ uint32_t wave_min[4][3], wave_max[4][3];
-	const uint32_t n = W.nbox + W.nsph;
-	if (blockIdx.x == 0 && threadIdx.x == 0) { ctl->count = n; ctl->top_n = 0u; ctl->top_depth = 0u; }
-	uint32_t lmin[3] = { 0xffffffffu, 0xffffffffu, 0xffffffffu }, lmax[3] = { 0u, 0u, 0u };
-	for (uint32_t c = blockIdx.x * blockDim.x + threadIdx.x; c < n; c += gridDim.x * blockDim.x) {
-		nh_QRec r;
-		nh_q_collider(W, c, r);
-		rec[c] = r;
-		if (r.a.x == r.a.x && r.a.y == r.a.y && r.a.z == r.a.z) {
-			uint32_t f;
-			f = nh_float_flip(r.a.x); lmin[0] = min(lmin[0], f); lmax[0] = max(lmax[0], f);
-			f = nh_float_flip(r.a.y); lmin[1] = min(lmin[1], f); lmax[1] = max(lmax[1], f);
-			f = nh_float_flip(r.a.z); lmin[2] = min(lmin[2], f); lmax[2] = max(lmax[2], f);
-		}
-	}
-	for (int k = 0; k < 3; ++k) {
-		for (int d = 32; d >= 1; d >>= 1) {
-			lmin[k] = min(lmin[k], (uint32_t)__shfl_xor((int)lmin[k], d));
-			lmax[k] = max(lmax[k], (uint32_t)__shfl_xor((int)lmax[k], d));
-		}
-	}
-	if (nh_lane() == 0) {
-		for (int k = 0; k < 3; ++k) { wave_min[threadIdx.x >> 6][k] = lmin[k]; wave_max[threadIdx.x >> 6][k] = lmax[k]; }
-	}
-	__syncthreads();
-	if (threadIdx.x < 3u) {
-		const uint32_t k = threadIdx.x;
-		const uint32_t mn = min(min(wave_min[0][k], wave_min[1][k]), min(wave_min[2][k], wave_min[3][k]));
-		const uint32_t mx = max(max(wave_max[0][k], wave_max[1][k]), max(wave_max[2][k], wave_max[3][k]));
-		// (no finite position in this workgroup: mn stays all ones and mx 0, which change nothing)
-		if (mn <= mx) { atomicMin(&ctl->smin[k], mn); atomicMax(&ctl->smax[k], mx); }
-	}
-}
-
-__global__ __launch_bounds__(256) void k_q_keys(const nh_QRec* __restrict__ rec, const nh_QCtl* __restrict__ ctl, uint32_t n,
-                                                uint64_t* __restrict__ keys, uint32_t* __restrict__ idx) {
-	const nh_f3 smin = nh_make3(nh_float_unflip(ctl->smin[0]), nh_float_unflip(ctl->smin[1]), nh_float_unflip(ctl->smin[2]));
-	const nh_f3 smax = nh_make3(nh_float_unflip(ctl->smax[0]), nh_float_unflip(ctl->smax[1]), nh_float_unflip(ctl->smax[2]));
-	const float scale = nh_morton_scale(smin, smax);
-	const nh_f3 smin_scaled = smin * scale;
-	for (uint32_t c = blockIdx.x * blockDim.x + threadIdx.x; c < n; c += gridDim.x * blockDim.x) {
-		const float4 a = rec[c].a;
-		keys[c] = nh_morton_of(nh_make3(a.x, a.y, a.z), scale, smin_scaled);
-		idx[c] = c;
-	}
-}
-
-// Karras 2012: length of the common prefix of the keys at sorted positions i and j, extended by the positions themselves on equal keys; -1 outside
-__device__ __forceinline__ int nh_q_delta(const uint64_t* __restrict__ keys, uint32_t n, int64_t i, int64_t j) {
-	if (j < 0 || j >= (int64_t)n) return -1;
-	const uint64_t a = keys[i], b = keys[j];
-	if (a == b) return 64 + __clz((uint32_t)i ^ (uint32_t)j);
-	return __clzll(a ^ b);
-}
-
-__global__ __launch_bounds__(256) void k_q_tree(const uint64_t* __restrict__ keys, uint32_t n, nh_QNode* __restrict__ nodes, uint32_t* __restrict__ parent,
-                                                uint32_t* __restrict__ rchild, uint32_t* __restrict__ last, uint32_t* __restrict__ right_at,
-                                                uint32_t* __restrict__ arrive, uint32_t* __restrict__ top, nh_QCtl* __restrict__ ctl) {
-	if (blockIdx.x == 0 && threadIdx.x == 0) {
-		parent[0] = NH_Q_NONE;
-		// the bounds the next build accumulates into (k_q_keys of this one has read them); this build's are kept for nh_closest
-		for (int k = 0; k < 3; ++k) { ctl->kmin[k] = ctl->smin[k]; ctl->kmax[k] = ctl->smax[k]; ctl->smin[k] = 0xffffffffu; ctl->smax[k] = 0u; }
-	}
-	// (whole waves go round together: the entry list is reserved per wave)
-	for (uint32_t u0 = blockIdx.x * blockDim.x; u0 + 1u < n; u0 += gridDim.x * blockDim.x) {
-		const uint32_t u = u0 + threadIdx.x;
-		bool enter_left = false, enter_right = false;
-		uint32_t left = 0u, right = 0u;
-		if (u + 1u < n) {
-			const int64_t i = u;
-			const int d = nh_q_delta(keys, n, i, i + 1) > nh_q_delta(keys, n, i, i - 1) ? 1 : -1;
-			const int dmin = nh_q_delta(keys, n, i, i - d);
-			int64_t lmax = 2;
-			while (nh_q_delta(keys, n, i, i + lmax * d) > dmin) lmax *= 2;
-			int64_t l = 0;
-			for (int64_t t = lmax / 2; t >= 1; t /= 2)
-				if (nh_q_delta(keys, n, i, i + (l + t) * d) > dmin) l += t;
-			const int64_t j = i + l * d;
-			const int dnode = nh_q_delta(keys, n, i, j);
-			int64_t s = 0, t = l;
-			do {
-				t = (t + 1) / 2;
-				if (nh_q_delta(keys, n, i, i + (s + t) * d) > dnode) s += t;
-			} while (t > 1);
-			const int64_t gamma = i + s * d + (d < 0 ? -1 : 0);
-			const int64_t first = i < j ? i : j, end = i < j ? j : i;
-			left = first == gamma ? (uint32_t)(n - 1u + gamma) : (uint32_t)gamma;
-			right = end == gamma + 1 ? (uint32_t)(n - 1u + gamma + 1) : (uint32_t)(gamma + 1);
-			nodes[u].a.w = __uint_as_float(left);
-			rchild[u] = right;
-			last[u] = (uint32_t)end;
-			right_at[gamma] = right;
-			const bool crossing = nh_q_run_crossing((uint32_t)first, (uint32_t)end);
-			parent[left] = nh_q_parent_word(u, false, crossing);
-			parent[right] = nh_q_parent_word(u, true, crossing);
-			arrive[u] = 0u;
-			// the top phase starts at the children that lie inside one run
-			enter_left = crossing && !nh_q_run_crossing((uint32_t)first, (uint32_t)gamma);
-			enter_right = crossing && !nh_q_run_crossing((uint32_t)gamma + 1u, (uint32_t)end);
-		}
-		const uint32_t at_left = nh_wave_reserve1(&ctl->top_n, enter_left);
-		if (enter_left) top[at_left] = left;
-		const uint32_t at_right = nh_wave_reserve1(&ctl->top_n, enter_right);
-		if (enter_right) top[at_right] = right;
-	}
-}
-
-// escape links of the internal nodes: the subtree of a node ends at the last leaf of its range; the next node in pre-order is the right child of the
-// split there (a leaf's is right_at[its position]: k_q_boxes_runs writes it with the leaf)
-__global__ __launch_bounds__(256) void k_q_links(uint32_t n, nh_QNode* __restrict__ nodes, const uint32_t* __restrict__ last, const uint32_t* __restrict__ right_at) {
-	for (uint32_t u = blockIdx.x * blockDim.x + threadIdx.x; u + 1u < n; u += gridDim.x * blockDim.x) {
-		const uint32_t e = last[u];
-		nodes[u].b.w = __uint_as_float(e + 1u == n ? NH_Q_NONE : right_at[e]);
-	}
-}
-
-// ---- box pass -------------------------------------------------------------------------------------------------------------------------------
-// Bottom phase.  Workgroup b owns leaves [b * NH_Q_RUN, (b + 1) * NH_Q_RUN) and the internal nodes whose range lies inside them (nh_query.h): LDS slot
-// = node index - run start.  A slot holds the boxes of the node's two children, by side, and its arrival counter: a lane puts its box on its side,
-// then counts itself in; the second to arrive reads the other side, merges and goes on with the parent, until the parent word says "top".  Every
-// hand-off is inside the workgroup: LDS stores released and acquired at workgroup scope by the counter's atomic, no agent-scope fence, no global
-// atomic.  fminf / fmaxf: the boxes do not depend on who arrives first, and a NaN leaf (a body that does not exist) drops out of its ancestors.
-// The finished nodes leave through the slots after a barrier (the .w words of an internal node, child and escape links, stay as the build wrote them).
-__global__ __launch_bounds__(NH_Q_RUN) void k_q_boxes_runs(nh_QWorld W, const uint32_t* __restrict__ idx, const uint32_t* __restrict__ parent,
-                                                           const uint32_t* __restrict__ right_at, uint32_t n, nh_QRec* __restrict__ rec, nh_QNode* __restrict__ nodes) {
-	__shared__ float child_box[NH_Q_RUN][2][6];
-	__shared__ uint32_t arrived[NH_Q_RUN];
-	__shared__ uint32_t up[NH_Q_RUN];            // parent words of the run's internal nodes
-	const uint32_t base = blockIdx.x * NH_Q_RUN, s = threadIdx.x, j = base + s;
-	arrived[s] = 0u;
-	up[s] = j + 1u < n ? parent[j] : NH_Q_NONE;
-	uint32_t pw = NH_Q_NONE;
-	float lo[3] = { 0.0f, 0.0f, 0.0f }, hi[3] = { 0.0f, 0.0f, 0.0f };
-	if (j < n) {
-		const uint32_t c = idx[j];
-		nh_QRec r;
-		const nh_f3 e = nh_q_collider(W, c, r);
-		rec[c] = r;
-		const nh_f3 mn = nh_make3(r.a.x - e.x, r.a.y - e.y, r.a.z - e.z), mx = nh_make3(r.a.x + e.x, r.a.y + e.y, r.a.z + e.z);
-		const float pad = nh_q_pad(mn, mx);      // (nh_query.h: the host's sweep rule rebuilds this box)
-		lo[0] = mn.x - pad; lo[1] = mn.y - pad; lo[2] = mn.z - pad;
-		hi[0] = mx.x + pad; hi[1] = mx.y + pad; hi[2] = mx.z + pad;
-		nh_QNode leaf;
-		leaf.a = make_float4(lo[0], lo[1], lo[2], __uint_as_float(NH_Q_LEAF | c));
-		leaf.b = make_float4(hi[0], hi[1], hi[2], __uint_as_float(j + 1u == n ? NH_Q_NONE : right_at[j]));
-		nodes[n - 1u + j] = leaf;
-		pw = parent[n - 1u + j];
-	}
-	__syncthreads();
-	while (!(pw & NH_Q_PARENT_TOP)) {
-		const uint32_t slot = (pw & NH_Q_PARENT_ID) - base, side = (pw & NH_Q_PARENT_RIGHT) ? 1u : 0u;
-		float* mine = child_box[slot][side];
-		for (int k = 0; k < 3; ++k) { mine[k] = lo[k]; mine[3 + k] = hi[k]; }
-		const uint32_t before = __hip_atomic_fetch_add(&arrived[slot], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
-		if (before == 0u) break;
-		const float* other = child_box[slot][side ^ 1u];
-		for (int k = 0; k < 3; ++k) { lo[k] = fminf(lo[k], other[k]); hi[k] = fmaxf(hi[k], other[3 + k]); }
-		pw = up[slot];
-	}
-	__syncthreads();
-	if (arrived[s] == 2u) {
-		const float* l = child_box[s][0];
-		const float* r = child_box[s][1];
-		float* a = reinterpret_cast<float*>(&nodes[j].a);
-		float* b = reinterpret_cast<float*>(&nodes[j].b);
-		for (int k = 0; k < 3; ++k) { a[k] = fminf(l[k], r[k]); b[k] = fmaxf(l[3 + k], r[3 + k]); }
-	}
-}
-
-// Top phase: the nodes that cross a run boundary -- with B runs at most B - 2 have two crossing children, the rest are chains with one child finished
-// below; few (nh_query_stats counts them) but deep.  The launch boundary has made k_q_boxes_runs' boxes visible.  ONE workgroup climbs from the entry
-// list: a lane whose box is in nodes[] counts itself in at the parent; the second to arrive merges its sibling's box, writes the parent and goes on.
-// All hand-offs are between waves of this one workgroup -- one CU, one L1, one L2 -- so the counter's atomic releases and acquires at WORKGROUP
-// scope and nothing in the pass needs an agent-scope fence.  The second arriver leaves the counter at 0 for the next pass.  The counter's upper 24
-// bits carry the first arriver's height, so that the root's lane knows the height of the top tree (the longest chain, for nh_query_stats).
-#define NH_Q_TOP_BLOCK 1024
-__global__ __launch_bounds__(NH_Q_TOP_BLOCK) void k_q_boxes_top(const uint32_t* __restrict__ top, nh_QCtl* ctl, nh_QNode* nodes,
-                                                                const uint32_t* __restrict__ parent, const uint32_t* __restrict__ rchild, uint32_t* arrive) {
-	const uint32_t m = ctl->top_n;
-	for (uint32_t e = threadIdx.x; e < m; e += NH_Q_TOP_BLOCK) {
-		const uint32_t me = top[e];
-		float4 mn = nodes[me].a, mx = nodes[me].b;
-		uint32_t height = 0u;
-		uint32_t pw = parent[me];
-		while (pw != NH_Q_NONE) {
-			const uint32_t id = pw & NH_Q_PARENT_ID;
-			const uint32_t before = __hip_atomic_fetch_add(&arrive[id], 1u | (height << 8), __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
-			if ((before & 0xffu) == 0u) break;
-			__hip_atomic_store(&arrive[id], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-			height = min(max(height, before >> 8) + 1u, 0xffffffu);
-			const uint32_t other = (pw & NH_Q_PARENT_RIGHT) ? __float_as_uint(nodes[id].a.w) : rchild[id];
-			const float4 omn = nodes[other].a, omx = nodes[other].b;
-			mn = make_float4(fminf(mn.x, omn.x), fminf(mn.y, omn.y), fminf(mn.z, omn.z), 0.0f);
-			mx = make_float4(fmaxf(mx.x, omx.x), fmaxf(mx.y, omx.y), fmaxf(mx.z, omx.z), 0.0f);
-			float* a = reinterpret_cast<float*>(&nodes[id].a);
-			float* b = reinterpret_cast<float*>(&nodes[id].b);
-			a[0] = mn.x; a[1] = mn.y; a[2] = mn.z;
-			b[0] = mx.x; b[1] = mx.y; b[2] = mx.z;
-			pw = parent[id];
-		}
-		if (pw == NH_Q_NONE) ctl->top_depth = height;
-	}
-}
-
-// ---- layer pass ------------------------------------------------------------------------------------------------------------------------------
-// Per node, the OR of the layer words of the leaves below it: the box pass's split with a word in place of a box.  It reads the sorted index, the parent
-// words, rchild and the entry list of the last build and counts arrivals as the box pass does; it runs behind nh_query_set_layers and at the tail of a
-// build while layers are set, never in a refit (the topology stands).
-// Bottom phase: workgroup b gathers the words of its run's colliders into leaf order and climbs inside the run, every hand-off in LDS, released and
-// acquired at workgroup scope by the counter's atomic.  OR does not depend on who arrives first.
-__global__ __launch_bounds__(NH_Q_RUN) void k_q_layers_runs(const uint32_t* __restrict__ layers, const uint32_t* __restrict__ idx, const uint32_t* __restrict__ parent,
-                                                            uint32_t n, uint32_t* __restrict__ node_layers) {
-	__shared__ uint32_t child_word[NH_Q_RUN][2];
-	__shared__ uint32_t arrived[NH_Q_RUN];
-	__shared__ uint32_t up[NH_Q_RUN];            // parent words of the run's internal nodes
-	const uint32_t base = blockIdx.x * NH_Q_RUN, s = threadIdx.x, j = base + s;
-	arrived[s] = 0u;
-	up[s] = j + 1u < n ? parent[j] : NH_Q_NONE;
-	uint32_t pw = NH_Q_NONE, word = 0u;
-	if (j < n) {
-		word = layers[idx[j]];
-		node_layers[n - 1u + j] = word;
-		pw = parent[n - 1u + j];
-	}
-	__syncthreads();
-	while (!(pw & NH_Q_PARENT_TOP)) {
-		const uint32_t slot = (pw & NH_Q_PARENT_ID) - base, side = (pw & NH_Q_PARENT_RIGHT) ? 1u : 0u;
-		child_word[slot][side] = word;
-		const uint32_t before = __hip_atomic_fetch_add(&arrived[slot], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
-		if (before == 0u) break;
-		word |= child_word[slot][side ^ 1u];
-		pw = up[slot];
-	}
-	__syncthreads();
-	if (arrived[s] == 2u) node_layers[j] = child_word[s][0] | child_word[s][1];
-}
-
-// Top phase, behind the kernel boundary: k_q_boxes_top's climb from the entry list in ONE workgroup, the same counters (0 between launches, left at 0),
-// hand-offs at workgroup scope.
-__global__ __launch_bounds__(NH_Q_TOP_BLOCK) void k_q_layers_top(const uint32_t* __restrict__ top, const nh_QCtl* __restrict__ ctl, const nh_QNode* __restrict__ nodes,
-                                                                 const uint32_t* __restrict__ parent, const uint32_t* __restrict__ rchild, uint32_t* arrive,
-                                                                 uint32_t* node_layers) {
-	const uint32_t m = ctl->top_n;
-	for (uint32_t e = threadIdx.x; e < m; e += NH_Q_TOP_BLOCK) {
-		const uint32_t me = top[e];
-		uint32_t word = node_layers[me];
-		uint32_t pw = parent[me];
-		while (pw != NH_Q_NONE) {
-			const uint32_t id = pw & NH_Q_PARENT_ID;
-			const uint32_t before = __hip_atomic_fetch_add(&arrive[id], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
-			if (before == 0u) break;
-			__hip_atomic_store(&arrive[id], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-			const uint32_t other = (pw & NH_Q_PARENT_RIGHT) ? __float_as_uint(nodes[id].a.w) : rchild[id];
-			word |= node_layers[other];
-			node_layers[id] = word;
-			pw = parent[id];
-		}
-	}
-}
+#include "nh_query_tree.h"
 
 // ---- what the walks share -------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ bool nh_q_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
@@ -386,6 +26,56 @@ __device__ __forceinline__ nh_QShape nh_q_unpack(const nh_QRec& r) {
 __device__ __forceinline__ uint4 nh_q_identity(uint32_t c, uint32_t nbox, const nh_QRec& r) {
 	return make_uint4(__float_as_uint(r.a.w), c < nbox ? c : c - nbox, c < nbox ? NH_SHAPE_BOX : NH_SHAPE_SPHERE, __float_as_uint(r.c.w));
 }
+
+// A volume record (nh_OverlapQuery; nh_DistanceQuery starts as one): the one decode nh_overlap, nh_penetration and nh_distance read it through -- the second
+// promises the first's set and the third its validity.  A capsule of half height 0 is a sphere query: the same functions, its rotation not read.  `ok`: a
+// known shape, every field it reads finite, no size negative.  a: the half axis of a capsule (else 0); e: the half extent of the world AABB, not padded.
+struct nh_QVolume {
+	nh_f3 c, h, a, e;
+	nh_quat q;
+	uint32_t ignore;
+	bool capsule, sphere, ok;
+	__device__ __forceinline__ void read(const float4* __restrict__ qp) {
+		const float4 q0 = qp[0], q1 = qp[1], q2 = qp[2];
+		c = nh_make3(q0.x, q0.y, q0.z); h = nh_make3(q2.x, q2.y, q2.z);
+		q = { q1.x, q1.y, q1.z, q1.w };
+		const uint32_t shape = __float_as_uint(q0.w);
+		ignore = __float_as_uint(q2.w);
+		capsule = shape == NH_SHAPE_CAPSULE && h.y != 0.0f;
+		sphere = !capsule && (shape == NH_SHAPE_SPHERE || shape == NH_SHAPE_CAPSULE);
+		ok = (sphere || capsule || shape == NH_SHAPE_BOX) && nh_q_finite(c) && nh_q_finite(h.x) && !(h.x < 0.0f);
+		if (!sphere) ok = ok && nh_q_finite(h.y) && !(h.y < 0.0f) && nh_q_finite(q);
+		if (!sphere && !capsule) ok = ok && nh_q_finite(h.z) && !(h.z < 0.0f);
+		a = capsule ? nh_q_capsule_axis(q, h.y) : nh_make3(0.0f, 0.0f, 0.0f);
+		e = sphere ? nh_make3(h.x, h.x, h.x) : capsule ? nh_q_capsule_extent(a, h.x) : nh_q_box_extent(q, h);
+	}
+};
+
+// A list call's segment of records (nh_overlap, nh_penetration, the all-hits casts): the count pass (LIST = false) counts what query i finds into
+// offsets[i]; behind the scan the list pass (LIST = true) finds the same again and writes record k of query i at offsets[i] + k.  Key and value are
+// the caller's own.
+template <bool LIST>
+struct nh_QSegment {
+	uint32_t base = 0u, end = 0u, k = 0u;
+	// before the loop over the queries; `first`: the chain's first launch resets the words the scan and k_q_overlap_fix go on from.  The written prefix.
+	__device__ static __forceinline__ uint32_t begin(bool first, uint32_t* offsets, uint32_t count, nh_QCtl* ctl) {
+		if (!LIST && first && blockIdx.x == 0 && threadIdx.x == 0) { offsets[count] = 0u; ctl->ov_wrap = 0u; ctl->ov_written = 0u; }   // (k_q_overlap_fix sets both)
+		return LIST ? ctl->ov_written : 0u;
+	}
+	// false: query i has nothing to list -- its segment is empty, or not in the written prefix
+	__device__ __forceinline__ bool open(const uint32_t* offsets, uint32_t i, uint32_t written) {
+		if (!LIST) return true;
+		base = offsets[i]; end = offsets[i + 1u];
+		return base < end && end <= written;
+	}
+	__device__ __forceinline__ uint32_t at() const { return base + k; }
+	// one more found (LIST: written at at()); true ends the walk: the count pass found exactly end - base, so the segment is full and nothing else can follow
+	__device__ __forceinline__ bool add() {
+		if (LIST && base + k + 1u == end) return true;
+		++k;
+		return false;
+	}
+};
 
 // The stackless walk (the head of this file) from `node`: enter(lo, hi, x) says whether a node's box is entered and may leave a number x for the leaf
 // (the casts' entry t0, the point query's squared distance); leaf(c, record, x) sees every entered leaf whose body is not `ignore` and returns true
@@ -563,6 +253,22 @@ __device__ __forceinline__ void nh_q_write_hit(nh_RayHit* __restrict__ hit, cons
 	hp[1] = make_float4(__uint_as_float(out.body), __uint_as_float(out.collider), __uint_as_float(out.shape), __uint_as_float(out.tag));
 }
 
+// One nh_PointHit, as three 16-byte stores: collider c at distance d with normal n and closest point x, or, for c = NH_Q_NONE, the miss record, whose distance
+// is d (the caller's max_distance) -- a quiet NaN where the query itself is not `valid`.
+__device__ __forceinline__ void nh_q_write_point(nh_PointHit* __restrict__ hit, const nh_QRec* __restrict__ rec, uint32_t nbox, bool valid, uint32_t c, float d, nh_f3 n, nh_f3 x) {
+	float4* hp = reinterpret_cast<float4*>(hit);
+	if (c == NH_Q_NONE) {
+		hp[0] = make_float4(valid ? d : __uint_as_float(0x7fc00000u), 0.0f, 0.0f, 0.0f);
+		hp[1] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(NH_Q_NONE));
+		hp[2] = make_float4(__uint_as_float(NH_Q_NONE), __uint_as_float(NH_SHAPE_NONE), __uint_as_float(NH_Q_NONE), 0.0f);
+	} else {
+		const uint4 id = nh_q_identity(c, nbox, rec[c]);
+		hp[0] = make_float4(d, n.x, n.y, n.z);
+		hp[1] = make_float4(x.x, x.y, x.z, __uint_as_float(id.x));
+		hp[2] = make_float4(__uint_as_float(id.y), __uint_as_float(id.z), __uint_as_float(id.w), 0.0f);
+	}
+}
+
 // One lane per cast: the walk prunes at the best t so far, nh_q_better (nh_query.h) keeps the closest hit and the tie rule, any_hit stops at the first.
 template <class Shape, bool FILTER>
 __device__ __forceinline__ void nh_q_cast(const float4* __restrict__ casts, uint32_t count, nh_RayHit* __restrict__ hits, const nh_QNode* __restrict__ nodes,
@@ -648,47 +354,50 @@ __device__ __forceinline__ void nh_q_seed(nh_f3 p, uint32_t win, uint32_t ignore
 	}
 }
 
+// nh_PointQuery as k_q_closest and k_q_closest_k read it, and the point function of a collider's record
+struct nh_QPointQuery {
+	nh_f3 p;
+	float max_d;
+	uint32_t ignore;
+	bool ok;
+	__device__ __forceinline__ void read(const float4* __restrict__ qp) {
+		const float4 q0 = qp[0], q1 = qp[1];
+		p = nh_make3(q0.x, q0.y, q0.z);
+		max_d = q0.w;
+		ignore = __float_as_uint(q1.x);
+		ok = nh_q_finite(p) && max_d >= 0.0f;       // (+inf is a valid max_distance; NaN is not)
+	}
+	__device__ __forceinline__ nh_QPoint to(const nh_QRec& q, bool box) const {
+		const nh_QShape s = nh_q_unpack(q);
+		return box ? nh_q_point_box(p, s.p, s.q, s.h) : nh_q_point_sphere(p, s.p, s.h.x);
+	}
+};
+
 template <bool FILTER>
 __global__ __launch_bounds__(256) void k_q_closest(const nh_PointQuery* __restrict__ queries, uint32_t count, nh_PointHit* __restrict__ hits,
                                                    const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec, const uint64_t* __restrict__ keys,
                                                    const nh_QCtl* __restrict__ ctl, uint32_t n, uint32_t nbox, nh_QFilter F) {
 	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
-		const float4* qp = reinterpret_cast<const float4*>(queries + i);
-		const float4 q0 = qp[0], q1 = qp[1];
-		const nh_f3 p = nh_make3(q0.x, q0.y, q0.z);
-		const float max_d = q0.w;
-		const uint32_t ignore = __float_as_uint(q1.x);
-		const bool ok = nh_q_finite(p) && max_d >= 0.0f;       // (+inf is a valid max_distance; NaN is not)
-		float bd = max_d;
+		nh_QPointQuery Q;
+		Q.read(reinterpret_cast<const float4*>(queries + i));
+		float bd = Q.max_d;
 		uint32_t bc = NH_Q_NONE;
 		nh_f3 bn = nh_make3(0.0f, 0.0f, 0.0f), bx = nh_make3(0.0f, 0.0f, 0.0f);
-		const bool walk = ok && n;
+		const bool walk = Q.ok && n;
 		const uint32_t fm = FILTER ? F.of(i) : 0u;
 		// a leaf of squared box distance d2, for the seed and the walk alike
 		const auto leaf = [&](uint32_t c, const nh_QRec& q, float d2) {
-			const nh_QShape s = nh_q_unpack(q);
-			const nh_QPoint h = c < nbox ? nh_q_point_box(p, s.p, s.q, s.h) : nh_q_point_sphere(p, s.p, s.h.x);
+			const nh_QPoint h = Q.to(q, c < nbox);
 			const float k = nh_q_point_key(h.d, d2);
-			if (nh_q_closer(k, c, max_d, bd, bc)) { bd = k; bc = c; bn = h.n; bx = h.x; }
+			if (nh_q_closer(k, c, Q.max_d, bd, bc)) { bd = k; bc = c; bn = h.n; bx = h.x; }
 			return false;
 		};
 #ifndef NH_Q_CLOSEST_NO_SEED
-		if (walk) nh_q_seed<FILTER>(p, NH_Q_SEED, ignore, nodes, rec, keys, ctl, n, F, fm, [&](uint32_t c, const nh_QRec& q, nh_f3 lo, nh_f3 hi) { leaf(c, q, nh_q_point_node(lo, hi, p)); });
+		if (walk) nh_q_seed<FILTER>(Q.p, NH_Q_SEED, Q.ignore, nodes, rec, keys, ctl, n, F, fm, [&](uint32_t c, const nh_QRec& q, nh_f3 lo, nh_f3 hi) { leaf(c, q, nh_q_point_node(lo, hi, Q.p)); });
 #endif
-		nh_q_walk<FILTER>(nodes, rec, walk ? 0u : NH_Q_NONE, ignore, F, fm,
-			[&](nh_f3 lo, nh_f3 hi, float& d2) { d2 = nh_q_point_node(lo, hi, p); return !(d2 > 0.0f && sqrtf(d2) > bd); }, leaf);
-		float4* hp = reinterpret_cast<float4*>(hits + i);
-		if (bc == NH_Q_NONE) {
-			const float md = ok ? max_d : __uint_as_float(0x7fc00000u);
-			hp[0] = make_float4(md, 0.0f, 0.0f, 0.0f);
-			hp[1] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(NH_Q_NONE));
-			hp[2] = make_float4(__uint_as_float(NH_Q_NONE), __uint_as_float(NH_SHAPE_NONE), __uint_as_float(NH_Q_NONE), 0.0f);
-		} else {
-			const uint4 id = nh_q_identity(bc, nbox, rec[bc]);
-			hp[0] = make_float4(bd, bn.x, bn.y, bn.z);
-			hp[1] = make_float4(bx.x, bx.y, bx.z, __uint_as_float(id.x));
-			hp[2] = make_float4(__uint_as_float(id.y), __uint_as_float(id.z), __uint_as_float(id.w), 0.0f);
-		}
+		nh_q_walk<FILTER>(nodes, rec, walk ? 0u : NH_Q_NONE, Q.ignore, F, fm,
+			[&](nh_f3 lo, nh_f3 hi, float& d2) { d2 = nh_q_point_node(lo, hi, Q.p); return !(d2 > 0.0f && sqrtf(d2) > bd); }, leaf);
+		nh_q_write_point(hits + i, rec, nbox, Q.ok, bc, bd, bn, bx);
 	}
 }
 
@@ -722,54 +431,39 @@ __global__ __launch_bounds__(256) void k_q_closest_k(const nh_PointQuery* __rest
 	const uint32_t stride = blockDim.x;
 	nh_QNear* const list = q_near + threadIdx.x;
 	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
-		const float4* qp = reinterpret_cast<const float4*>(queries + i);
-		const float4 q0 = qp[0], q1 = qp[1];
-		const nh_f3 p = nh_make3(q0.x, q0.y, q0.z);
-		const float max_d = q0.w;
-		const uint32_t ignore = __float_as_uint(q1.x);
-		const bool ok = nh_q_finite(p) && max_d >= 0.0f;       // (+inf is a valid max_distance; NaN is not)
-		float bd = max_d;
+		nh_QPointQuery Q;
+		Q.read(reinterpret_cast<const float4*>(queries + i));
+		float bd = Q.max_d;
 		uint32_t held = 0u;
-		const bool walk = ok && n;
+		const bool walk = Q.ok && n;
 		const uint32_t fm = FILTER ? F.of(i) : 0u;
 		// a leaf of squared box distance d2, for the seed and the walk alike
 		const auto leaf = [&](uint32_t c, const nh_QRec& q, float d2) {
-			const nh_QShape s = nh_q_unpack(q);
-			const nh_QPoint h = c < nbox ? nh_q_point_box(p, s.p, s.q, s.h) : nh_q_point_sphere(p, s.p, s.h.x);
-			const float key = nh_q_point_key(h.d, d2);
+			const float key = nh_q_point_key(Q.to(q, c < nbox).d, d2);
 			if (!(key <= bd)) return false;
-			if (nh_q_nearest_insert(list, stride, k, &held, key, c, max_d) && held == k) bd = list[(k - 1u) * stride].key;
+			if (nh_q_nearest_insert(list, stride, k, &held, key, c, Q.max_d) && held == k) bd = list[(k - 1u) * stride].key;
 			return false;
 		};
 #ifndef NH_Q_CLOSEST_K_NO_SEED
-		if (walk) nh_q_seed<FILTER>(p, NH_Q_SEED + k / 2u, ignore, nodes, rec, keys, ctl, n, F, fm, [&](uint32_t c, const nh_QRec& q, nh_f3 lo, nh_f3 hi) { leaf(c, q, nh_q_point_node(lo, hi, p)); });
+		if (walk) nh_q_seed<FILTER>(Q.p, NH_Q_SEED + k / 2u, Q.ignore, nodes, rec, keys, ctl, n, F, fm, [&](uint32_t c, const nh_QRec& q, nh_f3 lo, nh_f3 hi) { leaf(c, q, nh_q_point_node(lo, hi, Q.p)); });
 #endif
-		nh_q_walk<FILTER>(nodes, rec, walk ? 0u : NH_Q_NONE, ignore, F, fm,
-			[&](nh_f3 lo, nh_f3 hi, float& d2) { d2 = nh_q_point_node(lo, hi, p); return !(d2 > 0.0f && sqrtf(d2) > bd); }, leaf);
-		float4* hp = reinterpret_cast<float4*>(hits + (size_t)i * k);
-		for (uint32_t j = 0u; j < held; ++j, hp += 3) {
+		nh_q_walk<FILTER>(nodes, rec, walk ? 0u : NH_Q_NONE, Q.ignore, F, fm,
+			[&](nh_f3 lo, nh_f3 hi, float& d2) { d2 = nh_q_point_node(lo, hi, Q.p); return !(d2 > 0.0f && sqrtf(d2) > bd); }, leaf);
+		nh_PointHit* out = hits + (size_t)i * k;
+		for (uint32_t j = 0u; j < held; ++j, ++out) {
 			const nh_QNear e = list[j * stride];
-			const nh_QRec q = rec[e.c];
-			const nh_QShape s = nh_q_unpack(q);
-			const nh_QPoint h = e.c < nbox ? nh_q_point_box(p, s.p, s.q, s.h) : nh_q_point_sphere(p, s.p, s.h.x);
-			const uint4 id = nh_q_identity(e.c, nbox, q);
-			hp[0] = make_float4(e.key, h.n.x, h.n.y, h.n.z);
-			hp[1] = make_float4(h.x.x, h.x.y, h.x.z, __uint_as_float(id.x));
-			hp[2] = make_float4(__uint_as_float(id.y), __uint_as_float(id.z), __uint_as_float(id.w), 0.0f);
+			const nh_QPoint h = Q.to(rec[e.c], e.c < nbox);
+			nh_q_write_point(out, rec, nbox, true, e.c, e.key, h.n, h.x);
 		}
-		const float md = ok ? max_d : __uint_as_float(0x7fc00000u);
-		for (uint32_t j = held; j < k; ++j, hp += 3) {
-			hp[0] = make_float4(md, 0.0f, 0.0f, 0.0f);
-			hp[1] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(NH_Q_NONE));
-			hp[2] = make_float4(__uint_as_float(NH_Q_NONE), __uint_as_float(NH_SHAPE_NONE), __uint_as_float(NH_Q_NONE), 0.0f);
-		}
+		// (one cursor through both loops: with out[j] the kernel compiles to 13 more VGPRs and a wave less)
+		for (uint32_t j = held; j < k; ++j, ++out) nh_q_write_point(out, rec, nbox, Q.ok, NH_Q_NONE, Q.max_d, nh_make3(0.0f, 0.0f, 0.0f), nh_make3(0.0f, 0.0f, 0.0f));
 		if (counts) counts[i] = held;
 	}
 }
 
 // ---- distance ---------------------------------------------------------------------------------------------------------------------------------
 // nh_distance: one lane per query shape on nh_q_walk, k_q_closest with a volume in place of the point.
-//   decode  k_q_overlap's: the shape, its validity (nh_overlap's, and max_distance >= 0), the half axis of a capsule, the world AABB [qlo, qhi] (not padded)
+//   decode  nh_QVolume: the shape, its validity (nh_overlap's, and max_distance >= 0), the half axis of a capsule, the world AABB [qlo, qhi] (not padded)
 //   bound   bd starts at max_distance and only ever falls to the key of a real candidate (nh_q_point_key of the pair function's separation and the gap to
 //           the collider's own leaf box, nh_q_closer), so a node at squared gap g2 > 0 from the query's AABB with sqrtf(g2) > bd can be skipped: the gap is
 //           monotone from a leaf box to every box that contains it (nh_q_dist_node), and a collider's key is at least sqrtf of its leaf's gap
@@ -782,20 +476,11 @@ __global__ __launch_bounds__(256) void k_q_distance(const nh_DistanceQuery* __re
                                                     const nh_QCtl* __restrict__ ctl, uint32_t n, uint32_t nbox, nh_QFilter F) {
 	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
 		const float4* qp = reinterpret_cast<const float4*>(queries + i);
-		const float4 q0 = qp[0], q1 = qp[1], q2 = qp[2];
+		nh_QVolume v;
+		v.read(qp);
 		const float max_d = qp[3].x;          // (the record moves as four 16-byte words; of the fourth only .x is used: `reserved` takes part in nothing)
-		const nh_f3 c = nh_make3(q0.x, q0.y, q0.z), h = nh_make3(q2.x, q2.y, q2.z);
-		const nh_quat qr = { q1.x, q1.y, q1.z, q1.w };
-		const uint32_t shape = __float_as_uint(q0.w), ignore = __float_as_uint(q2.w);
-		// (a capsule of half height 0 is a sphere query: the same functions, its rotation not read)
-		const bool capsule = shape == NH_SHAPE_CAPSULE && h.y != 0.0f;
-		const bool sphere = !capsule && (shape == NH_SHAPE_SPHERE || shape == NH_SHAPE_CAPSULE);
-		bool ok = (sphere || capsule || shape == NH_SHAPE_BOX) && nh_q_finite(c) && nh_q_finite(h.x) && !(h.x < 0.0f) && max_d >= 0.0f;
-		if (!sphere) ok = ok && nh_q_finite(h.y) && !(h.y < 0.0f) && nh_q_finite(qr);
-		if (!sphere && !capsule) ok = ok && nh_q_finite(h.z) && !(h.z < 0.0f);
-		const nh_f3 a = capsule ? nh_q_capsule_axis(qr, h.y) : nh_make3(0.0f, 0.0f, 0.0f);
-		const nh_f3 e = sphere ? nh_make3(h.x, h.x, h.x) : capsule ? nh_q_capsule_extent(a, h.x) : nh_q_box_extent(qr, h);
-		const nh_f3 qlo = c - e, qhi = c + e;
+		const bool ok = v.ok && max_d >= 0.0f;
+		const nh_f3 qlo = v.c - v.e, qhi = v.c + v.e;
 		float bd = max_d;
 		uint32_t bc = NH_Q_NONE;
 		nh_f3 bn = nh_make3(0.0f, 0.0f, 0.0f), bx = nh_make3(0.0f, 0.0f, 0.0f);
@@ -805,28 +490,17 @@ __global__ __launch_bounds__(256) void k_q_distance(const nh_DistanceQuery* __re
 		const auto leaf = [&](uint32_t cc, const nh_QRec& r, float g2) {
 			const nh_QShape s = nh_q_unpack(r);
 			nh_QPoint d;
-			if (capsule) d = cc < nbox ? nh_q_dist_capsule_box_a(c, a, h.x, s.p, s.q, s.h) : nh_q_dist_capsule_sphere_a(c, a, h.x, s.p, s.h.x);
-			else if (cc < nbox) d = sphere ? nh_q_dist_sphere_box(c, h.x, s.p, s.q, s.h) : nh_q_dist_box_box(c, qr, h, s.p, s.q, s.h);
-			else d = sphere ? nh_q_dist_sphere_sphere(c, h.x, s.p, s.h.x) : nh_q_dist_box_sphere(c, qr, h, s.p, s.h.x);
+			if (v.capsule) d = cc < nbox ? nh_q_dist_capsule_box_a(v.c, v.a, v.h.x, s.p, s.q, s.h) : nh_q_dist_capsule_sphere_a(v.c, v.a, v.h.x, s.p, s.h.x);
+			else if (cc < nbox) d = v.sphere ? nh_q_dist_sphere_box(v.c, v.h.x, s.p, s.q, s.h) : nh_q_dist_box_box(v.c, v.q, v.h, s.p, s.q, s.h);
+			else d = v.sphere ? nh_q_dist_sphere_sphere(v.c, v.h.x, s.p, s.h.x) : nh_q_dist_box_sphere(v.c, v.q, v.h, s.p, s.h.x);
 			const float k = nh_q_point_key(d.d, g2);
 			if (nh_q_closer(k, cc, max_d, bd, bc)) { bd = k; bc = cc; bn = d.n; bx = d.x; }
 			return false;
 		};
-		if (walk) nh_q_seed<FILTER>(c, NH_Q_SEED, ignore, nodes, rec, keys, ctl, n, F, fm, [&](uint32_t cc, const nh_QRec& r, nh_f3 lo, nh_f3 hi) { leaf(cc, r, nh_q_dist_node(lo, hi, qlo, qhi)); });
-		nh_q_walk<FILTER>(nodes, rec, walk ? 0u : NH_Q_NONE, ignore, F, fm,
+		if (walk) nh_q_seed<FILTER>(v.c, NH_Q_SEED, v.ignore, nodes, rec, keys, ctl, n, F, fm, [&](uint32_t cc, const nh_QRec& r, nh_f3 lo, nh_f3 hi) { leaf(cc, r, nh_q_dist_node(lo, hi, qlo, qhi)); });
+		nh_q_walk<FILTER>(nodes, rec, walk ? 0u : NH_Q_NONE, v.ignore, F, fm,
 			[&](nh_f3 lo, nh_f3 hi, float& g2) { g2 = nh_q_dist_node(lo, hi, qlo, qhi); return !(g2 > 0.0f && sqrtf(g2) > bd); }, leaf);
-		float4* hp = reinterpret_cast<float4*>(hits + i);
-		if (bc == NH_Q_NONE) {
-			const float md = ok ? max_d : __uint_as_float(0x7fc00000u);
-			hp[0] = make_float4(md, 0.0f, 0.0f, 0.0f);
-			hp[1] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(NH_Q_NONE));
-			hp[2] = make_float4(__uint_as_float(NH_Q_NONE), __uint_as_float(NH_SHAPE_NONE), __uint_as_float(NH_Q_NONE), 0.0f);
-		} else {
-			const uint4 id = nh_q_identity(bc, nbox, rec[bc]);
-			hp[0] = make_float4(bd, bn.x, bn.y, bn.z);
-			hp[1] = make_float4(bx.x, bx.y, bx.z, __uint_as_float(id.x));
-			hp[2] = make_float4(__uint_as_float(id.y), __uint_as_float(id.z), __uint_as_float(id.w), 0.0f);
-		}
+		nh_q_write_point(hits + i, rec, nbox, ok, bc, bd, bn, bx);
 	}
 }
 
@@ -846,53 +520,33 @@ template <bool LIST, bool CAPSULE, bool FILTER>
 __global__ __launch_bounds__(256) void k_q_overlap(const nh_OverlapQuery* __restrict__ queries, uint32_t count, uint32_t* offsets,
                                                    const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox,
                                                    nh_QCtl* ctl, uint64_t* __restrict__ keys, uint32_t* __restrict__ vals, uint32_t cbits, nh_QFilter F) {
-	if (!LIST && !CAPSULE && blockIdx.x == 0 && threadIdx.x == 0) { offsets[count] = 0u; ctl->ov_wrap = 0u; ctl->ov_written = 0u; }   // (k_q_overlap_fix sets both)
-	const uint32_t written = LIST ? ctl->ov_written : 0u;
+	const uint32_t written = nh_QSegment<LIST>::begin(!CAPSULE, offsets, count, ctl);
 	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
-		uint32_t base = 0u, end = 0u;
-		if (LIST) {
-			base = offsets[i]; end = offsets[i + 1u];
-			if (!(base < end && end <= written)) continue;          // empty, or not in the written prefix
-		}
-		const float4* qp = reinterpret_cast<const float4*>(queries + i);
-		const float4 q0 = qp[0], q1 = qp[1], q2 = qp[2];
-		const nh_f3 c = nh_make3(q0.x, q0.y, q0.z), h = nh_make3(q2.x, q2.y, q2.z);
-		const nh_quat qr = { q1.x, q1.y, q1.z, q1.w };
-		const uint32_t shape = __float_as_uint(q0.w), ignore = __float_as_uint(q2.w);
-		// (a capsule of half height 0 is a sphere query: the same walk, the same predicates, its rotation not read.  Every other capsule -- an invalid
-		// half height included -- is the CAPSULE instantiation's, and only its)
-		if ((shape == NH_SHAPE_CAPSULE && h.y != 0.0f) != CAPSULE) continue;
-		const bool capsule = CAPSULE;
-		const bool sphere = !CAPSULE && (shape == NH_SHAPE_SPHERE || shape == NH_SHAPE_CAPSULE);
-		bool ok = (sphere || capsule || shape == NH_SHAPE_BOX) && nh_q_finite(c.x) && nh_q_finite(c.y) && nh_q_finite(c.z) && nh_q_finite(h.x) && !(h.x < 0.0f);
-		if (!sphere) ok = ok && nh_q_finite(h.y) && !(h.y < 0.0f) && nh_q_finite(qr.x) && nh_q_finite(qr.y) && nh_q_finite(qr.z) && nh_q_finite(qr.s);
-		if (!sphere && !capsule) ok = ok && nh_q_finite(h.z) && !(h.z < 0.0f);
+		nh_QSegment<LIST> seg;
+		if (!seg.open(offsets, i, written)) continue;
+		nh_QVolume v;
+		v.read(reinterpret_cast<const float4*>(queries + i));
+		// (a capsule of half height 0 is a sphere query: the same walk, the same predicates.  Every other capsule -- an invalid half height included -- is
+		// the CAPSULE instantiation's, and only its; each instantiation drops the other's predicates at compile time)
+		if (v.capsule != CAPSULE) continue;
+		const bool capsule = CAPSULE, sphere = !CAPSULE && v.sphere;
 		// the query's world AABB, padded by 2^-18 of its largest coordinate (only ever more generous than the exact test)
-		const nh_f3 a = capsule ? nh_q_capsule_axis(qr, h.y) : nh_make3(0.0f, 0.0f, 0.0f);
-		const nh_f3 e = sphere ? nh_make3(h.x, h.x, h.x) : capsule ? nh_q_capsule_extent(a, h.x) : nh_q_box_extent(qr, h);
-		nh_f3 lo = c - e, hi = c + e;
+		nh_f3 lo = v.c - v.e, hi = v.c + v.e;
 		const float s = fmaxf(fmaxf(fmaxf(fabsf(lo.x), fabsf(lo.y)), fmaxf(fabsf(lo.z), fabsf(hi.x))), fmaxf(fabsf(hi.y), fabsf(hi.z))) * 3.814697265625e-06f;
 		lo = nh_make3(lo.x - s, lo.y - s, lo.z - s); hi = nh_make3(hi.x + s, hi.y + s, hi.z + s);
-		uint32_t k = 0u;
-		nh_q_walk<FILTER>(nodes, rec, ok && n ? 0u : NH_Q_NONE, ignore, F, FILTER ? F.of(i) : 0u,
+		nh_q_walk<FILTER>(nodes, rec, v.ok && n ? 0u : NH_Q_NONE, v.ignore, F, FILTER ? F.of(i) : 0u,
 			[&](nh_f3 nlo, nh_f3 nhi, float&) { return nlo.x <= hi.x && lo.x <= nhi.x && nlo.y <= hi.y && lo.y <= nhi.y && nlo.z <= hi.z && lo.z <= nhi.z; },
 			[&](uint32_t cc, const nh_QRec& r, float) {
 				const nh_QShape col = nh_q_unpack(r);
 				bool hit;
-				if (capsule) hit = cc < nbox ? nh_q_overlap_capsule_box_a(c, a, h.x, col.p, col.q, col.h) : nh_q_overlap_capsule_sphere_a(c, a, h.x, col.p, col.h.x);
-				else if (cc < nbox) hit = sphere ? nh_q_overlap_sphere_box(c, h.x, col.p, col.q, col.h) : nh_q_overlap_box_box(c, qr, h, col.p, col.q, col.h);
-				else hit = sphere ? nh_q_overlap_sphere_sphere(c, h.x, col.p, col.h.x) : nh_q_overlap_sphere_box(col.p, col.h.x, c, qr, h);
+				if (capsule) hit = cc < nbox ? nh_q_overlap_capsule_box_a(v.c, v.a, v.h.x, col.p, col.q, col.h) : nh_q_overlap_capsule_sphere_a(v.c, v.a, v.h.x, col.p, col.h.x);
+				else if (cc < nbox) hit = sphere ? nh_q_overlap_sphere_box(v.c, v.h.x, col.p, col.q, col.h) : nh_q_overlap_box_box(v.c, v.q, v.h, col.p, col.q, col.h);
+				else hit = sphere ? nh_q_overlap_sphere_sphere(v.c, v.h.x, col.p, col.h.x) : nh_q_overlap_sphere_box(col.p, col.h.x, v.c, v.q, v.h);
 				if (!hit) return false;
-				if (LIST) {
-					// (the count pass found exactly end - base: the segment is full once they are written, nothing else can follow)
-					keys[base + k] = ((uint64_t)i << cbits) | cc;
-					vals[base + k] = cc;
-					if (base + k + 1u == end) return true;
-				}
-				++k;
-				return false;
+				if (LIST) { keys[seg.at()] = ((uint64_t)i << cbits) | cc; vals[seg.at()] = cc; }
+				return seg.add();
 			});
-		if (!LIST) offsets[i] = k;
+		if (!LIST) offsets[i] = seg.k;
 	}
 }
 
@@ -938,21 +592,14 @@ __global__ __launch_bounds__(256) void k_q_penetration_gather(const uint64_t* __
 		const uint32_t cc = vals[j];
 		const uint64_t i = keys[j] >> cbits;
 		if (cc >= n || i >= count) continue;          // (cannot happen: the list pass fills the whole prefix; a guard against reading outside the records)
-		const float4* qp = reinterpret_cast<const float4*>(queries + i);
-		const float4 q0 = qp[0], q1 = qp[1], q2 = qp[2];
-		const nh_f3 c = nh_make3(q0.x, q0.y, q0.z), h = nh_make3(q2.x, q2.y, q2.z);
-		const nh_quat qr = { q1.x, q1.y, q1.z, q1.w };
-		const uint32_t shape = __float_as_uint(q0.w);
-		const bool capsule = shape == NH_SHAPE_CAPSULE && h.y != 0.0f;
-		const bool sphere = !capsule && (shape == NH_SHAPE_SPHERE || shape == NH_SHAPE_CAPSULE);
+		nh_QVolume v;
+		v.read(reinterpret_cast<const float4*>(queries + i));
 		const nh_QRec r = rec[cc];
 		const nh_QShape s = nh_q_unpack(r);
 		nh_QPen o;
-		if (capsule) {
-			const nh_f3 a = nh_q_capsule_axis(qr, h.y);
-			o = cc < nbox ? nh_q_pen_capsule_box_a(c, a, h.x, s.p, s.q, s.h) : nh_q_pen_capsule_sphere_a(c, a, h.x, s.p, s.h.x);
-		} else if (cc < nbox) o = sphere ? nh_q_pen_sphere_box(c, h.x, s.p, s.q, s.h) : nh_q_pen_box_box(c, qr, h, s.p, s.q, s.h);
-		else o = sphere ? nh_q_pen_sphere_sphere(c, h.x, s.p, s.h.x) : nh_q_pen_box_sphere(c, qr, h, s.p, s.h.x);
+		if (v.capsule) o = cc < nbox ? nh_q_pen_capsule_box_a(v.c, v.a, v.h.x, s.p, s.q, s.h) : nh_q_pen_capsule_sphere_a(v.c, v.a, v.h.x, s.p, s.h.x);
+		else if (cc < nbox) o = v.sphere ? nh_q_pen_sphere_box(v.c, v.h.x, s.p, s.q, s.h) : nh_q_pen_box_box(v.c, v.q, v.h, s.p, s.q, s.h);
+		else o = v.sphere ? nh_q_pen_sphere_sphere(v.c, v.h.x, s.p, s.h.x) : nh_q_pen_box_sphere(v.c, v.q, v.h, s.p, s.h.x);
 		uint4* out = reinterpret_cast<uint4*>(hits + j);
 		out[0] = make_uint4(__float_as_uint(o.n.x), __float_as_uint(o.n.y), __float_as_uint(o.n.z), __float_as_uint(o.depth));
 		out[1] = nh_q_identity(cc, nbox, r);
@@ -980,42 +627,49 @@ __global__ __launch_bounds__(256) void k_q_penetration_gather(const uint64_t* __
 //                       normal goes through a sort.
 // every shape's decode, validity and grow are the closest-hit casts' own: a shape without a size gives the ray's bytes, a capsule of hh = 0 the ball's, and
 // the first record of a cast is the closest-hit record.  The box and capsule instantiations take their closest-hit siblings' waves-per-EU hint (ALL_WAVES)
+// The node test of "every hit up to `bound`" (max_t for the all-hits casts, the k-th t so far for the first-k casts); ray = k.raylike().  A ray's node box
+// also takes the predicates' own rounding, nh_q_all_pad; a sized shape's reach rule reads the entry of the box as the build stores it.
+template <class Shape>
+__device__ __forceinline__ bool nh_q_all_node(const Shape& k, bool ray, nh_f3 lo, nh_f3 hi, float bound, float& t0) {
+	if (ray) return nh_q_cast_node(lo, hi, k.o, k.inv, k.grow() + nh_q_all_pad(lo, hi, k.o), t0) && t0 <= bound;
+	return k.node(lo, hi, t0) && t0 <= bound;
+}
+
+// The record of a collider c the walk of cast k listed, rebuilt where no walk is at hand: the 48-byte collider record re-read, the leaf entry of the reach
+// rule from S::entry, S::all again -- the same function on the same inputs, the same bits -- and out through nh_q_write_hit.
+template <class Shape>
+__device__ __forceinline__ void nh_q_rebuild_hit(const Shape& k, uint32_t c, nh_RayHit* __restrict__ hit, const nh_QRec* __restrict__ rec, uint32_t nbox) {
+	const nh_QShape s = nh_q_unpack(rec[c]);
+	float t0 = 0.0f;
+	k.entry(s, c < nbox, t0);                          // (entered: the walk listed it)
+	const nh_QHit h = k.all(s, c < nbox, t0);
+	nh_q_write_hit(hit, rec, nbox, true, c, h.t, h.n);
+}
+
 template <class Shape, bool LIST, bool FILTER>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(Shape::ALL_WAVES))) void k_q_castall(const float4* __restrict__ casts, uint32_t count, uint32_t* offsets,
                                                    const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox,
                                                    nh_QCtl* ctl, uint64_t* __restrict__ keys, uint32_t* __restrict__ vals, uint32_t cbits, uint32_t one_sort, nh_QFilter F) {
-	if (!LIST && blockIdx.x == 0 && threadIdx.x == 0) { offsets[count] = 0u; ctl->ov_wrap = 0u; ctl->ov_written = 0u; }   // (k_q_overlap_fix sets both)
-	const uint32_t written = LIST ? ctl->ov_written : 0u;
+	const uint32_t written = nh_QSegment<LIST>::begin(true, offsets, count, ctl);
 	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
-		uint32_t base = 0u, end = 0u;
-		if (LIST) {
-			base = offsets[i]; end = offsets[i + 1u];
-			if (!(base < end && end <= written)) continue;          // empty, or not in the written prefix
-		}
+		nh_QSegment<LIST> seg;
+		if (!seg.open(offsets, i, written)) continue;
 		Shape k;
 		k.read(casts + (size_t)i * Shape::WORDS);
 		const bool ray = k.raylike();
-		uint32_t hits = 0u;
 		nh_q_walk<FILTER>(nodes, rec, k.ok && n ? 0u : NH_Q_NONE, k.ignore, F, FILTER ? F.of(i) : 0u,
-			[&](nh_f3 lo, nh_f3 hi, float& t0) {
-				// (a ray's node box also takes the predicates' own rounding, nh_q_all_pad; a sized shape's reach rule reads the entry of the box as the build stores it)
-				if (ray) return nh_q_cast_node(lo, hi, k.o, k.inv, k.grow() + nh_q_all_pad(lo, hi, k.o), t0) && t0 <= k.max_t;
-				return k.node(lo, hi, t0) && t0 <= k.max_t;
-			},
+			[&](nh_f3 lo, nh_f3 hi, float& t0) { return nh_q_all_node(k, ray, lo, hi, k.max_t, t0); },
 			[&](uint32_t c, const nh_QRec& q, float t0) {
 				const nh_QHit h = k.all(nh_q_unpack(q), c < nbox, t0);
 				if (!h.hit) return false;
 				if (LIST) {
-					// (the count pass found exactly end - base: the segment is full once they are written, nothing else can follow)
 					const uint32_t tb = nh_q_tbits(h.t);
-					keys[base + hits] = one_sort ? ((uint64_t)i << (32u + cbits)) | ((uint64_t)tb << cbits) | c : ((uint64_t)i << cbits) | c;
-					vals[base + hits] = one_sort ? c : tb;
-					if (base + hits + 1u == end) return true;
+					keys[seg.at()] = one_sort ? ((uint64_t)i << (32u + cbits)) | ((uint64_t)tb << cbits) | c : ((uint64_t)i << cbits) | c;
+					vals[seg.at()] = one_sort ? c : tb;
 				}
-				++hits;
-				return false;
+				return seg.add();
 			});
-		if (!LIST) offsets[i] = hits;
+		if (!LIST) offsets[i] = seg.k;
 	}
 }
 
@@ -1041,11 +695,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(Shape::ALL_
 		if (c >= n || i >= count) continue;          // (cannot happen: the list pass fills the whole prefix; a guard against reading outside the records)
 		Shape k;
 		k.read(casts + (size_t)i * Shape::WORDS);
-		const nh_QShape s = nh_q_unpack(rec[c]);
-		float t0 = 0.0f;
-		k.entry(s, c < nbox, t0);                          // (entered: the walk listed it)
-		const nh_QHit h = k.all(s, c < nbox, t0);
-		nh_q_write_hit(hits + j, rec, nbox, true, c, h.t, h.n);
+		nh_q_rebuild_hit(k, c, hits + j, rec, nbox);
 	}
 }
 
@@ -1078,10 +728,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(Shape::K_WA
 		float bd = k.max_t;
 		uint32_t held = 0u;
 		nh_q_walk<FILTER>(nodes, rec, k.ok && n ? 0u : NH_Q_NONE, k.ignore, F, FILTER ? F.of(i) : 0u,
-			[&](nh_f3 lo, nh_f3 hi, float& t0) {
-				if (ray) return nh_q_cast_node(lo, hi, k.o, k.inv, k.grow() + nh_q_all_pad(lo, hi, k.o), t0) && t0 <= bd;
-				return k.node(lo, hi, t0) && t0 <= bd;
-			},
+			[&](nh_f3 lo, nh_f3 hi, float& t0) { return nh_q_all_node(k, ray, lo, hi, bd, t0); },
 			[&](uint32_t c, const nh_QRec& q, float t0) {
 				const nh_QHit h = k.all(nh_q_unpack(q), c < nbox, t0);
 				if (!h.hit || !(h.t <= bd)) return false;
@@ -1089,100 +736,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(Shape::K_WA
 				return false;
 			});
 		nh_RayHit* out = hits + (size_t)i * kk;
-		for (uint32_t j = 0u; j < held; ++j) {
-			const uint32_t c = list[j * stride].c;
-			const nh_QShape s = nh_q_unpack(rec[c]);
-			float t0 = 0.0f;
-			k.entry(s, c < nbox, t0);                          // (entered: the walk listed it)
-			const nh_QHit h = k.all(s, c < nbox, t0);
-			nh_q_write_hit(out + j, rec, nbox, true, c, h.t, h.n);
-		}
+		for (uint32_t j = 0u; j < held; ++j) nh_q_rebuild_hit(k, list[j * stride].c, out + j, rec, nbox);
 		for (uint32_t j = held; j < kk; ++j) nh_q_write_hit(out + j, rec, nbox, k.ok, NH_Q_NONE, k.max_t, nh_make3(0.0f, 0.0f, 0.0f));
 		if (counts) counts[i] = held;
 	}
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------------------
-void nh_query_free(nh_context* ctx) {
-	nh_QueryState* q = ctx->query;
-	if (!q) return;
-	void* bufs[] = { q->ctl, q->rec, q->keys_a, q->keys_b, q->idx_a, q->idx_b, q->hist, q->nodes, q->parent, q->rchild, q->last, q->right_at, q->arrive, q->top,
-	                 q->ov_keys_a, q->ov_keys_b, q->ov_vals_a, q->ov_vals_b, q->layers, q->node_layers };
-	for (void* b : bufs) if (b) hipFree(b);
-	delete q;
-	ctx->query = nullptr;
-}
-
-// (buffers by collider count; a growth waits for the stream first: the last build / cast may still read the old ones)
-static int nh_query_reserve(nh_context* ctx, uint32_t C) {
-	if (!ctx->query) ctx->query = new nh_QueryState();
-	nh_QueryState* q = ctx->query;
-	if (!q->ctl) {
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&q->ctl, sizeof(nh_QCtl)));
-		NH_HIP_CHECK(ctx, hipMemsetAsync(q->ctl, 0, sizeof(nh_QCtl), ctx->stream));
-		NH_HIP_CHECK(ctx, hipMemsetAsync(q->ctl->smin, 0xff, sizeof(q->ctl->smin), ctx->stream));
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&q->hist, sizeof(uint32_t) * (256u * NH_SORT_GRID + 512u)));
-	}
-	if (C <= q->capacity) return NH_OK;
-	const uint32_t cap = C + C / 8u + 64u;
-	NH_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-	void* old[] = { q->rec, q->keys_a, q->keys_b, q->idx_a, q->idx_b, q->nodes, q->parent, q->rchild, q->last, q->right_at, q->arrive, q->top };
-	for (void* b : old) if (b) hipFree(b);
-	q->rec = nullptr; q->keys_a = q->keys_b = nullptr; q->idx_a = q->idx_b = nullptr; q->nodes = nullptr;
-	q->parent = q->rchild = q->last = q->right_at = q->arrive = q->top = nullptr;
-	q->capacity = 0; q->built = false; q->keys = nullptr; q->idx = nullptr;
-	NH_HIP_CHECK(ctx, hipMalloc((void**)&q->rec, sizeof(nh_QRec) * (size_t)cap));
-	NH_HIP_CHECK(ctx, hipMalloc((void**)&q->keys_a, sizeof(uint64_t) * (size_t)cap));
-	NH_HIP_CHECK(ctx, hipMalloc((void**)&q->keys_b, sizeof(uint64_t) * (size_t)cap));
-	NH_HIP_CHECK(ctx, hipMalloc((void**)&q->idx_a, sizeof(uint32_t) * (size_t)cap));
-	NH_HIP_CHECK(ctx, hipMalloc((void**)&q->idx_b, sizeof(uint32_t) * (size_t)cap));
-	NH_HIP_CHECK(ctx, hipMalloc((void**)&q->nodes, 2u * sizeof(nh_QNode) * (size_t)cap));
-	NH_HIP_CHECK(ctx, hipMalloc((void**)&q->parent, 2u * sizeof(uint32_t) * (size_t)cap));
-	NH_HIP_CHECK(ctx, hipMalloc((void**)&q->rchild, sizeof(uint32_t) * (size_t)cap));
-	NH_HIP_CHECK(ctx, hipMalloc((void**)&q->last, sizeof(uint32_t) * (size_t)cap));
-	NH_HIP_CHECK(ctx, hipMalloc((void**)&q->right_at, sizeof(uint32_t) * (size_t)cap));
-	NH_HIP_CHECK(ctx, hipMalloc((void**)&q->arrive, sizeof(uint32_t) * (size_t)cap));
-	// (a node has at most one entry child per side, and a tree of n leaves at most n entries: every entry is the root of a disjoint subtree)
-	NH_HIP_CHECK(ctx, hipMalloc((void**)&q->top, sizeof(uint32_t) * (size_t)cap));
-	q->capacity = cap;
-	return NH_OK;
-}
-
-static int nh_query_args(const nh_BodyData* bodies, const nh_ColliderData* colliders, uint32_t* count) {
-	const uint32_t nbox = colliders->boxes.count, nsph = colliders->spheres.count;
-	const uint64_t C64 = (uint64_t)nbox + nsph;
-	if (C64 >= NH_Q_MAX_COLLIDERS) return NH_ERR_INVALID;
-	if (C64 && (!bodies->transforms && bodies->count)) return NH_ERR_INVALID;
-	if (nbox && (!colliders->boxes.tags || !colliders->boxes.data || !colliders->boxes.transforms)) return NH_ERR_INVALID;
-	if (nsph && (!colliders->spheres.tags || !colliders->spheres.data || !colliders->spheres.transforms)) return NH_ERR_INVALID;
-	*count = (uint32_t)C64;
-	return NH_OK;
-}
-
-static nh_QWorld nh_query_world(const nh_BodyData* bodies, const nh_ColliderData* colliders) {
-	nh_QWorld W;
-	W.body_xf = bodies->transforms; W.nbodies = bodies->count;
-	W.box_xf = colliders->boxes.transforms; W.box_data = colliders->boxes.data; W.box_tags = colliders->boxes.tags; W.nbox = colliders->boxes.count;
-	W.sph_xf = colliders->spheres.transforms; W.sph_data = colliders->spheres.data; W.sph_tags = colliders->spheres.tags; W.nsph = colliders->spheres.count;
-	return W;
-}
-
-// The box pass over the tree of the last build: two launches, the second only where the tree has more than one run.
-static void nh_query_boxes(nh_context* ctx, const nh_QWorld& W, uint32_t C) {
-	nh_QueryState* q = ctx->query;
-	NH_LAUNCH(ctx, "q_boxes_runs", k_q_boxes_runs, (C + NH_Q_RUN - 1u) / NH_Q_RUN, NH_Q_RUN, W, q->idx, q->parent, q->right_at, C, q->rec, q->nodes);
-	if (C > NH_Q_RUN) NH_LAUNCH(ctx, "q_boxes_top", k_q_boxes_top, 1, NH_Q_TOP_BLOCK, q->top, q->ctl, q->nodes, q->parent, q->rchild, q->arrive);
-}
-
-// The layer pass over the tree of the last build (the comment above k_q_layers_runs): two launches, the second only where the tree has more than one run.
-static void nh_query_layer_pass(nh_context* ctx) {
-	nh_QueryState* q = ctx->query;
-	const uint32_t C = q->n;
-	if (!C) return;
-	NH_LAUNCH(ctx, "q_layers_runs", k_q_layers_runs, (C + NH_Q_RUN - 1u) / NH_Q_RUN, NH_Q_RUN, q->layers, q->idx, q->parent, C, q->node_layers);
-	if (C > NH_Q_RUN) NH_LAUNCH(ctx, "q_layers_top", k_q_layers_top, 1, NH_Q_TOP_BLOCK, q->top, q->ctl, q->nodes, q->parent, q->rchild, q->arrive, q->node_layers);
-}
-
 // What the walking kernels get of the context's filter; `on`: the call launches the FILTER = true instantiation.
 static nh_QFilter nh_query_filter_of(const nh_QueryState* q, bool* on) {
 	*on = q->filter_mode != NH_FILTER_OFF;
@@ -1193,140 +753,26 @@ static nh_QFilter nh_query_filter_of(const nh_QueryState* q, bool* on) {
 	return F;
 }
 
-// Observer: no nh_flush_pending, no view export, no counter -- only launches on the stream and buffers of its own (header, "scene queries").
-extern "C" int nh_query_build(nh_context* ctx, const nh_BodyData* bodies, const nh_ColliderData* colliders) {
-	if (!ctx || !bodies || !colliders) return NH_ERR_INVALID;
-	uint32_t C = 0;
-	{ const int rc = nh_query_args(bodies, colliders, &C); if (rc) return rc; }
+// The argument rules of the calls that write a fixed number of records per query, in the order that decides the error code: the flags the call takes, its k
+// bound (k_max = 0: it has no k), its count bound (count_end = 0: none), its optional counts.  The caller returns what this returns where that is an error
+// or count == 0.
+static int nh_query_call(nh_context* ctx, uint32_t flags, uint32_t flags_allowed, uint32_t k, uint32_t k_max, uint32_t count, uint32_t count_end,
+                         const void* in, const void* out, const uint32_t* counts) {
+	if (!ctx || !ctx->query || !ctx->query->built) return NH_ERR_INVALID;
+	if ((flags & ~flags_allowed) || (k_max && (k == 0u || k > k_max)) || (count_end && count >= count_end)) return NH_ERR_INVALID;
+	if (count == 0u) return NH_OK;
+	if (!in || !out || (((uintptr_t)in | (uintptr_t)out) & 15u) || ((uintptr_t)counts & 3u)) return NH_ERR_INVALID;    // (records are moved as 16-byte words)
 	NH_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-	{ const int rc = nh_query_reserve(ctx, C); if (rc) return rc; }
-	nh_QueryState* q = ctx->query;
-	if (C) {
-		const nh_QWorld W = nh_query_world(bodies, colliders);
-		NH_LAUNCH(ctx, "q_xform", k_q_xform, nh_grid_for(C, 256, 4096), 256, W, q->rec, q->ctl);
-		NH_LAUNCH(ctx, "q_keys", k_q_keys, nh_grid_for(C, 256, 4096), 256, q->rec, q->ctl, C, q->keys_a, q->idx_a);
-		// 48-bit keys: six passes, the result back in the *_a buffers
-		const int in_b = nh_sort_u64_u32(ctx, q->keys_a, q->keys_b, q->idx_a, q->idx_b, &q->ctl->count, q->hist, 0, 48);
-		q->keys = in_b ? q->keys_b : q->keys_a;
-		q->idx = in_b ? q->idx_b : q->idx_a;
-		NH_LAUNCH(ctx, "q_tree", k_q_tree, nh_grid_for(C > 1u ? C - 1u : 1u, 256, 4096), 256, q->keys, C, q->nodes, q->parent, q->rchild, q->last, q->right_at, q->arrive,
-		          q->top, q->ctl);
-		if (C > 1u) NH_LAUNCH(ctx, "q_links", k_q_links, nh_grid_for(C - 1u, 256, 4096), 256, C, q->nodes, q->last, q->right_at);
-		nh_query_boxes(ctx, W, C);
-	}
-	// (layers are by combined collider index: they outlive a build with the same two counts, whose tree needs the node words again)
-	const bool same_world = q->built && q->n == C && q->nbox == colliders->boxes.count;
-	q->built = true; q->n = C; q->nbox = colliders->boxes.count;
-	if (q->layers_set && !same_world) q->layers_set = false;
-	if (q->layers_set) nh_query_layer_pass(ctx);
 	return NH_OK;
 }
 
-// Layer words of the colliders of the last build (header, "layer masks").  Observer like the build.
-extern "C" int nh_query_set_layers(nh_context* ctx, const uint32_t* box_layers, const uint32_t* sphere_layers) {
-	if (!ctx) return NH_ERR_INVALID;
-	nh_QueryState* q = ctx->query;
-	if (!q || !q->built) return NH_ERR_INVALID;
-	if (((uintptr_t)box_layers | (uintptr_t)sphere_layers) & 3u) return NH_ERR_INVALID;
-	if (!box_layers && !sphere_layers) { q->layers_set = false; return NH_OK; }
-	NH_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-	if (q->capacity > q->layer_capacity) {
-		// (a growth waits for the stream first, as nh_query_reserve's does: a filtered call may still read the old words)
-		NH_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-		if (q->layers) hipFree(q->layers);
-		if (q->node_layers) hipFree(q->node_layers);
-		q->layers = q->node_layers = nullptr;
-		q->layer_capacity = 0; q->layers_set = false;
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&q->layers, sizeof(uint32_t) * (size_t)q->capacity));
-		NH_HIP_CHECK(ctx, hipMalloc((void**)&q->node_layers, 2u * sizeof(uint32_t) * (size_t)q->capacity));
-		q->layer_capacity = q->capacity;
-	}
-	const uint32_t nbox = q->nbox, nsph = q->n - q->nbox;
-	if (nbox) {
-		if (box_layers) NH_HIP_CHECK(ctx, hipMemcpyAsync(q->layers, box_layers, sizeof(uint32_t) * (size_t)nbox, hipMemcpyDeviceToDevice, ctx->stream));
-		else NH_HIP_CHECK(ctx, hipMemsetAsync(q->layers, 0xff, sizeof(uint32_t) * (size_t)nbox, ctx->stream));
-	}
-	if (nsph) {
-		if (sphere_layers) NH_HIP_CHECK(ctx, hipMemcpyAsync(q->layers + nbox, sphere_layers, sizeof(uint32_t) * (size_t)nsph, hipMemcpyDeviceToDevice, ctx->stream));
-		else NH_HIP_CHECK(ctx, hipMemsetAsync(q->layers + nbox, 0xff, sizeof(uint32_t) * (size_t)nsph, ctx->stream));
-	}
-	q->layers_set = true;
-	nh_query_layer_pass(ctx);
-	return NH_OK;
-}
-
-// The filter every later query call reads (header, "layer masks").  Host state only: nothing is launched.
-extern "C" int nh_query_filter(nh_context* ctx, uint32_t mode, uint32_t mask, const uint32_t* masks) {
-	if (!ctx) return NH_ERR_INVALID;
-	nh_QueryState* q = ctx->query;
-	if (!q || !q->built) return NH_ERR_INVALID;
-	if (mode != NH_FILTER_OFF && mode != NH_FILTER_UNIFORM && mode != NH_FILTER_PER_QUERY) return NH_ERR_INVALID;
-	if (mode == NH_FILTER_PER_QUERY && (!masks || ((uintptr_t)masks & 3u))) return NH_ERR_INVALID;
-	q->filter_mode = mode;
-	q->filter_mask = mode == NH_FILTER_UNIFORM ? mask : 0u;
-	q->filter_masks = mode == NH_FILTER_PER_QUERY ? masks : nullptr;
-	return NH_OK;
-}
-
-// Diagnostic: whether layers are in force and the root's node word.  Waits for the stream.
-extern "C" int nh_query_layer_info(nh_context* ctx, nh_QueryLayerInfo* out) {
-	if (!ctx || !out) return NH_ERR_INVALID;
-	nh_QueryState* q = ctx->query;
-	if (!q || !q->built) return NH_ERR_INVALID;
-	NH_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-	uint32_t any = q->n ? 0xffffffffu : 0u;
-	if (q->layers_set && q->n) NH_HIP_CHECK(ctx, hipMemcpyAsync(&any, q->node_layers, sizeof(any), hipMemcpyDeviceToHost, ctx->stream));
-	NH_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-	out->set = q->layers_set ? 1u : 0u;
-	out->colliders = q->n;
-	out->any_layers = any;
-	out->reserved = 0u;
-	return NH_OK;
-}
-
-// The tree of the last build with the boxes of the arrays given now (header: the contract).  Observer like the build; no allocation, no wait.
-extern "C" int nh_query_refit(nh_context* ctx, const nh_BodyData* bodies, const nh_ColliderData* colliders) {
-	if (!ctx || !bodies || !colliders) return NH_ERR_INVALID;
-	nh_QueryState* q = ctx->query;
-	if (!q || !q->built) return NH_ERR_INVALID;
-	uint32_t C = 0;
-	{ const int rc = nh_query_args(bodies, colliders, &C); if (rc) return rc; }
-	// (the leaf order is by combined collider index: other counts are another world)
-	if (colliders->boxes.count != q->nbox || C != q->n) return NH_ERR_INVALID;
-	if (!C) return NH_OK;
-	NH_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-	nh_query_boxes(ctx, nh_query_world(bodies, colliders), C);
-	return NH_OK;
-}
-
-// Diagnostics of the last build's tree (tools/refit_rates.py).  Waits for the stream.
-extern "C" int nh_query_stats(nh_context* ctx, nh_QueryStats* out) {
-	if (!ctx || !out) return NH_ERR_INVALID;
-	nh_QueryState* q = ctx->query;
-	if (!q || !q->built) return NH_ERR_INVALID;
-	NH_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-	nh_QCtl ctl;
-	NH_HIP_CHECK(ctx, hipMemcpyAsync(&ctl, q->ctl, sizeof(ctl), hipMemcpyDeviceToHost, ctx->stream));
-	NH_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-	out->colliders = q->n;
-	out->run_length = NH_Q_RUN;
-	out->runs = (q->n + NH_Q_RUN - 1u) / NH_Q_RUN;
-	out->top_nodes = q->n > NH_Q_RUN && ctl.top_n ? ctl.top_n - 1u : 0u;
-	out->top_depth = q->n > NH_Q_RUN ? ctl.top_depth : 0u;
-	return NH_OK;
-}
-
-// The four closest-hit casts: one record type and one kernel each, the same checks in the same order.
+// The four closest-hit casts: one record type and one kernel each.
 template <class Cast>
 using nh_CastKernel = void (*)(const Cast*, uint32_t, nh_RayHit*, const nh_QNode*, const nh_QRec*, uint32_t, uint32_t, uint32_t, nh_QFilter);
 template <class Cast>
 static int nh_cast(nh_context* ctx, const char* label, nh_CastKernel<Cast> plain, nh_CastKernel<Cast> filtered, const Cast* casts, uint32_t count, nh_RayHit* hits,
                    uint32_t flags) {
-	if (!ctx || !ctx->query || !ctx->query->built) return NH_ERR_INVALID;
-	if (flags & ~(uint32_t)NH_RAY_ANY_HIT) return NH_ERR_INVALID;
-	if (count == 0u) return NH_OK;
-	if (!casts || !hits || (((uintptr_t)casts | (uintptr_t)hits) & 15u)) return NH_ERR_INVALID;    // (records are moved as 16-byte words)
-	NH_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+	{ const int rc = nh_query_call(ctx, flags, NH_RAY_ANY_HIT, 0u, 0u, count, 0u, casts, hits, nullptr); if (rc || count == 0u) return rc; }
 	nh_QueryState* q = ctx->query;
 	bool on;
 	const nh_QFilter F = nh_query_filter_of(q, &on);
@@ -1352,11 +798,7 @@ extern "C" int nh_boxcast(nh_context* ctx, const nh_BoxCast* casts, uint32_t cou
 }
 
 extern "C" int nh_closest(nh_context* ctx, const nh_PointQuery* queries, uint32_t count, nh_PointHit* hits, uint32_t flags) {
-	if (!ctx || !ctx->query || !ctx->query->built) return NH_ERR_INVALID;
-	if (flags != 0u) return NH_ERR_INVALID;
-	if (count == 0u) return NH_OK;
-	if (!queries || !hits || (((uintptr_t)queries | (uintptr_t)hits) & 15u)) return NH_ERR_INVALID;    // (records are moved as 16-byte words)
-	NH_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+	{ const int rc = nh_query_call(ctx, flags, 0u, 0u, 0u, count, 0u, queries, hits, nullptr); if (rc || count == 0u) return rc; }
 	nh_QueryState* q = ctx->query;
 	bool on;
 	const nh_QFilter F = nh_query_filter_of(q, &on);
@@ -1367,29 +809,19 @@ extern "C" int nh_closest(nh_context* ctx, const nh_PointQuery* queries, uint32_
 
 // One launch with the lists' LDS sized by k (the table at k_q_closest_k); no allocation, no wait.
 extern "C" int nh_closest_k(nh_context* ctx, const nh_PointQuery* queries, uint32_t count, uint32_t k, uint32_t* counts, nh_PointHit* hits, uint32_t flags) {
-	if (!ctx || !ctx->query || !ctx->query->built) return NH_ERR_INVALID;
-	if (flags != 0u || k == 0u || k > NH_CLOSEST_K_MAX || count >= (1u << 30)) return NH_ERR_INVALID;
-	if (count == 0u) return NH_OK;
-	if (!queries || !hits || (((uintptr_t)queries | (uintptr_t)hits) & 15u) || ((uintptr_t)counts & 3u)) return NH_ERR_INVALID;    // (records are moved as 16-byte words)
-	NH_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+	{ const int rc = nh_query_call(ctx, flags, 0u, k, NH_CLOSEST_K_MAX, count, 1u << 30, queries, hits, counts); if (rc || count == 0u) return rc; }
 	nh_QueryState* q = ctx->query;
 	const uint32_t block = nh_q_nearest_block(k);
-	if (ctx->timing) nh_timer_begin(ctx, "q_closest_k");
 	bool on;
 	const nh_QFilter F = nh_query_filter_of(q, &on);
-	hipLaunchKernelGGL(on ? k_q_closest_k<true> : k_q_closest_k<false>, dim3(nh_grid_for(count, block, 1u << 20)), dim3(block), block * k * sizeof(nh_QNear), ctx->stream,
-	                   queries, count, k, counts, hits, q->nodes, q->rec, q->keys, q->ctl, q->n, q->nbox, F);
-	if (ctx->timing) nh_timer_end(ctx);
+	NH_LAUNCH_LDS(ctx, "q_closest_k", on ? k_q_closest_k<true> : k_q_closest_k<false>, nh_grid_for(count, block, 1u << 20), block, block * k * sizeof(nh_QNear),
+	              queries, count, k, counts, hits, q->nodes, q->rec, q->keys, q->ctl, q->n, q->nbox, F);
 	return NH_OK;
 }
 
 // One launch, as nh_closest; no allocation, no wait.
 extern "C" int nh_distance(nh_context* ctx, const nh_DistanceQuery* queries, uint32_t count, nh_PointHit* hits, uint32_t flags) {
-	if (!ctx || !ctx->query || !ctx->query->built) return NH_ERR_INVALID;
-	if (flags != 0u || count >= (1u << 30)) return NH_ERR_INVALID;
-	if (count == 0u) return NH_OK;
-	if (!queries || !hits || (((uintptr_t)queries | (uintptr_t)hits) & 15u)) return NH_ERR_INVALID;    // (records are moved as 16-byte words)
-	NH_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+	{ const int rc = nh_query_call(ctx, flags, 0u, 0u, 0u, count, 1u << 30, queries, hits, nullptr); if (rc || count == 0u) return rc; }
 	nh_QueryState* q = ctx->query;
 	bool on;
 	const nh_QFilter F = nh_query_filter_of(q, &on);
@@ -1405,14 +837,9 @@ static int nh_overlap_reserve(nh_context* ctx, uint32_t capacity) {
 	const uint64_t cap64 = (uint64_t)capacity + capacity / 8u + 64u;
 	const uint32_t cap = cap64 > 0xffffffffull ? 0xffffffffu : (uint32_t)cap64;
 	NH_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-	void* old[] = { q->ov_keys_a, q->ov_keys_b, q->ov_vals_a, q->ov_vals_b };
-	for (void* b : old) if (b) hipFree(b);
-	q->ov_keys_a = q->ov_keys_b = nullptr; q->ov_vals_a = q->ov_vals_b = nullptr;
 	q->ov_capacity = 0;
-	NH_HIP_CHECK(ctx, hipMalloc((void**)&q->ov_keys_a, sizeof(uint64_t) * (size_t)cap));
-	NH_HIP_CHECK(ctx, hipMalloc((void**)&q->ov_keys_b, sizeof(uint64_t) * (size_t)cap));
-	NH_HIP_CHECK(ctx, hipMalloc((void**)&q->ov_vals_a, sizeof(uint32_t) * (size_t)cap));
-	NH_HIP_CHECK(ctx, hipMalloc((void**)&q->ov_vals_b, sizeof(uint32_t) * (size_t)cap));
+	{ int rc = nh_device_buffers(ctx, { { &q->ov_keys_a, sizeof(uint64_t) * (size_t)cap }, { &q->ov_keys_b, sizeof(uint64_t) * (size_t)cap },
+	                                    { &q->ov_vals_a, sizeof(uint32_t) * (size_t)cap }, { &q->ov_vals_b, sizeof(uint32_t) * (size_t)cap } }); if (rc) return rc; }
 	q->ov_capacity = cap;
 	return NH_OK;
 }
@@ -1566,19 +993,13 @@ extern "C" int nh_capsulecast_all(nh_context* ctx, const nh_CapsuleCast* casts, 
 #define NH_Q_CAST_K_GRID 2048u
 template <class Shape>
 static int nh_cast_k(nh_context* ctx, const char* label, const void* casts, uint32_t count, uint32_t k, uint32_t* counts, nh_RayHit* hits, uint32_t flags) {
-	if (!ctx || !ctx->query || !ctx->query->built) return NH_ERR_INVALID;
-	if (flags != 0u || k == 0u || k > NH_CAST_K_MAX || count >= (1u << 30)) return NH_ERR_INVALID;
-	if (count == 0u) return NH_OK;
-	if (!casts || !hits || (((uintptr_t)casts | (uintptr_t)hits) & 15u) || ((uintptr_t)counts & 3u)) return NH_ERR_INVALID;    // (records are moved as 16-byte words)
-	NH_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+	{ const int rc = nh_query_call(ctx, flags, 0u, k, NH_CAST_K_MAX, count, 1u << 30, casts, hits, counts); if (rc || count == 0u) return rc; }
 	nh_QueryState* q = ctx->query;
 	const uint32_t block = nh_q_nearest_block(k);
-	if (ctx->timing) nh_timer_begin(ctx, label);
 	bool on;
 	const nh_QFilter F = nh_query_filter_of(q, &on);
-	hipLaunchKernelGGL((on ? k_q_cast_k<Shape, true> : k_q_cast_k<Shape, false>), dim3(nh_grid_for(count, block, NH_Q_CAST_K_GRID)), dim3(block), block * k * sizeof(nh_QNear),
-	                   ctx->stream, static_cast<const float4*>(casts), count, k, counts, hits, q->nodes, q->rec, q->n, q->nbox, F);
-	if (ctx->timing) nh_timer_end(ctx);
+	NH_LAUNCH_LDS(ctx, label, (on ? k_q_cast_k<Shape, true> : k_q_cast_k<Shape, false>), nh_grid_for(count, block, NH_Q_CAST_K_GRID), block, block * k * sizeof(nh_QNear),
+	              static_cast<const float4*>(casts), count, k, counts, hits, q->nodes, q->rec, q->n, q->nbox, F);
 	return NH_OK;
 }
 

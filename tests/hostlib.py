@@ -17,7 +17,7 @@ _TESTS = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_TESTS)
 _ORACLE = os.path.join(_TESTS, "hostoracle")
 _LIBS = {}
-# 12 words per collider (tests/hostoracle/oracle.h Rec, nh_query.hip's nh_QRec)
+# 12 words per collider (tests/hostoracle/oracle.h Rec, nh_query_tree.h's nh_QRec)
 REC = np.dtype([("p", "<f4", 3), ("body", "<u4"), ("q", "<f4", 4), ("h", "<f4", 3), ("tag", "<u4")])
 
 

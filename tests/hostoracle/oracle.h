@@ -9,7 +9,7 @@
 #include "../../include/nudge_hip.h"
 #include "../../nudge_amd/csrc/nh_query.h"
 
-// 12 words per collider (tests/hostlib.py REC, nh_query.hip's nh_QRec): position, bits(body), rotation, half extents | radius (x3), bits(tag)
+// 12 words per collider (tests/hostlib.py REC, nh_query_tree.h's nh_QRec): position, bits(body), rotation, half extents | radius (x3), bits(tag)
 struct Rec { float p[3]; uint32_t body; float q[4]; float h[3]; uint32_t tag; };
 static_assert(sizeof(Rec) == 48, "Rec is hostlib.REC: 12 words");
 

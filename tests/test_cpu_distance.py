@@ -38,6 +38,7 @@ import hostdistance_util as D               # noqa: E402
 import hostpoint_util as HP                 # noqa: E402
 import hostquery_util as Q                  # noqa: E402
 import hostsweep_util as HS                 # noqa: E402
+from volume_records import distance_bases, distance_lists      # noqa: E402
 from nudge_amd import engine as E           # noqa: E402
 
 NONE = 0xFFFFFFFF
@@ -478,42 +479,16 @@ def test_the_overlap_record_and_what_is_never_reported():
 
 def test_every_kind_of_invalid_query_writes_the_nan_miss():
     rec, nbox = _world([("box", (0, 0, 0), (1, 1, 1), 1), ("sphere", (6, 0, 0), 1.0, 2)])
-    nan, inf = np.float32(np.nan), np.float32(np.inf)
-    bad = []
-
-    def spoil(base, field, value, at=None):
-        qq = base.copy()
-        if at is None:
-            qq[field] = value
-        else:
-            qq[field][0, at] = value
-        bad.append(qq)
-
-    sphere, boxq, cap = D.queries([(3, 0, 0)], radii=0.5), D.queries([(3, 0, 0)], half_extents=(0.5, 0.5, 0.5)), D.queries([(3, 0, 0)], radii=0.5, half_heights=0.5)
-    for base in (sphere, boxq, cap):
+    for base in distance_bases():
         assert D.distance(rec, nbox, base)[0]["body"] in (1, 2)
-        spoil(base, "shape", 7)
-        spoil(base, "center", nan, 1)
-        spoil(base, "center", inf, 0)
-        spoil(base, "size", -1.0, 0)
-        spoil(base, "size", nan, 0)
-        spoil(base, "max_distance", nan)
-        spoil(base, "max_distance", -1.0)
-        spoil(base, "max_distance", -inf)
-    for base in (boxq, cap):
-        spoil(base, "size", -0.5, 1)
-        spoil(base, "size", inf, 1)
-        spoil(base, "rotation", nan, 2)
-    spoil(boxq, "size", nan, 2)
+    bad, ok = distance_lists()
+    assert len(bad) == 3 * 8 + 2 * 3 + 1
     for qq in bad:
         _miss(D.distance(rec, nbox, qq)[0], np.nan)
     # what is not read does not spoil: a sphere's rotation and size[1..2], a capsule's size[2], reserved
-    ok = sphere.copy()
-    ok["rotation"], ok["size"][0, 1:], ok["reserved"] = nan, nan, 0xDEADBEEF
-    assert D.distance(rec, nbox, ok).tobytes() == D.distance(rec, nbox, sphere).tobytes()
-    ok = cap.copy()
-    ok["size"][0, 2] = nan
-    assert D.distance(rec, nbox, ok).tobytes() == D.distance(rec, nbox, cap).tobytes()
+    assert len(ok) == 2
+    for qq, base in ok:
+        assert D.distance(rec, nbox, qq).tobytes() == D.distance(rec, nbox, base).tobytes()
 
 
 def _random_world(seed, n=300):

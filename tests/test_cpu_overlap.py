@@ -13,6 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import hostoverlap_util as O                 # noqa: E402
 from query_util import unit_quats as _quats  # noqa: E402
+from volume_records import overlap_lists, overlap_query      # noqa: E402
 from nudge_amd import engine as E           # noqa: E402
 from nudge_amd import scenes as S           # noqa: E402
 
@@ -173,11 +174,7 @@ def test_nan_anywhere_gives_no_overlap():
 
 
 # ---- the brute force's semantics on hand-built worlds ------------------------------------------------------------------------------------------
-def _query(shape, center, size, rotation=IDENT, ignore=NONE):
-    q = np.zeros(1, dtype=E.OVERLAP_QUERY)
-    q["shape"], q["center"], q["rotation"], q["ignore_body"] = shape, center, rotation, ignore
-    q["size"][0, :len(size)] = size
-    return q
+_query = overlap_query
 
 
 def _everything(ignore=NONE):
@@ -242,14 +239,7 @@ def test_invalid_queries_count_zero():
     scene = S.pile(16, 8, seed=2)
     rec = O.records(scene["body_transforms"], scene)
     nbox = len(scene["box_tags"])
-    nan, inf = float("nan"), float("inf")
-    S_, B_ = E.NH_SHAPE_SPHERE, E.NH_SHAPE_BOX
-    invalid = [_query(2, (0, 0, 0), (1e5,)), _query(NONE, (0, 0, 0), (1e5,)), _query(S_, (0, nan, 0), (1e5,)), _query(S_, (inf, 0, 0), (1e5,)),
-               _query(S_, (0, 0, 0), (inf,)), _query(S_, (0, 0, 0), (nan,)), _query(S_, (0, 0, 0), (-1.0,)),
-               _query(B_, (0, 0, 0), (1e5, 1e5, -1.0)), _query(B_, (0, 0, 0), (1e5, nan, 1e5)), _query(B_, (0, 0, 0), (1e5, 1e5, 1e5), rotation=(0, nan, 0, 1)),
-               _query(B_, (0, 0, 0), (1e5, 1e5, 1e5), rotation=(0, 0, 0, inf))]
-    valid = [_query(S_, (0, 0, 0), (1e5, nan, -1.0), rotation=(nan, nan, nan, nan)),        # a sphere ignores size[1..2] and the rotation
-             _query(S_, (0, 0, 0), (-0.0,)), _query(B_, (0, 0, 0), (1e5, 1e5, 1e5))]
+    invalid, valid = overlap_lists()
     off, hits, total = O.overlap(rec, nbox, np.concatenate(invalid))
     assert total == 0 and not off.any()
     off, hits, total = O.overlap(rec, nbox, np.concatenate(valid))

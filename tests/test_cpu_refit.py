@@ -1,5 +1,5 @@
 """nh_query_refit on the host (no GPU): the symbol through the header, the Python list and the built library; and a numpy model of the cut the box
-pass makes (nudge_amd/csrc/nh_query.hip: k_q_boxes_runs / k_q_boxes_top) -- the Karras tree of seeded key sets built on the host, every internal node
+pass makes (nudge_amd/csrc/nh_query_build.hip: k_q_boxes_runs / k_q_boxes_top) -- the Karras tree of seeded key sets built on the host, every internal node
 classified by nh_q_run_crossing itself (nudge_amd/csrc/nh_query.h, built for the host by tests/hostrefit_util.py), and the two phases replayed with
 the kernels' slots, sides and arrival counters against a plain refit of the whole tree."""
 import os
