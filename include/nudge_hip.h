@@ -79,7 +79,7 @@
  *      exported the views: nh_set_option(ctx, "sync_exports_views", 1) restores that contract at its old price; INTEGRATION.md.)  Any entry point outside the sample's
  *      call order between nh_collide and nh_apply_impulses turns a still step into a full one first, so everything it observes is what a full step
  *      produces.  nh_Counts.still_steps / still_replays count them.
- *      The scene queries (nh_query_build, nh_query_refit, nh_raycast, nh_spherecast, nh_raycast_all, nh_spherecast_all, nh_boxcast_all, nh_capsulecast_all, nh_raycast_k, nh_spherecast_k, nh_boxcast_k, nh_capsulecast_k, nh_boxcast, nh_capsulecast, nh_overlap, nh_penetration, nh_closest, nh_closest_k, nh_distance, nh_query_set_layers, nh_query_filter, nh_query_layer_info) are not entry points of the step in this sense: they neither export nor settle nor turn a still step into a
+ *      The scene queries (nh_query_build, nh_query_refit, nh_raycast, nh_spherecast, nh_raycast_all, nh_spherecast_all, nh_boxcast_all, nh_capsulecast_all, nh_raycast_k, nh_spherecast_k, nh_boxcast_k, nh_capsulecast_k, nh_boxcast, nh_capsulecast, nh_overlap, nh_penetration, nh_closest, nh_closest_k, nh_distance, nh_move, nh_query_set_layers, nh_query_filter, nh_query_layer_info) are not entry points of the step in this sense: they neither export nor settle nor turn a still step into a
  *      full one, and they do not count -- see "scene queries" below.
  *
  * Threading: one context = one HIP stream = one world at a time; no global mutable state.
@@ -428,8 +428,8 @@ int nh_query_stats(nh_context* ctx, nh_QueryStats* out);
                           NH_ERR_INVALID.
    An unknown mode, or a call before any nh_query_build, returns NH_ERR_INVALID; a refused call changes nothing -- the next query still uses the previous
    filter.  nh_query_filter is host state only: nothing is launched, nothing waits.  (The calls' own `flags` argument has no bit to spare for this.)
-   THE CONTRACT, for all nineteen query calls (nh_raycast, nh_spherecast, nh_boxcast, nh_capsulecast, their _all and _k forms, nh_overlap, nh_penetration,
-   nh_closest, nh_closest_k, nh_distance):
+   THE CONTRACT, for all twenty query calls (nh_raycast, nh_spherecast, nh_boxcast, nh_capsulecast, their _all and _k forms, nh_overlap, nh_penetration,
+   nh_closest, nh_closest_k, nh_distance, nh_move):
      - MASKED WORLD: with the filter on, a query with mask m writes byte for byte what the same call with the filter OFF writes on a world that is the same
        except for one thing: every collider with (layers & m) == 0 has a NaN pose -- "a collider of a body that does not exist", which every call above
        documents as never hit, never listed, never reported.  Collider indices, bodies and tags in the records are those of the real world.  For
@@ -852,6 +852,60 @@ int nh_penetration(nh_context* ctx, const nh_OverlapQuery* queries, uint32_t cou
 typedef struct nh_DistanceQuery { float center[3]; uint32_t shape; float rotation[4]; float size[3]; uint32_t ignore_body;   /* = nh_OverlapQuery, 48 B */
                                   float max_distance; uint32_t reserved[3]; } nh_DistanceQuery;                              /* 64 B */
 int nh_distance(nh_context* ctx, const nh_DistanceQuery* queries, uint32_t count, nh_PointHit* hits, uint32_t flags /* 0 */);
+
+/* nh_move: collide-and-slide for `count` swept capsules against the world of the LAST nh_query_build or nh_query_refit -- the loop a character controller
+   runs around nh_capsulecast (cast, advance to the contact, deflect what is left of the displacement along the surface, cast again), on the device, in ONE
+   launch, so that no slide costs a launch, a wait and an upload.  nh_Move is nh_CapsuleCast field for field with `skin` where max_t is and `max_slides`
+   where reserved[0] is; the capsule (rotation, radius, half_height) is nh_capsulecast's, and half_height = 0 is a ball.  `reserved` is not read.
+   ONE MOVE, all in float32; the arithmetic is nudge_amd/csrc/nh_query.h, "move" (nh_q_move_begin / nh_q_move_go / nh_q_move_advance), which is the
+   definition and fixes the order of every operation (each product rounded before its sum, no fused multiply-add; dot products (x*x + y*y) + z*z).
+   State: p = origin, v = displacement, d0 = displacement, no n_prev, slides = 0, flags = 0, last = the miss record of a capsule cast with max_t = 1.  Repeat:
+     1. v.v == 0: stop.
+     2. last = the closest-hit answer nh_capsulecast with flags 0 writes for { p, 1.0f, v, ignore_body, rotation, radius, half_height }: the same decode,
+        reach rule and tie rule, under the context's layer filter (the per-query mask index is the move's index).
+     3. a miss: p = p + v (one add per component), v = 0, stop.
+     4. a hit with t == 0 (START OVERLAP, or touching): flags |= NH_MOVE_START_OVERLAP, stop; p and v keep their bits.  The normal of such a hit is
+        -v / |v| and says nothing about the surface: getting out is nh_penetration's business.
+     5. a hit with t > 0: flags |= NH_MOVE_HIT, slides += 1, p = p + t*v, then p = p + skin*n (a multiply and an add per component each), rem = (1 - t)*v.
+     6. deflect: s = rem.n; v' = rem - s*n if s < 0, else rem.  Where a hit was taken before and v'.n_prev < 0 (a CREASE): c = n_prev x n; c.c < 2^-24:
+        v' = 0; else v' = c * ((rem.c) / (c.c)); then v' = 0 if v'.n_prev < 0 or v'.n < 0.  Then v' = 0 unless v'.d0 > 0 (a move never turns against what
+        was asked for), and v' = 0 unless v'.v' > 2^-40 * (d0.d0).  If one of these rules wrote v' = 0 and rem was not 0: flags |= NH_MOVE_WEDGED -- a
+        head-on hit sets it, through the d0 rule.  v = v', n_prev = n.
+        (The crease's last test compares rounded products of c with the normals it was built from: off the coordinate axes it fires on rounding dust in
+        about six creases in ten, which then end WEDGED where an exact evaluation would slide along c.  DESIGN 10.15.)
+     7. slides > max_slides and v.v > 0: flags |= NH_MOVE_SLIDES_OUT, stop.  So a move makes at most max_slides + 1 casts; max_slides = 0 is one cast.
+   Output: position = p, remaining = v, slides, flags, last_hit = last.  flags == 0 with remaining == 0: the move went through freely.
+   SKIN is the gap the capsule keeps: after a hit it is pushed skin along the NORMAL (not back along the path, which at a grazing angle would take
+   skin / sin of the angle away from the travel, or leave less than skin of clearance), so the next cast starts free.  skin = 0 is valid and leaves the capsule touching: the
+   next cast is then a START OVERLAP, so it is of use with max_slides = 0 only.  Scale skin to the scene: it must exceed the rounding of p (2^-23 of its
+   largest coordinate) by a margin for the slide to start free; 0.01 for bodies of size 1 near the origin.
+   INVALID RECORDS -- a non-finite origin or displacement; a non-finite or negative radius, half height or skin; half_height > 0 with a non-finite
+   rotation; max_slides > NH_MOVE_MAX_SLIDES -- write flags = NH_MOVE_INVALID, position = the bits of origin, remaining = the bits of displacement,
+   slides = 0 and last_hit = the miss record with t = NaN.  displacement = 0 is a valid no-op that makes no cast.  (Finite inputs whose sums overflow make a
+   cast with a non-finite origin: it is a miss with t = NaN, as in nh_capsulecast, and the move ends there.)
+   IDENTITIES (contracts):
+     - with max_slides = 0, last_hit holds byte for byte what nh_capsulecast with flags 0 writes for { origin, 1.0f, displacement, ignore_body, rotation,
+       radius, half_height };
+     - half_height = 0 does not read `rotation`: its casts are nh_spherecast's;
+     - REPLAY: running the loop on the host, one nh_capsulecast call per round and nh_q_move_advance between them, gives nh_move's 64 bytes per record;
+     - after nh_query_refit the bytes are those after an nh_query_build of the same arrays; nh_query_filter is honoured in all three modes.
+   Returns NH_ERR_INVALID before any nh_query_build, for flags != 0, for count >= 2^30, and for count > 0 with `moves` or `results` null or not 16-byte
+   aligned; count = 0 is a no-op that returns NH_OK and launches nothing.  Every byte of `count` results is written and nothing behind them.  Never
+   allocates, never waits: ONE launch on the context's stream (timing label q_move).  An OBSERVER like nh_capsulecast (note 9): no view export, no
+   settling of deferred gravity, no still step turned into a full one, no change to nh_Counts.
+   NOT BUILT: box movers; rotation during the move; depenetration of a move that starts in overlap (nh_penetration gives the push); gravity, step-up,
+   ground snapping and slope limits; moving platforms (the velocity of what is hit); pushing dynamic bodies (queries are observers); the list of everything
+   touched (last_hit is the last cast's record only).
+   Cost: one lane per move, up to max_slides + 1 walks of nh_capsulecast's; a lane that has finished waits for the slowest of its wave.  Measured (one
+   MI355X, the landed config-2 world of 1,004,524 colliders, 1,048,576 moves of r = hh = 0.5 from just above resting bodies by 0.75 - 3 units, max_slides 4;
+   tools/move_rates.py -> profiles/move_rates.log): 1.90 ms beside 1.14 ms for nh_capsulecast on the first casts alone; the moves made 1.61 casts
+   on average, so the call takes 1.03 of (casts per move x the capsule cast's time) on that workload. */
+#define NH_MOVE_MAX_SLIDES 8u
+enum { NH_MOVE_HIT = 1u, NH_MOVE_START_OVERLAP = 2u, NH_MOVE_SLIDES_OUT = 4u, NH_MOVE_WEDGED = 8u, NH_MOVE_INVALID = 0x80000000u };
+typedef struct nh_Move { float origin[3]; float skin; float displacement[3]; uint32_t ignore_body;
+                         float rotation[4]; float radius; float half_height; uint32_t max_slides; uint32_t reserved; } nh_Move;      /* 64 B */
+typedef struct nh_MoveResult { float position[3]; uint32_t flags; float remaining[3]; uint32_t slides; nh_RayHit last_hit; } nh_MoveResult;   /* 64 B */
+int nh_move(nh_context* ctx, const nh_Move* moves, uint32_t count, nh_MoveResult* results, uint32_t flags /* 0 */);
 
 /* ---- multi-GPU: one x-slab of a world per context ------------------------------------------------------------------------------------
    The world is cut into slabs along x, one rank (process, GPU, nh_context) per slab [lo, hi).  A rank's arrays hold

@@ -1214,4 +1214,90 @@ NH_HD float nh_q_all_pad(nh_f3 lo, nh_f3 hi, nh_f3 o) {
 // The sort key of a hit's t: the bits of t + 0.0f.  t >= 0, so -0 becomes +0 and the bits order as the floats do.
 NH_HD uint32_t nh_q_tbits(float t) { return nh_asuint(t + 0.0f); }
 
+// ---- move (nh_move): collide-and-slide of a swept capsule, the state between two capsule casts -----------------------------------------------------
+// These functions ARE the definition of nh_move (include/nudge_hip.h): k_q_move and the host's brute force (tests/hostoracle/hostmove.cpp) both run
+//     s = nh_q_move_begin(origin, displacement);
+//     while (nh_q_move_go(s)) { hit = the closest-hit capsule cast { s.p, 1.0f, s.v, ignore_body, rotation, radius, half_height };
+//                               if (!nh_q_move_advance(s, hit found, hit.t, hit.normal, skin, max_slides)) break; }
+// and write s.p, s.flags, s.v, s.slides and the last cast's record.  Every product is rounded before the sum it goes into (no fused multiply-add), and every
+// dot and cross product is nh_dot / nh_cross of nh_math.h: (x*x + y*y) + z*z, left to right.
+// The flag bits are nh_MoveResult.flags' (nh_query.hip asserts that they are the header's NH_MOVE_*).
+#define NH_Q_MOVE_HIT 1u
+#define NH_Q_MOVE_START_OVERLAP 2u
+#define NH_Q_MOVE_SLIDES_OUT 4u
+#define NH_Q_MOVE_WEDGED 8u
+#define NH_Q_MOVE_MAX_SLIDES 8u
+#define NH_Q_MOVE_CREASE_EPS 5.9604644775390625e-08f          // 2^-24: |n_prev x n|^2 below it, the two normals are one plane and there is no crease line
+#define NH_Q_MOVE_TINY 9.094947017729282e-13f                  // 2^-40: what is left counts as nothing below this share of |displacement|^2
+
+// p: where the capsule's centre is; v: what is left of the displacement; d0: the displacement asked for; np: the normal of the last hit taken, read only
+// where slides > 0 (slides counts exactly the hits taken, so "there is an n_prev" is slides > 0 before the count goes up).
+struct nh_QMove { nh_f3 p, v, d0, np; uint32_t slides, flags; };
+
+NH_HD bool nh_q_move_finite(float x) { return (nh_asuint(x) & 0x7f800000u) != 0x7f800000u; }
+
+// The record's validity (header, "Invalid records"); `rotation` is read only where hh > 0
+NH_HD bool nh_q_move_valid(nh_f3 o, nh_f3 d, nh_quat q, float r, float hh, float skin, uint32_t max_slides) {
+	bool ok = nh_q_move_finite(o.x) && nh_q_move_finite(o.y) && nh_q_move_finite(o.z) && nh_q_move_finite(d.x) && nh_q_move_finite(d.y) && nh_q_move_finite(d.z);
+	ok = ok && nh_q_move_finite(r) && nh_q_move_finite(hh) && nh_q_move_finite(skin) && !(r < 0.0f) && !(hh < 0.0f) && !(skin < 0.0f);
+	ok = ok && (hh == 0.0f || (nh_q_move_finite(q.x) && nh_q_move_finite(q.y) && nh_q_move_finite(q.z) && nh_q_move_finite(q.s)));
+	return ok && max_slides <= NH_Q_MOVE_MAX_SLIDES;
+}
+
+NH_HD nh_QMove nh_q_move_begin(nh_f3 origin, nh_f3 displacement) {
+	nh_QMove s;
+	s.p = origin; s.v = displacement; s.d0 = displacement; s.np = nh_make3(0.0f, 0.0f, 0.0f);
+	s.slides = 0u; s.flags = 0u;
+	return s;
+}
+
+// Rule 1: is there anything left to cast along?  (A v whose square underflows to 0 is nothing; a NaN v -- only an overflow of finite inputs makes one -- goes
+// on to a cast that is invalid, hence a miss, hence the end.)
+NH_HD bool nh_q_move_go(const nh_QMove& s) { return nh_dot(s.v, s.v) != 0.0f; }
+
+// Rules 3 - 7 behind one cast from s.p along s.v with max_t = 1: `hit` says whether it found a collider, (t, n) are its record's t and normal.  Returns
+// whether the move goes on (to rule 1).  Order of operations, per component k where a vector is written:
+//   miss        p_k = p_k + v_k; v = +0
+//   t == 0      nothing but the flag: p and v keep their bits
+//   t > 0       p_k = p_k + (t * v_k), then p_k = p_k + (skin * n_k); u = 1 - t; rem_k = u * v_k
+//   deflect     s = rem.n; w = s < 0 ? rem - s*n (w_k = rem_k - (s * n_k)) : rem
+//   crease      only where a hit was taken before and w.np < 0: c = np x n, cc = c.c; cc < 2^-24: w = 0; else g = (rem.c) / cc, w_k = c_k * g;
+//               then w = 0 if w.np < 0 or w.n < 0
+//   never back  w = 0 unless w.d0 > 0          ("unless": a NaN is zeroed too)
+//   tiny        w = 0 unless w.w > 2^-40 * (d0.d0)
+//   WEDGED      iff one of the four rules above wrote w = 0 and rem has a component that is not (+-)0.  A head-on hit needs no special case: w = rem - s*n is
+//               then 0 or rounding dust, w.d0 is not > 0, "never back" fires and the flag is set.  rem = 0 (t = 1: touching exactly at the end) sets none.
+//   v = w, np = n; slides > max_slides with v.v > 0: SLIDES_OUT and stop.  With v.v == 0 the move goes on to rule 1, which ends it.
+NH_HD bool nh_q_move_advance(nh_QMove& s, bool hit, float t, nh_f3 n, float skin, uint32_t max_slides) {
+	if (!hit) {
+		s.p = s.p + s.v;
+		s.v = nh_make3(0.0f, 0.0f, 0.0f);
+		return false;
+	}
+	if (t == 0.0f) { s.flags |= NH_Q_MOVE_START_OVERLAP; return false; }
+	const bool prev = s.slides != 0u;
+	s.flags |= NH_Q_MOVE_HIT;
+	s.slides += 1u;
+	s.p = s.p + t * s.v;
+	s.p = s.p + skin * n;
+	const nh_f3 rem = (1.0f - t) * s.v;
+	const float sn = nh_dot(rem, n);
+	nh_f3 w = sn < 0.0f ? rem - sn * n : rem;
+	const nh_f3 zero = nh_make3(0.0f, 0.0f, 0.0f);
+	bool zeroed = false;
+	if (prev && nh_dot(w, s.np) < 0.0f) {
+		const nh_f3 c = nh_cross(s.np, n);
+		const float cc = nh_dot(c, c);
+		if (cc < NH_Q_MOVE_CREASE_EPS) { w = zero; zeroed = true; }
+		else w = c * (nh_dot(rem, c) / cc);
+		if (nh_dot(w, s.np) < 0.0f || nh_dot(w, n) < 0.0f) { w = zero; zeroed = true; }
+	}
+	if (!(nh_dot(w, s.d0) > 0.0f)) { w = zero; zeroed = true; }
+	if (!(nh_dot(w, w) > NH_Q_MOVE_TINY * nh_dot(s.d0, s.d0))) { w = zero; zeroed = true; }
+	if (zeroed && (rem.x != 0.0f || rem.y != 0.0f || rem.z != 0.0f)) s.flags |= NH_Q_MOVE_WEDGED;
+	s.v = w; s.np = n;
+	if (s.slides > max_slides && nh_dot(w, w) > 0.0f) { s.flags |= NH_Q_MOVE_SLIDES_OUT; return false; }
+	return true;
+}
+
 #endif

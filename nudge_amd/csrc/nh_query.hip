@@ -2,7 +2,8 @@
 // nh_query.hip -- scene queries against the tree of the last nh_query_build or nh_query_refit (nh_query_build.hip, nh_query_tree.h): nh_raycast (batched
 // closest-hit / any-hit ray casts), nh_spherecast, nh_boxcast and nh_capsulecast (the same for swept balls, oriented boxes and capsules), their all-hits
 // (_all) and first-k (_k) forms, nh_closest / nh_closest_k / nh_distance (the nearest colliders to a point or a shape) and nh_overlap / nh_penetration (the
-// colliders touching each of a batch of spheres, boxes or capsules, as variable-length segments).  include/nudge_hip.h, "scene queries".
+// colliders touching each of a batch of spheres, boxes or capsules, as variable-length segments) and nh_move (collide-and-slide: the capsule cast in a loop).
+// include/nudge_hip.h, "scene queries".
 // Layer masks (include/nudge_hip.h, "layer masks"): every query call walks under the mask(s) nh_query_filter set, in the FILTER = true instantiation of its kernel.
 // Traversal is stackless: a node that is missed or a leaf that is done continues at its ESCAPE link (the next node in pre-order after its subtree),
 // a hit internal node at its left child.  A private stack array would go to scratch memory.
@@ -213,9 +214,10 @@ struct nh_QCapsule : nh_QCastHead {
 	nh_quat qa;
 	float r, hh;
 	nh_f3 w;
-	__device__ __forceinline__ void read(const float4* __restrict__ cp) {
-		head(cp[0], cp[1]);
-		const float4 c2 = cp[2], c3 = cp[3];
+	__device__ __forceinline__ void read(const float4* __restrict__ cp) { set(cp[0], cp[1], cp[2], cp[3]); }
+	// the decode of the record's four 16-byte words, for k_q_move as well, which builds each of its casts in registers
+	__device__ __forceinline__ void set(float4 c0, float4 c1, float4 c2, float4 c3) {
+		head(c0, c1);
 		qa = { c2.x, c2.y, c2.z, c2.w }; r = c3.x; hh = c3.y;
 		ok = ok && nh_q_finite(r) && nh_q_finite(hh) && !(r < 0.0f) && !(hh < 0.0f) && (hh == 0.0f || nh_q_finite(qa));
 		const nh_f3 e = nh_q_capsule_extent(nh_q_capsule_axis(qa, hh), r);
@@ -269,24 +271,36 @@ __device__ __forceinline__ void nh_q_write_point(nh_PointHit* __restrict__ hit, 
 	}
 }
 
-// One lane per cast: the walk prunes at the best t so far, nh_q_better (nh_query.h) keeps the closest hit and the tie rule, any_hit stops at the first.
+// One decoded cast k under the mask m: the walk prunes at the best t so far, nh_q_better (nh_query.h) keeps the closest hit and the tie rule, any_hit stops
+// at the first.  Leaves (bt, bc, bn) as nh_q_write_hit takes them: the hit, or bc = NH_Q_NONE with bt = the cast's max_t.  The closest-hit kernels and
+// every round of k_q_move answer through this one body.
+template <bool FILTER, class Shape>
+__device__ __forceinline__ void nh_q_cast_one(const Shape& k, const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox,
+                                              uint32_t any_hit, const nh_QFilter& F, uint32_t m, float& bt, uint32_t& bc, nh_f3& bn) {
+	bt = k.max_t;
+	bc = NH_Q_NONE;
+	bn = nh_make3(0.0f, 0.0f, 0.0f);
+	nh_q_walk<FILTER>(nodes, rec, k.ok && n ? 0u : NH_Q_NONE, k.ignore, F, m,
+		[&](nh_f3 lo, nh_f3 hi, float& t0) { return k.node(lo, hi, t0) && t0 <= bt; },
+		[&](uint32_t c, const nh_QRec& q, float t0) {
+			const nh_QHit h = k.leaf(nh_q_unpack(q), c < nbox, t0);
+			if (!(h.hit && nh_q_better(h.t, c, k.max_t, bt, bc))) return false;
+			bt = h.t; bc = c; bn = h.n;
+			return any_hit != 0u;
+		});
+}
+
+// One lane per cast.
 template <class Shape, bool FILTER>
 __device__ __forceinline__ void nh_q_cast(const float4* __restrict__ casts, uint32_t count, nh_RayHit* __restrict__ hits, const nh_QNode* __restrict__ nodes,
                                           const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox, uint32_t any_hit, const nh_QFilter& F) {
 	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
 		Shape k;
 		k.read(casts + (size_t)i * Shape::WORDS);
-		float bt = k.max_t;
-		uint32_t bc = NH_Q_NONE;
-		nh_f3 bn = nh_make3(0.0f, 0.0f, 0.0f);
-		nh_q_walk<FILTER>(nodes, rec, k.ok && n ? 0u : NH_Q_NONE, k.ignore, F, FILTER ? F.of(i) : 0u,
-			[&](nh_f3 lo, nh_f3 hi, float& t0) { return k.node(lo, hi, t0) && t0 <= bt; },
-			[&](uint32_t c, const nh_QRec& q, float t0) {
-				const nh_QHit h = k.leaf(nh_q_unpack(q), c < nbox, t0);
-				if (!(h.hit && nh_q_better(h.t, c, k.max_t, bt, bc))) return false;
-				bt = h.t; bc = c; bn = h.n;
-				return any_hit != 0u;
-			});
+		float bt;
+		uint32_t bc;
+		nh_f3 bn;
+		nh_q_cast_one<FILTER>(k, nodes, rec, n, nbox, any_hit, F, FILTER ? F.of(i) : 0u, bt, bc, bn);
 		nh_q_write_hit(hits + i, rec, nbox, k.ok, bc, bt, bn);
 	}
 }
@@ -315,6 +329,47 @@ template <bool FILTER>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k_q_capsulecast(const nh_CapsuleCast* __restrict__ casts, uint32_t count, nh_RayHit* __restrict__ hits,
                                                    const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox, uint32_t any_hit, nh_QFilter F) {
 	nh_q_cast<nh_QCapsule, FILTER>(reinterpret_cast<const float4*>(casts), count, hits, nodes, rec, n, nbox, any_hit, F);
+}
+
+// ---- move -------------------------------------------------------------------------------------------------------------------------------------
+// nh_move: one lane per move.  The state machine is nh_query.h's ("move": nh_q_move_begin / _go / _advance, which the host's brute force runs as well);
+// each round's cast is the record { p, 1.0f, v, ignore_body, rotation, radius, half_height } decoded by nh_QCapsule::set and answered by nh_q_cast_one, the
+// body of k_q_capsulecast -- so a round's (t, collider, normal) are nh_capsulecast's for that record, under the same mask (the move's index).  The loop
+// bound is a constant and every round is a walk that terminates, so the kernel terminates on any input.  A lane whose move has ended waits for the slowest
+// of its wave.  The record leaves as four 16-byte stores; `ok` of the last cast decides its miss t as it does in nh_capsulecast (a position
+// that overflowed makes an invalid cast: a miss with t = NaN).
+static_assert(NH_Q_MOVE_HIT == NH_MOVE_HIT && NH_Q_MOVE_START_OVERLAP == NH_MOVE_START_OVERLAP && NH_Q_MOVE_SLIDES_OUT == NH_MOVE_SLIDES_OUT &&
+              NH_Q_MOVE_WEDGED == NH_MOVE_WEDGED && NH_Q_MOVE_MAX_SLIDES == NH_MOVE_MAX_SLIDES, "nh_query.h's move constants are the header's");
+static_assert(sizeof(nh_Move) == 64 && sizeof(nh_MoveResult) == 64, "nh_Move and nh_MoveResult are four 16-byte words each");
+
+template <bool FILTER>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k_q_move(const nh_Move* __restrict__ moves, uint32_t count, nh_MoveResult* __restrict__ results,
+                                                   const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox, nh_QFilter F) {
+	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
+		const float4* mp = reinterpret_cast<const float4*>(moves + i);
+		const float4 m0 = mp[0], m1 = mp[1], m2 = mp[2], m3 = mp[3];
+		const float skin = m0.w;
+		const uint32_t max_slides = __float_as_uint(m3.z);
+		const bool valid = nh_q_move_valid(nh_make3(m0.x, m0.y, m0.z), nh_make3(m1.x, m1.y, m1.z), nh_quat{ m2.x, m2.y, m2.z, m2.w }, m3.x, m3.y, skin, max_slides);
+		nh_QMove s = nh_q_move_begin(nh_make3(m0.x, m0.y, m0.z), nh_make3(m1.x, m1.y, m1.z));
+		const uint32_t fm = FILTER ? F.of(i) : 0u;
+		float bt = 1.0f;
+		uint32_t bc = NH_Q_NONE;
+		nh_f3 bn = nh_make3(0.0f, 0.0f, 0.0f);
+		bool ok = valid;
+		for (uint32_t round = 0u; round <= NH_MOVE_MAX_SLIDES; ++round) {
+			if (!valid || !nh_q_move_go(s)) break;
+			nh_QCapsule k;
+			k.set(make_float4(s.p.x, s.p.y, s.p.z, 1.0f), make_float4(s.v.x, s.v.y, s.v.z, m1.w), m2, m3);
+			nh_q_cast_one<FILTER>(k, nodes, rec, n, nbox, 0u, F, fm, bt, bc, bn);
+			ok = k.ok;
+			if (!nh_q_move_advance(s, bc != NH_Q_NONE, bt, bn, skin, max_slides)) break;
+		}
+		float4* out = reinterpret_cast<float4*>(results + i);
+		out[0] = make_float4(s.p.x, s.p.y, s.p.z, __uint_as_float(valid ? s.flags : (uint32_t)NH_MOVE_INVALID));
+		out[1] = make_float4(s.v.x, s.v.y, s.v.z, __uint_as_float(s.slides));
+		nh_q_write_hit(&results[i].last_hit, rec, nbox, ok, bc, bt, bn);
+	}
 }
 
 // ---- closest point ----------------------------------------------------------------------------------------------------------------------------
@@ -795,6 +850,16 @@ extern "C" int nh_capsulecast(nh_context* ctx, const nh_CapsuleCast* casts, uint
 
 extern "C" int nh_boxcast(nh_context* ctx, const nh_BoxCast* casts, uint32_t count, nh_RayHit* hits, uint32_t flags) {
 	return nh_cast(ctx, "q_boxcast", k_q_boxcast<false>, k_q_boxcast<true>, casts, count, hits, flags);
+}
+
+// One launch, nh_distance's checks in nh_distance's order; no allocation, no wait.
+extern "C" int nh_move(nh_context* ctx, const nh_Move* moves, uint32_t count, nh_MoveResult* results, uint32_t flags) {
+	{ const int rc = nh_query_call(ctx, flags, 0u, 0u, 0u, count, 1u << 30, moves, results, nullptr); if (rc || count == 0u) return rc; }
+	nh_QueryState* q = ctx->query;
+	bool on;
+	const nh_QFilter F = nh_query_filter_of(q, &on);
+	NH_LAUNCH(ctx, "q_move", on ? k_q_move<true> : k_q_move<false>, nh_grid_for(count, 256, 1u << 20), 256, moves, count, results, q->nodes, q->rec, q->n, q->nbox, F);
+	return NH_OK;
 }
 
 extern "C" int nh_closest(nh_context* ctx, const nh_PointQuery* queries, uint32_t count, nh_PointHit* hits, uint32_t flags) {

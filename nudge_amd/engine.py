@@ -43,7 +43,7 @@ EXPORTS = [
     "nh_partition_top_speed", "nh_partition_set_peer_speeds", "nh_partition_refresh_is_quiet", "nh_partition_mark_ghosts", "nh_partition_pack_deltas", "nh_partition_unpack_deltas",
     "nh_partition_pack_momentum", "nh_partition_unpack_momentum", "nh_partition_exchange_iteration", "nh_partition_unpack_ghosts", "nh_partition_pack_step", "nh_partition_unpack_step", "nh_partition_choose_cut", "nh_partition_set_cut",
     "nh_partition_set_transport", "nh_partition_exchange_step", "nh_partition_step", "nh_partition_transport_check", "nh_partition_transport_result", "nh_set_first_ghost_body",
-    "nh_query_build", "nh_query_refit", "nh_query_stats", "nh_raycast", "nh_overlap", "nh_penetration", "nh_spherecast", "nh_raycast_all", "nh_spherecast_all", "nh_boxcast_all", "nh_capsulecast_all", "nh_boxcast", "nh_capsulecast", "nh_closest", "nh_closest_k", "nh_distance",
+    "nh_query_build", "nh_query_refit", "nh_query_stats", "nh_raycast", "nh_overlap", "nh_penetration", "nh_spherecast", "nh_raycast_all", "nh_spherecast_all", "nh_boxcast_all", "nh_capsulecast_all", "nh_boxcast", "nh_capsulecast", "nh_closest", "nh_closest_k", "nh_distance", "nh_move",
     "nh_raycast_k", "nh_spherecast_k", "nh_boxcast_k", "nh_capsulecast_k",
     "nh_query_set_layers", "nh_query_filter", "nh_query_layer_info",
 ]
@@ -170,6 +170,12 @@ POINT_HIT = np.dtype([("distance", "<f4"), ("normal", "<f4", 3), ("point", "<f4"
                       ("reserved", "<u4")])
 DISTANCE_QUERY = np.dtype([("center", "<f4", 3), ("shape", "<u4"), ("rotation", "<f4", 4), ("size", "<f4", 3), ("ignore_body", "<u4"), ("max_distance", "<f4"),
                            ("reserved", "<u4", 3)])
+# nh_move (include/nudge_hip.h): nh_CapsuleCast with `skin` where max_t is and `max_slides` where reserved[0] is; nh_MoveResult.flags
+MOVE = np.dtype([("origin", "<f4", 3), ("skin", "<f4"), ("displacement", "<f4", 3), ("ignore_body", "<u4"), ("rotation", "<f4", 4), ("radius", "<f4"),
+                 ("half_height", "<f4"), ("max_slides", "<u4"), ("reserved", "<u4")])
+MOVE_RESULT = np.dtype([("position", "<f4", 3), ("flags", "<u4"), ("remaining", "<f4", 3), ("slides", "<u4"), ("last_hit", RAY_HIT)])
+NH_MOVE_MAX_SLIDES = 8
+NH_MOVE_HIT, NH_MOVE_START_OVERLAP, NH_MOVE_SLIDES_OUT, NH_MOVE_WEDGED, NH_MOVE_INVALID = 1, 2, 4, 8, 0x80000000
 NH_OVERLAP_OVERFLOW = 0xFFFFFFFF          # offsets[count] when the total is 2^32 - 1 or more
 
 
@@ -291,6 +297,9 @@ def lib():
         # (an older build of the library, loaded through NUDGE_HIP_LIBRARY for an A/B, has no nh_distance: World.distance then raises AttributeError)
         if hasattr(L, "nh_distance"):
             L.nh_distance.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
+        # (likewise nh_move: World.move then raises AttributeError)
+        if hasattr(L, "nh_move"):
+            L.nh_move.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
         L.nh_overlap.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
         L.nh_penetration.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
         # (an older build of the library, loaded through NUDGE_HIP_LIBRARY for an A/B, has no all-hits casts: World.raycast_all then raises AttributeError)
@@ -1065,6 +1074,36 @@ class World:
         f = raw.view(torch.float32).reshape(n, 12)
         u = raw.view(torch.int32).reshape(n, 12).to(torch.int64) & 0xFFFFFFFF
         out = dict(distance=f[:, 0], normal=f[:, 1:4], point=f[:, 4:7], body=u[:, 7], collider=u[:, 8], shape=u[:, 9], tag=u[:, 10], raw=raw)
+        if synchronize:
+            torch.cuda.current_stream(self.dev).synchronize()
+        return out
+
+    def move_records(self, records, results=None):
+        """nh_move on records already laid out as nh_Move: `records` a contiguous device tensor of count x 64 bytes (any dtype).  Returns the
+        count x 64-byte uint8 device tensor of nh_MoveResult records (`results`, or a new one)."""
+        torch = self.torch
+        n = records.numel() * records.element_size() // 64
+        if results is None:
+            results = torch.empty((n, 64), dtype=torch.uint8, device=self.dev)
+        _check(self.L, self.L.nh_move(self.ctx, C.c_void_p(records.data_ptr() if n else 0), n, C.c_void_p(results.data_ptr() if n else 0), 0), "nh_move")
+        return results
+
+    def move(self, origins, displacements, radius, half_height=0.0, rotations=None, skin=0.01, max_slides=4, ignore_body=None, synchronize=False):
+        """Collide-and-slide (nh_move) against the last query_build(): each of n capsules of `radius` and `half_height` (numbers or n values; half
+        height 0 is a ball) and `rotations` ((n, 4) or (4,) quaternions (x, y, z, s); None = identity, upright) is moved from `origins` by
+        `displacements` ((n, 3) each), sliding along what it hits, at most `max_slides` (0 .. NH_MOVE_MAX_SLIDES; a number or n values) times, and
+        keeping `skin` (a number or n values, in world units: scale it to the scene) clear of it.  `ignore_body`: None, a body index, or n of them.
+        Returns a dict of device tensors: position (n, 3), remaining (n, 3; the displacement not used), flags (n, int64; NH_MOVE_*), slides (n,
+        int64), `last_hit` (capsulecast()'s dict for the last cast each move made) and `raw`, the nh_MoveResult records.  Nothing waits for the
+        device unless `synchronize`."""
+        torch = self.torch
+        rec, n = self._capsule_casts("move", origins, displacements, radius, half_height, rotations, skin, ignore_body)
+        rec.view(torch.int32)[:, 14] = torch.as_tensor(max_slides, dtype=torch.int64, device=self.dev).to(torch.int32)
+        raw = self.move_records(rec)
+        f = raw.view(torch.float32).reshape(n, 16)
+        u = raw.view(torch.int32).reshape(n, 16).to(torch.int64) & 0xFFFFFFFF
+        out = dict(position=f[:, 0:3], remaining=f[:, 4:7], flags=u[:, 3], slides=u[:, 7], last_hit=self._ray_hits(raw.reshape(n, 64)[:, 32:].contiguous(), False),
+                   raw=raw)
         if synchronize:
             torch.cuda.current_stream(self.dev).synchronize()
         return out
