@@ -79,7 +79,7 @@
  *      exported the views: nh_set_option(ctx, "sync_exports_views", 1) restores that contract at its old price; INTEGRATION.md.)  Any entry point outside the sample's
  *      call order between nh_collide and nh_apply_impulses turns a still step into a full one first, so everything it observes is what a full step
  *      produces.  nh_Counts.still_steps / still_replays count them.
- *      The scene queries (nh_query_build, nh_query_refit, nh_raycast, nh_spherecast, nh_raycast_all, nh_spherecast_all, nh_boxcast_all, nh_capsulecast_all, nh_raycast_k, nh_spherecast_k, nh_boxcast_k, nh_capsulecast_k, nh_boxcast, nh_capsulecast, nh_overlap, nh_penetration, nh_closest, nh_closest_k, nh_distance, nh_move, nh_query_set_layers, nh_query_filter, nh_query_layer_info) are not entry points of the step in this sense: they neither export nor settle nor turn a still step into a
+ *      The scene queries (nh_query_build, nh_query_refit, nh_raycast, nh_spherecast, nh_raycast_all, nh_spherecast_all, nh_boxcast_all, nh_capsulecast_all, nh_raycast_k, nh_spherecast_k, nh_boxcast_k, nh_capsulecast_k, nh_boxcast, nh_capsulecast, nh_overlap, nh_penetration, nh_region, nh_closest, nh_closest_k, nh_distance, nh_move, nh_query_set_layers, nh_query_filter, nh_query_layer_info) are not entry points of the step in this sense: they neither export nor settle nor turn a still step into a
  *      full one, and they do not count -- see "scene queries" below.
  *
  * Threading: one context = one HIP stream = one world at a time; no global mutable state.
@@ -428,8 +428,8 @@ int nh_query_stats(nh_context* ctx, nh_QueryStats* out);
                           NH_ERR_INVALID.
    An unknown mode, or a call before any nh_query_build, returns NH_ERR_INVALID; a refused call changes nothing -- the next query still uses the previous
    filter.  nh_query_filter is host state only: nothing is launched, nothing waits.  (The calls' own `flags` argument has no bit to spare for this.)
-   THE CONTRACT, for all twenty query calls (nh_raycast, nh_spherecast, nh_boxcast, nh_capsulecast, their _all and _k forms, nh_overlap, nh_penetration,
-   nh_closest, nh_closest_k, nh_distance, nh_move):
+   THE CONTRACT, for all twenty-one query calls (nh_raycast, nh_spherecast, nh_boxcast, nh_capsulecast, their _all and _k forms, nh_overlap, nh_penetration,
+   nh_region, nh_closest, nh_closest_k, nh_distance, nh_move; for nh_region the query is the region: NH_FILTER_PER_QUERY reads masks[i] for region i):
      - MASKED WORLD: with the filter on, a query with mask m writes byte for byte what the same call with the filter OFF writes on a world that is the same
        except for one thing: every collider with (layers & m) == 0 has a NaN pose -- "a collider of a body that does not exist", which every call above
        documents as never hit, never listed, never reported.  Collider indices, bodies and tags in the records are those of the real world.  For
@@ -801,6 +801,54 @@ int nh_overlap(nh_context* ctx, const nh_OverlapQuery* queries, uint32_t count, 
 typedef struct nh_PenetrationHit { float normal[3]; float depth; uint32_t body; uint32_t collider; uint32_t shape; uint32_t tag; } nh_PenetrationHit;  /* 32 B */
 int nh_penetration(nh_context* ctx, const nh_OverlapQuery* queries, uint32_t count, uint32_t* offsets /* count + 1 */, nh_PenetrationHit* hits,
                    uint32_t capacity, uint32_t flags /* 0 */);
+
+/* nh_region: which colliders of the LAST nh_query_build or nh_query_refit lie inside each of `count` convex regions -- the colliders in a camera
+   frustum or a shadow cascade before nh_stream_state is read, the colliders in a client's area of interest, "everything in this slab".  The large
+   question: a region may cover the whole world.  Every other query call gives one lane to a query; here the work of ONE region spreads over the GPU.
+   REGIONS (nh_Region): the intersection of the first `plane_count` (1 .. NH_REGION_MAX_PLANES) half-spaces.  Plane k is (nx, ny, nz, d): a point x is
+   inside it iff n.x + d >= 0.  n need not be unit length.  Planes behind `plane_count` and `reserved` are not read.
+   PER PLANE (float32, exactly nudge_amd/csrc/nh_query.h, "region"; each product rounded before its sum, dot = (x*x + y*y) + z*z, no fused multiply-add):
+   the plane KEEPS a collider at world position p iff s + r >= 0.0f, with s = dot(n, p) + d and r the collider's reach along n:
+     - sphere of radius R: r = R * sqrtf(dot(n, n));
+     - box of half extents h and rotation q: r = (h.x * |dot(n, A.c0)| + h.y * |dot(n, A.c1)|) + h.z * |dot(n, A.c2)|, A = the rotation matrix of q.
+   THE ANSWER of region i is every box and sphere collider of the last build or refit (those of sleeping bodies and of body 0 included) that EVERY one of
+   its planes keeps, less the colliders of `ignore_body` (0xffffffff: none is ignored).  A collider of a NaN pose (a body that does not exist) is never
+   listed: s is NaN and the >= fails.  This is the standard plane-by-plane frustum test, and it is CONSERVATIVE: it never misses a collider that reaches
+   into the region, and it may list one that lies outside it near an edge or a corner where two planes meet (the collider crosses each plane, but not
+   where they cross each other).  The answer is defined without the tree: a brute force over all colliders gives the same bytes.
+   An INVALID region lists nothing (count 0): plane_count == 0 or > NH_REGION_MAX_PLANES, a non-finite coefficient among those it reads, or a counted
+   plane whose dot(n, n) is not finite or not > 0 (a zero normal, a normal whose square overflows).  An asynchronous call cannot refuse one record.
+   OUTPUT, ORDER AND CAPACITY ARE nh_overlap's, word for word (the same chain of launches writes them): offsets[0 .. count] by the exclusive scan of
+   the per-region counts; the records of region i are hits[offsets[i] .. offsets[i+1]) as nh_OverlapHit in ascending COMBINED collider index; COUNT ONLY
+   with hits == NULL and capacity == 0; the CAPACITY prefix rule (segment i is written iff offsets[i+1] <= capacity, every byte of `hits` behind the
+   written prefix is left untouched, `offsets` is always complete); a true total of 2^32 - 1 or more writes offsets[count] = 0xffffffff and no record.
+   Returns NH_ERR_INVALID before any nh_query_build, for flags != 0, for `regions` null or not 16-byte aligned, `offsets` null or not 4-byte aligned,
+   `hits` null with capacity > 0 or not 16-byte aligned, and for count >= 2^30 -- nh_overlap's checks in nh_overlap's order; count = 0 is a no-op that
+   returns NH_OK.  A world of zero colliders gives all-zero offsets.
+   An OBSERVER like nh_overlap (note 9): no view export, no settling of deferred gravity, no still step turned into a full one, no change to nh_Counts.
+   Everything is enqueued on the context's stream, except that a list call with a larger capacity than any before grows nh_overlap's sort scratch, and one
+   with a larger count than any before a cursor word per region, each after a stream synchronise.  Layer masks: the twenty-first call of that contract.
+   HOW: a work item is (region, entry node), the entry nodes being the disjoint subtrees of at most 1024 consecutive leaves the box pass
+   starts its top phase from (about ten thousand at a million colliders).  A lane tests an item's box against the planes; for each item that is not
+   outside, a wave sweeps the entry's contiguous leaves with the exact predicate, the planes in scalar registers.  No walk, no stack, no one-lane tail.
+   Timing labels: q_region_count, q_region_list, then nh_overlap's own.
+   MEASURED (tools/region_rates.py -> profiles/region_rates.log; one MI355X, one run, the landed config-2 world of 1,004,524 colliders and 9,823 entry
+   nodes; ms per call, the best of 5 blocks of 20 calls by device events -- nh_overlap one call a block; the count-only call / it followed by the exactly
+   sized list call):
+     (a) one region that is the world's AABB, 1,004,524 records          0.152 / 0.681      nh_overlap with that box, one lane      1795.8 / 5979.2
+     (b) one frustum that sees a tenth, 100,452 records                  0.048 / 0.191
+     (c) 64 such frusta, 4,518,700 records                               0.557 / 2.323
+     (d) 4,096 cubes of one tile's size (267 units), 29,785,535 records  1.582 / 8.173      nh_overlap with the cubes, a lane each    33.42 / 109.20
+   WHICH CALL FOR WHICH QUESTION: nh_region for a volume of a tile's size or more (nh_overlap takes 21 x as long to count at that size and 11,800 x for the
+   world, where a full step takes 0.27 ms) and for anything that is not a sphere, a box or a capsule; nh_overlap for shapes of a body's size, where a lane per
+   query is the right shape (1 M of them count in 0.64 ms) and its predicates are exact where this test is conservative (in (d) it lists 174 fewer of
+   29.8 M records).  Sizes between a body and a tile were not measured.  With 30 M records the sort of the shared chain is the largest part of the
+   list call.  DESIGN 10.16 has the tables and the per-label times.
+   Not built: regions of more than eight planes; exact (non-conservative) convex intersection; queries on a partitioned world, as before. */
+#define NH_REGION_MAX_PLANES 8u
+typedef struct nh_Region { float planes[NH_REGION_MAX_PLANES][4]; uint32_t plane_count; uint32_t ignore_body; uint32_t reserved[2]; } nh_Region;   /* 144 B */
+int nh_region(nh_context* ctx, const nh_Region* regions, uint32_t count, uint32_t* offsets /* count + 1 */, nh_OverlapHit* hits, uint32_t capacity,
+              uint32_t flags /* 0 */);
 
 /* nh_distance: how far each of `count` query shapes is from the world of the LAST nh_query_build or nh_query_refit, and towards what -- the clearance
    of a crate, a hull or a limb.  nh_penetration describes a pair that overlaps; this describes the pairs that do not.

@@ -1,9 +1,9 @@
 // nh_query.h -- per-item arithmetic of the scene query (nh_query_build / nh_raycast / nh_spherecast / nh_boxcast / nh_capsulecast / nh_overlap /
 // nh_closest / nh_distance, nh_query.hip): a collider's world pose, a ray against one box and against one sphere, the overlap predicates of a query sphere, box or
 // capsule against one collider, a swept ball, box and capsule against one box and one sphere, the signed distance of a point from one box and one
-// sphere, with the walk's node tests they are pruned by.
+// sphere, the per-plane test of nh_region, with the walk's node tests they are pruned by.
 //
-// Every function is `NH_HD` so that tests/hostquery (hostoverlap, hostsweep, hostboxcast, hostcapsule, hostpoint) builds the SAME arithmetic with g++ -ffp-contract=off and gets the device's bits: the
+// Every function is `NH_HD` so that tests/hostquery (hostoverlap, hostsweep, hostboxcast, hostcapsule, hostpoint, hostregion) builds the SAME arithmetic with g++ -ffp-contract=off and gets the device's bits: the
 // brute force over all colliders there is the oracle of the GPU's tree traversal.  Only + - * /, sqrtf (correctly rounded on both sides)
 // and sign / absolute-value bit operations are used (and fminf / fmaxf in the pads and the walk's node test, which agree on both sides).
 //
@@ -1298,6 +1298,71 @@ NH_HD bool nh_q_move_advance(nh_QMove& s, bool hit, float t, nh_f3 n, float skin
 	s.v = w; s.np = n;
 	if (s.slides > max_slides && nh_dot(w, w) > 0.0f) { s.flags |= NH_Q_MOVE_SLIDES_OUT; return false; }
 	return true;
+}
+
+// ---- region (nh_region): is a collider inside a convex region, the intersection of up to NH_Q_REGION_MAX_PLANES half-spaces? ------------------------------
+// Plane (n, d): a point x is inside iff n.x + d >= 0; n need not be unit length.  The plane KEEPS a collider at world position p iff s + r >= 0.0f with
+//   s = nh_dot(n, p) + d
+//   r = R * sqrtf(nh_dot(n, n))                                                              for a sphere of radius R
+//   r = (h.x * |nh_dot(n, A.c0)| + h.y * |nh_dot(n, A.c1)|) + h.z * |nh_dot(n, A.c2)|        for a box of half extents h, A = nh_matrix(q)
+// (r: how far the collider reaches along n, its support distance).  A region keeps a collider iff every one of its planes does: the plane-by-plane frustum
+// test.  It never drops a collider that reaches into the region; near an edge or a corner where two planes meet it keeps some that lie outside.  A NaN
+// anywhere makes s + r NaN, the >= fails, and the collider is not kept.
+#define NH_Q_REGION_MAX_PLANES 8u
+
+NH_HD bool nh_q_region_finite(float x) { return (nh_asuint(x) & 0x7f800000u) != 0x7f800000u; }
+
+// A region's validity: 1 .. 8 planes, every coefficient it reads finite, every n.n finite and > 0.  `planes`: 4 floats per plane.
+NH_HD bool nh_q_region_valid(const float* planes, uint32_t plane_count) {
+	if (plane_count == 0u || plane_count > NH_Q_REGION_MAX_PLANES) return false;
+	bool ok = true;
+	for (uint32_t k = 0u; k < plane_count; ++k) {
+		const float* pl = planes + 4u * k;
+		const float nn = nh_dot(nh_make3(pl[0], pl[1], pl[2]), nh_make3(pl[0], pl[1], pl[2]));
+		ok = ok && nh_q_region_finite(pl[0]) && nh_q_region_finite(pl[1]) && nh_q_region_finite(pl[2]) && nh_q_region_finite(pl[3]);
+		ok = ok && nh_q_region_finite(nn) && nn > 0.0f;
+	}
+	return ok;
+}
+
+NH_HD bool nh_q_region_keeps_sphere(nh_f3 n, float d, nh_f3 p, float R) {
+	const float s = nh_dot(n, p) + d;
+	const float r = R * sqrtf(nh_dot(n, n));
+	return s + r >= 0.0f;
+}
+
+// (A = nh_matrix(q) of the box: the caller computes it once for all planes)
+NH_HD bool nh_q_region_keeps_box(nh_f3 n, float d, nh_f3 p, const nh_m33& A, nh_f3 h) {
+	const float s = nh_dot(n, p) + d;
+	const float r = (h.x * nh_abs(nh_dot(n, A.c0)) + h.y * nh_abs(nh_dot(n, A.c1))) + h.z * nh_abs(nh_dot(n, A.c2));
+	return s + r >= 0.0f;
+}
+
+// One collider (record: position p, rotation q, half extents h with h.x the radius of a sphere) against the first plane_count planes of a valid region
+NH_HD bool nh_q_region_keeps(const float* planes, uint32_t plane_count, nh_f3 p, nh_quat q, nh_f3 h, bool box) {
+	bool in = true;
+	if (box) {
+		const nh_m33 A = nh_matrix(q);
+		for (uint32_t k = 0u; k < plane_count; ++k)
+			in = in && nh_q_region_keeps_box(nh_make3(planes[4u * k], planes[4u * k + 1u], planes[4u * k + 2u]), planes[4u * k + 3u], p, A, h);
+	} else {
+		for (uint32_t k = 0u; k < plane_count; ++k)
+			in = in && nh_q_region_keeps_sphere(nh_make3(planes[4u * k], planes[4u * k + 1u], planes[4u * k + 2u]), planes[4u * k + 3u], p, h.x);
+	}
+	return in;
+}
+
+// The node test of nh_region's kernel: is the box [lo, hi] SURELY outside the plane (n, d)?  g = the largest value of n.x + d over the box, term by term
+// (fmaxf of the two products per axis); the box is outside iff g + m < 0 with the margin
+//   m = 2^-18 * (|n.x| * max(|lo.x|, |hi.x|) + |n.y| * max(|lo.y|, |hi.y|) + |n.z| * max(|lo.z|, |hi.z|) + |d|)
+// Only a comparison that is TRUE prunes: a NaN box or an overflow prunes nothing.  Conservative against the predicates above: in real
+// arithmetic s + r of a collider is at most g of its world AABB, hence of every box that contains it; the roundings of s + r and of g are each below
+// 2^-20 of the bracket of m, which is evaluated on a box that contains the collider's coordinates.
+NH_HD bool nh_q_region_node_outside(nh_f3 n, float d, nh_f3 lo, nh_f3 hi) {
+	const float g = ((fmaxf(n.x * lo.x, n.x * hi.x) + fmaxf(n.y * lo.y, n.y * hi.y)) + fmaxf(n.z * lo.z, n.z * hi.z)) + d;
+	const float m = (((fabsf(n.x) * fmaxf(fabsf(lo.x), fabsf(hi.x)) + fabsf(n.y) * fmaxf(fabsf(lo.y), fabsf(hi.y))) + fabsf(n.z) * fmaxf(fabsf(lo.z), fabsf(hi.z))) +
+	                 fabsf(d)) * 3.814697265625e-06f;
+	return g + m < 0.0f;
 }
 
 #endif

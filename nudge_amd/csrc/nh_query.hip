@@ -3,6 +3,7 @@
 // closest-hit / any-hit ray casts), nh_spherecast, nh_boxcast and nh_capsulecast (the same for swept balls, oriented boxes and capsules), their all-hits
 // (_all) and first-k (_k) forms, nh_closest / nh_closest_k / nh_distance (the nearest colliders to a point or a shape) and nh_overlap / nh_penetration (the
 // colliders touching each of a batch of spheres, boxes or capsules, as variable-length segments) and nh_move (collide-and-slide: the capsule cast in a loop).
+// nh_region (the colliders inside each of a batch of convex regions, through nh_overlap's chain) does not walk: it sweeps the leaves below the tree's entry nodes.
 // include/nudge_hip.h, "scene queries".
 // Layer masks (include/nudge_hip.h, "layer masks"): every query call walks under the mask(s) nh_query_filter set, in the FILTER = true instantiation of its kernel.
 // Traversal is stackless: a node that is missed or a leaf that is done continues at its ESCAPE link (the next node in pre-order after its subtree),
@@ -661,6 +662,118 @@ __global__ __launch_bounds__(256) void k_q_penetration_gather(const uint64_t* __
 	}
 }
 
+// ---- region -----------------------------------------------------------------------------------------------------------------------------------
+// nh_region: the colliders inside each of `count` convex regions (nh_query.h, "region").  No lane owns a region: a WORK ITEM is (region, entry node), the
+// entry nodes being nh_QueryState::top -- the roots of disjoint subtrees, each inside one run of NH_Q_RUN consecutive leaves, every leaf below exactly one
+// of them (k_q_tree lists the children, inside one run, of every node that crosses a run boundary; the root crosses iff n > NH_Q_RUN).  A tree of one run
+// has no such list: its one entry is the root.  An entry may be a leaf.  top_n lives on the device, so the grid is capped and the items, region-major, are
+// dealt to the waves in chunks of `ch` consecutive ones, ch = ceil(items / waves) clamped to 1 .. 64: few items spread over many waves, many fill the lanes.
+//   node test  one LANE per item of the chunk: the region's validity (nh_q_region_valid), under the filter the entry's layer word, then the entry's box
+//              against each plane (nh_q_region_node_outside: a margin of 2^-18 of |n| times the box's coordinates plus |d|; only a TRUE comparison
+//              prunes).  Outside any plane: the item is done after one node load.  The list pass takes the regions inside the written prefix only.
+//   leaf sweep one WAVE per item that is left, one after the other: its region and entry go to scalar registers (readlane), and with them the planes --
+//              every lane reads them at one address.  The entry's leaves are contiguous: [first, last[e]], the entry's own index being one end of its
+//              range (Karras), so first = e unless last[e] == e, and then a leftmost descent finds it.  64 leaves a step: idx[j] coalesced, rec[idx[j]]
+//              gathered, `ignore_body`, the leaf's layer word (FILTER), the exact predicate -- on every leaf, also where the entry's box lies wholly inside:
+//              that keeps the NaN poses out and needs no second margin.
+//   count      ballot and popcount per step, summed in a scalar register; one integer atomic per item on offsets[region] (zeroed at the head of the chain).
+//              Integer sums do not depend on their order: the counts are deterministic.
+//   list       per step, one atomic on the region's cursor reserves popcount slots of its segment; key (region << cbits) | c, value c.  Slot order is
+//              arbitrary; nh_overlap's sort over the written prefix and k_q_overlap_gather make the bytes deterministic.
+// No LDS, no barrier, no walk.  (registers and occupancy.)
+static_assert(sizeof(nh_Region) == 144 && NH_REGION_MAX_PLANES == NH_Q_REGION_MAX_PLANES, "nh_Region is nine 16-byte words; nh_query.h's plane bound is the header's");
+#define NH_Q_REGION_GRID 2048u
+
+template <bool LIST, bool FILTER>
+__global__ __launch_bounds__(256) void k_q_region(const nh_Region* __restrict__ regions, uint32_t count, uint32_t* offsets, const nh_QNode* __restrict__ nodes,
+                                                  const nh_QRec* __restrict__ rec, const uint32_t* __restrict__ idx, const uint32_t* __restrict__ last,
+                                                  const uint32_t* __restrict__ top, uint32_t n, uint32_t nbox, nh_QCtl* ctl, uint32_t* __restrict__ cursor,
+                                                  uint64_t* __restrict__ keys, uint32_t* __restrict__ vals, uint32_t cbits, nh_QFilter F) {
+	if (!LIST && blockIdx.x == 0 && threadIdx.x == 0) { ctl->ov_wrap = 0u; ctl->ov_written = 0u; }   // (k_q_overlap_fix sets both)
+	const uint32_t written = LIST ? ctl->ov_written : 0u;
+	const uint32_t entries = n > NH_Q_RUN ? ctl->top_n : (n ? 1u : 0u);
+	const uint64_t total = (uint64_t)count * entries;
+	const uint32_t lane = nh_lane();
+	const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
+	const uint64_t per = (total + waves - 1u) / waves;
+	const uint32_t ch = per > 64u ? 64u : (uint32_t)per;
+	const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
+	for (uint64_t item0 = (uint64_t)wave * ch; item0 < total; item0 += waves * ch) {
+		// ---- node test: lane l takes item item0 + l
+		const uint64_t item = item0 + lane;
+		uint32_t ri = 0u, node = 0u;
+		bool live = lane < ch && item < total;
+		if (live) {
+			ri = (uint32_t)(item / entries);
+			const uint32_t e = (uint32_t)(item - (uint64_t)ri * entries);
+			if (LIST) {
+				const uint32_t base = offsets[ri], end = offsets[ri + 1u];
+				live = base < end && end <= written;
+			}
+			if (live) {
+				const float* pl = &regions[ri].planes[0][0];
+				const uint32_t pc = regions[ri].plane_count;
+				live = nh_q_region_valid(pl, pc);
+				node = n > NH_Q_RUN ? top[e] : 0u;
+				if (node >= 2u * n - 1u) live = false;          // (cannot happen: a guard against reading outside the nodes)
+				if (FILTER && live) live = F.sees(node, F.of(ri));
+				if (live) {
+					const float4 na = nodes[node].a, nb = nodes[node].b;
+					const nh_f3 lo = nh_make3(na.x, na.y, na.z), hi = nh_make3(nb.x, nb.y, nb.z);
+					for (uint32_t k = 0u; k < pc; ++k)
+						if (nh_q_region_node_outside(nh_make3(pl[4u * k], pl[4u * k + 1u], pl[4u * k + 2u]), pl[4u * k + 3u], lo, hi)) live = false;
+				}
+			}
+		}
+		// ---- leaf sweep: the wave takes the items left, one after the other
+		uint64_t todo = __ballot(live);
+		while (todo) {
+			const int src = __ffsll((long long)todo) - 1;
+			todo &= todo - 1ull;
+			const uint32_t r = (uint32_t)__builtin_amdgcn_readlane((int)ri, src), e = (uint32_t)__builtin_amdgcn_readlane((int)node, src);
+			uint32_t jf, jl;
+			if (e >= n - 1u) jf = jl = e - (n - 1u);            // the entry is a leaf
+			else {
+				jl = last[e];
+				uint32_t u = e;
+				if (jl == e) while (u < n - 1u) u = __float_as_uint(nodes[u].a.w);      // leftmost descent (internal nodes carry their left child's id there)
+				jf = jl == e ? u - (n - 1u) : e;
+			}
+			if (jl >= n) jl = n - 1u;                           // (cannot happen; the sweep stays inside idx)
+			const float* pl = &regions[r].planes[0][0];
+			const uint32_t pc = regions[r].plane_count, ignore = regions[r].ignore_body;
+			const uint32_t fm = FILTER ? F.of(r) : 0u;
+			const uint32_t seg = LIST ? offsets[r] : 0u, seg_end = LIST ? offsets[r + 1u] : 0u;
+			uint32_t found = 0u;
+			for (uint32_t j0 = jf; j0 <= jl; j0 += 64u) {
+				const uint32_t j = j0 + lane;
+				bool keep = false;
+				uint32_t c = 0u;
+				if (j <= jl) {
+					c = idx[j];
+					if (c < n && (!FILTER || F.sees(n - 1u + j, fm))) {
+						const nh_QRec q = rec[c];
+						if (__float_as_uint(q.a.w) != ignore) {
+							const nh_QShape s = nh_q_unpack(q);
+							keep = nh_q_region_keeps(pl, pc, s.p, s.q, s.h, c < nbox);
+						}
+					}
+				}
+				const uint64_t bal = __ballot(keep);
+				if (!LIST) found += (uint32_t)__popcll(bal);
+				else if (bal) {
+					uint32_t at = 0u;
+					if (lane == 0u) at = atomicAdd(&cursor[r], (uint32_t)__popcll(bal));
+					at = seg + (uint32_t)__shfl((int)at, 0) + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+					// (at < seg_end: the count pass found the same set; a guard against writing outside the region's segment)
+					if (keep && at < seg_end) { keys[at] = ((uint64_t)r << cbits) | c; vals[at] = c; }
+				}
+			}
+			if (!LIST && found && lane == 0u) atomicAdd(&offsets[r], found);
+		}
+	}
+}
+
 // ---- all-hits casts ---------------------------------------------------------------------------------------------------------------------------
 // nh_raycast_all / nh_spherecast_all / nh_boxcast_all / nh_capsulecast_all: every collider a cast passes through, ordered along the cast.  nh_overlap's chain (kernel boundaries are the
 // only hand-offs, no atomic decides where a record goes) with the casts' walk in place of the volume walk and an ordering by t behind it:
@@ -987,6 +1100,45 @@ extern "C" int nh_penetration(nh_context* ctx, const nh_OverlapQuery* queries, u
 	nh_QueryState* q = ctx->query;
 	NH_LAUNCH(ctx, "q_penetration_gather", k_q_penetration_gather, nh_grid_for(capacity, 256, 1u << 20), 256, in_b ? q->ov_keys_b : q->ov_keys_a,
 	          in_b ? q->ov_vals_b : q->ov_vals_a, q->ctl, q->rec, q->n, q->nbox, queries, count, cbits, hits);
+	return NH_OK;
+}
+
+// nh_region's cursors, by region of the caller's count (a growth waits for the stream first, as nh_overlap_reserve's does)
+static int nh_region_reserve(nh_context* ctx, uint32_t count) {
+	nh_QueryState* q = ctx->query;
+	if (count <= q->rg_capacity) return NH_OK;
+	const uint32_t cap = count + count / 8u + 64u;          // (count < 2^30)
+	NH_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+	q->rg_capacity = 0;
+	{ int rc = nh_device_buffers(ctx, { { &q->rg_cursor, sizeof(uint32_t) * (size_t)cap } }); if (rc) return rc; }
+	q->rg_capacity = cap;
+	return NH_OK;
+}
+
+// nh_overlap's chain with k_q_region in place of the walks: nh_overlap's argument rules, offsets and capacity contract, sort and gather (the comment above
+// k_q_region).  offsets[0 .. count] are zeroed first: the count pass adds into them.
+extern "C" int nh_region(nh_context* ctx, const nh_Region* regions, uint32_t count, uint32_t* offsets, nh_OverlapHit* hits, uint32_t capacity, uint32_t flags) {
+	bool list = false;
+	{ const int rc = nh_overlap_args(ctx, regions, count, offsets, hits, capacity, flags, &list); if (rc || count == 0u) return rc; }
+	if (list) { const int rc = nh_region_reserve(ctx, count); if (rc) return rc; }
+	nh_QueryState* q = ctx->query;
+	const uint32_t cbits = (uint32_t)nh_q_bits(q->n);
+	// (one wave per item at most: a small world or a small batch launches a small grid)
+	const uint32_t grid = nh_grid_for((uint64_t)count * (q->n ? q->n : 1u), 4u, NH_Q_REGION_GRID);
+	bool on;
+	const nh_QFilter F = nh_query_filter_of(q, &on);
+	NH_HIP_CHECK(ctx, hipMemsetAsync(offsets, 0, sizeof(uint32_t) * ((size_t)count + 1u), ctx->stream));
+	NH_LAUNCH(ctx, "q_region_count", (on ? k_q_region<false, true> : k_q_region<false, false>), grid, 256, regions, count, offsets, q->nodes, q->rec, q->idx, q->last,
+	          q->top, q->n, q->nbox, q->ctl, (uint32_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, cbits, F);
+	nh_overlap_offsets(ctx, offsets, count, capacity);
+	if (!list) return NH_OK;
+	NH_HIP_CHECK(ctx, hipMemsetAsync(q->rg_cursor, 0, sizeof(uint32_t) * (size_t)count, ctx->stream));
+	NH_LAUNCH(ctx, "q_region_list", (on ? k_q_region<true, true> : k_q_region<true, false>), grid, 256, regions, count, offsets, q->nodes, q->rec, q->idx, q->last,
+	          q->top, q->n, q->nbox, q->ctl, q->rg_cursor, q->ov_keys_a, q->ov_vals_a, cbits, F);
+	const int bits = (((int)cbits + nh_q_bits(count)) + 7) / 8 * 8;
+	const int in_b = nh_sort_u64_u32(ctx, q->ov_keys_a, q->ov_keys_b, q->ov_vals_a, q->ov_vals_b, &q->ctl->ov_written, q->hist, 0, bits);
+	NH_LAUNCH(ctx, "q_overlap_gather", k_q_overlap_gather, nh_grid_for(capacity, 256, 4096), 256, in_b ? q->ov_vals_b : q->ov_vals_a, q->ctl, q->rec, q->n, q->nbox,
+	          hits);
 	return NH_OK;
 }
 

@@ -41,6 +41,8 @@ struct nh_QueryState {
 	uint32_t* top;               // the entry nodes of the top phase: nodes inside one run whose parent crosses a run boundary (ctl->top_n of them)
 	uint32_t ov_capacity;        // nh_overlap's sort scratch, by record of the caller's capacity
 	uint64_t* ov_keys_a; uint64_t* ov_keys_b; uint32_t* ov_vals_a; uint32_t* ov_vals_b;
+	uint32_t rg_capacity;        // nh_region's cursors, by region of the caller's count: where the list pass is in each region's segment
+	uint32_t* rg_cursor;
 	// layer masks (header, "layer masks"): the layer word of every collider of the last build, by combined index, and per node the OR of the words of
 	// the leaves below it (2 n - 1 words by node id, the layer pass writes them); both are only meaningful while layers_set
 	uint32_t layer_capacity;     // colliders the two arrays have room for

@@ -43,7 +43,7 @@ EXPORTS = [
     "nh_partition_top_speed", "nh_partition_set_peer_speeds", "nh_partition_refresh_is_quiet", "nh_partition_mark_ghosts", "nh_partition_pack_deltas", "nh_partition_unpack_deltas",
     "nh_partition_pack_momentum", "nh_partition_unpack_momentum", "nh_partition_exchange_iteration", "nh_partition_unpack_ghosts", "nh_partition_pack_step", "nh_partition_unpack_step", "nh_partition_choose_cut", "nh_partition_set_cut",
     "nh_partition_set_transport", "nh_partition_exchange_step", "nh_partition_step", "nh_partition_transport_check", "nh_partition_transport_result", "nh_set_first_ghost_body",
-    "nh_query_build", "nh_query_refit", "nh_query_stats", "nh_raycast", "nh_overlap", "nh_penetration", "nh_spherecast", "nh_raycast_all", "nh_spherecast_all", "nh_boxcast_all", "nh_capsulecast_all", "nh_boxcast", "nh_capsulecast", "nh_closest", "nh_closest_k", "nh_distance", "nh_move",
+    "nh_query_build", "nh_query_refit", "nh_query_stats", "nh_raycast", "nh_overlap", "nh_penetration", "nh_region", "nh_spherecast", "nh_raycast_all", "nh_spherecast_all", "nh_boxcast_all", "nh_capsulecast_all", "nh_boxcast", "nh_capsulecast", "nh_closest", "nh_closest_k", "nh_distance", "nh_move",
     "nh_raycast_k", "nh_spherecast_k", "nh_boxcast_k", "nh_capsulecast_k",
     "nh_query_set_layers", "nh_query_filter", "nh_query_layer_info",
 ]
@@ -177,6 +177,17 @@ MOVE_RESULT = np.dtype([("position", "<f4", 3), ("flags", "<u4"), ("remaining", 
 NH_MOVE_MAX_SLIDES = 8
 NH_MOVE_HIT, NH_MOVE_START_OVERLAP, NH_MOVE_SLIDES_OUT, NH_MOVE_WEDGED, NH_MOVE_INVALID = 1, 2, 4, 8, 0x80000000
 NH_OVERLAP_OVERFLOW = 0xFFFFFFFF          # offsets[count] when the total is 2^32 - 1 or more
+# nh_region (include/nudge_hip.h): up to NH_REGION_MAX_PLANES half-spaces (nx, ny, nz, d), inside where n.x + d >= 0
+NH_REGION_MAX_PLANES = 8
+REGION = np.dtype([("planes", "<f4", (NH_REGION_MAX_PLANES, 4)), ("plane_count", "<u4"), ("ignore_body", "<u4"), ("reserved", "<u4", 2)])
+
+
+def frustum_planes(m):
+    """The six inside-facing planes of the clip volume -w <= x, y, z <= w of a 4 x 4 clip matrix for column vectors, clip = m @ (x, y, z, 1): the rows
+    of `m` added to and subtracted from its last row (left, right, bottom, top, near, far), as a (6, 4) float32 array (nx, ny, nz, d), not normalised --
+    nh_region's planes as they are."""
+    m = np.asarray(m, dtype=np.float64).reshape(4, 4)
+    return np.stack([m[3] + m[0], m[3] - m[0], m[3] + m[1], m[3] - m[1], m[3] + m[2], m[3] - m[2]]).astype(np.float32)
 
 
 class OverlapQuery(C.Structure):
@@ -302,6 +313,9 @@ def lib():
             L.nh_move.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
         L.nh_overlap.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
         L.nh_penetration.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+        # (an older build of the library, loaded through NUDGE_HIP_LIBRARY for an A/B, has no nh_region: World.region then raises AttributeError)
+        if hasattr(L, "nh_region"):
+            L.nh_region.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
         # (an older build of the library, loaded through NUDGE_HIP_LIBRARY for an A/B, has no all-hits casts: World.raycast_all then raises AttributeError)
         if hasattr(L, "nh_raycast_all"):
             L.nh_raycast_all.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
@@ -1226,6 +1240,44 @@ class World:
             torch.cuda.current_stream(self.dev).synchronize()
         return dict(offsets=off, written=written, query=query, normal=f[:, 0:3], depth=f[:, 3], body=u[:, 4], collider=u[:, 5], shape=u[:, 6], tag=u[:, 7],
                     raw=hits)
+
+    def region_records(self, regions, offsets=None, hits=None, capacity=0):
+        """nh_region on records already laid out as nh_Region: `regions` a contiguous device tensor of count x 144 bytes (any dtype).  Returns
+        (offsets, hits) as overlap_records does, under the same count-only and capacity rules, with 16-byte nh_OverlapHit records.  Enqueued; nothing
+        waits (but a capacity or a count larger than any before grows the scratch)."""
+        torch = self.torch
+        n = regions.numel() * regions.element_size() // 144
+        if offsets is None:
+            offsets = torch.empty(n + 1, dtype=torch.int32, device=self.dev)
+        if hits is not None and hits.numel() * hits.element_size() < 16 * capacity:
+            raise ValueError(f"region_records: hits holds {hits.numel() * hits.element_size()} bytes, capacity {capacity} needs {16 * capacity}")
+        _check(self.L, self.L.nh_region(self.ctx, C.c_void_p(regions.data_ptr() if n else 0), n, C.c_void_p(offsets.data_ptr()),
+                                        C.c_void_p(hits.data_ptr() if hits is not None else 0), capacity, 0), "nh_region")
+        return offsets, hits
+
+    def region(self, planes, plane_counts=None, ignore_body=None, capacity=None, synchronize=False):
+        """The colliders inside each of n convex regions, against the last query_build() / query_refit(): `planes` is (n, P, 4) or (P, 4) with P <= 8,
+        plane (nx, ny, nz, d) keeping the side where n.x + d >= 0 (engine.frustum_planes gives a camera's six); `plane_counts` (a number or n values,
+        default P) says how many of a region's planes count; `ignore_body`: None, a body index, or n of them.  The test is the plane-by-plane frustum
+        test: it never misses a collider that reaches into the region and may list one just outside an edge or corner.
+        `capacity` and the returned dict are overlap()'s: offsets, written, and per record slot query (the region), body, collider, shape, tag, raw."""
+        torch = self.torch
+        pl = torch.as_tensor(planes, dtype=torch.float32, device=self.dev)
+        if pl.dim() == 2:
+            pl = pl[None]
+        if pl.dim() != 3 or pl.shape[2] != 4 or pl.shape[1] > NH_REGION_MAX_PLANES:
+            raise ValueError(f"region: planes must be (n, P, 4) or (P, 4) with P <= {NH_REGION_MAX_PLANES}, not {tuple(pl.shape)}")
+        n, P = pl.shape[0], pl.shape[1]
+        q = torch.zeros((n, 36), dtype=torch.float32, device=self.dev)
+        qi = q.view(torch.int32)
+        q[:, :4 * P] = pl.reshape(n, 4 * P)
+        qi[:, 32] = torch.as_tensor(P if plane_counts is None else plane_counts, dtype=torch.int32, device=self.dev)
+        qi[:, 33] = self._ignore_bits(ignore_body)
+        hits, off, written, query = self._overlap_lists(self.region_records, q, n, capacity, 16)
+        u = hits.view(torch.int32).reshape(-1, 4).to(torch.int64) & 0xFFFFFFFF
+        if synchronize:
+            torch.cuda.current_stream(self.dev).synchronize()
+        return dict(offsets=off, written=written, query=query, body=u[:, 0], collider=u[:, 1], shape=u[:, 2], tag=u[:, 3], raw=hits)
 
     # ---- measurement ----
     def enable_timing(self, on=True, only=None):
