@@ -79,7 +79,7 @@
  *      exported the views: nh_set_option(ctx, "sync_exports_views", 1) restores that contract at its old price; INTEGRATION.md.)  Any entry point outside the sample's
  *      call order between nh_collide and nh_apply_impulses turns a still step into a full one first, so everything it observes is what a full step
  *      produces.  nh_Counts.still_steps / still_replays count them.
- *      The scene queries (nh_query_build, nh_query_refit, nh_raycast, nh_spherecast, nh_raycast_all, nh_spherecast_all, nh_boxcast_all, nh_capsulecast_all, nh_raycast_k, nh_spherecast_k, nh_boxcast_k, nh_capsulecast_k, nh_boxcast, nh_capsulecast, nh_overlap, nh_penetration, nh_region, nh_closest, nh_closest_k, nh_distance, nh_move, nh_query_set_layers, nh_query_filter, nh_query_layer_info) are not entry points of the step in this sense: they neither export nor settle nor turn a still step into a
+ *      The scene queries (nh_query_build, nh_query_refit, nh_raycast, nh_spherecast, nh_raycast_all, nh_spherecast_all, nh_boxcast_all, nh_capsulecast_all, nh_raycast_k, nh_spherecast_k, nh_boxcast_k, nh_capsulecast_k, nh_boxcast, nh_capsulecast, nh_overlap, nh_penetration, nh_region, nh_closest, nh_closest_k, nh_distance, nh_move, nh_recover, nh_query_set_layers, nh_query_filter, nh_query_layer_info) are not entry points of the step in this sense: they neither export nor settle nor turn a still step into a
  *      full one, and they do not count -- see "scene queries" below.
  *
  * Threading: one context = one HIP stream = one world at a time; no global mutable state.
@@ -428,8 +428,8 @@ int nh_query_stats(nh_context* ctx, nh_QueryStats* out);
                           NH_ERR_INVALID.
    An unknown mode, or a call before any nh_query_build, returns NH_ERR_INVALID; a refused call changes nothing -- the next query still uses the previous
    filter.  nh_query_filter is host state only: nothing is launched, nothing waits.  (The calls' own `flags` argument has no bit to spare for this.)
-   THE CONTRACT, for all twenty-one query calls (nh_raycast, nh_spherecast, nh_boxcast, nh_capsulecast, their _all and _k forms, nh_overlap, nh_penetration,
-   nh_region, nh_closest, nh_closest_k, nh_distance, nh_move; for nh_region the query is the region: NH_FILTER_PER_QUERY reads masks[i] for region i):
+   THE CONTRACT, for all twenty-two query calls (nh_raycast, nh_spherecast, nh_boxcast, nh_capsulecast, their _all and _k forms, nh_overlap, nh_penetration,
+   nh_region, nh_closest, nh_closest_k, nh_distance, nh_move, nh_recover; for nh_region the query is the region: NH_FILTER_PER_QUERY reads masks[i] for region i):
      - MASKED WORLD: with the filter on, a query with mask m writes byte for byte what the same call with the filter OFF writes on a world that is the same
        except for one thing: every collider with (layers & m) == 0 has a NaN pose -- "a collider of a body that does not exist", which every call above
        documents as never hit, never listed, never reported.  Collider indices, bodies and tags in the records are those of the real world.  For
@@ -913,7 +913,7 @@ int nh_distance(nh_context* ctx, const nh_DistanceQuery* queries, uint32_t count
         reach rule and tie rule, under the context's layer filter (the per-query mask index is the move's index).
      3. a miss: p = p + v (one add per component), v = 0, stop.
      4. a hit with t == 0 (START OVERLAP, or touching): flags |= NH_MOVE_START_OVERLAP, stop; p and v keep their bits.  The normal of such a hit is
-        -v / |v| and says nothing about the surface: getting out is nh_penetration's business.
+        -v / |v| and says nothing about the surface: getting out is nh_recover's business (below).
      5. a hit with t > 0: flags |= NH_MOVE_HIT, slides += 1, p = p + t*v, then p = p + skin*n (a multiply and an add per component each), rem = (1 - t)*v.
      6. deflect: s = rem.n; v' = rem - s*n if s < 0, else rem.  Where a hit was taken before and v'.n_prev < 0 (a CREASE): c = n_prev x n; c.c < 2^-24:
         v' = 0; else v' = c * ((rem.c) / (c.c)); then v' = 0 if v'.n_prev < 0 or v'.n < 0.  Then v' = 0 unless v'.d0 > 0 (a move never turns against what
@@ -941,8 +941,8 @@ int nh_distance(nh_context* ctx, const nh_DistanceQuery* queries, uint32_t count
    aligned; count = 0 is a no-op that returns NH_OK and launches nothing.  Every byte of `count` results is written and nothing behind them.  Never
    allocates, never waits: ONE launch on the context's stream (timing label q_move).  An OBSERVER like nh_capsulecast (note 9): no view export, no
    settling of deferred gravity, no still step turned into a full one, no change to nh_Counts.
-   NOT BUILT: box movers; rotation during the move; depenetration of a move that starts in overlap (nh_penetration gives the push); gravity, step-up,
-   ground snapping and slope limits; moving platforms (the velocity of what is hit); pushing dynamic bodies (queries are observers); the list of everything
+   NOT BUILT: box movers; rotation during the move; gravity, step-up, ground snapping and slope limits (depenetration of a move that starts in
+   overlap is nh_recover, below: recover, then move); moving platforms (the velocity of what is hit); pushing dynamic bodies (queries are observers); the list of everything
    touched (last_hit is the last cast's record only).
    Cost: one lane per move, up to max_slides + 1 walks of nh_capsulecast's; a lane that has finished waits for the slowest of its wave.  Measured (one
    MI355X, the landed config-2 world of 1,004,524 colliders, 1,048,576 moves of r = hh = 0.5 from just above resting bodies by 0.75 - 3 units, max_slides 4;
@@ -954,6 +954,64 @@ typedef struct nh_Move { float origin[3]; float skin; float displacement[3]; uin
                          float rotation[4]; float radius; float half_height; uint32_t max_slides; uint32_t reserved; } nh_Move;      /* 64 B */
 typedef struct nh_MoveResult { float position[3]; uint32_t flags; float remaining[3]; uint32_t slides; nh_RayHit last_hit; } nh_MoveResult;   /* 64 B */
 int nh_move(nh_context* ctx, const nh_Move* moves, uint32_t count, nh_MoveResult* results, uint32_t flags /* 0 */);
+
+/* nh_recover: push each of `count` query shapes (spheres, boxes, capsules: nh_OverlapQuery's encoding) out of everything it overlaps in the world of the
+   LAST nh_query_build or nh_query_refit -- what follows a start overlap: a capsule that ends a step sunk into a body that moved onto it, a crate spawned
+   into a pile, a character teleported to a checkpoint.  The loop a host would run around nh_penetration (list, download, pick a push, upload, again) runs on
+   the device, one lane per query, in ONE call.  nh_Recover is nh_OverlapQuery (its first 48 bytes, field for field) followed by `skin` and
+   `max_iterations`; `reserved` is not read.
+   ONE RECOVER, all in float32; the arithmetic is nudge_amd/csrc/nh_query.h, "recover" (nh_q_recover_begin / nh_q_recover_better / nh_q_recover_advance),
+   which is the definition and fixes the order of every operation (each product rounded before its sum, no fused multiply-add).
+   State: p = center, iterations = 0, flags = 0, last = the NONE record (normal = 0, depth = 0, body = collider = tag = 0xffffffff, shape = NH_SHAPE_NONE).
+   Repeat:
+     1. S = the colliders nh_overlap lists for the shape at p: the same decode, the same predicates, ignore_body excluded, under the context's layer
+        filter (the per-query mask index is the query's index).  NaN poses are never in S.  S empty: stop.
+     2. Among S the collider of greatest depth under the pair function nh_penetration uses for that pair; ties go to the lowest combined collider index
+        (boxes before spheres).  last = that pair's nh_PenetrationHit: the bytes nh_penetration writes for it with the query at p.
+     3. s = depth + skin.  s == 0: flags |= NH_RECOVER_TOUCHING, stop.
+     4. iterations == max_iterations: flags |= NH_RECOVER_OVERLAPPING, stop.
+     5. p = p + s * normal (one multiply and one add per component), iterations += 1, flags |= NH_RECOVER_PUSHED.
+   Output: position = p, push = p - center (one subtract per component), iterations, flags, last.  So a recover makes at most max_iterations pushes and
+   max_iterations + 1 walks; max_iterations = 0 only looks.  A result with none of OVERLAPPING, TOUCHING and INVALID set is FREE: the last walk ran
+   nh_overlap's very predicates at that very p and found nothing, so nh_overlap of the same shape at `position` counts 0 -- exactly.
+   DEEPEST FIRST, not a sum of pushes: a maximum with an index tie-break does not depend on the order a walk meets the leaves, so the answer is defined
+   without the tree and a brute force over all colliders gives the same 64 bytes; a float sum over S would depend on the walk order.
+   SKIN is the gap kept: for a convex pair, depth along the minimum-translation normal leaves the pair touching, and another skin along the same normal
+   leaves at least skin between them, so the next round no longer sees that collider and a following nh_move starts free.  skin = 0 is valid and leaves the
+   shape touching: the next walk then finds the pair again at a depth of 0 (TOUCHING) or of rounding dust, which may spend the iterations on pushes of an
+   ulp.  Scale skin to the scene: it must exceed the rounding of p (2^-23 of its largest coordinate) by a margin; 0.01 for bodies of size 1 near the origin.
+   OVERFLOW: a p that overflows makes the next round's query invalid; an invalid query overlaps nothing, so the recover ends there, as nh_move's does.
+   INVALID RECORDS -- anything nh_overlap counts as an invalid query (an unknown shape, a non-finite centre, a non-finite or negative size the shape reads,
+   a non-finite rotation where it is read), a non-finite or negative skin, max_iterations > NH_RECOVER_MAX_ITERATIONS -- write flags =
+   NH_RECOVER_INVALID, position = the bits of center, push = 0, iterations = 0 and last = the NONE record.
+   IDENTITIES (contracts):
+     - a query for which nh_overlap counts 0 returns flags = 0, position = the bits of center and last = the NONE record;
+     - with max_iterations = 0, last is the record of greatest depth (ties to the lowest collider index) in the segment nh_penetration writes for the same
+       first 48 bytes, position keeps the bits of center, and flags is NH_RECOVER_OVERLAPPING, NH_RECOVER_TOUCHING or 0;
+     - REPLAY: one nh_penetration call per round and nh_q_recover_advance on the host between them give nh_recover's 64 bytes per record;
+     - a capsule of half height 0 writes the sphere query's bytes and does not read `rotation`;
+     - after nh_query_refit the bytes are those after an nh_query_build of the same arrays; nh_query_filter is honoured in all three modes (the
+       twenty-second call of the MASKED WORLD contract).
+   Returns NH_ERR_INVALID before any nh_query_build, for flags != 0, for count >= 2^30, and for count > 0 with `queries` or `results` null or not 16-byte
+   aligned; count = 0 is a no-op that returns NH_OK and launches nothing.  Every byte of `count` results is written and nothing behind them.  Never
+   allocates, never waits: two launches on the context's stream (spheres and boxes; capsules of nonzero half height, as nh_overlap splits them), one timing
+   label, q_recover.  An OBSERVER like nh_overlap (note 9): no view export, no settling of deferred gravity, no still step turned into a full one, no
+   change to nh_Counts.
+   NOT BUILT: rotation out of overlap (the shape keeps its orientation); a push shared among several colliders at once (each round answers the deepest
+   one only, so a shape between two colliders it cannot clear -- a ball in a slot narrower than itself, a concave wedge -- is pushed back and forth and
+   ends OVERLAPPING: raise max_iterations, move it by other means, or accept the overlap); velocities (recover moves a position, nothing else).
+   Cost: one lane per query, up to max_iterations + 1 walks of nh_overlap's with the pair function at each accepted leaf; a lane that has finished waits
+   for the slowest of its wave.  Measured (one MI355X, the landed config-2 world of 1,004,524 colliders, 1,048,576 shapes of size 0.5 sunk into the tops of
+   resting bodies, skin 0.01, max_iterations 4; tools/recover_rates.py -> profiles/recover_rates.log): 1.35 ms for spheres, 1.83 ms for
+   capsules, 1.97 ms for boxes, 1.96 - 2.08 walks per query on average -- 0.70, 0.91 and 0.96 of ONE nh_penetration count call + list call on the same
+   first 48 bytes (of which the host loop makes one per round, with a download and an upload), and 1.08, 1.37 and 1.43 of (walks per query x the
+   nh_overlap count walk).  Filter off, beside the parent commit's library in the same process: nh_overlap 0.995, nh_move 1.001 of its times. */
+#define NH_RECOVER_MAX_ITERATIONS 8u
+enum { NH_RECOVER_PUSHED = 1u, NH_RECOVER_OVERLAPPING = 2u, NH_RECOVER_TOUCHING = 4u, NH_RECOVER_INVALID = 0x80000000u };
+typedef struct nh_Recover { float center[3]; uint32_t shape; float rotation[4]; float size[3]; uint32_t ignore_body;   /* = nh_OverlapQuery, 48 B */
+                            float skin; uint32_t max_iterations; uint32_t reserved[2]; } nh_Recover;                      /* 64 B */
+typedef struct nh_RecoverResult { float position[3]; uint32_t flags; float push[3]; uint32_t iterations; nh_PenetrationHit last; } nh_RecoverResult; /* 64 B */
+int nh_recover(nh_context* ctx, const nh_Recover* queries, uint32_t count, nh_RecoverResult* results, uint32_t flags /* 0 */);
 
 /* ---- multi-GPU: one x-slab of a world per context ------------------------------------------------------------------------------------
    The world is cut into slabs along x, one rank (process, GPU, nh_context) per slab [lo, hi).  A rank's arrays hold

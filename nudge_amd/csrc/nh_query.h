@@ -1300,6 +1300,54 @@ NH_HD bool nh_q_move_advance(nh_QMove& s, bool hit, float t, nh_f3 n, float skin
 	return true;
 }
 
+// ---- recover (nh_recover): push a shape out of what it overlaps, the state between two overlap walks -------------------------------------------------
+// These functions ARE the definition of nh_recover (include/nudge_hip.h): k_q_recover and the host's brute force (tests/hostoracle/hostrecover.cpp) both run
+//     s = nh_q_recover_begin(center);
+//     for (;;) { over the set S nh_overlap's predicates accept for the shape at s.p: the pair function's (depth, n) of the collider nh_q_recover_better keeps;
+//                if (!nh_q_recover_advance(s, S not empty, depth, n, skin, max_iterations)) break; }
+// and write s.p, s.flags, s.p - center, s.iterations and the record of the last pair kept.  Every product is rounded before the sum it goes into (no fused
+// multiply-add).  The flag bits are nh_RecoverResult.flags' (nh_query.hip asserts that they are the header's NH_RECOVER_*).
+#define NH_Q_RECOVER_PUSHED 1u
+#define NH_Q_RECOVER_OVERLAPPING 2u
+#define NH_Q_RECOVER_TOUCHING 4u
+#define NH_Q_RECOVER_MAX_ITERATIONS 8u
+
+// p: where the shape's centre is; iterations counts exactly the pushes made.
+struct nh_QRecover { nh_f3 p; uint32_t iterations, flags; };
+
+// What a recover record adds to the validity of the nh_OverlapQuery it starts with (header, "Invalid records"): a finite skin >= 0 and a push count in range.
+NH_HD bool nh_q_recover_valid(float skin, uint32_t max_iterations) {
+	return (nh_asuint(skin) & 0x7f800000u) != 0x7f800000u && !(skin < 0.0f) && max_iterations <= NH_Q_RECOVER_MAX_ITERATIONS;
+}
+
+NH_HD nh_QRecover nh_q_recover_begin(nh_f3 center) {
+	nh_QRecover s;
+	s.p = center; s.iterations = 0u; s.flags = 0u;
+	return s;
+}
+
+// Rule 2's choice among S: the greatest depth, ties to the lowest combined index -- a strict total order on (depth, c), so the collider kept does not
+// depend on the order the colliders are met in.  The pair functions return depth >= +0, never -0; a NaN (only non-finite arithmetic on huge finite inputs
+// makes one) compares as 0 here, so that the order stays total.  Start with best_c = 0xffffffff, which every index beats at best_depth = 0.
+NH_HD bool nh_q_recover_better(float depth, uint32_t c, float best_depth, uint32_t best_c) {
+	const float a = nh_q_pen_clamp(depth), b = nh_q_pen_clamp(best_depth);
+	return a > b || (a == b && c < best_c);
+}
+
+// Rules 1 and 3 - 5 behind one walk with the shape at s.p: `found` says whether S held a collider, (depth, n) are the pair function's for the one kept.
+// Returns whether the recover goes on (to the next walk).  Order of operations, per component k:
+//   s = depth + skin;  p_k = p_k + (s * n_k)
+NH_HD bool nh_q_recover_advance(nh_QRecover& s, bool found, float depth, nh_f3 n, float skin, uint32_t max_iterations) {
+	if (!found) return false;
+	const float push = depth + skin;
+	if (push == 0.0f) { s.flags |= NH_Q_RECOVER_TOUCHING; return false; }
+	if (s.iterations == max_iterations) { s.flags |= NH_Q_RECOVER_OVERLAPPING; return false; }
+	s.p = s.p + push * n;
+	s.iterations += 1u;
+	s.flags |= NH_Q_RECOVER_PUSHED;
+	return true;
+}
+
 // ---- region (nh_region): is a collider inside a convex region, the intersection of up to NH_Q_REGION_MAX_PLANES half-spaces? ------------------------------
 // Plane (n, d): a point x is inside iff n.x + d >= 0; n need not be unit length.  The plane KEEPS a collider at world position p iff s + r >= 0.0f with
 //   s = nh_dot(n, p) + d

@@ -2,7 +2,8 @@
 // nh_query.hip -- scene queries against the tree of the last nh_query_build or nh_query_refit (nh_query_build.hip, nh_query_tree.h): nh_raycast (batched
 // closest-hit / any-hit ray casts), nh_spherecast, nh_boxcast and nh_capsulecast (the same for swept balls, oriented boxes and capsules), their all-hits
 // (_all) and first-k (_k) forms, nh_closest / nh_closest_k / nh_distance (the nearest colliders to a point or a shape) and nh_overlap / nh_penetration (the
-// colliders touching each of a batch of spheres, boxes or capsules, as variable-length segments) and nh_move (collide-and-slide: the capsule cast in a loop).
+// colliders touching each of a batch of spheres, boxes or capsules, as variable-length segments) and nh_move (collide-and-slide: the capsule cast in a loop) and nh_recover
+// (shapes pushed out of what they overlap: the overlap walk in a loop, the penetration functions at its leaves).
 // nh_region (the colliders inside each of a batch of convex regions, through nh_overlap's chain) does not walk: it sweeps the leaves below the tree's entry nodes.
 // include/nudge_hip.h, "scene queries".
 // Layer masks (include/nudge_hip.h, "layer masks"): every query call walks under the mask(s) nh_query_filter set, in the FILTER = true instantiation of its kernel.
@@ -662,6 +663,76 @@ __global__ __launch_bounds__(256) void k_q_penetration_gather(const uint64_t* __
 	}
 }
 
+// ---- recover ----------------------------------------------------------------------------------------------------------------------------------
+// nh_recover: one lane per query.  The state machine is nh_query.h's ("recover": nh_q_recover_begin / _better / _advance, which the host's brute force runs
+// as well).  The record's first 48 bytes go through nh_QVolume, k_q_overlap's decode; a round is k_q_overlap's walk with the shape at p -- p finite, the
+// padded world AABB of k_q_overlap as the node test, its predicate at the leaf -- and, where the predicate accepts, the pair function
+// k_q_penetration_gather picks for that pair; nh_q_recover_better keeps the deepest.  So a round's set is nh_overlap's for the shape at p and its (normal,
+// depth) nh_penetration's, under the same mask (the query's index).  Capsules of nonzero half height run in an instantiation of their own, as in k_q_overlap:
+// each writes the results of its own queries, every query is exactly one's.  The loop bound is a constant and every round is a walk that terminates, so the
+// kernel terminates on any input.  A lane whose recover has ended waits for the slowest of its wave.  The result leaves as four 16-byte
+// stores, the last two the nh_PenetrationHit of the last pair kept (nh_q_identity of its collider).
+static_assert(NH_Q_RECOVER_PUSHED == NH_RECOVER_PUSHED && NH_Q_RECOVER_OVERLAPPING == NH_RECOVER_OVERLAPPING && NH_Q_RECOVER_TOUCHING == NH_RECOVER_TOUCHING &&
+              NH_Q_RECOVER_MAX_ITERATIONS == NH_RECOVER_MAX_ITERATIONS, "nh_query.h's recover constants are the header's");
+static_assert(sizeof(nh_Recover) == 64 && sizeof(nh_RecoverResult) == 64 && sizeof(nh_OverlapQuery) == 48 && sizeof(nh_PenetrationHit) == 32,
+              "nh_Recover is nh_OverlapQuery and one more 16-byte word, nh_RecoverResult two words and an nh_PenetrationHit");
+
+template <bool CAPSULE, bool FILTER>
+__global__ __launch_bounds__(256) void k_q_recover(const nh_Recover* __restrict__ queries, uint32_t count, nh_RecoverResult* __restrict__ results,
+                                                   const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox, nh_QFilter F) {
+	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
+		const float4* qp = reinterpret_cast<const float4*>(queries + i);
+		nh_QVolume v;
+		v.read(qp);
+		if (v.capsule != CAPSULE) continue;
+		const float4 q3 = qp[3];
+		const float skin = q3.x;
+		const uint32_t max_iterations = __float_as_uint(q3.y);
+		const bool capsule = CAPSULE, sphere = !CAPSULE && v.sphere;
+		const bool valid = v.ok && nh_q_recover_valid(skin, max_iterations);
+		const uint32_t fm = FILTER ? F.of(i) : 0u;
+		nh_QRecover s = nh_q_recover_begin(v.c);
+		float ld = 0.0f;
+		uint32_t lc = NH_Q_NONE;
+		nh_f3 ln = nh_make3(0.0f, 0.0f, 0.0f);
+		for (uint32_t round = 0u; round <= NH_RECOVER_MAX_ITERATIONS; ++round) {
+			if (!valid) break;
+			const nh_f3 c = s.p;
+			// the shape's world AABB at p, padded by 2^-18 of its largest coordinate: k_q_overlap's node test
+			nh_f3 lo = c - v.e, hi = c + v.e;
+			const float pad = fmaxf(fmaxf(fmaxf(fabsf(lo.x), fabsf(lo.y)), fmaxf(fabsf(lo.z), fabsf(hi.x))), fmaxf(fabsf(hi.y), fabsf(hi.z))) * 3.814697265625e-06f;
+			lo = nh_make3(lo.x - pad, lo.y - pad, lo.z - pad); hi = nh_make3(hi.x + pad, hi.y + pad, hi.z + pad);
+			float bd = 0.0f;
+			uint32_t bc = NH_Q_NONE;
+			nh_f3 bn = nh_make3(0.0f, 0.0f, 0.0f);
+			nh_q_walk<FILTER>(nodes, rec, nh_q_finite(c) && n ? 0u : NH_Q_NONE, v.ignore, F, fm,
+				[&](nh_f3 nlo, nh_f3 nhi, float&) { return nlo.x <= hi.x && lo.x <= nhi.x && nlo.y <= hi.y && lo.y <= nhi.y && nlo.z <= hi.z && lo.z <= nhi.z; },
+				[&](uint32_t cc, const nh_QRec& r, float) {
+					const nh_QShape col = nh_q_unpack(r);
+					bool hit;
+					if (capsule) hit = cc < nbox ? nh_q_overlap_capsule_box_a(c, v.a, v.h.x, col.p, col.q, col.h) : nh_q_overlap_capsule_sphere_a(c, v.a, v.h.x, col.p, col.h.x);
+					else if (cc < nbox) hit = sphere ? nh_q_overlap_sphere_box(c, v.h.x, col.p, col.q, col.h) : nh_q_overlap_box_box(c, v.q, v.h, col.p, col.q, col.h);
+					else hit = sphere ? nh_q_overlap_sphere_sphere(c, v.h.x, col.p, col.h.x) : nh_q_overlap_sphere_box(col.p, col.h.x, c, v.q, v.h);
+					if (!hit) return false;
+					nh_QPen o;
+					if (capsule) o = cc < nbox ? nh_q_pen_capsule_box_a(c, v.a, v.h.x, col.p, col.q, col.h) : nh_q_pen_capsule_sphere_a(c, v.a, v.h.x, col.p, col.h.x);
+					else if (cc < nbox) o = sphere ? nh_q_pen_sphere_box(c, v.h.x, col.p, col.q, col.h) : nh_q_pen_box_box(c, v.q, v.h, col.p, col.q, col.h);
+					else o = sphere ? nh_q_pen_sphere_sphere(c, v.h.x, col.p, col.h.x) : nh_q_pen_box_sphere(c, v.q, v.h, col.p, col.h.x);
+					if (nh_q_recover_better(o.depth, cc, bd, bc)) { bd = o.depth; bc = cc; bn = o.n; }
+					return false;
+				});
+			if (bc != NH_Q_NONE) { ld = bd; lc = bc; ln = bn; }
+			if (!nh_q_recover_advance(s, bc != NH_Q_NONE, bd, bn, skin, max_iterations)) break;
+		}
+		float4* out = reinterpret_cast<float4*>(results + i);
+		const nh_f3 push = valid ? s.p - v.c : nh_make3(0.0f, 0.0f, 0.0f);
+		out[0] = make_float4(s.p.x, s.p.y, s.p.z, __uint_as_float(valid ? s.flags : (uint32_t)NH_RECOVER_INVALID));
+		out[1] = make_float4(push.x, push.y, push.z, __uint_as_float(s.iterations));
+		out[2] = make_float4(ln.x, ln.y, ln.z, ld);
+		reinterpret_cast<uint4*>(out)[3] = lc != NH_Q_NONE ? nh_q_identity(lc, nbox, rec[lc]) : make_uint4(NH_Q_NONE, NH_Q_NONE, NH_SHAPE_NONE, NH_Q_NONE);
+	}
+}
+
 // ---- region -----------------------------------------------------------------------------------------------------------------------------------
 // nh_region: the colliders inside each of `count` convex regions (nh_query.h, "region").  No lane owns a region: a WORK ITEM is (region, entry node), the
 // entry nodes being nh_QueryState::top -- the roots of disjoint subtrees, each inside one run of NH_Q_RUN consecutive leaves, every leaf below exactly one
@@ -972,6 +1043,18 @@ extern "C" int nh_move(nh_context* ctx, const nh_Move* moves, uint32_t count, nh
 	bool on;
 	const nh_QFilter F = nh_query_filter_of(q, &on);
 	NH_LAUNCH(ctx, "q_move", on ? k_q_move<true> : k_q_move<false>, nh_grid_for(count, 256, 1u << 20), 256, moves, count, results, q->nodes, q->rec, q->n, q->nbox, F);
+	return NH_OK;
+}
+
+// nh_move's checks in nh_move's order; the sphere-and-box launch and the capsule launch under one label, as nh_overlap splits its walks; no allocation, no wait.
+extern "C" int nh_recover(nh_context* ctx, const nh_Recover* queries, uint32_t count, nh_RecoverResult* results, uint32_t flags) {
+	{ const int rc = nh_query_call(ctx, flags, 0u, 0u, 0u, count, 1u << 30, queries, results, nullptr); if (rc || count == 0u) return rc; }
+	nh_QueryState* q = ctx->query;
+	bool on;
+	const nh_QFilter F = nh_query_filter_of(q, &on);
+	const uint32_t grid = nh_grid_for(count, 256, 1u << 20);
+	NH_LAUNCH(ctx, "q_recover", (on ? k_q_recover<false, true> : k_q_recover<false, false>), grid, 256, queries, count, results, q->nodes, q->rec, q->n, q->nbox, F);
+	NH_LAUNCH(ctx, "q_recover", (on ? k_q_recover<true, true> : k_q_recover<true, false>), grid, 256, queries, count, results, q->nodes, q->rec, q->n, q->nbox, F);
 	return NH_OK;
 }
 

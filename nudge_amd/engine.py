@@ -43,7 +43,7 @@ EXPORTS = [
     "nh_partition_top_speed", "nh_partition_set_peer_speeds", "nh_partition_refresh_is_quiet", "nh_partition_mark_ghosts", "nh_partition_pack_deltas", "nh_partition_unpack_deltas",
     "nh_partition_pack_momentum", "nh_partition_unpack_momentum", "nh_partition_exchange_iteration", "nh_partition_unpack_ghosts", "nh_partition_pack_step", "nh_partition_unpack_step", "nh_partition_choose_cut", "nh_partition_set_cut",
     "nh_partition_set_transport", "nh_partition_exchange_step", "nh_partition_step", "nh_partition_transport_check", "nh_partition_transport_result", "nh_set_first_ghost_body",
-    "nh_query_build", "nh_query_refit", "nh_query_stats", "nh_raycast", "nh_overlap", "nh_penetration", "nh_region", "nh_spherecast", "nh_raycast_all", "nh_spherecast_all", "nh_boxcast_all", "nh_capsulecast_all", "nh_boxcast", "nh_capsulecast", "nh_closest", "nh_closest_k", "nh_distance", "nh_move",
+    "nh_query_build", "nh_query_refit", "nh_query_stats", "nh_raycast", "nh_overlap", "nh_penetration", "nh_region", "nh_spherecast", "nh_raycast_all", "nh_spherecast_all", "nh_boxcast_all", "nh_capsulecast_all", "nh_boxcast", "nh_capsulecast", "nh_closest", "nh_closest_k", "nh_distance", "nh_move", "nh_recover",
     "nh_raycast_k", "nh_spherecast_k", "nh_boxcast_k", "nh_capsulecast_k",
     "nh_query_set_layers", "nh_query_filter", "nh_query_layer_info",
 ]
@@ -176,6 +176,12 @@ MOVE = np.dtype([("origin", "<f4", 3), ("skin", "<f4"), ("displacement", "<f4", 
 MOVE_RESULT = np.dtype([("position", "<f4", 3), ("flags", "<u4"), ("remaining", "<f4", 3), ("slides", "<u4"), ("last_hit", RAY_HIT)])
 NH_MOVE_MAX_SLIDES = 8
 NH_MOVE_HIT, NH_MOVE_START_OVERLAP, NH_MOVE_SLIDES_OUT, NH_MOVE_WEDGED, NH_MOVE_INVALID = 1, 2, 4, 8, 0x80000000
+# nh_recover (include/nudge_hip.h): nh_OverlapQuery followed by `skin` and `max_iterations`; nh_RecoverResult.flags
+RECOVER = np.dtype([("center", "<f4", 3), ("shape", "<u4"), ("rotation", "<f4", 4), ("size", "<f4", 3), ("ignore_body", "<u4"), ("skin", "<f4"),
+                    ("max_iterations", "<u4"), ("reserved", "<u4", 2)])
+RECOVER_RESULT = np.dtype([("position", "<f4", 3), ("flags", "<u4"), ("push", "<f4", 3), ("iterations", "<u4"), ("last", PENETRATION_HIT)])
+NH_RECOVER_MAX_ITERATIONS = 8
+NH_RECOVER_PUSHED, NH_RECOVER_OVERLAPPING, NH_RECOVER_TOUCHING, NH_RECOVER_INVALID = 1, 2, 4, 0x80000000
 NH_OVERLAP_OVERFLOW = 0xFFFFFFFF          # offsets[count] when the total is 2^32 - 1 or more
 # nh_region (include/nudge_hip.h): up to NH_REGION_MAX_PLANES half-spaces (nx, ny, nz, d), inside where n.x + d >= 0
 NH_REGION_MAX_PLANES = 8
@@ -200,6 +206,14 @@ class OverlapHit(C.Structure):
 
 class PenetrationHit(C.Structure):
     _fields_ = [("normal", C.c_float * 3), ("depth", C.c_float), ("body", C.c_uint32), ("collider", C.c_uint32), ("shape", C.c_uint32), ("tag", C.c_uint32)]
+
+
+class Recover(C.Structure):
+    _fields_ = OverlapQuery._fields_ + [("skin", C.c_float), ("max_iterations", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class RecoverResult(C.Structure):
+    _fields_ = [("position", C.c_float * 3), ("flags", C.c_uint32), ("push", C.c_float * 3), ("iterations", C.c_uint32), ("last", PenetrationHit)]
 
 
 class KernelTime(C.Structure):
@@ -311,6 +325,9 @@ def lib():
         # (likewise nh_move: World.move then raises AttributeError)
         if hasattr(L, "nh_move"):
             L.nh_move.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
+        # (likewise nh_recover: World.recover then raises AttributeError)
+        if hasattr(L, "nh_recover"):
+            L.nh_recover.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
         L.nh_overlap.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
         L.nh_penetration.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
         # (an older build of the library, loaded through NUDGE_HIP_LIBRARY for an A/B, has no nh_region: World.region then raises AttributeError)
@@ -1118,6 +1135,41 @@ class World:
         u = raw.view(torch.int32).reshape(n, 16).to(torch.int64) & 0xFFFFFFFF
         out = dict(position=f[:, 0:3], remaining=f[:, 4:7], flags=u[:, 3], slides=u[:, 7], last_hit=self._ray_hits(raw.reshape(n, 64)[:, 32:].contiguous(), False),
                    raw=raw)
+        if synchronize:
+            torch.cuda.current_stream(self.dev).synchronize()
+        return out
+
+    def recover_records(self, records, results=None):
+        """nh_recover on records already laid out as nh_Recover: `records` a contiguous device tensor of count x 64 bytes (any dtype).  Returns the
+        count x 64-byte uint8 device tensor of nh_RecoverResult records (`results`, or a new one)."""
+        torch = self.torch
+        n = records.numel() * records.element_size() // 64
+        if results is None:
+            results = torch.empty((n, 64), dtype=torch.uint8, device=self.dev)
+        _check(self.L, self.L.nh_recover(self.ctx, C.c_void_p(records.data_ptr() if n else 0), n, C.c_void_p(results.data_ptr() if n else 0), 0),
+               "nh_recover")
+        return results
+
+    def recover(self, centres, radii=None, half_extents=None, rotations=None, half_heights=None, skin=0.01, max_iterations=4, ignore_body=None,
+                synchronize=False):
+        """Push each of n spheres, oriented boxes or capsules (overlap()'s shape arguments) out of everything it overlaps in the last query_build()
+        (nh_recover): at most `max_iterations` (0 .. NH_RECOVER_MAX_ITERATIONS; a number or n values) pushes, each out of the deepest collider and
+        `skin` (a number or n values, in world units: scale it to the scene) further.  `ignore_body`: None, a body index, or n of them.
+        Returns a dict of device tensors: position (n, 3), push (n, 3; position - centre), flags (n, int64; NH_RECOVER_*: without OVERLAPPING,
+        TOUCHING and INVALID the shape is free at `position`), iterations (n, int64), `last` (the deepest pair of the last walk that found one:
+        normal, depth, body, collider, shape, tag; 0xffffffff = none) and `raw`, the nh_RecoverResult records.  Nothing waits for the device
+        unless `synchronize`."""
+        torch = self.torch
+        q, n = self._overlap_queries("recover", centres, radii, half_extents, rotations, ignore_body, half_heights)
+        rec = torch.zeros((n, 16), dtype=torch.float32, device=self.dev)
+        rec[:, 0:12] = q
+        rec[:, 12] = torch.as_tensor(skin, dtype=torch.float32, device=self.dev)
+        rec.view(torch.int32)[:, 13] = torch.as_tensor(max_iterations, dtype=torch.int64, device=self.dev).to(torch.int32)
+        raw = self.recover_records(rec)
+        f = raw.view(torch.float32).reshape(n, 16)
+        u = raw.view(torch.int32).reshape(n, 16).to(torch.int64) & 0xFFFFFFFF
+        last = dict(normal=f[:, 8:11], depth=f[:, 11], body=u[:, 12], collider=u[:, 13], shape=u[:, 14], tag=u[:, 15])
+        out = dict(position=f[:, 0:3], push=f[:, 4:7], flags=u[:, 3], iterations=u[:, 7], last=last, raw=raw)
         if synchronize:
             torch.cuda.current_stream(self.dev).synchronize()
         return out
