@@ -12,6 +12,7 @@
 // Sections 1-10 are the kernels in the order a full step launches them, 11 the entry points, 12 the host side of one call.  (nh_append_contacts: nh_append.hip)
 #include "nh_internal.h"
 #include "nh_narrowphase.h"
+#include "nh_still.h"
 #include <type_traits>
 #include "nh_solver.h"          // (nh_is_inert: k_pair_begin checks body 0 for the step it opens)
 #include <stdlib.h>
@@ -87,17 +88,13 @@ __global__ __launch_bounds__(1024) void k_xform(nh_DevState* __restrict__ st,
 			if (red[0]) atomicMax(&st->max_idle[parity], red[0]);
 			if (s_asleep) atomicAdd(&st->still_asleep[parity], s_asleep);
 			if (blockIdx.x == 0) {
-				// what the NEXT step (the other parity) accumulates into: nobody touches it during this one
-				st->max_idle[parity ^ 1u] = 0u; st->delta_count[parity ^ 1u] = 0u; st->delta_overflow[parity ^ 1u] = 0u; st->still_esc[parity ^ 1u] = 0u;
-				st->still_asleep[parity ^ 1u] = 0u; st->still_sleeping[parity ^ 1u] = 0u; st->still_culled[parity ^ 1u] = 0u;
-				for (int k = 0; k < 3; ++k) { st->still_smin[parity ^ 1u][k] = 0xffffffffu; st->still_smax[parity ^ 1u][k] = 0u; }
+				nh_still_open_next(st, parity ^ 1u);
 				st->still_fat0 = st->fat_count + st->fat_count_sph;          // (nobody appends to the kept list while this kernel runs: k_reinsert's verdict needs a value that stands still)
 			}
 		}
 		// (sleepers form: where THIS step's narrowphase counts its sleeping pairs)
 		if (awake_out && blockIdx.x == 0 && threadIdx.x < NH_SLEEP_PARTS * 2u) (&st->sleep_part[parity][0][0])[threadIdx.x] = 0u;
-		// (xform ahead, nh_internal.h: what this step's solver may gather for the next step)
-		if (blockIdx.x == 0 && threadIdx.x < NH_AHEAD_PARTS * 8u) (&st->ahead_part[parity ^ 1u][0][0])[threadIdx.x] = (threadIdx.x & 7u) < 3u ? 0xffffffffu : 0u;
+		if (blockIdx.x == 0) nh_ahead_parts_reset(st, parity ^ 1u, threadIdx.x, 1024u);
 		__syncthreads();
 		if (threadIdx.x < 3) { red[threadIdx.x] = 0xffffffffu; red[3 + threadIdx.x] = 0u; }
 		__syncthreads();
@@ -107,40 +104,31 @@ __global__ __launch_bounds__(1024) void k_xform(nh_DevState* __restrict__ st,
 			const float4 omin = aabb_min[c];
 			const uint32_t omark = reinterpret_cast<const uint32_t*>(aabb_max)[4u * (size_t)c + 3u], ob = __float_as_uint(omin.w);
 			if (omark == 1u && ob != 0u && ob < nbodies && idle[ob] == 0xffu) {
-				uint32_t f;
-				f = nh_float_flip(omin.x); lmin[0] = min(lmin[0], f); lmax[0] = max(lmax[0], f);
-				f = nh_float_flip(omin.y); lmin[1] = min(lmin[1], f); lmax[1] = max(lmax[1], f);
-				f = nh_float_flip(omin.z); lmin[2] = min(lmin[2], f); lmax[2] = max(lmax[2], f);
+				nh_bounds_fold(lmin, lmax, omin.x, omin.y, omin.z);
 				continue;
 			}
 		}
 		bool is_box = c < nbox;
 		nh_Transform l = is_box ? box_xf[c] : sph_xf[c - nbox];
 		nh_Transform b = body_xf[l.body];
-		// Transform * Transform (nudge.cpp:1165-1175)
-		nh_quat bq = { b.rotation[0], b.rotation[1], b.rotation[2], b.rotation[3] };
-		nh_quat lq = { l.rotation[0], l.rotation[1], l.rotation[2], l.rotation[3] };
-		nh_f3 p = nh_rotate(bq, nh_make3(l.position[0], l.position[1], l.position[2])) + nh_make3(b.position[0], b.position[1], b.position[2]);
-		nh_quat q = nh_qmul(bq, lq);
+		nh_f3 p, mn3, mx3;
+		nh_quat q;
+		nh_collider_pose(b.position, b.rotation, l.position, l.rotation, p, q);
 		nh_xform w;
 		w.px = p.x; w.py = p.y; w.pz = p.z; w.body = l.body;
 		w.qx = q.x; w.qy = q.y; w.qz = q.z; w.qs = q.s;
 		float sx, sy, sz;
 		if (is_box) {
-			// |R| * size (nudge.cpp:3027-3037)
-			nh_m33 m = nh_matrix(q);
 			nh_BoxCollider bc = box_data[c];
-			nh_f3 c0 = m.c0 * bc.size[0], c1 = m.c1 * bc.size[1], c2 = m.c2 * bc.size[2];
-			sx = fabsf(c0.x) + fabsf(c1.x) + fabsf(c2.x);
-			sy = fabsf(c0.y) + fabsf(c1.y) + fabsf(c2.y);
-			sz = fabsf(c0.z) + fabsf(c1.z) + fabsf(c2.z);
+			const nh_f3 reach = nh_box_reach(q, nh_make3(bc.size[0], bc.size[1], bc.size[2]));
+			sx = reach.x; sy = reach.y; sz = reach.z;
 			ctag[c] = box_tags[c];
 		} else {
 			sx = sy = sz = sph_data[c - nbox].radius;
 			ctag[c] = sph_tags[c - nbox];
 		}
-		float mnx = p.x - sx, mny = p.y - sy, mnz = p.z - sz;
-		float mxx = p.x + sx, mxy = p.y + sy, mxz = p.z + sz;
+		nh_aabb_of(p, nh_make3(sx, sy, sz), mn3, mx3);
+		const float mnx = mn3.x, mny = mn3.y, mnz = mn3.z, mxx = mx3.x, mxy = mx3.y, mxz = mx3.z;
 		float ext = fmaxf(fmaxf(mxx - mnx, mxy - mny), mxz - mnz);
 		xf[c] = w;
 		aabb_min[c] = make_float4(mnx, mny, mnz, __uint_as_float(l.body));
@@ -175,17 +163,12 @@ __global__ __launch_bounds__(1024) void k_xform(nh_DevState* __restrict__ st,
 			}
 		}
 		escaped |= out;
-		uint32_t f;
-		f = nh_float_flip(mnx); lmin[0] = min(lmin[0], f); lmax[0] = max(lmax[0], f);
-		f = nh_float_flip(mny); lmin[1] = min(lmin[1], f); lmax[1] = max(lmax[1], f);
-		f = nh_float_flip(mnz); lmin[2] = min(lmin[2], f); lmax[2] = max(lmax[2], f);
+		nh_bounds_fold(lmin, lmax, mnx, mny, mnz);
 		// exponent histogram: one LDS atomic per distinct exponent in the wave (usually 2-3), not one per lane
 		if (STILL) continue;
 		uint32_t ebin = (__float_as_uint(fext) >> 21) & 1023u;          // size class: exponent + two mantissa bits (quarter octaves)
 		if (ebin <= guess_exp && fext == fext) {
-			f = nh_float_flip(fx0); gmn[0] = min(gmn[0], f); gmx[0] = max(gmx[0], f);
-			f = nh_float_flip(fy0); gmn[1] = min(gmn[1], f); gmx[1] = max(gmx[1], f);
-			f = nh_float_flip(fz0); gmn[2] = min(gmn[2], f); gmx[2] = max(gmx[2], f);
+			nh_bounds_fold(gmn, gmx, fx0, fy0, fz0);
 		}
 		unsigned long long todo = __ballot(1);
 		while (todo) {
@@ -503,8 +486,7 @@ __device__ __forceinline__ void emit_pair(nh_DevState* st, uint2* pairs, uint32_
 	if (!bal) return;
 	if (hit && islands && body_a && body_b && (idle[body_a] == 0xff || idle[body_b] == 0xff)) uf_union(islands, body_a, body_b);
 	if (hit) {
-		bool a_first = (ka < kb) || (ka == kb && ca < cb);
-		// narrowphase "a" = later in Morton order (nudge.cpp:3495, 1202-1203)
+		const bool a_first = nh_a_is_first(ka, kb, ca, cb);
 		ps.buf[ps.count + (uint32_t)__popcll(bal & ((1ull << nh_lane()) - 1ull))] = a_first ? make_uint2(cb, ca) : make_uint2(ca, cb);
 	}
 	ps.count += (uint32_t)__popcll(bal);
@@ -932,8 +914,8 @@ __global__ __launch_bounds__(256) void k_kept_filter(nh_DevState* __restrict__ s
 		if (in_place) {
 			if (hit && islands && abody && bbody && (idle[abody] == 0xff || idle[bbody] == 0xff)) uf_union(islands, abody, bbody);
 			if (i < n) {
-				const bool a_first = (ka < kb) || (ka == kb && ca < cb);
-				const uint2 out = hit ? (a_first ? make_uint2(cb, ca) : make_uint2(ca, cb)) : make_uint2(NH_PAIR_INVALID, NH_PAIR_INVALID);       // narrowphase "a" = later in Morton order (emit_pair)
+				const bool a_first = nh_a_is_first(ka, kb, ca, cb);
+				const uint2 out = hit ? (a_first ? make_uint2(cb, ca) : make_uint2(ca, cb)) : make_uint2(NH_PAIR_INVALID, NH_PAIR_INVALID);
 				pairs[i < n_bb ? i : pair_cap - 1u - (i - n_bb)] = out;
 			}
 		} else {
@@ -988,13 +970,12 @@ __global__ __launch_bounds__(256) void k_narrowphase(nh_DevState* __restrict__ s
                                                      // asleep now is what it was -- counted, nothing else fetched (30 bytes per pair instead of 230)
                                                      uint32_t quick_sleepers = 0u) {
 	if (STILL && !LOCAL && ahead) {
-		// what k_xform<true> does for the step after this one (nobody touches the other parity's words during this step: the solver that gathers into them comes later)
+		// (no k_xform<true> this step: the next step's words are opened here)
 		if (blockIdx.x == 0 && threadIdx.x == 0) {
-			st->max_idle[parity ^ 1u] = 0u; st->delta_count[parity ^ 1u] = 0u; st->delta_overflow[parity ^ 1u] = 0u; st->still_esc[parity ^ 1u] = 0u;
-			st->still_asleep[parity ^ 1u] = 0u; st->still_sleeping[parity ^ 1u] = 0u; st->still_culled[parity ^ 1u] = 0u;
-			for (int k = 0; k < 3; ++k) { st->still_smin[parity ^ 1u][k] = 0xffffffffu; st->still_smax[parity ^ 1u][k] = 0u; }
+			nh_still_open_next(st, parity ^ 1u);
 			st->still_fat0 = st->fat_count + st->fat_count_sph;
 		}
+		// (the same store as nh_ahead_parts_reset)
 		if (blockIdx.x == 0) for (uint32_t k = threadIdx.x; k < NH_AHEAD_PARTS * 8u; k += blockDim.x) (&st->ahead_part[parity ^ 1u][0][0])[k] = (k & 7u) < 3u ? 0xffffffffu : 0u;
 		// ... and what it would have found: a collider outside its inflated box, a body asleep (the solver lane that advanced the body saw it), a world the lanes cannot
 		// stand in for k_xform in -- this step has not happened (every workgroup reads the same words and comes to the same verdict)
@@ -1024,17 +1005,14 @@ __global__ __launch_bounds__(256) void k_narrowphase(nh_DevState* __restrict__ s
 	uint2 kp_first = make_uint2(0u, 0u);
 	auto still_frame = [&]() {
 		if (!LOCAL && ahead) {
-			for (int k = 0; k < 3; ++k)
-				for (int d = 32; d >= 1; d >>= 1) { fr_min[k] = min(fr_min[k], (uint32_t)__shfl_xor((int)fr_min[k], d)); fr_max[k] = max(fr_max[k], (uint32_t)__shfl_xor((int)fr_max[k], d)); }
-			for (int d = 32; d >= 1; d >>= 1) fr_top = max(fr_top, (uint32_t)__shfl_xor((int)fr_top, d));
+			nh_pair_frame_reduce(fr_min, fr_max, fr_top);
 			// (the first wave files the result where a step with a k_xform<true> of its own would have it: the host's mirror, the sleep prediction)
 			if (blockIdx.x == 0 && threadIdx.x == 0) {
 				for (int k = 0; k < 3; ++k) { st->still_smin[parity][k] = fr_min[k]; st->still_smax[parity][k] = fr_max[k]; }
 				st->max_idle[parity] = fr_top;
 			}
 		}
-		const nh_f3 smin = nh_make3(nh_float_unflip(fr_min[0]), nh_float_unflip(fr_min[1]), nh_float_unflip(fr_min[2]));
-		const nh_f3 smax = nh_make3(nh_float_unflip(fr_max[0]), nh_float_unflip(fr_max[1]), nh_float_unflip(fr_max[2]));
+		const nh_f3 smin = nh_bounds_corner(fr_min), smax = nh_bounds_corner(fr_max);
 		mscale = nh_morton_scale(smin, smax);
 		mmin = nh_make3(smin.x * mscale, smin.y * mscale, smin.z * mscale);
 	};
@@ -1043,8 +1021,8 @@ __global__ __launch_bounds__(256) void k_narrowphase(nh_DevState* __restrict__ s
 	if (STILL) {
 		for (int k = 0; k < 3; ++k) { fr_min[k] = st->still_smin[parity][k]; fr_max[k] = st->still_smax[parity][k]; }
 		if (!LOCAL && ahead) {
-			// the bounds (and the largest idle counter) the last step's solver lanes gathered in NH_AHEAD_PARTS places, the static world's share beside them: asked for
-			// here, put together by every wave for itself (still_frame) once its lanes' first kept pairs are on their way as well
+			// the frame's parts are asked for here and put together by every wave for itself (still_frame) once its lanes' first kept pairs are on their way as well
+			// (the same three lines as nh_pair_frame_fetch)
 			const uint32_t* part = &st->ahead_part[parity][nh_lane() & (NH_AHEAD_PARTS - 1u)][0];
 			fr_top = part[6];
 			for (int k = 0; k < 3; ++k) { fr_min[k] = min(part[k], st->still_static_min[k]); fr_max[k] = max(part[3 + k], st->still_static_max[k]); }
@@ -1165,6 +1143,7 @@ __global__ __launch_bounds__(256) void k_narrowphase(nh_DevState* __restrict__ s
 					if (app || (__float_as_uint(amin.w) != 0u && __float_as_uint(bmin.w) != 0u)) { changed = true; atomicAdd(&st->still_diff[3], 1u); }
 					else sleeper_pair = true;
 				}
+				// (the same rule as nh_a_is_first)
 				const uint64_t ka = nh_morton_of(nh_make3(amin.x, amin.y, amin.z), mscale, mmin), kb = nh_morton_of(nh_make3(bmin.x, bmin.y, bmin.z), mscale, mmin);
 				const bool a_first = (ka < kb) || (ka == kb && ca < cb);
 				pr = hit ? (a_first ? make_uint2(cb, ca) : make_uint2(ca, cb)) : make_uint2(NH_PAIR_INVALID, NH_PAIR_INVALID);       // narrowphase "a" = later in Morton order (emit_pair)
@@ -1188,6 +1167,7 @@ __global__ __launch_bounds__(256) void k_narrowphase(nh_DevState* __restrict__ s
 					asleep = true;
 				}
 			}
+			// (the same three cases as nh_pair_contacts -- nh_narrowphase.h --, which k_pair_begin calls: here each collider's transform, shape and tag is read by index)
 			if (coarse_asleep) {
 			} else if (!SPH) {
 				nh_xform A = XF(a), B = XF(b);
@@ -1354,10 +1334,7 @@ __global__ __launch_bounds__(256) void k_ahead_check(nh_DevState* __restrict__ s
 		const float4 mn = aabb_min[c];
 		const uint32_t b = __float_as_uint(mn.w);
 		if (b) { multi |= body_col[b] != c; if (!(idle && idle[b] == 0xffu)) continue; }
-		uint32_t f;
-		f = nh_float_flip(mn.x); lmin[0] = min(lmin[0], f); lmax[0] = max(lmax[0], f);
-		f = nh_float_flip(mn.y); lmin[1] = min(lmin[1], f); lmax[1] = max(lmax[1], f);
-		f = nh_float_flip(mn.z); lmin[2] = min(lmin[2], f); lmax[2] = max(lmax[2], f);
+		nh_bounds_fold(lmin, lmax, mn.x, mn.y, mn.z);
 	}
 	if (__ballot(multi) != 0ull && nh_lane() == 0) st->ahead_multi = 1u;          // (plain store of a constant)
 	for (int k = 0; k < 3; ++k) {
@@ -1404,14 +1381,6 @@ __global__ __launch_bounds__(256) void k_pair_list(nh_DevState* __restrict__ st,
 // (hipcc -S --cuda-device-only with the Makefile's flags): in a pair lane's path there must be ONE s_waitcnt vmcnt between the list entry's load and kept / rec_key /
 // lay_rank, ONE between those and the group of 14 to 18 loads that ends with cnt_sorted[pos], and no global_load behind the overlap test other than body_rec's and
 // delta_overflow's (profiles/r09_steady_step_ab.log lists the trips).
-__device__ __forceinline__ void nh_pair_frame(const nh_DevState* __restrict__ st, uint32_t parity, uint32_t lane, uint32_t (&fr_min)[3], uint32_t (&fr_max)[3], uint32_t& fr_top) {
-	const uint32_t* part = &st->ahead_part[parity][lane & (NH_AHEAD_PARTS - 1u)][0];
-	fr_top = part[6];
-	for (int k = 0; k < 3; ++k) { fr_min[k] = min(part[k], st->still_static_min[k]); fr_max[k] = max(part[3 + k], st->still_static_max[k]); }
-	for (int k = 0; k < 3; ++k)
-		for (int d = 32; d >= 1; d >>= 1) { fr_min[k] = min(fr_min[k], (uint32_t)__shfl_xor((int)fr_min[k], d)); fr_max[k] = max(fr_max[k], (uint32_t)__shfl_xor((int)fr_max[k], d)); }
-	for (int d = 32; d >= 1; d >>= 1) fr_top = max(fr_top, (uint32_t)__shfl_xor((int)fr_top, d));
-}
 __global__ __launch_bounds__(64) void k_pair_begin(nh_DevState* __restrict__ st, uint32_t parity, uint32_t seq, const uint32_t* __restrict__ list, uint32_t list_cap,
                                                    const uint2* __restrict__ kept, uint32_t kept_cap, uint32_t pair_cap, const uint8_t* __restrict__ gen,
                                                    const nh_xform* __restrict__ xf, const float4* __restrict__ aabb_min, const float4* __restrict__ aabb_max, const uint32_t* __restrict__ ctag,
@@ -1435,11 +1404,10 @@ __global__ __launch_bounds__(64) void k_pair_begin(nh_DevState* __restrict__ st,
 		const uint32_t fat_count = st->fat_count, fat_count_sph = st->fat_count_sph, n_pairs = st->pairs, n_pairs_sph = st->pairs_sph;
 		const uint32_t active = st->active, sleeping = st->sleeping, culled = st->culled;
 		uint32_t fr_min[3], fr_max[3], fr_top;
-		nh_pair_frame(st, parity, lane, fr_min, fr_max, fr_top);
-		const float mscale = nh_morton_scale(nh_make3(nh_float_unflip(fr_min[0]), nh_float_unflip(fr_min[1]), nh_float_unflip(fr_min[2])),
-		                                     nh_make3(nh_float_unflip(fr_max[0]), nh_float_unflip(fr_max[1]), nh_float_unflip(fr_max[2])));
-		const float scale_was = nh_morton_scale(nh_make3(nh_float_unflip(was_min[0]), nh_float_unflip(was_min[1]), nh_float_unflip(was_min[2])),
-		                                        nh_make3(nh_float_unflip(was_max[0]), nh_float_unflip(was_max[1]), nh_float_unflip(was_max[2])));
+		nh_pair_frame_fetch(st, parity, lane, fr_min, fr_max, fr_top);
+		nh_pair_frame_reduce(fr_min, fr_max, fr_top);
+		const float mscale = nh_morton_scale(nh_bounds_corner(fr_min), nh_bounds_corner(fr_max));
+		const float scale_was = nh_morton_scale(nh_bounds_corner(was_min), nh_bounds_corner(was_max));
 		const bool inert = nh_is_inert(m0.velocity, m0.angular_velocity, p0.inertia_inverse, p0.mass_inverse);
 		const bool bad = ahead_failed_seq >= seq || ahead_multi != 0u || !lay_valid || fat_count != n_pairs || fat_count_sph != n_pairs_sph ||
 		                 n_list > list_cap || !(mscale >= 0.75f * scale_was) || !inert;
@@ -1458,13 +1426,10 @@ __global__ __launch_bounds__(64) void k_pair_begin(nh_DevState* __restrict__ st,
 				if (asleep) top = 0xffu;
 			}
 			st->max_idle[parity] = top;
-			// what k_xform<true> does for the step after this one
-			st->max_idle[op] = 0u; st->delta_count[op] = 0u; st->delta_overflow[op] = 0u; st->still_esc[op] = 0u;
-			st->still_asleep[op] = 0u; st->still_sleeping[op] = 0u; st->still_culled[op] = 0u;
-			for (int k = 0; k < 3; ++k) { st->still_smin[op][k] = 0xffffffffu; st->still_smax[op][k] = 0u; }
+			nh_still_open_next(st, op);
 			st->still_fat0 = fat_count + fat_count_sph;
 		}
-		for (uint32_t k = lane; k < NH_AHEAD_PARTS * 8u; k += 64u) (&st->ahead_part[op][0][0])[k] = (k & 7u) < 3u ? 0xffffffffu : 0u;
+		nh_ahead_parts_reset(st, op, lane, 64u);
 		if (sleepers_bodies) for (uint32_t k = lane; k < NH_SLEEP_PARTS * 2u; k += 64u) (&st->sleep_part[parity][0][0])[k] = 0u;          // (no narrowphase adds to them in such a step)
 		return;
 	}
@@ -1475,10 +1440,10 @@ __global__ __launch_bounds__(64) void k_pair_begin(nh_DevState* __restrict__ st,
 	uint32_t r = list[min(j, list_cap - 1u)];
 	const uint32_t n_list = st->pair_unowned, n_pairs = st->pairs, moved = st->moved_count;
 	uint32_t fr_min[3], fr_max[3], fr_top;
-	nh_pair_frame(st, parity, lane, fr_min, fr_max, fr_top);
+	nh_pair_frame_fetch(st, parity, lane, fr_min, fr_max, fr_top);
+	nh_pair_frame_reduce(fr_min, fr_max, fr_top);
 	asm volatile("" :: "s"(n_list), "s"(n_pairs), "s"(moved), "v"(r));          // (asked for with the parts, not behind their reduction)
-	const nh_f3 smin = nh_make3(nh_float_unflip(fr_min[0]), nh_float_unflip(fr_min[1]), nh_float_unflip(fr_min[2]));
-	const nh_f3 smax = nh_make3(nh_float_unflip(fr_max[0]), nh_float_unflip(fr_max[1]), nh_float_unflip(fr_max[2]));
+	const nh_f3 smin = nh_bounds_corner(fr_min), smax = nh_bounds_corner(fr_max);
 	const float mscale = nh_morton_scale(smin, smax);
 	const nh_f3 mmin = nh_make3(smin.x * mscale, smin.y * mscale, smin.z * mscale);
 	const uint32_t n = min(n_list, list_cap);
@@ -1526,32 +1491,15 @@ __global__ __launch_bounds__(64) void k_pair_begin(nh_DevState* __restrict__ st,
 			nh_contact_out single;
 			single.px = single.py = single.pz = single.penetration = single.nx = single.ny = single.nz = 0.0f; single.friction = 0.5f; single.feature = 0u;
 			if (hit) {
-				const uint64_t ka = nh_morton_of(nh_make3(amin.x, amin.y, amin.z), mscale, mmin), kb = nh_morton_of(nh_make3(bmin.x, bmin.y, bmin.z), mscale, mmin);
-				const bool a_first = (ka < kb) || (ka == kb && ca < cb);
-				// narrowphase "a" = later in Morton order (emit_pair)
+				const bool a_first = nh_a_is_first(amin, bmin, ca, cb, mscale, mmin);
 				const nh_xform A = a_first ? XB : XA, B = a_first ? XA : XB;
 				const uint32_t ta = a_first ? tcb : tca, tb = a_first ? tca : tcb;
 				const bool a_sph = a_first ? cb_sph : ca_sph, b_sph = a_first ? ca_sph : cb_sph;
 				const nh_BoxCollider sa = a_first ? szb : sza, sb = a_first ? sza : szb;
 				const float ra = a_first ? radb : rada, rb = a_first ? rada : radb;
-				if (!a_sph && !b_sph) {
-					nh_box_box_eval(A, B, sa.size, sb.size, ta, tb, bb);
-					count = nh_bb_count(bb);
-					key = (uint64_t)(bb.swapped ? tb : ta) | ((uint64_t)(bb.swapped ? ta : tb) << 32);
-					body_a = bb.swapped ? B.body : A.body; body_b = bb.swapped ? A.body : B.body;
-				} else if (a_sph && b_sph) {
-					count = nh_sphere_sphere(rb, ra, B, A, &single);
-					key = (uint64_t)tb | ((uint64_t)ta << 32);
-					body_a = B.body; body_b = A.body;
-				} else {
-					const nh_BoxCollider sz = a_sph ? sb : sa;
-					const nh_xform BX = a_sph ? B : A, SP = a_sph ? A : B;
-					count = nh_box_sphere(sz.size, a_sph ? ra : rb, BX, SP, &single);
-					key = (uint64_t)(a_sph ? tb : ta) | ((uint64_t)(a_sph ? ta : tb) << 32);
-					body_a = BX.body; body_b = SP.body;
-				}
+				count = nh_pair_contacts(A, B, sa.size, sb.size, ra, rb, ta, tb, a_sph, b_sph, bb, single, key, body_a, body_b);
 			}
-			// still_record (k_narrowphase): the key on file -- or the pair gone --, at most four contacts, and a pair WITH contacts joins a dynamic body to the static world and
+			// what the step relies on, per record (k_narrowphase: still_record): the key on file -- or the pair gone --, at most four contacts, and a pair WITH contacts joins a dynamic body to the static world and
 			// is that body's own record (a ghost's, in a partitioned world: its lane solves it, this launch evaluates it)
 			bool ok = (was_key == key || !hit) && count <= 4;
 			if (ok && count) {
@@ -1597,7 +1545,7 @@ __global__ __launch_bounds__(64) void k_pair_begin(nh_DevState* __restrict__ st,
 	if (__ballot(changed) != 0ull && lane == 0) atomicMax(&st->still_failed_seq, seq);
 }
 
-// Asleep steps (nh_internal.h: nh_AsleepState): is every collider's world AABB (k_xform's arithmetic, bit for bit) and tag what it was when the world was found asleep,
+// Asleep steps (nh_internal.h: nh_AsleepState): is every collider's world AABB and tag what it was when the world was found asleep,
 // and every body still asleep?  One lane per collider / body; any difference raises st->asleep_failed.
 __global__ __launch_bounds__(256) void k_asleep_check(nh_DevState* __restrict__ st, const nh_Transform* __restrict__ body_xf, const uint8_t* __restrict__ idle, uint32_t nbodies,
                                                       const nh_Transform* __restrict__ box_xf, const nh_BoxCollider* __restrict__ box_data, const uint32_t* __restrict__ box_tags, uint32_t nbox,
@@ -1611,26 +1559,23 @@ __global__ __launch_bounds__(256) void k_asleep_check(nh_DevState* __restrict__ 
 		const nh_Transform l = is_box ? box_xf[c] : sph_xf[c - nbox];
 		if (l.body >= nbodies) { differs = true; continue; }
 		const nh_Transform b = body_xf[l.body];
-		const nh_quat bq = { b.rotation[0], b.rotation[1], b.rotation[2], b.rotation[3] };
-		const nh_quat lq = { l.rotation[0], l.rotation[1], l.rotation[2], l.rotation[3] };
-		const nh_f3 p = nh_rotate(bq, nh_make3(l.position[0], l.position[1], l.position[2])) + nh_make3(b.position[0], b.position[1], b.position[2]);
-		const nh_quat q = nh_qmul(bq, lq);
+		nh_f3 p, mn3, mx3;
+		nh_quat q;
+		nh_collider_pose(b.position, b.rotation, l.position, l.rotation, p, q);
 		float sx, sy, sz;
 		uint32_t tag;
 		if (is_box) {
-			const nh_m33 m = nh_matrix(q);
 			const nh_BoxCollider bc = box_data[c];
-			const nh_f3 c0 = m.c0 * bc.size[0], c1 = m.c1 * bc.size[1], c2 = m.c2 * bc.size[2];
-			sx = fabsf(c0.x) + fabsf(c1.x) + fabsf(c2.x);
-			sy = fabsf(c0.y) + fabsf(c1.y) + fabsf(c2.y);
-			sz = fabsf(c0.z) + fabsf(c1.z) + fabsf(c2.z);
+			const nh_f3 reach = nh_box_reach(q, nh_make3(bc.size[0], bc.size[1], bc.size[2]));
+			sx = reach.x; sy = reach.y; sz = reach.z;
 			tag = box_tags[c];
 		} else {
 			sx = sy = sz = sph_data[c - nbox].radius;
 			tag = sph_tags[c - nbox];
 		}
 		const float4 mn = was_min[c], mx = was_max[c];
-		const float mnx = p.x - sx, mny = p.y - sy, mnz = p.z - sz, mxx = p.x + sx, mxy = p.y + sy, mxz = p.z + sz;
+		nh_aabb_of(p, nh_make3(sx, sy, sz), mn3, mx3);
+		const float mnx = mn3.x, mny = mn3.y, mnz = mn3.z, mxx = mx3.x, mxy = mx3.y, mxz = mx3.z;
 		differs |= __float_as_uint(mnx) != __float_as_uint(mn.x) || __float_as_uint(mny) != __float_as_uint(mn.y) || __float_as_uint(mnz) != __float_as_uint(mn.z) ||
 		           __float_as_uint(mxx) != __float_as_uint(mx.x) || __float_as_uint(mxy) != __float_as_uint(mx.y) || __float_as_uint(mxz) != __float_as_uint(mx.z) ||
 		           __float_as_uint(mn.w) != l.body || tag != was_tag[c];
@@ -1949,9 +1894,8 @@ __global__ __launch_bounds__(256) void k_collide_begin(nh_DevState* st, uint32_t
 	if (blockIdx.x == 0 && threadIdx.x == 0) {
 		st->any_idle[parity ^ 1u] = 0;
 		// (what a still step of the other parity -- the next step, if the host launches it as one -- accumulates into, and the verdict on this step's layout)
-		st->max_idle[parity ^ 1u] = 0u; st->lay_valid = 0u; st->lay_in_place = 0u; st->delta_count[parity ^ 1u] = 0u; st->delta_overflow[parity ^ 1u] = 0u; st->still_esc[parity ^ 1u] = 0u;
-		st->still_asleep[parity ^ 1u] = 0u; st->still_sleeping[parity ^ 1u] = 0u; st->still_culled[parity ^ 1u] = 0u;
-		for (int k = 0; k < 3; ++k) { st->still_smin[parity ^ 1u][k] = 0xffffffffu; st->still_smax[parity ^ 1u][k] = 0u; }
+		st->lay_valid = 0u; st->lay_in_place = 0u;
+		nh_still_open_next(st, parity ^ 1u);
 	}
 	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < NH_DEG_WORDS(nbodies); i += gridDim.x * blockDim.x) deg[i] = 0;      // degrees, pair counters, first contacts (NH_DEG_STRIDE)
 	if (blockIdx.x != 0) return;

@@ -213,4 +213,38 @@ NH_HD uint64_t nh_morton_of(nh_f3 p, float scale, nh_f3 smin_scaled) {
 	return nh_morton48(qx, qy, qz);
 }
 
+// Which collider of a pair plays "a" in the narrowphase: the one LATER in the Morton order of the AABB min corners (nudge.cpp:3495, 1202-1203); on equal keys
+// the lower collider index comes first.  true: ca comes first, so cb is "a".
+NH_HD bool nh_a_is_first(uint64_t ka, uint64_t kb, uint32_t ca, uint32_t cb) { return (ka < kb) || (ka == kb && ca < cb); }
+NH_HD bool nh_a_is_first(nh_f3 amin, nh_f3 bmin, uint32_t ca, uint32_t cb, float mscale, nh_f3 mmin) {
+	return nh_a_is_first(nh_morton_of(amin, mscale, mmin), nh_morton_of(bmin, mscale, mmin), ca, cb);
+}
+
+// ---- a collider's world pose and AABB, stated once: the full step's k_xform, the ghosts' and the asleep world's kernels call these, the scene query under its
+// own names (nh_query.h) and tests/hostsim too, so they agree to the bit (the still solver's lanes keep the same lines of their own: docs/KERNELS.md) ----
+// Transform * Transform of the body and the collider's local transform (nudge.cpp:1165-1175)
+NH_HD void nh_collider_pose(nh_quat bq, nh_f3 bp, nh_quat lq, nh_f3 lp, nh_f3& p, nh_quat& q) {
+	p = nh_rotate(bq, lp) + bp;
+	q = nh_qmul(bq, lq);
+}
+// (the same from the position[3] / rotation[4] of two nh_Transform)
+NH_HD void nh_collider_pose(const float bpos[3], const float brot[4], const float lpos[3], const float lrot[4], nh_f3& p, nh_quat& q) {
+	const nh_quat bq = { brot[0], brot[1], brot[2], brot[3] };
+	const nh_quat lq = { lrot[0], lrot[1], lrot[2], lrot[3] };
+	nh_collider_pose(bq, nh_make3(bpos[0], bpos[1], bpos[2]), lq, nh_make3(lpos[0], lpos[1], lpos[2]), p, q);
+}
+
+// World AABB half extents of a box: |R| * size (nudge.cpp:3027-3037)
+NH_HD nh_f3 nh_box_reach(nh_quat q, nh_f3 size) {
+	const nh_m33 m = nh_matrix(q);
+	const nh_f3 c0 = m.c0 * size.x, c1 = m.c1 * size.y, c2 = m.c2 * size.z;
+	return nh_make3(fabsf(c0.x) + fabsf(c1.x) + fabsf(c2.x), fabsf(c0.y) + fabsf(c1.y) + fabsf(c2.y), fabsf(c0.z) + fabsf(c1.z) + fabsf(c2.z));
+}
+
+// The world AABB: centre -+ reach
+NH_HD void nh_aabb_of(nh_f3 p, nh_f3 reach, nh_f3& mn, nh_f3& mx) {
+	mn = nh_make3(p.x - reach.x, p.y - reach.y, p.z - reach.z);
+	mx = nh_make3(p.x + reach.x, p.y + reach.y, p.z + reach.z);
+}
+
 #endif

@@ -566,19 +566,24 @@ NH_HD void nh_box_box_eval(nh_xform A, nh_xform B, const float* size_a, const fl
 	res.swapped = swapped;
 }
 
-// Convenience wrapper (host-side unit tests): materialises the contacts into out[], in candidate order.
+// The contacts of a box-box result, materialised into out[] in candidate order (host-side unit tests; the kernels walk the mask themselves, writing as they go)
+NH_HD int nh_bb_contacts(const nh_bb_result& r, nh_contact_out* out) {
+	int count = 0;
+	if (r.kind == 1) out[count++] = r.edge;
+	else if (r.kind == 2) {
+		for (int index = 0; index < 16; ++index) {
+			if (!((r.mask >> index) & 1u)) continue;
+			nh_bb_contact(r, index, r.fx[index], r.fy[index], r.fz[index], r.penetration[index], r.tags[index], out[count++]);
+		}
+	}
+	return count;
+}
+// Convenience wrapper (host-side unit tests): the box-box test with its contacts in out[]
 NH_HD nh_pair_result nh_box_box(nh_xform A, nh_xform B, const float* size_a, const float* size_b,
                                 uint32_t tag_a, uint32_t tag_b, nh_contact_out* out) {
 	nh_bb_result r;
 	nh_box_box_eval(A, B, size_a, size_b, tag_a, tag_b, r);
-	nh_pair_result res = { 0, r.swapped };
-	if (r.kind == 1) { out[0] = r.edge; res.count = 1; }
-	else if (r.kind == 2) {
-		for (int index = 0; index < 16; ++index) {
-			if (!((r.mask >> index) & 1u)) continue;
-			nh_bb_contact(r, index, r.fx[index], r.fy[index], r.fz[index], r.penetration[index], r.tags[index], out[res.count++]);
-		}
-	}
+	nh_pair_result res = { nh_bb_contacts(r, out), r.swapped };
 	return res;
 }
 
@@ -645,6 +650,32 @@ NH_HD int nh_box_sphere(const float* size, float radius, const nh_xform& A, cons
 	out->friction = 0.5f;
 	out->feature = 0;
 	return 1;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// One pair by shape: its contacts (box-box: in `bb`, not materialised; with a sphere: at most one, in `single`), its key (the tag of the contacts' "a" low,
+// of their "b" high) and its two bodies in that order.  (A, size_a / ra, ta) is the pair's "a" = the collider LATER in Morton order (nh_a_is_first), a size for
+// a box and a radius for a sphere.  Who is the CONTACTS' "a": box-box -- whom the SAT picks (bb.swapped); sphere-sphere -- the collider EARLIER in Morton order,
+// the pair's b (nudge.cpp:3775-3776); box-sphere -- the box (nudge.cpp:3746-3751, 3759-3768).
+NH_HD int nh_pair_contacts(const nh_xform& A, const nh_xform& B, const float* size_a, const float* size_b, float ra, float rb, uint32_t ta, uint32_t tb, bool a_sph, bool b_sph,
+                           nh_bb_result& bb, nh_contact_out& single, uint64_t& key, uint32_t& body_a, uint32_t& body_b) {
+	int count;
+	if (!a_sph && !b_sph) {
+		nh_box_box_eval(A, B, size_a, size_b, ta, tb, bb);
+		count = nh_bb_count(bb);
+		key = (uint64_t)(bb.swapped ? tb : ta) | ((uint64_t)(bb.swapped ? ta : tb) << 32);
+		body_a = bb.swapped ? B.body : A.body; body_b = bb.swapped ? A.body : B.body;
+	} else if (a_sph && b_sph) {
+		count = nh_sphere_sphere(rb, ra, B, A, &single);
+		key = (uint64_t)tb | ((uint64_t)ta << 32);
+		body_a = B.body; body_b = A.body;
+	} else {
+		const nh_xform BX = a_sph ? B : A, SP = a_sph ? A : B;
+		count = nh_box_sphere(a_sph ? size_b : size_a, a_sph ? ra : rb, BX, SP, &single);
+		key = (uint64_t)(a_sph ? tb : ta) | ((uint64_t)(a_sph ? ta : tb) << 32);
+		body_a = BX.body; body_b = SP.body;
+	}
+	return count;
 }
 
 #endif

@@ -7,6 +7,7 @@
 // colliders: the static ones the rank keeps | one per dynamic body, in slot order (boxes and spheres each in their own array).
 #include "nh_internal.h"
 #include "nh_math.h"
+#include "nh_still.h"
 #include <math.h>
 #include <string.h>
 
@@ -791,38 +792,31 @@ __global__ __launch_bounds__(256) void k_xform_ghosts(nh_DevState* __restrict__ 
 		const uint32_t cnt = idle[b];
 		top = max(top, cnt); fail |= cnt == 0xffu;
 		const nh_Transform bt = body_xf[b];
-		const nh_quat bq = { bt.rotation[0], bt.rotation[1], bt.rotation[2], bt.rotation[3] };
 		const uint32_t nb = nbx[b], ns = nsp[b];
 		for (uint32_t k = 0; k < nb + ns; ++k) {
 			const bool is_box = k < nb;
 			const uint32_t c = is_box ? n_static_box + s0[b] + k : nbox + n_static_sph + s1[b] + (k - nb);
 			const nh_Transform l = is_box ? box_xf[c] : sph_xf[c - nbox];
-			// Transform * Transform (nudge.cpp:1165-1175), |R| * size (3027-3037): k_xform's lines
-			const nh_quat lq = { l.rotation[0], l.rotation[1], l.rotation[2], l.rotation[3] };
-			const nh_f3 p = nh_rotate(bq, nh_make3(l.position[0], l.position[1], l.position[2])) + nh_make3(bt.position[0], bt.position[1], bt.position[2]);
-			const nh_quat q = nh_qmul(bq, lq);
+			nh_f3 p, mn3, mx3;
+			nh_quat q;
+			nh_collider_pose(bt.position, bt.rotation, l.position, l.rotation, p, q);
 			float sx, sy, sz;
 			if (is_box) {
-				const nh_m33 m = nh_matrix(q);
 				const nh_BoxCollider bc = box_data[c];
-				const nh_f3 c0 = m.c0 * bc.size[0], c1 = m.c1 * bc.size[1], c2 = m.c2 * bc.size[2];
-				sx = fabsf(c0.x) + fabsf(c1.x) + fabsf(c2.x);
-				sy = fabsf(c0.y) + fabsf(c1.y) + fabsf(c2.y);
-				sz = fabsf(c0.z) + fabsf(c1.z) + fabsf(c2.z);
+				const nh_f3 reach = nh_box_reach(q, nh_make3(bc.size[0], bc.size[1], bc.size[2]));
+				sx = reach.x; sy = reach.y; sz = reach.z;
 			} else {
 				sx = sy = sz = sph_data[c - nbox].radius;
 			}
-			const float mnx = p.x - sx, mny = p.y - sy, mnz = p.z - sz, mxx = p.x + sx, mxy = p.y + sy, mxz = p.z + sz;
+			nh_aabb_of(p, nh_make3(sx, sy, sz), mn3, mx3);
+			const float mnx = mn3.x, mny = mn3.y, mnz = mn3.z, mxx = mx3.x, mxy = mx3.y, mxz = mx3.z;
 			xf[2u * (size_t)c] = make_float4(p.x, p.y, p.z, __uint_as_float(l.body));
 			xf[2u * (size_t)c + 1u] = make_float4(q.x, q.y, q.z, q.s);
 			aabb_min[c] = make_float4(mnx, mny, mnz, __uint_as_float(l.body));
 			aabb_max[c] = make_float4(mxx, mxy, mxz, __uint_as_float(0u));
 			const float4 fmn = fat_box[2u * (size_t)c], fmx = fat_box[2u * (size_t)c + 1u];
 			fail |= !(mnx >= fmn.x && mny >= fmn.y && mnz >= fmn.z && mxx <= fmx.x && mxy <= fmx.y && mxz <= fmx.z);       // (NaN: out)
-			uint32_t f;
-			f = nh_float_flip(mnx); lmin[0] = min(lmin[0], f); lmax[0] = max(lmax[0], f);
-			f = nh_float_flip(mny); lmin[1] = min(lmin[1], f); lmax[1] = max(lmax[1], f);
-			f = nh_float_flip(mnz); lmin[2] = min(lmin[2], f); lmax[2] = max(lmax[2], f);
+			nh_bounds_fold(lmin, lmax, mnx, mny, mnz);
 		}
 	}
 	for (int k = 0; k < 3; ++k)

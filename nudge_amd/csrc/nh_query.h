@@ -21,23 +21,15 @@
 
 #include "nh_math.h"
 
-// A collider's world pose: Transform * Transform of the body and the collider's local transform (nudge.cpp:1165-1175), k_xform's arithmetic.
+// A collider's world pose and a box's world AABB half extents under the query layer's names: the step's own functions (nh_math.h), so a query sees the very
+// colliders the step collides
 struct nh_QPose { nh_f3 p; nh_quat q; };
 NH_HD nh_QPose nh_q_pose(const float bpos[3], const float brot[4], const float lpos[3], const float lrot[4]) {
-	const nh_quat bq = { brot[0], brot[1], brot[2], brot[3] };
-	const nh_quat lq = { lrot[0], lrot[1], lrot[2], lrot[3] };
 	nh_QPose w;
-	w.p = nh_rotate(bq, nh_make3(lpos[0], lpos[1], lpos[2])) + nh_make3(bpos[0], bpos[1], bpos[2]);
-	w.q = nh_qmul(bq, lq);
+	nh_collider_pose(bpos, brot, lpos, lrot, w.p, w.q);
 	return w;
 }
-
-// World AABB half extents of a box: |R| * size (nudge.cpp:3027-3037, k_xform)
-NH_HD nh_f3 nh_q_box_extent(nh_quat q, nh_f3 h) {
-	const nh_m33 m = nh_matrix(q);
-	const nh_f3 c0 = m.c0 * h.x, c1 = m.c1 * h.y, c2 = m.c2 * h.z;
-	return nh_make3(nh_abs(c0.x) + nh_abs(c1.x) + nh_abs(c2.x), nh_abs(c0.y) + nh_abs(c1.y) + nh_abs(c2.y), nh_abs(c0.z) + nh_abs(c1.z) + nh_abs(c2.z));
-}
+NH_HD nh_f3 nh_q_box_extent(nh_quat q, nh_f3 h) { return nh_box_reach(q, h); }
 
 struct nh_QHit { float t; nh_f3 n; bool hit; };
 

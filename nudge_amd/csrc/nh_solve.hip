@@ -1091,7 +1091,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MAXC ==
 					const float4 l0 = ah_l0, l1 = ah_l1, fmn = ah_fmn, fmx = ah_fmx;
 					float4 sz = ah_sz;
 					if (!is_box) sz.x = ah_rad;
-					// Transform * Transform (nudge.cpp:1165-1175), |R| * size (3027-3037): k_xform's lines
+					// Transform * Transform (nudge.cpp:1165-1175), |R| * size (3027-3037): the same lines as nh_collider_pose, nh_box_reach and nh_aabb_of (nh_math.h), which k_xform calls
 					const nh_quat bq = { rot[0], rot[1], rot[2], rot[3] };
 					const nh_quat lq = { l1.x, l1.y, l1.z, l1.w };
 					const nh_f3 p = nh_rotate(bq, nh_make3(l0.x, l0.y, l0.z)) + nh_make3(pos[0], pos[1], pos[2]);
@@ -1115,7 +1115,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MAXC ==
 					nfail |= !(mnx >= fmn.x && mny >= fmn.y && mnz >= fmn.z && mxx <= fmx.x && mxy <= fmx.y && mxz <= fmx.z);       // (NaN: out)
 					nmin[0] = nmax[0] = nh_float_flip(mnx); nmin[1] = nmax[1] = nh_float_flip(mny); nmin[2] = nmax[2] = nh_float_flip(mnz);
 					if (PAIR && (pp_bits & 1u)) {
-						// ---- the NEXT step's narrowphase for this body's pair (k_narrowphase<*, true, false>: exact boxes, stamps, roles, contact arithmetic, still_record) ----
+						// ---- the NEXT step's narrowphase for this body's pair (k_narrowphase<*, true, false>: exact boxes, stamps, roles, contact arithmetic, still_record; the contacts by shape: the same three cases as nh_pair_contacts) ----
 						const float4 omin = make_float4(mnx, mny, mnz, l0.w), omax = make_float4(mxx, mxy, mxz, 0.0f);
 						nh_xform OX; OX.px = p.x; OX.py = p.y; OX.pz = p.z; OX.body = __float_as_uint(l0.w); OX.qx = q.x; OX.qy = q.y; OX.qz = q.z; OX.qs = q.s;
 						const bool hit = nh_aabb_overlap(omin, omax, pp_min, pp_max) && __float_as_uint(pp_min.w) != OX.body && !(pp_bits & 2u);

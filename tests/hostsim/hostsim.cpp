@@ -26,26 +26,22 @@ int hs_collide(const Xf* body_xf, uint32_t nbox, const Xf* box_xf, const float* 
 	for (uint32_t i = 0; i < n; ++i) {
 		const Xf& l = i < nbox ? box_xf[i] : sph_xf[i - nbox];
 		const Xf& b = body_xf[l.body];
-		nh_quat bq = { b.q[0], b.q[1], b.q[2], b.q[3] }, lq = { l.q[0], l.q[1], l.q[2], l.q[3] };
-		nh_f3 p = nh_rotate(bq, nh_make3(l.p[0], l.p[1], l.p[2])) + nh_make3(b.p[0], b.p[1], b.p[2]);
-		nh_quat q = nh_qmul(bq, lq);
+		nh_f3 p, reach, lo, hi;
+		nh_quat q;
+		nh_collider_pose(b.p, b.q, l.p, l.q, p, q);
 		xf[i].px = p.x; xf[i].py = p.y; xf[i].pz = p.z; xf[i].body = l.body;
 		xf[i].qx = q.x; xf[i].qy = q.y; xf[i].qz = q.z; xf[i].qs = q.s;
-		float sx, sy, sz;
 		if (i < nbox) {
-			nh_m33 m = nh_matrix(q);
 			const float* s = box_size + 4 * i;
-			nh_f3 c0 = m.c0 * s[0], c1 = m.c1 * s[1], c2 = m.c2 * s[2];
-			sx = fabsf(c0.x) + fabsf(c1.x) + fabsf(c2.x);
-			sy = fabsf(c0.y) + fabsf(c1.y) + fabsf(c2.y);
-			sz = fabsf(c0.z) + fabsf(c1.z) + fabsf(c2.z);
+			reach = nh_box_reach(q, nh_make3(s[0], s[1], s[2]));
 			tags[i] = box_tags[i];
 		} else {
-			sx = sy = sz = sph_radius[i - nbox];
+			reach.x = reach.y = reach.z = sph_radius[i - nbox];
 			tags[i] = sph_tags[i - nbox];
 		}
-		mn[3*i+0] = p.x - sx; mn[3*i+1] = p.y - sy; mn[3*i+2] = p.z - sz;
-		mx[3*i+0] = p.x + sx; mx[3*i+1] = p.y + sy; mx[3*i+2] = p.z + sz;
+		nh_aabb_of(p, reach, lo, hi);
+		mn[3*i+0] = lo.x; mn[3*i+1] = lo.y; mn[3*i+2] = lo.z;
+		mx[3*i+0] = hi.x; mx[3*i+1] = hi.y; mx[3*i+2] = hi.z;
 	}
 	// morton keys
 	nh_f3 smin = nh_make3(mn[0], mn[1], mn[2]), smax = smin;
@@ -65,31 +61,18 @@ int hs_collide(const Xf* body_xf, uint32_t nbox, const Xf* box_xf, const float* 
 		bool ov = mx[3*j] > mn[3*i] && mx[3*i] > mn[3*j] && mx[3*j+1] > mn[3*i+1] && mx[3*i+1] > mn[3*j+1] && mx[3*j+2] > mn[3*i+2] && mx[3*i+2] > mn[3*j+2];
 		if (!ov) continue;
 		if (xf[i].body == xf[j].body) continue;
-		// first = earlier in morton order (ties: lower index)
-		uint32_t first = (mk[i] < mk[j] || (mk[i] == mk[j] && i < j)) ? i : j;
-		uint32_t second = first == i ? j : i;
+		// the pair's "a" = later in morton order (ties: the lower index comes first), then the pair by shape: what the kernels call
+		const bool i_first = nh_a_is_first(mk[i], mk[j], i, j);
+		const uint32_t a = i_first ? j : i, b = i_first ? i : j;
+		const bool a_sph = a >= nbox, b_sph = b >= nbox;
+		const float none[3] = { 0.0f, 0.0f, 0.0f };
 		nh_contact_out out[16];
-		int cnt = 0; uint64_t key = 0; uint32_t ba = 0, bb = 0;
-		bool fs = first >= nbox, ss = second >= nbox;
-		if (!fs && !ss) {
-			// narrowphase a = later in morton order
-			uint32_t a = second, b = first;
-			nh_pair_result r = nh_box_box(xf[a], xf[b], box_size + 4*a, box_size + 4*b, tags[a], tags[b], out);
-			cnt = r.count;
-			uint32_t ca = r.swapped ? b : a, cb = r.swapped ? a : b;
-			key = (uint64_t)tags[ca] | ((uint64_t)tags[cb] << 32);
-			ba = xf[ca].body; bb = xf[cb].body;
-		} else if (fs && ss) {
-			uint32_t a = first, b = second;   // sphere-sphere: a = earlier (pair >> 16)
-			cnt = nh_sphere_sphere(sph_radius[a - nbox], sph_radius[b - nbox], xf[a], xf[b], out);
-			key = (uint64_t)tags[a] | ((uint64_t)tags[b] << 32);
-			ba = xf[a].body; bb = xf[b].body;
-		} else {
-			uint32_t a = fs ? second : first, b = fs ? first : second;   // a = box, b = sphere
-			cnt = nh_box_sphere(box_size + 4*a, sph_radius[b - nbox], xf[a], xf[b], out);
-			key = (uint64_t)tags[a] | ((uint64_t)tags[b] << 32);
-			ba = xf[a].body; bb = xf[b].body;
-		}
+		nh_bb_result r;
+		r.kind = 0; r.mask = 0;
+		uint64_t key = 0; uint32_t ba = 0, bb = 0;
+		int cnt = nh_pair_contacts(xf[a], xf[b], a_sph ? none : box_size + 4*a, b_sph ? none : box_size + 4*b, a_sph ? sph_radius[a - nbox] : 0.0f, b_sph ? sph_radius[b - nbox] : 0.0f,
+		                           tags[a], tags[b], a_sph, b_sph, r, out[0], key, ba, bb);
+		if (r.kind) nh_bb_contacts(r, out);
 		for (int k = 0; k < cnt; ++k) {
 			Rec rc; rc.key = key; rc.feature = out[k].feature; rc.seq = seq++;
 			rc.c[0] = out[k].px; rc.c[1] = out[k].py; rc.c[2] = out[k].pz; rc.c[3] = out[k].penetration;
