@@ -428,8 +428,8 @@ int nh_query_stats(nh_context* ctx, nh_QueryStats* out);
                           NH_ERR_INVALID.
    An unknown mode, or a call before any nh_query_build, returns NH_ERR_INVALID; a refused call changes nothing -- the next query still uses the previous
    filter.  nh_query_filter is host state only: nothing is launched, nothing waits.  (The calls' own `flags` argument has no bit to spare for this.)
-   THE CONTRACT, for all twenty-two query calls (nh_raycast, nh_spherecast, nh_boxcast, nh_capsulecast, their _all and _k forms, nh_overlap, nh_penetration,
-   nh_region, nh_closest, nh_closest_k, nh_distance, nh_move, nh_recover; for nh_region the query is the region: NH_FILTER_PER_QUERY reads masks[i] for region i):
+   THE CONTRACT, for all twenty-three query calls (nh_raycast, nh_spherecast, nh_boxcast, nh_capsulecast, their _all and _k forms, nh_overlap, nh_penetration,
+   nh_region, nh_closest, nh_closest_k, nh_distance, nh_move, nh_recover, nh_walk; for nh_region the query is the region: NH_FILTER_PER_QUERY reads masks[i] for region i):
      - MASKED WORLD: with the filter on, a query with mask m writes byte for byte what the same call with the filter OFF writes on a world that is the same
        except for one thing: every collider with (layers & m) == 0 has a NaN pose -- "a collider of a body that does not exist", which every call above
        documents as never hit, never listed, never reported.  Collider indices, bodies and tags in the records are those of the real world.  For
@@ -941,8 +941,8 @@ int nh_distance(nh_context* ctx, const nh_DistanceQuery* queries, uint32_t count
    aligned; count = 0 is a no-op that returns NH_OK and launches nothing.  Every byte of `count` results is written and nothing behind them.  Never
    allocates, never waits: ONE launch on the context's stream (timing label q_move).  An OBSERVER like nh_capsulecast (note 9): no view export, no
    settling of deferred gravity, no still step turned into a full one, no change to nh_Counts.
-   NOT BUILT: box movers; rotation during the move; gravity, step-up, ground snapping and slope limits (depenetration of a move that starts in
-   overlap is nh_recover, below: recover, then move); moving platforms (the velocity of what is hit); pushing dynamic bodies (queries are observers); the list of everything
+   NOT BUILT: box movers; rotation during the move; gravity (step-up, ground snapping and slope limits are nh_walk, below; depenetration of a move that
+   starts in overlap is nh_recover, below: recover, then move or walk); moving platforms (the velocity of what is hit); pushing dynamic bodies (queries are observers); the list of everything
    touched (last_hit is the last cast's record only).
    Cost: one lane per move, up to max_slides + 1 walks of nh_capsulecast's; a lane that has finished waits for the slowest of its wave.  Measured (one
    MI355X, the landed config-2 world of 1,004,524 colliders, 1,048,576 moves of r = hh = 0.5 from just above resting bodies by 0.75 - 3 units, max_slides 4;
@@ -1012,6 +1012,73 @@ typedef struct nh_Recover { float center[3]; uint32_t shape; float rotation[4]; 
                             float skin; uint32_t max_iterations; uint32_t reserved[2]; } nh_Recover;                      /* 64 B */
 typedef struct nh_RecoverResult { float position[3]; uint32_t flags; float push[3]; uint32_t iterations; nh_PenetrationHit last; } nh_RecoverResult; /* 64 B */
 int nh_recover(nh_context* ctx, const nh_Recover* queries, uint32_t count, nh_RecoverResult* results, uint32_t flags /* 0 */);
+
+/* nh_walk: a GROUNDED character step for `count` capsules against the world of the LAST nh_query_build or nh_query_refit -- nh_move with the rules a
+   character controller puts around it: steps are climbed (step-up), faces too steep to stand on act as walls (slope limit), the capsule follows the
+   ground down a ledge or over a crest (snap), and the result says what it stands on.  The frame of a controller is nh_query_refit, nh_recover, nh_walk:
+   ONE launch each, no download between them.  The first 64 bytes of nh_Walk are nh_Move field for field; `up` is the unit vector against gravity,
+   `step_height` the highest riser climbed, `snap_distance` how far below the capsule ground is looked for, `min_ground_up` the cosine of the slope limit:
+   the least n.up of a hit normal that still counts as ground (0: no limit).  options: NH_WALK_PROBE_ONLY = look for ground but do not move onto it.
+   `reserved` and `reserved2` are not read.
+   ONE WALK, all in float32; the arithmetic is nudge_amd/csrc/nh_query.h, "walk" (nh_q_walk_begin / nh_q_walk_cast / nh_q_walk_advance), which is the
+   definition and fixes the order of every operation.  "The move loop from p along v with k slides" is nh_move's rules 1 - 7 with max_slides = k, each cast
+   the closest-hit capsule cast { p, 1.0f, v, ignore_body, rotation, radius, half_height }.  A hit normal n is WALKABLE when u = n.up has u > 0 and
+   u >= min_ground_up; otherwise it is STEEP.
+     A. SLIDE: the move loop from origin along displacement with max_slides, under the climb rule: pA, vA, flags, slides, last_hit.  A start overlap ends
+        the walk here: the outputs are nh_move's, ground is the miss record.  Any taken hit (t > 0) that is steep sets `blocked`.
+        CLIMB RULE (steep faces act as walls), off when min_ground_up == 0: at a taken hit that is steep with u >= 0 and whose plain deflection
+        w = rem - (rem.n) n (move's first deflect line) has w.up > 0, flags |= NH_WALK_STEEP and the deflection, the crease and n_prev use
+        ns = (n - u up) / |n - u up| in place of n (n itself where |n - u up|^2 < 2^-24); the skin push stays along n.
+     B. STEP UP, only when step_height > 0 and blocked:
+        U. the move loop from origin along step_height * up with 0 slides: pU; lift = (pU - origin).up.  Abandoned on a start overlap or !(lift > 0).
+        F. the move loop from pU along displacement with max_slides, under the climb rule: pF, vF, flags, slides, last_hit.  Abandoned on a start overlap.
+        D. the move loop from pF along -lift * up with 0 slides: pD and its cast's record gD.
+        ACCEPTED iff D took a hit with t > 0 whose normal is walkable and (pD - origin).dh > (pA - origin).dh, dh = displacement - (displacement.up) up.
+        Then position = pD; remaining, slides, last_hit and the move flags (NH_WALK_STEEP with them) are F's; flags |= STEPPED | GROUNDED; ground = gD;
+        step_up = (pD - pA).up; no probe.  Otherwise A stands.
+     C. GROUND PROBE, when snap_distance > 0, there was no start overlap and no step was taken: the capsule cast { p, 1, -snap_distance * up }.  ground =
+        its record.  A miss: airborne.  A steep hit: NH_WALK_ON_STEEP, no motion.  A walkable hit: NH_WALK_GROUNDED, and unless PROBE_ONLY or t == 0:
+        p = p + t*v, p = p + skin*n (move's rule 5), drop = t * snap_distance, NH_WALK_SNAPPED.
+   Output: position, flags (NH_MOVE_* of the slide that was kept in bits 0 - 3, NH_WALK_* above), remaining, slides (the hits taken in the kept slide),
+   last_hit (its last cast), ground, step_up, drop, casts (every cast made: at most NH_WALK_MAX_CASTS), reserved = 0.  Where no probe and no step wrote it,
+   ground is the miss record with t = 1.
+   INVALID RECORDS -- whatever nh_move rejects in the first 64 bytes; a non-finite up; |up.up - 1| > 2^-10; a non-finite or negative step_height or
+   snap_distance; min_ground_up non-finite or outside [0, 1]; an unknown options bit -- write flags = NH_WALK_INVALID, position = the bits of origin,
+   remaining = the bits of displacement, slides = casts = 0, step_up = drop = 0 and both hit records as the miss record with t = NaN.
+   IDENTITIES (contracts):
+     1. with step_height = 0, snap_distance = 0 and min_ground_up = 0 the first 64 bytes of the result are nh_move's 64 bytes for the record's first 64
+        bytes, and ground is the miss record;
+     2. REPLAY, with min_ground_up = 0: the phases run from the host -- nh_move calls for A, U, F and D, an nh_capsulecast call for C, nh_q_walk_phase_end
+        and nh_q_walk_advance between them -- give nh_walk's 112 bytes.  (`blocked` needs every taken hit of A, which nh_move's result does not hold: the
+        replay reads them off nh_move's own REPLAY, one nh_capsulecast per round.)
+     3. half_height = 0 does not read `rotation`;
+     4. after nh_query_refit the bytes are those after an nh_query_build of the same arrays; nh_query_filter is honoured in all three modes (the per-query
+        mask index is the walk's index);
+     5. a result without INVALID and START_OVERLAP never has casts > NH_WALK_MAX_CASTS; a GROUNDED result's ground.normal is walkable.
+   Returns NH_ERR_INVALID before any nh_query_build, for flags != 0, for count >= 2^30, and for count > 0 with `walks` or `results` null or not 16-byte
+   aligned; count = 0 is a no-op that returns NH_OK and launches nothing.  Every byte of `count` results is written and nothing behind them.  Never
+   allocates, never waits: ONE launch on the context's stream (timing label q_walk).  An OBSERVER like nh_move (note 9).
+   NOT BUILT: box movers; rotation during the walk; moving platforms (the velocity of what is stood on); pushing dynamic bodies (queries are observers);
+   the list of everything touched (last_hit and ground are single records); gravity integration and velocities (the caller passes a displacement); a
+   per-node AND word for the filter; queries on partitioned worlds; the `namespace nudge` extension in nudge_amd/compat; any change to nh_move's crease rule.
+   Cost: one lane per walk, up to 21 walks of nh_capsulecast's; the lanes of a wave walk the tree together whatever phase each is in, and a lane that has
+   finished waits for the slowest of its wave.  168 VGPRs at 3 waves per SIMD, no scratch (4 waves would spill 132 - 144 bytes per lane).  Measured (one
+   MI355X, the landed config-2 world of 1,004,524 colliders, 1,048,576 walks of r = 0.3, hh = 0.4, max_slides 4, snap 0.3, half on the slab walking towards a
+   resting body, half on a body's top; tools/walk_rates.py -> profiles/walk_rates.log): 2.85 ms with step_height 0 (2.31 casts per walk), slope
+   limit off or 45 degrees; 4.73 ms with step_height 1.0 and the limit off (2.98 casts), 5.50 ms with the limit at 45 degrees (3.79 casts), beside 0.956 ms
+   for nh_capsulecast on the first casts alone: 1.29, 1.29, 1.66 and 1.52 of (casts per walk x the capsule cast's time), where nh_move reported 1.03
+   (8.0 % of these walks start in overlap and end after one cast: they are in the means).  The
+   host loop of the REPLAY identity on the same batch, its uploads and downloads included: 824 ms for the same bytes.  Filter off, beside the parent commit's
+   library in the same process: nh_move 0.996, nh_capsulecast 1.002 of its times.  NOT MEASURED YET: the filtered instantiation. */
+#define NH_WALK_MAX_CASTS (2u * (NH_MOVE_MAX_SLIDES + 1u) + 3u)   /* 21 */
+enum { NH_WALK_STEPPED = 0x10u, NH_WALK_GROUNDED = 0x20u, NH_WALK_SNAPPED = 0x40u, NH_WALK_STEEP = 0x80u, NH_WALK_ON_STEEP = 0x100u, NH_WALK_INVALID = 0x80000000u };
+enum { NH_WALK_PROBE_ONLY = 1u };   /* nh_Walk.options */
+typedef struct nh_Walk { float origin[3]; float skin; float displacement[3]; uint32_t ignore_body;
+                         float rotation[4]; float radius; float half_height; uint32_t max_slides; uint32_t reserved;      /* = nh_Move, 64 B */
+                         float up[3]; float step_height; float snap_distance; float min_ground_up; uint32_t options; uint32_t reserved2; } nh_Walk;   /* 96 B */
+typedef struct nh_WalkResult { float position[3]; uint32_t flags; float remaining[3]; uint32_t slides; nh_RayHit last_hit; nh_RayHit ground;
+                               float step_up; float drop; uint32_t casts; uint32_t reserved; } nh_WalkResult;                                     /* 112 B */
+int nh_walk(nh_context* ctx, const nh_Walk* walks, uint32_t count, nh_WalkResult* results, uint32_t flags /* 0 */);
 
 /* ---- multi-GPU: one x-slab of a world per context ------------------------------------------------------------------------------------
    The world is cut into slabs along x, one rank (process, GPU, nh_context) per slab [lo, hi).  A rank's arrays hold

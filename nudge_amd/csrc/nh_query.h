@@ -1260,7 +1260,9 @@ NH_HD bool nh_q_move_go(const nh_QMove& s) { return nh_dot(s.v, s.v) != 0.0f; }
 //   WEDGED      iff one of the four rules above wrote w = 0 and rem has a component that is not (+-)0.  A head-on hit needs no special case: w = rem - s*n is
 //               then 0 or rounding dust, w.d0 is not > 0, "never back" fires and the flag is set.  rem = 0 (t = 1: touching exactly at the end) sets none.
 //   v = w, np = n; slides > max_slides with v.v > 0: SLIDES_OUT and stop.  With v.v == 0 the move goes on to rule 1, which ends it.
-NH_HD bool nh_q_move_advance(nh_QMove& s, bool hit, float t, nh_f3 n, float skin, uint32_t max_slides) {
+// nh_q_move_advance2 is the one body: `n` is the PUSH normal (the skin push of rule 5), `ns` the SLIDE normal (the deflection, the crease and n_prev of rule
+// 6).  nh_move slides along what it hit, ns = n; nh_walk's climb rule ("walk", below) deflects along the horizontal part of a face too steep to stand on.
+NH_HD bool nh_q_move_advance2(nh_QMove& s, bool hit, float t, nh_f3 n, nh_f3 ns, float skin, uint32_t max_slides) {
 	if (!hit) {
 		s.p = s.p + s.v;
 		s.v = nh_make3(0.0f, 0.0f, 0.0f);
@@ -1273,23 +1275,201 @@ NH_HD bool nh_q_move_advance(nh_QMove& s, bool hit, float t, nh_f3 n, float skin
 	s.p = s.p + t * s.v;
 	s.p = s.p + skin * n;
 	const nh_f3 rem = (1.0f - t) * s.v;
-	const float sn = nh_dot(rem, n);
-	nh_f3 w = sn < 0.0f ? rem - sn * n : rem;
+	const float sn = nh_dot(rem, ns);
+	nh_f3 w = sn < 0.0f ? rem - sn * ns : rem;
 	const nh_f3 zero = nh_make3(0.0f, 0.0f, 0.0f);
 	bool zeroed = false;
 	if (prev && nh_dot(w, s.np) < 0.0f) {
-		const nh_f3 c = nh_cross(s.np, n);
+		const nh_f3 c = nh_cross(s.np, ns);
 		const float cc = nh_dot(c, c);
 		if (cc < NH_Q_MOVE_CREASE_EPS) { w = zero; zeroed = true; }
 		else w = c * (nh_dot(rem, c) / cc);
-		if (nh_dot(w, s.np) < 0.0f || nh_dot(w, n) < 0.0f) { w = zero; zeroed = true; }
+		if (nh_dot(w, s.np) < 0.0f || nh_dot(w, ns) < 0.0f) { w = zero; zeroed = true; }
 	}
 	if (!(nh_dot(w, s.d0) > 0.0f)) { w = zero; zeroed = true; }
 	if (!(nh_dot(w, w) > NH_Q_MOVE_TINY * nh_dot(s.d0, s.d0))) { w = zero; zeroed = true; }
 	if (zeroed && (rem.x != 0.0f || rem.y != 0.0f || rem.z != 0.0f)) s.flags |= NH_Q_MOVE_WEDGED;
-	s.v = w; s.np = n;
+	s.v = w; s.np = ns;
 	if (s.slides > max_slides && nh_dot(w, w) > 0.0f) { s.flags |= NH_Q_MOVE_SLIDES_OUT; return false; }
 	return true;
+}
+
+NH_HD bool nh_q_move_advance(nh_QMove& s, bool hit, float t, nh_f3 n, float skin, uint32_t max_slides) { return nh_q_move_advance2(s, hit, t, n, n, skin, max_slides); }
+
+// ---- walk (nh_walk): a grounded character step, the state between two capsule casts ---------------------------------------------------------------------
+// These functions ARE the definition of nh_walk (include/nudge_hip.h): k_q_walk and the host's brute force (tests/hostoracle/hostwalk.cpp) both run
+//     s = nh_q_walk_begin(W);
+//     while (nh_q_walk_cast(s, W)) { hit = the closest-hit capsule cast { s.m.p, 1.0f, s.m.v, ignore_body, rotation, radius, half_height };
+//                                    nh_q_walk_advance(s, W, hit found, hit.t, hit's collider, hit.normal, the cast was valid); }
+// and write s.kp, s.kflags, s.kv, s.kslides, the records of s.klast and nh_q_walk_ground(s), s.step_up, nh_q_walk_drop(s, W) and s.casts.  A walk is up to five MOVE LOOPS ("move",
+// above: nh_q_move_begin / _go / _advance2 on s.m), one after the other, and the decisions between them; a lane is in one PHASE:
+//   A  slide    from origin along displacement, max_slides, under the climb rule.  Its end is KEPT (kp, kv, kslides, kflags, klast).  A taken hit (t > 0) whose
+//               normal is steep sets `blocked` (the phase AB).  START_OVERLAP: the walk ends here.  step_height > 0 and blocked: U.  Otherwise C.
+//   U  up       from origin along step_height * up (per component), 0 slides.  lift = (p - origin).up.  START_OVERLAP or !(lift > 0): C.  Otherwise F.
+//   F  forward  from U's end along displacement, max_slides, under the climb rule.  START_OVERLAP: C.  Otherwise its (v, slides, flags, last) wait in f*, and D.
+//   D  down     from F's end along (-lift) * up, 0 slides.  ACCEPT iff its cast hit at t > 0 (NH_Q_MOVE_HIT), the normal is walkable and
+//               (p - origin).dh > (kp - origin).dh with dh_k = displacement_k - ((displacement.up) * up_k): then step_up = (p - kp).up, kp = p, (kv, kslides,
+//               kflags, klast) = F's, kflags |= STEPPED | GROUNDED, ground = D's cast, and the walk ends.  Otherwise C: A stands.
+//   C  probe    only where snap_distance > 0: ONE cast (no move loop, no v.v test) from kp along (-snap_distance) * up.  ground = its record, hit or miss.
+//               A steep hit: ON_STEEP.  A walkable hit: GROUNDED, and unless PROBE_ONLY or t == 0: kp = kp + t*v, kp = kp + skin*n (move's rule 5),
+//               drop = t * snap_distance, SNAPPED.  (A t == 0 hit has the normal -v / |v| = up: grounded where it stands.)
+// A move loop that has nothing to cast along (v.v == 0: a zero displacement, a lift whose square underflows) ends without a cast; nh_q_walk_cast settles such
+// loops, at most four in a row, before it answers.  WALKABLE(n): u = n.up, u > 0 and u >= min_ground_up; anything else is STEEP.
+// CLIMB RULE, in A and F, off where min_ground_up == 0: at a taken hit that is steep with u >= 0 whose plain deflection w (rem_k = (1 - t) * v_k, s = rem.n,
+// w = s < 0 ? rem - s*n : rem -- move's bits) has w.up > 0: the loop's flags |= STEEP, and the slide normal is ns_k = h_k / sqrtf(h.h) with
+// h_k = n_k - (u * up_k), unless h.h < 2^-24 (ns = n).  The push stays along n.  STEEP is a flag of its loop: the result carries the kept loop's.
+// `casts` counts every cast; A and F make at most max_slides + 1 each, U, D and C one each: 2 * (8 + 1) + 3 = 21.
+#define NH_Q_WALK_STEPPED 0x10u
+#define NH_Q_WALK_GROUNDED 0x20u
+#define NH_Q_WALK_SNAPPED 0x40u
+#define NH_Q_WALK_STEEP 0x80u
+#define NH_Q_WALK_ON_STEEP 0x100u
+#define NH_Q_WALK_PROBE_ONLY 1u
+#define NH_Q_WALK_NOBODY 0xffffffffu                            // (nh_query_tree.h's NH_Q_NONE)
+#define NH_Q_WALK_MAX_CASTS (2u * (NH_Q_MOVE_MAX_SLIDES + 1u) + 3u)
+#define NH_Q_WALK_UP_EPS 0.0009765625f                         // 2^-10: |up.up - 1| above it, `up` is not a unit vector
+#define NH_Q_WALK_FLAT_EPS 5.9604644775390625e-08f             // 2^-24: |n - (n.up) up|^2 below it, the face has no horizontal part to slide along
+// (AB: A once a steep hit was taken, `blocked`; FOUND: the end behind a cast that wrote the ground record -- D's where the step is accepted, C's)
+enum { NH_Q_WALK_A = 0u, NH_Q_WALK_AB = 1u, NH_Q_WALK_U = 2u, NH_Q_WALK_F = 3u, NH_Q_WALK_D = 4u, NH_Q_WALK_C = 5u, NH_Q_WALK_END = 6u, NH_Q_WALK_FOUND = 7u };
+
+// The record's fields the rules read (the capsule itself -- ignore_body, rotation, radius, half_height -- goes into every cast unchanged)
+struct nh_QWalkIn { nh_f3 origin, disp, up; float skin, step_height, snap, mgu; uint32_t max_slides, options; };
+// One cast's answer as the state keeps it: c = NH_Q_WALK_NOBODY is a miss, whose t is the cast's max_t, 1 -- or the miss record's quiet NaN (0x7fc00000)
+// where the cast was invalid
+struct nh_QWalkHit { float t; nh_f3 n; uint32_t c; };
+// m: the running move loop (its slide budget is the phase's: nh_q_walk_slides); last: its last cast; k*: what is kept; f*: F's end while D runs.  The
+// ground record and the drop are written by the cast that ends the walk, so the state keeps the phase FOUND, not a copy: nh_q_walk_ground, _drop.
+struct nh_QWalk {
+	nh_QMove m; uint32_t phase, casts; float lift;
+	nh_QWalkHit last;
+	nh_f3 kp, kv; uint32_t kslides, kflags; nh_QWalkHit klast;
+	nh_f3 fv; uint32_t fslides, fflags; nh_QWalkHit flast;
+	float step_up;
+};
+
+// The record's validity (header, "Invalid records"): nh_move's rules for the first 64 bytes and the walk's own
+NH_HD bool nh_q_walk_valid(const nh_QWalkIn& W, nh_quat q, float r, float hh) {
+	bool ok = nh_q_move_valid(W.origin, W.disp, q, r, hh, W.skin, W.max_slides);
+	ok = ok && nh_q_move_finite(W.up.x) && nh_q_move_finite(W.up.y) && nh_q_move_finite(W.up.z) && nh_abs(nh_dot(W.up, W.up) - 1.0f) <= NH_Q_WALK_UP_EPS;
+	ok = ok && nh_q_move_finite(W.step_height) && !(W.step_height < 0.0f) && nh_q_move_finite(W.snap) && !(W.snap < 0.0f);
+	ok = ok && nh_q_move_finite(W.mgu) && W.mgu >= 0.0f && W.mgu <= 1.0f;
+	return ok && (W.options & ~NH_Q_WALK_PROBE_ONLY) == 0u;
+}
+
+NH_HD nh_QWalkHit nh_q_walk_miss() { nh_QWalkHit h; h.t = 1.0f; h.n = nh_make3(0.0f, 0.0f, 0.0f); h.c = NH_Q_WALK_NOBODY; return h; }
+
+NH_HD bool nh_q_walk_walkable(nh_f3 n, const nh_QWalkIn& W) {
+	const float u = nh_dot(n, W.up);
+	return u > 0.0f && u >= W.mgu;
+}
+
+// the next move loop: from p along v
+NH_HD void nh_q_walk_start(nh_QWalk& s, uint32_t phase, nh_f3 p, nh_f3 v) {
+	s.m = nh_q_move_begin(p, v); s.phase = phase; s.last = nh_q_walk_miss();
+}
+
+// the slide budget of the running loop: max_slides in A and F, 0 in U, D (and C, which is one cast)
+NH_HD uint32_t nh_q_walk_slides(const nh_QWalk& s, const nh_QWalkIn& W) { return s.phase <= NH_Q_WALK_AB || s.phase == NH_Q_WALK_F ? W.max_slides : 0u; }
+
+NH_HD nh_QWalk nh_q_walk_begin(const nh_QWalkIn& W) {
+	nh_QWalk s;
+	nh_q_walk_start(s, NH_Q_WALK_A, W.origin, W.disp);
+	s.casts = 0u; s.lift = 0.0f;
+	s.kp = W.origin; s.kv = W.disp; s.kslides = 0u; s.kflags = 0u; s.klast = s.last;
+	s.fv = nh_make3(0.0f, 0.0f, 0.0f); s.fslides = 0u; s.fflags = 0u; s.flast = s.last;
+	s.step_up = 0.0f;
+	return s;
+}
+
+// The ground record and the drop of a walk that has ended
+NH_HD nh_QWalkHit nh_q_walk_ground(const nh_QWalk& s) { return s.phase == NH_Q_WALK_FOUND ? s.last : nh_q_walk_miss(); }
+NH_HD float nh_q_walk_drop(const nh_QWalk& s, const nh_QWalkIn& W) { return (s.kflags & NH_Q_WALK_SNAPPED) != 0u ? s.last.t * W.snap : 0.0f; }
+
+// C, or the end where there is no probe to make
+NH_HD void nh_q_walk_probe(nh_QWalk& s, const nh_QWalkIn& W) {
+	if (W.snap > 0.0f) nh_q_walk_start(s, NH_Q_WALK_C, s.kp, (-W.snap) * W.up);
+	else s.phase = NH_Q_WALK_END;
+}
+
+// The decision behind a move loop that has ended (s.m and s.last hold its end): what the walk does next.  The REPLAY identity calls this between nh_move calls.
+NH_HD void nh_q_walk_phase_end(nh_QWalk& s, const nh_QWalkIn& W) {
+	const bool overlap = (s.m.flags & NH_Q_MOVE_START_OVERLAP) != 0u;
+	if (s.phase <= NH_Q_WALK_AB) {
+		s.kp = s.m.p; s.kv = s.m.v; s.kslides = s.m.slides; s.kflags = s.m.flags; s.klast = s.last;
+		if (overlap) s.phase = NH_Q_WALK_END;
+		else if (W.step_height > 0.0f && s.phase == NH_Q_WALK_AB) nh_q_walk_start(s, NH_Q_WALK_U, W.origin, W.step_height * W.up);
+		else nh_q_walk_probe(s, W);
+	} else if (s.phase == NH_Q_WALK_U) {
+		s.lift = nh_dot(s.m.p - W.origin, W.up);
+		if (overlap || !(s.lift > 0.0f)) nh_q_walk_probe(s, W);
+		else nh_q_walk_start(s, NH_Q_WALK_F, s.m.p, W.disp);
+	} else if (s.phase == NH_Q_WALK_F) {
+		if (overlap) nh_q_walk_probe(s, W);
+		else {
+			s.fv = s.m.v; s.fslides = s.m.slides; s.fflags = s.m.flags; s.flast = s.last;
+			nh_q_walk_start(s, NH_Q_WALK_D, s.m.p, (-s.lift) * W.up);
+		}
+	} else if (s.phase == NH_Q_WALK_D) {
+		const nh_f3 dh = W.disp - nh_dot(W.disp, W.up) * W.up;
+		const bool landed = (s.m.flags & NH_Q_MOVE_HIT) != 0u && !overlap && nh_q_walk_walkable(s.last.n, W);
+		if (landed && nh_dot(s.m.p - W.origin, dh) > nh_dot(s.kp - W.origin, dh)) {
+			s.step_up = nh_dot(s.m.p - s.kp, W.up);
+			s.kp = s.m.p; s.kv = s.fv; s.kslides = s.fslides; s.klast = s.flast;
+			s.kflags = s.fflags | NH_Q_WALK_STEPPED | NH_Q_WALK_GROUNDED;
+			s.phase = NH_Q_WALK_FOUND;
+		} else nh_q_walk_probe(s, W);
+	}
+}
+
+// Is there a cast to make?  It is { s.m.p, 1, s.m.v }.  Move loops with nothing to cast along end here (rule 1 of the move).
+NH_HD bool nh_q_walk_cast(nh_QWalk& s, const nh_QWalkIn& W) {
+	for (uint32_t k = 0u; k < 4u; ++k)
+		if (s.phase < NH_Q_WALK_C && !nh_q_move_go(s.m)) nh_q_walk_phase_end(s, W);
+	return s.phase < NH_Q_WALK_END;
+}
+
+// The slide normal of a taken hit (t > 0) with normal n in the running loop: the climb rule
+NH_HD nh_f3 nh_q_walk_slide_normal(nh_QWalk& s, const nh_QWalkIn& W, float t, nh_f3 n) {
+	if (W.mgu == 0.0f || !(s.phase <= NH_Q_WALK_AB || s.phase == NH_Q_WALK_F)) return n;
+	const float u = nh_dot(n, W.up);
+	if (!(u >= 0.0f) || (u > 0.0f && u >= W.mgu)) return n;
+	const nh_f3 rem = (1.0f - t) * s.m.v;
+	const float sn = nh_dot(rem, n);
+	const nh_f3 w = sn < 0.0f ? rem - sn * n : rem;
+	if (!(nh_dot(w, W.up) > 0.0f)) return n;
+	s.m.flags |= NH_Q_WALK_STEEP;
+	const nh_f3 h = n - u * W.up;
+	const float hh = nh_dot(h, h);
+	if (hh < NH_Q_WALK_FLAT_EPS) return n;
+	const float l = sqrtf(hh);
+	return nh_make3(h.x / l, h.y / l, h.z / l);
+}
+
+// Behind the cast nh_q_walk_cast asked for: (hit, t, c, n) its answer (c: what the caller names the collider by; a miss has t = 1), ok: the
+// cast was valid (an invalid cast is a miss)
+NH_HD void nh_q_walk_advance(nh_QWalk& s, const nh_QWalkIn& W, bool hit, float t, uint32_t c, nh_f3 n, bool ok) {
+	s.casts += 1u;
+	s.last.t = ok ? t : nh_asfloat(0x7fc00000u); s.last.n = n; s.last.c = hit ? c : NH_Q_WALK_NOBODY;
+	if (s.phase == NH_Q_WALK_C) {
+		if (hit) {
+			if (nh_q_walk_walkable(n, W)) {
+				s.kflags |= NH_Q_WALK_GROUNDED;
+				if (!(W.options & NH_Q_WALK_PROBE_ONLY) && t != 0.0f) {
+					s.kp = s.kp + t * s.m.v;
+					s.kp = s.kp + W.skin * n;
+					s.kflags |= NH_Q_WALK_SNAPPED;
+				}
+			} else s.kflags |= NH_Q_WALK_ON_STEEP;
+		}
+		s.phase = NH_Q_WALK_FOUND;
+		return;
+	}
+	nh_f3 ns = n;
+	if (hit && t != 0.0f) {
+		if (s.phase == NH_Q_WALK_A && !nh_q_walk_walkable(n, W)) s.phase = NH_Q_WALK_AB;
+		ns = nh_q_walk_slide_normal(s, W, t, n);
+	}
+	if (!nh_q_move_advance2(s.m, hit, t, n, ns, W.skin, nh_q_walk_slides(s, W))) nh_q_walk_phase_end(s, W);
 }
 
 // ---- recover (nh_recover): push a shape out of what it overlaps, the state between two overlap walks -------------------------------------------------

@@ -374,6 +374,59 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
 	}
 }
 
+// ---- walk -------------------------------------------------------------------------------------------------------------------------------------
+// nh_walk: one lane per walk.  The phase machine is nh_query.h's ("walk": nh_q_walk_begin / _cast / _advance, which the host's brute force runs as well): up
+// to five move loops one after the other (slide, up, forward, down, probe), each cast the record { s.m.p, 1.0f, s.m.v, ignore_body, rotation, radius,
+// half_height } decoded by nh_QCapsule::set and answered by nh_q_cast_one, the body of k_q_capsulecast.  There is ONE call site of the cast in ONE loop: the
+// lane's phase only picks the origin and the direction, so the capsule sweep is instantiated once and the lanes of a wave walk the tree together whatever
+// phase each is in.  The loop bound is the constant NH_WALK_MAX_CASTS and every round is a walk that terminates, so the kernel terminates on any input.
+// The record leaves as seven 16-byte stores.
+static_assert(NH_Q_WALK_STEPPED == NH_WALK_STEPPED && NH_Q_WALK_GROUNDED == NH_WALK_GROUNDED && NH_Q_WALK_SNAPPED == NH_WALK_SNAPPED && NH_Q_WALK_STEEP == NH_WALK_STEEP &&
+              NH_Q_WALK_ON_STEEP == NH_WALK_ON_STEEP && NH_Q_WALK_PROBE_ONLY == NH_WALK_PROBE_ONLY && NH_Q_WALK_MAX_CASTS == NH_WALK_MAX_CASTS && NH_WALK_MAX_CASTS == 21u &&
+              NH_Q_WALK_NOBODY == NH_Q_NONE, "nh_query.h's walk constants are the header's");
+static_assert(sizeof(nh_Walk) == 96 && sizeof(nh_WalkResult) == 112 && offsetof(nh_WalkResult, last_hit) == 32 && offsetof(nh_WalkResult, ground) == 64,
+              "nh_Walk is six and nh_WalkResult seven 16-byte words");
+// (What a walk keeps between two casts -- the record's rules, the kept slide, F's end while D runs: some 50 values -- lies idle during the tree walk.  Asked
+// for k_q_move's 4 waves the compiler puts 132 (filter off) and 144 (on) bytes of it per lane into scratch; at 3 waves both instantiations hold everything in
+// 168 VGPRs, no scratch.  DESIGN 10.18; -DNH_Q_WALK_WAVES=4 -Rpass-analysis=kernel-resource-usage reproduces the 4-wave figures.)
+#ifndef NH_Q_WALK_WAVES
+#define NH_Q_WALK_WAVES 3
+#endif
+
+template <bool FILTER>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NH_Q_WALK_WAVES))) void k_q_walk(const nh_Walk* __restrict__ walks, uint32_t count, nh_WalkResult* __restrict__ results,
+                                                   const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox, nh_QFilter F) {
+	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
+		const float4* wp = reinterpret_cast<const float4*>(walks + i);
+		const float4 m0 = wp[0], m1 = wp[1], m2 = wp[2], m3 = wp[3], m4 = wp[4], m5 = wp[5];
+		nh_QWalkIn W;
+		W.origin = nh_make3(m0.x, m0.y, m0.z); W.skin = m0.w;
+		W.disp = nh_make3(m1.x, m1.y, m1.z); W.max_slides = __float_as_uint(m3.z);
+		W.up = nh_make3(m4.x, m4.y, m4.z); W.step_height = m4.w;
+		W.snap = m5.x; W.mgu = m5.y; W.options = __float_as_uint(m5.z);
+		const bool valid = nh_q_walk_valid(W, nh_quat{ m2.x, m2.y, m2.z, m2.w }, m3.x, m3.y);
+		nh_QWalk s = nh_q_walk_begin(W);
+		const uint32_t fm = FILTER ? F.of(i) : 0u;
+		for (uint32_t round = 0u; round < NH_WALK_MAX_CASTS; ++round) {
+			if (!valid || !nh_q_walk_cast(s, W)) break;
+			nh_QCapsule k;
+			k.set(make_float4(s.m.p.x, s.m.p.y, s.m.p.z, 1.0f), make_float4(s.m.v.x, s.m.v.y, s.m.v.z, m1.w), m2, m3);
+			float bt;
+			uint32_t bc;
+			nh_f3 bn;
+			nh_q_cast_one<FILTER>(k, nodes, rec, n, nbox, 0u, F, fm, bt, bc, bn);
+			nh_q_walk_advance(s, W, bc != NH_Q_NONE, bt, bc, bn, k.ok);
+		}
+		float4* out = reinterpret_cast<float4*>(results + i);
+		out[0] = make_float4(s.kp.x, s.kp.y, s.kp.z, __uint_as_float(valid ? s.kflags : (uint32_t)NH_WALK_INVALID));
+		out[1] = make_float4(s.kv.x, s.kv.y, s.kv.z, __uint_as_float(s.kslides));
+		const nh_QWalkHit g = nh_q_walk_ground(s);
+		nh_q_write_hit(&results[i].last_hit, rec, nbox, valid, s.klast.c, s.klast.t, s.klast.n);
+		nh_q_write_hit(&results[i].ground, rec, nbox, valid, g.c, g.t, g.n);
+		out[6] = make_float4(s.step_up, nh_q_walk_drop(s, W), __uint_as_float(s.casts), 0.0f);
+	}
+}
+
 // ---- closest point ----------------------------------------------------------------------------------------------------------------------------
 // One lane per query.  The bound bd starts at max_distance and only ever falls to the key of a real candidate (nh_q_point_key, nh_q_closer: the reach
 // rule of DESIGN 10.5), so a node of squared distance d2 > 0 from p with sqrtf(d2) > bd can be skipped, and one with d2 = 0 is always entered.
@@ -1043,6 +1096,16 @@ extern "C" int nh_move(nh_context* ctx, const nh_Move* moves, uint32_t count, nh
 	bool on;
 	const nh_QFilter F = nh_query_filter_of(q, &on);
 	NH_LAUNCH(ctx, "q_move", on ? k_q_move<true> : k_q_move<false>, nh_grid_for(count, 256, 1u << 20), 256, moves, count, results, q->nodes, q->rec, q->n, q->nbox, F);
+	return NH_OK;
+}
+
+// One launch, nh_move's checks in nh_move's order; no allocation, no wait.
+extern "C" int nh_walk(nh_context* ctx, const nh_Walk* walks, uint32_t count, nh_WalkResult* results, uint32_t flags) {
+	{ const int rc = nh_query_call(ctx, flags, 0u, 0u, 0u, count, 1u << 30, walks, results, nullptr); if (rc || count == 0u) return rc; }
+	nh_QueryState* q = ctx->query;
+	bool on;
+	const nh_QFilter F = nh_query_filter_of(q, &on);
+	NH_LAUNCH(ctx, "q_walk", on ? k_q_walk<true> : k_q_walk<false>, nh_grid_for(count, 256, 1u << 20), 256, walks, count, results, q->nodes, q->rec, q->n, q->nbox, F);
 	return NH_OK;
 }
 

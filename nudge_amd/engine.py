@@ -43,7 +43,7 @@ EXPORTS = [
     "nh_partition_top_speed", "nh_partition_set_peer_speeds", "nh_partition_refresh_is_quiet", "nh_partition_mark_ghosts", "nh_partition_pack_deltas", "nh_partition_unpack_deltas",
     "nh_partition_pack_momentum", "nh_partition_unpack_momentum", "nh_partition_exchange_iteration", "nh_partition_unpack_ghosts", "nh_partition_pack_step", "nh_partition_unpack_step", "nh_partition_choose_cut", "nh_partition_set_cut",
     "nh_partition_set_transport", "nh_partition_exchange_step", "nh_partition_step", "nh_partition_transport_check", "nh_partition_transport_result", "nh_set_first_ghost_body",
-    "nh_query_build", "nh_query_refit", "nh_query_stats", "nh_raycast", "nh_overlap", "nh_penetration", "nh_region", "nh_spherecast", "nh_raycast_all", "nh_spherecast_all", "nh_boxcast_all", "nh_capsulecast_all", "nh_boxcast", "nh_capsulecast", "nh_closest", "nh_closest_k", "nh_distance", "nh_move", "nh_recover",
+    "nh_query_build", "nh_query_refit", "nh_query_stats", "nh_raycast", "nh_overlap", "nh_penetration", "nh_region", "nh_spherecast", "nh_raycast_all", "nh_spherecast_all", "nh_boxcast_all", "nh_capsulecast_all", "nh_boxcast", "nh_capsulecast", "nh_closest", "nh_closest_k", "nh_distance", "nh_move", "nh_recover", "nh_walk",
     "nh_raycast_k", "nh_spherecast_k", "nh_boxcast_k", "nh_capsulecast_k",
     "nh_query_set_layers", "nh_query_filter", "nh_query_layer_info",
 ]
@@ -176,6 +176,12 @@ MOVE = np.dtype([("origin", "<f4", 3), ("skin", "<f4"), ("displacement", "<f4", 
 MOVE_RESULT = np.dtype([("position", "<f4", 3), ("flags", "<u4"), ("remaining", "<f4", 3), ("slides", "<u4"), ("last_hit", RAY_HIT)])
 NH_MOVE_MAX_SLIDES = 8
 NH_MOVE_HIT, NH_MOVE_START_OVERLAP, NH_MOVE_SLIDES_OUT, NH_MOVE_WEDGED, NH_MOVE_INVALID = 1, 2, 4, 8, 0x80000000
+# nh_walk (include/nudge_hip.h): nh_Move followed by `up`, the step height, the snap distance, the slope limit (a cosine) and the options; nh_WalkResult.flags
+WALK = np.dtype(MOVE.descr + [("up", "<f4", 3), ("step_height", "<f4"), ("snap_distance", "<f4"), ("min_ground_up", "<f4"), ("options", "<u4"), ("reserved2", "<u4")])
+WALK_RESULT = np.dtype(MOVE_RESULT.descr + [("ground", RAY_HIT), ("step_up", "<f4"), ("drop", "<f4"), ("casts", "<u4"), ("reserved", "<u4")])
+NH_WALK_MAX_CASTS = 2 * (NH_MOVE_MAX_SLIDES + 1) + 3
+NH_WALK_STEPPED, NH_WALK_GROUNDED, NH_WALK_SNAPPED, NH_WALK_STEEP, NH_WALK_ON_STEEP, NH_WALK_INVALID = 0x10, 0x20, 0x40, 0x80, 0x100, 0x80000000
+NH_WALK_PROBE_ONLY = 1
 # nh_recover (include/nudge_hip.h): nh_OverlapQuery followed by `skin` and `max_iterations`; nh_RecoverResult.flags
 RECOVER = np.dtype([("center", "<f4", 3), ("shape", "<u4"), ("rotation", "<f4", 4), ("size", "<f4", 3), ("ignore_body", "<u4"), ("skin", "<f4"),
                     ("max_iterations", "<u4"), ("reserved", "<u4", 2)])
@@ -328,6 +334,9 @@ def lib():
         # (likewise nh_recover: World.recover then raises AttributeError)
         if hasattr(L, "nh_recover"):
             L.nh_recover.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
+        # (likewise nh_walk: World.walk then raises AttributeError)
+        if hasattr(L, "nh_walk"):
+            L.nh_walk.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
         L.nh_overlap.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
         L.nh_penetration.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
         # (an older build of the library, loaded through NUDGE_HIP_LIBRARY for an A/B, has no nh_region: World.region then raises AttributeError)
@@ -1135,6 +1144,50 @@ class World:
         u = raw.view(torch.int32).reshape(n, 16).to(torch.int64) & 0xFFFFFFFF
         out = dict(position=f[:, 0:3], remaining=f[:, 4:7], flags=u[:, 3], slides=u[:, 7], last_hit=self._ray_hits(raw.reshape(n, 64)[:, 32:].contiguous(), False),
                    raw=raw)
+        if synchronize:
+            torch.cuda.current_stream(self.dev).synchronize()
+        return out
+
+    def walk_records(self, records, results=None):
+        """nh_walk on records already laid out as nh_Walk: `records` a contiguous device tensor of count x 96 bytes (any dtype).  Returns the
+        count x 112-byte uint8 device tensor of nh_WalkResult records (`results`, or a new one)."""
+        torch = self.torch
+        n = records.numel() * records.element_size() // 96
+        if results is None:
+            results = torch.empty((n, 112), dtype=torch.uint8, device=self.dev)
+        _check(self.L, self.L.nh_walk(self.ctx, C.c_void_p(records.data_ptr() if n else 0), n, C.c_void_p(results.data_ptr() if n else 0), 0), "nh_walk")
+        return results
+
+    def walk(self, origins, displacements, radius, half_height=0.0, rotations=None, skin=0.01, max_slides=4, ignore_body=None, up=(0.0, 1.0, 0.0),
+             step_height=0.0, snap_distance=0.0, max_slope_degrees=None, min_ground_up=None, probe_only=False, synchronize=False):
+        """A grounded character step (nh_walk) against the last query_build(): move()'s capsules, moved from `origins` by `displacements` with move()'s
+        `skin`, `max_slides` and `ignore_body`, climbing risers up to `step_height`, treating faces steeper than the slope limit as walls, and
+        following ground found within `snap_distance` below.  `up`: the unit vector against gravity ((3,) or (n, 3)).  The slope limit is
+        `max_slope_degrees` (the steepest ground, in degrees) or `min_ground_up` (its cosine); give one, or neither for no limit.  `step_height`,
+        `snap_distance`, the limit and `probe_only` (look for ground, do not move onto it) are numbers or n values.
+        Returns move()'s dict for the slide that was kept -- position, remaining, flags (NH_MOVE_* and NH_WALK_*), slides, last_hit -- plus `ground`
+        (capsulecast()'s dict of what the capsule stands on), step_up, drop (n, float32), casts (n, int64) and `raw`, the nh_WalkResult records.
+        Nothing waits for the device unless `synchronize`."""
+        torch = self.torch
+        if max_slope_degrees is not None and min_ground_up is not None:
+            raise ValueError("walk: give max_slope_degrees or min_ground_up, not both")
+        head, n = self._capsule_casts("walk", origins, displacements, radius, half_height, rotations, skin, ignore_body)
+        head.view(torch.int32)[:, 14] = torch.as_tensor(max_slides, dtype=torch.int64, device=self.dev).to(torch.int32)
+        rec = torch.zeros((n, 24), dtype=torch.float32, device=self.dev)
+        rec[:, 0:16] = head
+        rec[:, 16:19] = torch.as_tensor(up, dtype=torch.float32, device=self.dev).reshape(-1, 3)
+        rec[:, 19] = torch.as_tensor(step_height, dtype=torch.float32, device=self.dev).reshape(-1)
+        rec[:, 20] = torch.as_tensor(snap_distance, dtype=torch.float32, device=self.dev).reshape(-1)
+        if max_slope_degrees is not None:
+            min_ground_up = torch.cos(torch.deg2rad(torch.as_tensor(max_slope_degrees, dtype=torch.float64, device=self.dev)))
+        rec[:, 21] = torch.as_tensor(0.0 if min_ground_up is None else min_ground_up, device=self.dev).to(torch.float32).reshape(-1)
+        rec.view(torch.int32)[:, 22] = torch.as_tensor(probe_only, device=self.dev).to(torch.int32).reshape(-1) & 1
+        raw = self.walk_records(rec)
+        f = raw.view(torch.float32).reshape(n, 28)
+        u = raw.view(torch.int32).reshape(n, 28).to(torch.int64) & 0xFFFFFFFF
+        bytes_ = raw.reshape(n, 112)
+        out = dict(position=f[:, 0:3], remaining=f[:, 4:7], flags=u[:, 3], slides=u[:, 7], last_hit=self._ray_hits(bytes_[:, 32:64].contiguous(), False),
+                   ground=self._ray_hits(bytes_[:, 64:96].contiguous(), False), step_up=f[:, 24], drop=f[:, 25], casts=u[:, 26], raw=raw)
         if synchronize:
             torch.cuda.current_stream(self.dev).synchronize()
         return out
