@@ -79,7 +79,7 @@
  *      exported the views: nh_set_option(ctx, "sync_exports_views", 1) restores that contract at its old price; INTEGRATION.md.)  Any entry point outside the sample's
  *      call order between nh_collide and nh_apply_impulses turns a still step into a full one first, so everything it observes is what a full step
  *      produces.  nh_Counts.still_steps / still_replays count them.
- *      The scene queries (nh_query_build, nh_query_refit, nh_raycast, nh_spherecast, nh_raycast_all, nh_spherecast_all, nh_boxcast_all, nh_capsulecast_all, nh_raycast_k, nh_spherecast_k, nh_boxcast_k, nh_capsulecast_k, nh_boxcast, nh_capsulecast, nh_overlap, nh_penetration, nh_region, nh_closest, nh_closest_k, nh_distance, nh_move, nh_recover, nh_query_set_layers, nh_query_filter, nh_query_layer_info) are not entry points of the step in this sense: they neither export nor settle nor turn a still step into a
+ *      The scene queries (nh_query_build, nh_query_refit, nh_raycast, nh_spherecast, nh_raycast_all, nh_spherecast_all, nh_boxcast_all, nh_capsulecast_all, nh_raycast_k, nh_spherecast_k, nh_boxcast_k, nh_capsulecast_k, nh_boxcast, nh_capsulecast, nh_overlap, nh_penetration, nh_region, nh_closest, nh_closest_k, nh_distance, nh_move, nh_recover, nh_walk, nh_boxmove, nh_boxwalk, nh_query_set_layers, nh_query_filter, nh_query_layer_info) are not entry points of the step in this sense: they neither export nor settle nor turn a still step into a
  *      full one, and they do not count -- see "scene queries" below.
  *
  * Threading: one context = one HIP stream = one world at a time; no global mutable state.
@@ -428,8 +428,8 @@ int nh_query_stats(nh_context* ctx, nh_QueryStats* out);
                           NH_ERR_INVALID.
    An unknown mode, or a call before any nh_query_build, returns NH_ERR_INVALID; a refused call changes nothing -- the next query still uses the previous
    filter.  nh_query_filter is host state only: nothing is launched, nothing waits.  (The calls' own `flags` argument has no bit to spare for this.)
-   THE CONTRACT, for all twenty-three query calls (nh_raycast, nh_spherecast, nh_boxcast, nh_capsulecast, their _all and _k forms, nh_overlap, nh_penetration,
-   nh_region, nh_closest, nh_closest_k, nh_distance, nh_move, nh_recover, nh_walk; for nh_region the query is the region: NH_FILTER_PER_QUERY reads masks[i] for region i):
+   THE CONTRACT, for all twenty-five query calls (nh_raycast, nh_spherecast, nh_boxcast, nh_capsulecast, their _all and _k forms, nh_overlap, nh_penetration,
+   nh_region, nh_closest, nh_closest_k, nh_distance, nh_move, nh_recover, nh_walk, nh_boxmove, nh_boxwalk; for nh_region the query is the region: NH_FILTER_PER_QUERY reads masks[i] for region i):
      - MASKED WORLD: with the filter on, a query with mask m writes byte for byte what the same call with the filter OFF writes on a world that is the same
        except for one thing: every collider with (layers & m) == 0 has a NaN pose -- "a collider of a body that does not exist", which every call above
        documents as never hit, never listed, never reported.  Collider indices, bodies and tags in the records are those of the real world.  For
@@ -941,7 +941,7 @@ int nh_distance(nh_context* ctx, const nh_DistanceQuery* queries, uint32_t count
    aligned; count = 0 is a no-op that returns NH_OK and launches nothing.  Every byte of `count` results is written and nothing behind them.  Never
    allocates, never waits: ONE launch on the context's stream (timing label q_move).  An OBSERVER like nh_capsulecast (note 9): no view export, no
    settling of deferred gravity, no still step turned into a full one, no change to nh_Counts.
-   NOT BUILT: box movers; rotation during the move; gravity (step-up, ground snapping and slope limits are nh_walk, below; depenetration of a move that
+   NOT BUILT: rotation during the move (boxes move by nh_boxmove, below); gravity (step-up, ground snapping and slope limits are nh_walk, below; depenetration of a move that
    starts in overlap is nh_recover, below: recover, then move or walk); moving platforms (the velocity of what is hit); pushing dynamic bodies (queries are observers); the list of everything
    touched (last_hit is the last cast's record only).
    Cost: one lane per move, up to max_slides + 1 walks of nh_capsulecast's; a lane that has finished waits for the slowest of its wave.  Measured (one
@@ -1058,7 +1058,7 @@ int nh_recover(nh_context* ctx, const nh_Recover* queries, uint32_t count, nh_Re
    Returns NH_ERR_INVALID before any nh_query_build, for flags != 0, for count >= 2^30, and for count > 0 with `walks` or `results` null or not 16-byte
    aligned; count = 0 is a no-op that returns NH_OK and launches nothing.  Every byte of `count` results is written and nothing behind them.  Never
    allocates, never waits: ONE launch on the context's stream (timing label q_walk).  An OBSERVER like nh_move (note 9).
-   NOT BUILT: box movers; rotation during the walk; moving platforms (the velocity of what is stood on); pushing dynamic bodies (queries are observers);
+   NOT BUILT: rotation during the walk (boxes walk by nh_boxwalk, below); moving platforms (the velocity of what is stood on); pushing dynamic bodies (queries are observers);
    the list of everything touched (last_hit and ground are single records); gravity integration and velocities (the caller passes a displacement); a
    per-node AND word for the filter; queries on partitioned worlds; the `namespace nudge` extension in nudge_amd/compat; any change to nh_move's crease rule.
    Cost: one lane per walk, up to 21 walks of nh_capsulecast's; the lanes of a wave walk the tree together whatever phase each is in, and a lane that has
@@ -1079,6 +1079,64 @@ typedef struct nh_Walk { float origin[3]; float skin; float displacement[3]; uin
 typedef struct nh_WalkResult { float position[3]; uint32_t flags; float remaining[3]; uint32_t slides; nh_RayHit last_hit; nh_RayHit ground;
                                float step_up; float drop; uint32_t casts; uint32_t reserved; } nh_WalkResult;                                     /* 112 B */
 int nh_walk(nh_context* ctx, const nh_Walk* walks, uint32_t count, nh_WalkResult* results, uint32_t flags /* 0 */);
+
+/* nh_boxmove, nh_boxwalk: nh_move and nh_walk for swept ORIENTED BOXES -- a kinematic crate, a lift, a door, a vehicle hull, an axis-aligned character of
+   a voxel world (rotation = identity) -- against the world of the LAST nh_query_build or nh_query_refit, in ONE launch each.  nh_BoxMove is nh_BoxCast
+   field for field with `skin` where max_t is and `max_slides` where reserved is; `size` holds the half extents and (0, 0, 0) is a ray.  nh_BoxWalk is
+   nh_BoxMove followed by the last 32 bytes of nh_Walk (up, step_height, snap_distance, min_ground_up, options, reserved2); `reserved2` is not read.  The
+   results are nh_MoveResult and nh_WalkResult unchanged, with the same flag bits, NH_MOVE_MAX_SLIDES and NH_WALK_MAX_CASTS.  The box does not turn.
+   DEFINITION: nh_boxmove is nh_move's rules 1 - 7 word for word, and nh_boxwalk is nh_walk's phases A, U, F, D and C word for word, the climb rule
+   included, where every cast is the closest-hit answer nh_boxcast with flags 0 writes for { p, 1.0f, v, ignore_body, rotation, size }: nh_boxcast's
+   decode, reach rule, tie rule and start-overlap rule, under the context's layer filter (the per-query mask index is the record's index).  The arithmetic
+   between two casts is the same functions of nudge_amd/csrc/nh_query.h ("move", "walk"), which never see the shape: a cast's (hit, t, normal, collider)
+   is all they read.  One kernel template serves both shapes (k_q_move<Shape, .>, k_q_walk<Shape, .>).
+   INVALID RECORDS -- nh_boxmove: a non-finite origin or displacement; a non-finite or negative size component or skin; a size other than (0, 0, 0) with a
+   non-finite rotation; max_slides > NH_MOVE_MAX_SLIDES.  nh_boxwalk: those, and nh_walk's rules for up, step_height, snap_distance, min_ground_up and
+   options.  They are written exactly as nh_move and nh_walk write theirs (flags = NH_MOVE_INVALID / NH_WALK_INVALID, position = the bits of origin,
+   remaining = the bits of displacement, the hit records as the miss record with t = NaN, every count 0).  A size with one or two components 0 (a plate, a
+   rod) is a box and reads its rotation.  displacement = 0 is a valid no-op that makes no cast.
+   IDENTITIES (contracts):
+     1. nh_boxmove with max_slides = 0: last_hit holds byte for byte what nh_boxcast with flags 0 writes for { origin, 1.0f, displacement, ignore_body,
+        rotation, size };
+     2. size (0, 0, 0) does not read `rotation`, and its 64 result bytes are those of nh_move with radius = half_height = 0 and the other fields equal:
+        both are ray casts;
+     3. REPLAY for nh_boxmove: running the loop on the host, one nh_boxcast call per round and nh_q_move_advance between them, gives nh_boxmove's 64 bytes;
+     4. nh_boxwalk with step_height = snap_distance = min_ground_up = 0 writes nh_boxmove's 64 bytes for the record's first 64 bytes, and the miss
+        record as ground;
+     5. REPLAY for nh_boxwalk, with min_ground_up = 0: nh_boxmove calls for A, U, F and D, an nh_boxcast call for C, and nh_query.h's decisions
+        (nh_q_walk_phase_end, nh_q_walk_advance) between them give nh_boxwalk's 112 bytes (`blocked` is read off nh_boxmove's own REPLAY of A);
+     6. after nh_query_refit the bytes are those after an nh_query_build of the same arrays; nh_query_filter is honoured in all three modes;
+     7. a result without INVALID and START_OVERLAP never has casts > NH_WALK_MAX_CASTS (21); a GROUNDED result's ground.normal is walkable.
+   Both return NH_ERR_INVALID before any nh_query_build, for flags != 0, for count >= 2^30, and for count > 0 with the records or `results` null or not
+   16-byte aligned; count = 0 is a no-op that returns NH_OK and launches nothing.  Every byte of `count` results is written and nothing behind them.
+   Never allocate, never wait: ONE launch each on the context's stream (timing labels q_boxmove, q_boxwalk).  OBSERVERS like nh_move (note 9).
+   WHAT A BOX STANDS ON: its bottom face.  A box that stands on a slope meets it with an edge; the ground normal is still the slope's (the sweep's
+   separating axis), so WALKABLE and the climb rule mean what they mean for a capsule.  A step is climbed when the whole bottom face clears the riser.
+   NOT BUILT: rotation during a move; moving platforms; pushing dynamic bodies; the list of everything touched; a change to the crease rule; the
+   `namespace nudge` extension; queries on partitioned worlds; sphere movers as a call of their own (half_height = 0 in nh_move is one).
+   Cost: one lane per record around the box-box sweep, the heaviest leaf test of the library, instantiated once per kernel.  Registers on gfx950 (hipcc
+   -Rpass-analysis=kernel-resource-usage): k_q_move<box> 146 VGPRs (147 filtered) at 3 waves per SIMD, no scratch -- asked for nh_move's 4
+   waves it spills 28 - 32 bytes per lane; k_q_walk<box> 194 VGPRs (195 filtered) at 2 waves, no scratch -- at nh_walk's 3 waves it spills 56 - 60 bytes
+   per lane.  The capsule instantiations are unchanged: 128 VGPRs at 4 waves and 168 at 3.
+   Measured (one MI355X, one run, the landed config-2 world of 1,004,524 colliders, 1,048,576 records, max_slides 4, the library's kernel timers, medians of 7
+   blocks of 10 calls; tools/boxmove_rates.py -> profiles/boxmove_rates.log): nh_boxmove of the box (0.3, 0.5, 0.4) under random rotations
+   1.365 ms beside 0.661 ms for nh_boxcast on the first casts alone, 1.378 casts per move: 1.50 of (casts per move x the box cast's time) at 3 waves per SIMD,
+   where nh_move reported 1.03 at the cast's own 4.  nh_boxwalk of the upright box (0.3, 0.7, 0.3), snap 0.3, at 2 waves per SIMD: 2.817 ms with step_height 0
+   (2.26 casts per walk), slope limit off or 45 degrees; 5.131 ms with step_height 1.0 and the limit off (3.32 casts), 5.357 ms with the limit at 45 degrees
+   (3.70 casts), beside 0.757 ms for nh_boxcast on the first casts: 1.65, 1.65, 2.04 and 1.90 of (casts per walk x the box cast's time), where nh_walk
+   reported 1.29 - 1.66 (11.5 % of these walks start in overlap and end after one cast: they are in the means).  Filter off, beside the parent commit's library
+   loaded twice in the same process, per block this / parent with parent / parent beside it: nh_move 1.000 (0.991 .. 1.008) beside 0.997 (0.991 .. 1.001),
+   nh_walk 1.000 (0.994 .. 1.003) beside 1.001 (0.998 .. 1.004), nh_boxcast 1.002 (0.999 .. 1.011) beside 1.000 (0.996 .. 1.011), nh_capsulecast 1.000
+   (0.995 .. 1.005) beside 1.002 (0.996 .. 1.008): every median inside the parent's own spread.  NOT MEASURED YET: the filtered instantiations' times; what of
+   the ratios is the lower occupancy and what is divergence; a third wave for the walk with the kept slide parked in the result record. */
+typedef struct nh_BoxMove { float origin[3]; float skin; float displacement[3]; uint32_t ignore_body;
+                            float rotation[4]; float size[3]; uint32_t max_slides; } nh_BoxMove;                 /* 64 B  = nh_BoxCast, skin at max_t, max_slides at reserved */
+typedef struct nh_BoxWalk { float origin[3]; float skin; float displacement[3]; uint32_t ignore_body;
+                            float rotation[4]; float size[3]; uint32_t max_slides;                               /* = nh_BoxMove, 64 B */
+                            float up[3]; float step_height; float snap_distance; float min_ground_up;
+                            uint32_t options; uint32_t reserved2; } nh_BoxWalk;                                  /* 96 B  = nh_Walk's tail behind nh_BoxMove */
+int nh_boxmove(nh_context* ctx, const nh_BoxMove* moves, uint32_t count, nh_MoveResult* results, uint32_t flags /* 0 */);
+int nh_boxwalk(nh_context* ctx, const nh_BoxWalk* walks, uint32_t count, nh_WalkResult* results, uint32_t flags /* 0 */);
 
 /* ---- multi-GPU: one x-slab of a world per context ------------------------------------------------------------------------------------
    The world is cut into slabs along x, one rank (process, GPU, nh_context) per slab [lo, hi).  A rank's arrays hold

@@ -1206,12 +1206,13 @@ NH_HD float nh_q_all_pad(nh_f3 lo, nh_f3 hi, nh_f3 o) {
 // The sort key of a hit's t: the bits of t + 0.0f.  t >= 0, so -0 becomes +0 and the bits order as the floats do.
 NH_HD uint32_t nh_q_tbits(float t) { return nh_asuint(t + 0.0f); }
 
-// ---- move (nh_move): collide-and-slide of a swept capsule, the state between two capsule casts -----------------------------------------------------
+// ---- move (nh_move, nh_boxmove): collide-and-slide of a swept capsule or box, the state between two casts -----------------------------------------------------
 // These functions ARE the definition of nh_move (include/nudge_hip.h): k_q_move and the host's brute force (tests/hostoracle/hostmove.cpp) both run
 //     s = nh_q_move_begin(origin, displacement);
 //     while (nh_q_move_go(s)) { hit = the closest-hit capsule cast { s.p, 1.0f, s.v, ignore_body, rotation, radius, half_height };
 //                               if (!nh_q_move_advance(s, hit found, hit.t, hit.normal, skin, max_slides)) break; }
-// and write s.p, s.flags, s.v, s.slides and the last cast's record.  Every product is rounded before the sum it goes into (no fused multiply-add), and every
+// and write s.p, s.flags, s.v, s.slides and the last cast's record.  nh_boxmove (tests/hostoracle/hostboxmove.cpp) is the same loop around the closest-hit box cast
+// { s.p, 1.0f, s.v, ignore_body, rotation, size }: nothing below sees the shape.  Every product is rounded before the sum it goes into (no fused multiply-add), and every
 // dot and cross product is nh_dot / nh_cross of nh_math.h: (x*x + y*y) + z*z, left to right.
 // The flag bits are nh_MoveResult.flags' (nh_query.hip asserts that they are the header's NH_MOVE_*).
 #define NH_Q_MOVE_HIT 1u
@@ -1233,6 +1234,15 @@ NH_HD bool nh_q_move_valid(nh_f3 o, nh_f3 d, nh_quat q, float r, float hh, float
 	bool ok = nh_q_move_finite(o.x) && nh_q_move_finite(o.y) && nh_q_move_finite(o.z) && nh_q_move_finite(d.x) && nh_q_move_finite(d.y) && nh_q_move_finite(d.z);
 	ok = ok && nh_q_move_finite(r) && nh_q_move_finite(hh) && nh_q_move_finite(skin) && !(r < 0.0f) && !(hh < 0.0f) && !(skin < 0.0f);
 	ok = ok && (hh == 0.0f || (nh_q_move_finite(q.x) && nh_q_move_finite(q.y) && nh_q_move_finite(q.z) && nh_q_move_finite(q.s)));
+	return ok && max_slides <= NH_Q_MOVE_MAX_SLIDES;
+}
+
+// nh_boxmove's record (header, "Invalid records"): the half extents h in place of r and hh; `rotation` is read only where h is not (0, 0, 0)
+NH_HD bool nh_q_boxmove_valid(nh_f3 o, nh_f3 d, nh_quat q, nh_f3 h, float skin, uint32_t max_slides) {
+	bool ok = nh_q_move_finite(o.x) && nh_q_move_finite(o.y) && nh_q_move_finite(o.z) && nh_q_move_finite(d.x) && nh_q_move_finite(d.y) && nh_q_move_finite(d.z);
+	ok = ok && nh_q_move_finite(h.x) && nh_q_move_finite(h.y) && nh_q_move_finite(h.z) && nh_q_move_finite(skin);
+	ok = ok && !(h.x < 0.0f) && !(h.y < 0.0f) && !(h.z < 0.0f) && !(skin < 0.0f);
+	ok = ok && ((h.x == 0.0f && h.y == 0.0f && h.z == 0.0f) || (nh_q_move_finite(q.x) && nh_q_move_finite(q.y) && nh_q_move_finite(q.z) && nh_q_move_finite(q.s)));
 	return ok && max_slides <= NH_Q_MOVE_MAX_SLIDES;
 }
 
@@ -1301,7 +1311,8 @@ NH_HD bool nh_q_move_advance(nh_QMove& s, bool hit, float t, nh_f3 n, float skin
 //     s = nh_q_walk_begin(W);
 //     while (nh_q_walk_cast(s, W)) { hit = the closest-hit capsule cast { s.m.p, 1.0f, s.m.v, ignore_body, rotation, radius, half_height };
 //                                    nh_q_walk_advance(s, W, hit found, hit.t, hit's collider, hit.normal, the cast was valid); }
-// and write s.kp, s.kflags, s.kv, s.kslides, the records of s.klast and nh_q_walk_ground(s), s.step_up, nh_q_walk_drop(s, W) and s.casts.  A walk is up to five MOVE LOOPS ("move",
+// and write s.kp, s.kflags, s.kv, s.kslides, the records of s.klast and nh_q_walk_ground(s), s.step_up, nh_q_walk_drop(s, W) and s.casts.  (nh_boxwalk,
+// tests/hostoracle/hostboxwalk.cpp: the same with the closest-hit box cast { s.m.p, 1.0f, s.m.v, ignore_body, rotation, size }.)  A walk is up to five MOVE LOOPS ("move",
 // above: nh_q_move_begin / _go / _advance2 on s.m), one after the other, and the decisions between them; a lane is in one PHASE:
 //   A  slide    from origin along displacement, max_slides, under the climb rule.  Its end is KEPT (kp, kv, kslides, kflags, klast).  A taken hit (t > 0) whose
 //               normal is steep sets `blocked` (the phase AB).  START_OVERLAP: the walk ends here.  step_height > 0 and blocked: U.  Otherwise C.
@@ -1347,13 +1358,22 @@ struct nh_QWalk {
 	float step_up;
 };
 
-// The record's validity (header, "Invalid records"): nh_move's rules for the first 64 bytes and the walk's own
-NH_HD bool nh_q_walk_valid(const nh_QWalkIn& W, nh_quat q, float r, float hh) {
-	bool ok = nh_q_move_valid(W.origin, W.disp, q, r, hh, W.skin, W.max_slides);
+// The record's validity (header, "Invalid records"): nh_move's rules (nh_boxmove's for a box) for the first 64 bytes -- `head` -- and the walk's own for the
+// 32 bytes behind them, which both shapes share
+NH_HD bool nh_q_walk_tail_valid(const nh_QWalkIn& W, bool head) {
+	bool ok = head;
 	ok = ok && nh_q_move_finite(W.up.x) && nh_q_move_finite(W.up.y) && nh_q_move_finite(W.up.z) && nh_abs(nh_dot(W.up, W.up) - 1.0f) <= NH_Q_WALK_UP_EPS;
 	ok = ok && nh_q_move_finite(W.step_height) && !(W.step_height < 0.0f) && nh_q_move_finite(W.snap) && !(W.snap < 0.0f);
 	ok = ok && nh_q_move_finite(W.mgu) && W.mgu >= 0.0f && W.mgu <= 1.0f;
 	return ok && (W.options & ~NH_Q_WALK_PROBE_ONLY) == 0u;
+}
+
+NH_HD bool nh_q_walk_valid(const nh_QWalkIn& W, nh_quat q, float r, float hh) {
+	return nh_q_walk_tail_valid(W, nh_q_move_valid(W.origin, W.disp, q, r, hh, W.skin, W.max_slides));
+}
+
+NH_HD bool nh_q_boxwalk_valid(const nh_QWalkIn& W, nh_quat q, nh_f3 h) {
+	return nh_q_walk_tail_valid(W, nh_q_boxmove_valid(W.origin, W.disp, q, h, W.skin, W.max_slides));
 }
 
 NH_HD nh_QWalkHit nh_q_walk_miss() { nh_QWalkHit h; h.t = 1.0f; h.n = nh_make3(0.0f, 0.0f, 0.0f); h.c = NH_Q_WALK_NOBODY; return h; }

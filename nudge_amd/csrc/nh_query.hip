@@ -186,9 +186,10 @@ struct nh_QBox : nh_QCastHead {
 	nh_quat qa;
 	nh_f3 h, w;
 	bool ray;
-	__device__ __forceinline__ void read(const float4* __restrict__ cp) {
-		head(cp[0], cp[1]);
-		const float4 c2 = cp[2], c3 = cp[3];
+	__device__ __forceinline__ void read(const float4* __restrict__ cp) { set(cp[0], cp[1], cp[2], cp[3]); }
+	// the decode of the record's four 16-byte words, for k_q_move and k_q_walk as well, which build each of their casts in registers
+	__device__ __forceinline__ void set(float4 c0, float4 c1, float4 c2, float4 c3) {
+		head(c0, c1);
 		qa = { c2.x, c2.y, c2.z, c2.w }; h = nh_make3(c3.x, c3.y, c3.z);
 		ray = h.x == 0.0f && h.y == 0.0f && h.z == 0.0f;
 		ok = ok && nh_q_finite(h) && !(h.x < 0.0f) && !(h.y < 0.0f) && !(h.z < 0.0f) && (ray || nh_q_finite(qa));
@@ -334,25 +335,64 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
 }
 
 // ---- move -------------------------------------------------------------------------------------------------------------------------------------
-// nh_move: one lane per move.  The state machine is nh_query.h's ("move": nh_q_move_begin / _go / _advance, which the host's brute force runs as well);
-// each round's cast is the record { p, 1.0f, v, ignore_body, rotation, radius, half_height } decoded by nh_QCapsule::set and answered by nh_q_cast_one, the
-// body of k_q_capsulecast -- so a round's (t, collider, normal) are nh_capsulecast's for that record, under the same mask (the move's index).  The loop
+// nh_move, nh_boxmove: one lane per move, Shape = nh_QCapsule or nh_QBox (nh_QMover<Shape> holds what differs).  The state machine is nh_query.h's ("move": nh_q_move_begin / _go / _advance, which the host's brute force runs as well);
+// each round's cast is the record { p, 1.0f, v, ignore_body, rotation, radius, half_height } (for the box: rotation, size) decoded by Shape::set and answered by
+// nh_q_cast_one, the body of k_q_capsulecast / k_q_boxcast -- so a round's (t, collider, normal) are nh_capsulecast's / nh_boxcast's for that record, under the same mask (the move's index).  The loop
 // bound is a constant and every round is a walk that terminates, so the kernel terminates on any input.  A lane whose move has ended waits for the slowest
 // of its wave.  The record leaves as four 16-byte stores; `ok` of the last cast decides its miss t as it does in nh_capsulecast (a position
 // that overflowed makes an invalid cast: a miss with t = NaN).
 static_assert(NH_Q_MOVE_HIT == NH_MOVE_HIT && NH_Q_MOVE_START_OVERLAP == NH_MOVE_START_OVERLAP && NH_Q_MOVE_SLIDES_OUT == NH_MOVE_SLIDES_OUT &&
               NH_Q_MOVE_WEDGED == NH_MOVE_WEDGED && NH_Q_MOVE_MAX_SLIDES == NH_MOVE_MAX_SLIDES, "nh_query.h's move constants are the header's");
 static_assert(sizeof(nh_Move) == 64 && sizeof(nh_MoveResult) == 64, "nh_Move and nh_MoveResult are four 16-byte words each");
+static_assert(sizeof(nh_BoxMove) == 64 && offsetof(nh_BoxMove, skin) == offsetof(nh_BoxCast, max_t) && offsetof(nh_BoxMove, max_slides) == offsetof(nh_BoxCast, reserved) &&
+              offsetof(nh_BoxMove, size) == offsetof(nh_BoxCast, size), "nh_BoxMove is nh_BoxCast with skin at max_t and max_slides at reserved");
+static_assert(sizeof(nh_BoxWalk) == 96 && offsetof(nh_BoxWalk, up) == offsetof(nh_Walk, up) && offsetof(nh_BoxWalk, options) == offsetof(nh_Walk, options),
+              "nh_BoxWalk is nh_Walk's tail behind nh_BoxMove");
 
-template <bool FILTER>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k_q_move(const nh_Move* __restrict__ moves, uint32_t count, nh_MoveResult* __restrict__ results,
+// What nh_move / nh_walk and nh_boxmove / nh_boxwalk do not share: the record types, where max_slides sits in the record's fourth word (the shape's own
+// fields come first), the validity functions of nh_query.h, and the occupancy each kernel is asked for (its own comment).
+template <class Shape> struct nh_QMover;
+template <> struct nh_QMover<nh_QCapsule> {
+	typedef nh_Move Move;
+	typedef nh_Walk Walk;
+	__device__ __forceinline__ static uint32_t max_slides(float4 m3) { return __float_as_uint(m3.z); }
+	__device__ __forceinline__ static bool move_valid(nh_f3 o, nh_f3 d, float4 m2, float4 m3, float skin, uint32_t max_slides) {
+		return nh_q_move_valid(o, d, nh_quat{ m2.x, m2.y, m2.z, m2.w }, m3.x, m3.y, skin, max_slides);
+	}
+	__device__ __forceinline__ static bool walk_valid(const nh_QWalkIn& W, float4 m2, float4 m3) { return nh_q_walk_valid(W, nh_quat{ m2.x, m2.y, m2.z, m2.w }, m3.x, m3.y); }
+};
+template <> struct nh_QMover<nh_QBox> {
+	typedef nh_BoxMove Move;
+	typedef nh_BoxWalk Walk;
+	__device__ __forceinline__ static uint32_t max_slides(float4 m3) { return __float_as_uint(m3.w); }
+	__device__ __forceinline__ static bool move_valid(nh_f3 o, nh_f3 d, float4 m2, float4 m3, float skin, uint32_t max_slides) {
+		return nh_q_boxmove_valid(o, d, nh_quat{ m2.x, m2.y, m2.z, m2.w }, nh_make3(m3.x, m3.y, m3.z), skin, max_slides);
+	}
+	__device__ __forceinline__ static bool walk_valid(const nh_QWalkIn& W, float4 m2, float4 m3) {
+		return nh_q_boxwalk_valid(W, nh_quat{ m2.x, m2.y, m2.z, m2.w }, nh_make3(m3.x, m3.y, m3.z));
+	}
+};
+// waves per SIMD asked for: the capsule's 4 (k_q_capsulecast's).  The box move holds a move's state across the box-box sweep: 146 / 147 VGPRs (filter off / on) at 3
+// waves, no scratch; asked for 4 waves the compiler spills 28 / 32 bytes per lane (-DNH_Q_BOXMOVE_WAVES=4 -DNH_Q_BOXMOVE_WAVES_FILTER=4 reproduces it)
+#ifndef NH_Q_BOXMOVE_WAVES
+#define NH_Q_BOXMOVE_WAVES 3
+#endif
+#ifndef NH_Q_BOXMOVE_WAVES_FILTER
+#define NH_Q_BOXMOVE_WAVES_FILTER 3
+#endif
+template <class Shape> constexpr int nh_q_move_waves(bool) { return 4; }
+template <> constexpr int nh_q_move_waves<nh_QBox>(bool filter) { return filter ? NH_Q_BOXMOVE_WAVES_FILTER : NH_Q_BOXMOVE_WAVES; }
+
+template <class Shape, bool FILTER>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(nh_q_move_waves<Shape>(FILTER)))) void k_q_move(const typename nh_QMover<Shape>::Move* __restrict__ moves, uint32_t count,
+                                                   nh_MoveResult* __restrict__ results,
                                                    const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox, nh_QFilter F) {
 	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
 		const float4* mp = reinterpret_cast<const float4*>(moves + i);
 		const float4 m0 = mp[0], m1 = mp[1], m2 = mp[2], m3 = mp[3];
 		const float skin = m0.w;
-		const uint32_t max_slides = __float_as_uint(m3.z);
-		const bool valid = nh_q_move_valid(nh_make3(m0.x, m0.y, m0.z), nh_make3(m1.x, m1.y, m1.z), nh_quat{ m2.x, m2.y, m2.z, m2.w }, m3.x, m3.y, skin, max_slides);
+		const uint32_t max_slides = nh_QMover<Shape>::max_slides(m3);
+		const bool valid = nh_QMover<Shape>::move_valid(nh_make3(m0.x, m0.y, m0.z), nh_make3(m1.x, m1.y, m1.z), m2, m3, skin, max_slides);
 		nh_QMove s = nh_q_move_begin(nh_make3(m0.x, m0.y, m0.z), nh_make3(m1.x, m1.y, m1.z));
 		const uint32_t fm = FILTER ? F.of(i) : 0u;
 		float bt = 1.0f;
@@ -361,7 +401,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
 		bool ok = valid;
 		for (uint32_t round = 0u; round <= NH_MOVE_MAX_SLIDES; ++round) {
 			if (!valid || !nh_q_move_go(s)) break;
-			nh_QCapsule k;
+			Shape k;
 			k.set(make_float4(s.p.x, s.p.y, s.p.z, 1.0f), make_float4(s.v.x, s.v.y, s.v.z, m1.w), m2, m3);
 			nh_q_cast_one<FILTER>(k, nodes, rec, n, nbox, 0u, F, fm, bt, bc, bn);
 			ok = k.ok;
@@ -375,10 +415,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
 }
 
 // ---- walk -------------------------------------------------------------------------------------------------------------------------------------
-// nh_walk: one lane per walk.  The phase machine is nh_query.h's ("walk": nh_q_walk_begin / _cast / _advance, which the host's brute force runs as well): up
+// nh_walk, nh_boxwalk: one lane per walk, Shape = nh_QCapsule or nh_QBox.  The phase machine is nh_query.h's ("walk": nh_q_walk_begin / _cast / _advance, which the host's brute force runs as well): up
 // to five move loops one after the other (slide, up, forward, down, probe), each cast the record { s.m.p, 1.0f, s.m.v, ignore_body, rotation, radius,
-// half_height } decoded by nh_QCapsule::set and answered by nh_q_cast_one, the body of k_q_capsulecast.  There is ONE call site of the cast in ONE loop: the
-// lane's phase only picks the origin and the direction, so the capsule sweep is instantiated once and the lanes of a wave walk the tree together whatever
+// half_height } (for the box: rotation, size) decoded by Shape::set and answered by nh_q_cast_one, the body of k_q_capsulecast / k_q_boxcast.  There is ONE call site of the
+// cast in ONE loop: the lane's phase only picks the origin and the direction, so the capsule sweep -- or the box-box SAT sweep -- is instantiated once and the lanes of a wave walk the tree together whatever
 // phase each is in.  The loop bound is the constant NH_WALK_MAX_CASTS and every round is a walk that terminates, so the kernel terminates on any input.
 // The record leaves as seven 16-byte stores.
 static_assert(NH_Q_WALK_STEPPED == NH_WALK_STEPPED && NH_Q_WALK_GROUNDED == NH_WALK_GROUNDED && NH_Q_WALK_SNAPPED == NH_WALK_SNAPPED && NH_Q_WALK_STEEP == NH_WALK_STEEP &&
@@ -393,23 +433,35 @@ static_assert(sizeof(nh_Walk) == 96 && sizeof(nh_WalkResult) == 112 && offsetof(
 #define NH_Q_WALK_WAVES 3
 #endif
 
-template <bool FILTER>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NH_Q_WALK_WAVES))) void k_q_walk(const nh_Walk* __restrict__ walks, uint32_t count, nh_WalkResult* __restrict__ results,
+// (The box walk holds a walk's state across the box-box sweep: 194 / 195 VGPRs (filter off / on) at 2 waves, no scratch; at nh_walk's 3 waves the compiler spills 56 / 60
+// bytes per lane, at 4 waves 216 / 228.  DESIGN 10.19; -DNH_Q_BOXWALK_WAVES=3 -DNH_Q_BOXWALK_WAVES_FILTER=3 -Rpass-analysis=kernel-resource-usage reproduces the row.)
+#ifndef NH_Q_BOXWALK_WAVES
+#define NH_Q_BOXWALK_WAVES 2
+#endif
+#ifndef NH_Q_BOXWALK_WAVES_FILTER
+#define NH_Q_BOXWALK_WAVES_FILTER 2
+#endif
+template <class Shape> constexpr int nh_q_walk_waves(bool) { return NH_Q_WALK_WAVES; }
+template <> constexpr int nh_q_walk_waves<nh_QBox>(bool filter) { return filter ? NH_Q_BOXWALK_WAVES_FILTER : NH_Q_BOXWALK_WAVES; }
+
+template <class Shape, bool FILTER>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(nh_q_walk_waves<Shape>(FILTER)))) void k_q_walk(const typename nh_QMover<Shape>::Walk* __restrict__ walks, uint32_t count,
+                                                   nh_WalkResult* __restrict__ results,
                                                    const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox, nh_QFilter F) {
 	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
 		const float4* wp = reinterpret_cast<const float4*>(walks + i);
 		const float4 m0 = wp[0], m1 = wp[1], m2 = wp[2], m3 = wp[3], m4 = wp[4], m5 = wp[5];
 		nh_QWalkIn W;
 		W.origin = nh_make3(m0.x, m0.y, m0.z); W.skin = m0.w;
-		W.disp = nh_make3(m1.x, m1.y, m1.z); W.max_slides = __float_as_uint(m3.z);
+		W.disp = nh_make3(m1.x, m1.y, m1.z); W.max_slides = nh_QMover<Shape>::max_slides(m3);
 		W.up = nh_make3(m4.x, m4.y, m4.z); W.step_height = m4.w;
 		W.snap = m5.x; W.mgu = m5.y; W.options = __float_as_uint(m5.z);
-		const bool valid = nh_q_walk_valid(W, nh_quat{ m2.x, m2.y, m2.z, m2.w }, m3.x, m3.y);
+		const bool valid = nh_QMover<Shape>::walk_valid(W, m2, m3);
 		nh_QWalk s = nh_q_walk_begin(W);
 		const uint32_t fm = FILTER ? F.of(i) : 0u;
 		for (uint32_t round = 0u; round < NH_WALK_MAX_CASTS; ++round) {
 			if (!valid || !nh_q_walk_cast(s, W)) break;
-			nh_QCapsule k;
+			Shape k;
 			k.set(make_float4(s.m.p.x, s.m.p.y, s.m.p.z, 1.0f), make_float4(s.m.v.x, s.m.v.y, s.m.v.z, m1.w), m2, m3);
 			float bt;
 			uint32_t bc;
@@ -1095,7 +1147,19 @@ extern "C" int nh_move(nh_context* ctx, const nh_Move* moves, uint32_t count, nh
 	nh_QueryState* q = ctx->query;
 	bool on;
 	const nh_QFilter F = nh_query_filter_of(q, &on);
-	NH_LAUNCH(ctx, "q_move", on ? k_q_move<true> : k_q_move<false>, nh_grid_for(count, 256, 1u << 20), 256, moves, count, results, q->nodes, q->rec, q->n, q->nbox, F);
+	NH_LAUNCH(ctx, "q_move", (on ? k_q_move<nh_QCapsule, true> : k_q_move<nh_QCapsule, false>), nh_grid_for(count, 256, 1u << 20), 256, moves, count, results, q->nodes, q->rec,
+	          q->n, q->nbox, F);
+	return NH_OK;
+}
+
+// nh_move's checks, launch and kernel, with the box cast in the loop
+extern "C" int nh_boxmove(nh_context* ctx, const nh_BoxMove* moves, uint32_t count, nh_MoveResult* results, uint32_t flags) {
+	{ const int rc = nh_query_call(ctx, flags, 0u, 0u, 0u, count, 1u << 30, moves, results, nullptr); if (rc || count == 0u) return rc; }
+	nh_QueryState* q = ctx->query;
+	bool on;
+	const nh_QFilter F = nh_query_filter_of(q, &on);
+	NH_LAUNCH(ctx, "q_boxmove", (on ? k_q_move<nh_QBox, true> : k_q_move<nh_QBox, false>), nh_grid_for(count, 256, 1u << 20), 256, moves, count, results, q->nodes, q->rec,
+	          q->n, q->nbox, F);
 	return NH_OK;
 }
 
@@ -1105,7 +1169,19 @@ extern "C" int nh_walk(nh_context* ctx, const nh_Walk* walks, uint32_t count, nh
 	nh_QueryState* q = ctx->query;
 	bool on;
 	const nh_QFilter F = nh_query_filter_of(q, &on);
-	NH_LAUNCH(ctx, "q_walk", on ? k_q_walk<true> : k_q_walk<false>, nh_grid_for(count, 256, 1u << 20), 256, walks, count, results, q->nodes, q->rec, q->n, q->nbox, F);
+	NH_LAUNCH(ctx, "q_walk", (on ? k_q_walk<nh_QCapsule, true> : k_q_walk<nh_QCapsule, false>), nh_grid_for(count, 256, 1u << 20), 256, walks, count, results, q->nodes, q->rec,
+	          q->n, q->nbox, F);
+	return NH_OK;
+}
+
+// nh_walk's checks, launch and kernel, with the box cast in the loop
+extern "C" int nh_boxwalk(nh_context* ctx, const nh_BoxWalk* walks, uint32_t count, nh_WalkResult* results, uint32_t flags) {
+	{ const int rc = nh_query_call(ctx, flags, 0u, 0u, 0u, count, 1u << 30, walks, results, nullptr); if (rc || count == 0u) return rc; }
+	nh_QueryState* q = ctx->query;
+	bool on;
+	const nh_QFilter F = nh_query_filter_of(q, &on);
+	NH_LAUNCH(ctx, "q_boxwalk", (on ? k_q_walk<nh_QBox, true> : k_q_walk<nh_QBox, false>), nh_grid_for(count, 256, 1u << 20), 256, walks, count, results, q->nodes, q->rec,
+	          q->n, q->nbox, F);
 	return NH_OK;
 }
 

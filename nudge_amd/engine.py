@@ -43,7 +43,7 @@ EXPORTS = [
     "nh_partition_top_speed", "nh_partition_set_peer_speeds", "nh_partition_refresh_is_quiet", "nh_partition_mark_ghosts", "nh_partition_pack_deltas", "nh_partition_unpack_deltas",
     "nh_partition_pack_momentum", "nh_partition_unpack_momentum", "nh_partition_exchange_iteration", "nh_partition_unpack_ghosts", "nh_partition_pack_step", "nh_partition_unpack_step", "nh_partition_choose_cut", "nh_partition_set_cut",
     "nh_partition_set_transport", "nh_partition_exchange_step", "nh_partition_step", "nh_partition_transport_check", "nh_partition_transport_result", "nh_set_first_ghost_body",
-    "nh_query_build", "nh_query_refit", "nh_query_stats", "nh_raycast", "nh_overlap", "nh_penetration", "nh_region", "nh_spherecast", "nh_raycast_all", "nh_spherecast_all", "nh_boxcast_all", "nh_capsulecast_all", "nh_boxcast", "nh_capsulecast", "nh_closest", "nh_closest_k", "nh_distance", "nh_move", "nh_recover", "nh_walk",
+    "nh_query_build", "nh_query_refit", "nh_query_stats", "nh_raycast", "nh_overlap", "nh_penetration", "nh_region", "nh_spherecast", "nh_raycast_all", "nh_spherecast_all", "nh_boxcast_all", "nh_capsulecast_all", "nh_boxcast", "nh_capsulecast", "nh_closest", "nh_closest_k", "nh_distance", "nh_move", "nh_recover", "nh_walk", "nh_boxmove", "nh_boxwalk",
     "nh_raycast_k", "nh_spherecast_k", "nh_boxcast_k", "nh_capsulecast_k",
     "nh_query_set_layers", "nh_query_filter", "nh_query_layer_info",
 ]
@@ -182,6 +182,11 @@ WALK_RESULT = np.dtype(MOVE_RESULT.descr + [("ground", RAY_HIT), ("step_up", "<f
 NH_WALK_MAX_CASTS = 2 * (NH_MOVE_MAX_SLIDES + 1) + 3
 NH_WALK_STEPPED, NH_WALK_GROUNDED, NH_WALK_SNAPPED, NH_WALK_STEEP, NH_WALK_ON_STEEP, NH_WALK_INVALID = 0x10, 0x20, 0x40, 0x80, 0x100, 0x80000000
 NH_WALK_PROBE_ONLY = 1
+# nh_boxmove, nh_boxwalk (include/nudge_hip.h): nh_BoxCast with `skin` where max_t is and `max_slides` where reserved is, and nh_Walk's tail behind it; the
+# results are MOVE_RESULT and WALK_RESULT
+BOX_MOVE = np.dtype([("origin", "<f4", 3), ("skin", "<f4"), ("displacement", "<f4", 3), ("ignore_body", "<u4"), ("rotation", "<f4", 4), ("size", "<f4", 3),
+                     ("max_slides", "<u4")])
+BOX_WALK = np.dtype(BOX_MOVE.descr + WALK.descr[len(MOVE.descr):])
 # nh_recover (include/nudge_hip.h): nh_OverlapQuery followed by `skin` and `max_iterations`; nh_RecoverResult.flags
 RECOVER = np.dtype([("center", "<f4", 3), ("shape", "<u4"), ("rotation", "<f4", 4), ("size", "<f4", 3), ("ignore_body", "<u4"), ("skin", "<f4"),
                     ("max_iterations", "<u4"), ("reserved", "<u4", 2)])
@@ -337,6 +342,10 @@ def lib():
         # (likewise nh_walk: World.walk then raises AttributeError)
         if hasattr(L, "nh_walk"):
             L.nh_walk.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
+        # (likewise nh_boxmove and nh_boxwalk: World.boxmove and World.boxwalk then raise AttributeError)
+        if hasattr(L, "nh_boxmove"):
+            L.nh_boxmove.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
+            L.nh_boxwalk.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
         L.nh_overlap.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
         L.nh_penetration.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
         # (an older build of the library, loaded through NUDGE_HIP_LIBRARY for an A/B, has no nh_region: World.region then raises AttributeError)
@@ -1139,7 +1148,11 @@ class World:
         torch = self.torch
         rec, n = self._capsule_casts("move", origins, displacements, radius, half_height, rotations, skin, ignore_body)
         rec.view(torch.int32)[:, 14] = torch.as_tensor(max_slides, dtype=torch.int64, device=self.dev).to(torch.int32)
-        raw = self.move_records(rec)
+        return self._move_results(self.move_records(rec), n, synchronize)
+
+    def _move_results(self, raw, n, synchronize):
+        """The dict move() and boxmove() return, from the nh_MoveResult records `raw`."""
+        torch = self.torch
         f = raw.view(torch.float32).reshape(n, 16)
         u = raw.view(torch.int32).reshape(n, 16).to(torch.int64) & 0xFFFFFFFF
         out = dict(position=f[:, 0:3], remaining=f[:, 4:7], flags=u[:, 3], slides=u[:, 7], last_hit=self._ray_hits(raw.reshape(n, 64)[:, 32:].contiguous(), False),
@@ -1147,6 +1160,26 @@ class World:
         if synchronize:
             torch.cuda.current_stream(self.dev).synchronize()
         return out
+
+    def boxmove_records(self, records, results=None):
+        """nh_boxmove on records already laid out as nh_BoxMove: `records` a contiguous device tensor of count x 64 bytes (any dtype).  Returns the
+        count x 64-byte uint8 device tensor of nh_MoveResult records (`results`, or a new one)."""
+        torch = self.torch
+        n = records.numel() * records.element_size() // 64
+        if results is None:
+            results = torch.empty((n, 64), dtype=torch.uint8, device=self.dev)
+        _check(self.L, self.L.nh_boxmove(self.ctx, C.c_void_p(records.data_ptr() if n else 0), n, C.c_void_p(results.data_ptr() if n else 0), 0), "nh_boxmove")
+        return results
+
+    def boxmove(self, origins, displacements, half_extents, rotations=None, skin=0.01, max_slides=4, ignore_body=None, synchronize=False):
+        """Collide-and-slide for oriented boxes (nh_boxmove) against the last query_build(): move() with boxcast()'s shape -- `half_extents` ((n, 3)
+        or (3,)) and `rotations` ((n, 4) or (4,) quaternions (x, y, z, s); None = identity, axis-aligned); the box does not turn while it moves.
+        `skin`, `max_slides`, `ignore_body` and the returned dict are move()'s, with boxcast()'s dict as `last_hit`.  Nothing waits for the device
+        unless `synchronize`."""
+        torch = self.torch
+        rec, n = self._box_casts("boxmove", origins, displacements, half_extents, rotations, skin, ignore_body)
+        rec.view(torch.int32)[:, 15] = torch.as_tensor(max_slides, dtype=torch.int64, device=self.dev).to(torch.int32)
+        return self._move_results(self.boxmove_records(rec), n, synchronize)
 
     def walk_records(self, records, results=None):
         """nh_walk on records already laid out as nh_Walk: `records` a contiguous device tensor of count x 96 bytes (any dtype).  Returns the
@@ -1173,6 +1206,12 @@ class World:
             raise ValueError("walk: give max_slope_degrees or min_ground_up, not both")
         head, n = self._capsule_casts("walk", origins, displacements, radius, half_height, rotations, skin, ignore_body)
         head.view(torch.int32)[:, 14] = torch.as_tensor(max_slides, dtype=torch.int64, device=self.dev).to(torch.int32)
+        rec = self._walk_tail(head, n, up, step_height, snap_distance, max_slope_degrees, min_ground_up, probe_only)
+        return self._walk_results(self.walk_records(rec), n, synchronize)
+
+    def _walk_tail(self, head, n, up, step_height, snap_distance, max_slope_degrees, min_ground_up, probe_only):
+        """nh_Walk / nh_BoxWalk records: the 64-byte `head` records followed by walk()'s rules."""
+        torch = self.torch
         rec = torch.zeros((n, 24), dtype=torch.float32, device=self.dev)
         rec[:, 0:16] = head
         rec[:, 16:19] = torch.as_tensor(up, dtype=torch.float32, device=self.dev).reshape(-1, 3)
@@ -1182,7 +1221,11 @@ class World:
             min_ground_up = torch.cos(torch.deg2rad(torch.as_tensor(max_slope_degrees, dtype=torch.float64, device=self.dev)))
         rec[:, 21] = torch.as_tensor(0.0 if min_ground_up is None else min_ground_up, device=self.dev).to(torch.float32).reshape(-1)
         rec.view(torch.int32)[:, 22] = torch.as_tensor(probe_only, device=self.dev).to(torch.int32).reshape(-1) & 1
-        raw = self.walk_records(rec)
+        return rec
+
+    def _walk_results(self, raw, n, synchronize):
+        """The dict walk() and boxwalk() return, from the nh_WalkResult records `raw`."""
+        torch = self.torch
         f = raw.view(torch.float32).reshape(n, 28)
         u = raw.view(torch.int32).reshape(n, 28).to(torch.int64) & 0xFFFFFFFF
         bytes_ = raw.reshape(n, 112)
@@ -1191,6 +1234,29 @@ class World:
         if synchronize:
             torch.cuda.current_stream(self.dev).synchronize()
         return out
+
+    def boxwalk_records(self, records, results=None):
+        """nh_boxwalk on records already laid out as nh_BoxWalk: `records` a contiguous device tensor of count x 96 bytes (any dtype).  Returns the
+        count x 112-byte uint8 device tensor of nh_WalkResult records (`results`, or a new one)."""
+        torch = self.torch
+        n = records.numel() * records.element_size() // 96
+        if results is None:
+            results = torch.empty((n, 112), dtype=torch.uint8, device=self.dev)
+        _check(self.L, self.L.nh_boxwalk(self.ctx, C.c_void_p(records.data_ptr() if n else 0), n, C.c_void_p(results.data_ptr() if n else 0), 0), "nh_boxwalk")
+        return results
+
+    def boxwalk(self, origins, displacements, half_extents, rotations=None, skin=0.01, max_slides=4, ignore_body=None, up=(0.0, 1.0, 0.0),
+                step_height=0.0, snap_distance=0.0, max_slope_degrees=None, min_ground_up=None, probe_only=False, synchronize=False):
+        """A grounded step for oriented boxes (nh_boxwalk) against the last query_build(): walk() with boxmove()'s shape (`half_extents`, `rotations`;
+        None = identity: an axis-aligned character).  Every other argument and the returned dict are walk()'s, with boxcast()'s dicts as `last_hit`
+        and `ground`.  Nothing waits for the device unless `synchronize`."""
+        torch = self.torch
+        if max_slope_degrees is not None and min_ground_up is not None:
+            raise ValueError("boxwalk: give max_slope_degrees or min_ground_up, not both")
+        head, n = self._box_casts("boxwalk", origins, displacements, half_extents, rotations, skin, ignore_body)
+        head.view(torch.int32)[:, 15] = torch.as_tensor(max_slides, dtype=torch.int64, device=self.dev).to(torch.int32)
+        rec = self._walk_tail(head, n, up, step_height, snap_distance, max_slope_degrees, min_ground_up, probe_only)
+        return self._walk_results(self.boxwalk_records(rec), n, synchronize)
 
     def recover_records(self, records, results=None):
         """nh_recover on records already laid out as nh_Recover: `records` a contiguous device tensor of count x 64 bytes (any dtype).  Returns the
