@@ -1207,11 +1207,11 @@ NH_HD float nh_q_all_pad(nh_f3 lo, nh_f3 hi, nh_f3 o) {
 NH_HD uint32_t nh_q_tbits(float t) { return nh_asuint(t + 0.0f); }
 
 // ---- move (nh_move, nh_boxmove): collide-and-slide of a swept capsule or box, the state between two casts -----------------------------------------------------
-// These functions ARE the definition of nh_move (include/nudge_hip.h): k_q_move and the host's brute force (tests/hostoracle/hostmove.cpp) both run
+// These functions ARE the definition of nh_move (include/nudge_hip.h): k_q_move and the host's brute force (tests/hostoracle/hostmover.cpp) both run
 //     s = nh_q_move_begin(origin, displacement);
 //     while (nh_q_move_go(s)) { hit = the closest-hit capsule cast { s.p, 1.0f, s.v, ignore_body, rotation, radius, half_height };
 //                               if (!nh_q_move_advance(s, hit found, hit.t, hit.normal, skin, max_slides)) break; }
-// and write s.p, s.flags, s.v, s.slides and the last cast's record.  nh_boxmove (tests/hostoracle/hostboxmove.cpp) is the same loop around the closest-hit box cast
+// and write s.p, s.flags, s.v, s.slides and the last cast's record.  nh_boxmove (the same file) is the same loop around the closest-hit box cast
 // { s.p, 1.0f, s.v, ignore_body, rotation, size }: nothing below sees the shape.  Every product is rounded before the sum it goes into (no fused multiply-add), and every
 // dot and cross product is nh_dot / nh_cross of nh_math.h: (x*x + y*y) + z*z, left to right.
 // The flag bits are nh_MoveResult.flags' (nh_query.hip asserts that they are the header's NH_MOVE_*).
@@ -1307,12 +1307,12 @@ NH_HD bool nh_q_move_advance2(nh_QMove& s, bool hit, float t, nh_f3 n, nh_f3 ns,
 NH_HD bool nh_q_move_advance(nh_QMove& s, bool hit, float t, nh_f3 n, float skin, uint32_t max_slides) { return nh_q_move_advance2(s, hit, t, n, n, skin, max_slides); }
 
 // ---- walk (nh_walk): a grounded character step, the state between two capsule casts ---------------------------------------------------------------------
-// These functions ARE the definition of nh_walk (include/nudge_hip.h): k_q_walk and the host's brute force (tests/hostoracle/hostwalk.cpp) both run
+// These functions ARE the definition of nh_walk (include/nudge_hip.h): k_q_walk and the host's brute force (tests/hostoracle/hostmover.cpp) both run
 //     s = nh_q_walk_begin(W);
 //     while (nh_q_walk_cast(s, W)) { hit = the closest-hit capsule cast { s.m.p, 1.0f, s.m.v, ignore_body, rotation, radius, half_height };
 //                                    nh_q_walk_advance(s, W, hit found, hit.t, hit's collider, hit.normal, the cast was valid); }
 // and write s.kp, s.kflags, s.kv, s.kslides, the records of s.klast and nh_q_walk_ground(s), s.step_up, nh_q_walk_drop(s, W) and s.casts.  (nh_boxwalk,
-// tests/hostoracle/hostboxwalk.cpp: the same with the closest-hit box cast { s.m.p, 1.0f, s.m.v, ignore_body, rotation, size }.)  A walk is up to five MOVE LOOPS ("move",
+// the same file: the same with the closest-hit box cast { s.m.p, 1.0f, s.m.v, ignore_body, rotation, size }.)  A walk is up to five MOVE LOOPS ("move",
 // above: nh_q_move_begin / _go / _advance2 on s.m), one after the other, and the decisions between them; a lane is in one PHASE:
 //   A  slide    from origin along displacement, max_slides, under the climb rule.  Its end is KEPT (kp, kv, kslides, kflags, klast).  A taken hit (t > 0) whose
 //               normal is steep sets `blocked` (the phase AB).  START_OVERLAP: the walk ends here.  step_height > 0 and blocked: U.  Otherwise C.

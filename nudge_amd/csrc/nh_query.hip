@@ -1141,48 +1141,35 @@ extern "C" int nh_boxcast(nh_context* ctx, const nh_BoxCast* casts, uint32_t cou
 	return nh_cast(ctx, "q_boxcast", k_q_boxcast<false>, k_q_boxcast<true>, casts, count, hits, flags);
 }
 
-// One launch, nh_distance's checks in nh_distance's order; no allocation, no wait.
+// The four movers: one record type, one result type and one kernel pair each.  One launch, nh_distance's checks in nh_distance's order; no allocation, no wait.
+// (`filtered` before `plain`: the callers name the instantiations in the order the code object has always held them.)
+template <class In, class Out>
+using nh_MoverKernel = void (*)(const In*, uint32_t, Out*, const nh_QNode*, const nh_QRec*, uint32_t, uint32_t, nh_QFilter);
+template <class In, class Out>
+static int nh_mover(nh_context* ctx, const char* label, nh_MoverKernel<In, Out> filtered, nh_MoverKernel<In, Out> plain, const In* in, uint32_t count, Out* out,
+                    uint32_t flags) {
+	{ const int rc = nh_query_call(ctx, flags, 0u, 0u, 0u, count, 1u << 30, in, out, nullptr); if (rc || count == 0u) return rc; }
+	nh_QueryState* q = ctx->query;
+	bool on;
+	const nh_QFilter F = nh_query_filter_of(q, &on);
+	NH_LAUNCH(ctx, label, on ? filtered : plain, nh_grid_for(count, 256, 1u << 20), 256, in, count, out, q->nodes, q->rec, q->n, q->nbox, F);
+	return NH_OK;
+}
+
 extern "C" int nh_move(nh_context* ctx, const nh_Move* moves, uint32_t count, nh_MoveResult* results, uint32_t flags) {
-	{ const int rc = nh_query_call(ctx, flags, 0u, 0u, 0u, count, 1u << 30, moves, results, nullptr); if (rc || count == 0u) return rc; }
-	nh_QueryState* q = ctx->query;
-	bool on;
-	const nh_QFilter F = nh_query_filter_of(q, &on);
-	NH_LAUNCH(ctx, "q_move", (on ? k_q_move<nh_QCapsule, true> : k_q_move<nh_QCapsule, false>), nh_grid_for(count, 256, 1u << 20), 256, moves, count, results, q->nodes, q->rec,
-	          q->n, q->nbox, F);
-	return NH_OK;
+	return nh_mover(ctx, "q_move", k_q_move<nh_QCapsule, true>, k_q_move<nh_QCapsule, false>, moves, count, results, flags);
 }
 
-// nh_move's checks, launch and kernel, with the box cast in the loop
 extern "C" int nh_boxmove(nh_context* ctx, const nh_BoxMove* moves, uint32_t count, nh_MoveResult* results, uint32_t flags) {
-	{ const int rc = nh_query_call(ctx, flags, 0u, 0u, 0u, count, 1u << 30, moves, results, nullptr); if (rc || count == 0u) return rc; }
-	nh_QueryState* q = ctx->query;
-	bool on;
-	const nh_QFilter F = nh_query_filter_of(q, &on);
-	NH_LAUNCH(ctx, "q_boxmove", (on ? k_q_move<nh_QBox, true> : k_q_move<nh_QBox, false>), nh_grid_for(count, 256, 1u << 20), 256, moves, count, results, q->nodes, q->rec,
-	          q->n, q->nbox, F);
-	return NH_OK;
+	return nh_mover(ctx, "q_boxmove", k_q_move<nh_QBox, true>, k_q_move<nh_QBox, false>, moves, count, results, flags);
 }
 
-// One launch, nh_move's checks in nh_move's order; no allocation, no wait.
 extern "C" int nh_walk(nh_context* ctx, const nh_Walk* walks, uint32_t count, nh_WalkResult* results, uint32_t flags) {
-	{ const int rc = nh_query_call(ctx, flags, 0u, 0u, 0u, count, 1u << 30, walks, results, nullptr); if (rc || count == 0u) return rc; }
-	nh_QueryState* q = ctx->query;
-	bool on;
-	const nh_QFilter F = nh_query_filter_of(q, &on);
-	NH_LAUNCH(ctx, "q_walk", (on ? k_q_walk<nh_QCapsule, true> : k_q_walk<nh_QCapsule, false>), nh_grid_for(count, 256, 1u << 20), 256, walks, count, results, q->nodes, q->rec,
-	          q->n, q->nbox, F);
-	return NH_OK;
+	return nh_mover(ctx, "q_walk", k_q_walk<nh_QCapsule, true>, k_q_walk<nh_QCapsule, false>, walks, count, results, flags);
 }
 
-// nh_walk's checks, launch and kernel, with the box cast in the loop
 extern "C" int nh_boxwalk(nh_context* ctx, const nh_BoxWalk* walks, uint32_t count, nh_WalkResult* results, uint32_t flags) {
-	{ const int rc = nh_query_call(ctx, flags, 0u, 0u, 0u, count, 1u << 30, walks, results, nullptr); if (rc || count == 0u) return rc; }
-	nh_QueryState* q = ctx->query;
-	bool on;
-	const nh_QFilter F = nh_query_filter_of(q, &on);
-	NH_LAUNCH(ctx, "q_boxwalk", (on ? k_q_walk<nh_QBox, true> : k_q_walk<nh_QBox, false>), nh_grid_for(count, 256, 1u << 20), 256, walks, count, results, q->nodes, q->rec,
-	          q->n, q->nbox, F);
-	return NH_OK;
+	return nh_mover(ctx, "q_boxwalk", k_q_walk<nh_QBox, true>, k_q_walk<nh_QBox, false>, walks, count, results, flags);
 }
 
 // nh_move's checks in nh_move's order; the sphere-and-box launch and the capsule launch under one label, as nh_overlap splits its walks; no allocation, no wait.

@@ -809,14 +809,14 @@ class World:
         casts.view(torch.int32)[:, 7] = self._ignore_bits(ignore_body)
         return casts, n
 
-    def _cast_records(self, name, size, casts, any_hit, hits):
-        torch = self.torch
-        n = casts.numel() * casts.element_size() // size
-        if hits is None:
-            hits = torch.empty((n, 32), dtype=torch.uint8, device=self.dev)
-        _check(self.L, getattr(self.L, name)(self.ctx, C.c_void_p(casts.data_ptr() if n else 0), n, C.c_void_p(hits.data_ptr() if n else 0),
-                                             NH_RAY_ANY_HIT if any_hit else 0), name)
-        return hits
+    def _records(self, name, in_bytes, out_bytes, records, results, flags=0):
+        """The C call `name`(ctx, records, count, results, flags) of the one-result-per-record queries: `records` a contiguous device tensor of
+        count x in_bytes bytes (any dtype).  Returns the count x out_bytes uint8 device tensor of its results (`results`, or a new one)."""
+        n = records.numel() * records.element_size() // in_bytes
+        if results is None:
+            results = self.torch.empty((n, out_bytes), dtype=self.torch.uint8, device=self.dev)
+        _check(self.L, getattr(self.L, name)(self.ctx, C.c_void_p(records.data_ptr() if n else 0), n, C.c_void_p(results.data_ptr() if n else 0), flags), name)
+        return results
 
     def _ray_hits(self, raw, synchronize, **first):
         """The dict the casts return: `first`, then the fields of the nh_RayHit records `raw` and `raw` itself."""
@@ -830,7 +830,7 @@ class World:
     def raycast_records(self, rays, any_hit=False, hits=None):
         """nh_raycast on records already laid out as nh_Ray: `rays` a contiguous device tensor of count x 32 bytes (any dtype).  Returns the
         count x 32-byte uint8 device tensor of nh_RayHit records (`hits`, or a new one)."""
-        return self._cast_records("nh_raycast", 32, rays, any_hit, hits)
+        return self._records("nh_raycast", 32, 32, rays, hits, NH_RAY_ANY_HIT if any_hit else 0)
 
     def raycast(self, origins, directions, max_t=float("inf"), ignore_body=None, any_hit=False, synchronize=False):
         """Closest-hit (or any-hit) ray casts against the last query_build().  `origins` / `directions`: (n, 3) torch tensors or arrays (uploaded once);
@@ -842,7 +842,7 @@ class World:
     def spherecast_records(self, casts, any_hit=False, hits=None):
         """nh_spherecast on records already laid out as nh_SphereCast: `casts` a contiguous device tensor of count x 48 bytes (any dtype).  Returns the
         count x 32-byte uint8 device tensor of nh_RayHit records (`hits`, or a new one)."""
-        return self._cast_records("nh_spherecast", 48, casts, any_hit, hits)
+        return self._records("nh_spherecast", 48, 32, casts, hits, NH_RAY_ANY_HIT if any_hit else 0)
 
     def spherecast(self, origins, directions, radii, max_t=float("inf"), ignore_body=None, any_hit=False, synchronize=False):
         """Closest-hit (or any-hit) sphere casts against the last query_build(): the ball of radius `radii` (a number or n values) swept from `origins`
@@ -924,7 +924,7 @@ class World:
     def boxcast_records(self, casts, any_hit=False, hits=None):
         """nh_boxcast on records already laid out as nh_BoxCast: `casts` a contiguous device tensor of count x 64 bytes (any dtype).  Returns the
         count x 32-byte uint8 device tensor of nh_RayHit records (`hits`, or a new one)."""
-        return self._cast_records("nh_boxcast", 64, casts, any_hit, hits)
+        return self._records("nh_boxcast", 64, 32, casts, hits, NH_RAY_ANY_HIT if any_hit else 0)
 
     def boxcast(self, origins, directions, half_extents, rotations=None, max_t=float("inf"), ignore_body=None, any_hit=False, synchronize=False):
         """Closest-hit (or any-hit) box casts against the last query_build(): the oriented box of `half_extents` ((n, 3) or (3,)) and `rotations`
@@ -937,7 +937,7 @@ class World:
     def capsulecast_records(self, casts, any_hit=False, hits=None):
         """nh_capsulecast on records already laid out as nh_CapsuleCast: `casts` a contiguous device tensor of count x 64 bytes (any dtype).  Returns
         the count x 32-byte uint8 device tensor of nh_RayHit records (`hits`, or a new one)."""
-        return self._cast_records("nh_capsulecast", 64, casts, any_hit, hits)
+        return self._records("nh_capsulecast", 64, 32, casts, hits, NH_RAY_ANY_HIT if any_hit else 0)
 
     def capsulecast(self, origins, directions, radii, half_heights, rotations=None, max_t=float("inf"), ignore_body=None, any_hit=False,
                     synchronize=False):
@@ -1032,13 +1032,7 @@ class World:
     def closest_records(self, queries, hits=None):
         """nh_closest on records already laid out as nh_PointQuery: `queries` a contiguous device tensor of count x 32 bytes (any dtype).  Returns
         the count x 48-byte uint8 device tensor of nh_PointHit records (`hits`, or a new one)."""
-        torch = self.torch
-        n = queries.numel() * queries.element_size() // 32
-        if hits is None:
-            hits = torch.empty((n, 48), dtype=torch.uint8, device=self.dev)
-        _check(self.L, self.L.nh_closest(self.ctx, C.c_void_p(queries.data_ptr() if n else 0), n, C.c_void_p(hits.data_ptr() if n else 0), 0),
-               "nh_closest")
-        return hits
+        return self._records("nh_closest", 32, 48, queries, hits)
 
     def _point_queries(self, points, max_distance, ignore_body):
         """The nh_PointQuery records (n x 8 float32 words on the device) of closest() / closest_k()'s arguments: (records, n)."""
@@ -1099,13 +1093,7 @@ class World:
     def distance_records(self, queries, hits=None):
         """nh_distance on records already laid out as nh_DistanceQuery: `queries` a contiguous device tensor of count x 64 bytes (any dtype).  Returns
         the count x 48-byte uint8 device tensor of nh_PointHit records (`hits`, or a new one)."""
-        torch = self.torch
-        n = queries.numel() * queries.element_size() // 64
-        if hits is None:
-            hits = torch.empty((n, 48), dtype=torch.uint8, device=self.dev)
-        _check(self.L, self.L.nh_distance(self.ctx, C.c_void_p(queries.data_ptr() if n else 0), n, C.c_void_p(hits.data_ptr() if n else 0), 0),
-               "nh_distance")
-        return hits
+        return self._records("nh_distance", 64, 48, queries, hits)
 
     def distance(self, centres, radii=None, half_extents=None, rotations=None, half_heights=None, max_distance=float("inf"), ignore_body=None,
                  synchronize=False):
@@ -1130,12 +1118,7 @@ class World:
     def move_records(self, records, results=None):
         """nh_move on records already laid out as nh_Move: `records` a contiguous device tensor of count x 64 bytes (any dtype).  Returns the
         count x 64-byte uint8 device tensor of nh_MoveResult records (`results`, or a new one)."""
-        torch = self.torch
-        n = records.numel() * records.element_size() // 64
-        if results is None:
-            results = torch.empty((n, 64), dtype=torch.uint8, device=self.dev)
-        _check(self.L, self.L.nh_move(self.ctx, C.c_void_p(records.data_ptr() if n else 0), n, C.c_void_p(results.data_ptr() if n else 0), 0), "nh_move")
-        return results
+        return self._records("nh_move", 64, 64, records, results)
 
     def move(self, origins, displacements, radius, half_height=0.0, rotations=None, skin=0.01, max_slides=4, ignore_body=None, synchronize=False):
         """Collide-and-slide (nh_move) against the last query_build(): each of n capsules of `radius` and `half_height` (numbers or n values; half
@@ -1145,14 +1128,22 @@ class World:
         Returns a dict of device tensors: position (n, 3), remaining (n, 3; the displacement not used), flags (n, int64; NH_MOVE_*), slides (n,
         int64), `last_hit` (capsulecast()'s dict for the last cast each move made) and `raw`, the nh_MoveResult records.  Nothing waits for the
         device unless `synchronize`."""
-        torch = self.torch
-        rec, n = self._capsule_casts("move", origins, displacements, radius, half_height, rotations, skin, ignore_body)
-        rec.view(torch.int32)[:, 14] = torch.as_tensor(max_slides, dtype=torch.int64, device=self.dev).to(torch.int32)
-        return self._move_results(self.move_records(rec), n, synchronize)
+        return self._move("move", origins, displacements, (radius, half_height), rotations, skin, max_slides, ignore_body, synchronize)
 
-    def _move_results(self, raw, n, synchronize):
-        """The dict move() and boxmove() return, from the nh_MoveResult records `raw`."""
+    def _mover_head(self, name, origins, displacements, shape, rotations, skin, max_slides, ignore_body):
+        """The 64-byte records nh_Move (`name` move, walk; `shape` = (radius, half_height)) or nh_BoxMove (boxmove, boxwalk; (half_extents,)): the
+        shape's cast records with `skin` at max_t and `max_slides` in the word behind the shape: (records, n)."""
         torch = self.torch
+        pack, column = (self._box_casts, 15) if name.startswith("box") else (self._capsule_casts, 14)
+        head, n = pack(name, origins, displacements, *shape, rotations, skin, ignore_body)
+        head.view(torch.int32)[:, column] = torch.as_tensor(max_slides, dtype=torch.int64, device=self.dev).to(torch.int32)
+        return head, n
+
+    def _move(self, name, origins, displacements, shape, rotations, skin, max_slides, ignore_body, synchronize):
+        """move() and boxmove(): the dict they return, from the nh_MoveResult records of the call nh_`name`."""
+        torch = self.torch
+        rec, n = self._mover_head(name, origins, displacements, shape, rotations, skin, max_slides, ignore_body)
+        raw = getattr(self, name + "_records")(rec)
         f = raw.view(torch.float32).reshape(n, 16)
         u = raw.view(torch.int32).reshape(n, 16).to(torch.int64) & 0xFFFFFFFF
         out = dict(position=f[:, 0:3], remaining=f[:, 4:7], flags=u[:, 3], slides=u[:, 7], last_hit=self._ray_hits(raw.reshape(n, 64)[:, 32:].contiguous(), False),
@@ -1164,32 +1155,19 @@ class World:
     def boxmove_records(self, records, results=None):
         """nh_boxmove on records already laid out as nh_BoxMove: `records` a contiguous device tensor of count x 64 bytes (any dtype).  Returns the
         count x 64-byte uint8 device tensor of nh_MoveResult records (`results`, or a new one)."""
-        torch = self.torch
-        n = records.numel() * records.element_size() // 64
-        if results is None:
-            results = torch.empty((n, 64), dtype=torch.uint8, device=self.dev)
-        _check(self.L, self.L.nh_boxmove(self.ctx, C.c_void_p(records.data_ptr() if n else 0), n, C.c_void_p(results.data_ptr() if n else 0), 0), "nh_boxmove")
-        return results
+        return self._records("nh_boxmove", 64, 64, records, results)
 
     def boxmove(self, origins, displacements, half_extents, rotations=None, skin=0.01, max_slides=4, ignore_body=None, synchronize=False):
         """Collide-and-slide for oriented boxes (nh_boxmove) against the last query_build(): move() with boxcast()'s shape -- `half_extents` ((n, 3)
         or (3,)) and `rotations` ((n, 4) or (4,) quaternions (x, y, z, s); None = identity, axis-aligned); the box does not turn while it moves.
         `skin`, `max_slides`, `ignore_body` and the returned dict are move()'s, with boxcast()'s dict as `last_hit`.  Nothing waits for the device
         unless `synchronize`."""
-        torch = self.torch
-        rec, n = self._box_casts("boxmove", origins, displacements, half_extents, rotations, skin, ignore_body)
-        rec.view(torch.int32)[:, 15] = torch.as_tensor(max_slides, dtype=torch.int64, device=self.dev).to(torch.int32)
-        return self._move_results(self.boxmove_records(rec), n, synchronize)
+        return self._move("boxmove", origins, displacements, (half_extents,), rotations, skin, max_slides, ignore_body, synchronize)
 
     def walk_records(self, records, results=None):
         """nh_walk on records already laid out as nh_Walk: `records` a contiguous device tensor of count x 96 bytes (any dtype).  Returns the
         count x 112-byte uint8 device tensor of nh_WalkResult records (`results`, or a new one)."""
-        torch = self.torch
-        n = records.numel() * records.element_size() // 96
-        if results is None:
-            results = torch.empty((n, 112), dtype=torch.uint8, device=self.dev)
-        _check(self.L, self.L.nh_walk(self.ctx, C.c_void_p(records.data_ptr() if n else 0), n, C.c_void_p(results.data_ptr() if n else 0), 0), "nh_walk")
-        return results
+        return self._records("nh_walk", 96, 112, records, results)
 
     def walk(self, origins, displacements, radius, half_height=0.0, rotations=None, skin=0.01, max_slides=4, ignore_body=None, up=(0.0, 1.0, 0.0),
              step_height=0.0, snap_distance=0.0, max_slope_degrees=None, min_ground_up=None, probe_only=False, synchronize=False):
@@ -1201,17 +1179,17 @@ class World:
         Returns move()'s dict for the slide that was kept -- position, remaining, flags (NH_MOVE_* and NH_WALK_*), slides, last_hit -- plus `ground`
         (capsulecast()'s dict of what the capsule stands on), step_up, drop (n, float32), casts (n, int64) and `raw`, the nh_WalkResult records.
         Nothing waits for the device unless `synchronize`."""
+        return self._walk("walk", origins, displacements, (radius, half_height), rotations, skin, max_slides, ignore_body, up, step_height,
+                          snap_distance, max_slope_degrees, min_ground_up, probe_only, synchronize)
+
+    def _walk(self, name, origins, displacements, shape, rotations, skin, max_slides, ignore_body, up, step_height, snap_distance, max_slope_degrees,
+              min_ground_up, probe_only, synchronize):
+        """walk() and boxwalk(): nh_Walk / nh_BoxWalk records -- the 64-byte head followed by walk()'s rules -- and the dict they return, from the
+        nh_WalkResult records of the call nh_`name`."""
         torch = self.torch
         if max_slope_degrees is not None and min_ground_up is not None:
-            raise ValueError("walk: give max_slope_degrees or min_ground_up, not both")
-        head, n = self._capsule_casts("walk", origins, displacements, radius, half_height, rotations, skin, ignore_body)
-        head.view(torch.int32)[:, 14] = torch.as_tensor(max_slides, dtype=torch.int64, device=self.dev).to(torch.int32)
-        rec = self._walk_tail(head, n, up, step_height, snap_distance, max_slope_degrees, min_ground_up, probe_only)
-        return self._walk_results(self.walk_records(rec), n, synchronize)
-
-    def _walk_tail(self, head, n, up, step_height, snap_distance, max_slope_degrees, min_ground_up, probe_only):
-        """nh_Walk / nh_BoxWalk records: the 64-byte `head` records followed by walk()'s rules."""
-        torch = self.torch
+            raise ValueError(f"{name}: give max_slope_degrees or min_ground_up, not both")
+        head, n = self._mover_head(name, origins, displacements, shape, rotations, skin, max_slides, ignore_body)
         rec = torch.zeros((n, 24), dtype=torch.float32, device=self.dev)
         rec[:, 0:16] = head
         rec[:, 16:19] = torch.as_tensor(up, dtype=torch.float32, device=self.dev).reshape(-1, 3)
@@ -1221,11 +1199,7 @@ class World:
             min_ground_up = torch.cos(torch.deg2rad(torch.as_tensor(max_slope_degrees, dtype=torch.float64, device=self.dev)))
         rec[:, 21] = torch.as_tensor(0.0 if min_ground_up is None else min_ground_up, device=self.dev).to(torch.float32).reshape(-1)
         rec.view(torch.int32)[:, 22] = torch.as_tensor(probe_only, device=self.dev).to(torch.int32).reshape(-1) & 1
-        return rec
-
-    def _walk_results(self, raw, n, synchronize):
-        """The dict walk() and boxwalk() return, from the nh_WalkResult records `raw`."""
-        torch = self.torch
+        raw = getattr(self, name + "_records")(rec)
         f = raw.view(torch.float32).reshape(n, 28)
         u = raw.view(torch.int32).reshape(n, 28).to(torch.int64) & 0xFFFFFFFF
         bytes_ = raw.reshape(n, 112)
@@ -1238,36 +1212,20 @@ class World:
     def boxwalk_records(self, records, results=None):
         """nh_boxwalk on records already laid out as nh_BoxWalk: `records` a contiguous device tensor of count x 96 bytes (any dtype).  Returns the
         count x 112-byte uint8 device tensor of nh_WalkResult records (`results`, or a new one)."""
-        torch = self.torch
-        n = records.numel() * records.element_size() // 96
-        if results is None:
-            results = torch.empty((n, 112), dtype=torch.uint8, device=self.dev)
-        _check(self.L, self.L.nh_boxwalk(self.ctx, C.c_void_p(records.data_ptr() if n else 0), n, C.c_void_p(results.data_ptr() if n else 0), 0), "nh_boxwalk")
-        return results
+        return self._records("nh_boxwalk", 96, 112, records, results)
 
     def boxwalk(self, origins, displacements, half_extents, rotations=None, skin=0.01, max_slides=4, ignore_body=None, up=(0.0, 1.0, 0.0),
                 step_height=0.0, snap_distance=0.0, max_slope_degrees=None, min_ground_up=None, probe_only=False, synchronize=False):
         """A grounded step for oriented boxes (nh_boxwalk) against the last query_build(): walk() with boxmove()'s shape (`half_extents`, `rotations`;
         None = identity: an axis-aligned character).  Every other argument and the returned dict are walk()'s, with boxcast()'s dicts as `last_hit`
         and `ground`.  Nothing waits for the device unless `synchronize`."""
-        torch = self.torch
-        if max_slope_degrees is not None and min_ground_up is not None:
-            raise ValueError("boxwalk: give max_slope_degrees or min_ground_up, not both")
-        head, n = self._box_casts("boxwalk", origins, displacements, half_extents, rotations, skin, ignore_body)
-        head.view(torch.int32)[:, 15] = torch.as_tensor(max_slides, dtype=torch.int64, device=self.dev).to(torch.int32)
-        rec = self._walk_tail(head, n, up, step_height, snap_distance, max_slope_degrees, min_ground_up, probe_only)
-        return self._walk_results(self.boxwalk_records(rec), n, synchronize)
+        return self._walk("boxwalk", origins, displacements, (half_extents,), rotations, skin, max_slides, ignore_body, up, step_height,
+                          snap_distance, max_slope_degrees, min_ground_up, probe_only, synchronize)
 
     def recover_records(self, records, results=None):
         """nh_recover on records already laid out as nh_Recover: `records` a contiguous device tensor of count x 64 bytes (any dtype).  Returns the
         count x 64-byte uint8 device tensor of nh_RecoverResult records (`results`, or a new one)."""
-        torch = self.torch
-        n = records.numel() * records.element_size() // 64
-        if results is None:
-            results = torch.empty((n, 64), dtype=torch.uint8, device=self.dev)
-        _check(self.L, self.L.nh_recover(self.ctx, C.c_void_p(records.data_ptr() if n else 0), n, C.c_void_p(results.data_ptr() if n else 0), 0),
-               "nh_recover")
-        return results
+        return self._records("nh_recover", 64, 64, records, results)
 
     def recover(self, centres, radii=None, half_extents=None, rotations=None, half_heights=None, skin=0.01, max_iterations=4, ignore_body=None,
                 synchronize=False):

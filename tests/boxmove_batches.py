@@ -2,7 +2,7 @@
 rotations, slide counts and ignored bodies, with oriented boxes in place of the capsules."""
 import numpy as np
 
-import hostboxmove_util as HBM
+from hostmover_util import BOX as HBM
 import hostoverlap_util as HO
 import move_batches as MB
 from move_batches import shares      # noqa: F401
@@ -24,8 +24,4 @@ def moves(rng, rec, nbox, n, skin=SKIN, scale=1.0, bodies=64, free_share=0.85, d
     size[rng.random(len(c)) < 1.0 / 32] = 0.0
     cand = HBM.moves(c["origin"], c["displacement"], size, rotations=c["rotation"], skin=c["skin"], max_slides=c["max_slides"], ignore_body=c["ignore_body"])
     free = np.diff(HO.overlap(rec, nbox, HBM.overlap_queries(cand))[0].astype(np.int64)) == 0
-    first = np.nonzero(free)[0][:int(free_share * n)]
-    rest = np.setdiff1d(np.arange(len(cand)), first)[:n - len(first)]
-    pick = np.concatenate([first, rest])
-    rng.shuffle(pick)
-    return cand[pick]
+    return MB.take_free(rng, cand, free, n, free_share)

@@ -2,8 +2,8 @@
 boxes that stand one skin above walkable tops on their bottom faces -- axis-aligned, or turned about `up` -- and are sent horizontally."""
 import numpy as np
 
-import hostboxmove_util as HBM
-import hostboxwalk_util as HBW
+import move_batches as MB
+from hostmover_util import BOX as HBW
 import hostoverlap_util as HO
 import walk_batches as WB
 from walk_batches import LANE, SKIN, terrain      # noqa: F401
@@ -75,9 +75,5 @@ def world_walks(rng, rec, nbox, n, slab_share=0.7, free_share=0.9):
     length = rng.uniform(0.3, 2.5, m)
     d = np.stack([np.cos(ang) * length, np.where(rng.random(m) < 0.33, -rng.uniform(0.05, 0.3, m), 0.0), np.sin(ang) * length], axis=1)
     cand = WB._draw_rules(rng, HBW.walks(stand(x, top, z, hy), d, np.stack([hw, hy, hw], axis=1), rotations=_yaw(rng, m, 1.0 / 3), skin=SKIN))
-    free = np.diff(HO.overlap(rec, nbox, HBM.overlap_queries(HBW.head(cand)))[0].astype(np.int64)) == 0
-    first = np.nonzero(free)[0][:int(free_share * n)]
-    rest = np.setdiff1d(np.arange(m), first)[:n - len(first)]
-    pick = np.concatenate([first, rest])
-    rng.shuffle(pick)
-    return cand[pick]
+    free = np.diff(HO.overlap(rec, nbox, HBW.overlap_queries(cand))[0].astype(np.int64)) == 0
+    return MB.take_free(rng, cand, free, n, free_share)

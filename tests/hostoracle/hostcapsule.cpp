@@ -1,50 +1,21 @@
 // hostcapsule.cpp -- CPU build of the capsule arithmetic of nudge_amd/csrc/nh_query.h, the oracle of the GPU's nh_capsulecast (tests/hostcapsule_util.py).
 // nh_overlap's capsule queries are judged by hostoverlap.cpp's hc_overlap.
-//   hc_capsulecast  closest hit (or the hit of one collider) by brute force over all colliders, with the header's exact rules -- invalid casts,
-//                   hh = 0 as a sphere cast, ignore_body, ties, the reach rule unless r = hh = 0 (the leaf box rebuilt as the build stores it)
+//   hc_capsulecast  closest hit (or the hit of one collider) by brute force over all colliders (oracle.h's closest_hit of a SweptCapsule), with the header's
+//                   exact rules -- invalid casts, hh = 0 as a sphere cast, ignore_body, ties, the reach rule unless r = hh = 0 (the leaf box rebuilt as
+//                   the build stores it)
 //   hc_*            the single-collider predicates alone
 #include "oracle.h"
-
-static void cast_one(const Rec* rec, uint32_t n, uint32_t nbox, const nh_CapsuleCast& cc, nh_RayHit& out, int64_t only) {
-	const nh_f3 o = v3(cc.origin), d = v3(cc.direction);
-	const nh_quat qa = q4(cc.rotation);
-	const float r = cc.radius, hh = cc.half_height;
-	const bool ok = finite(o.x) && finite(o.y) && finite(o.z) && finite(d.x) && finite(d.y) && finite(d.z) && finite(r) && finite(hh) && !(r < 0.0f) &&
-	                !(hh < 0.0f) && (hh == 0.0f || (finite(qa.x) && finite(qa.y) && finite(qa.z) && finite(qa.s)));
-	const nh_f3 inv = nh_make3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
-	const nh_f3 e = nh_q_capsule_extent(nh_q_capsule_axis(qa, hh), r);
-	const float s = nh_q_cast_pad(o, fmaxf(fmaxf(e.x, e.y), e.z));
-	const nh_f3 w = nh_make3(e.x + s, e.y + s, e.z + s);
-	const bool reach = r > 0.0f || hh > 0.0f;
-	float bt = cc.max_t; uint32_t bc = 0xffffffffu; nh_f3 bn = nh_make3(0.0f, 0.0f, 0.0f);
-	const uint32_t c0 = only >= 0 ? (uint32_t)only : 0u, c1 = only >= 0 ? (uint32_t)only + 1u : n;
-	for (uint32_t c = ok ? c0 : c1; c < c1; ++c) {
-		const Rec& rc = rec[c];
-		if (rc.body == cc.ignore_body) continue;
-		const bool box = c < nbox;
-		const nh_f3 p = rec_pos(rc), h = rec_half(rc);
-		const nh_quat q = rec_rot(rc);
-		nh_QHit hit = box ? nh_q_sweep_capsule_box(o, d, qa, r, hh, p, q, h) : nh_q_sweep_capsule_sphere(o, d, qa, r, hh, p, h.x);
-		if (!hit.hit) continue;
-		if (reach) {
-			// the reach rule: the leaf box must be entered, and the hit is no earlier than that entry
-			nh_f3 lo, hi;
-			nh_q_leaf_box(p, q, h, box, lo, hi);
-			float t0;
-			if (!nh_q_cast_node3(lo, hi, o, inv, w, t0)) continue;
-			if (t0 > hit.t) hit.t = t0;
-		}
-		if (nh_q_better(hit.t, c, cc.max_t, bt, bc)) { bt = hit.t; bc = c; bn = hit.n; }
-	}
-	if (bc == 0xffffffffu) write_ray_miss(out, ok, cc.max_t);
-	else write_ray_hit(out, rec, nbox, bc, bt, bn);
-}
 
 extern "C" {
 
 // only >= 0: the answer of that one collider (combined index) alone, as the closest-hit rule would give it
 void hc_capsulecast(const Rec* rec, uint32_t n, uint32_t nbox, const nh_CapsuleCast* casts, uint32_t count, nh_RayHit* hits, int64_t only, uint32_t threads) {
-	parallel(count, threads, [=](uint32_t i) { cast_one(rec, n, nbox, casts[i], hits[i], only); });
+	parallel(count, threads, [=](uint32_t i) {
+		const nh_CapsuleCast& cc = casts[i];
+		float bt; uint32_t bc; nh_f3 bn;
+		const bool ok = closest_hit(rec, n, nbox, SweptCapsule{ q4(cc.rotation), cc.radius, cc.half_height }, v3(cc.origin), v3(cc.direction), cc.max_t, cc.ignore_body, nullptr, 0u, only, bt, bc, bn);
+		write_cast(hits[i], rec, nbox, ok, cc.max_t, bt, bc, bn);
+	});
 }
 
 // one collider alone, the predicate without the reach rule (the geometry tests): out = t, normal[3], hit (1.0 / 0.0)

@@ -1,6 +1,7 @@
 // oracle.h -- what the host oracles of the scene queries (tests/hostoracle/host*.cpp, one library: tests/hostlib.py) have in common: the collider
-// record, the thread loop, and the rules every answer record encodes.  Built with g++ -ffp-contract=off, so that nudge_amd/csrc/nh_query.h's arithmetic
-// returns the device's bits.  Shared between oracles only: nothing here walks a tree or keeps a list, which is what the oracles judge.
+// record, the thread loop, the rules every answer record encodes, and the one brute-force closest-hit cast of a swept capsule or box.  Built with g++
+// -ffp-contract=off, so that nudge_amd/csrc/nh_query.h's arithmetic returns the device's bits.  Shared between oracles only: nothing here walks a tree or
+// keeps a list, which is what the oracles judge.
 #pragma once
 #include <stdint.h>
 #include <math.h>
@@ -97,6 +98,75 @@ static inline void write_ray_hit(nh_RayHit& out, const Rec* rec, uint32_t nbox, 
 static inline void write_ray_miss(nh_RayHit& out, bool ok, float max_t) {
 	out.t = ok ? max_t : nh_asfloat(0x7fc00000u); out.normal[0] = out.normal[1] = out.normal[2] = 0.0f;
 	write_nobody(out);
+}
+
+// a closest-hit cast's record from what closest_hit (below) left
+static inline void write_cast(nh_RayHit& out, const Rec* rec, uint32_t nbox, bool ok, float max_t, float bt, uint32_t bc, nh_f3 bn) {
+	if (bc == 0xffffffffu) write_ray_miss(out, ok, max_t);
+	else write_ray_hit(out, rec, nbox, bc, bt, bn);
+}
+
+// The swept shapes of the closest-hit casts and the movers (hostcapsule.cpp, hostboxcast.cpp, hostmover.cpp).  Each gives the validity of its own fields,
+// the half extent of its bounds for the cast's pad, whether the reach rule applies to it, and its sweep from o along d against one collider.
+// SweptCapsule: rotation q, radius r, half height hh.  hh = 0 is a ball, which does not read its rotation to be valid; r = hh = 0 is a ray
+struct SweptCapsule {
+	nh_quat q; float r, hh;
+	bool valid() const { return finite(r) && finite(hh) && !(r < 0.0f) && !(hh < 0.0f) && (hh == 0.0f || (finite(q.x) && finite(q.y) && finite(q.z) && finite(q.s))); }
+	nh_f3 extent() const { return nh_q_capsule_extent(nh_q_capsule_axis(q, hh), r); }
+	bool reach() const { return r > 0.0f || hh > 0.0f; }
+	nh_QHit sweep(nh_f3 o, nh_f3 d, bool box, nh_f3 p, nh_quat qb, nh_f3 hb) const {
+		return box ? nh_q_sweep_capsule_box(o, d, q, r, hh, p, qb, hb) : nh_q_sweep_capsule_sphere(o, d, q, r, hh, p, hb.x);
+	}
+};
+// SweptBox: rotation q, half extents h.  h = (0, 0, 0) is a ray, which does not read its rotation at all
+struct SweptBox {
+	nh_quat q; nh_f3 h;
+	bool ray() const { return h.x == 0.0f && h.y == 0.0f && h.z == 0.0f; }
+	bool valid() const {
+		return finite(h.x) && finite(h.y) && finite(h.z) && !(h.x < 0.0f) && !(h.y < 0.0f) && !(h.z < 0.0f) && (ray() || (finite(q.x) && finite(q.y) && finite(q.z) && finite(q.s)));
+	}
+	nh_f3 extent() const { return ray() ? nh_make3(0.0f, 0.0f, 0.0f) : nh_q_box_extent(q, h); }
+	bool reach() const { return !ray(); }
+	nh_QHit sweep(nh_f3 o, nh_f3 d, bool box, nh_f3 p, nh_quat qb, nh_f3 hb) const {
+		return box ? nh_q_sweep_box_box(o, d, q, h, p, qb, hb) : nh_q_sweep_box_sphere(o, d, q, h, p, hb.x);
+	}
+};
+
+// The closest hit of the shape `a` cast from o along d up to max_t, by brute force over all colliders with the header's exact rules: invalid casts (which
+// look at no collider), ignore_body, ties, the reach rule.  words, mask: colliders whose layer word shares no bit with the mask do not exist for this cast
+// (words = NULL: all are seen); only >= 0: that one collider (combined index) alone.  Leaves (bt, bc, bn) as nh_q_cast_one leaves them and returns whether
+// the cast was valid.
+template <class S>
+static bool closest_hit(const Rec* rec, uint32_t n, uint32_t nbox, const S& a, nh_f3 o, nh_f3 d, float max_t, uint32_t ignore_body, const uint32_t* words,
+                        uint32_t mask, int64_t only, float& bt, uint32_t& bc, nh_f3& bn) {
+	const bool ok = finite(o.x) && finite(o.y) && finite(o.z) && finite(d.x) && finite(d.y) && finite(d.z) && a.valid();
+	const nh_f3 inv = nh_make3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+	const nh_f3 e = a.extent();
+	const float s = nh_q_cast_pad(o, fmaxf(fmaxf(e.x, e.y), e.z));
+	const nh_f3 w = nh_make3(e.x + s, e.y + s, e.z + s);
+	const bool reach = a.reach();
+	bt = max_t; bc = 0xffffffffu; bn = nh_make3(0.0f, 0.0f, 0.0f);
+	const uint32_t c0 = only >= 0 ? (uint32_t)only : 0u, c1 = only >= 0 ? (uint32_t)only + 1u : n;
+	for (uint32_t c = ok ? c0 : c1; c < c1; ++c) {
+		const Rec& rc = rec[c];
+		if (rc.body == ignore_body) continue;
+		if (words && !(words[c] & mask)) continue;
+		const bool box = c < nbox;
+		const nh_f3 p = rec_pos(rc), h = rec_half(rc);
+		const nh_quat q = rec_rot(rc);
+		nh_QHit hit = a.sweep(o, d, box, p, q, h);
+		if (!hit.hit) continue;
+		if (reach) {
+			// the reach rule: the leaf box must be entered, and the hit is no earlier than that entry
+			nh_f3 lo, hi;
+			nh_q_leaf_box(p, q, h, box, lo, hi);
+			float t0;
+			if (!nh_q_cast_node3(lo, hi, o, inv, w, t0)) continue;
+			if (t0 > hit.t) hit.t = t0;
+		}
+		if (nh_q_better(hit.t, c, max_t, bt, bc)) { bt = hit.t; bc = c; bn = hit.n; }
+	}
+	return ok;
 }
 
 // nh_PointHit, likewise: the distance, the normal and the point of h

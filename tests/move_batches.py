@@ -3,11 +3,9 @@ units towards one of the colliders nearest to them, so that a good share slides 
 import numpy as np
 
 import hostcapsule_util as HC
-import hostmove_util as HM
+from hostmover_util import CAPSULE as HM
 from query_util import unit_quats
-from nudge_amd import engine as E
 
-NONE = 0xFFFFFFFF
 SKIN = 0.01
 
 
@@ -18,10 +16,12 @@ def moves(rng, rec, nbox, n, skin=SKIN, scale=1.0, bodies=64, free_share=0.85):
     bodies.  Four times as many are drawn, and those that start free of every collider (nh_overlap's capsule predicates on the host) are taken first, up
     to `free_share` of the batch: in a packed scene most random starts are inside something, and a move that starts in overlap never slides."""
     cand = _draw(rng, rec, 4 * n, skin, scale, bodies)
-    q = np.zeros(len(cand), dtype=E.OVERLAP_QUERY)
-    q["center"], q["shape"], q["rotation"], q["ignore_body"] = cand["origin"], E.NH_SHAPE_CAPSULE, cand["rotation"], NONE
-    q["size"][:, 0], q["size"][:, 1] = cand["radius"], cand["half_height"]
-    free = np.diff(HC.overlap(rec, nbox, q)[0].astype(np.int64)) == 0
+    free = np.diff(HC.overlap(rec, nbox, HM.overlap_queries(cand))[0].astype(np.int64)) == 0
+    return take_free(rng, cand, free, n, free_share)
+
+
+def take_free(rng, cand, free, n, free_share):
+    """n of the candidates `cand` in a shuffled order: those that start free first, up to `free_share` of the n, then the others."""
     first = np.nonzero(free)[0][:int(free_share * n)]
     rest = np.setdiff1d(np.arange(len(cand)), first)[:n - len(first)]
     pick = np.concatenate([first, rest])

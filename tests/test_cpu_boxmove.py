@@ -1,6 +1,6 @@
 """nh_boxmove's state machine on the CPU (include/nudge_hip.h, "nh_boxmove"; nudge_amd/csrc/nh_query.h, "move"): the host oracle of
-tests/hostoracle/hostboxmove.cpp -- the NH_HD functions the kernel runs, around a brute-force box cast -- against the replay through the oracles that
-were there before it (hostboxcast.cpp's cast, hostmove.cpp's begin / advance), on hand-built worlds, on every invalid-record rule, on the identities,
+tests/hostoracle/hostmover.cpp -- the NH_HD functions the kernel runs, around a brute-force box cast -- against the replay round by round
+(hostboxcast.cpp's cast, the capsule mover's begin / advance), on hand-built worlds, on every invalid-record rule, on the identities,
 on the conditions that keep the GPU tests' batches honest, and on THE INVARIANT of test_cpu_move's random world: a box move that starts free ends no
 deeper than its skin in anything."""
 import os
@@ -14,17 +14,16 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import boxmove_batches as BMB               # noqa: E402
 import hostboxcast_util as HB               # noqa: E402
-import hostboxmove_util as HBM              # noqa: E402
 import hostlib as H                         # noqa: E402
-import hostmove_util as HM                  # noqa: E402
 import hostoverlap_util as HO               # noqa: E402
 import hostpen_util as HP                   # noqa: E402
 import hostquery_util as Q                  # noqa: E402
+from hostmover_util import BOX as HBM, CAPSULE as HM      # noqa: E402
+from mover_util import NONE, miss           # noqa: E402
 from query_util import SMALL                # noqa: E402
-from test_cpu_move import FLOOR, QNAN, TOL, _random_world_and_moves, _unit_quats, miss, world      # noqa: E402
+from test_cpu_move import FLOOR, QNAN, TOL, _random_world_and_moves, world      # noqa: E402
 from nudge_amd import engine as E          # noqa: E402
 
-NONE = 0xFFFFFFFF
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 HALF, SKIN = (0.3, 0.5, 0.4), 0.01          # the box of the invariant and of the hand-built worlds
 # candidates drawn per move kept (boxmove_batches.moves): the ball pit is packed, 6 % of its candidates start free
@@ -86,7 +85,7 @@ def test_the_header_lists_the_new_observers_and_no_box_movers_as_not_built():
 
 # ---- the new oracle against the replay through the old ones -----------------------------------------------------------------------------------------
 def _replay_old(rec, nbox, m):
-    """hostboxcast.cpp's cast per round, hostmove.cpp's nh_q_move_advance between rounds: only code that existed before hostboxmove.cpp."""
+    """hostboxcast.cpp's cast per round, the capsule mover's nh_q_move_advance between rounds, on the capsule records of the same moves."""
     cm = np.zeros(len(m), dtype=E.MOVE)
     for name in ("origin", "skin", "displacement", "ignore_body", "rotation", "max_slides"):
         cm[name] = m[name]
@@ -120,8 +119,8 @@ def test_the_oracle_equals_the_replay_through_the_old_oracles():
     bad = (out.view(np.uint8).reshape(-1, 64) != ref.view(np.uint8).reshape(-1, 64)).any(axis=1)
     assert not bad.any(), (int(bad.sum()), out[np.argmax(bad)], ref[np.argmax(bad)])
     assert (out["slides"] >= 1).mean() >= 0.15 and (out["slides"] >= 2).mean() >= 0.02
-    # ... and hbm_begin / hbm_advance are hm_begin / hm_advance
-    got, rounds = HBM.replay(m, lambda c: HB.boxcast(rec, nbox, c))
+    # ... and the box mover's begin / advance are the capsule mover's
+    got, rounds = HBM.replay_move(m, lambda c: HB.boxcast(rec, nbox, c))
     assert got.tobytes() == out.tobytes() and rounds >= 3
 
 

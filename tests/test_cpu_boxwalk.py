@@ -1,6 +1,6 @@
 """nh_boxwalk's phase machine on the CPU (include/nudge_hip.h, "nh_boxmove, nh_boxwalk"; nudge_amd/csrc/nh_query.h, "walk"): the host oracle of
-tests/hostoracle/hostboxwalk.cpp -- the NH_HD functions the kernel runs, around a brute-force box cast -- against hostwalk_util.replay (code that was
-there before it) with box adaptors, on the hand-built terrain of tests/walk_batches.py for the upright box (0.25, 0.75, 0.25), on every
+tests/hostoracle/hostmover.cpp -- the NH_HD functions the kernel runs, around a brute-force box cast -- against the replay phase by phase through
+test_cpu_boxmove's replay round by round, on the hand-built terrain of tests/walk_batches.py for the upright box (0.25, 0.75, 0.25), on every
 invalid-record rule, on the identities, on the shares that keep the GPU tests' batches honest, and on THE INVARIANT of a random world."""
 import os
 import sys
@@ -11,18 +11,18 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import boxwalk_batches as BWB               # noqa: E402
 import hostboxcast_util as HB               # noqa: E402
-import hostboxmove_util as HBM              # noqa: E402
-import hostboxwalk_util as HBW              # noqa: E402
+import hostmover_util as MV                 # noqa: E402
 import hostlib as H                         # noqa: E402
 import hostoverlap_util as HO               # noqa: E402
 import hostquery_util as Q                  # noqa: E402
 import walk_batches as WB                   # noqa: E402
-from query_util import SMALL                # noqa: E402
+from hostmover_util import BOX as HBW       # noqa: E402
+from mover_util import NONE                 # noqa: E402
+from query_util import SMALL, unit_quats as _unit_quats      # noqa: E402
 from test_cpu_boxmove import deepest        # noqa: E402
 from test_cpu_walk import BALL_PIT_SHARES, RESTING, TERRAIN_SHARES, TOL, WORLD_SHARES, check_shares, has, is_miss      # noqa: E402
 from nudge_amd import engine as E          # noqa: E402
 
-NONE = 0xFFFFFFFF
 BOX, SKIN = BWB.BOX, BWB.SKIN               # the upright box of the hand-built answers
 HX, HY, HZ = BOX
 STAND = SKIN + HY                           # the height of its centre above what it stands on
@@ -101,7 +101,7 @@ def test_ledge_drop_and_probe_only(terrain):
 
 
 def test_ramps_and_the_slope_limit(terrain):
-    lim45 = float(HBW.cos_deg(45.0))
+    lim45 = float(MV.cos_deg(45.0))
     gentle = one(terrain, "ramp20", d=(3.0, 0.0, 0.0), step_height=0.4, snap_distance=0.3, min_ground_up=lim45)
     assert has(gentle, E.NH_WALK_GROUNDED) and not has(gentle, E.NH_WALK_STEEP) and not has(gentle, E.NH_WALK_ON_STEEP)
     n = gentle["ground"]["normal"]
@@ -234,35 +234,30 @@ def test_without_its_rules_a_walk_is_nh_boxmove(terrain, terrain_run):
     w = terrain_run[0].copy()
     w["step_height"], w["snap_distance"], w["min_ground_up"] = 0.0, 0.0, 0.0
     out = HBW.walk(rec, nbox, w)
-    ref, made = HBM.move(rec, nbox, HBW.head(w), casts=True)
+    ref, made = HBW.move(rec, nbox, HBW.head(w), casts=True)
     assert out.view(np.uint8).reshape(-1, 112)[:, :64].tobytes() == ref.tobytes()
     assert all(is_miss(h) for h in out["ground"]) and (out["step_up"] == 0).all() and (out["drop"] == 0).all() and (out["casts"] == made).all()
     assert (ref["slides"] >= 1).mean() >= 0.25
 
 
 def test_the_oracle_equals_the_replay_through_the_old_oracles(terrain, terrain_run):
-    """hbw_walk with min_ground_up = 0 against hostwalk_util.replay -- hostwalk.cpp's phase-by-phase helpers and hostmove.cpp's begin / advance, which
-    existed before the box oracles -- whose move and cast records are answered for a box by a Python loop around hostboxcast.cpp's cast (test_cpu_boxmove)
-    and by that cast itself.  Identity 5 on the CPU, and a check of the new oracle against code that does not share a line with it."""
+    """hw_walk for boxes with min_ground_up = 0 against replay_walk -- hostmover.cpp's phase-by-phase helpers -- whose move records are answered by a
+    Python loop around hostboxcast.cpp's cast and the capsule mover's begin / advance (test_cpu_boxmove) and whose cast records by that cast itself.
+    Identity 5 on the CPU."""
     from test_cpu_boxmove import _replay_old
     rec, nbox = terrain
     w = terrain_run[0].copy()
     w["min_ground_up"] = 0.0
     out = HBW.walk(rec, nbox, w)
-    got, calls = HBW.replay(w, lambda m: _replay_old(rec, nbox, m), lambda c: HB.boxcast(rec, nbox, c))
+    got, calls = HBW.replay_walk(w, lambda m: _replay_old(rec, nbox, m), lambda c: HB.boxcast(rec, nbox, c))
     bad = (got.view(np.uint8).reshape(-1, 112) != out.view(np.uint8).reshape(-1, 112)).any(axis=1)
     assert not bad.any(), (int(bad.sum()), out[np.argmax(bad)], got[np.argmax(bad)])
-    s = HBW.shares(w, out)
+    s = MV.shares(w, out)
     assert s["stepped"] >= 0.05 and s["snapped"] >= 0.05 and calls >= 6
 
 
 # ---- THE INVARIANT --------------------------------------------------------------------------------------------------------------------------------
 HALF = (0.3, 0.5, 0.4)
-
-
-def _unit_quats(rng, n):
-    q = rng.normal(size=(n, 4))
-    return (q / np.linalg.norm(q, axis=1, keepdims=True)).astype(np.float32)
 
 
 @pytest.fixture(scope="module")
@@ -282,14 +277,14 @@ def random_run():
     d = (d / np.linalg.norm(d, axis=1, keepdims=True) * rng.uniform(0.5, 3.0, size=(n, 1))).astype(np.float32)
     w = WB._draw_rules(rng, HBW.walks(o, d, HALF, rotations=_unit_quats(rng, n), skin=SKIN))
     out = HBW.walk(rec, n_boxes, w)
-    free = np.diff(HO.overlap(rec, n_boxes, HBM.overlap_queries(HBW.head(w)))[0].astype(np.int64)) == 0
+    free = np.diff(HO.overlap(rec, n_boxes, HBW.overlap_queries(w))[0].astype(np.int64)) == 0
     return rec, n_boxes, w, out, free
 
 
 def test_invariant_conditions(random_run):
     """What keeps the invariant honest: enough walks start free, and enough of those slide, step, snap and meet steep faces."""
     _, _, w, out, free = random_run
-    s = HBW.shares(w[free], out[free])
+    s = MV.shares(w[free], out[free])
     print("free %.3f, of them: %s" % (free.mean(), {k: round(v, 4) for k, v in s.items()}))
     assert free.mean() >= 0.5
     assert s["slid"] >= 0.25 and s["stepped"] >= 0.01 and s["snapped"] >= 0.02 and s["steep"] >= 0.02

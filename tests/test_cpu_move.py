@@ -1,4 +1,4 @@
-"""nh_move's state machine on the CPU (include/nudge_hip.h, "nh_move"; nudge_amd/csrc/nh_query.h, "move"): the host oracle of tests/hostoracle/hostmove.cpp --
+"""nh_move's state machine on the CPU (include/nudge_hip.h, "nh_move"; nudge_amd/csrc/nh_query.h, "move"): the host oracle of tests/hostoracle/hostmover.cpp --
 the same NH_HD functions the kernel runs, around a brute-force capsule cast -- on hand-built worlds whose answers are known, on every invalid-record rule,
 and on THE INVARIANT of a random world: a move that starts free ends no deeper than its skin in anything, never behind where it started and never
 farther than it was asked to go."""
@@ -11,11 +11,13 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import hostcapsule_util as HC               # noqa: E402
 import hostlib as H                         # noqa: E402
-import hostmove_util as HM                  # noqa: E402
+import hostmover_util as MV                 # noqa: E402
 import hostpen_util as HP                   # noqa: E402
+from hostmover_util import CAPSULE as HM    # noqa: E402
+from mover_util import NONE, miss           # noqa: E402
+from query_util import unit_quats as _unit_quats      # noqa: E402
 from nudge_amd import engine as E          # noqa: E402
 
-NONE = 0xFFFFFFFF
 R, HH, SKIN = 0.5, 0.5, 0.01                # the upright capsule of the hand-built worlds
 TOL = 2.0 ** -16 * 64                       # every coordinate of those worlds stays below 64
 QNAN = 0x7FC00000
@@ -24,7 +26,7 @@ QNAN = 0x7FC00000
 def world(boxes=(), spheres=()):
     """(rec, nbox) of a static world: boxes as (centre, half extents[, rotation]), spheres as (centre, radius); every collider belongs to body 0."""
     rec = np.zeros(len(boxes) + len(spheres), dtype=H.REC)
-    rec["q"] = HM.IDENTITY
+    rec["q"] = MV.IDENTITY
     for i, b in enumerate(boxes):
         rec["p"][i], rec["h"][i] = b[0], b[1]
         if len(b) > 2:
@@ -35,13 +37,7 @@ def world(boxes=(), spheres=()):
     return rec, len(boxes)
 
 
-def miss(t=1.0):
-    m = np.zeros(1, dtype=E.RAY_HIT)
-    m["t"], m["body"], m["collider"], m["shape"], m["tag"] = t, NONE, NONE, NONE, NONE
-    return m[0]
-
-
-def overlapping(rec, nbox, centres, rot=HM.IDENTITY, r=R, hh=HH):
+def overlapping(rec, nbox, centres, rot=MV.IDENTITY, r=R, hh=HH):
     """Per capsule at `centres`: how many colliders it overlaps (hc_overlap, the capsule predicates of nh_overlap)."""
     q = np.zeros(len(centres), dtype=E.OVERLAP_QUERY)
     q["center"], q["shape"], q["rotation"], q["ignore_body"] = centres, E.NH_SHAPE_CAPSULE, rot, NONE
@@ -235,7 +231,7 @@ def test_valid_edges():
 
 
 def test_advance_replays_the_oracle():
-    """hm_begin / hm_advance around the brute-force capsule cast give hm_move's bytes: the loop of the REPLAY identity, on the CPU."""
+    """hm_begin / hm_advance (hostmover.cpp) around the brute-force capsule cast give hm_move's bytes: the loop of the REPLAY identity, on the CPU."""
     rec, nbox, m = _random_world_and_moves(seed=21, n_moves=512)
     ref = HM.move(rec, nbox, m)
     st = HM.begin(m)
@@ -254,11 +250,6 @@ def test_advance_replays_the_oracle():
 
 
 # ---- THE INVARIANT --------------------------------------------------------------------------------------------------------------------------------
-def _unit_quats(rng, n):
-    q = rng.normal(size=(n, 4))
-    return (q / np.linalg.norm(q, axis=1, keepdims=True)).astype(np.float32)
-
-
 def _random_world_and_moves(seed, n_moves, n_boxes=2000, n_spheres=1000, side=40.0):
     """A static world of boxes and spheres of size 0.2 - 2 (half extents / radii 0.1 - 1) with random rotations inside a cube, and moves of the capsule
     (r, hh) = (0.5, 0.5) under random rotations from uniform origins by 0.5 - 4 units, max_slides drawn from 0 .. 8."""

@@ -1,4 +1,4 @@
-"""nh_walk's phase machine on the CPU (include/nudge_hip.h, "nh_walk"; nudge_amd/csrc/nh_query.h, "walk"): the host oracle of tests/hostoracle/hostwalk.cpp --
+"""nh_walk's phase machine on the CPU (include/nudge_hip.h, "nh_walk"; nudge_amd/csrc/nh_query.h, "walk"): the host oracle of tests/hostoracle/hostmover.cpp --
 the same NH_HD functions the kernel runs, around a brute-force capsule cast -- on the hand-built terrain of tests/walk_batches.py, whose answers are known,
 on every invalid-record rule, on the identities against the move oracle (nh_move's bytes; the REPLAY phase by phase), on the shares that keep the GPU
 tests' batches honest, and on THE INVARIANT of a random world: a walk that starts free ends no deeper than its skin in anything."""
@@ -11,15 +11,15 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import hostcapsule_util as HC               # noqa: E402
 import hostlib as H                         # noqa: E402
-import hostmove_util as HM                  # noqa: E402
+import hostmover_util as MV                 # noqa: E402
 import hostpen_util as HP                   # noqa: E402
 import hostquery_util as Q                  # noqa: E402
-import hostwalk_util as HW                  # noqa: E402
 import walk_batches as WB                   # noqa: E402
-from query_util import SMALL                # noqa: E402
+from hostmover_util import CAPSULE as HW    # noqa: E402
+from mover_util import NONE                 # noqa: E402
+from query_util import SMALL, unit_quats as _unit_quats      # noqa: E402
 from nudge_amd import engine as E          # noqa: E402
 
-NONE = 0xFFFFFFFF
 R, HH, SKIN = 0.25, 0.5, WB.SKIN            # the upright capsule of the hand-built answers
 TOL = 2.0 ** -16 * 64                       # every coordinate of the terrain stays below 64
 STAND = SKIN + R + HH                       # the height of its centre above what it stands on
@@ -104,7 +104,7 @@ def test_the_high_riser_blocks_a_low_step_and_is_climbed_by_a_high_one(terrain):
 
 
 def test_the_low_ceiling_vetoes_the_step(terrain):
-    for limit in (0.0, float(HW.cos_deg(45.0))):
+    for limit in (0.0, float(MV.cos_deg(45.0))):
         r = one(terrain, "ceiling", step_height=0.4, snap_distance=0.3, min_ground_up=limit)
         assert not has(r, E.NH_WALK_STEPPED) and r["step_up"] == 0 and has(r, E.NH_WALK_GROUNDED)
         assert abs(r["position"][0] - (2.0 - R - SKIN)) <= TOL and abs(r["position"][1] - STAND) <= TOL
@@ -114,7 +114,7 @@ def test_the_low_ceiling_vetoes_the_step(terrain):
 
 
 def test_ramps_and_the_slope_limit(terrain):
-    lim45 = float(HW.cos_deg(45.0))
+    lim45 = float(MV.cos_deg(45.0))
     gentle = one(terrain, "ramp20", d=(3.0, 0.0, 0.0), step_height=0.4, snap_distance=0.3, min_ground_up=lim45)
     assert has(gentle, E.NH_WALK_GROUNDED) and not has(gentle, E.NH_WALK_STEEP) and not has(gentle, E.NH_WALK_ON_STEEP)
     assert gentle["position"][1] > STAND + 0.3 and gentle["position"][0] > 3.0
@@ -231,7 +231,7 @@ def terrain_run(terrain):
 
 
 def check_shares(w, out, need, what):
-    got = HW.shares(w, out)
+    got = MV.shares(w, out)
     print(what, {k: round(v, 4) for k, v in got.items()})
     for k, least in need.items():
         assert got[k] >= least, (what, k, got[k], least)
@@ -275,7 +275,7 @@ def test_without_its_rules_a_walk_is_nh_move(terrain, terrain_run):
     w = terrain_run[0].copy()
     w["step_height"], w["snap_distance"], w["min_ground_up"] = 0.0, 0.0, 0.0
     out = HW.walk(rec, nbox, w)
-    ref, made = HM.move(rec, nbox, HW.head(w), casts=True)
+    ref, made = HW.move(rec, nbox, HW.head(w), casts=True)
     assert out.view(np.uint8).reshape(-1, 112)[:, :64].tobytes() == ref.tobytes()
     assert all(is_miss(h) for h in out["ground"]) and (out["step_up"] == 0).all() and (out["drop"] == 0).all() and (out["casts"] == made).all()
     assert (ref["slides"] >= 1).mean() >= 0.25
@@ -288,19 +288,14 @@ def test_replay_phase_by_phase(terrain, terrain_run):
     w = terrain_run[0].copy()
     w["min_ground_up"] = 0.0
     out = HW.walk(rec, nbox, w)
-    got, calls = HW.replay(w, lambda m: HM.move(rec, nbox, m), lambda c: HC.capsulecast(rec, nbox, c))
+    got, calls = HW.replay_walk(w, lambda m: HW.move(rec, nbox, m), lambda c: HC.capsulecast(rec, nbox, c))
     bad = (got.view(np.uint8).reshape(-1, 112) != out.view(np.uint8).reshape(-1, 112)).any(axis=1)
     assert not bad.any(), (int(bad.sum()), out[np.argmax(bad)], got[np.argmax(bad)])
-    s = HW.shares(w, out)
+    s = MV.shares(w, out)
     assert s["stepped"] >= 0.05 and s["snapped"] >= 0.05 and calls >= 6
 
 
 # ---- THE INVARIANT --------------------------------------------------------------------------------------------------------------------------------
-def _unit_quats(rng, n):
-    q = rng.normal(size=(n, 4))
-    return (q / np.linalg.norm(q, axis=1, keepdims=True)).astype(np.float32)
-
-
 @pytest.fixture(scope="module")
 def random_run():
     """test_cpu_move's random world -- boxes and spheres of size 0.2 - 2 under random rotations in a cube of side 40 -- and walks of upright capsules from
@@ -328,7 +323,7 @@ def random_run():
 def test_invariant_conditions(random_run):
     """What keeps the invariant honest: enough walks start free, and enough of those slide, step, snap and meet steep faces."""
     _, _, w, out, free = random_run
-    s = HW.shares(w[free], out[free])
+    s = MV.shares(w[free], out[free])
     print("free %.3f, of them: %s" % (free.mean(), {k: round(v, 4) for k, v in s.items()}))
     assert free.mean() >= 0.5
     assert s["slid"] >= 0.25 and s["stepped"] >= 0.01 and s["snapped"] >= 0.02 and s["steep"] >= 0.02

@@ -1,6 +1,6 @@
 """nh_boxmove on the GPU (pytest -m gpu): collide-and-slide for swept oriented boxes on the scene BVH (include/nudge_hip.h, "nh_boxmove, nh_boxwalk").
 
-The oracle is the host's brute force (tests/hostoracle/hostboxmove.cpp through tests/hostboxmove_util.py): the state machine of nudge_amd/csrc/nh_query.h,
+The oracle is the host's brute force (tests/hostoracle/hostmover.cpp through tests/hostmover_util.py): the state machine of nudge_amd/csrc/nh_query.h,
 "move" -- the functions the kernel runs -- around a box cast over every collider, so the kernel's 64 bytes per move must equal it bit for bit.  The
 identities of the header are tested against the GPU's own nh_boxcast and nh_move: max_slides = 0, size 0, and the REPLAY of the loop from the host."""
 import ctypes as C
@@ -12,9 +12,10 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import boxmove_batches as BMB                # noqa: E402
-import hostboxmove_util as HBM               # noqa: E402
-import hostmove_util as HM                   # noqa: E402
+import hostmover_util as MV                  # noqa: E402
 import hostquery_util as Q                   # noqa: E402
+from hostmover_util import BOX as HBM, CAPSULE as HM      # noqa: E402
+from mover_util import FUSED, NONE, SENTINEL, boxcast as _boxcast, boxmove as _boxmove, records as _records, same as _same      # noqa: E402
 from query_util import unit_quats            # noqa: E402
 from test_cpu_boxmove import BATCH_SEED, DRAW      # noqa: E402
 from test_gpu_query import OBSERVED, SMALL, _same_stepped_world, _upload      # noqa: E402
@@ -22,29 +23,6 @@ from nudge_amd import engine as E           # noqa: E402
 from nudge_amd import scenes as S           # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-NONE = 0xFFFFFFFF
-FUSED = E.NH_FLAG_SINGLE_APPLY | E.NH_FLAG_FUSED_STEP
-SENTINEL = 0xA5
-
-
-def _boxmove(w, m):
-    raw = w.boxmove_records(_upload(w, m))
-    return np.frombuffer(raw.cpu().numpy().tobytes(), dtype=E.MOVE_RESULT).copy()
-
-
-def _boxcast(w, casts):
-    raw = w.boxcast_records(_upload(w, casts))
-    return np.frombuffer(raw.cpu().numpy().tobytes(), dtype=E.RAY_HIT).copy()
-
-
-def _same(got, ref, what):
-    bad = (got.view(np.uint8).reshape(-1, 64) != ref.view(np.uint8).reshape(-1, 64)).any(axis=1)
-    assert not bad.any(), f"{what}: {int(bad.sum())} of {len(ref)} move results differ, first at {int(np.argmax(bad))}: {got[np.argmax(bad)]} != {ref[np.argmax(bad)]}"
-
-
-def _records(w, scene):
-    return Q.records(w.get_bodies()["transforms"], scene, w.nbox, w.nsph)
 
 
 def _check_world(w, scene, rng, n, what, **kw):
@@ -104,7 +82,7 @@ def test_size_zero_is_nh_move_of_a_point_and_does_not_read_the_rotation():
     rec = _records(w, scene)
     m = BMB.moves(np.random.default_rng(BATCH_SEED + 11), rec, w.nbox, 4096)
     m["size"] = 0.0
-    m["rotation"] = HM.IDENTITY
+    m["rotation"] = MV.IDENTITY
     plain = _boxmove(w, m)
     _same(plain, HBM.move(rec, w.nbox, m), "rays")
     m["rotation"] = np.nan
@@ -125,7 +103,7 @@ def test_replay_from_the_host_gives_the_same_bytes():
     rec = _records(w, scene)
     m = BMB.moves(np.random.default_rng(BATCH_SEED + 12), rec, w.nbox, 2048)
     got = _boxmove(w, m)
-    ref, rounds = HBM.replay(m, lambda c: _boxcast(w, c))
+    ref, rounds = HBM.replay_move(m, lambda c: _boxcast(w, c))
     _same(got, ref, "replay")
     assert 3 <= rounds <= E.NH_MOVE_MAX_SLIDES + 1 and BMB.shares(got)[1] >= 0.02
     w.close()
@@ -310,7 +288,7 @@ def test_abi_edge_cases():
     assert py["position"].cpu().numpy().tobytes() == got["position"][k].tobytes() and np.array_equal(py["last_hit"]["shape"].cpu().numpy(), got["last_hit"]["shape"][k])
     # rotations=None is the identity: the axis-aligned box of a voxel world
     ident = m[k].copy()
-    ident["rotation"] = HM.IDENTITY
+    ident["rotation"] = MV.IDENTITY
     py = w.boxmove(ident["origin"], ident["displacement"], ident["size"], skin=ident["skin"], max_slides=ident["max_slides"].astype(np.int64),
                    ignore_body=ident["ignore_body"].astype(np.int64), synchronize=True)
     assert py["raw"].cpu().numpy().tobytes() == _boxmove(w, ident).tobytes()

@@ -1,6 +1,6 @@
 """nh_boxwalk on the GPU (pytest -m gpu): a grounded step for oriented boxes on the scene BVH (include/nudge_hip.h, "nh_boxmove, nh_boxwalk").
 
-The oracle is the host's brute force (tests/hostoracle/hostboxwalk.cpp through tests/hostboxwalk_util.py): the phase machine of
+The oracle is the host's brute force (tests/hostoracle/hostmover.cpp through tests/hostmover_util.py): the phase machine of
 nudge_amd/csrc/nh_query.h, "walk" -- the functions the kernel runs -- around a box cast over every collider, so the kernel's 112 bytes per walk must equal
 it bit for bit.  The identities of the header are tested against the GPU's own nh_boxmove, nh_boxcast and nh_walk."""
 import ctypes as C
@@ -12,10 +12,12 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import boxwalk_batches as BWB                # noqa: E402
-import hostboxwalk_util as HBW               # noqa: E402
+import hostmover_util as MV                  # noqa: E402
 import hostquery_util as Q                   # noqa: E402
-import hostwalk_util as HW                   # noqa: E402
 import walk_batches as WB                    # noqa: E402
+from hostmover_util import BOX as HBW        # noqa: E402
+from mover_util import (FUSED, NONE, SENTINEL, boxcast as _boxcast, boxmove as _boxmove, boxwalk as _boxwalk, records as _records,      # noqa: E402
+                        same as _same, terrain_world as _terrain_world)
 from test_cpu_boxwalk import TERRAIN_SEED, WORLD_SEED      # noqa: E402
 from test_cpu_walk import BALL_PIT_SHARES, RESTING, TERRAIN_SHARES, WORLD_SHARES, check_shares      # noqa: E402
 from test_gpu_query import OBSERVED, SMALL, _same_stepped_world, _upload      # noqa: E402
@@ -23,41 +25,6 @@ from nudge_amd import engine as E           # noqa: E402
 from nudge_amd import scenes as S           # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-NONE = 0xFFFFFFFF
-FUSED = E.NH_FLAG_SINGLE_APPLY | E.NH_FLAG_FUSED_STEP
-SENTINEL = 0xA5
-
-
-def _boxwalk(w, walks):
-    raw = w.boxwalk_records(_upload(w, walks))
-    return np.frombuffer(raw.cpu().numpy().tobytes(), dtype=E.WALK_RESULT).copy()
-
-
-def _boxmove(w, m):
-    raw = w.boxmove_records(_upload(w, m))
-    return np.frombuffer(raw.cpu().numpy().tobytes(), dtype=E.MOVE_RESULT).copy()
-
-
-def _boxcast(w, casts):
-    raw = w.boxcast_records(_upload(w, casts))
-    return np.frombuffer(raw.cpu().numpy().tobytes(), dtype=E.RAY_HIT).copy()
-
-
-def _same(got, ref, what):
-    bad = (got.view(np.uint8).reshape(-1, 112) != ref.view(np.uint8).reshape(-1, 112)).any(axis=1)
-    assert not bad.any(), f"{what}: {int(bad.sum())} of {len(ref)} walk results differ, first at {int(np.argmax(bad))}: {got[np.argmax(bad)]} != {ref[np.argmax(bad)]}"
-
-
-def _records(w, scene):
-    return Q.records(w.get_bodies()["transforms"], scene, w.nbox, w.nsph)
-
-
-def _terrain_world():
-    scene = WB.terrain()
-    w = E.World(scene, flags=FUSED)
-    w.query_build()
-    return w, scene, _records(w, scene)
 
 
 def test_terrain_walks_equal_the_brute_force():
@@ -135,9 +102,9 @@ def test_replay_from_the_host_gives_the_same_bytes(where):
         walks = BWB.world_walks(np.random.default_rng(WORLD_SEED + 21), rec, w.nbox, 2048)
     walks["min_ground_up"] = 0.0
     got = _boxwalk(w, walks)
-    ref, calls = HBW.replay(walks, lambda m: _boxmove(w, m), lambda c: _boxcast(w, c))
+    ref, calls = HBW.replay_walk(walks, lambda m: _boxmove(w, m), lambda c: _boxcast(w, c))
     _same(got, ref, f"replay on {where}")
-    s = HBW.shares(walks, got)
+    s = MV.shares(walks, got)
     assert s["stepped"] >= 0.02 and s["snapped"] >= 0.05 and calls >= 6, (s, calls)
     w.close()
 
@@ -153,7 +120,7 @@ def test_size_zero_does_not_read_the_rotation_and_is_nh_walk_of_a_point():
     _same(plain, HBW.walk(rec, w.nbox, walks), "rays")
     walks["rotation"] = np.nan
     _same(_boxwalk(w, walks), plain, "rays with NaN rotations")
-    s = HBW.shares(walks, plain)
+    s = MV.shares(walks, plain)
     assert (plain["flags"] & E.NH_WALK_INVALID == 0).all() and s["grounded"] >= 0.4 and s["snapped"] >= 0.05, s
     cw = np.zeros(len(walks), dtype=E.WALK)
     for name in ("origin", "skin", "displacement", "ignore_body", "rotation", "max_slides", "up", "step_height", "snap_distance", "min_ground_up", "options"):
@@ -319,7 +286,7 @@ def test_degenerate_worlds():
     walks["origin"][:, 1] += -10.0
     got = _boxwalk(w, walks)
     _same(got, HBW.walk(rec, w.nbox, walks), "one collider")
-    s = HBW.shares(walks, got)
+    s = MV.shares(walks, got)
     assert s["grounded"] > 0.4 and s["stepped"] == 0 and (got["slides"] <= 1).all(), s          # (one convex collider is never hit twice)
     w.close()
 
@@ -332,14 +299,14 @@ def test_degenerate_worlds():
     walks = BWB.world_walks(rng, rec, w.nbox, 2048, slab_share=0.0)
     got = _boxwalk(w, walks)
     _same(got, HBW.walk(rec, w.nbox, walks), "spheres only")
-    assert HBW.shares(walks, got)["slid"] > 0.1
+    assert MV.shares(walks, got)["slid"] > 0.1
     w.set_counts(nb, 301, 0)
     w.query_build()
     rec = _records(w, scene)
     walks = BWB.world_walks(rng, rec, w.nbox, 2048)
     got = _boxwalk(w, walks)
     _same(got, HBW.walk(rec, w.nbox, walks), "boxes only")
-    assert HBW.shares(walks, got)["slid"] > 0.1
+    assert MV.shares(walks, got)["slid"] > 0.1
     w.close()
 
 

@@ -1,6 +1,6 @@
 """nh_move on the GPU (pytest -m gpu): collide-and-slide for swept capsules on the scene BVH (include/nudge_hip.h, "nh_move").
 
-The oracle is the host's brute force (tests/hostoracle/hostmove.cpp through tests/hostmove_util.py): the state machine of nudge_amd/csrc/nh_query.h,
+The oracle is the host's brute force (tests/hostoracle/hostmover.cpp through tests/hostmover_util.py): the state machine of nudge_amd/csrc/nh_query.h,
 "move" -- the functions the kernel runs -- around a capsule cast over every collider, so the kernel's 64 bytes per move must equal it bit for bit.  The
 identities of the header are tested against the GPU's own nh_capsulecast: max_slides = 0, half height 0, and the REPLAY of the loop from the host."""
 import ctypes as C
@@ -11,38 +11,17 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import hostmove_util as HM                   # noqa: E402
+import hostmover_util as MV                  # noqa: E402
 import hostquery_util as Q                   # noqa: E402
 import move_batches as MB                    # noqa: E402
+from hostmover_util import CAPSULE as HM     # noqa: E402
+from mover_util import FUSED, NONE, SENTINEL, capsulecast as _capsulecast, move as _move, records as _records, same as _same      # noqa: E402
 from query_util import unit_quats            # noqa: E402
 from test_gpu_query import OBSERVED, SMALL, _same_stepped_world, _upload      # noqa: E402
 from nudge_amd import engine as E           # noqa: E402
 from nudge_amd import scenes as S           # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-NONE = 0xFFFFFFFF
-FUSED = E.NH_FLAG_SINGLE_APPLY | E.NH_FLAG_FUSED_STEP
-SENTINEL = 0xA5
-
-
-def _move(w, m):
-    raw = w.move_records(_upload(w, m))
-    return np.frombuffer(raw.cpu().numpy().tobytes(), dtype=E.MOVE_RESULT).copy()
-
-
-def _capsulecast(w, casts):
-    raw = w.capsulecast_records(_upload(w, casts))
-    return np.frombuffer(raw.cpu().numpy().tobytes(), dtype=E.RAY_HIT).copy()
-
-
-def _same(got, ref, what):
-    bad = (got.view(np.uint8).reshape(-1, 64) != ref.view(np.uint8).reshape(-1, 64)).any(axis=1)
-    assert not bad.any(), f"{what}: {int(bad.sum())} of {len(ref)} move results differ, first at {int(np.argmax(bad))}: {got[np.argmax(bad)]} != {ref[np.argmax(bad)]}"
-
-
-def _records(w, scene):
-    return Q.records(w.get_bodies()["transforms"], scene, w.nbox, w.nsph)
 
 
 def _check_world(w, scene, rng, n, what, **kw):
@@ -99,7 +78,7 @@ def test_half_height_zero_does_not_read_the_rotation():
     rec = _records(w, scene)
     m = MB.moves(np.random.default_rng(711), rec, w.nbox, 4096)
     m["half_height"] = 0.0
-    m["rotation"] = HM.IDENTITY
+    m["rotation"] = MV.IDENTITY
     plain = _move(w, m)
     _same(plain, HM.move(rec, w.nbox, m), "balls")
     m["rotation"] = np.nan
@@ -123,21 +102,9 @@ def test_replay_from_the_host_gives_the_same_bytes():
     rec = _records(w, scene)
     m = MB.moves(np.random.default_rng(712), rec, w.nbox, 2048)
     got = _move(w, m)
-    st = HM.begin(m)
-    last = np.zeros(len(m), dtype=E.RAY_HIT)
-    last["t"], last["body"], last["collider"], last["shape"], last["tag"] = 1.0, NONE, NONE, NONE, NONE
-    rounds = 0
-    while (st["stopped"] == 0).any():
-        assert rounds <= E.NH_MOVE_MAX_SLIDES
-        live = st["stopped"] == 0
-        hits = _capsulecast(w, HM.state_casts(m, st))
-        last[live] = hits[live]
-        HM.advance(m, st, hits)
-        rounds += 1
-    ref = np.zeros(len(m), dtype=E.MOVE_RESULT)
-    ref["position"], ref["remaining"], ref["flags"], ref["slides"], ref["last_hit"] = st["p"], st["v"], st["flags"], st["slides"], last
+    ref, rounds = HM.replay_move(m, lambda c: _capsulecast(w, c))
     _same(got, ref, "replay")
-    assert rounds >= 3 and MB.shares(got)[1] >= 0.02
+    assert 3 <= rounds <= E.NH_MOVE_MAX_SLIDES + 1 and MB.shares(got)[1] >= 0.02
     w.close()
 
 

@@ -1,6 +1,6 @@
 """nh_walk on the GPU (pytest -m gpu): a grounded character step on the scene BVH (include/nudge_hip.h, "nh_walk").
 
-The oracle is the host's brute force (tests/hostoracle/hostwalk.cpp through tests/hostwalk_util.py): the phase machine of nudge_amd/csrc/nh_query.h,
+The oracle is the host's brute force (tests/hostoracle/hostmover.cpp through tests/hostmover_util.py): the phase machine of nudge_amd/csrc/nh_query.h,
 "walk" -- the functions the kernel runs -- around a capsule cast over every collider, so the kernel's 112 bytes per walk must equal it bit for bit.  The
 identities of the header are tested against the GPU's own nh_move, nh_capsulecast and nh_spherecast."""
 import ctypes as C
@@ -11,51 +11,18 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import hostmove_util as HM                   # noqa: E402
+import hostmover_util as MV                  # noqa: E402
 import hostquery_util as Q                   # noqa: E402
-import hostwalk_util as HW                   # noqa: E402
 import walk_batches as WB                    # noqa: E402
+from hostmover_util import CAPSULE as HW     # noqa: E402
+from mover_util import (FUSED, NONE, SENTINEL, capsulecast as _capsulecast, move as _move, records as _records, same as _same,      # noqa: E402
+                        terrain_world as _terrain_world, walk as _walk)
 from test_cpu_walk import BALL_PIT_SHARES, RESTING, TERRAIN_SEED, TERRAIN_SHARES, WORLD_SEED, WORLD_SHARES, check_shares      # noqa: E402
 from test_gpu_query import OBSERVED, SMALL, _same_stepped_world, _upload      # noqa: E402
 from nudge_amd import engine as E           # noqa: E402
 from nudge_amd import scenes as S           # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-NONE = 0xFFFFFFFF
-FUSED = E.NH_FLAG_SINGLE_APPLY | E.NH_FLAG_FUSED_STEP
-SENTINEL = 0xA5
-
-
-def _walk(w, walks):
-    raw = w.walk_records(_upload(w, walks))
-    return np.frombuffer(raw.cpu().numpy().tobytes(), dtype=E.WALK_RESULT).copy()
-
-
-def _move(w, m):
-    raw = w.move_records(_upload(w, m))
-    return np.frombuffer(raw.cpu().numpy().tobytes(), dtype=E.MOVE_RESULT).copy()
-
-
-def _capsulecast(w, casts):
-    raw = w.capsulecast_records(_upload(w, casts))
-    return np.frombuffer(raw.cpu().numpy().tobytes(), dtype=E.RAY_HIT).copy()
-
-
-def _same(got, ref, what):
-    bad = (got.view(np.uint8).reshape(-1, 112) != ref.view(np.uint8).reshape(-1, 112)).any(axis=1)
-    assert not bad.any(), f"{what}: {int(bad.sum())} of {len(ref)} walk results differ, first at {int(np.argmax(bad))}: {got[np.argmax(bad)]} != {ref[np.argmax(bad)]}"
-
-
-def _records(w, scene):
-    return Q.records(w.get_bodies()["transforms"], scene, w.nbox, w.nsph)
-
-
-def _terrain_world():
-    scene = WB.terrain()
-    w = E.World(scene, flags=FUSED)
-    w.query_build()
-    return w, scene, _records(w, scene)
 
 
 def test_terrain_walks_equal_the_brute_force():
@@ -154,9 +121,9 @@ def test_replay_from_the_host_gives_the_same_bytes(where):
         walks = WB.world_walks(np.random.default_rng(WORLD_SEED + 21), rec, w.nbox, 2048)
     walks["min_ground_up"] = 0.0
     got = _walk(w, walks)
-    ref, calls = HW.replay(walks, lambda m: _move(w, m), lambda c: _capsulecast(w, c))
+    ref, calls = HW.replay_walk(walks, lambda m: _move(w, m), lambda c: _capsulecast(w, c))
     _same(got, ref, f"replay on {where}")
-    s = HW.shares(walks, got)
+    s = MV.shares(walks, got)
     assert s["stepped"] >= 0.02 and s["snapped"] >= 0.05 and calls >= 6, (s, calls)
     w.close()
 
@@ -167,12 +134,12 @@ def test_half_height_zero_does_not_read_the_rotation():
     walks = WB.terrain_walks(np.random.default_rng(TERRAIN_SEED + 3), 2048)
     walks["origin"][:, 1] -= walks["half_height"]                          # the balls stand where the capsules' lower ends stood
     walks["half_height"] = 0.0
-    walks["rotation"] = HM.IDENTITY
+    walks["rotation"] = MV.IDENTITY
     plain = _walk(w, walks)
     _same(plain, HW.walk(rec, w.nbox, walks), "balls")
     walks["rotation"] = np.nan
     _same(_walk(w, walks), plain, "balls with NaN rotations")
-    s = HW.shares(walks, plain)
+    s = MV.shares(walks, plain)
     assert (plain["flags"] & E.NH_WALK_INVALID == 0).all() and s["stepped"] >= 0.05 and s["snapped"] >= 0.05, s
     walks["max_slides"], walks["step_height"], walks["snap_distance"], walks["min_ground_up"] = 0, 0.0, 0.0, 0.0
     sph = np.zeros(len(walks), dtype=E.SPHERE_CAST)
@@ -340,7 +307,7 @@ def test_degenerate_worlds():
     walks["origin"][:, 1] += -10.0
     got = _walk(w, walks)
     _same(got, HW.walk(rec, w.nbox, walks), "one collider")
-    s = HW.shares(walks, got)
+    s = MV.shares(walks, got)
     assert s["grounded"] > 0.4 and s["stepped"] == 0 and (got["slides"] <= 1).all(), s          # (one convex collider is never hit twice)
     w.close()
 
@@ -353,7 +320,7 @@ def test_degenerate_worlds():
     walks = WB.world_walks(rng, rec, w.nbox, 2048, slab_share=0.0)
     got = _walk(w, walks)
     _same(got, HW.walk(rec, w.nbox, walks), "spheres only")
-    assert HW.shares(walks, got)["slid"] > 0.1
+    assert MV.shares(walks, got)["slid"] > 0.1
     w.close()
 
 

@@ -4,11 +4,12 @@ horizontally, on the terrain and on the worlds of query_util.SMALL."""
 import numpy as np
 
 import hostcapsule_util as HC
-import hostwalk_util as HW
+import hostmover_util as HV
+import move_batches as MB
+from hostmover_util import CAPSULE as HW
 from nudge_amd import engine as E
 from nudge_amd import scenes as S
 
-NONE = 0xFFFFFFFF
 SKIN = 0.01
 # what the generators draw from
 STEP_HEIGHTS = (0.0, 0.4, 1.0, 2.2)
@@ -61,7 +62,7 @@ def _draw_rules(rng, w, probe_share=0.1, snap_share=0.9):
     n = len(w)
     w["step_height"] = rng.choice(STEP_HEIGHTS, n)
     w["snap_distance"] = np.where(rng.random(n) < snap_share, SNAPS[1], SNAPS[0])
-    w["min_ground_up"] = HW.cos_deg(rng.choice(LIMITS, n))
+    w["min_ground_up"] = HV.cos_deg(rng.choice(LIMITS, n))
     w["options"] = (rng.random(n) < probe_share).astype(np.uint32) * E.NH_WALK_PROBE_ONLY
     w["max_slides"] = rng.integers(0, 9, n)
     return w
@@ -127,12 +128,5 @@ def world_walks(rng, rec, nbox, n, slab_share=0.7, free_share=0.9):
     length = rng.uniform(0.3, 2.5, m)
     d = np.stack([np.cos(ang) * length, np.where(rng.random(m) < 0.33, -rng.uniform(0.05, 0.3, m), 0.0), np.sin(ang) * length], axis=1)
     cand = _draw_rules(rng, HW.walks(stand(x, top, z, r, hh), d, r, hh, skin=SKIN))
-    q = np.zeros(m, dtype=E.OVERLAP_QUERY)
-    q["center"], q["shape"], q["rotation"], q["ignore_body"] = cand["origin"], E.NH_SHAPE_CAPSULE, cand["rotation"], NONE
-    q["size"][:, 0], q["size"][:, 1] = cand["radius"], cand["half_height"]
-    free = np.diff(HC.overlap(rec, nbox, q)[0].astype(np.int64)) == 0
-    first = np.nonzero(free)[0][:int(free_share * n)]
-    rest = np.setdiff1d(np.arange(m), first)[:n - len(first)]
-    pick = np.concatenate([first, rest])
-    rng.shuffle(pick)
-    return cand[pick]
+    free = np.diff(HC.overlap(rec, nbox, HW.overlap_queries(cand))[0].astype(np.int64)) == 0
+    return MB.take_free(rng, cand, free, n, free_share)

@@ -10,7 +10,7 @@ median [min .. max] of --repeats blocks of --reps calls, the calls of a comparis
 
 Logged with the times: how the records ended, the mean number of casts a record made and THE RATIO the documents quote: the call's time over (mean
 casts per record x the box cast's time) -- 1 if a record cost exactly its casts.  258 records of every batch are compared byte for byte with the brute
-force over all colliders (tests/hostboxmove_util.py, tests/hostboxwalk_util.py).
+force over all colliders (tests/hostmover_util.py).
 
 With NUDGE_HIP_LIBRARY naming another build of the library (the parent commit's: tools/build_variant.sh parent "" <rev>), two more worlds on THAT
 library answer nh_move, nh_walk, nh_boxcast and nh_capsulecast on the same records, filter off, interleaved with this library's.  Per block: this /
@@ -52,11 +52,9 @@ def main():
     a = ap.parse_args()
     import torch
     import boxwalk_batches as BWB
-    import hostboxmove_util as HBM
-    import hostboxwalk_util as HBW
-    import hostmove_util as HM
+    import hostmover_util as MV
+    from hostmover_util import BOX as HBM, CAPSULE as HM
     import hostquery_util as Q
-    import hostwalk_util as HW
     import walk_batches as WB
     from query_util import unit_quats
     scene = S.grid_tiles(124, side=90, seed=2, lattice_cols=11)
@@ -173,23 +171,23 @@ def main():
     head = np.where(on_slab, ang + np.pi, rng.uniform(0.0, 2 * np.pi, n))
     length = rng.uniform(0.5, 2.0, n)
     d = np.stack([np.cos(head) * length, np.zeros(n), np.sin(head) * length], axis=1)
-    base = HBW.walks(BWB.stand(x, top, z, WALK_BOX[1]), d, WALK_BOX, rotations=BWB._yaw(rng, n, 1.0), skin=WB.SKIN, max_slides=a.max_slides, snap_distance=0.3)
-    wcasts = HBM.first_casts(HBW.head(base))
+    base = HBM.walks(BWB.stand(x, top, z, WALK_BOX[1]), d, WALK_BOX, rotations=BWB._yaw(rng, n, 1.0), skin=WB.SKIN, max_slides=a.max_slides, snap_distance=0.3)
+    wcasts = HBM.first_casts(HBM.head(base))
     wct = up(wcasts)
     r112 = torch.empty((n, 112), dtype=torch.uint8, device=w.dev)
     say(f"nh_boxwalk, the upright box {WALK_BOX} turned about y, snap 0.3; half on the slab beside a body, half on a body's top ({OCCUPANCY['boxwalk']} waves per SIMD):")
     for name, step, limit in CONFIGS:
         wk = base.copy()
-        wk["step_height"], wk["min_ground_up"] = step, HBW.cos_deg(limit)
+        wk["step_height"], wk["min_ground_up"] = step, MV.cos_deg(limit)
         wt = up(wk)
         t = {k: med(v) for k, v in interleaved(dict(boxwalk=(w, "q_boxwalk", lambda: w.boxwalk_records(wt, results=r112)),
                                                     boxcast=(w, "q_boxcast", lambda: w.boxcast_records(wct, hits=h32)))).items()}
         got = down(r112, E.WALK_RESULT)
         checked = 0
         if not a.no_check:
-            assert got[pick].tobytes() == HBW.walk(rec, w.nbox, wk[pick]).tobytes(), "nh_boxwalk differs from the brute force"
+            assert got[pick].tobytes() == HBM.walk(rec, w.nbox, wk[pick]).tobytes(), "nh_boxwalk differs from the brute force"
             checked = len(pick)
-        s = HBW.shares(wk, got)
+        s = MV.shares(wk, got)
         s["start_overlap"] = float(((got["flags"] & E.NH_MOVE_START_OVERLAP) != 0).mean())
         mean_casts = float(got["casts"].mean())
         ratio = t["boxwalk"]["ms"] / (mean_casts * t["boxcast"]["ms"])
@@ -206,7 +204,7 @@ def main():
     if others:
         # move_rates' and walk_rates' capsule batches on the records drawn above
         cm = HM.moves(bm["origin"], bm["displacement"], 0.5, 0.5, skin=0.01, max_slides=a.max_slides)
-        cw = HW.walks(WB.stand(x, top, z, 0.3, 0.4), d, 0.3, 0.4, skin=WB.SKIN, max_slides=a.max_slides, snap_distance=0.3, step_height=1.0)
+        cw = HM.walks(WB.stand(x, top, z, 0.3, 0.4), d, 0.3, 0.4, skin=WB.SKIN, max_slides=a.max_slides, snap_distance=0.3, step_height=1.0)
         cc = HM.first_casts(cm)
         calls = (("move", "q_move", cm, 64, lambda wd, t_, r_: wd.move_records(t_, results=r_)),
                  ("walk", "q_walk", cw, 112, lambda wd, t_, r_: wd.walk_records(t_, results=r_)),

@@ -5,7 +5,7 @@ device events, interleaved, the median [min .. max] of --repeats blocks of --rep
 `slides`, how the moves ended, the mean number of casts a move made (slides + 1 where the last cast missed or started in overlap, else slides), and THE
 RATIO the documents quote: the move call's time over (mean casts per move x the capsule cast's time) -- 1 if a move cost exactly its casts; what is above
 it is divergence (a lane that has finished waits for the slowest of its wave) and the later casts being short and incoherent.  258 moves are compared
-byte for byte with the brute force over all colliders (tests/hostmove_util.py).
+byte for byte with the brute force over all colliders (tests/hostmover_util.py).
 
     python tools/move_rates.py [--steps 70] [--reps 10] [--repeats 5] [--out profiles/move_rates.log]
     (on a GPU box; prints the table, one JSON line at the end, and writes both to --out)
@@ -37,7 +37,7 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "move_rates.log"))
     a = ap.parse_args()
     import torch
-    import hostmove_util as HM
+    from hostmover_util import CAPSULE as HM
     scene = S.grid_tiles(124, side=90, seed=2, lattice_cols=11)
     nb = len(scene["body_transforms"])
     C = len(scene["box_tags"]) + len(scene["sphere_tags"])

@@ -43,7 +43,7 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "recover_rates.log"))
     a = ap.parse_args()
     import torch
-    import hostmove_util as HM
+    from hostmover_util import CAPSULE as HM
     import hostrecover_util as HR
     from query_util import unit_quats
     scene = S.grid_tiles(124, side=90, seed=2, lattice_cols=11)

@@ -6,8 +6,8 @@ interleaved, the median [min .. max] of --repeats blocks of --reps calls after t
 of casts a walk made, and THE RATIO the documents quote: the walk call's time over (mean casts per walk x the capsule cast's time) -- 1 if a walk cost
 exactly its casts; what is above it is divergence (a lane that has finished waits for the slowest of its wave) and the later casts being short and
 incoherent.  For step height 1.0 with the limit off, the HOST LOOP of the REPLAY identity is timed as well (wall clock, its uploads and downloads included: nh_move
-calls for the phases, an nh_capsulecast call for the probe and one per round of the first slide, tests/hostwalk_util.py replay) and compared byte for
-byte.  258 walks of every configuration are compared byte for byte with the brute force over all colliders (tests/hostwalk_util.py).
+calls for the phases, an nh_capsulecast call for the probe and one per round of the first slide, tests/hostmover_util.py replay_walk) and compared byte for
+byte.  258 walks of every configuration are compared byte for byte with the brute force over all colliders (tests/hostmover_util.py).
 
 With NUDGE_HIP_LIBRARY naming another build of the library (the parent commit's: tools/build_variant.sh parent "" <rev>), a second world on THAT library
 answers nh_move and nh_capsulecast on the same records, filter off, interleaved with this library's: the same bytes, and the ratio of the times.
@@ -45,8 +45,8 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "walk_rates.log"))
     a = ap.parse_args()
     import torch
-    import hostmove_util as HM
-    import hostwalk_util as HW
+    import hostmover_util as MV
+    from hostmover_util import CAPSULE as HW
     import walk_batches as WB
     scene = S.grid_tiles(124, side=90, seed=2, lattice_cols=11)
     nb = len(scene["body_transforms"])
@@ -121,7 +121,7 @@ def main():
     length = rng.uniform(0.5, 2.0, n)
     d = np.stack([np.cos(head) * length, np.zeros(n), np.sin(head) * length], axis=1)
     base = HW.walks(WB.stand(x, top, z, R, HH), d, R, HH, skin=WB.SKIN, max_slides=a.max_slides, snap_distance=0.3)
-    casts = HM.first_casts(HW.head(base))
+    casts = HW.first_casts(HW.head(base))
     ct = up(casts)
     ht = torch.empty((n, 32), dtype=torch.uint8, device=w.dev)
     rt = torch.empty((n, 112), dtype=torch.uint8, device=w.dev)
@@ -132,7 +132,7 @@ def main():
     pick = np.sort(np.random.default_rng(3).choice(n, size=258, replace=False))
     for name, step, limit in CONFIGS:
         wk = base.copy()
-        wk["step_height"], wk["min_ground_up"] = step, HW.cos_deg(limit)
+        wk["step_height"], wk["min_ground_up"] = step, MV.cos_deg(limit)
         wt = up(wk)
         t = interleaved(dict(walk=lambda: w.walk_records(wt, results=rt), capsulecast=lambda: w.capsulecast_records(ct, hits=ht)))
         got = down(rt, E.WALK_RESULT)
@@ -140,7 +140,7 @@ def main():
         if not a.no_check:
             assert got[pick].tobytes() == HW.walk(rec, w.nbox, wk[pick]).tobytes(), "the GPU differs from the brute force"
             checked = len(pick)
-        s = HW.shares(wk, got)
+        s = MV.shares(wk, got)
         s["start_overlap"] = float(((got["flags"] & E.NH_MOVE_START_OVERLAP) != 0).mean())
         mean_casts = float(got["casts"].mean())
         ratio = t["walk"]["ms"] / (mean_casts * t["capsulecast"]["ms"])
@@ -159,10 +159,10 @@ def main():
 
             def cast(c):
                 return down(w.capsulecast_records(up(c)), E.RAY_HIT)
-            HW.replay(wk[:4096], move, cast)
+            HW.replay_walk(wk[:4096], move, cast)
             stream.synchronize()
             t0 = time.perf_counter()
-            ref, calls = HW.replay(wk, move, cast)
+            ref, calls = HW.replay_walk(wk, move, cast)
             host_ms = (time.perf_counter() - t0) * 1e3
             assert ref.tobytes() == got.tobytes(), "the host loop differs from nh_walk"
             say(f"  the host loop of the REPLAY identity   {host_ms:.1f} ms wall clock, {calls} GPU calls with their uploads and downloads; the same bytes;"
