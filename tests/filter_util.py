@@ -12,17 +12,13 @@ import hostcastk_util as HK                  # noqa: E402
 import hostdistance_util as D                # noqa: E402
 import hostnearest_util as N                 # noqa: E402
 import hostpen_util as HPEN                  # noqa: E402
-import test_gpu_boxcast as TB                # noqa: E402
-import test_gpu_capsulecast as TC            # noqa: E402
 import test_gpu_closest as TP                # noqa: E402
 import test_gpu_distance as TD               # noqa: E402
 import test_gpu_overlap as TO                # noqa: E402
 import test_gpu_penetration as TPEN          # noqa: E402
 import test_gpu_refit as TR                  # noqa: E402
-import test_gpu_spherecast as TS             # noqa: E402
-from query_util import bounds, unit_quats    # noqa: E402
-from test_gpu_query import _rays             # noqa: E402
-from nudge_amd import engine as E           # noqa: E402
+from cast_util import boxes, capsules, spheres      # noqa: E402
+from query_util import bounds, rays as _rays, unit_quats    # noqa: E402
 
 NONE = 0xFFFFFFFF
 SENTINEL = 0xA5
@@ -65,12 +61,12 @@ def batch(rng, rec, n=N_PER_KIND):
     points = np.concatenate([TP._points(rng, n, rec, lo, hi, kind) for kind in ("inside", "uniform", "above")])
     b = dict(
         rays=rays,
-        spheres=TS._casts(rays, rng.choice(np.float32(TS.RADII), size=m)),
-        boxes=TB._casts(rays, rng.choice(np.float32(TB.SIZES), size=m), unit_quats(rng, m)),
-        capsules=TC._casts(rays, rng.choice(np.float32([0.05, 0.5, 1.0]), size=m), rng.choice(np.float32([0.0, 0.5, 2.0]), size=m), unit_quats(rng, m)),
+        spheres=spheres(rays, rng.choice(np.float32((0.05, 0.5, 2.0)), size=m)),
+        boxes=boxes(rays, rng.choice(np.float32((0.05, 0.5, 2.0)), size=m), unit_quats(rng, m)),
+        capsules=capsules(rays, rng.choice(np.float32([0.05, 0.5, 1.0]), size=m), rng.choice(np.float32([0.0, 0.5, 2.0]), size=m), unit_quats(rng, m)),
         points=TP._queries(points, max_distance=rng.choice(np.float32([np.inf, 0.5, 2.0]), size=len(points))),
         overlaps=np.concatenate([TO._queries(rng, n, rec, kind) for kind in ("sphere", "box", "mixed")]),
-        capsule_overlaps=TC._capsule_queries(rng, n, rec))
+        capsule_overlaps=TO._capsule_queries(rng, n, rec))
     b["distances"] = np.concatenate([q for shape in TD.SHAPES for q in TD._batches(rng, shape, rec, n=24).values()])
     b["penetrations"] = TPEN._queries(rng, 3 * n, rec, "mixed")
     return b

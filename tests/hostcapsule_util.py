@@ -1,6 +1,6 @@
-"""ctypes access to the capsule oracle of tests/hostoracle/hostcapsule.cpp (built by tests/hostlib.py): the capsule arithmetic of
-nudge_amd/csrc/nh_query.h with the device's bits, and a brute-force nh_capsulecast over all colliders with the header's exact rules, the oracle of the
-GPU's tree traversal.  overlap() is hostoverlap_util's with capsule queries valid."""
+"""ctypes access to the capsule predicates of tests/hostoracle/hostshapes.cpp (built by tests/hostlib.py): the capsule arithmetic of
+nudge_amd/csrc/nh_query.h with the device's bits.  overlap() is hostoverlap_util's with capsule queries valid; the capsule casts are
+tests/hostcast_util.py's."""
 import ctypes as C
 import numpy as np
 
@@ -8,10 +8,8 @@ import hostlib as H
 from hostlib import records      # noqa: F401
 import hostoverlap_util as O
 from hostquery_util import _hit5
-from nudge_amd import engine as E
 
 _SIG = {
-    "hc_capsulecast": ([C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_uint32], None),
     "hc_sweep_capsule_box": ([C.c_void_p] * 3 + [C.c_float, C.c_float] + [C.c_void_p] * 4, None),
     "hc_sweep_capsule_sphere": ([C.c_void_p] * 3 + [C.c_float, C.c_float, C.c_void_p, C.c_float, C.c_void_p], None),
     "hc_overlap_capsule_box": ([C.c_void_p] * 2 + [C.c_float, C.c_float] + [C.c_void_p] * 3, C.c_int),
@@ -19,15 +17,6 @@ _SIG = {
     "hc_capsule_axis": ([C.c_void_p, C.c_float, C.c_void_p], None),
 }
 lib = H.oracle(_SIG)
-
-
-def capsulecast(rec, nbox, casts, only=-1, threads=None):
-    """nh_RayHit records (E.RAY_HIT) of `casts` (E.CAPSULE_CAST) by brute force over `rec`; `only` >= 0: that one collider (combined index) alone."""
-    casts = np.ascontiguousarray(casts, dtype=E.CAPSULE_CAST)
-    hits = np.zeros(len(casts), dtype=E.RAY_HIT)
-    rec = np.ascontiguousarray(rec, dtype=H.REC)
-    lib().hc_capsulecast(H.p(rec), len(rec), nbox, H.p(casts), len(casts), H.p(hits), int(only), H.threads(threads))
-    return hits
 
 
 def overlap(rec, nbox, queries, capacity=None, hits=None, threads=None):

@@ -1,43 +1,26 @@
 """The oracle of the first-k casts (nh_raycast_k / nh_spherecast_k / nh_boxcast_k / nh_capsulecast_k of include/nudge_hip.h), in plain Python over
-oracles that exist and share no code with the feature: the all-hits brute forces of tests/hostcastall_util.py and tests/hostcastall_shapes_util.py give
-each cast's segment, which is cut at k and padded with the miss record; for a cast whose segment is empty the miss is the record of the existing
-closest-hit brute force (hostquery_util, hostsweep_util, hostboxcast_util, hostcapsule_util), which must be a miss.  Nothing here keeps a bounded
-list.  premise() is tests/hostoracle/hostcastk.cpp: the pruning premise of the k walk, counted at the leaves."""
+oracles that exist and share no code with the feature: the all-hits brute force of tests/hostcast_util.py gives each cast's segment, which is cut at
+k and padded with the miss record; for a cast whose segment is empty the miss is the record of the closest-hit brute force beside it (a loop of its
+own over other predicates), which must be a miss.  Nothing here keeps a bounded list.  premise() is tests/hostoracle/hostcastk.cpp: the pruning
+premise of the k walk, counted at the leaves."""
 import ctypes as C
 
 import numpy as np
 
-import hostboxcast_util as B
-import hostcapsule_util as K
-import hostcastall_shapes_util as AS
-import hostcastall_util as A
 import hostlib as H
-import hostquery_util as Q
-import hostsweep_util as W
+from hostcast_util import cast, cast_all, shape_of
 from hostlib import records      # noqa: F401
 from nudge_amd import engine as E
 
 NONE = 0xFFFFFFFF
-# per shape: the cast record, the all-hits brute force, the closest-hit brute force, the shape number of hk_premise
-SHAPES = {
-    "ray": (E.RAY, A.raycast_all, Q.raycast, 0),
-    "sphere": (E.SPHERE_CAST, A.spherecast_all, W.spherecast, 1),
-    "box": (E.BOX_CAST, AS.boxcast_all, B.boxcast, 2),
-    "capsule": (E.CAPSULE_CAST, AS.capsulecast_all, K.capsulecast, 3),
-}
 
 _lib = H.oracle({"hk_premise": ([C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_float, C.c_uint32],
                                 C.c_uint64)})
 
 
-def shape_of(casts):
-    """The key of SHAPES whose record type `casts` has."""
-    return next(name for name, s in SHAPES.items() if s[0] == casts.dtype)
-
-
 def segments(rec, nbox, casts):
     """(offsets, hits) of the all-hits brute force for `casts`, whatever their shape: every segment complete."""
-    off, hits, total = SHAPES[shape_of(casts)][1](rec, nbox, casts)
+    off, hits, total = cast_all(shape_of(casts), rec, nbox, casts)
     assert total < NONE
     return off, hits[:total]
 
@@ -45,7 +28,7 @@ def segments(rec, nbox, casts):
 def misses(rec, nbox, casts, empty):
     """The miss record of every cast (E.RAY_HIT): shape NONE, normal 0, nobody, t = max_t -- NaN where the closest-hit brute force writes NaN.  For
     the casts of an `empty` segment it is that brute force's own record, which must be a miss."""
-    best = SHAPES[shape_of(casts)][2](rec, nbox, casts)
+    best = cast(shape_of(casts), rec, nbox, casts)
     assert (best["shape"][empty] == NONE).all(), "the closest-hit brute force hits where the all-hits segment is empty"
     # a record the closest-hit call writes as t = NaN: exactly the invalid ones, which list nothing (so `best` is their miss), and a NaN max_t
     miss = np.zeros(len(casts), dtype=E.RAY_HIT)
@@ -77,5 +60,5 @@ def premise(rec, nbox, casts, seg=None, extra=0.0, threads=None):
     casts = np.ascontiguousarray(casts)
     hits = np.ascontiguousarray(hits) if len(hits) else np.zeros(1, dtype=E.RAY_HIT)
     off = np.ascontiguousarray(off, dtype=np.uint32)
-    return int(_lib().hk_premise(H.p(rec), len(rec), nbox, SHAPES[shape_of(casts)][3], H.p(casts), len(casts), H.p(off), H.p(hits), C.c_float(extra),
+    return int(_lib().hk_premise(H.p(rec), len(rec), nbox, shape_of(casts).number, H.p(casts), len(casts), H.p(off), H.p(hits), C.c_float(extra),
                                  H.threads(threads)))

@@ -2,7 +2,7 @@
 //   ho_overlap   offsets and records of a batch of sphere and box queries by brute force over all colliders, with the header's exact semantics
 //                (ignore_body, invalid queries, capacity prefix, the 2^32 - 1 marker), on several threads: oracle.h's overlap_all
 //   hc_overlap   the same with capsule queries valid, as nh_overlap has them now; to ho_overlap a capsule query is invalid
-//   ho_*         the three predicates alone (the capsule's: hostcapsule.cpp)
+//   ho_*         the three predicates alone (the capsule's: hostshapes.cpp)
 #include "oracle.h"
 
 static uint64_t overlap(const Rec* rec, uint32_t n, uint32_t nbox, const nh_OverlapQuery* queries, uint32_t count, uint32_t* offsets, nh_OverlapHit* hits,

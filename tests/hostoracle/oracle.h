@@ -1,5 +1,5 @@
 // oracle.h -- what the host oracles of the scene queries (tests/hostoracle/host*.cpp, one library: tests/hostlib.py) have in common: the collider
-// record, the thread loop, the rules every answer record encodes, and the one brute-force closest-hit cast of a swept capsule or box.  Built with g++
+// record, the thread loop, the rules every answer record encodes, the swept shapes of the casts and the one brute-force closest-hit cast over them.  Built with g++
 // -ffp-contract=off, so that nudge_amd/csrc/nh_query.h's arithmetic returns the device's bits.  Shared between oracles only: nothing here walks a tree or
 // keeps a list, which is what the oracles judge.
 #pragma once
@@ -106,8 +106,26 @@ static inline void write_cast(nh_RayHit& out, const Rec* rec, uint32_t nbox, boo
 	else write_ray_hit(out, rec, nbox, bc, bt, bn);
 }
 
-// The swept shapes of the closest-hit casts and the movers (hostcapsule.cpp, hostboxcast.cpp, hostmover.cpp).  Each gives the validity of its own fields,
-// the half extent of its bounds for the cast's pad, whether the reach rule applies to it, and its sweep from o along d against one collider.
+// The swept shapes of the casts and the movers (hostcast.cpp, hostcastk.cpp, hostmover.cpp), each rule written once.  Each gives the validity of its own
+// fields, the half extent of its bounds for the cast's pad, whether the reach rule applies to it, its closest-hit sweep from o along d against one collider,
+// and its all-hits decision on one collider (nh_query.h's nh_q_all_hit*: t0 = the entry into the collider's leaf box, read only under the reach rule).
+// SweptRay: nothing but the ray's own predicates
+struct SweptRay {
+	bool valid() const { return true; }
+	nh_f3 extent() const { return nh_make3(0.0f, 0.0f, 0.0f); }
+	bool reach() const { return false; }
+	nh_QHit sweep(nh_f3 o, nh_f3 d, bool box, nh_f3 p, nh_quat qb, nh_f3 hb) const { return box ? nh_q_ray_box(o, d, p, qb, hb) : nh_q_ray_sphere(o, d, p, hb.x); }
+	nh_QHit all_hit(nh_f3 o, nh_f3 d, float max_t, float t0, nh_f3 p, nh_quat qb, nh_f3 hb, bool box) const { return nh_q_all_hit<false>(o, d, 0.0f, max_t, t0, p, qb, hb, box); }
+};
+// SweptSphere: radius r.  r = 0 is a ray
+struct SweptSphere {
+	float r;
+	bool valid() const { return finite(r) && !(r < 0.0f); }
+	nh_f3 extent() const { return nh_make3(r, r, r); }
+	bool reach() const { return r > 0.0f; }
+	nh_QHit sweep(nh_f3 o, nh_f3 d, bool box, nh_f3 p, nh_quat qb, nh_f3 hb) const { return box ? nh_q_sweep_box(o, d, r, p, qb, hb) : nh_q_sweep_sphere(o, d, r, p, hb.x); }
+	nh_QHit all_hit(nh_f3 o, nh_f3 d, float max_t, float t0, nh_f3 p, nh_quat qb, nh_f3 hb, bool box) const { return nh_q_all_hit<true>(o, d, r, max_t, t0, p, qb, hb, box); }
+};
 // SweptCapsule: rotation q, radius r, half height hh.  hh = 0 is a ball, which does not read its rotation to be valid; r = hh = 0 is a ray
 struct SweptCapsule {
 	nh_quat q; float r, hh;
@@ -117,6 +135,7 @@ struct SweptCapsule {
 	nh_QHit sweep(nh_f3 o, nh_f3 d, bool box, nh_f3 p, nh_quat qb, nh_f3 hb) const {
 		return box ? nh_q_sweep_capsule_box(o, d, q, r, hh, p, qb, hb) : nh_q_sweep_capsule_sphere(o, d, q, r, hh, p, hb.x);
 	}
+	nh_QHit all_hit(nh_f3 o, nh_f3 d, float max_t, float t0, nh_f3 p, nh_quat qb, nh_f3 hb, bool box) const { return nh_q_all_hit_capsule(o, d, q, r, hh, max_t, t0, p, qb, hb, box); }
 };
 // SweptBox: rotation q, half extents h.  h = (0, 0, 0) is a ray, which does not read its rotation at all
 struct SweptBox {
@@ -130,7 +149,35 @@ struct SweptBox {
 	nh_QHit sweep(nh_f3 o, nh_f3 d, bool box, nh_f3 p, nh_quat qb, nh_f3 hb) const {
 		return box ? nh_q_sweep_box_box(o, d, q, h, p, qb, hb) : nh_q_sweep_box_sphere(o, d, q, h, p, hb.x);
 	}
+	nh_QHit all_hit(nh_f3 o, nh_f3 d, float max_t, float t0, nh_f3 p, nh_quat qb, nh_f3 hb, bool box) const { return nh_q_all_hit_box(o, d, q, h, max_t, t0, p, qb, hb, box); }
 };
+
+// the swept shape of a cast record; all four records start with nh_Ray's fields (origin, max_t, direction, ignore_body)
+static inline SweptRay swept(const nh_Ray&) { return SweptRay{}; }
+static inline SweptSphere swept(const nh_SphereCast& c) { return SweptSphere{ c.radius }; }
+static inline SweptBox swept(const nh_BoxCast& c) { return SweptBox{ q4(c.rotation), v3(c.size) }; }
+static inline SweptCapsule swept(const nh_CapsuleCast& c) { return SweptCapsule{ q4(c.rotation), c.radius, c.half_height }; }
+
+// f(the records, typed) for the shape number of the entry points that take one: 0 nh_Ray, 1 nh_SphereCast, 2 nh_BoxCast, 3 nh_CapsuleCast; all ones for any other
+template <class F> static uint64_t by_shape(uint32_t shape, const void* casts, F f) {
+	switch (shape) {
+	case 0: return f(static_cast<const nh_Ray*>(casts));
+	case 1: return f(static_cast<const nh_SphereCast*>(casts));
+	case 2: return f(static_cast<const nh_BoxCast*>(casts));
+	case 3: return f(static_cast<const nh_CapsuleCast*>(casts));
+	}
+	return ~0ull;
+}
+
+static inline bool finite3(nh_f3 a) { return finite(a.x) && finite(a.y) && finite(a.z); }
+
+// the per-axis grow of the node boxes for the shape `a` cast from o: its extent and the cast's pad (nh_q_cast_node3's w; the same on every axis it is
+// nh_q_cast_node's, to the bit)
+template <class S> static nh_f3 cast_grow(const S& a, nh_f3 o) {
+	const nh_f3 e = a.extent();
+	const float s = nh_q_cast_pad(o, fmaxf(fmaxf(e.x, e.y), e.z));
+	return nh_make3(e.x + s, e.y + s, e.z + s);
+}
 
 // The closest hit of the shape `a` cast from o along d up to max_t, by brute force over all colliders with the header's exact rules: invalid casts (which
 // look at no collider), ignore_body, ties, the reach rule.  words, mask: colliders whose layer word shares no bit with the mask do not exist for this cast
@@ -139,11 +186,8 @@ struct SweptBox {
 template <class S>
 static bool closest_hit(const Rec* rec, uint32_t n, uint32_t nbox, const S& a, nh_f3 o, nh_f3 d, float max_t, uint32_t ignore_body, const uint32_t* words,
                         uint32_t mask, int64_t only, float& bt, uint32_t& bc, nh_f3& bn) {
-	const bool ok = finite(o.x) && finite(o.y) && finite(o.z) && finite(d.x) && finite(d.y) && finite(d.z) && a.valid();
-	const nh_f3 inv = nh_make3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
-	const nh_f3 e = a.extent();
-	const float s = nh_q_cast_pad(o, fmaxf(fmaxf(e.x, e.y), e.z));
-	const nh_f3 w = nh_make3(e.x + s, e.y + s, e.z + s);
+	const bool ok = finite3(o) && finite3(d) && a.valid();
+	const nh_f3 inv = nh_make3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z), w = cast_grow(a, o);
 	const bool reach = a.reach();
 	bt = max_t; bc = 0xffffffffu; bn = nh_make3(0.0f, 0.0f, 0.0f);
 	const uint32_t c0 = only >= 0 ? (uint32_t)only : 0u, c1 = only >= 0 ? (uint32_t)only + 1u : n;

@@ -1,14 +1,13 @@
-"""ctypes access to the ray-cast oracle of tests/hostoracle/hostquery.cpp (built by tests/hostlib.py): the scene query's per-item arithmetic
-(nudge_amd/csrc/nh_query.h) with the device's bits, and a brute-force closest hit over all colliders, the oracle of the GPU's tree traversal."""
+"""ctypes access to the ray predicates and the collider pose of tests/hostoracle/hostshapes.cpp (built by tests/hostlib.py): the scene query's
+per-item arithmetic (nudge_amd/csrc/nh_query.h) with the device's bits, and the per-collider records every query oracle reads.  The casts themselves
+are tests/hostcast_util.py's."""
 import ctypes as C
 import numpy as np
 
 import hostlib as H
 from hostlib import REC, records      # noqa: F401  (the per-collider records every query oracle reads)
-from nudge_amd import engine as E
 
 _SIG = {
-    "hq_raycast": ([C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_uint32], None),
     "hq_ray_box": ([C.c_void_p] * 6, None),
     "hq_ray_sphere": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p], None),
     "hq_pose": ([C.c_void_p] * 5, None),
@@ -21,15 +20,6 @@ def _hit5(fn, *args):
     out = np.zeros(5, dtype=np.float32)
     fn(*args, H.p(out))
     return float(out[0]), out[1:4].copy(), bool(out[4])
-
-
-def raycast(rec, nbox, rays, only=-1, threads=None):
-    """nh_RayHit records (E.RAY_HIT) of `rays` (E.RAY) by brute force over `rec`; `only` >= 0: that one collider (combined index) alone."""
-    rays = np.ascontiguousarray(rays, dtype=E.RAY)
-    hits = np.zeros(len(rays), dtype=E.RAY_HIT)
-    rec = np.ascontiguousarray(rec, dtype=REC)
-    lib().hq_raycast(H.p(rec), len(rec), nbox, H.p(rays), len(rays), H.p(hits), int(only), H.threads(threads))
-    return hits
 
 
 def ray_box(o, d, p, q, h):

@@ -2,19 +2,16 @@
 result records, a world's collider records, the terrain world, and the miss record."""
 import numpy as np
 
-import hostquery_util as Q
 import walk_batches as WB
+from query_util import FUSED, NONE, records, upload      # noqa: F401
 from nudge_amd import engine as E
 
-NONE = 0xFFFFFFFF
-FUSED = E.NH_FLAG_SINGLE_APPLY | E.NH_FLAG_FUSED_STEP
 SENTINEL = 0xA5
 
 
 def _call(name, result):
     def call(w, records):
-        from test_gpu_query import _upload
-        raw = getattr(w, name + "_records")(_upload(w, records))
+        raw = getattr(w, name + "_records")(upload(w, records))
         return np.frombuffer(raw.cpu().numpy().tobytes(), dtype=result).copy()
     call.__doc__ = f"World.{name}_records on the numpy records `records`: its result records, back on the host."
     return call
@@ -30,11 +27,6 @@ def same(got, ref, what):
     size, kind = ref.dtype.itemsize, "walk" if ref.dtype == E.WALK_RESULT else "move"
     bad = (got.view(np.uint8).reshape(-1, size) != ref.view(np.uint8).reshape(-1, size)).any(axis=1)
     assert not bad.any(), f"{what}: {int(bad.sum())} of {len(ref)} {kind} results differ, first at {int(np.argmax(bad))}: {got[np.argmax(bad)]} != {ref[np.argmax(bad)]}"
-
-
-def records(w, scene):
-    """The collider records of the world `w` as its bodies stand now."""
-    return Q.records(w.get_bodies()["transforms"], scene, w.nbox, w.nsph)
 
 
 def terrain_world():

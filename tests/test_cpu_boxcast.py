@@ -1,5 +1,5 @@
 """Box casts on the host (no GPU): the nh_BoxCast record of include/nudge_hip.h against its Python mirrors, and the box-cast arithmetic of
-nudge_amd/csrc/nh_query.h -- built for the host by tests/hostboxcast_util.py, the same bits as the device -- against a float64 model of the same
+nudge_amd/csrc/nh_query.h -- built for the host by tests/hostcast_util.py, the same bits as the device -- against a float64 model of the same
 definition, the named cases of its exact semantics, near-parallel edges and far casts, the ray predicates at size 0 and the overlap predicates at t = 0."""
 import ctypes
 import os
@@ -10,12 +10,13 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-import hostboxcast_util as B                 # noqa: E402
+import hostcast_util as CAST                 # noqa: E402
 import hostoverlap_util as O                 # noqa: E402
 import hostquery_util as Q                   # noqa: E402
+from cast_util import sweep_box64 as _sweep_box64      # noqa: E402
+from query_util import mat as _mat, unit_quats as _unit_quats      # noqa: E402
 from nudge_amd import engine as E           # noqa: E402
 from nudge_amd import scenes as S           # noqa: E402
-from test_cpu_spherecast import _mat, _sweep_box64, _unit_quats      # noqa: E402
 
 NONE = 0xFFFFFFFF
 EPS = 2.0 ** -20           # NH_Q_SAT_EPS: the radii of the 15-axis test use |R| + EPS
@@ -132,7 +133,7 @@ def test_box_box_sweeps_against_the_float64_model():
                 continue            # (the entering axis changes with the sizes)
             if max(abs(lo[1] - ref[1]), abs(hi[1] - ref[1])) > 1e-3 * max(ref[1], 1.0):
                 continue
-        t, nn, hit = B.sweep_box_box(o[i], d[i], qa[i], ha[i], p[i], qb[i], hb[i])
+        t, nn, hit = CAST.sweep_box_box(o[i], d[i], qa[i], ha[i], p[i], qb[i], hb[i])
         compared += 1
         assert hit == ref[0], (i, hit, ref)
         if not hit:
@@ -222,7 +223,7 @@ def test_near_parallel_edges_and_far_casts_never_miss():
         ref = _sweep64(o64, d64, _mat(qa), ha64, p64, _mat(qb), hb64)
         if not ref[0]:
             continue
-        t, nn, hit = B.sweep_box_box(o, d, qa, ha, p, qb, hb)
+        t, nn, hit = CAST.sweep_box_box(o, d, qa, ha, p, qb, hb)
         assert hit, (k, angle, dist, ref[1])
         assert abs(t - ref[1]) <= 1e-5 * max(ref[1], 1.0) + 1e-3 / np.linalg.norm(d64), (k, angle, dist, t, ref[1])
         assert abs(np.linalg.norm(nn.astype(np.float64)) - 1.0) <= 1e-6 and nn.astype(np.float64) @ d64 < 0.0
@@ -253,7 +254,7 @@ def test_elongated_rolled_bars_near_parallel_are_not_hit_across_a_gap():
         # towards the collider from one unit further back
         o_back, d_in = (o - n).astype(np.float32), n.astype(np.float32)
         ref = _sweep64(o_back.astype(np.float64), d_in.astype(np.float64), Ra, h64, p64, Rb, h64)
-        t, nn, hit = B.sweep_box_box(o_back, d_in, qa, half, p, qb, half)
+        t, nn, hit = CAST.sweep_box_box(o_back, d_in, qa, half, p, qb, half)
         assert hit == ref[0], (k, ref)
         if hit and ref[3] != "start":
             towards += 1
@@ -264,7 +265,7 @@ def test_elongated_rolled_bars_near_parallel_are_not_hit_across_a_gap():
         away += 1
         for d in ((-n).astype(np.float32), np.float32([1, 0, 0]), np.float32([-1, 0, 0])):
             ref = _sweep64(o64, d.astype(np.float64), Ra, h64, p64, Rb, h64)
-            t, nn, hit = B.sweep_box_box(o, d, qa, half, p, qb, half)
+            t, nn, hit = CAST.sweep_box_box(o, d, qa, half, p, qb, half)
             assert not (hit and t == 0.0), (k, d, gap, ref)
             assert hit == ref[0], (k, d, gap, ref)
     assert towards > 400 and away > 400, (towards, away)
@@ -287,7 +288,7 @@ def test_box_against_a_sphere_collider_against_float64():
             continue
         if ref[0] and max(abs(lo[1] - ref[1]), abs(hi[1] - ref[1])) > 1e-3 * max(ref[1], 1.0):
             continue
-        t, nn, hit = B.sweep_box_sphere(o[i], d[i], qa[i], ha[i], c[i], R[i])
+        t, nn, hit = CAST.sweep_box_sphere(o[i], d[i], qa[i], ha[i], c[i], R[i])
         compared += 1
         assert hit == ref[0], i
         if hit:
@@ -308,9 +309,9 @@ def test_size_zero_is_the_ray_predicate_bit_for_bit():
     hits = 0
     for i in range(n):
         for z in ((0.0, 0.0, 0.0), (-0.0, 0.0, -0.0)):
-            a, b = B.sweep_box_box(o[i], d[i], nanq, z, p[i], qb[i], hb[i]), Q.ray_box(o[i], d[i], p[i], qb[i], hb[i])
+            a, b = CAST.sweep_box_box(o[i], d[i], nanq, z, p[i], qb[i], hb[i]), Q.ray_box(o[i], d[i], p[i], qb[i], hb[i])
             assert a[2] == b[2] and np.float32(a[0]).tobytes() == np.float32(b[0]).tobytes() and a[1].tobytes() == b[1].tobytes(), i
-            a, b = B.sweep_box_sphere(o[i], d[i], nanq, z, p[i], hb[i, 0]), Q.ray_sphere(o[i], d[i], p[i], hb[i, 0])
+            a, b = CAST.sweep_box_sphere(o[i], d[i], nanq, z, p[i], hb[i, 0]), Q.ray_sphere(o[i], d[i], p[i], hb[i, 0])
             assert a[2] == b[2] and np.float32(a[0]).tobytes() == np.float32(b[0]).tobytes() and a[1].tobytes() == b[1].tobytes(), i
             hits += a[2]
     assert hits > 0.2 * n
@@ -324,7 +325,7 @@ def test_size_zero_is_the_ray_predicate_bit_for_bit():
     for k in ("origin", "direction", "max_t", "ignore_body"):
         casts[k] = rays[k]
     casts["rotation"][::2] = np.nan
-    assert B.boxcast(rec, nbox, casts).tobytes() == Q.raycast(rec, nbox, rays).tobytes()
+    assert CAST.cast(CAST.BOX, rec, nbox, casts).tobytes() == CAST.cast(CAST.RAY, rec, nbox, rays).tobytes()
 
 
 def test_a_start_overlap_under_the_overlap_predicates_hits_at_zero():
@@ -341,11 +342,11 @@ def test_a_start_overlap_under_the_overlap_predicates_hits_at_zero():
         inside = Q.ray_box(o[i], d[i], o[i], (0, 0, 0, 1), (1, 1, 1))[1]          # nh_q_inside(d): the ray's inside rule, bit for bit
         if O.box_box(o[i], qa[i], ha[i], ctr[i], qb[i], hb[i]):
             boxes += 1
-            t, nn, hit = B.sweep_box_box(o[i], d[i], qa[i], ha[i], ctr[i], qb[i], hb[i])
+            t, nn, hit = CAST.sweep_box_box(o[i], d[i], qa[i], ha[i], ctr[i], qb[i], hb[i])
             assert hit and t == 0.0 and nn.tobytes() == inside.tobytes(), i
         if O.sphere_box(ctr[i], hb[i, 0], o[i], qa[i], ha[i]):
             spheres += 1
-            t, nn, hit = B.sweep_box_sphere(o[i], d[i], qa[i], ha[i], ctr[i], hb[i, 0])
+            t, nn, hit = CAST.sweep_box_sphere(o[i], d[i], qa[i], ha[i], ctr[i], hb[i, 0])
             assert hit and t == 0.0 and nn.tobytes() == inside.tobytes(), i
     assert boxes > 300 and spheres > 300, (boxes, spheres)
 
@@ -375,7 +376,7 @@ def _cast(world, o, d, h, q=(0, 0, 0, 1), max_t=np.inf, ignore=NONE):
     rec, nbox = world
     c = np.zeros(1, dtype=E.BOX_CAST)
     c["origin"], c["direction"], c["size"], c["rotation"], c["max_t"], c["ignore_body"] = o, d, h, q, max_t, ignore
-    return B.boxcast(rec, nbox, c)[0]
+    return CAST.cast(CAST.BOX, rec, nbox, c)[0]
 
 
 TOL = 1e-5       # the radii carry 2^-20 per term (nh_q_overlap_box_box's): a face-on hit comes a few 1e-6 early

@@ -1,6 +1,6 @@
 """nh_boxmove's state machine on the CPU (include/nudge_hip.h, "nh_boxmove"; nudge_amd/csrc/nh_query.h, "move"): the host oracle of
 tests/hostoracle/hostmover.cpp -- the NH_HD functions the kernel runs, around a brute-force box cast -- against the replay round by round
-(hostboxcast.cpp's cast, the capsule mover's begin / advance), on hand-built worlds, on every invalid-record rule, on the identities,
+(hostcast.cpp's box cast, the capsule mover's begin / advance), on hand-built worlds, on every invalid-record rule, on the identities,
 on the conditions that keep the GPU tests' batches honest, and on THE INVARIANT of test_cpu_move's random world: a box move that starts free ends no
 deeper than its skin in anything."""
 import os
@@ -13,7 +13,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import boxmove_batches as BMB               # noqa: E402
-import hostboxcast_util as HB               # noqa: E402
+import hostcast_util as CAST                 # noqa: E402
 import hostlib as H                         # noqa: E402
 import hostoverlap_util as HO               # noqa: E402
 import hostpen_util as HP                   # noqa: E402
@@ -85,7 +85,7 @@ def test_the_header_lists_the_new_observers_and_no_box_movers_as_not_built():
 
 # ---- the new oracle against the replay through the old ones -----------------------------------------------------------------------------------------
 def _replay_old(rec, nbox, m):
-    """hostboxcast.cpp's cast per round, the capsule mover's nh_q_move_advance between rounds, on the capsule records of the same moves."""
+    """hostcast.cpp's box cast per round, the capsule mover's nh_q_move_advance between rounds, on the capsule records of the same moves."""
     cm = np.zeros(len(m), dtype=E.MOVE)
     for name in ("origin", "skin", "displacement", "ignore_body", "rotation", "max_slides"):
         cm[name] = m[name]
@@ -95,7 +95,7 @@ def _replay_old(rec, nbox, m):
     while (st["stopped"] == 0).any():
         assert rounds <= E.NH_MOVE_MAX_SLIDES
         live = st["stopped"] == 0
-        hits = HB.boxcast(rec, nbox, HBM.state_casts(m, st))
+        hits = CAST.cast(CAST.BOX, rec, nbox, HBM.state_casts(m, st))
         last[live] = hits[live]
         HM.advance(cm, st, hits)
         rounds += 1
@@ -120,7 +120,7 @@ def test_the_oracle_equals_the_replay_through_the_old_oracles():
     assert not bad.any(), (int(bad.sum()), out[np.argmax(bad)], ref[np.argmax(bad)])
     assert (out["slides"] >= 1).mean() >= 0.15 and (out["slides"] >= 2).mean() >= 0.02
     # ... and the box mover's begin / advance are the capsule mover's
-    got, rounds = HBM.replay_move(m, lambda c: HB.boxcast(rec, nbox, c))
+    got, rounds = HBM.replay_move(m, lambda c: CAST.cast(CAST.BOX, rec, nbox, c))
     assert got.tobytes() == out.tobytes() and rounds >= 3
 
 
@@ -143,7 +143,7 @@ def test_free_space_floor_and_wall():
     assert first["last_hit"]["normal"].tolist() == [0.0, 1.0, 0.0] and abs(first["last_hit"]["t"] - 0.2) <= TOL and first["last_hit"]["tag"] == 100
     assert first["flags"] == E.NH_MOVE_HIT | E.NH_MOVE_SLIDES_OUT and np.abs(first["remaining"] - np.float32([0.8, 0.0, 0.0])).max() <= TOL
     # identity 1 on the oracle: with max_slides = 0, last_hit is the box cast's record
-    assert first["last_hit"].tobytes() == HB.boxcast(rec, nbox, HBM.first_casts(m))[0].tobytes()
+    assert first["last_hit"].tobytes() == CAST.cast(CAST.BOX, rec, nbox, HBM.first_casts(m))[0].tobytes()
     # head-on into the wall: stops one skin in front of it, WEDGED through the d0 rule
     for max_slides in (0, 4):
         o, made = HBM.move(rec, nbox, HBM.moves([(0.0, 3.0, 0.0)], [(3.0, 0.0, 0.0)], HALF, skin=SKIN, max_slides=max_slides), casts=True)

@@ -10,7 +10,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import boxwalk_batches as BWB               # noqa: E402
-import hostboxcast_util as HB               # noqa: E402
+import hostcast_util as CAST                 # noqa: E402
 import hostmover_util as MV                 # noqa: E402
 import hostlib as H                         # noqa: E402
 import hostoverlap_util as HO               # noqa: E402
@@ -242,14 +242,14 @@ def test_without_its_rules_a_walk_is_nh_boxmove(terrain, terrain_run):
 
 def test_the_oracle_equals_the_replay_through_the_old_oracles(terrain, terrain_run):
     """hw_walk for boxes with min_ground_up = 0 against replay_walk -- hostmover.cpp's phase-by-phase helpers -- whose move records are answered by a
-    Python loop around hostboxcast.cpp's cast and the capsule mover's begin / advance (test_cpu_boxmove) and whose cast records by that cast itself.
+    Python loop around hostcast.cpp's box cast and the capsule mover's begin / advance (test_cpu_boxmove) and whose cast records by that cast itself.
     Identity 5 on the CPU."""
     from test_cpu_boxmove import _replay_old
     rec, nbox = terrain
     w = terrain_run[0].copy()
     w["min_ground_up"] = 0.0
     out = HBW.walk(rec, nbox, w)
-    got, calls = HBW.replay_walk(w, lambda m: _replay_old(rec, nbox, m), lambda c: HB.boxcast(rec, nbox, c))
+    got, calls = HBW.replay_walk(w, lambda m: _replay_old(rec, nbox, m), lambda c: CAST.cast(CAST.BOX, rec, nbox, c))
     bad = (got.view(np.uint8).reshape(-1, 112) != out.view(np.uint8).reshape(-1, 112)).any(axis=1)
     assert not bad.any(), (int(bad.sum()), out[np.argmax(bad)], got[np.argmax(bad)])
     s = MV.shares(w, out)

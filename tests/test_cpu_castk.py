@@ -16,13 +16,13 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import castk_batches as CB                   # noqa: E402
+import hostcast_util as CAST                 # noqa: E402
 import hostcastk_util as HK                  # noqa: E402
 import hostnearest_util as N                 # noqa: E402
 import hostquery_util as Q                   # noqa: E402
-import test_cpu_castall as TA                # noqa: E402
-import test_cpu_castall_shapes as TS         # noqa: E402
+from cast_util import (HOST_WORLDS, box_casts, capsule_casts, every_kind_of_ray, far_and_near_scene as _far_and_near_scene, host_world, sphere_casts,      # noqa: E402
+                       spheres, wide_casts)
 from query_util import SMALL                 # noqa: E402
-from test_gpu_castall_shapes import _far_and_near_scene      # noqa: E402
 from nudge_amd import engine as E           # noqa: E402
 
 NONE = 0xFFFFFFFF
@@ -67,19 +67,19 @@ def test_premise_on_the_small_worlds_under_the_all_hits_tests_rays_and_balls(nam
     scene = SMALL[name]()
     rec = Q.records(scene["body_transforms"], scene)
     nbox = len(scene["box_tags"])
-    rays = TA._rays(np.random.default_rng(300 + sorted(SMALL).index(name)), 512, rec)
+    rays = every_kind_of_ray(np.random.default_rng(300 + sorted(SMALL).index(name)), 512, rec)
     _premise(rec, nbox, rays, f"{name} rays", 512)
     for radius in (0.0, -0.0, 0.05, 0.75):
-        _premise(rec, nbox, TA._casts(rays, radius), f"{name} r {radius}", 512)
+        _premise(rec, nbox, spheres(rays, radius), f"{name} r {radius}", 512)
 
 
-@pytest.mark.parametrize("name", sorted(TS.WORLDS))
+@pytest.mark.parametrize("name", sorted(HOST_WORLDS))
 def test_premise_on_the_small_worlds_under_the_all_hits_tests_boxes_and_capsules(name):
-    rec, nbox = TS._world(name)
-    rng = np.random.default_rng(500 + sorted(TS.WORLDS).index(name))
-    _premise(rec, nbox, TS.box_casts(rng, TA._rays(rng, 384, rec)), f"{name} boxes", 384)
-    rng = np.random.default_rng(510 + sorted(TS.WORLDS).index(name))
-    _premise(rec, nbox, TS.capsule_casts(rng, TA._rays(rng, 384, rec)), f"{name} capsules", 384)
+    rec, nbox = host_world(name)
+    rng = np.random.default_rng(500 + sorted(HOST_WORLDS).index(name))
+    _premise(rec, nbox, box_casts(rng, every_kind_of_ray(rng, 384, rec)), f"{name} boxes", 384)
+    rng = np.random.default_rng(510 + sorted(HOST_WORLDS).index(name))
+    _premise(rec, nbox, capsule_casts(rng, every_kind_of_ray(rng, 384, rec)), f"{name} capsules", 384)
 
 
 @pytest.mark.parametrize("name", sorted(SMALL))
@@ -124,28 +124,18 @@ def test_premise_on_downward_rays_over_a_300_unit_column_of_spheres():
     listed = _premise(rec, 0, rays, "column rays", 100000)
     # the same lines as a ball of r = 0, a box of size 0 and a capsule of r = hh = 0 (the ray-like shapes take the same pad), and with a size
     rng = np.random.default_rng(10)
-    assert _premise(rec, 0, CB.sphere_casts(rays, np.float32([0.0, -0.0]), invalid=False), "column r 0") == listed
-    assert _premise(rec, 0, TS.box_casts(rng, rays, sizes=np.float32([(0, 0, 0)]), invalid=False), "column size 0") == listed
-    assert _premise(rec, 0, TS.capsule_casts(rng, rays, shapes=np.float32([(0, 0)]), invalid=False), "column r hh 0") == listed
-    _premise(rec, 0, CB.sphere_casts(rays, np.float32([1e-3, 0.25]), invalid=False), "column balls", listed)
-    _premise(rec, 0, TS.box_casts(rng, rays, invalid=False), "column boxes", listed)
-    _premise(rec, 0, TS.capsule_casts(rng, rays, invalid=False), "column capsules", listed)
+    assert _premise(rec, 0, sphere_casts(rays, np.float32([0.0, -0.0]), invalid=False), "column r 0") == listed
+    assert _premise(rec, 0, box_casts(rng, rays, sizes=np.float32([(0, 0, 0)]), invalid=False), "column size 0") == listed
+    assert _premise(rec, 0, capsule_casts(rng, rays, shapes=np.float32([(0, 0)]), invalid=False), "column r hh 0") == listed
+    _premise(rec, 0, sphere_casts(rays, np.float32([1e-3, 0.25]), invalid=False), "column balls", listed)
+    _premise(rec, 0, box_casts(rng, rays, invalid=False), "column boxes", listed)
+    _premise(rec, 0, capsule_casts(rng, rays, invalid=False), "column capsules", listed)
 
 
 def wide_world():
     """(records, nbox) of a world of 1e-3 .. 1e4 units: half the bodies within 0.05 of the origin at size 1e-3, the others anywhere within 1e4."""
     scene = _far_and_near_scene()
     return Q.records(scene["body_transforms"], scene), len(scene["box_tags"])
-
-
-def wide_casts(rng, rec):
-    """{shape: casts} for wide_world(): rays from all over it and rays inside the small cluster, under sizes from 0 (every degenerate shape) and 1e-4
-    to 100 units."""
-    rays = np.concatenate([CB.rays(rng, 768, rec), TA._rays(rng, 256, rec[np.abs(rec["p"]).max(axis=1) < 0.1])])
-    boxes = np.float32([(0, 0, 0), (1e-4, 1e-4, 1e-4), (5.0, 0.4, 2.0), (100.0, 100.0, 100.0), (0.0, 30.0, 0.0), (-0.0, 0.0, -0.0)])
-    capsules = np.float32([(0, 0), (1e-4, 1e-4), (5.0, 0.0), (0.0, 50.0), (100.0, 25.0), (-0.0, 0.0), (1e-4, -0.0)])
-    return {"ray": rays, "sphere": CB.sphere_casts(rays, np.float32([0.0, 1e-4, 5.0, 100.0, -0.0])),
-            "box": TS.box_casts(rng, rays, sizes=boxes), "capsule": TS.capsule_casts(rng, rays, shapes=capsules)}
 
 
 def test_premise_on_a_world_spanning_a_thousandth_and_ten_thousand_units():
@@ -203,7 +193,7 @@ def test_prefix_in_k_and_k_1_is_the_closest_hit_brute_force(name):
             assert hits.tobytes() == np.ascontiguousarray(hits32[:, :k]).tobytes(), (shape, k)
             held = np.arange(k)[None, :] < counts[:, None]
             assert (hits["shape"][held] != NONE).all() and (hits["shape"][~held] == NONE).all()
-        best = HK.SHAPES[shape][2](rec, nbox, casts)
+        best = CAST.cast(CAST.SHAPES[shape], rec, nbox, casts)
         counts, hits = HK.cast_k(rec, nbox, casts, 1, seg)
         assert hits[:, 0].tobytes() == best.tobytes(), shape
         assert np.array_equal(counts, (best["shape"] != NONE).astype(np.uint32))

@@ -32,12 +32,11 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-import hostboxcast_util as HB               # noqa: E402
 import hostcapsule_util as HC               # noqa: E402
+import hostcast_util as CAST                 # noqa: E402
 import hostdistance_util as D               # noqa: E402
 import hostpoint_util as HP                 # noqa: E402
 import hostquery_util as Q                  # noqa: E402
-import hostsweep_util as HS                 # noqa: E402
 from volume_records import distance_bases, distance_lists      # noqa: E402
 from nudge_amd import engine as E           # noqa: E402
 
@@ -394,11 +393,11 @@ def test_a_cast_along_the_normal_arrives_after_the_distance(kind):
     for i in np.nonzero(d > 0)[0]:
         o, dirn = q["center"][i], -n[i]
         if qs == "sphere":
-            t, _, hit = (HS.sweep_box(o, dirn, q["size"][i, 0], r["p"][i], r["q"][i], r["h"][i]) if box[i] else
-                         HS.sweep_sphere(o, dirn, q["size"][i, 0], r["p"][i], r["h"][i, 0]))
+            t, _, hit = (CAST.sweep_box(o, dirn, q["size"][i, 0], r["p"][i], r["q"][i], r["h"][i]) if box[i] else
+                         CAST.sweep_sphere(o, dirn, q["size"][i, 0], r["p"][i], r["h"][i, 0]))
         elif qs == "box":
-            t, _, hit = (HB.sweep_box_box(o, dirn, q["rotation"][i], q["size"][i], r["p"][i], r["q"][i], r["h"][i]) if box[i] else
-                         HB.sweep_box_sphere(o, dirn, q["rotation"][i], q["size"][i], r["p"][i], r["h"][i, 0]))
+            t, _, hit = (CAST.sweep_box_box(o, dirn, q["rotation"][i], q["size"][i], r["p"][i], r["q"][i], r["h"][i]) if box[i] else
+                         CAST.sweep_box_sphere(o, dirn, q["rotation"][i], q["size"][i], r["p"][i], r["h"][i, 0]))
         else:
             t, _, hit = (HC.sweep_capsule_box(o, dirn, q["rotation"][i], q["size"][i, 0], q["size"][i, 1], r["p"][i], r["q"][i], r["h"][i]) if box[i] else
                          HC.sweep_capsule_sphere(o, dirn, q["rotation"][i], q["size"][i, 0], q["size"][i, 1], r["p"][i], r["h"][i, 0]))

@@ -10,6 +10,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import hostcapsule_util as HC               # noqa: E402
+import hostcast_util as CAST                 # noqa: E402
 import hostlib as H                         # noqa: E402
 import hostmover_util as MV                 # noqa: E402
 import hostpen_util as HP                   # noqa: E402
@@ -92,7 +93,7 @@ def test_floor():
     assert first["last_hit"]["shape"] == E.NH_SHAPE_BOX and first["last_hit"]["tag"] == 100
     assert first["flags"] == E.NH_MOVE_HIT | E.NH_MOVE_SLIDES_OUT and first["slides"] == 1
     assert np.abs(first["remaining"] - np.float32([0.8, 0.0, 0.0])).max() <= TOL and abs(first["position"][1] - (1.0 + SKIN)) <= TOL
-    assert first["last_hit"].tobytes() == HC.capsulecast(rec, nbox, HM.first_casts(m))[0].tobytes()
+    assert first["last_hit"].tobytes() == CAST.cast(CAST.CAPSULE, rec, nbox, HM.first_casts(m))[0].tobytes()
 
 
 def test_wall_head_on():
@@ -240,7 +241,7 @@ def test_advance_replays_the_oracle():
         live = st["stopped"] == 0
         if not live.any():
             break
-        hits = HC.capsulecast(rec, nbox, HM.state_casts(m, st))
+        hits = CAST.cast(CAST.CAPSULE, rec, nbox, HM.state_casts(m, st))
         last[live] = hits[live]
         HM.advance(m, st, hits)
     assert (st["stopped"] == 1).all()

@@ -11,6 +11,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import hostcast_util as CAST                 # noqa: E402
 import hostquery_util as Q                   # noqa: E402
 from query_util import unit_quats as _unit_quats      # noqa: E402
 from nudge_amd import engine as E           # noqa: E402
@@ -207,7 +208,7 @@ def _ray(o, d, max_t=np.inf, ignore=NONE):
 
 def _cast(world, o, d, **kw):
     rec, nbox = world
-    return Q.raycast(rec, nbox, _ray(o, d, **kw))[0]
+    return CAST.cast(CAST.RAY, rec, nbox, _ray(o, d, **kw))[0]
 
 
 def test_origin_inside_a_box_and_inside_a_sphere_hits_at_zero():

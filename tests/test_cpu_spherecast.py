@@ -1,5 +1,5 @@
 """Sphere casts on the host (no GPU): the nh_SphereCast record of include/nudge_hip.h against its Python mirrors, and the sweep arithmetic of
-nudge_amd/csrc/nh_query.h -- built for the host by tests/hostsweep_util.py, the same bits as the device -- against float64 closed forms, the named
+nudge_amd/csrc/nh_query.h -- built for the host by tests/hostcast_util.py, the same bits as the device -- against float64 closed forms, the named
 cases of its exact semantics, the ray predicates at radius 0 and the overlap predicates at t = 0."""
 import ctypes
 import os
@@ -10,10 +10,11 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import hostcast_util as CAST                 # noqa: E402
 import hostoverlap_util as O                 # noqa: E402
 import hostquery_util as Q                   # noqa: E402
-import hostsweep_util as W                   # noqa: E402
-from query_util import unit_quats as _unit_quats      # noqa: E402
+from cast_util import ball64 as _ball64, sweep_box64 as _sweep_box64      # noqa: E402
+from query_util import mat as _mat, unit_quats as _unit_quats      # noqa: E402
 from nudge_amd import engine as E           # noqa: E402
 from nudge_amd import scenes as S           # noqa: E402
 
@@ -40,61 +41,6 @@ def test_sphere_cast_record_matches_the_header(tmp_path):
 
 
 # ---- float64 closed forms ----------------------------------------------------------------------------------------------------------------
-def _mat(q):
-    x, y, z, s = (float(v) for v in q)
-    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - s * z), 2 * (x * z + s * y)],
-                     [2 * (x * y + s * z), 1 - 2 * (x * x + z * z), 2 * (y * z - s * x)],
-                     [2 * (x * z - s * y), 2 * (y * z + s * x), 1 - 2 * (x * x + y * y)]])
-
-
-def _ball64(o, d, c, r):
-    """First t >= 0 of the ray in the ball (c, r), or inf."""
-    m = o - c
-    a, b, cc = d @ d, m @ d, m @ m - r * r
-    disc = b * b - a * cc
-    if disc < 0:
-        return np.inf
-    t = (-b - np.sqrt(disc)) / a
-    return t if t >= 0 else np.inf
-
-
-def _sweep_box64(o, d, r, p, R, h):
-    """(hit, t, normal, feature) of the first touch of the ball (o + t d, r) with the box, in float64: the least over the 6 faces pushed out by r, the
-    12 edge cylinders and the 8 corner balls.  feature: 'start', 'face', 'edge' or 'corner'."""
-    ol, dl = R.T @ (o - p), R.T @ d
-    if np.sum(np.maximum(np.abs(ol) - h, 0.0) ** 2) <= r * r:
-        return True, 0.0, -d / np.linalg.norm(d), "start"
-    best, feat = np.inf, None
-    for k in range(3):
-        i, j = (k + 1) % 3, (k + 2) % 3
-        for s in (-1.0, 1.0):
-            if dl[k] != 0.0:
-                t = (s * (h[k] + r) - ol[k]) / dl[k]
-                x = ol + t * dl
-                if t >= 0 and abs(x[i]) <= h[i] and abs(x[j]) <= h[j] and t < best:
-                    best, feat = t, "face"
-        for si in (-1.0, 1.0):
-            for sj in (-1.0, 1.0):
-                m = np.array([ol[i] - si * h[i], ol[j] - sj * h[j]])
-                dd = np.array([dl[i], dl[j]])
-                a, b, cc = dd @ dd, m @ dd, m @ m - r * r
-                if a > 0 and b * b - a * cc >= 0:
-                    t = (-b - np.sqrt(b * b - a * cc)) / a
-                    if t >= 0 and abs(ol[k] + t * dl[k]) <= h[k] and t < best:
-                        best, feat = t, "edge"
-    for sx in (-1.0, 1.0):
-        for sy in (-1.0, 1.0):
-            for sz in (-1.0, 1.0):
-                t = _ball64(ol, dl, np.array([sx, sy, sz]) * h, r)
-                if t < best:
-                    best, feat = t, "corner"
-    if feat is None:
-        return False, 0.0, None, None
-    x = ol + best * dl
-    v = x - np.clip(x, -h, h)
-    return True, best, R @ (v / np.linalg.norm(v)), feat
-
-
 def _casts_at(rng, n, centres):
     o = rng.uniform(-10.0, 10.0, size=(n, 3)).astype(np.float32)
     aim = centres + rng.normal(scale=1.5, size=(n, 3))
@@ -131,7 +77,7 @@ def test_box_and_sphere_sweeps_against_float64_closed_forms():
             continue
         if ref[0] and max(abs(lo[1] - ref[1]), abs(hi[1] - ref[1])) > 1e-3 * max(ref[1], 1.0):
             continue            # (a grazing touch: t rests on a near-zero discriminant)
-        t, nn, hit = W.sweep_box(o[i], d[i], r[i], ctr[i], q[i], h[i])
+        t, nn, hit = CAST.sweep_box(o[i], d[i], r[i], ctr[i], q[i], h[i])
         compared += 1
         assert hit == ref[0], (i, hit, ref)
         if hit:
@@ -151,7 +97,7 @@ def test_box_and_sphere_sweeps_against_float64_closed_forms():
         edge = [_ball64(o64, d64, c64, rho * (1 + s)) for s in (-EDGE, EDGE)]
         if not ((ref_t < np.inf) == (edge[0] < np.inf) == (edge[1] < np.inf)) or (ref_t < np.inf and abs(edge[0] - edge[1]) > 1e-3 * max(ref_t, 1)):
             continue
-        t, nn, hit = W.sweep_sphere(o[i], d[i], r[i], ctr[i], R_[i])
+        t, nn, hit = CAST.sweep_sphere(o[i], d[i], r[i], ctr[i], R_[i])
         compared += 1
         assert hit == (ref_t < np.inf), i
         if hit:
@@ -177,9 +123,9 @@ def test_radius_zero_is_the_ray_predicate_bit_for_bit():
     hits = 0
     for i in range(n):
         for r0 in (0.0, -0.0):
-            a, b = W.sweep_box(o[i], d[i], r0, ctr[i], q[i], h[i]), Q.ray_box(o[i], d[i], ctr[i], q[i], h[i])
+            a, b = CAST.sweep_box(o[i], d[i], r0, ctr[i], q[i], h[i]), Q.ray_box(o[i], d[i], ctr[i], q[i], h[i])
             assert a[2] == b[2] and np.float32(a[0]).tobytes() == np.float32(b[0]).tobytes() and a[1].tobytes() == b[1].tobytes(), i
-            a, b = W.sweep_sphere(o[i], d[i], r0, ctr[i], h[i, 0]), Q.ray_sphere(o[i], d[i], ctr[i], h[i, 0])
+            a, b = CAST.sweep_sphere(o[i], d[i], r0, ctr[i], h[i, 0]), Q.ray_sphere(o[i], d[i], ctr[i], h[i, 0])
             assert a[2] == b[2] and np.float32(a[0]).tobytes() == np.float32(b[0]).tobytes() and a[1].tobytes() == b[1].tobytes(), i
             hits += a[2]
     assert hits > 0.2 * n
@@ -192,7 +138,7 @@ def test_radius_zero_is_the_ray_predicate_bit_for_bit():
     casts = np.zeros(n, dtype=E.SPHERE_CAST)
     for k in ("origin", "direction", "max_t", "ignore_body"):
         casts[k] = rays[k]
-    assert W.spherecast(rec, nbox, casts).tobytes() == Q.raycast(rec, nbox, rays).tobytes()
+    assert CAST.cast(CAST.SPHERE, rec, nbox, casts).tobytes() == CAST.cast(CAST.RAY, rec, nbox, rays).tobytes()
 
 
 def test_a_start_overlap_under_the_overlap_predicates_hits_at_zero():
@@ -209,11 +155,11 @@ def test_a_start_overlap_under_the_overlap_predicates_hits_at_zero():
         inside = -d[i] / np.float32(np.sqrt(np.float32(d[i] @ d[i])))
         if O.sphere_box(o[i], r[i], ctr[i], q[i], h[i]):
             boxes += 1
-            t, nn, hit = W.sweep_box(o[i], d[i], r[i], ctr[i], q[i], h[i])
+            t, nn, hit = CAST.sweep_box(o[i], d[i], r[i], ctr[i], q[i], h[i])
             assert hit and t == 0.0 and np.allclose(nn, inside, atol=1e-6), i
         if O.sphere_sphere(o[i], r[i], ctr[i], h[i, 0]):
             spheres += 1
-            t, nn, hit = W.sweep_sphere(o[i], d[i], r[i], ctr[i], h[i, 0])
+            t, nn, hit = CAST.sweep_sphere(o[i], d[i], r[i], ctr[i], h[i, 0])
             assert hit and t == 0.0 and np.allclose(nn, inside, atol=1e-6), i
     assert boxes > 300 and spheres > 300, (boxes, spheres)
 
@@ -243,7 +189,7 @@ def _cast(world, o, d, r, max_t=np.inf, ignore=NONE):
     rec, nbox = world
     c = np.zeros(1, dtype=E.SPHERE_CAST)
     c["origin"], c["direction"], c["radius"], c["max_t"], c["ignore_body"] = o, d, r, max_t, ignore
-    return W.spherecast(rec, nbox, c)[0]
+    return CAST.cast(CAST.SPHERE, rec, nbox, c)[0]
 
 
 def test_head_on_edge_and_corner_hits():

@@ -10,6 +10,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import hostcapsule_util as HC               # noqa: E402
+import hostcast_util as CAST                 # noqa: E402
 import hostlib as H                         # noqa: E402
 import hostmover_util as MV                 # noqa: E402
 import hostpen_util as HP                   # noqa: E402
@@ -288,7 +289,7 @@ def test_replay_phase_by_phase(terrain, terrain_run):
     w = terrain_run[0].copy()
     w["min_ground_up"] = 0.0
     out = HW.walk(rec, nbox, w)
-    got, calls = HW.replay_walk(w, lambda m: HW.move(rec, nbox, m), lambda c: HC.capsulecast(rec, nbox, c))
+    got, calls = HW.replay_walk(w, lambda m: HW.move(rec, nbox, m), lambda c: CAST.cast(CAST.CAPSULE, rec, nbox, c))
     bad = (got.view(np.uint8).reshape(-1, 112) != out.view(np.uint8).reshape(-1, 112)).any(axis=1)
     assert not bad.any(), (int(bad.sum()), out[np.argmax(bad)], got[np.argmax(bad)])
     s = MV.shares(w, out)

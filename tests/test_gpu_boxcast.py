@@ -1,6 +1,6 @@
 """Box casts on the GPU (pytest -m gpu): nh_boxcast (include/nudge_hip.h, "scene queries").
 
-The oracle is a brute force over every collider on the host with the same arithmetic (nudge_amd/csrc/nh_query.h through tests/hostboxcast_util.py)
+The oracle is a brute force over every collider on the host with the same arithmetic (nudge_amd/csrc/nh_query.h through tests/hostcast_util.py)
 and the header's exact rules, so the tree's answer must equal it bit for bit in every field.  Size 0 must give nh_raycast's bytes, a start box that
 nh_overlap finds touching something must hit at t = 0, and casts are observers like the other queries."""
 import ctypes as C
@@ -11,42 +11,17 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import hostboxcast_util as B                 # noqa: E402
+import hostcast_util as CAST                 # noqa: E402
 import hostquery_util as Q                   # noqa: E402
-from query_util import unit_quats as _unit_quats      # noqa: E402
-from test_gpu_query import OBSERVED, SMALL, _bounds, _rays, _same_stepped_world, _upload      # noqa: E402
+from cast_util import boxes as _casts, closest as _sweep, degenerate_worlds, same_hits as _same_hits, slide_past      # noqa: E402
+from query_util import (FUSED, NONE, OBSERVED, SMALL, bounds as _bounds, mat, rays as _rays, same_stepped_world as _same_stepped_world,      # noqa: E402
+                        unit_quats as _unit_quats, upload as _upload)
 from nudge_amd import engine as E           # noqa: E402
 from nudge_amd import scenes as S           # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-NONE = 0xFFFFFFFF
-FUSED = E.NH_FLAG_SINGLE_APPLY | E.NH_FLAG_FUSED_STEP
 SIZES = (0.05, 0.5, 2.0)
-
-
-def _casts(rays, size, rotation=None):
-    """nh_BoxCast records from rays: half extents `size` (a number, n values or (n, 3)), `rotation` (n, 4) or identity."""
-    c = np.zeros(len(rays), dtype=E.BOX_CAST)
-    for k in ("origin", "max_t", "direction", "ignore_body"):
-        c[k] = rays[k]
-    size = np.asarray(size, dtype=np.float32)
-    c["size"] = size.reshape(-1, 1) if size.ndim == 1 else size
-    if rotation is None:
-        c["rotation"][:, 3] = 1.0
-    else:
-        c["rotation"] = rotation
-    return c
-
-
-def _sweep(w, casts, any_hit=False):
-    raw = w.boxcast_records(_upload(w, casts), any_hit=any_hit)
-    return np.frombuffer(raw.cpu().numpy().tobytes(), dtype=E.RAY_HIT).copy()
-
-
-def _same_hits(got, ref, what):
-    bad = (got.view(np.uint8).reshape(-1, 32) != ref.view(np.uint8).reshape(-1, 32)).any(axis=1)
-    assert not bad.any(), f"{what}: {int(bad.sum())} of {len(ref)} hit records differ, first at {int(np.argmax(bad))}"
 
 
 def _check_world(w, scene, rng, n, what, sizes=SIZES):
@@ -58,7 +33,7 @@ def _check_world(w, scene, rng, n, what, sizes=SIZES):
         for h in sizes:
             for rot in (None, _unit_quats(rng, n)):
                 casts = _casts(_rays(rng, n, lo, hi, kind), h, rot)
-                ref = B.boxcast(rec, w.nbox, casts)
+                ref = CAST.cast(CAST.BOX, rec, w.nbox, casts)
                 _same_hits(_sweep(w, casts), ref, f"{what} / {kind} / size {h} / {'identity' if rot is None else 'rotated'}")
                 share.append(float((ref["shape"] != NONE).mean()))
     return share
@@ -76,27 +51,7 @@ def test_box_casts_equal_the_brute_force_before_and_after_stepping(name):
 
 
 def test_degenerate_worlds():
-    scene = S.pile(4, 0, seed=3)
-    w = E.World(scene, flags=FUSED)
-    w.set_counts(len(scene["body_transforms"]), 1, 0)          # the ground slab alone (body 0)
-    rng = np.random.default_rng(31)
-    _check_world(w, scene, rng, 4096, "one collider")
-    w.close()
-
-    scene = S.pile(300, 300, seed=3)
-    nb = len(scene["body_transforms"])
-    w = E.World(scene, flags=FUSED)
-    w.set_counts(nb, 0, 300)
-    _check_world(w, scene, rng, 4096, "spheres only")
-    w.set_counts(nb, 301, 0)
-    _check_world(w, scene, rng, 4096, "boxes only")
-    w.close()
-
-    scene = S.pile(4096, 0, seed=3)
-    scene["body_transforms"]["position"][1:] = (0.25, 3.0, -0.5)        # every Morton key equal but the ground's
-    w = E.World(scene, flags=FUSED)
-    _check_world(w, scene, rng, 2048, "4096 coincident boxes")
-    w.close()
+    degenerate_worlds(_check_world, np.random.default_rng(31), 4096, 4096, 2048)
 
 
 def test_grazing_casts_beside_resting_boxes():
@@ -111,11 +66,6 @@ def test_grazing_casts_beside_resting_boxes():
     offs = [0.0] + [s * 10.0 ** e for e in range(-8, -1) for s in (-1.0, 1.0)]
     rng = np.random.default_rng(32)
 
-    def mat(q):
-        x, y, z, s = (float(v) for v in q)
-        return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - s * z), 2 * (x * z + s * y)], [2 * (x * y + s * z), 1 - 2 * (x * x + z * z), 2 * (y * z - s * x)],
-                         [2 * (x * z - s * y), 2 * (y * z + s * x), 1 - 2 * (x * x + y * y)]])
-
     casts = []
     for k, c in enumerate(boxes):
         p, q, h = rec["p"][c].astype(np.float64), rec["q"][c], rec["h"][c].astype(np.float64)
@@ -128,9 +78,7 @@ def test_grazing_casts_beside_resting_boxes():
                 for off in offs:
                     a, b = k % 3, (k + 1) % 3                      # slide along axis a past the face of axis b
                     for sb in (-1.0, 1.0):
-                        ol, dl = np.zeros(3), np.zeros(3)
-                        ol[a], ol[b], dl[a] = -(h[a] + ext[a] + 2.0), sb * (h[b] + ext[b] + off), 1.0
-                        casts.append((p + R @ ol, R @ dl, qc, hc))
+                        casts.append((*slide_past(p, R, h, ext, a, b, sb, off), qc, hc))
     c = np.zeros(len(casts), dtype=E.BOX_CAST)
     c["origin"] = [o for o, _, _, _ in casts]
     c["direction"] = [d for _, d, _, _ in casts]
@@ -138,7 +86,7 @@ def test_grazing_casts_beside_resting_boxes():
     c["size"] = [h for _, _, _, h in casts]
     c["max_t"] = np.inf
     c["ignore_body"] = NONE
-    ref = B.boxcast(rec, w.nbox, c)
+    ref = CAST.cast(CAST.BOX, rec, w.nbox, c)
     _same_hits(_sweep(w, c), ref, "grazing")
     assert (ref["shape"] != NONE).mean() > 0.1
     w.close()
@@ -157,8 +105,7 @@ def test_size_zero_equals_the_ray_cast(name):
         rays = _rays(rng, 32768, lo, hi, kind)
         rays["max_t"][::3] = 7.0
         rays["ignore_body"][::5] = rng.integers(0, 64, size=len(rays[::5]))
-        raw = w.raycast_records(_upload(w, rays))
-        ray_hits = np.frombuffer(raw.cpu().numpy().tobytes(), dtype=E.RAY_HIT)
+        ray_hits = _sweep(w, rays)
         rot = _unit_quats(rng, len(rays))
         rot[::2] = np.nan                                       # (size 0 does not read the rotation)
         _same_hits(_sweep(w, _casts(rays, 0.0, rot)), ray_hits, f"{name} / {kind}: size 0 against nh_raycast")
@@ -191,7 +138,7 @@ def test_a_start_box_that_overlaps_hits_at_zero(name):
     lowest = ov["collider"].cpu().numpy()[first] + np.where(ov["shape"].cpu().numpy()[first] == E.NH_SHAPE_SPHERE, w.nbox, 0)
     mine = got["collider"][touching].astype(np.int64) + np.where(got["shape"][touching] == E.NH_SHAPE_SPHERE, w.nbox, 0)
     assert (mine <= lowest).all()
-    _same_hits(got, B.boxcast(rec, w.nbox, casts), f"{name} start boxes")
+    _same_hits(got, CAST.cast(CAST.BOX, rec, w.nbox, casts), f"{name} start boxes")
     w.close()
 
 
@@ -217,7 +164,7 @@ def test_any_hit_agrees_with_closest_hit_about_hit_or_miss(name):
         assert (anyh["t"][idx] <= casts["max_t"][idx]).all()
         for i in idx[:: max(1, len(idx) // 500)]:
             c = int(anyh["collider"][i]) + (0 if anyh["shape"][i] == E.NH_SHAPE_BOX else w.nbox)
-            one = B.boxcast(rec, w.nbox, casts[i:i + 1], only=c)[0]
+            one = CAST.cast(CAST.BOX, rec, w.nbox, casts[i:i + 1], only=c)[0]
             assert one.tobytes() == anyh[i].tobytes(), (kind, i)
     w.close()
 
@@ -263,13 +210,13 @@ def test_the_python_wrapper_writes_the_records_it_describes():
     rays["ignore_body"][::3] = 2
     out = w.boxcast(rays["origin"], rays["direction"], size, rot, max_t=40.0, ignore_body=rays["ignore_body"].astype(np.int64), synchronize=True)
     rays["max_t"] = 40.0
-    ref = B.boxcast(rec, w.nbox, _casts(rays, size, rot))
+    ref = CAST.cast(CAST.BOX, rec, w.nbox, _casts(rays, size, rot))
     _same_hits(np.frombuffer(out["raw"].cpu().numpy().tobytes(), dtype=E.RAY_HIT), ref, "World.boxcast")
     assert np.array_equal(out["collider"].cpu().numpy(), ref["collider"].astype(np.int64))
     out = w.boxcast(rays["origin"], rays["direction"], (0.5, 0.5, 0.5), synchronize=True)        # rotations=None: identity
     rays["max_t"] = np.inf
     rays["ignore_body"] = NONE
-    _same_hits(np.frombuffer(out["raw"].cpu().numpy().tobytes(), dtype=E.RAY_HIT), B.boxcast(rec, w.nbox, _casts(rays, 0.5)), "World.boxcast, identity")
+    _same_hits(np.frombuffer(out["raw"].cpu().numpy().tobytes(), dtype=E.RAY_HIT), CAST.cast(CAST.BOX, rec, w.nbox, _casts(rays, 0.5)), "World.boxcast, identity")
     w.close()
 
 
@@ -358,5 +305,5 @@ def test_a_million_box_casts_on_the_landed_config_2_world():
     assert (~slab).mean() > 0.2
     # 1024 casts spread over the batch, bit for bit against the brute force over all 1,004,524 colliders
     pick = np.linspace(0, n - 1, 1024).astype(np.int64)
-    _same_hits(got[pick], B.boxcast(rec, w.nbox, casts[pick]), "config 2, 1 M box casts")
+    _same_hits(got[pick], CAST.cast(CAST.BOX, rec, w.nbox, casts[pick]), "config 2, 1 M box casts")
     w.close()

@@ -16,9 +16,8 @@ import hostmover_util as MV                  # noqa: E402
 import hostquery_util as Q                   # noqa: E402
 from hostmover_util import BOX as HBM, CAPSULE as HM      # noqa: E402
 from mover_util import FUSED, NONE, SENTINEL, boxcast as _boxcast, boxmove as _boxmove, records as _records, same as _same      # noqa: E402
-from query_util import unit_quats            # noqa: E402
 from test_cpu_boxmove import BATCH_SEED, DRAW      # noqa: E402
-from test_gpu_query import OBSERVED, SMALL, _same_stepped_world, _upload      # noqa: E402
+from query_util import OBSERVED, SMALL, same_stepped_world as _same_stepped_world, unit_quats, upload as _upload      # noqa: E402
 from nudge_amd import engine as E           # noqa: E402
 from nudge_amd import scenes as S           # noqa: E402
 

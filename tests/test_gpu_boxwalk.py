@@ -20,7 +20,7 @@ from mover_util import (FUSED, NONE, SENTINEL, boxcast as _boxcast, boxmove as _
                         same as _same, terrain_world as _terrain_world)
 from test_cpu_boxwalk import TERRAIN_SEED, WORLD_SEED      # noqa: E402
 from test_cpu_walk import BALL_PIT_SHARES, RESTING, TERRAIN_SHARES, WORLD_SHARES, check_shares      # noqa: E402
-from test_gpu_query import OBSERVED, SMALL, _same_stepped_world, _upload      # noqa: E402
+from query_util import OBSERVED, SMALL, same_stepped_world as _same_stepped_world, upload as _upload      # noqa: E402
 from nudge_amd import engine as E           # noqa: E402
 from nudge_amd import scenes as S           # noqa: E402
 

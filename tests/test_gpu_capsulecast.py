@@ -1,7 +1,7 @@
 """Capsule casts and capsule overlaps on the GPU (pytest -m gpu): nh_capsulecast and nh_overlap's NH_SHAPE_CAPSULE (include/nudge_hip.h, "scene
 queries").
 
-The oracle is a brute force over every collider on the host with the same arithmetic (nudge_amd/csrc/nh_query.h through tests/hostcapsule_util.py)
+The oracle is a brute force over every collider on the host with the same arithmetic (nudge_amd/csrc/nh_query.h through tests/hostcast_util.py and tests/hostcapsule_util.py)
 and the header's exact rules, so the tree's answer must equal it bit for bit in every field.  Half height 0 must give nh_spherecast's bytes (and with
 radius 0 nh_raycast's), the sphere and box queries of a mixed overlap batch must not notice the capsules beside them, and casts and capsule overlaps
 are observers like the other queries."""
@@ -14,43 +14,19 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import hostcapsule_util as H                 # noqa: E402
+import hostcast_util as CAST                 # noqa: E402
 import hostoverlap_util as O                 # noqa: E402
 import hostquery_util as Q                   # noqa: E402
-from query_util import unit_quats as _unit_quats      # noqa: E402
-from test_gpu_overlap import SENTINEL, _gpu, _queries                                       # noqa: E402
-from test_gpu_query import OBSERVED, SMALL, _bounds, _rays, _same_stepped_world, _upload      # noqa: E402
+from cast_util import capsules as _casts, closest as _sweep, degenerate_worlds, same_hits as _same_hits, slide_past, spheres      # noqa: E402
+from query_util import (FUSED, NONE, OBSERVED, SMALL, bounds as _bounds, mat, rays as _rays, same_stepped_world as _same_stepped_world,      # noqa: E402
+                        unit_quats as _unit_quats, upload as _upload)
+from test_gpu_overlap import SENTINEL, _capsule_queries, _gpu, _queries                                       # noqa: E402
 from nudge_amd import engine as E           # noqa: E402
 from nudge_amd import scenes as S           # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-NONE = 0xFFFFFFFF
-FUSED = E.NH_FLAG_SINGLE_APPLY | E.NH_FLAG_FUSED_STEP
 SHAPES = ((0.05, 0.5), (0.5, 0.5), (1.0, 2.0), (0.0, 1.0))         # (radius, half height)
-
-
-def _casts(rays, radius, half_height, rotation=None):
-    """nh_CapsuleCast records from rays: `radius` / `half_height` numbers or n values, `rotation` (n, 4) or identity."""
-    c = np.zeros(len(rays), dtype=E.CAPSULE_CAST)
-    for k in ("origin", "max_t", "direction", "ignore_body"):
-        c[k] = rays[k]
-    c["radius"] = radius
-    c["half_height"] = half_height
-    if rotation is None:
-        c["rotation"][:, 3] = 1.0
-    else:
-        c["rotation"] = rotation
-    return c
-
-
-def _sweep(w, casts, any_hit=False):
-    raw = w.capsulecast_records(_upload(w, casts), any_hit=any_hit)
-    return np.frombuffer(raw.cpu().numpy().tobytes(), dtype=E.RAY_HIT).copy()
-
-
-def _same_hits(got, ref, what):
-    bad = (got.view(np.uint8).reshape(-1, 32) != ref.view(np.uint8).reshape(-1, 32)).any(axis=1)
-    assert not bad.any(), f"{what}: {int(bad.sum())} of {len(ref)} hit records differ, first at {int(np.argmax(bad))}"
 
 
 def _check_world(w, scene, rng, n, what, shapes=SHAPES):
@@ -62,7 +38,7 @@ def _check_world(w, scene, rng, n, what, shapes=SHAPES):
         for r, hh in shapes:
             for rot in (None, _unit_quats(rng, n)):
                 casts = _casts(_rays(rng, n, lo, hi, kind), r, hh, rot)
-                ref = H.capsulecast(rec, w.nbox, casts)
+                ref = CAST.cast(CAST.CAPSULE, rec, w.nbox, casts)
                 _same_hits(_sweep(w, casts), ref, f"{what} / {kind} / r {r} hh {hh} / {'identity' if rot is None else 'rotated'}")
                 share.append(float((ref["shape"] != NONE).mean()))
     return share
@@ -80,27 +56,7 @@ def test_capsule_casts_equal_the_brute_force_before_and_after_stepping(name):
 
 
 def test_degenerate_worlds():
-    scene = S.pile(4, 0, seed=3)
-    w = E.World(scene, flags=FUSED)
-    w.set_counts(len(scene["body_transforms"]), 1, 0)          # the ground slab alone (body 0)
-    rng = np.random.default_rng(41)
-    _check_world(w, scene, rng, 2048, "one collider")
-    w.close()
-
-    scene = S.pile(300, 300, seed=3)
-    nb = len(scene["body_transforms"])
-    w = E.World(scene, flags=FUSED)
-    w.set_counts(nb, 0, 300)
-    _check_world(w, scene, rng, 2048, "spheres only")
-    w.set_counts(nb, 301, 0)
-    _check_world(w, scene, rng, 2048, "boxes only")
-    w.close()
-
-    scene = S.pile(4096, 0, seed=3)
-    scene["body_transforms"]["position"][1:] = (0.25, 3.0, -0.5)        # every Morton key equal but the ground's
-    w = E.World(scene, flags=FUSED)
-    _check_world(w, scene, rng, 1024, "4096 coincident boxes", shapes=((0.5, 0.5),))
-    w.close()
+    degenerate_worlds(_check_world, np.random.default_rng(41), 2048, 2048, 1024, shapes=((0.5, 0.5),))
 
 
 def test_mixed_radii_half_heights_rotations_ignore_body_and_max_t():
@@ -125,7 +81,7 @@ def test_mixed_radii_half_heights_rotations_ignore_body_and_max_t():
     casts["rotation"][bad[32:48], 1] = np.inf
     casts["half_height"][bad[32:48]] = 1.0
     casts["origin"][bad[48:], 2] = np.nan
-    ref = H.capsulecast(rec, w.nbox, casts)
+    ref = CAST.cast(CAST.CAPSULE, rec, w.nbox, casts)
     assert np.isnan(ref["t"][bad]).all()
     _same_hits(_sweep(w, casts), ref, "mixed")
     assert (ref["shape"] != NONE).mean() > 0.2
@@ -144,11 +100,6 @@ def test_grazing_casts_beside_resting_boxes():
     offs = [0.0] + [s * 10.0 ** e for e in range(-8, -1) for s in (-1.0, 1.0)]
     rng = np.random.default_rng(43)
 
-    def mat(q):
-        x, y, z, s = (float(v) for v in q)
-        return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - s * z), 2 * (x * z + s * y)], [2 * (x * y + s * z), 1 - 2 * (x * x + z * z), 2 * (y * z - s * x)],
-                         [2 * (x * z - s * y), 2 * (y * z + s * x), 1 - 2 * (x * x + y * y)]])
-
     rows = []
     for k, c in enumerate(boxes):
         p, q, h = rec["p"][c].astype(np.float64), rec["q"][c], rec["h"][c].astype(np.float64)
@@ -160,9 +111,7 @@ def test_grazing_casts_beside_resting_boxes():
                 for off in offs:
                     a, b = k % 3, (k + 1) % 3
                     for sb in (-1.0, 1.0):
-                        ol, dl = np.zeros(3), np.zeros(3)
-                        ol[a], ol[b], dl[a] = -(h[a] + ext[a] + 2.0), sb * (h[b] + ext[b] + off), 1.0
-                        rows.append((p + R @ ol, R @ dl, qc, r, hh))
+                        rows.append((*slide_past(p, R, h, ext, a, b, sb, off), qc, r, hh))
     c = np.zeros(len(rows), dtype=E.CAPSULE_CAST)
     c["origin"] = [x[0] for x in rows]
     c["direction"] = [x[1] for x in rows]
@@ -171,7 +120,7 @@ def test_grazing_casts_beside_resting_boxes():
     c["half_height"] = [x[4] for x in rows]
     c["max_t"] = np.inf
     c["ignore_body"] = NONE
-    ref = H.capsulecast(rec, w.nbox, c)
+    ref = CAST.cast(CAST.CAPSULE, rec, w.nbox, c)
     _same_hits(_sweep(w, c), ref, "grazing")
     assert (ref["shape"] != NONE).mean() > 0.1
     w.close()
@@ -193,17 +142,9 @@ def test_half_height_zero_equals_the_sphere_cast_and_the_ray_cast(name):
         rot = _unit_quats(rng, len(rays))
         rot[::2] = np.nan
         radius = rng.choice(np.float32([0.0, 0.3, 1.2]), size=len(rays))
-        sph = np.zeros(len(rays), dtype=E.SPHERE_CAST)
-        for k in ("origin", "max_t", "direction", "ignore_body"):
-            sph[k] = rays[k]
-        sph["radius"] = radius
-        raw = w.spherecast_records(_upload(w, sph))
-        sph_hits = np.frombuffer(raw.cpu().numpy().tobytes(), dtype=E.RAY_HIT)
         got = _sweep(w, _casts(rays, radius, 0.0, rot))
-        _same_hits(got, sph_hits, f"{name} / {kind}: hh 0 against nh_spherecast")
-        raw = w.raycast_records(_upload(w, rays))
-        ray_hits = np.frombuffer(raw.cpu().numpy().tobytes(), dtype=E.RAY_HIT)
-        _same_hits(_sweep(w, _casts(rays, 0.0, 0.0, rot)), ray_hits, f"{name} / {kind}: r = hh = 0 against nh_raycast")
+        _same_hits(got, _sweep(w, spheres(rays, radius)), f"{name} / {kind}: hh 0 against nh_spherecast")
+        _same_hits(_sweep(w, _casts(rays, 0.0, 0.0, rot)), _sweep(w, rays), f"{name} / {kind}: r = hh = 0 against nh_raycast")
     w.close()
 
 
@@ -234,7 +175,7 @@ def test_a_start_capsule_that_overlaps_hits_at_zero(name):
     lowest = ov["collider"].cpu().numpy()[first] + np.where(ov["shape"].cpu().numpy()[first] == E.NH_SHAPE_SPHERE, w.nbox, 0)
     mine = got["collider"][touching].astype(np.int64) + np.where(got["shape"][touching] == E.NH_SHAPE_SPHERE, w.nbox, 0)
     assert (mine <= lowest).all()
-    _same_hits(got, H.capsulecast(rec, w.nbox, casts), f"{name} start capsules")
+    _same_hits(got, CAST.cast(CAST.CAPSULE, rec, w.nbox, casts), f"{name} start capsules")
     w.close()
 
 
@@ -260,7 +201,7 @@ def test_any_hit_agrees_with_closest_hit_about_hit_or_miss(name):
         assert (anyh["t"][idx] <= casts["max_t"][idx]).all()
         for i in idx[:: max(1, len(idx) // 300)]:
             c = int(anyh["collider"][i]) + (0 if anyh["shape"][i] == E.NH_SHAPE_BOX else w.nbox)
-            one = H.capsulecast(rec, w.nbox, casts[i:i + 1], only=c)[0]
+            one = CAST.cast(CAST.CAPSULE, rec, w.nbox, casts[i:i + 1], only=c)[0]
             assert one.tobytes() == anyh[i].tobytes(), (kind, i)
     w.close()
 
@@ -307,13 +248,13 @@ def test_the_python_wrappers_write_the_records_they_describe():
     rays["ignore_body"][::3] = 2
     out = w.capsulecast(rays["origin"], rays["direction"], r, hh, rot, max_t=40.0, ignore_body=rays["ignore_body"].astype(np.int64), synchronize=True)
     rays["max_t"] = 40.0
-    ref = H.capsulecast(rec, w.nbox, _casts(rays, r, hh, rot))
+    ref = CAST.cast(CAST.CAPSULE, rec, w.nbox, _casts(rays, r, hh, rot))
     _same_hits(np.frombuffer(out["raw"].cpu().numpy().tobytes(), dtype=E.RAY_HIT), ref, "World.capsulecast")
     assert np.array_equal(out["collider"].cpu().numpy(), ref["collider"].astype(np.int64))
     out = w.capsulecast(rays["origin"], rays["direction"], 0.5, 1.0, synchronize=True)        # rotations=None: upright
     rays["max_t"] = np.inf
     rays["ignore_body"] = NONE
-    _same_hits(np.frombuffer(out["raw"].cpu().numpy().tobytes(), dtype=E.RAY_HIT), H.capsulecast(rec, w.nbox, _casts(rays, 0.5, 1.0)), "upright")
+    _same_hits(np.frombuffer(out["raw"].cpu().numpy().tobytes(), dtype=E.RAY_HIT), CAST.cast(CAST.CAPSULE, rec, w.nbox, _casts(rays, 0.5, 1.0)), "upright")
     # World.overlap with half_heights: a capsule batch
     cen = rays["origin"][:512]
     ov = w.overlap(cen, radii=r[:512], half_heights=hh[:512], rotations=rot[:512], synchronize=True)
@@ -327,32 +268,6 @@ def test_the_python_wrappers_write_the_records_they_describe():
 
 
 # ---- capsule overlaps ------------------------------------------------------------------------------------------------------------------------
-def _capsule_queries(rng, n, rec, scale=1.0):
-    """Capsule queries around the scene: half on a collider, radii and half heights from 0, random rotations, some ignore_body and invalid ones."""
-    q = _queries(rng, n, rec, "sphere", scale)
-    q["shape"] = E.NH_SHAPE_CAPSULE
-    q["size"][:, 0] = rng.uniform(0.0, 1.2 * scale, size=n)
-    q["size"][:, 1] = rng.choice([0.0, 0.3, 1.0, 2.5], size=n) * scale
-    q["size"][:, 2] = np.nan                                           # (not read)
-    q["rotation"] = _unit_quats(rng, n)
-    q["rotation"][(q["size"][:, 1] == 0.0) & (rng.random(n) < 0.5)] = np.nan     # (not read at half height 0)
-    live = np.nonzero(np.isfinite(rec["p"]).all(axis=1))[0]
-    ign = rng.random(n) < 0.2
-    q["ignore_body"][ign] = rec["body"][rng.choice(live, size=int(ign.sum()))]
-    bad = rng.choice(n, size=max(1, n // 64), replace=False)
-    for j, b in enumerate(bad):
-        k = j % 4
-        if k == 0:
-            q["size"][b, 1] = -0.5
-        elif k == 1:
-            q["size"][b, 1] = np.nan
-        elif k == 2:
-            q["size"][b, 1], q["rotation"][b, 2] = 1.0, np.inf
-        else:
-            q["center"][b, 0] = np.nan
-    return q
-
-
 def _same_capsule_overlaps(w, rec, queries, what, capacity=None):
     """Count only, then a list call with `capacity` (None: exactly the total), against hostcapsule's brute force; returns the total."""
     cnt, _ = _gpu(w, queries, None)
@@ -490,5 +405,5 @@ def test_a_million_capsule_casts_on_the_landed_config_2_world():
     assert (~slab).mean() > 0.2
     # 1024 casts spread over the batch, bit for bit against the brute force over all 1,004,524 colliders
     pick = np.linspace(0, n - 1, 1024).astype(np.int64)
-    _same_hits(got[pick], H.capsulecast(rec, w.nbox, casts[pick]), "config 2, 1 M capsule casts")
+    _same_hits(got[pick], CAST.cast(CAST.CAPSULE, rec, w.nbox, casts[pick]), "config 2, 1 M capsule casts")
     w.close()

@@ -1,6 +1,6 @@
 """All-hits casts on the GPU (pytest -m gpu): nh_raycast_all / nh_spherecast_all (include/nudge_hip.h, "scene queries").
 
-The oracle is a brute force over every collider on the host with the same arithmetic (nudge_amd/csrc/nh_query.h through tests/hostcastall_util.py,
+The oracle is a brute force over every collider on the host with the same arithmetic (nudge_amd/csrc/nh_query.h through tests/hostcast_util.py,
 itself checked against the existing single-collider oracles in tests/test_cpu_castall.py).  The answer is defined without reference to the tree --
 per cast the colliders it hits in ascending t, ties in ascending combined index, laid out by the exclusive scan of the counts -- so offsets and
 records must equal the brute force byte for byte, and so must every byte of `hits` behind the written prefix (a sentinel there stays the sentinel).
@@ -14,104 +14,22 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import hostcastall_util as A                 # noqa: E402
+import hostcast_util as CAST                 # noqa: E402
 import hostquery_util as Q                   # noqa: E402
-from test_gpu_query import OBSERVED, SMALL, _bounds, _rays, _same_stepped_world, _upload      # noqa: E402
+from cast_util import (SENTINEL, all_hits as _gpu, far_and_near, first_record_is_the_closest_hit as _first_record_is_the_closest_hit,      # noqa: E402
+                       host_all_hits as _host, mixed as _mixed, same_all_hits, spheres as _casts)
+from query_util import FUSED, NONE, OBSERVED, SMALL, bounds as _bounds, rays as _rays, same_stepped_world as _same_stepped_world, upload as _upload      # noqa: E402
 from nudge_amd import engine as E           # noqa: E402
 from nudge_amd import scenes as S           # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-NONE = 0xFFFFFFFF
-FUSED = E.NH_FLAG_SINGLE_APPLY | E.NH_FLAG_FUSED_STEP
-SENTINEL = 0xA5
 RADII = (0.05, 0.75)
 
 
-def _casts(rays, radius):
-    c = np.zeros(len(rays), dtype=E.SPHERE_CAST)
-    for k in ("origin", "max_t", "direction", "ignore_body"):
-        c[k] = rays[k]
-    c["radius"] = radius
-    return c
-
-
-def _sweep(casts):
-    return casts.dtype == E.SPHERE_CAST
-
-
-def _gpu(w, casts, capacity):
-    """(offsets, hits): one all-hits call with `hits` pre-filled with the sentinel (capacity records; None = count only)."""
-    import torch
-    ct = _upload(w, casts)
-    ot = torch.full((len(casts) + 1,), -1, dtype=torch.int32, device=w.dev)
-    ht = None if capacity is None else torch.full((max(capacity, 1), 32), SENTINEL, dtype=torch.uint8, device=w.dev)
-    (w.spherecast_all_records if _sweep(casts) else w.raycast_all_records)(ct, offsets=ot, hits=ht, capacity=capacity or 0)
-    off = ot.cpu().numpy().view(np.uint32).copy()
-    hits = None if ht is None else np.frombuffer(ht.cpu().numpy().tobytes(), dtype=E.RAY_HIT).copy()
-    return off, hits
-
-
-def _closest(w, casts):
-    raw = (w.spherecast_records if _sweep(casts) else w.raycast_records)(_upload(w, casts))
-    return np.frombuffer(raw.cpu().numpy().tobytes(), dtype=E.RAY_HIT).copy()
-
-
-def _host(rec, nbox, casts, capacity):
-    hits = np.frombuffer(bytes([SENTINEL]) * 32 * max(capacity, 1), dtype=E.RAY_HIT).copy()
-    return (A.spherecast_all if _sweep(casts) else A.raycast_all)(rec, nbox, casts, capacity=capacity, hits=hits)
-
-
-def _first_record_is_the_closest_hit(w, casts, off, hits, what):
-    """The contract, against the closest-hit call on the GPU itself, for every cast of the batch."""
-    best = _closest(w, casts)
-    cnt = np.diff(off.astype(np.int64))
-    full = cnt > 0
-    assert (best["shape"][~full] == NONE).all(), f"{what}: {int((best['shape'][~full] != NONE).sum())} empty segments where the closest-hit call hits"
-    first = hits[off[:-1][full]]
-    bad = (first.view(np.uint8).reshape(-1, 32) != best[full].view(np.uint8).reshape(-1, 32)).any(axis=1)
-    assert not bad.any(), f"{what}: {int(bad.sum())} of {int(full.sum())} first records differ from the closest hit"
-
-
 def _same(w, rec, casts, what, capacity=None):
-    """The count-only call, then a list call with `capacity` (None: exactly the total), against the brute force; returns the total."""
-    cnt, _ = _gpu(w, casts, None)
-    ref_cnt, _, total = (A.spherecast_all if _sweep(casts) else A.raycast_all)(rec, w.nbox, casts, capacity=0)
-    assert cnt.tobytes() == ref_cnt.tobytes(), f"{what}: count-only offsets differ in {int((cnt != ref_cnt).sum())} of {len(cnt)}"
-    cap = (0 if total >= NONE else total) if capacity is None else capacity
-    off, hits = _gpu(w, casts, cap)
-    ref_off, ref_hits, _ = _host(rec, w.nbox, casts, cap)
-    assert off.tobytes() == cnt.tobytes(), f"{what}: list-mode offsets differ from count-only ones"
-    assert off.tobytes() == ref_off.tobytes(), f"{what}: offsets differ"
-    assert hits.tobytes() == ref_hits.tobytes(), \
-        f"{what}: {int((hits.view(np.uint8).reshape(-1, 32) != ref_hits.view(np.uint8).reshape(-1, 32)).any(axis=1).sum())} of {len(hits)} records differ"
-    if cap >= total and total:
-        _first_record_is_the_closest_hit(w, casts, off, hits, what)
-    return total
-
-
-def _mixed(rng, n, rec, lo, hi):
-    """Random rays with ignore_body set on a third, finite max_t on a third, a few from inside colliders, a few invalid and a few of zero direction."""
-    r = _rays(rng, n, lo, hi, "random")
-    live = np.nonzero(np.isfinite(rec["p"]).all(axis=1))[0]
-    ign = rng.random(n) < 0.3
-    r["ignore_body"][ign] = rec["body"][rng.choice(live, size=int(ign.sum()))]
-    fin = rng.random(n) < 0.3
-    r["max_t"][fin] = rng.uniform(0.0, 0.5 * float(np.linalg.norm(np.asarray(hi, np.float64) - np.asarray(lo, np.float64))), size=int(fin.sum()))
-    ins = rng.choice(n, size=n // 8, replace=False)
-    r["origin"][ins] = rec["p"][rng.choice(live, size=len(ins))]
-    bad = rng.choice(n, size=max(4, n // 64), replace=False)
-    for j, b in enumerate(bad):
-        k = j % 4
-        if k == 0:
-            r["origin"][b, 1] = np.nan
-        elif k == 1:
-            r["direction"][b, 0] = np.inf
-        elif k == 2:
-            r["max_t"][b] = np.nan
-        else:
-            r["direction"][b] = 0.0
-    return r
+    """cast_util.same_all_hits(); returns the total."""
+    return same_all_hits(w, rec, casts, what, capacity)[2]
 
 
 def _check_world(w, scene, rng, n, what, radii=RADII):
@@ -227,13 +145,7 @@ def test_four_thousand_boxes_at_one_position():
 def test_a_scene_spanning_a_thousandth_and_ten_thousand_units():
     scene = S.pile(2000, 1000, seed=3)
     rng = np.random.default_rng(45)
-    nb = len(scene["body_transforms"])
-    small = rng.random(nb) < 0.5
-    pos = np.where(small[:, None], rng.uniform(-0.05, 0.05, size=(nb, 3)), rng.uniform(-1e4, 1e4, size=(nb, 3))).astype(np.float32)
-    scene["body_transforms"]["position"][1:] = pos[1:]
-    bsmall = small[scene["box_transforms"]["body"][1:]]
-    scene["box_data"]["size"][1:] = np.where(bsmall[:, None], np.float32(1e-3), np.float32(30.0))
-    scene["sphere_data"]["radius"] = np.where(small[scene["sphere_transforms"]["body"]], np.float32(1e-3), np.float32(25.0))
+    far_and_near(scene, rng)
     w = E.World(scene, flags=FUSED)
     w.query_build()
     _check_world(w, scene, rng, 4096, "1e-3 .. 1e4", radii=(1e-4, 5.0, 100.0))
@@ -301,13 +213,13 @@ def test_one_ray_along_a_row_of_a_4096_collider_world_and_a_million_rays_around_
     rays["direction"][::256, 1] = 0.0
     rays["max_t"][1::2] = rng.uniform(0, 60, size=m // 2)
     cnt, _ = _gpu(w, rays, None)
-    ref_cnt, _, total = A.raycast_all(rec, w.nbox, rays, capacity=0)
+    ref_cnt, _, total = CAST.cast_all(CAST.RAY, rec, w.nbox, rays, capacity=0)
     assert cnt.tobytes() == ref_cnt.tobytes() and m // 8 < total < NONE
     off, hits = _gpu(w, rays, total)
     assert off.tobytes() == cnt.tobytes()
     _first_record_is_the_closest_hit(w, rays, off, hits, "2^20 rays on 4097 colliders")
     pick = np.unique(np.concatenate([np.linspace(0, m - 1, 2048).astype(np.int64), np.argsort(np.diff(off.astype(np.int64)))[-64:]]))
-    ref_off, ref_hits, ref_total = A.raycast_all(rec, w.nbox, rays[pick])
+    ref_off, ref_hits, ref_total = CAST.cast_all(CAST.RAY, rec, w.nbox, rays[pick])
     assert np.array_equal(np.diff(ref_off.astype(np.int64)), np.diff(off.astype(np.int64))[pick])
     seg = np.concatenate([hits[off[i]:off[i + 1]] for i in pick])
     assert seg.tobytes() == ref_hits[:ref_total].tobytes()
@@ -321,7 +233,7 @@ def test_a_total_of_two_to_the_thirty_second_writes_the_marker_and_no_record():
     rec = Q.records(w.get_bodies()["transforms"], scene)
     rays = np.zeros(1 << 20, dtype=E.RAY)
     rays["origin"], rays["direction"], rays["max_t"], rays["ignore_body"] = (0.25, 3.0, -0.5), (0, 0, 1), np.inf, 0
-    assert A.raycast_all(rec, w.nbox, rays[:1], capacity=0)[2] == 4096          # so 2^20 of them make exactly 2^32: the 32-bit scan wraps to 0
+    assert CAST.cast_all(CAST.RAY, rec, w.nbox, rays[:1], capacity=0)[2] == 4096          # so 2^20 of them make exactly 2^32: the 32-bit scan wraps to 0
     for casts in (rays, _casts(rays, 0.5)):
         cnt, _ = _gpu(w, casts, None)
         assert cnt[-1] == NONE
@@ -351,7 +263,6 @@ def test_abi_edge_cases(entry):
     casts = _mixed(np.random.default_rng(48), 1024, rec, lo, hi)
     if entry == "nh_spherecast_all":
         casts = _casts(casts, 0.5)
-    size = casts.dtype.itemsize
     ct = _upload(w, casts)
     buf = torch.zeros(4 * 1032, dtype=torch.int32, device=w.dev)
     ot = buf[:1025]
@@ -378,7 +289,7 @@ def test_abi_edge_cases(entry):
     # offsets need 4-byte alignment only
     ot4 = buf[1:1026]
     assert fn(w.ctx, cp, 1024, C.c_void_p(ot4.data_ptr()), hp, cap, 0) == 0
-    ref_off, ref_hits, total = (A.spherecast_all if size == 48 else A.raycast_all)(rec, w.nbox, casts, capacity=cap)
+    ref_off, ref_hits, total = CAST.cast_all(CAST.shape_of(casts), rec, w.nbox, casts, capacity=cap)
     assert 0 < total <= cap
     assert ot4.cpu().numpy().view(np.uint32).tobytes() == ref_off.tobytes()
     got = np.frombuffer(ht.cpu().numpy().tobytes(), dtype=E.RAY_HIT)
@@ -487,7 +398,7 @@ def test_a_million_rays_on_the_landed_config_2_world():
     assert bool((t[1:] >= t[:-1])[inner[1:]].all())
     # a seeded sample of 2048 rays, byte for byte against the brute force over all 1,004,524 colliders
     pick = np.sort(rng.choice(n, size=2048, replace=False))
-    ref_off, ref_hits, ref_total = A.raycast_all(rec, w.nbox, rays[pick])
+    ref_off, ref_hits, ref_total = CAST.cast_all(CAST.RAY, rec, w.nbox, rays[pick])
     assert np.array_equal(np.diff(ref_off.astype(np.int64)), np.diff(off.astype(np.int64))[pick])
     idx = np.concatenate([np.arange(off[i], off[i + 1], dtype=np.int64) for i in pick])
     seg = np.frombuffer(ht[torch.from_numpy(idx).to(w.dev)].cpu().numpy().tobytes(), dtype=E.RAY_HIT)

@@ -1,7 +1,7 @@
 """All-hits box and capsule casts on the GPU (pytest -m gpu): nh_boxcast_all / nh_capsulecast_all (include/nudge_hip.h, "scene queries").
 
 The oracle is a brute force over every collider on the host with the same arithmetic (nudge_amd/csrc/nh_query.h through
-tests/hostcastall_shapes_util.py, itself checked against the existing single-collider oracles in tests/test_cpu_castall_shapes.py).  The answer is
+tests/hostcast_util.py, itself checked against the existing single-collider oracles in tests/test_cpu_castall_shapes.py).  The answer is
 defined without reference to the tree, so offsets and records must equal the brute force byte for byte, and so must every byte of `hits` behind the
 written prefix.  The first record of every segment must be the closest-hit call's record on the GPU itself, the degenerate shapes must give the GPU's
 own nh_raycast_all / nh_spherecast_all bytes, and the calls are observers."""
@@ -13,79 +13,23 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import hostcastall_shapes_util as A          # noqa: E402
+import hostcast_util as CAST                 # noqa: E402
 import hostquery_util as Q                   # noqa: E402
-from test_cpu_castall_shapes import box_casts, capsule_casts, casts_through, coincident      # noqa: E402
-from test_gpu_castall import _mixed           # noqa: E402
-from test_gpu_query import OBSERVED, SMALL, _bounds, _rays, _same_stepped_world, _upload      # noqa: E402
+from cast_util import (SENTINEL, all_hits as _gpu, as_balls as _as_balls, box_casts, capsule_casts, casts_through, coincident,      # noqa: E402
+                       far_and_near_scene as _far_and_near_scene, host_all_hits as _host, mixed as _mixed, same_all_hits)
+from query_util import FUSED, OBSERVED, SMALL, bounds as _bounds, rays as _rays, records as _records, same_stepped_world as _same_stepped_world, upload as _upload      # noqa: E402
 from nudge_amd import engine as E           # noqa: E402
 from nudge_amd import scenes as S           # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-NONE = 0xFFFFFFFF
-FUSED = E.NH_FLAG_SINGLE_APPLY | E.NH_FLAG_FUSED_STEP
-SENTINEL = 0xA5
 SHAPES = ("box", "capsule")
 STILL = ("still_steps", "still_replays", "ahead_steps", "pair_steps", "asleep_steps")
 
 
-def _is_box(casts):
-    return casts.dtype == E.BOX_CAST
-
-
-def _gpu(w, casts, capacity):
-    """(offsets, hits): one all-hits call with `hits` pre-filled with the sentinel (capacity records; None = count only)."""
-    import torch
-    ct = _upload(w, casts)
-    ot = torch.full((len(casts) + 1,), -1, dtype=torch.int32, device=w.dev)
-    ht = None if capacity is None else torch.full((max(capacity, 1), 32), SENTINEL, dtype=torch.uint8, device=w.dev)
-    (w.boxcast_all_records if _is_box(casts) else w.capsulecast_all_records)(ct, offsets=ot, hits=ht, capacity=capacity or 0)
-    off = ot.cpu().numpy().view(np.uint32).copy()
-    hits = None if ht is None else np.frombuffer(ht.cpu().numpy().tobytes(), dtype=E.RAY_HIT).copy()
-    return off, hits
-
-
-def _closest(w, casts):
-    raw = (w.boxcast_records if _is_box(casts) else w.capsulecast_records)(_upload(w, casts))
-    return np.frombuffer(raw.cpu().numpy().tobytes(), dtype=E.RAY_HIT).copy()
-
-
-def _host(rec, nbox, casts, capacity):
-    hits = np.frombuffer(bytes([SENTINEL]) * 32 * max(capacity, 1), dtype=E.RAY_HIT).copy()
-    return (A.boxcast_all if _is_box(casts) else A.capsulecast_all)(rec, nbox, casts, capacity=capacity, hits=hits)
-
-
-def _first_record_is_the_closest_hit(w, casts, off, hits, what):
-    """The contract, against the closest-hit call on the GPU itself, for every cast of the batch."""
-    best = _closest(w, casts)
-    cnt = np.diff(off.astype(np.int64))
-    full = cnt > 0
-    assert (best["shape"][~full] == NONE).all(), f"{what}: {int((best['shape'][~full] != NONE).sum())} empty segments where the closest-hit call hits"
-    first = hits[off[:-1][full]]
-    bad = (first.view(np.uint8).reshape(-1, 32) != best[full].view(np.uint8).reshape(-1, 32)).any(axis=1)
-    assert not bad.any(), f"{what}: {int(bad.sum())} of {int(full.sum())} first records differ from the closest hit"
-
-
 def _same(w, rec, casts, what, capacity=None):
-    """The count-only call, then a list call with `capacity` (None: exactly the total), against the brute force; returns (offsets, hits)."""
-    cnt, _ = _gpu(w, casts, None)
-    ref_cnt, _, total = (A.boxcast_all if _is_box(casts) else A.capsulecast_all)(rec, w.nbox, casts, capacity=0)
-    assert cnt.tobytes() == ref_cnt.tobytes(), f"{what}: count-only offsets differ in {int((cnt != ref_cnt).sum())} of {len(cnt)}"
-    cap = total if capacity is None else capacity
-    off, hits = _gpu(w, casts, cap)
-    ref_off, ref_hits, _ = _host(rec, w.nbox, casts, cap)
-    assert off.tobytes() == cnt.tobytes(), f"{what}: list-mode offsets differ from count-only ones"
-    assert off.tobytes() == ref_off.tobytes(), f"{what}: offsets differ"
-    assert hits.tobytes() == ref_hits.tobytes(), \
-        f"{what}: {int((hits.view(np.uint8).reshape(-1, 32) != ref_hits.view(np.uint8).reshape(-1, 32)).any(axis=1).sum())} of {len(hits)} records differ"
-    if cap >= total and total:
-        _first_record_is_the_closest_hit(w, casts, off, hits, what)
-    return off, hits
-
-
-def _records(w, scene):
-    return Q.records(w.get_bodies()["transforms"], scene, w.nbox, w.nsph)
+    """cast_util.same_all_hits(); returns (offsets, hits)."""
+    return same_all_hits(w, rec, casts, what, capacity)[:2]
 
 
 def _batches(rng, n, rec):
@@ -101,7 +45,7 @@ def _check_world(w, scene, rng, n, what, least=None):
     rec = _records(w, scene)
     out = []
     for casts in _batches(rng, n, rec):
-        off, hits = _same(w, rec, casts, f"{what} / {'box' if _is_box(casts) else 'capsule'} casts")
+        off, hits = _same(w, rec, casts, f"{what} / {CAST.shape_of(casts).name} casts")
         assert int(off[-1]) > (n // 2 if least is None else least), (what, int(off[-1]))
         out += [off.tobytes(), hits.tobytes()]
     return out
@@ -129,37 +73,6 @@ def test_all_hits_equal_the_brute_force_before_and_after_stepping_and_after_a_re
     w.close()
 
 
-def _far_and_near_scene():
-    """Half the bodies within 0.05 of the origin at size 1e-3, the others anywhere within 1e4 at sizes of 25 to 30."""
-    scene = S.pile(600, 300, seed=3)
-    rng = np.random.default_rng(61)
-    nb = len(scene["body_transforms"])
-    small = rng.random(nb) < 0.5
-    pos = np.where(small[:, None], rng.uniform(-0.05, 0.05, size=(nb, 3)), rng.uniform(-1e4, 1e4, size=(nb, 3))).astype(np.float32)
-    scene["body_transforms"]["position"][1:] = pos[1:]
-    bsmall = small[scene["box_transforms"]["body"][1:]]
-    scene["box_data"]["size"][1:] = np.where(bsmall[:, None], np.float32(1e-3), np.float32(30.0))
-    scene["sphere_data"]["radius"] = np.where(small[scene["sphere_transforms"]["body"]], np.float32(1e-3), np.float32(25.0))
-    return scene
-
-
-def _as_balls(casts):
-    b = np.zeros(len(casts), dtype=E.SPHERE_CAST)
-    for k in ("origin", "max_t", "direction", "ignore_body", "radius"):
-        b[k] = casts[k]
-    return b
-
-
-def _gpu_simple(w, casts, capacity):
-    """nh_raycast_all (E.RAY) / nh_spherecast_all (E.SPHERE_CAST) on the GPU, as _gpu."""
-    import torch
-    ct = _upload(w, casts)
-    ot = torch.full((len(casts) + 1,), -1, dtype=torch.int32, device=w.dev)
-    ht = torch.full((max(capacity, 1), 32), SENTINEL, dtype=torch.uint8, device=w.dev)
-    (w.raycast_all_records if casts.dtype == E.RAY else w.spherecast_all_records)(ct, offsets=ot, hits=ht, capacity=capacity)
-    return ot.cpu().numpy().view(np.uint32).copy(), np.frombuffer(ht.cpu().numpy().tobytes(), dtype=E.RAY_HIT).copy()
-
-
 @pytest.mark.parametrize("world", ["pile", "far_and_near"])
 def test_degenerate_shapes_write_the_bytes_of_the_simpler_all_hits_call_on_the_gpu(world):
     scene = SMALL["pile"]() if world == "pile" else _far_and_near_scene()
@@ -171,7 +84,7 @@ def test_degenerate_shapes_write_the_bytes_of_the_simpler_all_hits_call_on_the_g
     # (rays from all over a world of 1e-3 .. 1e4 units graze far colliders: what the ray pad of the walk is for; and rays inside the small cluster)
     rays = np.concatenate([_mixed(rng, 512, rec, lo, hi), _rays(rng, 256, (-0.05,) * 3, (0.05,) * 3, "random")])
     cap = 1 << 16
-    ray_off, ray_hits = _gpu_simple(w, rays, cap)
+    ray_off, ray_hits = _gpu(w, rays, cap)
     assert 128 < int(ray_off[-1]) <= cap
     # a box of size 0, whatever its rotation
     casts = box_casts(rng, rays, sizes=np.float32([(0, 0, 0), (-0.0, 0.0, -0.0)]), invalid=False)
@@ -190,7 +103,7 @@ def test_degenerate_shapes_write_the_bytes_of_the_simpler_all_hits_call_on_the_g
     casts["rotation"][::3] = np.nan
     casts["radius"][5::40], casts["radius"][6::40] = np.nan, -1.0
     cap = 1 << 18
-    ball_off, ball_hits = _gpu_simple(w, _as_balls(casts), cap)
+    ball_off, ball_hits = _gpu(w, _as_balls(casts), cap)
     assert 256 < int(ball_off[-1]) <= cap
     off, hits = _gpu(w, casts, cap)
     assert off.tobytes() == ball_off.tobytes() and hits.tobytes() == ball_hits.tobytes(), "hh = 0 differs from nh_spherecast_all"
@@ -336,7 +249,7 @@ def test_abi_edge_cases(entry):
     # offsets need 4-byte alignment only
     ot4 = buf[1:258]
     assert fn(w.ctx, cp, 256, C.c_void_p(ot4.data_ptr()), hp, cap, 0) == 0
-    ref_off, ref_hits, total = (A.boxcast_all if entry == "nh_boxcast_all" else A.capsulecast_all)(rec, w.nbox, casts, capacity=cap)
+    ref_off, ref_hits, total = CAST.cast_all(CAST.shape_of(casts), rec, w.nbox, casts, capacity=cap)
     assert 0 < total <= cap
     assert ot4.cpu().numpy().view(np.uint32).tobytes() == ref_off.tobytes()
     got = np.frombuffer(ht.cpu().numpy().tobytes(), dtype=E.RAY_HIT)
@@ -355,7 +268,7 @@ def test_the_python_wrappers_write_the_records_they_describe():
                                          ignore_body=box["ignore_body"].astype(np.int64), synchronize=True)),
                      (cap, w.capsulecast_all(cap["origin"], cap["direction"], cap["radius"], cap["half_height"], cap["rotation"], max_t=cap["max_t"],
                                              ignore_body=cap["ignore_body"].astype(np.int64), synchronize=True))):
-        ref_off, ref_hits, total = (A.boxcast_all if _is_box(casts) else A.capsulecast_all)(rec, w.nbox, casts)
+        ref_off, ref_hits, total = CAST.cast_all(CAST.shape_of(casts), rec, w.nbox, casts)
         assert int(r["written"]) == total == int(r["offsets"][-1]) and np.array_equal(r["offsets"].cpu().numpy(), ref_off.astype(np.int64))
         assert r["raw"].cpu().numpy().tobytes()[:32 * total] == ref_hits[:total].tobytes()
     # a capacity that cuts the list: nothing waits, whole segments only

@@ -13,44 +13,19 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import castk_batches as CB                   # noqa: E402
+import hostcast_util as CAST                 # noqa: E402
 import hostcastk_util as HK                  # noqa: E402
 import hostquery_util as Q                   # noqa: E402
-from test_cpu_castall_shapes import box_casts, capsule_casts, casts_through, coincident      # noqa: E402
-from test_cpu_castk import wide_casts        # noqa: E402
-from test_gpu_castall_shapes import _far_and_near_scene      # noqa: E402
-from test_gpu_query import OBSERVED, SMALL, _rays, _same_stepped_world, _upload      # noqa: E402
+from cast_util import (GUARD, SENTINEL, box_casts, capsule_casts, casts_through, closest as _closest, coincident,      # noqa: E402
+                       far_and_near_scene as _far_and_near_scene, first_k as _gpu, sphere_casts, wide_casts)
+from query_util import FUSED, NONE, OBSERVED, SMALL, rays as _rays, records as _records, same_stepped_world as _same_stepped_world, upload as _upload      # noqa: E402
 from nudge_amd import engine as E           # noqa: E402
 from nudge_amd import scenes as S           # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-NONE = 0xFFFFFFFF
-FUSED = E.NH_FLAG_SINGLE_APPLY | E.NH_FLAG_FUSED_STEP
-SENTINEL = 0xA5
-GUARD = 64                                   # records (and count words) behind the output that must stay the sentinel
 KS = (1, 2, 3, 8, 9, 16, 17, 32)             # both sides of each block-size step (256 lanes up to 8, 128 up to 16, 64 up to 32)
 STILL = ("still_steps", "still_replays", "ahead_steps", "pair_steps", "asleep_steps")
-CALLS = {"ray": ("raycast_k_records", "raycast_records"), "sphere": ("spherecast_k_records", "spherecast_records"),
-         "box": ("boxcast_k_records", "boxcast_records"), "capsule": ("capsulecast_k_records", "capsulecast_records")}
-
-
-def _gpu(w, casts, k, with_counts=True):
-    """(counts or None, hits (n, k)) of one first-k call on buffers pre-filled with the sentinel; the guards behind both must come back untouched."""
-    import torch
-    n = len(casts)
-    ht = torch.full((n * k + GUARD, 32), SENTINEL, dtype=torch.uint8, device=w.dev)
-    ct = torch.full((n + GUARD,), -1, dtype=torch.int32, device=w.dev)
-    getattr(w, CALLS[HK.shape_of(casts)][0])(_upload(w, casts), k, counts=ct if with_counts else None, hits=ht)
-    hits = np.frombuffer(ht.cpu().numpy().tobytes(), dtype=E.RAY_HIT).copy()
-    counts = ct.cpu().numpy().view(np.uint32).copy()
-    assert set(hits[n * k:].tobytes()) == {SENTINEL}, f"k {k}: bytes behind record count * k were written"
-    assert (counts[n:] == NONE).all() and (with_counts or (counts == NONE).all()), f"k {k}: words outside counts[0 .. count) were written"
-    return (counts[:n] if with_counts else None), hits[:n * k].reshape(n, k)
-
-
-def _closest(w, casts):
-    raw = getattr(w, CALLS[HK.shape_of(casts)][1])(_upload(w, casts))
-    return np.frombuffer(raw.cpu().numpy().tobytes(), dtype=E.RAY_HIT).copy()
 
 
 def _differ(a, b):
@@ -75,10 +50,6 @@ def _same(w, rec, casts, what, ks=KS, seg=None, closest=True):
     if 8 in by_k and 32 in by_k:
         assert np.ascontiguousarray(by_k[32][:, :8]).tobytes() == by_k[8].tobytes(), f"{what}: the first 8 of k = 32 differ from k = 8"
     return out
-
-
-def _records(w, scene):
-    return Q.records(w.get_bodies()["transforms"], scene, w.nbox, w.nsph)
 
 
 def _check_world(w, scene, rng, what):
@@ -122,7 +93,7 @@ def test_ties_through_4096_coincident_boxes_are_the_lowest_indices_in_order():
     rec = _records(w, scene)
     rng = np.random.default_rng(740)
     rays = casts_through((0.25, 3.0, -0.5), 64, rng)
-    batches = {"ray": rays, "sphere": CB.sphere_casts(rays, invalid=False), "box": box_casts(rng, rays, invalid=False),
+    batches = {"ray": rays, "sphere": sphere_casts(rays, invalid=False), "box": box_casts(rng, rays, invalid=False),
                "capsule": capsule_casts(rng, rays, invalid=False)}
     for shape, casts in batches.items():
         seg = HK.segments(rec, w.nbox, casts)
@@ -175,7 +146,7 @@ def test_degenerate_shapes_write_the_simpler_calls_bytes_on_a_world_of_a_thousan
         ray = _gpu(w, rays, k)
         assert int(ray[0].sum()) > 256
         # a ball of r = 0 (and -0), a box of size 0 and a capsule of r = hh = 0, whatever their rotations: the ray call's bytes
-        ball = CB.sphere_casts(rays, np.float32([0.0, -0.0]), invalid=False)
+        ball = sphere_casts(rays, np.float32([0.0, -0.0]), invalid=False)
         box = box_casts(rng, rays, sizes=np.float32([(0, 0, 0), (-0.0, 0.0, -0.0)]), invalid=False)
         cap = capsule_casts(rng, rays, shapes=np.float32([(0.0, 0.0), (-0.0, 0.0), (0.0, -0.0)]), invalid=False)
         box["rotation"][::3] = np.nan
@@ -270,7 +241,7 @@ def _observer_batch(a):
     import torch
     rays = _rays(np.random.default_rng(790), 1000, (-30, -12, -30), (30, 20, 30), "random")
     rng = np.random.default_rng(791)
-    casts = [rays, CB.sphere_casts(rays), box_casts(rng, rays), capsule_casts(rng, rays)]
+    casts = [rays, sphere_casts(rays), box_casts(rng, rays), capsule_casts(rng, rays)]
     return [_upload(a, c) for c in casts], torch.empty(1000, dtype=torch.int32, device=a.dev), torch.empty((1000 * 32, 32), dtype=torch.uint8, device=a.dev)
 
 
@@ -280,7 +251,7 @@ def _query(w, casts, nt, ht, turn):
     else:
         w.query_build()
     for j, (shape, ct) in enumerate(zip(CB.SHAPES, casts)):
-        getattr(w, CALLS[shape][0])(ct, KS[(turn + 2 * j) % len(KS)], counts=nt, hits=ht)
+        getattr(w, CAST.SHAPES[shape].call + "_k_records")(ct, KS[(turn + 2 * j) % len(KS)], counts=nt, hits=ht)
 
 
 @pytest.mark.parametrize("name", sorted(OBSERVED))

@@ -15,8 +15,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import hostdistance_util as D               # noqa: E402
 import hostpoint_util as HP                 # noqa: E402
 import hostquery_util as Q                  # noqa: E402
-from query_util import unit_quats           # noqa: E402
-from test_gpu_query import OBSERVED, SMALL, _bounds, _same_stepped_world, _upload      # noqa: E402
+from query_util import OBSERVED, SMALL, bounds as _bounds, same_stepped_world as _same_stepped_world, unit_quats, upload as _upload      # noqa: E402
 from nudge_amd import engine as E           # noqa: E402
 from nudge_amd import scenes as S           # noqa: E402
 

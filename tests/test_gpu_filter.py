@@ -13,22 +13,17 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import castk_batches as CB                   # noqa: E402
 import filter_util as F                      # noqa: E402
+import hostcast_util as CAST                 # noqa: E402
+import hostcastk_util as HK                  # noqa: E402
 import hostquery_util as Q                   # noqa: E402
-import test_gpu_boxcast as TB                # noqa: E402
-import test_gpu_capsulecast as TC            # noqa: E402
-import test_gpu_castall as TA                # noqa: E402
-import test_gpu_castall_shapes as TAS        # noqa: E402
-import test_gpu_castk as TK                  # noqa: E402
 import test_gpu_closest as TP                # noqa: E402
 import test_gpu_distance as TD               # noqa: E402
 import test_gpu_nearest as TN                # noqa: E402
 import test_gpu_overlap as TO                # noqa: E402
 import test_gpu_penetration as TPEN          # noqa: E402
-import test_gpu_spherecast as TS             # noqa: E402
-from test_cpu_castall_shapes import box_casts, capsule_casts, casts_through, coincident      # noqa: E402
-from test_gpu_query import OBSERVED, SMALL, _bounds, _cast, _same_stepped_world, _upload      # noqa: E402
+from cast_util import all_hits, box_casts, capsule_casts, casts_through, closest as _cast, coincident, first_k, sphere_casts      # noqa: E402
+from query_util import OBSERVED, SMALL, bounds as _bounds, same_stepped_world as _same_stepped_world, upload as _upload      # noqa: E402
 from nudge_amd import engine as E           # noqa: E402
 from nudge_amd import scenes as S           # noqa: E402
 
@@ -38,9 +33,6 @@ NONE = 0xFFFFFFFF
 FUSED = E.NH_FLAG_SINGLE_APPLY | E.NH_FLAG_FUSED_STEP
 SENTINEL = F.SENTINEL
 BIT31 = 0x80000000
-# the closest-hit call of each cast batch, and the all-hits call
-SWEEP = {"rays": _cast, "spheres": TS._sweep, "boxes": TB._sweep, "capsules": TC._sweep}
-ALL = {"rays": TA._gpu, "spheres": TA._gpu, "boxes": TAS._gpu, "capsules": TAS._gpu}
 
 
 def _records(w, scene):
@@ -67,11 +59,11 @@ def _gpu(w, b, ref, before=lambda name: None):
     out, any_hit = {}, {}
     for name in F.CASTS:
         before(name)
-        out[name] = SWEEP[name](w, b[name])
-        any_hit[name] = SWEEP[name](w, b[name], any_hit=True)["shape"] != NONE
-        out[name + "_all"] = _list(ALL[name], w, b[name], len(ref[name + "_all"][1]))
-        out[name + "_k"] = TK._gpu(w, b[name], F.CAST_K)
-        assert TK._gpu(w, b[name], F.CAST_K, with_counts=False)[1].tobytes() == out[name + "_k"][1].tobytes(), f"{name}: counts = NULL writes other records"
+        out[name] = _cast(w, b[name])
+        any_hit[name] = _cast(w, b[name], any_hit=True)["shape"] != NONE
+        out[name + "_all"] = _list(all_hits, w, b[name], len(ref[name + "_all"][1]))
+        out[name + "_k"] = first_k(w, b[name], F.CAST_K)
+        assert first_k(w, b[name], F.CAST_K, with_counts=False)[1].tobytes() == out[name + "_k"][1].tobytes(), f"{name}: counts = NULL writes other records"
     before("points")
     out["points"] = TP._closest(w, b["points"])
     out["points_k"] = TN._nearest(w, b["points"], F.NEAR_K)
@@ -172,7 +164,7 @@ def test_a_bit_of_one_collider_reaches_the_root_of_a_tree_of_several_runs():
         rays["ignore_body"] = NONE
         hits = _cast(w, rays)
         assert (hits["shape"] == shape).all() and (hits["collider"] == index).all(), c
-        assert hits.tobytes() == Q.raycast(F.masked(rec, one, BIT31), w.nbox, rays).tobytes(), c
+        assert hits.tobytes() == CAST.cast(CAST.RAY, F.masked(rec, one, BIT31), w.nbox, rays).tobytes(), c
     w.close()
 
 
@@ -279,17 +271,17 @@ def test_ties_through_4096_coincident_boxes_go_to_the_lowest_index_the_mask_sees
     masked = F.masked(rec, words, 2)
     rng = np.random.default_rng(960)
     rays = casts_through((0.25, 3.0, -0.5), 64, rng)
-    batches = {"rays": rays, "spheres": CB.sphere_casts(rays, invalid=False), "boxes": box_casts(rng, rays, invalid=False),
+    batches = {"rays": rays, "spheres": sphere_casts(rays, invalid=False), "boxes": box_casts(rng, rays, invalid=False),
                "capsules": capsule_casts(rng, rays, invalid=False)}
     for name, casts in batches.items():
-        best = SWEEP[name](w, casts)
+        best = _cast(w, casts)
         assert (best["shape"] == E.NH_SHAPE_BOX).all() and (best["collider"] == 1).all(), name
-        counts, hits = TK._gpu(w, casts, 32)
+        counts, hits = first_k(w, casts, 32)
         assert (counts == 32).all() and (hits["collider"] == np.arange(1, 65, 2)).all(), name
         assert hits[:, 0].tobytes() == best.tobytes(), name
-        off, _ = ALL[name](w, casts, None)
+        off, _ = all_hits(w, casts, None)
         assert (np.diff(off.astype(np.int64)) == 2048).all(), name
-        ref_counts, ref_hits = TK.HK.cast_k(masked, w.nbox, casts, 32)
+        ref_counts, ref_hits = HK.cast_k(masked, w.nbox, casts, 32)
         assert counts.tobytes() == ref_counts.tobytes() and hits.tobytes() == ref_hits.tobytes(), name
     w.close()
 

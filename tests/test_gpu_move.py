@@ -16,8 +16,7 @@ import hostquery_util as Q                   # noqa: E402
 import move_batches as MB                    # noqa: E402
 from hostmover_util import CAPSULE as HM     # noqa: E402
 from mover_util import FUSED, NONE, SENTINEL, capsulecast as _capsulecast, move as _move, records as _records, same as _same      # noqa: E402
-from query_util import unit_quats            # noqa: E402
-from test_gpu_query import OBSERVED, SMALL, _same_stepped_world, _upload      # noqa: E402
+from query_util import OBSERVED, SMALL, same_stepped_world as _same_stepped_world, unit_quats, upload as _upload      # noqa: E402
 from nudge_amd import engine as E           # noqa: E402
 from nudge_amd import scenes as S           # noqa: E402
 

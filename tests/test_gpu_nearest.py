@@ -14,7 +14,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import hostnearest_util as N                 # noqa: E402
 import hostquery_util as Q                   # noqa: E402
 from test_gpu_closest import _closest, _points, _queries                                 # noqa: E402
-from test_gpu_query import OBSERVED, SMALL, _bounds, _same_stepped_world, _upload      # noqa: E402
+from query_util import OBSERVED, SMALL, bounds as _bounds, same_stepped_world as _same_stepped_world, upload as _upload      # noqa: E402
 from nudge_amd import engine as E           # noqa: E402
 from nudge_amd import scenes as S           # noqa: E402
 

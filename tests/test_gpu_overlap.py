@@ -70,6 +70,32 @@ def _queries(rng, n, rec, kind, scale=1.0):
     return q
 
 
+def _capsule_queries(rng, n, rec, scale=1.0):
+    """Capsule queries around the scene: half on a collider, radii and half heights from 0, random rotations, some ignore_body and invalid ones."""
+    q = _queries(rng, n, rec, "sphere", scale)
+    q["shape"] = E.NH_SHAPE_CAPSULE
+    q["size"][:, 0] = rng.uniform(0.0, 1.2 * scale, size=n)
+    q["size"][:, 1] = rng.choice([0.0, 0.3, 1.0, 2.5], size=n) * scale
+    q["size"][:, 2] = np.nan                                           # (not read)
+    q["rotation"] = _unit_quats(rng, n)
+    q["rotation"][(q["size"][:, 1] == 0.0) & (rng.random(n) < 0.5)] = np.nan     # (not read at half height 0)
+    live = np.nonzero(np.isfinite(rec["p"]).all(axis=1))[0]
+    ign = rng.random(n) < 0.2
+    q["ignore_body"][ign] = rec["body"][rng.choice(live, size=int(ign.sum()))]
+    bad = rng.choice(n, size=max(1, n // 64), replace=False)
+    for j, b in enumerate(bad):
+        k = j % 4
+        if k == 0:
+            q["size"][b, 1] = -0.5
+        elif k == 1:
+            q["size"][b, 1] = np.nan
+        elif k == 2:
+            q["size"][b, 1], q["rotation"][b, 2] = 1.0, np.inf
+        else:
+            q["center"][b, 0] = np.nan
+    return q
+
+
 def _upload(w, arr):
     import torch
     return torch.from_numpy(np.ascontiguousarray(arr).view(np.uint8).copy()).to(w.dev)

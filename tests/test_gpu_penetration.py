@@ -14,8 +14,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import hostpen_util as H                     # noqa: E402
 import hostquery_util as Q                   # noqa: E402
-from query_util import unit_quats as _unit_quats      # noqa: E402
-from test_gpu_query import OBSERVED, SMALL, _bounds, _same_stepped_world, _upload      # noqa: E402
+from query_util import OBSERVED, SMALL, bounds as _bounds, same_stepped_world as _same_stepped_world, unit_quats as _unit_quats, upload as _upload      # noqa: E402
 from nudge_amd import engine as E           # noqa: E402
 from nudge_amd import scenes as S           # noqa: E402
 

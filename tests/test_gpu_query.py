@@ -11,61 +11,14 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import hostcast_util as CAST                 # noqa: E402
 import hostquery_util as Q                   # noqa: E402
-import parity_util as P                      # noqa: E402
-from query_util import SMALL, bounds as _bounds      # noqa: E402
+from cast_util import closest as _cast, far_and_near, same_hits as _same_hits      # noqa: E402
+from query_util import FUSED, NONE, OBSERVED, SMALL, bounds as _bounds, rays as _rays, same_stepped_world as _same_stepped_world, upload as _upload      # noqa: E402
 from nudge_amd import engine as E           # noqa: E402
 from nudge_amd import scenes as S           # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-NONE = 0xFFFFFFFF
-FUSED = E.NH_FLAG_SINGLE_APPLY | E.NH_FLAG_FUSED_STEP
-
-
-def _rays(rng, n, lo, hi, kind, max_t=np.inf):
-    """`kind`: random origins / directions around the scene; axis-aligned (one or two direction components exactly zero); a downward grid."""
-    lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
-    span = np.maximum(hi - lo, 1.0)
-    r = np.zeros(n, dtype=E.RAY)
-    r["max_t"] = max_t
-    r["ignore_body"] = NONE
-    if kind == "random":
-        r["origin"] = rng.uniform(lo - 0.2 * span, hi + 0.2 * span, size=(n, 3))
-        aim = rng.uniform(lo, hi, size=(n, 3))
-        d = aim - r["origin"]
-        r["direction"] = d / np.linalg.norm(d, axis=1, keepdims=True) * rng.uniform(0.25, 4.0, size=(n, 1))
-    elif kind == "axis":
-        r["origin"] = rng.uniform(lo - 0.1 * span, hi + 0.1 * span, size=(n, 3))
-        d = np.zeros((n, 3))
-        ax = rng.integers(0, 3, size=n)
-        d[np.arange(n), ax] = rng.choice([-1.0, 1.0], size=n) * rng.uniform(0.5, 2.0, size=n)
-        two = rng.random(n) < 0.3          # (a third of them with one zero component only)
-        ax2 = (ax + 1) % 3
-        d[two, ax2[two]] = rng.uniform(-1.0, 1.0, size=int(two.sum()))
-        r["direction"] = d
-    else:
-        side = int(np.sqrt(n))
-        gx, gz = np.meshgrid(np.linspace(lo[0], hi[0], side), np.linspace(lo[2], hi[2], n // side + 1))
-        r["origin"][:, 0] = gx.reshape(-1)[:n]
-        r["origin"][:, 1] = hi[1] + 5.0
-        r["origin"][:, 2] = gz.reshape(-1)[:n]
-        r["direction"] = (0.0, -1.0, 0.0)
-    return r
-
-
-def _upload(w, rays):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(rays).view(np.uint8).copy()).to(w.dev)
-
-
-def _cast(w, rays, any_hit=False):
-    raw = w.raycast_records(_upload(w, rays), any_hit=any_hit)
-    return np.frombuffer(raw.cpu().numpy().tobytes(), dtype=E.RAY_HIT).copy()
-
-
-def _same_hits(got, ref, what):
-    assert got.tobytes() == ref.tobytes(), f"{what}: {int((got.view(np.uint8).reshape(-1, 32) != ref.view(np.uint8).reshape(-1, 32)).any(axis=1).sum())} of {len(ref)} hit records differ"
 
 
 def _check_world(w, scene, rng, n, what):
@@ -76,7 +29,7 @@ def _check_world(w, scene, rng, n, what):
     for kind in ("random", "axis", "down"):
         rays = _rays(rng, n, lo, hi, kind)
         got = _cast(w, rays)
-        ref = Q.raycast(rec, w.nbox, rays)
+        ref = CAST.cast(CAST.RAY, rec, w.nbox, rays)
         _same_hits(got, ref, f"{what} / {kind}")
         hit_share.append(float((ref["shape"] != NONE).mean()))
     return hit_share
@@ -134,20 +87,14 @@ def test_four_thousand_boxes_at_one_position():
 def test_a_scene_spanning_a_thousandth_and_ten_thousand_units():
     scene = S.pile(2000, 1000, seed=3)
     rng = np.random.default_rng(4)
-    nb = len(scene["body_transforms"])
-    small = rng.random(nb) < 0.5
-    pos = np.where(small[:, None], rng.uniform(-0.05, 0.05, size=(nb, 3)), rng.uniform(-1e4, 1e4, size=(nb, 3))).astype(np.float32)
-    scene["body_transforms"]["position"][1:] = pos[1:]
-    bsmall = small[scene["box_transforms"]["body"][1:]]
-    scene["box_data"]["size"][1:] = np.where(bsmall[:, None], np.float32(1e-3), np.float32(30.0))
-    scene["sphere_data"]["radius"] = np.where(small[scene["sphere_transforms"]["body"]], np.float32(1e-3), np.float32(25.0))
+    far_and_near(scene, rng)
     w = E.World(scene, flags=FUSED)
     _check_world(w, scene, rng, 32768, "1e-3 .. 1e4")
     # rays at the small cluster from afar and from inside it
     rec = Q.records(w.get_bodies()["transforms"], scene)
     for lo, hi in (((-0.05,) * 3, (0.05,) * 3), ((-0.01,) * 3, (0.01,) * 3)):
         rays = _rays(rng, 16384, lo, hi, "random")
-        _same_hits(_cast(w, rays), Q.raycast(rec, w.nbox, rays), f"small cluster {lo}")
+        _same_hits(_cast(w, rays), CAST.cast(CAST.RAY, rec, w.nbox, rays), f"small cluster {lo}")
     w.close()
 
 
@@ -177,7 +124,7 @@ def test_abi_edge_cases():
     w.query_build()
     got = _cast(w, rays)
     rec = Q.records(w.get_bodies()["transforms"], scene, 33, 8)
-    _same_hits(got, Q.raycast(rec, 33, rays), "after set_counts")
+    _same_hits(got, CAST.cast(CAST.RAY, rec, 33, rays), "after set_counts")
     assert not ((got["shape"] == E.NH_SHAPE_BOX) & (got["collider"] >= 33)).any()
     assert not ((got["shape"] == E.NH_SHAPE_SPHERE) & (got["collider"] >= 8)).any()
     # ... and grows back
@@ -208,7 +155,7 @@ def test_any_hit_agrees_with_closest_hit_about_hit_or_miss(name):
         assert (anyh["t"][idx] <= rays["max_t"][idx]).all()
         for i in idx[:: max(1, len(idx) // 500)]:
             c = int(anyh["collider"][i]) + (0 if anyh["shape"][i] == E.NH_SHAPE_BOX else w.nbox)
-            one = Q.raycast(rec, w.nbox, rays[i:i + 1], only=c)[0]
+            one = CAST.cast(CAST.RAY, rec, w.nbox, rays[i:i + 1], only=c)[0]
             assert one.tobytes() == anyh[i].tobytes(), (kind, i)
     w.close()
 
@@ -218,33 +165,6 @@ def _query(w, rays_t, hits_t):
     w.query_build()
     w.raycast_records(rays_t, hits=hits_t)
     w.raycast_records(rays_t, any_hit=True, hits=hits_t)
-
-
-# what nh_read_counts reports of a context's history, not of its last step: tallies over its whole life, and the large colliders of the broadphase's last grid --
-# built whenever this context last had to (a context that rebuilt eight steps in a row searches directly for a while: same pairs, another grid)
-BY_HISTORY = ("large_colliders", "broadphase_rebuilds", "sort_reuses", "broadphase_inserts", "still_steps", "still_replays", "still_diff_key", "still_diff_count", "still_diff_feature",
-           "still_diff_escape", "asleep_steps", "ahead_steps", "fused_steps", "pair_steps", "pair_diag_roles", "pair_diag_record", "pair_diag_scale", "pair_diag_owned")
-
-
-def _same_stepped_world(a, b, what, history=True):
-    """history=False: for two contexts of different age, which can only agree about the last step."""
-    ba, bb = a.get_bodies(), b.get_bodies()
-    assert P.bits_equal(ba["transforms"], bb["transforms"]) and P.bits_equal(ba["momentum"], bb["momentum"]) and np.array_equal(ba["idle"], bb["idle"]), what
-    a.export_views(E.NH_VIEW_ALL)
-    b.export_views(E.NH_VIEW_ALL)
-    ka, kb = a.get_contacts(), b.get_contacts()
-    assert ka["count"] == kb["count"] and ka["data"].tobytes() == kb["data"].tobytes() and np.array_equal(ka["tags"], kb["tags"]), what
-    assert np.array_equal(ka["features"], kb["features"]) and np.array_equal(ka["bodies"], kb["bodies"]) and np.array_equal(ka["sleeping_pairs"], kb["sleeping_pairs"]), what
-    ca, cb = a.get_cache(), b.get_cache()
-    assert ca["count"] == cb["count"] and ca["data"].tobytes() == cb["data"].tobytes() and np.array_equal(ca["tags"], cb["tags"]), what
-    assert np.array_equal(a.get_active(), b.get_active()), what
-    na, nb = a.counts(), b.counts()
-    if not history:
-        na, nb = ({k: v for k, v in n.items() if k not in BY_HISTORY} for n in (na, nb))
-    assert na == nb, (what, na, nb)
-
-
-OBSERVED = {"pile": lambda: S.pile(256, 0, seed=1), "grid_tiles": lambda: S.grid_tiles(2, side=20, seed=2)}
 
 
 @pytest.mark.parametrize("name", sorted(OBSERVED))
@@ -334,6 +254,6 @@ def test_a_million_rays_on_the_landed_config_2_world():
     assert (~slab).mean() > 0.2
     # 1024 rays spread over the batch, bit for bit against the brute force over all 1,004,524 colliders
     pick = np.linspace(0, n - 1, 1024).astype(np.int64)
-    ref = Q.raycast(rec, w.nbox, rays[pick])
+    ref = CAST.cast(CAST.RAY, rec, w.nbox, rays[pick])
     _same_hits(got[pick], ref, "config 2, 1 M rays")
     w.close()

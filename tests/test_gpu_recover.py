@@ -16,7 +16,7 @@ import filter_util as F                      # noqa: E402
 import hostquery_util as Q                   # noqa: E402
 import hostrecover_util as HR                # noqa: E402
 import recover_batches as RB                 # noqa: E402
-from test_gpu_query import OBSERVED, SMALL, _same_stepped_world, _upload      # noqa: E402
+from query_util import OBSERVED, SMALL, same_stepped_world as _same_stepped_world, upload as _upload      # noqa: E402
 from nudge_amd import engine as E           # noqa: E402
 from nudge_amd import scenes as S           # noqa: E402
 

@@ -11,17 +11,14 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import hostboxcast_util as HB                # noqa: E402
 import hostcapsule_util as HC                # noqa: E402
+import hostcast_util as CAST                 # noqa: E402
 import hostpoint_util as HP                  # noqa: E402
 import hostquery_util as Q                   # noqa: E402
-import hostsweep_util as HS                  # noqa: E402
-import test_gpu_boxcast as TB                # noqa: E402
-import test_gpu_capsulecast as TC            # noqa: E402
 import test_gpu_closest as TP                # noqa: E402
 import test_gpu_overlap as TO                # noqa: E402
-import test_gpu_spherecast as TS             # noqa: E402
-from test_gpu_query import OBSERVED, SMALL, _bounds, _cast, _rays, _same_hits, _same_stepped_world, _upload      # noqa: E402
+from cast_util import boxes, capsules, closest as _cast, same_hits as _same_hits, spheres      # noqa: E402
+from query_util import OBSERVED, SMALL, bounds as _bounds, rays as _rays, records as _records, same_stepped_world as _same_stepped_world, unit_quats, upload as _upload      # noqa: E402
 from nudge_amd import engine as E           # noqa: E402
 from nudge_amd import scenes as S           # noqa: E402
 
@@ -29,10 +26,6 @@ pytestmark = pytest.mark.gpu
 
 NONE = 0xFFFFFFFF
 FUSED = E.NH_FLAG_SINGLE_APPLY | E.NH_FLAG_FUSED_STEP
-
-
-def _records(w, scene):
-    return Q.records(w.get_bodies()["transforms"], scene, w.nbox, w.nsph)
 
 
 def _batch(rng, n, rec):
@@ -44,20 +37,20 @@ def _batch(rng, n, rec):
     points = np.concatenate([TP._points(rng, n, rec, lo, hi, kind) for kind in ("inside", "uniform", "above")])
     return dict(
         rays=rays,
-        spheres=TS._casts(rays, rng.choice(np.float32(TS.RADII), size=m)),
-        boxes=TB._casts(rays, rng.choice(np.float32(TB.SIZES), size=m), TB._unit_quats(rng, m)),
-        capsules=TC._casts(rays, rng.choice(np.float32([0.05, 0.5, 1.0]), size=m), rng.choice(np.float32([0.0, 0.5, 2.0]), size=m), TC._unit_quats(rng, m)),
+        spheres=spheres(rays, rng.choice(np.float32((0.05, 0.5, 2.0)), size=m)),
+        boxes=boxes(rays, rng.choice(np.float32((0.05, 0.5, 2.0)), size=m), unit_quats(rng, m)),
+        capsules=capsules(rays, rng.choice(np.float32([0.05, 0.5, 1.0]), size=m), rng.choice(np.float32([0.0, 0.5, 2.0]), size=m), unit_quats(rng, m)),
         points=TP._queries(points, max_distance=rng.choice(np.float32([np.inf, 0.5, 2.0]), size=len(points))),
         overlaps=np.concatenate([TO._queries(rng, n, rec, kind) for kind in ("sphere", "box", "mixed")]),
-        capsule_overlaps=TC._capsule_queries(rng, n, rec))
+        capsule_overlaps=TO._capsule_queries(rng, n, rec))
 
 
 def _host(rec, nbox, b):
     """The brute-force answers to a batch over the records `rec`: what a build on those transforms must answer, byte for byte."""
     ov_off, _, ov_total = TO.O.overlap(rec, nbox, b["overlaps"], capacity=0)
     cap_off, _, cap_total = HC.overlap(rec, nbox, b["capsule_overlaps"], capacity=0)
-    return dict(rays=Q.raycast(rec, nbox, b["rays"]), spheres=HS.spherecast(rec, nbox, b["spheres"]), boxes=HB.boxcast(rec, nbox, b["boxes"]),
-                capsules=HC.capsulecast(rec, nbox, b["capsules"]), points=HP.closest(rec, nbox, b["points"]),
+    return dict(rays=CAST.cast(CAST.RAY, rec, nbox, b["rays"]), spheres=CAST.cast(CAST.SPHERE, rec, nbox, b["spheres"]), boxes=CAST.cast(CAST.BOX, rec, nbox, b["boxes"]),
+                capsules=CAST.cast(CAST.CAPSULE, rec, nbox, b["capsules"]), points=HP.closest(rec, nbox, b["points"]),
                 overlap_counts=ov_off, overlap_list=TO._host(rec, nbox, b["overlaps"], ov_total)[:2],
                 capsule_counts=cap_off, capsule_list=_capsule_host(rec, nbox, b["capsule_overlaps"], cap_total))
 
@@ -70,8 +63,8 @@ def _capsule_host(rec, nbox, queries, cap):
 
 def _gpu(w, b, ref):
     """The GPU's answers to the batch, in the layout of _host (list calls with the capacity of `ref`'s lists)."""
-    return dict(rays=_cast(w, b["rays"]), any_hit=_cast(w, b["rays"], any_hit=True), spheres=TS._sweep(w, b["spheres"]), boxes=TB._sweep(w, b["boxes"]),
-                capsules=TC._sweep(w, b["capsules"]), points=TP._closest(w, b["points"]),
+    return dict(rays=_cast(w, b["rays"]), any_hit=_cast(w, b["rays"], any_hit=True), spheres=_cast(w, b["spheres"]), boxes=_cast(w, b["boxes"]),
+                capsules=_cast(w, b["capsules"]), points=TP._closest(w, b["points"]),
                 overlap_counts=TO._gpu(w, b["overlaps"], None)[0], overlap_list=TO._gpu(w, b["overlaps"], len(ref["overlap_list"][1])),
                 capsule_counts=TO._gpu(w, b["capsule_overlaps"], None)[0], capsule_list=TO._gpu(w, b["capsule_overlaps"], len(ref["capsule_list"][1])))
 
@@ -166,7 +159,7 @@ def test_a_teleported_body_is_found_at_its_new_place_only():
     w.query_refit()
     rec = _records(w, scene)
     after = _cast(w, rays)
-    _same_hits(after, Q.raycast(rec, w.nbox, rays), "teleported")
+    _same_hits(after, CAST.cast(CAST.RAY, rec, w.nbox, rays), "teleported")
     assert after["body"][0] == body and after["body"][1] != body
     _check(w, rec, np.random.default_rng(711), 1024, "teleported, all types")
     w.close()
@@ -389,7 +382,7 @@ def test_a_refit_of_the_landed_config_2_world():
     q = np.concatenate([TP._queries(near, 2.0), TP._queries(TP._points(rng, k, rec, lo, hi, "uniform")), TP._queries(TP._points(rng, k, rec, lo, hi, "above")),
                         TP._queries(TP._points(rng, n - 3 * k, rec, lo, hi, "inside"), rng.choice(np.float32([np.inf, 0.0, 0.5]), size=n - 3 * k))])
     pick = np.linspace(0, n - 1, 2048).astype(np.int64)
-    ref_rays, ref_points = Q.raycast(rec, w.nbox, rays[pick]), HP.closest(rec, w.nbox, q[pick])
+    ref_rays, ref_points = CAST.cast(CAST.RAY, rec, w.nbox, rays[pick]), HP.closest(rec, w.nbox, q[pick])
     assert (ref_rays["shape"] != NONE).mean() > 0.3 and (ref_points["shape"] != NONE).mean() > 0.5
     hits, near_hits = _cast(w, rays), TP._closest(w, q)
     _same_hits(hits[pick], ref_rays, "config 2, 1 M rays after a refit")

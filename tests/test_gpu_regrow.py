@@ -10,7 +10,7 @@ import sys
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from test_gpu_query import FUSED, _same_stepped_world      # noqa: E402
+from query_util import FUSED, same_stepped_world as _same_stepped_world      # noqa: E402
 from nudge_amd import engine as E           # noqa: E402
 from nudge_amd import scenes as S           # noqa: E402
 

@@ -1,6 +1,6 @@
 """Sphere casts on the GPU (pytest -m gpu): nh_spherecast (include/nudge_hip.h, "scene queries").
 
-The oracle is a brute force over every collider on the host with the same arithmetic (nudge_amd/csrc/nh_query.h through tests/hostsweep_util.py) and
+The oracle is a brute force over every collider on the host with the same arithmetic (nudge_amd/csrc/nh_query.h through tests/hostcast_util.py) and
 the header's exact rules, so the tree's answer must equal it bit for bit in every field.  Radius 0 must give nh_raycast's bytes, a start ball that
 nh_overlap finds touching something must hit at t = 0, and casts are observers like the other queries."""
 import ctypes as C
@@ -11,35 +11,16 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import hostcast_util as CAST                 # noqa: E402
 import hostquery_util as Q                   # noqa: E402
-import hostsweep_util as W                   # noqa: E402
-from test_gpu_query import OBSERVED, SMALL, _bounds, _rays, _same_stepped_world, _upload      # noqa: E402
+from cast_util import closest as _sweep, degenerate_worlds, far_and_near, same_hits as _same_hits, slide_past, spheres as _casts      # noqa: E402
+from query_util import FUSED, NONE, OBSERVED, SMALL, bounds as _bounds, mat, rays as _rays, same_stepped_world as _same_stepped_world, upload as _upload      # noqa: E402
 from nudge_amd import engine as E           # noqa: E402
 from nudge_amd import scenes as S           # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-NONE = 0xFFFFFFFF
-FUSED = E.NH_FLAG_SINGLE_APPLY | E.NH_FLAG_FUSED_STEP
 RADII = (0.05, 0.5, 2.0)
-
-
-def _casts(rays, radius):
-    c = np.zeros(len(rays), dtype=E.SPHERE_CAST)
-    for k in ("origin", "max_t", "direction", "ignore_body"):
-        c[k] = rays[k]
-    c["radius"] = radius
-    return c
-
-
-def _sweep(w, casts, any_hit=False):
-    raw = w.spherecast_records(_upload(w, casts), any_hit=any_hit)
-    return np.frombuffer(raw.cpu().numpy().tobytes(), dtype=E.RAY_HIT).copy()
-
-
-def _same_hits(got, ref, what):
-    bad = (got.view(np.uint8).reshape(-1, 32) != ref.view(np.uint8).reshape(-1, 32)).any(axis=1)
-    assert not bad.any(), f"{what}: {int(bad.sum())} of {len(ref)} hit records differ, first at {int(np.argmax(bad))}"
 
 
 def _check_world(w, scene, rng, n, what, radii=RADII):
@@ -50,7 +31,7 @@ def _check_world(w, scene, rng, n, what, radii=RADII):
     for kind in ("random", "axis", "down"):
         for r in radii:
             casts = _casts(_rays(rng, n, lo, hi, kind), r)
-            ref = W.spherecast(rec, w.nbox, casts)
+            ref = CAST.cast(CAST.SPHERE, rec, w.nbox, casts)
             _same_hits(_sweep(w, casts), ref, f"{what} / {kind} / r {r}")
             share.append(float((ref["shape"] != NONE).mean()))
     return share
@@ -68,42 +49,17 @@ def test_sphere_casts_equal_the_brute_force_before_and_after_stepping(name):
 
 
 def test_degenerate_worlds():
-    scene = S.pile(4, 0, seed=3)
-    w = E.World(scene, flags=FUSED)
-    w.set_counts(len(scene["body_transforms"]), 1, 0)          # the ground slab alone (body 0)
     rng = np.random.default_rng(21)
-    _check_world(w, scene, rng, 4096, "one collider")
-    w.close()
-
-    scene = S.pile(300, 300, seed=3)
-    nb = len(scene["body_transforms"])
-    w = E.World(scene, flags=FUSED)
-    w.set_counts(nb, 0, 300)
-    _check_world(w, scene, rng, 8192, "spheres only")
-    w.set_counts(nb, 301, 0)
-    _check_world(w, scene, rng, 8192, "boxes only")
-    w.close()
-
-    scene = S.pile(4096, 0, seed=3)
-    scene["body_transforms"]["position"][1:] = (0.25, 3.0, -0.5)        # every Morton key equal but the ground's
-    w = E.World(scene, flags=FUSED)
-    _check_world(w, scene, rng, 8192, "4096 coincident boxes")
-    w.close()
+    degenerate_worlds(_check_world, rng, 4096, 8192, 8192)
 
     scene = S.pile(2000, 1000, seed=3)
-    nb = len(scene["body_transforms"])
-    small = rng.random(nb) < 0.5
-    pos = np.where(small[:, None], rng.uniform(-0.05, 0.05, size=(nb, 3)), rng.uniform(-1e4, 1e4, size=(nb, 3))).astype(np.float32)
-    scene["body_transforms"]["position"][1:] = pos[1:]
-    bsmall = small[scene["box_transforms"]["body"][1:]]
-    scene["box_data"]["size"][1:] = np.where(bsmall[:, None], np.float32(1e-3), np.float32(30.0))
-    scene["sphere_data"]["radius"] = np.where(small[scene["sphere_transforms"]["body"]], np.float32(1e-3), np.float32(25.0))
+    far_and_near(scene, rng)
     w = E.World(scene, flags=FUSED)
     _check_world(w, scene, rng, 16384, "1e-3 .. 1e4", radii=(1e-4, 0.01, 5.0, 100.0))
     rec = Q.records(w.get_bodies()["transforms"], scene)
     for r in (1e-4, 0.01, 0.05):
         casts = _casts(_rays(rng, 16384, (-0.05,) * 3, (0.05,) * 3, "random"), r)
-        _same_hits(_sweep(w, casts), W.spherecast(rec, w.nbox, casts), f"small cluster r {r}")
+        _same_hits(_sweep(w, casts), CAST.cast(CAST.SPHERE, rec, w.nbox, casts), f"small cluster r {r}")
     w.close()
 
 
@@ -119,17 +75,13 @@ def test_grazing_casts_beside_resting_boxes():
     offs = [0.0] + [s * 10.0 ** e for e in range(-8, -1) for s in (-1.0, 1.0)]
     casts = []
     for k, c in enumerate(boxes):
-        p, q, h = rec["p"][c].astype(np.float64), rec["q"][c].astype(np.float64), rec["h"][c].astype(np.float64)
-        x, y, z, s = q
-        R = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - s * z), 2 * (x * z + s * y)], [2 * (x * y + s * z), 1 - 2 * (x * x + z * z), 2 * (y * z - s * x)],
-                      [2 * (x * z - s * y), 2 * (y * z + s * x), 1 - 2 * (x * x + y * y)]])
+        p, h = rec["p"][c].astype(np.float64), rec["h"][c].astype(np.float64)
+        R = mat(rec["q"][c])
         for r in (0.05, 0.3):
             for off in offs:
                 a, b = k % 3, (k + 1) % 3                    # slide along axis a past the face of axis b, and across the edge (a, b) at 45 degrees
                 for sb in (-1.0, 1.0):
-                    ol, dl = np.zeros(3), np.zeros(3)
-                    ol[a], ol[b], dl[a] = -(h[a] + r + 2.0), sb * (h[b] + r + off), 1.0
-                    casts.append((p + R @ ol, R @ dl, r))
+                    casts.append((*slide_past(p, R, h, (r, r, r), a, b, sb, off), r))
                     e = np.zeros(3)
                     e[a], e[b] = h[a], sb * h[b]
                     nrm = np.zeros(3)
@@ -146,7 +98,7 @@ def test_grazing_casts_beside_resting_boxes():
     c["radius"] = [r for _, _, r in casts]
     c["max_t"] = np.inf
     c["ignore_body"] = NONE
-    ref = W.spherecast(rec, w.nbox, c)
+    ref = CAST.cast(CAST.SPHERE, rec, w.nbox, c)
     _same_hits(_sweep(w, c), ref, "grazing")
     assert (ref["shape"] != NONE).mean() > 0.1          # (in a stack most casts that pass one box go on to touch its neighbours)
     w.close()
@@ -165,8 +117,7 @@ def test_radius_zero_equals_the_ray_cast(name):
         rays = _rays(rng, 32768, lo, hi, kind)
         rays["max_t"][::3] = 7.0
         rays["ignore_body"][::5] = rng.integers(0, 64, size=len(rays[::5]))
-        raw = w.raycast_records(_upload(w, rays))
-        ray_hits = np.frombuffer(raw.cpu().numpy().tobytes(), dtype=E.RAY_HIT)
+        ray_hits = _sweep(w, rays)
         _same_hits(_sweep(w, _casts(rays, 0.0)), ray_hits, f"{name} / {kind}: radius 0 against nh_raycast")
     w.close()
 
@@ -191,7 +142,7 @@ def test_a_start_ball_that_overlaps_hits_at_zero(name):
     touching = np.diff(ov["offsets"].cpu().numpy()) > 0
     assert touching.mean() > 0.05, touching.mean()
     assert (got["t"][touching] == 0.0).all() and (got["shape"][touching] != NONE).all()
-    _same_hits(got, W.spherecast(rec, w.nbox, casts), f"{name} start balls")
+    _same_hits(got, CAST.cast(CAST.SPHERE, rec, w.nbox, casts), f"{name} start balls")
     w.close()
 
 
@@ -217,7 +168,7 @@ def test_any_hit_agrees_with_closest_hit_about_hit_or_miss(name):
         assert (anyh["t"][idx] <= casts["max_t"][idx]).all()
         for i in idx[:: max(1, len(idx) // 500)]:
             c = int(anyh["collider"][i]) + (0 if anyh["shape"][i] == E.NH_SHAPE_BOX else w.nbox)
-            one = W.spherecast(rec, w.nbox, casts[i:i + 1], only=c)[0]
+            one = CAST.cast(CAST.SPHERE, rec, w.nbox, casts[i:i + 1], only=c)[0]
             assert one.tobytes() == anyh[i].tobytes(), (kind, i)
     w.close()
 
@@ -330,5 +281,5 @@ def test_a_million_sphere_casts_on_the_landed_config_2_world():
     assert (~slab).mean() > 0.2
     # 1024 casts spread over the batch, bit for bit against the brute force over all 1,004,524 colliders
     pick = np.linspace(0, n - 1, 1024).astype(np.int64)
-    _same_hits(got[pick], W.spherecast(rec, w.nbox, casts[pick]), "config 2, 1 M sphere casts")
+    _same_hits(got[pick], CAST.cast(CAST.SPHERE, rec, w.nbox, casts[pick]), "config 2, 1 M sphere casts")
     w.close()

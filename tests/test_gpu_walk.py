@@ -18,7 +18,7 @@ from hostmover_util import CAPSULE as HW     # noqa: E402
 from mover_util import (FUSED, NONE, SENTINEL, capsulecast as _capsulecast, move as _move, records as _records, same as _same,      # noqa: E402
                         terrain_world as _terrain_world, walk as _walk)
 from test_cpu_walk import BALL_PIT_SHARES, RESTING, TERRAIN_SEED, TERRAIN_SHARES, WORLD_SEED, WORLD_SHARES, check_shares      # noqa: E402
-from test_gpu_query import OBSERVED, SMALL, _same_stepped_world, _upload      # noqa: E402
+from query_util import OBSERVED, SMALL, same_stepped_world as _same_stepped_world, upload as _upload      # noqa: E402
 from nudge_amd import engine as E           # noqa: E402
 from nudge_amd import scenes as S           # noqa: E402
 

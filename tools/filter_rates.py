@@ -155,6 +155,7 @@ def main():
     checked = 0
     if not a.no_check:
         import filter_util as F
+        import hostcast_util as CAST
         import hostpoint_util as HP
         import hostquery_util as Q
         rec = Q.records(w.get_bodies()["transforms"], scene)
@@ -170,7 +171,7 @@ def main():
             for m in np.unique(mvals):
                 sel = mvals == m
                 world_m = rec if flt is None else F.masked(rec, words, m)
-                assert got_r[sel].tobytes() == Q.raycast(world_m, w.nbox, rays[pick][sel]).tobytes(), f"{way}: rays differ from the brute force"
+                assert got_r[sel].tobytes() == CAST.cast(CAST.RAY, world_m, w.nbox, rays[pick][sel]).tobytes(), f"{way}: rays differ from the brute force"
                 assert got_p[sel].tobytes() == HP.closest(world_m, w.nbox, points[pick][sel]).tobytes(), f"{way}: closest points differ from the brute force"
                 checked += 2 * int(sel.sum())
         w.query_filter(None)
