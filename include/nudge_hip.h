@@ -79,7 +79,7 @@
  *      exported the views: nh_set_option(ctx, "sync_exports_views", 1) restores that contract at its old price; INTEGRATION.md.)  Any entry point outside the sample's
  *      call order between nh_collide and nh_apply_impulses turns a still step into a full one first, so everything it observes is what a full step
  *      produces.  nh_Counts.still_steps / still_replays count them.
- *      The scene queries (nh_query_build, nh_query_refit, nh_raycast, nh_spherecast, nh_raycast_all, nh_spherecast_all, nh_boxcast_all, nh_capsulecast_all, nh_raycast_k, nh_spherecast_k, nh_boxcast_k, nh_capsulecast_k, nh_boxcast, nh_capsulecast, nh_overlap, nh_penetration, nh_region, nh_closest, nh_closest_k, nh_distance, nh_move, nh_recover, nh_walk, nh_boxmove, nh_boxwalk, nh_query_set_layers, nh_query_filter, nh_query_layer_info) are not entry points of the step in this sense: they neither export nor settle nor turn a still step into a
+ *      The scene queries (nh_query_build, nh_query_refit, nh_raycast, nh_spherecast, nh_raycast_all, nh_spherecast_all, nh_boxcast_all, nh_capsulecast_all, nh_raycast_k, nh_spherecast_k, nh_boxcast_k, nh_capsulecast_k, nh_boxcast, nh_capsulecast, nh_overlap, nh_penetration, nh_region, nh_closest, nh_closest_k, nh_distance, nh_move, nh_recover, nh_walk, nh_boxmove, nh_boxwalk, nh_move_touched, nh_boxmove_touched, nh_walk_touched, nh_boxwalk_touched, nh_query_set_layers, nh_query_filter, nh_query_layer_info) are not entry points of the step in this sense: they neither export nor settle nor turn a still step into a
  *      full one, and they do not count -- see "scene queries" below.
  *
  * Threading: one context = one HIP stream = one world at a time; no global mutable state.
@@ -436,6 +436,8 @@ int nh_query_stats(nh_context* ctx, nh_QueryStats* out);
        NH_RAY_ANY_HIT the guarantee is the same hit-or-miss, which is all that flag promises.
      - Everything else composes with the filter exactly as without it: `ignore_body`, NaN poses, invalid records, NH_RAY_ANY_HIT, capacities, counts and
        offsets, the tie rules, the reach rule.  The answers above are defined without the tree, so pruning by node words changes the work, never the bytes.
+     - The four _touched forms of the movers (nh_move_touched, nh_boxmove_touched, nh_walk_touched, nh_boxwalk_touched) run their mover's casts under the same
+       contract: results, counts and touches are those of the plain mover's casts on the masked world.
    Identities that follow:
      - mask 0 sees nothing: misses with t = max_t (max_distance), empty segments, counts 0;
      - all-ones layers (or none set) with any non-zero mask write the filter-off bytes;
@@ -942,8 +944,8 @@ int nh_distance(nh_context* ctx, const nh_DistanceQuery* queries, uint32_t count
    allocates, never waits: ONE launch on the context's stream (timing label q_move).  An OBSERVER like nh_capsulecast (note 9): no view export, no
    settling of deferred gravity, no still step turned into a full one, no change to nh_Counts.
    NOT BUILT: rotation during the move (boxes move by nh_boxmove, below); gravity (step-up, ground snapping and slope limits are nh_walk, below; depenetration of a move that
-   starts in overlap is nh_recover, below: recover, then move or walk); moving platforms (the velocity of what is hit); pushing dynamic bodies (queries are observers); the list of everything
-   touched (last_hit is the last cast's record only).
+   starts in overlap is nh_recover, below: recover, then move or walk); moving platforms (the velocity of what is hit); pushing dynamic bodies (queries are observers; what
+   the move touched is listed by nh_move_touched, below).
    Cost: one lane per move, up to max_slides + 1 walks of nh_capsulecast's; a lane that has finished waits for the slowest of its wave.  Measured (one
    MI355X, the landed config-2 world of 1,004,524 colliders, 1,048,576 moves of r = hh = 0.5 from just above resting bodies by 0.75 - 3 units, max_slides 4;
    tools/move_rates.py -> profiles/move_rates.log): 1.90 ms beside 1.14 ms for nh_capsulecast on the first casts alone; the moves made 1.61 casts
@@ -1058,8 +1060,8 @@ int nh_recover(nh_context* ctx, const nh_Recover* queries, uint32_t count, nh_Re
    Returns NH_ERR_INVALID before any nh_query_build, for flags != 0, for count >= 2^30, and for count > 0 with `walks` or `results` null or not 16-byte
    aligned; count = 0 is a no-op that returns NH_OK and launches nothing.  Every byte of `count` results is written and nothing behind them.  Never
    allocates, never waits: ONE launch on the context's stream (timing label q_walk).  An OBSERVER like nh_move (note 9).
-   NOT BUILT: rotation during the walk (boxes walk by nh_boxwalk, below); moving platforms (the velocity of what is stood on); pushing dynamic bodies (queries are observers);
-   the list of everything touched (last_hit and ground are single records); gravity integration and velocities (the caller passes a displacement); a
+   NOT BUILT: rotation during the walk (boxes walk by nh_boxwalk, below); moving platforms (the velocity of what is stood on); pushing dynamic bodies (queries are observers;
+   last_hit and ground are single records: what the walk touched is listed by nh_walk_touched, below); gravity integration and velocities (the caller passes a displacement); a
    per-node AND word for the filter; queries on partitioned worlds; the `namespace nudge` extension in nudge_amd/compat; any change to nh_move's crease rule.
    Cost: one lane per walk, up to 21 walks of nh_capsulecast's; the lanes of a wave walk the tree together whatever phase each is in, and a lane that has
    finished waits for the slowest of its wave.  168 VGPRs at 3 waves per SIMD, no scratch (4 waves would spill 132 - 144 bytes per lane).  Measured (one
@@ -1112,7 +1114,7 @@ int nh_walk(nh_context* ctx, const nh_Walk* walks, uint32_t count, nh_WalkResult
    Never allocate, never wait: ONE launch each on the context's stream (timing labels q_boxmove, q_boxwalk).  OBSERVERS like nh_move (note 9).
    WHAT A BOX STANDS ON: its bottom face.  A box that stands on a slope meets it with an edge; the ground normal is still the slope's (the sweep's
    separating axis), so WALKABLE and the climb rule mean what they mean for a capsule.  A step is climbed when the whole bottom face clears the riser.
-   NOT BUILT: rotation during a move; moving platforms; pushing dynamic bodies; the list of everything touched; a change to the crease rule; the
+   NOT BUILT: rotation during a move; moving platforms; pushing dynamic bodies; a change to the crease rule; the
    `namespace nudge` extension; queries on partitioned worlds; sphere movers as a call of their own (half_height = 0 in nh_move is one).
    Cost: one lane per record around the box-box sweep, the heaviest leaf test of the library, instantiated once per kernel.  Registers on gfx950 (hipcc
    -Rpass-analysis=kernel-resource-usage): k_q_move<box> 146 VGPRs (147 filtered) at 3 waves per SIMD, no scratch -- asked for nh_move's 4
@@ -1137,6 +1139,67 @@ typedef struct nh_BoxWalk { float origin[3]; float skin; float displacement[3]; 
                             uint32_t options; uint32_t reserved2; } nh_BoxWalk;                                  /* 96 B  = nh_Walk's tail behind nh_BoxMove */
 int nh_boxmove(nh_context* ctx, const nh_BoxMove* moves, uint32_t count, nh_MoveResult* results, uint32_t flags /* 0 */);
 int nh_boxwalk(nh_context* ctx, const nh_BoxWalk* walks, uint32_t count, nh_WalkResult* results, uint32_t flags /* 0 */);
+
+/* nh_move_touched, nh_boxmove_touched, nh_walk_touched, nh_boxwalk_touched: the four movers, and beside each result THE LIST OF EVERYTHING THE MOVER
+   TOUCHED -- what a controller needs to push the crate it slid into, fire a trigger, play the footstep of the right material, ride the lift it stands on.
+   last_hit and ground are single records: a capsule that slides along the floor into a crate and then along a wall reports the wall only.  The list used to
+   take the REPLAY identity run from the host, one cast call and one round trip per round; the kernels hold every hit in registers when it is taken, and these
+   calls let it out, in ONE launch each.
+   DEFINITION: each call is its plain mover word for word -- the same rules, the same casts, the same layer filter with the record's index as the per-query
+   mask index -- and `results` receives byte for byte what the plain call writes.  Every cast the mover makes whose answer is a HIT -- a collider, whether
+   taken with t > 0 or a start overlap with t == 0 -- produces one TOUCH, in the order the casts are made.  A miss touches nothing; an invalid cast from an
+   overflowed position touches nothing.  The fields of a touch:
+     hit                 the nh_RayHit of that cast, written by the routine that writes last_hit;
+     origin, direction   the p and v the cast was made from and along (rule 2 of the move): the bits the state held before the advance;
+     phase               NH_TOUCH_SLIDE for every cast of a move; for a walk the phase the cast was asked for in: A and its blocked form give SLIDE, U gives
+                         UP, F gives FORWARD, D gives DOWN, C gives PROBE;
+     cast                how many casts the record had made before this one: nh_WalkResult.casts before its increment; for a move, the round.
+   counts[i] is the number of touches of record i WHATEVER k IS: at most NH_MOVE_MAX_SLIDES + 1 (9) for a move, NH_WALK_MAX_CASTS (21) for a walk.  Touch j
+   of record i goes to touches[(size_t)i * k + j] for j < min(counts[i], k): all 64 bytes, the first k in order.  THE SLOTS BEHIND THOSE ARE NOT WRITTEN --
+   the one place where the query calls' habit "every byte is written" is broken, on purpose: a million walks at k = 21 would otherwise store 1.3 GB of
+   nothing.  Read counts[i] before touches: a slot at or behind it holds whatever the memory held.  An INVALID record writes the plain call's result,
+   counts[i] = 0 and no touch.
+   WHAT A WALK LISTS is everything it probed, kept or not; the result's flags tell kept from abandoned.  With NH_WALK_STEPPED set, UP, FORWARD and DOWN are
+   the path taken and SLIDE holds what blocked it; without it, SLIDE and PROBE are the path and UP, FORWARD and DOWN are an attempt that was abandoned.  A
+   small k can fill up with SLIDE touches before the kept ones arrive: counts[i] > k tells, and k = the maximum never loses one.
+   IDENTITIES (contracts):
+     T1. `results` holds byte for byte what the plain call writes for the same records, under every filter mode, after nh_query_refit as after a build;
+     T2. REPLAY per touch: `hit` is byte for byte what the shape's closest-hit cast with flags 0 (nh_capsulecast, nh_boxcast) writes for { origin, 1.0f,
+         direction, ignore_body, rotation, the shape } under the record's mask; half height 0 and size (0, 0, 0) follow the sphere's and the ray's rules as in
+         the plain calls;
+     T3. for a move, counts == slides + (flags & NH_MOVE_START_OVERLAP ? 1 : 0) and touch j has cast == j; where last_hit is a collider, the last touch's
+         hit is last_hit;
+     T4. for a walk, counts <= casts; `cast` is strictly ascending and < casts; `phase` never decreases; the touches with t > 0 of the kept slide (FORWARD if
+         STEPPED, else SLIDE) number `slides`; with STEPPED the last DOWN touch's hit is `ground`; without it, where `ground` is a collider, the PROBE
+         touch's hit is `ground`;
+     T5. a smaller k writes the same counts, and the first min(counts, k) touches hold the same bytes.
+   All four return NH_ERR_INVALID, in nh_move's order, before any nh_query_build, for flags != 0, for count >= 2^30, for k == 0 or k above 9 (the two moves)
+   or 21 (the two walks), and for count > 0 with any of the four pointers null, the records, `results` or `touches` not 16-byte aligned, or `counts` not
+   4-byte aligned; count = 0 is a no-op that returns NH_OK and launches nothing.  A refused call writes nothing.  Never allocate, never wait: ONE launch
+   each on the context's stream (timing labels q_move_touched, q_boxmove_touched, q_walk_touched, q_boxwalk_touched).  OBSERVERS like nh_move (note 9).
+   NOT BUILT: touches de-duplicated per body; a contact point (the casts return none: origin + t * direction is where the SHAPE's centre was); touches for
+   nh_recover; pushing dynamic bodies and moving platforms inside the library (queries are observers: INTEGRATION.md, "touched", has the caller's recipe).
+   Cost: the mover's cost, and per touch four 16-byte stores (64 B) beside the tree walk of its cast, per record one 4-byte count; the lane holds the slot
+   pointer, k and the count across the sweep.  Registers on gfx950 (hipcc -Rpass-analysis=kernel-resource-usage): the
+   touched capsule move 128 VGPRs at 4 waves per SIMD and the touched box move 150 (151 filtered) at 3, their plain siblings' occupancy; the touched box walk
+   198 (199 filtered) at 2, its sibling's; the touched capsule walk 182 (183 filtered) at 2 waves where nh_walk runs at 3 -- asked for 3 it spills 20 - 28
+   bytes per lane.  None has scratch.  The eight plain instantiations are unchanged: 128 at 4, 146 / 147 at 3, 168 at 3, 194 / 195 at 2.
+   Measured (one MI355X, one run, the landed config-2 world of 1,004,524 colliders, 1,048,576 records, max_slides 4, the workloads of move_rates, walk_rates
+   and boxmove_rates, the library's kernel timers, medians of 7 blocks of 10 calls; tools/touched_rates.py -> profiles/touched_rates.log), the
+   touched call at k = the maximum over the plain call per block: nh_move_touched 2.311 ms beside 2.307 ms, 1.002 (1.000 .. 1.010), 0.51 touches per move;
+   nh_boxmove_touched 1.378 beside 1.363 ms, 1.008 (1.005 .. 1.012), 0.38 touches; nh_boxwalk_touched (step_height 1.0) 5.159 beside 5.123 ms, 1.006 (1.000 ..
+   1.009), 1.39 touches per walk; nh_walk_touched (step_height 1.0) 6.396 beside 4.705 ms, 1.360 (1.353 .. 1.364), 1.29 touches per walk: the one kernel that
+   gave up a wave.  k = 4 measures the same within 0.4 %: on these workloads at most 3 in 10,000 records have more than four touches.  The four plain movers
+   beside the parent commit's library loaded twice in the same process, this / parent with parent / parent beside it: nh_move 1.000 (0.991 .. 1.005) beside
+   1.001 (0.994 .. 1.009), nh_boxmove 1.001 (0.994 .. 1.005) beside 0.999 (0.992 .. 1.004), nh_walk 1.001 (0.994 .. 1.004) beside 0.999 (0.994 .. 1.002),
+   nh_boxwalk 1.000 (0.997 .. 1.007) beside 1.001 (0.999 .. 1.002): every median inside the parent's own spread.  NOT MEASURED YET: the filtered
+   instantiations' times; the touched capsule walk at 3 waves (it was compiled, not run); workloads where most records touch many colliders. */
+enum { NH_TOUCH_SLIDE = 0u, NH_TOUCH_UP = 1u, NH_TOUCH_FORWARD = 2u, NH_TOUCH_DOWN = 3u, NH_TOUCH_PROBE = 4u };   /* nh_Touch.phase: nh_walk's A, U, F, D, C */
+typedef struct nh_Touch { nh_RayHit hit; float origin[3]; uint32_t phase; float direction[3]; uint32_t cast; } nh_Touch;   /* 64 B */
+int nh_move_touched   (nh_context* ctx, const nh_Move* moves,    uint32_t count, nh_MoveResult* results, uint32_t k, uint32_t* counts, nh_Touch* touches, uint32_t flags /* 0 */);
+int nh_boxmove_touched(nh_context* ctx, const nh_BoxMove* moves, uint32_t count, nh_MoveResult* results, uint32_t k, uint32_t* counts, nh_Touch* touches, uint32_t flags /* 0 */);
+int nh_walk_touched   (nh_context* ctx, const nh_Walk* walks,    uint32_t count, nh_WalkResult* results, uint32_t k, uint32_t* counts, nh_Touch* touches, uint32_t flags /* 0 */);
+int nh_boxwalk_touched(nh_context* ctx, const nh_BoxWalk* walks, uint32_t count, nh_WalkResult* results, uint32_t k, uint32_t* counts, nh_Touch* touches, uint32_t flags /* 0 */);
 
 /* ---- multi-GPU: one x-slab of a world per context ------------------------------------------------------------------------------------
    The world is cut into slabs along x, one rank (process, GPU, nh_context) per slab [lo, hi).  A rank's arrays hold

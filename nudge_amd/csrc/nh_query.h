@@ -1492,6 +1492,15 @@ NH_HD void nh_q_walk_advance(nh_QWalk& s, const nh_QWalkIn& W, bool hit, float t
 	if (!nh_q_move_advance2(s.m, hit, t, n, ns, W.skin, nh_q_walk_slides(s, W))) nh_q_walk_phase_end(s, W);
 }
 
+// nh_Touch.phase of a cast asked for in the walk's phase `phase` (nh_walk_touched; the header's NH_TOUCH_*, which nh_query.hip asserts): A and its blocked
+// form AB are SLIDE, then U, F, D, C in order.  A move's casts are all SLIDE.
+#define NH_Q_TOUCH_SLIDE 0u
+#define NH_Q_TOUCH_UP 1u
+#define NH_Q_TOUCH_FORWARD 2u
+#define NH_Q_TOUCH_DOWN 3u
+#define NH_Q_TOUCH_PROBE 4u
+NH_HD uint32_t nh_q_walk_touch_phase(uint32_t phase) { return phase <= NH_Q_WALK_AB ? NH_Q_TOUCH_SLIDE : phase - 1u; }
+
 // ---- recover (nh_recover): push a shape out of what it overlaps, the state between two overlap walks -------------------------------------------------
 // These functions ARE the definition of nh_recover (include/nudge_hip.h): k_q_recover and the host's brute force (tests/hostoracle/hostrecover.cpp) both run
 //     s = nh_q_recover_begin(center);

@@ -383,10 +383,35 @@ template <> struct nh_QMover<nh_QBox> {
 template <class Shape> constexpr int nh_q_move_waves(bool) { return 4; }
 template <> constexpr int nh_q_move_waves<nh_QBox>(bool filter) { return filter ? NH_Q_BOXMOVE_WAVES_FILTER : NH_Q_BOXMOVE_WAVES; }
 
-template <class Shape, bool FILTER>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(nh_q_move_waves<Shape>(FILTER)))) void k_q_move(const typename nh_QMover<Shape>::Move* __restrict__ moves, uint32_t count,
+// ---- touched ----------------------------------------------------------------------------------------------------------------------------------
+// nh_move_touched and kin (TOUCHED = true of k_q_move and k_q_walk): the mover's own loop, and behind every cast that found a collider one nh_Touch, written
+// while the state still holds the cast's origin and direction -- before the advance.  A lane owns the k slots touches[i * k ..] (a size_t index: count * k
+// passes 2^32), fills them in cast order with four 16-byte stores each (nh_q_write_hit for the first two) and counts on where they are full; slots behind
+// the count are never written (header, "nh_move_touched").  TOUCHED = false compiles none of it: k, counts and touches are then not read.
+static_assert(NH_Q_TOUCH_SLIDE == NH_TOUCH_SLIDE && NH_Q_TOUCH_UP == NH_TOUCH_UP && NH_Q_TOUCH_FORWARD == NH_TOUCH_FORWARD && NH_Q_TOUCH_DOWN == NH_TOUCH_DOWN &&
+              NH_Q_TOUCH_PROBE == NH_TOUCH_PROBE, "nh_query.h's touch phases are the header's");
+static_assert(sizeof(nh_Touch) == 64 && offsetof(nh_Touch, origin) == 32 && offsetof(nh_Touch, phase) == 44 && offsetof(nh_Touch, direction) == 48 && offsetof(nh_Touch, cast) == 60,
+              "nh_Touch is nh_RayHit and two 16-byte words");
+__device__ __forceinline__ void nh_q_write_touch(nh_Touch* __restrict__ touch, const nh_QRec* __restrict__ rec, uint32_t nbox, uint32_t c, float t, nh_f3 n, nh_f3 o, nh_f3 d,
+                                                 uint32_t phase, uint32_t cast) {
+	nh_q_write_hit(&touch->hit, rec, nbox, true, c, t, n);
+	float4* tp = reinterpret_cast<float4*>(touch);
+	tp[2] = make_float4(o.x, o.y, o.z, __uint_as_float(phase));
+	tp[3] = make_float4(d.x, d.y, d.z, __uint_as_float(cast));
+}
+// waves per SIMD asked for by the TOUCHED moves: their plain siblings' (the count and the slot address are held across the sweep: 128 VGPRs still for the capsule,
+// 150 / 151 for the box, no scratch; the register table is DESIGN 10.20)
+#ifndef NH_Q_MOVE_TOUCHED_WAVES
+#define NH_Q_MOVE_TOUCHED_WAVES 4
+#endif
+template <class Shape> constexpr int nh_q_move_waves(bool filter, bool touched) { return touched ? NH_Q_MOVE_TOUCHED_WAVES : nh_q_move_waves<Shape>(filter); }
+template <> constexpr int nh_q_move_waves<nh_QBox>(bool filter, bool) { return nh_q_move_waves<nh_QBox>(filter); }
+
+template <class Shape, bool FILTER, bool TOUCHED>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(nh_q_move_waves<Shape>(FILTER, TOUCHED)))) void k_q_move(const typename nh_QMover<Shape>::Move* __restrict__ moves, uint32_t count,
                                                    nh_MoveResult* __restrict__ results,
-                                                   const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox, nh_QFilter F) {
+                                                   const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox, nh_QFilter F,
+                                                   uint32_t k_touches, uint32_t* __restrict__ counts, nh_Touch* __restrict__ touches) {
 	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
 		const float4* mp = reinterpret_cast<const float4*>(moves + i);
 		const float4 m0 = mp[0], m1 = mp[1], m2 = mp[2], m3 = mp[3];
@@ -399,18 +424,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(nh_q_move_w
 		uint32_t bc = NH_Q_NONE;
 		nh_f3 bn = nh_make3(0.0f, 0.0f, 0.0f);
 		bool ok = valid;
+		uint32_t touched = 0u;
 		for (uint32_t round = 0u; round <= NH_MOVE_MAX_SLIDES; ++round) {
 			if (!valid || !nh_q_move_go(s)) break;
 			Shape k;
 			k.set(make_float4(s.p.x, s.p.y, s.p.z, 1.0f), make_float4(s.v.x, s.v.y, s.v.z, m1.w), m2, m3);
 			nh_q_cast_one<FILTER>(k, nodes, rec, n, nbox, 0u, F, fm, bt, bc, bn);
 			ok = k.ok;
+			if (TOUCHED && bc != NH_Q_NONE) {
+				if (touched < k_touches) nh_q_write_touch(touches + ((size_t)i * k_touches + touched), rec, nbox, bc, bt, bn, s.p, s.v, NH_TOUCH_SLIDE, round);
+				++touched;
+			}
 			if (!nh_q_move_advance(s, bc != NH_Q_NONE, bt, bn, skin, max_slides)) break;
 		}
 		float4* out = reinterpret_cast<float4*>(results + i);
 		out[0] = make_float4(s.p.x, s.p.y, s.p.z, __uint_as_float(valid ? s.flags : (uint32_t)NH_MOVE_INVALID));
 		out[1] = make_float4(s.v.x, s.v.y, s.v.z, __uint_as_float(s.slides));
 		nh_q_write_hit(&results[i].last_hit, rec, nbox, ok, bc, bt, bn);
+		if (TOUCHED) counts[i] = touched;
 	}
 }
 
@@ -443,11 +474,20 @@ static_assert(sizeof(nh_Walk) == 96 && sizeof(nh_WalkResult) == 112 && offsetof(
 #endif
 template <class Shape> constexpr int nh_q_walk_waves(bool) { return NH_Q_WALK_WAVES; }
 template <> constexpr int nh_q_walk_waves<nh_QBox>(bool filter) { return filter ? NH_Q_BOXWALK_WAVES_FILTER : NH_Q_BOXWALK_WAVES; }
+// (The TOUCHED capsule walk holds the touch count across the sweep on top of nh_walk's 168 VGPRs: asked for nh_walk's 3 waves the compiler spills 20 / 28 bytes
+// per lane (filter off / on); at 2 waves it keeps everything in registers.  The box walk is at 2 waves already.  DESIGN 10.20;
+// -DNH_Q_WALK_TOUCHED_WAVES=3 -Rpass-analysis=kernel-resource-usage reproduces the 3-wave figures.)
+#ifndef NH_Q_WALK_TOUCHED_WAVES
+#define NH_Q_WALK_TOUCHED_WAVES 2
+#endif
+template <class Shape> constexpr int nh_q_walk_waves(bool filter, bool touched) { return touched ? NH_Q_WALK_TOUCHED_WAVES : nh_q_walk_waves<Shape>(filter); }
+template <> constexpr int nh_q_walk_waves<nh_QBox>(bool filter, bool) { return nh_q_walk_waves<nh_QBox>(filter); }
 
-template <class Shape, bool FILTER>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(nh_q_walk_waves<Shape>(FILTER)))) void k_q_walk(const typename nh_QMover<Shape>::Walk* __restrict__ walks, uint32_t count,
+template <class Shape, bool FILTER, bool TOUCHED>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(nh_q_walk_waves<Shape>(FILTER, TOUCHED)))) void k_q_walk(const typename nh_QMover<Shape>::Walk* __restrict__ walks, uint32_t count,
                                                    nh_WalkResult* __restrict__ results,
-                                                   const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox, nh_QFilter F) {
+                                                   const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox, nh_QFilter F,
+                                                   uint32_t k_touches, uint32_t* __restrict__ counts, nh_Touch* __restrict__ touches) {
 	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
 		const float4* wp = reinterpret_cast<const float4*>(walks + i);
 		const float4 m0 = wp[0], m1 = wp[1], m2 = wp[2], m3 = wp[3], m4 = wp[4], m5 = wp[5];
@@ -459,6 +499,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(nh_q_walk_w
 		const bool valid = nh_QMover<Shape>::walk_valid(W, m2, m3);
 		nh_QWalk s = nh_q_walk_begin(W);
 		const uint32_t fm = FILTER ? F.of(i) : 0u;
+		uint32_t touched = 0u;
 		for (uint32_t round = 0u; round < NH_WALK_MAX_CASTS; ++round) {
 			if (!valid || !nh_q_walk_cast(s, W)) break;
 			Shape k;
@@ -467,6 +508,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(nh_q_walk_w
 			uint32_t bc;
 			nh_f3 bn;
 			nh_q_cast_one<FILTER>(k, nodes, rec, n, nbox, 0u, F, fm, bt, bc, bn);
+			if (TOUCHED && bc != NH_Q_NONE) {
+				if (touched < k_touches)
+					nh_q_write_touch(touches + ((size_t)i * k_touches + touched), rec, nbox, bc, bt, bn, s.m.p, s.m.v, nh_q_walk_touch_phase(s.phase), s.casts);
+				++touched;
+			}
 			nh_q_walk_advance(s, W, bc != NH_Q_NONE, bt, bc, bn, k.ok);
 		}
 		float4* out = reinterpret_cast<float4*>(results + i);
@@ -476,6 +522,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(nh_q_walk_w
 		nh_q_write_hit(&results[i].last_hit, rec, nbox, valid, s.klast.c, s.klast.t, s.klast.n);
 		nh_q_write_hit(&results[i].ground, rec, nbox, valid, g.c, g.t, g.n);
 		out[6] = make_float4(s.step_up, nh_q_walk_drop(s, W), __uint_as_float(s.casts), 0.0f);
+		if (TOUCHED) counts[i] = touched;
 	}
 }
 
@@ -1141,35 +1188,57 @@ extern "C" int nh_boxcast(nh_context* ctx, const nh_BoxCast* casts, uint32_t cou
 	return nh_cast(ctx, "q_boxcast", k_q_boxcast<false>, k_q_boxcast<true>, casts, count, hits, flags);
 }
 
-// The four movers: one record type, one result type and one kernel pair each.  One launch, nh_distance's checks in nh_distance's order; no allocation, no wait.
-// (`filtered` before `plain`: the callers name the instantiations in the order the code object has always held them.)
+// The four movers and their _touched forms: one record type, one result type and one kernel pair each.  One launch, nh_distance's checks in nh_distance's order; no
+// allocation, no wait.  k_max = 0: the plain call (k, counts and touches are not read); otherwise the touched call, whose k, counts and touches follow the plain
+// call's checks.  (`filtered` before `plain`: the callers name the instantiations in the order the code object has always held them.)
 template <class In, class Out>
-using nh_MoverKernel = void (*)(const In*, uint32_t, Out*, const nh_QNode*, const nh_QRec*, uint32_t, uint32_t, nh_QFilter);
+using nh_MoverKernel = void (*)(const In*, uint32_t, Out*, const nh_QNode*, const nh_QRec*, uint32_t, uint32_t, nh_QFilter, uint32_t, uint32_t*, nh_Touch*);
 template <class In, class Out>
 static int nh_mover(nh_context* ctx, const char* label, nh_MoverKernel<In, Out> filtered, nh_MoverKernel<In, Out> plain, const In* in, uint32_t count, Out* out,
-                    uint32_t flags) {
-	{ const int rc = nh_query_call(ctx, flags, 0u, 0u, 0u, count, 1u << 30, in, out, nullptr); if (rc || count == 0u) return rc; }
+                    uint32_t flags, uint32_t k = 0u, uint32_t k_max = 0u, uint32_t* counts = nullptr, nh_Touch* touches = nullptr) {
+	{ const int rc = nh_query_call(ctx, flags, 0u, k, k_max, count, 1u << 30, in, out, counts); if (rc || count == 0u) return rc; }
+	if (k_max && (!counts || !touches || ((uintptr_t)touches & 15u))) return NH_ERR_INVALID;
 	nh_QueryState* q = ctx->query;
 	bool on;
 	const nh_QFilter F = nh_query_filter_of(q, &on);
-	NH_LAUNCH(ctx, label, on ? filtered : plain, nh_grid_for(count, 256, 1u << 20), 256, in, count, out, q->nodes, q->rec, q->n, q->nbox, F);
+	NH_LAUNCH(ctx, label, on ? filtered : plain, nh_grid_for(count, 256, 1u << 20), 256, in, count, out, q->nodes, q->rec, q->n, q->nbox, F, k, counts, touches);
 	return NH_OK;
 }
 
 extern "C" int nh_move(nh_context* ctx, const nh_Move* moves, uint32_t count, nh_MoveResult* results, uint32_t flags) {
-	return nh_mover(ctx, "q_move", k_q_move<nh_QCapsule, true>, k_q_move<nh_QCapsule, false>, moves, count, results, flags);
+	return nh_mover(ctx, "q_move", k_q_move<nh_QCapsule, true, false>, k_q_move<nh_QCapsule, false, false>, moves, count, results, flags);
 }
 
 extern "C" int nh_boxmove(nh_context* ctx, const nh_BoxMove* moves, uint32_t count, nh_MoveResult* results, uint32_t flags) {
-	return nh_mover(ctx, "q_boxmove", k_q_move<nh_QBox, true>, k_q_move<nh_QBox, false>, moves, count, results, flags);
+	return nh_mover(ctx, "q_boxmove", k_q_move<nh_QBox, true, false>, k_q_move<nh_QBox, false, false>, moves, count, results, flags);
 }
 
 extern "C" int nh_walk(nh_context* ctx, const nh_Walk* walks, uint32_t count, nh_WalkResult* results, uint32_t flags) {
-	return nh_mover(ctx, "q_walk", k_q_walk<nh_QCapsule, true>, k_q_walk<nh_QCapsule, false>, walks, count, results, flags);
+	return nh_mover(ctx, "q_walk", k_q_walk<nh_QCapsule, true, false>, k_q_walk<nh_QCapsule, false, false>, walks, count, results, flags);
 }
 
 extern "C" int nh_boxwalk(nh_context* ctx, const nh_BoxWalk* walks, uint32_t count, nh_WalkResult* results, uint32_t flags) {
-	return nh_mover(ctx, "q_boxwalk", k_q_walk<nh_QBox, true>, k_q_walk<nh_QBox, false>, walks, count, results, flags);
+	return nh_mover(ctx, "q_boxwalk", k_q_walk<nh_QBox, true, false>, k_q_walk<nh_QBox, false, false>, walks, count, results, flags);
+}
+
+extern "C" int nh_move_touched(nh_context* ctx, const nh_Move* moves, uint32_t count, nh_MoveResult* results, uint32_t k, uint32_t* counts, nh_Touch* touches, uint32_t flags) {
+	return nh_mover(ctx, "q_move_touched", k_q_move<nh_QCapsule, true, true>, k_q_move<nh_QCapsule, false, true>, moves, count, results, flags, k, NH_MOVE_MAX_SLIDES + 1u,
+	                counts, touches);
+}
+
+extern "C" int nh_boxmove_touched(nh_context* ctx, const nh_BoxMove* moves, uint32_t count, nh_MoveResult* results, uint32_t k, uint32_t* counts, nh_Touch* touches, uint32_t flags) {
+	return nh_mover(ctx, "q_boxmove_touched", k_q_move<nh_QBox, true, true>, k_q_move<nh_QBox, false, true>, moves, count, results, flags, k, NH_MOVE_MAX_SLIDES + 1u,
+	                counts, touches);
+}
+
+extern "C" int nh_walk_touched(nh_context* ctx, const nh_Walk* walks, uint32_t count, nh_WalkResult* results, uint32_t k, uint32_t* counts, nh_Touch* touches, uint32_t flags) {
+	return nh_mover(ctx, "q_walk_touched", k_q_walk<nh_QCapsule, true, true>, k_q_walk<nh_QCapsule, false, true>, walks, count, results, flags, k, NH_WALK_MAX_CASTS, counts,
+	                touches);
+}
+
+extern "C" int nh_boxwalk_touched(nh_context* ctx, const nh_BoxWalk* walks, uint32_t count, nh_WalkResult* results, uint32_t k, uint32_t* counts, nh_Touch* touches, uint32_t flags) {
+	return nh_mover(ctx, "q_boxwalk_touched", k_q_walk<nh_QBox, true, true>, k_q_walk<nh_QBox, false, true>, walks, count, results, flags, k, NH_WALK_MAX_CASTS, counts,
+	                touches);
 }
 
 // nh_move's checks in nh_move's order; the sphere-and-box launch and the capsule launch under one label, as nh_overlap splits its walks; no allocation, no wait.

@@ -45,6 +45,7 @@ EXPORTS = [
     "nh_partition_set_transport", "nh_partition_exchange_step", "nh_partition_step", "nh_partition_transport_check", "nh_partition_transport_result", "nh_set_first_ghost_body",
     "nh_query_build", "nh_query_refit", "nh_query_stats", "nh_raycast", "nh_overlap", "nh_penetration", "nh_region", "nh_spherecast", "nh_raycast_all", "nh_spherecast_all", "nh_boxcast_all", "nh_capsulecast_all", "nh_boxcast", "nh_capsulecast", "nh_closest", "nh_closest_k", "nh_distance", "nh_move", "nh_recover", "nh_walk", "nh_boxmove", "nh_boxwalk",
     "nh_raycast_k", "nh_spherecast_k", "nh_boxcast_k", "nh_capsulecast_k",
+    "nh_move_touched", "nh_boxmove_touched", "nh_walk_touched", "nh_boxwalk_touched",
     "nh_query_set_layers", "nh_query_filter", "nh_query_layer_info",
 ]
 HALO_RECORD_BYTES = 64
@@ -187,6 +188,10 @@ NH_WALK_PROBE_ONLY = 1
 BOX_MOVE = np.dtype([("origin", "<f4", 3), ("skin", "<f4"), ("displacement", "<f4", 3), ("ignore_body", "<u4"), ("rotation", "<f4", 4), ("size", "<f4", 3),
                      ("max_slides", "<u4")])
 BOX_WALK = np.dtype(BOX_MOVE.descr + WALK.descr[len(MOVE.descr):])
+# nh_move_touched and kin (include/nudge_hip.h): one nh_Touch per cast of a mover that found a collider; nh_Touch.phase
+TOUCH = np.dtype([("hit", RAY_HIT), ("origin", "<f4", 3), ("phase", "<u4"), ("direction", "<f4", 3), ("cast", "<u4")])
+NH_TOUCH_SLIDE, NH_TOUCH_UP, NH_TOUCH_FORWARD, NH_TOUCH_DOWN, NH_TOUCH_PROBE = 0, 1, 2, 3, 4
+NH_MOVE_MAX_TOUCHES, NH_WALK_MAX_TOUCHES = NH_MOVE_MAX_SLIDES + 1, NH_WALK_MAX_CASTS
 # nh_recover (include/nudge_hip.h): nh_OverlapQuery followed by `skin` and `max_iterations`; nh_RecoverResult.flags
 RECOVER = np.dtype([("center", "<f4", 3), ("shape", "<u4"), ("rotation", "<f4", 4), ("size", "<f4", 3), ("ignore_body", "<u4"), ("skin", "<f4"),
                     ("max_iterations", "<u4"), ("reserved", "<u4", 2)])
@@ -346,6 +351,10 @@ def lib():
         if hasattr(L, "nh_boxmove"):
             L.nh_boxmove.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
             L.nh_boxwalk.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
+        # (likewise the movers' _touched forms: World.move_touched_records and its siblings then raise AttributeError)
+        if hasattr(L, "nh_move_touched"):
+            for fn in (L.nh_move_touched, L.nh_boxmove_touched, L.nh_walk_touched, L.nh_boxwalk_touched):
+                fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]
         L.nh_overlap.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
         L.nh_penetration.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
         # (an older build of the library, loaded through NUDGE_HIP_LIBRARY for an A/B, has no nh_region: World.region then raises AttributeError)
@@ -1120,15 +1129,19 @@ class World:
         count x 64-byte uint8 device tensor of nh_MoveResult records (`results`, or a new one)."""
         return self._records("nh_move", 64, 64, records, results)
 
-    def move(self, origins, displacements, radius, half_height=0.0, rotations=None, skin=0.01, max_slides=4, ignore_body=None, synchronize=False):
+    def move(self, origins, displacements, radius, half_height=0.0, rotations=None, skin=0.01, max_slides=4, ignore_body=None, synchronize=False, touched=None):
         """Collide-and-slide (nh_move) against the last query_build(): each of n capsules of `radius` and `half_height` (numbers or n values; half
         height 0 is a ball) and `rotations` ((n, 4) or (4,) quaternions (x, y, z, s); None = identity, upright) is moved from `origins` by
         `displacements` ((n, 3) each), sliding along what it hits, at most `max_slides` (0 .. NH_MOVE_MAX_SLIDES; a number or n values) times, and
         keeping `skin` (a number or n values, in world units: scale it to the scene) clear of it.  `ignore_body`: None, a body index, or n of them.
         Returns a dict of device tensors: position (n, 3), remaining (n, 3; the displacement not used), flags (n, int64; NH_MOVE_*), slides (n,
         int64), `last_hit` (capsulecast()'s dict for the last cast each move made) and `raw`, the nh_MoveResult records.  Nothing waits for the
-        device unless `synchronize`."""
-        return self._move("move", origins, displacements, (radius, half_height), rotations, skin, max_slides, ignore_body, synchronize)
+        device unless `synchronize`.
+        `touched` = k (1 .. NH_MOVE_MAX_TOUCHES): the call is nh_move_touched, and the dict gains `touch_count` (n, int64: every collider a cast of the
+        move found, whatever k is) and `touches`, a dict of (n, k, ...) views of the nh_Touch records: capsulecast()'s fields of each touch's hit, and
+        origin, direction (n, k, 3), phase, cast (n, k, int64) and `raw`.  Slots at or behind touch_count hold whatever the tensor held: they are not
+        written."""
+        return self._move("move", origins, displacements, (radius, half_height), rotations, skin, max_slides, ignore_body, synchronize, touched)
 
     def _mover_head(self, name, origins, displacements, shape, rotations, skin, max_slides, ignore_body):
         """The 64-byte records nh_Move (`name` move, walk; `shape` = (radius, half_height)) or nh_BoxMove (boxmove, boxwalk; (half_extents,)): the
@@ -1139,15 +1152,68 @@ class World:
         head.view(torch.int32)[:, column] = torch.as_tensor(max_slides, dtype=torch.int64, device=self.dev).to(torch.int32)
         return head, n
 
-    def _move(self, name, origins, displacements, shape, rotations, skin, max_slides, ignore_body, synchronize):
-        """move() and boxmove(): the dict they return, from the nh_MoveResult records of the call nh_`name`."""
+    def _touched_records(self, name, in_bytes, out_bytes, records, k, results, counts, touches):
+        """The C call `name`(ctx, records, count, results, k, counts, touches, 0) of the movers' _touched forms: `records` a contiguous device tensor
+        of count x in_bytes bytes (any dtype).  Returns (results, counts, touches): the count x out_bytes uint8 result records, the count words as an
+        int32 device tensor and the count x k x 64-byte uint8 tensor of nh_Touch records (each the one given, or a new one).  Of record i's k slots
+        only the first min(counts[i], k) are written.  Enqueued; nothing waits, and nothing allocates where all three are given."""
+        torch = self.torch
+        n = records.numel() * records.element_size() // in_bytes
+        if results is None:
+            results = torch.empty((n, out_bytes), dtype=torch.uint8, device=self.dev)
+        if counts is None:
+            counts = torch.empty(n, dtype=torch.int32, device=self.dev)
+        if touches is None:
+            touches = torch.empty((n, max(int(k), 0), 64), dtype=torch.uint8, device=self.dev)
+        _check(self.L, getattr(self.L, name)(self.ctx, C.c_void_p(records.data_ptr() if n else 0), n, C.c_void_p(results.data_ptr() if n else 0), k,
+                                             C.c_void_p(counts.data_ptr() if n else 0), C.c_void_p(touches.data_ptr() if n else 0), 0), name)
+        return results, counts, touches
+
+    def move_touched_records(self, records, k, results=None, counts=None, touches=None):
+        """nh_move_touched on records already laid out as nh_Move (count x 64 bytes): (results, counts, touches) -- move_records()'s nh_MoveResult
+        records, the touches per move (int32) and the count x k x 64-byte nh_Touch records, k in 1 .. NH_MOVE_MAX_TOUCHES.  Slots at or behind a
+        move's count are not written."""
+        return self._touched_records("nh_move_touched", 64, 64, records, k, results, counts, touches)
+
+    def boxmove_touched_records(self, records, k, results=None, counts=None, touches=None):
+        """nh_boxmove_touched on records already laid out as nh_BoxMove (count x 64 bytes): move_touched_records()'s arguments and result."""
+        return self._touched_records("nh_boxmove_touched", 64, 64, records, k, results, counts, touches)
+
+    def walk_touched_records(self, records, k, results=None, counts=None, touches=None):
+        """nh_walk_touched on records already laid out as nh_Walk (count x 96 bytes): (results, counts, touches) -- walk_records()'s nh_WalkResult
+        records, the touches per walk (int32) and the count x k x 64-byte nh_Touch records, k in 1 .. NH_WALK_MAX_TOUCHES.  Slots at or behind a
+        walk's count are not written."""
+        return self._touched_records("nh_walk_touched", 96, 112, records, k, results, counts, touches)
+
+    def boxwalk_touched_records(self, records, k, results=None, counts=None, touches=None):
+        """nh_boxwalk_touched on records already laid out as nh_BoxWalk (count x 96 bytes): walk_touched_records()'s arguments and result."""
+        return self._touched_records("nh_boxwalk_touched", 96, 112, records, k, results, counts, touches)
+
+    def _mover_call(self, name, rec, touched, out):
+        """The mover nh_`name` on the packed records `rec`: its result records, from the plain call or, with `touched` = k, from the _touched form,
+        which also puts `touch_count` and `touches` into `out`."""
+        torch = self.torch
+        if touched is None:
+            return getattr(self, name + "_records")(rec)
+        raw, counts, touches = getattr(self, name + "_touched_records")(rec, touched)
+        n, k = touches.shape[0], touches.shape[1]
+        f = touches.view(torch.float32).reshape(n, k, 16)
+        u = touches.view(torch.int32).reshape(n, k, 16).to(torch.int64) & 0xFFFFFFFF
+        out["touch_count"] = counts.to(torch.int64)
+        out["touches"] = dict(t=f[:, :, 0], normal=f[:, :, 1:4], body=u[:, :, 4], collider=u[:, :, 5], shape=u[:, :, 6], tag=u[:, :, 7], origin=f[:, :, 8:11],
+                              phase=u[:, :, 11], direction=f[:, :, 12:15], cast=u[:, :, 15], raw=touches)
+        return raw
+
+    def _move(self, name, origins, displacements, shape, rotations, skin, max_slides, ignore_body, synchronize, touched=None):
+        """move() and boxmove(): the dict they return, from the nh_MoveResult records of the call nh_`name` (nh_`name`_touched with `touched` = k)."""
         torch = self.torch
         rec, n = self._mover_head(name, origins, displacements, shape, rotations, skin, max_slides, ignore_body)
-        raw = getattr(self, name + "_records")(rec)
+        more = {}
+        raw = self._mover_call(name, rec, touched, more)
         f = raw.view(torch.float32).reshape(n, 16)
         u = raw.view(torch.int32).reshape(n, 16).to(torch.int64) & 0xFFFFFFFF
         out = dict(position=f[:, 0:3], remaining=f[:, 4:7], flags=u[:, 3], slides=u[:, 7], last_hit=self._ray_hits(raw.reshape(n, 64)[:, 32:].contiguous(), False),
-                   raw=raw)
+                   raw=raw, **more)
         if synchronize:
             torch.cuda.current_stream(self.dev).synchronize()
         return out
@@ -1157,12 +1223,12 @@ class World:
         count x 64-byte uint8 device tensor of nh_MoveResult records (`results`, or a new one)."""
         return self._records("nh_boxmove", 64, 64, records, results)
 
-    def boxmove(self, origins, displacements, half_extents, rotations=None, skin=0.01, max_slides=4, ignore_body=None, synchronize=False):
+    def boxmove(self, origins, displacements, half_extents, rotations=None, skin=0.01, max_slides=4, ignore_body=None, synchronize=False, touched=None):
         """Collide-and-slide for oriented boxes (nh_boxmove) against the last query_build(): move() with boxcast()'s shape -- `half_extents` ((n, 3)
         or (3,)) and `rotations` ((n, 4) or (4,) quaternions (x, y, z, s); None = identity, axis-aligned); the box does not turn while it moves.
-        `skin`, `max_slides`, `ignore_body` and the returned dict are move()'s, with boxcast()'s dict as `last_hit`.  Nothing waits for the device
-        unless `synchronize`."""
-        return self._move("boxmove", origins, displacements, (half_extents,), rotations, skin, max_slides, ignore_body, synchronize)
+        `skin`, `max_slides`, `ignore_body`, `touched` (nh_boxmove_touched) and the returned dict are move()'s, with boxcast()'s dict as `last_hit`.
+        Nothing waits for the device unless `synchronize`."""
+        return self._move("boxmove", origins, displacements, (half_extents,), rotations, skin, max_slides, ignore_body, synchronize, touched)
 
     def walk_records(self, records, results=None):
         """nh_walk on records already laid out as nh_Walk: `records` a contiguous device tensor of count x 96 bytes (any dtype).  Returns the
@@ -1170,7 +1236,7 @@ class World:
         return self._records("nh_walk", 96, 112, records, results)
 
     def walk(self, origins, displacements, radius, half_height=0.0, rotations=None, skin=0.01, max_slides=4, ignore_body=None, up=(0.0, 1.0, 0.0),
-             step_height=0.0, snap_distance=0.0, max_slope_degrees=None, min_ground_up=None, probe_only=False, synchronize=False):
+             step_height=0.0, snap_distance=0.0, max_slope_degrees=None, min_ground_up=None, probe_only=False, synchronize=False, touched=None):
         """A grounded character step (nh_walk) against the last query_build(): move()'s capsules, moved from `origins` by `displacements` with move()'s
         `skin`, `max_slides` and `ignore_body`, climbing risers up to `step_height`, treating faces steeper than the slope limit as walls, and
         following ground found within `snap_distance` below.  `up`: the unit vector against gravity ((3,) or (n, 3)).  The slope limit is
@@ -1178,14 +1244,17 @@ class World:
         `snap_distance`, the limit and `probe_only` (look for ground, do not move onto it) are numbers or n values.
         Returns move()'s dict for the slide that was kept -- position, remaining, flags (NH_MOVE_* and NH_WALK_*), slides, last_hit -- plus `ground`
         (capsulecast()'s dict of what the capsule stands on), step_up, drop (n, float32), casts (n, int64) and `raw`, the nh_WalkResult records.
-        Nothing waits for the device unless `synchronize`."""
+        Nothing waits for the device unless `synchronize`.
+        `touched` = k (1 .. NH_WALK_MAX_TOUCHES): the call is nh_walk_touched, and the dict gains move()'s `touch_count` and `touches` for everything the
+        walk probed, kept or not (phase: NH_TOUCH_*; with NH_WALK_STEPPED set UP, FORWARD and DOWN are the path taken, without it SLIDE and PROBE).
+        Slots at or behind touch_count hold whatever the tensor held: they are not written."""
         return self._walk("walk", origins, displacements, (radius, half_height), rotations, skin, max_slides, ignore_body, up, step_height,
-                          snap_distance, max_slope_degrees, min_ground_up, probe_only, synchronize)
+                          snap_distance, max_slope_degrees, min_ground_up, probe_only, synchronize, touched)
 
     def _walk(self, name, origins, displacements, shape, rotations, skin, max_slides, ignore_body, up, step_height, snap_distance, max_slope_degrees,
-              min_ground_up, probe_only, synchronize):
+              min_ground_up, probe_only, synchronize, touched=None):
         """walk() and boxwalk(): nh_Walk / nh_BoxWalk records -- the 64-byte head followed by walk()'s rules -- and the dict they return, from the
-        nh_WalkResult records of the call nh_`name`."""
+        nh_WalkResult records of the call nh_`name` (nh_`name`_touched with `touched` = k)."""
         torch = self.torch
         if max_slope_degrees is not None and min_ground_up is not None:
             raise ValueError(f"{name}: give max_slope_degrees or min_ground_up, not both")
@@ -1199,12 +1268,13 @@ class World:
             min_ground_up = torch.cos(torch.deg2rad(torch.as_tensor(max_slope_degrees, dtype=torch.float64, device=self.dev)))
         rec[:, 21] = torch.as_tensor(0.0 if min_ground_up is None else min_ground_up, device=self.dev).to(torch.float32).reshape(-1)
         rec.view(torch.int32)[:, 22] = torch.as_tensor(probe_only, device=self.dev).to(torch.int32).reshape(-1) & 1
-        raw = getattr(self, name + "_records")(rec)
+        more = {}
+        raw = self._mover_call(name, rec, touched, more)
         f = raw.view(torch.float32).reshape(n, 28)
         u = raw.view(torch.int32).reshape(n, 28).to(torch.int64) & 0xFFFFFFFF
         bytes_ = raw.reshape(n, 112)
         out = dict(position=f[:, 0:3], remaining=f[:, 4:7], flags=u[:, 3], slides=u[:, 7], last_hit=self._ray_hits(bytes_[:, 32:64].contiguous(), False),
-                   ground=self._ray_hits(bytes_[:, 64:96].contiguous(), False), step_up=f[:, 24], drop=f[:, 25], casts=u[:, 26], raw=raw)
+                   ground=self._ray_hits(bytes_[:, 64:96].contiguous(), False), step_up=f[:, 24], drop=f[:, 25], casts=u[:, 26], raw=raw, **more)
         if synchronize:
             torch.cuda.current_stream(self.dev).synchronize()
         return out
@@ -1215,12 +1285,12 @@ class World:
         return self._records("nh_boxwalk", 96, 112, records, results)
 
     def boxwalk(self, origins, displacements, half_extents, rotations=None, skin=0.01, max_slides=4, ignore_body=None, up=(0.0, 1.0, 0.0),
-                step_height=0.0, snap_distance=0.0, max_slope_degrees=None, min_ground_up=None, probe_only=False, synchronize=False):
+                step_height=0.0, snap_distance=0.0, max_slope_degrees=None, min_ground_up=None, probe_only=False, synchronize=False, touched=None):
         """A grounded step for oriented boxes (nh_boxwalk) against the last query_build(): walk() with boxmove()'s shape (`half_extents`, `rotations`;
-        None = identity: an axis-aligned character).  Every other argument and the returned dict are walk()'s, with boxcast()'s dicts as `last_hit`
-        and `ground`.  Nothing waits for the device unless `synchronize`."""
+        None = identity: an axis-aligned character).  Every other argument (`touched`: nh_boxwalk_touched) and the returned dict are walk()'s, with
+        boxcast()'s dicts as `last_hit` and `ground`.  Nothing waits for the device unless `synchronize`."""
         return self._walk("boxwalk", origins, displacements, (half_extents,), rotations, skin, max_slides, ignore_body, up, step_height,
-                          snap_distance, max_slope_degrees, min_ground_up, probe_only, synchronize)
+                          snap_distance, max_slope_degrees, min_ground_up, probe_only, synchronize, touched)
 
     def recover_records(self, records, results=None):
         """nh_recover on records already laid out as nh_Recover: `records` a contiguous device tensor of count x 64 bytes (any dtype).  Returns the
