@@ -852,6 +852,63 @@ typedef struct nh_Region { float planes[NH_REGION_MAX_PLANES][4]; uint32_t plane
 int nh_region(nh_context* ctx, const nh_Region* regions, uint32_t count, uint32_t* offsets /* count + 1 */, nh_OverlapHit* hits, uint32_t capacity,
               uint32_t flags /* 0 */);
 
+/* TRIGGER EVENTS -- nh_overlap_bodies and nh_overlap_events: what ENTERED and what LEFT each of `count` overlap volumes since the last step, per collider
+   or per body, computed on the device from two lists.  A trigger volume, an explosion radius or a client's area of interest is listed every step by
+   nh_overlap or nh_region; what a caller acts on is the difference between this step's list and the last one's, and for a compound body one event, not
+   one per collider.
+   A LIST (nh_HitList: a host struct of DEVICE pointers) is what a list call of nh_overlap or nh_region wrote, or what these two calls write: `offsets`
+   (count + 1 words), `hits`, and the `capacity` that call was given.  Both calls read lists only -- not the hierarchy, not the colliders, not the layer
+   filter: they are not query calls of the filter contract above, and a list stays usable after any number of builds, refits and steps.
+   PRESENT SEGMENTS: segment i of an input list is present iff offsets[i+1] <= capacity and offsets[count] != 0xffffffff -- nh_overlap's own written-prefix
+   rule, so the present segments are a prefix and the caller sees from its own offsets where a list was cut short.  No record at or beyond `capacity` is
+   ever read, whatever the offsets hold (a pair offsets[i+1] < offsets[i] is an absent segment); lists that no list call wrote give unspecified records
+   but never an access outside the arrays.
+   nh_overlap_bodies -- ONE RECORD PER BODY: for every present segment of `in`, one record per distinct body in it: the record of the body's lowest
+   COMBINED collider index in the segment, copied whole (body, collider, shape, tag); the records of a segment in ascending body.  An absent segment
+   counts 0.  (The input's segments must be in nh_overlap's order, ascending combined collider index: the sort is stable and that order decides the tie.)
+   nh_overlap_events -- WHAT ENTERED AND WHAT LEFT: the IDENTITY of a record is (shape, collider) with flags = 0, and both inputs are in nh_overlap's
+   order; with NH_EVENTS_BY_BODY it is `body`, and both inputs are outputs of nh_overlap_bodies.
+     - a volume's segments are read only when both its `cur` and its `prev` segment are present (or prev == NULL); any other volume gives no event and
+       counts 0 in both outputs;
+     - `entered` gets, for volume i, the records of cur's segment whose identity is not in prev's segment, copied from cur in cur's order;
+     - `left` gets the records of prev's segment whose identity is not in cur's segment, copied from prev in prev's order: `body` and `tag` are those of
+       the step the collider was last seen in;
+     - prev == NULL is the FIRST FRAME: `entered` equals cur's present segments and `left` is empty.
+   OUTPUT (`out`, `entered`, `left`, each on its own) follows nh_overlap's rules word for word: offsets[0 .. count] by the exclusive scan of the per-volume
+   counts, always complete; COUNT ONLY with hits == NULL and capacity == 0; the records of volume i are written iff offsets[i+1] <= capacity, and every byte
+   behind the written prefix is left untouched.  An output's total is at most its input's, so the overflow marker never appears in an output.  Outputs
+   must not alias inputs or each other.
+   Returns NH_ERR_INVALID before any nh_query_build, for unknown flags, for count >= 2^30, and (count > 0) for a NULL cur, in, out, entered or left, for
+   `offsets` null or not 4-byte aligned, for `hits` null with capacity > 0 or not 16-byte aligned, and where the input capacities add up to 2^32 - 2 or
+   more; count = 0 is a no-op that returns NH_OK (nh_overlap's order: before the lists are looked at).
+   OBSERVERS (note 9): no view export, no settling of deferred gravity, no still step turned into a full one, no change to nh_Counts.  Everything is
+   enqueued on the context's stream, except that larger input capacities than any before grow the library's scratch after a stream synchronise: 4.5 B of
+   flag and scan words (one word, scanned in place) per record of in.capacity or prev.capacity + cur.capacity, and for nh_overlap_bodies nh_overlap's own sort scratch (~24 B per record
+   of in.capacity).  nh_destroy frees both.
+   HOW: the work item is the RECORD, so one region of a million records spreads over the GPU.  A record finds its volume by a binary
+   search over `offsets` (the last i with offsets[i] <= r: empty segments are stepped over) and its identity in the other list's segment by a second one;
+   the exclusive scan of the per-record flags gives the compacted position and the output's offsets[i] = scan[input offsets[i]].  No atomics: the bytes
+   are deterministic.  nh_overlap_bodies sorts (segment, body) keys with the library's stable radix sort, flags the first record of each run, scans and
+   compacts.
+   Timing labels: q_bodies_prefix, q_bodies_keys, q_bodies_flag, q_bodies_offsets, q_bodies_compact; q_events_flag, q_events_offsets, q_events_compact;
+   the sort's and the scan's own between them.
+   MEASURED (tools/events_rates.py -> profiles/events_rates.log; one MI355X, one run, the landed config-2 world of 1,004,524 colliders; two lists per case,
+   the volumes at A and moved by one body's size; ms per call, the best of 5 blocks of 10 calls by device events; in brackets the ratio to the list call --
+   count + exactly sized list -- that produced the input):
+                                                                  list call   nh_overlap_bodies   nh_overlap_events, by collider / by body
+     (1) 1 M sphere queries of a box's size, 2,185,844 records      2.545       0.359 (0.141)       0.140 (0.055) / 0.141 (0.055)
+     (2) 4,096 cubes of a tile's size, 29,776,132 records           7.994       3.997 (0.500)       2.264 (0.283) / 2.294 (0.287)
+     (3) one region that is the world, 1,004,524 records            0.675       0.170 (0.251)       0.062 (0.092) / 0.063 (0.094)
+   The bodies' time is its radix sort's (3.25 of 4.0 ms in (2): six passes for 32 + bits(count) = 45 key bits); the events' time is the flag kernel's two
+   binary searches (1.86 of 2.26 ms in (2)).  In this world every collider is its own body, so (1)'s body list is as long as its input.
+   Not built: a stay list (it is `cur` minus `entered`); events for nh_penetration's 32-byte records; events for the movers' touch records, which are
+   nh_Touch, not nh_OverlapHit. */
+typedef struct nh_HitList { uint32_t* offsets /* count + 1 */; nh_OverlapHit* hits; uint32_t capacity; uint32_t reserved; } nh_HitList;   /* host struct, DEVICE pointers */
+enum { NH_EVENTS_BY_BODY = 1u };
+int nh_overlap_bodies(nh_context* ctx, uint32_t count, const nh_HitList* in, const nh_HitList* out, uint32_t flags /* 0 */);
+int nh_overlap_events(nh_context* ctx, uint32_t count, const nh_HitList* prev /* or NULL */, const nh_HitList* cur, const nh_HitList* entered,
+                      const nh_HitList* left, uint32_t flags /* 0 or NH_EVENTS_BY_BODY */);
+
 /* nh_distance: how far each of `count` query shapes is from the world of the LAST nh_query_build or nh_query_refit, and towards what -- the clearance
    of a crate, a hull or a limb.  nh_penetration describes a pair that overlaps; this describes the pairs that do not.
    Query shapes: nh_overlap's (NH_SHAPE_SPHERE, NH_SHAPE_BOX, NH_SHAPE_CAPSULE), the same fields read and the same validity rules; the first 48 bytes
@@ -1179,6 +1236,8 @@ int nh_boxwalk(nh_context* ctx, const nh_BoxWalk* walks, uint32_t count, nh_Walk
    each on the context's stream (timing labels q_move_touched, q_boxmove_touched, q_walk_touched, q_boxwalk_touched).  OBSERVERS like nh_move (note 9).
    NOT BUILT: touches de-duplicated per body; a contact point (the casts return none: origin + t * direction is where the SHAPE's centre was); touches for
    nh_recover; pushing dynamic bodies and moving platforms inside the library (queries are observers: INTEGRATION.md, "touched", has the caller's recipe).
+   (nh_overlap_bodies, above, de-duplicates LISTS OF nh_OverlapHit per body -- what nh_overlap and nh_region write.  A mover's touches are nh_Touch records,
+   which it does not read: for them the de-duplication stays not built.)
    Cost: the mover's cost, and per touch four 16-byte stores (64 B) beside the tree walk of its cast, per record one 4-byte count; the lane holds the slot
    pointer, k and the count across the sweep.  Registers on gfx950 (hipcc -Rpass-analysis=kernel-resource-usage): the
    touched capsule move 128 VGPRs at 4 waves per SIMD and the touched box move 150 (151 filtered) at 3, their plain siblings' occupancy; the touched box walk

@@ -1614,4 +1614,47 @@ NH_HD bool nh_q_region_node_outside(nh_f3 n, float d, nh_f3 lo, nh_f3 hi) {
 	return g + m < 0.0f;
 }
 
+// ---- events: the per-record functions of nh_overlap_bodies / nh_overlap_events (nh_query.hip, "events"; tests/hostoracle/hostevents.cpp) ------------------
+// A list is what a list call of nh_overlap / nh_region wrote: offsets[0 .. count], records of four words (body, collider, shape, tag) and the capacity
+// the call was given.  Nothing here reads a record at or beyond `capacity`, whatever the offsets hold.
+#define NH_Q_EVENTS_BY_BODY 1u
+
+// Segment i (i < count) is PRESENT iff its records were written: offsets[i+1] <= capacity and no overflow marker -- nh_overlap's written-prefix rule.  A
+// non-monotone pair (lists no call wrote) is absent, so a present segment is a range [offsets[i], offsets[i+1]) inside the records.
+NH_HD bool nh_q_seg_present(const uint32_t* offsets, uint32_t count, uint32_t capacity, uint32_t i) {
+	return offsets[count] != 0xffffffffu && offsets[i + 1u] <= capacity && offsets[i] <= offsets[i + 1u];
+}
+
+// The segment of record r: the last i in [0, count] with offsets[i] <= r, so that empty segments are stepped over (offsets[0] = 0 <= r always; offsets
+// that do not start at 0 give 0).  `count` itself says that r lies at or behind the total.
+NH_HD uint32_t nh_q_seg_of(const uint32_t* offsets, uint32_t count, uint32_t r) {
+	uint32_t lo = 0u, hi = count;          // the answer is in [lo, hi]
+	while (lo < hi) {
+		const uint32_t mid = lo + (hi - lo + 1u) / 2u;
+		if (offsets[mid] <= r) lo = mid; else hi = mid - 1u;
+	}
+	return lo;
+}
+
+// The segment record r of a list belongs to when that record is one of a present segment; 0xffffffff otherwise (r < capacity is the caller's bound).
+NH_HD uint32_t nh_q_seg_of_present(const uint32_t* offsets, uint32_t count, uint32_t capacity, uint32_t r) {
+	const uint32_t i = nh_q_seg_of(offsets, count, r);
+	if (i >= count || !nh_q_seg_present(offsets, count, capacity, i) || r < offsets[i] || r >= offsets[i + 1u]) return 0xffffffffu;
+	return i;
+}
+
+// A record's identity as one ordered word: the body (NH_Q_EVENTS_BY_BODY), or (shape, collider) -- with the boxes first that is the combined collider
+// index's order, the order nh_overlap writes a segment in; nh_overlap_bodies writes a segment by body.
+NH_HD uint64_t nh_q_ident(const uint32_t* rec, uint32_t by_body) { return by_body ? (uint64_t)rec[0] : ((uint64_t)rec[2] << 32) | rec[1]; }
+
+// Is the identity `key` among records [lo, hi) of `hits` (four words a record, sorted by identity)?  A lower-bound search; lo <= hi <= capacity.
+NH_HD bool nh_q_ident_find(const uint32_t* hits, uint32_t lo, uint32_t hi, uint64_t key, uint32_t by_body) {
+	const uint32_t end = hi;
+	while (lo < hi) {
+		const uint32_t mid = lo + (hi - lo) / 2u;
+		if (nh_q_ident(hits + 4u * (uint64_t)mid, by_body) < key) lo = mid + 1u; else hi = mid;
+	}
+	return lo < end && nh_q_ident(hits + 4u * (uint64_t)lo, by_body) == key;          // (every record read lies in [lo, end) of the call)
+}
+
 #endif

@@ -1513,3 +1513,202 @@ extern "C" int nh_boxcast_k(nh_context* ctx, const nh_BoxCast* casts, uint32_t c
 extern "C" int nh_capsulecast_k(nh_context* ctx, const nh_CapsuleCast* casts, uint32_t count, uint32_t k, uint32_t* counts, nh_RayHit* hits, uint32_t flags) {
 	return nh_cast_k<nh_QCapsule>(ctx, "q_capsulecast_k", casts, count, k, counts, hits, flags);
 }
+
+// ---- events ------------------------------------------------------------------------------------------------------------------------------------
+// nh_overlap_bodies / nh_overlap_events (header, "trigger events") work on LISTS that a list call of nh_overlap / nh_region wrote: they read neither the
+// hierarchy nor the colliders nor the layer filter.  The work item is the RECORD (nh_query.h, "events": the segment-of-record search, the identity search
+// within a segment, which the host oracle compiles as well); kernel boundaries are the only hand-offs and no atomic decides where a record goes.
+//   nh_overlap_events   k_q_events_flag     one lane per record slot of cur, then of prev: 1 where the record's segment is read and its identity is not in
+//                                           the other list's segment (cur's flags at [0, cur.capacity], prev's behind them; a slot that is no record: 0)
+//                       nh_scan_u32         in place over both ranges at once: a position among `entered` is scan[r], among `left` scan[base + r] - scan[base]
+//                       k_q_events_offsets  one lane per offset: out offsets[i] = the scan at the input's offsets[i], clamped to its capacity, and the
+//                                           written prefix of each output by k_q_overlap_fix's rule (no wrap: an output's total is at most its input's)
+//                       k_q_events_compact  one lane per record slot again: a flagged record whose position lies in the written prefix is copied whole
+//   nh_overlap_bodies   k_q_bodies_prefix   the length of the input's written prefix, by k_q_overlap_fix's rule, for the sort
+//                       k_q_bodies_keys     key (segment << 32 | body), value the record's index
+//                       nh_sort_u64_u32     STABLE, in nh_overlap's scratch: a segment keeps its place (the segment is the key's upper part) and within
+//                                           a run of one body the records keep the input's order -- ascending combined collider index -- so the first of
+//                                           a run is the body's lowest collider
+//                       k_q_bodies_flag     1 at the first record of each run;  nh_scan_u32;  k_q_bodies_offsets;  k_q_bodies_compact through the values
+// Every record index a kernel reads is below the list's capacity and every position it writes below the output's written prefix, which is at most the
+// output's capacity, whatever the offsets hold.
+struct nh_QList { const uint32_t* offsets; const uint32_t* hits; uint32_t capacity; };          // (hits: four words a record)
+
+__global__ __launch_bounds__(256) void k_q_events_flag(nh_QList cur, nh_QList prev, bool has_prev, uint32_t count, uint32_t by_body, uint32_t* __restrict__ scan) {
+	const uint64_t words = (uint64_t)cur.capacity + prev.capacity + 2u;
+	for (uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; w < words; w += (uint64_t)gridDim.x * blockDim.x) {
+		const bool left = w > cur.capacity;
+		const nh_QList& mine = left ? prev : cur;
+		const nh_QList& other = left ? cur : prev;
+		const uint32_t r = (uint32_t)(left ? w - cur.capacity - 1u : w);
+		uint32_t f = 0u;
+		if (r < mine.capacity) {
+			const uint32_t i = nh_q_seg_of_present(mine.offsets, count, mine.capacity, r);
+			if (i != NH_Q_NONE) {
+				if (!has_prev) f = 1u;          // (the first frame: prev has no record slot, so this is a record of cur)
+				else if (nh_q_seg_present(other.offsets, count, other.capacity, i))
+					f = nh_q_ident_find(other.hits, other.offsets[i], other.offsets[i + 1u], nh_q_ident(mine.hits + 4u * (size_t)r, by_body), by_body) ? 0u : 1u;
+			}
+		}
+		scan[w] = f;
+	}
+}
+
+// (scan: the exclusive scan of one list's flags, `capacity` + 1 words; offsets: that list's)
+__device__ __forceinline__ void nh_q_events_offset(const uint32_t* __restrict__ scan, const uint32_t* __restrict__ offsets, uint32_t capacity, uint32_t count,
+                                                   uint32_t i, uint32_t* __restrict__ out, uint32_t out_capacity, uint32_t* __restrict__ written) {
+	const uint32_t a = scan[min(offsets[i], capacity)] - scan[0];
+	out[i] = a;
+	if (i == count) { if (a <= out_capacity) *written = a; return; }          // everything fits
+	const uint32_t b = scan[min(offsets[i + 1u], capacity)] - scan[0];
+	if (a <= out_capacity && out_capacity < b) *written = a;                   // monotone offsets: exactly one lane
+}
+
+__global__ __launch_bounds__(256) void k_q_events_offsets(nh_QList cur, nh_QList prev, bool has_prev, uint32_t count, const uint32_t* __restrict__ scan,
+                                                           uint32_t* __restrict__ entered, uint32_t entered_capacity, uint32_t* __restrict__ left,
+                                                           uint32_t left_capacity, nh_QEventCtl* __restrict__ ctl) {
+	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i <= count; i += gridDim.x * blockDim.x) {
+		nh_q_events_offset(scan, cur.offsets, cur.capacity, count, i, entered, entered_capacity, &ctl->out_written[0]);
+		if (has_prev) nh_q_events_offset(scan + cur.capacity + 1u, prev.offsets, prev.capacity, count, i, left, left_capacity, &ctl->out_written[1]);
+		else left[i] = 0u;
+	}
+}
+
+__global__ __launch_bounds__(256) void k_q_events_compact(nh_QList cur, nh_QList prev, const uint32_t* __restrict__ scan, const nh_QEventCtl* __restrict__ ctl,
+                                                           uint4* __restrict__ entered, uint4* __restrict__ left) {
+	const uint64_t words = (uint64_t)cur.capacity + prev.capacity + 1u;          // (the last word is the flag of no record)
+	const uint32_t base = scan[cur.capacity + 1u];
+	for (uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; w < words; w += (uint64_t)gridDim.x * blockDim.x) {
+		const uint32_t at = scan[w];
+		if (scan[w + 1u] == at || w == cur.capacity) continue;
+		const bool l = w > cur.capacity;
+		const uint32_t r = (uint32_t)(l ? w - cur.capacity - 1u : w), pos = l ? at - base : at;
+		if (pos >= ctl->out_written[l ? 1 : 0] || r >= (l ? prev.capacity : cur.capacity)) continue;
+		(l ? left : entered)[pos] = reinterpret_cast<const uint4*>(l ? prev.hits : cur.hits)[r];
+	}
+}
+
+__global__ __launch_bounds__(256) void k_q_bodies_prefix(nh_QList in, uint32_t count, nh_QEventCtl* __restrict__ ctl) {
+	if (in.offsets[count] == NH_Q_NONE) return;          // (the marker: nothing was written; in_written stays 0)
+	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i <= count; i += gridDim.x * blockDim.x) {
+		const uint32_t lo = in.offsets[i];
+		if (i == count) { if (lo <= in.capacity) ctl->in_written = lo; continue; }
+		const uint32_t hi = in.offsets[i + 1u];
+		if (lo <= in.capacity && in.capacity < hi) ctl->in_written = lo;
+	}
+}
+
+__global__ __launch_bounds__(256) void k_q_bodies_keys(nh_QList in, uint32_t count, const nh_QEventCtl* __restrict__ ctl, uint64_t* __restrict__ keys,
+                                                        uint32_t* __restrict__ vals) {
+	const uint32_t m = min(ctl->in_written, in.capacity);
+	for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < m; r += gridDim.x * blockDim.x) {
+		const uint32_t i = min(nh_q_seg_of(in.offsets, count, r), count - 1u);
+		keys[r] = ((uint64_t)i << 32) | in.hits[4u * (size_t)r];
+		vals[r] = r;
+	}
+}
+
+__global__ __launch_bounds__(256) void k_q_bodies_flag(const uint64_t* __restrict__ keys, const nh_QEventCtl* __restrict__ ctl, uint32_t capacity,
+                                                        uint32_t* __restrict__ scan) {
+	const uint32_t m = min(ctl->in_written, capacity);
+	for (uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; w <= capacity; w += (uint64_t)gridDim.x * blockDim.x)
+		scan[w] = w < m && (w == 0u || keys[w] != keys[w - 1u]) ? 1u : 0u;
+}
+
+__global__ __launch_bounds__(256) void k_q_bodies_offsets(nh_QList in, uint32_t count, const uint32_t* __restrict__ scan, uint32_t* __restrict__ out,
+                                                           uint32_t out_capacity, nh_QEventCtl* __restrict__ ctl) {
+	const uint32_t m = min(ctl->in_written, in.capacity);          // (the sorted records of segment i lie where the input's did)
+	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i <= count; i += gridDim.x * blockDim.x)
+		nh_q_events_offset(scan, in.offsets, m, count, i, out, out_capacity, &ctl->out_written[0]);
+}
+
+__global__ __launch_bounds__(256) void k_q_bodies_compact(nh_QList in, const uint32_t* __restrict__ vals, const uint32_t* __restrict__ scan,
+                                                           const nh_QEventCtl* __restrict__ ctl, uint4* __restrict__ out) {
+	const uint32_t m = min(ctl->in_written, in.capacity), written = ctl->out_written[0];
+	for (uint32_t w = blockIdx.x * blockDim.x + threadIdx.x; w < m; w += gridDim.x * blockDim.x) {
+		const uint32_t at = scan[w], r = vals[w];
+		if (scan[w + 1u] == at || at >= written || r >= in.capacity) continue;
+		out[at] = reinterpret_cast<const uint4*>(in.hits)[r];
+	}
+}
+
+// The flag and scan words, by record of the input capacities' sum, and the control words (a growth waits for the stream first, as nh_overlap_reserve's does)
+static int nh_events_reserve(nh_context* ctx, uint32_t records) {
+	nh_QueryState* q = ctx->query;
+	if (q->ev_ctl && records <= q->ev_capacity) return NH_OK;
+	const uint64_t cap64 = (uint64_t)records + records / 8u + 64u;
+	const uint32_t cap = cap64 > 0xfffffffdull ? 0xfffffffdu : (uint32_t)cap64;
+	NH_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+	q->ev_capacity = 0;
+	{ int rc = nh_device_buffers(ctx, { { &q->ev_scan, sizeof(uint32_t) * ((size_t)cap + 2u) }, { &q->ev_ctl, sizeof(nh_QEventCtl) } }); if (rc) return rc; }
+	q->ev_capacity = cap;
+	return NH_OK;
+}
+
+static bool nh_hitlist_ok(const nh_HitList* l) {
+	return l && l->offsets && !((uintptr_t)l->offsets & 3u) && !(!l->hits && l->capacity) && !((uintptr_t)l->hits & 15u);
+}
+
+static nh_QList nh_hitlist_of(const nh_HitList* l) {
+	return l ? nh_QList{ l->offsets, reinterpret_cast<const uint32_t*>(l->hits), l->capacity } : nh_QList{ nullptr, nullptr, 0u };
+}
+
+// nh_overlap's checks in nh_overlap's order, then the lists'; then the scratch for `records` record slots.  The caller returns what this returns where
+// that is an error or count == 0.
+static int nh_events_args(nh_context* ctx, uint32_t count, uint32_t flags, uint32_t known_flags, std::initializer_list<const nh_HitList*> lists, uint64_t records) {
+	if (!ctx || !ctx->query || !ctx->query->built) return NH_ERR_INVALID;
+	if ((flags & ~known_flags) || count >= NH_Q_MAX_COLLIDERS) return NH_ERR_INVALID;
+	if (count == 0u) return NH_OK;
+	for (const nh_HitList* l : lists) if (!nh_hitlist_ok(l)) return NH_ERR_INVALID;
+	if (records + 2u > 0xffffffffull) return NH_ERR_INVALID;          // (the scan counts its words in 32 bits)
+	NH_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+	{ const int rc = nh_events_reserve(ctx, (uint32_t)records); if (rc) return rc; }
+	NH_HIP_CHECK(ctx, hipMemsetAsync(ctx->query->ev_ctl, 0, sizeof(nh_QEventCtl), ctx->stream));
+	return NH_OK;
+}
+
+extern "C" int nh_overlap_bodies(nh_context* ctx, uint32_t count, const nh_HitList* in, const nh_HitList* out, uint32_t flags) {
+	{ const int rc = nh_events_args(ctx, count, flags, 0u, { in, out }, in ? in->capacity : 0u); if (rc || count == 0u) return rc; }
+	nh_QueryState* q = ctx->query;
+	if (in->capacity == 0u || !in->hits) {          // (a count-only list holds no record: every segment counts 0)
+		NH_HIP_CHECK(ctx, hipMemsetAsync(out->offsets, 0, sizeof(uint32_t) * ((size_t)count + 1u), ctx->stream));
+		return NH_OK;
+	}
+	{ const int rc = nh_overlap_reserve(ctx, in->capacity); if (rc) return rc; }
+	const nh_QList L = nh_hitlist_of(in);
+	const bool list = out->hits != nullptr && out->capacity != 0u;
+	const uint32_t per_offset = nh_grid_for((uint64_t)count + 1u, 256, 4096), per_record = nh_grid_for((uint64_t)L.capacity + 1u, 256, 1u << 20);
+	NH_LAUNCH(ctx, "q_bodies_prefix", k_q_bodies_prefix, per_offset, 256, L, count, q->ev_ctl);
+	NH_LAUNCH(ctx, "q_bodies_keys", k_q_bodies_keys, per_record, 256, L, count, q->ev_ctl, q->ov_keys_a, q->ov_vals_a);
+	const int in_b = nh_sort_u64_u32(ctx, q->ov_keys_a, q->ov_keys_b, q->ov_vals_a, q->ov_vals_b, &q->ev_ctl->in_written, q->hist, 0,
+	                                 (32 + nh_q_bits(count) + 7) / 8 * 8);
+	NH_LAUNCH(ctx, "q_bodies_flag", k_q_bodies_flag, per_record, 256, in_b ? q->ov_keys_b : q->ov_keys_a, q->ev_ctl, L.capacity, q->ev_scan);
+	nh_scan_u32(ctx, q->ev_scan, q->ev_scan, &q->ctl->zero, L.capacity + 1u, q->hist, nullptr);
+	NH_LAUNCH(ctx, "q_bodies_offsets", k_q_bodies_offsets, per_offset, 256, L, count, q->ev_scan, out->offsets, list ? out->capacity : 0u, q->ev_ctl);
+	if (list) NH_LAUNCH(ctx, "q_bodies_compact", k_q_bodies_compact, per_record, 256, L, in_b ? q->ov_vals_b : q->ov_vals_a, q->ev_scan, q->ev_ctl,
+	                    reinterpret_cast<uint4*>(out->hits));
+	return NH_OK;
+}
+
+extern "C" int nh_overlap_events(nh_context* ctx, uint32_t count, const nh_HitList* prev, const nh_HitList* cur, const nh_HitList* entered,
+                                 const nh_HitList* left, uint32_t flags) {
+	{
+		const uint64_t records = (uint64_t)(cur ? cur->capacity : 0u) + (prev ? prev->capacity : 0u);
+		const int rc = prev ? nh_events_args(ctx, count, flags, NH_EVENTS_BY_BODY, { cur, entered, left, prev }, records)
+		                    : nh_events_args(ctx, count, flags, NH_EVENTS_BY_BODY, { cur, entered, left }, records);
+		if (rc || count == 0u) return rc;
+	}
+	nh_QueryState* q = ctx->query;
+	const nh_QList C = nh_hitlist_of(cur), P = nh_hitlist_of(prev);          // (a list without records has capacity 0: the argument rules)
+	const bool has_prev = prev != nullptr;
+	const bool list_e = entered->hits != nullptr && entered->capacity != 0u, list_l = left->hits != nullptr && left->capacity != 0u;
+	const uint32_t words = C.capacity + P.capacity + 2u;
+	const uint32_t per_record = nh_grid_for(words, 256, 1u << 20);
+	NH_LAUNCH(ctx, "q_events_flag", k_q_events_flag, per_record, 256, C, P, has_prev, count, flags & NH_EVENTS_BY_BODY ? 1u : 0u, q->ev_scan);
+	nh_scan_u32(ctx, q->ev_scan, q->ev_scan, &q->ctl->zero, words, q->hist, nullptr);
+	NH_LAUNCH(ctx, "q_events_offsets", k_q_events_offsets, nh_grid_for((uint64_t)count + 1u, 256, 4096), 256, C, P, has_prev, count, q->ev_scan, entered->offsets,
+	          list_e ? entered->capacity : 0u, left->offsets, list_l ? left->capacity : 0u, q->ev_ctl);
+	if (list_e || list_l) NH_LAUNCH(ctx, "q_events_compact", k_q_events_compact, per_record, 256, C, P, q->ev_scan, q->ev_ctl,
+	                                reinterpret_cast<uint4*>(entered->hits), reinterpret_cast<uint4*>(left->hits));
+	return NH_OK;
+}

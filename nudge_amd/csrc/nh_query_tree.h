@@ -23,6 +23,10 @@ struct nh_QNode { float4 a, b; };
 struct nh_QCtl { uint32_t count, zero, ov_written, ov_wrap; uint32_t smin[4]; uint32_t smax[4]; uint32_t kmin[4]; uint32_t kmax[4];
                  uint32_t top_n, top_depth, pad0, pad1; };
 
+// words of nh_overlap_bodies / nh_overlap_events (zeroed at the head of every call): the length of the input's written prefix (the sort reads it) and of
+// each output's (entered or the bodies' list, left)
+struct nh_QEventCtl { uint32_t in_written, out_written[2], pad; };
+
 struct nh_QueryState {
 	uint32_t capacity;           // colliders the buffers have room for
 	bool built;
@@ -43,6 +47,9 @@ struct nh_QueryState {
 	uint64_t* ov_keys_a; uint64_t* ov_keys_b; uint32_t* ov_vals_a; uint32_t* ov_vals_b;
 	uint32_t rg_capacity;        // nh_region's cursors, by region of the caller's count: where the list pass is in each region's segment
 	uint32_t* rg_cursor;
+	uint32_t ev_capacity;        // nh_overlap_bodies' / nh_overlap_events' flag and scan words, by record of the input capacities' sum (ev_scan: that + 2 words)
+	uint32_t* ev_scan;
+	struct nh_QEventCtl* ev_ctl; // their control words (allocated with the first scratch)
 	// layer masks (header, "layer masks"): the layer word of every collider of the last build, by combined index, and per node the OR of the words of
 	// the leaves below it (2 n - 1 words by node id, the layer pass writes them); both are only meaningful while layers_set
 	uint32_t layer_capacity;     // colliders the two arrays have room for

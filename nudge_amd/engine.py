@@ -47,6 +47,7 @@ EXPORTS = [
     "nh_raycast_k", "nh_spherecast_k", "nh_boxcast_k", "nh_capsulecast_k",
     "nh_move_touched", "nh_boxmove_touched", "nh_walk_touched", "nh_boxwalk_touched",
     "nh_query_set_layers", "nh_query_filter", "nh_query_layer_info",
+    "nh_overlap_bodies", "nh_overlap_events",
 ]
 HALO_RECORD_BYTES = 64
 
@@ -201,6 +202,12 @@ NH_RECOVER_PUSHED, NH_RECOVER_OVERLAPPING, NH_RECOVER_TOUCHING, NH_RECOVER_INVAL
 NH_OVERLAP_OVERFLOW = 0xFFFFFFFF          # offsets[count] when the total is 2^32 - 1 or more
 # nh_region (include/nudge_hip.h): up to NH_REGION_MAX_PLANES half-spaces (nx, ny, nz, d), inside where n.x + d >= 0
 NH_REGION_MAX_PLANES = 8
+NH_EVENTS_BY_BODY = 1                     # nh_overlap_events: a record's identity is its body (both inputs are nh_overlap_bodies' outputs)
+
+
+class HitList(C.Structure):
+    """nh_HitList: a host struct of device pointers."""
+    _fields_ = [("offsets", C.c_void_p), ("hits", C.c_void_p), ("capacity", C.c_uint32), ("reserved", C.c_uint32)]
 REGION = np.dtype([("planes", "<f4", (NH_REGION_MAX_PLANES, 4)), ("plane_count", "<u4"), ("ignore_body", "<u4"), ("reserved", "<u4", 2)])
 
 
@@ -368,6 +375,10 @@ def lib():
         if hasattr(L, "nh_boxcast_all"):
             L.nh_boxcast_all.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
             L.nh_capsulecast_all.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+        # (likewise the trigger events: World.overlap_bodies_records / overlap_events_records then raise AttributeError)
+        if hasattr(L, "nh_overlap_events"):
+            L.nh_overlap_bodies.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]
+            L.nh_overlap_events.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
         _LIB = L
     return _LIB
 
@@ -1477,6 +1488,85 @@ class World:
         if synchronize:
             torch.cuda.current_stream(self.dev).synchronize()
         return dict(offsets=off, written=written, query=query, body=u[:, 0], collider=u[:, 1], shape=u[:, 2], tag=u[:, 3], raw=hits)
+
+    # ---- trigger events: what entered and what left each overlap volume (include/nudge_hip.h, "trigger events") ----
+    def _hit_list(self, what, n, offsets, hits, capacity):
+        """The nh_HitList of (offsets, hits, capacity): `offsets` an int32 device tensor of n + 1 words, `hits` None or capacity x 16 bytes."""
+        if offsets.numel() * offsets.element_size() != 4 * (n + 1):
+            raise ValueError(f"{what}: offsets holds {offsets.numel() * offsets.element_size()} bytes, {n} volumes need {4 * (n + 1)}")
+        if hits is not None and hits.numel() * hits.element_size() < 16 * capacity:
+            raise ValueError(f"{what}: hits holds {hits.numel() * hits.element_size()} bytes, capacity {capacity} needs {16 * capacity}")
+        return HitList(offsets.data_ptr(), hits.data_ptr() if hits is not None and capacity else 0, capacity, 0)
+
+    def overlap_bodies_records(self, n, src, offsets=None, hits=None, capacity=0):
+        """nh_overlap_bodies: one record per distinct body of every present segment of the list `src` = (offsets, hits, capacity) that a list call of
+        overlap_records / region_records wrote for n volumes (int32 offsets, 16-byte records, the capacity that call was given).  Returns (offsets,
+        hits) as overlap_records does, under the same count-only and capacity rules.  Enqueued; nothing waits (but a capacity larger than any
+        before grows the scratch)."""
+        if offsets is None:
+            offsets = self.torch.empty(n + 1, dtype=self.torch.int32, device=self.dev)
+        a, b = self._hit_list("overlap_bodies_records (src)", n, *src), self._hit_list("overlap_bodies_records", n, offsets, hits, capacity)
+        _check(self.L, self.L.nh_overlap_bodies(self.ctx, n, C.byref(a), C.byref(b), 0), "nh_overlap_bodies")
+        return offsets, hits
+
+    def overlap_events_records(self, n, prev, cur, entered=None, left=None, by_body=False):
+        """nh_overlap_events on lists for n volumes, each (offsets, hits, capacity): `prev` (or None: the first frame) and `cur` as a list call or
+        overlap_bodies_records wrote them, `entered` and `left` the outputs (None: count only, with new offsets).  Returns (entered offsets, left
+        offsets).  Enqueued; nothing waits (but capacities larger than any before grow the scratch)."""
+        torch = self.torch
+        entered, left = (o if o is not None else (torch.empty(n + 1, dtype=torch.int32, device=self.dev), None, 0) for o in (entered, left))
+        p = None if prev is None else self._hit_list("overlap_events_records (prev)", n, *prev)
+        c, e, l = (self._hit_list(f"overlap_events_records ({k})", n, *v) for k, v in (("cur", cur), ("entered", entered), ("left", left)))
+        _check(self.L, self.L.nh_overlap_events(self.ctx, n, C.byref(p) if p is not None else None, C.byref(c), C.byref(e), C.byref(l),
+                                                NH_EVENTS_BY_BODY if by_body else 0), "nh_overlap_events")
+        return entered[0], left[0]
+
+    def _list_dict(self, offsets, hits, n, capacity):
+        """overlap()'s dict of a list: int32 offsets (n + 1), the records (capacity x 16 bytes)."""
+        torch = self.torch
+        off = offsets.to(torch.int64) & 0xFFFFFFFF
+        last = torch.searchsorted(off, torch.tensor([capacity], dtype=torch.int64, device=self.dev), right=True) - 1
+        written = torch.where(off[n] == NH_OVERLAP_OVERFLOW, torch.zeros_like(last), off[last.clamp(min=0)])[0]
+        j = torch.arange(capacity, dtype=torch.int64, device=self.dev)
+        query = (torch.searchsorted(off[1:], j, right=True) if n else j).clamp(max=max(n - 1, 0))
+        u = hits.view(torch.int32).reshape(-1, 4).to(torch.int64) & 0xFFFFFFFF
+        return dict(offsets=off, written=written, query=query, body=u[:, 0], collider=u[:, 1], shape=u[:, 2], tag=u[:, 3], raw=hits)
+
+    def overlap_events(self, prev, cur, by_body=False, capacity=None, synchronize=False):
+        """What entered and what left each volume between two lists: `prev` and `cur` are the dicts overlap() / region() returned for the same n
+        volumes on the last step and on this one (`prev` None: the first frame -- everything listed has entered).  by_body=True: one event per body,
+        not per collider (overlap_bodies on both lists first).  A volume whose segment either list's capacity cut off gives no event.
+        capacity=None: each output gets room for every record of its input -- nothing waits.  A capacity: both outputs list only the segments that
+        fit it.  Returns dict(entered=..., left=...), each in overlap()'s layout: `entered` holds records of `cur`, `left` records of `prev`."""
+        torch = self.torch
+        n = cur["offsets"].numel() - 1
+        if prev is not None and prev["offsets"].numel() != n + 1:
+            raise ValueError(f"overlap_events: prev lists {prev['offsets'].numel() - 1} volumes, cur {n}")
+        lists = []
+        for d in (prev, cur):
+            if d is None:
+                lists.append(None)
+                continue
+            cap = d["raw"].shape[0]
+            lst = (d["offsets"].to(torch.int32), d["raw"] if cap else None, cap)          # (int64 -> int32 keeps the low 32 bits: the marker too)
+            if by_body and n:
+                offsets = torch.empty(n + 1, dtype=torch.int32, device=self.dev)
+                hits = torch.empty((cap, 16), dtype=torch.uint8, device=self.dev)
+                self.overlap_bodies_records(n, lst, offsets=offsets, hits=hits if cap else None, capacity=cap)
+                lst = (offsets, hits if cap else None, cap)
+            lists.append(lst)
+        out = []
+        for src in lists:
+            cap = (src[2] if src is not None else 0) if capacity is None else capacity
+            out.append((torch.zeros(n + 1, dtype=torch.int32, device=self.dev), torch.empty((cap, 16), dtype=torch.uint8, device=self.dev), cap))
+        left, entered = out
+        if n:
+            self.overlap_events_records(n, lists[0], lists[1], entered=(entered[0], entered[1] if entered[2] else None, entered[2]),
+                                        left=(left[0], left[1] if left[2] else None, left[2]), by_body=by_body)
+        r = dict(entered=self._list_dict(entered[0], entered[1], n, entered[2]), left=self._list_dict(left[0], left[1], n, left[2]))
+        if synchronize:
+            torch.cuda.current_stream(self.dev).synchronize()
+        return r
 
     # ---- measurement ----
     def enable_timing(self, on=True, only=None):
