@@ -12,17 +12,26 @@
 
 struct Xf { float p[3]; uint32_t body; float q[4]; };
 
-extern "C" {
+// The world pose and the exact AABB of every collider (boxes first, then spheres), as k_xform computes them, and the broadphase's pair rule:
+// strictly overlapping AABBs (nudge.cpp:3306-3308) of colliders on two different bodies.  Shared by hs_collide and hs_pairs.
+struct Boxes {
+	std::vector<nh_xform> xf;
+	std::vector<float> mn, mx;
+	std::vector<uint32_t> tags;
+	bool is_pair(uint32_t i, uint32_t j) const {
+		const bool ov = mx[3*j] > mn[3*i] && mx[3*i] > mn[3*j] && mx[3*j+1] > mn[3*i+1] && mx[3*i+1] > mn[3*j+1] && mx[3*j+2] > mn[3*i+2] && mx[3*i+2] > mn[3*j+2];
+		return ov && xf[i].body != xf[j].body;
+	}
+};
 
-// World transforms + AABBs + morton keys for all colliders (boxes first, then spheres).
-// Returns number of contacts; outputs sorted by (key, feature).
-int hs_collide(const Xf* body_xf, uint32_t nbox, const Xf* box_xf, const float* box_size /*4 per*/, const uint32_t* box_tags,
-               uint32_t nsph, const Xf* sph_xf, const float* sph_radius, const uint32_t* sph_tags,
-               uint32_t cap, float* out_contacts /*8 per*/, uint32_t* out_bodies /*2 per*/, uint64_t* out_keys, uint32_t* out_features) {
-	uint32_t n = nbox + nsph;
-	std::vector<nh_xform> xf(n);
-	std::vector<float> mn(3 * n), mx(3 * n);
-	std::vector<uint32_t> tags(n);
+static Boxes world_boxes(const Xf* body_xf, uint32_t nbox, const Xf* box_xf, const float* box_size /*4 per*/, const uint32_t* box_tags,
+                         uint32_t nsph, const Xf* sph_xf, const float* sph_radius, const uint32_t* sph_tags) {
+	const uint32_t n = nbox + nsph;
+	Boxes w;
+	w.xf.resize(n); w.mn.resize(3 * (size_t)n); w.mx.resize(3 * (size_t)n); w.tags.resize(n);
+	std::vector<nh_xform>& xf = w.xf;
+	std::vector<float>& mn = w.mn; std::vector<float>& mx = w.mx;
+	std::vector<uint32_t>& tags = w.tags;
 	for (uint32_t i = 0; i < n; ++i) {
 		const Xf& l = i < nbox ? box_xf[i] : sph_xf[i - nbox];
 		const Xf& b = body_xf[l.body];
@@ -43,6 +52,38 @@ int hs_collide(const Xf* body_xf, uint32_t nbox, const Xf* box_xf, const float* 
 		mn[3*i+0] = lo.x; mn[3*i+1] = lo.y; mn[3*i+2] = lo.z;
 		mx[3*i+0] = hi.x; mx[3*i+1] = hi.y; mx[3*i+2] = hi.z;
 	}
+	return w;
+}
+
+extern "C" {
+
+// The broadphase's result by brute force: the collider index pairs (i < j) whose exact AABBs overlap strictly and whose bodies differ, in (i, j) order.
+// Returns their number; the first `cap` are written to out_pairs (2 per).  `out_aabb` (6 per collider: min xyz, max xyz), when given, receives the AABBs.
+long long hs_pairs(const Xf* body_xf, uint32_t nbox, const Xf* box_xf, const float* box_size /*4 per*/, uint32_t nsph, const Xf* sph_xf, const float* sph_radius,
+                   uint64_t cap, uint32_t* out_pairs, float* out_aabb) {
+	const uint32_t n = nbox + nsph;
+	std::vector<uint32_t> no_tags(n, 0u);
+	const Boxes w = world_boxes(body_xf, nbox, box_xf, box_size, no_tags.data(), nsph, sph_xf, sph_radius, no_tags.data());
+	if (out_aabb) for (uint32_t i = 0; i < n; ++i) { memcpy(out_aabb + 6*(size_t)i, &w.mn[3*(size_t)i], 12); memcpy(out_aabb + 6*(size_t)i + 3, &w.mx[3*(size_t)i], 12); }
+	uint64_t found = 0;
+	for (uint32_t i = 0; i < n; ++i) for (uint32_t j = i + 1; j < n; ++j) {
+		if (!w.is_pair(i, j)) continue;
+		if (found < cap) { out_pairs[2*found] = i; out_pairs[2*found+1] = j; }
+		++found;
+	}
+	return (long long)found;
+}
+
+// World transforms + AABBs + morton keys for all colliders (boxes first, then spheres).
+// Returns number of contacts; outputs sorted by (key, feature).
+int hs_collide(const Xf* body_xf, uint32_t nbox, const Xf* box_xf, const float* box_size /*4 per*/, const uint32_t* box_tags,
+               uint32_t nsph, const Xf* sph_xf, const float* sph_radius, const uint32_t* sph_tags,
+               uint32_t cap, float* out_contacts /*8 per*/, uint32_t* out_bodies /*2 per*/, uint64_t* out_keys, uint32_t* out_features) {
+	uint32_t n = nbox + nsph;
+	const Boxes w = world_boxes(body_xf, nbox, box_xf, box_size, box_tags, nsph, sph_xf, sph_radius, sph_tags);
+	const std::vector<nh_xform>& xf = w.xf;
+	const std::vector<float>& mn = w.mn;
+	const std::vector<uint32_t>& tags = w.tags;
 	// morton keys
 	nh_f3 smin = nh_make3(mn[0], mn[1], mn[2]), smax = smin;
 	for (uint32_t i = 1; i < n; ++i) {
@@ -58,9 +99,7 @@ int hs_collide(const Xf* body_xf, uint32_t nbox, const Xf* box_xf, const float* 
 	std::vector<Rec> recs;
 	uint32_t seq = 0;
 	for (uint32_t i = 0; i < n; ++i) for (uint32_t j = i + 1; j < n; ++j) {
-		bool ov = mx[3*j] > mn[3*i] && mx[3*i] > mn[3*j] && mx[3*j+1] > mn[3*i+1] && mx[3*i+1] > mn[3*j+1] && mx[3*j+2] > mn[3*i+2] && mx[3*i+2] > mn[3*j+2];
-		if (!ov) continue;
-		if (xf[i].body == xf[j].body) continue;
+		if (!w.is_pair(i, j)) continue;
 		// the pair's "a" = later in morton order (ties: the lower index comes first), then the pair by shape: what the kernels call
 		const bool i_first = nh_a_is_first(mk[i], mk[j], i, j);
 		const uint32_t a = i_first ? j : i, b = i_first ? i : j;

@@ -31,6 +31,21 @@ def collide(body_transforms, scene, cap=1 << 20):
     return dict(count=n, data=oc[:n], bodies=ob[:n], keys=ok[:n], features=of[:n])
 
 
+def pairs(body_transforms, scene, cap=1 << 22, aabbs=False):
+    """The broadphase's result by brute force (hs_pairs): the (m, 2) collider index pairs i < j, in (i, j) order, whose exact AABBs overlap strictly and whose
+    bodies differ; with `aabbs` also the (C, 6) float32 AABBs (min xyz, max xyz) they were tested with."""
+    L = lib()
+    nbox, nsph = len(scene["box_tags"]), len(scene["sphere_tags"])
+    bt = np.ascontiguousarray(body_transforms)
+    out = np.zeros((cap, 2), dtype=np.uint32)
+    box = np.zeros((nbox + nsph, 6), dtype=np.float32)
+    L.hs_pairs.restype = C.c_longlong
+    n = L.hs_pairs(_p(bt), C.c_uint32(nbox), _p(scene["box_transforms"]), _p(scene["box_data"]), C.c_uint32(nsph), _p(scene["sphere_transforms"]), _p(scene["sphere_data"]),
+                   C.c_uint64(cap), _p(out), _p(box))
+    assert n <= cap, (n, cap)
+    return (out[:n].copy(), box) if aabbs else out[:n].copy()
+
+
 def narrow_tags(keys, features):
     """(a_tag | b_tag<<32, feature) -> the reference's u64 tag (nudge.h:76)."""
     a = keys & np.uint64(0xFFFF)

@@ -1,0 +1,147 @@
+"""The crafted broadphase worlds of tests/broadphase_cases_util.py without a GPU: that the worlds are what they claim to be, that the brute-force host oracle
+(tests/hostsim: hs_collide, hs_pairs) equals the compiled reference on every one of them the reference can hold, phase by phase and bit for bit -- which is what
+lets tests/test_gpu_broadphase_cases.py use it as the oracle, also beyond the reference's 8192 colliders --, and that a numpy model of the documented rebuild rules
+(size class, budget, cell, margin, containment, the four `crowded` clauses, the stamp limit, the host's switch to the DIRECT search) predicts the path every
+script states: rebuilds, re-insertions and, where stated, the number of large colliders."""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import broadphase_cases_util as U          # noqa: E402
+import hostsim_util as H                    # noqa: E402
+import parity_util as P                     # noqa: E402
+from nudge_amd import scenes as S           # noqa: E402
+from oracle import refworld                 # noqa: E402
+
+needs_ref = pytest.mark.skipif(not refworld.available("exact"), reason="oracle/_ref not built (needs the reference sources: make -C oracle)")
+
+
+def _distinct(scene):
+    """(phase index, scene with the edits so far) of the phases whose placement has not been seen yet (stamp_wear and direct_and_back repeat theirs)."""
+    seen, out = set(), []
+    n_edits = 0
+    for k, ph in enumerate(scene["bp"]["phases"]):
+        n_edits += len(ph["edits"])
+        key = (ph["transforms"].tobytes(), n_edits)
+        if key not in seen:
+            seen.add(key)
+            out.append((k, U.scene_at(scene, k)))
+    return out
+
+
+@pytest.mark.parametrize("case", U.CASES)
+def test_broadphase_worlds_are_well_formed(case):
+    scene = U.world(case)
+    bp = scene["bp"]
+    C, nb = U.ncolliders(scene), len(scene["body_transforms"])
+    owners = np.concatenate([scene["box_transforms"]["body"], scene["sphere_transforms"]["body"]])
+    tags = np.concatenate([scene["box_tags"], scene["sphere_tags"]])
+    assert np.array_equal(tags, np.arange(C)), case
+    if bp["oracle"] in ("ref", "ref_only"):
+        assert C <= U.REF_LIMIT and C < (1 << 16) and S.narrow_ok(scene), case
+    assert not scene["body_momentum"].view(np.float32).any(), case
+    assert (scene["idle_counters"] == 0).all() or case == "sleeper_edge", case
+    assert np.array_equal(np.unique(owners[owners != 0]), np.arange(1, nb)), case          # (no dynamic body without a collider)
+    # a collider the script moves sits alone on its dynamic body, with an identity local transform
+    first = bp["phases"][0]["transforms"]
+    assert P.bits_equal(first, scene["body_transforms"]), case
+    moved = np.zeros(nb, dtype=bool)
+    for ph in bp["phases"]:
+        assert len(ph["transforms"]) == nb
+        moved |= (ph["transforms"].view(np.uint8).reshape(nb, -1) != first.view(np.uint8).reshape(nb, -1)).any(axis=1)
+    assert not moved[0]
+    local = np.concatenate([scene["box_transforms"], scene["sphere_transforms"]])
+    for body in np.flatnonzero(moved):
+        mine = np.flatnonzero(owners == body)
+        assert len(mine) == 1 and not local["position"][mine[0]].any() and np.array_equal(local["rotation"][mine[0]], np.array([0, 0, 0, 1], np.float32)), (case, body)
+    assert len(bp["phases"]) == 1 if bp["kind"] == "grid" else bp["phases"][0]["expect"] == (1, 0)
+    # the designated pairs
+    for k, sc in _distinct(scene):
+        ph = bp["phases"][k]
+        if bp["oracle"] == "list":
+            # (the O(n^2) oracle is too slow at 67,543 colliders: the pairs are known by construction, and checked here with the cell hashing of the util)
+            lo, hi, _ = U.plain_aabbs(sc, ph["transforms"])
+            have = {tuple(p) for p in U.overlap_pairs(lo, hi).tolist()}
+            assert sorted(have) == bp["known_pairs"], (case, k)
+        else:
+            prs, box = H.pairs(ph["transforms"], sc, aabbs=True)
+            have = {tuple(p) for p in prs.tolist()}
+            # (the util's own pair search, which the trigger model counts kept pairs with, against hs_pairs: same-body pairs taken out)
+            mine = U.overlap_pairs(box[:, :3].copy(), box[:, 3:].copy())
+            mine = {tuple(p) for p in mine[owners[mine[:, 0]] != owners[mine[:, 1]]].tolist()}
+            assert mine == have, (case, k, len(mine), len(have))
+            if bp["kind"] == "kept":
+                lo, hi, _ = U.plain_aabbs(sc, ph["transforms"])
+                assert P.bits_equal(lo, box[:, :3]) and P.bits_equal(hi, box[:, 3:]), (case, k)
+        assert have or case.startswith("fallbacks_esc"), case
+        for p in ph["pairs_in"]:
+            assert p in have, (case, k, ph["name"], "missing", p)
+        for p in ph["pairs_out"]:
+            assert p not in have, (case, k, ph["name"], "unexpected", p)
+    if case == "dense_cell":
+        assert len(have) == 19900
+    if case == "sparse_far":
+        assert (box[:, 3:] == box[:, :3]).all(axis=1).sum() == 12          # (the AABBs of zero extent)
+
+
+@needs_ref
+@pytest.mark.parametrize("case", [c for c in U.CASES if U._BUILDERS[c][1] == "ref"])
+def test_host_oracle_matches_reference_on_broadphase_worlds(case):
+    scene = U.world(case)
+    seen = 0
+    w, edits = None, -1
+    for k, sc in _distinct(scene):
+        ph = scene["bp"]["phases"][k]
+        n_edits = sum(len(p["edits"]) for p in scene["bp"]["phases"][:k + 1])
+        if n_edits != edits:          # (a collider was edited: the reference gets the edited world)
+            w, edits = refworld.RefWorld(sc, max_contacts=scene["bp"]["world"].get("max_contacts")), n_edits
+        w.set_bodies(transforms=ph["transforms"])
+        w.collide()
+        od, ob, ok, of, _ = P.oracle_contacts_sorted(w.contacts())
+        assert np.isfinite(od.view(np.float32)).all(), (case, k)
+        h = H.collide(ph["transforms"], sc, cap=1 << 17)
+        assert h["count"] == len(ok), (case, k, ph["name"], h["count"], len(ok))
+        assert np.array_equal(h["keys"], ok) and np.array_equal(h["features"], of), (case, k, ph["name"])
+        assert np.array_equal(h["bodies"], ob), (case, k, ph["name"])
+        assert P.bits_equal(h["data"], od), (case, k, ph["name"])
+        seen += len(ok)
+    # (sleeper_edge is not here: hostsim models no sleeping, the reference is that world's only oracle)
+    assert seen > 0
+
+
+@pytest.mark.parametrize("case", U.CASES)
+def test_trigger_model_predicts_the_scripts(case):
+    """The numpy model of the documented rules (broadphase_cases_util.Model; it never calls the library) against the path each script states."""
+    scene = U.world(case)
+    bp = scene["bp"]
+    m = U.model_for(scene)
+    line = []
+    for k, ph in enumerate(bp["phases"]):
+        sc = U.scene_at(scene, k)
+        if bp["kind"] == "kept":
+            lo, hi, _ = U.plain_aabbs(sc, ph["transforms"])
+        else:
+            box = _aabbs(ph["transforms"], sc)
+            lo, hi = box[:, :3].copy(), box[:, 3:].copy()
+        info = m.call(lo, hi)
+        got = (1 if info["rebuild"] else 0, info["inserts"])
+        assert got == ph["expect"], (case, k, ph["name"], got, ph["expect"], info)
+        if ph["large"] is not None:
+            assert info["large"] == ph["large"], (case, k, ph["name"], info["large"], ph["large"])
+        U.check_trigger(ph, info)
+        if ph["trigger"]:
+            line.append(f"{ph['name']}: {ph['trigger']}")
+        if k == 0:
+            print(f"\n[{case}] C {U.ncolliders(scene)}, first grid: origin {info['origin']}, cell {1.0 / float(info['cell_inv'])}, dims {info['dims']}, large {info['large']}")
+    if case == "sparse_far":
+        assert float(info["cell_inv"]) < 1.0 / 16.0          # (the cell has doubled many times over the 0.0125 of its size class)
+    if line:
+        print(f"[{case}] rebuild triggers: " + "; ".join(line))
+
+
+def _aabbs(transforms, scene):
+    """The exact AABBs of a world with rotated colliders: from the host build (the model needs the boxes, not the library's decisions)."""
+    return H.pairs(transforms, scene, cap=1 << 22, aabbs=True)[1]
