@@ -79,7 +79,7 @@
  *      exported the views: nh_set_option(ctx, "sync_exports_views", 1) restores that contract at its old price; INTEGRATION.md.)  Any entry point outside the sample's
  *      call order between nh_collide and nh_apply_impulses turns a still step into a full one first, so everything it observes is what a full step
  *      produces.  nh_Counts.still_steps / still_replays count them.
- *      The scene queries (nh_query_build, nh_query_refit, nh_raycast, nh_spherecast, nh_raycast_all, nh_spherecast_all, nh_boxcast_all, nh_capsulecast_all, nh_raycast_k, nh_spherecast_k, nh_boxcast_k, nh_capsulecast_k, nh_boxcast, nh_capsulecast, nh_overlap, nh_penetration, nh_region, nh_closest, nh_closest_k, nh_distance, nh_move, nh_recover, nh_walk, nh_boxmove, nh_boxwalk, nh_move_touched, nh_boxmove_touched, nh_walk_touched, nh_boxwalk_touched, nh_query_set_layers, nh_query_filter, nh_query_layer_info) are not entry points of the step in this sense: they neither export nor settle nor turn a still step into a
+ *      The scene queries (nh_query_build, nh_query_refit, nh_raycast, nh_spherecast, nh_raycast_all, nh_spherecast_all, nh_boxcast_all, nh_capsulecast_all, nh_raycast_k, nh_spherecast_k, nh_boxcast_k, nh_capsulecast_k, nh_boxcast, nh_capsulecast, nh_overlap, nh_penetration, nh_overlap_wide, nh_penetration_wide, nh_region, nh_closest, nh_closest_k, nh_distance, nh_move, nh_recover, nh_walk, nh_boxmove, nh_boxwalk, nh_move_touched, nh_boxmove_touched, nh_walk_touched, nh_boxwalk_touched, nh_query_set_layers, nh_query_filter, nh_query_layer_info) are not entry points of the step in this sense: they neither export nor settle nor turn a still step into a
  *      full one, and they do not count -- see "scene queries" below.
  *
  * Threading: one context = one HIP stream = one world at a time; no global mutable state.
@@ -438,6 +438,8 @@ int nh_query_stats(nh_context* ctx, nh_QueryStats* out);
        offsets, the tie rules, the reach rule.  The answers above are defined without the tree, so pruning by node words changes the work, never the bytes.
      - The four _touched forms of the movers (nh_move_touched, nh_boxmove_touched, nh_walk_touched, nh_boxwalk_touched) run their mover's casts under the same
        contract: results, counts and touches are those of the plain mover's casts on the masked world.
+     - The two wide forms (nh_overlap_wide, nh_penetration_wide) run under the same contract: they write what nh_overlap and nh_penetration write on the
+       masked world, NH_FILTER_PER_QUERY reading masks[i] for query i.
    Identities that follow:
      - mask 0 sees nothing: misses with t = max_t (max_distance), empty segments, counts 0;
      - all-ones layers (or none set) with any non-zero mask write the filter-off bytes;
@@ -844,13 +846,60 @@ int nh_penetration(nh_context* ctx, const nh_OverlapQuery* queries, uint32_t cou
    WHICH CALL FOR WHICH QUESTION: nh_region for a volume of a tile's size or more (nh_overlap takes 21 x as long to count at that size and 11,800 x for the
    world, where a full step takes 0.27 ms) and for anything that is not a sphere, a box or a capsule; nh_overlap for shapes of a body's size, where a lane per
    query is the right shape (1 M of them count in 0.64 ms) and its predicates are exact where this test is conservative (in (d) it lists 174 fewer of
-   29.8 M records).  Sizes between a body and a tile were not measured.  With 30 M records the sort of the shared chain is the largest part of the
+   29.8 M records).  For large spheres, boxes and capsules there is nh_overlap_wide (below): the same decomposition with nh_overlap's exact predicates; it and
+   nh_overlap cross at a radius of about 12 units, eight bodies across, on that world (4,096 spheres: nh_overlap 6 x faster at radius 1.5, 2 x at 6, equal at
+   12; nh_overlap_wide 2.5 x faster at 24, 16 x at 96, 38 x at a tile's 267).  With 30 M records the sort of the shared chain is the largest part of the
    list call.  DESIGN 10.16 has the tables and the per-label times.
    Not built: regions of more than eight planes; exact (non-conservative) convex intersection; queries on a partitioned world, as before. */
 #define NH_REGION_MAX_PLANES 8u
 typedef struct nh_Region { float planes[NH_REGION_MAX_PLANES][4]; uint32_t plane_count; uint32_t ignore_body; uint32_t reserved[2]; } nh_Region;   /* 144 B */
 int nh_region(nh_context* ctx, const nh_Region* regions, uint32_t count, uint32_t* offsets /* count + 1 */, nh_OverlapHit* hits, uint32_t capacity,
               uint32_t flags /* 0 */);
+
+/* nh_overlap_wide and nh_penetration_wide: nh_overlap and nh_penetration for LARGE volumes -- an explosion radius, a large trigger volume, a client's area
+   of interest, a vehicle-sized box.  nh_overlap gives one lane to a query, which is the right shape for a body-sized question and the wrong one for a
+   volume that holds thousands of colliders: one lane then walks thousands of nodes.  Here the work of ONE query spreads over the GPU, as nh_region's does,
+   with nh_overlap's exact predicates in place of the plane test -- so spheres and capsules can be asked, nothing is listed that only the conservative
+   plane test would keep, and the penetration form exists.
+   THE ANSWER, THE OUTPUT, THE ORDER AND THE CAPACITY RULE ARE nh_overlap's AND nh_penetration's, BYTE FOR BYTE: for the same queries on the same build or
+   refit nh_overlap_wide writes exactly what nh_overlap writes and nh_penetration_wide exactly what nh_penetration writes -- `offsets`, the records, and
+   every byte of `hits` behind the written prefix left untouched; COUNT ONLY with hits == NULL and capacity == 0; the CAPACITY prefix rule; offsets[count] =
+   0xffffffff and no record for a true total of 2^32 - 1 or more; an invalid query counts 0; a capsule of half height 0 is the sphere query; `ignore_body`;
+   a collider of a NaN pose is never listed.  Only the distribution of the work differs, and with it the time.
+   Returns NH_ERR_INVALID in the cases and in the order of nh_overlap (before any nh_query_build, flags != 0, count >= 2^30, `queries` null or not 16-byte
+   aligned, `offsets` null or not 4-byte aligned, `hits` null with capacity > 0 or not 16-byte aligned); count = 0 is a no-op that returns NH_OK.
+   OBSERVERS like nh_overlap (note 9): no view export, no settling of deferred gravity, no still step turned into a full one, no change to nh_Counts.
+   Everything is enqueued on the context's stream, except that a list call with a larger capacity than any before grows nh_overlap's sort scratch, and one
+   with a larger count than any before nh_region's cursor word per query, each after a stream synchronise.  Layer masks: both run under that contract.
+   THE CALLER CHOOSES THE CALL BY SIZE, as it chooses nh_region today; a batch that mixes body-sized and tile-sized volumes is the caller's to split (there
+   is no dispatch by size inside nh_overlap: its flags != 0 refusal stands).  The lists feed nh_overlap_events and nh_overlap_bodies as nh_overlap's do.
+   HOW: a work item is (query, entry node) over the entry nodes of nh_region.  A lane tests the entry's box against the query's padded world
+   AABB -- nh_overlap's own node test; for each item that is left a wave sweeps the entry's contiguous leaves, 64 a step, with the exact predicate of the
+   shape pair, the query decoded once per item at a wave-uniform address.  Counts are ballots summed by one integer atomic per item; the list pass
+   reserves slots of the query's segment by one atomic per step, and nh_overlap's sort and gathers make the bytes: no atomic decides a byte of the output.
+   Capsules of nonzero half height run in launches of their own, as in nh_overlap.
+   Timing labels: q_wide_count, q_wide_count_capsule, q_wide_list, q_wide_list_capsule, then nh_overlap's own.
+   MEASURED (tools/overlap_wide_rates.py -> profiles/overlap_wide_rates.log; one MI355X, one run, the landed config-2 world of 1,004,524 colliders of about
+   1.5 units and 9,823 entry nodes; ms per call, the best of 5 blocks of 20 calls by device events -- nh_overlap one call a block from 20 ms up; the
+   count-only call / it followed by the exactly sized list call; every pair wrote the same bytes):
+                                                                          nh_overlap_wide        nh_overlap            nh_region, the same boxes
+     (a) one box that is the world's AABB, 1,004,524 records               0.150 /  0.681     1783.3 / 5831.8           0.149 / 0.677
+     (d) 4,096 cubes of one tile's size (267 units), 29,798,281 records    1.102 /  7.014      33.50 / 109.73           1.558 / 8.342 (170 records more)
+     4,096 spheres of radius 1.5, 8,192 records                            0.377 /  1.208      0.059 /   0.222
+     4,096 spheres of radius 6, 84,418 records                             0.389 /  1.267      0.179 /   0.610
+     4,096 spheres of radius 12, 244,564 records                           0.411 /  1.344      0.391 /   1.248
+     4,096 spheres of radius 24, 861,337 records                           0.435 /  1.478      1.066 /   3.335
+     4,096 spheres of radius 96, 12,444,142 records                        0.729 /  3.684      12.02 /  38.15
+     4,096 spheres of radius 267, 89,800,260 records                       2.137 / 16.436      82.16 / 259.98
+     (d) through nh_penetration_wide / nh_penetration                      1.100 /  6.978      33.49 / 109.89
+   WHICH CALL FOR WHICH QUESTION: the two cross at a radius of about 12 units on that world -- a volume eight bodies across, 60 colliders a query.  Below it
+   nh_overlap: the wide call pays a node test per (query, entry node) whatever the size, 0.38 ms for 4,096 queries x 9,823 entries.  Above it nh_overlap_wide.
+   nh_region stays the call for volumes given by planes; for a box it is no faster than the exact test (d).
+   Not built: a dispatch by size inside nh_overlap; wide forms of nh_distance and nh_recover; queries on a partitioned world, as before. */
+int nh_overlap_wide(nh_context* ctx, const nh_OverlapQuery* queries, uint32_t count, uint32_t* offsets /* count + 1 */, nh_OverlapHit* hits,
+                    uint32_t capacity, uint32_t flags /* 0 */);
+int nh_penetration_wide(nh_context* ctx, const nh_OverlapQuery* queries, uint32_t count, uint32_t* offsets /* count + 1 */, nh_PenetrationHit* hits,
+                        uint32_t capacity, uint32_t flags /* 0 */);
 
 /* TRIGGER EVENTS -- nh_overlap_bodies and nh_overlap_events: what ENTERED and what LEFT each of `count` overlap volumes since the last step, per collider
    or per body, computed on the device from two lists.  A trigger volume, an explosion radius or a client's area of interest is listed every step by

@@ -5,6 +5,7 @@
 // colliders touching each of a batch of spheres, boxes or capsules, as variable-length segments) and nh_move (collide-and-slide: the capsule cast in a loop) and nh_recover
 // (shapes pushed out of what they overlap: the overlap walk in a loop, the penetration functions at its leaves).
 // nh_region (the colliders inside each of a batch of convex regions, through nh_overlap's chain) does not walk: it sweeps the leaves below the tree's entry nodes.
+// nh_overlap_wide / nh_penetration_wide (nh_overlap's and nh_penetration's bytes for large volumes) sweep the same way, with nh_overlap's predicates.
 // include/nudge_hip.h, "scene queries".
 // Layer masks (include/nudge_hip.h, "layer masks"): every query call walks under the mask(s) nh_query_filter set, in the FILTER = true instantiation of its kernel.
 // Traversal is stackless: a node that is missed or a leaf that is done continues at its ESCAPE link (the next node in pre-order after its subtree),
@@ -907,20 +908,82 @@ __global__ __launch_bounds__(256) void k_q_recover(const nh_Recover* __restrict_
 static_assert(sizeof(nh_Region) == 144 && NH_REGION_MAX_PLANES == NH_Q_REGION_MAX_PLANES, "nh_Region is nine 16-byte words; nh_query.h's plane bound is the header's");
 #define NH_Q_REGION_GRID 2048u
 
-template <bool LIST, bool FILTER>
-__global__ __launch_bounds__(256) void k_q_region(const nh_Region* __restrict__ regions, uint32_t count, uint32_t* offsets, const nh_QNode* __restrict__ nodes,
-                                                  const nh_QRec* __restrict__ rec, const uint32_t* __restrict__ idx, const uint32_t* __restrict__ last,
-                                                  const uint32_t* __restrict__ top, uint32_t n, uint32_t nbox, nh_QCtl* ctl, uint32_t* __restrict__ cursor,
-                                                  uint64_t* __restrict__ keys, uint32_t* __restrict__ vals, uint32_t cbits, nh_QFilter F) {
-	if (!LIST && blockIdx.x == 0 && threadIdx.x == 0) { ctl->ov_wrap = 0u; ctl->ov_written = 0u; }   // (k_q_overlap_fix sets both)
+// The volume of an item loop (nh_q_items, below).  valid(i): one lane decodes volume i for the node test and says whether it can list anything at all;
+// enters(lo, hi): false only where nothing in that box can be kept; sweep(i): i is wave-uniform, so every lane reads the volume at one address; keeps():
+// the exact per-collider decision; ignore: the volume's ignore_body.
+// nh_Region: the planes.
+struct nh_QPlanes {
+	const nh_Region* __restrict__ regions;
+	const float* pl;
+	uint32_t pc, ignore;
+	__device__ __forceinline__ bool valid(uint32_t i) {
+		pl = &regions[i].planes[0][0];
+		pc = regions[i].plane_count;
+		return nh_q_region_valid(pl, pc);
+	}
+	__device__ __forceinline__ bool enters(nh_f3 lo, nh_f3 hi) const {
+		bool in = true;
+		for (uint32_t k = 0u; k < pc; ++k)
+			if (nh_q_region_node_outside(nh_make3(pl[4u * k], pl[4u * k + 1u], pl[4u * k + 2u]), pl[4u * k + 3u], lo, hi)) in = false;
+		return in;
+	}
+	__device__ __forceinline__ void sweep(uint32_t i) {
+		pl = &regions[i].planes[0][0];
+		pc = regions[i].plane_count; ignore = regions[i].ignore_body;
+	}
+	__device__ __forceinline__ bool keeps(const nh_QShape& s, bool box) const { return nh_q_region_keeps(pl, pc, s.p, s.q, s.h, box); }
+};
+
+// nh_OverlapQuery, for nh_overlap_wide / nh_penetration_wide: k_q_overlap's geometry.  The decode is nh_QVolume; the node test is the query's world AABB
+// padded by 2^-18 of its largest coordinate against the box -- the expressions of k_q_overlap's `enter`, applied to the entry node alone -- and keeps() is
+// the predicate k_q_overlap picks for the shape pair.  CAPSULE: as in k_q_overlap, the capsules of nonzero half height (an invalid half height included)
+// run in an instantiation of their own and the other takes the spheres and boxes; one kernel for every shape needs 86 to 91 VGPRs, 5 waves per SIMD
+// where the two have 7.  A launch takes its own queries and adds nothing for the others.  In the sweep the shape is wave-uniform, so the
+// shape branch of keeps() is one branch for the wave.
+template <bool CAPSULE>
+struct nh_QWide {
+	const nh_OverlapQuery* __restrict__ queries;
+	nh_QVolume v;
+	nh_f3 lo, hi;
+	uint32_t ignore;
+	__device__ __forceinline__ bool valid(uint32_t i) {
+		v.read(reinterpret_cast<const float4*>(queries + i));
+		lo = v.c - v.e; hi = v.c + v.e;
+		const float s = fmaxf(fmaxf(fmaxf(fabsf(lo.x), fabsf(lo.y)), fmaxf(fabsf(lo.z), fabsf(hi.x))), fmaxf(fabsf(hi.y), fabsf(hi.z))) * 3.814697265625e-06f;
+		lo = nh_make3(lo.x - s, lo.y - s, lo.z - s); hi = nh_make3(hi.x + s, hi.y + s, hi.z + s);
+		return v.ok && v.capsule == CAPSULE;
+	}
+	__device__ __forceinline__ bool enters(nh_f3 nlo, nh_f3 nhi) const {
+		return nlo.x <= hi.x && lo.x <= nhi.x && nlo.y <= hi.y && lo.y <= nhi.y && nlo.z <= hi.z && lo.z <= nhi.z;
+	}
+	__device__ __forceinline__ void sweep(uint32_t i) {
+		v.read(reinterpret_cast<const float4*>(queries + i));
+		ignore = v.ignore;
+	}
+	__device__ __forceinline__ bool keeps(const nh_QShape& col, bool box) const {
+		const bool capsule = CAPSULE, sphere = !CAPSULE && v.sphere;
+		if (capsule) return box ? nh_q_overlap_capsule_box_a(v.c, v.a, v.h.x, col.p, col.q, col.h) : nh_q_overlap_capsule_sphere_a(v.c, v.a, v.h.x, col.p, col.h.x);
+		if (box) return sphere ? nh_q_overlap_sphere_box(v.c, v.h.x, col.p, col.q, col.h) : nh_q_overlap_box_box(v.c, v.q, v.h, col.p, col.q, col.h);
+		return sphere ? nh_q_overlap_sphere_sphere(v.c, v.h.x, col.p, col.h.x) : nh_q_overlap_sphere_box(col.p, col.h.x, v.c, v.q, v.h);
+	}
+};
+
+// The item loop of k_q_region and k_q_wide (the comment above): `first` -- the chain's first count launch -- resets the words k_q_overlap_fix sets; wpb: the
+// kernel's waves per workgroup (blockDim.x >> 6, read in the kernel itself).
+template <bool LIST, bool FILTER, class Vol>
+__device__ __forceinline__ void nh_q_items(const Vol V, bool first, uint32_t wpb, uint32_t count, uint32_t* offsets, const nh_QNode* __restrict__ nodes,
+                                           const nh_QRec* __restrict__ rec, const uint32_t* __restrict__ idx, const uint32_t* __restrict__ last,
+                                           const uint32_t* __restrict__ top, uint32_t n, uint32_t nbox, nh_QCtl* ctl, uint32_t* __restrict__ cursor,
+                                           uint64_t* __restrict__ keys, uint32_t* __restrict__ vals, uint32_t cbits, const nh_QFilter& F) {
+	if (!LIST && first && blockIdx.x == 0 && threadIdx.x == 0) { ctl->ov_wrap = 0u; ctl->ov_written = 0u; }   // (k_q_overlap_fix sets both)
 	const uint32_t written = LIST ? ctl->ov_written : 0u;
 	const uint32_t entries = n > NH_Q_RUN ? ctl->top_n : (n ? 1u : 0u);
 	const uint64_t total = (uint64_t)count * entries;
 	const uint32_t lane = nh_lane();
-	const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
+	const uint64_t waves = (uint64_t)gridDim.x * wpb;
 	const uint64_t per = (total + waves - 1u) / waves;
 	const uint32_t ch = per > 64u ? 64u : (uint32_t)per;
-	const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
+	const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * wpb + (threadIdx.x >> 6));
 	for (uint64_t item0 = (uint64_t)wave * ch; item0 < total; item0 += waves * ch) {
 		// ---- node test: lane l takes item item0 + l
 		const uint64_t item = item0 + lane;
@@ -934,17 +997,14 @@ __global__ __launch_bounds__(256) void k_q_region(const nh_Region* __restrict__ 
 				live = base < end && end <= written;
 			}
 			if (live) {
-				const float* pl = &regions[ri].planes[0][0];
-				const uint32_t pc = regions[ri].plane_count;
-				live = nh_q_region_valid(pl, pc);
+				Vol t = V;
+				live = t.valid(ri);
 				node = n > NH_Q_RUN ? top[e] : 0u;
 				if (node >= 2u * n - 1u) live = false;          // (cannot happen: a guard against reading outside the nodes)
 				if (FILTER && live) live = F.sees(node, F.of(ri));
 				if (live) {
 					const float4 na = nodes[node].a, nb = nodes[node].b;
-					const nh_f3 lo = nh_make3(na.x, na.y, na.z), hi = nh_make3(nb.x, nb.y, nb.z);
-					for (uint32_t k = 0u; k < pc; ++k)
-						if (nh_q_region_node_outside(nh_make3(pl[4u * k], pl[4u * k + 1u], pl[4u * k + 2u]), pl[4u * k + 3u], lo, hi)) live = false;
+					live = t.enters(nh_make3(na.x, na.y, na.z), nh_make3(nb.x, nb.y, nb.z));
 				}
 			}
 		}
@@ -963,8 +1023,8 @@ __global__ __launch_bounds__(256) void k_q_region(const nh_Region* __restrict__ 
 				jf = jl == e ? u - (n - 1u) : e;
 			}
 			if (jl >= n) jl = n - 1u;                           // (cannot happen; the sweep stays inside idx)
-			const float* pl = &regions[r].planes[0][0];
-			const uint32_t pc = regions[r].plane_count, ignore = regions[r].ignore_body;
+			Vol t = V;
+			t.sweep(r);
 			const uint32_t fm = FILTER ? F.of(r) : 0u;
 			const uint32_t seg = LIST ? offsets[r] : 0u, seg_end = LIST ? offsets[r + 1u] : 0u;
 			uint32_t found = 0u;
@@ -976,10 +1036,7 @@ __global__ __launch_bounds__(256) void k_q_region(const nh_Region* __restrict__ 
 					c = idx[j];
 					if (c < n && (!FILTER || F.sees(n - 1u + j, fm))) {
 						const nh_QRec q = rec[c];
-						if (__float_as_uint(q.a.w) != ignore) {
-							const nh_QShape s = nh_q_unpack(q);
-							keep = nh_q_region_keeps(pl, pc, s.p, s.q, s.h, c < nbox);
-						}
+						if (__float_as_uint(q.a.w) != t.ignore) keep = t.keeps(nh_q_unpack(q), c < nbox);
 					}
 				}
 				const uint64_t bal = __ballot(keep);
@@ -988,13 +1045,39 @@ __global__ __launch_bounds__(256) void k_q_region(const nh_Region* __restrict__ 
 					uint32_t at = 0u;
 					if (lane == 0u) at = atomicAdd(&cursor[r], (uint32_t)__popcll(bal));
 					at = seg + (uint32_t)__shfl((int)at, 0) + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
-					// (at < seg_end: the count pass found the same set; a guard against writing outside the region's segment)
+					// (at < seg_end: the count pass found the same set; a guard against writing outside the volume's segment)
 					if (keep && at < seg_end) { keys[at] = ((uint64_t)r << cbits) | c; vals[at] = c; }
 				}
 			}
 			if (!LIST && found && lane == 0u) atomicAdd(&offsets[r], found);
 		}
 	}
+}
+
+template <bool LIST, bool FILTER>
+__global__ __launch_bounds__(256) void k_q_region(const nh_Region* __restrict__ regions, uint32_t count, uint32_t* offsets, const nh_QNode* __restrict__ nodes,
+                                                  const nh_QRec* __restrict__ rec, const uint32_t* __restrict__ idx, const uint32_t* __restrict__ last,
+                                                  const uint32_t* __restrict__ top, uint32_t n, uint32_t nbox, nh_QCtl* ctl, uint32_t* __restrict__ cursor,
+                                                  uint64_t* __restrict__ keys, uint32_t* __restrict__ vals, uint32_t cbits, nh_QFilter F) {
+	nh_QPlanes V;
+	V.regions = regions;
+	nh_q_items<LIST, FILTER>(V, true, blockDim.x >> 6, count, offsets, nodes, rec, idx, last, top, n, nbox, ctl, cursor, keys, vals, cbits, F);
+}
+
+// ---- wide overlap -----------------------------------------------------------------------------------------------------------------------------
+// nh_overlap_wide / nh_penetration_wide: nh_overlap's and nh_penetration's bytes for volumes too large for a lane -- k_q_region's decomposition (a work
+// item is (query, entry node); a lane per node test, a wave per leaf sweep; ballot counts, an integer atomic per item on offsets[query], one per step
+// on the query's cursor) with k_q_overlap's geometry (nh_QWide).  The set is nh_overlap's: the entry's box is tested by the expressions of k_q_overlap's
+// walk, which never prune what the predicates accept, and below an entry every leaf meets the predicate itself, which rejects a NaN pose.
+// The atomics decide slots inside a segment only; nh_overlap's sort and gathers decide the bytes.  (registers, occupancy, rates.)
+template <bool LIST, bool CAPSULE, bool FILTER>
+__global__ __launch_bounds__(256) void k_q_wide(const nh_OverlapQuery* __restrict__ queries, uint32_t count, uint32_t* offsets, const nh_QNode* __restrict__ nodes,
+                                                const nh_QRec* __restrict__ rec, const uint32_t* __restrict__ idx, const uint32_t* __restrict__ last,
+                                                const uint32_t* __restrict__ top, uint32_t n, uint32_t nbox, nh_QCtl* ctl, uint32_t* __restrict__ cursor,
+                                                uint64_t* __restrict__ keys, uint32_t* __restrict__ vals, uint32_t cbits, nh_QFilter F) {
+	nh_QWide<CAPSULE> V;
+	V.queries = queries;
+	nh_q_items<LIST, FILTER>(V, !CAPSULE, blockDim.x >> 6, count, offsets, nodes, rec, idx, last, top, n, nbox, ctl, cursor, keys, vals, cbits, F);
 }
 
 // ---- all-hits casts ---------------------------------------------------------------------------------------------------------------------------
@@ -1326,61 +1409,6 @@ static void nh_overlap_offsets(nh_context* ctx, uint32_t* offsets, uint32_t coun
 	NH_LAUNCH(ctx, "q_overlap_fin", k_q_overlap_fin, 1, 1, offsets, count, q->ctl);
 }
 
-// The chain nh_overlap and nh_penetration share, from the argument checks to the sort: offsets are complete behind it, and for a list call (*list) the
-// written prefix (ctl->ov_written records) lies sorted by (query, combined collider index) in the ov_*_b buffers (*in_b) or the ov_*_a ones.  Each
-// entry point ends in its own gather.  `hits` is only checked here: records of either size are moved as 16-byte words.
-static int nh_overlap_chain(nh_context* ctx, const nh_OverlapQuery* queries, uint32_t count, uint32_t* offsets, const void* hits, uint32_t capacity,
-                            uint32_t flags, bool* list_out, int* in_b, uint32_t* cbits_out) {
-	*list_out = false;
-	bool list = false;
-	{ const int rc = nh_overlap_args(ctx, queries, count, offsets, hits, capacity, flags, &list); if (rc || count == 0u) return rc; }
-	nh_QueryState* q = ctx->query;
-	const uint32_t cbits = (uint32_t)nh_q_bits(q->n);
-	*cbits_out = cbits;
-	const uint32_t grid = nh_grid_for(count, 256, 1u << 20);
-	bool on;
-	const nh_QFilter F = nh_query_filter_of(q, &on);
-	NH_LAUNCH(ctx, "q_overlap_count", (on ? k_q_overlap<false, false, true> : k_q_overlap<false, false, false>), grid, 256, queries, count, offsets, q->nodes, q->rec,
-	          q->n, q->nbox, q->ctl, (uint64_t*)nullptr, (uint32_t*)nullptr, cbits, F);
-	NH_LAUNCH(ctx, "q_overlap_count_capsule", (on ? k_q_overlap<false, true, true> : k_q_overlap<false, true, false>), grid, 256, queries, count, offsets, q->nodes, q->rec,
-	          q->n, q->nbox, q->ctl, (uint64_t*)nullptr, (uint32_t*)nullptr, cbits, F);
-	nh_overlap_offsets(ctx, offsets, count, capacity);
-	if (!list) return NH_OK;
-	NH_LAUNCH(ctx, "q_overlap_list", (on ? k_q_overlap<true, false, true> : k_q_overlap<true, false, false>), grid, 256, queries, count, offsets, q->nodes, q->rec,
-	          q->n, q->nbox, q->ctl, q->ov_keys_a, q->ov_vals_a, cbits, F);
-	NH_LAUNCH(ctx, "q_overlap_list_capsule", (on ? k_q_overlap<true, true, true> : k_q_overlap<true, true, false>), grid, 256, queries, count, offsets, q->nodes, q->rec,
-	          q->n, q->nbox, q->ctl, q->ov_keys_a, q->ov_vals_a, cbits, F);
-	const int bits = (((int)cbits + nh_q_bits(count)) + 7) / 8 * 8;
-	*in_b = nh_sort_u64_u32(ctx, q->ov_keys_a, q->ov_keys_b, q->ov_vals_a, q->ov_vals_b, &q->ctl->ov_written, q->hist, 0, bits);
-	*list_out = true;
-	return NH_OK;
-}
-
-extern "C" int nh_overlap(nh_context* ctx, const nh_OverlapQuery* queries, uint32_t count, uint32_t* offsets, nh_OverlapHit* hits, uint32_t capacity,
-                          uint32_t flags) {
-	bool list = false;
-	int in_b = 0;
-	uint32_t cbits = 0u;
-	{ const int rc = nh_overlap_chain(ctx, queries, count, offsets, hits, capacity, flags, &list, &in_b, &cbits); if (rc || !list) return rc; }
-	nh_QueryState* q = ctx->query;
-	NH_LAUNCH(ctx, "q_overlap_gather", k_q_overlap_gather, nh_grid_for(capacity, 256, 4096), 256, in_b ? q->ov_vals_b : q->ov_vals_a, q->ctl, q->rec, q->n, q->nbox,
-	          hits);
-	return NH_OK;
-}
-
-// nh_overlap's chain with a gather that evaluates the pair function of each record (header: the same set, the same order, the same offsets).
-extern "C" int nh_penetration(nh_context* ctx, const nh_OverlapQuery* queries, uint32_t count, uint32_t* offsets, nh_PenetrationHit* hits, uint32_t capacity,
-                              uint32_t flags) {
-	bool list = false;
-	int in_b = 0;
-	uint32_t cbits = 0u;
-	{ const int rc = nh_overlap_chain(ctx, queries, count, offsets, hits, capacity, flags, &list, &in_b, &cbits); if (rc || !list) return rc; }
-	nh_QueryState* q = ctx->query;
-	NH_LAUNCH(ctx, "q_penetration_gather", k_q_penetration_gather, nh_grid_for(capacity, 256, 1u << 20), 256, in_b ? q->ov_keys_b : q->ov_keys_a,
-	          in_b ? q->ov_vals_b : q->ov_vals_a, q->ctl, q->rec, q->n, q->nbox, queries, count, cbits, hits);
-	return NH_OK;
-}
-
 // nh_region's cursors, by region of the caller's count (a growth waits for the stream first, as nh_overlap_reserve's does)
 static int nh_region_reserve(nh_context* ctx, uint32_t count) {
 	nh_QueryState* q = ctx->query;
@@ -1391,6 +1419,104 @@ static int nh_region_reserve(nh_context* ctx, uint32_t count) {
 	{ int rc = nh_device_buffers(ctx, { { &q->rg_cursor, sizeof(uint32_t) * (size_t)cap } }); if (rc) return rc; }
 	q->rg_capacity = cap;
 	return NH_OK;
+}
+
+// The chain nh_overlap and nh_penetration share, from the argument checks to the sort: offsets are complete behind it, and for a list call (*list) the
+// written prefix (ctl->ov_written records) lies sorted by (query, combined collider index) in the ov_*_b buffers (*in_b) or the ov_*_a ones.  Each
+// entry point ends in its own gather.  `hits` is only checked here: records of either size are moved as 16-byte words.
+// `wide` (nh_overlap_wide, nh_penetration_wide): k_q_wide in place of the walks, as nh_region runs k_q_region -- offsets[0 .. count] zeroed first, for the
+// count pass adds into them, and nh_region's cursors zeroed before the list pass.  Everything else is the same chain.
+static int nh_overlap_chain(nh_context* ctx, const nh_OverlapQuery* queries, uint32_t count, uint32_t* offsets, const void* hits, uint32_t capacity,
+                            uint32_t flags, bool wide, bool* list_out, int* in_b, uint32_t* cbits_out) {
+	*list_out = false;
+	bool list = false;
+	{ const int rc = nh_overlap_args(ctx, queries, count, offsets, hits, capacity, flags, &list); if (rc || count == 0u) return rc; }
+	if (wide && list) { const int rc = nh_region_reserve(ctx, count); if (rc) return rc; }
+	nh_QueryState* q = ctx->query;
+	const uint32_t cbits = (uint32_t)nh_q_bits(q->n);
+	*cbits_out = cbits;
+	// (wide: one wave per item at most, as in nh_region)
+	const uint32_t grid = wide ? nh_grid_for((uint64_t)count * (q->n ? q->n : 1u), 4u, NH_Q_REGION_GRID) : nh_grid_for(count, 256, 1u << 20);
+	bool on;
+	const nh_QFilter F = nh_query_filter_of(q, &on);
+	if (wide) {
+		NH_HIP_CHECK(ctx, hipMemsetAsync(offsets, 0, sizeof(uint32_t) * ((size_t)count + 1u), ctx->stream));
+		NH_LAUNCH(ctx, "q_wide_count", (on ? k_q_wide<false, false, true> : k_q_wide<false, false, false>), grid, 256, queries, count, offsets, q->nodes, q->rec, q->idx, q->last,
+		          q->top, q->n, q->nbox, q->ctl, (uint32_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, cbits, F);
+		NH_LAUNCH(ctx, "q_wide_count_capsule", (on ? k_q_wide<false, true, true> : k_q_wide<false, true, false>), grid, 256, queries, count, offsets, q->nodes, q->rec, q->idx,
+		          q->last, q->top, q->n, q->nbox, q->ctl, (uint32_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, cbits, F);
+	} else {
+		NH_LAUNCH(ctx, "q_overlap_count", (on ? k_q_overlap<false, false, true> : k_q_overlap<false, false, false>), grid, 256, queries, count, offsets, q->nodes, q->rec,
+		          q->n, q->nbox, q->ctl, (uint64_t*)nullptr, (uint32_t*)nullptr, cbits, F);
+		NH_LAUNCH(ctx, "q_overlap_count_capsule", (on ? k_q_overlap<false, true, true> : k_q_overlap<false, true, false>), grid, 256, queries, count, offsets, q->nodes, q->rec,
+		          q->n, q->nbox, q->ctl, (uint64_t*)nullptr, (uint32_t*)nullptr, cbits, F);
+	}
+	nh_overlap_offsets(ctx, offsets, count, capacity);
+	if (!list) return NH_OK;
+	if (wide) {
+		NH_HIP_CHECK(ctx, hipMemsetAsync(q->rg_cursor, 0, sizeof(uint32_t) * (size_t)count, ctx->stream));
+		NH_LAUNCH(ctx, "q_wide_list", (on ? k_q_wide<true, false, true> : k_q_wide<true, false, false>), grid, 256, queries, count, offsets, q->nodes, q->rec, q->idx, q->last,
+		          q->top, q->n, q->nbox, q->ctl, q->rg_cursor, q->ov_keys_a, q->ov_vals_a, cbits, F);
+		NH_LAUNCH(ctx, "q_wide_list_capsule", (on ? k_q_wide<true, true, true> : k_q_wide<true, true, false>), grid, 256, queries, count, offsets, q->nodes, q->rec, q->idx,
+		          q->last, q->top, q->n, q->nbox, q->ctl, q->rg_cursor, q->ov_keys_a, q->ov_vals_a, cbits, F);
+	} else {
+		NH_LAUNCH(ctx, "q_overlap_list", (on ? k_q_overlap<true, false, true> : k_q_overlap<true, false, false>), grid, 256, queries, count, offsets, q->nodes, q->rec,
+		          q->n, q->nbox, q->ctl, q->ov_keys_a, q->ov_vals_a, cbits, F);
+		NH_LAUNCH(ctx, "q_overlap_list_capsule", (on ? k_q_overlap<true, true, true> : k_q_overlap<true, true, false>), grid, 256, queries, count, offsets, q->nodes, q->rec,
+		          q->n, q->nbox, q->ctl, q->ov_keys_a, q->ov_vals_a, cbits, F);
+	}
+	const int bits = (((int)cbits + nh_q_bits(count)) + 7) / 8 * 8;
+	*in_b = nh_sort_u64_u32(ctx, q->ov_keys_a, q->ov_keys_b, q->ov_vals_a, q->ov_vals_b, &q->ctl->ov_written, q->hist, 0, bits);
+	*list_out = true;
+	return NH_OK;
+}
+
+// nh_overlap and nh_overlap_wide: the chain, then the gather of nh_OverlapHit
+static int nh_overlap_call(nh_context* ctx, const nh_OverlapQuery* queries, uint32_t count, uint32_t* offsets, nh_OverlapHit* hits, uint32_t capacity, uint32_t flags,
+                           bool wide) {
+	bool list = false;
+	int in_b = 0;
+	uint32_t cbits = 0u;
+	{ const int rc = nh_overlap_chain(ctx, queries, count, offsets, hits, capacity, flags, wide, &list, &in_b, &cbits); if (rc || !list) return rc; }
+	nh_QueryState* q = ctx->query;
+	NH_LAUNCH(ctx, "q_overlap_gather", k_q_overlap_gather, nh_grid_for(capacity, 256, 4096), 256, in_b ? q->ov_vals_b : q->ov_vals_a, q->ctl, q->rec, q->n, q->nbox,
+	          hits);
+	return NH_OK;
+}
+
+// nh_penetration and nh_penetration_wide: nh_overlap's chain with a gather that evaluates the pair function of each record (header: the same set, the same
+// order, the same offsets).
+static int nh_penetration_call(nh_context* ctx, const nh_OverlapQuery* queries, uint32_t count, uint32_t* offsets, nh_PenetrationHit* hits, uint32_t capacity,
+                               uint32_t flags, bool wide) {
+	bool list = false;
+	int in_b = 0;
+	uint32_t cbits = 0u;
+	{ const int rc = nh_overlap_chain(ctx, queries, count, offsets, hits, capacity, flags, wide, &list, &in_b, &cbits); if (rc || !list) return rc; }
+	nh_QueryState* q = ctx->query;
+	NH_LAUNCH(ctx, "q_penetration_gather", k_q_penetration_gather, nh_grid_for(capacity, 256, 1u << 20), 256, in_b ? q->ov_keys_b : q->ov_keys_a,
+	          in_b ? q->ov_vals_b : q->ov_vals_a, q->ctl, q->rec, q->n, q->nbox, queries, count, cbits, hits);
+	return NH_OK;
+}
+
+extern "C" int nh_overlap(nh_context* ctx, const nh_OverlapQuery* queries, uint32_t count, uint32_t* offsets, nh_OverlapHit* hits, uint32_t capacity,
+                          uint32_t flags) {
+	return nh_overlap_call(ctx, queries, count, offsets, hits, capacity, flags, false);
+}
+
+extern "C" int nh_penetration(nh_context* ctx, const nh_OverlapQuery* queries, uint32_t count, uint32_t* offsets, nh_PenetrationHit* hits, uint32_t capacity,
+                              uint32_t flags) {
+	return nh_penetration_call(ctx, queries, count, offsets, hits, capacity, flags, false);
+}
+
+// The wide forms (header, "nh_overlap_wide"): the same bytes, the work of one query spread over the GPU.
+extern "C" int nh_overlap_wide(nh_context* ctx, const nh_OverlapQuery* queries, uint32_t count, uint32_t* offsets, nh_OverlapHit* hits, uint32_t capacity,
+                               uint32_t flags) {
+	return nh_overlap_call(ctx, queries, count, offsets, hits, capacity, flags, true);
+}
+
+extern "C" int nh_penetration_wide(nh_context* ctx, const nh_OverlapQuery* queries, uint32_t count, uint32_t* offsets, nh_PenetrationHit* hits, uint32_t capacity,
+                                   uint32_t flags) {
+	return nh_penetration_call(ctx, queries, count, offsets, hits, capacity, flags, true);
 }
 
 // nh_overlap's chain with k_q_region in place of the walks: nh_overlap's argument rules, offsets and capacity contract, sort and gather (the comment above

@@ -48,6 +48,7 @@ EXPORTS = [
     "nh_move_touched", "nh_boxmove_touched", "nh_walk_touched", "nh_boxwalk_touched",
     "nh_query_set_layers", "nh_query_filter", "nh_query_layer_info",
     "nh_overlap_bodies", "nh_overlap_events",
+    "nh_overlap_wide", "nh_penetration_wide",
 ]
 HALO_RECORD_BYTES = 64
 
@@ -367,6 +368,10 @@ def lib():
         # (an older build of the library, loaded through NUDGE_HIP_LIBRARY for an A/B, has no nh_region: World.region then raises AttributeError)
         if hasattr(L, "nh_region"):
             L.nh_region.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+        # (likewise the wide forms of nh_overlap and nh_penetration: World.overlap_wide / penetration_wide then raise AttributeError)
+        if hasattr(L, "nh_overlap_wide"):
+            L.nh_overlap_wide.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+            L.nh_penetration_wide.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
         # (an older build of the library, loaded through NUDGE_HIP_LIBRARY for an A/B, has no all-hits casts: World.raycast_all then raises AttributeError)
         if hasattr(L, "nh_raycast_all"):
             L.nh_raycast_all.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
@@ -1444,6 +1449,51 @@ class World:
         torch = self.torch
         q, n = self._overlap_queries("penetration", centres, radii, half_extents, rotations, ignore_body, half_heights)
         hits, off, written, query = self._overlap_lists(self.penetration_records, q, n, capacity, 32)
+        f = hits.view(torch.float32).reshape(-1, 8)
+        u = hits.view(torch.int32).reshape(-1, 8).to(torch.int64) & 0xFFFFFFFF
+        if synchronize:
+            torch.cuda.current_stream(self.dev).synchronize()
+        return dict(offsets=off, written=written, query=query, normal=f[:, 0:3], depth=f[:, 3], body=u[:, 4], collider=u[:, 5], shape=u[:, 6], tag=u[:, 7],
+                    raw=hits)
+
+    # ---- the wide forms: nh_overlap's and nh_penetration's bytes, the work of one query spread over the GPU (include/nudge_hip.h, "nh_overlap_wide") ----
+    def _wide_records(self, name, size, queries, offsets, hits, capacity):
+        torch = self.torch
+        n = queries.numel() * queries.element_size() // 48
+        if offsets is None:
+            offsets = torch.empty(n + 1, dtype=torch.int32, device=self.dev)
+        if hits is not None and hits.numel() * hits.element_size() < size * capacity:
+            raise ValueError(f"{name[3:]}_records: hits holds {hits.numel() * hits.element_size()} bytes, capacity {capacity} needs {size * capacity}")
+        _check(self.L, getattr(self.L, name)(self.ctx, C.c_void_p(queries.data_ptr() if n else 0), n, C.c_void_p(offsets.data_ptr()),
+                                             C.c_void_p(hits.data_ptr() if hits is not None else 0), capacity, 0), name)
+        return offsets, hits
+
+    def overlap_wide_records(self, queries, offsets=None, hits=None, capacity=0):
+        """nh_overlap_wide on nh_OverlapQuery records: overlap_records' arguments, rules and bytes.  Enqueued; nothing waits (but a capacity or a
+        count larger than any before grows the scratch)."""
+        return self._wide_records("nh_overlap_wide", 16, queries, offsets, hits, capacity)
+
+    def penetration_wide_records(self, queries, offsets=None, hits=None, capacity=0):
+        """nh_penetration_wide on nh_OverlapQuery records: penetration_records' arguments, rules and bytes (32-byte records)."""
+        return self._wide_records("nh_penetration_wide", 32, queries, offsets, hits, capacity)
+
+    def overlap_wide(self, centres, radii=None, half_extents=None, rotations=None, ignore_body=None, capacity=None, synchronize=False, half_heights=None):
+        """overlap() for LARGE volumes -- an explosion radius, a trigger volume, an area of interest: the same arguments and the same dict, byte for
+        byte, through nh_overlap_wide, which spreads the work of one query over the GPU where overlap() gives it one lane.  Which of the two is faster
+        depends on the size alone (header, "which call for which question"); a mixed batch is the caller's to split."""
+        torch = self.torch
+        q, n = self._overlap_queries("overlap_wide", centres, radii, half_extents, rotations, ignore_body, half_heights)
+        hits, off, written, query = self._overlap_lists(self.overlap_wide_records, q, n, capacity, 16)
+        u = hits.view(torch.int32).reshape(-1, 4).to(torch.int64) & 0xFFFFFFFF
+        if synchronize:
+            torch.cuda.current_stream(self.dev).synchronize()
+        return dict(offsets=off, written=written, query=query, body=u[:, 0], collider=u[:, 1], shape=u[:, 2], tag=u[:, 3], raw=hits)
+
+    def penetration_wide(self, centres, radii=None, half_extents=None, rotations=None, ignore_body=None, capacity=None, synchronize=False, half_heights=None):
+        """penetration() for large volumes: the same arguments and the same dict, byte for byte, through nh_penetration_wide (see overlap_wide)."""
+        torch = self.torch
+        q, n = self._overlap_queries("penetration_wide", centres, radii, half_extents, rotations, ignore_body, half_heights)
+        hits, off, written, query = self._overlap_lists(self.penetration_wide_records, q, n, capacity, 32)
         f = hits.view(torch.float32).reshape(-1, 8)
         u = hits.view(torch.int32).reshape(-1, 8).to(torch.int64) & 0xFFFFFFFF
         if synchronize:
