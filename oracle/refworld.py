@@ -98,7 +98,12 @@ class RefWorld:
             # worst temp of collide = coarse_count^2 u32 (nudge.cpp:3276) + scheduler buckets (4222-4223)
             arena_bytes = (64 << 20) + max_contacts * 1400
         self.params = dict(scene["params"])
-        self.h = self.L.ref_world_create(nb, max(nbox, 1), max(nsph, 1), max_contacts, arena_bytes)
+        # (the binding gives the connection list room for one entry per body of CAPACITY: a scene with more connections than bodies asks for that many bodies' room;
+        # the counts handed to the reference below are the scene's own)
+        con = np.zeros((0, 2), dtype=np.uint16)
+        if "connections" in scene and len(scene["connections"]):
+            con = np.asarray(scene["connections"], dtype=np.uint16).reshape(-1, 2)
+        self.h = self.L.ref_world_create(max(nb, len(con)), max(nbox, 1), max(nsph, 1), max_contacts, arena_bytes)
         self.max_contacts = max_contacts
         v = self._view()
         _view_array(v.body_transforms, S.TRANSFORM, nb)[:] = scene["body_transforms"]
@@ -113,10 +118,8 @@ class RefWorld:
             _view_array(v.sphere_tags, np.uint16, nsph)[:] = scene["sphere_tags"].astype(np.uint16)
             _view_array(v.sphere_data, S.SPHERE, nsph)[:] = scene["sphere_data"]
             _view_array(v.sphere_transforms, S.TRANSFORM, nsph)[:] = scene["sphere_transforms"]
-        ncon = 0
-        if "connections" in scene and len(scene["connections"]):
-            con = np.asarray(scene["connections"], dtype=np.uint16).reshape(-1, 2)
-            ncon = len(con)
+        ncon = len(con)
+        if ncon:
             _view_array(v.connections, np.uint16, 2 * ncon)[:] = con.reshape(-1)
         self.L.ref_world_set_counts(self.h, nb, nbox, nsph, ncon)
         self.n_bodies, self.n_boxes, self.n_spheres = nb, nbox, nsph
@@ -166,6 +169,18 @@ class RefWorld:
             ab[:m] = ab[keep].copy(); tags[:m] = tags[keep].copy(); data[:m] = data[keep].copy()
             self.L.ref_world_set_contact_count(self.h, m)
         return n - m
+
+    def append_contacts(self, data, bodies, tags):
+        """Between collide() and read_cache(): custom contacts behind the list ("Custom contacts can be added here", example/main.cpp:287); `tags` in the reference's
+        narrow format."""
+        v = self._view()
+        n, k = v.contact_count, len(tags)
+        if n + k > self.max_contacts:
+            raise ValueError("append_contacts: contact capacity")
+        _view_array(v.contact_data, self.S.CONTACT, n + k)[n:] = data
+        _view_array(v.contact_bodies, np.uint16, 2 * (n + k)).reshape(-1, 2)[n:] = np.asarray(bodies, dtype=np.uint16).reshape(-1, 2)
+        _view_array(v.contact_tags, np.uint64, n + k)[n:] = np.asarray(tags, dtype=np.uint64)
+        self.L.ref_world_set_contact_count(self.h, n + k)
 
     def read_cache(self): self.L.ref_stage_read_cache(self.h)
     def setup(self): self.L.ref_stage_setup(self.h)

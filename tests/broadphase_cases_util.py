@@ -31,7 +31,7 @@ KEPT-LIST worlds (base: 16 x 8 x 16 cubes of extent 7/8 that touch their x neigh
 from writing in place, so that raw_pairs counts overlapping pairs --, a static slab under them, two dynamic walls, eight movers resting on the top layer; cell 1,
 margin 1/32 after the first rebuild; the first collide() rebuilds):
   wiggle, one_leaver, leavers_meet, stamp_wear, fallbacks, fallbacks_kept (max_pairs 2048: the 7/8 rule), fallbacks_combos (16,400 colliders), fallbacks_esc
-  (67,543 colliders: pairs known by construction), direct_and_back, sleeper_edge (reference only: hostsim models no sleeping) -- see each builder.
+  (67,543 colliders: pairs known by construction), direct_and_back, sleeper_edge (reference only here: hostsim models no sleeping; the numpy oracle for islands and sleeping is tests/island_cases_util.islands) -- see each builder.
 
 What the clauses of k_grid_setup allow (asserted by `check_trigger`): moved >= leavers always (a first-time leaver joins the moved list in the same pass), so
 "leavers x 16 > C" implies "moved x 32 > C" and can never be the only clause that holds; and more than NH_ESC_MAX leavers imply moved x 32 > C below 131,104

@@ -108,7 +108,7 @@ def test_host_oracle_matches_reference_on_broadphase_worlds(case):
         assert np.array_equal(h["bodies"], ob), (case, k, ph["name"])
         assert P.bits_equal(h["data"], od), (case, k, ph["name"])
         seen += len(ok)
-    # (sleeper_edge is not here: hostsim models no sleeping, the reference is that world's only oracle)
+    # (sleeper_edge is not here: hostsim models no sleeping; the reference is that world's oracle, and tests/island_cases_util.py holds the numpy oracle for sleeping)
     assert seen > 0
 
 
