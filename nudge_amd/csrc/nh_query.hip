@@ -1421,81 +1421,105 @@ static int nh_region_reserve(nh_context* ctx, uint32_t count) {
 	return NH_OK;
 }
 
-// The chain nh_overlap and nh_penetration share, from the argument checks to the sort: offsets are complete behind it, and for a list call (*list) the
-// written prefix (ctl->ov_written records) lies sorted by (query, combined collider index) in the ov_*_b buffers (*in_b) or the ov_*_a ones.  Each
-// entry point ends in its own gather.  `hits` is only checked here: records of either size are moved as 16-byte words.
-// `wide` (nh_overlap_wide, nh_penetration_wide): k_q_wide in place of the walks, as nh_region runs k_q_region -- offsets[0 .. count] zeroed first, for the
-// count pass adds into them, and nh_region's cursors zeroed before the list pass.  Everything else is the same chain.
-static int nh_overlap_chain(nh_context* ctx, const nh_OverlapQuery* queries, uint32_t count, uint32_t* offsets, const void* hits, uint32_t capacity,
-                            uint32_t flags, bool wide, bool* list_out, int* in_b, uint32_t* cbits_out) {
-	*list_out = false;
+// ---- the list calls: one host chain --------------------------------------------------------------------------------------------------------------
+// nh_overlap, nh_penetration, their wide forms, nh_region and the four all-hits casts run one chain, nh_list_chain, and end in their own gather.  They differ in
+// `walk`, a callable that enqueues one pass over the tree given an nh_QPass (the count pass: list false, cursor / keys / vals null; then the list pass), and in
+//   spread   the walk deals (query, entry node) items to waves (k_q_wide, k_q_region): it ADDS into offsets, so offsets[0 .. count] are zeroed before the count
+//            pass; it takes nh_region's cursors, reserved for a list call and zeroed before the list pass; its grid is one wave per item at most
+//   by_t     the all-hits casts' key plan (the comment above k_q_castall): one sort where query, t and collider fit 64 bits, or else the sort by collider,
+//            q_castall_rekey, the sort by (query, t).  Otherwise one sort by (query, combined collider index).
+struct nh_QPass { bool list, on; nh_QFilter F; uint32_t grid, cbits, one_sort; uint32_t* cursor; uint64_t* keys; uint32_t* vals; };
+// Where the chain left the written prefix (ctl->ov_written records) of a list call, sorted; keys null: a count-only call, or count == 0.
+struct nh_QSorted { uint64_t* keys; uint32_t* vals; uint32_t cbits, one_sort; };
+
+// The instantiation a pass launches: LIST or not, FILTER or not.
+template <class K>
+static K nh_q_pass_kernel(const nh_QPass& p, K count, K count_filtered, K list, K list_filtered) {
+	return p.list ? (p.on ? list_filtered : list) : (p.on ? count_filtered : count);
+}
+
+// From the argument checks to the sort or sorts: offsets are complete behind it.  `hits` is only checked here: records of any size are moved as 16-byte words.  The
+// caller returns what this returns where that is an error or out->keys is null.
+template <class Walk>
+static int nh_list_chain(nh_context* ctx, const void* in, uint32_t count, uint32_t* offsets, const void* hits, uint32_t capacity, uint32_t flags, bool spread,
+                         bool by_t, Walk walk, nh_QSorted* out) {
+	*out = nh_QSorted{};
 	bool list = false;
-	{ const int rc = nh_overlap_args(ctx, queries, count, offsets, hits, capacity, flags, &list); if (rc || count == 0u) return rc; }
-	if (wide && list) { const int rc = nh_region_reserve(ctx, count); if (rc) return rc; }
+	{ const int rc = nh_overlap_args(ctx, in, count, offsets, hits, capacity, flags, &list); if (rc || count == 0u) return rc; }
+	if (spread && list) { const int rc = nh_region_reserve(ctx, count); if (rc) return rc; }
 	nh_QueryState* q = ctx->query;
-	const uint32_t cbits = (uint32_t)nh_q_bits(q->n);
-	*cbits_out = cbits;
-	// (wide: one wave per item at most, as in nh_region)
-	const uint32_t grid = wide ? nh_grid_for((uint64_t)count * (q->n ? q->n : 1u), 4u, NH_Q_REGION_GRID) : nh_grid_for(count, 256, 1u << 20);
-	bool on;
-	const nh_QFilter F = nh_query_filter_of(q, &on);
-	if (wide) {
-		NH_HIP_CHECK(ctx, hipMemsetAsync(offsets, 0, sizeof(uint32_t) * ((size_t)count + 1u), ctx->stream));
-		NH_LAUNCH(ctx, "q_wide_count", (on ? k_q_wide<false, false, true> : k_q_wide<false, false, false>), grid, 256, queries, count, offsets, q->nodes, q->rec, q->idx, q->last,
-		          q->top, q->n, q->nbox, q->ctl, (uint32_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, cbits, F);
-		NH_LAUNCH(ctx, "q_wide_count_capsule", (on ? k_q_wide<false, true, true> : k_q_wide<false, true, false>), grid, 256, queries, count, offsets, q->nodes, q->rec, q->idx,
-		          q->last, q->top, q->n, q->nbox, q->ctl, (uint32_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, cbits, F);
-	} else {
-		NH_LAUNCH(ctx, "q_overlap_count", (on ? k_q_overlap<false, false, true> : k_q_overlap<false, false, false>), grid, 256, queries, count, offsets, q->nodes, q->rec,
-		          q->n, q->nbox, q->ctl, (uint64_t*)nullptr, (uint32_t*)nullptr, cbits, F);
-		NH_LAUNCH(ctx, "q_overlap_count_capsule", (on ? k_q_overlap<false, true, true> : k_q_overlap<false, true, false>), grid, 256, queries, count, offsets, q->nodes, q->rec,
-		          q->n, q->nbox, q->ctl, (uint64_t*)nullptr, (uint32_t*)nullptr, cbits, F);
-	}
+	const int cbits = nh_q_bits(q->n), ibits = nh_q_bits(count);
+	nh_QPass p{};
+	p.cbits = (uint32_t)cbits;
+	p.one_sort = by_t && ibits + 32 + cbits <= 64 ? 1u : 0u;
+	// (spread: one wave per item at most -- a small world or a small batch launches a small grid)
+	p.grid = spread ? nh_grid_for((uint64_t)count * (q->n ? q->n : 1u), 4u, NH_Q_REGION_GRID) : nh_grid_for(count, 256, 1u << 20);
+	p.F = nh_query_filter_of(q, &p.on);
+	if (spread) NH_HIP_CHECK(ctx, hipMemsetAsync(offsets, 0, sizeof(uint32_t) * ((size_t)count + 1u), ctx->stream));
+	walk(p);
 	nh_overlap_offsets(ctx, offsets, count, capacity);
 	if (!list) return NH_OK;
-	if (wide) {
-		NH_HIP_CHECK(ctx, hipMemsetAsync(q->rg_cursor, 0, sizeof(uint32_t) * (size_t)count, ctx->stream));
-		NH_LAUNCH(ctx, "q_wide_list", (on ? k_q_wide<true, false, true> : k_q_wide<true, false, false>), grid, 256, queries, count, offsets, q->nodes, q->rec, q->idx, q->last,
-		          q->top, q->n, q->nbox, q->ctl, q->rg_cursor, q->ov_keys_a, q->ov_vals_a, cbits, F);
-		NH_LAUNCH(ctx, "q_wide_list_capsule", (on ? k_q_wide<true, true, true> : k_q_wide<true, true, false>), grid, 256, queries, count, offsets, q->nodes, q->rec, q->idx,
-		          q->last, q->top, q->n, q->nbox, q->ctl, q->rg_cursor, q->ov_keys_a, q->ov_vals_a, cbits, F);
-	} else {
-		NH_LAUNCH(ctx, "q_overlap_list", (on ? k_q_overlap<true, false, true> : k_q_overlap<true, false, false>), grid, 256, queries, count, offsets, q->nodes, q->rec,
-		          q->n, q->nbox, q->ctl, q->ov_keys_a, q->ov_vals_a, cbits, F);
-		NH_LAUNCH(ctx, "q_overlap_list_capsule", (on ? k_q_overlap<true, true, true> : k_q_overlap<true, true, false>), grid, 256, queries, count, offsets, q->nodes, q->rec,
-		          q->n, q->nbox, q->ctl, q->ov_keys_a, q->ov_vals_a, cbits, F);
+	if (spread) NH_HIP_CHECK(ctx, hipMemsetAsync(q->rg_cursor, 0, sizeof(uint32_t) * (size_t)count, ctx->stream));
+	nh_QSorted s{ q->ov_keys_a, q->ov_vals_a, p.cbits, p.one_sort };
+	p.list = true; p.cursor = spread ? q->rg_cursor : nullptr; p.keys = s.keys; p.vals = s.vals;
+	walk(p);
+	// (the low `bits` of the keys, rounded to whole bytes; the sorted pairs lie in whichever pair of buffers the last digit wrote)
+	uint64_t* keys_other = q->ov_keys_b;
+	uint32_t* vals_other = q->ov_vals_b;
+	const auto sort = [&](int bits) {
+		if (!nh_sort_u64_u32(ctx, s.keys, keys_other, s.vals, vals_other, &q->ctl->ov_written, q->hist, 0, (bits + 7) / 8 * 8)) return;
+		std::swap(s.keys, keys_other); std::swap(s.vals, vals_other);
+	};
+	if (!by_t) sort(cbits + ibits);
+	else if (p.one_sort) sort(ibits + 32 + cbits);
+	else {
+		sort(cbits);
+		NH_LAUNCH(ctx, "q_castall_rekey", k_q_castall_rekey, nh_grid_for(capacity, 256, 4096), 256, s.keys, s.vals, q->ctl, p.cbits);
+		sort(ibits + 32);
 	}
-	const int bits = (((int)cbits + nh_q_bits(count)) + 7) / 8 * 8;
-	*in_b = nh_sort_u64_u32(ctx, q->ov_keys_a, q->ov_keys_b, q->ov_vals_a, q->ov_vals_b, &q->ctl->ov_written, q->hist, 0, bits);
-	*list_out = true;
+	*out = s;
 	return NH_OK;
 }
 
-// nh_overlap and nh_overlap_wide: the chain, then the gather of nh_OverlapHit
-static int nh_overlap_call(nh_context* ctx, const nh_OverlapQuery* queries, uint32_t count, uint32_t* offsets, nh_OverlapHit* hits, uint32_t capacity, uint32_t flags,
-                           bool wide) {
-	bool list = false;
-	int in_b = 0;
-	uint32_t cbits = 0u;
-	{ const int rc = nh_overlap_chain(ctx, queries, count, offsets, hits, capacity, flags, wide, &list, &in_b, &cbits); if (rc || !list) return rc; }
+// The gather of nh_OverlapHit records (nh_overlap, nh_overlap_wide, nh_region), and nh_penetration's, which evaluates the pair function of each record (header: the
+// same set, the same order, the same offsets).
+static void nh_list_gather(nh_context* ctx, const nh_QSorted& s, const void*, uint32_t, nh_OverlapHit* hits, uint32_t capacity) {
 	nh_QueryState* q = ctx->query;
-	NH_LAUNCH(ctx, "q_overlap_gather", k_q_overlap_gather, nh_grid_for(capacity, 256, 4096), 256, in_b ? q->ov_vals_b : q->ov_vals_a, q->ctl, q->rec, q->n, q->nbox,
-	          hits);
-	return NH_OK;
+	NH_LAUNCH(ctx, "q_overlap_gather", k_q_overlap_gather, nh_grid_for(capacity, 256, 4096), 256, s.vals, q->ctl, q->rec, q->n, q->nbox, hits);
+}
+static void nh_list_gather(nh_context* ctx, const nh_QSorted& s, const nh_OverlapQuery* queries, uint32_t count, nh_PenetrationHit* hits, uint32_t capacity) {
+	nh_QueryState* q = ctx->query;
+	NH_LAUNCH(ctx, "q_penetration_gather", k_q_penetration_gather, nh_grid_for(capacity, 256, 1u << 20), 256, s.keys, s.vals, q->ctl, q->rec, q->n, q->nbox, queries,
+	          count, s.cbits, hits);
 }
 
-// nh_penetration and nh_penetration_wide: nh_overlap's chain with a gather that evaluates the pair function of each record (header: the same set, the same
-// order, the same offsets).
-static int nh_penetration_call(nh_context* ctx, const nh_OverlapQuery* queries, uint32_t count, uint32_t* offsets, nh_PenetrationHit* hits, uint32_t capacity,
-                               uint32_t flags, bool wide) {
-	bool list = false;
-	int in_b = 0;
-	uint32_t cbits = 0u;
-	{ const int rc = nh_overlap_chain(ctx, queries, count, offsets, hits, capacity, flags, wide, &list, &in_b, &cbits); if (rc || !list) return rc; }
-	nh_QueryState* q = ctx->query;
-	NH_LAUNCH(ctx, "q_penetration_gather", k_q_penetration_gather, nh_grid_for(capacity, 256, 1u << 20), 256, in_b ? q->ov_keys_b : q->ov_keys_a,
-	          in_b ? q->ov_vals_b : q->ov_vals_a, q->ctl, q->rec, q->n, q->nbox, queries, count, cbits, hits);
-	return NH_OK;
+// nh_overlap and nh_penetration, or (wide) their wide forms with k_q_wide in place of the walks: the chain with the sphere-and-box walk and the capsule walk in each
+// pass, sorted by (query, combined collider index), then the gather of the record type.
+template <class Hit>
+static int nh_overlap_call(nh_context* ctx, const nh_OverlapQuery* queries, uint32_t count, uint32_t* offsets, Hit* hits, uint32_t capacity, uint32_t flags, bool wide) {
+	const auto walks = [&](const nh_QPass& p) {
+		nh_QueryState* q = ctx->query;
+		NH_LAUNCH(ctx, p.list ? "q_overlap_list" : "q_overlap_count",
+		          nh_q_pass_kernel(p, k_q_overlap<false, false, false>, k_q_overlap<false, false, true>, k_q_overlap<true, false, false>, k_q_overlap<true, false, true>),
+		          p.grid, 256, queries, count, offsets, q->nodes, q->rec, q->n, q->nbox, q->ctl, p.keys, p.vals, p.cbits, p.F);
+		NH_LAUNCH(ctx, p.list ? "q_overlap_list_capsule" : "q_overlap_count_capsule",
+		          nh_q_pass_kernel(p, k_q_overlap<false, true, false>, k_q_overlap<false, true, true>, k_q_overlap<true, true, false>, k_q_overlap<true, true, true>),
+		          p.grid, 256, queries, count, offsets, q->nodes, q->rec, q->n, q->nbox, q->ctl, p.keys, p.vals, p.cbits, p.F);
+	};
+	const auto spread_walks = [&](const nh_QPass& p) {
+		nh_QueryState* q = ctx->query;
+		NH_LAUNCH(ctx, p.list ? "q_wide_list" : "q_wide_count",
+		          nh_q_pass_kernel(p, k_q_wide<false, false, false>, k_q_wide<false, false, true>, k_q_wide<true, false, false>, k_q_wide<true, false, true>),
+		          p.grid, 256, queries, count, offsets, q->nodes, q->rec, q->idx, q->last, q->top, q->n, q->nbox, q->ctl, p.cursor, p.keys, p.vals, p.cbits, p.F);
+		NH_LAUNCH(ctx, p.list ? "q_wide_list_capsule" : "q_wide_count_capsule",
+		          nh_q_pass_kernel(p, k_q_wide<false, true, false>, k_q_wide<false, true, true>, k_q_wide<true, true, false>, k_q_wide<true, true, true>),
+		          p.grid, 256, queries, count, offsets, q->nodes, q->rec, q->idx, q->last, q->top, q->n, q->nbox, q->ctl, p.cursor, p.keys, p.vals, p.cbits, p.F);
+	};
+	nh_QSorted s;
+	const int rc = wide ? nh_list_chain(ctx, queries, count, offsets, hits, capacity, flags, true, false, spread_walks, &s)
+	                    : nh_list_chain(ctx, queries, count, offsets, hits, capacity, flags, false, false, walks, &s);
+	if (rc == NH_OK && s.keys) nh_list_gather(ctx, s, queries, count, hits, capacity);
+	return rc;
 }
 
 extern "C" int nh_overlap(nh_context* ctx, const nh_OverlapQuery* queries, uint32_t count, uint32_t* offsets, nh_OverlapHit* hits, uint32_t capacity,
@@ -1505,7 +1529,7 @@ extern "C" int nh_overlap(nh_context* ctx, const nh_OverlapQuery* queries, uint3
 
 extern "C" int nh_penetration(nh_context* ctx, const nh_OverlapQuery* queries, uint32_t count, uint32_t* offsets, nh_PenetrationHit* hits, uint32_t capacity,
                               uint32_t flags) {
-	return nh_penetration_call(ctx, queries, count, offsets, hits, capacity, flags, false);
+	return nh_overlap_call(ctx, queries, count, offsets, hits, capacity, flags, false);
 }
 
 // The wide forms (header, "nh_overlap_wide"): the same bytes, the work of one query spread over the GPU.
@@ -1516,71 +1540,40 @@ extern "C" int nh_overlap_wide(nh_context* ctx, const nh_OverlapQuery* queries, 
 
 extern "C" int nh_penetration_wide(nh_context* ctx, const nh_OverlapQuery* queries, uint32_t count, uint32_t* offsets, nh_PenetrationHit* hits, uint32_t capacity,
                                    uint32_t flags) {
-	return nh_penetration_call(ctx, queries, count, offsets, hits, capacity, flags, true);
+	return nh_overlap_call(ctx, queries, count, offsets, hits, capacity, flags, true);
 }
 
-// nh_overlap's chain with k_q_region in place of the walks: nh_overlap's argument rules, offsets and capacity contract, sort and gather (the comment above
-// k_q_region).  offsets[0 .. count] are zeroed first: the count pass adds into them.
+// The spread chain with k_q_region as its walk (the comment above k_q_region), and nh_overlap's gather.
 extern "C" int nh_region(nh_context* ctx, const nh_Region* regions, uint32_t count, uint32_t* offsets, nh_OverlapHit* hits, uint32_t capacity, uint32_t flags) {
-	bool list = false;
-	{ const int rc = nh_overlap_args(ctx, regions, count, offsets, hits, capacity, flags, &list); if (rc || count == 0u) return rc; }
-	if (list) { const int rc = nh_region_reserve(ctx, count); if (rc) return rc; }
-	nh_QueryState* q = ctx->query;
-	const uint32_t cbits = (uint32_t)nh_q_bits(q->n);
-	// (one wave per item at most: a small world or a small batch launches a small grid)
-	const uint32_t grid = nh_grid_for((uint64_t)count * (q->n ? q->n : 1u), 4u, NH_Q_REGION_GRID);
-	bool on;
-	const nh_QFilter F = nh_query_filter_of(q, &on);
-	NH_HIP_CHECK(ctx, hipMemsetAsync(offsets, 0, sizeof(uint32_t) * ((size_t)count + 1u), ctx->stream));
-	NH_LAUNCH(ctx, "q_region_count", (on ? k_q_region<false, true> : k_q_region<false, false>), grid, 256, regions, count, offsets, q->nodes, q->rec, q->idx, q->last,
-	          q->top, q->n, q->nbox, q->ctl, (uint32_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, cbits, F);
-	nh_overlap_offsets(ctx, offsets, count, capacity);
-	if (!list) return NH_OK;
-	NH_HIP_CHECK(ctx, hipMemsetAsync(q->rg_cursor, 0, sizeof(uint32_t) * (size_t)count, ctx->stream));
-	NH_LAUNCH(ctx, "q_region_list", (on ? k_q_region<true, true> : k_q_region<true, false>), grid, 256, regions, count, offsets, q->nodes, q->rec, q->idx, q->last,
-	          q->top, q->n, q->nbox, q->ctl, q->rg_cursor, q->ov_keys_a, q->ov_vals_a, cbits, F);
-	const int bits = (((int)cbits + nh_q_bits(count)) + 7) / 8 * 8;
-	const int in_b = nh_sort_u64_u32(ctx, q->ov_keys_a, q->ov_keys_b, q->ov_vals_a, q->ov_vals_b, &q->ctl->ov_written, q->hist, 0, bits);
-	NH_LAUNCH(ctx, "q_overlap_gather", k_q_overlap_gather, nh_grid_for(capacity, 256, 4096), 256, in_b ? q->ov_vals_b : q->ov_vals_a, q->ctl, q->rec, q->n, q->nbox,
-	          hits);
-	return NH_OK;
+	const auto walk = [&](const nh_QPass& p) {
+		nh_QueryState* q = ctx->query;
+		NH_LAUNCH(ctx, p.list ? "q_region_list" : "q_region_count",
+		          nh_q_pass_kernel(p, k_q_region<false, false>, k_q_region<false, true>, k_q_region<true, false>, k_q_region<true, true>), p.grid, 256, regions, count,
+		          offsets, q->nodes, q->rec, q->idx, q->last, q->top, q->n, q->nbox, q->ctl, p.cursor, p.keys, p.vals, p.cbits, p.F);
+	};
+	nh_QSorted s;
+	const int rc = nh_list_chain(ctx, regions, count, offsets, hits, capacity, flags, true, false, walk, &s);
+	if (rc == NH_OK && s.keys) nh_list_gather(ctx, s, regions, count, hits, capacity);
+	return rc;
 }
 
-// The all-hits chain (the comment above k_q_castall): nh_overlap's argument rules, offsets and capacity contract, the casts' walk, the ordering by t.
-// `label`: the timing labels' stem, q_<entry point without nh_>.
+// The all-hits casts (the comment above k_q_castall): the chain with the casts' walk, ordered by t.  `label`: the timing labels' stem, q_<entry point without
+// nh_>.
 template <class Shape>
 static int nh_castall(nh_context* ctx, const char* const label[3], const void* casts, uint32_t count, uint32_t* offsets, nh_RayHit* hits, uint32_t capacity,
                       uint32_t flags) {
-	bool list = false;
-	{ const int rc = nh_overlap_args(ctx, casts, count, offsets, hits, capacity, flags, &list); if (rc || count == 0u) return rc; }
-	nh_QueryState* q = ctx->query;
 	const float4* recs = static_cast<const float4*>(casts);
-	const uint32_t cbits = (uint32_t)nh_q_bits(q->n);
-	const int ibits = nh_q_bits(count);
-	const bool one_sort = ibits + 32 + (int)cbits <= 64;
-	const uint32_t grid = nh_grid_for(count, 256, 1u << 20);
-	bool on;
-	const nh_QFilter F = nh_query_filter_of(q, &on);
-	NH_LAUNCH(ctx, label[0], (on ? k_q_castall<Shape, false, true> : k_q_castall<Shape, false, false>), grid, 256, recs, count, offsets, q->nodes, q->rec, q->n, q->nbox,
-	          q->ctl, (uint64_t*)nullptr, (uint32_t*)nullptr, cbits, one_sort ? 1u : 0u, F);
-	nh_overlap_offsets(ctx, offsets, count, capacity);
-	if (!list) return NH_OK;
-	NH_LAUNCH(ctx, label[1], (on ? k_q_castall<Shape, true, true> : k_q_castall<Shape, true, false>), grid, 256, recs, count, offsets, q->nodes, q->rec, q->n, q->nbox,
-	          q->ctl, q->ov_keys_a, q->ov_vals_a, cbits, one_sort ? 1u : 0u, F);
-	uint64_t* keys = q->ov_keys_a; uint64_t* keys_other = q->ov_keys_b;
-	uint32_t* vals = q->ov_vals_a; uint32_t* vals_other = q->ov_vals_b;
-	const uint32_t* m = &q->ctl->ov_written;
-	if (nh_sort_u64_u32(ctx, keys, keys_other, vals, vals_other, m, q->hist, 0, one_sort ? (ibits + 32 + (int)cbits + 7) / 8 * 8 : ((int)cbits + 7) / 8 * 8)) {
-		std::swap(keys, keys_other); std::swap(vals, vals_other);
-	}
-	if (!one_sort) {
-		NH_LAUNCH(ctx, "q_castall_rekey", k_q_castall_rekey, nh_grid_for(capacity, 256, 4096), 256, keys, vals, q->ctl, cbits);
-		if (nh_sort_u64_u32(ctx, keys, keys_other, vals, vals_other, m, q->hist, 0, (ibits + 32 + 7) / 8 * 8)) {
-			std::swap(keys, keys_other); std::swap(vals, vals_other);
-		}
-	}
-	NH_LAUNCH(ctx, label[2], (k_q_castall_gather<Shape>), nh_grid_for(capacity, 256, 1u << 20), 256, keys, vals, q->ctl, q->rec, q->n, q->nbox, recs, count,
-	          one_sort ? 32u + cbits : 32u, hits);
+	const auto walk = [&](const nh_QPass& p) {
+		nh_QueryState* q = ctx->query;
+		NH_LAUNCH(ctx, label[p.list ? 1 : 0],
+		          nh_q_pass_kernel(p, k_q_castall<Shape, false, false>, k_q_castall<Shape, false, true>, k_q_castall<Shape, true, false>, k_q_castall<Shape, true, true>),
+		          p.grid, 256, recs, count, offsets, q->nodes, q->rec, q->n, q->nbox, q->ctl, p.keys, p.vals, p.cbits, p.one_sort, p.F);
+	};
+	nh_QSorted s;
+	{ const int rc = nh_list_chain(ctx, casts, count, offsets, hits, capacity, flags, false, true, walk, &s); if (rc || !s.keys) return rc; }
+	nh_QueryState* q = ctx->query;
+	NH_LAUNCH(ctx, label[2], (k_q_castall_gather<Shape>), nh_grid_for(capacity, 256, 1u << 20), 256, s.keys, s.vals, q->ctl, q->rec, q->n, q->nbox, recs, count,
+	          s.one_sort ? 32u + s.cbits : 32u, hits);
 	return NH_OK;
 }
 

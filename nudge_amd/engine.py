@@ -878,14 +878,16 @@ class World:
         casts[:, 8] = torch.as_tensor(radii, dtype=torch.float32, device=self.dev).reshape(-1)
         return self._ray_hits(self.spherecast_records(casts, any_hit=any_hit), synchronize)
 
-    def _castall_records(self, name, size, casts, offsets, hits, capacity):
-        torch = self.torch
-        n = casts.numel() * casts.element_size() // size
+    def _list_records(self, name, in_bytes, out_bytes, records, offsets, hits, capacity):
+        """The C call `name`(ctx, records, count, offsets, hits, capacity, 0) of the queries that write variable-length lists: `records` a contiguous
+        device tensor of count x in_bytes bytes (any dtype), `hits` None or at least capacity x out_bytes bytes.  Returns (offsets, hits): the
+        count + 1 offsets as an int32 device tensor holding the uint32 bits (`offsets`, or a new one) and `hits` as given."""
+        n = records.numel() * records.element_size() // in_bytes
         if offsets is None:
-            offsets = torch.empty(n + 1, dtype=torch.int32, device=self.dev)
-        if hits is not None and hits.numel() * hits.element_size() < 32 * capacity:
-            raise ValueError(f"{name}: hits holds {hits.numel() * hits.element_size()} bytes, capacity {capacity} needs {32 * capacity}")
-        _check(self.L, getattr(self.L, name)(self.ctx, C.c_void_p(casts.data_ptr() if n else 0), n, C.c_void_p(offsets.data_ptr()),
+            offsets = self.torch.empty(n + 1, dtype=self.torch.int32, device=self.dev)
+        if hits is not None and hits.numel() * hits.element_size() < out_bytes * capacity:
+            raise ValueError(f"{name[3:]}_records: hits holds {hits.numel() * hits.element_size()} bytes, capacity {capacity} needs {out_bytes * capacity}")
+        _check(self.L, getattr(self.L, name)(self.ctx, C.c_void_p(records.data_ptr() if n else 0), n, C.c_void_p(offsets.data_ptr()),
                                              C.c_void_p(hits.data_ptr() if hits is not None else 0), capacity, 0), name)
         return offsets, hits
 
@@ -894,15 +896,15 @@ class World:
         (offsets, hits) as overlap_records does: the count + 1 offsets as an int32 device tensor holding the uint32 bits and `hits` as given.  With
         hits = None and capacity = 0 only the offsets are written (count only); otherwise `hits` must hold `capacity` x 32 bytes (nh_RayHit), and the
         records of ray i are written iff offsets[i + 1] <= capacity.  Enqueued; nothing waits (but a capacity larger than any before grows the scratch)."""
-        return self._castall_records("nh_raycast_all", 32, rays, offsets, hits, capacity)
+        return self._list_records("nh_raycast_all", 32, 32, rays, offsets, hits, capacity)
 
     def spherecast_all_records(self, casts, offsets=None, hits=None, capacity=0):
         """nh_spherecast_all on records already laid out as nh_SphereCast (count x 48 bytes): raycast_all_records for swept balls."""
-        return self._castall_records("nh_spherecast_all", 48, casts, offsets, hits, capacity)
+        return self._list_records("nh_spherecast_all", 48, 32, casts, offsets, hits, capacity)
 
     def _castall(self, records, casts, n, capacity, synchronize):
-        hits, off, written, query = self._overlap_lists(records, casts, n, capacity, 32)
-        return self._ray_hits(hits, synchronize, offsets=off, written=written, query=query)
+        offsets, hits, n, capacity = self._overlap_lists(records, casts, n, capacity, 32)
+        return self._ray_hits(hits, synchronize, **self._list_index(offsets, n, capacity))
 
     def raycast_all(self, origins, directions, max_t=float("inf"), ignore_body=None, capacity=None, synchronize=False):
         """Every collider each of n rays passes through, ordered along the ray (nh_raycast_all), against the last query_build().  The arguments are
@@ -975,11 +977,11 @@ class World:
 
     def boxcast_all_records(self, casts, offsets=None, hits=None, capacity=0):
         """nh_boxcast_all on records already laid out as nh_BoxCast (count x 64 bytes): raycast_all_records for swept oriented boxes."""
-        return self._castall_records("nh_boxcast_all", 64, casts, offsets, hits, capacity)
+        return self._list_records("nh_boxcast_all", 64, 32, casts, offsets, hits, capacity)
 
     def capsulecast_all_records(self, casts, offsets=None, hits=None, capacity=0):
         """nh_capsulecast_all on records already laid out as nh_CapsuleCast (count x 64 bytes): raycast_all_records for swept capsules."""
-        return self._castall_records("nh_capsulecast_all", 64, casts, offsets, hits, capacity)
+        return self._list_records("nh_capsulecast_all", 64, 32, casts, offsets, hits, capacity)
 
     def boxcast_all(self, origins, directions, half_extents, rotations=None, max_t=float("inf"), ignore_body=None, capacity=None, synchronize=False):
         """Every collider each of n swept oriented boxes touches, ordered along the cast (nh_boxcast_all): boxcast()'s arguments, raycast_all()'s
@@ -1342,15 +1344,7 @@ class World:
         (offsets, hits): the count + 1 offsets as an int32 device tensor holding the uint32 bits (`offsets`, or a new one) and `hits` as given.  With
         hits = None and capacity = 0 only the offsets are written (count only); otherwise `hits` must hold `capacity` x 16 bytes, and the records of
         query i are written iff offsets[i + 1] <= capacity.  Enqueued; nothing waits (but a capacity larger than any before grows the scratch)."""
-        torch = self.torch
-        n = queries.numel() * queries.element_size() // 48
-        if offsets is None:
-            offsets = torch.empty(n + 1, dtype=torch.int32, device=self.dev)
-        if hits is not None and hits.numel() * hits.element_size() < 16 * capacity:
-            raise ValueError(f"overlap_records: hits holds {hits.numel() * hits.element_size()} bytes, capacity {capacity} needs {16 * capacity}")
-        _check(self.L, self.L.nh_overlap(self.ctx, C.c_void_p(queries.data_ptr() if n else 0), n, C.c_void_p(offsets.data_ptr()),
-                                         C.c_void_p(hits.data_ptr() if hits is not None else 0), capacity, 0), "nh_overlap")
-        return offsets, hits
+        return self._list_records("nh_overlap", 48, 16, queries, offsets, hits, capacity)
 
     def _overlap_queries(self, what, centres, radii, half_extents, rotations, ignore_body, half_heights):
         """The nh_OverlapQuery records (n x 12 float32 words on the device) of overlap() / penetration()'s arguments."""
@@ -1388,7 +1382,7 @@ class World:
 
     def _overlap_lists(self, records, q, n, capacity, size):
         """The count-then-list path (capacity=None) or the one call with a capacity, through `records` (overlap_records / penetration_records) with
-        records of `size` bytes: (hits, offsets as int64, written, the query of every record slot)."""
+        records of `size` bytes: (int32 offsets, hits, n, the capacity of `hits`), what _list_index and the unpackers take."""
         torch = self.torch
         if capacity is None:
             offsets, _ = records(q)
@@ -1400,13 +1394,37 @@ class World:
         else:
             hits = torch.empty((capacity, size), dtype=torch.uint8, device=self.dev)
             offsets, _ = records(q, hits=hits if capacity else None, capacity=capacity)
+        return offsets, hits, n, capacity
+
+    def _list_index(self, offsets, n, capacity):
+        """What every list dict starts with, from a list's int32 offsets (n + 1) and capacity: offsets (int64), written, the query of every record slot."""
+        torch = self.torch
         off = offsets.to(torch.int64) & 0xFFFFFFFF
         # the written prefix: the largest offset <= capacity (offsets are monotone unless the total overflowed, and then nothing is written)
         last = torch.searchsorted(off, torch.tensor([capacity], dtype=torch.int64, device=self.dev), right=True) - 1
         written = torch.where(off[n] == NH_OVERLAP_OVERFLOW, torch.zeros_like(last), off[last.clamp(min=0)])[0]
         j = torch.arange(capacity, dtype=torch.int64, device=self.dev)
         query = (torch.searchsorted(off[1:], j, right=True) if n else j).clamp(max=max(n - 1, 0))
-        return hits, off, written, query
+        return dict(offsets=off, written=written, query=query)
+
+    def _list_dict(self, offsets, hits, n, capacity, synchronize=False):
+        """overlap()'s dict of a list: int32 offsets (n + 1), the nh_OverlapHit records (capacity x 16 bytes)."""
+        torch = self.torch
+        u = hits.view(torch.int32).reshape(-1, 4).to(torch.int64) & 0xFFFFFFFF
+        r = dict(self._list_index(offsets, n, capacity), body=u[:, 0], collider=u[:, 1], shape=u[:, 2], tag=u[:, 3], raw=hits)
+        if synchronize:
+            torch.cuda.current_stream(self.dev).synchronize()
+        return r
+
+    def _penetration_dict(self, offsets, hits, n, capacity, synchronize=False):
+        """penetration()'s dict of a list: int32 offsets (n + 1), the nh_PenetrationHit records (capacity x 32 bytes)."""
+        torch = self.torch
+        f = hits.view(torch.float32).reshape(-1, 8)
+        u = hits.view(torch.int32).reshape(-1, 8).to(torch.int64) & 0xFFFFFFFF
+        r = dict(self._list_index(offsets, n, capacity), normal=f[:, 0:3], depth=f[:, 3], body=u[:, 4], collider=u[:, 5], shape=u[:, 6], tag=u[:, 7], raw=hits)
+        if synchronize:
+            torch.cuda.current_stream(self.dev).synchronize()
+        return r
 
     def overlap(self, centres, radii=None, half_extents=None, rotations=None, ignore_body=None, capacity=None, synchronize=False, half_heights=None):
         """The colliders touching each of n spheres (`radii`: a number or n values), n oriented boxes (`half_extents` (n, 3) or (3,), `rotations`
@@ -1418,27 +1436,14 @@ class World:
         Returns a dict of device tensors: offsets (n + 1, int64; offsets[n] = 0xffffffff when the total is 2^32 - 1 or more), `written` (0-d: the
         records listed, a prefix of whole segments), and per record slot (capacity of them; the first `written` are meaningful) query, body,
         collider, shape, tag (int64) and `raw`, the nh_OverlapHit records (capacity x 16 bytes)."""
-        torch = self.torch
         q, n = self._overlap_queries("overlap", centres, radii, half_extents, rotations, ignore_body, half_heights)
-        hits, off, written, query = self._overlap_lists(self.overlap_records, q, n, capacity, 16)
-        u = hits.view(torch.int32).reshape(-1, 4).to(torch.int64) & 0xFFFFFFFF
-        if synchronize:
-            torch.cuda.current_stream(self.dev).synchronize()
-        return dict(offsets=off, written=written, query=query, body=u[:, 0], collider=u[:, 1], shape=u[:, 2], tag=u[:, 3], raw=hits)
+        return self._list_dict(*self._overlap_lists(self.overlap_records, q, n, capacity, 16), synchronize)
 
     def penetration_records(self, queries, offsets=None, hits=None, capacity=0):
         """nh_penetration on records already laid out as nh_OverlapQuery: overlap_records with 32-byte nh_PenetrationHit records -- `hits` must hold
         `capacity` x 32 bytes.  The offsets, the set, the order and the capacity rule are nh_overlap's.  Enqueued; nothing waits (but a capacity
         larger than any before grows the scratch)."""
-        torch = self.torch
-        n = queries.numel() * queries.element_size() // 48
-        if offsets is None:
-            offsets = torch.empty(n + 1, dtype=torch.int32, device=self.dev)
-        if hits is not None and hits.numel() * hits.element_size() < 32 * capacity:
-            raise ValueError(f"penetration_records: hits holds {hits.numel() * hits.element_size()} bytes, capacity {capacity} needs {32 * capacity}")
-        _check(self.L, self.L.nh_penetration(self.ctx, C.c_void_p(queries.data_ptr() if n else 0), n, C.c_void_p(offsets.data_ptr()),
-                                             C.c_void_p(hits.data_ptr() if hits is not None else 0), capacity, 0), "nh_penetration")
-        return offsets, hits
+        return self._list_records("nh_penetration", 48, 32, queries, offsets, hits, capacity)
 
     def penetration(self, centres, radii=None, half_extents=None, rotations=None, ignore_body=None, capacity=None, synchronize=False, half_heights=None):
         """The push that frees a shape: for every collider that each of n spheres, oriented boxes or capsules touches (overlap()'s arguments, set,
@@ -1446,74 +1451,36 @@ class World:
         Returns overlap()'s dict with, per record slot, `normal` ((capacity, 3) float32: a unit vector from the collider towards the shape) and
         `depth` (float32, >= 0: the shape moved by depth * normal touches the collider); `raw` holds the nh_PenetrationHit records
         (capacity x 32 bytes)."""
-        torch = self.torch
         q, n = self._overlap_queries("penetration", centres, radii, half_extents, rotations, ignore_body, half_heights)
-        hits, off, written, query = self._overlap_lists(self.penetration_records, q, n, capacity, 32)
-        f = hits.view(torch.float32).reshape(-1, 8)
-        u = hits.view(torch.int32).reshape(-1, 8).to(torch.int64) & 0xFFFFFFFF
-        if synchronize:
-            torch.cuda.current_stream(self.dev).synchronize()
-        return dict(offsets=off, written=written, query=query, normal=f[:, 0:3], depth=f[:, 3], body=u[:, 4], collider=u[:, 5], shape=u[:, 6], tag=u[:, 7],
-                    raw=hits)
+        return self._penetration_dict(*self._overlap_lists(self.penetration_records, q, n, capacity, 32), synchronize)
 
     # ---- the wide forms: nh_overlap's and nh_penetration's bytes, the work of one query spread over the GPU (include/nudge_hip.h, "nh_overlap_wide") ----
-    def _wide_records(self, name, size, queries, offsets, hits, capacity):
-        torch = self.torch
-        n = queries.numel() * queries.element_size() // 48
-        if offsets is None:
-            offsets = torch.empty(n + 1, dtype=torch.int32, device=self.dev)
-        if hits is not None and hits.numel() * hits.element_size() < size * capacity:
-            raise ValueError(f"{name[3:]}_records: hits holds {hits.numel() * hits.element_size()} bytes, capacity {capacity} needs {size * capacity}")
-        _check(self.L, getattr(self.L, name)(self.ctx, C.c_void_p(queries.data_ptr() if n else 0), n, C.c_void_p(offsets.data_ptr()),
-                                             C.c_void_p(hits.data_ptr() if hits is not None else 0), capacity, 0), name)
-        return offsets, hits
-
     def overlap_wide_records(self, queries, offsets=None, hits=None, capacity=0):
         """nh_overlap_wide on nh_OverlapQuery records: overlap_records' arguments, rules and bytes.  Enqueued; nothing waits (but a capacity or a
         count larger than any before grows the scratch)."""
-        return self._wide_records("nh_overlap_wide", 16, queries, offsets, hits, capacity)
+        return self._list_records("nh_overlap_wide", 48, 16, queries, offsets, hits, capacity)
 
     def penetration_wide_records(self, queries, offsets=None, hits=None, capacity=0):
         """nh_penetration_wide on nh_OverlapQuery records: penetration_records' arguments, rules and bytes (32-byte records)."""
-        return self._wide_records("nh_penetration_wide", 32, queries, offsets, hits, capacity)
+        return self._list_records("nh_penetration_wide", 48, 32, queries, offsets, hits, capacity)
 
     def overlap_wide(self, centres, radii=None, half_extents=None, rotations=None, ignore_body=None, capacity=None, synchronize=False, half_heights=None):
         """overlap() for LARGE volumes -- an explosion radius, a trigger volume, an area of interest: the same arguments and the same dict, byte for
         byte, through nh_overlap_wide, which spreads the work of one query over the GPU where overlap() gives it one lane.  Which of the two is faster
         depends on the size alone (header, "which call for which question"); a mixed batch is the caller's to split."""
-        torch = self.torch
         q, n = self._overlap_queries("overlap_wide", centres, radii, half_extents, rotations, ignore_body, half_heights)
-        hits, off, written, query = self._overlap_lists(self.overlap_wide_records, q, n, capacity, 16)
-        u = hits.view(torch.int32).reshape(-1, 4).to(torch.int64) & 0xFFFFFFFF
-        if synchronize:
-            torch.cuda.current_stream(self.dev).synchronize()
-        return dict(offsets=off, written=written, query=query, body=u[:, 0], collider=u[:, 1], shape=u[:, 2], tag=u[:, 3], raw=hits)
+        return self._list_dict(*self._overlap_lists(self.overlap_wide_records, q, n, capacity, 16), synchronize)
 
     def penetration_wide(self, centres, radii=None, half_extents=None, rotations=None, ignore_body=None, capacity=None, synchronize=False, half_heights=None):
         """penetration() for large volumes: the same arguments and the same dict, byte for byte, through nh_penetration_wide (see overlap_wide)."""
-        torch = self.torch
         q, n = self._overlap_queries("penetration_wide", centres, radii, half_extents, rotations, ignore_body, half_heights)
-        hits, off, written, query = self._overlap_lists(self.penetration_wide_records, q, n, capacity, 32)
-        f = hits.view(torch.float32).reshape(-1, 8)
-        u = hits.view(torch.int32).reshape(-1, 8).to(torch.int64) & 0xFFFFFFFF
-        if synchronize:
-            torch.cuda.current_stream(self.dev).synchronize()
-        return dict(offsets=off, written=written, query=query, normal=f[:, 0:3], depth=f[:, 3], body=u[:, 4], collider=u[:, 5], shape=u[:, 6], tag=u[:, 7],
-                    raw=hits)
+        return self._penetration_dict(*self._overlap_lists(self.penetration_wide_records, q, n, capacity, 32), synchronize)
 
     def region_records(self, regions, offsets=None, hits=None, capacity=0):
         """nh_region on records already laid out as nh_Region: `regions` a contiguous device tensor of count x 144 bytes (any dtype).  Returns
         (offsets, hits) as overlap_records does, under the same count-only and capacity rules, with 16-byte nh_OverlapHit records.  Enqueued; nothing
         waits (but a capacity or a count larger than any before grows the scratch)."""
-        torch = self.torch
-        n = regions.numel() * regions.element_size() // 144
-        if offsets is None:
-            offsets = torch.empty(n + 1, dtype=torch.int32, device=self.dev)
-        if hits is not None and hits.numel() * hits.element_size() < 16 * capacity:
-            raise ValueError(f"region_records: hits holds {hits.numel() * hits.element_size()} bytes, capacity {capacity} needs {16 * capacity}")
-        _check(self.L, self.L.nh_region(self.ctx, C.c_void_p(regions.data_ptr() if n else 0), n, C.c_void_p(offsets.data_ptr()),
-                                        C.c_void_p(hits.data_ptr() if hits is not None else 0), capacity, 0), "nh_region")
-        return offsets, hits
+        return self._list_records("nh_region", 144, 16, regions, offsets, hits, capacity)
 
     def region(self, planes, plane_counts=None, ignore_body=None, capacity=None, synchronize=False):
         """The colliders inside each of n convex regions, against the last query_build() / query_refit(): `planes` is (n, P, 4) or (P, 4) with P <= 8,
@@ -1533,11 +1500,7 @@ class World:
         q[:, :4 * P] = pl.reshape(n, 4 * P)
         qi[:, 32] = torch.as_tensor(P if plane_counts is None else plane_counts, dtype=torch.int32, device=self.dev)
         qi[:, 33] = self._ignore_bits(ignore_body)
-        hits, off, written, query = self._overlap_lists(self.region_records, q, n, capacity, 16)
-        u = hits.view(torch.int32).reshape(-1, 4).to(torch.int64) & 0xFFFFFFFF
-        if synchronize:
-            torch.cuda.current_stream(self.dev).synchronize()
-        return dict(offsets=off, written=written, query=query, body=u[:, 0], collider=u[:, 1], shape=u[:, 2], tag=u[:, 3], raw=hits)
+        return self._list_dict(*self._overlap_lists(self.region_records, q, n, capacity, 16), synchronize)
 
     # ---- trigger events: what entered and what left each overlap volume (include/nudge_hip.h, "trigger events") ----
     def _hit_list(self, what, n, offsets, hits, capacity):
@@ -1570,17 +1533,6 @@ class World:
         _check(self.L, self.L.nh_overlap_events(self.ctx, n, C.byref(p) if p is not None else None, C.byref(c), C.byref(e), C.byref(l),
                                                 NH_EVENTS_BY_BODY if by_body else 0), "nh_overlap_events")
         return entered[0], left[0]
-
-    def _list_dict(self, offsets, hits, n, capacity):
-        """overlap()'s dict of a list: int32 offsets (n + 1), the records (capacity x 16 bytes)."""
-        torch = self.torch
-        off = offsets.to(torch.int64) & 0xFFFFFFFF
-        last = torch.searchsorted(off, torch.tensor([capacity], dtype=torch.int64, device=self.dev), right=True) - 1
-        written = torch.where(off[n] == NH_OVERLAP_OVERFLOW, torch.zeros_like(last), off[last.clamp(min=0)])[0]
-        j = torch.arange(capacity, dtype=torch.int64, device=self.dev)
-        query = (torch.searchsorted(off[1:], j, right=True) if n else j).clamp(max=max(n - 1, 0))
-        u = hits.view(torch.int32).reshape(-1, 4).to(torch.int64) & 0xFFFFFFFF
-        return dict(offsets=off, written=written, query=query, body=u[:, 0], collider=u[:, 1], shape=u[:, 2], tag=u[:, 3], raw=hits)
 
     def overlap_events(self, prev, cur, by_body=False, capacity=None, synchronize=False):
         """What entered and what left each volume between two lists: `prev` and `cur` are the dicts overlap() / region() returned for the same n

@@ -2,14 +2,16 @@
 tests that borrow their batches), written once over the shape table of tests/hostcast_util.py: cast records on the heads of rays, the batches of the
 all-hits and first-k tests, the GPU calls on numpy records, the byte comparisons, the checks of an all-hits list against the single-collider oracle and
 against a plain restatement, and the worlds several of the files step through."""
+import functools
+
 import numpy as np
 
 import hostcast_util as HC
+from list_util import SENTINEL, gpu_list, same_lists, sentinel_hits
 from query_util import FUSED, NONE, bounds, rays as kinds_of_rays, unit_quats, upload
 from nudge_amd import engine as E
 from nudge_amd import scenes as S
 
-SENTINEL = 0xA5
 GUARD = 64                                   # records (and count words) behind a first-k call's output that must stay the sentinel
 IDENTITY = (0.0, 0.0, 0.0, 1.0)
 HOST_WORLDS = {"pile": lambda: S.pile(200, 100, seed=11), "compound": lambda: S.compound(100, seed=12)}      # a few hundred mixed boxes and spheres
@@ -287,20 +289,12 @@ def same_hits(got, ref, what):
 
 def all_hits(w, casts, capacity):
     """(offsets, hits): one all-hits call of the casts' shape with `hits` pre-filled with the sentinel (capacity records; None = count only)."""
-    import torch
-    ct = upload(w, casts)
-    ot = torch.full((len(casts) + 1,), -1, dtype=torch.int32, device=w.dev)
-    ht = None if capacity is None else torch.full((max(capacity, 1), 32), SENTINEL, dtype=torch.uint8, device=w.dev)
-    getattr(w, HC.shape_of(casts).call + "_all_records")(ct, offsets=ot, hits=ht, capacity=capacity or 0)
-    off = ot.cpu().numpy().view(np.uint32).copy()
-    hits = None if ht is None else np.frombuffer(ht.cpu().numpy().tobytes(), dtype=E.RAY_HIT).copy()
-    return off, hits
+    return gpu_list(w, HC.shape_of(casts).call + "_all_records", casts, capacity, E.RAY_HIT)
 
 
 def host_all_hits(rec, nbox, casts, capacity):
     """(offsets, hits, total) of the brute force, `hits` pre-filled with the sentinel as all_hits() has them."""
-    hits = np.frombuffer(bytes([SENTINEL]) * 32 * max(capacity, 1), dtype=E.RAY_HIT).copy()
-    return HC.cast_all(HC.shape_of(casts), rec, nbox, casts, capacity=capacity, hits=hits)
+    return HC.cast_all(HC.shape_of(casts), rec, nbox, casts, capacity=capacity, hits=sentinel_hits(capacity, E.RAY_HIT))
 
 
 def first_record_is_the_closest_hit(w, casts, off, hits, what):
@@ -316,17 +310,9 @@ def first_record_is_the_closest_hit(w, casts, off, hits, what):
 
 def same_all_hits(w, rec, casts, what, capacity=None):
     """The count-only call, then a list call with `capacity` (None: exactly the total), against the brute force; returns (offsets, hits, total)."""
-    cnt, _ = all_hits(w, casts, None)
-    ref_cnt, _, total = HC.cast_all(HC.shape_of(casts), rec, w.nbox, casts, capacity=0)
-    assert cnt.tobytes() == ref_cnt.tobytes(), f"{what}: count-only offsets differ in {int((cnt != ref_cnt).sum())} of {len(cnt)}"
-    cap = (0 if total >= NONE else total) if capacity is None else capacity
-    off, hits = all_hits(w, casts, cap)
-    ref_off, ref_hits, _ = host_all_hits(rec, w.nbox, casts, cap)
-    assert off.tobytes() == cnt.tobytes(), f"{what}: list-mode offsets differ from count-only ones"
-    assert off.tobytes() == ref_off.tobytes(), f"{what}: offsets differ"
-    assert hits.tobytes() == ref_hits.tobytes(), \
-        f"{what}: {int((hits.view(np.uint8).reshape(-1, 32) != ref_hits.view(np.uint8).reshape(-1, 32)).any(axis=1).sum())} of {len(hits)} records differ"
-    if cap >= total and total:
+    shape = HC.shape_of(casts)
+    off, hits, total = same_lists(w, shape.call + "_all_records", functools.partial(HC.cast_all, shape), rec, casts, E.RAY_HIT, what, capacity, with_hits=True)
+    if total and ((0 if total >= NONE else total) if capacity is None else capacity) >= total:
         first_record_is_the_closest_hit(w, casts, off, hits, what)
     return off, hits, total
 

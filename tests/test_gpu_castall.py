@@ -18,7 +18,8 @@ import hostcast_util as CAST                 # noqa: E402
 import hostquery_util as Q                   # noqa: E402
 from cast_util import (SENTINEL, all_hits as _gpu, far_and_near, first_record_is_the_closest_hit as _first_record_is_the_closest_hit,      # noqa: E402
                        host_all_hits as _host, mixed as _mixed, same_all_hits, spheres as _casts)
-from query_util import FUSED, NONE, OBSERVED, SMALL, bounds as _bounds, rays as _rays, same_stepped_world as _same_stepped_world, upload as _upload      # noqa: E402
+import list_util as LU                       # noqa: E402
+from query_util import FUSED, NONE, OBSERVED, SMALL, bounds as _bounds, rays as _rays, upload as _upload      # noqa: E402
 from nudge_amd import engine as E           # noqa: E402
 from nudge_amd import scenes as S           # noqa: E402
 
@@ -317,43 +318,12 @@ def _observer_batch(a):
 
 @pytest.mark.parametrize("name", sorted(OBSERVED))
 def test_all_hits_casts_between_nh_step_calls_change_nothing(name):
-    scene = OBSERVED[name]()
-    a, b = E.World(scene, flags=FUSED), E.World(scene, flags=FUSED)
-    batch = _observer_batch(a)
-    done = 0
-    for k in [1, 2, 3, 5, 7, 4, 8] * 10:
-        k = min(k, 300 - done)
-        if k <= 0:
-            break
-        _query(a, *batch)
-        a.step(k)
-        b.step(k)
-        done += k
-    _query(a, *batch)
-    assert done == 300
-    _same_stepped_world(a, b, f"{name} nh_step")
-    if name == "grid_tiles":
-        assert a.counts()["still_steps"] > 0, a.counts()
-    a.close(); b.close()
+    LU.queries_between_nh_step_calls_change_nothing(OBSERVED[name], lambda a, scene: _observer_batch(a), _query, name, still=name == "grid_tiles")
 
 
 @pytest.mark.parametrize("name", sorted(OBSERVED))
 def test_all_hits_casts_between_every_call_of_the_fused_step_change_nothing(name):
-    scene = OBSERVED[name]()
-    a, b = E.World(scene, flags=FUSED), E.World(scene, flags=FUSED)
-    batch = _observer_batch(a)
-    calls = ("collide", "gravity", "read_cache", "setup", "apply", "update", "write_cache", "advance")
-    for s in range(300):
-        for name_ in calls:
-            _query(a, *batch)
-            getattr(a, name_)()
-            getattr(b, name_)()
-        a.step_done(); b.step_done()
-    _query(a, *batch)
-    _same_stepped_world(a, b, f"{name} call by call")
-    if name == "grid_tiles":
-        assert a.counts()["still_steps"] > 0, a.counts()
-    a.close(); b.close()
+    LU.queries_between_every_call_of_the_fused_step_change_nothing(OBSERVED[name], lambda a, scene: _observer_batch(a), _query, name, still=name == "grid_tiles")
 
 
 # ---- at size -------------------------------------------------------------------------------------------------------------------------------

@@ -17,14 +17,14 @@ import hostcast_util as CAST                 # noqa: E402
 import hostquery_util as Q                   # noqa: E402
 from cast_util import (SENTINEL, all_hits as _gpu, as_balls as _as_balls, box_casts, capsule_casts, casts_through, coincident,      # noqa: E402
                        far_and_near_scene as _far_and_near_scene, host_all_hits as _host, mixed as _mixed, same_all_hits)
-from query_util import FUSED, OBSERVED, SMALL, bounds as _bounds, rays as _rays, records as _records, same_stepped_world as _same_stepped_world, upload as _upload      # noqa: E402
+import list_util as LU                       # noqa: E402
+from query_util import FUSED, OBSERVED, SMALL, bounds as _bounds, rays as _rays, records as _records, upload as _upload      # noqa: E402
 from nudge_amd import engine as E           # noqa: E402
 from nudge_amd import scenes as S           # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 SHAPES = ("box", "capsule")
-STILL = ("still_steps", "still_replays", "ahead_steps", "pair_steps", "asleep_steps")
 
 
 def _same(w, rec, casts, what, capacity=None):
@@ -297,44 +297,10 @@ def _observer_batch(a):
     return bt, kt, ot, ht
 
 
-def _same_still_counters(a, b):
-    ca, cb = a.counts(), b.counts()
-    assert [ca[k] for k in STILL] == [cb[k] for k in STILL], (ca, cb)
-    assert ca["still_steps"] > 0, ca
-
-
+# (the still counters of the two worlds agree with all their other counts: same_stepped_world compares every one)
 def test_all_hits_casts_between_nh_step_calls_change_nothing():
-    scene = OBSERVED["grid_tiles"]()
-    a, b = E.World(scene, flags=FUSED), E.World(scene, flags=FUSED)
-    batch = _observer_batch(a)
-    done = 0
-    for k in [1, 2, 3, 5, 7, 4, 8] * 10:
-        k = min(k, 300 - done)
-        if k <= 0:
-            break
-        _query(a, *batch)
-        a.step(k)
-        b.step(k)
-        done += k
-    _query(a, *batch)
-    assert done == 300
-    _same_stepped_world(a, b, "grid_tiles nh_step")
-    _same_still_counters(a, b)
-    a.close(); b.close()
+    LU.queries_between_nh_step_calls_change_nothing(OBSERVED["grid_tiles"], lambda a, scene: _observer_batch(a), _query, "grid_tiles", still=True)
 
 
 def test_all_hits_casts_between_every_call_of_the_fused_step_change_nothing():
-    scene = OBSERVED["grid_tiles"]()
-    a, b = E.World(scene, flags=FUSED), E.World(scene, flags=FUSED)
-    batch = _observer_batch(a)
-    calls = ("collide", "gravity", "read_cache", "setup", "apply", "update", "write_cache", "advance")
-    for s in range(300):
-        for name_ in calls:
-            _query(a, *batch)
-            getattr(a, name_)()
-            getattr(b, name_)()
-        a.step_done(); b.step_done()
-    _query(a, *batch)
-    _same_stepped_world(a, b, "grid_tiles call by call")
-    _same_still_counters(a, b)
-    a.close(); b.close()
+    LU.queries_between_every_call_of_the_fused_step_change_nothing(OBSERVED["grid_tiles"], lambda a, scene: _observer_batch(a), _query, "grid_tiles", still=True)

@@ -14,16 +14,14 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import hostoverlap_util as O                 # noqa: E402
-import parity_util as P                      # noqa: E402
-from query_util import SMALL, bounds as _bounds, unit_quats as _unit_quats      # noqa: E402
+import list_util as LU                       # noqa: E402
+from list_util import SENTINEL, gpu_list, same_lists, sentinel_hits      # noqa: E402
+from query_util import FUSED, NONE, OBSERVED, SMALL, bounds as _bounds, unit_quats as _unit_quats, upload as _upload      # noqa: E402
 from nudge_amd import engine as E           # noqa: E402
 from nudge_amd import scenes as S           # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-NONE = 0xFFFFFFFF
-FUSED = E.NH_FLAG_SINGLE_APPLY | E.NH_FLAG_FUSED_STEP
-SENTINEL = 0xA5
 
 
 def _queries(rng, n, rec, kind, scale=1.0):
@@ -96,42 +94,14 @@ def _capsule_queries(rng, n, rec, scale=1.0):
     return q
 
 
-def _upload(w, arr):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(arr).view(np.uint8).copy()).to(w.dev)
-
-
 def _gpu(w, queries, capacity):
     """(offsets, hits): one nh_overlap call with `hits` pre-filled with the sentinel (capacity records; None = count only)."""
-    import torch
-    qt = _upload(w, queries)
-    ot = torch.full((len(queries) + 1,), -1, dtype=torch.int32, device=w.dev)
-    ht = None if capacity is None else torch.full((max(capacity, 1), 16), SENTINEL, dtype=torch.uint8, device=w.dev)
-    w.overlap_records(qt, offsets=ot, hits=ht, capacity=capacity or 0)
-    off = ot.cpu().numpy().view(np.uint32).copy()
-    hits = None if ht is None else np.frombuffer(ht.cpu().numpy().tobytes(), dtype=E.OVERLAP_HIT).copy()
-    return off, hits
-
-
-def _host(rec, nbox, queries, capacity):
-    hits = np.frombuffer(bytes([SENTINEL]) * 16 * max(capacity, 1), dtype=E.OVERLAP_HIT).copy()
-    off, hits, total = O.overlap(rec, nbox, queries, capacity=capacity, hits=hits)
-    return off, hits, total
+    return gpu_list(w, "overlap_records", queries, capacity, E.OVERLAP_HIT)
 
 
 def _same(w, rec, queries, what, capacity=None):
-    """The count-only call, then a list call with `capacity` (None: exactly the total), against the brute force; returns the host offsets."""
-    cnt, _ = _gpu(w, queries, None)
-    ref_cnt, _, total = O.overlap(rec, w.nbox, queries, capacity=0)
-    assert cnt.tobytes() == ref_cnt.tobytes(), f"{what}: count-only offsets differ in {int((cnt != ref_cnt).sum())} of {len(cnt)}"
-    cap = (0 if total >= NONE else total) if capacity is None else capacity
-    off, hits = _gpu(w, queries, cap)
-    ref_off, ref_hits, _ = _host(rec, w.nbox, queries, cap)
-    assert off.tobytes() == cnt.tobytes(), f"{what}: list-mode offsets differ from count-only ones"
-    assert off.tobytes() == ref_off.tobytes(), f"{what}: offsets differ"
-    assert hits.tobytes() == ref_hits.tobytes(), \
-        f"{what}: {int((hits.view(np.uint8).reshape(-1, 16) != ref_hits.view(np.uint8).reshape(-1, 16)).any(axis=1).sum())} of {len(hits)} records differ"
-    return ref_off, total
+    """The count-only call, then a list call with `capacity` (None: exactly the total), against the brute force; returns the host offsets and the total."""
+    return same_lists(w, "overlap_records", O.overlap, rec, queries, E.OVERLAP_HIT, what, capacity)
 
 
 def _check_world(w, scene, rng, n, what):
@@ -319,7 +289,7 @@ def test_abi_edge_cases():
     # offsets need 4-byte alignment only
     ot4 = buf[1:1026]
     assert L.nh_overlap(w.ctx, qp, 1024, C.c_void_p(ot4.data_ptr()), hp, 4096, 0) == 0
-    ref_off, ref_hits, total = _host(rec, w.nbox, q, 4096)
+    ref_off, ref_hits, total = O.overlap(rec, w.nbox, q, capacity=4096, hits=sentinel_hits(4096, E.OVERLAP_HIT))
     assert total <= 4096
     assert ot4.cpu().numpy().view(np.uint32).tobytes() == ref_off.tobytes()
     got = np.frombuffer(ht.cpu().numpy().tobytes(), dtype=E.OVERLAP_HIT)
@@ -332,23 +302,6 @@ def _query(w, qt, ot, ht):
     w.query_build()
     w.overlap_records(qt, offsets=ot)
     w.overlap_records(qt, offsets=ot, hits=ht, capacity=ht.shape[0])
-
-
-def _same_stepped_world(a, b, what):
-    ba, bb = a.get_bodies(), b.get_bodies()
-    assert P.bits_equal(ba["transforms"], bb["transforms"]) and P.bits_equal(ba["momentum"], bb["momentum"]) and np.array_equal(ba["idle"], bb["idle"]), what
-    a.export_views(E.NH_VIEW_ALL)
-    b.export_views(E.NH_VIEW_ALL)
-    ka, kb = a.get_contacts(), b.get_contacts()
-    assert ka["count"] == kb["count"] and ka["data"].tobytes() == kb["data"].tobytes() and np.array_equal(ka["tags"], kb["tags"]), what
-    assert np.array_equal(ka["features"], kb["features"]) and np.array_equal(ka["bodies"], kb["bodies"]) and np.array_equal(ka["sleeping_pairs"], kb["sleeping_pairs"]), what
-    ca, cb = a.get_cache(), b.get_cache()
-    assert ca["count"] == cb["count"] and ca["data"].tobytes() == cb["data"].tobytes() and np.array_equal(ca["tags"], cb["tags"]), what
-    assert np.array_equal(a.get_active(), b.get_active()), what
-    assert a.counts() == b.counts(), (what, a.counts(), b.counts())
-
-
-OBSERVED = {"pile": lambda: S.pile(256, 0, seed=1), "grid_tiles": lambda: S.grid_tiles(2, side=20, seed=2)}
 
 
 def _observer_batch(a, scene):
@@ -364,46 +317,12 @@ def _observer_batch(a, scene):
 
 @pytest.mark.parametrize("name", sorted(OBSERVED))
 def test_overlaps_between_nh_step_calls_change_nothing(name):
-    scene = OBSERVED[name]()
-    a, b = E.World(scene, flags=FUSED), E.World(scene, flags=FUSED)
-    qt, ot, ht = _observer_batch(a, scene)
-    lengths = [1, 2, 3, 5, 7, 4, 8] * 10
-    done = 0
-    for k in lengths:
-        k = min(k, 300 - done)
-        if k <= 0:
-            break
-        _query(a, qt, ot, ht)
-        a.step(k)
-        b.step(k)
-        done += k
-    _query(a, qt, ot, ht)
-    assert done == 300
-    _same_stepped_world(a, b, f"{name} nh_step")
-    c = a.counts()
-    if name == "grid_tiles":
-        assert c["still_steps"] > 0, c
-    a.close(); b.close()
+    LU.queries_between_nh_step_calls_change_nothing(OBSERVED[name], _observer_batch, _query, name, still=name == "grid_tiles")
 
 
 @pytest.mark.parametrize("name", sorted(OBSERVED))
 def test_overlaps_between_every_call_of_the_fused_step_change_nothing(name):
-    scene = OBSERVED[name]()
-    a, b = E.World(scene, flags=FUSED), E.World(scene, flags=FUSED)
-    qt, ot, ht = _observer_batch(a, scene)
-    calls = ("collide", "gravity", "read_cache", "setup", "apply", "update", "write_cache", "advance")
-    for s in range(300):
-        for name_ in calls:
-            _query(a, qt, ot, ht)
-            getattr(a, name_)()
-            getattr(b, name_)()
-        a.step_done(); b.step_done()
-    _query(a, qt, ot, ht)
-    _same_stepped_world(a, b, f"{name} call by call")
-    c = a.counts()
-    if name == "grid_tiles":
-        assert c["still_steps"] > 0, c
-    a.close(); b.close()
+    LU.queries_between_every_call_of_the_fused_step_change_nothing(OBSERVED[name], _observer_batch, _query, name, still=name == "grid_tiles")
 
 
 # ---- at size -------------------------------------------------------------------------------------------------------------------------------

@@ -18,17 +18,15 @@ import filter_util as F                      # noqa: E402
 import hostlib as H                          # noqa: E402
 import hostoverlap_util as O                 # noqa: E402
 import hostpen_util as HP                    # noqa: E402
-from query_util import SMALL, bounds as _bounds, unit_quats as _unit_quats      # noqa: E402
-from test_gpu_overlap import OBSERVED, _capsule_queries, _coincident, _queries, _same_stepped_world, _upload      # noqa: E402
+import list_util as LU                       # noqa: E402
+from list_util import SENTINEL, differ, gpu_list as _gpu, same_lists      # noqa: E402
+from query_util import FUSED, NONE, OBSERVED, SMALL, bounds as _bounds, unit_quats as _unit_quats, upload as _upload      # noqa: E402
+from test_gpu_overlap import _capsule_queries, _coincident, _queries            # noqa: E402
 from test_gpu_region import RUN, _rotated, _three_runs                          # noqa: E402
 from nudge_amd import engine as E           # noqa: E402
 from nudge_amd import scenes as S           # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-NONE = 0xFFFFFFFF
-FUSED = E.NH_FLAG_SINGLE_APPLY | E.NH_FLAG_FUSED_STEP
-SENTINEL = 0xA5
 
 # per call family: the wide wrapper, the plain one, the record, the brute force
 KINDS = {
@@ -114,41 +112,17 @@ def _swallow(rec):
 
 
 # ---- the comparison -------------------------------------------------------------------------------------------------------------------------
-def _gpu(w, call, queries, capacity, dtype):
-    """(offsets, hits): one call of World.<call> with `hits` pre-filled with the sentinel (capacity records; None = count only)."""
-    import torch
-    qt = _upload(w, queries)
-    ot = torch.full((len(queries) + 1,), -1, dtype=torch.int32, device=w.dev)
-    ht = None if capacity is None else torch.full((max(capacity, 1), dtype.itemsize), SENTINEL, dtype=torch.uint8, device=w.dev)
-    getattr(w, call)(qt, offsets=ot, hits=ht, capacity=capacity or 0)
-    off = ot.cpu().numpy().view(np.uint32).copy()
-    hits = None if ht is None else np.frombuffer(ht.cpu().numpy().tobytes(), dtype=dtype).copy()
-    return off, hits
-
-
-def _differ(a, b):
-    size = a.dtype.itemsize
-    return int((a.view(np.uint8).reshape(-1, size) != b.view(np.uint8).reshape(-1, size)).any(axis=1).sum())
-
-
 def _same(w, rec, queries, what, capacity=None, kinds=("overlap", "penetration")):
     """For each call family: the wide count-only call, then the wide list call with `capacity` (None: exactly the total), against the brute force
-    and against the plain call -- offsets, records and the sentinel behind the written prefix.  Returns the host offsets and the total."""
+    (list_util.same_lists) and against the plain call -- offsets, records and the sentinel behind the written prefix, which the wide call's were
+    just found to share with the brute force's byte for byte.  Returns the host offsets and the total."""
     for kind in kinds:
         wide, plain, dtype, brute = KINDS[kind]
-        cnt, _ = _gpu(w, wide, queries, None, dtype)
-        ref_cnt, _, total = brute(rec, w.nbox, queries, capacity=0)
-        assert cnt.tobytes() == ref_cnt.tobytes(), f"{what} / {kind}: count-only offsets differ from the brute force in {int((cnt != ref_cnt).sum())} of {len(cnt)}"
-        assert cnt.tobytes() == _gpu(w, plain, queries, None, dtype)[0].tobytes(), f"{what} / {kind}: count-only offsets differ from the plain call's"
-        cap = (0 if total >= NONE else total) if capacity is None else capacity
-        off, hits = _gpu(w, wide, queries, cap, dtype)
-        ref_hits = np.frombuffer(bytes([SENTINEL]) * dtype.itemsize * max(cap, 1), dtype=dtype).copy()
-        ref_off, ref_hits, _ = brute(rec, w.nbox, queries, capacity=cap, hits=ref_hits)
-        plain_off, plain_hits = _gpu(w, plain, queries, cap, dtype)
-        assert off.tobytes() == cnt.tobytes(), f"{what} / {kind}: list-mode offsets differ from count-only ones"
-        assert off.tobytes() == ref_off.tobytes() and off.tobytes() == plain_off.tobytes(), f"{what} / {kind}: offsets differ"
-        assert hits.tobytes() == ref_hits.tobytes(), f"{what} / {kind}: {_differ(hits, ref_hits)} of {len(hits)} records differ from the brute force"
-        assert hits.tobytes() == plain_hits.tobytes(), f"{what} / {kind}: {_differ(hits, plain_hits)} of {len(hits)} records differ from the plain call's"
+        ref_off, ref_hits, total = same_lists(w, wide, brute, rec, queries, dtype, f"{what} / {kind}", capacity, with_hits=True)
+        assert ref_off.tobytes() == _gpu(w, plain, queries, None, dtype)[0].tobytes(), f"{what} / {kind}: count-only offsets differ from the plain call's"
+        plain_off, plain_hits = _gpu(w, plain, queries, (0 if total >= NONE else total) if capacity is None else capacity, dtype)
+        assert ref_off.tobytes() == plain_off.tobytes(), f"{what} / {kind}: offsets differ from the plain call's"
+        assert ref_hits.tobytes() == plain_hits.tobytes(), f"{what} / {kind}: {differ(ref_hits, plain_hits)} of {len(ref_hits)} records differ from the plain call's"
     return ref_off, total
 
 
@@ -479,39 +453,11 @@ def _query(w, qt, ot, ht):
 
 
 def test_wide_calls_between_nh_step_calls_change_nothing():
-    scene = OBSERVED["grid_tiles"]()
-    a, b = E.World(scene, flags=FUSED), E.World(scene, flags=FUSED)
-    qt, ot, ht = _observer_batch(a, scene)
-    done = 0
-    for k in [1, 2, 3, 5, 7, 4, 8] * 10:
-        k = min(k, 300 - done)
-        if k <= 0:
-            break
-        _query(a, qt, ot, ht)
-        a.step(k)
-        b.step(k)
-        done += k
-    _query(a, qt, ot, ht)
-    assert done == 300
-    _same_stepped_world(a, b, "grid_tiles nh_step")
-    assert a.counts()["still_steps"] > 0, a.counts()
-    a.close(); b.close()
+    LU.queries_between_nh_step_calls_change_nothing(OBSERVED["grid_tiles"], _observer_batch, _query, "grid_tiles", still=True)
 
 
 def test_wide_calls_between_every_call_of_the_fused_step_change_nothing():
-    scene = OBSERVED["pile"]()
-    a, b = E.World(scene, flags=FUSED), E.World(scene, flags=FUSED)
-    qt, ot, ht = _observer_batch(a, scene)
-    calls = ("collide", "gravity", "read_cache", "setup", "apply", "update", "write_cache", "advance")
-    for s in range(120):
-        for name in calls:
-            _query(a, qt, ot, ht)
-            getattr(a, name)()
-            getattr(b, name)()
-        a.step_done(); b.step_done()
-    _query(a, qt, ot, ht)
-    _same_stepped_world(a, b, "pile call by call")
-    a.close(); b.close()
+    LU.queries_between_every_call_of_the_fused_step_change_nothing(OBSERVED["pile"], _observer_batch, _query, "pile", steps=120)
 
 
 # ---- trigger events fed by the wide lists ---------------------------------------------------------------------------------------------------

@@ -14,15 +14,14 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import hostpen_util as H                     # noqa: E402
 import hostquery_util as Q                   # noqa: E402
-from query_util import OBSERVED, SMALL, bounds as _bounds, same_stepped_world as _same_stepped_world, unit_quats as _unit_quats, upload as _upload      # noqa: E402
+import list_util as LU                       # noqa: E402
+from list_util import SENTINEL, gpu_list, same_lists      # noqa: E402
+from query_util import FUSED, NONE, OBSERVED, SMALL, bounds as _bounds, unit_quats as _unit_quats, upload as _upload      # noqa: E402
 from nudge_amd import engine as E           # noqa: E402
 from nudge_amd import scenes as S           # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-NONE = 0xFFFFFFFF
-FUSED = E.NH_FLAG_SINGLE_APPLY | E.NH_FLAG_FUSED_STEP
-SENTINEL = 0xA5
 KINDS = ("sphere", "box", "capsule", "mixed")
 
 
@@ -70,42 +69,17 @@ def _queries(rng, n, rec, kind, scale=1.0):
 
 def _gpu(w, queries, capacity, call="penetration"):
     """(offsets, hits): one call with `hits` pre-filled with the sentinel (capacity records; None = count only)."""
-    import torch
-    size, dtype, fn = (32, E.PENETRATION_HIT, w.penetration_records) if call == "penetration" else (16, E.OVERLAP_HIT, w.overlap_records)
-    qt = _upload(w, queries)
-    ot = torch.full((len(queries) + 1,), -1, dtype=torch.int32, device=w.dev)
-    ht = None if capacity is None else torch.full((max(capacity, 1), size), SENTINEL, dtype=torch.uint8, device=w.dev)
-    fn(qt, offsets=ot, hits=ht, capacity=capacity or 0)
-    off = ot.cpu().numpy().view(np.uint32).copy()
-    hits = None if ht is None else np.frombuffer(ht.cpu().numpy().tobytes(), dtype=dtype).copy()
-    return off, hits
-
-
-def _host(rec, nbox, queries, capacity):
-    hits = np.frombuffer(bytes([SENTINEL]) * 32 * max(capacity, 1), dtype=E.PENETRATION_HIT).copy()
-    return H.penetration(rec, nbox, queries, capacity=capacity, hits=hits)
-
-
-def _differ(a, b):
-    return int((a.view(np.uint8).reshape(-1, 32) != b.view(np.uint8).reshape(-1, 32)).any(axis=1).sum())
+    return gpu_list(w, call + "_records", queries, capacity, E.PENETRATION_HIT if call == "penetration" else E.OVERLAP_HIT)
 
 
 def _same(w, rec, queries, what, capacity=None):
     """The count-only call, then a list call with `capacity` (None: exactly the total), against the brute force -- and against nh_overlap on the
     GPU itself; returns the host offsets and the total."""
-    cnt, _ = _gpu(w, queries, None)
-    ref_cnt, _, total = H.penetration(rec, w.nbox, queries, capacity=0)
-    assert cnt.tobytes() == ref_cnt.tobytes(), f"{what}: count-only offsets differ in {int((cnt != ref_cnt).sum())} of {len(cnt)}"
-    cap = (0 if total >= NONE else total) if capacity is None else capacity
-    off, hits = _gpu(w, queries, cap)
-    ref_off, ref_hits, _ = _host(rec, w.nbox, queries, cap)
-    assert off.tobytes() == cnt.tobytes(), f"{what}: list-mode offsets differ from count-only ones"
-    assert off.tobytes() == ref_off.tobytes(), f"{what}: offsets differ"
-    assert hits.tobytes() == ref_hits.tobytes(), f"{what}: {_differ(hits, ref_hits)} of {len(hits)} records differ"
-    ooff, ohits = _gpu(w, queries, cap, call="overlap")
+    off, hits, total = same_lists(w, "penetration_records", H.penetration, rec, queries, E.PENETRATION_HIT, what, capacity, with_hits=True)
+    ooff, ohits = _gpu(w, queries, (0 if total >= NONE else total) if capacity is None else capacity, call="overlap")
     assert ooff.tobytes() == off.tobytes(), f"{what}: offsets differ from nh_overlap's"
     assert hits.view(np.uint8).reshape(-1, 32)[:, 16:].tobytes() == ohits.view(np.uint8).reshape(-1, 16).tobytes(), f"{what}: records differ from nh_overlap's"
-    return ref_off, total
+    return off, total
 
 
 def _check_world(w, scene, rng, n, what, build=True):
@@ -149,7 +123,7 @@ def test_count_only_and_a_capacity_in_the_middle_of_the_list():
         off, hits = _gpu(w, q, cap)
         written = int(full_off[np.searchsorted(full_off, cap, side="right") - 1])
         assert off.tobytes() == full_off.tobytes(), cap
-        assert hits[:written].tobytes() == full[:written].tobytes(), (cap, _differ(hits[:written], full[:written]))
+        assert hits[:written].tobytes() == full[:written].tobytes(), (cap, LU.differ(hits[:written], full[:written]))
         assert (hits[written:].view(np.uint8) == SENTINEL).all(), cap          # every byte behind the written prefix is untouched
         _same(w, rec, q, f"capacity {cap}", capacity=cap)
     w.close()
@@ -279,7 +253,6 @@ def _query(w, queries_t, offsets_t, hits_t, capacity):
 
 @pytest.mark.parametrize("name", sorted(OBSERVED))
 def test_penetration_queries_between_calls_change_nothing(name):
-    scene = OBSERVED[name]()
     rng = np.random.default_rng(76)
     n, cap = 4096, 1 << 16
     q = np.zeros(n, dtype=E.OVERLAP_QUERY)
@@ -287,38 +260,10 @@ def test_penetration_queries_between_calls_change_nothing(name):
     q["center"] = rng.uniform((-30, -12, -30), (30, 20, 30), size=(n, 3))
     q["rotation"], q["size"] = _unit_quats(rng, n), rng.uniform(0.1, 3.0, size=(n, 3))
 
-    def buffers(w):
-        return _upload(w, q), w.torch.empty(n + 1, dtype=w.torch.int32, device=w.dev), w.torch.empty((cap, 32), dtype=w.torch.uint8, device=w.dev)
+    def buffers(w, scene):
+        return _upload(w, q), w.torch.empty(n + 1, dtype=w.torch.int32, device=w.dev), w.torch.empty((cap, 32), dtype=w.torch.uint8, device=w.dev), cap
 
-    # between nh_step calls
-    a, b = E.World(scene, flags=FUSED), E.World(scene, flags=FUSED)
-    qt, ot, ht = buffers(a)
-    done = 0
-    for k in [1, 2, 3, 5, 7, 4, 8] * 10:
-        k = min(k, 300 - done)
-        if k <= 0:
-            break
-        _query(a, qt, ot, ht, cap)
-        a.step(k)
-        b.step(k)
-        done += k
-    _query(a, qt, ot, ht, cap)
-    _same_stepped_world(a, b, f"{name} nh_step")
+    still = name == "grid_tiles"
+    _, ot, _, _ = LU.queries_between_nh_step_calls_change_nothing(OBSERVED[name], buffers, _query, name, still=still)
     assert 0 < (int(ot[n]) & NONE) != NONE                                     # the queries did find something
-    if name == "grid_tiles":
-        assert a.counts()["still_steps"] > 0, a.counts()
-    a.close(); b.close()
-    # between every call of the fused step
-    a, b = E.World(scene, flags=FUSED), E.World(scene, flags=FUSED)
-    qt, ot, ht = buffers(a)
-    for s in range(300):
-        for call in ("collide", "gravity", "read_cache", "setup", "apply", "update", "write_cache", "advance"):
-            _query(a, qt, ot, ht, cap)
-            getattr(a, call)()
-            getattr(b, call)()
-        a.step_done(); b.step_done()
-    _query(a, qt, ot, ht, cap)
-    _same_stepped_world(a, b, f"{name} call by call")
-    if name == "grid_tiles":
-        assert a.counts()["still_steps"] > 0, a.counts()
-    a.close(); b.close()
+    LU.queries_between_every_call_of_the_fused_step_change_nothing(OBSERVED[name], buffers, _query, name, still=still)

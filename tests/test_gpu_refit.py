@@ -51,7 +51,7 @@ def _host(rec, nbox, b):
     cap_off, _, cap_total = HC.overlap(rec, nbox, b["capsule_overlaps"], capacity=0)
     return dict(rays=CAST.cast(CAST.RAY, rec, nbox, b["rays"]), spheres=CAST.cast(CAST.SPHERE, rec, nbox, b["spheres"]), boxes=CAST.cast(CAST.BOX, rec, nbox, b["boxes"]),
                 capsules=CAST.cast(CAST.CAPSULE, rec, nbox, b["capsules"]), points=HP.closest(rec, nbox, b["points"]),
-                overlap_counts=ov_off, overlap_list=TO._host(rec, nbox, b["overlaps"], ov_total)[:2],
+                overlap_counts=ov_off, overlap_list=TO.O.overlap(rec, nbox, b["overlaps"], capacity=ov_total, hits=TO.sentinel_hits(ov_total, E.OVERLAP_HIT))[:2],
                 capsule_counts=cap_off, capsule_list=_capsule_host(rec, nbox, b["capsule_overlaps"], cap_total))
 
 

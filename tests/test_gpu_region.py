@@ -14,16 +14,14 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import filter_util as F                      # noqa: E402
 import hostregion_util as R                  # noqa: E402
-from query_util import SMALL, bounds as _bounds, unit_quats as _unit_quats      # noqa: E402
-from test_gpu_overlap import OBSERVED, _same_stepped_world, _upload             # noqa: E402
+import list_util as LU                       # noqa: E402
+from list_util import SENTINEL, gpu_list, same_lists, sentinel_hits      # noqa: E402
+from query_util import FUSED, NONE, OBSERVED, SMALL, bounds as _bounds, unit_quats as _unit_quats, upload as _upload      # noqa: E402
 from nudge_amd import engine as E           # noqa: E402
 from nudge_amd import scenes as S           # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-NONE = 0xFFFFFFFF
-FUSED = E.NH_FLAG_SINGLE_APPLY | E.NH_FLAG_FUSED_STEP
-SENTINEL = 0xA5
 RUN = 1024                                   # NH_Q_RUN
 
 
@@ -126,35 +124,13 @@ def _regions(rng, n, rec):
 # ---- the comparison -------------------------------------------------------------------------------------------------------------------------
 def _gpu(w, regs, capacity):
     """(offsets, hits): one nh_region call with `hits` pre-filled with the sentinel (capacity records; None = count only)."""
-    import torch
-    qt = _upload(w, regs)
-    ot = torch.full((len(regs) + 1,), -1, dtype=torch.int32, device=w.dev)
-    ht = None if capacity is None else torch.full((max(capacity, 1), 16), SENTINEL, dtype=torch.uint8, device=w.dev)
-    w.region_records(qt, offsets=ot, hits=ht, capacity=capacity or 0)
-    off = ot.cpu().numpy().view(np.uint32).copy()
-    hits = None if ht is None else np.frombuffer(ht.cpu().numpy().tobytes(), dtype=E.OVERLAP_HIT).copy()
-    return off, hits
-
-
-def _host(rec, nbox, regs, capacity):
-    hits = np.frombuffer(bytes([SENTINEL]) * 16 * max(capacity, 1), dtype=E.OVERLAP_HIT).copy()
-    return R.region(rec, nbox, regs, capacity=capacity, hits=hits)
+    return gpu_list(w, "region_records", regs, capacity, E.OVERLAP_HIT)
 
 
 def _same(w, rec, regs, what, capacity=None):
     """The count-only call, then a list call with `capacity` (None: exactly the total), against the brute force -- the sentinel behind the written
     prefix included; returns the host offsets and the total."""
-    cnt, _ = _gpu(w, regs, None)
-    ref_cnt, _, total = R.region(rec, w.nbox, regs, capacity=0)
-    assert cnt.tobytes() == ref_cnt.tobytes(), f"{what}: count-only offsets differ in {int((cnt != ref_cnt).sum())} of {len(cnt)}"
-    cap = total if capacity is None else capacity
-    off, hits = _gpu(w, regs, cap)
-    ref_off, ref_hits, _ = _host(rec, w.nbox, regs, cap)
-    assert off.tobytes() == cnt.tobytes(), f"{what}: list-mode offsets differ from count-only ones"
-    assert off.tobytes() == ref_off.tobytes(), f"{what}: offsets differ"
-    assert hits.tobytes() == ref_hits.tobytes(), \
-        f"{what}: {int((hits.view(np.uint8).reshape(-1, 16) != ref_hits.view(np.uint8).reshape(-1, 16)).any(axis=1).sum())} of {len(hits)} records differ"
-    return ref_off, total
+    return same_lists(w, "region_records", R.region, rec, regs, E.OVERLAP_HIT, what, capacity)
 
 
 def _records(w, scene, bodies=None):
@@ -481,7 +457,7 @@ def test_abi_edge_cases():
     # offsets need 4-byte alignment only
     ot4 = buf[1:66]
     assert L.nh_region(w.ctx, qp, 64, C.c_void_p(ot4.data_ptr()), hp, 4096, 0) == 0
-    ref_off, ref_hits, total = _host(rec, w.nbox, regs, 4096)
+    ref_off, ref_hits, total = R.region(rec, w.nbox, regs, capacity=4096, hits=sentinel_hits(4096, E.OVERLAP_HIT))
     assert 0 < total <= 4096
     assert ot4.cpu().numpy().view(np.uint32).tobytes() == ref_off.tobytes()
     got = np.frombuffer(ht.cpu().numpy().tobytes(), dtype=E.OVERLAP_HIT)
@@ -506,36 +482,8 @@ def _query(w, qt, ot, ht):
 
 
 def test_regions_between_nh_step_calls_change_nothing():
-    scene = OBSERVED["grid_tiles"]()
-    a, b = E.World(scene, flags=FUSED), E.World(scene, flags=FUSED)
-    qt, ot, ht = _observer_batch(a, scene)
-    done = 0
-    for k in [1, 2, 3, 5, 7, 4, 8] * 10:
-        k = min(k, 300 - done)
-        if k <= 0:
-            break
-        _query(a, qt, ot, ht)
-        a.step(k)
-        b.step(k)
-        done += k
-    _query(a, qt, ot, ht)
-    assert done == 300
-    _same_stepped_world(a, b, "grid_tiles nh_step")
-    assert a.counts()["still_steps"] > 0, a.counts()
-    a.close(); b.close()
+    LU.queries_between_nh_step_calls_change_nothing(OBSERVED["grid_tiles"], _observer_batch, _query, "grid_tiles", still=True)
 
 
 def test_regions_between_every_call_of_the_fused_step_change_nothing():
-    scene = OBSERVED["pile"]()
-    a, b = E.World(scene, flags=FUSED), E.World(scene, flags=FUSED)
-    qt, ot, ht = _observer_batch(a, scene)
-    calls = ("collide", "gravity", "read_cache", "setup", "apply", "update", "write_cache", "advance")
-    for s in range(120):
-        for name in calls:
-            _query(a, qt, ot, ht)
-            getattr(a, name)()
-            getattr(b, name)()
-        a.step_done(); b.step_done()
-    _query(a, qt, ot, ht)
-    _same_stepped_world(a, b, "pile call by call")
-    a.close(); b.close()
+    LU.queries_between_every_call_of_the_fused_step_change_nothing(OBSERVED["pile"], _observer_batch, _query, "pile", steps=120)

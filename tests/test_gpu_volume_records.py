@@ -14,12 +14,13 @@ import hostcapsule_util as HC                # noqa: E402
 import hostdistance_util as D                # noqa: E402
 import hostpen_util as HP                    # noqa: E402
 import hostquery_util as Q                   # noqa: E402
+from list_util import gpu_list               # noqa: E402
+from query_util import upload as _upload      # noqa: E402
 from volume_records import distance_bases, distance_lists, overlap_lists      # noqa: E402
 from nudge_amd import engine as E           # noqa: E402
 from nudge_amd import scenes as S           # noqa: E402
 
 FUSED = E.NH_FLAG_SINGLE_APPLY | E.NH_FLAG_FUSED_STEP
-SENTINEL = 0xA5
 
 
 def _batch():
@@ -73,21 +74,6 @@ def test_the_two_oracles_agree_on_which_records_are_valid():
     assert int((~md_ok).sum()) == 9 and int(valid.sum()) == 9 + 2 + 3 + 1 + 1
 
 
-def _upload(w, arr):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(arr).view(np.uint8).copy()).to(w.dev)
-
-
-def _list_call(w, fn, size, dtype, queries, capacity):
-    import torch
-    qt = _upload(w, queries)
-    ot = torch.full((len(queries) + 1,), -1, dtype=torch.int32, device=w.dev)
-    ht = None if capacity is None else torch.full((max(capacity, 1), size), SENTINEL, dtype=torch.uint8, device=w.dev)
-    fn(qt, offsets=ot, hits=ht, capacity=capacity or 0)
-    off = ot.cpu().numpy().view(np.uint32).copy()
-    return off, None if ht is None else np.frombuffer(ht.cpu().numpy().tobytes(), dtype=dtype).copy()
-
-
 @pytest.mark.gpu
 def test_one_batch_of_every_invalid_and_every_unspoiled_record():
     scene = S.pile(0, 2, seed=3)
@@ -104,15 +90,15 @@ def test_one_batch_of_every_invalid_and_every_unspoiled_record():
 
     ref_off, ref_hits, total = HC.overlap(rec, w.nbox, o)
     assert 0 < total < 3 * len(q)
-    cnt, _ = _list_call(w, w.overlap_records, 16, E.OVERLAP_HIT, o, None)
-    off, hits = _list_call(w, w.overlap_records, 16, E.OVERLAP_HIT, o, total)
+    cnt, _ = gpu_list(w, "overlap_records", o, None, E.OVERLAP_HIT)
+    off, hits = gpu_list(w, "overlap_records", o, total, E.OVERLAP_HIT)
     assert cnt.tobytes() == ref_off.tobytes() and off.tobytes() == ref_off.tobytes()
     assert hits.tobytes() == ref_hits[:total].tobytes()
 
     pen_off, pen_hits, pen_total = HP.penetration(rec, w.nbox, o)
     assert pen_total == total
-    pcnt, _ = _list_call(w, w.penetration_records, 32, HP.HIT, o, None)
-    poff, phits = _list_call(w, w.penetration_records, 32, HP.HIT, o, total)
+    pcnt, _ = gpu_list(w, "penetration_records", o, None, HP.HIT)
+    poff, phits = gpu_list(w, "penetration_records", o, total, HP.HIT)
     assert pcnt.tobytes() == pen_off.tobytes() and poff.tobytes() == pen_off.tobytes()
     assert phits.tobytes() == pen_hits[:total].tobytes()
     assert poff.tobytes() == off.tobytes()
