@@ -958,6 +958,89 @@ int nh_overlap_bodies(nh_context* ctx, uint32_t count, const nh_HitList* in, con
 int nh_overlap_events(nh_context* ctx, uint32_t count, const nh_HitList* prev /* or NULL */, const nh_HitList* cur, const nh_HitList* entered,
                       const nh_HitList* left, uint32_t flags /* 0 or NH_EVENTS_BY_BODY */);
 
+/* CONTACT EVENTS -- nh_contact_pairs, nh_contact_events and nh_step_contact_pairs: which body pairs touch, how hard, and which pairs BEGAN and STOPPED
+   touching since the last step, computed on the device.  The solver's contact list has one record per contact POINT, in collider-tag order; what a game,
+   a robot or a recorder acts on is one record per BODY PAIR and the difference of two steps' records.
+   nh_contact_pairs -- ONE RECORD PER UNORDERED BODY PAIR of a contact list (nh_ContactList: a host struct of DEVICE pointers; the list is the first
+   min(*count, capacity) contacts, or `capacity` of them with count == NULL; nothing at or beyond `capacity` is ever read), sorted ascending by (lo, hi).
+   The rules are exact -- a host oracle reproduces every byte (tests/hostoracle/hostcontacts.cpp):
+     - a contact's pair is lo = min(a, b), hi = max(a, b); the contact is FLIPPED when its `a` is not lo, and then contributes its impulse and its
+       normal with the sign inverted (exact), so that every vector of a record has the sense lo -> hi; a == b is a pair like any other;
+     - a RUN is a maximal stretch of consecutive contacts of the list with the same (lo, hi) -- contacts are in tag order, so a collider pair's points
+       are one run.  A run's sums start at +0 and take its contacts left to right in fp32, a contact's normal impulse being
+       (ix * nx + iy * ny) + iz * nz (the library is built with -ffp-contract=off);
+     - a pair's `impulse` and `normal_impulse` start at +0 and take its runs' sums in list order.  This TWO-LEVEL order is the specification, not an
+       implementation detail: it is what lets the runs be reduced before the sort.  Sums with a NaN in them are NaN, of unspecified payload;
+     - the DEEPEST contact: start with the pair's first contact and replace iff penetration > best, in list order -- ties keep the lower index, a NaN
+       penetration never replaces anything, and one that comes first is never replaced.  position, penetration, normal (same sense) and `deepest`,
+       its index in the list, are that contact's;
+     - `first` is the lowest contact index of the pair and `count` the number of its contact points.
+   `impulses` holds one nh_CachedContactImpulse per contact (`unused` is not read), or is NULL: every impulse is zero.  `body_count` promises that every
+   body index of the list is below it and sizes the sort keys -- lo << bits | hi, sorted over only the 8-bit passes that 2 x bits(body_count - 1) need;
+   0 = unknown, all 64 bits.  A list that breaks the promise gives unspecified records, never an access outside the arrays.
+   OUTPUT (nh_PairList; `out`, `began`, `ended`, each on its own): *count always receives the true number of records; the records are written iff that
+   number is <= capacity -- all or none, as nh_overlap does with a segment -- every byte behind the written records is left untouched, and so is every
+   byte of `pairs` when nothing is written.  COUNT ONLY: pairs == NULL and capacity == 0.
+   nh_contact_events -- THE DIFFERENCE OF TWO PAIR LISTS, both outputs of nh_contact_pairs / nh_step_contact_pairs (unique ascending keys).  A list is
+   PRESENT iff its *count <= capacity.  If `cur` or a non-NULL `prev` is absent both outputs count 0.  `began` gets cur's records whose (lo, hi) is not
+   in prev, copied whole from cur in cur's order; `ended` gets prev's records that are not in cur, copied from prev: they carry the values of the last
+   step the pair touched.  prev == NULL is the FIRST FRAME: `began` equals cur and `ended` is empty.  Outputs must not alias inputs or each other.
+   nh_step_contact_pairs -- THE SAME FOR THE WORLD'S OWN LAST STEP, with no download: it (1) calls nh_export_views(NH_VIEW_CONTACTS | NH_VIEW_CACHE) -- a
+   no-op after a full step; it has that call's effect on speculation (note 9) and no other, so nh_Counts.still_steps / still_replays are those of a world
+   that calls nh_export_views at the same places --, (2) takes the contact and the cache count from the context's device counters, clamped to the two
+   capacities, (3) finds each contact's cache entry by (tag, feature) -- the binary search nh_read_cached_impulses does; a contact without an entry has a
+   zero impulse -- and (4) runs nh_contact_pairs' pipeline on the result.  `contacts` and `cache` are the structs of the step.  It changes no body state,
+   no counter of nh_Counts and nothing a later step computes.  Call it after nh_advance, or after nh_step returns: the cache then holds the impulses the
+   step solved, as world-space vectors (nudge.cpp:4857-4884).  BETWEEN nh_collide AND nh_write_cached_impulses THE CACHE IS STILL LAST STEP'S: there the
+   impulses are the warm-start values of the contacts that persist and zero for the new ones, not what this step will solve.
+   Returns NH_ERR_INVALID, before any launch, for flags != 0; for a NULL ctx, in, out, cur, began, ended, contacts or cache; for a pair list whose `count`
+   is NULL or not 4-byte aligned, whose `pairs` is NULL with capacity > 0 or not 16-byte aligned; for a contact list with capacity > 0 and a NULL data or
+   bodies (the step-bound call: any NULL array of either struct), for `data` or `impulses` not 16-byte or `bodies` not 8-byte aligned; and for any capacity
+   of 2^31 or more.  A contact list of capacity 0 is the empty list: *out->count = 0 and no other launch.  nh_contact_pairs and nh_contact_events read
+   lists only and need no nh_query_build; like the trigger events they are no entry points of the step (note 9).
+   SCRATCH is the context's: per contact of the largest `capacity` seen 92 B (a 64-byte run record, two 8-byte keys, two 4-byte values, one flag word), per
+   pair of the largest prev.capacity + cur.capacity seen 4 B (one flag word, scanned in place), and 514 KB for the sort.  It grows after a stream
+   synchronise, only when a capacity exceeds every earlier one; nh_destroy frees it.  Everything else is enqueued on the context's stream.
+   HOW: flag the run heads, scan, one lane per run head walks its run and writes one partial record; the stable radix sort orders the run
+   keys; flag the pair heads, scan, one lane per pair head merges its runs in order and writes the record with four 16-byte stores.  Events: per record a
+   binary search in the other list, a scan, a copy.  No atomics: the bytes are a function of the input alone.  A run or a pair with very many members --
+   one huge compound body resting on another -- is walked by ONE lane: correct and slow; there is no second path.
+   Timing labels: cp_run_flag, cp_runs, cp_runs_lookup, cp_pair_flag, cp_merge; cp_ev_flag, cp_ev_compact; the sort's and the scan's own between them.
+   MEASURED (tools/contact_events_rates.py -> profiles/contact_events_rates.log; one MI355X, one run, the landed config-2 world of 1,004,401 bodies, 4,017,582
+   contacts and 1,004,400 body pairs; ms per call, the best of 5 blocks of 10 calls by device events; in brackets the price in steady steps of the same run):
+     nh_step(1), still steps / full steps (option no_still)                    0.280 / 0.497
+     nh_contact_pairs on the exported views (count only)                       0.309 (0.279)
+     nh_step_contact_pairs, views current                                      0.374
+     nh_step_contact_pairs behind every step, by difference: after a still step, view export included / after a full step     0.545 (1.95) / 0.378 (0.76)
+     nh_contact_events on two consecutive steps' lists (0 began, 0 ended) / the first frame            0.084 / 0.041
+     nh_overlap_bodies on one list of 1,004,524 records, the nearest existing sort-and-compact         0.168
+   The sort of the 1 M run keys -- five passes for 2 x 20 key bits -- is 0.19 of the 0.31 ms, the run walk 0.09 (0.14 with the cache search), the merge 0.035; the events' time
+   is the flag kernel's binary searches (0.07).  The pair list equals the host oracle byte for byte.  No bar was set in advance.
+   Not built: a "stayed" list (it is `cur` minus `began`); per-body reductions; a threshold filter (threshold `normal_impulse` yourself). */
+typedef struct nh_ContactPair {      /* 64 bytes */
+	uint32_t lo, hi;             /* the two bodies, lo <= hi */
+	uint32_t first, count;       /* lowest contact index of the pair in the input list; number of contact points */
+	float impulse[3];            /* sum of the contacts' impulse vectors, in the sense lo -> hi */
+	float normal_impulse;        /* sum of dot(impulse_i, normal_i) */
+	float position[3]; float penetration;   /* of the DEEPEST contact */
+	float normal[3];             /* of that contact, same sense */
+	uint32_t deepest;            /* its index in the input list */
+} nh_ContactPair;
+typedef struct nh_ContactList {      /* host struct, DEVICE pointers */
+	const nh_Contact* data; const nh_BodyPair* bodies;
+	const nh_CachedContactImpulse* impulses;   /* one per contact, or NULL: all zero */
+	const uint32_t* count;       /* device word, or NULL: `capacity` is the count */
+	uint32_t capacity;           /* host bound: nothing at or beyond it is ever read; *count is clamped to it */
+	uint32_t body_count;         /* every body index < body_count (sizes the sort keys), or 0: unknown, full 32 bits */
+} nh_ContactList;
+typedef struct nh_PairList { uint32_t* count /* device word */; nh_ContactPair* pairs /* 16-byte aligned */; uint32_t capacity; uint32_t reserved; } nh_PairList;
+
+int nh_contact_pairs(nh_context* ctx, const nh_ContactList* in, const nh_PairList* out, uint32_t flags /* 0 */);
+int nh_contact_events(nh_context* ctx, const nh_PairList* prev /* or NULL */, const nh_PairList* cur,
+                      const nh_PairList* began, const nh_PairList* ended, uint32_t flags /* 0 */);
+int nh_step_contact_pairs(nh_context* ctx, const nh_ContactData* contacts, const nh_ContactCache* cache,
+                          uint32_t body_count, const nh_PairList* out, uint32_t flags /* 0 */);
+
 /* nh_distance: how far each of `count` query shapes is from the world of the LAST nh_query_build or nh_query_refit, and towards what -- the clearance
    of a crate, a hull or a limb.  nh_penetration describes a pair that overlaps; this describes the pairs that do not.
    Query shapes: nh_overlap's (NH_SHAPE_SPHERE, NH_SHAPE_BOX, NH_SHAPE_CAPSULE), the same fields read and the same validity rules; the first 48 bytes

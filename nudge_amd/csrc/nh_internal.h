@@ -473,9 +473,11 @@ struct nh_context {
 	uint32_t first_ghost;          // nh_set_first_ghost_body: bodies >= first_ghost are ghosts of a partitioned world (0 = no ownership rule)
 	nh_StateStream stream_state;
 	struct nh_QueryState* query;   // scene queries (nh_query_tree.h): the hierarchy of the last nh_query_build; nullptr until the first
+	struct nh_CpState* contact_events;   // contact events (nh_contact_events.hip): the scratch of nh_contact_pairs / nh_contact_events; nullptr until the first call
 };
 int nh_stream_after_advance(nh_context* ctx);          // nh_advance -> state streaming (nh_context.hip)
 void nh_query_free(nh_context* ctx);                   // nh_destroy -> the scene query's buffers (nh_query_build.hip)
+void nh_contact_events_free(nh_context* ctx);          // nh_destroy -> the contact events' scratch (nh_contact_events.hip)
 
 // ---- functions used across the .hip files: each is declared here, once, and defined in the file named behind it --------------------------------------
 // (NH_LOCAL: a helper of the library's own that is not part of what libnudge_hip.so exports)

@@ -49,6 +49,7 @@ EXPORTS = [
     "nh_query_set_layers", "nh_query_filter", "nh_query_layer_info",
     "nh_overlap_bodies", "nh_overlap_events",
     "nh_overlap_wide", "nh_penetration_wide",
+    "nh_contact_pairs", "nh_contact_events", "nh_step_contact_pairs",
 ]
 HALO_RECORD_BYTES = 64
 
@@ -209,6 +210,24 @@ NH_EVENTS_BY_BODY = 1                     # nh_overlap_events: a record's identi
 class HitList(C.Structure):
     """nh_HitList: a host struct of device pointers."""
     _fields_ = [("offsets", C.c_void_p), ("hits", C.c_void_p), ("capacity", C.c_uint32), ("reserved", C.c_uint32)]
+# contact events (include/nudge_hip.h): one record per touching body pair
+CONTACT_PAIR = np.dtype([("lo", "<u4"), ("hi", "<u4"), ("first", "<u4"), ("count", "<u4"), ("impulse", "<f4", 3), ("normal_impulse", "<f4"),
+                         ("position", "<f4", 3), ("penetration", "<f4"), ("normal", "<f4", 3), ("deepest", "<u4")])
+
+
+class ContactPair(C.Structure):
+    _fields_ = [("lo", C.c_uint32), ("hi", C.c_uint32), ("first", C.c_uint32), ("count", C.c_uint32), ("impulse", C.c_float * 3), ("normal_impulse", C.c_float),
+                ("position", C.c_float * 3), ("penetration", C.c_float), ("normal", C.c_float * 3), ("deepest", C.c_uint32)]
+
+
+class ContactList(C.Structure):
+    """nh_ContactList: a host struct of device pointers."""
+    _fields_ = [("data", C.c_void_p), ("bodies", C.c_void_p), ("impulses", C.c_void_p), ("count", C.c_void_p), ("capacity", C.c_uint32), ("body_count", C.c_uint32)]
+
+
+class PairList(C.Structure):
+    """nh_PairList: a host struct of device pointers."""
+    _fields_ = [("count", C.c_void_p), ("pairs", C.c_void_p), ("capacity", C.c_uint32), ("reserved", C.c_uint32)]
 REGION = np.dtype([("planes", "<f4", (NH_REGION_MAX_PLANES, 4)), ("plane_count", "<u4"), ("ignore_body", "<u4"), ("reserved", "<u4", 2)])
 
 
@@ -384,6 +403,11 @@ def lib():
         if hasattr(L, "nh_overlap_events"):
             L.nh_overlap_bodies.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]
             L.nh_overlap_events.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+        # (likewise the contact events: World.contact_pairs_records / contact_events_records / step_contact_pairs then raise AttributeError)
+        if hasattr(L, "nh_contact_events"):
+            L.nh_contact_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+            L.nh_contact_events.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+            L.nh_step_contact_pairs.argtypes = [C.c_void_p, C.POINTER(ContactData), C.POINTER(ContactCache), C.c_uint32, C.c_void_p, C.c_uint32]
         _LIB = L
     return _LIB
 
@@ -1569,6 +1593,73 @@ class World:
         if synchronize:
             torch.cuda.current_stream(self.dev).synchronize()
         return r
+
+    # ---- contact events: which body pairs touch, began and stopped touching (include/nudge_hip.h, "contact events") ----
+    def _pair_list(self, what, count, pairs, capacity):
+        """The nh_PairList of (count, pairs, capacity): `count` a device tensor of one 32-bit word, `pairs` None or at least capacity x 64 bytes."""
+        if count.numel() * count.element_size() < 4:
+            raise ValueError(f"{what}: count holds {count.numel() * count.element_size()} bytes, not a 32-bit word")
+        if pairs is not None and pairs.numel() * pairs.element_size() < 64 * capacity:
+            raise ValueError(f"{what}: pairs holds {pairs.numel() * pairs.element_size()} bytes, capacity {capacity} needs {64 * capacity}")
+        return PairList(count.data_ptr(), pairs.data_ptr() if pairs is not None and capacity else 0, capacity, 0)
+
+    def _pair_out(self, out, capacity=0):
+        """`out` as given, or a new (count, pairs, capacity): a zero count word and capacity x 64 bytes (None where capacity is 0)."""
+        if out is not None:
+            return out
+        torch = self.torch
+        return (torch.zeros(1, dtype=torch.int32, device=self.dev),
+                torch.empty((capacity, 64), dtype=torch.uint8, device=self.dev) if capacity else None, capacity)
+
+    def contact_pairs_records(self, data, bodies, impulses=None, count=None, capacity=0, body_count=0, out=None):
+        """nh_contact_pairs: one record per unordered body pair of a contact list of device tensors -- `data` 32-byte nh_Contact records, `bodies`
+        (a, b) pairs, `impulses` 16-byte records or None (all zero), `count` a device word or None (`capacity` is the count).  `out` = (count, pairs,
+        capacity): a device word, None or capacity x 64 bytes (E.CONTACT_PAIR), the capacity; None: count only, with a new word.  Returns `out`.
+        Enqueued; nothing waits (but a capacity larger than any before grows the scratch)."""
+        out = self._pair_out(out)
+        lst = ContactList(data.data_ptr() if data is not None else 0, bodies.data_ptr() if bodies is not None else 0,
+                          impulses.data_ptr() if impulses is not None else 0, count.data_ptr() if count is not None else 0, capacity, body_count)
+        o = self._pair_list("contact_pairs_records", *out)
+        _check(self.L, self.L.nh_contact_pairs(self.ctx, C.byref(lst), C.byref(o), 0), "nh_contact_pairs")
+        return out
+
+    def contact_events_records(self, prev, cur, began=None, ended=None):
+        """nh_contact_events on pair lists, each (count, pairs, capacity): `prev` (or None: the first frame) and `cur` as contact_pairs_records /
+        step_contact_pairs wrote them, `began` and `ended` the outputs (None: count only, with new words).  Returns (began, ended)."""
+        began, ended = self._pair_out(began), self._pair_out(ended)
+        p = None if prev is None else self._pair_list("contact_events_records (prev)", *prev)
+        c, b, e = (self._pair_list(f"contact_events_records ({k})", *v) for k, v in (("cur", cur), ("began", began), ("ended", ended)))
+        _check(self.L, self.L.nh_contact_events(self.ctx, C.byref(p) if p is not None else None, C.byref(c), C.byref(b), C.byref(e), 0), "nh_contact_events")
+        return began, ended
+
+    def step_contact_pairs(self, out=None, capacity=None, body_count=None):
+        """nh_step_contact_pairs: the pair records of the world's own last step, with the solved impulses of its contact cache, without a download.
+        `out` = (count, pairs, capacity) as in contact_pairs_records, or None: a new list of `capacity` records (None: room for one pair per
+        contact the world can hold).  body_count=None: the world's.  Returns `out`.  Call it after step() or advance()."""
+        out = self._pair_out(out, self.max_contacts if capacity is None else capacity)
+        o = self._pair_list("step_contact_pairs", *out)
+        _check(self.L, self.L.nh_step_contact_pairs(self.ctx, C.byref(self.contacts), C.byref(self.cache), self.bodies.count if body_count is None else body_count,
+                                                    C.byref(o), 0), "nh_step_contact_pairs")
+        return out
+
+    def pair_records(self, lst):
+        """The host's copy of a pair list (count, pairs, capacity): (true count, E.CONTACT_PAIR records -- none where the count exceeds the capacity).
+        Waits for the stream."""
+        n = int(lst[0].cpu().numpy().view(np.uint32)[0])
+        if lst[1] is None or n > lst[2]:
+            return n, np.zeros(0, dtype=CONTACT_PAIR)
+        return n, np.frombuffer(lst[1].reshape(-1)[:64 * n].cpu().numpy().tobytes(), dtype=CONTACT_PAIR, count=n).copy()
+
+    def contact_events(self, prev, cur, capacity=None, synchronize=False):
+        """Which pairs began and which stopped touching between two pair lists: `prev` and `cur` are what step_contact_pairs / contact_pairs_records
+        returned on the last step and on this one (`prev` None: the first frame -- every pair of `cur` has begun).  capacity=None: each output gets
+        room for every record of its input -- nothing waits.  Returns dict(began=..., ended=...), each a (count, pairs, capacity) list: `began` holds
+        records of `cur`, `ended` records of `prev` -- the values of the last step the pair touched.  Keep `cur` as the next frame's `prev`."""
+        caps = [(src[2] if src is not None else 0) if capacity is None else capacity for src in (cur, prev)]
+        began, ended = self.contact_events_records(prev, cur, began=self._pair_out(None, caps[0]), ended=self._pair_out(None, caps[1]))
+        if synchronize:
+            self.torch.cuda.current_stream(self.dev).synchronize()
+        return dict(began=began, ended=ended)
 
     # ---- measurement ----
     def enable_timing(self, on=True, only=None):
