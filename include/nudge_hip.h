@@ -79,7 +79,7 @@
  *      exported the views: nh_set_option(ctx, "sync_exports_views", 1) restores that contract at its old price; INTEGRATION.md.)  Any entry point outside the sample's
  *      call order between nh_collide and nh_apply_impulses turns a still step into a full one first, so everything it observes is what a full step
  *      produces.  nh_Counts.still_steps / still_replays count them.
- *      The scene queries (nh_query_build, nh_query_refit, nh_raycast, nh_spherecast, nh_raycast_all, nh_spherecast_all, nh_boxcast_all, nh_capsulecast_all, nh_raycast_k, nh_spherecast_k, nh_boxcast_k, nh_capsulecast_k, nh_boxcast, nh_capsulecast, nh_overlap, nh_penetration, nh_overlap_wide, nh_penetration_wide, nh_region, nh_closest, nh_closest_k, nh_distance, nh_move, nh_recover, nh_walk, nh_boxmove, nh_boxwalk, nh_move_touched, nh_boxmove_touched, nh_walk_touched, nh_boxwalk_touched, nh_query_set_layers, nh_query_filter, nh_query_layer_info) are not entry points of the step in this sense: they neither export nor settle nor turn a still step into a
+ *      The scene queries (nh_query_build, nh_query_refit, nh_raycast, nh_spherecast, nh_raycast_all, nh_spherecast_all, nh_boxcast_all, nh_capsulecast_all, nh_raycast_k, nh_spherecast_k, nh_boxcast_k, nh_capsulecast_k, nh_boxcast, nh_capsulecast, nh_overlap, nh_penetration, nh_overlap_wide, nh_penetration_wide, nh_region, nh_sense, nh_sense_rays, nh_closest, nh_closest_k, nh_distance, nh_move, nh_recover, nh_walk, nh_boxmove, nh_boxwalk, nh_move_touched, nh_boxmove_touched, nh_walk_touched, nh_boxwalk_touched, nh_query_set_layers, nh_query_filter, nh_query_layer_info) are not entry points of the step in this sense: they neither export nor settle nor turn a still step into a
  *      full one, and they do not count -- see "scene queries" below.
  *
  * Threading: one context = one HIP stream = one world at a time; no global mutable state.
@@ -429,7 +429,8 @@ int nh_query_stats(nh_context* ctx, nh_QueryStats* out);
    An unknown mode, or a call before any nh_query_build, returns NH_ERR_INVALID; a refused call changes nothing -- the next query still uses the previous
    filter.  nh_query_filter is host state only: nothing is launched, nothing waits.  (The calls' own `flags` argument has no bit to spare for this.)
    THE CONTRACT, for all twenty-five query calls (nh_raycast, nh_spherecast, nh_boxcast, nh_capsulecast, their _all and _k forms, nh_overlap, nh_penetration,
-   nh_region, nh_closest, nh_closest_k, nh_distance, nh_move, nh_recover, nh_walk, nh_boxmove, nh_boxwalk; for nh_region the query is the region: NH_FILTER_PER_QUERY reads masks[i] for region i):
+   nh_region, nh_closest, nh_closest_k, nh_distance, nh_move, nh_recover, nh_walk, nh_boxmove, nh_boxwalk; for nh_region the query is the region: NH_FILTER_PER_QUERY reads masks[i] for region i)
+   and for the twenty-sixth, nh_sense (the query is the SENSOR: NH_FILTER_PER_QUERY reads masks[s] for every ray of sensor s; nh_sense_rays casts nothing and reads no filter):
      - MASKED WORLD: with the filter on, a query with mask m writes byte for byte what the same call with the filter OFF writes on a world that is the same
        except for one thing: every collider with (layers & m) == 0 has a NaN pose -- "a collider of a body that does not exist", which every call above
        documents as never hit, never listed, never reported.  Collider indices, bodies and tags in the records are those of the real world.  For
@@ -855,6 +856,62 @@ int nh_penetration(nh_context* ctx, const nh_OverlapQuery* queries, uint32_t cou
 typedef struct nh_Region { float planes[NH_REGION_MAX_PLANES][4]; uint32_t plane_count; uint32_t ignore_body; uint32_t reserved[2]; } nh_Region;   /* 144 B */
 int nh_region(nh_context* ctx, const nh_Region* regions, uint32_t count, uint32_t* offsets /* count + 1 */, nh_OverlapHit* hits, uint32_t capacity,
               uint32_t flags /* 0 */);
+
+/* ---- sensors: depth cameras and lidar fans cast from poses ---------------------------------------------------------------------------------------
+   nh_sense: `count` sensors with `beam_count` rays each -- agent perception, every step -- in ONE launch from (sensor poses, one shared beam pattern) to
+   depth / id images.  No nh_Ray and no nh_RayHit record is materialised: 4,096 agents with 64 x 64 beams are 16.7 M rays, 537 MB of ray records and
+   537 MB of hit records through nh_raycast, against 192 KB of sensors, 64 KB of pattern and 67 MB for a depth image here.  A sensor MOUNTED on a body
+   follows it with no per-frame upload: step -> nh_query_refit -> nh_sense is an agent's whole frame on the device.
+   THE RAY of beam j of sensor s has index i = s * beam_count + j and is the nh_Ray
+       origin = p_s,  direction = rotate(q_s, beams[j].direction),  max_t = beams[j].range,  ignore_body = sensors[s].ignore_body
+   (float32, exactly nudge_amd/csrc/nh_query.h, "sensors": nh_q_sensor_pose, nh_q_sensor_ray; rotate is the step's own quaternion rotation).  The pose
+   (p_s, q_s) is the sensor's own `position` / `rotation` when `body` == 0xffffffff or `bodies` == NULL (the `body` word is then not read for a NULL
+   `bodies`); otherwise the sensor's pose is the LOCAL transform of body `body`, composed with bodies->transforms[body] as a collider's is with its body's
+   (nudge.cpp:1165-1175): p_s = rotate(q_body, position) + p_body, q_s = q_body * rotation.  bodies->transforms is read as the stream has it at that point.
+   A mount with body >= bodies->count makes every ray of that sensor INVALID: all six words of origin and direction are the quiet NaN 0x7fc00000; max_t
+   and ignore_body are set as for any other ray.  The direction need not be unit length (t is in units of it): a beam of unit direction measures range in
+   world units, and a pinhole pattern with direction.z = 1 measures depth along the optical axis.
+   nh_sense_rays writes exactly these `count * beam_count` nh_Ray records (for a caller that wants the rays themselves, for nh_raycast_all or nh_raycast_k
+   on a sensor's rays, and for the tests).
+   nh_sense writes, for every i, into each non-NULL channel of `out` (a HOST struct of DEVICE pointers, each count * beam_count long or NULL) the
+   corresponding field of the nh_RayHit that nh_raycast writes for ray i under the same `flags` and the context's filter: t[i] = .t (max_t at a miss, NaN
+   at an invalid ray), body[i] = .body and tag[i] = .tag (0xffffffff at a miss), hits[i] = the whole record.  Everything else follows from that identity
+   and has no rules of its own: zero directions, origins inside a collider, NaN poses, `ignore_body`, the tie rule, NH_RAY_ANY_HIT (the same hit-or-miss;
+   a reported hit is a real one with t <= max_t), and the MASKED WORLD contract of the layer masks, where the query is the SENSOR: NH_FILTER_PER_QUERY
+   reads masks[s] for sensor s (`count` words), as nh_region reads masks[i] for region i.  A NULL channel costs nothing; a depth image is `t` alone.
+   THE TREE is that of the last nh_query_build / nh_query_refit, while a mounted sensor reads TODAY's body transforms: after a step, call nh_query_refit
+   first, or the sensors have moved and the world they see has not.
+   Both return NH_ERR_INVALID before any nh_query_build; for flags other than 0 or NH_RAY_ANY_HIT (nh_sense_rays: other than 0); for
+   count * beam_count >= 2^31; and, where count and beam_count are both non-zero, for `sensors`, `beams`, `rays` or out->hits null (hits: when given) or
+   not 16-byte aligned, out->t / out->body / out->tag not 4-byte aligned, `out` NULL or all four channels NULL, and `bodies` given with a NULL
+   bodies->transforms.  count == 0 or beam_count == 0 is a no-op that returns NH_OK: nothing is read.  A refused call writes nothing.
+   Never allocate, never wait: ONE launch each on the context's stream (timing labels q_sense, q_sense_rays).  OBSERVERS like nh_raycast (note 9): no view
+   export, no settling of deferred gravity, no still step turned into a full one, no change to nh_Counts.
+   HOW: the work item of a WAVE is (sensor, block of 64 consecutive beams).  The sensor's record, its mount and the pose composition are
+   read and done once per wave; the lanes read 64 adjacent beams, rotate them and walk the tree with nh_raycast's own per-ray body on a ray held in
+   registers; each requested channel leaves as one 4-byte store per lane.  The ORDER of the pattern decides which rays share a wave: beams that are
+   neighbours in direction should be neighbours in the pattern (an 8 x 8 image tile per 64 beams rather than a 64-pixel row: INTEGRATION.md, "sensors").
+   MEASURED (tools/sense_rates.py -> profiles/sense_rates.log; one MI355X, one run, the landed config-2 world of 1,004,524 colliders; sensors riding on
+   dynamic bodies; 16,777,216 rays a call; ms per call, the best of 5 blocks of 5 calls by device events; nh_sense writing t / t + body / full records,
+   then nh_sense_rays, then nh_raycast -- the yardstick -- on the records nh_sense_rays wrote):
+     4,096 cameras x 64 x 64 beams in 8 x 8 tiles     8.154 / 8.161 / 8.431     0.121     7.951
+     the same pattern in row-major order              9.006 / 9.040 / 9.401     0.121     8.842
+     256 lidars x 64 rings x 1,024 azimuths           2.809 / 2.816 / 2.957     0.114     2.831
+   So the WALK is the cost: nh_sense takes what nh_raycast takes on the same rays (0.98 - 1.01 of its rate), whichever channels it writes, and materialising
+   the rays costs 1.5 % on top.  What nh_sense saves is not time but the 1.07 GB of ray and hit records, the per-frame upload or the caller's own
+   ray kernel, and one launch.  Pattern order is worth 10 % (tiles against rows).  DESIGN 10.25 has the table and the grid that lost.
+   Not built: beams with a radius (sphere-cast sensors); different patterns within one call; per-beam time offsets (a rolling lidar); normals as a channel
+   of their own (they are in `hits`); noise models and images beyond depth / ids; all-hits or first-k forms of a sensor; packet or shared-stack traversal;
+   sensors on a partitioned world. */
+typedef struct nh_Beam { float direction[3]; float range; } nh_Beam;                               /* 16 B: sensor-local direction; max_t of its ray */
+typedef struct nh_Sensor { float position[3]; uint32_t body;                                        /* mount: a body index, or 0xffffffff = world frame */
+                           float rotation[4];
+                           uint32_t ignore_body; uint32_t reserved[3]; } nh_Sensor;                 /* 48 B; reserved is not read */
+typedef struct nh_SenseOut { float* t; uint32_t* body; uint32_t* tag; nh_RayHit* hits; } nh_SenseOut;   /* DEVICE pointers, each count * beam_count long or NULL */
+int nh_sense(nh_context* ctx, const nh_BodyData* bodies /* or NULL */, const nh_Sensor* sensors, uint32_t count, const nh_Beam* beams, uint32_t beam_count,
+             const nh_SenseOut* out, uint32_t flags /* 0 or NH_RAY_ANY_HIT */);
+int nh_sense_rays(nh_context* ctx, const nh_BodyData* bodies /* or NULL */, const nh_Sensor* sensors, uint32_t count, const nh_Beam* beams, uint32_t beam_count,
+                  nh_Ray* rays /* count * beam_count */, uint32_t flags /* 0 */);
 
 /* nh_overlap_wide and nh_penetration_wide: nh_overlap and nh_penetration for LARGE volumes -- an explosion radius, a large trigger volume, a client's area
    of interest, a vehicle-sized box.  nh_overlap gives one lane to a query, which is the right shape for a body-sized question and the wrong one for a

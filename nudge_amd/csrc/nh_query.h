@@ -1,7 +1,7 @@
 // nh_query.h -- per-item arithmetic of the scene query (nh_query_build / nh_raycast / nh_spherecast / nh_boxcast / nh_capsulecast / nh_overlap /
 // nh_closest / nh_distance, nh_query.hip): a collider's world pose, a ray against one box and against one sphere, the overlap predicates of a query sphere, box or
 // capsule against one collider, a swept ball, box and capsule against one box and one sphere, the signed distance of a point from one box and one
-// sphere, the per-plane test of nh_region, with the walk's node tests they are pruned by.
+// sphere, the per-plane test of nh_region, the ray of a (sensor, beam) of nh_sense, with the walk's node tests they are pruned by.
 //
 // Every function is `NH_HD` so that tests/hostquery (hostoverlap, hostsweep, hostboxcast, hostcapsule, hostpoint, hostregion) builds the SAME arithmetic with g++ -ffp-contract=off and gets the device's bits: the
 // brute force over all colliders there is the oracle of the GPU's tree traversal.  Only + - * /, sqrtf (correctly rounded on both sides)
@@ -1655,6 +1655,33 @@ NH_HD bool nh_q_ident_find(const uint32_t* hits, uint32_t lo, uint32_t hi, uint6
 		if (nh_q_ident(hits + 4u * (uint64_t)mid, by_body) < key) lo = mid + 1u; else hi = mid;
 	}
 	return lo < end && nh_q_ident(hits + 4u * (uint64_t)lo, by_body) == key;          // (every record read lies in [lo, end) of the call)
+}
+
+// ---- sensors (nh_sense, nh_sense_rays): the ray of beam j of sensor s ------------------------------------------------------------------------------
+// A sensor is a pose and a mount; a beam a sensor-local direction and a range.  The pose is the sensor's own (world frame: no mount), or the sensor's as
+// the LOCAL transform of the body it rides on -- nh_collider_pose, the arithmetic that puts a collider on its body.  A mount that does not exist makes the
+// pose a quiet NaN, and with it every ray of the sensor: "a ray with a non-finite origin or direction", a miss with t = NaN.
+// The ray is (origin = p, max_t = range, direction = rotate(q, beam direction), ignore_body): nh_Ray's eight words, which nh_sense_rays stores and
+// nh_sense casts from registers.  Only + - * here: the host oracle (tests/hostoracle/hostsense.cpp) gets the device's bits.
+// mounted: the call has bodies and the sensor's body word is not 0xffffffff; exists: false only for a mounted sensor whose body index is out of range.
+NH_HD nh_QPose nh_q_sensor_pose(nh_f3 sp, nh_quat sq, bool mounted, bool exists, nh_f3 bp, nh_quat bq) {
+	nh_QPose w;
+	w.p = sp; w.q = sq;
+	if (mounted && exists) nh_collider_pose(bq, bp, sq, sp, w.p, w.q);
+	if (mounted && !exists) {                    // (bp, bq are not read)
+		const float nan = nh_asfloat(0x7fc00000u);
+		w.p = nh_make3(nan, nan, nan); w.q = nh_quat{ nan, nan, nan, nan };
+	}
+	return w;
+}
+
+struct nh_QSensorRay { nh_f3 o; float max_t; nh_f3 d; uint32_t ignore; };
+// `exists` as above: the rotation of a NaN quaternion would be a NaN of the platform's making; the contract wants 0x7fc00000 in all six words
+NH_HD nh_QSensorRay nh_q_sensor_ray(nh_QPose w, bool exists, nh_f3 beam, float range, uint32_t ignore) {
+	nh_QSensorRay r;
+	r.o = w.p; r.max_t = range; r.ignore = ignore;
+	r.d = exists ? nh_rotate(w.q, beam) : w.p;
+	return r;
 }
 
 #endif

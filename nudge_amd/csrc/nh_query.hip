@@ -141,8 +141,10 @@ struct nh_QCastHead {
 struct nh_QRay : nh_QCastHead {
 	static constexpr uint32_t WORDS = 2u;
 	float r, w;
-	__device__ __forceinline__ void read(const float4* __restrict__ cp) {
-		head(cp[0], cp[1]);
+	__device__ __forceinline__ void read(const float4* __restrict__ cp) { set(cp[0], cp[1]); }
+	// the decode of the record's two 16-byte words, for k_q_sense as well, which builds each of its rays in registers
+	__device__ __forceinline__ void set(float4 c0, float4 c1) {
+		head(c0, c1);
 		r = 0.0f;
 		w = fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fabsf(o.z)) * 3.814697265625e-06f;
 	}
@@ -333,6 +335,92 @@ template <bool FILTER>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k_q_capsulecast(const nh_CapsuleCast* __restrict__ casts, uint32_t count, nh_RayHit* __restrict__ hits,
                                                    const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox, uint32_t any_hit, nh_QFilter F) {
 	nh_q_cast<nh_QCapsule, FILTER>(reinterpret_cast<const float4*>(casts), count, hits, nodes, rec, n, nbox, any_hit, F);
+}
+
+// ---- sensors ------------------------------------------------------------------------------------------------------------------------------------
+// nh_sense, nh_sense_rays: the work item of a WAVE is (sensor s, block of 64 consecutive beams), count * ceil(beam_count / 64) of them, one a wave up to
+// NH_Q_SENSE_GRID workgroups and dealt to the waves of that grid in turn beyond it.  s is the same in every lane by construction and is marked so (readfirstlane): the sensor's record, its mount's body transform and
+// the pose composition (nh_q_sensor_pose, nh_query.h) are fetched and done once per wave from one address, and every lane shares the origin, the ignored
+// body, the mask and the ray's pad.  The lanes read 64 adjacent nh_Beam (1 KB), rotate them (nh_q_sensor_ray) and -- k_q_sense -- answer the ray they hold
+// in registers through nh_q_cast_one, the body of k_q_raycast: so (t, collider, normal) are nh_raycast's for the nh_Ray record k_q_sense_rays stores,
+// under the same flags and the same mask (the sensor's index).  Each requested channel leaves as one 4-byte store per lane, adjacent across the wave; a
+// NULL channel costs no store.  Tail lanes (beam >= beam_count) do nothing.  No packets, no shared stack: the per-lane stackless walk on near-identical
+// rays already reads the same nodes in the same order.
+static_assert(sizeof(nh_Beam) == 16 && sizeof(nh_Sensor) == 48 && offsetof(nh_Sensor, body) == 12 && offsetof(nh_Sensor, rotation) == 16 && offsetof(nh_Sensor, ignore_body) == 32,
+              "nh_Beam is one 16-byte word, nh_Sensor three");
+// Workgroups of four waves: 262,144 wave items a pass, 16.7 M rays at 64 beams an item.  A grid of one wave per SIMD slot (2048 workgroups) that strides over
+// the items was measured first and lost: the stride is a multiple of the items of a sensor, so a wave takes the SAME block of the pattern of sensor after
+// sensor -- the waves that hold a camera's horizon tiles or a lidar's level rings walk long every time, the ones that look at the sky finish at once -- and
+// nh_sense took 1.4 x (pinhole) and 4.2 x (lidar) the time of nh_raycast on the same rays.  With an item a wave the hardware deals the work as it deals
+// nh_raycast's, and the two take the same time (profiles/sense_rates.log).  Larger batches stride.
+#define NH_Q_SENSE_GRID 65536u
+
+struct nh_QSensorHead { nh_QPose w; uint32_t ignore; bool exists; };
+__device__ __forceinline__ nh_QSensorHead nh_q_sensor_head(const nh_Sensor* __restrict__ sensors, uint32_t s, const nh_Transform* __restrict__ bodies, uint32_t body_count) {
+	const float4* sp = reinterpret_cast<const float4*>(sensors + s);
+	const float4 s0 = sp[0], s1 = sp[1];
+	nh_QSensorHead h;
+	h.ignore = __float_as_uint(sp[2].x);
+	const uint32_t body = __float_as_uint(s0.w);
+	const bool mounted = bodies != nullptr && body != NH_Q_NONE;
+	h.exists = !mounted || body < body_count;
+	nh_Transform b = {};
+	if (mounted && h.exists) b = bodies[body];
+	h.w = nh_q_sensor_pose(nh_make3(s0.x, s0.y, s0.z), nh_quat{ s1.x, s1.y, s1.z, s1.w }, mounted, h.exists, nh_make3(b.position[0], b.position[1], b.position[2]),
+	                       nh_quat{ b.rotation[0], b.rotation[1], b.rotation[2], b.rotation[3] });
+	return h;
+}
+
+// f(s, j, i, head) for every ray of the call whose wave item this wave is dealt: sensor s (wave-uniform), beam j, ray i = s * beam_count + j
+template <class F>
+__device__ __forceinline__ void nh_q_sense_items(const nh_Sensor* __restrict__ sensors, uint32_t count, uint32_t beam_count, const nh_Transform* __restrict__ bodies,
+                                                 uint32_t body_count, F f) {
+	const uint32_t lane = threadIdx.x & 63u, per = (beam_count + 63u) / 64u, items = count * per, waves = gridDim.x * (blockDim.x / 64u);
+	for (uint32_t item = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x / 64u) + threadIdx.x / 64u); item < items; item += waves) {
+		const uint32_t s = item / per, j = (item - s * per) * 64u + lane;
+		const nh_QSensorHead h = nh_q_sensor_head(sensors, s, bodies, body_count);
+		if (j < beam_count) f(s, j, (size_t)s * beam_count + j, h);
+	}
+}
+
+__device__ __forceinline__ nh_QSensorRay nh_q_sense_ray(const nh_Beam* __restrict__ beams, uint32_t j, const nh_QSensorHead& h) {
+	const float4 b = reinterpret_cast<const float4*>(beams)[j];
+	return nh_q_sensor_ray(h.w, h.exists, nh_make3(b.x, b.y, b.z), b.w, h.ignore);
+}
+
+template <bool FILTER>
+__global__ __launch_bounds__(256) void k_q_sense(const nh_Sensor* __restrict__ sensors, uint32_t count, const nh_Beam* __restrict__ beams, uint32_t beam_count,
+                                                 const nh_Transform* __restrict__ bodies, uint32_t body_count, nh_SenseOut out,
+                                                 const nh_QNode* __restrict__ nodes, const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox, uint32_t any_hit, nh_QFilter F) {
+	float* __restrict__ const out_t = out.t;
+	uint32_t* __restrict__ const out_body = out.body;
+	uint32_t* __restrict__ const out_tag = out.tag;
+	nh_RayHit* __restrict__ const out_hits = out.hits;
+	nh_q_sense_items(sensors, count, beam_count, bodies, body_count, [&](uint32_t s, uint32_t j, size_t i, const nh_QSensorHead& h) {
+		const nh_QSensorRay r = nh_q_sense_ray(beams, j, h);
+		nh_QRay k;
+		k.set(make_float4(r.o.x, r.o.y, r.o.z, r.max_t), make_float4(r.d.x, r.d.y, r.d.z, __uint_as_float(r.ignore)));
+		float bt;
+		uint32_t bc;
+		nh_f3 bn;
+		nh_q_cast_one<FILTER>(k, nodes, rec, n, nbox, any_hit, F, FILTER ? F.of(s) : 0u, bt, bc, bn);
+		if (out_t) out_t[i] = k.ok ? bt : __uint_as_float(0x7fc00000u);
+		uint32_t body = NH_Q_NONE, tag = NH_Q_NONE;
+		if ((out_body || out_tag) && bc != NH_Q_NONE) { body = __float_as_uint(rec[bc].a.w); tag = __float_as_uint(rec[bc].c.w); }      // (nh_q_identity's words)
+		if (out_body) out_body[i] = body;
+		if (out_tag) out_tag[i] = tag;
+		if (out_hits) nh_q_write_hit(out_hits + i, rec, nbox, k.ok, bc, bt, bn);
+	});
+}
+
+__global__ __launch_bounds__(256) void k_q_sense_rays(const nh_Sensor* __restrict__ sensors, uint32_t count, const nh_Beam* __restrict__ beams, uint32_t beam_count,
+                                                      const nh_Transform* __restrict__ bodies, uint32_t body_count, nh_Ray* __restrict__ rays) {
+	nh_q_sense_items(sensors, count, beam_count, bodies, body_count, [&](uint32_t, uint32_t j, size_t i, const nh_QSensorHead& h) {
+		const nh_QSensorRay r = nh_q_sense_ray(beams, j, h);
+		float4* rp = reinterpret_cast<float4*>(rays + i);
+		rp[0] = make_float4(r.o.x, r.o.y, r.o.z, r.max_t);
+		rp[1] = make_float4(r.d.x, r.d.y, r.d.z, __uint_as_float(r.ignore));
+	});
 }
 
 // ---- move -------------------------------------------------------------------------------------------------------------------------------------
@@ -1269,6 +1357,45 @@ extern "C" int nh_capsulecast(nh_context* ctx, const nh_CapsuleCast* casts, uint
 
 extern "C" int nh_boxcast(nh_context* ctx, const nh_BoxCast* casts, uint32_t count, nh_RayHit* hits, uint32_t flags) {
 	return nh_cast(ctx, "q_boxcast", k_q_boxcast<false>, k_q_boxcast<true>, casts, count, hits, flags);
+}
+
+// The two sensor calls: nh_raycast's checks in nh_raycast's order, then their own.  *rays = 0 where the call is a no-op (or refused): nothing is read then.
+static int nh_sense_args(nh_context* ctx, const nh_BodyData* bodies, const nh_Sensor* sensors, uint32_t count, const nh_Beam* beams, uint32_t beam_count,
+                         uint32_t flags, uint32_t flags_allowed, uint64_t* rays) {
+	*rays = 0u;
+	if (!ctx || !ctx->query || !ctx->query->built) return NH_ERR_INVALID;
+	if ((flags & ~flags_allowed) || (uint64_t)count * beam_count >= (1ull << 31)) return NH_ERR_INVALID;
+	if (count == 0u || beam_count == 0u) return NH_OK;
+	if (!sensors || !beams || (((uintptr_t)sensors | (uintptr_t)beams) & 15u)) return NH_ERR_INVALID;          // (records are moved as 16-byte words)
+	if (bodies && !bodies->transforms) return NH_ERR_INVALID;
+	NH_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+	*rays = (uint64_t)count * beam_count;
+	return NH_OK;
+}
+static uint32_t nh_sense_grid(uint32_t count, uint32_t beam_count) { return nh_grid_for((uint64_t)count * ((beam_count + 63u) / 64u), 4, NH_Q_SENSE_GRID); }
+
+extern "C" int nh_sense(nh_context* ctx, const nh_BodyData* bodies, const nh_Sensor* sensors, uint32_t count, const nh_Beam* beams, uint32_t beam_count,
+                        const nh_SenseOut* out, uint32_t flags) {
+	uint64_t rays;
+	{ const int rc = nh_sense_args(ctx, bodies, sensors, count, beams, beam_count, flags, NH_RAY_ANY_HIT, &rays); if (rc || !rays) return rc; }
+	if (!out || (!out->t && !out->body && !out->tag && !out->hits)) return NH_ERR_INVALID;
+	if ((((uintptr_t)out->t | (uintptr_t)out->body | (uintptr_t)out->tag) & 3u) || ((uintptr_t)out->hits & 15u)) return NH_ERR_INVALID;
+	nh_QueryState* q = ctx->query;
+	bool on;
+	const nh_QFilter F = nh_query_filter_of(q, &on);
+	NH_LAUNCH(ctx, "q_sense", on ? k_q_sense<true> : k_q_sense<false>, nh_sense_grid(count, beam_count), 256, sensors, count, beams, beam_count,
+	          bodies ? bodies->transforms : nullptr, bodies ? bodies->count : 0u, *out, q->nodes, q->rec, q->n, q->nbox, (flags & NH_RAY_ANY_HIT) ? 1u : 0u, F);
+	return NH_OK;
+}
+
+extern "C" int nh_sense_rays(nh_context* ctx, const nh_BodyData* bodies, const nh_Sensor* sensors, uint32_t count, const nh_Beam* beams, uint32_t beam_count,
+                             nh_Ray* rays, uint32_t flags) {
+	uint64_t total;
+	{ const int rc = nh_sense_args(ctx, bodies, sensors, count, beams, beam_count, flags, 0u, &total); if (rc || !total) return rc; }
+	if (!rays || ((uintptr_t)rays & 15u)) return NH_ERR_INVALID;
+	NH_LAUNCH(ctx, "q_sense_rays", k_q_sense_rays, nh_sense_grid(count, beam_count), 256, sensors, count, beams, beam_count,
+	          bodies ? bodies->transforms : nullptr, bodies ? bodies->count : 0u, rays);
+	return NH_OK;
 }
 
 // The four movers and their _touched forms: one record type, one result type and one kernel pair each.  One launch, nh_distance's checks in nh_distance's order; no

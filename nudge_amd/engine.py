@@ -50,6 +50,7 @@ EXPORTS = [
     "nh_overlap_bodies", "nh_overlap_events",
     "nh_overlap_wide", "nh_penetration_wide",
     "nh_contact_pairs", "nh_contact_events", "nh_step_contact_pairs",
+    "nh_sense", "nh_sense_rays",
 ]
 HALO_RECORD_BYTES = 64
 
@@ -239,6 +240,50 @@ def frustum_planes(m):
     return np.stack([m[3] + m[0], m[3] - m[0], m[3] + m[1], m[3] - m[1], m[3] + m[2], m[3] - m[2]]).astype(np.float32)
 
 
+# sensors (include/nudge_hip.h, "sensors"): one shared pattern of beams, one record per sensor
+BEAM = np.dtype([("direction", "<f4", 3), ("range", "<f4")])
+SENSOR = np.dtype([("position", "<f4", 3), ("body", "<u4"), ("rotation", "<f4", 4), ("ignore_body", "<u4"), ("reserved", "<u4", 3)])
+SENSE_CHANNELS = ("t", "body", "tag", "hits")
+
+
+class SenseOut(C.Structure):
+    """nh_SenseOut: a host struct of device pointers."""
+    _fields_ = [("t", C.c_void_p), ("body", C.c_void_p), ("tag", C.c_void_p), ("hits", C.c_void_p)]
+
+
+def pinhole_beams(width, height, fov_y, range, tile=8):
+    """The beams of a pinhole camera that looks down its local -z axis with +y up (the frustum of a perspective matrix): (beams, back).  Pixel (row,
+    column) looks through its centre; the direction has z = -1, so that t is DEPTH along the optical axis, and a hit farther than `range` of depth is a
+    miss.  The beams come in tile x tile blocks, row-major over the blocks and within one (a ragged edge keeps its smaller blocks), so that the 64 beams
+    a wave holds are an 8 x 8 patch of the image and not a 64-pixel row; `back` is the permutation to row-major: image = channel[..., back].reshape(height,
+    width).  tile = 1 is the row-major pattern (`back` the identity).  A table made in float64 and rounded once: no bits are promised."""
+    width, height, tile = int(width), int(height), max(int(tile), 1)
+    rows, cols = np.mgrid[0:height, 0:width]
+    order = np.lexsort((cols.ravel() % tile, rows.ravel() % tile, cols.ravel() // tile, rows.ravel() // tile))          # (last key first)
+    ty = np.tan(0.5 * float(fov_y))
+    tx = ty * width / height
+    beams = np.zeros(width * height, dtype=BEAM)
+    beams["direction"][:, 0] = ((cols.ravel()[order] + 0.5) / width * 2.0 - 1.0) * tx
+    beams["direction"][:, 1] = (1.0 - (rows.ravel()[order] + 0.5) / height * 2.0) * ty
+    beams["direction"][:, 2] = -1.0
+    beams["range"] = range
+    back = np.empty(width * height, dtype=np.int64)
+    back[order] = np.arange(width * height)
+    return beams, back
+
+
+def lidar_beams(azimuths, elevations, range):
+    """The beams of a spinning lidar whose axis is its local +y: one unit direction per (elevation, azimuth), angles in radians, azimuth from local -z
+    towards +x, ordered elevation-major -- a wave's 64 beams are neighbours in azimuth on one ring.  t is then the range along the beam in world
+    units.  (len(elevations) * len(azimuths)) records of BEAM; index = e * len(azimuths) + a."""
+    az, el = np.asarray(azimuths, dtype=np.float64).reshape(-1), np.asarray(elevations, dtype=np.float64).reshape(-1)
+    e, a = np.meshgrid(el, az, indexing="ij")
+    beams = np.zeros(e.size, dtype=BEAM)
+    beams["direction"] = np.stack([np.cos(e) * np.sin(a), np.sin(e), -np.cos(e) * np.cos(a)], axis=-1).reshape(-1, 3)
+    beams["range"] = range
+    return beams
+
+
 class OverlapQuery(C.Structure):
     _fields_ = [("center", C.c_float * 3), ("shape", C.c_uint32), ("rotation", C.c_float * 4), ("size", C.c_float * 3), ("ignore_body", C.c_uint32)]
 
@@ -408,6 +453,10 @@ def lib():
             L.nh_contact_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
             L.nh_contact_events.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
             L.nh_step_contact_pairs.argtypes = [C.c_void_p, C.POINTER(ContactData), C.POINTER(ContactCache), C.c_uint32, C.c_void_p, C.c_uint32]
+        # (likewise the sensors: World.sense_records / sense_rays_records / sense then raise AttributeError)
+        if hasattr(L, "nh_sense"):
+            L.nh_sense.argtypes = [C.c_void_p, C.POINTER(BodyData), C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(SenseOut), C.c_uint32]
+            L.nh_sense_rays.argtypes = [C.c_void_p, C.POINTER(BodyData), C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
         _LIB = L
     return _LIB
 
@@ -1525,6 +1574,92 @@ class World:
         qi[:, 32] = torch.as_tensor(P if plane_counts is None else plane_counts, dtype=torch.int32, device=self.dev)
         qi[:, 33] = self._ignore_bits(ignore_body)
         return self._list_dict(*self._overlap_lists(self.region_records, q, n, capacity, 16), synchronize)
+
+    # ---- sensors: depth / id images from poses and one shared beam pattern (include/nudge_hip.h, "sensors") ----
+    def _sense_counts(self, what, sensors, beams):
+        ns, nb = sensors.numel() * sensors.element_size(), beams.numel() * beams.element_size()
+        if ns % 48 or nb % 16:
+            raise ValueError(f"{what}: sensors hold {ns} bytes (48 a record), beams {nb} (16 a record)")
+        return ns // 48, nb // 16
+
+    def sense_records(self, sensors, beams, t=None, body=None, tag=None, hits=None, any_hit=False, mounted=True):
+        """nh_sense on records already laid out: `sensors` a contiguous device tensor of count x 48 bytes (nh_Sensor, engine.SENSOR), `beams` one of
+        beam_count x 16 bytes (nh_Beam, engine.BEAM), any dtype.  Each channel is None (not asked for, costs nothing), True (a new tensor) or a device
+        tensor of at least count * beam_count records to write into: t float32, body and tag int32 holding the uint32 bits, hits 32-byte nh_RayHit
+        records as uint8.  mounted=False passes no bodies: every sensor is in the world frame and its `body` word is not read.  Returns the dict of
+        the channels asked for.  Enqueued; nothing waits."""
+        torch = self.torch
+        count, beam_count = self._sense_counts("sense_records", sensors, beams)
+        n = count * beam_count
+        new = dict(t=lambda: torch.empty(n, dtype=torch.float32, device=self.dev), body=lambda: torch.empty(n, dtype=torch.int32, device=self.dev),
+                   tag=lambda: torch.empty(n, dtype=torch.int32, device=self.dev), hits=lambda: torch.empty((n, 32), dtype=torch.uint8, device=self.dev))
+        size = dict(t=4, body=4, tag=4, hits=32)
+        out = {}
+        for name, given in (("t", t), ("body", body), ("tag", tag), ("hits", hits)):
+            if given is None or given is False:
+                continue
+            out[name] = new[name]() if given is True else given
+            if out[name].numel() * out[name].element_size() < n * size[name]:
+                raise ValueError(f"sense_records: {name} holds {out[name].numel() * out[name].element_size()} bytes, {n} rays need {n * size[name]}")
+        so = SenseOut(*[out[k].data_ptr() if k in out and n else None for k in SENSE_CHANNELS])
+        rc = self.L.nh_sense(self.ctx, C.byref(self.bodies) if mounted else None, C.c_void_p(sensors.data_ptr() if n else 0), count,
+                             C.c_void_p(beams.data_ptr() if n else 0), beam_count, C.byref(so), NH_RAY_ANY_HIT if any_hit else 0)
+        _check(self.L, rc, "nh_sense")
+        return out
+
+    def sense_rays_records(self, sensors, beams, rays=None, mounted=True):
+        """nh_sense_rays: the nh_Ray record of every (sensor, beam) of sense_records' arguments, ray s * beam_count + j for beam j of sensor s.  Returns
+        the count * beam_count x 32-byte uint8 device tensor (`rays`, or a new one)."""
+        count, beam_count = self._sense_counts("sense_rays_records", sensors, beams)
+        n = count * beam_count
+        if rays is None:
+            rays = self.torch.empty((n, 32), dtype=self.torch.uint8, device=self.dev)
+        rc = self.L.nh_sense_rays(self.ctx, C.byref(self.bodies) if mounted else None, C.c_void_p(sensors.data_ptr() if n else 0), count,
+                                  C.c_void_p(beams.data_ptr() if n else 0), beam_count, C.c_void_p(rays.data_ptr() if n else 0), 0)
+        _check(self.L, rc, "nh_sense_rays")
+        return rays
+
+    def sense(self, positions, rotations, beams, bodies=None, ignore_body=None, channels=("t", "body"), any_hit=False, synchronize=False):
+        """Depth / id images of n sensors that share one pattern, against the last query_build() / query_refit().  `positions` (n, 3) and `rotations`
+        (n, 4; x, y, z, w) are the sensors' poses: in the world frame where `bodies` is None, else local to the body each rides on (`bodies`: a body
+        index or n of them; 0xffffffff = that sensor is in the world frame) -- call query_refit() after stepping, the mounts read today's transforms.
+        `beams`: engine.BEAM records (pinhole_beams, lidar_beams) or a (m, 4) array / tensor of (direction, range).  `ignore_body`: None, a body
+        index, or n of them (a lidar's own vehicle).  `channels`: any of "t", "body", "tag", "hits".  Returns a dict of (n, m) device tensors: t
+        (float32; the beam's range at a miss, NaN for an invalid ray), body and tag (int64; 0xffffffff = none), and for "hits" normal (n, m, 3),
+        collider, shape and `raw`, the (n, m, 32) nh_RayHit records.  Nothing waits for the device unless `synchronize`."""
+        torch = self.torch
+        unknown = set(channels) - set(SENSE_CHANNELS)
+        if unknown or not channels:
+            raise ValueError(f"sense: channels must be some of {SENSE_CHANNELS}, not {tuple(channels)}")
+        p = torch.as_tensor(positions, dtype=torch.float32, device=self.dev).reshape(-1, 3)
+        q = torch.as_tensor(rotations, dtype=torch.float32, device=self.dev).reshape(-1, 4)
+        n = p.shape[0]
+        if q.shape[0] != n:
+            raise ValueError(f"sense: {n} positions but {q.shape[0]} rotations")
+        if isinstance(beams, np.ndarray) and beams.dtype == BEAM:
+            beams = np.ascontiguousarray(beams).view(np.float32).reshape(-1, 4)
+        bt = torch.as_tensor(beams, dtype=torch.float32, device=self.dev).reshape(-1, 4).contiguous()
+        m = bt.shape[0]
+        rec = torch.zeros((n, 12), dtype=torch.float32, device=self.dev)
+        ri = rec.view(torch.int32)
+        rec[:, 0:3], rec[:, 4:8] = p, q
+        ri[:, 3] = self._ignore_bits(bodies)               # (None: 0xffffffff, the world frame)
+        ri[:, 8] = self._ignore_bits(ignore_body)
+        got = self.sense_records(rec, bt, any_hit=any_hit, mounted=bodies is not None, **{c: True for c in channels})
+        out = {}
+        if "t" in got:
+            out["t"] = got["t"].reshape(n, m)
+        for c in ("body", "tag"):
+            if c in got:
+                out[c] = (got[c].to(torch.int64) & 0xFFFFFFFF).reshape(n, m)
+        if "hits" in got:
+            raw = got["hits"]
+            f, u = raw.view(torch.float32).reshape(n, m, 8), raw.view(torch.int32).reshape(n, m, 8).to(torch.int64) & 0xFFFFFFFF
+            out.update(normal=f[:, :, 1:4], collider=u[:, :, 5], shape=u[:, :, 6], raw=raw.reshape(n, m, 32))
+            out.setdefault("t", f[:, :, 0]); out.setdefault("body", u[:, :, 4]); out.setdefault("tag", u[:, :, 7])
+        if synchronize:
+            torch.cuda.current_stream(self.dev).synchronize()
+        return out
 
     # ---- trigger events: what entered and what left each overlap volume (include/nudge_hip.h, "trigger events") ----
     def _hit_list(self, what, n, offsets, hits, capacity):
