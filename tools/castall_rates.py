@@ -11,110 +11,37 @@ the list call over nh_overlap's list call per record written.
     python tools/castall_rates.py [--steps 70] [--reps 10] [--repeats 5] [--out profiles/castall_rates.log]
     (on a GPU box; prints the table, one JSON line at the end, and writes both to --out)
 """
-import argparse
 import json
-import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import rates
 from nudge_amd import engine as E           # noqa: E402
-from nudge_amd import scenes as S           # noqa: E402
 
-NONE = 0xFFFFFFFF
+NONE = rates.NONE
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=70)
+    ap = rates.parser("castall_rates")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--rays", type=int, default=1 << 20)
     ap.add_argument("--only", default="", help="time only the workloads whose name contains this")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "castall_rates.log"))
     a = ap.parse_args()
     import torch
-    scene = S.grid_tiles(124, side=90, seed=2, lattice_cols=11)
-    nb = len(scene["body_transforms"])
-    C = len(scene["box_tags"]) + len(scene["sphere_tags"])
-    w = E.World(scene, flags=E.NH_FLAG_SINGLE_APPLY | E.NH_FLAG_FUSED_STEP, max_contacts=6 * nb)
-    w.step(a.steps)
-    w.synchronize()
-    w.query_build()
-    stream = torch.cuda.current_stream(w.dev)
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    lines = []
-
-    def say(s=""):
-        print(s, flush=True)
-        lines.append(s)
-
-    def timed(fn, reps):
-        ev0.record(stream)
-        for _ in range(reps):
-            fn()
-        ev1.record(stream)
-        ev1.synchronize()
-        return ev0.elapsed_time(ev1) / reps
-
-    def kernels(fn, reps):
-        w.enable_timing(True)
-        w.kernel_times(reset=True)
-        for _ in range(reps):
-            fn()
-        stream.synchronize()
-        kt = w.kernel_times(reset=True)
-        w.enable_timing(False)
-        return {k: v[0] / reps for k, v in kt.items()}
-
-    def med(v):
-        return dict(ms=float(np.median(v)), min=min(v), max=max(v))
-
-    # the ray sets of tools/query_rates.py (the same seed)
+    land = rates.landed(a)
+    w, C, n = land.world, land.colliders, a.rays
+    log = rates.Log()
     rng = np.random.default_rng(1)
-    n = a.rays
-    slab_p, slab_h = scene["box_transforms"]["position"][:124].astype(np.float64), scene["box_data"]["size"][:124].astype(np.float64)
-    lo, hi = (slab_p - slab_h).min(axis=0), (slab_p + slab_h).max(axis=0)
-    r = np.zeros(n, dtype=E.RAY)
-    r["max_t"] = np.inf
-    r["ignore_body"] = NONE
-    r["origin"] = rng.uniform(lo, hi + np.array([0, 60, 0]), size=(n, 3))
-    d = rng.normal(size=(n, 3))
-    r["direction"] = d / np.linalg.norm(d, axis=1, keepdims=True)
-    incoherent = r.copy()
-    side = 1024
-    gx, gz = np.meshgrid(np.linspace(lo[0], hi[0], side), np.linspace(lo[2], hi[2], n // side))
-    r["origin"][:, 0] = gx.reshape(-1)
-    r["origin"][:, 1] = 30.0
-    r["origin"][:, 2] = gz.reshape(-1)
-    r["direction"] = (0.0, -1.0, 0.0)
-    coherent = r.copy()
-
-    def casts(rays, radius):
-        c = np.zeros(len(rays), dtype=E.SPHERE_CAST)
-        for k in ("origin", "max_t", "direction", "ignore_body"):
-            c[k] = rays[k]
-        c["radius"] = radius
-        return c
+    incoherent, coherent = rates.ray_sets(rng, n, land.lo, land.hi)          # tools/query_rates.py's
 
     def shaped(rays, dtype, turned):
-        c = np.zeros(len(rays), dtype=dtype)
-        for k in ("origin", "max_t", "direction", "ignore_body"):
-            c[k] = rays[k]
-        c["rotation"] = (0.0, 0.0, 0.0, 1.0)
-        if turned:
-            qr = np.random.default_rng(2).normal(size=(len(rays), 4))
-            c["rotation"] = qr / np.linalg.norm(qr, axis=1, keepdims=True)
-        if dtype == E.BOX_CAST:
-            c["size"] = 0.75
-        else:
-            c["radius"], c["half_height"] = 0.5, 0.5
-        return c
+        size = dict(size=0.75) if dtype == E.BOX_CAST else dict(radius=0.5, half_height=0.5)
+        return rates.cast_records(rays, dtype, rotation=rates.random_rotations(len(rays)) if turned else None, **size)
 
     sets = {"rays, incoherent": incoherent, "rays, coherent grid": coherent,
-            "balls r=.75, incoherent": casts(incoherent, 0.75), "balls r=.75, coherent grid": casts(coherent, 0.75)}
+            "balls r=.75, incoherent": rates.cast_records(incoherent, E.SPHERE_CAST, radius=0.75),
+            "balls r=.75, coherent grid": rates.cast_records(coherent, E.SPHERE_CAST, radius=0.75)}
     for label, dtype in (("boxes h=.75", E.BOX_CAST), ("capsules r=.5 hh=.5", E.CAPSULE_CAST)):
         for turn, turned in (("identity", False), ("random rot", True)):
             sets[f"{label} {turn}, incoherent"] = shaped(incoherent, dtype, turned)
@@ -125,15 +52,10 @@ def main():
              E.BOX_CAST: (w.boxcast_all_records, w.boxcast_records), E.CAPSULE_CAST: (w.capsulecast_all_records, w.capsulecast_records)}
 
     # nh_overlap's usual 1 M sphere queries (tools/overlap_rates.py's first set), list mode
-    pos = w.get_bodies()["transforms"]["position"][1:].astype(np.float64)
-    q = np.zeros(n, dtype=E.OVERLAP_QUERY)
-    q["shape"], q["rotation"], q["ignore_body"] = E.NH_SHAPE_SPHERE, (0, 0, 0, 1), NONE
-    q["center"] = pos[rng.integers(0, len(pos), size=n)] + rng.normal(scale=0.25, size=(n, 3))
-    q["size"][:, 0] = 1.0
-    qt = torch.from_numpy(q.view(np.uint8).copy()).to(w.dev)
+    qt = rates.upload(w, rates.spheres_on_bodies(rng, n, land.positions))
     qo = torch.empty(n + 1, dtype=torch.int32, device=w.dev)
     w.overlap_records(qt, offsets=qo)
-    qtotal = int(qo[-1].item()) & NONE
+    qtotal = rates.total_of(qo)
     qh = torch.empty((max(qtotal, 1), 16), dtype=torch.uint8, device=w.dev)
     overlap = lambda: w.overlap_records(qt, offsets=qo, hits=qh, capacity=qtotal)              # noqa: E731
     overlap(); overlap()
@@ -141,60 +63,52 @@ def main():
     rows = {}
     for name, recs in sets.items():
         all_records, closest_records = calls[recs.dtype]
-        ct = torch.from_numpy(recs.view(np.uint8).copy()).to(w.dev)
+        ct = rates.upload(w, recs)
         ot = torch.empty(n + 1, dtype=torch.int32, device=w.dev)
         bt = torch.empty((n, 32), dtype=torch.uint8, device=w.dev)
         all_records(ct, offsets=ot)
         off = ot.to(torch.int64) & NONE
         total = int(off[-1].item())
         if total == NONE:
-            say(f"{name}: the total overflows 2^32 - 1; not timed")
+            log.say(f"{name}: the total overflows 2^32 - 1; not timed")
             continue
         longest = int((off[1:] - off[:-1]).max().item())
         ht = torch.empty((max(total, 1), 32), dtype=torch.uint8, device=w.dev)
         count = lambda: all_records(ct, offsets=ot)                                              # noqa: E731
         lst = lambda: all_records(ct, offsets=ot, hits=ht, capacity=total)                       # noqa: E731
         best = lambda: closest_records(ct, hits=bt)                                              # noqa: E731
-        for fn in (count, lst, best, overlap):                                                   # warm-up: the scratch grows here, not in a timed call
+        for fn in (count, lst, best, overlap):                                                   # warm-up in this order: the scratch grows here, not in a timed call
             fn(); fn()
-        stream.synchronize()
-        tc, tl, tb, to = [], [], [], []
-        for _ in range(a.repeats):
-            tb.append(timed(best, a.reps))
-            tc.append(timed(count, a.reps))
-            tl.append(timed(lst, a.reps))
-            to.append(timed(overlap, a.reps))
-        kl = kernels(lst, a.reps)
-        kb = kernels(best, a.reps)
+        t = rates.spreads(rates.interleaved(w, dict(best=best, count=count, list=lst, overlap=overlap), a.reps, a.repeats, warm=0))
+        kl = {k: v[0] / a.reps for k, v in rates.kernel_times(w, lst, a.reps).items()}
+        kb = {k: v[0] / a.reps for k, v in rates.kernel_times(w, best, a.reps).items()}
         walk = [v for k, v in kl.items() if k.endswith("_all_count")][0]
         closest_kernel = [v for k, v in kb.items() if k in ("q_raycast", "q_spherecast", "q_boxcast", "q_capsulecast")][0]
-        c, ls, b, o = med(tc), med(tl), med(tb), med(to)
+        c, ls, b, o = t["count"], t["list"], t["best"], t["overlap"]
         rows[name] = dict(casts=n, records=total, per_cast=total / n, longest=longest, closest=b, count_only=c, list_call=ls, count_plus_list_ms=c["ms"] + ls["ms"],
                           overlap_list=o, overlap_records=qtotal,
                           count_walk_over_closest_kernel=walk / closest_kernel, count_only_over_closest_call=c["ms"] / b["ms"],
                           list_per_record_over_overlap_per_record=(ls["ms"] / max(total, 1)) / (o["ms"] / max(qtotal, 1)),
                           kernels_list_call=kl, kernels_closest=kb)
 
-    say(f"landed config-2 world: {C:,} colliders, {nb:,} bodies, after {a.steps} steps; GPU {torch.cuda.get_device_name(w.dev)}")
-    say(f"median of {a.repeats} blocks of {a.reps} calls, interleaved (min .. max of the blocks); one box, one run")
-    say(f"nh_overlap, list mode, {n:,} sphere queries r=1: {qtotal:,} records")
-    say(f"{'workload':<48}{'records':>11}{'/cast':>7}{'longest':>8}{'closest hit ms':>24}{'all: count only ms':>24}{'all: list call ms':>24}{'nh_overlap list ms':>24}")
-    fmt = lambda v: f"{v['ms']:.3f} ({v['min']:.3f} .. {v['max']:.3f})"                       # noqa: E731
+    fmt = rates.fmt
+    log.say(f"landed {land.name} world: {C:,} colliders, {land.bodies:,} bodies, after {a.steps} steps; GPU {rates.gpu_name(w)}")
+    log.say(f"median of {a.repeats} blocks of {a.reps} calls, interleaved (min .. max of the blocks); one box, one run")
+    log.say(f"nh_overlap, list mode, {n:,} sphere queries r=1: {qtotal:,} records")
+    log.say(f"{'workload':<48}{'records':>11}{'/cast':>7}{'longest':>8}{'closest hit ms':>24}{'all: count only ms':>24}{'all: list call ms':>24}{'nh_overlap list ms':>24}")
     for k, v in rows.items():
-        say(f"{k:<48}{v['records']:11d}{v['per_cast']:7.2f}{v['longest']:8d}{fmt(v['closest']):>24}{fmt(v['count_only']):>24}{fmt(v['list_call']):>24}{fmt(v['overlap_list']):>24}")
-    say()
-    say("(the list call runs the count walk, the scan, the list walk, the ordering and the gather: count, read the total, list = the two columns added)")
-    say(f"{'workload':<48}{'count + list ms':>16}{'count walk / closest kernel':>29}{'count only / closest call':>27}{'list / overlap list, per record':>33}")
+        log.say(f"{k:<48}{v['records']:11d}{v['per_cast']:7.2f}{v['longest']:8d}{fmt(v['closest']):>24}{fmt(v['count_only']):>24}{fmt(v['list_call']):>24}{fmt(v['overlap_list']):>24}")
+    log.say()
+    log.say("(the list call runs the count walk, the scan, the list walk, the ordering and the gather: count, read the total, list = the two columns added)")
+    log.say(f"{'workload':<48}{'count + list ms':>16}{'count walk / closest kernel':>29}{'count only / closest call':>27}{'list / overlap list, per record':>33}")
     for k, v in rows.items():
-        say(f"{k:<48}{v['count_plus_list_ms']:16.3f}{v['count_walk_over_closest_kernel']:29.2f}{v['count_only_over_closest_call']:27.2f}{v['list_per_record_over_overlap_per_record']:33.2f}")
+        log.say(f"{k:<48}{v['count_plus_list_ms']:16.3f}{v['count_walk_over_closest_kernel']:29.2f}{v['count_only_over_closest_call']:27.2f}{v['list_per_record_over_overlap_per_record']:33.2f}")
     for k, v in rows.items():
-        say(f"\n{k}: the list call per kernel, ms per call (nh_kernel_times); closest hit: " + ", ".join(f"{kn} {t:.4f}" for kn, t in v["kernels_closest"].items()))
+        log.say(f"\n{k}: the list call per kernel, ms per call (nh_kernel_times); closest hit: " + ", ".join(f"{kn} {t:.4f}" for kn, t in v["kernels_closest"].items()))
         for kn, t in sorted(v["kernels_list_call"].items(), key=lambda kv: -kv[1]):
-            say(f"  {kn:<28}{t:9.4f}")
-    say(json.dumps(dict(colliders=C, steps=a.steps, workloads=rows)))
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
+            log.say(f"  {kn:<28}{t:9.4f}")
+    log.say(json.dumps(dict(colliders=C, steps=a.steps, workloads=rows)))
+    log.write(a.out)
     w.close()
 
 

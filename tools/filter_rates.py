@@ -15,111 +15,51 @@ timings of it per block: the spread repeated runs of one library show).
     [NUDGE_HIP_LIBRARY=.../libparent.so] python tools/filter_rates.py [--steps 70] [--reps 10] [--repeats 5] [--out profiles/filter_rates.log]
     (on a GPU box; prints the table, one JSON line at the end, and writes both to --out)
 """
-import argparse
 import json
 import os
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-OTHER = os.environ.pop("NUDGE_HIP_LIBRARY", None)          # (engine reads it on import: this process loads the tree's library first)
+import rates
+OTHER = rates.other_library()
 from nudge_amd import engine as E           # noqa: E402
-from nudge_amd import scenes as S           # noqa: E402
 
-NONE = 0xFFFFFFFF
+NONE = rates.NONE
 WAYS = ("off", "mask 3", "mask 1", "per query")
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=70)
+    ap = rates.parser("filter_rates")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--queries", type=int, default=1 << 20)
     ap.add_argument("--no-check", action="store_true", help="skip the brute-force spot check")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "filter_rates.log"))
     a = ap.parse_args()
     import torch
-    scene = S.grid_tiles(124, side=90, seed=2, lattice_cols=11)
-    nb = len(scene["body_transforms"])
-    C = len(scene["box_tags"]) + len(scene["sphere_tags"])
-
-    def world():
-        w = E.World(scene, flags=E.NH_FLAG_SINGLE_APPLY | E.NH_FLAG_FUSED_STEP, max_contacts=6 * nb)
-        w.step(a.steps)
-        w.synchronize()
-        w.query_build()
-        return w
-
-    w = world()
-    other = None
-    if OTHER:
-        E._LIB, E._LIB_PATH = None, os.path.abspath(OTHER)
-        other = world()
-        assert other.L is not w.L
-    stream = torch.cuda.current_stream(w.dev)
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    lines = []
-
-    def say(s=""):
-        print(s, flush=True)
-        lines.append(s)
-
-    def timed(fn, reps):
-        ev0.record(stream)
-        for _ in range(reps):
-            fn()
-        ev1.record(stream)
-        ev1.synchronize()
-        return ev0.elapsed_time(ev1) / reps
-
-    def med(v):
-        return dict(ms=float(np.median(v)), min=min(v), max=max(v))
+    land = rates.landed(a)
+    other = rates.landed(a, OTHER, like=land).world if OTHER else None
+    w, C, n, scene, lo, hi = land.world, land.colliders, a.queries, land.scene, land.lo, land.hi
+    up, log = rates.upload, rates.Log()
 
     def interleaved(fns):
-        for fn in fns.values():                                # warm-up: scratch grows here, not in a timed call
-            fn(); fn()
-        stream.synchronize()
-        times = {key: [] for key in fns}
-        for _ in range(a.repeats):
-            for key, fn in fns.items():
-                times[key].append(timed(fn, a.reps))
-        return {key: med(v) for key, v in times.items()}
+        return rates.spreads(rates.interleaved(w, fns, a.reps, a.repeats))
 
     # the incoherent rays of tools/query_rates.py (the same seed); the other calls take their origins
     rng = np.random.default_rng(1)
-    n = a.queries
-    slab_p, slab_h = scene["box_transforms"]["position"][:124].astype(np.float64), scene["box_data"]["size"][:124].astype(np.float64)
-    lo, hi = (slab_p - slab_h).min(axis=0), (slab_p + slab_h).max(axis=0)
-    rays = np.zeros(n, dtype=E.RAY)
-    rays["max_t"] = np.inf
-    rays["ignore_body"] = NONE
-    rays["origin"] = rng.uniform(lo, hi + np.array([0, 60, 0]), size=(n, 3))
-    d = rng.normal(size=(n, 3))
-    rays["direction"] = d / np.linalg.norm(d, axis=1, keepdims=True)
-    balls = np.zeros(n, dtype=E.SPHERE_CAST)
-    for k in ("origin", "max_t", "direction", "ignore_body"):
-        balls[k] = rays[k]
-    balls["radius"] = 0.75
+    rays, _ = rates.ray_sets(rng, n, lo, hi)
+    balls = rates.cast_records(rays, E.SPHERE_CAST, radius=0.75)
     near = rng.uniform(lo, hi + np.array([0, 6, 0]), size=(n, 3))          # where the bodies lie
-    overlaps = np.zeros(n, dtype=E.OVERLAP_QUERY)
-    overlaps["center"], overlaps["shape"], overlaps["ignore_body"] = near, E.NH_SHAPE_SPHERE, NONE
-    overlaps["size"][:, 0] = 1.0
-    overlaps["rotation"][:, 3] = 1.0
-    points = np.zeros(n, dtype=E.POINT_QUERY)
-    points["point"], points["max_distance"], points["ignore_body"] = rays["origin"], np.inf, NONE
+    overlaps = rates.overlap_queries(near, (1.0, 0.0, 0.0), E.NH_SHAPE_SPHERE)
+    points = rates.point_queries(rays["origin"], np.inf)
 
     words = np.where(np.concatenate([scene["box_transforms"]["body"], scene["sphere_transforms"]["body"]]) == 0, 1, 2).astype(np.uint32)
-    up = lambda arr, to: torch.from_numpy(np.ascontiguousarray(arr).view(np.uint8).copy()).to(to.dev)      # noqa: E731
-    box_layers, sphere_layers = up(words[:w.nbox], w).view(torch.int32), (up(words[w.nbox:], w).view(torch.int32) if w.nsph else None)
-    alternating = up(np.where(np.arange(n) % 2 == 0, 1, 2).astype(np.uint32), w).view(torch.int32)
+    box_layers, sphere_layers = up(w, words[:w.nbox]).view(torch.int32), (up(w, words[w.nbox:]).view(torch.int32) if w.nsph else None)
+    alternating = up(w, np.where(np.arange(n) % 2 == 0, 1, 2).astype(np.uint32)).view(torch.int32)
     filters = {"off": None, "mask 3": 3, "mask 1": 1, "per query": alternating}
 
     def calls(world):
-        rt, bt, ot_, pt = up(rays, world), up(balls, world), up(overlaps, world), up(points, world)
+        rt, bt, ot_, pt = up(world, rays), up(world, balls), up(world, overlaps), up(world, points)
         hits = torch.empty((n, 48), dtype=torch.uint8, device=world.dev)
         offsets = torch.empty(n + 1, dtype=torch.int32, device=world.dev)
         return {"nh_raycast": lambda: world.raycast_records(rt, hits=hits), "nh_spherecast r=.75": lambda: world.spherecast_records(bt, hits=hits),
@@ -157,15 +97,14 @@ def main():
         import filter_util as F
         import hostcast_util as CAST
         import hostpoint_util as HP
-        import hostquery_util as Q
-        rec = Q.records(w.get_bodies()["transforms"], scene)
+        rec = land.records
         pick = np.sort(np.random.default_rng(3).choice(n // 2, size=128, replace=False)) * 2
         pick = np.sort(np.concatenate([pick, pick + 1]))
         w.query_set_layers(box_layers, sphere_layers)
         for way, flt in filters.items():
             w.query_filter(flt)
-            got_r = np.frombuffer(w.raycast_records(up(rays, w)).cpu().numpy().tobytes(), dtype=E.RAY_HIT)[pick]
-            got_p = np.frombuffer(w.closest_records(up(points, w)).cpu().numpy().tobytes(), dtype=E.POINT_HIT)[pick]
+            got_r = rates.download(w.raycast_records(up(w, rays)), E.RAY_HIT)[pick]
+            got_p = rates.download(w.closest_records(up(w, points)), E.POINT_HIT)[pick]
             # the mask of every picked query (off: none -- the whole world)
             mvals = np.zeros(len(pick), np.uint32) if flt is None else np.full(len(pick), flt, np.uint32) if isinstance(flt, int) else np.where(pick % 2 == 0, 1, 2).astype(np.uint32)
             for m in np.unique(mvals):
@@ -184,31 +123,29 @@ def main():
             t = interleaved({"other (a)": theirs[name], "this": mine[name], "other (b)": theirs[name]})
             ab[name] = dict(t, this_over_other=t["this"]["ms"] / (0.5 * (t["other (a)"]["ms"] + t["other (b)"]["ms"])), other_over_itself=t["other (b)"]["ms"] / t["other (a)"]["ms"])
 
-    say(f"landed config-2 world: {C:,} colliders, {nb:,} bodies, after {a.steps} steps; GPU {torch.cuda.get_device_name(w.dev)}")
-    say(f"{n:,} incoherent queries per call; dynamic boxes in layer 2, body 0's colliders in layer 1; median of {a.repeats} blocks of {a.reps} calls, "
-        f"interleaved (min .. max of the blocks); one box, one run; {checked} records equal the brute force over the masked world byte for byte")
-    fmt = lambda v: f"{v['ms']:.3f} ({v['min']:.3f} .. {v['max']:.3f})"                       # noqa: E731
-    say()
-    say(f"{'call':<24}" + "".join(f"{way + ' ms':>28}" for way in WAYS) + "".join(f"{way + ' / off':>16}" for way in WAYS[1:]))
+    fmt = rates.fmt
+    log.say(f"landed {land.name} world: {C:,} colliders, {land.bodies:,} bodies, after {a.steps} steps; GPU {rates.gpu_name(w)}")
+    log.say(f"{n:,} incoherent queries per call; dynamic boxes in layer 2, body 0's colliders in layer 1; median of {a.repeats} blocks of {a.reps} calls, "
+            f"interleaved (min .. max of the blocks); one box, one run; {checked} records equal the brute force over the masked world byte for byte")
+    log.say()
+    log.say(f"{'call':<24}" + "".join(f"{way + ' ms':>28}" for way in WAYS) + "".join(f"{way + ' / off':>16}" for way in WAYS[1:]))
     for name, v in rows.items():
-        say(f"{name:<24}" + "".join(f"{fmt(v['ways'][way]):>28}" for way in WAYS) + "".join(f"{v['over_off'][way]:16.3f}" for way in WAYS[1:]))
-    say()
-    say("the layer pass, and the tree with and without layers (ms):")
+        log.say(f"{name:<24}" + "".join(f"{fmt(v['ways'][way]):>28}" for way in WAYS) + "".join(f"{v['over_off'][way]:16.3f}" for way in WAYS[1:]))
+    log.say()
+    log.say("the layer pass, and the tree with and without layers (ms):")
     for key, v in passes.items():
-        say(f"  {key:<22}{fmt(v):>28}")
-    say()
+        log.say(f"  {key:<22}{fmt(v):>28}")
+    log.say()
     if ab is None:
-        say("filter off, this library beside another build: no NUDGE_HIP_LIBRARY given, not measured")
+        log.say("filter off, this library beside another build: no NUDGE_HIP_LIBRARY given, not measured")
     else:
-        say(f"filter off, this library beside {os.path.basename(OTHER)} in the same process (ms):")
-        say(f"{'call':<24}{'other (a)':>28}{'this':>28}{'other (b)':>28}{'this / other':>14}{'other b / a':>14}")
+        log.say(f"filter off, this library beside {os.path.basename(OTHER)} in the same process (ms):")
+        log.say(f"{'call':<24}{'other (a)':>28}{'this':>28}{'other (b)':>28}{'this / other':>14}{'other b / a':>14}")
         for name, v in ab.items():
-            say(f"{name:<24}{fmt(v['other (a)']):>28}{fmt(v['this']):>28}{fmt(v['other (b)']):>28}{v['this_over_other']:14.3f}{v['other_over_itself']:14.3f}")
-    say()
-    say(json.dumps(dict(colliders=C, steps=a.steps, queries=n, calls=rows, passes=passes, off_beside_other=ab, checked=checked)))
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
+            log.say(f"{name:<24}{fmt(v['other (a)']):>28}{fmt(v['this']):>28}{fmt(v['other (b)']):>28}{v['this_over_other']:14.3f}{v['other_over_itself']:14.3f}")
+    log.say()
+    log.say(json.dumps(dict(colliders=C, steps=a.steps, queries=n, calls=rows, passes=passes, off_beside_other=ab, checked=checked)))
+    log.write(a.out)
     w.close()
     if other is not None:
         other.close()

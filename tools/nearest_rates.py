@@ -9,8 +9,6 @@ all colliders (tests/hostnearest_util.py).  Timed with device events.
     tools/build_variant.sh noseedk -DNH_Q_CLOSEST_K_NO_SEED       (here: hipcc cross-compiles)
     python tools/nearest_rates.py [--steps 70] [--reps 10]        (on a GPU box; prints the table, writes profiles/nearest_rates.log)
 """
-import argparse
-import io
 import json
 import os
 import subprocess
@@ -18,74 +16,37 @@ import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-NOSEED = os.path.join(ROOT, "nudge_amd", "_ab", "libnoseedk.so")
+import rates
+
+NOSEED = os.path.join(rates.ROOT, "nudge_amd", "_ab", "libnoseedk.so")
 KS = (1, 4, 8, 16, 32)
 
 
-def measure(steps, reps, n, full):
+def measure(a, full):
     """The figures of the library this process loaded (engine reads NUDGE_HIP_LIBRARY): one dict.  `full`: nh_closest, the overlap detour and the
     brute-force spot check as well (the seeded run); otherwise nh_closest_k's times and digests alone."""
     import torch
     from nudge_amd import engine as E
-    from nudge_amd import scenes as S
-    scene = S.grid_tiles(124, side=90, seed=2, lattice_cols=11)
-    nb = len(scene["body_transforms"])
-    w = E.World(scene, flags=E.NH_FLAG_SINGLE_APPLY | E.NH_FLAG_FUSED_STEP, max_contacts=6 * nb)
-    w.step(steps)
-    w.query_build()
-    w.synchronize()
-    stream = torch.cuda.current_stream(w.dev)
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-
-    def timed(fn):
-        fn()
-        stream.synchronize()
-        ev0.record(stream)
-        for _ in range(reps):
-            fn()
-        ev1.record(stream)
-        ev1.synchronize()
-        return ev0.elapsed_time(ev1) / reps
-
-    def upload(arr):
-        return torch.from_numpy(np.ascontiguousarray(arr).view(np.uint8).copy()).to(w.dev)
-
-    bt = w.get_bodies()["transforms"]
-    live = bt["position"].astype(np.float64)[1:]
-    slab_p, slab_h = scene["box_transforms"]["position"][:124].astype(np.float64), scene["box_data"]["size"][:124].astype(np.float64)
-    lo, hi = (slab_p - slab_h).min(axis=0), np.maximum((slab_p + slab_h).max(axis=0), live.max(axis=0))
-    rng = np.random.default_rng(5)
-    q = np.zeros(n, dtype=E.POINT_QUERY)
-    q["ignore_body"] = 0xFFFFFFFF
-    near = q.copy()
-    near["point"] = live[rng.integers(0, len(live), size=n)] + rng.normal(scale=0.5, size=(n, 3))
-    near["max_distance"] = 2.0
-    uni = q.copy()
-    uni["point"] = rng.uniform(lo, hi, size=(n, 3))
-    uni["max_distance"] = np.inf
-    above = q.copy()
-    above["point"] = rng.uniform(lo, hi, size=(n, 3))
-    above["point"][:, 1] = live[:, 1].max() + 20.0
-    above["max_distance"] = np.inf
-    sets = [("near bodies, max 2", near), ("uniform in bounds, inf", uni), ("20 m above the pile, inf", above)]
+    land = rates.landed(a)
+    w, n, reps = land.world, a.queries, a.reps
+    lo, hi = land.pile_bounds()
+    sets = [(name, rates.point_queries(points, md)) for name, points, md in rates.point_sets(np.random.default_rng(5), n, land.positions, lo, hi)]
+    near = sets[0][1]
     h1 = torch.empty((n, 48), dtype=torch.uint8, device=w.dev)
     hk = torch.empty((n * max(KS), 48), dtype=torch.uint8, device=w.dev)
     ck = torch.empty(n, dtype=torch.int32, device=w.dev)
     pick = np.linspace(0, n - 1, 86).astype(np.int64)
     rows, kth, checks = [], {}, {}
     for name, arr in sets:
-        t = upload(arr)
+        t = rates.upload(w, arr)
         row = dict(set=name, k={})
         if full:
-            row["closest_ms"] = timed(lambda: w.closest_records(t, hits=h1))
+            row["closest_ms"] = rates.block(w, lambda: w.closest_records(t, hits=h1), reps)
             single = h1.cpu().numpy().tobytes()
         for k in KS:
-            ms = timed(lambda: w.closest_k_records(t, k, counts=ck, hits=hk))
+            ms = rates.block(w, lambda: w.closest_k_records(t, k, counts=ck, hits=hk), reps)
             counts = ck.cpu().numpy().view(np.uint32)
-            hits = np.frombuffer(hk[: n * k].cpu().numpy().tobytes(), dtype=E.POINT_HIT).reshape(n, k)
+            hits = rates.download(hk[: n * k], E.POINT_HIT).reshape(n, k)
             row["k"][k] = dict(ms=ms, per_s=n / (ms * 1e-3), full=float((counts == k).mean()), mean=float(counts.mean()),
                                digest=int(np.frombuffer(hits.tobytes(), dtype=np.uint64).sum(dtype=np.uint64)) ^ int(counts.sum(dtype=np.uint64)))
             if full:
@@ -95,33 +56,27 @@ def measure(steps, reps, n, full):
                     kth[k] = float(np.median(hits[counts == k, k - 1]["distance"])) if (counts == k).any() else 2.0
                 checks.setdefault(k, []).append((arr[pick], counts[pick].copy(), hits[pick].copy()))
         rows.append(row)
-    out = dict(library=os.path.relpath(E._LIB_PATH, ROOT), gpu=torch.cuda.get_device_name(w.dev), colliders=len(scene["box_tags"]) + len(scene["sphere_tags"]),
-               bodies=nb, rows=rows)
+    out = dict(library=os.path.relpath(E._LIB_PATH, rates.ROOT), gpu=rates.gpu_name(w), colliders=land.colliders, bodies=land.bodies, rows=rows)
     if full:
         # the detour: count the colliders touching a ball of the k-th distance around each near-bodies point, read the total, list them
         detour = {}
         ot = torch.empty(n + 1, dtype=torch.int32, device=w.dev)
         for k in KS:
-            sp = np.zeros(n, dtype=E.OVERLAP_QUERY)
-            sp["center"] = near["point"]
-            sp["shape"] = E.NH_SHAPE_SPHERE
-            sp["size"][:, 0] = max(kth[k], 0.0)
-            sp["ignore_body"] = 0xFFFFFFFF
-            st = upload(sp)
-            count_ms = timed(lambda: w.overlap_records(st, offsets=ot))
-            total = int(ot[n].item()) & 0xFFFFFFFF
+            sp = rates.overlap_queries(near["point"], (max(kth[k], 0.0), 0.0, 0.0), E.NH_SHAPE_SPHERE, rotation=0.0)
+            st = rates.upload(w, sp)
+            count_ms = rates.block(w, lambda: w.overlap_records(st, offsets=ot), reps)
+            total = rates.total_of(ot)
             d = dict(radius=sp["size"][0, 0].item(), count_ms=count_ms, per_query=total / n)
             if 0 < total <= (1 << 26):
                 ht = torch.empty((total, 16), dtype=torch.uint8, device=w.dev)
-                w.overlap_records(st, offsets=ot, hits=ht, capacity=total)             # (grows the sort scratch once, outside the timing)
-                d["list_ms"] = timed(lambda: w.overlap_records(st, offsets=ot, hits=ht, capacity=total))
+                # (warm = 2: the first grows the sort scratch once, outside the timing)
+                d["list_ms"] = rates.block(w, lambda: w.overlap_records(st, offsets=ot, hits=ht, capacity=total), reps, warm=2)
                 del ht
             detour[k] = d
         out["detour"] = detour
         # the spot check: 3 x 86 queries per k against the brute force over every collider
         import hostnearest_util as N
-        import hostquery_util as Q
-        rec = Q.records(bt, scene)
+        rec = land.records
         checked = 0
         for k, parts in checks.items():
             for qs, counts, hits in parts:
@@ -134,56 +89,50 @@ def measure(steps, reps, n, full):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=70)
+    ap = rates.parser("nearest_rates")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--queries", type=int, default=1 << 20)
     ap.add_argument("--child", action="store_true", help="measure the library this process loads and print one JSON line")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "nearest_rates.log"))
     a = ap.parse_args()
     if a.child:
-        print(json.dumps(measure(a.steps, a.reps, a.queries, False)))
+        print(json.dumps(measure(a, False)))
         return
     if not os.path.exists(NOSEED):
         sys.exit(f"{NOSEED} is missing: tools/build_variant.sh noseedk -DNH_Q_CLOSEST_K_NO_SEED")
-    seeded = measure(a.steps, a.reps, a.queries, True)
+    seeded = measure(a, True)
     env = dict(os.environ, NUDGE_HIP_LIBRARY=NOSEED)
-    child = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--steps", str(a.steps), "--reps", str(a.reps), "--queries", str(a.queries)],
+    child = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--reps", str(a.reps), "--queries", str(a.queries)] + rates.world_flags(a),
                            env=env, capture_output=True, text=True, timeout=600)
     if child.returncode != 0:
         sys.exit(f"the unseeded run failed ({child.returncode}):\n{child.stderr[-2000:]}")
     plain = json.loads(child.stdout.strip().split("\n")[-1])
     n = a.queries
-    out = io.StringIO()
-    print(f"landed config-2 world: {seeded['colliders']:,} colliders, {seeded['bodies']:,} bodies, after {a.steps} steps; GPU {seeded['gpu']}; {n:,} queries per set",
-          file=out)
+    log = rates.Log()
+    log.say(f"landed {rates.world_name(a.tiles, a.world_side)} world: {seeded['colliders']:,} colliders, {seeded['bodies']:,} bodies, after {a.steps} steps; GPU {seeded['gpu']}; "
+            f"{n:,} queries per set")
     for s, u in zip(seeded["rows"], plain["rows"]):
-        print(f"{s['set']}: nh_closest {s['closest_ms']:.3f} ms ({n / s['closest_ms'] / 1e3:.1f} M q/s)", file=out)
-        print(f"{'  k':<6}{'seeded ms':>11}{'M q/s':>9}{'/nh_closest':>13}{'unseeded ms':>13}{'seed gain':>11}{'full lists':>12}{'mean held':>11}", file=out)
+        log.say(f"{s['set']}: nh_closest {s['closest_ms']:.3f} ms ({n / s['closest_ms'] / 1e3:.1f} M q/s)")
+        log.say(f"{'  k':<6}{'seeded ms':>11}{'M q/s':>9}{'/nh_closest':>13}{'unseeded ms':>13}{'seed gain':>11}{'full lists':>12}{'mean held':>11}")
         for k in KS:
             sk, uk = s["k"][k], u["k"][str(k)]              # (the child's keys came through JSON)
             assert sk["digest"] == uk["digest"], f"{s['set']}, k {k}: the seed changed the answer"
-            print(f"{k:>3}   {sk['ms']:11.3f}{sk['per_s'] / 1e6:9.1f}{sk['ms'] / s['closest_ms']:12.2f}x{uk['ms']:13.3f}{uk['ms'] / sk['ms']:10.2f}x"
-                  f"{100 * sk['full']:11.1f}%{sk['mean']:11.2f}", file=out)
-    print("the detour (near-bodies points): nh_overlap with a ball of the median k-th distance, count call + list call, beside nh_closest_k on that set", file=out)
-    print(f"{'  k':<6}{'radius':>9}{'listed/query':>14}{'count ms':>10}{'list ms':>10}{'both ms':>10}{'nh_closest_k ms':>17}{'detour/call':>13}", file=out)
+            log.say(f"{k:>3}   {sk['ms']:11.3f}{sk['per_s'] / 1e6:9.1f}{sk['ms'] / s['closest_ms']:12.2f}x{uk['ms']:13.3f}{uk['ms'] / sk['ms']:10.2f}x"
+                    f"{100 * sk['full']:11.1f}%{sk['mean']:11.2f}")
+    log.say("the detour (near-bodies points): nh_overlap with a ball of the median k-th distance, count call + list call, beside nh_closest_k on that set")
+    log.say(f"{'  k':<6}{'radius':>9}{'listed/query':>14}{'count ms':>10}{'list ms':>10}{'both ms':>10}{'nh_closest_k ms':>17}{'detour/call':>13}")
     for k in KS:
         d = seeded["detour"][k]
         sk = seeded["rows"][0]["k"][k]
         if "list_ms" in d:
             both = d["count_ms"] + d["list_ms"]
-            print(f"{k:>3}   {d['radius']:9.3f}{d['per_query']:14.2f}{d['count_ms']:10.3f}{d['list_ms']:10.3f}{both:10.3f}{sk['ms']:17.3f}{both / sk['ms']:12.2f}x", file=out)
+            log.say(f"{k:>3}   {d['radius']:9.3f}{d['per_query']:14.2f}{d['count_ms']:10.3f}{d['list_ms']:10.3f}{both:10.3f}{sk['ms']:17.3f}{both / sk['ms']:12.2f}x")
         else:
-            print(f"{k:>3}   {d['radius']:9.3f}{d['per_query']:14.2f}{d['count_ms']:10.3f}{'-':>10}{'-':>10}{sk['ms']:17.3f}{'-':>13}", file=out)
-    print("(the detour still owes the distances and the order: its records are unordered collider identities)", file=out)
-    print(f"(k = 1 equals nh_closest's bytes in every set; the seeded and unseeded records are identical: equal digests; {seeded['checked']} queries equal the "
-          f"brute force over all colliders byte for byte)", file=out)
-    print(json.dumps(dict(queries=n, seeded=seeded, unseeded=plain)), file=out)
-    text = out.getvalue()
-    print(text, end="")
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write(text)
+            log.say(f"{k:>3}   {d['radius']:9.3f}{d['per_query']:14.2f}{d['count_ms']:10.3f}{'-':>10}{'-':>10}{sk['ms']:17.3f}{'-':>13}")
+    log.say("(the detour still owes the distances and the order: its records are unordered collider identities)")
+    log.say(f"(k = 1 equals nh_closest's bytes in every set; the seeded and unseeded records are identical: equal digests; {seeded['checked']} queries equal the "
+            f"brute force over all colliders byte for byte)")
+    log.say(json.dumps(dict(queries=n, seeded=seeded, unseeded=plain)))
+    log.write(a.out)
 
 
 if __name__ == "__main__":

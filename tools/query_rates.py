@@ -4,19 +4,15 @@ downward grid, any-hit), timed with device events; per kernel the bytes moved ov
 
     python tools/query_rates.py [--steps 70] [--reps 10]        (on a GPU box; prints the table, one JSON line at the end)
 """
-import argparse
 import json
-import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import rates
 from nudge_amd import engine as E           # noqa: E402
-from nudge_amd import scenes as S           # noqa: E402
 
 HBM = 8.0e12
+
 
 # bytes each kernel moves at C colliders (n rays), read + write, counting every record once (caches not modelled)
 #   q_xform: collider transform 32 + body transform 32 + shape 16 + tag 4 in; record 48 out
@@ -40,75 +36,38 @@ def byte_model(C, n_rays):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=70)
+    ap = rates.parser("query_rates")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--rays", type=int, default=1 << 20)
     a = ap.parse_args()
     import torch
-    scene = S.grid_tiles(124, side=90, seed=2, lattice_cols=11)
-    nb = len(scene["body_transforms"])
-    C = len(scene["box_tags"]) + len(scene["sphere_tags"])
-    w = E.World(scene, flags=E.NH_FLAG_SINGLE_APPLY | E.NH_FLAG_FUSED_STEP, max_contacts=6 * nb)
-    w.step(a.steps)
-    w.synchronize()
-    stream = torch.cuda.current_stream(w.dev)
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-
-    def timed(fn, reps):
-        fn()
-        stream.synchronize()
-        ev0.record(stream)
-        for _ in range(reps):
-            fn()
-        ev1.record(stream)
-        ev1.synchronize()
-        return ev0.elapsed_time(ev1) / reps
-
+    land = rates.landed(a, build=False)
+    w, C, n = land.world, land.colliders, a.rays
     # the step, for scale: the landed world's still step and a full step (option no_still on a second world would double the memory: a kernel-time
     # sum of the steps is what DESIGN quotes; here the event time of 10 nh_step sub-steps)
-    step_ms = timed(lambda: w.step(1), 20)
-    build_ms = timed(w.query_build, a.reps)
-    w.enable_timing(True)
-    w.kernel_times(reset=True)
-    for _ in range(a.reps):
-        w.query_build()
-    w.synchronize()
-    kt = w.kernel_times(reset=True)
-    w.enable_timing(False)
+    step_ms = rates.block(w, lambda: w.step(1), 20)
+    build_ms = rates.block(w, w.query_build, a.reps)
+    kt = rates.kernel_times(w, w.query_build, a.reps)
 
-    rng = np.random.default_rng(1)
-    n = a.rays
-    slab_p, slab_h = scene["box_transforms"]["position"][:124].astype(np.float64), scene["box_data"]["size"][:124].astype(np.float64)
-    lo, hi = (slab_p - slab_h).min(axis=0), (slab_p + slab_h).max(axis=0)
-    sets = {}
-    r = np.zeros(n, dtype=E.RAY)
-    r["max_t"] = np.inf; r["ignore_body"] = 0xFFFFFFFF
-    r["origin"] = rng.uniform(lo, hi + np.array([0, 60, 0]), size=(n, 3))
-    d = rng.normal(size=(n, 3)); r["direction"] = d / np.linalg.norm(d, axis=1, keepdims=True)
-    sets["incoherent"] = r.copy()
-    side = 1024
-    gx, gz = np.meshgrid(np.linspace(lo[0], hi[0], side), np.linspace(lo[2], hi[2], n // side))
-    r["origin"][:, 0] = gx.reshape(-1); r["origin"][:, 1] = 30.0; r["origin"][:, 2] = gz.reshape(-1)
-    r["direction"] = (0.0, -1.0, 0.0)
-    sets["coherent"] = r.copy()
+    sets = dict(zip(("incoherent", "coherent"), rates.ray_sets(np.random.default_rng(1), n, land.lo, land.hi)))
     rows = {}
     for name, rays in sets.items():
-        t = torch.from_numpy(rays.view(np.uint8).copy()).to(w.dev)
+        t = rates.upload(w, rays)
         h = torch.empty((n, 32), dtype=torch.uint8, device=w.dev)
         for any_hit in (False, True):
             if name == "coherent" and any_hit:
                 continue
-            ms = timed(lambda: w.raycast_records(t, any_hit=any_hit, hits=h), a.reps)
-            hits = np.frombuffer(h.cpu().numpy().tobytes(), dtype=E.RAY_HIT)
+            ms = rates.block(w, lambda: w.raycast_records(t, any_hit=any_hit, hits=h), a.reps)
+            hits = rates.download(h, E.RAY_HIT)
             key = name + (" any-hit" if any_hit else "")
-            rows[key] = dict(ms=ms, rays_per_s=n / (ms * 1e-3), hit_share=float((hits["shape"] != 0xFFFFFFFF).mean()))
+            rows[key] = dict(ms=ms, rays_per_s=n / (ms * 1e-3), hit_share=float((hits["shape"] != rates.NONE).mean()))
 
     model = byte_model(C, n)
-    print(f"landed config-2 world: {C:,} colliders, {nb:,} bodies, after {a.steps} steps; GPU {torch.cuda.get_device_name(w.dev)}")
-    print(f"step (nh_step, 1 sub-step, event time): {step_ms:.3f} ms")
-    print(f"nh_query_build (event time, mean of {a.reps}): {build_ms:.3f} ms = {build_ms / step_ms:.2f} steps")
-    print(f"{'kernel':<16}{'ms/build':>10}{'launches':>10}{'MB':>10}{'% of 8 TB/s':>13}")
+    log = rates.Log()
+    log.say(f"landed {land.name} world: {C:,} colliders, {land.bodies:,} bodies, after {a.steps} steps; GPU {rates.gpu_name(w)}")
+    log.say(f"step (nh_step, 1 sub-step, event time): {step_ms:.3f} ms")
+    log.say(f"nh_query_build (event time, mean of {a.reps}): {build_ms:.3f} ms = {build_ms / step_ms:.2f} steps")
+    log.say(f"{'kernel':<16}{'ms/build':>10}{'launches':>10}{'MB':>10}{'% of 8 TB/s':>13}")
     sort_ms = 0.0
     for k, (ms, launches) in sorted(kt.items(), key=lambda kv: -kv[1][0]):
         per = ms / a.reps
@@ -116,13 +75,14 @@ def main():
             sort_ms += per
         b = model.get(k)
         share = f"{100.0 * b / (per * 1e-3) / HBM:12.1f}" if b and per > 0 else f"{'':>12}"
-        print(f"{k:<16}{per:10.4f}{launches // a.reps:10d}{(b or 0) / 1e6:10.1f} {share}")
-    print(f"  sort (radix_*) {sort_ms:.4f} ms of the build")
-    print(f"{'ray set':<22}{'ms':>9}{'M rays/s':>11}{'hits':>7}{'% of 8 TB/s (64 B/ray)':>25}")
+        log.say(f"{k:<16}{per:10.4f}{launches // a.reps:10d}{(b or 0) / 1e6:10.1f} {share}")
+    log.say(f"  sort (radix_*) {sort_ms:.4f} ms of the build")
+    log.say(f"{'ray set':<22}{'ms':>9}{'M rays/s':>11}{'hits':>7}{'% of 8 TB/s (64 B/ray)':>25}")
     for k, v in rows.items():
-        print(f"{k:<22}{v['ms']:9.3f}{v['rays_per_s'] / 1e6:11.1f}{100 * v['hit_share']:6.1f}%{100.0 * model['q_raycast'] / (v['ms'] * 1e-3) / HBM:24.2f}")
-    print(json.dumps(dict(colliders=C, step_ms=step_ms, build_ms=build_ms, kernels={k: v[0] / a.reps for k, v in kt.items()}, sort_ms=sort_ms,
-                          rays=n, casts=rows)))
+        log.say(f"{k:<22}{v['ms']:9.3f}{v['rays_per_s'] / 1e6:11.1f}{100 * v['hit_share']:6.1f}%{100.0 * model['q_raycast'] / (v['ms'] * 1e-3) / HBM:24.2f}")
+    log.say(json.dumps(dict(colliders=C, step_ms=step_ms, build_ms=build_ms, kernels={k: v[0] / a.reps for k, v in kt.items()}, sort_ms=sort_ms,
+                            rays=n, casts=rows)))
+    log.write(a.out)
     w.close()
 
 

@@ -13,8 +13,6 @@ stepped alike, with 2048 records of each compared byte for byte.
     tools/build_variant.sh parent "" <parent rev>                (where the tree is a git repository; hipcc cross-compiles)
     python tools/refit_rates.py [--steps 70] [--reps 10]          (on a GPU box; prints the tables, writes profiles/refit_rates.log)
 """
-import argparse
-import io
 import json
 import os
 import subprocess
@@ -22,9 +20,9 @@ import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-PARENT = os.path.join(ROOT, "nudge_amd", "_ab", "libparent.so")
+import rates
+
+PARENT = os.path.join(rates.ROOT, "nudge_amd", "_ab", "libparent.so")
 HBM = 8.0e12
 DECAY_AT = (1, 10, 30, 70)
 
@@ -39,74 +37,32 @@ def byte_model(C, top):
             "q_xform": C * (32 + 32 + 16 + 4 + 48), "q_keys": C * (16 + 8 + 4), "q_tree": (C - 1) * (4 * 8 + 28)}
 
 
-def _world(steps):
+def measure_ab(a):
+    """The figures of the library this process loaded: one dict.  Every repetition's device-event time apart (blocks of one call after a warm-up)."""
     from nudge_amd import engine as E
-    from nudge_amd import scenes as S
-    scene = S.grid_tiles(124, side=90, seed=2, lattice_cols=11)
-    nb = len(scene["body_transforms"])
-    w = E.World(scene, flags=E.NH_FLAG_SINGLE_APPLY | E.NH_FLAG_FUSED_STEP, max_contacts=6 * nb)
-    if steps:
-        w.step(steps)
-    w.synchronize()
-    return scene, w
-
-
-def _timers(w, torch):
-    stream = torch.cuda.current_stream(w.dev)
-
-    def each(fn, reps, inner=1):
-        """Device-event time of `reps` repetitions of fn (each `inner` calls), one by one, after a warm-up: a list of ms per call."""
-        fn()
-        stream.synchronize()
-        out = []
-        for _ in range(reps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(stream)
-            for _ in range(inner):
-                fn()
-            e1.record(stream)
-            e1.synchronize()
-            out.append(e0.elapsed_time(e1) / inner)
-        return out
-    return each
-
-
-def measure_ab(steps, reps):
-    """The figures of the library this process loaded: one dict."""
-    import torch
-    from nudge_amd import engine as E
-    scene, w = _world(steps)
-    each = _timers(w, torch)
+    land = rates.landed(a, build=False)
+    w, reps = land.world, a.reps
     has_refit = hasattr(w.L, "nh_query_refit")
-    out = dict(library=os.path.relpath(E._LIB_PATH, ROOT), gpu=torch.cuda.get_device_name(w.dev), colliders=len(scene["box_tags"]) + len(scene["sphere_tags"]),
-               bodies=len(scene["body_transforms"]), has_refit=has_refit)
-    out["build_ms"] = each(w.query_build, reps)
+    out = dict(library=os.path.relpath(E._LIB_PATH, rates.ROOT), gpu=rates.gpu_name(w), colliders=land.colliders, bodies=land.bodies, has_refit=has_refit)
+    out["build_ms"] = rates.blocks(w, w.query_build, reps, 1)
     if has_refit:
-        out["refit_ms"] = each(w.query_refit, reps)
+        out["refit_ms"] = rates.blocks(w, w.query_refit, reps, 1)
         out["stats"] = w.query_stats()
 
     def kernels(fn):
-        w.enable_timing(True)
-        w.kernel_times(reset=True)
-        for _ in range(reps):
-            fn()
-        w.synchronize()
-        kt = w.kernel_times(reset=True)
-        w.enable_timing(False)
-        return {k: (v[0] / reps, v[1] // reps) for k, v in kt.items()}
+        return {k: (v[0] / reps, v[1] // reps) for k, v in rates.kernel_times(w, fn, reps).items()}
     out["build_kernels"] = kernels(w.query_build)
     if has_refit:
         out["refit_kernels"] = kernels(w.query_refit)
     # the steps of this run, for scale: one nh_step call of one sub-step; the landed world's step inside a longer call (still steps, as the counters
     # say); the same with the still path switched off (full steps)
-    out["step1_ms"] = each(lambda: w.step(1), reps)
+    out["step1_ms"] = rates.blocks(w, lambda: w.step(1), reps, 1)
     c0 = w.counts()
-    out["still_ms"] = each(lambda: w.step(10), reps)
-    out["still_ms"] = [t / 10 for t in out["still_ms"]]
+    out["still_ms"] = [t / 10 for t in rates.blocks(w, lambda: w.step(10), reps, 1)]
     c1 = w.counts()
     out["still_share"] = (c1["still_steps"] - c0["still_steps"]) / float(10 * (reps + 1))
     w.set_option("no_still", 1)
-    out["full_ms"] = [t / 10 for t in each(lambda: w.step(10), reps)]
+    out["full_ms"] = [t / 10 for t in rates.blocks(w, lambda: w.step(10), reps, 1)]
     c2 = w.counts()
     out["full_still_share"] = (c2["still_steps"] - c1["still_steps"]) / float(10 * (reps + 1))
     out["error"] = c2["error"]
@@ -114,56 +70,43 @@ def measure_ab(steps, reps):
     return out
 
 
-def measure_decay(reps, n):
+def measure_decay(a):
     import torch
     from nudge_amd import engine as E
-    scene, a = _world(0)
-    _, b = _world(0)
-    each = _timers(a, torch)
-    slab_p, slab_h = scene["box_transforms"]["position"][:124].astype(np.float64), scene["box_data"]["size"][:124].astype(np.float64)
-    lo, hi = (slab_p - slab_h).min(axis=0), (slab_p + slab_h).max(axis=0)
-    rng = np.random.default_rng(1)
-    rays = np.zeros(n, dtype=E.RAY)
-    rays["max_t"] = np.inf
-    rays["ignore_body"] = 0xFFFFFFFF
-    rays["origin"] = rng.uniform(lo, hi + np.array([0, 60, 0]), size=(n, 3))
-    d = rng.normal(size=(n, 3))
-    rays["direction"] = d / np.linalg.norm(d, axis=1, keepdims=True)
+    land = rates.landed(a, build=False, steps=0)
+    refit, fresh = land.world, rates.landed(a, build=False, steps=0, like=land).world
+    n, reps, lo, hi = a.queries, a.reps, land.lo, land.hi
+    rays, _ = rates.ray_sets(np.random.default_rng(1), n, lo, hi)          # tools/query_rates.py's incoherent rays
     pick = torch.from_numpy(np.linspace(0, n - 1, 2048).astype(np.int64))
     rows = []
-    a.query_build()
+    refit.query_build()
     done = 0
     for at in DECAY_AT:
         while done < at:
-            a.step(1)
-            a.query_refit()
-            b.step(1)
+            refit.step(1)
+            refit.query_refit()
+            fresh.step(1)
             done += 1
-        b.query_build()
-        a.synchronize(); b.synchronize()
-        live = a.get_bodies()["transforms"]["position"][1:].astype(np.float64)
-        phi = np.maximum(hi, live.max(axis=0))
-        q = np.zeros(n, dtype=E.POINT_QUERY)
-        q["ignore_body"] = 0xFFFFFFFF
-        q["point"] = np.random.default_rng(5).uniform(lo, phi, size=(n, 3))
-        q["max_distance"] = np.inf
+        fresh.query_build()
+        refit.synchronize(); fresh.synchronize()
+        live = refit.get_bodies()["transforms"]["position"][1:].astype(np.float64)
+        q = rates.point_queries(np.random.default_rng(5).uniform(lo, np.maximum(hi, live.max(axis=0)), size=(n, 3)), np.inf)
         row = dict(step=at)
-        for w, side in ((a, "refit"), (b, "fresh")):
-            rt = torch.from_numpy(rays.view(np.uint8).copy()).to(w.dev)
-            qt = torch.from_numpy(q.view(np.uint8).copy()).to(w.dev)
+        for w, side in ((refit, "refit"), (fresh, "fresh")):
+            rt, qt = rates.upload(w, rays), rates.upload(w, q)
             rh = torch.empty((n, 32), dtype=torch.uint8, device=w.dev)
             qh = torch.empty((n, 48), dtype=torch.uint8, device=w.dev)
-            row[f"rays_{side}_ms"] = float(np.mean(each(lambda: w.raycast_records(rt, hits=rh), reps)))
-            row[f"closest_{side}_ms"] = float(np.mean(each(lambda: w.closest_records(qt, hits=qh), reps)))
+            row[f"rays_{side}_ms"] = float(np.mean(rates.blocks(w, lambda: w.raycast_records(rt, hits=rh), reps, 1)))
+            row[f"closest_{side}_ms"] = float(np.mean(rates.blocks(w, lambda: w.closest_records(qt, hits=qh), reps, 1)))
             row[f"rays_{side}"] = rh.cpu()[pick].numpy().tobytes().hex()
             row[f"closest_{side}"] = qh.cpu()[pick].numpy().tobytes().hex()
-            row[f"hit_share_{side}"] = float((np.frombuffer(rh.cpu().numpy().tobytes(), dtype=E.RAY_HIT)["shape"] != 0xFFFFFFFF).mean())
+            row[f"hit_share_{side}"] = float((rates.download(rh, E.RAY_HIT)["shape"] != rates.NONE).mean())
         same = [row.pop(f"{k}_refit") == row.pop(f"{k}_fresh") for k in ("rays", "closest")]
         row["same_bytes"] = all(same)
-        row["refit_ms"] = float(np.mean(each(a.query_refit, reps)))
+        row["refit_ms"] = float(np.mean(rates.blocks(refit, refit.query_refit, reps, 1)))
         rows.append(row)
-    out = dict(rows=rows, error=a.counts()["error"] | b.counts()["error"])
-    a.close(); b.close()
+    out = dict(rows=rows, error=refit.counts()["error"] | fresh.counts()["error"])
+    refit.close(); fresh.close()
     return out
 
 
@@ -172,7 +115,7 @@ def _child(mode, library, a, limit):
     env.pop("NUDGE_HIP_LIBRARY", None)
     if library:
         env["NUDGE_HIP_LIBRARY"] = library
-    child = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", mode, "--steps", str(a.steps), "--reps", str(a.reps), "--queries", str(a.queries)],
+    child = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", mode, "--reps", str(a.reps), "--queries", str(a.queries)] + rates.world_flags(a),
                            env=env, capture_output=True, text=True, timeout=limit)
     if child.returncode != 0:
         sys.exit(f"the {mode} child of {library or 'the library'} failed ({child.returncode}); nothing more is started:\n{child.stderr[-3000:]}")
@@ -185,18 +128,16 @@ def _span(v):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=70)
+    ap = rates.parser("refit_rates")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--queries", type=int, default=1 << 20)
     ap.add_argument("--child", choices=("ab", "decay"), help="measure with the library this process loads and print one JSON line")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "refit_rates.log"))
     a = ap.parse_args()
     if a.child == "ab":
-        print(json.dumps(measure_ab(a.steps, a.reps)))
+        print(json.dumps(measure_ab(a)))
         return
     if a.child == "decay":
-        print(json.dumps(measure_decay(a.reps, a.queries)))
+        print(json.dumps(measure_decay(a)))
         return
     if not os.path.exists(PARENT):
         sys.exit(f"{PARENT} is missing: tools/build_variant.sh parent \"\" <parent rev>")
@@ -206,55 +147,50 @@ def main():
     decay = _child("decay", None, a, 900)
     assert decay["error"] == 0
 
-    out = io.StringIO()
+    log = rates.Log()
     r0 = new[0]
     st = r0["stats"]
-    print(f"landed config-2 world: {r0['colliders']:,} colliders, {r0['bodies']:,} bodies, after {a.steps} steps; GPU {r0['gpu']}; device-event time per call, "
-          f"{a.reps} repetitions after a warm-up, mean [min .. max] in ms; a fresh process per library, order A B A B", file=out)
-    print(f"box pass: runs of {st['run_length']} leaves, {st['runs']} runs; top phase: {st['top_nodes']} nodes, the tree they form is {st['top_depth']} high", file=out)
+    log.say(f"landed {rates.world_name(a.tiles, a.world_side)} world: {r0['colliders']:,} colliders, {r0['bodies']:,} bodies, after {a.steps} steps; GPU {r0['gpu']}; "
+            f"device-event time per call, {a.reps} repetitions after a warm-up, mean [min .. max] in ms; a fresh process per library, order A B A B")
+    log.say(f"box pass: runs of {st['run_length']} leaves, {st['runs']} runs; top phase: {st['top_nodes']} nodes, the tree they form is {st['top_depth']} high")
     for k, (n_, o_) in enumerate(zip(new, old)):
-        print(f"run {k + 1}  A {n_['library']:<28} nh_query_refit {_span(n_['refit_ms'])}   nh_query_build {_span(n_['build_ms'])}", file=out)
-        print(f"run {k + 1}  B {o_['library']:<28} {'':<14} {'':<30}   nh_query_build {_span(o_['build_ms'])}", file=out)
+        log.say(f"run {k + 1}  A {n_['library']:<28} nh_query_refit {_span(n_['refit_ms'])}   nh_query_build {_span(n_['build_ms'])}")
+        log.say(f"run {k + 1}  B {o_['library']:<28} {'':<14} {'':<30}   nh_query_build {_span(o_['build_ms'])}")
     refit = [t for r in new for t in r["refit_ms"]]
     build_new = [t for r in new for t in r["build_ms"]]
     build_old = [t for r in old for t in r["build_ms"]]
     full = [t for r in new for t in r["full_ms"]]
     still = [t for r in new for t in r["still_ms"]]
     step1 = [t for r in new for t in r["step1_ms"]]
-    print(f"nh_query_refit                 {_span(refit)}", file=out)
-    print(f"nh_query_build, this library   {_span(build_new)}", file=out)
-    print(f"nh_query_build, parent library {_span(build_old)}", file=out)
+    log.say(f"nh_query_refit                 {_span(refit)}")
+    log.say(f"nh_query_build, this library   {_span(build_new)}")
+    log.say(f"nh_query_build, parent library {_span(build_old)}")
     verdict = "BEATS" if max(refit) < min(build_old) else "DOES NOT BEAT"
-    print(f"THE BAR: the slowest refit repetition ({max(refit):.4f}) {verdict} the fastest parent build repetition ({min(build_old):.4f}): "
-          f"parent build / refit = {np.mean(build_old) / np.mean(refit):.1f}x; parent build / this build = {np.mean(build_old) / np.mean(build_new):.2f}x", file=out)
-    print(f"steps of the same runs: still step {_span(still)} ({100 * r0['still_share']:.0f} % still steps), full step (option no_still) {_span(full)} "
-          f"({100 * r0['full_still_share']:.0f} % still steps), one-sub-step nh_step call {_span(step1)}", file=out)
+    log.say(f"THE BAR: the slowest refit repetition ({max(refit):.4f}) {verdict} the fastest parent build repetition ({min(build_old):.4f}): "
+            f"parent build / refit = {np.mean(build_old) / np.mean(refit):.1f}x; parent build / this build = {np.mean(build_old) / np.mean(build_new):.2f}x")
+    log.say(f"steps of the same runs: still step {_span(still)} ({100 * r0['still_share']:.0f} % still steps), full step (option no_still) {_span(full)} "
+            f"({100 * r0['full_still_share']:.0f} % still steps), one-sub-step nh_step call {_span(step1)}")
     ratio = np.mean(refit) / np.mean(full)
-    print(f"EXPECTATION (keeping the hierarchy current costs about one full step): refit = {ratio:.2f} full steps = {np.mean(refit) / np.mean(still):.2f} still steps: "
-          f"{'met' if ratio <= 1.0 else 'missed'}; this build = {np.mean(build_new) / np.mean(full):.1f} full steps; parent build = {np.mean(build_old) / np.mean(full):.1f} full steps",
-          file=out)
+    log.say(f"EXPECTATION (keeping the hierarchy current costs about one full step): refit = {ratio:.2f} full steps = {np.mean(refit) / np.mean(still):.2f} still steps: "
+            f"{'met' if ratio <= 1.0 else 'missed'}; this build = {np.mean(build_new) / np.mean(full):.1f} full steps; parent build = {np.mean(build_old) / np.mean(full):.1f} full steps")
     model = byte_model(r0["colliders"], st["top_nodes"])
     for title, key, src in (("nh_query_refit, this library", "refit_kernels", r0), ("nh_query_build, this library", "build_kernels", r0),
                             ("nh_query_build, parent library", "build_kernels", old[0])):
-        print(f"{title}: {'kernel':<16}{'ms/call':>10}{'launches':>10}{'MB':>10}{'% of 8 TB/s':>13}", file=out)
+        log.say(f"{title}: {'kernel':<16}{'ms/call':>10}{'launches':>10}{'MB':>10}{'% of 8 TB/s':>13}")
         for k, (ms, launches) in sorted(src[key].items(), key=lambda kv: -kv[1][0]):
             bts = model.get(k) if src is r0 else None
             share = f"{100.0 * bts / (ms * 1e-3) / HBM:12.1f}" if bts and ms > 0 else f"{'':>12}"
-            print(f"    {k:<16}{ms:10.4f}{launches:10d}{(bts or 0) / 1e6:10.1f} {share}", file=out)
-    print(f"DECAY: one build at step 0 (everything in the air), then nh_step(1) + nh_query_refit per step; {a.queries:,} incoherent closest-hit rays and "
-          f"{a.queries:,} unbounded nh_closest queries (uniform in the scene's bounds), refitted tree / fresh build of the same state", file=out)
-    print(f"{'step':>6}{'rays refit ms':>15}{'fresh ms':>10}{'rate x':>8}{'closest refit ms':>18}{'fresh ms':>10}{'rate x':>8}{'refit ms':>10}{'hits':>7}{'2048 + 2048 records':>22}", file=out)
+            log.say(f"    {k:<16}{ms:10.4f}{launches:10d}{(bts or 0) / 1e6:10.1f} {share}")
+    log.say(f"DECAY: one build at step 0 (everything in the air), then nh_step(1) + nh_query_refit per step; {a.queries:,} incoherent closest-hit rays and "
+            f"{a.queries:,} unbounded nh_closest queries (uniform in the scene's bounds), refitted tree / fresh build of the same state")
+    log.say(f"{'step':>6}{'rays refit ms':>15}{'fresh ms':>10}{'rate x':>8}{'closest refit ms':>18}{'fresh ms':>10}{'rate x':>8}{'refit ms':>10}{'hits':>7}{'2048 + 2048 records':>22}")
     for r in decay["rows"]:
         assert r["same_bytes"], f"step {r['step']}: the refitted tree and the fresh build answer differently"
-        print(f"{r['step']:6d}{r['rays_refit_ms']:15.3f}{r['rays_fresh_ms']:10.3f}{r['rays_fresh_ms'] / r['rays_refit_ms']:8.2f}{r['closest_refit_ms']:18.3f}"
-              f"{r['closest_fresh_ms']:10.3f}{r['closest_fresh_ms'] / r['closest_refit_ms']:8.2f}{r['refit_ms']:10.4f}{100 * r['hit_share_refit']:6.1f}%{'identical':>22}", file=out)
-    print("(rate x: the refitted tree's query rate as a multiple of the fresh build's)", file=out)
-    print(json.dumps(dict(new=new, parent=old, decay=decay)), file=out)
-    text = out.getvalue()
-    print(text, end="")
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write(text)
+        log.say(f"{r['step']:6d}{r['rays_refit_ms']:15.3f}{r['rays_fresh_ms']:10.3f}{r['rays_fresh_ms'] / r['rays_refit_ms']:8.2f}{r['closest_refit_ms']:18.3f}"
+                f"{r['closest_fresh_ms']:10.3f}{r['closest_fresh_ms'] / r['closest_refit_ms']:8.2f}{r['refit_ms']:10.4f}{100 * r['hit_share_refit']:6.1f}%{'identical':>22}")
+    log.say("(rate x: the refitted tree's query rate as a multiple of the fresh build's)")
+    log.say(json.dumps(dict(new=new, parent=old, decay=decay)))
+    log.write(a.out)
 
 
 if __name__ == "__main__":

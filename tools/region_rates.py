@@ -15,30 +15,13 @@ compared; they may differ by the few colliders near edges and corners that the p
     python tools/region_rates.py [--steps 70] [--reps 5] [--inner 20] [--out profiles/region_rates.log]
     (on a GPU box; prints the table, one JSON line at the end, and writes both to --out)
 """
-import argparse
 import json
-import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import rates
+from rates import box_planes
 from nudge_amd import engine as E           # noqa: E402
-from nudge_amd import scenes as S           # noqa: E402
-
-NONE = 0xFFFFFFFF
-
-
-def box_planes(lo, hi):
-    """The six planes of the axis-aligned boxes [lo, hi] ((n, 3) each), as (n, 6, 4)."""
-    lo, hi = np.atleast_2d(lo), np.atleast_2d(hi)
-    out = np.zeros((len(lo), 6, 4), dtype=np.float32)
-    for k in range(3):
-        out[:, 2 * k, k], out[:, 2 * k, 3] = 1.0, -lo[:, k]
-        out[:, 2 * k + 1, k], out[:, 2 * k + 1, 3] = -1.0, hi[:, k]
-    return out
 
 
 def camera(eye, target, fov_deg, aspect, near, far):
@@ -56,47 +39,26 @@ def camera(eye, target, fov_deg, aspect, near, far):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=70)
+    ap = rates.parser("region_rates")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--inner", type=int, default=20, help="nh_region calls per timed block (the nh_overlap twins are timed one call at a time)")
     ap.add_argument("--walk-reps", type=int, default=1, help="calls of the one-lane nh_overlap twin of (a): each takes seconds")
     ap.add_argument("--cubes", type=int, default=4096)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "region_rates.log"))
     a = ap.parse_args()
-    import torch
     import hostregion_util as R
-    scene = S.grid_tiles(124, side=90, seed=2, lattice_cols=11)
-    nb = len(scene["body_transforms"])
-    w = E.World(scene, flags=E.NH_FLAG_SINGLE_APPLY | E.NH_FLAG_FUSED_STEP, max_contacts=6 * nb)
-    w.step(a.steps)
-    w.synchronize()
-    w.query_build()
+    land = rates.landed(a)
+    w, rec = land.world, land.records
     st = w.query_stats()
-    stream = torch.cuda.current_stream(w.dev)
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    lines = []
-
-    def say(s=""):
-        print(s, flush=True)
-        lines.append(s)
-
-    def up(arr):
-        return torch.from_numpy(np.ascontiguousarray(arr).view(np.uint8).copy()).to(w.dev)
-
-    rec = R.records(w.get_bodies()["transforms"], scene)
+    log = rates.Log()
     C = len(rec)
-    reach = np.linalg.norm(rec["h"].astype(np.float64), axis=1, keepdims=True)
-    lo, hi = (rec["p"] - reach).min(axis=0) - 1.0, (rec["p"] + reach).max(axis=0) + 1.0
+    lo, hi = rates.reach_bounds(rec)
     dyn = rec["p"][rec["body"] != 0].astype(np.float64)
     dlo, dhi = dyn.min(axis=0), dyn.max(axis=0)
-    tile = np.nonzero(np.asarray(scene["tile_of_body"]) == 0)[0]
-    tp = w.get_bodies()["transforms"]["position"][tile].astype(np.float64)
-    tile_size = float((tp.max(axis=0) - tp.min(axis=0))[[0, 2]].max())
+    tile_size = rates.tile_size(land.scene, w.get_bodies()["transforms"]["position"])
 
     def count_of(planes):
-        off, _ = w.region_records(up(R.regions(planes)))
-        return int(off[-1].item()) & 0xFFFFFFFF
+        off, _ = w.region_records(rates.upload(w, R.regions(planes)))
+        return rates.total_of(off)
 
     # (b): from outside a corner of the world, looking at its middle; the far plane by bisection on the count
     mid = 0.5 * (dlo + dhi)
@@ -124,78 +86,44 @@ def main():
         "c": R.regions(np.stack(ring)),
         "d": R.regions(box_planes(centres - half, centres + half)),
     }
-
-    def boxes(c, h):
-        q = np.zeros(len(c), dtype=E.OVERLAP_QUERY)
-        q["center"], q["size"], q["shape"], q["rotation"], q["ignore_body"] = c, h, E.NH_SHAPE_BOX, (0, 0, 0, 1), NONE
-        return q
-    twins = {"a": boxes([0.5 * (lo + hi)], [0.5 * (hi - lo)]), "d": boxes(centres, np.full((a.cubes, 3), half))}
+    twins = {"a": rates.overlap_queries([0.5 * (lo + hi)], [0.5 * (hi - lo)], E.NH_SHAPE_BOX),
+             "d": rates.overlap_queries(centres, np.full((a.cubes, 3), half), E.NH_SHAPE_BOX)}
 
     def measure(records, q, reps, inner, breakdown=True):
-        """(total, best and median ms per call of the count-only call and of count + exactly sized list over `reps` blocks of `inner` calls, the labels of
-        one more pair of calls where `breakdown`)."""
-        qt = up(q)
-        ot = torch.empty(len(q) + 1, dtype=torch.int32, device=w.dev)
-        records(qt, offsets=ot)
-        total = int(ot[-1].item()) & 0xFFFFFFFF
-        ht = torch.empty((max(total, 1), 16), dtype=torch.uint8, device=w.dev)
-        fns = (lambda: records(qt, offsets=ot), lambda: (records(qt, offsets=ot), records(qt, offsets=ot, hits=ht, capacity=total)))
-        fns[1]()                                                          # warm-up: the scratch grows here
-        stream.synchronize()
-        best = []
-        for fn in fns:
-            ts = []
-            for _ in range(reps):
-                ev0.record(stream)
-                for _ in range(inner):
-                    fn()
-                ev1.record(stream)
-                ev1.synchronize()
-                ts.append(ev0.elapsed_time(ev1) / inner)
-            best.append((min(ts), float(np.median(ts))))
-        labels = {}
-        if breakdown:
-            w.enable_timing(True)
-            w.kernel_times()
-            fns[1]()
-            labels = {k: round(v[0], 4) for k, v in sorted(w.kernel_times().items()) if v[1]}
-            w.enable_timing(False)
-        return total, best[0], best[1], labels
+        return rates.count_then_list(w, records, rates.upload(w, q), len(q), 16, reps, inner, breakdown)[0]
 
-    say(f"landed config-2 world: {C:,} colliders, {nb:,} bodies, after {a.steps} steps; {st['runs']} runs, {st['top_nodes'] + 1} entry nodes; "
-        f"GPU {torch.cuda.get_device_name(w.dev)}")
-    say(f"ms per call: the best of {a.reps} blocks of {a.inner} calls after a warm-up, device events around the block; one box, one run.  "
-        f"tile size {tile_size:.1f}, frustum far plane {far:.1f}")
-    say(f"  {'case':58s} {'regions':>8s} {'records':>11s} {'count ms':>10s} {'count+list ms':>14s}")
+    log.say(f"landed {land.name} world: {C:,} colliders, {land.bodies:,} bodies, after {a.steps} steps; {st['runs']} runs, {st['top_nodes'] + 1} entry nodes; "
+            f"GPU {rates.gpu_name(w)}")
+    log.say(f"ms per call: the best of {a.reps} blocks of {a.inner} calls after a warm-up, device events around the block; one box, one run.  "
+            f"tile size {tile_size:.1f}, frustum far plane {far:.1f}")
+    log.say(f"  {'case':58s} {'regions':>8s} {'records':>11s} {'count ms':>10s} {'count+list ms':>14s}")
     names = {"a": "(a) nh_region, the world's AABB", "b": "(b) nh_region, a frustum that sees a tenth", "c": "(c) nh_region, 64 such frusta",
              "d": f"(d) nh_region, {a.cubes:,} cubes of a tile's size"}
     out = {}
     for key, regs in cases.items():
-        total, (t_count, m_count), (t_list, m_list), labels = measure(w.region_records, regs, a.reps, a.inner)
-        out[key] = dict(regions=len(regs), records=total, count_ms=t_count, list_ms=t_list, count_median_ms=m_count, list_median_ms=m_list, labels=labels)
-        say(f"  {names[key]:58s} {len(regs):8,d} {total:11,d} {t_count:10.3f} {t_list:14.3f}   (medians {m_count:.3f}, {m_list:.3f})")
-        say(f"      labels of count + list, ms: {labels}")
+        r = measure(w.region_records, regs, a.reps, a.inner)
+        out[key] = dict(regions=len(regs), **r)
+        log.say(f"  {names[key]:58s} {len(regs):8,d} {r['records']:11,d} {r['count_ms']:10.3f} {r['list_ms']:14.3f}   (medians {r['count_median_ms']:.3f}, {r['list_median_ms']:.3f})")
+        log.say(f"      labels of count + list, ms: {r['labels']}")
         if key in twins:
             reps = a.walk_reps if key == "a" else a.reps
-            total2, (o_count, mo_count), (o_list, mo_list), labels = measure(w.overlap_records, twins[key], reps, 1, breakdown=key != "a")
-            out[key + "_overlap"] = dict(queries=len(twins[key]), records=total2, count_ms=o_count, list_ms=o_list, count_median_ms=mo_count, list_median_ms=mo_list,
-                                         labels=labels)
-            say(f"  {'    nh_overlap, the same as box queries (%d x 1 call)' % reps:58s} {len(twins[key]):8,d} {total2:11,d} {o_count:10.3f} {o_list:14.3f}"
-                f"   (medians {mo_count:.3f}, {mo_list:.3f})")
-            say(f"      nh_overlap / nh_region: count {o_count / t_count:.1f} x, count + list {o_list / t_list:.1f} x"
-                f"{'' if total2 == total else f'   (the box test lists {total - total2:,} fewer: edges and corners)'}")
+            o = measure(w.overlap_records, twins[key], reps, 1, breakdown=key != "a")
+            out[key + "_overlap"] = dict(queries=len(twins[key]), **o)
+            log.say(f"  {'    nh_overlap, the same as box queries (%d x 1 call)' % reps:58s} {len(twins[key]):8,d} {o['records']:11,d} {o['count_ms']:10.3f} {o['list_ms']:14.3f}"
+                    f"   (medians {o['count_median_ms']:.3f}, {o['list_median_ms']:.3f})")
+            fewer = "" if o["records"] == r["records"] else f"   (the box test lists {r['records'] - o['records']:,} fewer: edges and corners)"
+            log.say(f"      nh_overlap / nh_region: count {o['count_ms'] / r['count_ms']:.1f} x, count + list {o['list_ms'] / r['list_ms']:.1f} x{fewer}")
     assert out["a"]["records"] == C, "the world's AABB does not hold every collider"
     # 3 regions of (c) and 8 of (d), byte for byte against the brute force over all colliders
+    import torch
     pick = np.concatenate([cases["c"][:3], cases["d"][:8]])
     ref_off, ref_hits, total = R.region(rec, w.nbox, pick)
-    ot, ht = w.region_records(up(pick), hits=torch.empty((total, 16), dtype=torch.uint8, device=w.dev), capacity=total)
+    ot, ht = w.region_records(rates.upload(w, pick), hits=torch.empty((total, 16), dtype=torch.uint8, device=w.dev), capacity=total)
     assert ot.cpu().numpy().view(np.uint32).tobytes() == ref_off.tobytes() and ht.cpu().numpy().tobytes() == ref_hits[:total].tobytes(), "the GPU differs from the brute force"
-    say(f"  {len(pick)} regions ({total:,} records) equal the brute force byte for byte")
-    say()
-    say(json.dumps(dict(colliders=C, steps=a.steps, entries=st["top_nodes"] + 1, **out)))
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
+    log.say(f"  {len(pick)} regions ({total:,} records) equal the brute force byte for byte")
+    log.say()
+    log.say(json.dumps(dict(colliders=C, steps=a.steps, entries=st["top_nodes"] + 1, **out)))
+    log.write(a.out)
     w.close()
 
 

@@ -12,23 +12,16 @@ a ray; nh_sense reads 48 bytes a sensor and writes 4 bytes a ray and channel.
     python tools/sense_rates.py [--steps 70] [--reps 5] [--inner 5] [--out profiles/sense_rates.log]
     (on a GPU box; prints the table, one JSON line at the end, and writes both to --out)
 """
-import argparse
 import json
-import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import rates
 from nudge_amd import engine as E           # noqa: E402
-from nudge_amd import scenes as S           # noqa: E402
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=70)
+    ap = rates.parser("sense_rates", side_flag="--world-side")          # (--side is the camera image's here)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--inner", type=int, default=5)
     ap.add_argument("--cameras", type=int, default=4096)
@@ -36,27 +29,10 @@ def main():
     ap.add_argument("--lidars", type=int, default=256)
     ap.add_argument("--rings", type=int, default=64)
     ap.add_argument("--azimuths", type=int, default=1024)
-    ap.add_argument("--tiles", type=int, default=124, help="tiles of the world (124: config 2; fewer for a rehearsal)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sense_rates.log"))
     a = ap.parse_args()
     import torch
-    scene = S.grid_tiles(a.tiles, side=90, seed=2, lattice_cols=11)
-    nb = len(scene["body_transforms"])
-    w = E.World(scene, flags=E.NH_FLAG_SINGLE_APPLY | E.NH_FLAG_FUSED_STEP, max_contacts=6 * nb)
-    w.step(a.steps)
-    w.synchronize()
-    w.query_build()
-    stream = torch.cuda.current_stream(w.dev)
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    lines = []
-
-    def say(s=""):
-        print(s, flush=True)
-        lines.append(s)
-
-    def up(arr):
-        return torch.from_numpy(np.ascontiguousarray(arr).view(np.uint8).copy()).to(w.dev)
-
+    land = rates.landed(a)
+    w, scene, log = land.world, land.scene, rates.Log()
     rng = np.random.default_rng(1)
     dynamic = np.unique(np.concatenate([scene["box_transforms"]["body"], scene["sphere_transforms"]["body"]]))
     dynamic = dynamic[dynamic != 0]
@@ -71,17 +47,7 @@ def main():
         return s
 
     def timed(fn):
-        fn()
-        stream.synchronize()
-        ts = []
-        for _ in range(a.reps):
-            ev0.record(stream)
-            for _ in range(a.inner):
-                fn()
-            ev1.record(stream)
-            ev1.synchronize()
-            ts.append(ev0.elapsed_time(ev1) / a.inner)
-        return min(ts), float(np.median(ts))
+        return rates.best_median(rates.blocks(w, fn, a.reps, a.inner))
 
     tiled, _ = E.pinhole_beams(a.side, a.side, np.radians(60.0), 200.0)
     rows, _ = E.pinhole_beams(a.side, a.side, np.radians(60.0), 200.0, tile=1)
@@ -89,13 +55,13 @@ def main():
     cams, lids = riders(a.cameras), riders(a.lidars)
     cases = [(f"pinhole {a.side} x {a.side}, 8 x 8 tiles", cams, tiled), (f"pinhole {a.side} x {a.side}, row-major", cams, rows),
              (f"lidar {a.rings} x {a.azimuths}", lids, lidar)]
-    say(f"landed config-2 world: {w.nbox + w.nsph:,} colliders, {nb:,} bodies, after {a.steps} steps; GPU {torch.cuda.get_device_name(w.dev)}")
-    say(f"ms per call: the best (median) of {a.reps} blocks of {a.inner} calls after a warm-up, device events around the block; one box, one run.  "
-        f"G/s: 1e9 rays a second from the best.")
-    say(f"  {'case':36s} {'sensors':>8s} {'rays':>12s} {'hit share':>9s} | {'sense t':>16s} {'t + body':>16s} {'full hits':>16s} | {'sense_rays':>16s} {'nh_raycast':>16s} | raycast / sense t")
+    log.say(f"landed {land.name} world: {w.nbox + w.nsph:,} colliders, {land.bodies:,} bodies, after {a.steps} steps; GPU {rates.gpu_name(w)}")
+    log.say(f"ms per call: the best (median) of {a.reps} blocks of {a.inner} calls after a warm-up, device events around the block; one box, one run.  "
+            f"G/s: 1e9 rays a second from the best.")
+    log.say(f"  {'case':36s} {'sensors':>8s} {'rays':>12s} {'hit share':>9s} | {'sense t':>16s} {'t + body':>16s} {'full hits':>16s} | {'sense_rays':>16s} {'nh_raycast':>16s} | raycast / sense t")
     out = {}
     for name, sensors, beams in cases:
-        st, bm = up(sensors), up(beams)
+        st, bm = rates.upload(w, sensors), rates.upload(w, beams)
         n = len(sensors) * len(beams)
         t = torch.empty(n, dtype=torch.float32, device=w.dev)
         body = torch.empty(n, dtype=torch.int32, device=w.dev)
@@ -110,22 +76,20 @@ def main():
         r["sense_rays"] = timed(lambda: w.sense_rays_records(st, bm, rays=rays))
         r["raycast"] = timed(lambda: w.raycast_records(rays, hits=cast))
         w.sense_records(st, bm, t=t, body=body)
-        stream.synchronize()
+        torch.cuda.current_stream(w.dev).synchronize()
         same = bool(torch.equal(t.view(torch.int32), cast.view(torch.int32).reshape(n, 8)[:, 0])) and bool(torch.equal(hits, cast))
         assert same, f"{name}: nh_sense differs from nh_raycast on nh_sense_rays' records"
         share = float((body != -1).float().mean())
         cell = lambda k: f"{r[k][0]:7.3f} ({r[k][1]:7.3f})"      # noqa: E731
-        say(f"  {name:36s} {len(sensors):8,d} {n:12,d} {share:9.3f} | {cell('sense_t')} {cell('sense_t_body')} {cell('sense_hits')} | {cell('sense_rays')} {cell('raycast')} | "
-            f"{r['raycast'][0] / r['sense_t'][0]:.2f} x  ({n / r['sense_t'][0] / 1e6:.2f} against {n / r['raycast'][0] / 1e6:.2f} G/s)")
+        log.say(f"  {name:36s} {len(sensors):8,d} {n:12,d} {share:9.3f} | {cell('sense_t')} {cell('sense_t_body')} {cell('sense_hits')} | {cell('sense_rays')} {cell('raycast')} | "
+                f"{r['raycast'][0] / r['sense_t'][0]:.2f} x  ({n / r['sense_t'][0] / 1e6:.2f} against {n / r['raycast'][0] / 1e6:.2f} G/s)")
         out[name] = dict(sensors=len(sensors), beams=len(beams), rays=n, hit_share=share, same_bytes=same,
                          **{k: dict(best_ms=v[0], median_ms=v[1], grays_per_s=n / v[0] / 1e6) for k, v in r.items()})
         del t, body, hits, rays, cast
-    say("  every case: t and the hit records of nh_sense equal nh_raycast's on nh_sense_rays' records byte for byte")
-    say()
-    say(json.dumps(dict(colliders=w.nbox + w.nsph, steps=a.steps, cases=out)))
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
+    log.say("  every case: t and the hit records of nh_sense equal nh_raycast's on nh_sense_rays' records byte for byte")
+    log.say()
+    log.say(json.dumps(dict(colliders=w.nbox + w.nsph, steps=a.steps, cases=out)))
+    log.write(a.out)
     w.close()
 
 

@@ -21,21 +21,15 @@ are unchanged).
     [NUDGE_HIP_LIBRARY=.../libparent.so] python tools/touched_rates.py [--steps 70] [--reps 10] [--repeats 7] [--out profiles/touched_rates.log]
     (on a GPU box; prints the table, one JSON line at the end, and writes both to --out)
 """
-import argparse
 import json
 import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-OTHER = os.environ.pop("NUDGE_HIP_LIBRARY", None)          # (engine reads it on import: this process loads the tree's library first)
+import rates
+OTHER = rates.other_library()
 from nudge_amd import engine as E           # noqa: E402
-from nudge_amd import scenes as S           # noqa: E402
 
-NONE = 0xFFFFFFFF
 MOVE_BOX, WALK_BOX = (0.3, 0.5, 0.4), (0.3, 0.7, 0.3)
 # what the kernels were compiled for (nh_query.hip, DESIGN 10.20): waves per SIMD, plain and touched
 OCCUPANCY = dict(move=(4, 4), boxmove=(3, 3), walk=(3, 2), boxwalk=(2, 2))
@@ -43,106 +37,39 @@ K_SMALL = 4
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=70)
+    ap = rates.parser("touched_rates")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--records", type=int, default=1 << 20)
     ap.add_argument("--max-slides", type=int, default=4)
     ap.add_argument("--no-check", action="store_true", help="skip the brute-force spot checks")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "touched_rates.log"))
     a = ap.parse_args()
     import torch
     import boxwalk_batches as BWB
     import hosttouch_util as HT
-    import hostquery_util as Q
     import walk_batches as WB
     from hostmover_util import BOX as HBM, CAPSULE as HM
     from query_util import unit_quats
-    scene = S.grid_tiles(124, side=90, seed=2, lattice_cols=11)
-    nb = len(scene["body_transforms"])
-    colliders = len(scene["box_tags"]) + len(scene["sphere_tags"])
-
-    def world():
-        w = E.World(scene, flags=E.NH_FLAG_SINGLE_APPLY | E.NH_FLAG_FUSED_STEP, max_contacts=6 * nb)
-        w.step(a.steps)
-        w.synchronize()
-        w.query_build()
-        return w
-
-    w = world()
+    land = rates.landed(a)
     others = []
     if OTHER:
-        E._LIB, E._LIB_PATH = None, os.path.abspath(OTHER)
-        others = [world(), world()]
-        assert others[0].L is not w.L
-    lines = []
-
-    def say(s=""):
-        print(s, flush=True)
-        lines.append(s)
-
-    def interleaved(fns):
-        """fns: {key: (world, timing label, call)}.  Per key the per-call kernel time of each of --repeats blocks of --reps calls, by the world's timers."""
-        for wd, _, fn in fns.values():
-            fn(); fn()
-            wd.synchronize()
-        blocks = {key: [] for key in fns}
-        for _ in range(a.repeats):
-            for key, (wd, label, fn) in fns.items():
-                wd.enable_timing(True, only=label)
-                wd.kernel_times(reset=True)
-                for _ in range(a.reps):
-                    fn()
-                ms, launches = wd.kernel_times(reset=True)[label]
-                wd.enable_timing(False)
-                assert launches == a.reps, (label, launches)
-                blocks[key].append(ms / launches)
-        return {key: np.array(v) for key, v in blocks.items()}
-
-    def med(v):
-        return dict(ms=float(np.median(v)), min=float(min(v)), max=float(max(v)))
-
-    def up(x, wd=None):
-        return torch.from_numpy(np.ascontiguousarray(x).view(np.uint8).copy()).to((wd or w).dev)
-
-    def down(t, dtype):
-        return np.frombuffer(t.cpu().numpy().tobytes(), dtype=dtype).copy()
-
-    fmt = lambda v: f"{v['ms']:.3f} ({v['min']:.3f} .. {v['max']:.3f})"                       # noqa: E731
-    n = a.records
-    rec = Q.records(w.get_bodies()["transforms"], scene)
-    pick = np.sort(np.random.default_rng(3).choice(n, size=258, replace=False))
-    say(f"landed config-2 world: {colliders:,} colliders, {nb:,} bodies, after {a.steps} steps; GPU {torch.cuda.get_device_name(w.dev)}")
-    say(f"{n:,} records per call, max_slides {a.max_slides}; the library's kernel timers, median of {a.repeats} blocks of {a.reps} calls, interleaved "
-        f"(min .. max of the blocks); one box, one run")
+        first = rates.landed(a, OTHER, like=land)
+        others = [first.world, rates.landed(a, first, like=land).world]
+    w, colliders, n, rec = land.world, land.colliders, a.records, land.records
+    med, fmt, log = rates.spread, rates.fmt, rates.Log()
+    pick = rates.spot(n)
+    log.say(f"landed {land.name} world: {colliders:,} colliders, {land.bodies:,} bodies, after {a.steps} steps; GPU {rates.gpu_name(w)}")
+    log.say(f"{n:,} records per call, max_slides {a.max_slides}; the library's kernel timers, median of {a.repeats} blocks of {a.reps} calls, interleaved "
+            f"(min .. max of the blocks); one box, one run")
 
     # ---- the records: move_rates' and boxmove_rates' moves, walk_rates' and boxmove_rates' walks
     rng = np.random.default_rng(1)
-    pos = w.get_bodies()["transforms"]["position"][1:].astype(np.float64)           # the dynamic bodies, landed
-    at = rng.integers(0, len(pos), size=n)
-    o = pos[at] + np.stack([rng.uniform(-0.5, 0.5, n), rng.uniform(2.2, 3.0, n), rng.uniform(-0.5, 0.5, n)], axis=1)
-    d = rng.normal(size=(n, 3))
-    d[:, 1] = -np.abs(d[:, 1]) - 0.5
-    d *= rng.uniform(0.75, 3.0, size=(n, 1)) / np.linalg.norm(d, axis=1, keepdims=True)
+    o, d = rates.move_batch(rng, n, land.positions)
     rot = unit_quats(rng, n)
     records = dict(move=HM.moves(o, d, 0.5, 0.5, rotations=rot, skin=0.01, max_slides=a.max_slides),
                    boxmove=HBM.moves(o, d, MOVE_BOX, rotations=rot, skin=0.01, max_slides=a.max_slides))
     rng = np.random.default_rng(2)
-    tops = WB._tops(rec, w.nbox)
-    dyn = np.nonzero(rec["body"] != 0)[0]
-    at = rng.choice(dyn, size=n)
-    p = rec["p"].astype(np.float64)
-    slab_top = float(np.median(tops[rec["body"] == 0]))
-    on_slab = rng.random(n) < 0.5
-    ang = rng.uniform(0.0, 2 * np.pi, n)
-    away = rng.uniform(1.3, 2.2, n)                                        # a body is ~1.5 across: beside it, not in it
-    x = np.where(on_slab, p[at, 0] + np.cos(ang) * away, p[at, 0] + rng.uniform(-0.3, 0.3, n))
-    z = np.where(on_slab, p[at, 2] + np.sin(ang) * away, p[at, 2] + rng.uniform(-0.3, 0.3, n))
-    top = np.where(on_slab, slab_top, tops[at])
-    head = np.where(on_slab, ang + np.pi, rng.uniform(0.0, 2 * np.pi, n))
-    length = rng.uniform(0.5, 2.0, n)
-    d = np.stack([np.cos(head) * length, np.zeros(n), np.sin(head) * length], axis=1)
+    x, top, z, d = rates.walk_batch(rng, n, rec, WB._tops(rec, w.nbox))
     records["walk"] = HM.walks(WB.stand(x, top, z, 0.3, 0.4), d, 0.3, 0.4, skin=WB.SKIN, max_slides=a.max_slides, snap_distance=0.3, step_height=1.0)
     records["boxwalk"] = HBM.walks(BWB.stand(x, top, z, WALK_BOX[1]), d, WALK_BOX, rotations=BWB._yaw(rng, n, 1.0), skin=WB.SKIN, max_slides=a.max_slides,
                                    snap_distance=0.3, step_height=1.0)
@@ -153,7 +80,7 @@ def main():
     # ---- each mover: plain, touched at k = 4, touched at k = the maximum
     cn = torch.empty(n, dtype=torch.int32, device=w.dev)
     for name, T, kind, size, dtype, k_max in movers:
-        rt = up(records[name])
+        rt = rates.upload(w, records[name])
         plain_out = torch.empty((n, size), dtype=torch.uint8, device=w.dev)
         outs = {k: torch.empty((n, size), dtype=torch.uint8, device=w.dev) for k in (K_SMALL, k_max)}
         tch = {k: torch.empty((n, k, 64), dtype=torch.uint8, device=w.dev) for k in (K_SMALL, k_max)}
@@ -161,60 +88,46 @@ def main():
         fns = dict(plain=(w, "q_" + name, lambda: plain_call(rt, results=plain_out)))
         for k in (K_SMALL, k_max):
             fns[k] = (w, f"q_{name}_touched", lambda k=k: touched_call(rt, k, results=outs[k], counts=cn, touches=tch[k]))
-        blocks = interleaved(fns)
+        blocks = rates.interleaved_kernels(fns, a.reps, a.repeats)
         w.synchronize()
         assert torch.equal(outs[K_SMALL], plain_out) and torch.equal(outs[k_max], plain_out), f"nh_{name}_touched: results differ from nh_{name}'s"
         counts = cn.cpu().numpy().view(np.uint32)
         checked = 0
         if not a.no_check:
             ref, ref_counts, ref_touches = getattr(T, kind)(rec, w.nbox, records[name][pick])
-            got_touches = np.frombuffer(tch[k_max][torch.from_numpy(pick).to(w.dev)].cpu().numpy().tobytes(), dtype=E.TOUCH).reshape(len(pick), k_max)
-            assert down(outs[k_max], dtype)[pick].tobytes() == ref.tobytes(), f"nh_{name}_touched differs from the brute force"
+            got_touches = rates.download(tch[k_max][torch.from_numpy(pick).to(w.dev)], E.TOUCH).reshape(len(pick), k_max)
+            assert rates.download(outs[k_max], dtype)[pick].tobytes() == ref.tobytes(), f"nh_{name}_touched differs from the brute force"
             HT.same_touches(got_touches, counts[pick], ref_touches, ref_counts, name)
             checked = len(pick)
         hist = [int(v) for v in np.bincount(counts, minlength=2)]
-        t = {key: med(v) for key, v in blocks.items()}
+        t = rates.spreads(blocks)
         ratios = {k: med(blocks[k] / blocks["plain"]) for k in (K_SMALL, k_max)}
         mean = float(counts.mean())
         cut = float((counts > K_SMALL).mean())
         plain_waves, touched_waves = OCCUPANCY[name]
-        say(f"nh_{name} ({plain_waves} waves per SIMD) and nh_{name}_touched ({touched_waves}):")
-        say(f"  nh_{name:<34} {fmt(t['plain'])} ms")
+        log.say(f"nh_{name} ({plain_waves} waves per SIMD) and nh_{name}_touched ({touched_waves}):")
+        log.say(f"  nh_{name:<34} {fmt(t['plain'])} ms")
         for k in (K_SMALL, k_max):
-            say(f"  {'nh_%s_touched, k = %d' % (name, k):<37} {fmt(t[k])} ms   touched / plain per block {fmt(ratios[k])}")
-        say(f"  touches per record, mean               {mean:.3f}   (histogram 0, 1, 2, ...: {hist}; {cut:.4f} of the records have more than {K_SMALL})")
-        say(f"  bytes of touches and counts written    {(64 * np.minimum(counts, k_max).sum() + 4 * n) / 1e6:.1f} MB at k = {k_max} beside {size * n / 1e6:.1f} MB of results")
-        say(f"  {checked} records equal the brute force byte for byte; all results equal nh_{name}'s")
+            log.say(f"  {'nh_%s_touched, k = %d' % (name, k):<37} {fmt(t[k])} ms   touched / plain per block {fmt(ratios[k])}")
+        log.say(f"  touches per record, mean               {mean:.3f}   (histogram 0, 1, 2, ...: {hist}; {cut:.4f} of the records have more than {K_SMALL})")
+        log.say(f"  bytes of touches and counts written    {(64 * np.minimum(counts, k_max).sum() + 4 * n) / 1e6:.1f} MB at k = {k_max} beside {size * n / 1e6:.1f} MB of results")
+        log.say(f"  {checked} records equal the brute force byte for byte; all results equal nh_{name}'s")
         result["movers"][name] = dict(plain=t["plain"], touched={str(k): t[k] for k in (K_SMALL, k_max)}, ratio={str(k): ratios[k] for k in (K_SMALL, k_max)},
                                       mean_touches=mean, touches=hist, more_than_k_small=cut, checked_against_brute_force=checked)
         del rt, plain_out, outs, tch
 
     # ---- the plain movers beside the other library
     if others:
-        say(f"filter off, this library beside {os.path.basename(OTHER)} loaded twice (the same bytes from all three); per block this / parent, and parent again / parent:")
-        result["beside_other"] = {}
-        for name, _, _, size, _, _ in movers:
-            worlds = dict(this=w, parent=others[0], again=others[1])
-            ins = {k: up(records[name], wd) for k, wd in worlds.items()}
-            outs = {k: torch.empty((n, size), dtype=torch.uint8, device=w.dev) for k in worlds}
-            blocks = interleaved({k: (wd, "q_" + name, (lambda k=k, wd=wd: getattr(wd, name + "_records")(ins[k], results=outs[k]))) for k, wd in worlds.items()})
-            assert torch.equal(outs["this"], outs["parent"]) and torch.equal(outs["again"], outs["parent"]), f"nh_{name}: the libraries differ"
-            this, parent, again = (blocks[k] for k in ("this", "parent", "again"))
-            r_this, r_self = this / parent, again / parent
-            inside = bool(r_self.min() <= np.median(r_this) <= r_self.max())
-            say(f"  nh_{name:<8} this {fmt(med(this))} ms   parent {fmt(med(parent))} ms   this / parent {np.median(r_this):.3f} ({r_this.min():.3f} .. {r_this.max():.3f})"
-                f"   parent / parent {np.median(r_self):.3f} ({r_self.min():.3f} .. {r_self.max():.3f})   {'inside' if inside else 'OUTSIDE'} the parent's own spread")
-            result["beside_other"][name] = dict(this=med(this), parent=med(parent), again=med(again), this_over_parent=med(r_this), parent_over_parent=med(r_self),
-                                                inside=inside)
+        log.say(f"filter off, this library beside {os.path.basename(OTHER)} loaded twice (the same bytes from all three); per block this / parent, and parent again / parent:")
+        calls = [(name, "q_" + name, records[name], size, (lambda wd, t_, r_, name=name: getattr(wd, name + "_records")(t_, results=r_))) for name, _, _, size, _, _ in movers]
+        result["beside_other"] = rates.beside_parent(log, dict(this=w, parent=others[0], again=others[1]), calls, n, a.reps, a.repeats)
         for wd in others:
             wd.close()
     else:
-        say("filter off, this library beside another build: no NUDGE_HIP_LIBRARY given, not measured")
-    say()
-    say(json.dumps(result))
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
+        log.say("filter off, this library beside another build: no NUDGE_HIP_LIBRARY given, not measured")
+    log.say()
+    log.say(json.dumps(result))
+    log.write(a.out)
     w.close()
 
 

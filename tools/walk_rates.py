@@ -15,126 +15,52 @@ answers nh_move and nh_capsulecast on the same records, filter off, interleaved 
     [NUDGE_HIP_LIBRARY=.../libparent.so] python tools/walk_rates.py [--steps 70] [--reps 10] [--repeats 5] [--out profiles/walk_rates.log]
     (on a GPU box; prints the table, one JSON line at the end, and writes both to --out)
 """
-import argparse
 import json
 import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-OTHER = os.environ.pop("NUDGE_HIP_LIBRARY", None)          # (engine reads it on import: this process loads the tree's library first)
+import rates
+OTHER = rates.other_library()
 from nudge_amd import engine as E           # noqa: E402
-from nudge_amd import scenes as S           # noqa: E402
 
-NONE = 0xFFFFFFFF
 CONFIGS = (("step 0, limit off", 0.0, 0.0), ("step 0, limit 45", 0.0, 45.0), ("step 1.0, limit off", 1.0, 0.0), ("step 1.0, limit 45", 1.0, 45.0))
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=70)
+    ap = rates.parser("walk_rates")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--walks", type=int, default=1 << 20)
     ap.add_argument("--max-slides", type=int, default=4)
     ap.add_argument("--no-check", action="store_true", help="skip the brute-force spot check")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "walk_rates.log"))
     a = ap.parse_args()
     import torch
     import hostmover_util as MV
     from hostmover_util import CAPSULE as HW
     import walk_batches as WB
-    scene = S.grid_tiles(124, side=90, seed=2, lattice_cols=11)
-    nb = len(scene["body_transforms"])
-    C = len(scene["box_tags"]) + len(scene["sphere_tags"])
-
-    def world():
-        w = E.World(scene, flags=E.NH_FLAG_SINGLE_APPLY | E.NH_FLAG_FUSED_STEP, max_contacts=6 * nb)
-        w.step(a.steps)
-        w.synchronize()
-        w.query_build()
-        return w
-
-    w = world()
-    other = None
-    if OTHER:
-        E._LIB, E._LIB_PATH = None, os.path.abspath(OTHER)
-        other = world()
-        assert other.L is not w.L
-    stream = torch.cuda.current_stream(w.dev)
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    lines = []
-
-    def say(s=""):
-        print(s, flush=True)
-        lines.append(s)
-
-    def timed(fn, reps):
-        ev0.record(stream)
-        for _ in range(reps):
-            fn()
-        ev1.record(stream)
-        ev1.synchronize()
-        return ev0.elapsed_time(ev1) / reps
-
-    def med(v):
-        return dict(ms=float(np.median(v)), min=min(v), max=max(v))
-
-    def interleaved(fns):
-        for fn in fns.values():
-            fn(); fn()
-        stream.synchronize()
-        times = {key: [] for key in fns}
-        for _ in range(a.repeats):
-            for key, fn in fns.items():
-                times[key].append(timed(fn, a.reps))
-        return {key: med(v) for key, v in times.items()}
-
-    def up(x, world_=None):
-        return torch.from_numpy(np.ascontiguousarray(x).view(np.uint8).copy()).to((world_ or w).dev)
-
-    def down(t, dtype):
-        return np.frombuffer(t.cpu().numpy().tobytes(), dtype=dtype).copy()
-
-    fmt = lambda v: f"{v['ms']:.3f} ({v['min']:.3f} .. {v['max']:.3f})"                       # noqa: E731
-    rng = np.random.default_rng(1)
-    n = a.walks
-    import hostquery_util as Q
-    rec = Q.records(w.get_bodies()["transforms"], scene)
-    tops = WB._tops(rec, w.nbox)
-    dyn = np.nonzero(rec["body"] != 0)[0]
-    at = rng.choice(dyn, size=n)
-    p = rec["p"].astype(np.float64)
-    slab_top = float(np.median(tops[rec["body"] == 0]))
-    on_slab = rng.random(n) < 0.5
+    land = rates.landed(a)
+    other = rates.landed(a, OTHER, like=land).world if OTHER else None
+    w, C, n, rec = land.world, land.colliders, a.walks, land.records
+    up, down, fmt, log = rates.upload, rates.download, rates.fmt, rates.Log()
     R, HH = 0.3, 0.4
-    ang = rng.uniform(0.0, 2 * np.pi, n)
-    away = rng.uniform(1.3, 2.2, n)                                        # a body is ~1.5 across: beside it, not in it
-    x = np.where(on_slab, p[at, 0] + np.cos(ang) * away, p[at, 0] + rng.uniform(-0.3, 0.3, n))
-    z = np.where(on_slab, p[at, 2] + np.sin(ang) * away, p[at, 2] + rng.uniform(-0.3, 0.3, n))
-    top = np.where(on_slab, slab_top, tops[at])
-    head = np.where(on_slab, ang + np.pi, rng.uniform(0.0, 2 * np.pi, n))
-    length = rng.uniform(0.5, 2.0, n)
-    d = np.stack([np.cos(head) * length, np.zeros(n), np.sin(head) * length], axis=1)
+    x, top, z, d = rates.walk_batch(np.random.default_rng(1), n, rec, WB._tops(rec, w.nbox))
     base = HW.walks(WB.stand(x, top, z, R, HH), d, R, HH, skin=WB.SKIN, max_slides=a.max_slides, snap_distance=0.3)
     casts = HW.first_casts(HW.head(base))
-    ct = up(casts)
+    ct = up(w, casts)
     ht = torch.empty((n, 32), dtype=torch.uint8, device=w.dev)
     rt = torch.empty((n, 112), dtype=torch.uint8, device=w.dev)
-    say(f"landed config-2 world: {C:,} colliders, {nb:,} bodies, after {a.steps} steps; GPU {torch.cuda.get_device_name(w.dev)}")
-    say(f"{n:,} walks (r {R}, hh {HH}, max_slides {a.max_slides}, snap 0.3; half on the slab beside a body, half on a body's top); median of {a.repeats} blocks of "
-        f"{a.reps} calls, interleaved (min .. max of the blocks); one box, one run")
+    log.say(f"landed {land.name} world: {C:,} colliders, {land.bodies:,} bodies, after {a.steps} steps; GPU {rates.gpu_name(w)}")
+    log.say(f"{n:,} walks (r {R}, hh {HH}, max_slides {a.max_slides}, snap 0.3; half on the slab beside a body, half on a body's top); median of {a.repeats} blocks of "
+            f"{a.reps} calls, interleaved (min .. max of the blocks); one box, one run")
     result = dict(colliders=C, steps=a.steps, walks=n, max_slides=a.max_slides, configs={})
-    pick = np.sort(np.random.default_rng(3).choice(n, size=258, replace=False))
+    pick = rates.spot(n)
     for name, step, limit in CONFIGS:
         wk = base.copy()
         wk["step_height"], wk["min_ground_up"] = step, MV.cos_deg(limit)
-        wt = up(wk)
-        t = interleaved(dict(walk=lambda: w.walk_records(wt, results=rt), capsulecast=lambda: w.capsulecast_records(ct, hits=ht)))
+        wt = up(w, wk)
+        t = rates.spreads(rates.interleaved(w, dict(walk=lambda: w.walk_records(wt, results=rt), capsulecast=lambda: w.capsulecast_records(ct, hits=ht)), a.reps, a.repeats))
         got = down(rt, E.WALK_RESULT)
         checked = 0
         if not a.no_check:
@@ -144,52 +70,50 @@ def main():
         s["start_overlap"] = float(((got["flags"] & E.NH_MOVE_START_OVERLAP) != 0).mean())
         mean_casts = float(got["casts"].mean())
         ratio = t["walk"]["ms"] / (mean_casts * t["capsulecast"]["ms"])
-        say(f"{name}:")
-        say(f"  nh_walk                               {fmt(t['walk'])} ms")
-        say(f"  nh_capsulecast, the first casts       {fmt(t['capsulecast'])} ms")
-        say(f"  shares: {({k: round(v, 4) for k, v in s.items()})}")
-        say(f"  casts per walk, mean                  {mean_casts:.3f}   (most in one walk {int(got['casts'].max())})")
-        say(f"  nh_walk / (mean casts x capsulecast)  {ratio:.2f}")
-        say(f"  {checked} walks equal the brute force byte for byte")
+        log.say(f"{name}:")
+        log.say(f"  nh_walk                               {fmt(t['walk'])} ms")
+        log.say(f"  nh_capsulecast, the first casts       {fmt(t['capsulecast'])} ms")
+        log.say(f"  shares: {({k: round(v, 4) for k, v in s.items()})}")
+        log.say(f"  casts per walk, mean                  {mean_casts:.3f}   (most in one walk {int(got['casts'].max())})")
+        log.say(f"  nh_walk / (mean casts x capsulecast)  {ratio:.2f}")
+        log.say(f"  {checked} walks equal the brute force byte for byte")
         result["configs"][name] = dict(walk=t["walk"], capsulecast=t["capsulecast"], shares=s, mean_casts=mean_casts, ratio=ratio, checked_against_brute_force=checked)
         if step > 0 and limit == 0:
             # the host loop of the REPLAY identity, on the whole batch: wall clock, its transfers included
             def move(m):
-                return down(w.move_records(up(m)), E.MOVE_RESULT)
+                return down(w.move_records(up(w, m)), E.MOVE_RESULT)
 
             def cast(c):
-                return down(w.capsulecast_records(up(c)), E.RAY_HIT)
+                return down(w.capsulecast_records(up(w, c)), E.RAY_HIT)
             HW.replay_walk(wk[:4096], move, cast)
-            stream.synchronize()
+            torch.cuda.current_stream(w.dev).synchronize()
             t0 = time.perf_counter()
             ref, calls = HW.replay_walk(wk, move, cast)
             host_ms = (time.perf_counter() - t0) * 1e3
             assert ref.tobytes() == got.tobytes(), "the host loop differs from nh_walk"
-            say(f"  the host loop of the REPLAY identity   {host_ms:.1f} ms wall clock, {calls} GPU calls with their uploads and downloads; the same bytes;"
-                f" nh_walk is {host_ms / t['walk']['ms']:.0f} times faster")
+            log.say(f"  the host loop of the REPLAY identity   {host_ms:.1f} ms wall clock, {calls} GPU calls with their uploads and downloads; the same bytes;"
+                    f" nh_walk is {host_ms / t['walk']['ms']:.0f} times faster")
             result["configs"][name]["host_loop"] = dict(ms=host_ms, calls=calls)
     if other is not None:
         mv = HW.head(base)
-        mt, mto, cto = up(mv), up(mv, other), up(casts, other)
+        mt, mto, cto = up(w, mv), up(other, mv), up(other, casts)
         r64 = {k: torch.empty((n, 64), dtype=torch.uint8, device=w.dev) for k in ("this", "other")}
         h32 = {k: torch.empty((n, 32), dtype=torch.uint8, device=w.dev) for k in ("this", "other")}
-        t = interleaved({"move this": lambda: w.move_records(mt, results=r64["this"]), "move other": lambda: other.move_records(mto, results=r64["other"]),
-                         "capsulecast this": lambda: w.capsulecast_records(ct, hits=h32["this"]),
-                         "capsulecast other": lambda: other.capsulecast_records(cto, hits=h32["other"])})
+        t = rates.spreads(rates.interleaved(w, {"move this": lambda: w.move_records(mt, results=r64["this"]), "move other": lambda: other.move_records(mto, results=r64["other"]),
+                                                "capsulecast this": lambda: w.capsulecast_records(ct, hits=h32["this"]),
+                                                "capsulecast other": lambda: other.capsulecast_records(cto, hits=h32["other"])}, a.reps, a.repeats))
         assert torch.equal(r64["this"], r64["other"]) and torch.equal(h32["this"], h32["other"]), "the two libraries differ"
-        say(f"filter off, this library beside {os.path.basename(OTHER)} (the same bytes from both):")
+        log.say(f"filter off, this library beside {os.path.basename(OTHER)} (the same bytes from both):")
         for call in ("move", "capsulecast"):
             ratio = t[call + " this"]["ms"] / t[call + " other"]["ms"]
-            say(f"  nh_{call:<12} this {fmt(t[call + ' this'])} ms   other {fmt(t[call + ' other'])} ms   this / other {ratio:.3f} (medians)")
+            log.say(f"  nh_{call:<12} this {fmt(t[call + ' this'])} ms   other {fmt(t[call + ' other'])} ms   this / other {ratio:.3f} (medians)")
             result[call + "_beside_other"] = dict(this=t[call + " this"], other=t[call + " other"], ratio=ratio)
         other.close()
     else:
-        say("filter off, this library beside another build: no NUDGE_HIP_LIBRARY given, not measured")
-    say()
-    say(json.dumps(result))
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
+        log.say("filter off, this library beside another build: no NUDGE_HIP_LIBRARY given, not measured")
+    log.say()
+    log.say(json.dumps(result))
+    log.write(a.out)
     w.close()
 
 
