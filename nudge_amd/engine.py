@@ -479,7 +479,8 @@ class World:
 
     def __init__(self, scene, device=0, max_contacts=None, arena_bytes=None, flags=NH_FLAG_SYNC_COUNTS, tag_bits=None, capacity=None, max_pairs=None):
         """`capacity` = dict(bodies=, boxes=, spheres=): allocate room for more records than the scene holds (the
-        partitioned world appends ghost / migrated bodies, nudge_amd/partition.py); counts then change via set_counts().
+        partitioned world appends ghost / migrated bodies: nh_partition_unpack_ghosts behind partition.HipPartition, which sets the counts itself;
+        partition.TorchPartition rewrites the arrays and calls set_counts()).
         `max_pairs`: capacity of the broadphase pair buffer (nh_set_pair_capacity); default max_contacts / 2 + 1024."""
         import torch
         if not torch.cuda.is_available():

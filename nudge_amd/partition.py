@@ -51,19 +51,25 @@ from where it started than the static colliders a rank keeps allow (`split_scene
 A dynamic body carries up to MAX_COLLIDERS colliders (compound bodies: nudge.cpp:3023-3025, 3058-3060), any local transforms; they travel with it in its
 record, boxes first, then spheres.  Static colliders are unrestricted.
 
-WHERE THE WORK IS DONE.  On the HIP engine every operation below -- migration, ghost listing and installation, the collider rebuild, the per-step records,
-the choice of a new cut -- is a call into the C ABI (include/nudge_hip.h "multi-GPU": nh_partition_*, kernels with device-side counts in
-nudge_amd/csrc/nh_partition.hip); this class then only carries message buffers between the library and the transport, exactly like the C++ host
-examples/partition_rccl.cpp.  The torch implementation of the same operations further down is what the CPU tests run (the compiled reference as the
-engine, gloo as the transport) and what the GPU tests check the kernels against (`Partition(..., force_torch=True)`).
+WHERE THE WORK IS DONE.  `Partition(...)` makes one of two classes that share the arguments, the counters and the step in phases (_PartitionBase).  On the HIP
+engine it is a `HipPartition`: every operation -- migration, ghost listing and installation, the collider rebuild, the per-step records, the choice of a new cut --
+is a call into the C ABI (include/nudge_hip.h "multi-GPU": nh_partition_*, kernels with device-side counts in nudge_amd/csrc/nh_partition.hip), and the class only
+carries message buffers between the library and the transport, exactly like the C++ host examples/partition_rccl.cpp.  `TorchPartition` is the torch implementation
+of the same operations on any engine: what the CPU tests run (the compiled reference as the engine, gloo as the transport) and what the GPU tests check the kernels
+against (`Partition(..., force_torch=True)`).
 
-Transport is pluggable: `LocalCluster` moves tensors between partitions living in one process (tests, one GPU),
-`DistCluster` uses torch.distributed point-to-point ops (one process per GPU).  The same `Partition` code runs in both.
+Transport is pluggable.  The step protocol -- refresh phases, per-step exchange, per-iteration loop -- is written once (_Cluster) over two primitives, one round of
+messages and one vote: `LocalCluster` moves tensors between partitions living in one process (tests, one GPU), `DistCluster` uses torch.distributed point-to-point
+ops and a one-word all-reduce (one process per GPU).  The same partition code runs in both.
 """
 from __future__ import annotations
 
+import ctypes as C
+import time
+
 import numpy as np
 
+from . import engine as E
 from . import scenes as S
 
 MAX_COLLIDERS = 4                                 # colliders a dynamic body may carry across ranks (include/nudge_hip.h: NH_PARTITION_MAX_COLLIDERS)
@@ -169,12 +175,12 @@ def split_scene(scene, cuts, rank, slack=0.15, min_extra=4096, static_margin=Non
     return local, info
 
 
-class Partition:
-    """One rank's share of the world.  `engine` exposes the caller-owned arrays as [capacity, record] uint8 torch
-    tensors (`records(name, bytes)`), `set_counts(bodies, boxes, spheres)`, `step(n)` and `params` -- nudge_amd.engine.World
-    does; the CPU tests plug the oracle in behind the same four members."""
+class _PartitionBase:
+    """What does not depend on who does the work: the arguments and their checks, the engine's record tensors, the counters, the re-balancing rule, the step in phases,
+    the 8-byte scalar message and the 64-byte step record.  A subclass brings the refresh_* / step_* / delta_* / momentum_* pack and unpack methods, delta_mark, and what
+    the shared messages are made from: _choose_cut(d), _top_speed(), _peer_speeds(peers), _nothing_would_change()."""
 
-    def __init__(self, engine, info, epoch=16, speed_floor=1.0, per_iteration=False, rebalance=True, balance_tolerance=0.05, force_torch=False, single_owner=False):
+    def __init__(self, engine, info, epoch, speed_floor, per_iteration, rebalance, balance_tolerance, single_owner):
         import torch
         self.per_iteration = per_iteration
         # one owner per contact that crosses a cut (module docstring): needs the per-iteration exchange, and an engine that can drop the contacts it does not own
@@ -183,8 +189,7 @@ class Partition:
         if single_owner and not hasattr(engine, "set_first_ghost"):
             raise ValueError("single_owner=True needs an engine with set_first_ghost()")
         self.single_owner = single_owner
-        self._ghost_ref = None
-        self.hip = None                       # the nh_partition handle when the engine is the HIP world (set at the end of __init__)
+        self.hip = None                       # the nh_partition handle (HipPartition only)
         # per-iteration exchange = one apply call per sweep with ghost momentum written in between: the engine must keep its solver states and
         # re-read momentum every call, which NH_FLAG_SINGLE_APPLY (4) / NH_FLAG_FUSED_STEP (8) promise away
         if per_iteration and (getattr(engine, "flags", 0) & (4 | 8)):
@@ -195,18 +200,349 @@ class Partition:
         self._nb_count = {}
         self.torch = torch
         self.e = engine
+        # the engine's optional members, probed once: the HIP kernels for the per-step records, the stream, the per-step book-keeping
+        self._halo_pack, self._halo_unpack = getattr(engine, "halo_pack", None), getattr(engine, "halo_unpack", None)
+        self._synchronize, self._step_done = getattr(engine, "synchronize", None), getattr(engine, "step_done", None)
         self.rank, self.ranks = info["rank"], info["ranks"]
         self.lo, self.hi = info["lo"], info["hi"]
         self.n_owned = info["n_owned"]
         self.n_static_box, self.n_static_sph = info["n_static_box"], info["n_static_sph"]
         self.max_reach = info["max_reach"]
         self.epoch, self.speed_floor = epoch, speed_floor
+        self.quiet_refresh = True             # (switch for A/B and tests: False = every epoch boundary is a refresh, as in rounds 3-5)
         self.dt = float(engine.params["time_step"])
         self.gravity = abs(float(engine.params["gravity"]))
         r = engine.records
         self.bt, self.bp, self.bm, self.bi = r("bt", 32), r("bp", 16), r("bm", 32), r("bi", 1)
         self.xt, self.xd, self.xx = r("xt", 4), r("xd", 16), r("xx", 32)
         self.st, self.sd, self.sx = r("st", 4), r("sd", 4), r("sx", 32)
+        self.ghost_in = {-1: 0, +1: 0}             # ghost records received from the left / right neighbour
+        self.steps = 0
+        # steps_total: every step ever taken (`steps` is the epoch clock, which bench.py rewinds before each timed block -- it cannot be the divisor of step_bytes)
+        self.stats = dict(refreshes=0, migrated_out=0, migrated_in=0, ghosts=0, late_bodies=0, step_bytes=0, refresh_bytes=0, cut_moves=0, steps_total=0)
+
+    def close(self):
+        pass
+
+    # ---- helpers -------------------------------------------------------------------------------------------------
+    def neighbours(self):
+        return [d for d in (-1, +1) if 0 <= self.rank + d < self.ranks]
+
+    def _scalar(self, value, dtype):
+        """The 8-byte message: one int64 / float64 as a [1, 8] uint8 record."""
+        t = self.torch
+        return t.tensor([value], dtype=dtype, device=self.bt.device).view(t.uint8).reshape(1, 8)
+
+    def _scalars(self, incoming, dtype):
+        """... and what the neighbours sent in that form: {d: value} for every neighbour whose message is not empty."""
+        return {d: incoming[d].reshape(-1).view(dtype)[0].item() for d in self.neighbours() if incoming.get(d) is not None and incoming[d].numel()}
+
+    # the 64-byte per-step record (nh_halo_pack's): position 12, rotation 16, momentum 32, idle 1 + pad -- the engine's HIP kernels when it has them, else torch ops
+    def _step_records(self, idx, idx32=None):
+        """Per-step records [len, 64] of the given body slots."""
+        if self._halo_pack is not None:
+            return self._halo_pack(idx32 if idx32 is not None else idx.to(self.torch.int32))
+        t = self.torch
+        pad = t.zeros((len(idx), 4), dtype=t.uint8, device=idx.device)
+        pad[:, 0] = self.bi[idx, 0]
+        return t.cat([self.bt[idx][:, :12], self.bt[idx][:, 16:], self.bm[idx], pad], dim=1)
+
+    def _step_install(self, at, rec):
+        """... written over the bodies in slots [at, at + len): the same bodies as before (the lists only change at a refresh, which announces itself: set_counts)."""
+        if self._halo_unpack is not None:
+            self._halo_unpack(at, rec.contiguous(), same_bodies=True)
+            return
+        s = slice(at, at + rec.shape[0])
+        self.bt[s, :12] = rec[:, :12]                 # position
+        self.bt[s, 16:] = rec[:, 12:28]               # rotation (the `body` field keeps the global id)
+        self.bm[s] = rec[:, 28:60]
+        self.bi[s, 0] = rec[:, 60]
+
+    # ---- refresh: phase 0 (re-balancing the cuts) ------------------------------------------------------------------
+    def balance_pack_counts(self):
+        """One 8-byte message per neighbour: how many bodies I own."""
+        return {d: self._scalar(self.n_owned, self.torch.int64) for d in self.neighbours()}
+
+    def _moves(self, d):
+        """Does the cut towards neighbour d move this refresh, and who picks the new place?  Both sides evaluate the same rule on the same two counts."""
+        if not self.rebalance or d not in self._nb_count:
+            return None
+        mine, theirs = self.n_owned, self._nb_count[d]
+        if abs(mine - theirs) <= self.balance_tolerance * max(1, mine + theirs):
+            return None
+        return "me" if mine > theirs else "neighbour"
+
+    def balance_unpack_counts(self, incoming):
+        self._nb_count = self._scalars(incoming, self.torch.int64)
+
+    def balance_expected(self):
+        """Rows of the second message I expect from each neighbour (1 when the neighbour is the heavier side of a cut that moves)."""
+        return {d: (1 if self._moves(d) == "neighbour" else 0) for d in self.neighbours()}
+
+    def balance_pack_cuts(self):
+        """The heavier side of an unbalanced cut picks the x that hands half the difference -- at most 5 % of its bodies -- to the neighbour (_choose_cut)."""
+        t = self.torch
+        # (the neighbour expects exactly one row from the side that picks, whatever comes out)
+        return {d: (self._scalar(self._choose_cut(d), t.float64) if self._moves(d) == "me" else t.zeros((0, 8), dtype=t.uint8, device=self.bt.device)) for d in self.neighbours()}
+
+    def balance_unpack_cuts(self, incoming):
+        for d, cut in self._scalars(incoming, self.torch.float64).items():
+            self._move_cut(d, cut)
+
+    def _move_cut(self, d, cut):
+        if cut != (self.lo if d < 0 else self.hi):
+            if d < 0: self.lo = cut
+            else: self.hi = cut
+            self.stats["cut_moves"] += 1
+
+    # ---- refresh: top speeds across the cuts ---------------------------------------------------------------------
+    # A cut's ghost margin is reach + 2 x drift: the two bodies of a cross-cut pair approach each other from BOTH sides, so the drift must come from the top speed on
+    # both sides of that cut -- mine (now: before this refresh's migration) and the neighbour's.  One 8-byte message per neighbour, like the body counts.
+    # (Round-4 advisor finding: with a rank's own top speed only, a fast body owned by the neighbour reached slow bodies here that this rank had never listed for it and
+    # tunnelled through them until the next refresh.  tests/test_partition_cpu.py::test_a_fast_body_from_the_neighbour_finds_its_ghosts)
+    def speed_pack(self):
+        v = self._top_speed()
+        return {d: self._scalar(v, self.torch.float64) for d in self.neighbours()}
+
+    def speed_unpack(self, incoming):
+        self._peer_speeds(self._scalars(incoming, self.torch.float64))
+
+    # ---- refresh: is it needed at all?  (round 6) ---------------------------------------------------------------
+    def refresh_is_quiet(self):
+        """Would a refresh change nothing on this rank?  No owned body beyond a cut, and the bodies within reach of a cut -- at the speeds just exchanged (speed_pack /
+        speed_unpack first; nothing is consumed) -- exactly the ones listed for the neighbours at the last refresh, in the same order.  The clusters skip the refresh only
+        when EVERY rank says so: the epoch boundary is then a per-step exchange like any other sub-step, and a world at rest stays in its still steps."""
+        if not self.quiet_refresh or self.steps == 0 or self.per_iteration:
+            return False
+        return self._nothing_would_change()
+
+    # ---- every step ---------------------------------------------------------------------------------------------------
+    def local_step(self):
+        self.e.step(1)
+        self.steps += 1
+        self.stats["steps_total"] += 1
+
+    # ---- per-iteration mode: the step in phases, ghost momentum refreshed after every sweep ---------------------------
+    def step_begin(self):
+        e = self.e
+        if self.single_owner:
+            e.set_first_ghost(self.n_owned + 1)
+        e.collide(); e.gravity(); e.read_cache()
+        if self.single_owner:
+            self.delta_mark()                     # (the warm start inside setup() already moves the ghosts of the contacts owned here)
+        e.setup()
+        if self.single_owner and self._synchronize is not None:
+            self._synchronize()                   # (the HIP engine may defer the warm start into the first apply call, header note 7: it has to be in the momentum the deltas are taken from)
+
+    def sweep(self):
+        self.e.apply(1)
+
+    def step_end(self):
+        e = self.e
+        e.update(); e.write_cache(); e.advance()
+        if self._step_done is not None:
+            self._step_done()
+        self.steps += 1
+        self.stats["steps_total"] += 1
+
+    def iterations(self):
+        return int(self.e.params["iterations"])
+
+    def needs_refresh(self):
+        return self.steps % self.epoch == 0
+
+    # ---- results ------------------------------------------------------------------------------------------------------------
+    def owned_state(self):
+        """(global ids, transforms, momentum, idle) of the owned bodies, as numpy arrays."""
+        n = self.n_owned + 1
+        if self._synchronize is not None:
+            self._synchronize()
+        bt = np.frombuffer(self.bt[1:n].cpu().numpy().tobytes(), dtype=S.TRANSFORM).copy()
+        bm = np.frombuffer(self.bm[1:n].cpu().numpy().tobytes(), dtype=S.MOMENTUM).copy()
+        bi = self.bi[1:n, 0].cpu().numpy().copy()
+        return bt["body"].astype(np.int64), bt, bm, bi
+
+
+class HipPartition(_PartitionBase):
+    """The HIP engine: every operation is ONE call into the C ABI (include/nudge_hip.h "multi-GPU"); this class holds the handle and the message buffers and carries
+    them between the library and the transport, exactly like examples/partition_rccl.cpp.  The ghost lists and the body-parallel collider description live in the library."""
+
+    def __init__(self, engine, info, epoch, speed_floor, per_iteration, rebalance, balance_tolerance, single_owner):
+        super().__init__(engine, info, epoch, speed_floor, per_iteration, rebalance, balance_tolerance, single_owner)
+        t, e = self.torch, self.e
+        cap = e.capacity
+        inf = float("inf")
+        cfg = E.PartitionConfig(self.rank, self.ranks, self.lo if self.lo > -inf else -1e308 * 10, self.hi if self.hi < inf else 1e308 * 10, self.n_owned, self.n_static_box, self.n_static_sph,
+                                cap["bodies"], cap["boxes"], cap["spheres"], self.epoch, self.dt, self.gravity, self.speed_floor, self.max_reach,
+                                self.cut_slack if self.cut_slack < inf else 1e308 * 10)
+        h = C.c_void_p()
+        E._check(e.L, e.L.nh_partition_create(C.byref(h), e.ctx, C.byref(cfg), C.byref(e.bodies), C.byref(e.colliders)), "nh_partition_create")
+        self.hip = h
+        dev = self.bt.device
+        self._msg_cap = max(4096, cap["bodies"] // 4)
+        self._fullbuf = {d: t.empty((self._msg_cap, FULL_BYTES), dtype=t.uint8, device=dev) for d in (-1, +1)}      # migrants / ghosts out
+        self._stepbuf = {d: t.empty((0, STEP_BYTES), dtype=t.uint8, device=dev) for d in (-1, +1)}                  # per-step records out, sized at every refresh
+        self._ghost_out_total = 0             # how many of my bodies are listed for the two neighbours together
+        self._iter_keep = None                # the last per-iteration message buffers (_call_pair)
+
+    def close(self):
+        if self.hip is not None:
+            self.e.L.nh_partition_destroy(self.hip)
+            self.hip = None
+
+    def _call(self, name, *args):
+        E._check(self.e.L, getattr(self.e.L, name)(self.hip, *args), name)
+
+    def _hip_info(self):
+        i = E.PartitionInfo()
+        self._call("nh_partition_info", C.byref(i))
+        self.n_owned = int(i.n_owned)
+        self.lo, self.hi = (float(i.lo) if self.rank > 0 else self.lo), (float(i.hi) if self.rank + 1 < self.ranks else self.hi)
+        self.stats.update(refreshes=int(i.refreshes), migrated_out=int(i.migrated_out), migrated_in=int(i.migrated_in), cut_moves=int(i.cut_moves),
+                          ghosts=int(i.ghost_in[0]) + int(i.ghost_in[1]))
+        return i
+
+    def _ghost_out_n(self, d):
+        """How many of my bodies are listed for neighbour d (the lists are on the device: nh_partition_info)."""
+        return int(self._hip_info().ghost_out[0 if d < 0 else 1])
+
+    def _pack_full(self, name):
+        counts = (C.c_uint32 * 2)()
+        ptr = lambda d: C.c_void_p(self._fullbuf[d].data_ptr()) if d in self.neighbours() else C.c_void_p(0)      # noqa: E731
+        self._call(name, C.byref(self.e.bodies), ptr(-1), ptr(+1), self._msg_cap, C.byref(counts))
+        return {d: self._fullbuf[d][:int(counts[0 if d < 0 else 1])] for d in self.neighbours()}
+
+    def _unpack_full_args(self, incoming):
+        args = []
+        for d in (-1, +1):
+            rec = incoming.get(d) if d in self.neighbours() else None
+            m = 0 if rec is None else int(rec.shape[0])
+            if m:
+                rec = rec.contiguous()
+                incoming[d] = rec              # (keeps the buffer alive until the kernels have been enqueued behind it)
+            args += [C.c_void_p(rec.data_ptr() if m else 0), m]
+        return args
+
+    # ---- refresh ------------------------------------------------------------------------------------------------------------
+    def _choose_cut(self, d):
+        cut = C.c_double(0.0)
+        self._call("nh_partition_choose_cut", C.byref(self.e.bodies), d, int(self._nb_count[d]), C.byref(cut))
+        if d < 0: self.lo = cut.value
+        else: self.hi = cut.value
+        self._hip_info()
+        return cut.value
+
+    def _move_cut(self, d, cut):
+        self._call("nh_partition_set_cut", d, cut)
+        super()._move_cut(d, cut)
+
+    def _top_speed(self):
+        v = C.c_double(0.0)
+        self._call("nh_partition_top_speed", C.byref(self.e.bodies), C.byref(v))
+        return float(v.value)
+
+    def _peer_speeds(self, peers):
+        self._call("nh_partition_set_peer_speeds", peers.get(-1, 0.0), peers.get(+1, 0.0))
+
+    def _nothing_would_change(self):
+        q = C.c_int(0)
+        self._call("nh_partition_refresh_is_quiet", C.byref(self.e.bodies), C.byref(q))
+        return bool(q.value)
+
+    def refresh_pack_migrants(self):
+        return self._pack_full("nh_partition_pack_migrants")
+
+    def refresh_unpack_migrants(self, incoming):
+        self._call("nh_partition_unpack_migrants", C.byref(self.e.bodies), *self._unpack_full_args(incoming))
+        self._hip_info()
+
+    def refresh_pack_ghosts(self):
+        out = self._pack_full("nh_partition_pack_ghosts")
+        t = self.torch
+        for d in self.neighbours():
+            self._stepbuf[d] = t.empty((out[d].shape[0], STEP_BYTES), dtype=t.uint8, device=self.bt.device)
+        self._ghost_out_total = sum(int(out[d].shape[0]) for d in self.neighbours())
+        return out
+
+    def refresh_unpack_ghosts(self, incoming):
+        e = self.e
+        self._call("nh_partition_unpack_ghosts", C.byref(e.bodies), C.byref(e.colliders), *self._unpack_full_args(incoming))
+        i = self._hip_info()
+        self.ghost_in = {-1: int(i.ghost_in[0]), +1: int(i.ghost_in[1])}
+        e.nb, e.nbox, e.nsph = int(i.n_bodies), int(i.n_boxes), int(i.n_spheres)         # (the C call has set the counts of the engine's structs and told the context)
+
+    # ---- every step ---------------------------------------------------------------------------------------------------
+    def step_pack(self):
+        ptr = lambda d: C.c_void_p(self._stepbuf[d].data_ptr()) if d in self.neighbours() and self._stepbuf[d].shape[0] else C.c_void_p(0)      # noqa: E731
+        self._call("nh_partition_pack_step", C.byref(self.e.bodies), ptr(-1), ptr(+1))
+        out = {d: self._stepbuf[d] for d in self.neighbours()}
+        self.stats["step_bytes"] += sum(int(r.numel()) for r in out.values())
+        return out
+
+    def step_unpack(self, incoming):
+        recs = {d: (incoming[d].contiguous() if self.ghost_in[d] else None) for d in (-1, +1)}
+        ptr = lambda d: C.c_void_p(recs[d].data_ptr()) if recs[d] is not None else C.c_void_p(0)      # noqa: E731
+        self._call("nh_partition_unpack_step", C.byref(self.e.bodies), ptr(-1), ptr(+1))
+
+    def exchange_step(self):
+        """Pack, send / receive, unpack of the per-step records in ONE library call, over the library's own transport (nh_partition_set_transport)."""
+        self._call("nh_partition_exchange_step", C.byref(self.e.bodies))
+        self.stats["step_bytes"] += STEP_BYTES * self._ghost_out_total
+
+    def library_steps(self, n, exchange_first, loopback_records=0):
+        """n sub-steps in ONE library call (nh_partition_step): per-step halo exchanges enqueued by the library over its own transport between them.  Must not reach past
+        the next refresh (the caller's business)."""
+        self.e.partition_step(self.hip, n, exchange_first, loopback_records)
+        self.stats["step_bytes"] += STEP_BYTES * self._ghost_out_total * (n if exchange_first else n - 1)
+        self.steps += n
+        self.stats["steps_total"] += n
+
+    # ---- per-iteration mode (round 5: nh_partition_mark_ghosts / pack_deltas / unpack_deltas / pack_momentum / unpack_momentum) ----------------------------------
+    def _call_pair(self, name, sizes, incoming=None):
+        """One of the four pack / unpack entry points: `sizes` records of 32 bytes per side; returns {d: tensor} for a pack."""
+        t = self.torch
+        dev = self.bt.device
+        bufs = {}
+        for d in (-1, +1):
+            if incoming is None:
+                bufs[d] = t.empty((sizes[d], 32), dtype=t.uint8, device=dev) if d in self.neighbours() else None
+            else:
+                r = incoming.get(d) if d in self.neighbours() else None
+                bufs[d] = r.contiguous().to(dev) if (r is not None and sizes[d]) else None
+                if bufs[d] is not None:
+                    assert bufs[d].numel() == 32 * sizes[d], (name, d, bufs[d].shape, sizes[d])
+        ptr = lambda d: C.c_void_p(bufs[d].data_ptr() if (bufs[d] is not None and bufs[d].numel()) else 0)      # noqa: E731
+        self._call(name, C.byref(self.e.bodies), ptr(-1), ptr(+1))
+        self._iter_keep = bufs                   # (the kernels are enqueued: keep the message tensors alive until the next call)
+        if incoming is not None:
+            return None
+        out = {d: b for d, b in bufs.items() if b is not None}
+        self.stats["step_bytes"] += sum(int(v.numel()) for v in out.values())
+        return out
+
+    def delta_mark(self):
+        self._call("nh_partition_mark_ghosts", C.byref(self.e.bodies))
+
+    def delta_pack(self):
+        return self._call_pair("nh_partition_pack_deltas", self.ghost_in)
+
+    def delta_unpack(self, incoming):
+        self._call_pair("nh_partition_unpack_deltas", {d: self._ghost_out_n(d) for d in (-1, +1)}, incoming)
+
+    def momentum_pack(self):
+        return self._call_pair("nh_partition_pack_momentum", {d: self._ghost_out_n(d) for d in (-1, +1)})
+
+    def momentum_unpack(self, incoming):
+        self._call_pair("nh_partition_unpack_momentum", self.ghost_in, incoming)
+
+
+class TorchPartition(_PartitionBase):
+    """The same operations in torch, on any engine: what the CPU tests run (the compiled reference as the engine) and the independent check of the kernels on the GPU
+    (`Partition(..., force_torch=True)`).  It keeps the body-parallel collider description and the ghost lists itself."""
+
+    def __init__(self, engine, info, epoch, speed_floor, per_iteration, rebalance, balance_tolerance, single_owner):
+        super().__init__(engine, info, epoch, speed_floor, per_iteration, rebalance, balance_tolerance, single_owner)
+        torch = self.torch
         dev = self.bt.device
         cap = self.bt.shape[0]
         n = self.n_owned + 1
@@ -227,82 +563,25 @@ class Partition:
         self.nsp[:n] = torch.from_numpy(info["nsp"].astype(np.uint8).copy()).to(dev)
         self.reach = torch.zeros(cap, dtype=torch.float32, device=dev)
         self.reach[:n] = torch.from_numpy(info["reach"].copy()).to(dev)
+        self.n_bodies = n                          # owned + ghosts (+ slot 0)
         self.ghost_out = {-1: None, +1: None}      # owned slots sent to the left / right neighbour every step
         self.ghost_out32 = {-1: None, +1: None}
-        self.ghost_in = {-1: 0, +1: 0}             # ghost records received from the left / right neighbour
-        self.steps = 0
-        # steps_total: every step ever taken (`steps` is the epoch clock, which bench.py rewinds before each timed block -- it cannot be the divisor of step_bytes)
-        self.stats = dict(refreshes=0, migrated_out=0, migrated_in=0, ghosts=0, late_bodies=0, step_bytes=0, refresh_bytes=0, cut_moves=0, steps_total=0)
-        # (round 5: the per-iteration exchange of single ownership is behind the C ABI too -- nh_partition_mark_ghosts / pack_deltas / ... -- so the HIP engine takes the
-        # C-ABI path in every mode; force_torch=True keeps the torch implementation, the independent check)
-        self.force_torch = force_torch
-        if not force_torch and hasattr(engine, "L") and hasattr(engine, "ctx") and hasattr(engine.L, "nh_partition_create"):
-            self._hip_create(info)
-
-    # ---- the HIP engine: every operation is a C-ABI call (include/nudge_hip.h "multi-GPU"); this class moves message buffers ---------------------------------
-    def _hip_create(self, info):
-        import ctypes as C
-        from . import engine as E
-        t, e = self.torch, self.e
-        cap = e.capacity
-        inf = float("inf")
-        cfg = E.PartitionConfig(self.rank, self.ranks, self.lo if self.lo > -inf else -1e308 * 10, self.hi if self.hi < inf else 1e308 * 10, self.n_owned, self.n_static_box, self.n_static_sph,
-                                cap["bodies"], cap["boxes"], cap["spheres"], self.epoch, self.dt, self.gravity, self.speed_floor, self.max_reach,
-                                self.cut_slack if self.cut_slack < inf else 1e308 * 10)
-        h = C.c_void_p()
-        E._check(e.L, e.L.nh_partition_create(C.byref(h), e.ctx, C.byref(cfg), C.byref(e.bodies), C.byref(e.colliders)), "nh_partition_create")
-        self.hip = h
-        dev = self.bt.device
-        self._msg_cap = max(4096, cap["bodies"] // 4)
-        self._full = {d: t.empty((self._msg_cap, FULL_BYTES), dtype=t.uint8, device=dev) for d in (-1, +1)}
-        self._stepbuf = {d: t.empty((0, STEP_BYTES), dtype=t.uint8, device=dev) for d in (-1, +1)}
-
-    def _hip_info(self):
-        import ctypes as C
-        from . import engine as E
-        i = E.PartitionInfo()
-        E._check(self.e.L, self.e.L.nh_partition_info(self.hip, C.byref(i)), "nh_partition_info")
-        self.n_owned = int(i.n_owned)
-        self.lo, self.hi = (float(i.lo) if self.rank > 0 else self.lo), (float(i.hi) if self.rank + 1 < self.ranks else self.hi)
-        self.stats.update(refreshes=int(i.refreshes), migrated_out=int(i.migrated_out), migrated_in=int(i.migrated_in), cut_moves=int(i.cut_moves),
-                          ghosts=int(i.ghost_in[0]) + int(i.ghost_in[1]))
-        return i
-
-    def _hip_pack(self, fn, what):
-        import ctypes as C
-        from . import engine as E
-        e = self.e
-        counts = (C.c_uint32 * 2)()
-        ptr = lambda d: C.c_void_p(self._full[d].data_ptr()) if d in self.neighbours() else C.c_void_p(0)
-        E._check(e.L, fn(self.hip, C.byref(e.bodies), ptr(-1), ptr(+1), self._msg_cap, C.byref(counts)), what)
-        return {d: self._full[d][:int(counts[0 if d < 0 else 1])] for d in self.neighbours()}
-
-    def _hip_unpack_args(self, incoming):
-        import ctypes as C
-        args = []
-        for d in (-1, +1):
-            rec = incoming.get(d) if d in self.neighbours() else None
-            m = 0 if rec is None else int(rec.shape[0])
-            if m:
-                rec = rec.contiguous()
-                incoming[d] = rec              # (keeps the buffer alive until the kernels have been enqueued behind it)
-            args += [C.c_void_p(rec.data_ptr() if m else 0), m]
-        return args
-
-    def close(self):
-        if self.hip is not None:
-            self.e.L.nh_partition_destroy(self.hip)
-            self.hip = None
+        self._speed_pre, self._peer_speed = 0.0, {}     # top speeds on my side / the neighbours' side of the cuts, from speed_pack to the next refresh_pack_ghosts
+        self._leave = None                         # who migrates away, from refresh_pack_migrants to refresh_unpack_migrants
+        self._ghost_ref = None                     # the ghosts' momentum at the last delta_mark()
 
     # ---- helpers -------------------------------------------------------------------------------------------------
-    def neighbours(self):
-        return [d for d in (-1, +1) if 0 <= self.rank + d < self.ranks]
-
     def _f32(self, rec):
         return rec.view(self.torch.float32)
 
-    def _x(self, n):
-        return self._f32(self.bt[:n])[:, 0]
+    def _owned_x(self):
+        """(x of slots [0, n_owned], the mask of the owned ones: everything but slot 0)"""
+        x = self._f32(self.bt[:self.n_owned + 1])[:, 0]
+        return x, self.torch.arange(self.n_owned + 1, device=x.device) > 0
+
+    def _ghost_out_n(self, d):
+        """How many of my bodies are listed for neighbour d."""
+        return int(len(self.ghost_out[d])) if self.ghost_out.get(d) is not None else 0
 
     def _full(self, idx):
         """Full records of the given body slots: [len, FULL_BYTES] uint8 (the layout of nh_FullRecord, nudge_amd/csrc/nh_partition.hip)."""
@@ -345,167 +624,70 @@ class Partition:
             reach = t.where(c < nb + ns, t.maximum(reach, (off + ext) * 1.0001), reach)
         self.reach[s] = reach
 
-    def _step_records(self, idx, idx32=None):
-        """Per-step records [len, 64] of the given body slots: the engine's HIP kernel when it has one (nh_halo_pack), else torch ops."""
-        if hasattr(self.e, "halo_pack"):
-            return self.e.halo_pack(idx32 if idx32 is not None else idx.to(self.torch.int32))
+    # ---- refresh ------------------------------------------------------------------------------------------------------------
+    def _choose_cut(self, d):
         t = self.torch
-        pad = t.zeros((len(idx), 4), dtype=t.uint8, device=idx.device)
-        pad[:, 0] = self.bi[idx, 0]
-        return t.cat([self.bt[idx][:, :12], self.bt[idx][:, 16:], self.bm[idx], pad], dim=1)
-
-    # ---- refresh: phase 0 (re-balancing the cuts) ------------------------------------------------------------------
-    def balance_pack_counts(self):
-        """One 8-byte message per neighbour: how many bodies I own."""
-        t = self.torch
-        dev = self.bt.device
-        return {d: t.tensor([self.n_owned], dtype=t.int64, device=dev).view(t.uint8).reshape(1, 8) for d in self.neighbours()}
-
-    def _moves(self, d):
-        """Does the cut towards neighbour d move this refresh, and who picks the new place?  Both sides evaluate the same rule on the same two counts."""
-        if not self.rebalance or d not in self._nb_count:
-            return None
-        mine, theirs = self.n_owned, self._nb_count[d]
-        if abs(mine - theirs) <= self.balance_tolerance * max(1, mine + theirs):
-            return None
-        return "me" if mine > theirs else "neighbour"
-
-    def balance_unpack_counts(self, incoming):
-        t = self.torch
-        self._nb_count = {d: int(incoming[d].reshape(-1).view(t.int64)[0].item()) for d in self.neighbours() if d in incoming and incoming[d].numel()}
-
-    def balance_expected(self):
-        """Rows of the second message I expect from each neighbour (1 when the neighbour is the heavier side of a cut that moves)."""
-        return {d: (1 if self._moves(d) == "neighbour" else 0) for d in self.neighbours()}
-
-    def balance_pack_cuts(self):
-        """The heavier side of an unbalanced cut picks the x that hands half the difference -- at most 5 % of its bodies -- to the neighbour."""
-        t = self.torch
-        dev = self.bt.device
-        out = {}
         n = self.n_owned
-        x = self._x(n + 1)[1:] if n else None
-        for d in self.neighbours():
-            rec = t.zeros((0, 8), dtype=t.uint8, device=dev)
-            if self._moves(d) == "me" and self.hip is not None:
-                import ctypes as C
-                from . import engine as E
-                cut = C.c_double(0.0)
-                E._check(self.e.L, self.e.L.nh_partition_choose_cut(self.hip, C.byref(self.e.bodies), d, int(self._nb_count[d]), C.byref(cut)), "nh_partition_choose_cut")
-                if d < 0: self.lo = cut.value
-                else: self.hi = cut.value
-                self._hip_info()
-                rec = t.tensor([cut.value], dtype=t.float64, device=dev).view(t.uint8).reshape(1, 8)
-            elif self._moves(d) == "me":                     # (the neighbour expects exactly one row then, whatever comes out)
-                old = self.lo if d < 0 else self.hi
+        old = self.lo if d < 0 else self.hi
+        cut = old
+        if n > 1:
+            x = self._owned_x()[0][1:]
+            k = max(1, min((n - self._nb_count[d]) // 2, int(0.05 * n), n - 1))
+            if d < 0:          # bodies with x < new lo leave: between the k-th and the (k+1)-th smallest x
+                a, b = t.kthvalue(x, k).values, t.kthvalue(x, k + 1).values
+            else:              # bodies with x >= new hi leave: between the k-th and the (k+1)-th largest x
+                a, b = t.kthvalue(x, n - k + 1).values, t.kthvalue(x, n - k).values
+            cut = 0.5 * (float(a) + float(b))
+            # never further from where the cut started than the static colliders this rank kept allow
+            cut = min(max(cut, self.cut0[d] - self.cut_slack), self.cut0[d] + self.cut_slack)
+            if not np.isfinite(cut):
                 cut = old
-                if n > 1:
-                    k = max(1, min((n - self._nb_count[d]) // 2, int(0.05 * n), n - 1))
-                    if d < 0:          # bodies with x < new lo leave: between the k-th and the (k+1)-th smallest x
-                        a, b = t.kthvalue(x, k).values, t.kthvalue(x, k + 1).values
-                    else:              # bodies with x >= new hi leave: between the k-th and the (k+1)-th largest x
-                        a, b = t.kthvalue(x, n - k + 1).values, t.kthvalue(x, n - k).values
-                    cut = 0.5 * (float(a) + float(b))
-                    # never further from where the cut started than the static colliders this rank kept allow
-                    cut = min(max(cut, self.cut0[d] - self.cut_slack), self.cut0[d] + self.cut_slack)
-                    if not np.isfinite(cut):
-                        cut = old
-                if cut != old:
-                    if d < 0: self.lo = cut
-                    else: self.hi = cut
-                    self.stats["cut_moves"] += 1
-                rec = t.tensor([cut], dtype=t.float64, device=dev).view(t.uint8).reshape(1, 8)
-            out[d] = rec
-        return out
+        self._move_cut(d, cut)
+        return cut
 
-    def balance_unpack_cuts(self, incoming):
-        t = self.torch
+    def _top_speed(self):
+        n = self.n_owned + 1
+        self._speed_pre = float(self._f32(self.bm[:n])[1:, :3].norm(dim=1).max()) if n > 1 else 0.0
+        return self._speed_pre
+
+    def _peer_speeds(self, peers):
+        self._peer_speed = peers
+
+    def _leavers(self):
+        """(d, mask over slots [0, n_owned]) per neighbour: the owned bodies whose centre is beyond the cut towards d."""
+        x, own = self._owned_x()
         for d in self.neighbours():
-            rec = incoming.get(d)
-            if rec is not None and rec.numel():
-                cut = float(rec.reshape(-1).view(t.float64)[0].item())
-                if self.hip is not None:
-                    from . import engine as E
-                    E._check(self.e.L, self.e.L.nh_partition_set_cut(self.hip, d, cut), "nh_partition_set_cut")
-                if cut != (self.lo if d < 0 else self.hi):
-                    if d < 0: self.lo = cut
-                    else: self.hi = cut
-                    self.stats["cut_moves"] += 1
+            yield d, own & ((x < self.lo) if d < 0 else (x >= self.hi))
 
-    # ---- refresh: top speeds across the cuts ---------------------------------------------------------------------
-    # A cut's ghost margin is reach + 2 x drift: the two bodies of a cross-cut pair approach each other from BOTH sides, so the drift must come from the top speed on
-    # both sides of that cut -- mine (now: before this refresh's migration) and the neighbour's.  One 8-byte message per neighbour, like the body counts.
-    # (Round-4 advisor finding: with a rank's own top speed only, a fast body owned by the neighbour reached slow bodies here that this rank had never listed for it and
-    # tunnelled through them until the next refresh.  tests/test_partition_cpu.py::test_a_fast_body_from_the_neighbour_finds_its_ghosts)
-    def speed_pack(self):
-        t = self.torch
-        if self.hip is not None:
-            import ctypes as C
-            from . import engine as E
-            v = C.c_double(0.0)
-            E._check(self.e.L, self.e.L.nh_partition_top_speed(self.hip, C.byref(self.e.bodies), C.byref(v)), "nh_partition_top_speed")
-            self._speed_pre = float(v.value)
-        else:
-            n = self.n_owned + 1
-            self._speed_pre = float(self._f32(self.bm[:n])[1:, :3].norm(dim=1).max()) if n > 1 else 0.0
-        dev = self.bt.device
-        return {d: t.tensor([self._speed_pre], dtype=t.float64, device=dev).view(t.uint8).reshape(1, 8) for d in self.neighbours()}
-
-    def speed_unpack(self, incoming):
-        t = self.torch
-        self._peer_speed = {d: float(incoming[d].reshape(-1).view(t.float64)[0].item()) for d in self.neighbours() if d in incoming and incoming[d].numel()}
-        if self.hip is not None:
-            from . import engine as E
-            E._check(self.e.L, self.e.L.nh_partition_set_peer_speeds(self.hip, self._peer_speed.get(-1, 0.0), self._peer_speed.get(+1, 0.0)), "nh_partition_set_peer_speeds")
-
-    # ---- refresh: is it needed at all?  (round 6) ---------------------------------------------------------------
-    quiet_refresh = True          # (class switch for A/B and tests: False = every epoch boundary is a refresh, as in rounds 3-5)
-
-    def refresh_is_quiet(self):
-        """Would a refresh change nothing on this rank?  No owned body beyond a cut, and the bodies within reach of a cut -- at the speeds just exchanged (speed_pack /
-        speed_unpack first; nothing is consumed) -- exactly the ones listed for the neighbours at the last refresh, in the same order.  The clusters skip the refresh only
-        when EVERY rank says so: the epoch boundary is then a per-step exchange like any other sub-step, and a world at rest stays in its still steps."""
-        if not self.quiet_refresh or self.steps == 0 or self.per_iteration:
-            return False
-        if self.hip is not None:
-            import ctypes as C
-            from . import engine as E
-            q = C.c_int(0)
-            E._check(self.e.L, self.e.L.nh_partition_refresh_is_quiet(self.hip, C.byref(self.e.bodies), C.byref(q)), "nh_partition_refresh_is_quiet")
-            return bool(q.value)
+    def _reaching(self):
+        """(d, slots) per neighbour: the owned bodies that can reach across the cut towards d within the coming epoch (module docstring)."""
         t = self.torch
         n = self.n_owned + 1
-        x = self._x(n)
-        own = t.arange(n, device=x.device) > 0
-        for d in self.neighbours():
-            if bool((own & ((x < self.lo) if d < 0 else (x >= self.hi))).any()):
-                return False
+        x, own = self._owned_x()
         v = self._f32(self.bm[:n])[:, :3].norm(dim=1)
         vmax = float(v[1:].max()) if n > 1 else 0.0
-        own_speed = max(vmax, getattr(self, "_speed_pre", 0.0), self.speed_floor)
-        peers = getattr(self, "_peer_speed", {})
+        # how far anything can travel in one epoch: top speed on BOTH sides of the cut (speed_pack / speed_unpack) + free-fall gain, never below the floor
+        own_speed = max(vmax, self._speed_pre, self.speed_floor)
         for d in self.neighbours():
-            drift_d = self.epoch * self.dt * (max(own_speed, peers.get(d, 0.0)) + self.gravity * self.epoch * self.dt)
-            margin = self.reach[:n] + (self.max_reach + 2.0 * drift_d)
-            idx = t.nonzero(own & ((x - margin < self.lo) if d < 0 else (x + margin >= self.hi))).flatten()
+            drift = self.epoch * self.dt * (max(own_speed, self._peer_speed.get(d, 0.0)) + self.gravity * self.epoch * self.dt)
+            margin = self.reach[:n] + (self.max_reach + 2.0 * drift)
+            yield d, t.nonzero(own & ((x - margin < self.lo) if d < 0 else (x + margin >= self.hi))).flatten()
+
+    def _nothing_would_change(self):
+        if any(bool(m.any()) for _, m in self._leavers()):
+            return False
+        for d, idx in self._reaching():
             old = self.ghost_out.get(d)
             if old is None or idx.shape != old.shape or not bool((idx == old).all()):
                 return False
         return True
 
-    # ---- refresh: phase 1 (migration) --------------------------------------------------------------------------
+    # phase 1 (migration)
     def refresh_pack_migrants(self):
-        if self.hip is not None:
-            return self._hip_pack(self.e.L.nh_partition_pack_migrants, "nh_partition_pack_migrants")
-        t = self.torch
-        n = self.n_owned + 1
-        x = self._x(n)
-        own = t.arange(n, device=x.device) > 0
         out = {}
-        self._leave = t.zeros(n, dtype=t.bool, device=x.device)
-        for d in self.neighbours():
-            m = own & ((x < self.lo) if d < 0 else (x >= self.hi))
-            idx = t.nonzero(m).flatten()
+        self._leave = self.torch.zeros(self.n_owned + 1, dtype=self.torch.bool, device=self.bt.device)
+        for d, m in self._leavers():
+            idx = self.torch.nonzero(m).flatten()
             out[d] = self._full(idx)
             self._leave |= m
             self.stats["migrated_out"] += int(idx.numel())
@@ -513,12 +695,6 @@ class Partition:
 
     def refresh_unpack_migrants(self, incoming):
         """Drops the bodies that left, appends the ones that arrived (owned region stays contiguous from slot 1)."""
-        if self.hip is not None:
-            import ctypes as C
-            from . import engine as E
-            E._check(self.e.L, self.e.L.nh_partition_unpack_migrants(self.hip, C.byref(self.e.bodies), *self._hip_unpack_args(incoming)), "nh_partition_unpack_migrants")
-            self._hip_info()
-            return
         t = self.torch
         n = self.n_owned + 1
         keep = t.nonzero(~self._leave).flatten()          # includes slot 0
@@ -536,50 +712,17 @@ class Partition:
                 self.stats["migrated_in"] += int(rec.shape[0])
         self.n_owned = at - 1
 
-    # ---- refresh: phase 2 (ghost lists) ------------------------------------------------------------------------------
+    # phase 2 (ghost lists)
     def refresh_pack_ghosts(self):
-        if self.hip is not None:
-            out = self._hip_pack(self.e.L.nh_partition_pack_ghosts, "nh_partition_pack_ghosts")
-            dev = self.bt.device
-            for d in self.neighbours():
-                self._stepbuf[d] = self.torch.empty((out[d].shape[0], STEP_BYTES), dtype=self.torch.uint8, device=dev)
-            self._ghost_out_total = sum(int(out[d].shape[0]) for d in self.neighbours())
-            return out
-        t = self.torch
-        n = self.n_owned + 1
-        x = self._x(n)
-        v = self._f32(self.bm[:n])[:, :3].norm(dim=1)
-        vmax = float(v[1:].max()) if n > 1 else 0.0
-        # how far anything can travel in one epoch: top speed on BOTH sides of the cut (speed_pack / speed_unpack) + free-fall gain, never below the floor
-        own_speed = max(vmax, getattr(self, "_speed_pre", 0.0), self.speed_floor)
-        peers = getattr(self, "_peer_speed", {})
-        self._speed_pre, self._peer_speed = 0.0, {}
-        own = t.arange(n, device=x.device) > 0
         out = {}
-        drift = 0.0
-        for d in self.neighbours():
-            drift_d = self.epoch * self.dt * (max(own_speed, peers.get(d, 0.0)) + self.gravity * self.epoch * self.dt)
-            drift = max(drift, drift_d)
-            margin = self.reach[:n] + (self.max_reach + 2.0 * drift_d)
-            m = own & ((x - margin < self.lo) if d < 0 else (x + margin >= self.hi))
-            idx = t.nonzero(m).flatten()
+        for d, idx in self._reaching():
             self.ghost_out[d] = idx
-            self.ghost_out32[d] = idx.to(t.int32)
+            self.ghost_out32[d] = idx.to(self.torch.int32)
             out[d] = self._full(idx)
-        self._drift = drift
+        self._speed_pre, self._peer_speed = 0.0, {}
         return out
 
     def refresh_unpack_ghosts(self, incoming):
-        if self.hip is not None:
-            import ctypes as C
-            from . import engine as E
-            e = self.e
-            E._check(e.L, e.L.nh_partition_unpack_ghosts(self.hip, C.byref(e.bodies), C.byref(e.colliders), *self._hip_unpack_args(incoming)), "nh_partition_unpack_ghosts")
-            i = self._hip_info()
-            self.ghost_in = {-1: int(i.ghost_in[0]), +1: int(i.ghost_in[1])}
-            self.n_bodies = int(i.n_bodies)
-            e.nb, e.nbox, e.nsph = int(i.n_bodies), int(i.n_boxes), int(i.n_spheres)         # (the C call has set the counts of the engine's structs and told the context)
-            return
         at = self.n_owned + 1
         for d in (-1, +1):
             rec = incoming.get(d) if d in self.neighbours() else None
@@ -619,122 +762,35 @@ class Partition:
         self.e.set_counts(n, counts[0], counts[1])
 
     # ---- every step ---------------------------------------------------------------------------------------------------
+    def _ghost_slots(self):
+        """(d, first slot, count) of the ghosts received from each side: the left neighbour's first."""
+        at = self.n_owned + 1
+        for d in (-1, +1):
+            yield d, at, self.ghost_in[d]
+            at += self.ghost_in[d]
+
     def step_pack(self):
-        if self.hip is not None:
-            import ctypes as C
-            from . import engine as E
-            e = self.e
-            ptr = lambda d: C.c_void_p(self._stepbuf[d].data_ptr()) if d in self.neighbours() and self._stepbuf[d].shape[0] else C.c_void_p(0)
-            E._check(e.L, e.L.nh_partition_pack_step(self.hip, C.byref(e.bodies), ptr(-1), ptr(+1)), "nh_partition_pack_step")
-            out = {d: self._stepbuf[d] for d in self.neighbours()}
-            self.stats["step_bytes"] += sum(int(r.numel()) for r in out.values())
-            return out
-        out = {}
-        for d in self.neighbours():
-            rec = self._step_records(self.ghost_out[d], self.ghost_out32[d])
-            out[d] = rec
-            self.stats["step_bytes"] += int(rec.numel())
+        out = {d: self._step_records(self.ghost_out[d], self.ghost_out32[d]) for d in self.neighbours()}
+        self.stats["step_bytes"] += sum(int(rec.numel()) for rec in out.values())
         return out
 
     def step_unpack(self, incoming):
-        if self.hip is not None:
-            import ctypes as C
-            from . import engine as E
-            e = self.e
-            recs = {d: (incoming[d].contiguous() if self.ghost_in[d] else None) for d in (-1, +1)}
-            ptr = lambda d: C.c_void_p(recs[d].data_ptr()) if recs[d] is not None else C.c_void_p(0)
-            E._check(e.L, e.L.nh_partition_unpack_step(self.hip, C.byref(e.bodies), ptr(-1), ptr(+1)), "nh_partition_unpack_step")
-            return
-        at = self.n_owned + 1
-        for d in (-1, +1):
-            m = self.ghost_in[d]
+        for d, at, m in self._ghost_slots():
             if m:
-                rec = incoming[d]
-                if hasattr(self.e, "halo_unpack"):
-                    self.e.halo_unpack(at, rec.contiguous(), same_bodies=True)      # (the ghost lists only change at a refresh, which announces itself: set_counts)
-                else:
-                    s = slice(at, at + m)
-                    self.bt[s, :12] = rec[:, :12]                 # position
-                    self.bt[s, 16:] = rec[:, 12:28]               # rotation (the `body` field keeps the global id)
-                    self.bm[s] = rec[:, 28:60]
-                    self.bi[s, 0] = rec[:, 60]
-            at += m
-
-    def local_step(self):
-        self.e.step(1)
-        self.steps += 1
-        self.stats["steps_total"] += 1
-
-    def library_steps(self, n, exchange_first, loopback_records=0):
-        """n sub-steps in ONE library call (nh_partition_step): per-step halo exchanges enqueued by the library over its own transport between them.  Must not reach past
-        the next refresh (the caller's business)."""
-        self.e.partition_step(self.hip, n, exchange_first, loopback_records)
-        if exchange_first:
-            self.stats["step_bytes"] += STEP_BYTES * getattr(self, "_ghost_out_total", 0)
-        self.stats["step_bytes"] += STEP_BYTES * getattr(self, "_ghost_out_total", 0) * (n - 1)
-        self.steps += n
-        self.stats["steps_total"] += n
-
-    # ---- per-iteration mode: the step in phases, ghost momentum refreshed after every sweep ---------------------------
-    def step_begin(self):
-        e = self.e
-        if self.single_owner:
-            e.set_first_ghost(self.n_owned + 1)
-        e.collide(); e.gravity(); e.read_cache()
-        if self.single_owner:
-            self.delta_mark()                     # (the warm start inside setup() already moves the ghosts of the contacts owned here)
-        e.setup()
-        if self.single_owner and hasattr(e, "synchronize"):
-            e.synchronize()                       # (the HIP engine may defer the warm start into the first apply call, header note 7: it has to be in the momentum the deltas are taken from)
+                self._step_install(at, incoming[d])
 
     # ---- single ownership: what the solver did to a ghost goes back to the ghost's owner ----------------------------------------------
-    def _ghost_span(self):
+    def _ghost_momentum(self):
         at = self.n_owned + 1
-        return at, at + self.ghost_in[-1] + self.ghost_in[+1]
-
-    # (round 5: behind the C ABI -- nh_partition_mark_ghosts / pack_deltas / unpack_deltas / pack_momentum / unpack_momentum -- when the engine is the HIP world; the
-    # torch form below is the same arithmetic and stays as the independent check: Partition(force_torch=True), and the reference-engine clusters of the tests)
-    def _hip_iter(self):
-        return self.hip is not None and not self.force_torch
-
-    def _hip_pair(self, fn, what, sizes, incoming=None):
-        """One of the four pack / unpack entry points: `sizes` records of 32 bytes per side; returns {d: tensor} for a pack."""
-        import ctypes as C
-        from . import engine as E
-        t = self.torch
-        dev = self.bt.device
-        bufs = {}
-        for d in (-1, +1):
-            if incoming is None:
-                bufs[d] = t.empty((sizes[d], 32), dtype=t.uint8, device=dev) if d in self.neighbours() else None
-            else:
-                r = incoming.get(d) if d in self.neighbours() else None
-                bufs[d] = r.contiguous().to(dev) if (r is not None and sizes[d]) else None
-                if bufs[d] is not None:
-                    assert bufs[d].numel() == 32 * sizes[d], (what, d, bufs[d].shape, sizes[d])
-        ptr = lambda d: C.c_void_p(bufs[d].data_ptr() if (bufs[d] is not None and bufs[d].numel()) else 0)      # noqa: E731
-        E._check(self.e.L, fn(self.hip, C.byref(self.e.bodies), ptr(-1), ptr(+1)), what)
-        self._iter_keep = bufs                   # (the kernels are enqueued: keep the message tensors alive until the next call)
-        return {d: b for d, b in bufs.items() if b is not None} if incoming is None else None
+        return self.bm[at:at + self.ghost_in[-1] + self.ghost_in[+1]]
 
     def delta_mark(self):
-        if self._hip_iter():
-            import ctypes as C
-            from . import engine as E
-            E._check(self.e.L, self.e.L.nh_partition_mark_ghosts(self.hip, C.byref(self.e.bodies)), "nh_partition_mark_ghosts")
-            return
-        a, b = self._ghost_span()
-        self._ghost_ref = self.bm[a:b].clone()
+        self._ghost_ref = self._ghost_momentum().clone()
 
     def delta_pack(self):
         """Per neighbour: momentum of its bodies' ghosts here now minus at the last delta_mark() (8 floats per ghost, in the order of the neighbour's list)."""
-        if self._hip_iter():
-            out = self._hip_pair(self.e.L.nh_partition_pack_deltas, "nh_partition_pack_deltas", {d: self.ghost_in[d] for d in (-1, +1)})
-            self.stats["step_bytes"] += sum(int(v.numel()) for v in out.values())
-            return out
         t = self.torch
-        a, b = self._ghost_span()
-        d = self.bm[a:b].contiguous().view(t.float32) - self._ghost_ref.contiguous().view(t.float32)
+        d = self._ghost_momentum().contiguous().view(t.float32) - self._ghost_ref.contiguous().view(t.float32)
         d[:, 3] = 0.0; d[:, 7] = 0.0              # (the two spare words of a momentum record are the engine's: the inverse mass rides there during a solve, nudge.cpp:4358)
         out, m = {}, self.ghost_in[-1]
         for dirn, part in ((-1, d[:m]), (+1, d[m:])):
@@ -745,84 +801,116 @@ class Partition:
 
     def delta_unpack(self, incoming):
         """Adds the neighbours' deltas to the bodies listed for them (ghost_out[d] is the order the neighbour holds their ghosts in)."""
-        if self._hip_iter():
-            self._hip_pair(self.e.L.nh_partition_unpack_deltas, "nh_partition_unpack_deltas", {d: (len(self.ghost_out[d]) if self.ghost_out.get(d) is not None else self._ghost_out_n(d)) for d in (-1, +1)}, incoming)
-            return
         t = self.torch
         bmf = self.bm.view(t.float32)
         for d in self.neighbours():
             idx = self.ghost_out[d]
             if idx is not None and len(idx):
                 bmf.index_add_(0, idx.long(), incoming[d].contiguous().view(t.float32).to(bmf.device))
-        if hasattr(self.e, "momentum_written"):
-            self.e.momentum_written()
-
-    def sweep(self):
-        self.e.apply(1)
-
-    def _ghost_out_n(self, d):
-        """How many of my bodies are listed for neighbour d (the HIP partition keeps the lists on the device: nh_partition_info)."""
-        if self.hip is not None:
-            i = self._hip_info()
-            return int(i.ghost_out[0 if d < 0 else 1])
-        return int(len(self.ghost_out[d])) if self.ghost_out.get(d) is not None else 0
 
     def momentum_pack(self):
-        if self._hip_iter():
-            out = self._hip_pair(self.e.L.nh_partition_pack_momentum, "nh_partition_pack_momentum", {d: self._ghost_out_n(d) for d in (-1, +1)})
-            self.stats["step_bytes"] += sum(int(v.numel()) for v in out.values())
-            return out
-        out = {}
-        for d in self.neighbours():
-            rec = self.bm[self.ghost_out[d]]
-            out[d] = rec
-            self.stats["step_bytes"] += int(rec.numel())
+        out = {d: self.bm[self.ghost_out[d]] for d in self.neighbours()}
+        self.stats["step_bytes"] += sum(int(rec.numel()) for rec in out.values())
         return out
 
     def momentum_unpack(self, incoming):
-        if self._hip_iter():
-            self._hip_pair(self.e.L.nh_partition_unpack_momentum, "nh_partition_unpack_momentum", {d: self.ghost_in[d] for d in (-1, +1)}, incoming)
-            return
-        at = self.n_owned + 1
-        for d in (-1, +1):
-            m = self.ghost_in[d]
+        for d, at, m in self._ghost_slots():
             if m:
                 self.bm[at:at + m] = incoming[d]
-                if hasattr(self.e, "momentum_written"):
-                    self.e.momentum_written()
-            at += m
-
-    def step_end(self):
-        e = self.e
-        e.update(); e.write_cache(); e.advance()
-        if hasattr(e, "step_done"):
-            e.step_done()
-        self.steps += 1
-        self.stats["steps_total"] += 1
-
-    def iterations(self):
-        return int(self.e.params["iterations"])
-
-    def needs_refresh(self):
-        return self.steps % self.epoch == 0
-
-    # ---- results ------------------------------------------------------------------------------------------------------------
-    def owned_state(self):
-        """(global ids, transforms, momentum, idle) of the owned bodies, as numpy arrays."""
-        n = self.n_owned + 1
-        if hasattr(self.e, "synchronize"):
-            self.e.synchronize()
-        bt = np.frombuffer(self.bt[1:n].cpu().numpy().tobytes(), dtype=S.TRANSFORM).copy()
-        bm = np.frombuffer(self.bm[1:n].cpu().numpy().tobytes(), dtype=S.MOMENTUM).copy()
-        bi = self.bi[1:n, 0].cpu().numpy().copy()
-        return bt["body"].astype(np.int64), bt, bm, bi
 
 
-class LocalCluster:
+def Partition(engine, info, epoch=16, speed_floor=1.0, per_iteration=False, rebalance=True, balance_tolerance=0.05, force_torch=False, single_owner=False):
+    """One rank's share of the world.  `engine` exposes the caller-owned arrays as [capacity, record] uint8 torch
+    tensors (`records(name, bytes)`), `set_counts(bodies, boxes, spheres)`, `step(n)` and `params` -- nudge_amd.engine.World
+    does; the CPU tests plug the oracle in behind the same four members.
+    (Round 5: the per-iteration exchange of single ownership is behind the C ABI too, so the HIP engine gets a HipPartition in every mode; force_torch=True keeps the
+    torch implementation, the independent check.)"""
+    on_the_abi = not force_torch and hasattr(engine, "L") and hasattr(engine, "ctx") and hasattr(engine.L, "nh_partition_create")
+    return (HipPartition if on_the_abi else TorchPartition)(engine, info, epoch, speed_floor, per_iteration, rebalance, balance_tolerance, single_owner)
+
+
+def _merge(states):
+    """owned_state() of several partitions merged by global id: dict(ids, transforms, momentum, idle), sorted by id."""
+    ids = np.concatenate([q[0] for q in states])
+    order = np.argsort(ids, kind="stable")
+    return dict(ids=ids[order], transforms=np.concatenate([q[1] for q in states])[order],
+                momentum=np.concatenate([q[2] for q in states])[order], idle=np.concatenate([q[3] for q in states])[order])
+
+
+class _Cluster:
+    """The step protocol, once, over the partitions this process holds (`parts`: all of them in a LocalCluster, one in a DistCluster).  A transport brings two
+    primitives: _round(name, width, counts) -- `name.format("pack")` on every local partition, deliver, `name.format("unpack")` (the methods are looked up on the
+    partition at call time; `width` the record bytes, `counts(p)` the rows expected per neighbour when they are known in advance) -- and _vote(answers): does
+    every rank of the job say yes?"""
+
+    def __init__(self, parts):
+        self.parts = parts
+        self.quiet_refreshes = 0
+
+    def _refresh(self):
+        """Counts and cuts (re-balancing), top speeds, the quiet vote, migrants, ghosts.  False: a QUIET refresh -- nobody has crossed a cut, every ghost list would come
+        out as it is, on EVERY partition -- and the epoch boundary is a per-step exchange."""
+        parts, lead = self.parts, self.parts[0]
+        one_row = lambda p: dict.fromkeys(p.neighbours(), 1)      # noqa: E731
+        if lead.rebalance and lead.steps > 0:
+            self._round("balance_{}_counts", 8, one_row)
+            self._round("balance_{}_cuts", 8, lambda p: p.balance_expected())
+        self._round("speed_{}", 8, one_row)
+        # (the vote is taken whenever a partition here could say yes -- at step 0 too, where every refresh_is_quiet() says no: all ranks of a job must vote or none)
+        if any(p.quiet_refresh and not p.per_iteration for p in parts) and self._vote([p.refresh_is_quiet() for p in parts]):
+            self.quiet_refreshes += 1
+            return False
+        self._round("refresh_{}_migrants", FULL_BYTES)
+        self._round("refresh_{}_ghosts", FULL_BYTES)
+        return True
+
+    def _boundary(self):
+        """The start of a step: (is it an epoch boundary, was a refresh made).  Without a refresh the caller owes the ghosts a per-step exchange."""
+        boundary = self.parts[0].needs_refresh()
+        return boundary, boundary and self._refresh()
+
+    def _step_exchange(self):
+        self._round("step_{}", STEP_BYTES, lambda p: p.ghost_in)
+
+    def _iteration_exchange(self):
+        single_owner = self.parts[0].single_owner
+        if single_owner:                          # ghost deltas to their owners first: the momentum sent back below includes them
+            self._round("delta_{}", 32, lambda p: {d: p._ghost_out_n(d) for d in p.neighbours()})
+        self._round("momentum_{}", 32, lambda p: p.ghost_in)
+        if single_owner:
+            for p in self.parts:
+                p.delta_mark()
+
+    def _solve(self):
+        """Collide .. advance on every local partition: one engine step, or (per_iteration) the step in phases with an exchange after every sweep."""
+        parts, lead = self.parts, self.parts[0]
+        if not lead.per_iteration:
+            for p in parts:
+                p.local_step()
+            return
+        for p in parts:
+            p.step_begin()
+        if lead.single_owner:
+            self._iteration_exchange()            # (the warm start)
+        for _it in range(lead.iterations()):
+            if lead.single_owner:
+                # even ranks sweep, their results travel, odd ranks sweep: with one owner per contact that IS one Gauss-Seidel sweep over all contacts of the
+                # world (module docstring); sweeping both parities at once would be a Jacobi step between the ranks, which overshoots on a body held from both sides
+                for phase in (0, 1):
+                    for p in parts:
+                        if p.rank % 2 == phase:
+                            p.sweep()
+                    self._iteration_exchange()
+            else:
+                for p in parts:
+                    p.sweep()
+                self._iteration_exchange()
+        for p in parts:
+            p.step_end()
+
+
+class LocalCluster(_Cluster):
     """All partitions in one process (one GPU or the CPU): messages are tensor hand-overs."""
-
-    def __init__(self, partitions):
-        self.parts = partitions
 
     def _route(self, outs):
         ins = [dict() for _ in self.parts]
@@ -831,78 +919,23 @@ class LocalCluster:
                 ins[r + d][-d] = rec.clone()
         return ins
 
+    def _round(self, name, width=None, counts=None):
+        ins = self._route([getattr(p, name.format("pack"))() for p in self.parts])
+        for p, i in zip(self.parts, ins):
+            getattr(p, name.format("unpack"))(i)
+
+    def _vote(self, answers):
+        return all(answers)
+
     def step(self, steps=1):
         for _ in range(steps):
-            if self.parts[0].needs_refresh():
-                if self.parts[0].rebalance and self.parts[0].steps > 0:
-                    ins = self._route([p.balance_pack_counts() for p in self.parts])
-                    for p, i in zip(self.parts, ins):
-                        p.balance_unpack_counts(i)
-                    ins = self._route([p.balance_pack_cuts() for p in self.parts])
-                    for p, i in zip(self.parts, ins):
-                        p.balance_unpack_cuts(i)
-                ins = self._route([p.speed_pack() for p in self.parts])
-                for p, i in zip(self.parts, ins):
-                    p.speed_unpack(i)
-                # (a QUIET refresh -- nobody has crossed a cut, every ghost list would come out as it is, on EVERY partition -- is a per-step exchange)
-                refreshed = not all([p.refresh_is_quiet() for p in self.parts])
-                if refreshed:
-                    ins = self._route([p.refresh_pack_migrants() for p in self.parts])
-                    for p, i in zip(self.parts, ins):
-                        p.refresh_unpack_migrants(i)
-                    ins = self._route([p.refresh_pack_ghosts() for p in self.parts])
-                    for p, i in zip(self.parts, ins):
-                        p.refresh_unpack_ghosts(i)
-                else:
-                    self.quiet_refreshes = getattr(self, "quiet_refreshes", 0) + 1
-            else:
-                refreshed = False
-            if not refreshed:
-                ins = self._route([p.step_pack() for p in self.parts])
-                for p, i in zip(self.parts, ins):
-                    p.step_unpack(i)
-            if self.parts[0].per_iteration:
-                def exchange():
-                    if self.parts[0].single_owner:          # ghost deltas to their owners first: the momentum sent back below includes them
-                        ins = self._route([p.delta_pack() for p in self.parts])
-                        for p, i in zip(self.parts, ins):
-                            p.delta_unpack(i)
-                    ins = self._route([p.momentum_pack() for p in self.parts])
-                    for p, i in zip(self.parts, ins):
-                        p.momentum_unpack(i)
-                    if self.parts[0].single_owner:
-                        for p in self.parts:
-                            p.delta_mark()
-                for p in self.parts:
-                    p.step_begin()
-                if self.parts[0].single_owner:
-                    exchange()                              # (the warm start)
-                for _it in range(self.parts[0].iterations()):
-                    if self.parts[0].single_owner:
-                        # even ranks sweep, their results travel, odd ranks sweep: with one owner per contact that IS one Gauss-Seidel sweep over all contacts of the
-                        # world (module docstring); sweeping both parities at once would be a Jacobi step between the ranks, which overshoots on a body held from both sides
-                        for phase in (0, 1):
-                            for p in self.parts:
-                                if p.rank % 2 == phase:
-                                    p.sweep()
-                            exchange()
-                    else:
-                        for p in self.parts:
-                            p.sweep()
-                        exchange()
-                for p in self.parts:
-                    p.step_end()
-            else:
-                for p in self.parts:
-                    p.local_step()
+            if not self._boundary()[1]:
+                self._step_exchange()
+            self._solve()
 
     def gather(self):
         """Owned bodies of all partitions merged by global id: dict(ids, transforms, momentum, idle), sorted by id."""
-        parts = [p.owned_state() for p in self.parts]
-        ids = np.concatenate([q[0] for q in parts])
-        order = np.argsort(ids, kind="stable")
-        return dict(ids=ids[order], transforms=np.concatenate([q[1] for q in parts])[order],
-                    momentum=np.concatenate([q[2] for q in parts])[order], idle=np.concatenate([q[3] for q in parts])[order])
+        return _merge([p.owned_state() for p in self.parts])
 
 
 class RcclDirect:
@@ -912,7 +945,6 @@ class RcclDirect:
     caller keeps the torch.distributed transport."""
 
     def __init__(self, dist, group, device, timeout_s=60.0):
-        import ctypes as C
         self.ok, self.why, self.comm, self.lib = False, "", None, None
         try:
             import torch
@@ -955,9 +987,6 @@ class RcclDirect:
     def attach(self, partition, loopback=False, timeout_s=60.0):
         """Hands communicator and entry points to the partition's library object and checks both neighbours with a pattern exchange, polled with a time-out so that a
         neighbour that never answers cannot hang the job.  Returns True when the library-driven exchange may be used."""
-        import time
-        import ctypes as C
-        from . import engine as E
         p = partition
         if not self.ok or p.hip is None:
             return False
@@ -986,7 +1015,7 @@ class RcclDirect:
         return True
 
 
-class DistCluster:
+class DistCluster(_Cluster):
     """One partition per process; neighbour messages over torch.distributed point-to-point ops
     (backend "nccl" = RCCL over xGMI for GPU tensors, "gloo" for the CPU tests)."""
 
@@ -995,6 +1024,7 @@ class DistCluster:
         `loopback` = m > 0: every step this rank also sends the per-step records of its first m owned bodies to ITSELF through the same
         point-to-point ops and writes them back onto those bodies (a no-op for the simulation) -- what a ONE-GPU box can execute of the RCCL path."""
         import torch.distributed as dist
+        super().__init__([partition])
         self.dist = dist
         self.p = partition
         self.group = group
@@ -1002,20 +1032,33 @@ class DistCluster:
         self.host_staging = host_staging
         self.loopback = int(loopback)
         self.loopback_records = 0
+        self.loopback_steps = 0
+        self._loop_plan = None              # the loopback's buffers and P2P ops, built once
         self._step_plan = None              # per-step exchange of a HIP partition: send / receive buffers and the P2P ops, built once per refresh
         self.direct = False                 # the per-step halo is driven by the library over its own RCCL communicator (use_rccl_direct)
         self.direct_why = ""
+        self._rccl = None
+        self.multi_step = True              # with the library-driven transport: the sub-steps between two refreshes in ONE call (nh_partition_step); False: one call per sub-step (round 5)
+        self._can_multi_step = partition.hip is not None and hasattr(partition.e, "partition_step")
+        self._on_the_abi = hasattr(partition.e, "L") and hasattr(partition.e, "ctx")
+        # host-side accounting for bench.py (wall time of the refreshes, their own synchronisations included; host time to ENQUEUE a per-step halo)
+        self.t_refresh, self.n_refresh, self.t_halo, self.n_halo = 0.0, 0, 0.0, 0
+
+    def _vote(self, answers):
+        """Every rank of the job must say yes: one all-reduce of one word."""
+        t, dist = self.torch, self.dist
+        red = "cuda" if dist.get_backend(self.group) == "nccl" else "cpu"
+        flag = t.tensor([1.0 if all(answers) else 0.0], device=red)
+        dist.all_reduce(flag, op=dist.ReduceOp.MIN, group=self.group)
+        return bool(flag.item() > 0.5)
 
     def use_rccl_direct(self, device, loopback=False):
         """Per-step halo through nh_partition_exchange_step (pack, ncclSend / ncclRecv, unpack in ONE library call) instead of torch.distributed point-to-point ops: the
         host's share of a step shrinks to two C calls.  Every rank must end up with the same answer, so the outcome is agreed on with an all-reduce; any doubt -> False."""
-        t, dist, p = self.torch, self.dist, self.p
-        r = RcclDirect(dist, self.group, device)
+        p = self.p
+        r = RcclDirect(self.dist, self.group, device)
         ok = r.attach(p, loopback=loopback)
-        red = "cuda" if dist.get_backend(self.group) == "nccl" else "cpu"
-        flag = t.tensor([1.0 if ok else 0.0], device=red)
-        dist.all_reduce(flag, op=dist.ReduceOp.MIN, group=self.group)
-        self.direct = bool(flag.item() > 0.5)
+        self.direct = self._vote([ok])
         self.direct_why = r.why
         self._rccl = r                      # (keeps library and communicator alive)
         if not self.direct and ok:
@@ -1049,8 +1092,7 @@ class DistCluster:
         if m <= 0:
             return
         home = p.bt.device
-        plan = getattr(self, "_loop_plan", None)
-        if plan is None or plan[0] != m:
+        if self._loop_plan is None or self._loop_plan[0] != m:
             # (buffers and ops built once, like the per-step exchange with real neighbours: _fast_step_exchange)
             idx = t.arange(1, 1 + m, dtype=t.int32, device=home)
             dev = t.device("cpu") if self.host_staging else home
@@ -1059,11 +1101,9 @@ class DistCluster:
             me = dist.get_rank(self.group)
             stage = out if not self.host_staging else t.empty((m, STEP_BYTES), dtype=t.uint8, device=dev)
             ops = [dist.P2POp(dist.isend, stage, me, self.group), dist.P2POp(dist.irecv, back, me, self.group)]
-            plan = self._loop_plan = (m, idx, out, stage, back, ops)
-        _, idx, out, stage, back, ops = plan
-        if hasattr(p.e, "L") and hasattr(p.e, "ctx"):
-            import ctypes as C
-            from . import engine as E
+            self._loop_plan = (m, idx, out, stage, back, ops)
+        _, idx, out, stage, back, ops = self._loop_plan
+        if self._on_the_abi:                # (nh_halo_pack straight into the prepared buffer)
             E._check(p.e.L, p.e.L.nh_halo_pack(p.e.ctx, C.byref(p.e.bodies), C.c_void_p(idx.data_ptr()), m, C.c_void_p(out.data_ptr())), "halo_pack")
         else:
             out.copy_(p._step_records(idx.to(t.int64), idx))
@@ -1071,13 +1111,9 @@ class DistCluster:
             stage.copy_(out)
         for w in dist.batch_isend_irecv(ops):
             w.wait()
-        rec = back.to(home) if self.host_staging else back
-        if hasattr(p.e, "halo_unpack"):
-            p.e.halo_unpack(1, rec, same_bodies=True)
-        else:
-            p.bt[1:1 + m, :12] = rec[:, :12]; p.bt[1:1 + m, 16:] = rec[:, 12:28]; p.bm[1:1 + m] = rec[:, 28:60]; p.bi[1:1 + m, 0] = rec[:, 60]
+        p._step_install(1, back.to(home) if self.host_staging else back)
         self.loopback_records += m
-        self.loopback_steps = getattr(self, "loopback_steps", 0) + 1
+        self.loopback_steps += 1
 
     def _exchange(self, out, widths=None, known_counts=None):
         """Sends out[d] to rank+d and returns what the neighbours sent.  Counts are exchanged first unless known."""
@@ -1112,96 +1148,55 @@ class DistCluster:
             ins = {d: r.to(home) for d, r in ins.items()}
         return ins
 
-    # host-side accounting for bench.py (wall time of the refreshes, their own synchronisations included; host time to ENQUEUE a per-step halo)
-    t_refresh = 0.0; n_refresh = 0; t_halo = 0.0; n_halo = 0
-    multi_step = True          # with the library-driven transport: the sub-steps between two refreshes in ONE call (nh_partition_step); False: one call per sub-step (round 5)
-
-    def _refresh(self):
+    def _round(self, name, width, counts=None):
         p = self.p
-        if p.rebalance and p.steps > 0:
-            p.balance_unpack_counts(self._exchange(p.balance_pack_counts(), 8, known_counts={d: 1 for d in p.neighbours()}))
-            p.balance_unpack_cuts(self._exchange(p.balance_pack_cuts(), 8, known_counts=p.balance_expected()))
-        p.speed_unpack(self._exchange(p.speed_pack(), 8, known_counts={d: 1 for d in p.neighbours()}))
-        # a QUIET refresh (Partition.refresh_is_quiet): every rank of the job must say so -- one all-reduce of one word -- and the epoch boundary is a per-step exchange
-        if p.quiet_refresh and not p.per_iteration:
-            t, dist = self.torch, self.dist
-            red = "cuda" if dist.get_backend(self.group) == "nccl" else "cpu"
-            flag = t.tensor([1.0 if p.refresh_is_quiet() else 0.0], device=red)
-            dist.all_reduce(flag, op=dist.ReduceOp.MIN, group=self.group)
-            if flag.item() > 0.5:
-                self.quiet_refreshes = getattr(self, "quiet_refreshes", 0) + 1
-                return False
-        p.refresh_unpack_migrants(self._exchange(p.refresh_pack_migrants(), FULL_BYTES))
-        p.refresh_unpack_ghosts(self._exchange(p.refresh_pack_ghosts(), FULL_BYTES))
-        return True
+        out = getattr(p, name.format("pack"))()
+        getattr(p, name.format("unpack"))(self._exchange(out, width, known_counts=None if counts is None else counts(p)))
+
+    def _step_exchange(self):
+        p = self.p
+        if self.direct:
+            p.exchange_step()
+        elif p.hip is not None and not self.host_staging:
+            self._fast_step_exchange()
+        else:
+            super()._step_exchange()
+
+    def _clock(self, boundary, t_0, n=1):
+        """Books the host time since t_0 on the refreshes (an epoch boundary, quiet or not) or on the per-step halo of n sub-steps."""
+        if boundary:
+            self.t_refresh += time.perf_counter() - t_0; self.n_refresh += 1
+        else:
+            self.t_halo += time.perf_counter() - t_0; self.n_halo += n
 
     def step(self, steps=1):
-        import time
         p = self.p
-        if self.direct and self.multi_step and not p.per_iteration and p.hip is not None and hasattr(p.e, "partition_step"):
-            # the library drives the sub-steps between two refreshes itself (nh_partition_step): refresh (host), then one call for the steps up to the next one
-            left = steps
-            while left > 0:
-                t_0 = time.perf_counter()
-                refreshing = p.needs_refresh()
-                if refreshing:
-                    refreshing = self._refresh()          # (False: a quiet one -- the boundary is a per-step exchange inside the library call below)
-                    self.t_refresh += time.perf_counter() - t_0; self.n_refresh += 1
-                n = min(left, p.epoch - (p.steps % p.epoch))
-                t_1 = time.perf_counter()
-                lb = min(self.loopback, p.n_owned) if self.loopback else 0
-                p.library_steps(n, exchange_first=not refreshing, loopback_records=lb)
-                self.t_halo += time.perf_counter() - t_1; self.n_halo += n
-                if lb:
-                    self.loopback_records += lb * (n if not refreshing else n - 1)
-                    self.loopback_steps = getattr(self, "loopback_steps", 0) + n
-                left -= n
-            return
-        for _ in range(steps):
+        # the library drives the sub-steps between two refreshes itself (nh_partition_step): refresh (host), then one call for the steps up to the next one
+        library = self.direct and self.multi_step and not p.per_iteration and self._can_multi_step
+        left = steps
+        while left > 0:
             t_0 = time.perf_counter()
-            refreshing = p.needs_refresh()
-            boundary = refreshing
-            if refreshing:
-                refreshing = self._refresh()
-            if refreshing:
-                pass
-            elif self.direct:
-                import ctypes as C
-                from . import engine as E
-                E._check(p.e.L, p.e.L.nh_partition_exchange_step(p.hip, C.byref(p.e.bodies)), "nh_partition_exchange_step")
-                p.stats["step_bytes"] += STEP_BYTES * getattr(p, "_ghost_out_total", 0)
-            elif p.hip is not None and not self.host_staging:
-                self._fast_step_exchange()
+            boundary, refreshed = self._boundary()          # (refreshed False at a boundary: a quiet one)
+            if library:
+                if boundary:
+                    self._clock(True, t_0)
+                n = min(left, p.epoch - (p.steps % p.epoch))
+                t_0 = time.perf_counter()
+                lb = min(self.loopback, p.n_owned) if self.loopback else 0
+                p.library_steps(n, exchange_first=not refreshed, loopback_records=lb)          # (no refresh: the first sub-step's exchange is the library's as well)
+                self._clock(False, t_0, n)
+                if lb:
+                    self.loopback_records += lb * (n if not refreshed else n - 1)
+                    self.loopback_steps += n
             else:
-                p.step_unpack(self._exchange(p.step_pack(), STEP_BYTES, known_counts={d: p.ghost_in[d] for d in p.neighbours()}))
-            if boundary:
-                self.t_refresh += time.perf_counter() - t_0; self.n_refresh += 1
-            else:
-                self.t_halo += time.perf_counter() - t_0; self.n_halo += 1
-            if self.loopback:
-                self._loopback()
-            if p.per_iteration:
-                def exchange():
-                    if p.single_owner:
-                        p.delta_unpack(self._exchange(p.delta_pack(), 32, known_counts={d: p._ghost_out_n(d) for d in p.neighbours()}))
-                    p.momentum_unpack(self._exchange(p.momentum_pack(), 32, known_counts={d: p.ghost_in[d] for d in p.neighbours()}))
-                    if p.single_owner:
-                        p.delta_mark()
-                p.step_begin()
-                if p.single_owner:
-                    exchange()
-                for _it in range(p.iterations()):
-                    if p.single_owner:
-                        for phase in (0, 1):          # (see LocalCluster.step)
-                            if p.rank % 2 == phase:
-                                p.sweep()
-                            exchange()
-                    else:
-                        p.sweep()
-                        exchange()
-                p.step_end()
-            else:
-                p.local_step()
+                n = 1
+                if not refreshed:
+                    self._step_exchange()
+                self._clock(boundary, t_0)
+                if self.loopback:
+                    self._loopback()
+                self._solve()
+            left -= n
 
     def gather(self, dst=0):
         """Owned bodies of all ranks merged by global id on rank `dst` (None elsewhere)."""
@@ -1210,9 +1205,4 @@ class DistCluster:
         world = dist.get_world_size(self.group)
         objs = [None] * world if dist.get_rank(self.group) == dst else None
         dist.gather_object(mine, objs, dst=dst, group=self.group)
-        if objs is None:
-            return None
-        ids = np.concatenate([q[0] for q in objs])
-        order = np.argsort(ids, kind="stable")
-        return dict(ids=ids[order], transforms=np.concatenate([q[1] for q in objs])[order],
-                    momentum=np.concatenate([q[2] for q in objs])[order], idle=np.concatenate([q[3] for q in objs])[order])
+        return None if objs is None else _merge(objs)
