@@ -1098,6 +1098,90 @@ int nh_contact_events(nh_context* ctx, const nh_PairList* prev /* or NULL */, co
 int nh_step_contact_pairs(nh_context* ctx, const nh_ContactData* contacts, const nh_ContactCache* cache,
                           uint32_t body_count, const nh_PairList* out, uint32_t flags /* 0 */);
 
+/* BODY IMPULSES -- nh_body_impulses, nh_impulse_sums, nh_blast_impulses and nh_touch_impulses: push, blast and wake bodies on the device.  The way back from
+   the queries into the simulation: a list of impulse records (nh_ImpulseList: a host struct of DEVICE pointers), written by the caller's own kernel or by one
+   of the two generators below, is summed per body in an order that does not depend on the hardware and added to the bodies' momentum, with nothing downloaded:
+   "refit, recover, walk_touched, touch_impulses, body_impulses, step" and "overlap_wide, overlap_bodies, blast_impulses, body_impulses, step" are frames that
+   never leave the device.  The rules are exact -- a host oracle reproduces every byte (tests/hostoracle/hostimpulse.cpp):
+     - LIST: the first min(*count, capacity) records, or `capacity` of them with count == NULL; nothing at or beyond `capacity` is ever read;
+     - a record is VALID iff 0 < body < bodies->count.  Body 0 is the static world (nudge.cpp:3663, 3954) and takes no impulse; NH_IMPULSE_NO_BODY is
+       invalid by the same test;
+     - a record's PAIR (L, T): L is `impulse`.  With NH_IMPULSE_AT_CENTRE `point` is not read and T = (+0, +0, +0); otherwise r = point -
+       transforms[body].position componentwise and T = (r.y * J.z - r.z * J.y, r.z * J.x - r.x * J.z, r.x * J.y - r.y * J.x) in fp32 -- two products and
+       one subtraction per component, no contraction (the library is built with -ffp-contract=off);
+     - a RUN is a maximal stretch of consecutive valid records of one body; an invalid record ends a run and belongs to none.  A run's six sums start
+       at +0 and take its records left to right;
+     - a BODY's six sums start at +0 and take its runs' sums in list order -- the stable sort's order.  This TWO-LEVEL order is the specification, as it
+       is for the contact events: it is what lets the runs be reduced before the sort.  Sums with a NaN in them are NaN, of unspecified
+       payload.
+   nh_impulse_sums -- ONE nh_ImpulseSum PER DISTINCT VALID BODY, ascending by body; `count` is the body's number of records.  The output follows
+   nh_contact_pairs' contract: *count always receives the true number; the records are written iff that number is <= capacity -- all or none -- every byte
+   behind the written records is left untouched; sums == NULL with capacity 0 counts only.  It reads bodies->transforms and bodies->count and writes no
+   body state; it is no entry point of the step (note 9).
+   nh_body_impulses -- THE SAME PIPELINE, but the lane of each distinct body loads the body's nh_BodyMomentum whole, adds
+       velocity[c]       += linear[c] * mass_inverse                                  (per component: one product, one sum)
+       angular_velocity  += W . angular,  W = the world-space inverse inertia of (rotation, inertia_inverse), six terms as the solver computes them;
+                            x = (W.xx * Tx + W.xy * Ty) + W.xz * Tz,  y = (W.xy * Tx + W.yy * Ty) + W.yz * Tz,  z = (W.xz * Tx + W.yz * Ty) + W.zz * Tz
+   and stores the record whole, unused0 and unused1 with the bits they had.  With NH_IMPULSE_WAKE the lane also stores idle_counters[body] = 0: the next
+   nh_collide then wakes the body's whole set, as the reference does (nudge.cpp:3669-3672, 3960-3971).  Without the flag no idle counter is written: a
+   sleeper keeps the velocity it was given until something wakes it, exactly as if the caller had written the momentum array.  Bodies without a valid record
+   are not touched.
+   RELATION TO THE STEP: nh_body_impulses writes momentum, so it first completes pending work (as nh_halo_unpack does).  With NH_IMPULSE_WAKE it then
+   does on the host everything nh_bodies_changed does, unconditionally -- whether anybody was asleep is known only on the device.  Without the flag it
+   leaves speculation to the device-side checks of note 9, as for momentum written from outside: the still step whose checks fail is replayed.
+   nh_blast_impulses -- ONE RECORD IN, ONE RECORD OUT: `hits` is a list of nh_overlap, nh_overlap_wide, nh_region or nh_overlap_bodies for `count` volumes;
+   segment i belongs to blasts[i].  Record j of the list gives out[j] for every j < min(offsets[count], hits->capacity); its segment is found by binary
+   search in `offsets` (an index past every offset belongs to the last blast).  With p = transforms[hit.body].position: r = p - centre,
+   d = sqrtf((r.x * r.x + r.y * r.y) + r.z * r.z), s = strength * (1.0f - falloff * (d / radius)).  If hit.body == 0, hit.body >= bodies->count or !(s > 0)
+   the record is NH_IMPULSE_NO_BODY with all other words 0 -- there is no compaction.  Otherwise dir = d > 0 ? r / d : (0, 1, 0) (three plain divisions),
+   impulse = dir * s, point = p, flags = NH_IMPULSE_AT_CENTRE, body = hit.body.  Plain `/` and sqrtf are correctly rounded on the host and on the device.
+   A compound body gets one record per COLLIDER the volume touches: one record per BODY is the caller's nh_overlap_bodies first.
+   nh_touch_impulses -- INTEGRATION's pushing recipe, word for word, on what a _touched mover wrote for `count` movers with `k` slots each: slot j of mover
+   i gives out[i * k + j], a real record iff j < min(counts[i], k), hit.shape != NH_SHAPE_NONE, hit.body != 0, hit.t > 0, phase < 32 with
+   (pushes[i].phases >> phase) & 1, and the approach a = -((d.x * n.x + d.y * n.y) + d.z * n.z) > 0 (d the touch's `direction`, n its hit.normal, the
+   sign bit inverted).  Then m = mass_over_dt * a, or max_impulse where that is smaller; impulse[c] = -n[c] * m; point[c] = origin[c] + d[c] * t; flags
+   are the push's, body = hit.body.  Otherwise NH_IMPULSE_NO_BODY with all other words 0.  Touch slots at or behind counts[i] are never read.
+   Neither generator reads the query tree or obeys the layer filter; neither is an entry point of the step.
+   Returns NH_ERR_INVALID, before any launch, for a NULL ctx, bodies, in or out (generators: blasts / hits / pushes / counts / touches / out with
+   count > 0); for unknown flags; for `records` NULL with capacity > 0 or not 16-byte aligned; for a count word that is not 4-byte aligned; for a capacity of
+   2^31 or more; for NULL body arrays with bodies->count > 0 (nh_impulse_sums and nh_blast_impulses: transforms; nh_body_impulses: all four); for a sum
+   list that breaks nh_PairList's rules.  Capacity 0 is the empty list: nh_impulse_sums sets *count = 0, nh_body_impulses completes pending work and
+   otherwise does nothing.
+   SCRATCH is the context's: per record of the largest `capacity` seen 60 B (a 32-byte run record, two 8-byte keys, two 4-byte values, one flag word,
+   scanned in place), and 514 KB for the sort.  It grows after a stream synchronise, only when a capacity exceeds every earlier one; nh_destroy frees
+   it.  Everything else is enqueued on the context's stream.
+   HOW: flag the run heads, scan, one lane per run head walks its run with two 16-byte loads per record and writes one partial sum; the
+   stable radix sort orders the run keys over only the 8-bit passes that bits(bodies->count - 1) need; flag the body heads, scan, one lane per body head
+   merges its runs in order and either writes the sum with two 16-byte stores or applies it.  No atomics: the bytes are a function of the input alone.  A
+   body with very many runs is merged by ONE lane: correct and slow; there is no second path.
+   Timing labels: bi_run_flag, bi_runs, bi_body_flag, bi_sums, bi_apply; bi_blast, bi_touch; the sort's and the scan's own between them.
+   MEASURED (tools/body_impulses.py -> profiles/body_impulses.log; one MI355X, one run, the landed config-2 world of 1,004,401 bodies and 4,017,582 contacts; ms per
+   call, the best of 5 blocks of 10 calls by device events):
+     nh_step(1), still steps, before / after the series                                       0.282 / 0.274   (profiles/contact_events_rates.log: 0.280, median 0.291)
+     nh_impulse_sums / nh_body_impulses, one record per body in body order (1,004,400 records)  0.163 / 0.173   (with NH_IMPULSE_WAKE 0.173)
+     nh_impulse_sums / nh_body_impulses, four records per body, shuffled (4,017,600 records)   0.538 / 0.554
+     nh_overlap_wide, nh_overlap_bodies, nh_blast_impulses, nh_impulse_sums: one blast over 6,329 colliders, 6,216 bodies pushed     0.207
+     nh_contact_pairs on the same world's exported views, for scale                             0.306
+   The sort of the run keys -- three passes for 20 key bits -- is 0.12 of the 0.16 ms (0.27 of the 0.54 for 4 M runs of one record), the run walk 0.023 (0.124), the
+   apply 0.027 (0.105: a gather of four scattered partial sums per body); the blast chain is launch-bound (some twenty launches of 6 - 7 us).  The sums equal the host
+   oracle byte for byte on both lists.  No bar was set in advance.
+   Not built: velocity-change records; torque-only records; forces over time; impulses on partitioned worlds; the `namespace nudge` extension; a second
+   path for huge bodies. */
+typedef struct nh_BodyImpulse { float point[3]; uint32_t body; float impulse[3]; uint32_t flags; } nh_BodyImpulse;   /* 32 B, 16-byte aligned */
+enum { NH_IMPULSE_AT_CENTRE = 1u };          /* record flag: `point` is not read, the record has no angular part */
+#define NH_IMPULSE_NO_BODY 0xFFFFFFFFu       /* a record that applies to nobody (what the generators write for "nothing here") */
+typedef struct nh_ImpulseList { const nh_BodyImpulse* records; const uint32_t* count /* device word, or NULL: capacity is the count */; uint32_t capacity; uint32_t reserved; } nh_ImpulseList;
+typedef struct nh_ImpulseSum { uint32_t body; uint32_t count; float linear[3]; float angular[3]; } nh_ImpulseSum;   /* 32 B */
+typedef struct nh_ImpulseSumList { uint32_t* count /* device word */; nh_ImpulseSum* sums /* 16-byte aligned */; uint32_t capacity; uint32_t reserved; } nh_ImpulseSumList;
+enum { NH_IMPULSE_WAKE = 1u };               /* call flag */
+typedef struct nh_Blast { float centre[3]; float radius; float strength; float falloff; uint32_t reserved[2]; } nh_Blast;   /* 32 B */
+typedef struct nh_Push { float mass_over_dt; float max_impulse; uint32_t phases /* bit p: touches of phase p push */; uint32_t flags /* 0 or NH_IMPULSE_AT_CENTRE */; } nh_Push;   /* 16 B, one per mover */
+
+int nh_impulse_sums (nh_context* ctx, const nh_BodyData* bodies, const nh_ImpulseList* in, const nh_ImpulseSumList* out, uint32_t flags /* 0 */);
+int nh_body_impulses(nh_context* ctx, const nh_BodyData* bodies, const nh_ImpulseList* in, uint32_t flags /* 0 or NH_IMPULSE_WAKE */);
+int nh_blast_impulses(nh_context* ctx, const nh_BodyData* bodies, const nh_Blast* blasts, uint32_t count, const nh_HitList* hits, nh_BodyImpulse* out, uint32_t flags /* 0 */);
+/* (nh_touch_impulses is declared behind nh_Touch, with the movers' _touched forms) */
+
 /* nh_distance: how far each of `count` query shapes is from the world of the LAST nh_query_build or nh_query_refit, and towards what -- the clearance
    of a crate, a hull or a limb.  nh_penetration describes a pair that overlaps; this describes the pairs that do not.
    Query shapes: nh_overlap's (NH_SHAPE_SPHERE, NH_SHAPE_BOX, NH_SHAPE_CAPSULE), the same fields read and the same validity rules; the first 48 bytes
@@ -1448,6 +1532,8 @@ int nh_move_touched   (nh_context* ctx, const nh_Move* moves,    uint32_t count,
 int nh_boxmove_touched(nh_context* ctx, const nh_BoxMove* moves, uint32_t count, nh_MoveResult* results, uint32_t k, uint32_t* counts, nh_Touch* touches, uint32_t flags /* 0 */);
 int nh_walk_touched   (nh_context* ctx, const nh_Walk* walks,    uint32_t count, nh_WalkResult* results, uint32_t k, uint32_t* counts, nh_Touch* touches, uint32_t flags /* 0 */);
 int nh_boxwalk_touched(nh_context* ctx, const nh_BoxWalk* walks, uint32_t count, nh_WalkResult* results, uint32_t k, uint32_t* counts, nh_Touch* touches, uint32_t flags /* 0 */);
+/* the touches as impulse records for nh_body_impulses ("body impulses", above): out[i * k + j] of slot j of mover i, count x k records */
+int nh_touch_impulses (nh_context* ctx, const nh_Push* pushes, uint32_t count, uint32_t k, const uint32_t* counts, const nh_Touch* touches, nh_BodyImpulse* out, uint32_t flags /* 0 */);
 
 /* ---- multi-GPU: one x-slab of a world per context ------------------------------------------------------------------------------------
    The world is cut into slabs along x, one rank (process, GPU, nh_context) per slab [lo, hi).  A rank's arrays hold

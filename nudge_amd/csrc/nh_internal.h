@@ -474,10 +474,12 @@ struct nh_context {
 	nh_StateStream stream_state;
 	struct nh_QueryState* query;   // scene queries (nh_query_tree.h): the hierarchy of the last nh_query_build; nullptr until the first
 	struct nh_CpState* contact_events;   // contact events (nh_contact_events.hip): the scratch of nh_contact_pairs / nh_contact_events; nullptr until the first call
+	struct nh_ImpulseState* impulses;    // body impulses (nh_impulse.hip): the scratch of nh_impulse_sums / nh_body_impulses; nullptr until the first call
 };
 int nh_stream_after_advance(nh_context* ctx);          // nh_advance -> state streaming (nh_context.hip)
 void nh_query_free(nh_context* ctx);                   // nh_destroy -> the scene query's buffers (nh_query_build.hip)
 void nh_contact_events_free(nh_context* ctx);          // nh_destroy -> the contact events' scratch (nh_contact_events.hip)
+void nh_impulses_free(nh_context* ctx);                // nh_destroy -> the body impulses' scratch (nh_impulse.hip)
 
 // ---- functions used across the .hip files: each is declared here, once, and defined in the file named behind it --------------------------------------
 // (NH_LOCAL: a helper of the library's own that is not part of what libnudge_hip.so exports)

@@ -51,6 +51,7 @@ EXPORTS = [
     "nh_overlap_wide", "nh_penetration_wide",
     "nh_contact_pairs", "nh_contact_events", "nh_step_contact_pairs",
     "nh_sense", "nh_sense_rays",
+    "nh_impulse_sums", "nh_body_impulses", "nh_blast_impulses", "nh_touch_impulses",
 ]
 HALO_RECORD_BYTES = 64
 
@@ -229,6 +230,40 @@ class ContactList(C.Structure):
 class PairList(C.Structure):
     """nh_PairList: a host struct of device pointers."""
     _fields_ = [("count", C.c_void_p), ("pairs", C.c_void_p), ("capacity", C.c_uint32), ("reserved", C.c_uint32)]
+# body impulses (include/nudge_hip.h): impulse records in, one sum per body out or the bodies' momentum changed
+BODY_IMPULSE = np.dtype([("point", "<f4", 3), ("body", "<u4"), ("impulse", "<f4", 3), ("flags", "<u4")])
+IMPULSE_SUM = np.dtype([("body", "<u4"), ("count", "<u4"), ("linear", "<f4", 3), ("angular", "<f4", 3)])
+BLAST = np.dtype([("centre", "<f4", 3), ("radius", "<f4"), ("strength", "<f4"), ("falloff", "<f4"), ("reserved", "<u4", 2)])
+PUSH = np.dtype([("mass_over_dt", "<f4"), ("max_impulse", "<f4"), ("phases", "<u4"), ("flags", "<u4")])
+NH_IMPULSE_AT_CENTRE = 1                  # record flag: `point` is not read, the record has no angular part
+NH_IMPULSE_NO_BODY = 0xFFFFFFFF           # a record that applies to nobody
+NH_IMPULSE_WAKE = 1                       # call flag of nh_body_impulses: idle_counters[body] = 0 as well
+
+
+class BodyImpulse(C.Structure):
+    _fields_ = [("point", C.c_float * 3), ("body", C.c_uint32), ("impulse", C.c_float * 3), ("flags", C.c_uint32)]
+
+
+class ImpulseList(C.Structure):
+    """nh_ImpulseList: a host struct of device pointers."""
+    _fields_ = [("records", C.c_void_p), ("count", C.c_void_p), ("capacity", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class ImpulseSum(C.Structure):
+    _fields_ = [("body", C.c_uint32), ("count", C.c_uint32), ("linear", C.c_float * 3), ("angular", C.c_float * 3)]
+
+
+class ImpulseSumList(C.Structure):
+    """nh_ImpulseSumList: a host struct of device pointers."""
+    _fields_ = [("count", C.c_void_p), ("sums", C.c_void_p), ("capacity", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class Blast(C.Structure):
+    _fields_ = [("centre", C.c_float * 3), ("radius", C.c_float), ("strength", C.c_float), ("falloff", C.c_float), ("reserved", C.c_uint32 * 2)]
+
+
+class Push(C.Structure):
+    _fields_ = [("mass_over_dt", C.c_float), ("max_impulse", C.c_float), ("phases", C.c_uint32), ("flags", C.c_uint32)]
 REGION = np.dtype([("planes", "<f4", (NH_REGION_MAX_PLANES, 4)), ("plane_count", "<u4"), ("ignore_body", "<u4"), ("reserved", "<u4", 2)])
 
 
@@ -457,6 +492,12 @@ def lib():
         if hasattr(L, "nh_sense"):
             L.nh_sense.argtypes = [C.c_void_p, C.POINTER(BodyData), C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(SenseOut), C.c_uint32]
             L.nh_sense_rays.argtypes = [C.c_void_p, C.POINTER(BodyData), C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
+        # (likewise the body impulses: World.impulse_sums_records / body_impulses_records and the generators then raise AttributeError)
+        if hasattr(L, "nh_body_impulses"):
+            L.nh_impulse_sums.argtypes = [C.c_void_p, C.POINTER(BodyData), C.c_void_p, C.c_void_p, C.c_uint32]
+            L.nh_body_impulses.argtypes = [C.c_void_p, C.POINTER(BodyData), C.c_void_p, C.c_uint32]
+            L.nh_blast_impulses.argtypes = [C.c_void_p, C.POINTER(BodyData), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]
+            L.nh_touch_impulses.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
         _LIB = L
     return _LIB
 
@@ -1796,6 +1837,103 @@ class World:
         if synchronize:
             self.torch.cuda.current_stream(self.dev).synchronize()
         return dict(began=began, ended=ended)
+
+    # ---- body impulses: push, blast and wake bodies on the device (include/nudge_hip.h, "body impulses") ----
+    def _impulse_list(self, what, records, count, capacity):
+        """The nh_ImpulseList of device tensors: `records` at least capacity x 32 bytes (E.BODY_IMPULSE) or None, `count` a device word or None."""
+        if records is not None and records.numel() * records.element_size() < 32 * capacity:
+            raise ValueError(f"{what}: records holds {records.numel() * records.element_size()} bytes, capacity {capacity} needs {32 * capacity}")
+        return ImpulseList(records.data_ptr() if records is not None else 0, count.data_ptr() if count is not None else 0, capacity, 0)
+
+    def impulse_sums_records(self, records, count=None, capacity=0, out=None, bodies=None):
+        """nh_impulse_sums: one 32-byte E.IMPULSE_SUM record per distinct valid body of a list of E.BODY_IMPULSE records on the device, ascending by
+        body.  `count` a device word or None (`capacity` is the count).  `out` = (count, sums, capacity): a device word, None or capacity x 32 bytes,
+        the capacity; None: count only, with a new word.  `bodies`: another E.BodyData than the world's.  Returns `out`.  Enqueued; nothing waits
+        (but a capacity larger than any before grows the scratch)."""
+        torch = self.torch
+        if out is None:
+            out = (torch.zeros(1, dtype=torch.int32, device=self.dev), None, 0)
+        if out[1] is not None and out[1].numel() * out[1].element_size() < 32 * out[2]:
+            raise ValueError(f"impulse_sums_records: sums holds {out[1].numel() * out[1].element_size()} bytes, capacity {out[2]} needs {32 * out[2]}")
+        lst = self._impulse_list("impulse_sums_records", records, count, capacity)
+        o = ImpulseSumList(out[0].data_ptr(), out[1].data_ptr() if out[1] is not None and out[2] else 0, out[2], 0)
+        _check(self.L, self.L.nh_impulse_sums(self.ctx, C.byref(self.bodies if bodies is None else bodies), C.byref(lst), C.byref(o), 0), "nh_impulse_sums")
+        return out
+
+    def body_impulses_records(self, records, count=None, capacity=0, wake=False):
+        """nh_body_impulses: the list's impulses added to the bodies' momentum on the device; wake=True: NH_IMPULSE_WAKE.  Enqueued; nothing waits
+        (but a capacity larger than any before grows the scratch)."""
+        lst = self._impulse_list("body_impulses_records", records, count, capacity)
+        _check(self.L, self.L.nh_body_impulses(self.ctx, C.byref(self.bodies), C.byref(lst), NH_IMPULSE_WAKE if wake else 0), "nh_body_impulses")
+
+    def blast_impulses_records(self, blasts, n, src, out=None):
+        """nh_blast_impulses: `blasts` n x 32 bytes (E.BLAST) on the device, `src` = (offsets, hits, capacity) a hit list for n volumes as
+        overlap_records / overlap_wide_records / region_records / overlap_bodies_records wrote it; `out` capacity x 32 bytes or None: a new tensor
+        filled with NH_IMPULSE_NO_BODY records (only the first min(offsets[n], capacity) are written).  Returns `out`."""
+        torch = self.torch
+        cap = src[2]
+        if out is None:
+            out = torch.zeros((max(cap, 1), 8), dtype=torch.int32, device=self.dev)
+            out[:, 3] = -1
+        elif out.numel() * out.element_size() < 32 * cap:
+            raise ValueError(f"blast_impulses_records: out holds {out.numel() * out.element_size()} bytes, capacity {cap} needs {32 * cap}")
+        if blasts.numel() * blasts.element_size() < 32 * n:
+            raise ValueError(f"blast_impulses_records: blasts holds {blasts.numel() * blasts.element_size()} bytes, {n} blasts need {32 * n}")
+        lst = self._hit_list("blast_impulses_records", n, *src)
+        _check(self.L, self.L.nh_blast_impulses(self.ctx, C.byref(self.bodies), blasts.data_ptr(), n, C.byref(lst), out.data_ptr(), 0), "nh_blast_impulses")
+        return out
+
+    def touch_impulses_records(self, pushes, n, k, counts, touches, out=None):
+        """nh_touch_impulses: `pushes` n x 16 bytes (E.PUSH), `counts` n words and `touches` n x k x 64 bytes as a *_touched_records call wrote them;
+        `out` n x k x 32 bytes or None: a new tensor.  Returns `out`: record i * k + j is slot j of mover i, NH_IMPULSE_NO_BODY where nothing pushes."""
+        torch = self.torch
+        for name, t, size in (("pushes", pushes, 16 * n), ("counts", counts, 4 * n), ("touches", touches, 64 * n * k)):
+            if t.numel() * t.element_size() < size:
+                raise ValueError(f"touch_impulses_records: {name} holds {t.numel() * t.element_size()} bytes, not {size}")
+        if out is None:
+            out = torch.empty((max(n * k, 1), 32), dtype=torch.uint8, device=self.dev)
+        elif out.numel() * out.element_size() < 32 * n * k:
+            raise ValueError(f"touch_impulses_records: out holds {out.numel() * out.element_size()} bytes, not {32 * n * k}")
+        _check(self.L, self.L.nh_touch_impulses(self.ctx, pushes.data_ptr(), n, k, counts.data_ptr(), touches.data_ptr(), out.data_ptr(), 0), "nh_touch_impulses")
+        return out
+
+    def body_impulses(self, bodies, impulses, points=None, wake=True):
+        """Push bodies: `impulses` (n, 3) added to the momentum of `bodies` (n indices), at the world-space `points` (n, 3) or, with points=None, at
+        the bodies' centres (no angular part).  Several records may name one body; they are summed in list order (header, "body impulses").
+        wake=True: the bodies' idle counters are zeroed as well, so that a sleeper -- and with the next step its whole set -- wakes."""
+        torch = self.torch
+        b = torch.as_tensor(bodies, device=self.dev).reshape(-1).to(torch.int64)
+        n = b.shape[0]
+        if n == 0:
+            return self.body_impulses_records(None, capacity=0, wake=wake)
+        rec = torch.zeros((n, 8), dtype=torch.float32, device=self.dev)
+        ri = rec.view(torch.int32)
+        ri[:, 3] = (b & 0xFFFFFFFF).to(torch.int32)          # (int64 -> int32 keeps the low 32 bits)
+        rec[:, 4:7] = torch.as_tensor(impulses, dtype=torch.float32, device=self.dev).reshape(-1, 3)
+        if points is None:
+            ri[:, 7] = NH_IMPULSE_AT_CENTRE
+        else:
+            rec[:, 0:3] = torch.as_tensor(points, dtype=torch.float32, device=self.dev).reshape(-1, 3)
+        self.body_impulses_records(rec, capacity=n, wake=wake)
+
+    def blast(self, centres, radii, strengths, falloff=1.0, wake=True):
+        """Explosions: every body with a collider inside the sphere (centre, radius) gets an impulse away from the centre through its own centre, of
+        strength * (1 - falloff * distance / radius) where that is positive -- overlap_wide, overlap_bodies, blast_impulses, body_impulses against
+        the last query_build(), with nothing downloaded and nothing waited for: each list gets room for one record per collider of the world.
+        `radii`, `strengths`, `falloff`: numbers or n values.  Returns the impulse records (a device tensor, NH_IMPULSE_NO_BODY where nothing was pushed)."""
+        torch = self.torch
+        q, n = self._overlap_queries("blast", centres, radii, None, None, None, None)
+        cap = max(n * (self.colliders.boxes.count + self.colliders.spheres.count), 1)
+        b = torch.zeros((n, 8), dtype=torch.float32, device=self.dev)
+        b[:, 0:3], b[:, 3] = q[:, 0:3], q[:, 8]
+        b[:, 4] = torch.as_tensor(strengths, dtype=torch.float32, device=self.dev).reshape(-1)
+        b[:, 5] = torch.as_tensor(falloff, dtype=torch.float32, device=self.dev).reshape(-1)
+        hits, per_body = (torch.empty((cap, 16), dtype=torch.uint8, device=self.dev) for _ in range(2))
+        offsets, _ = self.overlap_wide_records(q, hits=hits, capacity=cap)
+        body_offsets, _ = self.overlap_bodies_records(n, (offsets, hits, cap), hits=per_body, capacity=cap)
+        out = self.blast_impulses_records(b, n, (body_offsets, per_body, cap))
+        self.body_impulses_records(out, capacity=cap, wake=wake)
+        return out
 
     # ---- measurement ----
     def enable_timing(self, on=True, only=None):
