@@ -79,8 +79,10 @@
  *      exported the views: nh_set_option(ctx, "sync_exports_views", 1) restores that contract at its old price; INTEGRATION.md.)  Any entry point outside the sample's
  *      call order between nh_collide and nh_apply_impulses turns a still step into a full one first, so everything it observes is what a full step
  *      produces.  nh_Counts.still_steps / still_replays count them.
- *      The scene queries (nh_query_build, nh_query_refit, nh_raycast, nh_spherecast, nh_raycast_all, nh_spherecast_all, nh_boxcast_all, nh_capsulecast_all, nh_raycast_k, nh_spherecast_k, nh_boxcast_k, nh_capsulecast_k, nh_boxcast, nh_capsulecast, nh_overlap, nh_penetration, nh_overlap_wide, nh_penetration_wide, nh_region, nh_sense, nh_sense_rays, nh_closest, nh_closest_k, nh_distance, nh_move, nh_recover, nh_walk, nh_boxmove, nh_boxwalk, nh_move_touched, nh_boxmove_touched, nh_walk_touched, nh_boxwalk_touched, nh_query_set_layers, nh_query_filter, nh_query_layer_info) are not entry points of the step in this sense: they neither export nor settle nor turn a still step into a
+ *      The scene queries (nh_query_build, nh_query_refit, nh_raycast, nh_spherecast, nh_raycast_all, nh_spherecast_all, nh_boxcast_all, nh_capsulecast_all, nh_raycast_k, nh_spherecast_k, nh_boxcast_k, nh_capsulecast_k, nh_boxcast, nh_capsulecast, nh_overlap, nh_penetration, nh_overlap_wide, nh_penetration_wide, nh_region, nh_sense, nh_sense_rays, nh_sweep, nh_closest, nh_closest_k, nh_distance, nh_move, nh_recover, nh_walk, nh_boxmove, nh_boxwalk, nh_move_touched, nh_boxmove_touched, nh_walk_touched, nh_boxwalk_touched, nh_query_set_layers, nh_query_filter, nh_query_layer_info) are not entry points of the step in this sense: they neither export nor settle nor turn a still step into a
  *      full one, and they do not count -- see "scene queries" below.
+ *      nh_body_impulses and nh_sweep_limit WRITE momentum from outside the step: they complete pending work first and, without NH_IMPULSE_WAKE, leave speculation to
+ *      the checks above -- see "body impulses" and "fast bodies" below.
  *
  * Threading: one context = one HIP stream = one world at a time; no global mutable state.
  */
@@ -1181,6 +1183,78 @@ int nh_impulse_sums (nh_context* ctx, const nh_BodyData* bodies, const nh_Impuls
 int nh_body_impulses(nh_context* ctx, const nh_BodyData* bodies, const nh_ImpulseList* in, uint32_t flags /* 0 or NH_IMPULSE_WAKE */);
 int nh_blast_impulses(nh_context* ctx, const nh_BodyData* bodies, const nh_Blast* blasts, uint32_t count, const nh_HitList* hits, nh_BodyImpulse* out, uint32_t flags /* 0 */);
 /* (nh_touch_impulses is declared behind nh_Touch, with the movers' _touched forms) */
+
+/* ---- fast bodies: sweep the colliders that travel far along their velocity, stop their bodies at the hit ------------------------------------------
+   The engine steps discretely, as the reference does, and the reference has no sweep: a body that travels further in one step than a thin obstacle is
+   deep leaves no contact and passes through it (a ball of radius 0.25 at 240 m/s and 1/120 s moves 2 m a step: a wall 0.1 thick never sees it).
+   nh_sweep takes the casts from the bodies' own state and nh_sweep_limit applies the result, with no download between them:
+       nh_step, nh_query_refit, nh_sweep, nh_sweep_limit          -- every step; a tunnelling guard that never leaves the device
+   Both are opt-in: no other call changes a byte.
+   THE SWEEP OF A COLLIDER.  For the combined collider index c (boxes first, then spheres) take its record in the tree of the last nh_query_build /
+   nh_query_refit: world position p_c, rotation q_c, half extents h (a sphere: its radius in h.x), body b, tag.  bodies->transforms and bodies->momentum
+   are read as the stream has them.  In fp32, exactly nudge_amd/csrc/nh_query.h ("fast bodies"), only + - * and compares, no contraction:
+       r = p_c - transforms[b].position                                                     (componentwise)
+       u = velocity + (w.y * r.z - w.z * r.y, w.z * r.x - w.x * r.z, w.x * r.y - w.y * r.x)   (w the angular velocity: two products, one subtraction, one sum)
+       d = u * time_step
+       m = the smallest of the three half extents (a sphere: the radius);  s = min_travel * m
+   SELECTED iff 0 < b < bodies->count and ((d.x * d.x + d.y * d.y) + d.z * d.z) > s * s.  A NaN anywhere makes the comparison false: body 0, a collider of
+   a body that does not exist (a NaN pose) and non-finite momentum are never swept; the state of a body >= bodies->count is not read.
+   THE CAST of a selected collider is a 64-byte record.  A box gives the nh_BoxCast { origin = p_c, max_t = 1.0f, direction = d, ignore_body = b,
+   rotation = q_c, size = h * core (one product per component), reserved = 0 }; a sphere the nh_CapsuleCast { the same head, rotation = (0, 0, 0, 1),
+   radius = h.x * core, half_height = 0, reserved = 0 } -- by nh_capsulecast's own contract nh_spherecast's ball of that radius.  Nothing rotates during
+   a sweep, and other dynamic bodies stand where the tree has them.
+   `core`, in [0, 1]: only the inner `core` share of the shape is swept, because touching counts in the cast predicates: a body that rests on or slides
+   along the ground would start every sweep of its full shape in contact at t = 0, while its core does not.
+   nh_sweep lists the selected colliders in ascending combined index -- boxes before spheres.  counts[0] / counts[1] ALWAYS receive the true numbers of
+   selected boxes / spheres.  Entry i writes colliders[i] (the combined index), casts[i] (the record above) and hits[i]: EXACTLY the 32 bytes nh_boxcast
+   writes for casts[i] with flags 0 under the context's filter -- for a sphere entry nh_capsulecast's bytes, which are nh_spherecast's for the ball
+   (head, radius).  That identity is the whole contract of `hits`: start overlaps of the core, the reach rule, ties and NaN handling are the casts' own
+   rules.  Under NH_FILTER_PER_QUERY the query is the COLLIDER: masks[c] is read by combined index (boxes + spheres words in all).
+   A NULL channel costs nothing; with hits == NULL nothing walks the tree.  The channels are written iff counts[0] + counts[1] <= capacity -- all or none,
+   and no byte behind the written records is touched (nh_contact_pairs' rule); capacity == 0 with all three channels NULL counts only.  A tree of zero
+   colliders writes counts 0, 0.
+   nh_sweep returns NH_ERR_INVALID, before any launch and writing nothing: before any nh_query_build; for a NULL ctx, bodies, params, list or
+   list->counts; for bodies->transforms or bodies->momentum NULL with bodies->count > 0; for counts / colliders not 4-byte or casts / hits not 16-byte
+   aligned; for flags != 0; for capacity >= 2^31; for a channel given with capacity 0; for time_step, min_travel or core not finite, min_travel or core
+   negative, or core > 1.
+   An OBSERVER like nh_sense (note 9): no view export, no settling of deferred gravity, no still step turned into a full one, no change to nh_Counts.  It
+   never waits for a count: its kernels read the device counts, its grids are sized from `capacity` and the tree and stride.  It allocates one flag /
+   scan word per collider of the tree, on first use or when the tree has grown, behind a stream synchronise (as nh_overlap's scratch).
+   HOW: one lane per collider computes the rule and writes a flag; the library's scan gives the places; a gather writes `colliders` and
+   `casts`.  Then two walk kernels, one per shape so that a wave is homogeneous, over the entries [0, counts[0]) and [counts[0], total), one lane per ENTRY:
+   the lane finds its collider by binary search in the scan words, rebuilds the cast in registers, and answers it with nh_boxcast's / nh_spherecast's own
+   per-cast body.  No cast record is read back.  Compacting before the walk is the point: in a world at rest with a few thousand fast bodies a
+   lane-per-collider walk would run waves with one live lane.  Timing labels: q_sweep_flag, q_sweep_gather, q_sweep_box, q_sweep_ball.
+   nh_sweep_limit reads counts, colliders and hits of a list nh_sweep filled (casts is not read; a total above capacity means nothing was written and
+   nothing is read).  The body of entry i is that of collider colliders[i] in the tree, as nh_sweep saw it.  An entry LIMITS iff its hit is a real one
+   (shape != NH_SHAPE_NONE) with t > 0; a core that starts in overlap (t == 0) limits nothing -- the body is already deep inside, and contacts are what
+   frees it.  f_b = the smallest such t over body b's entries, 1.0f when none limits.  For every body with f_b < 1 ONE lane loads its nh_BodyMomentum's
+   first 16 bytes, multiplies velocity[c] *= f_b (three products) and stores them; every other word keeps its bits: the angular velocity and the idle counter are
+   not written.  factors[i], if given, receives f of entry i's body (1.0f for an entry that names no collider of the tree or no body).  The minimum of
+   non-negative floats does not depend on the order (an atomic min on the bit patterns): the bytes are a function of the input alone.  The work is
+   proportional to the list: the per-body words (8 B per body of bodies->count, allocated as above) are never cleared, the list's own entries set the
+   ones they use.  Timing labels: q_limit_init, q_limit_min, q_limit_apply.
+   RELATION TO THE STEP: exactly nh_body_impulses' without NH_IMPULSE_WAKE -- it completes pending work first, then leaves speculation to the device-side
+   checks of note 9.  Returns NH_ERR_INVALID for a NULL ctx, bodies, list or list->counts, before any nh_query_build, for flags != 0, for
+   bodies->momentum NULL with bodies->count > 0, for the alignments above (factors: 4 bytes), for capacity >= 2^31 and for capacity > 0 with colliders or
+   hits NULL.  Capacity 0 completes pending work and otherwise does nothing.
+   WHAT THIS BUYS: the limited body's next nh_advance ends with its core touching the obstacle, and the step after that finds an ordinary contact, at
+   a depth of at most (1 - core) of the shape.  WHAT IT COSTS: the clamped share of the momentum is gone; the reference's contacts are inelastic, so
+   against static geometry nothing else is lost.
+   MEASURED: NOT MEASURED YET (tools/fast_bodies.py -> profiles/sweep_rates.log has not been run on a GPU; no bar is set in advance).
+   Not built: rotation during the sweep; the coming step's gravity in d (2.7 mm per step squared at 60 Hz); sweeps relative to other moving bodies;
+   restoring the speed after the impact step; speculative contacts; partitioned worlds. */
+typedef struct nh_SweepParams { float time_step; float min_travel; float core; uint32_t reserved; } nh_SweepParams;      /* 16 B */
+typedef struct nh_SweepList {
+    uint32_t* counts;      /* device, 2 words, always written: selected boxes, selected spheres */
+    uint32_t* colliders;   /* device, capacity words or NULL: combined indices, ascending */
+    nh_BoxCast* casts;     /* device, capacity x 64 B or NULL: the records above */
+    nh_RayHit* hits;       /* device, capacity x 32 B or NULL */
+    uint32_t capacity;
+    uint32_t reserved;
+} nh_SweepList;
+int nh_sweep(nh_context* ctx, const nh_BodyData* bodies, const nh_SweepParams* params, const nh_SweepList* list, uint32_t flags /* 0 */);
+int nh_sweep_limit(nh_context* ctx, const nh_BodyData* bodies, const nh_SweepList* list, float* factors /* device floats, capacity, or NULL */, uint32_t flags /* 0 */);
 
 /* nh_distance: how far each of `count` query shapes is from the world of the LAST nh_query_build or nh_query_refit, and towards what -- the clearance
    of a crate, a hull or a limb.  nh_penetration describes a pair that overlaps; this describes the pairs that do not.

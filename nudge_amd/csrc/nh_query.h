@@ -1,7 +1,7 @@
 // nh_query.h -- per-item arithmetic of the scene query (nh_query_build / nh_raycast / nh_spherecast / nh_boxcast / nh_capsulecast / nh_overlap /
 // nh_closest / nh_distance, nh_query.hip): a collider's world pose, a ray against one box and against one sphere, the overlap predicates of a query sphere, box or
 // capsule against one collider, a swept ball, box and capsule against one box and one sphere, the signed distance of a point from one box and one
-// sphere, the per-plane test of nh_region, the ray of a (sensor, beam) of nh_sense, with the walk's node tests they are pruned by.
+// sphere, the per-plane test of nh_region, the ray of a (sensor, beam) of nh_sense, the sweep of a collider along its own velocity of nh_sweep, with the walk's node tests they are pruned by.
 //
 // Every function is `NH_HD` so that tests/hostquery (hostoverlap, hostsweep, hostboxcast, hostcapsule, hostpoint, hostregion) builds the SAME arithmetic with g++ -ffp-contract=off and gets the device's bits: the
 // brute force over all colliders there is the oracle of the GPU's tree traversal.  Only + - * /, sqrtf (correctly rounded on both sides)
@@ -1683,5 +1683,28 @@ NH_HD nh_QSensorRay nh_q_sensor_ray(nh_QPose w, bool exists, nh_f3 beam, float r
 	r.d = exists ? nh_rotate(w.q, beam) : w.p;
 	return r;
 }
+
+// ---- fast bodies (nh_sweep, nh_sweep_limit): the sweep of a collider along its own velocity --------------------------------------------------------
+// A collider at p_c of body b (position p_b, velocity v, angular velocity w) travels d = (v + w x (p_c - p_b)) * time_step in the coming step: two
+// products and one subtraction per component of the cross product, one sum, one product -- only + - *, so the host oracle
+// (tests/hostoracle/hostsweep.cpp) gets the device's bits.  It is SELECTED iff its body is a dynamic one that exists and |d|^2 > (min_travel * m)^2, m its
+// smallest half extent (a sphere: its radius); any NaN makes the comparison false.  The cast is (origin = p_c, max_t = 1, direction = d, ignore_body =
+// b, rotation, size = h * core): nh_BoxCast's words for a box, nh_CapsuleCast's with the identity rotation, radius h.x * core and half height 0 for a sphere.
+NH_HD nh_f3 nh_q_sweep_travel(nh_f3 pc, nh_f3 pb, nh_f3 v, nh_f3 w, float time_step) {
+	const nh_f3 r = nh_make3(pc.x - pb.x, pc.y - pb.y, pc.z - pb.z);
+	const nh_f3 u = nh_make3(v.x + (w.y * r.z - w.z * r.y), v.y + (w.z * r.x - w.x * r.z), v.z + (w.x * r.y - w.y * r.x));
+	return nh_make3(u.x * time_step, u.y * time_step, u.z * time_step);
+}
+// (asked BEFORE the body's state is read: a body that does not exist has none)
+NH_HD bool nh_q_sweep_body(uint32_t body, uint32_t body_count) { return body > 0u && body < body_count; }
+NH_HD bool nh_q_sweep_far(nh_f3 d, nh_f3 h, bool box, float min_travel) {
+	const float m = box ? nh_min(nh_min(h.x, h.y), h.z) : h.x;
+	const float s = min_travel * m;
+	return ((d.x * d.x + d.y * d.y) + d.z * d.z) > s * s;
+}
+// the swept core: words 12 .. 14 of the cast record (a sphere: radius, half height 0, and the first reserved word 0)
+NH_HD nh_f3 nh_q_sweep_core(nh_f3 h, bool box, float core) { return box ? nh_make3(h.x * core, h.y * core, h.z * core) : nh_make3(h.x * core, 0.0f, 0.0f); }
+// an entry LIMITS its body iff its hit is a real one behind the start: a core that starts in overlap (t == 0) limits nothing
+NH_HD bool nh_q_sweep_limits(uint32_t shape, float t) { return shape != 0xffffffffu /* NH_SHAPE_NONE */ && t > 0.0f; }
 
 #endif

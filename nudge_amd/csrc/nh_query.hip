@@ -4,12 +4,15 @@
 // (_all) and first-k (_k) forms, nh_closest / nh_closest_k / nh_distance (the nearest colliders to a point or a shape) and nh_overlap / nh_penetration (the
 // colliders touching each of a batch of spheres, boxes or capsules, as variable-length segments) and nh_move (collide-and-slide: the capsule cast in a loop) and nh_recover
 // (shapes pushed out of what they overlap: the overlap walk in a loop, the penetration functions at its leaves).
+// nh_sweep / nh_sweep_limit ("fast bodies": the colliders that travel far, swept along their own velocity through the closest-hit casts' body, and their bodies stopped at the hit).
 // nh_region (the colliders inside each of a batch of convex regions, through nh_overlap's chain) does not walk: it sweeps the leaves below the tree's entry nodes.
 // nh_overlap_wide / nh_penetration_wide (nh_overlap's and nh_penetration's bytes for large volumes) sweep the same way, with nh_overlap's predicates.
 // include/nudge_hip.h, "scene queries".
 // Layer masks (include/nudge_hip.h, "layer masks"): every query call walks under the mask(s) nh_query_filter set, in the FILTER = true instantiation of its kernel.
 // Traversal is stackless: a node that is missed or a leaf that is done continues at its ESCAPE link (the next node in pre-order after its subtree),
 // a hit internal node at its left child.  A private stack array would go to scratch memory.
+#include <algorithm>
+#include <cmath>
 #include <type_traits>
 #include <utility>
 #include "nh_query_tree.h"
@@ -166,6 +169,13 @@ struct nh_QBall : nh_QCastHead {
 	__device__ __forceinline__ void read(const float4* __restrict__ cp) {
 		head(cp[0], cp[1]);
 		r = cp[2].x;
+		ok = ok && nh_q_finite(r) && !(r < 0.0f);
+		w = r + nh_q_cast_pad(o, r);
+	}
+	// the same decode from registers, for k_q_sweep, which builds each of its casts there (read() stays as it is: its kernels keep their code)
+	__device__ __forceinline__ void set(float4 c0, float4 c1, float radius) {
+		head(c0, c1);
+		r = radius;
 		ok = ok && nh_q_finite(r) && !(r < 0.0f);
 		w = r + nh_q_cast_pad(o, r);
 	}
@@ -421,6 +431,150 @@ __global__ __launch_bounds__(256) void k_q_sense_rays(const nh_Sensor* __restric
 		rp[0] = make_float4(r.o.x, r.o.y, r.o.z, r.max_t);
 		rp[1] = make_float4(r.d.x, r.d.y, r.d.z, __uint_as_float(r.ignore));
 	});
+}
+
+// ---- fast bodies ----------------------------------------------------------------------------------------------------------------------------------
+// nh_sweep, nh_sweep_limit (header, "fast bodies"): every collider that travels far in the coming step is swept along its own velocity, and
+// its body's velocity cut to where the sweep first touches.  The per-item arithmetic is nh_query.h's ("fast bodies"), which the host oracle runs as well.
+//   k_q_sweep_flag     one lane per collider: its travel d from the tree's record and its body's state, 1 where it is selected; a closing 0
+//   nh_scan_u32        in place: a selected collider's word is its place in the list, word nbox the number of boxes, word n the total
+//   k_q_sweep_gather   one lane per collider: a selected one writes its index and its 64-byte cast record at its place -- iff the total fits; its first
+//                      lane writes the two counts
+//   k_q_sweep<BALL>    one lane per ENTRY of one shape's share of the list, [0, boxes) or [boxes, total): the lane finds its collider in the scan
+//                      words (the last c whose word is <= the entry: 20 probes for a million colliders, against a walk of hundreds of nodes), rebuilds the
+//                      cast in registers as the gather built it, decodes it through nh_QBox::set / nh_QBall::set and answers through nh_q_cast_one,
+//                      nh_boxcast's and nh_spherecast's own body.  No cast record is read back, and a wave holds casts of one shape
+//   k_q_limit_init     one lane per entry: its body's two words = (1.0f, nobody)
+//   k_q_limit_min      one lane per entry: atomic min of the entry into its body's second word and, where the entry limits, of t's bits into the first
+//                      (non-negative floats order as their bits do, and a minimum does not depend on the order: the bytes are a function of the input)
+//   k_q_limit_apply    one lane per entry: the factor out; the one entry a body's second word names scales the body's velocity
+// Every collider index read from a list is checked against n, every body index against the body count, every entry against the capacity.
+struct nh_QSweepIn { const nh_Transform* transforms; const nh_BodyMomentum* momentum; uint32_t body_count; float time_step, min_travel, core; };
+
+// The cast of collider c as four 16-byte words (nh_BoxCast's; a sphere's: nh_CapsuleCast's), and whether it is selected.  A body that does not exist is
+// not read.
+struct nh_QSweepCast { float4 c0, c1, c2, c3; bool selected; };
+__device__ __forceinline__ nh_QSweepCast nh_q_sweep_cast(const nh_QRec& r, bool box, const nh_QSweepIn& in) {
+	nh_QSweepCast k;
+	const uint32_t b = __float_as_uint(r.a.w);
+	k.selected = nh_q_sweep_body(b, in.body_count);
+	nh_f3 d = nh_make3(0.0f, 0.0f, 0.0f);
+	const nh_f3 h = nh_make3(r.c.x, r.c.y, r.c.z);
+	if (k.selected) {
+		const float4 pb = *reinterpret_cast<const float4*>(in.transforms + b);
+		const float4* m = reinterpret_cast<const float4*>(in.momentum + b);
+		const float4 v = m[0], w = m[1];
+		d = nh_q_sweep_travel(nh_make3(r.a.x, r.a.y, r.a.z), nh_make3(pb.x, pb.y, pb.z), nh_make3(v.x, v.y, v.z), nh_make3(w.x, w.y, w.z), in.time_step);
+		k.selected = nh_q_sweep_far(d, h, box, in.min_travel);
+	}
+	const nh_f3 s = nh_q_sweep_core(h, box, in.core);
+	k.c0 = make_float4(r.a.x, r.a.y, r.a.z, 1.0f);
+	k.c1 = make_float4(d.x, d.y, d.z, r.a.w);
+	k.c2 = box ? r.b : make_float4(0.0f, 0.0f, 0.0f, 1.0f);
+	k.c3 = make_float4(s.x, s.y, s.z, 0.0f);
+	return k;
+}
+
+__global__ __launch_bounds__(256) void k_q_sweep_flag(const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox, nh_QSweepIn in, uint32_t* __restrict__ scan) {
+	for (uint32_t c = blockIdx.x * blockDim.x + threadIdx.x; c <= n; c += gridDim.x * blockDim.x)
+		scan[c] = c < n && nh_q_sweep_cast(rec[c], c < nbox, in).selected ? 1u : 0u;
+}
+
+__global__ __launch_bounds__(256) void k_q_sweep_gather(const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox, nh_QSweepIn in, const uint32_t* __restrict__ scan,
+                                                        uint32_t* __restrict__ counts, uint32_t* __restrict__ colliders, nh_BoxCast* __restrict__ casts, uint32_t capacity) {
+	const uint32_t boxes = scan[nbox], total = scan[n];
+	if (blockIdx.x == 0 && threadIdx.x == 0) { counts[0] = boxes; counts[1] = total - boxes; }
+	if ((!colliders && !casts) || total > capacity) return;          // all or none
+	for (uint32_t c = blockIdx.x * blockDim.x + threadIdx.x; c < n; c += gridDim.x * blockDim.x) {
+		const uint32_t at = scan[c];
+		if (scan[c + 1u] == at || at >= capacity) continue;          // not selected
+		if (colliders) colliders[at] = c;
+		if (!casts) continue;
+		const nh_QSweepCast k = nh_q_sweep_cast(rec[c], c < nbox, in);
+		float4* cp = reinterpret_cast<float4*>(casts + at);
+		cp[0] = k.c0; cp[1] = k.c1; cp[2] = k.c2; cp[3] = k.c3;
+	}
+}
+
+// the collider of entry e among [lo, hi): the last c whose scan word is <= e (the words do not decrease, and a selected collider's is its own place)
+__device__ __forceinline__ uint32_t nh_q_sweep_find(const uint32_t* __restrict__ scan, uint32_t lo, uint32_t hi, uint32_t e) {
+	while (hi - lo > 1u) {
+		const uint32_t mid = lo + (hi - lo) / 2u;
+		if (scan[mid] <= e) lo = mid; else hi = mid;
+	}
+	return lo;
+}
+
+// (the hint: k_q_boxcast's, for the same box-box test under the same walk; the ball's walk needs none, as k_q_spherecast's)
+template <bool BALL, bool FILTER>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BALL ? 0 : FILTER ? 3 : 4)))
+void k_q_sweep(const nh_QRec* __restrict__ rec, uint32_t n, uint32_t nbox, nh_QSweepIn in, const uint32_t* __restrict__ scan, nh_RayHit* __restrict__ hits,
+               uint32_t capacity, const nh_QNode* __restrict__ nodes, nh_QFilter F) {
+	const uint32_t boxes = scan[nbox], total = scan[n];
+	if (total > capacity) return;
+	const uint32_t first = BALL ? boxes : 0u, end = BALL ? total : boxes, c_lo = BALL ? nbox : 0u, c_hi = BALL ? n : nbox;
+	for (uint32_t e = first + blockIdx.x * blockDim.x + threadIdx.x; e < end; e += gridDim.x * blockDim.x) {
+		const uint32_t c = nh_q_sweep_find(scan, c_lo, c_hi, e);
+		const nh_QSweepCast k = nh_q_sweep_cast(rec[c], !BALL, in);
+		typename std::conditional<BALL, nh_QBall, nh_QBox>::type shape;
+		if constexpr (BALL) shape.set(k.c0, k.c1, k.c3.x);
+		else shape.set(k.c0, k.c1, k.c2, k.c3);
+		float bt;
+		uint32_t bc;
+		nh_f3 bn;
+		nh_q_cast_one<FILTER>(shape, nodes, rec, n, nbox, 0u, F, FILTER ? F.of(c) : 0u, bt, bc, bn);
+		nh_q_write_hit(hits + e, rec, nbox, shape.ok, bc, bt, bn);
+	}
+}
+
+// the entries of a list nh_sweep filled, as nh_sweep_limit reads them: none where the list was not written
+struct nh_QSweepEntries { const uint32_t* counts; const uint32_t* colliders; const nh_RayHit* hits; uint32_t capacity; };
+__device__ __forceinline__ uint32_t nh_q_limit_total(const nh_QSweepEntries& L) {
+	const uint32_t a = L.counts[0], b = L.counts[1];
+	return a <= L.capacity && b <= L.capacity - a ? a + b : 0u;
+}
+// the body of entry i, or NH_Q_NONE for an entry that names no collider of the tree or no body of the call
+__device__ __forceinline__ uint32_t nh_q_limit_body(const nh_QSweepEntries& L, uint32_t i, const nh_QRec* __restrict__ rec, uint32_t n, uint32_t body_count) {
+	const uint32_t c = L.colliders[i];
+	if (c >= n) return NH_Q_NONE;
+	const uint32_t b = __float_as_uint(rec[c].a.w);
+	return b < body_count ? b : NH_Q_NONE;
+}
+
+__global__ __launch_bounds__(256) void k_q_limit_init(nh_QSweepEntries L, const nh_QRec* __restrict__ rec, uint32_t n, uint32_t body_count, uint2* __restrict__ words) {
+	const uint32_t total = nh_q_limit_total(L);
+	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+		const uint32_t b = nh_q_limit_body(L, i, rec, n, body_count);
+		if (b != NH_Q_NONE) words[b] = make_uint2(0x3f800000u, NH_Q_NONE);          // (every entry of a body stores the same two words)
+	}
+}
+
+__global__ __launch_bounds__(256) void k_q_limit_min(nh_QSweepEntries L, const nh_QRec* __restrict__ rec, uint32_t n, uint32_t body_count, uint2* __restrict__ words) {
+	const uint32_t total = nh_q_limit_total(L);
+	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+		const uint32_t b = nh_q_limit_body(L, i, rec, n, body_count);
+		if (b == NH_Q_NONE) continue;
+		atomicMin(&words[b].y, i);
+		const float4 h0 = reinterpret_cast<const float4*>(L.hits + i)[0];
+		const uint32_t shape = reinterpret_cast<const uint32_t*>(L.hits + i)[6];
+		if (nh_q_sweep_limits(shape, h0.x)) atomicMin(&words[b].x, __float_as_uint(h0.x));
+	}
+}
+
+__global__ __launch_bounds__(256) void k_q_limit_apply(nh_QSweepEntries L, const nh_QRec* __restrict__ rec, uint32_t n, uint32_t body_count, const uint2* __restrict__ words,
+                                                       nh_BodyMomentum* __restrict__ momentum, float* __restrict__ factors) {
+	const uint32_t total = nh_q_limit_total(L);
+	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+		const uint32_t b = nh_q_limit_body(L, i, rec, n, body_count);
+		const uint2 w = b != NH_Q_NONE ? words[b] : make_uint2(0x3f800000u, NH_Q_NONE);
+		const float f = __uint_as_float(w.x);
+		if (factors) factors[i] = f;
+		if (w.y != i || !(f < 1.0f)) continue;
+		float4* m = reinterpret_cast<float4*>(momentum + b);
+		float4 v = m[0];          // (.w: unused0, stored back as loaded)
+		v.x *= f; v.y *= f; v.z *= f;
+		m[0] = v;
+	}
 }
 
 // ---- move -------------------------------------------------------------------------------------------------------------------------------------
@@ -1395,6 +1549,72 @@ extern "C" int nh_sense_rays(nh_context* ctx, const nh_BodyData* bodies, const n
 	if (!rays || ((uintptr_t)rays & 15u)) return NH_ERR_INVALID;
 	NH_LAUNCH(ctx, "q_sense_rays", k_q_sense_rays, nh_sense_grid(count, beam_count), 256, sensors, count, beams, beam_count,
 	          bodies ? bodies->transforms : nullptr, bodies ? bodies->count : 0u, rays);
+	return NH_OK;
+}
+
+// nh_sweep's flag and scan words, by collider of the tree (a growth waits for the stream first, as nh_overlap_reserve's does)
+static int nh_sweep_reserve(nh_context* ctx, uint32_t colliders) {
+	nh_QueryState* q = ctx->query;
+	if (q->sw_scan && colliders <= q->sw_capacity) return NH_OK;
+	const uint32_t cap = colliders + colliders / 8u + 64u;          // (colliders < 2^30)
+	NH_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+	q->sw_capacity = 0;
+	{ int rc = nh_device_buffers(ctx, { { &q->sw_scan, sizeof(uint32_t) * ((size_t)cap + 1u + 16u) } }); if (rc) return rc; }
+	q->sw_capacity = cap;
+	return NH_OK;
+}
+
+extern "C" int nh_sweep(nh_context* ctx, const nh_BodyData* bodies, const nh_SweepParams* params, const nh_SweepList* list, uint32_t flags) {
+	if (!ctx || !ctx->query || !ctx->query->built || flags || !bodies || !params || !list || !list->counts) return NH_ERR_INVALID;
+	if (bodies->count && (!bodies->transforms || !bodies->momentum)) return NH_ERR_INVALID;
+	if ((((uintptr_t)list->counts | (uintptr_t)list->colliders) & 3u) || (((uintptr_t)list->casts | (uintptr_t)list->hits) & 15u)) return NH_ERR_INVALID;
+	if (list->capacity >= 0x80000000u || (!list->capacity && (list->colliders || list->casts || list->hits))) return NH_ERR_INVALID;
+	const float ts = params->time_step, mt = params->min_travel, core = params->core;
+	if (!std::isfinite(ts) || !std::isfinite(mt) || !std::isfinite(core) || !(mt >= 0.0f) || !(core >= 0.0f) || !(core <= 1.0f)) return NH_ERR_INVALID;
+	NH_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+	nh_QueryState* q = ctx->query;
+	if (q->n == 0u) {          // no collider: no entry
+		NH_HIP_CHECK(ctx, hipMemsetAsync(list->counts, 0, 2u * sizeof(uint32_t), ctx->stream));
+		return NH_OK;
+	}
+	{ const int rc = nh_sweep_reserve(ctx, q->n); if (rc) return rc; }
+	const nh_QSweepIn in{ bodies->transforms, bodies->momentum, bodies->count, ts, mt, core };
+	const uint32_t per_collider = nh_grid_for((uint64_t)q->n + 1u, 256, 1u << 16);
+	NH_LAUNCH(ctx, "q_sweep_flag", k_q_sweep_flag, per_collider, 256, q->rec, q->n, q->nbox, in, q->sw_scan);
+	nh_scan_u32(ctx, q->sw_scan, q->sw_scan, &q->ctl->zero, q->n + 1u, q->hist, nullptr);
+	NH_LAUNCH(ctx, "q_sweep_gather", k_q_sweep_gather, per_collider, 256, q->rec, q->n, q->nbox, in, q->sw_scan, list->counts, list->colliders, list->casts, list->capacity);
+	if (!list->hits) return NH_OK;
+	bool on;
+	const nh_QFilter F = nh_query_filter_of(q, &on);
+	// (the device knows how many entries there are; the host only that a share is no longer than the capacity or than its shape's colliders)
+	const uint32_t nsph = q->n - q->nbox;
+	if (q->nbox) NH_LAUNCH(ctx, "q_sweep_box", on ? (k_q_sweep<false, true>) : (k_q_sweep<false, false>), nh_grid_for(std::min(list->capacity, q->nbox), 256, 1u << 20), 256,
+	                       q->rec, q->n, q->nbox, in, q->sw_scan, list->hits, list->capacity, q->nodes, F);
+	if (nsph) NH_LAUNCH(ctx, "q_sweep_ball", on ? (k_q_sweep<true, true>) : (k_q_sweep<true, false>), nh_grid_for(std::min(list->capacity, nsph), 256, 1u << 20), 256,
+	                    q->rec, q->n, q->nbox, in, q->sw_scan, list->hits, list->capacity, q->nodes, F);
+	return NH_OK;
+}
+
+extern "C" int nh_sweep_limit(nh_context* ctx, const nh_BodyData* bodies, const nh_SweepList* list, float* factors, uint32_t flags) {
+	if (!ctx || !ctx->query || !ctx->query->built || flags || !bodies || !list || !list->counts) return NH_ERR_INVALID;
+	if (bodies->count && !bodies->momentum) return NH_ERR_INVALID;
+	if ((((uintptr_t)list->counts | (uintptr_t)list->colliders | (uintptr_t)factors) & 3u) || ((uintptr_t)list->hits & 15u)) return NH_ERR_INVALID;
+	if (list->capacity >= 0x80000000u || (list->capacity && (!list->colliders || !list->hits))) return NH_ERR_INVALID;
+	{ int rc = nh_flush_pending(ctx); if (rc) return rc; }          // momentum is written: whatever was deferred comes first
+	if (list->capacity == 0u || bodies->count == 0u) return NH_OK;          // no entry can be read: nobody is limited
+	NH_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+	nh_QueryState* q = ctx->query;
+	if (bodies->count > q->sw_body_capacity) {          // (a growth waits for the stream first; the words are never cleared: a list's entries set the ones they use)
+		NH_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+		q->sw_body_capacity = 0;
+		{ int rc = nh_device_buffers(ctx, { { &q->sw_body, sizeof(uint2) * (size_t)bodies->count } }); if (rc) return rc; }
+		q->sw_body_capacity = bodies->count;
+	}
+	const nh_QSweepEntries L{ list->counts, list->colliders, list->hits, list->capacity };
+	const uint32_t grid = nh_grid_for(std::min(list->capacity, q->n ? q->n : 1u), 256, 1u << 16);
+	NH_LAUNCH(ctx, "q_limit_init", k_q_limit_init, grid, 256, L, q->rec, q->n, bodies->count, q->sw_body);
+	NH_LAUNCH(ctx, "q_limit_min", k_q_limit_min, grid, 256, L, q->rec, q->n, bodies->count, q->sw_body);
+	NH_LAUNCH(ctx, "q_limit_apply", k_q_limit_apply, grid, 256, L, q->rec, q->n, bodies->count, q->sw_body, bodies->momentum, factors);
 	return NH_OK;
 }
 

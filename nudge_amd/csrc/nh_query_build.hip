@@ -308,7 +308,7 @@ void nh_query_free(nh_context* ctx) {
 	nh_QueryState* q = ctx->query;
 	if (!q) return;
 	void* bufs[] = { q->ctl, q->rec, q->keys_a, q->keys_b, q->idx_a, q->idx_b, q->hist, q->nodes, q->parent, q->rchild, q->last, q->right_at, q->arrive, q->top,
-	                 q->ov_keys_a, q->ov_keys_b, q->ov_vals_a, q->ov_vals_b, q->layers, q->node_layers, q->rg_cursor, q->ev_scan, q->ev_ctl };
+	                 q->ov_keys_a, q->ov_keys_b, q->ov_vals_a, q->ov_vals_b, q->layers, q->node_layers, q->rg_cursor, q->ev_scan, q->ev_ctl, q->sw_scan, q->sw_body };
 	for (void* b : bufs) if (b) hipFree(b);
 	delete q;
 	ctx->query = nullptr;

@@ -50,6 +50,10 @@ struct nh_QueryState {
 	uint32_t ev_capacity;        // nh_overlap_bodies' / nh_overlap_events' flag and scan words, by record of the input capacities' sum (ev_scan: that + 2 words)
 	uint32_t* ev_scan;
 	struct nh_QEventCtl* ev_ctl; // their control words (allocated with the first scratch)
+	uint32_t sw_capacity;        // nh_sweep's flag and scan words, by collider of the tree (sw_scan: that + 1 word and the scan's slack)
+	uint32_t* sw_scan;
+	uint32_t sw_body_capacity;   // nh_sweep_limit's words, by body: (bits of the least limiting t, the entry that applies it); only the words a list names are ever set
+	uint2* sw_body;
 	// layer masks (header, "layer masks"): the layer word of every collider of the last build, by combined index, and per node the OR of the words of
 	// the leaves below it (2 n - 1 words by node id, the layer pass writes them); both are only meaningful while layers_set
 	uint32_t layer_capacity;     // colliders the two arrays have room for

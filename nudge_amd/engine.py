@@ -52,6 +52,7 @@ EXPORTS = [
     "nh_contact_pairs", "nh_contact_events", "nh_step_contact_pairs",
     "nh_sense", "nh_sense_rays",
     "nh_impulse_sums", "nh_body_impulses", "nh_blast_impulses", "nh_touch_impulses",
+    "nh_sweep", "nh_sweep_limit",
 ]
 HALO_RECORD_BYTES = 64
 
@@ -256,6 +257,19 @@ class ImpulseSum(C.Structure):
 class ImpulseSumList(C.Structure):
     """nh_ImpulseSumList: a host struct of device pointers."""
     _fields_ = [("count", C.c_void_p), ("sums", C.c_void_p), ("capacity", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+# fast bodies (include/nudge_hip.h, "fast bodies"): the colliders that travel far, swept along their velocity
+SWEEP_CHANNELS = ("colliders", "casts", "hits")
+
+
+class SweepParams(C.Structure):
+    _fields_ = [("time_step", C.c_float), ("min_travel", C.c_float), ("core", C.c_float), ("reserved", C.c_uint32)]
+
+
+class SweepList(C.Structure):
+    """nh_SweepList: a host struct of device pointers."""
+    _fields_ = [("counts", C.c_void_p), ("colliders", C.c_void_p), ("casts", C.c_void_p), ("hits", C.c_void_p), ("capacity", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class Blast(C.Structure):
@@ -498,6 +512,10 @@ def lib():
             L.nh_body_impulses.argtypes = [C.c_void_p, C.POINTER(BodyData), C.c_void_p, C.c_uint32]
             L.nh_blast_impulses.argtypes = [C.c_void_p, C.POINTER(BodyData), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]
             L.nh_touch_impulses.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+        # (likewise the fast bodies: World.sweep_records / sweep_limit_records / sweep then raise AttributeError)
+        if hasattr(L, "nh_sweep"):
+            L.nh_sweep.argtypes = [C.c_void_p, C.POINTER(BodyData), C.POINTER(SweepParams), C.POINTER(SweepList), C.c_uint32]
+            L.nh_sweep_limit.argtypes = [C.c_void_p, C.POINTER(BodyData), C.POINTER(SweepList), C.c_void_p, C.c_uint32]
         _LIB = L
     return _LIB
 
@@ -1933,6 +1951,68 @@ class World:
         body_offsets, _ = self.overlap_bodies_records(n, (offsets, hits, cap), hits=per_body, capacity=cap)
         out = self.blast_impulses_records(b, n, (body_offsets, per_body, cap))
         self.body_impulses_records(out, capacity=cap, wake=wake)
+        return out
+
+    # ---- fast bodies: sweep what travels far along its velocity, stop it at the hit (include/nudge_hip.h, "fast bodies") ----
+    def _sweep_list(self, lst):
+        cap = lst["capacity"]
+        return SweepList(lst["counts"].data_ptr(), *[lst[c].data_ptr() if lst.get(c) is not None and cap else 0 for c in SWEEP_CHANNELS], cap, 0)
+
+    def sweep_records(self, time_step, min_travel=0.5, core=0.5, capacity=0, counts=None, colliders=None, casts=None, hits=None):
+        """nh_sweep against the last query_build() / query_refit().  `counts`: a device tensor of two int32 words, or None for a new one.  Each channel
+        is None (not asked for, costs nothing), True (a new tensor of `capacity` records) or a device tensor of at least that many to write into:
+        colliders int32, casts 64-byte records (E.BOX_CAST; a sphere's: E.CAPSULE_CAST), hits 32-byte E.RAY_HIT records.  Returns the list as a dict:
+        counts, the channels given, capacity -- what sweep_limit_records takes.  Enqueued; nothing waits (a tree larger than any before grows the
+        scratch)."""
+        torch = self.torch
+        new = dict(colliders=lambda: torch.empty(capacity, dtype=torch.int32, device=self.dev), casts=lambda: torch.empty((capacity, 64), dtype=torch.uint8, device=self.dev),
+                   hits=lambda: torch.empty((capacity, 32), dtype=torch.uint8, device=self.dev))
+        size = dict(colliders=4, casts=64, hits=32)
+        lst = dict(counts=torch.zeros(2, dtype=torch.int32, device=self.dev) if counts is None else counts, capacity=int(capacity))
+        for name, given in (("colliders", colliders), ("casts", casts), ("hits", hits)):
+            if given is None or given is False:
+                continue
+            lst[name] = new[name]() if given is True else given
+            if lst[name].numel() * lst[name].element_size() < capacity * size[name]:
+                raise ValueError(f"sweep_records: {name} holds {lst[name].numel() * lst[name].element_size()} bytes, capacity {capacity} needs {capacity * size[name]}")
+        sl, sp = self._sweep_list(lst), SweepParams(time_step, min_travel, core, 0)
+        _check(self.L, self.L.nh_sweep(self.ctx, C.byref(self.bodies), C.byref(sp), C.byref(sl), 0), "nh_sweep")
+        return lst
+
+    def sweep_limit_records(self, lst, factors=None):
+        """nh_sweep_limit on a list sweep_records filled with colliders and hits: every body's velocity scaled to where its earliest sweep hit.
+        `factors`: None, True (a new float32 tensor of the list's capacity) or a device tensor of at least that many.  Returns `factors`.  Enqueued."""
+        if factors is True:
+            factors = self.torch.empty(max(lst["capacity"], 1), dtype=self.torch.float32, device=self.dev)
+        if factors is not None and factors.numel() * factors.element_size() < 4 * lst["capacity"]:
+            raise ValueError(f"sweep_limit_records: factors holds {factors.numel() * factors.element_size()} bytes, capacity {lst['capacity']} needs {4 * lst['capacity']}")
+        sl = self._sweep_list(lst)
+        _check(self.L, self.L.nh_sweep_limit(self.ctx, C.byref(self.bodies), C.byref(sl), C.c_void_p(factors.data_ptr() if factors is not None else 0), 0), "nh_sweep_limit")
+        return factors
+
+    def sweep(self, time_step=None, min_travel=0.5, core=0.5, capacity=None, limit=False, synchronize=False):
+        """The tunnelling guard of one step: call after step() and query_refit().  Every collider whose body would carry it further than `min_travel`
+        times its smallest half extent in `time_step` (None: the world's) is swept, its inner `core` share, along that travel; limit=True then cuts
+        the velocity of every body whose sweep hits to where the earliest one hits.  capacity=None: room for every collider -- nothing waits.
+        Returns a dict of device tensors: counts (2,) int64 (selected boxes, selected spheres; above `capacity` together: nothing else was written),
+        colliders (capacity,) int64 combined indices, casts (capacity, 16) float32 words of the cast records, t (capacity,), normal (capacity, 3),
+        body / collider / shape / tag (capacity,) int64 of the hit records, `raw` the (capacity, 32) records, and with limit=True `factors`
+        (capacity,).  Only the first counts.sum() rows are written."""
+        torch = self.torch
+        cap = self.colliders.boxes.count + self.colliders.spheres.count if capacity is None else int(capacity)
+        dt = self.params["time_step"] if time_step is None else time_step
+        lst = self.sweep_records(dt, min_travel, core, capacity=cap, colliders=True, casts=True, hits=True) if cap else self.sweep_records(dt, min_travel, core)
+        out = dict(counts=lst["counts"].to(torch.int64) & 0xFFFFFFFF)
+        if cap:
+            raw = lst["hits"]
+            f, u = raw.view(torch.float32).reshape(cap, 8), raw.view(torch.int32).reshape(cap, 8).to(torch.int64) & 0xFFFFFFFF
+            out.update(colliders=lst["colliders"].to(torch.int64) & 0xFFFFFFFF, casts=lst["casts"].view(torch.float32).reshape(cap, 16), t=f[:, 0], normal=f[:, 1:4],
+                       body=u[:, 4], collider=u[:, 5], shape=u[:, 6], tag=u[:, 7], raw=raw)
+        if limit:
+            factors = self.sweep_limit_records(lst, factors=True)
+            out["factors"] = factors[:cap]
+        if synchronize:
+            torch.cuda.current_stream(self.dev).synchronize()
         return out
 
     # ---- measurement ----
