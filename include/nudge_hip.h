@@ -83,6 +83,8 @@
  *      full one, and they do not count -- see "scene queries" below.
  *      nh_body_impulses and nh_sweep_limit WRITE momentum from outside the step: they complete pending work first and, without NH_IMPULSE_WAKE, leave speculation to
  *      the checks above -- see "body impulses" and "fast bodies" below.
+ *      nh_joints_setup and nh_joints_apply ARE entry points of the step in this sense: they complete pending work, and a pending still step becomes a full one
+ *      first -- see "joints" below.  nh_joints_prepare and nh_joint_connections touch nothing of the step.
  *
  * Threading: one context = one HIP stream = one world at a time; no global mutable state.
  */
@@ -1255,6 +1257,98 @@ typedef struct nh_SweepList {
 } nh_SweepList;
 int nh_sweep(nh_context* ctx, const nh_BodyData* bodies, const nh_SweepParams* params, const nh_SweepList* list, uint32_t flags /* 0 */);
 int nh_sweep_limit(nh_context* ctx, const nh_BodyData* bodies, const nh_SweepList* list, float* factors /* device floats, capacity, or NULL */, uint32_t flags /* 0 */);
+
+/* ---- joints: ball, distance and hinge joints solved on the device -------------------------------------------------------------------------------------
+   The reference has no joints; its sample says where a caller's own constraints go: "for (i < iterations) { nudge::apply_impulses(...); NOTE: Custom
+   constraint impulses should be applied here. }" (example/main.cpp:313-317).  On a device-resident world that loop cannot be the caller's without a download and
+   an upload of the momentum per iteration, so the library offers it: a door on a hinge, a rope bridge, a crate on a chain, a ragdoll, a trailer on a hitch.
+   All four calls are opt-in; they slot between the calls of the call-by-call ABI and no other call changes a byte:
+       nh_joints_prepare, nh_joint_connections                         -- when the list changes (the topology is the caller's and static)
+       nh_collide (the connections among its body_connections), nh_apply_gravity_damping, nh_read_cached_impulses, nh_setup_contact_constraints,
+       nh_joints_setup, iterations x { nh_apply_impulses(1), nh_joints_apply(1) }, nh_update_cached_impulses, nh_write_cached_impulses, nh_advance
+   Under NH_FLAG_SINGLE_APPLY or NH_FLAG_FUSED_STEP there is one contact apply per step: joints can only FOLLOW it (nh_apply_impulses(iterations), then
+   nh_joints_apply(iterations)) -- and under NH_FLAG_FUSED_STEP the bodies that solver owns have then been advanced already.  Use neither flag for jointed worlds.
+   RECORDS (device memory, 16-byte aligned).  nh_Joint: two bodies, a type, flags (0), one body-local anchor per body, six parameters p -- DISTANCE: p[0] =
+   min_length, p[1] = max_length, the rest 0; HINGE: p[0..2] = axis_a, p[3..5] = axis_b, body-local unit vectors that the library does not normalise; BALL: all
+   0.  For body 0, the static world, transforms[0] is read like any other transform; its velocity counts as zero and its momentum is never read or written.
+   nh_JointImpulse: the accumulated impulse per row, caller-owned and persistent like the contact cache; the caller zeroes it once.
+   A joint is VALID iff its type is known, flags == 0, a != b, a and b < bodies->count and, for DISTANCE, 0 <= min <= max (comparisons: a NaN is invalid).  An
+   invalid joint does nothing anywhere and has level 0.
+   THE SCHEDULE: THE CALLER'S LIST ORDER, REPLAYED IN PARALLEL.  nh_joints_setup and every sweep of nh_joints_apply give the bytes of the serial loop "for each
+   joint in list order, for each row in row order".  That order is the specification and what the host oracle runs (tests/hostoracle/hostjoint.cpp).  The device gets
+   there through dependency LEVELS: level(j) = 1 + max(level of the last earlier valid joint of the same BIN that names j's dynamic body a, the same for b); a
+   joint without such a predecessor has level 1, body 0 creates no dependency.  Joints of one level share no dynamic body, so any execution that finishes level L
+   before level L + 1 is the serial loop.  The caller controls the depth: a rope listed link by link has as many levels as links; listed even links first, odd
+   links second, it has two.
+   nh_JointList.offsets (assemblies + 1 device words, or NULL: the list is one assembly) are permitted CUT POINTS: the caller promises that no dynamic body is named
+   on both sides of one.  BIN w holds the assemblies i with offsets[i] / NH_JOINT_BIN == w; their joints are one contiguous span.  An assembly holds at most
+   NH_JOINT_ASSEMBLY_MAX joints, a span therefore at most 1279.  One workgroup owns one bin (it finds its span by two binary searches in `offsets`); levels restart at 1
+   per bin.  A body shared by two assemblies of the SAME bin is scheduled correctly by the level rule and is no error.
+   nh_joints_prepare(ctx, bodies_count, list, plan) -- when the list changes, not per step.  Writes levels[j]; order[]: every span's joint indices sorted by
+   (level, index), level-0 joints first; status[0]: NH_JOINT_ERR_OFFSETS (offsets[0] != 0, offsets[assemblies] != count or offsets[i + 1] < offsets[i]),
+   NH_JOINT_ERR_ASSEMBLY_SIZE (an ascending pair more than NH_JOINT_ASSEMBLY_MAX apart; a list without offsets: count above it), NH_JOINT_ERR_SHARED_BODY (a dynamic
+   body named by valid joints of two different bins; not looked for under NH_JOINT_ERR_OFFSETS); status[1]: valid joints; status[2]: the highest level; status[3]:
+   bins with at least one joint.  With status[0] != 0: levels[j] = 0, order[j] = j, status[2] = status[3] = 0.  The owner check is one word per body, cleared per
+   call: a min over bin numbers sets it, a second pass compares -- the bits are a function of the input alone.  count == 0 writes four zero status words.
+   nh_joints_setup and nh_joints_apply read status[0] ON THE DEVICE and do nothing when it is non-zero.
+   THE ARITHMETIC (nudge_amd/csrc/nh_joint.h states it once; fp32, only + - * /, sqrtf and compares, no contraction: the library is built with
+   -ffp-contract=off; dot products and 3x3 products associate left to right, (x + y) + z; rotate, cross, dot, the world inverse inertia W and the tangent pair are
+   the solver's own).  Per joint: r_x = rotate(q_x, anchor_x); d = (p_b + r_b) - (p_a + r_a); mi_x = mass_inverse, W_x = W(q_x, inertia_inverse) -- body 0: mi = 0,
+   W = 0.  A ROW has a linear direction n (or none), ja and jb (linear: ja = -(r_a x n), jb = r_b x n; angular: ja = -t, jb = t), k = [(mi_a + mi_b), linear rows
+   only] + ja . (W_a ja) + jb . (W_b jb), m = k > 0 ? 1 / k : 0, bias = clamp(beta * C, -max_bias, max_bias) with beta = time_step > 0 ? baumgarte / time_step : 0,
+   and bounds [lo, hi].
+     BALL      three rows: n = e_x, e_y, e_z; C = d.x, d.y, d.z; unbounded.
+     DISTANCE  one row: len = sqrtf(d . d), n = len > 0 ? d / len : (0, 1, 0).  min == max: C = len - min, unbounded (a rod); len > max: C = len - max, [-inf, 0];
+               len < min: C = len - min, [0, +inf]; otherwise the row is DEAD: m = 0, bias = 0, and its accumulated impulse is forced to +0.
+     HINGE     BALL's three rows, then two angular ones: a1 = rotate(q_a, axis_a), a2 = rotate(q_b, axis_b), (t1, t2) = the solver's tangents of a1,
+               C_k = (a1 x a2) . t_k, unbounded.
+   ONE VISIT of a row: jv = n . (v_b - v_a) + ja . w_a + jb . w_b; lambda = -(jv + bias) * m; acc' = clamp(acc + lambda, lo, hi); delta = acc' - acc;
+   v_a -= n * (delta * mi_a); w_a += (W_a ja) * delta; v_b += n * (delta * mi_b); w_b += (W_b jb) * delta.  unused0 and unused1 of nh_BodyMomentum keep their bits
+   (the reference's setup stashes mass_inverse in unused0, nudge.cpp:4182-4199).
+   nh_joints_setup(ctx, active_bodies, bodies, list, plan, params, impulses) -- after nh_setup_contact_constraints.  It completes pending work and is an entry
+   point of the step in note 9's sense.  A joint is LIVE this step iff it is valid and one of its dynamic bodies is on this step's active list (the list and its
+   device-side count as nh_apply_gravity_damping reads them; one flag byte per body in context scratch).  Per live joint, in schedule order: the rows are built
+   into the context's solve records, acc_k = warm * impulses[j].row[k] (a dead row: +0), and every acc_k is applied as a delta.  A joint that is not live writes
+   nothing, and its nh_JointImpulse keeps its bytes.
+   nh_joints_apply(ctx, bodies, list, plan, impulses, iterations) -- `iterations` sweeps in ONE launch: the bin's workgroup walks the levels with a workgroup
+   barrier between them, lanes take the joints of a level and move the two bodies' 32-byte momentum records with 16-byte accesses; after the last sweep the
+   lane stores impulses[j] whole (rows the type does not have: +0; reserved: 0).  It completes pending work first.  NH_ERR_STALE_SETUP without an nh_joints_setup
+   of a list of this count since the last nh_collide or nh_joints_prepare.
+   nh_joint_connections(ctx, list, out) -- (a, b) per valid joint, (0, 0) per invalid one (valid by the bodies_count of the last nh_joints_prepare, which must
+   have been called: NH_ERR_INVALID otherwise); nh_collide skips connections with a zero.  Passed as nh_BodyConnections, an assembly sleeps and wakes as one set.
+   All calls return NH_ERR_INVALID, before any launch and writing nothing: for a NULL ctx, list, plan, bodies, active_bodies, params, impulses, out or plan array;
+   for joints NULL with count > 0; for joints / impulses not 16-byte, out not 8-byte, offsets / status / levels / order not 4-byte aligned; for count or assemblies
+   >= 2^31; for plan->capacity < count; for NULL body arrays with bodies->count > 0; for a time_step, baumgarte, max_bias or warm that is not finite or is
+   negative, or warm > 1; for iterations == 0.  count == 0: setup and apply complete pending work and do nothing else.
+   SCRATCH is the context's: 432 B of solve record per joint of the largest count seen, and per body of the largest bodies->count one owner word and one flag byte.
+   It grows behind a stream synchronise; nh_destroy frees it.  Everything else is enqueued on the context's stream; nothing waits for a count.
+   Timing labels: j_owner (clear, offsets check, owner min, owner compare), j_levels, j_setup (flag bytes and setup), j_sweep, j_connections.
+   MEASURED: NOT MEASURED YET (tools/joints.py -> profiles/joint_rates.log has not been run at size on a GPU; no bar is set in advance).
+   Not built: weld joints; hinge limits and motors; springs; block (3x3) solves; assemblies over 1024 joints; joints inside nh_step and still steps; partitioned
+   worlds; the `namespace nudge` extension. */
+enum { NH_JOINT_BALL = 1u, NH_JOINT_DISTANCE = 2u, NH_JOINT_HINGE = 3u };
+#define NH_JOINT_BIN 256u
+#define NH_JOINT_ASSEMBLY_MAX 1024u
+enum { NH_JOINT_ERR_ASSEMBLY_SIZE = 1u, NH_JOINT_ERR_SHARED_BODY = 2u, NH_JOINT_ERR_OFFSETS = 4u };          /* bits of plan->status[0] */
+typedef struct nh_Joint { uint32_t a, b, type, flags /* 0 */; float anchor_a[3], anchor_b[3]; float p[6]; } nh_Joint;          /* 64 B */
+typedef struct nh_JointImpulse { float row[6]; uint32_t reserved[2]; } nh_JointImpulse;                                       /* 32 B */
+typedef struct nh_JointParams { float time_step, baumgarte, max_bias, warm; } nh_JointParams;                                 /* 16 B */
+typedef struct nh_JointList {        /* host struct, DEVICE pointers; host counts */
+	const nh_Joint* joints;
+	const uint32_t* offsets;         /* assemblies + 1 device words, or NULL */
+	uint32_t count, assemblies;
+} nh_JointList;
+typedef struct nh_JointPlan {        /* host struct, DEVICE pointers */
+	uint32_t* status;                /* 4 words */
+	uint32_t* levels;                /* capacity words */
+	uint32_t* order;                 /* capacity words */
+	uint32_t capacity, reserved;
+} nh_JointPlan;
+int nh_joints_prepare(nh_context* ctx, uint32_t bodies_count, const nh_JointList* list, const nh_JointPlan* plan);
+int nh_joints_setup(nh_context* ctx, const nh_ActiveBodies* active_bodies, const nh_BodyData* bodies, const nh_JointList* list, const nh_JointPlan* plan,
+                    const nh_JointParams* params, const nh_JointImpulse* impulses);
+int nh_joints_apply(nh_context* ctx, const nh_BodyData* bodies, const nh_JointList* list, const nh_JointPlan* plan, nh_JointImpulse* impulses, uint32_t iterations);
+int nh_joint_connections(nh_context* ctx, const nh_JointList* list, nh_BodyPair* out);
 
 /* nh_distance: how far each of `count` query shapes is from the world of the LAST nh_query_build or nh_query_refit, and towards what -- the clearance
    of a crate, a hull or a limb.  nh_penetration describes a pair that overlaps; this describes the pairs that do not.

@@ -105,6 +105,7 @@ extern "C" void nh_destroy(nh_context* ctx) {
 	nh_query_free(ctx);
 	nh_contact_events_free(ctx);
 	nh_impulses_free(ctx);
+	nh_joints_free(ctx);
 	{
 		void* bufs[] = { ctx->asleep.aabb_min, ctx->asleep.aabb_max, ctx->asleep.tags, ctx->hint, ctx->deg, ctx->fat_pairs, ctx->fat_box, ctx->grid_sbox, ctx->grid_skeys, ctx->grid_cstart, ctx->grid_counts, ctx->grid_large, ctx->fat_gen,
 		                 ctx->fat_esc_mark, ctx->fat_esc_list, ctx->fat_moved_list, ctx->sort_keys_by_position, ctx->sort_sorted_keys, ctx->sort_sorted_idx, ctx->sort_splitters, ctx->sort_counts, ctx->sort_starts,

@@ -475,7 +475,9 @@ struct nh_context {
 	struct nh_QueryState* query;   // scene queries (nh_query_tree.h): the hierarchy of the last nh_query_build; nullptr until the first
 	struct nh_CpState* contact_events;   // contact events (nh_contact_events.hip): the scratch of nh_contact_pairs / nh_contact_events; nullptr until the first call
 	struct nh_ImpulseState* impulses;    // body impulses (nh_impulse.hip): the scratch of nh_impulse_sums / nh_body_impulses; nullptr until the first call
+	struct nh_JointState* joints;        // joints (nh_joints.hip): solve records, owner words, flag bytes, and which setup they belong to; nullptr until the first call
 };
+void nh_joints_free(nh_context* ctx);                  // nh_destroy -> the joints' scratch (nh_joints.hip)
 int nh_stream_after_advance(nh_context* ctx);          // nh_advance -> state streaming (nh_context.hip)
 void nh_query_free(nh_context* ctx);                   // nh_destroy -> the scene query's buffers (nh_query_build.hip)
 void nh_contact_events_free(nh_context* ctx);          // nh_destroy -> the contact events' scratch (nh_contact_events.hip)

@@ -53,6 +53,7 @@ EXPORTS = [
     "nh_sense", "nh_sense_rays",
     "nh_impulse_sums", "nh_body_impulses", "nh_blast_impulses", "nh_touch_impulses",
     "nh_sweep", "nh_sweep_limit",
+    "nh_joints_prepare", "nh_joints_setup", "nh_joints_apply", "nh_joint_connections",
 ]
 HALO_RECORD_BYTES = 64
 
@@ -270,6 +271,37 @@ class SweepParams(C.Structure):
 class SweepList(C.Structure):
     """nh_SweepList: a host struct of device pointers."""
     _fields_ = [("counts", C.c_void_p), ("colliders", C.c_void_p), ("casts", C.c_void_p), ("hits", C.c_void_p), ("capacity", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+# joints (include/nudge_hip.h, "joints"): ball, distance and hinge joints between the calls of the step
+NH_JOINT_BALL, NH_JOINT_DISTANCE, NH_JOINT_HINGE = 1, 2, 3
+NH_JOINT_BIN, NH_JOINT_ASSEMBLY_MAX = 256, 1024
+NH_JOINT_ERR_ASSEMBLY_SIZE, NH_JOINT_ERR_SHARED_BODY, NH_JOINT_ERR_OFFSETS = 1, 2, 4
+JOINT = np.dtype([("a", "<u4"), ("b", "<u4"), ("type", "<u4"), ("flags", "<u4"), ("anchor_a", "<f4", 3), ("anchor_b", "<f4", 3), ("p", "<f4", 6)])
+JOINT_IMPULSE = np.dtype([("row", "<f4", 6), ("reserved", "<u4", 2)])
+
+
+class Joint(C.Structure):
+    _fields_ = [("a", C.c_uint32), ("b", C.c_uint32), ("type", C.c_uint32), ("flags", C.c_uint32), ("anchor_a", C.c_float * 3), ("anchor_b", C.c_float * 3),
+                ("p", C.c_float * 6)]
+
+
+class JointImpulse(C.Structure):
+    _fields_ = [("row", C.c_float * 6), ("reserved", C.c_uint32 * 2)]
+
+
+class JointParams(C.Structure):
+    _fields_ = [("time_step", C.c_float), ("baumgarte", C.c_float), ("max_bias", C.c_float), ("warm", C.c_float)]
+
+
+class JointList(C.Structure):
+    """nh_JointList: a host struct of device pointers and host counts."""
+    _fields_ = [("joints", C.c_void_p), ("offsets", C.c_void_p), ("count", C.c_uint32), ("assemblies", C.c_uint32)]
+
+
+class JointPlan(C.Structure):
+    """nh_JointPlan: a host struct of device pointers."""
+    _fields_ = [("status", C.c_void_p), ("levels", C.c_void_p), ("order", C.c_void_p), ("capacity", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class Blast(C.Structure):
@@ -516,6 +548,12 @@ def lib():
         if hasattr(L, "nh_sweep"):
             L.nh_sweep.argtypes = [C.c_void_p, C.POINTER(BodyData), C.POINTER(SweepParams), C.POINTER(SweepList), C.c_uint32]
             L.nh_sweep_limit.argtypes = [C.c_void_p, C.POINTER(BodyData), C.POINTER(SweepList), C.c_void_p, C.c_uint32]
+        # (likewise the joints: World.joints_* then raise AttributeError)
+        if hasattr(L, "nh_joints_prepare"):
+            L.nh_joints_prepare.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(JointList), C.POINTER(JointPlan)]
+            L.nh_joints_setup.argtypes = [C.c_void_p, C.POINTER(ActiveBodies), C.POINTER(BodyData), C.POINTER(JointList), C.POINTER(JointPlan), C.POINTER(JointParams), C.c_void_p]
+            L.nh_joints_apply.argtypes = [C.c_void_p, C.POINTER(BodyData), C.POINTER(JointList), C.POINTER(JointPlan), C.c_void_p, C.c_uint32]
+            L.nh_joint_connections.argtypes = [C.c_void_p, C.POINTER(JointList), C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -2014,6 +2052,83 @@ class World:
         if synchronize:
             torch.cuda.current_stream(self.dev).synchronize()
         return out
+
+    # ---- joints: ball, distance and hinge joints between the calls of the step (include/nudge_hip.h, "joints") ----
+    def joints_prepare(self, joints, offsets=None, connect=True, baumgarte=0.2, max_bias=4.0, warm=1.0):
+        """nh_joints_prepare for a list of E.JOINT records (numpy) and, optionally, its cut points (`offsets`: assemblies + 1 ascending words from 0 to
+        len(joints)); call it when the list changes, not per step.  Uploads the list, zeroes the accumulated impulses (E.JOINT_IMPULSE, kept on the
+        device in self.joint_impulses), keeps the plan, and with connect=True installs the joints' body pairs behind the scene's own connections
+        (nh_joint_connections), so that an assembly sleeps and wakes as one set.  `baumgarte`, `max_bias`, `warm`: what joints_setup passes as
+        nh_JointParams beside the world's time step.  Enqueued; joint_status() reads the four status words."""
+        torch = self.torch
+        j = np.ascontiguousarray(joints, dtype=JOINT).reshape(-1)
+        n = len(j)
+
+        def up(a, dtype, min_bytes=16):
+            raw = np.ascontiguousarray(a, dtype=dtype).view(np.uint8).reshape(-1)
+            t = torch.zeros(max(raw.size, min_bytes), dtype=torch.uint8, device=self.dev)
+            if raw.size:
+                t[:raw.size] = torch.from_numpy(raw.copy()).to(self.dev)
+            return t
+
+        jt = dict(joints=up(j, JOINT), n=n, impulses=torch.zeros(max(32 * n, 32), dtype=torch.uint8, device=self.dev),
+                  status=torch.zeros(4, dtype=torch.int32, device=self.dev), levels=torch.zeros(max(n, 1), dtype=torch.int32, device=self.dev),
+                  order=torch.zeros(max(n, 1), dtype=torch.int32, device=self.dev), offsets=None, assemblies=0)
+        if offsets is not None:
+            off = np.ascontiguousarray(offsets, dtype=np.uint32).reshape(-1)
+            jt["offsets"], jt["assemblies"] = up(off, np.uint32), len(off) - 1
+        jt["list"] = JointList(jt["joints"].data_ptr(), jt["offsets"].data_ptr() if jt["offsets"] is not None else 0, n, jt["assemblies"])
+        jt["plan"] = JointPlan(jt["status"].data_ptr(), jt["levels"].data_ptr(), jt["order"].data_ptr(), n, 0)
+        jt["params"] = dict(baumgarte=baumgarte, max_bias=max_bias, warm=warm)
+        _check(self.L, self.L.nh_joints_prepare(self.ctx, self.bodies.count, C.byref(jt["list"]), C.byref(jt["plan"])), "nh_joints_prepare")
+        self._joints = jt
+        self.joint_impulses = jt["impulses"]
+        if connect:
+            base = self._keep.setdefault("cn_scene", self._keep["cn"])
+            nbase = self._scene_connections = getattr(self, "_scene_connections", self.connections.count)
+            con = torch.zeros(max(8 * (nbase + n), 16), dtype=torch.uint8, device=self.dev)
+            con[:8 * nbase] = base[:8 * nbase]
+            _check(self.L, self.L.nh_joint_connections(self.ctx, C.byref(jt["list"]), C.c_void_p(con.data_ptr() + 8 * nbase)), "nh_joint_connections")
+            self._keep["cn"] = con
+            self.connections = BodyConnections(con.data_ptr(), nbase + n)
+
+    def joint_status(self):
+        """(error bits, valid joints, highest level, non-empty bins) of the last joints_prepare; waits for the stream."""
+        return tuple(int(x) & 0xFFFFFFFF for x in self._joints["status"].cpu().tolist())
+
+    def joints_setup(self, time_step=None, baumgarte=None, max_bias=None, warm=None):
+        """nh_joints_setup: after setup(), before the first apply().  Parameters default to joints_prepare's and the world's time step."""
+        jt = self._joints
+        p = jt["params"]
+        jp = JointParams(self.params["time_step"] if time_step is None else time_step, p["baumgarte"] if baumgarte is None else baumgarte,
+                         p["max_bias"] if max_bias is None else max_bias, p["warm"] if warm is None else warm)
+        _check(self.L, self.L.nh_joints_setup(self.ctx, C.byref(self.active), C.byref(self.bodies), C.byref(jt["list"]), C.byref(jt["plan"]), C.byref(jp),
+                                              C.c_void_p(jt["impulses"].data_ptr())), "nh_joints_setup")
+
+    def joints_apply(self, iterations=1):
+        """nh_joints_apply: `iterations` sweeps over the joints in one launch."""
+        jt = self._joints
+        _check(self.L, self.L.nh_joints_apply(self.ctx, C.byref(self.bodies), C.byref(jt["list"]), C.byref(jt["plan"]), C.c_void_p(jt["impulses"].data_ptr()),
+                                              iterations), "nh_joints_apply")
+
+    def step_joints(self, steps=1, iterations=None):
+        """`steps` sub-steps of a jointed world through the call-by-call ABI: the eight calls of step()'s loop with joints_setup() behind setup() and
+        apply(1), joints_apply(1) per iteration -- where the sample says custom constraint impulses go (example/main.cpp:313-317).  Not for worlds
+        created with NH_FLAG_SINGLE_APPLY or NH_FLAG_FUSED_STEP (one contact apply per step)."""
+        it = self.params["iterations"] if iterations is None else iterations
+        for _ in range(steps):
+            self.collide()
+            self.gravity()
+            self.read_cache()
+            self.setup()
+            self.joints_setup()
+            for _i in range(it):
+                self.apply(1)
+                self.joints_apply(1)
+            self.update()
+            self.write_cache()
+            self.advance()
+            self.step_done()
 
     # ---- measurement ----
     def enable_timing(self, on=True, only=None):
